@@ -35,6 +35,11 @@ checkpoints offline).  Recall@10 is measured, untimed, on >= 8192 distinct queri
 exact ranking of the UNQUANTISED fp32 rows (fp64 accumulation), not against the quantised slab; the line carries the sample
 size, the certified fraction and the number of escalated queries.  --through-pipeline times the plugin surface instead
 (texts -> RAGPipeline.retrieve_batch -> lists of dicts).
+
+A plain run sets up, warms up, times --steps steps and prints the line (recall, check_ok, roofline and cpu_baseline null).
+--full adds everything else the line reports: the recall / exactness check (exit status 1 when it fails), the other refine
+mode, the roofline's own kernel timings and the CPU baseline.  --dump-outputs DIR writes the lists the last timed step
+returned (DIR/scores.npy, ids.npy, status.npy; the enc-* workloads: embeddings.npy) in float32 / float64.
 """
 from __future__ import annotations
 
@@ -113,6 +118,24 @@ def recall_rows(got_i, ref_i):
     return hits.any(dim=1).float().sum(1) / (ref_i >= 0).float().sum(1).clamp(min=1)
 
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array (float32 / float64 only; at most 64 MB in all)."""
+    import numpy as np
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def dump_lists(path, torch, scores, ids, status):
+    """The final top-k lists of the timed path: scores fp32, ids fp64 (exact below 2^53; -1 = empty), certificate status."""
+    arrays = {"scores": scores.float().cpu().numpy(), "ids": ids.to(torch.float64).cpu().numpy()}
+    if status is not None:
+        arrays["status"] = status.float().cpu().numpy()
+    dump_outputs(path, arrays)
+
+
 def bench_encoder(args, torch, nat, dev, rank, world, dist):
     """--workload enc-*: the index-build side of the path (EmbeddingModel.embed_chunks, reference
     rag/embedding.py:75-87): full-length synthetic chunks through the encoder, tokens/s and MFMA fraction."""
@@ -158,6 +181,8 @@ def bench_encoder(args, torch, nat, dev, rank, world, dist):
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"embeddings": torch.cat(outs).cpu().numpy()})
     batch *= nfl
     tokens = batch * seq
     h, f, nl = shape.hidden, shape.ffn, shape.layers
@@ -232,6 +257,12 @@ def bench_pipeline(args, torch, nat, dev):
             t0 = time.perf_counter()
             out = p.retrieve_batch(queries)
             lat.append(time.perf_counter() - t0)
+        if args.dump_outputs and not results:       # the headline config's last timed call: score and row of every hit
+            sc, ids = np.full((n_q, k), np.nan), np.full((n_q, k), -1.0)
+            for r_, hits_ in enumerate(out):
+                for j_, h_ in enumerate(hits_[:k]):
+                    sc[r_, j_], ids[r_, j_] = h_["score"], float(h_["chunk_id"].rsplit("_", 1)[1])
+            dump_outputs(args.dump_outputs, {"scores": sc, "ids": ids})
         # the same queries one at a time through the unchanged per-query entry (what the reference's loop does)
         t0 = time.perf_counter()
         for q in queries[:64]:
@@ -314,6 +345,11 @@ def main():
     ap.add_argument("--proxy-encode-shard", type=int, default=0,
                     help="diagnostic, N = 1: encode only Qb / W queries per batch and tile them W times in place of the all-gather "
                          "(what one rank of a W-GPU step with --encode sharded executes, minus the collectives)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the recall / exactness check (exit 1 on failure), the other refine mode, "
+                         "the roofline's kernel timings and the CPU baseline (a plain run reports them as null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
 
     import numpy as np
@@ -479,6 +515,41 @@ def main():
     ms_step = dt / args.steps * 1e3
     qps = q_per_step * args.steps / dt
     timed_status = torch.stack([eng.outputs(i)[2] for i in range(n_ctx)]).clone()     # certificate outcome of the in-flight batches
+    if args.dump_outputs and rank == 0:
+        outs = [eng.outputs(i) for i in range(n_ctx)]
+        dump_lists(args.dump_outputs, torch, torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs]), timed_status.flatten())
+
+    def result_line(recall_report=None, check_ok=None, roofline=None, cpu=None):
+        return {
+            "metric": "queries/sec over N-vector corpus (exact cosine top-k; Recall@10 vs the exact fp32 ranking)",
+            "value": round(qps, 1), "unit": "queries/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(ms_step, 5), "higher_is_better": True,
+            "scaling": args.scaling, "vs_baseline": None,
+            "dtype": "f16 x f16 -> f32" if slab_type == nat.SLAB_F16 else "i8 x i16(f16 query) -> i32 -> f32",
+            "data": "synthetic",
+            "config": {"workload": args.workload, "corpus_rows": corpus_rows, "rows_per_gpu": rows, "dim": dim,
+                       "queries_per_batch": nq_all, "batches_per_step": n_ctx, "queries_per_step": q_per_step,
+                       "distinct_queries_in_flight": q_per_step,
+                       "ms_per_batch": round(ms_step / n_ctx, 5), "lanes": eng.describe_lanes(), "batches_per_encoder_forward": eng.enc_group, "searches_per_graph": eng.search_fuse, "top_k": k, "k_scan": k_scan,
+                       "slab": slab_kind, "refine_fp32": refine, "exact_escalation": bool(eng.exact), "encoder_in_step": not args.scan_only,
+                       "engine": "rag._engine.RetrievalEngine (the object ContextRetriever.retrieve_batch drives)",
+                       "encoder": ("all-MiniLM-L6-v2" if enc_name == "minilm" else "bge-base-en-v1.5") + " shape, seeded random weights",
+                       "query_tokens": QUERY_TOKENS, "hip_graph": eng.use_graph,
+                       "collectives_per_batch": eng.collectives_per_batch, "dist_single_rank": bool(multi and world == 1),
+                       "query_encode": ("replicated" if not gather_q else ("per-rank queries (weak scaling)" if not strong else
+                                        f"sharded: {q_loc} of {qb} queries per rank" + (" [single-GPU proxy: tiled instead of gathered]" if not multi else ""))),
+                       "recall_at_10_vs_fp32": recall_report, "check_ok": check_ok,
+                       "row_err_max_tracked": view.row_err_max,
+                       "index_build_s_per_gpu": round(t_build, 3)},
+            "roofline": roofline, "cpu_baseline": cpu,
+        }
+
+    if not args.full:               # a plain run: the headline figure only
+        if rank == 0:
+            print(json.dumps(result_line()), flush=True)
+        if multi:
+            dist.destroy_process_group()
+        return
 
     # ---- correctness of the timed path (untimed): EVERY query of the set through the same engine (same graphs, fresh token
     # ids per batch), final lists against the exact ranking of the UNQUANTISED fp32 rows of every shard (fp64 accumulation)
@@ -675,30 +746,7 @@ def main():
                "recall_at_10_gpu_vs_oracle_on_sample": recall_oracle, "max_abs_score_err_on_sample": max_err}
 
     if rank == 0:
-        line = {
-            "metric": "queries/sec over N-vector corpus (exact cosine top-k; Recall@10 vs the exact fp32 ranking)",
-            "value": round(qps, 1), "unit": "queries/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_step, 5), "higher_is_better": True,
-            "scaling": args.scaling, "vs_baseline": None,
-            "dtype": "f16 x f16 -> f32" if slab_type == nat.SLAB_F16 else "i8 x i16(f16 query) -> i32 -> f32",
-            "data": "synthetic",
-            "config": {"workload": args.workload, "corpus_rows": corpus_rows, "rows_per_gpu": rows, "dim": dim,
-                       "queries_per_batch": nq_all, "batches_per_step": n_ctx, "queries_per_step": q_per_step,
-                       "distinct_queries_in_flight": q_per_step,
-                       "ms_per_batch": round(ms_step / n_ctx, 5), "lanes": eng.describe_lanes(), "batches_per_encoder_forward": eng.enc_group, "searches_per_graph": eng.search_fuse, "top_k": k, "k_scan": k_scan,
-                       "slab": slab_kind, "refine_fp32": refine, "exact_escalation": bool(eng.exact), "encoder_in_step": not args.scan_only,
-                       "engine": "rag._engine.RetrievalEngine (the object ContextRetriever.retrieve_batch drives)",
-                       "encoder": ("all-MiniLM-L6-v2" if enc_name == "minilm" else "bge-base-en-v1.5") + " shape, seeded random weights",
-                       "query_tokens": QUERY_TOKENS, "hip_graph": eng.use_graph,
-                       "collectives_per_batch": eng.collectives_per_batch, "dist_single_rank": bool(multi and world == 1),
-                       "query_encode": ("replicated" if not gather_q else ("per-rank queries (weak scaling)" if not strong else
-                                        f"sharded: {q_loc} of {qb} queries per rank" + (" [single-GPU proxy: tiled instead of gathered]" if not multi else ""))),
-                       "recall_at_10_vs_fp32": recall_report, "check_ok": check_ok,
-                       "row_err_max_tracked": view.row_err_max,
-                       "index_build_s_per_gpu": round(t_build, 3)},
-            "roofline": roofline, "cpu_baseline": cpu,
-        }
-        print(json.dumps(line), flush=True)
+        print(json.dumps(result_line(recall_report, check_ok, roofline, cpu)), flush=True)
     if multi:
         ok_t = torch.tensor([1 if check_ok else 0], device=dev)
         dist.all_reduce(ok_t, op=dist.ReduceOp.MIN)

@@ -20,7 +20,7 @@ def _run(extra, port):
     env = dict(os.environ, CRS_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "4", "--warmup", "1", "--streams", "3", "--no-cpu-baseline"] + extra
+           "--gpus", "2", "--steps", "4", "--warmup", "1", "--streams", "3", "--full", "--no-cpu-baseline"] + extra
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -75,7 +75,7 @@ def _run_single_rccl(extra):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29541")
     env.pop("CRS_DIST_BACKEND", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--dist-single", "--steps", "4", "--warmup", "1", "--streams", "3",
-           "--no-cpu-baseline"] + extra
+           "--full", "--no-cpu-baseline"] + extra
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

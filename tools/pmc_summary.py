@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
-"""gpurun_out/<TAG>_* (tools/make_profiles.sh) -> profiles/<TAG>_{bench_*.json, *_kernel_stats.csv, pmc_summary.json}.
+"""$OUT/<TAG>_* (tools/make_profiles.sh; default profile_runs/) -> profiles/<TAG>_{bench_*.json, *_kernel_stats.csv, pmc_summary.json}.
 HBM bytes follow MI355X_MICROARCH.md (HBM section): FETCH_SIZE is reported in KiB and, on gfx950, at HALF the
 bytes of a wide coalesced streaming read -> read bytes = FETCH_SIZE * 1024 * 2; WRITE_SIZE is reported raw."""
 import csv, glob, json, os, re, shutil, sys, collections
 tag = sys.argv[1] if len(sys.argv) > 1 else "r01"
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-go, pr = os.path.join(root, "gpurun_out"), os.path.join(root, "profiles")
+go, pr = os.path.join(root, os.environ.get("OUT", "profile_runs")), os.path.join(root, "profiles")
 os.makedirs(pr, exist_ok=True)
 csv.field_size_limit(1 << 30)
 for w in ("c2", "c3", "c4", "c5", "enc-minilm", "enc-bge"):
@@ -14,7 +14,7 @@ for w in ("c2", "c3", "c4", "c5", "enc-minilm", "enc-bge"):
         shutil.copy(src, os.path.join(pr, f"{tag}_bench_{w}.json"))
 for w in ("c2", "c3", "c4", "c5", "enc-minilm", "enc-bge"):
     found = sorted(glob.glob(os.path.join(go, f"{tag}_stats_{w}", "**", "*kernel_stats.csv"), recursive=True), key=os.path.getmtime)
-    for f in found[-1:]:   # gpurun merges every call's files into gpurun_out/: keep the newest run only
+    for f in found[-1:]:   # runs accumulate in the output directory: keep the newest one only
         rows = list(csv.reader(open(f)))
         with open(os.path.join(pr, f"{tag}_{w.replace('-', '_')}_kernel_stats.csv"), "w", newline="") as fh:
             wr = csv.writer(fh)

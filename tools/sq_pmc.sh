@@ -7,13 +7,14 @@
 # THERMAL / CLOCK state a launch starts in, not concurrency.
 set -o pipefail
 TAG=${1:-r03}; W=${2:-c5}
-cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-mkdir -p gpurun_out
+cd "$(dirname "$0")/.."
+export OUT=${OUT:-profile_runs}
+mkdir -p $OUT
 i=0
 for set in "SQ_BUSY_CU_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_LDS" \
            "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INST_CYCLES_VMEM_RD SQ_ACTIVE_INST_VALU SQ_INSTS_MFMA SQ_WAVES"; do
   i=$((i+1))
-  rocprofv3 --pmc $set --kernel-trace --output-format csv -d gpurun_out/${TAG}_sq${i}_$W -- python3 bench.py --workload $W --steps 6 --warmup 1 --streams 1 --no-graph --no-cpu-baseline --recall-queries 64 > gpurun_out/${TAG}_sq${i}_$W.log 2>&1 || { tail -5 gpurun_out/${TAG}_sq${i}_$W.log; exit 1; }
+  rocprofv3 --pmc $set --kernel-trace --output-format csv -d $OUT/${TAG}_sq${i}_$W -- python3 bench.py --workload $W --steps 6 --warmup 1 --streams 1 --no-graph --full --no-cpu-baseline --recall-queries 64 > $OUT/${TAG}_sq${i}_$W.log 2>&1 || { tail -5 $OUT/${TAG}_sq${i}_$W.log; exit 1; }
 done
 python3 - $TAG $W <<'PY'
 import csv, glob, json, os, sys, collections
@@ -21,7 +22,7 @@ tag, w = sys.argv[1], sys.argv[2]
 csv.field_size_limit(1 << 30)
 acc = collections.defaultdict(lambda: collections.defaultdict(list))
 for i in (1, 2):
-    fs = sorted(glob.glob(f"gpurun_out/{tag}_sq{i}_{w}/**/*counter_collection.csv", recursive=True), key=os.path.getmtime)
+    fs = sorted(glob.glob(f"{os.environ['OUT']}/{tag}_sq{i}_{w}/**/*counter_collection.csv", recursive=True), key=os.path.getmtime)
     rows = list(csv.DictReader(open(fs[-1])))
     # one row per (dispatch, counter): order dispatches by start time, remember each dispatch's predecessor kernel
     disp = {}
@@ -36,7 +37,7 @@ for i in (1, 2):
         grp = "back_to_back" if prev[r["Dispatch_Id"]] == k else "in_mix"
         acc[(name, grp)][r["Counter_Name"]].append(float(r["Counter_Value"]))
         acc[(name, grp)].setdefault("_ns", []).append(float(r["End_Timestamp"]) - float(r["Start_Timestamp"]))
-out = {"_how": f"rocprofv3 --pmc <set> --kernel-trace -- python3 bench.py --workload {w} --steps 6 --warmup 1 --streams 1 --no-graph "
+out = {"_how": f"rocprofv3 --pmc <set> --kernel-trace -- python3 bench.py --workload {w} --steps 6 --warmup 1 --streams 1 --no-graph --full "
                "--no-cpu-baseline --recall-queries 64 (tools/sq_pmc.sh; two passes of six SQ counters); per-dispatch means over the scan kernel's "
                "launches, split by the dispatch that preceded them (back_to_back: the same scan kernel, i.e. the crs_time_cosine_topk loop; in_mix: "
                "another kernel, i.e. the step loop). Ratios: mfma_busy_per_simd = SQ_VALU_MFMA_BUSY_CYCLES / (4 x SQ_BUSY_CU_CYCLES); lds_active = "
@@ -54,6 +55,6 @@ for (name, grp), d in sorted(acc.items()):
     if m.get("SQ_WAVE_CYCLES"):
         e["wait_any"] = round(m.get("SQ_WAIT_ANY", 0) / m["SQ_WAVE_CYCLES"], 3)
     out[f"{name} [{grp}]"] = e
-json.dump(out, open(f"gpurun_out/{tag}_sq_{w}.json", "w"), indent=1)
+json.dump(out, open(f"{os.environ['OUT']}/{tag}_sq_{w}.json", "w"), indent=1)
 print(json.dumps(out, indent=1)[:4000])
 PY
