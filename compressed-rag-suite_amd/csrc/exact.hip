@@ -145,17 +145,23 @@ __global__ __launch_bounds__(256) void refine_cert_kernel(const float* __restric
     float dq = sqrtf(dd) * 1.0001f;
     if (is_i8) dq += sqrtf((float)pdim) * mx * (1.0001f / 65024.0f);
     const float eps = dq * (1.0f + err_rows) * 1.0001f + sqrtf(nn) * err_rows * 1.0002f + err_arith;
-    // t = the k'-th slab score; fewer than k' valid candidates = every row of the shard was fetched
-    int valid = 0;
+    // t = the k'-th slab score.  Proof without a bound only when the list holds every row of the shard (valid in-shard
+    // candidates >= n_rows); a -1 slot on a larger shard, or an id outside [id_base, id_base + n_rows), proves nothing
+    int valid = 0, outside = 0;
     float tmin = __builtin_huge_valf();
-    for (int c = 0; c < k_in; ++c) {   // (a candidate id outside this shard counts as fetched-but-unusable: never certifies)
-      if (cand[(size_t)qi * k_in + c] >= 0) { ++valid; tmin = fminf(tmin, cand_s[(size_t)qi * k_in + c]); }
+    for (int c = 0; c < k_in; ++c) {
+      const int64_t id = cand[(size_t)qi * k_in + c];
+      if (id < 0) continue;
+      if (id - id_base >= 0 && id - id_base < n_rows) { ++valid; tmin = fminf(tmin, cand_s[(size_t)qi * k_in + c]); }
+      else ++outside;
     }
     const float kth = kth_s;
-    int st = 0;
-    if (valid == k_in && (int64_t)k_in < n_rows) {
+    int st = 1;
+    if (outside == 0 && (int64_t)valid >= n_rows) {
+      st = 0;                            // every row of the shard is in the list
+    } else if (outside == 0 && valid == k_in) {
       const float bound = tmin + eps + 2e-5f * fabsf(tmin);
-      st = (kth > bound) ? 0 : 1;        // kth == -inf (fewer than k_out candidates, all rows fetched) cannot get here
+      st = (kth > bound) ? 0 : 1;        // (kth == -inf, fewer than k_out candidates, never passes)
     }
     status[qi] = st;
     ws_thr[qi] = kth - eps;

@@ -472,10 +472,12 @@ class RetrievalEngine:
         return f"{self.n_enc} encoder + {self.n_srch} search (encoder kernels <= 48 KB of LDS)"
 
     # ---- the product entry: many query batches through the pipeline -------------------------------------------------
-    def search_token_batches(self, batches):
+    def search_token_batches(self, batches, overflow_queries: bool = False):
         """batches: iterable of (ids int32 [m, seq], lens int32 [m]) host arrays with m <= queries per batch (a short last
         batch is padded with copies of its first query).  Yields, in order, (scores [m, k], rows [m, k], status [m]) numpy
-        arrays.  Up to n_ctx batches are in flight; results are read back as their buffer set comes round again."""
+        arrays.  Up to n_ctx batches are in flight; results are read back as their buffer set comes round again.
+        overflow_queries: yield a fourth item, the fp32 embeddings (numpy [j, dim]) of the batch's status-2 queries (escalation
+        list longer than exact_cap: the caller repeats them with a longer list), None when there are none."""
         import numpy as np
         if self.multi or self.gather_q:
             raise nat.NativeError("search_token_batches drives a single-rank engine")
@@ -487,7 +489,13 @@ class RetrievalEngine:
             self.wait(i)
             s, r, st = self.outputs(i)
             m = pending.pop(i)
-            return s[:m].cpu().numpy(), r[:m].cpu().numpy(), st[:m].cpu().numpy()
+            out = (s[:m].cpu().numpy(), r[:m].cpu().numpy(), st[:m].cpu().numpy())
+            if not overflow_queries:
+                return out
+            over = np.nonzero(out[2] == 2)[0]
+            # (read back now: the buffer set's next forward overwrites q_out from another stream)
+            q2 = self.ctxs[i].q_out[:m][self.torch.as_tensor(over, device=self.dev)].cpu().numpy() if over.size else None
+            return out + (q2,)
 
         G = self.enc_group
         nb = 0

@@ -249,11 +249,16 @@ def overfetch(nq: int, top_k: int, want: int = 24, n_rows: int = 1 << 62, slab_t
     allows: the large-batch kernels (scan_wide.hip) carry a 16-slot chain, and 32 candidates would send those launches to the
     64-query kernel once per query block.  int8 slabs: 16 -- their certificate is too wide to hold at either length
     (0.07 % / 34 % of C5's queries at 16 / 32), the empirical Recall@10 is 1.0 on 8192 queries at both, and the 32-slot chain makes the
-    issue-bound int8 kernel 6 % slower (C5 31.3 -> 33.5 k q/s)."""
+    issue-bound int8 kernel 6 % slower (C5 31.3 -> 33.5 k q/s).
+    Above top_k 10 the margin grows with top_k: k' >= ceil(1.6 top_k) (capped at MAX_K).  k' == top_k would leave the re-rank
+    nothing to re-rank and the certificate nothing to stand on: every query escalated on fp16, the slab's own order on int8.
+    1.6 is the ratio top_k 10 already runs at (16 / 10), so the lengths up to top_k 10 stay as above.  Measured on 1 M x 384
+    fp16 rows, 64 queries (half planted near a row): every query certified at k' = 1.4, 1.6, 2 and 2.4 x top_k for each
+    top_k from 10 to 40."""
     want = int(want)
     if n_rows < 4_000_000 or (nq > 64 and top_k <= 16) or slab_type == SLAB_I8:
         want = min(want, 16)
-    return min(MAX_K, max(int(top_k), want))
+    return min(MAX_K, max(int(top_k), want, -(-8 * int(top_k) // 5)))
 
 
 def exact_workspace_bytes(nq: int, cap: int = EXACT_CAP) -> int:

@@ -11,7 +11,8 @@ New, additive surface (all keys absent from the reference config.json default so
   ``search_batch``            many queries per launch
   ``index_dtype``             'fp16' (default) | 'int8' (per-row scale)
   ``refine_fp32``             (default ON) keep an fp32 shadow of the rows (4 x dim bytes per row beside the fp16 / int8
-                              slab), over-fetch ``refine_overfetch`` (24; 16 on shards below 4 M rows) candidates and re-rank them in fp32: the ranking an
+                              slab), over-fetch ``refine_overfetch`` (24; 16 on shards below 4 M rows; at least 1.6 x top_k
+                              above top_k 10: nat.overfetch) candidates and re-rank them in fp32: the ranking an
                               fp32 store such as the reference's returns (rag/indexing.py:114-119,171-176).  False = the
                               plain fp16 / int8 ranking, no shadow
   ``refine_exact``            'auto' (default) | True | False: every re-ranked list carries a per-query PROOF that it is the
@@ -22,6 +23,7 @@ New, additive surface (all keys absent from the reference config.json default so
                               bound (~1e-2 for 768-d rows) is wider than typical score gaps, so the certificate rarely
                               holds and escalating would cost a second sweep for most batches: int8 stays
                               EMPIRICAL (re-rank only) unless refine_exact=True.  ``last_exactness`` reports the counts
+                              of the last search and its mode (top_k > 64: re-rank without proof, counted unproven)
   ``num_gpus`` / ``devices``  ONE process driving N devices: contiguous row shards, per-device scans, partial lists
                               copied to the first device and merged there -- RAGPipeline stays one object
   ``sharded``                 SPMD (one process per GPU, torch.distributed): each rank keeps a row shard; ONE RCCL
@@ -296,9 +298,12 @@ class VectorStore:
             raise ValueError(f"refine_exact must be 'auto', True or False, got {exact!r}")
         self.refine_exact = exact
         self.exact_cap = int(config.get('exact_cap', nat.EXACT_CAP))
-        # certificate outcome of the most recent search: queries proven exact by the over-fetch alone / escalated to
-        # exactness on the device / left unproven (escalation off, or a band of more than EXACT_MAX_CAP near-identical rows)
-        self.last_exactness = {"queries": 0, "certified": 0, "escalated": 0, "unproven": 0}
+        # certificate outcome of the most recent search, rewritten by every search: queries proven exact by the over-fetch
+        # alone / escalated to exactness on the device / left unproven (escalation off, or a band of more than EXACT_MAX_CAP
+        # near-identical rows).  mode: 'certificate' (fp32 re-rank + proof, top_k <= 64), 'rerank' (top_k > 64: fp32 re-rank
+        # of an over-fetch without proof, every query counted unproven), 'slab' (refine_fp32=False: the slab's own ranking,
+        # no fp32 claim; queries 0)
+        self.last_exactness = {"queries": 0, "certified": 0, "escalated": 0, "unproven": 0, "mode": None}
         self.sharded = bool(config.get('sharded', False))
         self._device = config.get('device', None)
         self._devices_cfg = config.get('devices', None)
@@ -631,7 +636,9 @@ class VectorStore:
         of a row block through the library's GEMM kernel (crs_gemm_f16, fp32 out), device top-k per block, order by two
         stable sorts (score desc, row asc).  int8 rows are widened per block.  With the fp32 shadow the slab pass over-fetches
         by half and the candidates are re-scored in fp32 by the library (crs::score_rows_f32) before the final order -- the
-        over-fetch re-rank without a certificate (that exists for top_k <= 64)."""
+        over-fetch re-rank without a certificate (that exists for top_k <= 64).  The guarantee is the weaker, empirical one:
+        a band of near-identical rows wider than the over-fetch can leave the list off the fp32 ranking, so last_exactness
+        counts every query of such a search unproven (mode 'rerank')."""
         import torch
         from rag._encoder import gemm_f16
         q16 = nat.queries_to_f16(q32, nat.SLAB_F16)
@@ -683,8 +690,15 @@ class VectorStore:
                 q = q32 if q32.device == sh.device else q32.to(sh.device, non_blocking=True)
                 parts.append(self._search_shard(sh, q, top_k, filt, g=g))
         # certificate bookkeeping (the one host wait of a refined search; search_batch reads the results right after anyway):
-        # status 2 = an escalated query's band held more rows than the list -- repeat that shard with a longer list
-        tally = {"queries": nq, "certified": 0, "escalated": 0, "unproven": 0}
+        # status 2 = an escalated query's band held more rows than the list -- repeat that shard with a longer list.
+        # The tally describes THIS search whatever its path (see __init__)
+        refined = any(sh.refine_fp32 for sh in col.shards)
+        if not refined:
+            tally = {"queries": 0, "certified": 0, "escalated": 0, "unproven": 0, "mode": "slab"}
+        elif top_k > nat.MAX_K:
+            tally = {"queries": nq, "certified": 0, "escalated": 0, "unproven": nq, "mode": "rerank"}
+        else:
+            tally = {"queries": nq, "certified": nq, "escalated": 0, "unproven": 0, "mode": "certificate"}
         worst = None
         for g, sh in enumerate(col.shards):
             if parts[g][2] is None:
@@ -703,9 +717,9 @@ class VectorStore:
             if not self._escalates(sh):
                 st = np.where(st == 1, 2, st)          # not escalated: unproven
             worst = st if worst is None else np.maximum(worst, st)
-        if worst is not None:          # a query counts once: by its worst shard
+        if worst is not None:          # a query counts once: by its worst shard (no shard with rows to search: nothing to miss)
             tally.update(certified=int((worst == 0).sum()), escalated=int((worst == 1).sum()), unproven=int((worst == 2).sum()))
-            self.last_exactness = tally
+        self.last_exactness = tally
         parts = [(s_, i_) for s_, i_, _ in parts]
         if len(parts) > 1:             # one process, N devices: partial lists to the first device, merge there
             dev0 = col.device

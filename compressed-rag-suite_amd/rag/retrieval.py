@@ -174,14 +174,28 @@ class ContextRetriever:
                     lens[r] = len(t)
                 yield ids, lens
 
-        tally = {"queries": len(queries), "certified": 0, "escalated": 0, "unproven": 0}
-        for s, r, st in eng.search_token_batches(batches()):
-            tally["certified"] += int((st == 0).sum())
-            tally["escalated"] += int((st == 1).sum()) if eng.exact else 0
-            tally["unproven"] += int((st == 2).sum()) + (0 if eng.exact else int((st == 1).sum()))
+        tally = {"queries": len(queries), "certified": 0, "escalated": 0, "unproven": 0, "mode": "certificate"}
+        if not eng.refine:
+            tally = {"queries": 0, "certified": 0, "escalated": 0, "unproven": 0, "mode": "slab"}
+        for s, r, st, q_over in eng.search_token_batches(batches(), overflow_queries=True):
+            if q_over is not None:
+                # status 2 (more rows in a query's band than the engine's escalation list holds): the store's own search
+                # repeats those queries with longer lists, as search_batch does; they count by their final status
+                over = np.nonzero(st == 2)[0]
+                s2, r2 = store.search_rows(q_over, s.shape[1])
+                s, r = s.copy(), r.copy()
+                s[over], r[over] = s2, r2
+                sub = store.last_exactness
+                tally["certified"] += sub["certified"]
+                tally["escalated"] += sub["escalated"]
+                tally["unproven"] += sub["unproven"]
+                st = np.where(st == 2, -1, st)
+            if eng.refine:
+                tally["certified"] += int((st == 0).sum())
+                tally["escalated"] += int((st == 1).sum()) if eng.exact else 0
+                tally["unproven"] += int((st == 2).sum()) + (0 if eng.exact else int((st == 1).sum()))
             yield [(s[i], r[i]) for i in range(s.shape[0])]
-        if eng.refine:
-            store.last_exactness = tally
+        store.last_exactness = tally
 
     def retrieve_batch(self, queries: List[str], top_k: Optional[int] = None) -> List[List[Dict]]:
         """``[retrieve(q) for q in queries]`` for many queries at once: the encoder forwards and scans of the whole list

@@ -15,6 +15,8 @@ terms: the oracle's sgemm and the kernel's FMA chain + butterfly round different
 import numpy as np
 import pytest
 
+from topk_check import assert_topk as _assert_topk
+
 pytestmark = pytest.mark.gpu
 
 
@@ -46,23 +48,6 @@ def _search_exact(q32, slab, scales, shadow, row_err, n, d, slab_type, k, k_scan
         nat.escalate_exact(q32, q16, slab, shadow, n, 0, k, s, i, st, ws, cap, scales=scales)
     torch.cuda.synchronize()
     return s.cpu().numpy(), i.cpu().numpy(), st0.cpu().numpy(), st.cpu().numpy()
-
-
-def _assert_topk(got_s, got_i, q32_h, rows_h, k, what, tol=3e-7):
-    """got == the oracle's exact fp32 ranking of the fp32 rows; id differences only between fp64-near-equal rows."""
-    from oracle import scan_ref
-    rs, ri = scan_ref.cosine_topk_ref(q32_h, rows_h, k)
-    assert np.abs(got_s - rs).max() < 1e-5, what
-    bad = np.nonzero((got_i != ri).any(axis=1))[0]
-    for r in bad:
-        ids = np.union1d(got_i[r], ri[r])
-        f64 = rows_h[ids].astype(np.float64) @ q32_h[r].astype(np.float64)
-        score = dict(zip(ids.tolist(), f64.tolist()))
-        kth = sorted(score.values(), reverse=True)[k - 1]
-        for a, b in zip(got_i[r], ri[r]):
-            if a != b:
-                assert abs(score[int(a)] - score[int(b)]) < tol, f"{what}: query {r}: got row {a}, oracle row {b}"
-        assert all(score[int(a)] >= kth - tol for a in got_i[r]), f"{what}: query {r} holds a row below the k-th best"
 
 
 @pytest.mark.parametrize("name,n,d,slab,k_scan", [("f16-384", 1_000_000, 384, "f16", 32), ("f16-768", 400_000, 768, "f16", 32),

@@ -40,5 +40,37 @@ def check_topk(gpu_s, gpu_i, full64, k, id_base=0, band=BAND, tight=TIGHT_TOL):
         assert (true >= kth - band).all(), f"q{r}: id below the k-th best returned"
 
 
+def topk_errors(got_i, q32_h, rows_h, ref_i, k, tol=3e-7):
+    """assert_topk's id rule per query: {query: reason} for every list that is not the oracle's ref_i up to swaps between
+    rows whose fp64 scores differ by less than tol (empty dict = every list passes)."""
+    errs = {}
+    for r in np.nonzero((got_i != ref_i).any(axis=1))[0].tolist():
+        if (got_i[r] < 0).any() or (ref_i[r] < 0).any():
+            errs[r] = f"got rows {got_i[r].tolist()}, oracle rows {ref_i[r].tolist()}"
+            continue
+        ids = np.union1d(got_i[r], ref_i[r])
+        f64 = rows_h[ids].astype(np.float64) @ q32_h[r].astype(np.float64)
+        score = dict(zip(ids.tolist(), f64.tolist()))
+        kth = sorted(score.values(), reverse=True)[k - 1]
+        for a, b in zip(got_i[r], ref_i[r]):
+            if a != b and not abs(score[int(a)] - score[int(b)]) < tol:
+                errs[r] = f"got row {a}, oracle row {b}"
+                break
+        else:
+            if not all(score[int(a)] >= kth - tol for a in got_i[r]):
+                errs[r] = "holds a row below the k-th best"
+    return errs
+
+
+def assert_topk(got_s, got_i, q32_h, rows_h, k, what, tol=3e-7, ref=None):
+    """got == the oracle's exact fp32 ranking of the fp32 rows; id differences only between fp64-near-equal rows.
+    ref: the oracle's (scores, ids) when the caller has them already."""
+    from oracle import scan_ref
+    rs, ri = ref if ref is not None else scan_ref.cosine_topk_ref(q32_h, rows_h, k)
+    assert np.abs(got_s - rs).max() < 1e-5, what
+    errs = topk_errors(got_i, q32_h, rows_h, ri, k, tol)
+    assert not errs, f"{what}: " + "; ".join(f"query {r}: {m}" for r, m in list(errs.items())[:5])
+
+
 def check_exact_ids(gpu_i, ref_i):
     assert np.array_equal(np.asarray(gpu_i), np.asarray(ref_i))
