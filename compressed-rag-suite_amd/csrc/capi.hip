@@ -51,6 +51,7 @@ struct Plan {
   int tb_nw;                               // > 0: scan_tb.hip with this many waves per workgroup
   int tb_slots;                            //   its chain length (0: dump mode)
   int group_best;                          // 1: the scan leaves tile representatives (scan_refine.hip finishes)
+  int nt;                                  // 1: slab tiles streamed non-temporal (scan_tb / scan_i8; scan_nt_policy)
   size_t part_elems;  // nwg * nq * kp
 };
 
@@ -82,6 +83,16 @@ bool tb_enabled() {   // CRS_SCAN_TB=0: always use the threshold/compaction kern
   static int v = -1;
   if (v < 0) { const char* e = getenv("CRS_SCAN_TB"); v = (e && e[0] == '0') ? 0 : 1; }
   return v == 1;
+}
+
+// The search tail after the scan: finish.hip's one kernel (merge + tile re-score + fp32 re-rank + certificate) where the plan
+// fits it, else the three-kernel chain.  CRS_FUSED_TAIL=0 forces the chain (tests compare the two); read per call.
+bool fused_tail(const Plan& p, int slab_type, int k_in) {
+  return slab_type == CRS_SLAB_F16 && p.group_best && crs::finish_fits(p.nwg, p.kp, k_in, p.tile_rows, p.pdim);
+}
+bool fused_tail_enabled() {
+  const char* e = getenv("CRS_FUSED_TAIL");
+  return !(e && e[0] == '0');
 }
 
 // workspace: [shared thresholds | partial scores | partial rows | stage-1 winners (scores, ids) | two-level merge scratch
@@ -160,6 +171,13 @@ int make_plan(int nq, int dim, int k, int64_t n_rows, int slab_type, Plan* p) {
     break;
   }
   p->part_elems = (size_t)p->nwg * nq * p->kp;
+  // Non-temporal slab stream: a shard's slab far larger than the 256 MB Infinity Cache is read once per launch and replays
+  // from nowhere, so its tiles go nt and stop evicting what the encoder lanes beside the sweep re-read; one query block only
+  // (several blocks of a launch read every tile several times).  A 77 MB slab (C2) replays from the cache and keeps the default.
+  // CRS_SCAN_NT=0 / 1 forces the policy off / on; read per call.
+  const size_t slab_bytes = (size_t)n_rows * p->pdim * (slab_type == CRS_SLAB_I8 ? 1 : 2);
+  const char* ne = getenv("CRS_SCAN_NT");
+  p->nt = (p->tb_nw || p->i8_tb) ? ((ne && ne[0] == '0') ? 0 : (ne && ne[0] == '1') ? 1 : (slab_bytes >= ((size_t)1 << 30) && p->nqb == 1)) : 0;
   return CRS_OK;
 }
 
@@ -265,6 +283,7 @@ static int run_scan(const Plan& p, const void* q16, int nq, int slab_type, const
   a.ticket = nullptr;
   a.t_dyn = p.n_tiles;
   a.dyn_mask = 0;
+  a.nt = p.nt;
   if (((slab_type == CRS_SLAB_F16 && p.tb_nw) || (slab_type == CRS_SLAB_I8 && p.i8_tb && p.pdim <= 768)) && p.tb_slots > 0 && p.nqb == 1 && !share) {
     // (int8 rows of 1024 elements stay static: those instantiations spill, and the ticket's register must not travel through scratch
     // while its value is in flight)
@@ -430,6 +449,48 @@ int crs_escalate_exact(const float* q32_dev, const void* q16_dev, int nq, int di
   return e ? hip_fail((hipError_t)e, "escalate launch") : CRS_OK;
 }
 
+int crs_cosine_topk_cert(const void* q16_dev, int nq, int dim, int slab_type, const void* slab_dev, const float* scales_dev,
+                         int64_t n_rows, int k_in, int64_t id_base, void* workspace_dev, size_t workspace_bytes, float* cand_scores_dev,
+                         int64_t* cand_ids_dev, const float* q32_dev, const float* shadow_dev, int k_out, float row_err_max,
+                         float* out_scores_dev, int64_t* out_ids_dev, int32_t* status_dev, void* exact_ws_dev, size_t exact_ws_bytes,
+                         int cap, void* stream) {
+  if (slab_type != CRS_SLAB_F16 && slab_type != CRS_SLAB_I8) return fail(CRS_EINVAL, "bad slab_type");
+  Plan p;
+  int rc = make_plan(nq, dim, k_in, n_rows, slab_type, &p);
+  if (rc) return rc;
+  if (!(fused_tail_enabled() && fused_tail(p, slab_type, k_in))) {   // the chain: scan + merge (+ refine), then the certificate
+    rc = crs_cosine_topk(q16_dev, nq, dim, slab_type, slab_dev, scales_dev, n_rows, k_in, id_base, workspace_dev, workspace_bytes,
+                         cand_scores_dev, cand_ids_dev, stream);
+    if (rc) return rc;
+    return crs_refine_f32_cert(q32_dev, q16_dev, nq, dim, slab_type, shadow_dev, n_rows, id_base, cand_ids_dev, cand_scores_dev, k_in,
+                               k_out, row_err_max, out_scores_dev, out_ids_dev, status_dev, exact_ws_dev, exact_ws_bytes, cap, stream);
+  }
+  // the same argument checks as the two calls of the chain
+  rc = exact_args_ok(nq, dim, slab_type, cap, exact_ws_bytes, exact_ws_dev);
+  if (rc) return rc;
+  if (k_out <= 0 || k_in < k_out) return fail(CRS_EINVAL, "bad sizes (1 <= k_out <= k_in <= CRS_MAX_K)");
+  if (!q16_dev || !slab_dev || !workspace_dev || !cand_scores_dev || !cand_ids_dev || !q32_dev || !shadow_dev || !out_scores_dev ||
+      !out_ids_dev || !status_dev)
+    return fail(CRS_EINVAL, "null pointer");
+  if (((uintptr_t)q16_dev | (uintptr_t)slab_dev) & 15) return fail(CRS_EINVAL, "q/slab must be 16-byte aligned");
+  if (workspace_bytes < ws_bytes(p.part_elems, nq, k_in)) return fail(CRS_ENOSPC, "workspace too small");
+  if (!(row_err_max >= 0.f)) row_err_max = crs::exact_err_rows_bound(dim, slab_type);
+  hipStream_t st = (hipStream_t)stream;
+  float* ps;
+  int* pr;
+  int e = run_scan(p, q16_dev, nq, slab_type, slab_dev, scales_dev, n_rows, k_in, workspace_dev, st, &ps, &pr);
+  if (e == -1) return fail(CRS_EINVAL, "unsupported padded dimension");
+  if (e) return hip_fail((hipError_t)e, "scan launch");
+  char* ws = reinterpret_cast<char*>(exact_ws_dev);
+  e = crs::finish_cert_launch(ps, pr, p.nwg, p.kp, reinterpret_cast<const _Float16*>(q16_dev), nq, p.pdim,
+                              reinterpret_cast<const _Float16*>(slab_dev), (int)n_rows, p.tile_rows, q32_dev, dim, shadow_dev, id_base, k_in,
+                              k_out, row_err_max, cand_scores_dev, cand_ids_dev, out_scores_dev, out_ids_dev, status_dev,
+                              reinterpret_cast<float*>(ws), reinterpret_cast<int*>(ws + align_up((size_t)nq * 4, 256)),
+                              reinterpret_cast<int*>(ws + exact_done_off(nq)), st);
+  if (e == -1) return fail(CRS_EINVAL, "unsupported plan for the fused tail");
+  return e ? hip_fail((hipError_t)e, "finish launch") : CRS_OK;
+}
+
 size_t crs_wire_scores_offset(int nq, int k) { return (nq > 0 && k > 0) ? (size_t)nq * k * 8 : 0; }
 size_t crs_wire_bytes(int nq, int k) {
   return (nq > 0 && k > 0) ? (size_t)nq * k * 8 + align_up((size_t)nq * k * 4, 8) : 0;
@@ -456,7 +517,9 @@ int crs_scan_plan_describe(int nq, int dim, int k, int64_t n_rows, int slab_type
   else if (p.tb_nw) snprintf(name, sizeof name, "scan_tb_kernel<%d,%d,%d,%d>", p.pdim, p.tile_rows, p.tb_nw, p.tb_slots);
   else if (slab_type == CRS_SLAB_I8) snprintf(name, sizeof name, "scan_i8_kernel<%d,%d,%d,%d>", p.pdim, p.tile_rows, (p.i8_tb || k <= 16) ? 16 : 32, p.i8_tb ? p.tb_slots : -1);
   else snprintf(name, sizeof name, "scan_f16_kernel<%d,%d,%d>", p.pdim, p.tile_rows, k <= 16 ? 16 : 32);
-  snprintf(buf, cap, "%s streams=%d qblocks=%d kp=%d + merge%s", name, p.nwg, p.nqb, p.kp, p.group_best ? " + refine" : "");
+  // the tail crs_cosine_topk_cert takes with this plan (crs_cosine_topk itself always runs merge [+ refine])
+  snprintf(buf, cap, "%s streams=%d qblocks=%d kp=%d%s + merge%s; cert tail: %s", name, p.nwg, p.nqb, p.kp, p.nt ? " nt" : "",
+           p.group_best ? " + refine" : "", fused_tail(p, slab_type, k) ? "fused" : "chain");
   return CRS_OK;
 }
 

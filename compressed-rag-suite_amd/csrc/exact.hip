@@ -23,6 +23,7 @@
 // when every query of the batch is certified, so they sit in the hipGraph of a batch at the price of two empty launches.
 // A list longer than `cap` (more near-identical rows than that) sets status 2: the caller repeats with a larger cap.
 
+#include "dot_f32.h"
 #include "scan.h"
 
 namespace crs {
@@ -32,11 +33,6 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr float kNegInfE = -__builtin_huge_valf();
 
-__device__ __forceinline__ float wsum(float x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-  return x;
-}
 __device__ __forceinline__ float wmax(float x) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o));
@@ -50,22 +46,7 @@ __device__ __forceinline__ float dot_f32(const float* __restrict__ a, const floa
   return wsum(acc);
 }
 
-// the same for up to four rows at once (loads of all rows in flight together: one HBM round trip instead of four);
-// per row the identical FMA order as dot_f32, so a candidate's score does not depend on which path scored it
-__device__ __forceinline__ void dot4_f32(const float* __restrict__ a, const float* const* __restrict__ rows, int n, int dim, int lane,
-                                         float* __restrict__ out) {
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
-  for (int e = lane; e < dim; e += 64) {
-    const float x = a[e];
-    float y[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) y[u] = (u < n) ? rows[u][e] : 0.f;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) acc[u] = fmaf(x, y[u], acc[u]);
-  }
-#pragma unroll
-  for (int u = 0; u < 4; ++u) out[u] = wsum(acc[u]);
-}
+// (dot4_f32, dot_f32.h: the same for up to four rows at once, per row the identical FMA order)
 
 // ---- certificate -----------------------------------------------------------------------------------------------
 // One 256-thread workgroup per query.  ws_thr / ws_cnt: the escalation workspace's per-query threshold and counter.

@@ -17,6 +17,7 @@
 // k_out rounds of workgroup-wide arg-max, which is slow but exact for any input.
 
 #include "scan.h"
+#include "wave_sort.h"
 
 namespace crs {
 namespace {
@@ -28,31 +29,6 @@ constexpr float kNegInf = -__builtin_huge_valf();
 template <typename IdT>
 __device__ __forceinline__ bool better(float s, IdT id, float s2, IdT id2) {
   return s > s2 || (s == s2 && id < id2);
-}
-
-// full bitonic sort (descending by lane) of one value per lane across a wave64
-__device__ __forceinline__ float wave_sort_desc(float v, int lane) {
-#pragma unroll
-  for (int k = 2; k <= 64; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      const float o = __shfl_xor(v, j);
-      const bool lower = (lane & j) == 0;
-      const bool desc = (lane & k) == 0;       // k == 64: always descending
-      const bool want_max = (lower == desc);
-      v = want_max ? fmaxf(v, o) : fminf(v, o);
-    }
-  }
-  return v;
-}
-// v is a bitonic sequence across the wave -> sorted descending
-__device__ __forceinline__ float wave_clean_desc(float v, int lane) {
-#pragma unroll
-  for (int j = 32; j > 0; j >>= 1) {
-    const float o = __shfl_xor(v, j);
-    v = ((lane & j) == 0) ? fmaxf(v, o) : fminf(v, o);
-  }
-  return v;
 }
 
 // REGE: candidates a thread keeps in registers on the single-pass path (32: 8192 per workgroup, 173 VGPRs; 64: 16384, 244 VGPRs)

@@ -25,6 +25,7 @@ struct ScanArgs {
   unsigned* ticket;       // scan_tb.hip chain mode: tiles >= t_dyn are handed out through this counter (zero at launch); else nullptr
   int t_dyn;              //   first dynamically scheduled tile (a multiple of nwg, >= 2 nwg); n_tiles when the schedule is static
   int dyn_mask;           //   a ticket stands for dyn_mask + 1 consecutive tiles (a power of two)
+  int nt;                 // scan_tb.hip / scan_i8.hip: 1 = slab tiles streamed with the non-temporal policy (lds_dma16_nt)
 };
 
 // scan_refine.hip: re-open the k winning tiles (16, 32 or 64 rows each) per query, re-score, rank
@@ -83,6 +84,14 @@ int score_rows_launch(const float* q32, int nq, int dim, const float* shadow, in
                       float* scores, hipStream_t stream);
 int rescore_launch(const float* q32, int nq, int dim, const float* shadow, int64_t n_rows,
                    int64_t id_base, int k, float* scores, int64_t* ids, hipStream_t stream);
+
+// finish.hip: the tail of a tile-best fp16 scan (merge + tile re-score + fp32 re-rank + certificate) in one kernel; -1 = the plan
+// does not fit it (finish_fits)
+bool finish_fits(int nlists, int kp, int kc, int tile_rows, int pdim);
+int finish_cert_launch(const float* part_s, const int* part_r, int nlists, int kp, const _Float16* q16, int nq, int pdim,
+                       const _Float16* slab, int n_rows, int tile_rows, const float* q32, int dim, const float* shadow, int64_t id_base,
+                       int kc, int k_out, float err_rows, float* cand_s, int64_t* cand_i, float* out_s, int64_t* out_i, int* status,
+                       float* ws_thr, int* ws_cnt, int* ws_done, hipStream_t stream);
 
 // exact.hip: exactness certificate of the over-fetch re-rank + in-stream escalation of uncertified queries
 float exact_err_arith(int dim, int pdim);

@@ -85,10 +85,12 @@ __global__ __launch_bounds__(kThreads, 2) void scan_i8_kernel(const ScanArgs a) 
     const unsigned dst0 = lds_wave + (unsigned)(buf * C::kTileBytes);
     if (tile < n_full) {
       const char* base = uniform_ptr(slab + (size_t)tile * C::kTileBytes);
+      if (a.nt) {   // (a kernel argument: a scalar branch)
 #pragma unroll
-      for (int j = 0; j < C::kLoads; ++j) {
-        const unsigned dst = dst0 + (unsigned)(j * kThreads * 16);
-        lds_dma16(dst, src_off[j], base);
+        for (int j = 0; j < C::kLoads; ++j) lds_dma16_nt(dst0 + (unsigned)(j * kThreads * 16), src_off[j], base);
+      } else {
+#pragma unroll
+        for (int j = 0; j < C::kLoads; ++j) lds_dma16(dst0 + (unsigned)(j * kThreads * 16), src_off[j], base);
       }
       if (wave == 0 && lane < TR / 4) {
         const float* sb = uniform_ptr(a.scales + (size_t)tile * TR);

@@ -83,10 +83,12 @@ __global__ __launch_bounds__(NW * 64, (TbCfg<D, TR, NW>::kWgpc * NW) / 4) void s
     const unsigned dst0 = lds_wave + (unsigned)(buf * C::kTileBytes);
     if (tile < n_full) {
       const char* base = uniform_ptr(slab + (size_t)tile * C::kTileBytes);
+      if (a.nt) {   // (a kernel argument: a scalar branch)
 #pragma unroll
-      for (int j = 0; j < C::kLoads; ++j) {
-        const unsigned dst = dst0 + (unsigned)(j * kT * 16);
-        lds_dma16(dst, src_off[j], base);
+        for (int j = 0; j < C::kLoads; ++j) lds_dma16_nt(dst0 + (unsigned)(j * kT * 16), src_off[j], base);
+      } else {
+#pragma unroll
+        for (int j = 0; j < C::kLoads; ++j) lds_dma16(dst0 + (unsigned)(j * kT * 16), src_off[j], base);
       }
     } else {   // the ragged last tile: clamp every lane to the slab's last 16 bytes (rows past the end never rank)
 #pragma unroll

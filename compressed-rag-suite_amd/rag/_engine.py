@@ -6,8 +6,8 @@ is the rate the plugin surface reaches.  The reference times one query at a time
 
 One BATCH of Qb queries = device segments with the (optional) collectives between them:
     E  encode   token ids [Qb, S] -> fp32 unit embeddings + the scan's fp16 query block        (crs::encoder_forward)
-    S  search   exact scan of this rank's shard, over-fetching k' candidates                   (crs::cosine_topk)
-                -> fp32 re-rank against the shadow + per-query exactness certificate            (crs::refine_f32_cert)
+    S  search   exact scan of this rank's shard, over-fetching k' candidates,
+                -> fp32 re-rank against the shadow + per-query exactness certificate            (crs::cosine_topk_cert)
                 -> escalation of unproven queries, a no-op launch when all are proven           (crs::escalate_exact)
                 -> best k in this rank's wire block
     M  merge    (N > 1) after ONE all-gather of the wire blocks: k-way merge                    (crs::merge_topk_wire)
@@ -278,9 +278,20 @@ class RetrievalEngine:
         nat.queries_to_f16(g.q_all32, v.slab_type, out=g.q_all16)
 
     def _seg_search(self, c: _Ctx) -> None:   # all queries x this rank's shard -> wire block
-        self._seg_scan(c)
-        if self.refine:
-            self._seg_post(c)
+        if not self.refine:
+            self._seg_scan(c)
+            return
+        # the sweep + fp32 re-rank + certificate in one call (one fused tail kernel after the scan where the plan allows; the
+        # k' candidates still land in cand_s / cand_i), then the escalation of unproven queries
+        v = self.view
+        qa32 = c.q_all32 if self.gather_q else c.q_out
+        qa16 = c.q_all16 if self.gather_q else c.q16
+        nat.cosine_topk_cert(qa32, qa16, v.slab, v.shadow, v.n, v.dim, self.k_scan, self.k, v.row_err_max, c.exact_ws, self.exact_cap,
+                             scales=v.scales, id_base=v.id_base, workspace=c.ws, cand_scores=c.cand_s, cand_ids=c.cand_i,
+                             out_scores=c.wire.scores, out_ids=c.wire.ids, status=c.status)
+        if self.exact:
+            nat.escalate_exact(qa32, qa16, v.slab, v.shadow, v.n, v.id_base, self.k, c.wire.scores, c.wire.ids, c.status,
+                               c.exact_ws, self.exact_cap, scales=v.scales)
 
     def _seg_scan(self, c: _Ctx) -> None:     # the sweep: k' candidates per query (no re-rank configured: the final lists)
         v = self.view

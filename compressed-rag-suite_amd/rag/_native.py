@@ -46,6 +46,9 @@ _SIGNATURES = {
     "crs_exact_row_error_bound": (c_float, [c_int, c_int]),
     "crs_refine_f32_cert": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
                                     c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "crs_cosine_topk_cert": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p, c_size_t,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_size_t, c_int, c_void_p]),
     "crs_escalate_exact": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                    c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "crs_wire_bytes": (c_size_t, [c_int, c_int]),
@@ -285,6 +288,34 @@ def refine_f32_cert(q32, q16, shadow, n_rows: int, id_base: int, cand_ids, cand_
     with _translate():
         ops().refine_f32_cert_out(q32, q16, shadow, int(n_rows), int(id_base), cand_ids, cand_scores, int(k_out),
                                   float(row_err_max), int(slab_type), out_scores, out_ids, status, exact_ws, int(cap))
+    return out_scores, out_ids, status
+
+
+def cosine_topk_cert(q32, q16, slab, shadow, n_rows: int, dim: int, k_in: int, k_out: int, row_err_max: float, exact_ws,
+                     cap: int = EXACT_CAP, *, scales=None, id_base: int = 0, workspace=None, cand_scores=None, cand_ids=None,
+                     out_scores=None, out_ids=None, status=None):
+    """cosine_topk with k = k_in followed by refine_f32_cert, in one call (crs_cosine_topk_cert: one fused tail kernel after the
+    scan where the plan allows).  q32: the unit fp32 queries [nq, dim]; q16: the scan's query block.  Returns (scores [nq, k_out],
+    ids [nq, k_out], status int32 [nq]); cand_scores / cand_ids [nq, k_in] receive the k_in candidates of the slab."""
+    import torch
+    nq = q32.shape[0]
+    dev = q32.device
+    need = scan_workspace_bytes(nq, dim, k_in, n_rows)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    if cand_scores is None:
+        cand_scores = torch.empty((nq, k_in), dtype=torch.float32, device=dev)
+    if cand_ids is None:
+        cand_ids = torch.empty((nq, k_in), dtype=torch.int64, device=dev)
+    if out_scores is None:
+        out_scores = torch.empty((nq, k_out), dtype=torch.float32, device=dev)
+    if out_ids is None:
+        out_ids = torch.empty((nq, k_out), dtype=torch.int64, device=dev)
+    if status is None:
+        status = torch.empty(nq, dtype=torch.int32, device=dev)
+    with _translate():
+        ops().cosine_topk_cert_out(q32, q16, slab, scales, shadow, int(n_rows), int(id_base), int(k_out), float(row_err_max), workspace,
+                                   cand_scores, cand_ids, out_scores, out_ids, status, exact_ws, int(cap))
     return out_scores, out_ids, status
 
 

@@ -616,15 +616,17 @@ class VectorStore:
         else:
             q16 = nat.queries_to_f16(q32, sh.slab_type)
             k_scan = nat.overfetch(nq, top_k, self.refine_overfetch, n, sh.slab_type) if refine else top_k
-            s, i = nat.cosine_topk(q16, slab, n, sh.dim, k_scan, slab_type=sh.slab_type, scales=scales,
-                                   workspace=sh.workspace(nq, k_scan, n))
-            if refine:
-                # fp32 re-rank of the k_scan candidates + the proof that no un-fetched row can reach the list; queries
-                # without proof are made exact on the device (one more sweep for them; a no-op launch otherwise)
+            if not refine:
+                s, i = nat.cosine_topk(q16, slab, n, sh.dim, k_scan, slab_type=sh.slab_type, scales=scales,
+                                       workspace=sh.workspace(nq, k_scan, n))
+            else:
+                # the scan's k_scan candidates, their fp32 re-rank and the proof that no un-fetched row can reach the list, in one
+                # call; queries without proof are made exact on the device (one more sweep for them; a no-op launch otherwise)
                 qn = torch.nn.functional.normalize(q32, p=2, dim=1, eps=1e-12).contiguous()
                 cap = cap or self.exact_cap
                 ws = sh.exact_workspace(nq, cap)
-                s, i, status = nat.refine_f32_cert(qn, q16, shadow, n, 0, i, s, top_k, sh.row_err_max(), sh.slab_type, ws, cap)
+                s, i, status = nat.cosine_topk_cert(qn, q16, slab, shadow, n, sh.dim, k_scan, top_k, sh.row_err_max(), ws, cap,
+                                                    scales=scales, workspace=sh.workspace(nq, k_scan, n))
                 if self._escalates(sh):
                     nat.escalate_exact(qn, q16, slab, shadow, n, 0, top_k, s, i, status, ws, cap, scales=scales)
         if row_map is not None:

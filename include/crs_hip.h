@@ -132,6 +132,20 @@ int crs_escalate_exact(const float* q32_dev, const void* q16_dev, int nq, int di
                        float* out_scores_dev, int64_t* out_ids_dev, int32_t* status_dev, void* exact_ws_dev,
                        size_t exact_ws_bytes, int cap, void* stream);
 
+/* The scan and the certificate in one call (additive to ABI 3): crs_cosine_topk with k = k_in >= k_out into
+ * cand_scores / cand_ids [nq, k_in], then crs_refine_f32_cert of those candidates into out_scores / out_ids [nq, k_out],
+ * status and the exactness workspace -- the same outputs, bit for bit, as the two calls.  Where the scan plan ends in tile
+ * representatives (tile-best kernels) of an fp16 slab with <= 16 384 candidates per query and rows of <= 640 elements, the
+ * merge, the tile re-score, the fp32 re-rank and the certificate run as ONE kernel (csrc/finish.hip) instead of three;
+ * other plans (int8 slabs, the threshold kernels, larger lists) take the two calls' kernels.  crs_scan_plan_describe names
+ * the tail a plan takes ("cert tail: fused" / "chain").  crs_escalate_exact follows it as it follows crs_refine_f32_cert.
+ * workspace: crs_scan_workspace_bytes(nq, dim, k_in, n_rows); exact_ws: crs_exact_workspace_bytes(nq, cap). */
+int crs_cosine_topk_cert(const void* q16_dev, int nq, int dim, int slab_type, const void* slab_dev, const float* scales_dev,
+                         int64_t n_rows, int k_in, int64_t id_base, void* workspace_dev, size_t workspace_bytes, float* cand_scores_dev,
+                         int64_t* cand_ids_dev, const float* q32_dev, const float* shadow_dev, int k_out, float row_err_max,
+                         float* out_scores_dev, int64_t* out_ids_dev, int32_t* status_dev, void* exact_ws_dev, size_t exact_ws_bytes,
+                         int cap, void* stream);
+
 /* ---- one-collective exchange (ONE all-gather per query batch) ------------------
  * A rank's per-shard result travels as one contiguous "wire block":
  *     [ ids int64 [nq, k] | scores fp32 [nq, k] | pad to 8 bytes ]        crs_wire_bytes(nq, k) bytes
