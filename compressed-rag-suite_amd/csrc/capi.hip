@@ -435,7 +435,8 @@ int crs_escalate_exact(const float* q32_dev, const void* q16_dev, int nq, int di
                        size_t exact_ws_bytes, int cap, void* stream) {
   int rc = exact_args_ok(nq, dim, slab_type, cap, exact_ws_bytes, exact_ws_dev);
   if (rc) return rc;
-  if (n_rows <= 0 || n_rows > 0x7fffffffLL - 64 || k_out <= 0 || k_out > CRS_MAX_K) return fail(CRS_EINVAL, "bad sizes");
+  if (n_rows <= 0 || n_rows > 0x7fffffffLL - 64 || k_out <= 0 || k_out > CRS_MAX_K_CERT) return fail(CRS_EINVAL, "bad sizes");
+  if (k_out > CRS_MAX_K && cap < k_out) return fail(CRS_EINVAL, "k_out above CRS_MAX_K needs cap >= k_out");
   if (!q32_dev || !q16_dev || !slab_dev || !shadow_dev || !out_scores_dev || !out_ids_dev || !status_dev) return fail(CRS_EINVAL, "null pointer");
   if (slab_type == CRS_SLAB_I8 && !scales_dev) return fail(CRS_EINVAL, "int8 slab needs scales");
   if (((uintptr_t)q16_dev | (uintptr_t)slab_dev) & 15) return fail(CRS_EINVAL, "q/slab must be 16-byte aligned");
@@ -489,6 +490,98 @@ int crs_cosine_topk_cert(const void* q16_dev, int nq, int dim, int slab_type, co
                               reinterpret_cast<int*>(ws + exact_done_off(nq)), st);
   if (e == -1) return fail(CRS_EINVAL, "unsupported plan for the fused tail");
   return e ? hip_fail((hipError_t)e, "finish launch") : CRS_OK;
+}
+
+// ---- certified top-k above CRS_MAX_K (csrc/large_k.hip) ----------------------------------------------------------------------
+// workspace: [candidate scores f32 [parts, nq, 64] | candidate ids i64 [parts, nq, 64] | the chunk scans' workspace]
+int crs_large_k_plan(int nq, int k_out, int64_t n_rows, int* parts, int64_t* chunk_rows, size_t* cand_bytes) {
+  if (!parts || !chunk_rows || !cand_bytes) return fail(CRS_EINVAL, "null pointer");
+  if (nq <= 0 || k_out <= 0 || k_out > CRS_MAX_K_CERT) return fail(CRS_EINVAL, "need nq > 0 and 1 <= k_out <= CRS_MAX_K_CERT");
+  if (n_rows <= 0 || n_rows > 0x7fffffffLL - 64) return fail(CRS_EINVAL, "n_rows must be in 1..2^31-65");
+  int64_t p0 = (k_out + 15) / 16;
+  p0 = p0 < 2 ? 2 : p0 > crs::large_k_max_parts() ? crs::large_k_max_parts() : p0;
+  const int64_t rows = ((n_rows + p0 - 1) / p0 + 15) / 16 * 16;
+  *chunk_rows = rows;
+  *parts = (int)((n_rows + rows - 1) / rows);
+  const size_t slots = (size_t)*parts * nq * CRS_MAX_K;
+  *cand_bytes = align_up(slots * 4, 256) + align_up(slots * 8, 256);
+  return CRS_OK;
+}
+
+int crs_cosine_topk_large_cert_workspace_bytes(int nq, int dim, int k_out, int64_t n_rows, size_t* bytes) {
+  if (!bytes) return fail(CRS_EINVAL, "null pointer");
+  int parts;
+  int64_t rows;
+  size_t cand;
+  int rc = crs_large_k_plan(nq, k_out, n_rows, &parts, &rows, &cand);
+  if (rc) return rc;
+  size_t scan = 0, last = 0;   // the chunks share one scan workspace: the larger of a full chunk's and the last chunk's
+  rc = crs_scan_workspace_bytes(nq, dim, CRS_MAX_K, rows < n_rows ? rows : n_rows, &scan);
+  if (rc) return rc;
+  rc = crs_scan_workspace_bytes(nq, dim, CRS_MAX_K, n_rows - (int64_t)(parts - 1) * rows, &last);
+  if (rc) return rc;
+  *bytes = cand + (scan > last ? scan : last);
+  return CRS_OK;
+}
+
+int crs_refine_large_cert(const float* q32_dev, const void* q16_dev, int nq, int dim, int slab_type, const float* shadow_dev,
+                          int64_t n_rows, int64_t id_base, const int64_t* cand_ids_dev, const float* cand_scores_dev, int parts,
+                          int64_t chunk_rows, int k_out, float row_err_max, float* out_scores_dev, int64_t* out_ids_dev,
+                          int32_t* status_dev, void* exact_ws_dev, size_t exact_ws_bytes, int cap, void* stream) {
+  int rc = exact_args_ok(nq, dim, slab_type, cap, exact_ws_bytes, exact_ws_dev);
+  if (rc) return rc;
+  if (n_rows <= 0 || k_out <= 0 || k_out > CRS_MAX_K_CERT) return fail(CRS_EINVAL, "bad sizes (1 <= k_out <= CRS_MAX_K_CERT)");
+  if (parts <= 0 || parts > crs::large_k_max_parts() || chunk_rows <= 0 || (int64_t)parts * chunk_rows < n_rows ||
+      (int64_t)(parts - 1) * chunk_rows >= n_rows)
+    return fail(CRS_EINVAL, "parts x chunk_rows must cover n_rows with 1..64 chunks, none of them empty");
+  if (!q32_dev || !q16_dev || !shadow_dev || !cand_ids_dev || !cand_scores_dev || !out_scores_dev || !out_ids_dev || !status_dev)
+    return fail(CRS_EINVAL, "null pointer");
+  if (!(row_err_max >= 0.f)) row_err_max = crs::exact_err_rows_bound(dim, slab_type);   // untracked (or NaN): the analytic worst case
+  char* ws = reinterpret_cast<char*>(exact_ws_dev);
+  const int e = crs::large_cert_launch(q32_dev, reinterpret_cast<const _Float16*>(q16_dev), nq, dim, crs_row_elems(dim, slab_type), slab_type,
+                                       shadow_dev, n_rows, id_base, cand_ids_dev, cand_scores_dev, parts, chunk_rows, k_out, row_err_max,
+                                       out_scores_dev, out_ids_dev, status_dev, reinterpret_cast<float*>(ws),
+                                       reinterpret_cast<int*>(ws + align_up((size_t)nq * 4, 256)), reinterpret_cast<int*>(ws + exact_done_off(nq)),
+                                       (hipStream_t)stream);
+  if (e == -1) return fail(CRS_EINVAL, "bad parts");
+  return e ? hip_fail((hipError_t)e, "large_cert launch") : CRS_OK;
+}
+
+int crs_cosine_topk_large_cert(const void* q16_dev, int nq, int dim, int slab_type, const void* slab_dev, const float* scales_dev,
+                               int64_t n_rows, int64_t id_base, void* workspace_dev, size_t workspace_bytes, const float* q32_dev,
+                               const float* shadow_dev, int k_out, float row_err_max, float* out_scores_dev, int64_t* out_ids_dev,
+                               int32_t* status_dev, void* exact_ws_dev, size_t exact_ws_bytes, int cap, void* stream) {
+  if (slab_type != CRS_SLAB_F16 && slab_type != CRS_SLAB_I8) return fail(CRS_EINVAL, "bad slab_type");
+  int rc = exact_args_ok(nq, dim, slab_type, cap, exact_ws_bytes, exact_ws_dev);
+  if (rc) return rc;
+  size_t need = 0;
+  rc = crs_cosine_topk_large_cert_workspace_bytes(nq, dim, k_out, n_rows, &need);
+  if (rc) return rc;
+  if (!q16_dev || !slab_dev || !workspace_dev || !q32_dev || !shadow_dev || !out_scores_dev || !out_ids_dev || !status_dev)
+    return fail(CRS_EINVAL, "null pointer");
+  if (slab_type == CRS_SLAB_I8 && !scales_dev) return fail(CRS_EINVAL, "int8 slab needs scales");
+  if (((uintptr_t)q16_dev | (uintptr_t)slab_dev | (uintptr_t)workspace_dev) & 15) return fail(CRS_EINVAL, "q/slab/workspace must be 16-byte aligned");
+  if (workspace_bytes < need) return fail(CRS_ENOSPC, "workspace too small");
+  int parts;
+  int64_t rows;
+  size_t cand;
+  rc = crs_large_k_plan(nq, k_out, n_rows, &parts, &rows, &cand);
+  if (rc) return rc;
+  const size_t slots = (size_t)parts * nq * CRS_MAX_K;
+  float* cand_s = reinterpret_cast<float*>(workspace_dev);
+  int64_t* cand_i = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(workspace_dev) + align_up(slots * 4, 256));
+  char* scan_ws = reinterpret_cast<char*>(workspace_dev) + cand;
+  const size_t row_bytes = (size_t)crs_row_elems(dim, slab_type) * (slab_type == CRS_SLAB_I8 ? 1 : 2);
+  for (int p = 0; p < parts; ++p) {   // chunk p: rows [lo, lo + n) of the shard, its 64 best into block p of the candidates
+    const int64_t lo = (int64_t)p * rows;
+    const int64_t n = (n_rows - lo < rows) ? n_rows - lo : rows;
+    rc = crs_cosine_topk(q16_dev, nq, dim, slab_type, reinterpret_cast<const char*>(slab_dev) + (size_t)lo * row_bytes,
+                         scales_dev ? scales_dev + lo : nullptr, n, CRS_MAX_K, id_base + lo, scan_ws, workspace_bytes - cand,
+                         cand_s + (size_t)p * nq * CRS_MAX_K, cand_i + (size_t)p * nq * CRS_MAX_K, stream);
+    if (rc) return rc;
+  }
+  return crs_refine_large_cert(q32_dev, q16_dev, nq, dim, slab_type, shadow_dev, n_rows, id_base, cand_i, cand_s, parts, rows, k_out,
+                               row_err_max, out_scores_dev, out_ids_dev, status_dev, exact_ws_dev, exact_ws_bytes, cap, stream);
 }
 
 size_t crs_wire_scores_offset(int nq, int k) { return (nq > 0 && k > 0) ? (size_t)nq * k * 8 : 0; }

@@ -23,6 +23,7 @@
 // when every query of the batch is certified, so they sit in the hipGraph of a batch at the price of two empty launches.
 // A list longer than `cap` (more near-identical rows than that) sets status 2: the caller repeats with a larger cap.
 
+#include "cert_eps.h"
 #include "dot_f32.h"
 #include "scan.h"
 
@@ -32,12 +33,6 @@ namespace {
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr float kNegInfE = -__builtin_huge_valf();
-
-__device__ __forceinline__ float wmax(float x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o));
-  return x;
-}
 
 // fp32 score of one candidate row, the arithmetic of crs_refine_f32 (convert.hip): lane-strided FMA chain + butterfly
 __device__ __forceinline__ float dot_f32(const float* __restrict__ a, const float* __restrict__ b, int dim, int lane) {
@@ -64,16 +59,7 @@ __global__ __launch_bounds__(256) void refine_cert_kernel(const float* __restric
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const float* a = q32 + (size_t)qi * dim;
   const _Float16* a16 = q16 + (size_t)qi * pdim;
-  // |q16 - q|^2, |q|^2, max |q16| over the padded row (elements past dim: q = 0)
-  float d2 = 0.f, n2 = 0.f, am = 0.f;
-  for (int e = t; e < pdim; e += 256) {
-    const float x = e < dim ? a[e] : 0.f, h = (float)a16[e];
-    d2 = fmaf(h - x, h - x, d2);
-    n2 = fmaf(x, x, n2);
-    am = fmaxf(am, fabsf(h));
-  }
-  d2 = wsum(d2); n2 = wsum(n2); am = wmax(am);
-  if (lane == 0) { red[wave][0] = d2; red[wave][1] = n2; red[wave][2] = am; }
+  cert_query_partials(a, a16, dim, pdim, t, red);     // |q16 - q|^2, |q|^2, max |q16| (cert_eps.h)
   // candidate c is scored by wave c & 3, four candidates of a wave at a time (k_in = 16: ONE round trip per wave)
   for (int c0 = wave; c0 < k_in; c0 += 16) {
     const float* rows[4];
@@ -120,12 +106,7 @@ __global__ __launch_bounds__(256) void refine_cert_kernel(const float* __restric
   }
   __syncthreads();
   if (t == 0) {
-    const float dd = red[0][0] + red[1][0] + red[2][0] + red[3][0];
-    const float nn = red[0][1] + red[1][1] + red[2][1] + red[3][1];
-    const float mx = fmaxf(fmaxf(red[0][2], red[1][2]), fmaxf(red[2][2], red[3][2]));
-    float dq = sqrtf(dd) * 1.0001f;
-    if (is_i8) dq += sqrtf((float)pdim) * mx * (1.0001f / 65024.0f);
-    const float eps = dq * (1.0f + err_rows) * 1.0001f + sqrtf(nn) * err_rows * 1.0002f + err_arith;
+    const float eps = cert_query_eps(red, pdim, is_i8, err_rows, err_arith);
     // t = the k'-th slab score.  Proof without a bound only when the list holds every row of the shard (valid in-shard
     // candidates >= n_rows); a -1 slot on a larger shard, or an id outside [id_base, id_base + n_rows), proves nothing
     int valid = 0, outside = 0;
@@ -196,7 +177,7 @@ __device__ void refine_list_one(int qi, char* smem, const float* __restrict__ q3
         if (c0 + 4 * u < n) { ls[c0 + 4 * u] = oks[u] ? sc[u] : kNegInfE; li[c0 + 4 * u] = oks[u] ? ids[u] : (int64_t)-1; }
     }
   }
-  if (t < k_out) { out_s[(size_t)qi * k_out + t] = kNegInfE; out_i[(size_t)qi * k_out + t] = -1; }
+  for (int o = t; o < k_out; o += 256) { out_s[(size_t)qi * k_out + o] = kNegInfE; out_i[(size_t)qi * k_out + o] = -1; }
   __syncthreads();
   for (int c = t; c < n; c += 256) {
     const float s = ls[c];

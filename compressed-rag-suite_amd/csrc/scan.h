@@ -104,4 +104,11 @@ int escalate_launch(const float* q32, const _Float16* q16, int nq, int dim, int 
                     int64_t* out_i, int* status, const float* ws_thr, int* ws_cnt, int* ws_done, int64_t* ws_lists, int cap, int cus,
                     hipStream_t stream);
 
+// large_k.hip: fp32 re-rank + certificate of a partitioned over-fetch, cand / cand_s [parts, nq, 64] (k_out <= 4096 candidates);
+// -1 = parts out of 1..large_k_max_parts()
+int large_k_max_parts();
+int large_cert_launch(const float* q32, const _Float16* q16, int nq, int dim, int pdim, int slab_type, const float* shadow, int64_t n_rows,
+                      int64_t id_base, const int64_t* cand, const float* cand_s, int parts, int64_t chunk_rows, int k_out, float err_rows,
+                      float* out_s, int64_t* out_i, int* status, float* ws_thr, int* ws_cnt, int* ws_done, hipStream_t stream);
+
 }  // namespace crs

@@ -10,6 +10,8 @@
 //   crs::refine_f32_cert / crs::escalate_exact   the same with a per-query exactness proof, and the in-stream
 //                          escalation of unproven queries (identical ids to an fp32 store: rag/indexing.py:171-176)
 //   crs::cosine_topk_cert  the scan and the certificate in one call (one fused tail kernel where the plan allows)
+//   crs::cosine_topk_large_cert / crs::refine_large_cert   the same for 64 < k_out <= 1024: partitioned over-fetch, one
+//                          fp32 re-rank + certificate kernel over every chunk's candidates
 //   crs::merge_topk / crs::merge_topk_wire   cross-shard merge                (new vs the reference)
 // Tensors are torch-owned; every op launches on the CURRENT HIP stream of the tensors' device, so the ops
 // compose with torch streams and hipGraph capture.  Errors of the C ABI surface as RuntimeError (TORCH_CHECK)
@@ -228,6 +230,68 @@ void cosine_topk_cert_out(const Tensor& q32, const Tensor& q16, const Tensor& sl
                           cur_stream(q32)), "crs::cosine_topk_cert");
 }
 
+// ---- certified top-k above CRS_MAX_K (include/crs_hip.h, csrc/large_k.hip) ------------------------------------------------------
+void cosine_topk_large_cert_out(const Tensor& q32, const Tensor& q16, const Tensor& slab, c10::optional<Tensor> scales, const Tensor& shadow,
+                                int64_t n_rows, int64_t id_base, int64_t k_out, double row_err_max, Tensor workspace, Tensor out_scores,
+                                Tensor out_ids, Tensor status, Tensor exact_ws, int64_t cap) {
+  want(q32, at::kFloat, "q32");
+  want(q16, at::kHalf, "q16");
+  want(shadow, at::kFloat, "shadow");
+  want(out_scores, at::kFloat, "out_scores");
+  want(out_ids, at::kLong, "out_ids");
+  want(status, at::kInt, "status");
+  TORCH_CHECK(slab.is_cuda() && slab.is_contiguous() && slab.dim() == 2, "slab [rows, pdim]");
+  TORCH_CHECK(workspace.is_cuda() && workspace.is_contiguous(), "workspace must be a contiguous device tensor");
+  TORCH_CHECK(exact_ws.is_cuda() && exact_ws.is_contiguous(), "exact_ws must be a contiguous device tensor");
+  const int st = slab_type_of(slab);
+  const int64_t nq = q32.size(0);
+  const int dim = (int)q32.size(1);
+  const int pdim = crs_row_elems(dim, st);
+  TORCH_CHECK(q32.dim() == 2 && q16.dim() == 2 && q16.size(0) == nq && q16.size(1) == pdim && slab.size(1) == pdim && shadow.dim() == 2 &&
+                  shadow.size(1) == dim && n_rows >= 1 && n_rows <= slab.size(0) && n_rows <= shadow.size(0),
+              "q32 [nq, dim], q16 [nq, pdim], slab [>= n_rows, pdim], shadow [>= n_rows, dim]");
+  TORCH_CHECK(out_scores.numel() == nq * k_out && out_ids.numel() == nq * k_out && status.numel() == nq, "outputs must hold [nq, k_out], status [nq]");
+  if (st == CRS_SLAB_I8) {
+    TORCH_CHECK(has(scales), "int8 slab needs scales");
+    want(*scales, at::kFloat, "scales");
+    TORCH_CHECK(scales->numel() >= n_rows, "scales shorter than n_rows");
+  }
+  same_device(q32, {&q16, &slab, opt_t(scales), &shadow, &workspace, &out_scores, &out_ids, &status, &exact_ws}, "crs::cosine_topk_large_cert");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(q32.device());
+  ok(crs_cosine_topk_large_cert(q16.data_ptr(), (int)nq, dim, st, slab.data_ptr(), (const float*)opt_ptr(scales), n_rows, id_base,
+                                workspace.data_ptr(), (size_t)workspace.nbytes(), q32.data_ptr<float>(), shadow.data_ptr<float>(), (int)k_out,
+                                (float)row_err_max, out_scores.data_ptr<float>(), out_ids.data_ptr<int64_t>(), status.data_ptr<int32_t>(),
+                                exact_ws.data_ptr(), (size_t)exact_ws.nbytes(), (int)cap, cur_stream(q32)),
+     "crs::cosine_topk_large_cert");
+}
+
+void refine_large_cert_out(const Tensor& q32, const Tensor& q16, const Tensor& shadow, int64_t n_rows, int64_t id_base, const Tensor& cand_ids,
+                           const Tensor& cand_scores, int64_t chunk_rows, int64_t k_out, double row_err_max, int64_t slab_type,
+                           Tensor out_scores, Tensor out_ids, Tensor status, Tensor exact_ws, int64_t cap) {
+  want(q32, at::kFloat, "q32");
+  want(q16, at::kHalf, "q16");
+  want(shadow, at::kFloat, "shadow");
+  want(cand_ids, at::kLong, "cand_ids");
+  want(cand_scores, at::kFloat, "cand_scores");
+  want(out_scores, at::kFloat, "out_scores");
+  want(out_ids, at::kLong, "out_ids");
+  want(status, at::kInt, "status");
+  TORCH_CHECK(exact_ws.is_cuda() && exact_ws.is_contiguous(), "exact_ws must be a contiguous device tensor");
+  const int64_t nq = q32.size(0);
+  TORCH_CHECK(q32.dim() == 2 && q16.dim() == 2 && shadow.dim() == 2 && cand_ids.dim() == 3 && shadow.size(1) == q32.size(1) &&
+                  cand_ids.size(1) == nq && cand_ids.size(2) == CRS_MAX_K && cand_scores.sizes() == cand_ids.sizes() &&
+                  n_rows <= shadow.size(0) && q16.size(0) == nq && q16.size(1) == crs_row_elems((int)q32.size(1), (int)slab_type),
+              "q32 [nq, dim], q16 [nq, crs_row_elems], shadow [>= n_rows, dim], cand_ids / cand_scores [parts, nq, 64]");
+  TORCH_CHECK(out_scores.numel() == nq * k_out && out_ids.numel() == nq * k_out && status.numel() == nq, "outputs must hold [nq, k_out], status [nq]");
+  same_device(q32, {&q16, &shadow, &cand_ids, &cand_scores, &out_scores, &out_ids, &status, &exact_ws}, "crs::refine_large_cert");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(q32.device());
+  ok(crs_refine_large_cert(q32.data_ptr<float>(), q16.data_ptr(), (int)nq, (int)q32.size(1), (int)slab_type, shadow.data_ptr<float>(), n_rows,
+                           id_base, cand_ids.data_ptr<int64_t>(), cand_scores.data_ptr<float>(), (int)cand_ids.size(0), chunk_rows, (int)k_out,
+                           (float)row_err_max, out_scores.data_ptr<float>(), out_ids.data_ptr<int64_t>(), status.data_ptr<int32_t>(),
+                           exact_ws.data_ptr(), (size_t)exact_ws.nbytes(), (int)cap, cur_stream(q32)),
+     "crs::refine_large_cert");
+}
+
 void escalate_exact(const Tensor& q32, const Tensor& q16, const Tensor& slab, c10::optional<Tensor> scales, const Tensor& shadow,
                     int64_t n_rows, int64_t id_base, int64_t k_out, Tensor out_scores, Tensor out_ids, Tensor status, Tensor exact_ws,
                     int64_t cap) {
@@ -366,6 +430,12 @@ TORCH_LIBRARY(crs, m) {
         "Tensor(f!) status, Tensor(g!) exact_ws, int cap) -> ()");
   m.def("escalate_exact(Tensor q32, Tensor q16, Tensor slab, Tensor? scales, Tensor shadow, int n_rows, int id_base, int k_out, "
         "Tensor(a!) out_scores, Tensor(b!) out_ids, Tensor(c!) status, Tensor(d!) exact_ws, int cap) -> ()");
+  m.def("cosine_topk_large_cert_out(Tensor q32, Tensor q16, Tensor slab, Tensor? scales, Tensor shadow, int n_rows, int id_base, "
+        "int k_out, float row_err_max, Tensor(a!) workspace, Tensor(b!) out_scores, Tensor(c!) out_ids, Tensor(d!) status, "
+        "Tensor(e!) exact_ws, int cap) -> ()");
+  m.def("refine_large_cert_out(Tensor q32, Tensor q16, Tensor shadow, int n_rows, int id_base, Tensor cand_ids, Tensor cand_scores, "
+        "int chunk_rows, int k_out, float row_err_max, int slab_type, Tensor(a!) out_scores, Tensor(b!) out_ids, Tensor(c!) status, "
+        "Tensor(d!) exact_ws, int cap) -> ()");
   m.def("merge_topk(Tensor scores, Tensor ids, int k_out) -> (Tensor, Tensor)");
   m.def("merge_topk_out(Tensor scores, Tensor ids, int k_out, Tensor(a!) out_scores, Tensor(b!) out_ids) -> ()");
   m.def("merge_topk_wire_out(Tensor wire, int nlists, int nq, int k_in, int k_out, Tensor(a!) out_scores, Tensor(b!) out_ids) -> ()");
@@ -384,6 +454,8 @@ TORCH_LIBRARY_IMPL(crs, CUDA, m) {   // the HIP backend of torch-ROCm dispatches
   m.impl("refine_f32_cert_out", &refine_f32_cert_out);
   m.impl("cosine_topk_cert_out", &cosine_topk_cert_out);
   m.impl("escalate_exact", &escalate_exact);
+  m.impl("cosine_topk_large_cert_out", &cosine_topk_large_cert_out);
+  m.impl("refine_large_cert_out", &refine_large_cert_out);
   m.impl("merge_topk", &merge_topk);
   m.impl("merge_topk_out", &merge_topk_out);
   m.impl("merge_topk_wire_out", &merge_topk_wire_out);

@@ -20,6 +20,8 @@ TORCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libcrs_torch.so")
 SLAB_F16 = 0
 SLAB_I8 = 1
 MAX_K = 64
+MAX_K_CERT = 1024          # CRS_MAX_K_CERT: largest top_k with a certificate (partitioned over-fetch, csrc/large_k.hip)
+LARGE_K_MAX_PARTS = 64     # chunks of the partition (x 64 candidates: at most 4096 per query)
 EXACT_MAX_CAP = 13312      # CRS_EXACT_MAX_CAP: longest per-query row list of crs_escalate_exact
 EXACT_CAP = 1024           # default list length (12 KB of LDS per query in the re-rank)
 
@@ -51,6 +53,13 @@ _SIGNATURES = {
                                      c_size_t, c_int, c_void_p]),
     "crs_escalate_exact": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                    c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "crs_large_k_plan": (c_int, [c_int, c_int, c_int64, POINTER(c_int), POINTER(c_int64), POINTER(c_size_t)]),
+    "crs_cosine_topk_large_cert_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int64, POINTER(c_size_t)]),
+    "crs_cosine_topk_large_cert": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_size_t,
+                                           c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int,
+                                           c_void_p]),
+    "crs_refine_large_cert": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int,
+                                      c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "crs_wire_bytes": (c_size_t, [c_int, c_int]),
     "crs_wire_scores_offset": (c_size_t, [c_int, c_int]),
     "crs_merge_topk_wire": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
@@ -326,6 +335,71 @@ def escalate_exact(q32, q16, slab, shadow, n_rows: int, id_base: int, k_out: int
     with _translate():
         ops().escalate_exact(q32, q16, slab, scales, shadow, int(n_rows), int(id_base), int(k_out), out_scores, out_ids,
                              status, exact_ws, int(cap))
+
+
+def large_k_plan(k_out: int, n_rows: int):
+    """The partition of crs_cosine_topk_large_cert (crs_large_k_plan): (parts, chunk_rows).  P = clamp(ceil(k_out / 16), 2, 64)
+    chunks are asked for; chunk_rows = ceil(n_rows / P) rounded up to a multiple of 16, so a small shard gets fewer chunks.  Chunk
+    p holds rows [p chunk_rows, min(n_rows, (p + 1) chunk_rows)); each is scanned for its 64 best, so parts x 64 <= 4096
+    candidates per query, each chunk's list about 4 x its expected share of the top-k_out."""
+    k_out, n_rows = int(k_out), int(n_rows)
+    p = min(LARGE_K_MAX_PARTS, max(2, -(-k_out // 16)))
+    rows = -(-(-(-n_rows // p)) // 16) * 16
+    return -(-n_rows // rows), rows
+
+
+def large_k_cand_bytes(nq: int, k_out: int, n_rows: int) -> int:
+    """Bytes of the [parts, nq, 64] candidate block at the head of the large-k workspace: scores fp32 | ids int64, each 256-aligned."""
+    parts, _ = large_k_plan(k_out, n_rows)
+    slots = parts * int(nq) * MAX_K
+    return -(-slots * 4 // 256) * 256 + -(-slots * 8 // 256) * 256
+
+
+def large_cert_workspace_bytes(nq: int, dim: int, k_out: int, n_rows: int) -> int:
+    """crs_cosine_topk_large_cert_workspace_bytes: the candidate block + one workspace the chunk scans share."""
+    out = c_size_t(0)
+    check(load().crs_cosine_topk_large_cert_workspace_bytes(int(nq), int(dim), int(k_out), int(n_rows), byref(out)))
+    return int(out.value)
+
+
+def cosine_topk_large_cert(q32, q16, slab, shadow, n_rows: int, dim: int, k_out: int, row_err_max: float, exact_ws,
+                           cap: int = EXACT_CAP, *, scales=None, id_base: int = 0, workspace=None, out_scores=None, out_ids=None,
+                           status=None):
+    """Certified fp32 top-k_out for k_out up to MAX_K_CERT: the partitioned over-fetch (large_k_plan) of the slab, its fp32 re-rank
+    and the per-query proof (crs_cosine_topk_large_cert).  Returns (scores [nq, k_out], ids [nq, k_out], status int32 [nq]) like
+    cosine_topk_cert; escalate_exact (same k_out, cap >= k_out) makes status-1 queries exact."""
+    import torch
+    nq = q32.shape[0]
+    dev = q32.device
+    need = large_cert_workspace_bytes(nq, dim, k_out, n_rows)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    if out_scores is None:
+        out_scores = torch.empty((nq, k_out), dtype=torch.float32, device=dev)
+    if out_ids is None:
+        out_ids = torch.empty((nq, k_out), dtype=torch.int64, device=dev)
+    if status is None:
+        status = torch.empty(nq, dtype=torch.int32, device=dev)
+    with _translate():
+        ops().cosine_topk_large_cert_out(q32, q16, slab, scales, shadow, int(n_rows), int(id_base), int(k_out), float(row_err_max),
+                                         workspace, out_scores, out_ids, status, exact_ws, int(cap))
+    return out_scores, out_ids, status
+
+
+def refine_large_cert(q32, q16, shadow, n_rows: int, id_base: int, cand_ids, cand_scores, chunk_rows: int, k_out: int,
+                      row_err_max: float, slab_type: int, exact_ws, cap: int = EXACT_CAP):
+    """The re-rank + certificate kernel of cosine_topk_large_cert alone, on a candidate block the caller holds: cand_ids /
+    cand_scores [parts, nq, 64], block p = the slab top-64 of rows [p chunk_rows, (p + 1) chunk_rows) + id_base."""
+    import torch
+    nq = q32.shape[0]
+    out_scores = torch.empty((nq, k_out), dtype=torch.float32, device=q32.device)
+    out_ids = torch.empty((nq, k_out), dtype=torch.int64, device=q32.device)
+    status = torch.empty(nq, dtype=torch.int32, device=q32.device)
+    with _translate():
+        ops().refine_large_cert_out(q32, q16, shadow, int(n_rows), int(id_base), cand_ids.contiguous(), cand_scores.contiguous(),
+                                    int(chunk_rows), int(k_out), float(row_err_max), int(slab_type), out_scores, out_ids, status,
+                                    exact_ws, int(cap))
+    return out_scores, out_ids, status
 
 
 class WireBlock:

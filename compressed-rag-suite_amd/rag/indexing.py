@@ -23,14 +23,15 @@ New, additive surface (all keys absent from the reference config.json default so
                               bound (~1e-2 for 768-d rows) is wider than typical score gaps, so the certificate rarely
                               holds and escalating would cost a second sweep for most batches: int8 stays
                               EMPIRICAL (re-rank only) unless refine_exact=True.  ``last_exactness`` reports the counts
-                              of the last search and its mode (top_k > 64: re-rank without proof, counted unproven)
+                              of the last search and its mode (top_k > 1024: re-rank without proof, counted unproven)
   ``num_gpus`` / ``devices``  ONE process driving N devices: contiguous row shards, per-device scans, partial lists
                               copied to the first device and merged there -- RAGPipeline stays one object
   ``sharded``                 SPMD (one process per GPU, torch.distributed): each rank keeps a row shard; ONE RCCL
                               all-gather of the per-shard wire blocks + merge on every rank
 ``where`` / ``where_document`` filters work on every layout (the sidecars are replicated; each shard scans the
-allowed rows it owns).  ``top_k`` is unlimited as in the reference: above the scan kernels' 64 the shard is
-scored by the library's GEMM kernel and selected with a device sort.
+allowed rows it owns).  ``top_k`` is unlimited as in the reference: up to 1024 a refined shard is over-fetched by
+partition (64 candidates from each of up to 64 row chunks, crs::cosine_topk_large_cert) and certified like top_k <= 64;
+above that, or without the fp32 shadow, the shard is scored by the library's GEMM kernel and selected with a device sort.
 
 There is no CPU fallback: without a GPU or without the native libraries every search raises.
 """
@@ -134,9 +135,14 @@ class _Shard:
             ws = self._exact_ws[key] = torch.empty(nat.exact_workspace_bytes(nq, cap), dtype=torch.uint8, device=self.device)
         return ws
 
-    def workspace(self, nq: int, k: int, n_rows: int):
+    def workspace(self, nq: int, k: int, n_rows: int, large: bool = False):
+        """The scan workspace (large: that of the partitioned over-fetch of top-k, nat.cosine_topk_large_cert); one buffer,
+        grown on demand."""
         import torch
-        need = nat.scan_workspace_bytes(nq, self.dim, k, max(n_rows, 1))
+        if large:
+            need = nat.large_cert_workspace_bytes(nq, self.dim, k, max(n_rows, 1))
+        else:
+            need = nat.scan_workspace_bytes(nq, self.dim, k, max(n_rows, 1))
         if self._workspace is None or self._workspace.numel() < need:
             self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._workspace
@@ -300,9 +306,9 @@ class VectorStore:
         self.exact_cap = int(config.get('exact_cap', nat.EXACT_CAP))
         # certificate outcome of the most recent search, rewritten by every search: queries proven exact by the over-fetch
         # alone / escalated to exactness on the device / left unproven (escalation off, or a band of more than EXACT_MAX_CAP
-        # near-identical rows).  mode: 'certificate' (fp32 re-rank + proof, top_k <= 64), 'rerank' (top_k > 64: fp32 re-rank
-        # of an over-fetch without proof, every query counted unproven), 'slab' (refine_fp32=False: the slab's own ranking,
-        # no fp32 claim; queries 0)
+        # near-identical rows).  mode: 'certificate' (fp32 re-rank + proof, top_k <= 1024; above 64 the over-fetch is partitioned,
+        # nat.cosine_topk_large_cert), 'rerank' (top_k > 1024: fp32 re-rank of an over-fetch without proof, every query counted
+        # unproven), 'slab' (refine_fp32=False: the slab's own ranking, no fp32 claim; queries 0)
         self.last_exactness = {"queries": 0, "certified": 0, "escalated": 0, "unproven": 0, "mode": None}
         self.sharded = bool(config.get('sharded', False))
         self._device = config.get('device', None)
@@ -566,6 +572,13 @@ class VectorStore:
             raise
 
     # -- search --------------------------------------------------------------------------------
+    def _cap(self, top_k: int) -> int:
+        """First length of the escalation's row list: exact_cap, and at least 4 x top_k above MAX_K (the list must hold the
+        top_k rows and the band around the k-th)."""
+        if top_k <= nat.MAX_K:
+            return self.exact_cap
+        return min(nat.EXACT_MAX_CAP, max(self.exact_cap, 4 * top_k))
+
     def _escalates(self, sh: _Shard) -> bool:
         """refine_exact 'auto': fp16 slabs escalate unproven queries, int8 slabs stay empirical (module docstring)."""
         if self.refine_exact == 'auto':
@@ -611,7 +624,18 @@ class VectorStore:
                     torch.full((nq, top_k), -1, dtype=torch.int64, device=sh.device), None)
         refine = sh.refine_fp32 and shadow is not None
         status = None
-        if top_k > nat.MAX_K:
+        if top_k > nat.MAX_K and refine and top_k <= nat.MAX_K_CERT:
+            # partitioned over-fetch: 64 candidates from each row chunk, fp32 re-rank of all of them and the proof, in one call;
+            # unproven queries escalated as below (the list of the escalation holds at least top_k rows: cap >= 4 top_k)
+            q16 = nat.queries_to_f16(q32, sh.slab_type)
+            qn = torch.nn.functional.normalize(q32, p=2, dim=1, eps=1e-12).contiguous()
+            cap = cap or self._cap(top_k)
+            ws = sh.exact_workspace(nq, cap)
+            s, i, status = nat.cosine_topk_large_cert(qn, q16, slab, shadow, n, sh.dim, top_k, sh.row_err_max(), ws, cap,
+                                                      scales=scales, workspace=sh.workspace(nq, top_k, n, large=True))
+            if self._escalates(sh):
+                nat.escalate_exact(qn, q16, slab, shadow, n, 0, top_k, s, i, status, ws, cap, scales=scales)
+        elif top_k > nat.MAX_K:
             s, i = self._topk_large(sh, q32, slab, scales, shadow if refine else None, n, top_k)
         else:
             q16 = nat.queries_to_f16(q32, sh.slab_type)
@@ -638,7 +662,8 @@ class VectorStore:
         of a row block through the library's GEMM kernel (crs_gemm_f16, fp32 out), device top-k per block, order by two
         stable sorts (score desc, row asc).  int8 rows are widened per block.  With the fp32 shadow the slab pass over-fetches
         by half and the candidates are re-scored in fp32 by the library (crs::score_rows_f32) before the final order -- the
-        over-fetch re-rank without a certificate (that exists for top_k <= 64).  The guarantee is the weaker, empirical one:
+        over-fetch re-rank without a certificate (that exists for top_k <= MAX_K_CERT: this path serves larger top_k and
+        stores without the shadow).  The guarantee is the weaker, empirical one:
         a band of near-identical rows wider than the over-fetch can leave the list off the fp32 ranking, so last_exactness
         counts every query of such a search unproven (mode 'rerank')."""
         import torch
@@ -697,7 +722,7 @@ class VectorStore:
         refined = any(sh.refine_fp32 for sh in col.shards)
         if not refined:
             tally = {"queries": 0, "certified": 0, "escalated": 0, "unproven": 0, "mode": "slab"}
-        elif top_k > nat.MAX_K:
+        elif top_k > nat.MAX_K_CERT:
             tally = {"queries": nq, "certified": 0, "escalated": 0, "unproven": nq, "mode": "rerank"}
         else:
             tally = {"queries": nq, "certified": nq, "escalated": 0, "unproven": 0, "mode": "certificate"}
@@ -706,7 +731,7 @@ class VectorStore:
             if parts[g][2] is None:
                 continue
             st = parts[g][2].cpu().numpy()
-            cap = self.exact_cap
+            cap = self._cap(top_k)
             while (st == 2).any() and cap < nat.EXACT_MAX_CAP:
                 cap = min(nat.EXACT_MAX_CAP, cap * 4)
                 with torch.cuda.device(sh.device):

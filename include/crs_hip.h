@@ -119,7 +119,8 @@ int crs_refine_f32(const float* q32_dev, int nq, int dim, const float* shadow_de
  * certified queries are left alone, and the one kernel's blocks all leave at once when nothing is to do (so the call can sit in a
  * captured graph; the lists are re-ranked by the last block through the sweep -- release fence + counter, no spinning).  A list longer than `cap` rows leaves status[i] = 2: call again with a larger cap
  * (<= CRS_EXACT_MAX_CAP).  Workspace: crs_exact_workspace_bytes(nq, cap) bytes, written by crs_refine_f32_cert and
- * consumed by crs_escalate_exact (same nq, cap). */
+ * consumed by crs_escalate_exact (same nq, cap).  crs_escalate_exact takes k_out <= CRS_MAX_K, or up to CRS_MAX_K_CERT when
+ * cap >= k_out (after crs_cosine_topk_large_cert). */
 #define CRS_EXACT_MAX_CAP 13312
 size_t crs_exact_workspace_bytes(int nq, int cap);
 float crs_exact_row_error_bound(int dim, int slab_type);
@@ -145,6 +146,32 @@ int crs_cosine_topk_cert(const void* q16_dev, int nq, int dim, int slab_type, co
                          int64_t* cand_ids_dev, const float* q32_dev, const float* shadow_dev, int k_out, float row_err_max,
                          float* out_scores_dev, int64_t* out_ids_dev, int32_t* status_dev, void* exact_ws_dev, size_t exact_ws_bytes,
                          int cap, void* stream);
+
+/* ---- certified top-k above one scan's 64 (additive to ABI 3; csrc/large_k.hip holds the derivation) -------------------------
+ * One scan keeps at most CRS_MAX_K candidates per query.  crs_cosine_topk_large_cert over-fetches by partition instead: the
+ * n_rows rows are cut into `parts` contiguous chunks of `chunk_rows` rows (the last one shorter; crs_large_k_plan), each chunk is
+ * scanned with crs_cosine_topk at k = 64 on `stream` (no host sync), and one kernel re-scores the parts x 64 candidates in fp32
+ * against the shadow, ranks them (score desc, id asc) into out_scores / out_ids [nq, k_out] (empty slots: -inf, -1) and certifies
+ * each query as crs_refine_f32_cert does, against the largest (64th slab score + eps_i) of the chunks whose lists do not hold all
+ * their rows: status 0 = the fp32 top-k_out of all n_rows rows, 1 = not proven.  It writes the exactness workspace like
+ * crs_refine_f32_cert, so crs_escalate_exact (same k_out, cap >= k_out) follows it.  1 <= k_out <= CRS_MAX_K_CERT.
+ *   crs_large_k_plan: parts = ceil(n_rows / chunk_rows) with chunk_rows = 16 * ceil(ceil(n_rows / P) / 16) and
+ *     P = clamp(ceil(k_out / 16), 2, 64), so parts x 64 <= 4096; cand_bytes = the [parts, nq, 64] candidate block (scores fp32,
+ *     ids int64, each 256-byte aligned).  Host arithmetic only.
+ *   workspace: crs_cosine_topk_large_cert_workspace_bytes(nq, dim, k_out, n_rows) bytes = cand_bytes + the chunk scans' workspace.
+ * crs_refine_large_cert is the kernel alone, for a candidate block the caller holds: cand_ids / cand_scores [parts, nq, 64] as
+ * the chunk scans leave them (chunk p covers rows [p chunk_rows, min(n_rows, (p + 1) chunk_rows)) + id_base). */
+#define CRS_MAX_K_CERT 1024
+int crs_large_k_plan(int nq, int k_out, int64_t n_rows, int* parts, int64_t* chunk_rows, size_t* cand_bytes);
+int crs_cosine_topk_large_cert_workspace_bytes(int nq, int dim, int k_out, int64_t n_rows, size_t* bytes);
+int crs_cosine_topk_large_cert(const void* q16_dev, int nq, int dim, int slab_type, const void* slab_dev, const float* scales_dev,
+                               int64_t n_rows, int64_t id_base, void* workspace_dev, size_t workspace_bytes, const float* q32_dev,
+                               const float* shadow_dev, int k_out, float row_err_max, float* out_scores_dev, int64_t* out_ids_dev,
+                               int32_t* status_dev, void* exact_ws_dev, size_t exact_ws_bytes, int cap, void* stream);
+int crs_refine_large_cert(const float* q32_dev, const void* q16_dev, int nq, int dim, int slab_type, const float* shadow_dev,
+                          int64_t n_rows, int64_t id_base, const int64_t* cand_ids_dev, const float* cand_scores_dev, int parts,
+                          int64_t chunk_rows, int k_out, float row_err_max, float* out_scores_dev, int64_t* out_ids_dev,
+                          int32_t* status_dev, void* exact_ws_dev, size_t exact_ws_bytes, int cap, void* stream);
 
 /* ---- one-collective exchange (ONE all-gather per query batch) ------------------
  * A rank's per-shard result travels as one contiguous "wire block":
