@@ -38,8 +38,11 @@ typedef struct crs_encoder_desc {
 
 /* Kernel-form selection for query-batch forwards that run BESIDE a corpus scan (the role-lane layout of
  * rag/_engine.py): only kernel forms of <= 48 KB of LDS per workgroup, so that a forward's workgroups fit on CUs that
- * hold two scan workgroups (2 x 48 KB of 160 KB) instead of waiting for the scan to drain.  Same arithmetic, same
- * results; slower when the forward runs alone. */
+ * hold two scan workgroups (2 x 48 KB of 160 KB) instead of waiting for the scan to drain.  Same arithmetic and the same
+ * fp16 rounding points; bit-identical results except where the default selection runs the fused QKV + attention kernel
+ * (hidden <= 384, head_dim 32 / 64, 16 / 32 / 64-token sequences): there the separate attention kernel sums in another
+ * order and the results differ within the encoder's fp16 quantisation error (tests/test_encoder_*_gpu.py).  Slower when
+ * the forward runs alone. */
 #define CRS_ENC_SMALL_LDS 1
 
 /* Per-layer device pointers.  Matrices are fp16 row-major [out_features, in_features] exactly as
