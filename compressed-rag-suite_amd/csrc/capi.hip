@@ -22,7 +22,6 @@ int hip_fail(hipError_t e, const char* where) {
 }
 
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-size_t align_up16(size_t x) { return (x + 255) / 256 * 256; }
 
 int device_cus() {
   static int cus[64] = {0};
@@ -36,7 +35,6 @@ int device_cus() {
   }
   return cus[dev];
 }
-
 
 constexpr int kW1MaxDump = 256;
 // streams shorter than this many tiles keep the static stride (1.25 M x 384 rows = 76 tiles per stream measured no gain)
@@ -58,7 +56,6 @@ struct Plan {
 // slots per (query, workgroup) partial list: k, or 16 when threshold sharing is on (lists may then be
 // dumped unselected)
 int partial_width(int k) { return (crs::scan_share_tau() && k <= 16) ? 16 : k; }
-size_t tau_bytes(int nq) { return align_up16((size_t)nq * 4); }
 
 bool tb_long_chain() {   // CRS_SCAN_LONG_CHAIN=0: 16 < k <= 64 on long streams back on the threshold kernels (A/B, tests)
   static int v = -1;
@@ -95,14 +92,36 @@ bool fused_tail_enabled() {
   return !(e && e[0] == '0');
 }
 
-// workspace: [shared thresholds | partial scores | partial rows | stage-1 winners (scores, ids) | two-level merge scratch
-// (scores, ids): one k-entry list per 8192 candidates of a query (merge.hip)]
+// scan workspace: [shared thresholds (or the tile ticket) | partial scores | partial rows | stage-1 winners (scores, ids) |
+// two-level merge scratch (scores, ids): one k-entry list per 8192 candidates of a query (merge.hip)], each 256-byte aligned
 size_t inter_lists(size_t part_elems, int nq) { return part_elems / ((size_t)nq * 4096) + 2; }   // >= merge_slices(nwg, kp)
-size_t ws_bytes(size_t part_elems, int nq, int k) {
+struct ScanWs {
+  unsigned* tau;
+  float* part_s;
+  int* part_r;
+  float* win_s;
+  int64_t* win_i;
+  float* inter_s;
+  int64_t* inter_i;
+  size_t tau_bytes, bytes;   // of the first block, of all of them
+};
+ScanWs scan_ws(void* base, size_t part_elems, int nq, int k) {
   const size_t inter = (size_t)nq * inter_lists(part_elems, nq) * k;
-  return tau_bytes(nq) + 2 * align_up(part_elems * 4, 256) + align_up((size_t)nq * k * 4, 256) + align_up((size_t)nq * k * 8, 256) +
-         align_up(inter * 4, 256) + align_up(inter * 8, 256);
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const uintptr_t at = (uintptr_t)base + off; off += align_up(bytes, 256); return at; };
+  ScanWs w;
+  w.tau = reinterpret_cast<unsigned*>(take((size_t)nq * 4));
+  w.tau_bytes = off;
+  w.part_s = reinterpret_cast<float*>(take(part_elems * 4));
+  w.part_r = reinterpret_cast<int*>(take(part_elems * 4));
+  w.win_s = reinterpret_cast<float*>(take((size_t)nq * k * 4));
+  w.win_i = reinterpret_cast<int64_t*>(take((size_t)nq * k * 8));
+  w.inter_s = reinterpret_cast<float*>(take(inter * 4));
+  w.inter_i = reinterpret_cast<int64_t*>(take(inter * 8));
+  w.bytes = off;
+  return w;
 }
+size_t ws_bytes(size_t part_elems, int nq, int k) { return scan_ws(nullptr, part_elems, nq, k).bytes; }
 
 int make_plan(int nq, int dim, int k, int64_t n_rows, int slab_type, Plan* p) {
   if (nq <= 0 || dim <= 0 || dim > 1024) return fail(CRS_EINVAL, "nq must be > 0 and 0 < dim <= 1024");
@@ -181,8 +200,6 @@ int make_plan(int nq, int dim, int k, int64_t n_rows, int slab_type, Plan* p) {
   return CRS_OK;
 }
 
-
-
 }  // namespace
 
 namespace crs {
@@ -244,24 +261,20 @@ int crs_scan_workspace_bytes(int nq, int dim, int k, int64_t n_rows, size_t* byt
 }
 
 static int run_scan(const Plan& p, const void* q16, int nq, int slab_type, const void* slab,
-                    const float* scales, int64_t n_rows, int k, void* ws, hipStream_t st,
-                    float** ps_out, int** pr_out) {
-  unsigned* tau = reinterpret_cast<unsigned*>(ws);
-  float* ps = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + tau_bytes(nq));
-  int* pr = reinterpret_cast<int*>(reinterpret_cast<char*>(ps) + align_up(p.part_elems * 4, 256));
+                    const float* scales, int64_t n_rows, int k, const ScanWs& ws, hipStream_t st) {
   const bool share = crs::scan_share_tau();
   if (share) {
-    const hipError_t me = hipMemsetAsync(tau, 0, tau_bytes(nq), st);
+    const hipError_t me = hipMemsetAsync(ws.tau, 0, ws.tau_bytes, st);
     if (me != hipSuccess) return (int)me;
   }
   crs::ScanArgs a;
   a.q = reinterpret_cast<const _Float16*>(q16);
   a.slab = slab;
   a.scales = scales;
-  a.part_scores = ps;
-  a.part_rows = pr;
+  a.part_scores = ws.part_s;
+  a.part_rows = ws.part_r;
   a.stamps = nullptr;
-  a.tau_shared = share ? tau : nullptr;
+  a.tau_shared = share ? ws.tau : nullptr;
   a.kp = p.kp;
   {
     static int boot = -1;
@@ -296,7 +309,7 @@ static int run_scan(const Plan& p, const void* q16, int nq, int slab_type, const
       int stat = (int)((int64_t)rounds * (100 - pct) / 100);
       if (stat < 2) stat = 2;
       a.t_dyn = stat * p.nwg;
-      a.ticket = tau;
+      a.ticket = ws.tau;
       a.dyn_mask = tb_dyn_granule() - 1;
       const int ze = crs::scan_ticket_zero(a.ticket, st);
       if (ze) return ze;
@@ -304,13 +317,21 @@ static int run_scan(const Plan& p, const void* q16, int nq, int slab_type, const
   }
   const int e = p.w1_qg ? crs::scan_launch_w1(a, p.pdim, st)
                 : p.wide_nw ? crs::scan_launch_wide(a, p.pdim, p.wide_nw, st)
-                
                 : (slab_type == CRS_SLAB_I8) ? crs::scan_launch_i8(a, p.pdim, p.i8_tb ? p.tb_slots : -1, st)
                 : p.tb_nw ? crs::scan_launch_tb(a, p.pdim, p.tb_nw, p.tb_slots, st)
                                : crs::scan_launch_f16(a, p.pdim, p.nwg, st);
-  *ps_out = ps;
-  *pr_out = pr;
   return e;
+}
+
+// the argument checks of a search (scan + tail into out_scores / out_ids) once its plan is made
+static int search_args_ok(const Plan& p, const void* q16_dev, int nq, int slab_type, const void* slab_dev, const float* scales_dev, int k,
+                          const void* workspace_dev, size_t workspace_bytes, const void* out_scores_dev, const void* out_ids_dev) {
+  if (!q16_dev || !slab_dev || !workspace_dev || !out_scores_dev || !out_ids_dev)
+    return fail(CRS_EINVAL, "null pointer");
+  if (slab_type == CRS_SLAB_I8 && !scales_dev) return fail(CRS_EINVAL, "int8 slab needs scales");
+  if (((uintptr_t)q16_dev | (uintptr_t)slab_dev) & 15) return fail(CRS_EINVAL, "q/slab must be 16-byte aligned");
+  if (workspace_bytes < ws_bytes(p.part_elems, nq, k)) return fail(CRS_ENOSPC, "workspace too small");
+  return CRS_OK;
 }
 
 int crs_cosine_topk(const void* q16_dev, int nq, int dim, int slab_type, const void* slab_dev,
@@ -321,35 +342,27 @@ int crs_cosine_topk(const void* q16_dev, int nq, int dim, int slab_type, const v
   Plan p;
   int rc = make_plan(nq, dim, k, n_rows, slab_type, &p);
   if (rc) return rc;
-  if (!q16_dev || !slab_dev || !workspace_dev || !out_scores_dev || !out_ids_dev)
-    return fail(CRS_EINVAL, "null pointer");
-  if (slab_type == CRS_SLAB_I8 && !scales_dev) return fail(CRS_EINVAL, "int8 slab needs scales");
-  if (((uintptr_t)q16_dev | (uintptr_t)slab_dev) & 15) return fail(CRS_EINVAL, "q/slab must be 16-byte aligned");
-  if (workspace_bytes < ws_bytes(p.part_elems, nq, k)) return fail(CRS_ENOSPC, "workspace too small");
+  rc = search_args_ok(p, q16_dev, nq, slab_type, slab_dev, scales_dev, k, workspace_dev, workspace_bytes, out_scores_dev, out_ids_dev);
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  float* ps;
-  int* pr;
-  int e = run_scan(p, q16_dev, nq, slab_type, slab_dev, scales_dev, n_rows, k, workspace_dev, st, &ps, &pr);
+  ScanWs w = scan_ws(workspace_dev, p.part_elems, nq, k);
+  int e = run_scan(p, q16_dev, nq, slab_type, slab_dev, scales_dev, n_rows, k, w, st);
   if (e == -1) return fail(CRS_EINVAL, "unsupported padded dimension");
   if (e) return hip_fail((hipError_t)e, "scan launch");
-  float* win_s = reinterpret_cast<float*>(reinterpret_cast<char*>(pr) + align_up(p.part_elems * 4, 256));
-  int64_t* win_i = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(win_s) + align_up((size_t)nq * k * 4, 256));
-  float* inter_s = reinterpret_cast<float*>(reinterpret_cast<char*>(win_i) + align_up((size_t)nq * k * 8, 256));
-  int64_t* inter_i = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(inter_s) + align_up((size_t)nq * inter_lists(p.part_elems, nq) * k * 4, 256));
-  if ((size_t)crs::merge_slices(p.nwg, p.kp) > inter_lists(p.part_elems, nq)) inter_s = nullptr;   // (cannot happen: see inter_lists)
+  if ((size_t)crs::merge_slices(p.nwg, p.kp) > inter_lists(p.part_elems, nq)) w.inter_s = nullptr;   // (cannot happen: see inter_lists)
   if (!p.group_best) {
-    e = crs::merge_launch_i32(ps, pr, p.nwg, nq, p.kp, k, id_base, out_scores_dev, out_ids_dev, inter_s, inter_i, st);
+    e = crs::merge_launch_i32(w.part_s, w.part_r, p.nwg, nq, p.kp, k, id_base, out_scores_dev, out_ids_dev, w.inter_s, w.inter_i, st);
     if (e) return hip_fail((hipError_t)e, "merge launch");
     return CRS_OK;
   }
   // group-best variants: k best representatives (local rows) -> their row groups re-scored and ranked
-  e = crs::merge_launch_i32(ps, pr, p.nwg, nq, p.kp, k, 0, win_s, win_i, inter_s, inter_i, st);
+  e = crs::merge_launch_i32(w.part_s, w.part_r, p.nwg, nq, p.kp, k, 0, w.win_s, w.win_i, w.inter_s, w.inter_i, st);
   if (e) return hip_fail((hipError_t)e, "merge launch");
   e = (slab_type == CRS_SLAB_I8)
-          ? crs::refine_i8_launch(reinterpret_cast<const _Float16*>(q16_dev), nq, p.pdim, slab_dev, scales_dev, (int)n_rows, win_s,
-                                  win_i, k, p.tile_rows, id_base, out_scores_dev, out_ids_dev, st)
+          ? crs::refine_i8_launch(reinterpret_cast<const _Float16*>(q16_dev), nq, p.pdim, slab_dev, scales_dev, (int)n_rows, w.win_s,
+                                  w.win_i, k, p.tile_rows, id_base, out_scores_dev, out_ids_dev, st)
           : crs::refine_launch(reinterpret_cast<const _Float16*>(q16_dev), nq, p.pdim, reinterpret_cast<const _Float16*>(slab_dev),
-                               (int)n_rows, win_s, win_i, k, p.tile_rows, id_base, out_scores_dev, out_ids_dev, st);
+                               (int)n_rows, w.win_s, w.win_i, k, p.tile_rows, id_base, out_scores_dev, out_ids_dev, st);
   if (e == -1) return fail(CRS_EINVAL, "unsupported padded dimension");
   if (e) return hip_fail((hipError_t)e, "refine launch");
   return CRS_OK;
@@ -392,21 +405,43 @@ int crs_refine_f32(const float* q32_dev, int nq, int dim, const float* shadow_de
   return e ? hip_fail((hipError_t)e, "refine_f32 launch") : CRS_OK;
 }
 
-// exactness workspace: [threshold f32 [nq] | counter i32 [nq] | row lists i64 [nq, cap]]
-// exactness workspace: [thresholds | counters | the escalation kernel's blocks-through counter (256 B) | lists]
-static size_t exact_done_off(int nq) { return 2 * align_up((size_t)nq * 4, 256); }
-static size_t exact_lists_off(int nq) { return exact_done_off(nq) + 256; }
+// exactness workspace: [thresholds f32 [nq] | counters i32 [nq] | the escalation kernel's blocks-through counter (256 B) |
+// row lists i64 [nq, cap]]; *bytes = its size
+static crs::ExactWs exact_ws_at(void* base, int nq, int cap, size_t* bytes) {
+  const size_t col = align_up((size_t)nq * 4, 256), lists = 2 * col + 256;
+  const uintptr_t b = (uintptr_t)base;
+  if (bytes) *bytes = lists + (size_t)nq * cap * 8;
+  return {reinterpret_cast<float*>(b), reinterpret_cast<int*>(b + col), reinterpret_cast<int*>(b + 2 * col), reinterpret_cast<int64_t*>(b + lists)};
+}
 size_t crs_exact_workspace_bytes(int nq, int cap) {
-  return (nq > 0 && cap > 0) ? exact_lists_off(nq) + (size_t)nq * cap * 8 : 0;
+  size_t bytes = 0;
+  if (nq > 0 && cap > 0) exact_ws_at(nullptr, nq, cap, &bytes);
+  return bytes;
 }
 float crs_exact_row_error_bound(int dim, int slab_type) { return crs::exact_err_rows_bound(dim, slab_type); }
 
-static int exact_args_ok(int nq, int dim, int slab_type, int cap, size_t ws_bytes, const void* ws) {
+// validates the arguments every certificate entry shares and carves the exactness workspace
+static int exact_ws(int nq, int dim, int slab_type, int cap, size_t ws_bytes, void* ws, crs::ExactWs* out) {
   if (slab_type != CRS_SLAB_F16 && slab_type != CRS_SLAB_I8) return fail(CRS_EINVAL, "bad slab_type");
   if (nq <= 0 || dim <= 0 || dim > 1024) return fail(CRS_EINVAL, "bad nq/dim");
   if (cap < 64 || cap > CRS_EXACT_MAX_CAP) return fail(CRS_EINVAL, "cap must be in 64..CRS_EXACT_MAX_CAP");
   if (!ws || ((uintptr_t)ws & 15)) return fail(CRS_EINVAL, "exactness workspace must be a 16-byte aligned device pointer");
-  if (ws_bytes < crs_exact_workspace_bytes(nq, cap)) return fail(CRS_ENOSPC, "exactness workspace too small");
+  size_t need = 0;
+  *out = exact_ws_at(ws, nq, cap, &need);
+  if (ws_bytes < need) return fail(CRS_ENOSPC, "exactness workspace too small");
+  return CRS_OK;
+}
+// untracked (or NaN) row error: the analytic worst case
+static float row_err_or_bound(float row_err_max, int dim, int slab_type) {
+  return (row_err_max >= 0.f) ? row_err_max : crs::exact_err_rows_bound(dim, slab_type);
+}
+// the argument checks of the fp32 re-rank + certificate of k_in <= CRS_MAX_K candidates per query
+static int cert_args_ok(int64_t n_rows, int k_in, int k_out, const void* q32_dev, const void* q16_dev, const void* shadow_dev,
+                        const void* cand_ids_dev, const void* cand_scores_dev, const void* out_scores_dev, const void* out_ids_dev,
+                        const void* status_dev) {
+  if (n_rows <= 0 || k_out <= 0 || k_in < k_out || k_in > CRS_MAX_K) return fail(CRS_EINVAL, "bad sizes (1 <= k_out <= k_in <= CRS_MAX_K)");
+  if (!q32_dev || !q16_dev || !shadow_dev || !cand_ids_dev || !cand_scores_dev || !out_scores_dev || !out_ids_dev || !status_dev)
+    return fail(CRS_EINVAL, "null pointer");
   return CRS_OK;
 }
 
@@ -414,17 +449,14 @@ int crs_refine_f32_cert(const float* q32_dev, const void* q16_dev, int nq, int d
                         int64_t n_rows, int64_t id_base, const int64_t* cand_ids_dev, const float* cand_scores_dev, int k_in,
                         int k_out, float row_err_max, float* out_scores_dev, int64_t* out_ids_dev, int32_t* status_dev,
                         void* exact_ws_dev, size_t exact_ws_bytes, int cap, void* stream) {
-  int rc = exact_args_ok(nq, dim, slab_type, cap, exact_ws_bytes, exact_ws_dev);
+  crs::ExactWs ws;
+  int rc = exact_ws(nq, dim, slab_type, cap, exact_ws_bytes, exact_ws_dev, &ws);
   if (rc) return rc;
-  if (n_rows <= 0 || k_out <= 0 || k_in < k_out || k_in > CRS_MAX_K) return fail(CRS_EINVAL, "bad sizes (1 <= k_out <= k_in <= CRS_MAX_K)");
-  if (!q32_dev || !q16_dev || !shadow_dev || !cand_ids_dev || !cand_scores_dev || !out_scores_dev || !out_ids_dev || !status_dev)
-    return fail(CRS_EINVAL, "null pointer");
-  if (!(row_err_max >= 0.f)) row_err_max = crs::exact_err_rows_bound(dim, slab_type);   // untracked (or NaN): the analytic worst case
-  char* ws = reinterpret_cast<char*>(exact_ws_dev);
+  rc = cert_args_ok(n_rows, k_in, k_out, q32_dev, q16_dev, shadow_dev, cand_ids_dev, cand_scores_dev, out_scores_dev, out_ids_dev, status_dev);
+  if (rc) return rc;
   const int e = crs::refine_cert_launch(q32_dev, reinterpret_cast<const _Float16*>(q16_dev), nq, dim, crs_row_elems(dim, slab_type),
-                                        slab_type, shadow_dev, n_rows, id_base, cand_ids_dev, cand_scores_dev, k_in, k_out, row_err_max,
-                                        out_scores_dev, out_ids_dev, status_dev, reinterpret_cast<float*>(ws),
-                                        reinterpret_cast<int*>(ws + align_up((size_t)nq * 4, 256)), reinterpret_cast<int*>(ws + exact_done_off(nq)),
+                                        slab_type, shadow_dev, n_rows, id_base, cand_ids_dev, cand_scores_dev, k_in, k_out,
+                                        row_err_or_bound(row_err_max, dim, slab_type), out_scores_dev, out_ids_dev, status_dev, ws,
                                         (hipStream_t)stream);
   return e ? hip_fail((hipError_t)e, "refine_f32_cert launch") : CRS_OK;
 }
@@ -433,19 +465,17 @@ int crs_escalate_exact(const float* q32_dev, const void* q16_dev, int nq, int di
                        const float* scales_dev, const float* shadow_dev, int64_t n_rows, int64_t id_base, int k_out,
                        float* out_scores_dev, int64_t* out_ids_dev, int32_t* status_dev, void* exact_ws_dev,
                        size_t exact_ws_bytes, int cap, void* stream) {
-  int rc = exact_args_ok(nq, dim, slab_type, cap, exact_ws_bytes, exact_ws_dev);
+  crs::ExactWs ws;
+  int rc = exact_ws(nq, dim, slab_type, cap, exact_ws_bytes, exact_ws_dev, &ws);
   if (rc) return rc;
   if (n_rows <= 0 || n_rows > 0x7fffffffLL - 64 || k_out <= 0 || k_out > CRS_MAX_K_CERT) return fail(CRS_EINVAL, "bad sizes");
   if (k_out > CRS_MAX_K && cap < k_out) return fail(CRS_EINVAL, "k_out above CRS_MAX_K needs cap >= k_out");
   if (!q32_dev || !q16_dev || !slab_dev || !shadow_dev || !out_scores_dev || !out_ids_dev || !status_dev) return fail(CRS_EINVAL, "null pointer");
   if (slab_type == CRS_SLAB_I8 && !scales_dev) return fail(CRS_EINVAL, "int8 slab needs scales");
   if (((uintptr_t)q16_dev | (uintptr_t)slab_dev) & 15) return fail(CRS_EINVAL, "q/slab must be 16-byte aligned");
-  char* ws = reinterpret_cast<char*>(exact_ws_dev);
   const int e = crs::escalate_launch(q32_dev, reinterpret_cast<const _Float16*>(q16_dev), nq, dim, crs_row_elems(dim, slab_type), slab_type,
                                      slab_dev, scales_dev, shadow_dev, n_rows, id_base, k_out, out_scores_dev, out_ids_dev, status_dev,
-                                     reinterpret_cast<const float*>(ws), reinterpret_cast<int*>(ws + align_up((size_t)nq * 4, 256)),
-                                     reinterpret_cast<int*>(ws + exact_done_off(nq)),
-                                     reinterpret_cast<int64_t*>(ws + exact_lists_off(nq)), cap, device_cus(), (hipStream_t)stream);
+                                     ws, cap, device_cus(), (hipStream_t)stream);
   if (e == -1) return fail(CRS_EINVAL, "unsupported padded dimension");
   return e ? hip_fail((hipError_t)e, "escalate launch") : CRS_OK;
 }
@@ -459,6 +489,14 @@ int crs_cosine_topk_cert(const void* q16_dev, int nq, int dim, int slab_type, co
   Plan p;
   int rc = make_plan(nq, dim, k_in, n_rows, slab_type, &p);
   if (rc) return rc;
+  // one set of argument checks for both tails: the search's, then the certificate's
+  rc = search_args_ok(p, q16_dev, nq, slab_type, slab_dev, scales_dev, k_in, workspace_dev, workspace_bytes, cand_scores_dev, cand_ids_dev);
+  if (rc) return rc;
+  crs::ExactWs ews;
+  rc = exact_ws(nq, dim, slab_type, cap, exact_ws_bytes, exact_ws_dev, &ews);
+  if (rc) return rc;
+  rc = cert_args_ok(n_rows, k_in, k_out, q32_dev, q16_dev, shadow_dev, cand_ids_dev, cand_scores_dev, out_scores_dev, out_ids_dev, status_dev);
+  if (rc) return rc;
   if (!(fused_tail_enabled() && fused_tail(p, slab_type, k_in))) {   // the chain: scan + merge (+ refine), then the certificate
     rc = crs_cosine_topk(q16_dev, nq, dim, slab_type, slab_dev, scales_dev, n_rows, k_in, id_base, workspace_dev, workspace_bytes,
                          cand_scores_dev, cand_ids_dev, stream);
@@ -466,28 +504,15 @@ int crs_cosine_topk_cert(const void* q16_dev, int nq, int dim, int slab_type, co
     return crs_refine_f32_cert(q32_dev, q16_dev, nq, dim, slab_type, shadow_dev, n_rows, id_base, cand_ids_dev, cand_scores_dev, k_in,
                                k_out, row_err_max, out_scores_dev, out_ids_dev, status_dev, exact_ws_dev, exact_ws_bytes, cap, stream);
   }
-  // the same argument checks as the two calls of the chain
-  rc = exact_args_ok(nq, dim, slab_type, cap, exact_ws_bytes, exact_ws_dev);
-  if (rc) return rc;
-  if (k_out <= 0 || k_in < k_out) return fail(CRS_EINVAL, "bad sizes (1 <= k_out <= k_in <= CRS_MAX_K)");
-  if (!q16_dev || !slab_dev || !workspace_dev || !cand_scores_dev || !cand_ids_dev || !q32_dev || !shadow_dev || !out_scores_dev ||
-      !out_ids_dev || !status_dev)
-    return fail(CRS_EINVAL, "null pointer");
-  if (((uintptr_t)q16_dev | (uintptr_t)slab_dev) & 15) return fail(CRS_EINVAL, "q/slab must be 16-byte aligned");
-  if (workspace_bytes < ws_bytes(p.part_elems, nq, k_in)) return fail(CRS_ENOSPC, "workspace too small");
-  if (!(row_err_max >= 0.f)) row_err_max = crs::exact_err_rows_bound(dim, slab_type);
   hipStream_t st = (hipStream_t)stream;
-  float* ps;
-  int* pr;
-  int e = run_scan(p, q16_dev, nq, slab_type, slab_dev, scales_dev, n_rows, k_in, workspace_dev, st, &ps, &pr);
+  const ScanWs w = scan_ws(workspace_dev, p.part_elems, nq, k_in);
+  int e = run_scan(p, q16_dev, nq, slab_type, slab_dev, scales_dev, n_rows, k_in, w, st);
   if (e == -1) return fail(CRS_EINVAL, "unsupported padded dimension");
   if (e) return hip_fail((hipError_t)e, "scan launch");
-  char* ws = reinterpret_cast<char*>(exact_ws_dev);
-  e = crs::finish_cert_launch(ps, pr, p.nwg, p.kp, reinterpret_cast<const _Float16*>(q16_dev), nq, p.pdim,
+  e = crs::finish_cert_launch(w.part_s, w.part_r, p.nwg, p.kp, reinterpret_cast<const _Float16*>(q16_dev), nq, p.pdim,
                               reinterpret_cast<const _Float16*>(slab_dev), (int)n_rows, p.tile_rows, q32_dev, dim, shadow_dev, id_base, k_in,
-                              k_out, row_err_max, cand_scores_dev, cand_ids_dev, out_scores_dev, out_ids_dev, status_dev,
-                              reinterpret_cast<float*>(ws), reinterpret_cast<int*>(ws + align_up((size_t)nq * 4, 256)),
-                              reinterpret_cast<int*>(ws + exact_done_off(nq)), st);
+                              k_out, row_err_or_bound(row_err_max, dim, slab_type), cand_scores_dev, cand_ids_dev, out_scores_dev,
+                              out_ids_dev, status_dev, ews, st);
   if (e == -1) return fail(CRS_EINVAL, "unsupported plan for the fused tail");
   return e ? hip_fail((hipError_t)e, "finish launch") : CRS_OK;
 }
@@ -528,7 +553,8 @@ int crs_refine_large_cert(const float* q32_dev, const void* q16_dev, int nq, int
                           int64_t n_rows, int64_t id_base, const int64_t* cand_ids_dev, const float* cand_scores_dev, int parts,
                           int64_t chunk_rows, int k_out, float row_err_max, float* out_scores_dev, int64_t* out_ids_dev,
                           int32_t* status_dev, void* exact_ws_dev, size_t exact_ws_bytes, int cap, void* stream) {
-  int rc = exact_args_ok(nq, dim, slab_type, cap, exact_ws_bytes, exact_ws_dev);
+  crs::ExactWs ws;
+  int rc = exact_ws(nq, dim, slab_type, cap, exact_ws_bytes, exact_ws_dev, &ws);
   if (rc) return rc;
   if (n_rows <= 0 || k_out <= 0 || k_out > CRS_MAX_K_CERT) return fail(CRS_EINVAL, "bad sizes (1 <= k_out <= CRS_MAX_K_CERT)");
   if (parts <= 0 || parts > crs::large_k_max_parts() || chunk_rows <= 0 || (int64_t)parts * chunk_rows < n_rows ||
@@ -536,12 +562,9 @@ int crs_refine_large_cert(const float* q32_dev, const void* q16_dev, int nq, int
     return fail(CRS_EINVAL, "parts x chunk_rows must cover n_rows with 1..64 chunks, none of them empty");
   if (!q32_dev || !q16_dev || !shadow_dev || !cand_ids_dev || !cand_scores_dev || !out_scores_dev || !out_ids_dev || !status_dev)
     return fail(CRS_EINVAL, "null pointer");
-  if (!(row_err_max >= 0.f)) row_err_max = crs::exact_err_rows_bound(dim, slab_type);   // untracked (or NaN): the analytic worst case
-  char* ws = reinterpret_cast<char*>(exact_ws_dev);
   const int e = crs::large_cert_launch(q32_dev, reinterpret_cast<const _Float16*>(q16_dev), nq, dim, crs_row_elems(dim, slab_type), slab_type,
-                                       shadow_dev, n_rows, id_base, cand_ids_dev, cand_scores_dev, parts, chunk_rows, k_out, row_err_max,
-                                       out_scores_dev, out_ids_dev, status_dev, reinterpret_cast<float*>(ws),
-                                       reinterpret_cast<int*>(ws + align_up((size_t)nq * 4, 256)), reinterpret_cast<int*>(ws + exact_done_off(nq)),
+                                       shadow_dev, n_rows, id_base, cand_ids_dev, cand_scores_dev, parts, chunk_rows, k_out,
+                                       row_err_or_bound(row_err_max, dim, slab_type), out_scores_dev, out_ids_dev, status_dev, ws,
                                        (hipStream_t)stream);
   if (e == -1) return fail(CRS_EINVAL, "bad parts");
   return e ? hip_fail((hipError_t)e, "large_cert launch") : CRS_OK;
@@ -552,7 +575,8 @@ int crs_cosine_topk_large_cert(const void* q16_dev, int nq, int dim, int slab_ty
                                const float* shadow_dev, int k_out, float row_err_max, float* out_scores_dev, int64_t* out_ids_dev,
                                int32_t* status_dev, void* exact_ws_dev, size_t exact_ws_bytes, int cap, void* stream) {
   if (slab_type != CRS_SLAB_F16 && slab_type != CRS_SLAB_I8) return fail(CRS_EINVAL, "bad slab_type");
-  int rc = exact_args_ok(nq, dim, slab_type, cap, exact_ws_bytes, exact_ws_dev);
+  crs::ExactWs ews;
+  int rc = exact_ws(nq, dim, slab_type, cap, exact_ws_bytes, exact_ws_dev, &ews);
   if (rc) return rc;
   size_t need = 0;
   rc = crs_cosine_topk_large_cert_workspace_bytes(nq, dim, k_out, n_rows, &need);
@@ -653,12 +677,11 @@ int crs_time_cosine_topk(const void* q16_dev, int nq, int dim, int slab_type, co
   hipError_t he;
   if ((he = hipEventCreate(&e0)) != hipSuccess) return hip_fail(he, "hipEventCreate");
   if ((he = hipEventCreate(&e1)) != hipSuccess) return hip_fail(he, "hipEventCreate");
-  float* ps;
-  int* pr;
+  const ScanWs w = scan_ws(workspace_dev, p.part_elems, nq, k);
   // scan kernel alone
   hipEventRecord(e0, st);
   for (int i = 0; i < iters; ++i) {
-    const int e = run_scan(p, q16_dev, nq, slab_type, slab_dev, scales_dev, n_rows, k, workspace_dev, st, &ps, &pr);
+    const int e = run_scan(p, q16_dev, nq, slab_type, slab_dev, scales_dev, n_rows, k, w, st);
     if (e) { hipEventDestroy(e0); hipEventDestroy(e1); return e == -1 ? fail(CRS_EINVAL, "unsupported padded dimension") : hip_fail((hipError_t)e, "scan launch"); }
   }
   hipEventRecord(e1, st);

@@ -10,22 +10,10 @@
 // One wave64 per row; rows are <= 1024 elements so a lane owns <= 16 strided elements.
 
 #include "scan.h"
+#include "tail_steps.h"
 
 namespace crs {
 namespace {
-
-constexpr float kNegInf = -__builtin_huge_valf();
-
-__device__ __forceinline__ float wave_sum(float x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-  return x;
-}
-__device__ __forceinline__ float wave_max(float x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o));
-  return x;
-}
 
 // grid: one wave per row, 4 waves per block
 template <bool I8>
@@ -43,14 +31,14 @@ __global__ __launch_bounds__(256) void slab_append_kernel(const float* __restric
     const float x = src[c];
     ss += x * x;
   }
-  ss = wave_sum(ss);
+  ss = wsum(ss);
   const float inv_den = fmaxf(sqrtf(ss), 1e-12f);
   const int64_t dr = row0 + r;
   float err2 = 0.f;
   if (I8) {
     float amax = 0.f;
     for (int c = lane; c < dim; c += 64) amax = fmaxf(amax, fabsf(src[c] / inv_den));
-    amax = wave_max(amax);
+    amax = wmax(amax);
     const float sc = amax / 127.0f;
     const float safe = sc > 0.f ? sc : 1.0f;
     int8_t* dst = reinterpret_cast<int8_t*>(slab) + dr * pdim;
@@ -80,7 +68,7 @@ __global__ __launch_bounds__(256) void slab_append_kernel(const float* __restric
   // |stored row - fp32 row|_2, maximum over the shard's rows: the row term of the exactness certificate (exact.hip).
   // Non-negative floats order like their bit patterns; the plain read first keeps the atomics to the few rows that raise it.
   if (row_err_max) {
-    const float err = sqrtf(wave_sum(err2)) * 1.0001f;
+    const float err = sqrtf(wsum(err2)) * 1.0001f;
     if (lane == 0) {
       int* p = reinterpret_cast<int*>(row_err_max);
       if (__float_as_int(err) > __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p, __float_as_int(err));
@@ -107,9 +95,7 @@ __global__ __launch_bounds__(256) void rescore_dot_kernel(const float* __restric
   if (row < 0 || row >= n_rows) return;  // foreign shard: leave untouched (the caller pre-fills)
   const float* a = q32 + (size_t)qi * dim;
   const float* b = shadow + (size_t)row * dim;
-  float acc = 0.f;
-  for (int c = lane; c < dim; c += 64) acc = fmaf(a[c], b[c], acc);
-  acc = wave_sum(acc);
+  const float acc = dot_f32(a, b, dim, lane);
   if (lane == 0) scores[e] = acc;
 }
 
@@ -126,11 +112,11 @@ __global__ __launch_bounds__(64) void sort_rows_kernel(int nq, int k, float* __r
   for (int j = 0; j < k; ++j) {
     const float sj = __shfl(s, j);
     const int64_t ij = __shfl(id, j);
-    bool before;  // does entry j precede this lane's entry?
-    if (ij < 0) before = (id < 0) && (j < lane);
-    else if (id < 0) before = true;
-    else before = (sj > s) || (sj == s && ij < id);
-    rank += before ? 1 : 0;
+    bool first;  // does entry j precede this lane's entry?
+    if (ij < 0) first = (id < 0) && (j < lane);
+    else if (id < 0) first = true;
+    else first = before(sj, ij, s, id);
+    rank += first ? 1 : 0;
   }
   if (in) {
     scores[(size_t)qi * k + rank] = s;
@@ -155,31 +141,11 @@ __global__ __launch_bounds__(256) void refine_f32_kernel(const float* __restrict
     int64_t id = cand[(size_t)qi * k_in + c];
     const int64_t row = id - id_base;
     const bool ok = id >= 0 && row >= 0 && row < n_rows;
-    float acc = 0.f;
-    if (ok) {
-      const float* b = shadow + (size_t)row * dim;
-      for (int e = lane; e < dim; e += 64) acc = fmaf(a[e], b[e], acc);
-    }
-    acc = wave_sum(acc);
+    const float acc = ok ? dot_f32(a, shadow + (size_t)row * dim, dim, lane) : 0.f;   // (ok is wave-uniform)
     if (lane == 0) { sh_s[c] = ok ? acc : kNegInf; sh_i[c] = ok ? id : (int64_t)-1; }
   }
   __syncthreads();
-  const int t = threadIdx.x;
-  if (t < k_out) { out_s[(size_t)qi * k_out + t] = kNegInf; out_i[(size_t)qi * k_out + t] = -1; }
-  __syncthreads();
-  if (t < k_in) {
-    const float s = sh_s[t];
-    const int64_t id = sh_i[t];
-    if (id >= 0) {
-      int rank = 0;
-      for (int j = 0; j < k_in; ++j) {
-        const float sj = sh_s[j];
-        const int64_t ij = sh_i[j];
-        rank += (ij >= 0 && (sj > s || (sj == s && (ij < id || (ij == id && j < t))))) ? 1 : 0;
-      }
-      if (rank < k_out) { out_s[(size_t)qi * k_out + rank] = s; out_i[(size_t)qi * k_out + rank] = id; }
-    }
-  }
+  rank_rescored(sh_s, sh_i, k_in, k_out, threadIdx.x, out_s + (size_t)qi * k_out, out_i + (size_t)qi * k_out, nullptr);
 }
 
 }  // namespace

@@ -1,56 +1,27 @@
 // exact.hip -- the exactness certificate behind "Recall@10 = 1.0 vs the fp32 ranking", and the escalation that
 // restores it when the certificate fails (the reference stores and ranks fp32: rag/indexing.py:114-119,171-176).
 //
-// The store over-fetches k' candidates per query from the fp16 / int8 slab (crs_cosine_topk) and re-ranks them by
-// their fp32 scores against the fp32 shadow.  That result IS the fp32 top-k of ALL rows whenever no un-fetched row
-// can reach it:
-//     every un-fetched row j has   slab_score(j) <= t            (t = the k'-th slab score: the scan is exact on its
-//                                                                 own scores; + 2e-5 |t| for the last-bit difference
-//                                                                 between the scan's and the tile refine's MFMA shape)
-//     and                          |slab_score(j) - s32(j)| <= eps_q
-// so s32(j) <= t + eps_q =: bound, and the re-ranked list is exact iff its k-th fp32 score is > bound.
-// eps_q is a worst-case (Cauchy-Schwarz) bound, per query, from quantities that are MEASURED, not assumed:
-//     slab_score - s32 = <q16 - q, c^_j> + <q, c^_j - c_j>  (+ accumulation error)      c^_j = the row as the slab holds it
-//     |.| <= dq (1 + E) + |q| E + arith
-//     dq    = |q16 - q|_2 computed here from the very two query blocks the scan and the re-rank read
-//             (+ sqrt(pdim) max|q16| / 65024 for int8 slabs: the scan moves the query to 16-bit fixed point, scan_i8.hip)
-//     E     = max over the shard's rows of |c^_j - c_j|_2, tracked by slab_append (convert.hip) in a device scalar
-//     arith = (1.5 pdim + 8) 2^-23: pdim exact products summed in fp32 in any order with truncation (<= pdim 2^-23
-//             sum |a_i b_i| <= pdim 2^-23) plus the fp32 FMA chain of the re-rank (<= dim 2^-24 + the butterfly)
+// The certificate itself -- the bound, eps_q and their derivation -- is cert_verdict / cert_query_eps in tail_steps.h.
 // Uncertified queries (status 1) are escalated INSIDE the same stream with no host round trip: collect_above sweeps
 // the slab once more for them and lists every row whose slab score is >= (k-th fp32 score so far) - eps_q -- a row of
 // the true fp32 top-k cannot score lower -- and refine_list re-ranks that list in fp32.  Both kernels return at once
 // when every query of the batch is certified, so they sit in the hipGraph of a batch at the price of two empty launches.
 // A list longer than `cap` (more near-identical rows than that) sets status 2: the caller repeats with a larger cap.
 
-#include "cert_eps.h"
-#include "dot_f32.h"
 #include "scan.h"
+#include "tail_steps.h"
 
 namespace crs {
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-constexpr float kNegInfE = -__builtin_huge_valf();
-
-// fp32 score of one candidate row, the arithmetic of crs_refine_f32 (convert.hip): lane-strided FMA chain + butterfly
-__device__ __forceinline__ float dot_f32(const float* __restrict__ a, const float* __restrict__ b, int dim, int lane) {
-  float acc = 0.f;
-  for (int e = lane; e < dim; e += 64) acc = fmaf(a[e], b[e], acc);
-  return wsum(acc);
-}
-
-// (dot4_f32, dot_f32.h: the same for up to four rows at once, per row the identical FMA order)
-
 // ---- certificate -----------------------------------------------------------------------------------------------
-// One 256-thread workgroup per query.  ws_thr / ws_cnt: the escalation workspace's per-query threshold and counter.
+// One 256-thread workgroup per query.
 __global__ __launch_bounds__(256) void refine_cert_kernel(const float* __restrict__ q32, const _Float16* __restrict__ q16, int dim,
                                                          int pdim, int is_i8, const float* __restrict__ shadow, int64_t n_rows,
                                                          int64_t id_base, const int64_t* __restrict__ cand,
                                                          const float* __restrict__ cand_s, int k_in, int k_out, float err_rows,
                                                          float err_arith, float* __restrict__ out_s, int64_t* __restrict__ out_i,
-                                                         int* __restrict__ status, float* __restrict__ ws_thr, int* __restrict__ ws_cnt, int* __restrict__ ws_done) {
+                                                         int* __restrict__ status, ExactWs ws) {
   __shared__ float sh_s[64];
   __shared__ int64_t sh_i[64];
   __shared__ float red[4][3];
@@ -58,77 +29,20 @@ __global__ __launch_bounds__(256) void refine_cert_kernel(const float* __restric
   const int qi = blockIdx.x;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const float* a = q32 + (size_t)qi * dim;
-  const _Float16* a16 = q16 + (size_t)qi * pdim;
-  cert_query_partials(a, a16, dim, pdim, t, red);     // |q16 - q|^2, |q|^2, max |q16| (cert_eps.h)
+  const int64_t* qc = cand + (size_t)qi * k_in;
+  const float* qcs = cand_s + (size_t)qi * k_in;
+  cert_query_partials(a, q16 + (size_t)qi * pdim, dim, pdim, t, red);     // |q16 - q|^2, |q|^2, max |q16|
   // candidate c is scored by wave c & 3, four candidates of a wave at a time (k_in = 16: ONE round trip per wave)
-  for (int c0 = wave; c0 < k_in; c0 += 16) {
-    const float* rows[4];
-    int64_t ids[4];
-    bool oks[4];
-    int n = 0;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int c = c0 + 4 * u;
-      ids[u] = -1; oks[u] = false; rows[u] = shadow;
-      if (c < k_in) {
-        n = u + 1;
-        ids[u] = cand[(size_t)qi * k_in + c];
-        const int64_t row = ids[u] - id_base;
-        oks[u] = ids[u] >= 0 && row >= 0 && row < n_rows;
-        if (oks[u]) rows[u] = shadow + (size_t)row * dim;
-      }
-    }
-    float sc[4];
-    dot4_f32(a, rows, n, dim, lane, sc);
-    if (lane == 0) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (c0 + 4 * u < k_in) { sh_s[c0 + 4 * u] = oks[u] ? sc[u] : kNegInfE; sh_i[c0 + 4 * u] = oks[u] ? ids[u] : (int64_t)-1; }
-    }
-  }
-  if (t == 0) kth_s = kNegInfE;
+  for (int c0 = wave; c0 < k_in; c0 += 16)
+    score_candidates4(a, shadow, dim, n_rows, id_base, c0, 4, k_in, [&](int c) { return qc[c]; }, (int64_t)-1, lane, sh_s, sh_i);
+  if (t == 0) kth_s = kNegInf;
   __syncthreads();
-  if (t < k_out) { out_s[(size_t)qi * k_out + t] = kNegInfE; out_i[(size_t)qi * k_out + t] = -1; }
-  __syncthreads();
-  if (t < k_in) {
-    const float s = sh_s[t];
-    const int64_t id = sh_i[t];
-    if (id >= 0) {
-      int rank = 0;
-      for (int j = 0; j < k_in; ++j) {
-        const float sj = sh_s[j];
-        const int64_t ij = sh_i[j];
-        rank += (ij >= 0 && (sj > s || (sj == s && (ij < id || (ij == id && j < t))))) ? 1 : 0;
-      }
-      if (rank < k_out) { out_s[(size_t)qi * k_out + rank] = s; out_i[(size_t)qi * k_out + rank] = id; }
-      if (rank == k_out - 1) kth_s = s;
-    }
-  }
+  rank_rescored(sh_s, sh_i, k_in, k_out, t, out_s + (size_t)qi * k_out, out_i + (size_t)qi * k_out, &kth_s);
   __syncthreads();
   if (t == 0) {
-    const float eps = cert_query_eps(red, pdim, is_i8, err_rows, err_arith);
-    // t = the k'-th slab score.  Proof without a bound only when the list holds every row of the shard (valid in-shard
-    // candidates >= n_rows); a -1 slot on a larger shard, or an id outside [id_base, id_base + n_rows), proves nothing
-    int valid = 0, outside = 0;
-    float tmin = __builtin_huge_valf();
-    for (int c = 0; c < k_in; ++c) {
-      const int64_t id = cand[(size_t)qi * k_in + c];
-      if (id < 0) continue;
-      if (id - id_base >= 0 && id - id_base < n_rows) { ++valid; tmin = fminf(tmin, cand_s[(size_t)qi * k_in + c]); }
-      else ++outside;
-    }
-    const float kth = kth_s;
-    int st = 1;
-    if (outside == 0 && (int64_t)valid >= n_rows) {
-      st = 0;                            // every row of the shard is in the list
-    } else if (outside == 0 && valid == k_in) {
-      const float bound = tmin + eps + 2e-5f * fabsf(tmin);
-      st = (kth > bound) ? 0 : 1;        // (kth == -inf, fewer than k_out candidates, never passes)
-    }
-    status[qi] = st;
-    ws_thr[qi] = kth - eps;
-    ws_cnt[qi] = 0;
-    if (qi == 0) *ws_done = 0;       // the escalation kernel's "blocks through" counter
+    const float eps = cert_query_eps(red, pdim, is_i8, err_rows, err_arith), kth = kth_s;
+    const int st = cert_verdict(k_in, [&](int c) { return qc[c]; }, [&](int c) { return qcs[c]; }, id_base, n_rows, kth, eps);
+    cert_publish(qi, st, kth, eps, status, ws.thr, ws.cnt, ws.done);
   }
 }
 
@@ -152,43 +66,19 @@ __device__ void refine_list_one(int qi, char* smem, const float* __restrict__ q3
   int64_t* li = reinterpret_cast<int64_t*>(smem);
   float* ls = reinterpret_cast<float*>(smem + (size_t)cap * 8);
   const float* a = q32 + (size_t)qi * dim;
-  for (int c0 = wave; c0 < n; c0 += 16) {
-    const float* rows[4];
-    int64_t ids[4];
-    bool oks[4];
-    int m = 0;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int c = c0 + 4 * u;
-      ids[u] = -1; oks[u] = false; rows[u] = shadow;
-      if (c < n) {
-        m = u + 1;
-        ids[u] = lists[(size_t)qi * cap + c];
-        const int64_t row = ids[u] - id_base;
-        oks[u] = row >= 0 && row < n_rows;
-        if (oks[u]) rows[u] = shadow + (size_t)row * dim;
-      }
-    }
-    float sc[4];
-    dot4_f32(a, rows, m, dim, lane, sc);
-    if (lane == 0) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (c0 + 4 * u < n) { ls[c0 + 4 * u] = oks[u] ? sc[u] : kNegInfE; li[c0 + 4 * u] = oks[u] ? ids[u] : (int64_t)-1; }
-    }
-  }
-  for (int o = t; o < k_out; o += 256) { out_s[(size_t)qi * k_out + o] = kNegInfE; out_i[(size_t)qi * k_out + o] = -1; }
+  const int64_t* ql = lists + (size_t)qi * cap;
+  for (int c0 = wave; c0 < n; c0 += 16)
+    score_candidates4(a, shadow, dim, n_rows, id_base, c0, 4, n, [&](int c) { return ql[c]; }, (int64_t)-1, lane, ls, li);
+  for (int o = t; o < k_out; o += 256) { out_s[(size_t)qi * k_out + o] = kNegInf; out_i[(size_t)qi * k_out + o] = -1; }
   __syncthreads();
+  // Not rank_by_count / rank_rescored: a list is up to cap (thousands of) entries for k_out outputs, so the count stops at k_out
+  // (n k_out compares, not n^2); the listed rows are distinct, so there is no slot rule, and out-of-shard entries are skipped.
   for (int c = t; c < n; c += 256) {
     const float s = ls[c];
     const int64_t id = li[c];
     if (id < 0) continue;
     int rank = 0;
-    for (int j = 0; j < n && rank < k_out; ++j) {
-      const float sj = ls[j];
-      const int64_t ij = li[j];
-      rank += (ij >= 0 && (sj > s || (sj == s && ij < id))) ? 1 : 0;
-    }
+    for (int j = 0; j < n && rank < k_out; ++j) rank += (li[j] >= 0 && before(ls[j], li[j], s, id)) ? 1 : 0;
     if (rank < k_out) { out_s[(size_t)qi * k_out + rank] = s; out_i[(size_t)qi * k_out + rank] = id; }
   }
   __syncthreads();                     // the list's LDS is reused by the next query
@@ -315,17 +205,16 @@ float exact_err_rows_bound(int dim, int slab_type) {
 
 int refine_cert_launch(const float* q32, const _Float16* q16, int nq, int dim, int pdim, int slab_type, const float* shadow,
                        int64_t n_rows, int64_t id_base, const int64_t* cand, const float* cand_s, int k_in, int k_out,
-                       float err_rows, float* out_s, int64_t* out_i, int* status, float* ws_thr, int* ws_cnt, int* ws_done, hipStream_t stream) {
+                       float err_rows, float* out_s, int64_t* out_i, int* status, const ExactWs& ws, hipStream_t stream) {
   if (nq <= 0) return 0;
   hipLaunchKernelGGL(refine_cert_kernel, dim3(nq), dim3(256), 0, stream, q32, q16, dim, pdim, slab_type == 1 ? 1 : 0, shadow, n_rows,
-                     id_base, cand, cand_s, k_in, k_out, err_rows, exact_err_arith(dim, pdim), out_s, out_i, status, ws_thr, ws_cnt, ws_done);
+                     id_base, cand, cand_s, k_in, k_out, err_rows, exact_err_arith(dim, pdim), out_s, out_i, status, ws);
   return (int)hipGetLastError();
 }
 
 int escalate_launch(const float* q32, const _Float16* q16, int nq, int dim, int pdim, int slab_type, const void* slab,
                     const float* scales, const float* shadow, int64_t n_rows, int64_t id_base, int k_out, float* out_s,
-                    int64_t* out_i, int* status, const float* ws_thr, int* ws_cnt, int* ws_done, int64_t* ws_lists, int cap, int cus,
-                    hipStream_t stream) {
+                    int64_t* out_i, int* status, const ExactWs& ws, int cap, int cus, hipStream_t stream) {
   if (nq <= 0) return 0;
   const bool i8 = slab_type == 1;
   const int64_t tiles = (n_rows + 15) / 16;
@@ -334,7 +223,7 @@ int escalate_launch(const float* q32, const _Float16* q16, int nq, int dim, int 
   const unsigned grid = (unsigned)(g < gmax ? (g < 1 ? 1 : g) : gmax);
   const size_t lds = (size_t)cap * 12 > 4096 ? (size_t)cap * 12 : 4096;
 #define CRS_ESC(KS_) return launch_escalate<KS_>(i8, grid, lds, stream, q32, q16, nq, dim, slab, scales, shadow, (int)n_rows, id_base, status, \
-                                                  ws_thr, cap, ws_cnt, ws_lists, ws_done, k_out, out_s, out_i)
+                                                  ws.thr, cap, ws.cnt, ws.lists, ws.done, k_out, out_s, out_i)
   switch (pdim / 128) {
     case 1: CRS_ESC(1);
     case 2: CRS_ESC(2);

@@ -6,7 +6,7 @@
 // scores; t_c = the 64th slab score of chunk c.  This kernel re-scores every candidate in fp32 against the shadow (dot4_f32: the
 // bits of the k <= 64 path), orders them (score desc, id asc) with a bitonic sort in LDS and keeps the best k_out.
 //
-// Certificate (exact.hip has the derivation of eps_q, cert_eps.h its code): a row missing from chunk c's list has slab score
+// Certificate (tail_steps.h has the derivation of eps_q and the bound): a row missing from chunk c's list has slab score
 // <= t_c, so its fp32 score is <= t_c + 2e-5 |t_c| + eps_q.  The list is the fp32 top-k_out of all n_rows rows when
 //     k_out-th fp32 score > max over the chunks c that do not list every one of their rows of (t_c + eps_q + 2e-5 |t_c|)
 // with the rules of refine_cert_kernel, per chunk: a chunk proves without a bound only when its list holds every row of the chunk;
@@ -18,9 +18,8 @@
 // Sizing (crs_large_k_plan): P = clamp(ceil(k_out / 16), 2, 64) chunks, fewer on small shards, so each chunk's 64-deep list is
 // about 4 x its expected share of the top-k_out (k_out / P <= 16).
 
-#include "cert_eps.h"
-#include "dot_f32.h"
 #include "scan.h"
+#include "tail_steps.h"
 
 namespace crs {
 namespace {
@@ -28,17 +27,7 @@ namespace {
 constexpr int kLkThreads = 1024;           // 16 waves per query
 constexpr int kLkSlots = 64;               // candidates per chunk (the scan's k)
 constexpr int kLkMaxCand = 4096;           // 64 chunks x 64
-constexpr float kNegInfL = -__builtin_huge_valf();
 constexpr int64_t kNoId = 0x7fffffffffffffffLL;   // empty slot while sorting: after every real row on a -inf tie
-
-// (score desc, id asc)
-__device__ __forceinline__ bool lk_before(float sa, int64_t ia, float sb, int64_t ib) { return sa > sb || (sa == sb && ia < ib); }
-
-__device__ __forceinline__ float wmin(float x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x = fminf(x, __shfl_xor(x, o));
-  return x;
-}
 
 // One 1024-thread workgroup per query.  cand / cand_s: [parts, nq, 64] (chunk p of query qi at (p * nq + qi) * 64).
 // LDS: 4096 x (4 + 8) B = 48 KB for the list, plus the per-chunk verdicts.
@@ -47,7 +36,7 @@ __global__ __launch_bounds__(kLkThreads) void large_cert_kernel(const float* __r
                                                                int64_t id_base, const int64_t* __restrict__ cand, const float* __restrict__ cand_s,
                                                                int parts, int64_t chunk_rows, int k_out, float err_rows, float err_arith,
                                                                float* __restrict__ out_s, int64_t* __restrict__ out_i, int* __restrict__ status,
-                                                               float* __restrict__ ws_thr, int* __restrict__ ws_cnt, int* __restrict__ ws_done) {
+                                                               ExactWs ws) {
   __shared__ float sh_s[kLkMaxCand];
   __shared__ int64_t sh_i[kLkMaxCand];
   __shared__ float red[4][3];
@@ -63,32 +52,10 @@ __global__ __launch_bounds__(kLkThreads) void large_cert_kernel(const float* __r
   if (t < 256) cert_query_partials(a, q16 + (size_t)qi * pdim, dim, pdim, t, red);
 
   // fp32 re-score: candidate c = chunk c / 64, slot c % 64; wave w takes c = w + 64 r + 16 u, four rows per dot4_f32
-  for (int c0 = wave; c0 < n_c; c0 += 64) {
-    const float* rows[4];
-    int64_t ids[4];
-    bool oks[4];
-    int n = 0;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int c = c0 + 16 * u;
-      ids[u] = -1; oks[u] = false; rows[u] = shadow;
-      if (c < n_c) {
-        n = u + 1;
-        ids[u] = cand[((size_t)(c / kLkSlots) * nq + qi) * kLkSlots + (c % kLkSlots)];
-        const int64_t row = ids[u] - id_base;
-        oks[u] = ids[u] >= 0 && row >= 0 && row < n_rows;
-        if (oks[u]) rows[u] = shadow + (size_t)row * dim;
-      }
-    }
-    float sc[4];
-    dot4_f32(a, rows, n, dim, lane, sc);
-    if (lane == 0) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (c0 + 16 * u < n_c) { sh_s[c0 + 16 * u] = oks[u] ? sc[u] : kNegInfL; sh_i[c0 + 16 * u] = oks[u] ? ids[u] : kNoId; }
-    }
-  }
-  for (int c = n_c + t; c < npow; c += kLkThreads) { sh_s[c] = kNegInfL; sh_i[c] = kNoId; }
+  for (int c0 = wave; c0 < n_c; c0 += 64)
+    score_candidates4(a, shadow, dim, n_rows, id_base, c0, 16, n_c,
+                      [&](int c) { return cand[((size_t)(c / kLkSlots) * nq + qi) * kLkSlots + (c % kLkSlots)]; }, kNoId, lane, sh_s, sh_i);
+  for (int c = n_c + t; c < npow; c += kLkThreads) { sh_s[c] = kNegInf; sh_i[c] = kNoId; }
   __syncthreads();
   if (t == 0) eps_s = cert_query_eps(red, pdim, is_i8, err_rows, err_arith);
 
@@ -100,7 +67,7 @@ __global__ __launch_bounds__(kLkThreads) void large_cert_kernel(const float* __r
         if (ix > i) {
           const float si = sh_s[i], sx = sh_s[ix];
           const int64_t ii = sh_i[i], ixx = sh_i[ix];
-          const bool swap = ((i & k) == 0) ? lk_before(sx, ixx, si, ii) : lk_before(si, ii, sx, ixx);
+          const bool swap = ((i & k) == 0) ? before(sx, ixx, si, ii) : before(si, ii, sx, ixx);
           if (swap) { sh_s[i] = sx; sh_s[ix] = si; sh_i[i] = ixx; sh_i[ix] = ii; }
         }
       }
@@ -110,7 +77,7 @@ __global__ __launch_bounds__(kLkThreads) void large_cert_kernel(const float* __r
 
   for (int o = t; o < k_out; o += kLkThreads) {
     const bool v = o < npow && sh_i[o] != kNoId;
-    out_s[(size_t)qi * k_out + o] = v ? sh_s[o] : kNegInfL;
+    out_s[(size_t)qi * k_out + o] = v ? sh_s[o] : kNegInf;
     out_i[(size_t)qi * k_out + o] = v ? sh_i[o] : (int64_t)-1;
   }
 
@@ -129,24 +96,21 @@ __global__ __launch_bounds__(kLkThreads) void large_cert_kernel(const float* __r
     const float tmin = wmin(in_chunk ? cand_s[at] : __builtin_huge_valf());
     if (lane == 0) {
       ch_state[p] = any_out ? 2 : (int64_t)valid >= rows_c ? 0 : valid == kLkSlots ? 1 : 2;   // (2 after "valid < 64": a -1 slot)
-      ch_bound[p] = tmin + eps + 2e-5f * fabsf(tmin);
+      ch_bound[p] = cert_bound(tmin, eps);
     }
   }
   __syncthreads();
   if (t == 0) {
-    const float kth = (k_out <= npow && sh_i[k_out - 1] != kNoId) ? sh_s[k_out - 1] : kNegInfL;
+    const float kth = (k_out <= npow && sh_i[k_out - 1] != kNoId) ? sh_s[k_out - 1] : kNegInf;
     int bad = 0, whole = 1;
-    float bound = kNegInfL;
+    float bound = kNegInf;
     for (int p = 0; p < parts; ++p) {
       bad |= ch_state[p] == 2;
       if (ch_state[p] == 1) { whole = 0; bound = fmaxf(bound, ch_bound[p]); }
     }
     int st = 1;
     if (!bad) st = (whole || kth > bound) ? 0 : 1;     // (kth == -inf, fewer than k_out candidates, passes only when whole)
-    status[qi] = st;
-    ws_thr[qi] = kth - eps;
-    ws_cnt[qi] = 0;
-    if (qi == 0) *ws_done = 0;        // the escalation kernel's "blocks through" counter
+    cert_publish(qi, st, kth, eps, status, ws.thr, ws.cnt, ws.done);
   }
 }
 
@@ -156,12 +120,11 @@ int large_k_max_parts() { return kLkMaxCand / kLkSlots; }
 
 int large_cert_launch(const float* q32, const _Float16* q16, int nq, int dim, int pdim, int slab_type, const float* shadow, int64_t n_rows,
                       int64_t id_base, const int64_t* cand, const float* cand_s, int parts, int64_t chunk_rows, int k_out, float err_rows,
-                      float* out_s, int64_t* out_i, int* status, float* ws_thr, int* ws_cnt, int* ws_done, hipStream_t stream) {
+                      float* out_s, int64_t* out_i, int* status, const ExactWs& ws, hipStream_t stream) {
   if (nq <= 0) return 0;
   if (parts <= 0 || parts > large_k_max_parts()) return -1;
   hipLaunchKernelGGL(large_cert_kernel, dim3(nq), dim3(kLkThreads), 0, stream, q32, q16, nq, dim, pdim, slab_type == 1 ? 1 : 0, shadow, n_rows,
-                     id_base, cand, cand_s, parts, chunk_rows, k_out, err_rows, exact_err_arith(dim, pdim), out_s, out_i, status, ws_thr,
-                     ws_cnt, ws_done);
+                     id_base, cand, cand_s, parts, chunk_rows, k_out, err_rows, exact_err_arith(dim, pdim), out_s, out_i, status, ws);
   return (int)hipGetLastError();
 }
 

@@ -10,27 +10,22 @@
 //   1. every thread streams its strided share and keeps its best score ("bucket maximum");
 //   2. the k-th largest of the 256 bucket maxima is a lower bound tau on the true k-th best
 //      (those k maxima are k distinct candidates).  It is found without atomics: a 64-lane
-//      bitonic sort per wave (shuffles), then three "top-64 of two sorted lists" merges via LDS;
+//      bitonic sort per wave (shuffles), then three "top-64 of two sorted lists" merges (top64_of_sorted);
 //   3. candidates with score >= tau (typically k .. 2k of them) are appended to an LDS list;
 //   4. each candidate's rank among the list = its output slot (order: score desc, id asc).
 // If the list overflows (only when thousands of candidates tie), the kernel falls back to
 // k_out rounds of workgroup-wide arg-max, which is slow but exact for any input.
+// The steps are tail_steps.h's (the fused tail, finish.hip, runs the same ones); this kernel adds the global-memory walk for
+// lists that are not contiguous or too long for the registers.
 
 #include "scan.h"
-#include "wave_sort.h"
+#include "tail_steps.h"
 
 namespace crs {
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kCap = 1024;  // LDS candidate list capacity
-constexpr float kNegInf = -__builtin_huge_valf();
-
-template <typename IdT>
-__device__ __forceinline__ bool better(float s, IdT id, float s2, IdT id2) {
-  return s > s2 || (s == s2 && id < id2);
-}
-
 // REGE: candidates a thread keeps in registers on the single-pass path (32: 8192 per workgroup, 173 VGPRs; 64: 16384, 244 VGPRs)
 template <typename IdT, int REGE = 32>
 __global__ __launch_bounds__(kThreads) void merge_kernel(const float* __restrict__ scores,
@@ -39,7 +34,7 @@ __global__ __launch_bounds__(kThreads) void merge_kernel(const float* __restrict
                                                         size_t id_list_stride, size_t q_stride, int64_t id_base,
                                                         float* __restrict__ out_s,
                                                         int64_t* __restrict__ out_i, int lists_per_slice) {
-  __shared__ float sh_sorted[4][64];
+  __shared__ float sh_sorted[1][kThreads / 64][64];
   __shared__ float sh_cs[kCap];
   __shared__ IdT sh_ci[kCap];
   __shared__ int sh_cnt;
@@ -55,39 +50,20 @@ __global__ __launch_bounds__(kThreads) void merge_kernel(const float* __restrict
   nlists = (nlists - first_list < lists_per_slice) ? nlists - first_list : lists_per_slice;
   scores += (size_t)first_list * list_stride;
   ids += (size_t)first_list * id_list_stride;
-  const int m = nlists * k_in;
   // candidate e = (list e / k_in, slot e % k_in) lives at list*list_stride + q*q_stride + slot
   // (== e when a query's lists are contiguous).  Threads walk the entries in passes (below), eight passes at a
   // time with all loads issued before any use, so L2 latency is paid once per batch of 8.
   const float* qs = scores + (size_t)q * q_stride;
   const IdT* qi = ids + (size_t)q * q_stride;
   const bool contig = (list_stride == (size_t)k_in) && (id_list_stride == (size_t)k_in);
-  // Which entry a thread visits in pass p.  Plain striding (entry = tid + 256 p) gives thread t the SAME slot t % k_in of
-  // every list whenever k_in divides 256 (a few slots when it shares a factor) -- and the lists arrive sorted, so a few
-  // threads own every list's best entries, the k-th largest "bucket maximum" below is then the maximum of a bucket of
-  // 4th-best entries, far too low a bar, the LDS list overflows and the exact-but-slow fallback runs (k = 32 over 512
-  // lists: 210-250 us instead of ~ 15).  So a pass covers WHOLE lists (C = the largest multiple of k_in <= 256 entries;
-  // threads >= C sit the pass out) and the slot is rotated by the pass number -- a bijection inside each list: every
-  // thread meets all slots in turn.
-  const bool rotate = k_in > 1 && k_in <= kThreads;
-  const int C = rotate ? (kThreads / k_in) * k_in : kThreads;          // entries per pass
-  // A pass advances a thread by C / k_in whole lists, so (list, slot) need ONE division per thread, not two per entry
-  // (k_in is a run-time value: at 123 slots per list the divisions were most of a 31 488-candidate merge, 53 us)
-  const int lpp = rotate ? kThreads / k_in : 0;                          // lists per pass
-  const int list0 = rotate ? tid / k_in : 0, slot0 = rotate ? tid - list0 * k_in : 0;
-  auto entry_at = [&](int p, int slot) {                                 // slot = (slot0 + p) % k_in, kept by the caller
-    if (tid >= C) return -1;
-    const int e = rotate ? (list0 + p * lpp) * k_in + slot : p * kThreads + tid;
-    return e < m && (!rotate || list0 + p * lpp < nlists) ? e : -1;
-  };
-  const int n_pass = (m + C - 1) / C;
+  const MergePasses<kThreads> g(tid, nlists, k_in);   // which entry a thread visits in pass p: whole lists per pass, rotating slot
 #define CRS_FOR_EACH_ENTRY(BODY)                                                         \
-  for (int p0 = 0, sl_ = slot0; p0 < n_pass; p0 += 8) {                                  \
+  for (int p0 = 0, sl_ = g.slot0; p0 < g.n_pass; p0 += 8) {                              \
     float s_[8];                                                                         \
     IdT id_[8];                                                                          \
     _Pragma("unroll") for (int u = 0; u < 8; ++u) {                                      \
-      const int e = (p0 + u < n_pass) ? entry_at(p0 + u, sl_) : -1;                      \
-      sl_ = (sl_ + 1 == k_in) ? 0 : sl_ + 1;                                             \
+      const int e = (p0 + u < g.n_pass) ? g.entry_at(p0 + u, sl_) : -1;                  \
+      sl_ = g.next_slot(sl_);                                                            \
       const bool in = e >= 0;                                                            \
       size_t at = 0, ati = 0;                                                            \
       if (in) {                                                                          \
@@ -113,66 +89,31 @@ __global__ __launch_bounds__(kThreads) void merge_kernel(const float* __restrict
   // pulls its <= 64 strided candidates into registers with all loads in flight at once, so the
   // candidate set crosses the memory system exactly once (the generic path below walks it twice in
   // batches of 8 and was bound by those serial round trips).
-  constexpr int kRegE = REGE;
-  const bool cached = contig && n_pass <= kRegE;
-  float cs[kRegE];
-  IdT ci[kRegE];
+  const bool cached = contig && g.n_pass <= REGE;
+  float cs[REGE];
+  IdT ci[REGE];
   float best = kNegInf;
   if (cached) {
-    int sl = slot0;
-#pragma unroll
-    for (int u = 0; u < kRegE; ++u) {
-      const int e = (u < n_pass) ? entry_at(u, sl) : -1;
-      sl = (sl + 1 == k_in) ? 0 : sl + 1;
-      cs[u] = e >= 0 ? qs[e] : kNegInf;
-      ci[u] = e >= 0 ? qi[e] : (IdT)-1;
-    }
-#pragma unroll
-    for (int u = 0; u < kRegE; ++u) best = fmaxf(best, (ci[u] >= 0) ? cs[u] : kNegInf);
+    best = merge_load_entries<REGE>(g, qs, qi, cs, ci);
   } else {
     // 1. bucket maxima
     CRS_FOR_EACH_ENTRY({ best = fmaxf(best, (id >= 0) ? s : kNegInf); })
   }
   // 2. k-th largest of the 256 maxima (k_out <= 64)
-  const float sorted = wave_sort_desc(best, lane);
-  sh_sorted[wave][lane] = sorted;
-  __syncthreads();
-  float a = fmaxf(sh_sorted[0][lane], sh_sorted[1][63 - lane]);
-  float b = fmaxf(sh_sorted[2][lane], sh_sorted[3][63 - lane]);
-  a = wave_clean_desc(a, lane);
-  b = wave_clean_desc(b, lane);
-  float t = fmaxf(a, __shfl(b, 63 - lane));
-  t = wave_clean_desc(t, lane);  // top-64 of all maxima, identical in every wave
-  const float tau = __shfl(t, k_out - 1);
+  const float tau = __shfl(top64_of_sorted<kThreads / 64>(sh_sorted, wave_sort_desc(best, lane), wave, lane), k_out - 1);
 
   // 3. candidates >= tau
   if (cached) {
 #pragma unroll
-    for (int u = 0; u < kRegE; ++u) {
-      if (ci[u] >= 0 && cs[u] >= tau) {
-        const int p = atomicAdd(&sh_cnt, 1);
-        if (p < kCap) { sh_cs[p] = cs[u]; sh_ci[p] = ci[u]; }
-      }
-    }
+    for (int u = 0; u < REGE; ++u) merge_append(cs[u], ci[u], tau, &sh_cnt, kCap, sh_cs, sh_ci);
   } else {
-    CRS_FOR_EACH_ENTRY({
-      if (id >= 0 && s >= tau) {
-        const int p = atomicAdd(&sh_cnt, 1);
-        if (p < kCap) { sh_cs[p] = s; sh_ci[p] = id; }
-      }
-    })
+    CRS_FOR_EACH_ENTRY({ merge_append(s, id, tau, &sh_cnt, kCap, sh_cs, sh_ci); })
   }
   __syncthreads();
   const int cnt = sh_cnt;
   if (cnt <= kCap) {
     // 4. rank = output slot
-    for (int c = tid; c < cnt; c += kThreads) {
-      const float s = sh_cs[c];
-      const IdT id = sh_ci[c];
-      int rank = 0;
-      for (int o = 0; o < cnt; ++o) rank += better<IdT>(sh_cs[o], sh_ci[o], s, id) ? 1 : 0;
-      if (rank < k_out) { os[rank] = s; oi[rank] = (int64_t)id + id_base; }
-    }
+    rank_by_count<kThreads>(sh_cs, sh_ci, cnt, k_out, tid, [&](int rank, float s, IdT id) { os[rank] = s; oi[rank] = (int64_t)id + id_base; });
     return;
   }
 
@@ -183,29 +124,9 @@ __global__ __launch_bounds__(kThreads) void merge_kernel(const float* __restrict
     float bs = kNegInf;
     IdT bi = (IdT)-1;
     CRS_FOR_EACH_ENTRY({
-      const bool after = (s < last_s) || (s == last_s && id > last_i);
-      if (id >= 0 && after && (bi < 0 || better<IdT>(s, id, bs, bi))) { bs = s; bi = id; }
+      if (argmax_after(s, id, last_s, last_i) && argmax_take(s, id, bs, bi)) { bs = s; bi = id; }
     })
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const float os2 = __shfl_xor(bs, off);
-      const IdT oi2 = __shfl_xor(bi, off);
-      const bool take = (oi2 >= 0) && (bi < 0 || better<IdT>(os2, oi2, bs, bi));
-      bs = take ? os2 : bs;
-      bi = take ? oi2 : bi;
-    }
-    const int pp = r & 1;
-    if (lane == 0) { sh_rs[pp][wave] = bs; sh_ri[pp][wave] = bi; }
-    __syncthreads();
-    bs = sh_rs[pp][0]; bi = sh_ri[pp][0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) {
-      const float os2 = sh_rs[pp][w];
-      const IdT oi2 = sh_ri[pp][w];
-      const bool take = (oi2 >= 0) && (bi < 0 || better<IdT>(os2, oi2, bs, bi));
-      bs = take ? os2 : bs;
-      bi = take ? oi2 : bi;
-    }
+    wg_argmax<kThreads / 64>(bs, bi, r, sh_rs, sh_ri, wave, lane);
     if (bi < 0) break;  // exhausted (uniform); the tail already holds (-inf, -1)
     if (tid == 0) { os[r] = bs; oi[r] = (int64_t)bi + id_base; }
     last_s = bs; last_i = bi;

@@ -28,6 +28,15 @@ struct ScanArgs {
   int nt;                 // scan_tb.hip / scan_i8.hip: 1 = slab tiles streamed with the non-temporal policy (lds_dma16_nt)
 };
 
+// the exactness workspace of a batch (capi.hip carves it): per-query escalation threshold and row counter, the escalation
+// kernel's "blocks through" counter, and the per-query row lists [nq, cap]
+struct ExactWs {
+  float* thr;
+  int* cnt;
+  int* done;
+  int64_t* lists;
+};
+
 // scan_refine.hip: re-open the k winning tiles (16, 32 or 64 rows each) per query, re-score, rank
 int refine_launch(const _Float16* q16, int nq, int pdim, const _Float16* slab, int n_rows, const float* win_s,
                   const int64_t* win, int k, int tile_rows, int64_t id_base, float* out_s, int64_t* out_i, hipStream_t stream);
@@ -91,24 +100,23 @@ bool finish_fits(int nlists, int kp, int kc, int tile_rows, int pdim);
 int finish_cert_launch(const float* part_s, const int* part_r, int nlists, int kp, const _Float16* q16, int nq, int pdim,
                        const _Float16* slab, int n_rows, int tile_rows, const float* q32, int dim, const float* shadow, int64_t id_base,
                        int kc, int k_out, float err_rows, float* cand_s, int64_t* cand_i, float* out_s, int64_t* out_i, int* status,
-                       float* ws_thr, int* ws_cnt, int* ws_done, hipStream_t stream);
+                       const ExactWs& ws, hipStream_t stream);
 
 // exact.hip: exactness certificate of the over-fetch re-rank + in-stream escalation of uncertified queries
 float exact_err_arith(int dim, int pdim);
 float exact_err_rows_bound(int dim, int slab_type);
 int refine_cert_launch(const float* q32, const _Float16* q16, int nq, int dim, int pdim, int slab_type, const float* shadow,
                        int64_t n_rows, int64_t id_base, const int64_t* cand, const float* cand_s, int k_in, int k_out,
-                       float err_rows, float* out_s, int64_t* out_i, int* status, float* ws_thr, int* ws_cnt, int* ws_done, hipStream_t stream);
+                       float err_rows, float* out_s, int64_t* out_i, int* status, const ExactWs& ws, hipStream_t stream);
 int escalate_launch(const float* q32, const _Float16* q16, int nq, int dim, int pdim, int slab_type, const void* slab,
                     const float* scales, const float* shadow, int64_t n_rows, int64_t id_base, int k_out, float* out_s,
-                    int64_t* out_i, int* status, const float* ws_thr, int* ws_cnt, int* ws_done, int64_t* ws_lists, int cap, int cus,
-                    hipStream_t stream);
+                    int64_t* out_i, int* status, const ExactWs& ws, int cap, int cus, hipStream_t stream);
 
 // large_k.hip: fp32 re-rank + certificate of a partitioned over-fetch, cand / cand_s [parts, nq, 64] (k_out <= 4096 candidates);
 // -1 = parts out of 1..large_k_max_parts()
 int large_k_max_parts();
 int large_cert_launch(const float* q32, const _Float16* q16, int nq, int dim, int pdim, int slab_type, const float* shadow, int64_t n_rows,
                       int64_t id_base, const int64_t* cand, const float* cand_s, int parts, int64_t chunk_rows, int k_out, float err_rows,
-                      float* out_s, int64_t* out_i, int* status, float* ws_thr, int* ws_cnt, int* ws_done, hipStream_t stream);
+                      float* out_s, int64_t* out_i, int* status, const ExactWs& ws, hipStream_t stream);
 
 }  // namespace crs
