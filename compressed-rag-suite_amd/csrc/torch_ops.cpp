@@ -4,6 +4,8 @@
 // ops".  TORCH_LIBRARY(crs, ...) registers, for the HIP ("CUDA" dispatch key on torch-ROCm) backend:
 //   crs::encoder_forward   replaces SentenceTransformer.encode's forward      (reference rag/embedding.py:65-71)
 //   crs::slab_append       replaces collection.add(embeddings=...)            (reference rag/indexing.py:114-119)
+//   crs::slab_write_rows / crs::slab_compact   in-place update and delete of rows (csrc/mutate.hip; the reference's ChromaDB
+//                          collection offers update / delete, its own code never calls them)
 //   crs::queries_to_f16    query side of the same conversion                  (reference rag/indexing.py:156-168)
 //   crs::cosine_topk       replaces collection.query(query_embeddings, n)     (reference rag/indexing.py:171-176)
 //   crs::refine_f32        over-fetch re-rank against the fp32 shadow         
@@ -82,6 +84,56 @@ void slab_append(const Tensor& emb, Tensor slab, c10::optional<Tensor> scales, c
   c10::hip::HIPGuardMasqueradingAsCUDA g(emb.device());
   ok(crs_slab_append_f32(emb.data_ptr<float>(), n, dim, st, slab.data_ptr(), (float*)opt_ptr(scales), (float*)opt_ptr(shadow), row0,
                          (float*)opt_ptr(row_err), cur_stream(emb)), "crs::slab_append");
+}
+
+// ---- in-place mutation (csrc/mutate.hip) ------------------------------------------------------------------------
+void slab_write_rows(const Tensor& emb, const Tensor& rows, Tensor slab, c10::optional<Tensor> scales, c10::optional<Tensor> shadow,
+                     int64_t n_rows, c10::optional<Tensor> row_err) {
+  want(emb, at::kFloat, "emb");
+  want(rows, at::kLong, "rows");
+  same_device(emb, {&rows, &slab, opt_t(scales), opt_t(shadow), opt_t(row_err)}, "crs::slab_write_rows");
+  if (has(row_err)) { want(*row_err, at::kFloat, "row_err"); TORCH_CHECK(row_err->numel() >= 1, "row_err must hold one fp32"); }
+  TORCH_CHECK(emb.dim() == 2 && slab.dim() == 2 && slab.is_cuda() && slab.is_contiguous(), "emb [m, dim], slab [cap, pdim]");
+  TORCH_CHECK(rows.dim() == 1 && rows.size(0) == emb.size(0), "rows must be int64 [m]");
+  const int st = slab_type_of(slab);
+  const int dim = (int)emb.size(1);
+  TORCH_CHECK(slab.size(1) == crs_row_elems(dim, st), "slab row length must be crs_row_elems(dim, slab_type)");
+  TORCH_CHECK(n_rows >= 0 && n_rows <= slab.size(0), "n_rows exceeds the slab");
+  if (st == CRS_SLAB_I8) {
+    TORCH_CHECK(has(scales), "int8 slab needs scales");
+    want(*scales, at::kFloat, "scales");
+    TORCH_CHECK(scales->numel() >= n_rows, "scales too short");
+  }
+  if (has(shadow)) {
+    want(*shadow, at::kFloat, "shadow");
+    TORCH_CHECK(shadow->dim() == 2 && shadow->size(1) == dim && shadow->size(0) >= n_rows, "shadow must be fp32 [>= n_rows, dim]");
+  }
+  c10::hip::HIPGuardMasqueradingAsCUDA g(emb.device());
+  ok(crs_slab_write_rows_f32(emb.data_ptr<float>(), rows.data_ptr<int64_t>(), emb.size(0), dim, st, slab.data_ptr(), (float*)opt_ptr(scales),
+                             (float*)opt_ptr(shadow), n_rows, (float*)opt_ptr(row_err), cur_stream(emb)), "crs::slab_write_rows");
+}
+
+void slab_compact(const Tensor& dead, int64_t n_rows, Tensor slab, c10::optional<Tensor> scales, c10::optional<Tensor> shadow,
+                  c10::optional<Tensor> rows_global, Tensor bounce, int64_t first_row) {
+  want(dead, at::kLong, "dead");
+  want(bounce, at::kByte, "bounce");
+  same_device(dead, {&slab, opt_t(scales), opt_t(shadow), opt_t(rows_global), &bounce}, "crs::slab_compact");
+  TORCH_CHECK(dead.dim() == 1 && slab.dim() == 2 && slab.is_cuda() && slab.is_contiguous(), "dead [m], slab [cap, pdim]");
+  const int st = slab_type_of(slab);
+  TORCH_CHECK(n_rows >= 0 && n_rows <= slab.size(0) && dead.size(0) <= n_rows, "n_rows exceeds the slab, or more dead rows than rows");
+  int dim = (int)slab.size(1);        // without a shadow only the padded row length matters
+  if (has(shadow)) {
+    want(*shadow, at::kFloat, "shadow");
+    TORCH_CHECK(shadow->dim() == 2 && shadow->size(0) >= n_rows, "shadow must be fp32 [>= n_rows, dim]");
+    dim = (int)shadow->size(1);
+  }
+  TORCH_CHECK(slab.size(1) == crs_row_elems(dim, st), "slab row length must be crs_row_elems(dim, slab_type)");
+  if (has(scales)) { want(*scales, at::kFloat, "scales"); TORCH_CHECK(scales->numel() >= n_rows, "scales too short"); }
+  if (has(rows_global)) { want(*rows_global, at::kLong, "rows_global"); TORCH_CHECK(rows_global->numel() >= n_rows, "rows_global too short"); }
+  c10::hip::HIPGuardMasqueradingAsCUDA g(dead.device());
+  ok(crs_slab_compact(dead.data_ptr<int64_t>(), dead.size(0), n_rows, first_row, dim, st, slab.data_ptr(), (float*)opt_ptr(scales),
+                      (float*)opt_ptr(shadow), (int64_t*)opt_ptr(rows_global), bounce.data_ptr(), (size_t)bounce.nbytes(), cur_stream(dead)),
+     "crs::slab_compact");
 }
 
 void queries_to_f16(const Tensor& q32, Tensor out16, int64_t slab_type) {
@@ -415,6 +467,9 @@ void encoder_forward(const Tensor& ids, const Tensor& lens, at::TensorList weigh
 
 TORCH_LIBRARY(crs, m) {
   m.def("slab_append(Tensor emb, Tensor(a!) slab, Tensor(b!)? scales, Tensor(c!)? shadow, int row0, Tensor(d!)? row_err=None) -> ()");
+  m.def("slab_write_rows(Tensor emb, Tensor rows, Tensor(a!) slab, Tensor(b!)? scales, Tensor(c!)? shadow, int n_rows, Tensor(d!)? row_err=None) -> ()");
+  m.def("slab_compact(Tensor dead, int n_rows, Tensor(a!) slab, Tensor(b!)? scales, Tensor(c!)? shadow, Tensor(d!)? rows_global, "
+        "Tensor(e!) bounce, int first_row=0) -> ()");
   m.def("queries_to_f16(Tensor q32, Tensor(a!) out16, int slab_type) -> ()");
   m.def("cosine_topk(Tensor q16, Tensor slab, Tensor? scales, int n_rows, int dim, int k, int id_base) -> (Tensor, Tensor)");
   m.def("cosine_topk_out(Tensor q16, Tensor slab, Tensor? scales, int n_rows, int dim, int k, int id_base, Tensor(a!) workspace, "
@@ -445,6 +500,8 @@ TORCH_LIBRARY(crs, m) {
 
 TORCH_LIBRARY_IMPL(crs, CUDA, m) {   // the HIP backend of torch-ROCm dispatches under the "CUDA" key
   m.impl("slab_append", &slab_append);
+  m.impl("slab_write_rows", &slab_write_rows);
+  m.impl("slab_compact", &slab_compact);
   m.impl("queries_to_f16", &queries_to_f16);
   m.impl("cosine_topk", &cosine_topk);
   m.impl("cosine_topk_out", &cosine_topk_out);

@@ -33,6 +33,12 @@ _SIGNATURES = {
     "crs_row_elems": (c_int, [c_int, c_int]),
     "crs_slab_append_f32": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                     c_int64, c_void_p, c_void_p]),
+    "crs_slab_write_rows_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                        c_void_p]),
+    "crs_slab_compact_bounce_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "crs_slab_compact_window_rows": (c_int64, [c_int, c_int, c_int, c_size_t]),
+    "crs_slab_compact": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_size_t, c_void_p]),
     "crs_queries_to_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "crs_scan_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int64, POINTER(c_size_t)]),
     "crs_cosine_topk": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int,
@@ -172,6 +178,51 @@ def slab_append_f32(emb, slab, row0: int, slab_type: int, scales=None, shadow=No
         return
     with _translate():
         ops().slab_append(emb, slab, scales, shadow, int(row0), row_err)
+
+
+def slab_write_rows_f32(emb, rows, slab, n_rows: int, scales=None, shadow=None, row_err=None) -> None:
+    """The scatter form of slab_append_f32: emb cuda fp32 [m, dim] -> rows `rows` (cuda int64 [m], distinct, < n_rows) of slab /
+    scales / shadow, through the same per-row device function as the append (same bits); row_err raised likewise."""
+    if emb.shape[0] == 0:
+        return
+    with _translate():
+        ops().slab_write_rows(emb, rows, slab, scales, shadow, int(n_rows), row_err)
+
+
+COMPACT_BOUNCE_MAX = 256 << 20     # the bounce buffer VectorStore.delete allocates at most (and frees after the call)
+
+
+def slab_compact_bounce_bytes(dim: int, slab_type: int, has_shadow: bool) -> int:
+    """Smallest legal bounce buffer of slab_compact: one window of 1024 rows of every array."""
+    return int(load().crs_slab_compact_bounce_bytes(int(dim), int(slab_type), int(bool(has_shadow))))
+
+
+def slab_compact_window_rows(dim: int, slab_type: int, has_shadow: bool, bounce_bytes: int) -> int:
+    """Rows per window of slab_compact for a bounce size (0: too small)."""
+    return int(load().crs_slab_compact_window_rows(int(dim), int(slab_type), int(bool(has_shadow)), int(bounce_bytes)))
+
+
+def compact_bounce_size(n_rows: int, dim: int, slab_type: int, has_shadow: bool) -> int:
+    """min(COMPACT_BOUNCE_MAX, one window over all n_rows rows), never below the legal minimum.  Host arithmetic."""
+    least = slab_compact_bounce_bytes(dim, slab_type, has_shadow)
+    per_row = (least - 4 * 256 - 16) // 1024
+    whole = (-(-int(n_rows) // 32) * 32) * per_row + 4 * 256 + 16
+    return max(least, min(COMPACT_BOUNCE_MAX, whole))
+
+
+def slab_compact(dead, n_rows: int, slab, scales=None, shadow=None, rows_global=None, bounce=None, first_row: int = 0) -> None:
+    """Remove the rows `dead` (cuda int64, strictly ascending, < n_rows) from slab / scales / shadow / rows_global in place,
+    keeping the order of the others (crs_slab_compact): rows [0, n_rows - len(dead)) hold the survivors afterwards.  No
+    allocation beside the bounce buffer (made here, and dropped on return, when none is passed); no host sync."""
+    import torch
+    if dead.numel() == 0:
+        return
+    if bounce is None:
+        dim = shadow.shape[1] if shadow is not None else slab.shape[1]
+        st = SLAB_I8 if slab.dtype == torch.int8 else SLAB_F16
+        bounce = torch.empty(compact_bounce_size(n_rows, dim, st, shadow is not None), dtype=torch.uint8, device=slab.device)
+    with _translate():
+        ops().slab_compact(dead, int(n_rows), slab, scales, shadow, rows_global, bounce, int(first_row))
 
 
 def queries_to_f16(q32, slab_type: int = SLAB_F16, out=None):

@@ -28,6 +28,21 @@ New, additive surface (all keys absent from the reference config.json default so
                               copied to the first device and merged there -- RAGPipeline stays one object
   ``sharded``                 SPMD (one process per GPU, torch.distributed): each rank keeps a row shard; ONE RCCL
                               all-gather of the per-shard wire blocks + merge on every rank
+  ``delete`` / ``update`` / ``upsert``   change ONE document without re-indexing (a ChromaDB collection offers the three; the
+                              reference never calls them, so the semantics are this module's):
+                                delete(ids, where, where_document) -> rows removed: rows whose id is in ``ids`` AND that pass the
+                                  filters; unknown ids ignored, an id several rows carry removes them all.  The shard's arrays
+                                  are compacted IN PLACE and in order on the device (crs::slab_compact: a bounce buffer of at
+                                  most 256 MB, no second copy, same data_ptr and capacity), so the store afterwards is, row for
+                                  row, the store a fresh index of the survivors would be -- search results are bit-identical
+                                update(ids, embeddings, documents, metadatas): per id, replace what is given (crs::slab_write_rows:
+                                  the append's per-row function, same bits as an append); the metadata dict is replaced WHOLE,
+                                  not merged key by key as ChromaDB does.  Unknown / ambiguous / repeated ids raise ValueError
+                                  before anything changes
+                                upsert(chunks, embeddings, metadata_fields): create_index's signature; known chunk ids are
+                                  updated in place, the others appended in their given order
+                              ``mutation_epoch`` counts the calls that changed something.  With persist_directory each such call
+                              rewrites the files as a new generation (O(index) disk I/O: batch ids into one call)
 ``where`` / ``where_document`` filters work on every layout (the sidecars are replicated; each shard scans the
 allowed rows it owns).  ``top_k`` is unlimited as in the reference: up to 1024 a refined shard is over-fetched by
 partition (64 candidates from each of up to 64 row chunks, crs::cosine_topk_large_cert) and certified like top_k <= 64;
@@ -148,6 +163,30 @@ class _Shard:
         return self._workspace
 
 
+def survivor_rows(n: int, dead) -> np.ndarray:
+    """Stable compaction restated on the host: the source row of every destination row after the sorted rows `dead` left
+    [0, n) -- what crs::slab_compact computes per row (source = destination + dead rows below the source)."""
+    keep = np.ones(int(n), dtype=bool)
+    keep[np.asarray(dead, dtype=np.int64)] = False
+    return np.flatnonzero(keep).astype(np.int64)
+
+
+def renumber_rows(rows, dead) -> np.ndarray:
+    """Sidecar rows after the sorted sidecar rows `dead` were removed: new = old - number of dead rows below it (rows must
+    not be dead themselves).  The device does the same with one torch.searchsorted per shard."""
+    rows = np.asarray(rows, dtype=np.int64)
+    return rows - np.searchsorted(np.asarray(dead, dtype=np.int64), rows, side="left")
+
+
+def compact_windows(n_rows: int, m: int, window_rows: int, first_row: int = 0):
+    """The destination windows [d0, d0 + w) crs::slab_compact walks for n_rows rows, m of them dead, W rows per window and the
+    first dead row at or above first_row: whole multiples of W from the window holding first_row up to the n_rows - m survivors."""
+    n_out, W = int(n_rows) - int(m), int(window_rows)
+    if m <= 0 or n_out <= 0 or W <= 0:
+        return []
+    return [(d0, min(W, n_out - d0)) for d0 in range(int(first_row) // W * W, n_out, W)]
+
+
 class SlabCollection:
     """What ``VectorStore.collection`` exposes (the retriever reads ``.metadata`` and the harness ``.count()``,
     reference rag/retrieval.py:48-50).  Owns the per-device shards and the host sidecars."""
@@ -197,6 +236,41 @@ class SlabCollection:
 
     def count(self) -> int:
         return len(self.ids)
+
+    # -- one-document mutation, for callers who hold the collection as they would a ChromaDB one (VectorStore does the work)
+    def _store(self):
+        owner = self.__dict__.get("_owner")
+        store = owner() if owner is not None else None
+        if store is None or store.collection is not self:
+            raise ValueError("this collection is no longer attached to a VectorStore")
+        return store
+
+    def delete(self, ids=None, where=None, where_document=None) -> int:
+        return self._store().delete(ids=ids, where=where, where_document=where_document)
+
+    def update(self, ids, embeddings=None, documents=None, metadatas=None) -> None:
+        return self._store().update(ids, embeddings=embeddings, documents=documents, metadatas=metadatas)
+
+    def upsert(self, chunks, embeddings, metadata_fields=None) -> None:
+        return self._store().upsert(chunks, embeddings, metadata_fields=metadata_fields)
+
+    def _id_rows(self):
+        """id -> sidecar rows (a list: create_index accepts duplicate ids), built once and extended as rows arrive like
+        _inverted; dropped by a delete (every row number above the first deleted row changes)."""
+        idmap = self.__dict__.setdefault("_idmap", {})
+        done = self.__dict__.get("_idmap_rows", 0)
+        for row in range(done, len(self.ids)):
+            idmap.setdefault(self.ids[row], []).append(row)
+        self.__dict__["_idmap_rows"] = len(self.ids)
+        return idmap
+
+    def _drop_derived(self, ids_changed: bool):
+        """Forget what was derived from the sidecars: the inverted metadata index, and (rows renumbered) the id map."""
+        self.__dict__.pop("_inv", None)
+        self.__dict__.pop("_inv_rows", None)
+        if ids_changed:
+            self.__dict__.pop("_idmap", None)
+            self.__dict__.pop("_idmap_rows", None)
 
     # -- metadata filters: value -> rows, built once and extended as rows arrive (the per-query loop over all metadatas is gone)
     def _inverted(self):
@@ -322,6 +396,9 @@ class VectorStore:
         self._filters = {}      # filter key -> {"n": rows when built, "rows": allowed sidecar rows, "shards": {g: compacted sub-slab}}
         self._persisted_rows = None   # rows the append-only files hold (None: nothing / legacy format on disk)
         self._docs_bytes = 0          # length of the sidecar file the header vouches for
+        self._gen = None              # generation of the files the header names (None: the un-suffixed names)
+        self._gen_pending = False     # a generation rewrite failed: the memory is ahead of the files, the next persist rewrites
+        self.mutation_epoch = 0       # +1 per delete / update / upsert that changed something
         self.client = self  # the reference keeps a chromadb client here; nothing else reads it
         self.collection: Optional[SlabCollection] = None
         self._wire = {}     # (nq, k) -> WireBlock (SPMD exchange buffers)
@@ -350,7 +427,12 @@ class VectorStore:
         return dist if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 else None
 
     def _new_collection(self) -> SlabCollection:
-        return SlabCollection(self.collection_name, self.index_dtype, self.refine_fp32, self._torch_devices())
+        return self._adopt(SlabCollection(self.collection_name, self.index_dtype, self.refine_fp32, self._torch_devices()))
+
+    def _adopt(self, col: SlabCollection) -> SlabCollection:
+        import weakref
+        col._owner = weakref.ref(self)        # collection.delete / update / upsert delegate to this store
+        return col
 
     # -- persistence (the PersistentClient analogue, reference rag/indexing.py:32-34): APPEND-ONLY files, so that an add
     # costs O(batch), not O(index):
@@ -362,11 +444,31 @@ class VectorStore:
     # The header's n is the truth: bytes or lines past it (a crash between the appends and the header) are ignored and
     # overwritten by the next add; files SHORTER than the header says mean corruption and raise.  The round-2 format
     # (<name>.slab.npz + <name>.docs.json, rewritten whole on every add) is still read.
-    def _persist_paths(self):
+    # GENERATIONS: delete / update / upsert change rows the files already hold, so they write the complete new set under new
+    # names -- <name>.g<G>.slab.bin, .scales.bin, .shadow.bin, .docs.jsonl, each fsynced -- THEN replace the header (which
+    # carries "gen": G), THEN remove the previous generation.  A crash before the header's rename leaves the old header and the
+    # old files untouched: the store re-opens as it was before the call.  A header without "gen" names the un-suffixed files.
+    # Appends continue into the current generation's files.  Cost: O(index) disk I/O per mutating call.
+    _GEN_KEYS = ("slab", "scales", "shadow", "docs")
+
+    def _persist_paths(self, gen="current"):
         base = os.path.join(self.persist_directory, self.collection_name)
-        return {k: base + ext for k, ext in (("meta", ".meta.json"), ("slab", ".slab.bin"), ("scales", ".scales.bin"),
-                                             ("shadow", ".shadow.bin"), ("docs", ".docs.jsonl"),
-                                             ("legacy_slab", ".slab.npz"), ("legacy_docs", ".docs.json"))}
+        gen = self._gen if gen == "current" else gen
+        sfx = f".g{int(gen)}" if gen else ""
+        out = {k: base + ext for k, ext in (("meta", ".meta.json"), ("legacy_slab", ".slab.npz"), ("legacy_docs", ".docs.json"))}
+        out.update({k: base + sfx + ext for k, ext in (("slab", ".slab.bin"), ("scales", ".scales.bin"),
+                                                       ("shadow", ".shadow.bin"), ("docs", ".docs.jsonl"))})
+        return out
+
+    def _remove_other_generations(self, keep):
+        """Remove the data files of every generation but `keep` (None: the un-suffixed names): the previous one, and whatever a
+        crashed rewrite left behind."""
+        import re
+        pat = re.compile(re.escape(self.collection_name) + r"(?:\.g(\d+))?\.(?:slab\.bin|scales\.bin|shadow\.bin|docs\.jsonl)$")
+        for name in os.listdir(self.persist_directory):
+            hit = pat.fullmatch(name)
+            if hit and (int(hit.group(1)) if hit.group(1) else None) != (int(keep) if keep else None):
+                os.remove(os.path.join(self.persist_directory, name))
 
     def _load_rows_into(self, col, n, dim, rows, refine, row_err):
         import torch
@@ -409,6 +511,8 @@ class VectorStore:
             else:
                 with open(paths["meta"]) as fh:
                     meta = json.load(fh)
+                self._gen = int(meta["gen"]) if meta.get("gen") else None
+                paths = self._persist_paths()
                 n, dim, pdim, dtype = int(meta["n"]), int(meta["dim"]), int(meta["pdim"]), str(meta["index_dtype"])
                 elem = np.int8 if dtype == "int8" else np.float16
 
@@ -440,7 +544,7 @@ class VectorStore:
         refine = self.refine_fp32 and rows["shadow"] is not None
         if self.refine_fp32 and not refine:
             logger.warning("persisted collection has no fp32 shadow; refine_fp32 disabled")
-        col = SlabCollection(self.collection_name, dtype, refine, self._torch_devices())
+        col = self._adopt(SlabCollection(self.collection_name, dtype, refine, self._torch_devices()))
         # the certificate's row term: the persisted maximum, or the analytic worst case for files written before it existed
         if row_err is None:
             row_err = nat.exact_row_error_bound(dim, nat.SLAB_I8 if dtype == "int8" else nat.SLAB_F16)
@@ -452,17 +556,24 @@ class VectorStore:
         self._persisted_rows = n if (not legacy and bool(meta.get("shadow")) == bool(refine)) else None
         logger.info(f"Loaded existing collection: {self.collection_name} ({col.count()} rows)")
 
-    def persist(self, first_new_row: Optional[int] = None):
+    def persist(self, first_new_row: Optional[int] = None, generation: bool = False):
         """Bring the files under persist_directory up to date.  With first_new_row = the files' row count, only rows
-        [first_new_row, n) are APPENDED (create_index does this: O(batch)); otherwise everything is rewritten."""
+        [first_new_row, n) are APPENDED (create_index does this: O(batch)); otherwise everything is rewritten.
+        generation=True (delete / update / upsert): everything is written as a NEW generation of files and the header switched
+        to it last, so a crash leaves the previous state readable (see the comment above _persist_paths)."""
         if not self.persist_directory or self.collection is None:
             return
         import torch
         os.makedirs(self.persist_directory, exist_ok=True)
         col = self.collection
-        paths = self._persist_paths()
+        generation = generation or self._gen_pending
+        new_gen = (self._gen or 0) + 1 if generation else self._gen
+        paths = self._persist_paths(new_gen)
         n = col.count()
-        append = first_new_row is not None and self._persisted_rows == first_new_row and first_new_row <= n
+        append = (not generation and first_new_row is not None and self._persisted_rows == first_new_row and first_new_row <= n)
+        if generation:
+            self._gen_pending = True        # until the header names the new files
+            self._persisted_rows = None
         lo = first_new_row if append else 0
         pdim, dim = col.pdim, col.dim
         elem = 1 if col.slab_type == nat.SLAB_I8 else 2
@@ -505,15 +616,22 @@ class VectorStore:
                 fh.write((json.dumps({"id": col.ids[r], "document": col.documents[r], "metadata": col.metadatas[r]}) + "\n").encode("utf-8"))
             fh.flush()
             os.fsync(fh.fileno())
-            self._docs_bytes = fh.tell()
+            docs_bytes = fh.tell()
+        if not generation:
+            self._docs_bytes = docs_bytes
         meta = {"format": 2, "n": n, "dim": dim, "pdim": pdim, "index_dtype": col.index_dtype, "shadow": bool(col.refine_fp32),
-                "row_err_max": max(sh.row_err_max() for sh in col.shards), "docs_bytes": self._docs_bytes}
+                "row_err_max": max(sh.row_err_max() for sh in col.shards), "docs_bytes": docs_bytes}
+        if new_gen:
+            meta["gen"] = int(new_gen)
         tmp = paths["meta"] + ".tmp"
         with open(tmp, "w") as fh:
             json.dump(meta, fh)
             fh.flush()
             os.fsync(fh.fileno())
         os.replace(tmp, paths["meta"])
+        if generation:                                   # the header names the new files: they are the store now
+            self._gen, self._docs_bytes, self._gen_pending = new_gen, docs_bytes, False
+            self._remove_other_generations(new_gen)
         for key in ("legacy_slab", "legacy_docs"):       # superseded
             if os.path.exists(paths[key]):
                 os.remove(paths[key])
@@ -570,6 +688,195 @@ class VectorStore:
         except Exception as e:
             logger.error(f"Failed to add documents to collection: {e}")
             raise
+
+    # -- one-document mutation (module docstring: delete / update / upsert) -------------------------------------
+    @staticmethod
+    def _as_f32(embeddings):
+        import torch
+        if isinstance(embeddings, torch.Tensor):
+            return embeddings.to(dtype=torch.float32)
+        return torch.from_numpy(np.ascontiguousarray(embeddings, dtype=np.float32))
+
+    def _mutated(self, ids_changed: bool, sidecars_changed: bool = True):
+        """Everything derived from rows dies: filter sub-slabs (keyed by row COUNT only: an update, or a delete followed by an
+        equal add, would serve a stale one), the inverted metadata index, the id map (delete), the SPMD wire blocks, the cached
+        row error.  mutation_epoch tells the retriever's engine (graphs captured with the old row error) to rebuild."""
+        self._filters = {}
+        self._wire = {}
+        if sidecars_changed or ids_changed:
+            self.collection._drop_derived(ids_changed)
+        for sh in self.collection.shards:
+            sh._row_err_host = None
+        self.mutation_epoch += 1
+        if self.persist_directory:
+            self.persist(generation=True)
+
+    @staticmethod
+    def _local_rows(sh: _Shard, g_rows):
+        """g_rows: ascending or arbitrary sidecar rows (int64 on the shard's device) -> (positions into g_rows of the rows this
+        shard owns, their local rows).  rows_global is ascending on every layout (appends only ever add larger rows)."""
+        import torch
+        if sh.n == 0 or g_rows.numel() == 0:
+            e = torch.zeros(0, dtype=torch.int64, device=sh.device)
+            return e, e
+        if sh.identity:
+            sel = (g_rows < sh.n).nonzero().flatten()
+            return sel, g_rows[sel]
+        rg = sh.rows_global[: sh.n]
+        pos = torch.searchsorted(rg, g_rows).clamp_(max=sh.n - 1)
+        sel = (rg[pos] == g_rows).nonzero().flatten()
+        return sel, pos[sel]
+
+    def delete(self, ids: Optional[Sequence[str]] = None, where: Optional[dict] = None,
+               where_document: Optional[dict] = None) -> int:
+        """Remove the rows whose id is in `ids` AND that pass the filters (either part may be absent, not all three).  Unknown
+        ids are ignored; an id that several rows carry removes all of them.  Returns the number of rows removed; 0 touches
+        nothing.  The device arrays are compacted in place and in order (same capacity, same data_ptr): the store is then, row
+        for row, what create_index of the survivors alone would have built, and searches return the same bits.  The tracked row
+        error is left as it is (an upper bound stays an upper bound).  SPMD: the same call on every rank."""
+        if ids is None and not where and not where_document:
+            raise ValueError("delete needs ids, where or where_document")
+        if self.collection is None:
+            raise ValueError("No collection available. Create index first.")
+        col = self.collection
+        rows = None
+        if ids is not None:
+            idmap = col._id_rows()
+            hit = [r for i in ([ids] if isinstance(ids, str) else ids) for r in idmap.get(i, ())]
+            rows = np.unique(np.asarray(hit, dtype=np.int64))
+        allowed = col.rows_matching(where, where_document)
+        if allowed is not None:
+            allowed = np.asarray(allowed, dtype=np.int64)
+            rows = allowed if rows is None else np.intersect1d(rows, allowed)
+        if rows.size == 0:
+            return 0
+        self._delete_rows(np.sort(rows))
+        self._mutated(ids_changed=True)
+        return int(rows.size)
+
+    def _delete_rows(self, dead: np.ndarray):
+        """dead: ascending distinct sidecar rows.  Every shard compacts the rows it owns (crs::slab_compact) and renumbers its
+        row map; the host sidecars lose the same rows in one pass."""
+        import torch
+        col = self.collection
+        for sh in col.shards:
+            if sh.n == 0:
+                continue
+            with torch.cuda.device(sh.device):
+                dead_t = torch.from_numpy(dead).to(sh.device)
+                _, local = self._local_rows(sh, dead_t)
+                m = int(local.numel())
+                if m:
+                    nat.slab_compact(local.contiguous(), sh.n, sh.slab, scales=sh.scales, shadow=sh.shadow,
+                                     rows_global=None if sh.identity else sh.rows_global, first_row=int(local[0]))
+                    # the kernel leaves the m rows past the survivors unspecified; a fresh store has zeros there
+                    for arr in (sh.slab, sh.scales, sh.shadow):
+                        if arr is not None:
+                            arr[sh.n - m: sh.n].zero_()
+                    sh.n -= m
+                if not sh.identity and sh.n:
+                    # new sidecar row = old - deleted sidecar rows below it (an identity shard's map is 0, 1, 2, ... before and after)
+                    rg = sh.rows_global[: sh.n]
+                    rg.sub_(torch.searchsorted(dead_t, rg))
+        keep = survivor_rows(len(col.ids), dead).tolist()
+        col.ids = [col.ids[r] for r in keep]
+        col.documents = [col.documents[r] for r in keep]
+        col.metadatas = [col.metadatas[r] for r in keep]
+
+    def _plan_update(self, ids, embeddings, documents, metadatas):
+        """Every check of update(), before anything changes -> (sidecar rows int64 [m], fp32 torch embeddings or None)."""
+        if self.collection is None:
+            raise ValueError("No collection available. Create index first.")
+        col = self.collection
+        ids = [ids] if isinstance(ids, str) else list(ids)
+        for name, val in (("embeddings", embeddings), ("documents", documents), ("metadatas", metadatas)):
+            if val is not None and len(val) != len(ids):
+                raise ValueError(f"{name} count ({len(val)}) doesn't match id count ({len(ids)})")
+        if len(set(ids)) != len(ids):
+            raise ValueError("update: an id is given twice")
+        idmap = col._id_rows()
+        rows = []
+        for i in ids:
+            at = idmap.get(i)
+            if not at:
+                raise ValueError(f"update: unknown id {i!r}")
+            if len(at) > 1:
+                raise ValueError(f"update: id {i!r} is carried by {len(at)} rows")
+            rows.append(at[0])
+        emb = None
+        if embeddings is not None:
+            emb = self._as_f32(embeddings)
+            if emb.ndim != 2:
+                raise ValueError(f"embeddings must be 2-D, got shape {tuple(emb.shape)}")
+            if len(ids) and emb.shape[1] != col.dim:
+                raise ValueError(f"Embedding dimension {emb.shape[1]} doesn't match the index dimension {col.dim}")
+        if metadatas is not None and not all(isinstance(m, dict) for m in metadatas):
+            raise ValueError("metadatas must be dicts")
+        return np.asarray(rows, dtype=np.int64), emb
+
+    def _apply_update(self, rows: np.ndarray, emb, documents, metadatas):
+        import torch
+        col = self.collection
+        if emb is not None:
+            for sh in col.shards:
+                if sh.n == 0:
+                    continue
+                with torch.cuda.device(sh.device):
+                    sel, local = self._local_rows(sh, torch.from_numpy(rows).to(sh.device))
+                    if sel.numel():
+                        mine = emb.to(sh.device)[sel].contiguous()
+                        nat.slab_write_rows_f32(mine, local.contiguous(), sh.slab, sh.n, scales=sh.scales, shadow=sh.shadow,
+                                                row_err=sh.row_err)
+        for at, row in enumerate(rows.tolist()):
+            if documents is not None:
+                col.documents[row] = documents[at]
+            if metadatas is not None:
+                col.metadatas[row] = dict(metadatas[at])
+
+    def update(self, ids: Sequence[str], embeddings=None, documents: Optional[Sequence[str]] = None,
+               metadatas: Optional[Sequence[dict]] = None) -> None:
+        """Per id, replace what is given: the embedding (the device rows are rewritten by the append's own per-row function),
+        the document text, the metadata dict -- replaced WHOLE, not merged key by key (simpler than ChromaDB's update).
+        An unknown id, an id that several rows carry, an id twice in one call, a length mismatch or a wrong dimension raise
+        ValueError before anything is changed.  SPMD: the same call on every rank."""
+        rows, emb = self._plan_update(ids, embeddings, documents, metadatas)
+        if rows.size == 0 or (emb is None and documents is None and metadatas is None):
+            return
+        self._apply_update(rows, emb, documents, metadatas)
+        self._mutated(ids_changed=False, sidecars_changed=metadatas is not None)
+
+    def upsert(self, chunks: List[Chunk], embeddings, metadata_fields: Optional[List[str]] = None) -> None:
+        """create_index's signature: chunks whose chunk_id exists are updated in place (embedding, text, metadata), the others
+        are appended in their given order by create_index."""
+        if len(chunks) != len(embeddings):
+            raise ValueError(f"Chunk count ({len(chunks)}) doesn't match embedding count ({len(embeddings)})")
+        if len(chunks) == 0:
+            return
+        if self.collection is None or self.collection.count() == 0:
+            self.create_index(chunks, embeddings, metadata_fields)
+            self.mutation_epoch += 1
+            return
+        col = self.collection
+        fields = ['page_number', 'section', 'tokens'] if metadata_fields is None else metadata_fields
+        emb = self._as_f32(embeddings)
+        if emb.ndim != 2:
+            raise ValueError(f"embeddings must be 2-D, got shape {tuple(emb.shape)}")
+        if emb.shape[1] != col.dim:
+            raise ValueError(f"Embedding dimension {emb.shape[1]} doesn't match the index dimension {col.dim}")
+        idmap = col._id_rows()
+        known = [a for a, c in enumerate(chunks) if c.chunk_id in idmap]
+        fresh = [a for a, c in enumerate(chunks) if c.chunk_id not in idmap]
+        rows, emb_known = self._plan_update([chunks[a].chunk_id for a in known], emb[known] if known else None,
+                                            [chunks[a].text for a in known] if known else None,
+                                            [self._chunk_metadata(chunks[a], fields) for a in known] if known else None)
+        if known:
+            self._apply_update(rows, emb_known, [chunks[a].text for a in known],
+                               [self._chunk_metadata(chunks[a], fields) for a in known])
+            self._mutated(ids_changed=False)
+        else:
+            self.mutation_epoch += 1
+        if fresh:
+            self.create_index([chunks[a] for a in fresh], emb[fresh], metadata_fields)
 
     # -- search --------------------------------------------------------------------------------
     def _cap(self, top_k: int) -> int:
@@ -901,6 +1208,9 @@ class VectorStore:
                 for path in self._persist_paths().values():
                     if os.path.exists(path):
                         os.remove(path)
+                if os.path.isdir(self.persist_directory):
+                    self._remove_other_generations(-1)       # every generation's files, a crashed rewrite's included
+            self._gen, self._gen_pending, self._docs_bytes = None, False, 0
             logger.info(f"Deleted collection: {self.collection_name}")
 
     def reset_collection(self):

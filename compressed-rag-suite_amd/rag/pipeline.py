@@ -78,6 +78,11 @@ class RAGPipeline:
         logger.info(f"Indexing complete in {elapsed:.2f}s")
         return elapsed
 
+    def remove_documents(self, ids: Optional[List[str]] = None, where: Optional[dict] = None) -> int:
+        """Additive: remove chunks by chunk id and / or metadata filter (VectorStore.delete); returns the rows removed.  The
+        pipeline keeps no document-to-chunk registry: callers pass chunk ids, or a `where` on the metadata they indexed."""
+        return self.vector_store.delete(ids=ids, where=where)
+
     # ---- retrieval -------------------------------------------------------------------------------
     def retrieve(self, query: str, top_k: Optional[int] = None) -> List[Dict]:
         return self.retriever.retrieve(query, top_k=top_k)

@@ -132,7 +132,8 @@ class ContextRetriever:
             return None
         # one encoder forward serves a group of batches (rag/_engine.py): never more of them than a call of this size brings
         cap = 1 << (max(1, n_batches).bit_length() - 1)
-        key = (fetch, seq, view.n, int(view.slab.data_ptr()), self.batch_queries, min(cap, 16))
+        # mutation_epoch: an in-place update leaves n and the slab pointer as they were, but the engine's graphs hold the OLD row_err_max
+        key = (fetch, seq, view.n, int(view.slab.data_ptr()), self.batch_queries, min(cap, 16), getattr(store, "mutation_epoch", 0))
         if self._engine_key != key:
             from rag._engine import RetrievalEngine
             self._engine = RetrievalEngine(enc, view, self.batch_queries, seq, fetch, k_scan=store.refine_overfetch,

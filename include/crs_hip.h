@@ -55,6 +55,32 @@ int crs_padded_dim(int dim);
 int crs_slab_append_f32(const float* emb_dev, int64_t n, int dim, int slab_type, void* slab_dev,
                         float* scales_dev, float* shadow_f32_dev, int64_t row0, float* row_err_max_dev, void* stream);
 
+/* ---- in-place mutation (additive to ABI 3; csrc/mutate.hip) -- no reference call site: the reference's ChromaDB collection
+ * offers delete / update / upsert, its own code never calls them --------------------------------------------------------------
+ * crs_slab_write_rows_f32 is the scatter form of crs_slab_append_f32: row rows[i] (dev int64 [m], distinct, each < n_rows;
+ * rows outside [0, n_rows) are skipped) of slab / scales / shadow is rewritten from emb[i] by the SAME per-row device function
+ * the append kernel calls, so an updated row equals the same vector appended bit for bit; row_err_max is raised likewise.
+ *
+ * crs_slab_compact removes the `m` rows dead[0] < dead[1] < ... (dev int64, strictly ascending, all < n_rows) from the arrays
+ * of one shard IN PLACE, keeping the order of the others: afterwards rows [0, n_rows - m) of slab, scales (may be NULL),
+ * shadow (may be NULL; stride `dim`) and rows_global (dev int64, may be NULL) hold the survivors in their old order; what lies
+ * past that is unspecified.  The survivor at destination d comes from source d + j, j = the number of dead rows below it.
+ * Rows below dead[0] are not touched; `first_row` (0 <= first_row <= dead[0], 0 when the host does not know dead[0]) lets the
+ * call skip the windows below it altogether.  The destination is walked in windows of W rows (W from bounce_bytes); per
+ * window one launch gathers the window's source rows into `bounce`, the next copies `bounce` to the window.  Window i + 1
+ * reads rows >= (i + 1) W and everything written before lies below that, so STREAM ORDER is the whole ordering argument: no
+ * workgroup waits for another.  2 ceil((n_rows - m - first_row) / W) launches, no allocation, no host synchronisation.
+ * crs_slab_compact_bounce_bytes is the smallest legal bounce size (a window of 1024 rows of every array); larger = fewer
+ * windows.  bounce must be 256-byte aligned. */
+int crs_slab_write_rows_f32(const float* emb_dev, const int64_t* rows_dev, int64_t m, int dim, int slab_type, void* slab_dev,
+                            float* scales_dev, float* shadow_f32_dev, int64_t n_rows, float* row_err_max_dev, void* stream);
+size_t crs_slab_compact_bounce_bytes(int dim, int slab_type, int has_shadow);
+int crs_slab_compact(const int64_t* dead_dev, int64_t m, int64_t n_rows, int64_t first_row, int dim, int slab_type, void* slab_dev,
+                     float* scales_dev, float* shadow_f32_dev, int64_t* rows_global_dev, void* bounce_dev, size_t bounce_bytes,
+                     void* stream);
+/* Host arithmetic of the above, for tests and callers that size buffers: rows per window for a bounce size (0 = too small). */
+int64_t crs_slab_compact_window_rows(int dim, int slab_type, int has_shadow, size_t bounce_bytes);
+
 /* Query side of the same conversion: fp32 [nq, dim] -> normalised fp16 [nq, crs_row_elems(dim, slab_type)]. */
 int crs_queries_to_f16(const float* q_dev, int nq, int dim, int slab_type, void* q16_dev, void* stream);
 
