@@ -76,6 +76,11 @@ int tb_dyn_granule() {
   const int v = e ? atoi(e) : 8;
   return v >= 16 ? 16 : v >= 8 ? 8 : v >= 4 ? 4 : v >= 2 ? 2 : 1;
 }
+// The same schedule in scan_wide.hip's 24- / 32-slot forms.  CRS_WIDE_DYN=0 keeps their static stride (A/B runs).  Read per call.
+bool wide_dyn_enabled() {
+  const char* e = getenv("CRS_WIDE_DYN");
+  return !(e && e[0] == '0');
+}
 bool tb_enabled() {   // CRS_SCAN_TB=0: always use the threshold/compaction kernel for <= 64 queries (A/B runs, tests)
   static int v = -1;
   if (v < 0) { const char* e = getenv("CRS_SCAN_TB"); v = (e && e[0] == '0') ? 0 : 1; }
@@ -137,7 +142,8 @@ int make_plan(int nq, int dim, int k, int64_t n_rows, int slab_type, Plan* p) {
   for (int attempt = 0; attempt < 3; ++attempt) {
     const bool allow_tb = attempt < 2 && tb_enabled();
     p->w1_qg = (allow_tb && allow_w1 && slab_type == CRS_SLAB_F16) ? crs::scan_w1_queries_per_wg(nq, k, p->pdim) : 0;
-    p->wide_nw = (allow_tb && !p->w1_qg && slab_type == CRS_SLAB_F16 && k <= 16) ? crs::scan_wide_waves(nq, k, p->pdim) : 0;
+    // (16 < k <= 32 on rows of <= 384 elements too: one launch then serves up to 256 queries per sweep at the re-rank's over-fetch)
+    p->wide_nw = (allow_tb && !p->w1_qg && slab_type == CRS_SLAB_F16 && k <= 32) ? crs::scan_wide_waves(nq, k, p->pdim) : 0;
     p->tb_nw = 0;
     if (allow_tb && !p->w1_qg && !p->wide_nw && slab_type == CRS_SLAB_F16)
       p->tb_nw = (nq > 64 && k <= 16 && crs::scan_tb_has_8_waves(p->pdim)) ? 8 : 4;
@@ -196,7 +202,8 @@ int make_plan(int nq, int dim, int k, int64_t n_rows, int slab_type, Plan* p) {
   // CRS_SCAN_NT=0 / 1 forces the policy off / on; read per call.
   const size_t slab_bytes = (size_t)n_rows * p->pdim * (slab_type == CRS_SLAB_I8 ? 1 : 2);
   const char* ne = getenv("CRS_SCAN_NT");
-  p->nt = (p->tb_nw || p->i8_tb) ? ((ne && ne[0] == '0') ? 0 : (ne && ne[0] == '1') ? 1 : (slab_bytes >= ((size_t)1 << 30) && p->nqb == 1)) : 0;
+  const bool streamed = p->tb_nw || p->i8_tb || (p->wide_nw && crs::scan_wide_streamed(k));
+  p->nt = streamed ? ((ne && ne[0] == '0') ? 0 : (ne && ne[0] == '1') ? 1 : (slab_bytes >= ((size_t)1 << 30) && p->nqb == 1)) : 0;
   return CRS_OK;
 }
 
@@ -297,7 +304,9 @@ static int run_scan(const Plan& p, const void* q16, int nq, int slab_type, const
   a.t_dyn = p.n_tiles;
   a.dyn_mask = 0;
   a.nt = p.nt;
-  if (((slab_type == CRS_SLAB_F16 && p.tb_nw) || (slab_type == CRS_SLAB_I8 && p.i8_tb && p.pdim <= 768)) && p.tb_slots > 0 && p.nqb == 1 && !share) {
+  const bool tb_chain = ((slab_type == CRS_SLAB_F16 && p.tb_nw) || (slab_type == CRS_SLAB_I8 && p.i8_tb && p.pdim <= 768)) && p.tb_slots > 0;
+  const bool wide_chain = p.wide_nw && crs::scan_wide_streamed(k) && wide_dyn_enabled();   // scan_wide.hip's 24- / 32-slot forms
+  if ((tb_chain || wide_chain) && p.nqb == 1 && !share) {
     // (int8 rows of 1024 elements stay static: those instantiations spill, and the ticket's register must not travel through scratch
     // while its value is in flight)
     // long chain-mode streams: the last tb_dyn_percent() of the tiles are drawn from a counter (scan_tb.hip, scan_i8.hip), which lives in the

@@ -60,8 +60,9 @@ int scan_launch_tb(const ScanArgs& a, int pdim, int nw, int slots, hipStream_t s
 int scan_ticket_zero(unsigned* ticket, hipStream_t stream);   // ScanArgs::ticket := 0, in stream order (scan_tb.hip / scan_i8.hip chain modes)
 int scan_tb_long_chain_slots(int pdim, int nw, int k);   // chain length for 16 < k <= 64 on long streams (0: none)
 int scan_i8_long_chain_slots(int pdim, int k);
-// scan_wide.hip: 65+ queries per launch, k <= 16, fp16 slabs
+// scan_wide.hip: 65+ queries per launch, fp16 slabs, k <= 16 (rows of <= 512 elements) or k <= 32 (<= 384)
 int scan_wide_waves(int nq, int k, int pdim);
+bool scan_wide_streamed(int k);   // the 24- / 32-slot forms: ScanArgs::nt and ticket / t_dyn / dyn_mask apply
 int scan_wide_wg_per_cu(int nw, int pdim);
 int scan_wide_slots(int k);
 int scan_wide_tile_rows(int nw, int pdim);

@@ -27,7 +27,11 @@
 //   * tile staging, XOR swizzle (conflict-free for the 32-row fragment reads too: every 16-lane group of
 //     a ds_read_b128 covers 16 distinct rows mod 16), early asm loads and the one-barrier double buffer
 //     are those of scan.hip.
-// k <= 16 only (the launcher falls back to scan.hip otherwise).
+// Chains of 4 / 10 / 16 slots per lane, and 24 / 32 for rows of <= 384 elements (the over-fetch of the fp32 re-rank on large
+// shards is 24: one launch then serves the four 64-query batches of a fused search chunk from ONE sweep of the shard).  The 24- /
+// 32-slot forms run one query block per launch in practice, so they also take scan_tb.hip's non-temporal slab stream and its
+// ticketed dynamic tile schedule behind the same plan fields (ScanArgs::nt, ticket / t_dyn / dyn_mask); the shorter chains are
+// compiled without either, exactly as they were measured.
 
 #include "scan_common.h"
 
@@ -48,6 +52,15 @@ typedef __attribute__((address_space(3))) void* lds_ptr_t;
 // per wave and 32-row tile against 1.5 k of matrix work) are then paid once per 64 rows.
 template <int D, int NW>
 constexpr int wide_rb() { return (NW == 8 && D <= 384) ? 2 : 1; }
+
+// the forms with chains longer than 16 slots: nt stream + dynamic tile schedule compiled in (header)
+template <int K>
+constexpr bool wide_streamed() { return K > 16; }
+// Waves 4..7 defer a tile's selection by one iteration (the stagger below) where the deferred accumulators fit: two waves per
+// SIMD leave 256 registers per lane, VGPRs and AGPRs together.  384-element rows: 96 of query fragments, 32 + 32 of current and
+// deferred accumulators and 2 K of chain -- 16 slots and more would spill (profiles/r07_wide_resources.txt).
+template <int D, int NW, int K>
+constexpr bool wide_stagger() { return NW == 8 && D <= 384 && !(D == 384 && K >= 16) && !(D == 256 && K >= 32); }
 
 template <int D, int NW>
 struct WCfg {
@@ -99,10 +112,12 @@ __global__ __launch_bounds__(NW * 64, 2) void scan_wide_kernel(const ScanArgs a)
     const unsigned dst0 = lds_wave + (unsigned)(buf * C::kTileBytes);
     if (tile < n_full) {
       const char* base = uniform_ptr(slab + (size_t)tile * C::kTileBytes);
+      if (wide_streamed<K>() && a.nt) {   // (a kernel argument: a scalar branch)
 #pragma unroll
-      for (int j = 0; j < C::kLoads; ++j) {
-        const unsigned dst = dst0 + (unsigned)(j * kT * 16);
-        lds_dma16(dst, src_off[j], base);
+        for (int j = 0; j < C::kLoads; ++j) lds_dma16_nt(dst0 + (unsigned)(j * kT * 16), src_off[j], base);
+      } else {
+#pragma unroll
+        for (int j = 0; j < C::kLoads; ++j) lds_dma16(dst0 + (unsigned)(j * kT * 16), src_off[j], base);
       }
     } else {   // the ragged last tile: clamp every lane to the slab's last 16 bytes (rows past the end never rank)
 #pragma unroll
@@ -116,7 +131,16 @@ __global__ __launch_bounds__(NW * 64, 2) void scan_wide_kernel(const ScanArgs a)
     }
   };
 
-  int t = stream;
+  // Tile order: static stride below t_dyn, then (24- / 32-slot forms) granules of dyn_mask + 1 consecutive tiles drawn from a
+  // device-wide counter, exactly scan_tb.hip's schedule ("Tile order" there): the ticket for the tile AFTER the look-ahead tile
+  // is requested at the top of an iteration and handed round through LDS behind the iteration's barrier.  A workgroup still
+  // sees its tiles in increasing order, so any assignment leaves the same lists after the merge.
+  __shared__ int sh_next[2];
+  constexpr bool kDyn = wide_streamed<K>();
+  const int tend = a.n_tiles;
+  const int t_dyn = kDyn ? a.t_dyn : a.n_tiles;
+  int t = stream, t_prev = stream;
+  int tn = t + nwg;     // the look-ahead tile (t_dyn >= 2 nwg: static for the first iteration)
   dma_tile(t, 0);   // goes out before the query fragments are fetched, so the two latencies overlap
 
   // ---- this wave's 32 queries, full depth, as B fragments: lane (n = l & 31, h = l >> 5) holds
@@ -212,8 +236,7 @@ __global__ __launch_bounds__(NW * 64, 2) void scan_wide_kernel(const ScanArgs a)
   // both in the VALU selection with the matrix pipe idle -- measured 3.7 k cycles per tile against 1.5 k
   // of MFMA work.  So waves 4..7 defer the selection of a tile by one iteration (its 16 accumulators stay
   // in registers across the barrier): on every SIMD one wave multiplies while the other selects.
-  const bool late = (NW == 8 && D <= 384 && !(D == 384 && K == 16)) && wave >= 4;   // wave-uniform; off where the
-                                                                                      // deferred accumulators would spill
+  const bool late = wide_stagger<D, NW, K>() && wave >= 4;   // wave-uniform; off where the deferred accumulators would spill
   struct Acc { f32x16 a[RB]; };
   Acc acc_prev;
 #pragma unroll
@@ -268,9 +291,24 @@ __global__ __launch_bounds__(NW * 64, 2) void scan_wide_kernel(const ScanArgs a)
   };
 
   int cur = 0, it = 0;
-  // one iteration: tile t sits in LDS buffer `cur`, tile t + nwg streams into the other one
-  while (t < a.n_tiles) {
-    if (t + nwg < a.n_tiles) dma_tile(t + nwg, cur ^ 1);
+  // one iteration: tile t sits in LDS buffer `cur`, the look-ahead tile tn streams into the other one
+  while (t < tend) {
+    const bool has_next = tn < tend;
+    if (has_next) dma_tile(tn, cur ^ 1);
+    // the tile after tn: static stride, the next tile of tn's granule, or -- tn is the last static tile / the last tile of its
+    // granule -- the first tile of the granule the counter hands out (wave-uniform)
+    const bool in_dyn = kDyn && tn >= t_dyn;
+    const bool draw = kDyn && a.ticket != nullptr && has_next && (in_dyn ? ((tn - t_dyn) & a.dyn_mask) == a.dyn_mask : tn + nwg >= t_dyn);
+    unsigned tk = 0;
+    if constexpr (kDyn) {
+      // one lane draws, under a hand-set exec mask (scan_tb.hip: hipcc's atomicAdd would wait for the value, and with it for the
+      // look-ahead transfer, on the spot).  The value is first read behind the vmcnt(0) below.
+      const unsigned mask = __builtin_amdgcn_readfirstlane((draw && wave == 0) ? 1u : 0u);   // lane 0 of wave 0, or nobody
+      unsigned long long keep;
+      const unsigned zero = 0u, one = 1u;
+      asm volatile("s_mov_b64 %1, exec\n\ts_mov_b32 exec_lo, %2\n\ts_mov_b32 exec_hi, 0\n\tglobal_atomic_add %0, %3, %4, %5 sc0\n\ts_mov_b64 exec, %1"
+                   : "+v"(tk), "=&s"(keep) : "s"(mask), "v"(zero), "v"(one), "s"(a.ticket) : "memory");
+    }
     if (wave_active) {
       WP_LAP(1);   // tile-load issue
       const char* buf = tile_buf + cur * C::kTileBytes;
@@ -279,23 +317,35 @@ __global__ __launch_bounds__(NW * 64, 2) void scan_wide_kernel(const ScanArgs a)
         WP_LAP(3);   // MFMA sweep
         select(acc, t, it);
       } else {       // waves 4..7: last tile's selection first, then this tile's MFMAs
-        if (it > 0) select(acc_prev, t - nwg, it - 1);
+        if (it > 0) select(acc_prev, t_prev, it - 1);
         WP_LAP(2);
         acc_prev = sweep(buf);
         WP_LAP(3);
       }
     }
     WP_LAP(4);   // selection (waves 0..3)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    WP_LAP(6);   // wait for the next tile
+    int tnn = in_dyn ? tn + 1 : tn + nwg;
+    if constexpr (kDyn) {
+      asm volatile("s_waitcnt vmcnt(0)" : "+v"(tk) : : "memory");
+      if (draw && tid == 0) sh_next[it & 1] = t_dyn + (int)tk * (a.dyn_mask + 1);
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    WP_LAP(6);   // wait for the next tile (and for the ticket)
     __syncthreads();
     WP_LAP(7);   // barrier
+    if (kDyn && draw) {   // two slots: iteration it + 1 writes the other one
+      tnn = __builtin_amdgcn_readfirstlane(sh_next[it & 1]);
+      tnn = (unsigned)tnn < (unsigned)tend ? tnn : tend;   // a poisoned counter must not become an address
+    }
     cur ^= 1;
     ++it;
-    t += nwg;
+    t_prev = t;
+    t = tn;
+    tn = tnn;
   }
 
-  if (wave_active && late && it > 0) select(acc_prev, t - nwg, it - 1);   // the deferred last tile
+  if (wave_active && late && it > 0) select(acc_prev, t_prev, it - 1);   // the deferred last tile
   if (wave_active && (it & 1)) insert(px, pr);   // odd tile count: the last (even) tile is still pending
   if (wave_active && q_valid) {   // [nq, nwg, kp = 2 K]: lane half h owns slots h K .. h K + K - 1
     const size_t o = ((size_t)qi * nwg + stream) * a.kp + (size_t)h * K;
@@ -329,7 +379,12 @@ int launch_wide_k(const ScanArgs& a, hipStream_t stream) {
   const int kk = scan_wide_slots(a.k);
   if (kk == 4) return launch_wide<D, NW, 4>(a, stream);
   if (kk == 10) return launch_wide<D, NW, 10>(a, stream);
-  return launch_wide<D, NW, 16>(a, stream);
+  if (kk == 16) return launch_wide<D, NW, 16>(a, stream);
+  if constexpr (D <= 384) {   // no scratch in any of them: tools/check_resources.py, profiles/r07_wide_resources.txt
+    if (kk == 24) return launch_wide<D, NW, 24>(a, stream);
+    if (kk == 32) return launch_wide<D, NW, 32>(a, stream);
+  }
+  return -1;
 }
 
 template <int D>
@@ -347,13 +402,15 @@ int scan_wide_waves(int nq, int k, int pdim) {
     const char* e = getenv("CRS_SCAN_WIDE");
     on = (e && e[0] == '0') ? 0 : 1;
   }
-  if (!on || nq <= 64 || k > 16 || pdim > 512) return 0;
+  if (!on || nq <= 64 || k > 32 || pdim > 512 || (k > 16 && pdim > 384)) return 0;
   return nq > 128 ? 8 : 4;
 }
 // rows per tile of the configuration scan_wide_waves() picks
 int scan_wide_tile_rows(int nw, int pdim) { return (nw == 8 && pdim <= 384) ? 64 : 32; }
 // list slots per lane the kernel is instantiated for (>= k); the partial lists are 2 * this wide
-int scan_wide_slots(int k) { return k <= 4 ? 4 : k <= 10 ? 10 : 16; }
+int scan_wide_slots(int k) { return k <= 4 ? 4 : k <= 10 ? 10 : k <= 16 ? 16 : k <= 24 ? 24 : 32; }
+// the 24- / 32-slot forms carry the non-temporal slab stream and the ticketed tile schedule (ScanArgs::nt / ticket)
+bool scan_wide_streamed(int k) { return scan_wide_slots(k) > 16; }
 // resident workgroups per CU: the query fragments cost D/4 registers per lane -> two waves per SIMD
 int scan_wide_wg_per_cu(int nw, int pdim) { return nw == 8 ? 1 : 2; }
 

@@ -22,6 +22,10 @@ encoder for its <= 48 KB kernel forms (``CRS_ENC_SMALL_LDS`` in the descriptor's
 faster (bge-class encoders: single rank only, together with encode groups), and keeps one lane per batch
 otherwise.
 
+Sweep groups.  On one rank, over fp16 shards of >= 2 GB, the F = ``search_fuse`` batches of a fused search chunk are searched by
+ONE launch over their F x 64 contiguous queries: the shard is read once per chunk instead of once per batch (``plan_layout``).
+Every batch keeps its own queries, output lists and status -- they are views of the chunk's blocks.
+
 Encode groups.  With role lanes a bge-class encoder forward serves G = 8 consecutive batches (``encode_group``): the per-batch
 searches are unchanged, the forward's GEMMs see 8 x the tokens (C3: 134 -> 165 k q/s).  See ``__init__``.
 """
@@ -56,10 +60,22 @@ class _Group:
     """Buffers of one encoder forward: the token / embedding blocks of G consecutive batches (G = 1: of one batch)."""
 
 
+class _Chunk:
+    """Blocks of the F buffer sets whose searches share one sweep (their attributes are views of these)."""
+
+
+class _WireView:
+    """A buffer set's (ids | scores) result as views of its chunk's blocks (single rank: nothing is sent, so no wire layout)."""
+
+    def __init__(self, scores, ids):
+        self.scores, self.ids, self.buf, self.gathered = scores, ids, None, None
+
+
 class RetrievalEngine:
     @staticmethod
     def plan_layout(hidden: int, scan_bytes: int, *, encode: bool = True, multi: bool = False, lanes: str = "auto", encode_group="auto",
-                    n_ctx: int = 0, enc_lanes: int = 0, search_lanes: int = 0, group_cap: int = 0, batch_tokens: int = 0) -> dict:
+                    n_ctx: int = 0, enc_lanes: int = 0, search_lanes: int = 0, group_cap: int = 0, batch_tokens: int = 0,
+                    search_fuse="auto", graphs: bool = True, nq_all: int = 0, pdim: int = 0, slab_f16: bool = False) -> dict:
         """Lanes, encode groups and buffer sets for an encoder of width `hidden` beside scans of `scan_bytes` per batch (measured
         rules; every explicit argument wins over its rule):
           * role lanes ('split') for MiniLM-class encoders always, for bge-class ones over scans of >= 512 MB on one rank; else every
@@ -74,7 +90,18 @@ class RetrievalEngine:
             -- 38 kernel boundaries per 16 batches instead of per batch: 47.3 -> 48.6 - 49.0 k q/s on one box (8 per forward over 16
             sets: 48.6 k; a second search lane: 49.8 k, not taken -- consecutive scans then overlap and a trace's per-kernel
             durations stop meaning "one scan").
-        group_cap > 0 limits the group (a caller that knows its calls bring fewer batches than a group holds)."""
+        group_cap > 0 limits the group (a caller that knows its calls bring fewer batches than a group holds).
+          * fused search chunks (single rank, graphs on): the searches of 4 consecutive members of a group replay as one hipGraph
+            (``search_fuse``; CRS_SEARCH_FUSE overrides);
+          * sweep groups (``sweep_group``): the chunk's F batches share ONE sweep of the shard -- one launch over their F x nq_all
+            contiguous queries with the batch's own k' -- when all of these hold: single rank, graphs on, an fp16 slab whose padded
+            rows are within the 256-query kernel's 24- / 32-slot range (<= 384 elements), nq_all <= 64 (F x nq_all <= 256),
+            search_fuse > 1, and a scan of >= 2 GB per batch.  The members' results completed together before (one graph); now
+            they complete together after one read of the shard instead of F (no measured pair yet: DESIGN.md section 4).
+            Short scans (C2's 77 MB, a 1.25 M-row rank shard) keep one sweep per batch: they were not measured with a shared sweep,
+            and there the lanes wait for launch chains, not for HBM.  N > 1 keeps one sweep per batch: a collective follows each.
+            CRS_SWEEP_GROUP=1 restores one sweep per batch (A/B runs, tests).
+        nq_all / pdim / slab_f16 describe the searches (0 / False: unknown, no sweep groups)."""
         big, short = hidden > 384, scan_bytes < (2 << 30)
         pipelined = lanes == "split" or (lanes == "auto" and encode and ((not big) or (scan_bytes >= (512 << 20) and not multi)))
         if encode_group == "auto":
@@ -93,7 +120,19 @@ class RetrievalEngine:
             n_srch = search_lanes if search_lanes > 0 else (2 if (minilm_groups and short) else 1)
         else:
             n_enc = n_srch = n_ctx
-        return {"pipelined": pipelined, "encode_group": encode_group, "n_ctx": n_ctx, "n_enc": n_enc, "n_srch": n_srch}
+        if search_fuse == "auto":
+            search_fuse = 4 if (not multi and encode_group % 4 == 0 and graphs) else 1
+        search_fuse = max(1, int(os.environ.get("CRS_SEARCH_FUSE", search_fuse)))
+        if multi or encode_group % search_fuse:
+            search_fuse = 1
+        sweep_group = 1
+        if (not multi and graphs and slab_f16 and 0 < pdim <= 384 and 0 < nq_all <= 64 and search_fuse > 1
+                and search_fuse * nq_all <= 256 and not short):
+            sweep_group = min(search_fuse, max(1, int(os.environ.get("CRS_SWEEP_GROUP", search_fuse))))
+            if sweep_group != search_fuse:     # (a chunk is searched whole or batch by batch)
+                sweep_group = 1
+        return {"pipelined": pipelined, "encode_group": encode_group, "n_ctx": n_ctx, "n_enc": n_enc, "n_srch": n_srch,
+                "search_fuse": search_fuse, "sweep_group": sweep_group}
 
     def __init__(self, encoder, view: ShardView, queries_per_batch: int, seq: int, top_k: int, *, k_scan: int = 24, k_scan_exact: int = 0,
                  refine: bool = True, exact="auto", exact_cap: int = nat.EXACT_CAP, n_ctx: int = 0, lanes: str = "auto",
@@ -135,15 +174,16 @@ class RetrievalEngine:
         self.pd = nat.padded_dim(view.dim, view.slab_type)
         scan_bytes = view.n * self.pd * (1 if view.slab_type == nat.SLAB_I8 else 2)
         hidden = encoder.shape.hidden if encoder is not None else view.dim
+        self.use_graph = bool(graphs)
         plan = self.plan_layout(hidden, scan_bytes, encode=self.encode, multi=self.multi, lanes=lanes, encode_group=encode_group,
                                 n_ctx=int(n_ctx), enc_lanes=enc_lanes, search_lanes=search_lanes, group_cap=int(group_cap),
-                                batch_tokens=self.q_loc * self.seq)
+                                batch_tokens=self.q_loc * self.seq, search_fuse=search_fuse, graphs=self.use_graph,
+                                nq_all=self.nq_all, pdim=self.pd, slab_f16=view.slab_type == nat.SLAB_F16)
         self.pipelined, self.enc_group, self.n_ctx = plan["pipelined"], plan["encode_group"], plan["n_ctx"]
         self.n_enc, self.n_srch = plan["n_enc"], plan["n_srch"]
         # <= 48 KB kernel forms of the encoder (they can start beside a scan's resident workgroups): with role lanes always;
         # 'auto' otherwise keeps the default forms
         self.small_lds = self.pipelined if enc_small_lds == "auto" else bool(enc_small_lds)
-        self.use_graph = bool(graphs)
         if self.pipelined:
             self.enc_cus = int(os.environ.get("CRS_ENC_CUS", enc_cus))
             if self.enc_cus > 0:
@@ -168,11 +208,12 @@ class RetrievalEngine:
         # FUSED SEARCH GRAPHS (single rank): the search segments of F consecutive members of a group replayed as ONE hipGraph --
         # a graph boundary on the search lane costs ~20 us (tools/timeline.py), 1.5 % of a C4 batch, once per F batches instead of
         # once per batch.  The members' results then complete together.  N > 1 keeps one graph per batch: a collective follows each.
-        if search_fuse == "auto":
-            search_fuse = 4 if (not self.multi and self.enc_group % 4 == 0 and self.use_graph) else 1
-        self.search_fuse = max(1, int(os.environ.get("CRS_SEARCH_FUSE", search_fuse)))
-        if self.multi or self.enc_group % self.search_fuse:
-            self.search_fuse = 1
+        # SWEEP GROUPS: where plan_layout allows it, the chunk's F searches are ONE search over the chunk's F x nq_all contiguous
+        # queries (their fp32 / fp16 blocks are consecutive slices of the group's), with the batch's own k': the shard is swept once
+        # per chunk.  The chunk's result blocks are allocated whole and every buffer set's attributes are views of them, so a
+        # per-batch search (submit(i), step(fused=False), a short last group) runs on the same memory.
+        self.search_fuse = plan["search_fuse"]
+        self.sweep_group = plan["sweep_group"] if (self.refine and not self.gather_q and self.q_loc == self.nq_all) else 1
         self.groups: List[_Group] = []
         self.ctxs: List[_Ctx] = []
         for g0 in range(0, self.n_ctx, self.enc_group):
@@ -223,19 +264,53 @@ class RetrievalEngine:
         g.n_enc = 0
         return g
 
+    def _make_chunk(self, grp: _Group, slot0: int) -> _Chunk:
+        """One contiguous block per result / workspace of the F buffer sets from slot0 on, sized for F x nq_all queries.  The two
+        workspaces are scratch of one call: the chunk's call uses their head, a buffer set's call its own slice."""
+        torch, v, dev = self.torch, self.view, self.dev
+        F, nq = self.sweep_group, self.nq_all
+        ch = _Chunk()
+        lo, hi = slot0 * self.q_loc, (slot0 + F) * self.q_loc
+        ch.q_out, ch.q16 = grp.q_out[lo:hi], grp.q16[lo:hi]
+        ch.cand_s = torch.empty((F * nq, self.k_scan), dtype=torch.float32, device=dev)
+        ch.cand_i = torch.empty((F * nq, self.k_scan), dtype=torch.int64, device=dev)
+        ch.out_s = torch.zeros((F * nq, self.k), dtype=torch.float32, device=dev)
+        ch.out_i = torch.zeros((F * nq, self.k), dtype=torch.int64, device=dev)
+        ch.status = torch.zeros(F * nq, dtype=torch.int32, device=dev)
+        ch.ws_one = -(-nat.scan_workspace_bytes(nq, v.dim, self.k_scan, v.n) // 256) * 256
+        ch.ws_all = nat.scan_workspace_bytes(F * nq, v.dim, self.k_scan, v.n)
+        ch.ws = torch.empty(max(ch.ws_all, F * ch.ws_one), dtype=torch.uint8, device=dev)
+        ch.exact_one = -(-nat.exact_workspace_bytes(nq, self.exact_cap) // 256) * 256
+        ch.exact_all = nat.exact_workspace_bytes(F * nq, self.exact_cap)
+        ch.exact_ws = torch.empty(max(ch.exact_all, F * ch.exact_one), dtype=torch.uint8, device=dev)
+        return ch
+
     def _make_ctx(self, grp: _Group, slot: int) -> _Ctx:
         torch, v, dev = self.torch, self.view, self.dev
         c = _Ctx()
         c.grp, c.slot, c.n_sub = grp, slot, 0
         lo, hi = slot * self.q_loc, (slot + 1) * self.q_loc
         c.ids, c.lens, c.q_out, c.q16 = grp.ids[lo:hi], grp.lens[lo:hi], grp.q_out[lo:hi], grp.q16[lo:hi]   # views of the group's blocks
-        c.ws = torch.empty(nat.scan_workspace_bytes(self.nq_all, v.dim, self.k_scan, v.n), dtype=torch.uint8, device=dev)
-        c.cand_s = torch.empty((self.nq_all, self.k_scan), dtype=torch.float32, device=dev)
-        c.cand_i = torch.empty((self.nq_all, self.k_scan), dtype=torch.int64, device=dev)
-        c.wire = nat.WireBlock(self.nq_all, self.k, dev, self.world, gather=self.multi)   # this rank's (ids | scores) block
-        c.status = torch.zeros(self.nq_all, dtype=torch.int32, device=dev)
-        c.exact_ws = (torch.empty(nat.exact_workspace_bytes(self.nq_all, self.exact_cap), dtype=torch.uint8, device=dev)
-                      if self.refine else None)
+        if self.sweep_group > 1:     # views of the chunk's blocks (allocated with the chunk's first buffer set)
+            F, nq = self.sweep_group, self.nq_all
+            j = slot % F
+            if j == 0:
+                grp.chunks = getattr(grp, "chunks", []) + [self._make_chunk(grp, slot)]
+            ch = c.chunk = grp.chunks[slot // F]
+            r = slice(j * nq, (j + 1) * nq)
+            c.ws = ch.ws[j * ch.ws_one:(j + 1) * ch.ws_one]
+            c.cand_s, c.cand_i, c.status = ch.cand_s[r], ch.cand_i[r], ch.status[r]
+            c.wire = _WireView(ch.out_s[r], ch.out_i[r])
+            c.exact_ws = ch.exact_ws[j * ch.exact_one:(j + 1) * ch.exact_one]
+        else:
+            c.chunk = None
+            c.ws = torch.empty(nat.scan_workspace_bytes(self.nq_all, v.dim, self.k_scan, v.n), dtype=torch.uint8, device=dev)
+            c.cand_s = torch.empty((self.nq_all, self.k_scan), dtype=torch.float32, device=dev)
+            c.cand_i = torch.empty((self.nq_all, self.k_scan), dtype=torch.int64, device=dev)
+            c.wire = nat.WireBlock(self.nq_all, self.k, dev, self.world, gather=self.multi)   # this rank's (ids | scores) block
+            c.status = torch.zeros(self.nq_all, dtype=torch.int32, device=dev)
+            c.exact_ws = (torch.empty(nat.exact_workspace_bytes(self.nq_all, self.exact_cap), dtype=torch.uint8, device=dev)
+                          if self.refine else None)
         c.graphs = None
         c.chunk_graph = None
         if self.multi:
@@ -292,6 +367,15 @@ class RetrievalEngine:
         if self.exact:
             nat.escalate_exact(qa32, qa16, v.slab, v.shadow, v.n, v.id_base, self.k, c.wire.scores, c.wire.ids, c.status,
                                c.exact_ws, self.exact_cap, scales=v.scales)
+
+    def _seg_search_chunk(self, ch: _Chunk) -> None:   # the chunk's F x nq_all queries x the shard in ONE sweep -> every member's lists
+        v = self.view
+        nat.cosine_topk_cert(ch.q_out, ch.q16, v.slab, v.shadow, v.n, v.dim, self.k_scan, self.k, v.row_err_max,
+                             ch.exact_ws[:ch.exact_all], self.exact_cap, scales=v.scales, id_base=v.id_base, workspace=ch.ws,
+                             cand_scores=ch.cand_s, cand_ids=ch.cand_i, out_scores=ch.out_s, out_ids=ch.out_i, status=ch.status)
+        if self.exact:
+            nat.escalate_exact(ch.q_out, ch.q16, v.slab, v.shadow, v.n, v.id_base, self.k, ch.out_s, ch.out_i, ch.status,
+                               ch.exact_ws[:ch.exact_all], self.exact_cap, scales=v.scales)
 
     def _seg_scan(self, c: _Ctx) -> None:     # the sweep: k' candidates per query (no re-rank configured: the final lists)
         v = self.view
@@ -405,10 +489,17 @@ class RetrievalEngine:
                     if self.search_fuse > 1:
                         j = self.last_search_seg
                         for i0 in range(g.members[0], g.members[-1] + 1, self.search_fuse):
+                            if self.sweep_group > 1:      # (once eagerly: the chunk's kernels are not those of the per-batch warm-up)
+                                with torch.cuda.stream(self.srch_streams[0]):
+                                    self._seg_search_chunk(self.ctxs[i0].chunk)
+                                torch.cuda.synchronize()
                             g_ = torch.cuda.CUDAGraph()
                             with torch.cuda.graph(g_, stream=self.srch_streams[0], capture_error_mode="thread_local"):
-                                for i in range(i0, i0 + self.search_fuse):
-                                    self.segs[j](self.ctxs[i])
+                                if self.sweep_group > 1:
+                                    self._seg_search_chunk(self.ctxs[i0].chunk)
+                                else:
+                                    for i in range(i0, i0 + self.search_fuse):
+                                        self.segs[j](self.ctxs[i])
                             self.ctxs[i0].chunk_graph = g_
                 except Exception as exc:   # noqa: BLE001 -- report and keep going without graphs
                     print(f"[engine] hipGraph capture failed on rank {self.rank} ({exc!r}); launching eagerly", file=sys.stderr, flush=True)
@@ -480,7 +571,8 @@ class RetrievalEngine:
     def describe_lanes(self) -> str:
         if not self.pipelined:
             return "one per batch"
-        return f"{self.n_enc} encoder + {self.n_srch} search (encoder kernels <= 48 KB of LDS)"
+        sweep = f"; {self.sweep_group} batches per sweep" if (self.sweep_group > 1 and self.use_graph) else ""
+        return f"{self.n_enc} encoder + {self.n_srch} search (encoder kernels <= 48 KB of LDS){sweep}"
 
     # ---- the product entry: many query batches through the pipeline -------------------------------------------------
     def search_token_batches(self, batches, overflow_queries: bool = False):
