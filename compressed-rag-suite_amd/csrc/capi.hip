@@ -386,6 +386,21 @@ int crs_merge_topk(const float* scores_dev, const int64_t* ids_dev, int nlists, 
   return e ? hip_fail((hipError_t)e, "merge launch") : CRS_OK;
 }
 
+// crs_merge_sorted / crs_merge_sorted_wire: one check of the sizes (merge_sorted.hip: a list fits the threads' registers and
+// an LDS group up to CRS_MAX_K_CERT entries; the grid is nq x nlists workgroups)
+static bool merge_sorted_sizes_ok(int nlists, int nq, int k_in, int k_out) {
+  return nlists >= 1 && nlists <= 64 && nq >= 1 && nq <= 0x7fffffff / 64 && k_in >= 1 && k_in <= CRS_MAX_K_CERT && k_out >= 1 &&
+         k_out <= CRS_MAX_K_CERT;
+}
+
+int crs_merge_sorted(const float* scores_dev, const int64_t* ids_dev, int nlists, int nq, int k_in,
+                     int k_out, float* out_scores_dev, int64_t* out_ids_dev, void* stream) {
+  if (!merge_sorted_sizes_ok(nlists, nq, k_in, k_out)) return fail(CRS_EINVAL, "bad sizes (k_in, k_out <= CRS_MAX_K_CERT, nlists <= 64)");
+  if (!scores_dev || !ids_dev || !out_scores_dev || !out_ids_dev) return fail(CRS_EINVAL, "null pointer");
+  const int e = crs::merge_sorted_launch_i64(scores_dev, ids_dev, nlists, nq, k_in, k_out, out_scores_dev, out_ids_dev, (hipStream_t)stream);
+  return e ? hip_fail((hipError_t)e, "merge launch") : CRS_OK;
+}
+
 int crs_rescore_f32(const float* q32_dev, int nq, int dim, const float* shadow_dev, int64_t n_rows,
                     int64_t id_base, int k, float* scores_dev, int64_t* ids_dev, void* stream) {
   if (nq <= 0 || dim <= 0 || k <= 0 || k > 64 || n_rows <= 0) return fail(CRS_EINVAL, "bad sizes (k <= 64)");
@@ -628,6 +643,16 @@ int crs_merge_topk_wire(const void* wire_dev, int nlists, int nq, int k_in, int 
   if ((uintptr_t)wire_dev & 7) return fail(CRS_EINVAL, "wire buffer must be 8-byte aligned");
   const int e = crs::merge_launch_wire(wire_dev, crs_wire_bytes(nq, k_in), crs_wire_scores_offset(nq, k_in), nlists, nq,
                                        k_in, k_out, out_scores_dev, out_ids_dev, (hipStream_t)stream);
+  return e ? hip_fail((hipError_t)e, "merge launch") : CRS_OK;
+}
+
+int crs_merge_sorted_wire(const void* wire_dev, int nlists, int nq, int k_in, int k_out,
+                          float* out_scores_dev, int64_t* out_ids_dev, void* stream) {
+  if (!merge_sorted_sizes_ok(nlists, nq, k_in, k_out)) return fail(CRS_EINVAL, "bad sizes (k_in, k_out <= CRS_MAX_K_CERT, nlists <= 64)");
+  if (!wire_dev || !out_scores_dev || !out_ids_dev) return fail(CRS_EINVAL, "null pointer");
+  if ((uintptr_t)wire_dev & 7) return fail(CRS_EINVAL, "wire buffer must be 8-byte aligned");
+  const int e = crs::merge_sorted_launch_wire(wire_dev, crs_wire_bytes(nq, k_in), crs_wire_scores_offset(nq, k_in), nlists, nq,
+                                              k_in, k_out, out_scores_dev, out_ids_dev, (hipStream_t)stream);
   return e ? hip_fail((hipError_t)e, "merge launch") : CRS_OK;
 }
 

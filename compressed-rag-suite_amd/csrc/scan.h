@@ -84,6 +84,12 @@ int merge_launch_i64(const float* scores, const int64_t* ids, int nlists, int nq
 int merge_launch_wire(const void* wire, size_t block_bytes, size_t scores_off, int nlists, int nq, int k_in, int k_out,
                       float* out_scores, int64_t* out_ids, hipStream_t stream);
 
+// merge_sorted.hip: lists that arrive sorted (score desc, id asc, empty slots last), k_in / k_out <= CRS_MAX_K_CERT, nlists <= 64
+int merge_sorted_launch_i64(const float* scores, const int64_t* ids, int nlists, int nq, int k_in, int k_out, float* out_scores,
+                            int64_t* out_ids, hipStream_t stream);
+int merge_sorted_launch_wire(const void* wire, size_t block_bytes, size_t scores_off, int nlists, int nq, int k_in, int k_out,
+                             float* out_scores, int64_t* out_ids, hipStream_t stream);
+
 // convert.hip
 int refine_f32_launch(const float* q32, int nq, int dim, const float* shadow, int64_t n_rows, int64_t id_base,
                       const int64_t* cand, int k_in, int k_out, float* out_s, int64_t* out_i, hipStream_t stream);

@@ -15,6 +15,7 @@
 //   crs::cosine_topk_large_cert / crs::refine_large_cert   the same for 64 < k_out <= 1024: partitioned over-fetch, one
 //                          fp32 re-rank + certificate kernel over every chunk's candidates
 //   crs::merge_topk / crs::merge_topk_wire   cross-shard merge                (new vs the reference)
+//   crs::merge_sorted / crs::merge_sorted_wire   the same for sorted lists, k 65 .. 1024
 // Tensors are torch-owned; every op launches on the CURRENT HIP stream of the tensors' device, so the ops
 // compose with torch streams and hipGraph capture.  Errors of the C ABI surface as RuntimeError (TORCH_CHECK)
 // carrying crs_last_error(); the Python wrappers (rag/_native.py) translate where the reference's types differ.
@@ -418,6 +419,32 @@ void merge_topk_wire_out(const Tensor& wire, int64_t nlists, int64_t nq, int64_t
                          out_ids.data_ptr<int64_t>(), cur_stream(wire)), "crs::merge_topk_wire");
 }
 
+// sorted lists, k up to CRS_MAX_K_CERT (csrc/merge_sorted.hip)
+void merge_sorted_out(const Tensor& scores, const Tensor& ids, int64_t k_out, Tensor out_scores, Tensor out_ids) {
+  want(scores, at::kFloat, "scores");
+  want(ids, at::kLong, "ids");
+  want(out_scores, at::kFloat, "out_scores");
+  want(out_ids, at::kLong, "out_ids");
+  TORCH_CHECK(scores.dim() == 3 && ids.sizes() == scores.sizes(), "scores / ids must be [nlists, nq, k_in]");
+  TORCH_CHECK(out_scores.numel() == scores.size(1) * k_out && out_ids.numel() == scores.size(1) * k_out, "outputs must hold [nq, k_out]");
+  same_device(scores, {&ids, &out_scores, &out_ids}, "crs::merge_sorted");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(scores.device());
+  ok(crs_merge_sorted(scores.data_ptr<float>(), ids.data_ptr<int64_t>(), (int)scores.size(0), (int)scores.size(1), (int)scores.size(2),
+                      (int)k_out, out_scores.data_ptr<float>(), out_ids.data_ptr<int64_t>(), cur_stream(scores)), "crs::merge_sorted");
+}
+
+void merge_sorted_wire_out(const Tensor& wire, int64_t nlists, int64_t nq, int64_t k_in, int64_t k_out, Tensor out_scores, Tensor out_ids) {
+  TORCH_CHECK(wire.is_cuda() && wire.is_contiguous() && wire.scalar_type() == at::kByte, "wire must be a contiguous uint8 device tensor");
+  TORCH_CHECK(nlists >= 0 && (size_t)wire.numel() >= (size_t)nlists * crs_wire_bytes((int)nq, (int)k_in), "wire buffer shorter than nlists * crs_wire_bytes(nq, k_in)");
+  want(out_scores, at::kFloat, "out_scores");
+  want(out_ids, at::kLong, "out_ids");
+  TORCH_CHECK(out_scores.numel() == nq * k_out && out_ids.numel() == nq * k_out, "outputs must hold [nq, k_out]");
+  same_device(wire, {&out_scores, &out_ids}, "crs::merge_sorted_wire");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(wire.device());
+  ok(crs_merge_sorted_wire(wire.data_ptr(), (int)nlists, (int)nq, (int)k_in, (int)k_out, out_scores.data_ptr<float>(),
+                           out_ids.data_ptr<int64_t>(), cur_stream(wire)), "crs::merge_sorted_wire");
+}
+
 // ---- encoder -------------------------------------------------------------------------------------------------
 // desc = [vocab_size, hidden, layers, heads, ffn, max_pos, pooling, flags (CRS_ENC_*, optional)]; weights = [word_emb, pos_emb, type_emb, emb_ln_g, emb_ln_b]
 // followed by 12 tensors per layer in crs_encoder_layer order (w_qkv b_qkv w_o b_o ln1_g ln1_b w_up b_up w_down b_down ln2_g ln2_b).
@@ -494,6 +521,8 @@ TORCH_LIBRARY(crs, m) {
   m.def("merge_topk(Tensor scores, Tensor ids, int k_out) -> (Tensor, Tensor)");
   m.def("merge_topk_out(Tensor scores, Tensor ids, int k_out, Tensor(a!) out_scores, Tensor(b!) out_ids) -> ()");
   m.def("merge_topk_wire_out(Tensor wire, int nlists, int nq, int k_in, int k_out, Tensor(a!) out_scores, Tensor(b!) out_ids) -> ()");
+  m.def("merge_sorted_out(Tensor scores, Tensor ids, int k_out, Tensor(a!) out_scores, Tensor(b!) out_ids) -> ()");
+  m.def("merge_sorted_wire_out(Tensor wire, int nlists, int nq, int k_in, int k_out, Tensor(a!) out_scores, Tensor(b!) out_ids) -> ()");
   m.def("encoder_forward(Tensor ids, Tensor lens, Tensor[] weights, int[] desc, float ln_eps, Tensor(a!) workspace, Tensor(b!) out, "
         "Tensor(c!)? q16_out, int slab_type, bool normalize, Tensor(d!)? hidden_out) -> ()");
 }
@@ -516,5 +545,7 @@ TORCH_LIBRARY_IMPL(crs, CUDA, m) {   // the HIP backend of torch-ROCm dispatches
   m.impl("merge_topk", &merge_topk);
   m.impl("merge_topk_out", &merge_topk_out);
   m.impl("merge_topk_wire_out", &merge_topk_wire_out);
+  m.impl("merge_sorted_out", &merge_sorted_out);
+  m.impl("merge_sorted_wire_out", &merge_sorted_wire_out);
   m.impl("encoder_forward", &encoder_forward);
 }

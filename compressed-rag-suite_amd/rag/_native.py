@@ -21,6 +21,7 @@ SLAB_F16 = 0
 SLAB_I8 = 1
 MAX_K = 64
 MAX_K_CERT = 1024          # CRS_MAX_K_CERT: largest top_k with a certificate (partitioned over-fetch, csrc/large_k.hip)
+MERGE_SORTED_MAX_LISTS = 64   # crs_merge_sorted: lists per query (csrc/merge_sorted.hip)
 LARGE_K_MAX_PARTS = 64     # chunks of the partition (x 64 candidates: at most 4096 per query)
 EXACT_MAX_CAP = 13312      # CRS_EXACT_MAX_CAP: longest per-query row list of crs_escalate_exact
 EXACT_CAP = 1024           # default list length (12 KB of LDS per query in the re-rank)
@@ -45,6 +46,7 @@ _SIGNATURES = {
                                 c_int64, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     "crs_merge_topk": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                c_void_p]),
+    "crs_merge_sorted": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "crs_rescore_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p,
                                 c_void_p, c_void_p]),
     "crs_score_rows_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
@@ -69,6 +71,7 @@ _SIGNATURES = {
     "crs_wire_bytes": (c_size_t, [c_int, c_int]),
     "crs_wire_scores_offset": (c_size_t, [c_int, c_int]),
     "crs_merge_topk_wire": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "crs_merge_sorted_wire": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "crs_scan_plan_describe": (c_int, [c_int, c_int, c_int, c_int64, c_int, ctypes.c_char_p, c_size_t]),
     "crs_stream_create_cu_masked": (c_int, [c_int, c_int, POINTER(c_void_p)]),
     "crs_stream_destroy": (c_int, [c_void_p]),
@@ -267,6 +270,19 @@ def merge_topk(scores, ids, k_out: int, out_scores=None, out_ids=None):
     out_i = out_ids if out_ids is not None else torch.empty((nq, k_out), dtype=torch.int64, device=scores.device)
     with _translate():
         ops().merge_topk_out(scores, ids, int(k_out), out_s, out_i)
+    return out_s, out_i
+
+
+def merge_sorted(scores, ids, k_out: int, out_scores=None, out_ids=None):
+    """merge_topk for k above MAX_K: scores/ids cuda [G, nq, k_in], every list ALREADY sorted (score desc, id asc, empty slots
+    (-inf, -1) last), ids >= 0 distinct across lists -> the first k_out of their union, same bits, same order.
+    G <= 64, k_in and k_out <= MAX_K_CERT (csrc/merge_sorted.hip)."""
+    import torch
+    g, nq, k_in = scores.shape
+    out_s = out_scores if out_scores is not None else torch.empty((nq, k_out), dtype=torch.float32, device=scores.device)
+    out_i = out_ids if out_ids is not None else torch.empty((nq, k_out), dtype=torch.int64, device=scores.device)
+    with _translate():
+        ops().merge_sorted_out(scores, ids, int(k_out), out_s, out_i)
     return out_s, out_i
 
 
@@ -477,6 +493,16 @@ def merge_topk_wire(gathered, nlists: int, nq: int, k_in: int, k_out: int, out_s
     out_i = out_ids if out_ids is not None else torch.empty((nq, k_out), dtype=torch.int64, device=gathered.device)
     with _translate():
         ops().merge_topk_wire_out(gathered, int(nlists), int(nq), int(k_in), int(k_out), out_s, out_i)
+    return out_s, out_i
+
+
+def merge_sorted_wire(gathered, nlists: int, nq: int, k_in: int, k_out: int, out_scores=None, out_ids=None):
+    """merge_sorted over the all-gathered WireBlocks (cuda uint8 [nlists * crs_wire_bytes(nq, k_in)])."""
+    import torch
+    out_s = out_scores if out_scores is not None else torch.empty((nq, k_out), dtype=torch.float32, device=gathered.device)
+    out_i = out_ids if out_ids is not None else torch.empty((nq, k_out), dtype=torch.int64, device=gathered.device)
+    with _translate():
+        ops().merge_sorted_wire_out(gathered, int(nlists), int(nq), int(k_in), int(k_out), out_s, out_i)
     return out_s, out_i
 
 

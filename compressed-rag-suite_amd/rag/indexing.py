@@ -1060,21 +1060,27 @@ class VectorStore:
             with torch.cuda.device(dev0):
                 gs = torch.stack([s.to(dev0) for s, _ in parts]).contiguous()
                 gi = torch.stack([i.to(dev0) for _, i in parts]).contiguous()
-                s, i = nat.merge_topk(gs, gi, top_k) if top_k <= nat.MAX_K else self._order(
-                    gs.permute(1, 0, 2).reshape(nq, -1), gi.permute(1, 0, 2).reshape(nq, -1), top_k)
+                if top_k <= nat.MAX_K:
+                    s, i = nat.merge_topk(gs, gi, top_k)
+                elif top_k <= nat.MAX_K_CERT and len(parts) <= nat.MERGE_SORTED_MAX_LISTS:
+                    s, i = nat.merge_sorted(gs, gi, top_k)      # every shard's list arrives sorted (score desc, row asc): co-ranking
+                else:
+                    s, i = self._order(gs.permute(1, 0, 2).reshape(nq, -1), gi.permute(1, 0, 2).reshape(nq, -1), top_k)
         else:
             s, i = parts[0]
         dist = self._dist()
         if dist is not None:           # SPMD: ONE all-gather of the wire blocks, k-way merge on every rank
-            if top_k > nat.MAX_K:
-                raise ValueError(f"top_k {top_k} > {nat.MAX_K} is not supported on an SPMD-sharded store")
+            if top_k > nat.MAX_K_CERT:
+                raise ValueError(f"top_k {top_k} > {nat.MAX_K_CERT} is not supported on an SPMD-sharded store")
             key = (nq, top_k, dist.get_world_size())
             wb = self._wire.get(key)
             if wb is None:
                 wb = self._wire[key] = nat.WireBlock(nq, top_k, col.device, dist.get_world_size())
             wb.scores.copy_(s)
             wb.ids.copy_(i)
-            s, i = _shard.allgather_merge(dist, wb.buf, wb.gathered, nq, top_k, top_k, nat.merge_topk_wire)
+            # above MAX_K the shards' lists (certified, escalated or _topk_large's) arrive sorted: the co-ranking merge
+            s, i = _shard.allgather_merge(dist, wb.buf, wb.gathered, nq, top_k, top_k,
+                                          nat.merge_topk_wire if top_k <= nat.MAX_K else nat.merge_sorted_wire)
         return s, i
 
     def _filter_entry(self, where: Optional[dict], where_document: Optional[dict]):

@@ -106,6 +106,18 @@ int crs_cosine_topk(const void* q16_dev, int nq, int dim, int slab_type, const v
 int crs_merge_topk(const float* scores_dev, const int64_t* ids_dev, int nlists, int nq, int k_in,
                    int k_out, float* out_scores_dev, int64_t* out_ids_dev, void* stream);
 
+/* The same merge for lists that arrive SORTED, for k above CRS_MAX_K (additive to ABI 3; csrc/merge_sorted.hip): what the shards
+ * of a store return for top_k 65 .. CRS_MAX_K_CERT (crs_cosine_topk_large_cert + crs_escalate_exact).  Precondition: every list
+ * [l, q, :] is already in the order of the results (score desc, id asc) with its empty slots (id < 0, any score) at the tail,
+ * and ids >= 0 are distinct across the lists of a query.  The kernel does no arithmetic and no sort: an entry's output slot is
+ * its position plus one binary-search count per other list, so out_scores / out_ids [nq, k_out] hold the input's own bits, in
+ * the same order, with (-inf, -1) behind the last valid entry.  Lists that break the precondition give an unspecified order,
+ * never an access outside the buffers.
+ * Limits: 1 <= nlists <= 64, 1 <= k_in <= CRS_MAX_K_CERT, 1 <= k_out <= CRS_MAX_K_CERT; k_out may exceed k_in; nlists == 1 copies
+ * or truncates. */
+int crs_merge_sorted(const float* scores_dev, const int64_t* ids_dev, int nlists, int nq, int k_in,
+                     int k_out, float* out_scores_dev, int64_t* out_ids_dev, void* stream);
+
 /* Exact fp32 re-score of candidates: out[i, j] = <q32[i, :], shadow[ids[i, j], :]> for ids >= 0
  * (id_base subtracted first), then each row re-sorted by (score desc, id asc). Used when the
  * store keeps an fp32 shadow and over-fetches (recall vs an exact fp32 ranking). */
@@ -209,6 +221,11 @@ size_t crs_wire_bytes(int nq, int k);
 size_t crs_wire_scores_offset(int nq, int k);
 int crs_merge_topk_wire(const void* wire_dev, int nlists, int nq, int k_in, int k_out,
                         float* out_scores_dev, int64_t* out_ids_dev, void* stream);
+
+/* crs_merge_sorted over the wire layout (same precondition and limits; wire_dev 8-byte aligned): the exchange of a sharded
+ * search with top_k above CRS_MAX_K. */
+int crs_merge_sorted_wire(const void* wire_dev, int nlists, int nq, int k_in, int k_out,
+                          float* out_scores_dev, int64_t* out_ids_dev, void* stream);
 
 /* Which scan kernel (and launch geometry) crs_cosine_topk would use for these sizes on the current
  * device, as text, e.g. "scan_tb_kernel<384,32,4,0> streams=768 qblocks=1 kp=5 + merge + refine".

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Build-time guard on the kernels' register budgets and on the hand-counted asm loops.
 
-  python tools/check_resources.py [file.hip ...]        (default: every csrc/*.hip; exit 1 on a violation)
+  python tools/check_resources.py [--list] [file.hip ...]        (default: every csrc/*.hip; exit 1 on a violation)
+  --list also prints one line per kernel: file, kernel, VGPRs, scratch bytes per lane (the lines kept under profiles/)
 
 1. Scratch.  Compiles each translation unit for gfx950 with -Rpass-analysis=kernel-resource-usage and fails when a kernel
    uses scratch memory (register spills) unless it is on the ALLOW list below -- the list names the cold instantiations that
@@ -85,7 +86,7 @@ def analyse(path):
     return path, rows, asm_bad
 
 
-def main(files):
+def main(files, list_rows=False):
     files = files or sorted(glob.glob(os.path.join(CSRC, "*.hip")))
     failures, allowed, n_kernels = [], [], 0
     with cf.ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
@@ -95,6 +96,8 @@ def main(files):
                 continue
             n_kernels += len(rows)
             for name, vgpr, scratch in rows:
+                if list_rows:
+                    print(f"  kernel    {os.path.basename(path)}: {name[:110]}: {vgpr} VGPRs, {scratch} B/lane of scratch")
                 if scratch:
                     why = next((w for pat, w in ALLOW if re.search(pat, name)), None)
                     (allowed if why else failures).append(f"{os.path.basename(path)}: {name[:110]}: {scratch} B/lane of scratch, {vgpr} VGPRs"
@@ -110,4 +113,4 @@ def main(files):
 
 
 if __name__ == "__main__":
-    sys.exit(main([os.path.join(CSRC, a) if not os.path.exists(a) else a for a in sys.argv[1:]]))
+    sys.exit(main([os.path.join(CSRC, a) if not os.path.exists(a) else a for a in sys.argv[1:] if a != "--list"], "--list" in sys.argv[1:]))
