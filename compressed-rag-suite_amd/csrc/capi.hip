@@ -401,6 +401,17 @@ int crs_merge_sorted(const float* scores_dev, const int64_t* ids_dev, int nlists
   return e ? hip_fail((hipError_t)e, "merge launch") : CRS_OK;
 }
 
+int crs_mmr_order(const float* vecs_dev, int64_t n_rows, int dim, const int64_t* rows_dev, const double* rel_dev,
+                  const int32_t* counts_dev, int nq, int m_max, double lam, int32_t* order_dev, void* stream) {
+  if (nq < 0 || dim <= 0 || n_rows < 0) return fail(CRS_EINVAL, "bad nq/dim/n_rows");
+  if (m_max < 1 || m_max > CRS_MAX_K) return fail(CRS_EINVAL, "bad m_max (1 <= m_max <= CRS_MAX_K)");
+  if (!(lam >= 0.0 && lam <= 1.0)) return fail(CRS_EINVAL, "lam must lie in [0, 1]");
+  if (!vecs_dev || !rows_dev || !rel_dev || !counts_dev || !order_dev) return fail(CRS_EINVAL, "null pointer");
+  if (nq == 0) return CRS_OK;
+  const int e = crs::mmr_order_launch(vecs_dev, n_rows, dim, rows_dev, rel_dev, counts_dev, nq, m_max, lam, order_dev, (hipStream_t)stream);
+  return e ? hip_fail((hipError_t)e, "mmr_order launch") : CRS_OK;
+}
+
 int crs_rescore_f32(const float* q32_dev, int nq, int dim, const float* shadow_dev, int64_t n_rows,
                     int64_t id_base, int k, float* scores_dev, int64_t* ids_dev, void* stream) {
   if (nq <= 0 || dim <= 0 || k <= 0 || k > 64 || n_rows <= 0) return fail(CRS_EINVAL, "bad sizes (k <= 64)");

@@ -90,6 +90,10 @@ int merge_sorted_launch_i64(const float* scores, const int64_t* ids, int nlists,
 int merge_sorted_launch_wire(const void* wire, size_t block_bytes, size_t scores_off, int nlists, int nq, int k_in, int k_out,
                              float* out_scores, int64_t* out_ids, hipStream_t stream);
 
+// mmr.hip: greedy MMR ordering of lists of <= CRS_MAX_K shadow rows, one workgroup per list
+int mmr_order_launch(const float* vecs, int64_t n_rows, int dim, const int64_t* rows, const double* rel, const int* counts, int nq,
+                     int m_max, double lam, int* order, hipStream_t stream);
+
 // convert.hip
 int refine_f32_launch(const float* q32, int nq, int dim, const float* shadow, int64_t n_rows, int64_t id_base,
                       const int64_t* cand, int k_in, int k_out, float* out_s, int64_t* out_i, hipStream_t stream);

@@ -16,6 +16,7 @@
 //                          fp32 re-rank + certificate kernel over every chunk's candidates
 //   crs::merge_topk / crs::merge_topk_wire   cross-shard merge                (new vs the reference)
 //   crs::merge_sorted / crs::merge_sorted_wire   the same for sorted lists, k 65 .. 1024
+//   crs::mmr_order         replaces the greedy MMR loop of _apply_diversity  (reference rag/retrieval.py:219-277)
 // Tensors are torch-owned; every op launches on the CURRENT HIP stream of the tensors' device, so the ops
 // compose with torch streams and hipGraph capture.  Errors of the C ABI surface as RuntimeError (TORCH_CHECK)
 // carrying crs_last_error(); the Python wrappers (rag/_native.py) translate where the reference's types differ.
@@ -445,6 +446,26 @@ void merge_sorted_wire_out(const Tensor& wire, int64_t nlists, int64_t nq, int64
                            out_ids.data_ptr<int64_t>(), cur_stream(wire)), "crs::merge_sorted_wire");
 }
 
+// ---- diversity re-ordering (csrc/mmr.hip) -------------------------------------------------------------------------
+// vecs fp32 [>= n_rows, dim]; rows int64 / rel fp64 / order int32 [nq, m_max]; counts int32 [nq]
+void mmr_order_out(const Tensor& vecs, int64_t n_rows, const Tensor& rows, const Tensor& rel, const Tensor& counts, double lam, Tensor order) {
+  want(vecs, at::kFloat, "vecs");
+  want(rows, at::kLong, "rows");
+  want(rel, at::kDouble, "rel");
+  want(counts, at::kInt, "counts");
+  want(order, at::kInt, "order");
+  same_device(vecs, {&rows, &rel, &counts, &order}, "crs::mmr_order");
+  TORCH_CHECK(vecs.dim() == 2 && n_rows >= 0 && n_rows <= vecs.size(0), "vecs must be fp32 [>= n_rows, dim]");
+  TORCH_CHECK(rows.dim() == 2 && rel.sizes() == rows.sizes() && order.sizes() == rows.sizes(), "rows / rel / order must be [nq, m_max]");
+  TORCH_CHECK(counts.dim() == 1 && counts.size(0) == rows.size(0), "counts must be int32 [nq]");
+  TORCH_CHECK(rows.size(0) <= 0x7fffffff, "too many lists");
+  if (rows.size(0) == 0) return;
+  c10::hip::HIPGuardMasqueradingAsCUDA g(vecs.device());
+  ok(crs_mmr_order(vecs.data_ptr<float>(), n_rows, (int)vecs.size(1), rows.data_ptr<int64_t>(), rel.data_ptr<double>(),
+                   counts.data_ptr<int32_t>(), (int)rows.size(0), (int)rows.size(1), lam, order.data_ptr<int32_t>(), cur_stream(vecs)),
+     "crs::mmr_order");
+}
+
 // ---- encoder -------------------------------------------------------------------------------------------------
 // desc = [vocab_size, hidden, layers, heads, ffn, max_pos, pooling, flags (CRS_ENC_*, optional)]; weights = [word_emb, pos_emb, type_emb, emb_ln_g, emb_ln_b]
 // followed by 12 tensors per layer in crs_encoder_layer order (w_qkv b_qkv w_o b_o ln1_g ln1_b w_up b_up w_down b_down ln2_g ln2_b).
@@ -523,6 +544,7 @@ TORCH_LIBRARY(crs, m) {
   m.def("merge_topk_wire_out(Tensor wire, int nlists, int nq, int k_in, int k_out, Tensor(a!) out_scores, Tensor(b!) out_ids) -> ()");
   m.def("merge_sorted_out(Tensor scores, Tensor ids, int k_out, Tensor(a!) out_scores, Tensor(b!) out_ids) -> ()");
   m.def("merge_sorted_wire_out(Tensor wire, int nlists, int nq, int k_in, int k_out, Tensor(a!) out_scores, Tensor(b!) out_ids) -> ()");
+  m.def("mmr_order_out(Tensor vecs, int n_rows, Tensor rows, Tensor rel, Tensor counts, float lam, Tensor(a!) order) -> ()");
   m.def("encoder_forward(Tensor ids, Tensor lens, Tensor[] weights, int[] desc, float ln_eps, Tensor(a!) workspace, Tensor(b!) out, "
         "Tensor(c!)? q16_out, int slab_type, bool normalize, Tensor(d!)? hidden_out) -> ()");
 }
@@ -547,5 +569,6 @@ TORCH_LIBRARY_IMPL(crs, CUDA, m) {   // the HIP backend of torch-ROCm dispatches
   m.impl("merge_topk_wire_out", &merge_topk_wire_out);
   m.impl("merge_sorted_out", &merge_sorted_out);
   m.impl("merge_sorted_wire_out", &merge_sorted_wire_out);
+  m.impl("mmr_order_out", &mmr_order_out);
   m.impl("encoder_forward", &encoder_forward);
 }

@@ -47,6 +47,7 @@ _SIGNATURES = {
     "crs_merge_topk": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                c_void_p]),
     "crs_merge_sorted": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "crs_mmr_order": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_void_p, c_void_p]),
     "crs_rescore_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p,
                                 c_void_p, c_void_p]),
     "crs_score_rows_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
@@ -284,6 +285,18 @@ def merge_sorted(scores, ids, k_out: int, out_scores=None, out_ids=None):
     with _translate():
         ops().merge_sorted_out(scores, ids, int(k_out), out_s, out_i)
     return out_s, out_i
+
+
+def mmr_order(vecs, n_rows: int, rows, rel, counts, lam: float, out=None):
+    """Greedy MMR order of nq lists of rows of `vecs` (cuda fp32 [>= n_rows, dim]) in one launch (crs_mmr_order, csrc/mmr.hip):
+    rows int64 / rel fp64 [nq, m_max <= MAX_K], counts int32 [nq], lam = 1 - diversity_penalty -> order int32 [nq, m_max], the
+    first counts[i] slots of list i its positions in MMR order, the others -1.  No host sync."""
+    import torch
+    if out is None:
+        out = torch.empty(rows.shape, dtype=torch.int32, device=vecs.device)
+    with _translate():
+        ops().mmr_order_out(vecs, int(n_rows), rows, rel, counts, float(lam), out)
+    return out
 
 
 def rescore_f32(q32, shadow, n_rows: int, id_base: int, scores, ids) -> None:

@@ -1148,6 +1148,33 @@ class VectorStore:
         idx = torch.as_tensor(np.asarray(rows, dtype=np.int64), device=sh.device)
         return sh.shadow[idx].cpu().numpy()
 
+    def mmr_order(self, rows, rel, counts, lam: float):
+        """Greedy MMR order of many result lists at once, on the device (crs_mmr_order, csrc/mmr.hip): rows int64 / rel fp64
+        [nq, m_max <= MAX_K] (sidecar rows and their relevance, list order), counts [nq], lam = 1 - diversity_penalty -> numpy
+        int32 [nq, m_max], the first counts[i] slots the positions of list i in MMR order, the others -1.  One upload of the
+        three arrays, one launch over the fp32 rows in place, one readback.  None when the store cannot serve it (the
+        conditions of rows_f32: no fp32 rows kept, or not a single identity shard) or a list is longer than MAX_K."""
+        import torch
+        col = self.collection
+        if col is None or len(col.shards) != 1 or not col.shards[0].identity or col.shards[0].shadow is None:
+            return None
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        if rows.ndim != 2 or not 1 <= rows.shape[1] <= nat.MAX_K:
+            return None
+        sh = col.shards[0]
+        nq, m_max = rows.shape
+        # one host block -> one copy: [rows int64 | rel fp64 | counts int32 (padded to 8 bytes)]
+        block = np.empty(2 * nq * m_max + (nq + 1) // 2, dtype=np.int64)
+        block[:nq * m_max] = rows.ravel()
+        block[nq * m_max:2 * nq * m_max].view(np.float64)[:] = np.asarray(rel, dtype=np.float64).ravel()
+        block[2 * nq * m_max:].view(np.int32)[:nq] = np.asarray(counts, dtype=np.int32)
+        dev = torch.from_numpy(block).to(sh.device)
+        with torch.cuda.device(sh.device):
+            order = nat.mmr_order(sh.shadow, sh.n, dev[:nq * m_max].view(nq, m_max),
+                                  dev[nq * m_max:2 * nq * m_max].view(torch.float64).view(nq, m_max),
+                                  dev[2 * nq * m_max:].view(torch.int32)[:nq], float(lam))
+        return order.cpu().numpy()
+
     def search_rows(self, query_embeddings, top_k: int):
         """search_batch without the sidecar lookup: (scores fp32 [nq, k], sidecar rows int64 [nq, k]) as numpy, best first,
         -1 rows = fewer than k hits.  (retrieve_batch builds its dicts straight from these.)"""

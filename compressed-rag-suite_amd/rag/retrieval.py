@@ -3,9 +3,12 @@
 Same class / method names, arguments, return dicts and numeric behaviour as
 /root/reference/rag/retrieval.py (``ContextRetriever`` :13-277) -- pinned bit for bit by
 tests/golden/retrieve_cases.json, which holds the reference class's own outputs.  The scoring,
-lexical rerank and MMR steps are a few hundred scalar operations per query and stay on the host
-in fp64 Python exactly like the reference; the heavy steps they call (``embed``, ``search``) run
-on the GPU.
+lexical rerank and MMR steps are a few hundred scalar operations per query and by default stay on
+the host in fp64 Python exactly like the reference; the heavy steps they call (``embed``,
+``search``) run on the GPU.  Opt-in, ``mmr_vectors: 'device'``: ``retrieve_batch`` orders the MMR
+lists of all its queries with one kernel launch over the store's fp32 rows (csrc/mmr.hip) instead
+of the Python loop -- same rule, cosines in fp32 on the device; scoring, threshold and the lexical
+rerank stay on the host.
 
 Additive: ``retrieve_batch`` embeds and searches many queries in one launch each and then applies
 the identical per-query post-processing; ``reuse_index_embeddings`` is NOT offered because the
@@ -38,10 +41,14 @@ class ContextRetriever:
         # additive: where the MMR step takes the chunks' vectors from.  'reembed' = encode the chunk texts again, as the
         # reference does (rag/retrieval.py:238-239); 'index' = the fp32 rows the store kept when those very texts were
         # indexed (the same encoder's output for the same text: equal up to the rounding of a different batch composition;
-        # no tokenisation, no encoder pass); 'auto' = retrieve() re-embeds (reference parity), retrieve_batch() reads the index
+        # no tokenisation, no encoder pass); 'auto' = retrieve() re-embeds (reference parity), retrieve_batch() reads the index;
+        # 'device' = the index rows again, ordered by ONE kernel launch per retrieve_batch call (VectorStore.mmr_order) instead of
+        # the Python loop; lists longer than 64 and stores that cannot serve it (several shards, no fp32 rows) run as 'auto'
         self.mmr_vectors = config.get('mmr_vectors', 'auto')
-        if self.mmr_vectors not in ('auto', 'reembed', 'index'):
-            raise ValueError(f"mmr_vectors must be 'auto', 'reembed' or 'index', got {self.mmr_vectors!r}")
+        if self.mmr_vectors not in ('auto', 'reembed', 'index', 'device'):
+            raise ValueError(f"mmr_vectors must be 'auto', 'reembed', 'index' or 'device', got {self.mmr_vectors!r}")
+        self.last_mmr = {'mode': 'host', 'lists': 0}      # which path ordered the lists of the last retrieve_batch call
+        self._token_sets: Dict[str, frozenset] = {}       # _rerank: text -> its lower-cased token set
         self._engine, self._engine_key = None, None
         self.distance_metric = self._get_distance_metric()
         logger.info(f"Using distance metric: {self.distance_metric}")
@@ -114,7 +121,7 @@ class ContextRetriever:
             metas = results['metadatas'][0] if results['metadatas'] else None
             chunks = self._hits_to_chunks(results['ids'][0], results['documents'][0], metas,
                                           results['distances'][0])
-            if self.mmr_vectors == 'index' and self.diversity_penalty > 0:
+            if self.mmr_vectors in ('index', 'device') and self.diversity_penalty > 0:
                 return self.retrieve_batch([query], top_k=top_k)[0] if filters is None else self._post_process(query, chunks, k)
             return self._post_process(query, chunks, k)
         except Exception as e:
@@ -256,7 +263,10 @@ class ContextRetriever:
                 else:
                     chunks = chunks[:k]
                 per_query.append(chunks)
-        from_index = self.mmr_vectors in ('auto', 'index') and ids_l is not None and hasattr(store, 'rows_f32')
+        self.last_mmr = {'mode': 'host', 'lists': sum(1 for chunks in per_query if len(chunks) > 1) if self.diversity_penalty > 0 else 0}
+        if self.diversity_penalty > 0 and self.mmr_vectors == 'device' and ids_l is not None and self._mmr_on_device(per_query, row_of):
+            return per_query
+        from_index = self.mmr_vectors in ('auto', 'index', 'device') and ids_l is not None and hasattr(store, 'rows_f32')
         if self.diversity_penalty > 0 and from_index:
             # the chunks' vectors straight from the index (one gather for the whole batch), then the reference's greedy MMR
             need = sorted({row_of[id(c)] for chunks in per_query if len(chunks) > 1 for c in chunks})
@@ -282,17 +292,58 @@ class ContextRetriever:
                              if len(chunks) > 1 else chunks for chunks in per_query]
         return per_query
 
+    def _mmr_on_device(self, per_query: List[List[Dict]], row_of: Dict[int, int]) -> bool:
+        """Re-order, in place, every list of `per_query` with more than one chunk by the store's MMR kernel: one padded
+        [lists, longest] block of sidecar rows and fp64 scores, one VectorStore.mmr_order call.  False (nothing changed) when a
+        list is longer than the kernel's 64 or the store answers None: the caller goes on with the host path."""
+        store = self.vector_store
+        todo = [p for p, chunks in enumerate(per_query) if len(chunks) > 1]
+        if not todo:
+            return True
+        m_max = max(len(per_query[p]) for p in todo)
+        if m_max > 64 or not hasattr(store, 'mmr_order'):
+            return False
+        rows = np.full((len(todo), m_max), -1, dtype=np.int64)
+        rel = np.zeros((len(todo), m_max), dtype=np.float64)
+        counts = np.empty(len(todo), dtype=np.int32)
+        for i, p in enumerate(todo):
+            chunks = per_query[p]
+            counts[i] = len(chunks)
+            rows[i, :len(chunks)] = [row_of[id(c)] for c in chunks]
+            rel[i, :len(chunks)] = [c['score'] for c in chunks]
+        order = store.mmr_order(rows, rel, counts, 1.0 - self.diversity_penalty)
+        if order is None:
+            return False
+        for i, p in enumerate(todo):
+            chunks = per_query[p]
+            per_query[p] = [chunks[j] for j in order[i, :len(chunks)].tolist()]
+        self.last_mmr = {'mode': 'device', 'lists': len(todo)}
+        return True
+
     def get_context_string(self, query: str, top_k: Optional[int] = None, separator: str = "\n\n") -> str:
         chunks = self.retrieve(query, top_k=top_k)
         return separator.join(chunk['text'] for chunk in chunks) if chunks else ""
 
     # ---- rerank / diversity ----------------------------------------------------------------------
+    TOKEN_SET_CACHE_CAP = 65536       # entries; the cache is dropped whole when it passes this
+
+    def _tokens_of(self, text: str) -> frozenset:
+        """set(text.lower().split()), kept per text string: the same chunks come back for query after query.  Keyed by the
+        text itself, so a deleted, updated or upserted chunk can never meet another text's set."""
+        cache = self._token_sets
+        got = cache.get(text)
+        if got is None:
+            if len(cache) >= self.TOKEN_SET_CACHE_CAP:
+                cache.clear()
+            got = cache[text] = frozenset(text.lower().split())
+        return got
+
     def _rerank(self, query: str, chunks: List[Dict], top_k: int) -> List[Dict]:
         """70 % semantic score + 30 % fraction of query tokens present in the chunk."""
         wanted = set(query.lower().split())
         norm = max(len(wanted), 1)
         for chunk in chunks:
-            hits = len(wanted & set(chunk['text'].lower().split()))
+            hits = len(wanted & self._tokens_of(chunk['text']))
             chunk['rerank_score'] = chunk['score'] * 0.7 + (hits / norm) * 0.3
         chunks.sort(key=lambda c: c.get('rerank_score', c['score']), reverse=True)
         return chunks[:top_k]

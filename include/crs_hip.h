@@ -211,6 +211,23 @@ int crs_refine_large_cert(const float* q32_dev, const void* q16_dev, int nq, int
                           int64_t chunk_rows, int k_out, float row_err_max, float* out_scores_dev, int64_t* out_ids_dev,
                           int32_t* status_dev, void* exact_ws_dev, size_t exact_ws_bytes, int cap, void* stream);
 
+/* ---- diversity re-ordering: replaces the greedy MMR loop of ContextRetriever._apply_diversity -- rag/retrieval.py:219-277 ----
+ * (additive to ABI 3; csrc/mmr.hip).  Orders `nq` lists of at most m_max <= CRS_MAX_K rows of one shard's fp32 rows in one launch,
+ * one workgroup per list, reading the rows in place:
+ *   vecs_dev    fp32 [n_rows, dim], the shard's shadow
+ *   rows_dev    int64 [nq, m_max]   row of each list entry; an entry whose row is outside [0, n_rows) is never read and behaves
+ *                                   as a zero vector
+ *   rel_dev     fp64 [nq, m_max]    the relevance the host computed for each entry (the chunk's 'score'), in list order
+ *   counts_dev  int32 [nq]          entries per list (clamped to [0, m_max])
+ *   lam         1 - diversity_penalty, in [0, 1]
+ *   order_dev   int32 [nq, m_max]   out: the first counts[i] slots are the list's positions in MMR order, the others -1
+ * Position 0 is taken first.  Every candidate's `closest` starts at 0 and becomes max(closest, cos(candidate, newest pick)) after
+ * each pick; cos = dot / (|a| |b|) in fp32 (fp32 products, fp32 accumulation; 0 when a norm is 0, never NaN);
+ * value = lam * rel - (1 - lam) * closest in fp64; the largest value wins, equal values go to the lowest position -- the
+ * reference's strict `>` over the pending candidates in ascending order.  No host synchronisation, no workspace. */
+int crs_mmr_order(const float* vecs_dev, int64_t n_rows, int dim, const int64_t* rows_dev, const double* rel_dev,
+                  const int32_t* counts_dev, int nq, int m_max, double lam, int32_t* order_dev, void* stream);
+
 /* ---- one-collective exchange (ONE all-gather per query batch) ------------------
  * A rank's per-shard result travels as one contiguous "wire block":
  *     [ ids int64 [nq, k] | scores fp32 [nq, k] | pad to 8 bytes ]        crs_wire_bytes(nq, k) bytes
