@@ -6,7 +6,7 @@ is the rate the plugin surface reaches.  The reference times one query at a time
 
 One BATCH of Qb queries = device segments with the (optional) collectives between them:
     E  encode   token ids [Qb, S] -> fp32 unit embeddings + the scan's fp16 query block        (crs::encoder_forward)
-    S  search   exact scan of this rank's shard, over-fetching k' candidates,
+    S  search   (rag/_search.py, as the store's) exact scan of this rank's shard, over-fetching k' candidates,
                 -> fp32 re-rank against the shadow + per-query exactness certificate            (crs::cosine_topk_cert)
                 -> escalation of unproven queries, a no-op launch when all are proven           (crs::escalate_exact)
                 -> best k in this rank's wire block
@@ -33,26 +33,14 @@ from __future__ import annotations
 
 import os
 import sys
-from dataclasses import dataclass
-from typing import List, Optional
+from typing import List
 
 from rag import _native as nat
+from rag import _search
+from rag._search import SearchBuffers, ShardView   # noqa: F401 -- ShardView: what callers build an engine from
 
 
-@dataclass
-class ShardView:
-    """The rows of ONE device that an engine searches (tensors stay owned by the store / the caller)."""
-    slab: object                 # cuda fp16 | int8 [>= n, pdim]
-    scales: object               # cuda fp32 [>= n] (int8) or None
-    shadow: object               # cuda fp32 [>= n, dim] or None (no fp32 re-rank then)
-    n: int
-    dim: int
-    slab_type: int
-    id_base: int = 0             # added to local rows: the shard's first global row
-    row_err_max: float = -1.0    # tracked |stored row - fp32 row|_2 maximum (< 0: the analytic worst case)
-
-
-class _Ctx:
+class _Ctx(SearchBuffers):
     """Buffers of one in-flight query batch (a batch touches nothing outside its _Ctx + read-only state)."""
 
 
@@ -60,7 +48,7 @@ class _Group:
     """Buffers of one encoder forward: the token / embedding blocks of G consecutive batches (G = 1: of one batch)."""
 
 
-class _Chunk:
+class _Chunk(SearchBuffers):
     """Blocks of the F buffer sets whose searches share one sweep (their attributes are views of these)."""
 
 
@@ -153,8 +141,7 @@ class RetrievalEngine:
         self.multi = dist is not None
         self.k, self.seq = int(top_k), int(seq)
         self.refine = bool(refine) and view.shadow is not None
-        self.exact = (view.slab_type == nat.SLAB_F16) if exact == "auto" else bool(exact)
-        self.exact = self.exact and self.refine
+        self.exact = self.refine and _search.escalates(exact, view.slab_type)
         self.exact_cap = int(exact_cap)
         self.encode = bool(encode)
         qb = int(queries_per_batch)
@@ -271,7 +258,7 @@ class RetrievalEngine:
         F, nq = self.sweep_group, self.nq_all
         ch = _Chunk()
         lo, hi = slot0 * self.q_loc, (slot0 + F) * self.q_loc
-        ch.q_out, ch.q16 = grp.q_out[lo:hi], grp.q16[lo:hi]
+        ch.qa32, ch.qa16 = grp.q_out[lo:hi], grp.q16[lo:hi]
         ch.cand_s = torch.empty((F * nq, self.k_scan), dtype=torch.float32, device=dev)
         ch.cand_i = torch.empty((F * nq, self.k_scan), dtype=torch.int64, device=dev)
         ch.out_s = torch.zeros((F * nq, self.k), dtype=torch.float32, device=dev)
@@ -281,8 +268,9 @@ class RetrievalEngine:
         ch.ws_all = nat.scan_workspace_bytes(F * nq, v.dim, self.k_scan, v.n)
         ch.ws = torch.empty(max(ch.ws_all, F * ch.ws_one), dtype=torch.uint8, device=dev)
         ch.exact_one = -(-nat.exact_workspace_bytes(nq, self.exact_cap) // 256) * 256
-        ch.exact_all = nat.exact_workspace_bytes(F * nq, self.exact_cap)
-        ch.exact_ws = torch.empty(max(ch.exact_all, F * ch.exact_one), dtype=torch.uint8, device=dev)
+        exact_all = nat.exact_workspace_bytes(F * nq, self.exact_cap)
+        ch.exact_block = torch.empty(max(exact_all, F * ch.exact_one), dtype=torch.uint8, device=dev)
+        ch.exact_ws = ch.exact_block[:exact_all]
         return ch
 
     def _make_ctx(self, grp: _Group, slot: int) -> _Ctx:
@@ -301,7 +289,7 @@ class RetrievalEngine:
             c.ws = ch.ws[j * ch.ws_one:(j + 1) * ch.ws_one]
             c.cand_s, c.cand_i, c.status = ch.cand_s[r], ch.cand_i[r], ch.status[r]
             c.wire = _WireView(ch.out_s[r], ch.out_i[r])
-            c.exact_ws = ch.exact_ws[j * ch.exact_one:(j + 1) * ch.exact_one]
+            c.exact_ws = ch.exact_block[j * ch.exact_one:(j + 1) * ch.exact_one]
         else:
             c.chunk = None
             c.ws = torch.empty(nat.scan_workspace_bytes(self.nq_all, v.dim, self.k_scan, v.n), dtype=torch.uint8, device=dev)
@@ -319,6 +307,9 @@ class RetrievalEngine:
         if self.gather_q:
             c.q_all32 = grp.q_all32[slot * self.nq_all:(slot + 1) * self.nq_all]
             c.q_all16 = grp.q_all16[slot * self.nq_all:(slot + 1) * self.nq_all]
+        # what the search reads and where its lists land: every query of the batch, this rank's (ids | scores) block
+        c.qa32, c.qa16 = (c.q_all32, c.q_all16) if self.gather_q else (c.q_out, c.q16)
+        c.out_s, c.out_i = c.wire.scores, c.wire.ids
         c.ev_done = torch.cuda.Event()
         c.ev_seg = [torch.cuda.Event() for _ in range(4)]     # a segment's output is complete (next segment on another lane)
         return c
@@ -352,51 +343,16 @@ class RetrievalEngine:
             g.q_all32.view(G, self.world, self.q_loc, v.dim).copy_(g.q_gath.view(self.world, G, self.q_loc, v.dim).transpose(0, 1))
         nat.queries_to_f16(g.q_all32, v.slab_type, out=g.q_all16)
 
-    def _seg_search(self, c: _Ctx) -> None:   # all queries x this rank's shard -> wire block
-        if not self.refine:
-            self._seg_scan(c)
-            return
-        # the sweep + fp32 re-rank + certificate in one call (one fused tail kernel after the scan where the plan allows; the
-        # k' candidates still land in cand_s / cand_i), then the escalation of unproven queries
+    def _seg_search(self, b: SearchBuffers) -> None:
+        """All queries of a buffer set (_Ctx) -- or, in ONE sweep, the F x nq_all queries of a chunk (_Chunk) -- x this rank's
+        shard -> its result lists (a buffer set's: the wire block): the store's certified search on these buffers (the k'
+        candidates still land in cand_s / cand_i); no re-rank configured: the sweep's own best k."""
         v = self.view
-        qa32 = c.q_all32 if self.gather_q else c.q_out
-        qa16 = c.q_all16 if self.gather_q else c.q16
-        nat.cosine_topk_cert(qa32, qa16, v.slab, v.shadow, v.n, v.dim, self.k_scan, self.k, v.row_err_max, c.exact_ws, self.exact_cap,
-                             scales=v.scales, id_base=v.id_base, workspace=c.ws, cand_scores=c.cand_s, cand_ids=c.cand_i,
-                             out_scores=c.wire.scores, out_ids=c.wire.ids, status=c.status)
-        if self.exact:
-            nat.escalate_exact(qa32, qa16, v.slab, v.shadow, v.n, v.id_base, self.k, c.wire.scores, c.wire.ids, c.status,
-                               c.exact_ws, self.exact_cap, scales=v.scales)
-
-    def _seg_search_chunk(self, ch: _Chunk) -> None:   # the chunk's F x nq_all queries x the shard in ONE sweep -> every member's lists
-        v = self.view
-        nat.cosine_topk_cert(ch.q_out, ch.q16, v.slab, v.shadow, v.n, v.dim, self.k_scan, self.k, v.row_err_max,
-                             ch.exact_ws[:ch.exact_all], self.exact_cap, scales=v.scales, id_base=v.id_base, workspace=ch.ws,
-                             cand_scores=ch.cand_s, cand_ids=ch.cand_i, out_scores=ch.out_s, out_ids=ch.out_i, status=ch.status)
-        if self.exact:
-            nat.escalate_exact(ch.q_out, ch.q16, v.slab, v.shadow, v.n, v.id_base, self.k, ch.out_s, ch.out_i, ch.status,
-                               ch.exact_ws[:ch.exact_all], self.exact_cap, scales=v.scales)
-
-    def _seg_scan(self, c: _Ctx) -> None:     # the sweep: k' candidates per query (no re-rank configured: the final lists)
-        v = self.view
-        qa16 = c.q_all16 if self.gather_q else c.q16
         if self.refine:
-            nat.cosine_topk(qa16, v.slab, v.n, v.dim, self.k_scan, slab_type=v.slab_type, scales=v.scales, id_base=v.id_base,
-                            workspace=c.ws, out_scores=c.cand_s, out_ids=c.cand_i)
+            _search.search_certified(v, b.qa32, b.qa16, self.k_scan, self.k, self.exact_cap, self.exact, b)
         else:
-            nat.cosine_topk(qa16, v.slab, v.n, v.dim, self.k, slab_type=v.slab_type, scales=v.scales, id_base=v.id_base,
-                            workspace=c.ws, out_scores=c.wire.scores, out_ids=c.wire.ids)
-
-    def _seg_post(self, c: _Ctx) -> None:     # fp32 re-rank + certificate + escalation -> this rank's wire block
-        v = self.view
-        qa32 = c.q_all32 if self.gather_q else c.q_out
-        qa16 = c.q_all16 if self.gather_q else c.q16
-        if self.refine:
-            nat.refine_f32_cert(qa32, qa16, v.shadow, v.n, v.id_base, c.cand_i, c.cand_s, self.k, v.row_err_max, v.slab_type,
-                                c.exact_ws, self.exact_cap, out_scores=c.wire.scores, out_ids=c.wire.ids, status=c.status)
-            if self.exact:
-                nat.escalate_exact(qa32, qa16, v.slab, v.shadow, v.n, v.id_base, self.k, c.wire.scores, c.wire.ids, c.status,
-                                   c.exact_ws, self.exact_cap, scales=v.scales)
+            nat.cosine_topk(b.qa16, v.slab, v.n, v.dim, self.k, slab_type=v.slab_type, scales=v.scales, id_base=v.id_base,
+                            workspace=b.ws, out_scores=b.out_s, out_ids=b.out_i)
 
     def _seg_merge(self, c: _Ctx) -> None:       # N > 1: the gathered wire blocks -> global top-k
         nat.merge_topk_wire(c.wire.gathered, self.world, self.nq_all, self.k, self.k, out_scores=c.fin_s, out_ids=c.fin_i)
@@ -491,12 +447,12 @@ class RetrievalEngine:
                         for i0 in range(g.members[0], g.members[-1] + 1, self.search_fuse):
                             if self.sweep_group > 1:      # (once eagerly: the chunk's kernels are not those of the per-batch warm-up)
                                 with torch.cuda.stream(self.srch_streams[0]):
-                                    self._seg_search_chunk(self.ctxs[i0].chunk)
+                                    self._seg_search(self.ctxs[i0].chunk)
                                 torch.cuda.synchronize()
                             g_ = torch.cuda.CUDAGraph()
                             with torch.cuda.graph(g_, stream=self.srch_streams[0], capture_error_mode="thread_local"):
                                 if self.sweep_group > 1:
-                                    self._seg_search_chunk(self.ctxs[i0].chunk)
+                                    self._seg_search(self.ctxs[i0].chunk)
                                 else:
                                     for i in range(i0, i0 + self.search_fuse):
                                         self.segs[j](self.ctxs[i])

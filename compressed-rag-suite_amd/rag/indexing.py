@@ -61,7 +61,7 @@ import numpy as np
 
 from rag.chunking import Chunk
 from rag import _native as nat
-from rag import _shard
+from rag import _search, _shard
 
 logger = logging.getLogger(__name__)
 
@@ -78,7 +78,6 @@ class _Shard:
         # exactness certificate (csrc/exact.hip).  Lives on the device; read back lazily (row_err_max()).
         self.row_err = torch.zeros(1, dtype=torch.float32, device=device)
         self._row_err_host = None
-        self._exact_ws = {}            # (nq, cap) -> uint8 workspace of the certificate / escalation
         self.dim: Optional[int] = None
         self.pdim: Optional[int] = None
         self.n = 0
@@ -88,7 +87,6 @@ class _Shard:
         self.shadow = None             # torch [capacity, dim] fp32 (refine_fp32 only)
         self.rows_global = None        # torch [capacity] int64: sidecar row of each local row
         self.identity = True           # rows_global[i] == i for every row (single shard, unsharded): no mapping needed
-        self._workspace = None
 
     @property
     def slab_type(self) -> int:
@@ -141,26 +139,12 @@ class _Shard:
         return self._row_err_host
 
     def exact_workspace(self, nq: int, cap: int):
-        import torch
-        key = (nq, cap)
-        ws = self._exact_ws.get(key)
-        if ws is None:
-            if len(self._exact_ws) > 8:
-                self._exact_ws.clear()
-            ws = self._exact_ws[key] = torch.empty(nat.exact_workspace_bytes(nq, cap), dtype=torch.uint8, device=self.device)
-        return ws
+        return _search.exact_workspace(nq, cap, self.device)
 
-    def workspace(self, nq: int, k: int, n_rows: int, large: bool = False):
-        """The scan workspace (large: that of the partitioned over-fetch of top-k, nat.cosine_topk_large_cert); one buffer,
-        grown on demand."""
-        import torch
-        if large:
-            need = nat.large_cert_workspace_bytes(nq, self.dim, k, max(n_rows, 1))
-        else:
-            need = nat.scan_workspace_bytes(nq, self.dim, k, max(n_rows, 1))
-        if self._workspace is None or self._workspace.numel() < need:
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._workspace
+    def view(self) -> _search.ShardView:
+        """These rows as a search sees them (the tensors are shared, not copied)."""
+        return _search.ShardView(self.slab, self.scales, self.shadow, self.n, self.dim, self.slab_type, 0, self.row_err_max(),
+                                 None if (self.identity or not self.n) else self.rows_global[:self.n])
 
 
 def survivor_rows(n: int, dead) -> np.ndarray:
@@ -662,10 +646,7 @@ class VectorStore:
                 self.collection = self._new_collection()
                 logger.info(f"Created new collection: {self.collection_name}")
             col = self.collection
-            if isinstance(embeddings, torch.Tensor):
-                emb = embeddings.to(dtype=torch.float32)
-            else:
-                emb = torch.from_numpy(np.ascontiguousarray(embeddings, dtype=np.float32))
+            emb = self._as_f32(embeddings)
             if emb.ndim != 2:
                 raise ValueError(f"embeddings must be 2-D, got shape {tuple(emb.shape)}")
             logger.info(f"Adding {len(chunks)} chunks to index...")
@@ -880,194 +861,60 @@ class VectorStore:
 
     # -- search --------------------------------------------------------------------------------
     def _cap(self, top_k: int) -> int:
-        """First length of the escalation's row list: exact_cap, and at least 4 x top_k above MAX_K (the list must hold the
-        top_k rows and the band around the k-th)."""
-        if top_k <= nat.MAX_K:
-            return self.exact_cap
-        return min(nat.EXACT_MAX_CAP, max(self.exact_cap, 4 * top_k))
+        return _search.first_cap(self.exact_cap, top_k)
 
-    def _escalates(self, sh: _Shard) -> bool:
-        """refine_exact 'auto': fp16 slabs escalate unproven queries, int8 slabs stay empirical (module docstring)."""
-        if self.refine_exact == 'auto':
-            return sh.slab_type == nat.SLAB_F16
-        return bool(self.refine_exact)
+    _order = staticmethod(_search.order)
 
-    def _filtered_view(self, g: int, sh: _Shard, filt: dict):
+    def _filtered_view(self, g: int, sh: _Shard, filt: dict) -> _search.ShardView:
         """The allowed rows shard g owns, compacted ONCE per distinct filter into a sub-slab (+ scales, shadow, row map) and
         kept with the filter's cache entry: a filtered query then costs one scan of exactly the allowed rows -- no per-query
         gather, no Python pass over the metadata (the reference hands `where` to ChromaDB, rag/indexing.py:129-130,174)."""
+        import dataclasses
         import torch
-        ent = filt["shards"].get(g)
-        if ent is None:
+        sub = filt["shards"].get(g)
+        if sub is None:
             allowed_t = torch.as_tensor(filt["rows"], dtype=torch.int64, device=sh.device)
-            n = sh.n
             if sh.identity:
-                local = allowed_t[allowed_t < n]
+                local = allowed_t[allowed_t < sh.n]
             else:
-                local = torch.isin(sh.rows_global[:n], allowed_t).nonzero().flatten()
-            ent = {"n": int(local.numel())}
-            if ent["n"]:
-                ent["slab"] = sh.slab[local].contiguous()
-                ent["scales"] = sh.scales[local].contiguous() if sh.scales is not None else None
-                ent["shadow"] = sh.shadow[local].contiguous() if sh.shadow is not None else None
-                ent["row_map"] = sh.rows_global[local].contiguous()
-            filt["shards"][g] = ent
-        return ent
+                local = torch.isin(sh.rows_global[:sh.n], allowed_t).nonzero().flatten()
+            pick = lambda arr: None if arr is None else arr[local].contiguous()                # noqa: E731
+            sub = filt["shards"][g] = dataclasses.replace(sh.view(), slab=pick(sh.slab), scales=pick(sh.scales), shadow=pick(sh.shadow),
+                                                          n=int(local.numel()), row_map=pick(sh.rows_global))
+        return sub
 
-    def _search_shard(self, sh: _Shard, q32, top_k: int, filt, cap: Optional[int] = None, g: int = 0):
-        """q32: fp32 [nq, dim] on the shard's device -> (scores [nq, top_k], GLOBAL sidecar rows [nq, top_k], certificate
-        status int32 [nq] or None) there.  Nothing here waits for the device."""
+    def _search_shard(self, g: int, q32, top_k: int, filt, cap: int):
+        """q32: fp32 [nq, dim] on any device -> (scores [nq, top_k], GLOBAL sidecar rows [nq, top_k], certificate status int32
+        [nq] or None) on shard g's device, from its rows or (metadata filter) the cached, compacted sub-slab of the allowed rows it
+        owns.  Nothing here waits for the device."""
         import torch
-        nq = q32.shape[0]
-        slab, scales, shadow, n = sh.slab, sh.scales, sh.shadow, sh.n
-        row_map = None if sh.identity else (sh.rows_global[:n] if n else None)
-        if filt is not None and n:        # metadata filter: scan the cached, compacted sub-slab of the allowed rows this shard owns
-            ent = self._filtered_view(g, sh, filt)
-            n = ent["n"]
-            if n:
-                slab, scales, shadow, row_map = ent["slab"], ent["scales"], ent["shadow"], ent["row_map"]
-        if n == 0:
-            return (torch.full((nq, top_k), float("-inf"), dtype=torch.float32, device=sh.device),
-                    torch.full((nq, top_k), -1, dtype=torch.int64, device=sh.device), None)
-        refine = sh.refine_fp32 and shadow is not None
-        status = None
-        if top_k > nat.MAX_K and refine and top_k <= nat.MAX_K_CERT:
-            # partitioned over-fetch: 64 candidates from each row chunk, fp32 re-rank of all of them and the proof, in one call;
-            # unproven queries escalated as below (the list of the escalation holds at least top_k rows: cap >= 4 top_k)
-            q16 = nat.queries_to_f16(q32, sh.slab_type)
-            qn = torch.nn.functional.normalize(q32, p=2, dim=1, eps=1e-12).contiguous()
-            cap = cap or self._cap(top_k)
-            ws = sh.exact_workspace(nq, cap)
-            s, i, status = nat.cosine_topk_large_cert(qn, q16, slab, shadow, n, sh.dim, top_k, sh.row_err_max(), ws, cap,
-                                                      scales=scales, workspace=sh.workspace(nq, top_k, n, large=True))
-            if self._escalates(sh):
-                nat.escalate_exact(qn, q16, slab, shadow, n, 0, top_k, s, i, status, ws, cap, scales=scales)
-        elif top_k > nat.MAX_K:
-            s, i = self._topk_large(sh, q32, slab, scales, shadow if refine else None, n, top_k)
-        else:
-            q16 = nat.queries_to_f16(q32, sh.slab_type)
-            k_scan = nat.overfetch(nq, top_k, self.refine_overfetch, n, sh.slab_type) if refine else top_k
-            if not refine:
-                s, i = nat.cosine_topk(q16, slab, n, sh.dim, k_scan, slab_type=sh.slab_type, scales=scales,
-                                       workspace=sh.workspace(nq, k_scan, n))
-            else:
-                # the scan's k_scan candidates, their fp32 re-rank and the proof that no un-fetched row can reach the list, in one
-                # call; queries without proof are made exact on the device (one more sweep for them; a no-op launch otherwise)
-                qn = torch.nn.functional.normalize(q32, p=2, dim=1, eps=1e-12).contiguous()
-                cap = cap or self.exact_cap
-                ws = sh.exact_workspace(nq, cap)
-                s, i, status = nat.cosine_topk_cert(qn, q16, slab, shadow, n, sh.dim, k_scan, top_k, sh.row_err_max(), ws, cap,
-                                                    scales=scales, workspace=sh.workspace(nq, k_scan, n))
-                if self._escalates(sh):
-                    nat.escalate_exact(qn, q16, slab, shadow, n, 0, top_k, s, i, status, ws, cap, scales=scales)
-        if row_map is not None:
-            i = torch.where(i >= 0, row_map[i.clamp(min=0)], i)
-        return s, i, status
-
-    def _topk_large(self, sh: _Shard, q32, slab, scales, shadow, n: int, top_k: int):
-        """top_k above the scan kernels' limit (the reference accepts any n_results, rag/indexing.py:152-153): all slab scores
-        of a row block through the library's GEMM kernel (crs_gemm_f16, fp32 out), device top-k per block, order by two
-        stable sorts (score desc, row asc).  int8 rows are widened per block.  With the fp32 shadow the slab pass over-fetches
-        by half and the candidates are re-scored in fp32 by the library (crs::score_rows_f32) before the final order -- the
-        over-fetch re-rank without a certificate (that exists for top_k <= MAX_K_CERT: this path serves larger top_k and
-        stores without the shadow).  The guarantee is the weaker, empirical one:
-        a band of near-identical rows wider than the over-fetch can leave the list off the fp32 ranking, so last_exactness
-        counts every query of such a search unproven (mode 'rerank')."""
-        import torch
-        from rag._encoder import gemm_f16
-        q16 = nat.queries_to_f16(q32, nat.SLAB_F16)
-        if q16.shape[1] != slab.shape[1]:            # int8 slabs pad rows to 256 elements
-            q16 = torch.nn.functional.pad(q16, (0, slab.shape[1] - q16.shape[1]))
-        nq = q32.shape[0]
-        keep = min(n, top_k + max(64, top_k // 2)) if shadow is not None else top_k
-        best_s = torch.empty((nq, 0), dtype=torch.float32, device=sh.device)
-        best_i = torch.empty((nq, 0), dtype=torch.int64, device=sh.device)
-        block = 1 << 16
-        zero = torch.zeros((nq, min(block, n)), dtype=torch.float32, device=sh.device)
-        for lo in range(0, n, block):
-            hi = min(n, lo + block)
-            w = slab[lo:hi] if scales is None else (slab[lo:hi].float() * scales[lo:hi, None]).half()
-            sc = gemm_f16(q16, w.contiguous(), residual=zero[:, : hi - lo].contiguous(), mode=2)
-            ts, ti = sc.topk(min(keep, hi - lo), dim=1)
-            best_s, best_i = torch.cat([best_s, ts], 1), torch.cat([best_i, ti + lo], 1)
-            if best_s.shape[1] > 4 * keep:
-                best_s, best_i = self._order(best_s, best_i, keep)
-        s, i = self._order(best_s, best_i, keep)
-        if shadow is not None:
-            qn = torch.nn.functional.normalize(q32, p=2, dim=1, eps=1e-12).contiguous()
-            s, i = self._order(nat.score_rows_f32(qn, shadow, n, 0, i), i, top_k)
-        if s.shape[1] < top_k:
-            pad = top_k - s.shape[1]
-            s = torch.nn.functional.pad(s, (0, pad), value=float("-inf"))
-            i = torch.nn.functional.pad(i, (0, pad), value=-1)
-        return s, i
-
-    @staticmethod
-    def _order(s, i, k: int):
-        """(score desc, row asc) via two stable sorts; empty slots (row < 0) last; keep k."""
-        import torch
-        big = torch.iinfo(torch.int64).max
-        o = torch.argsort(torch.where(i >= 0, i, big), dim=1, stable=True)
-        s, i = torch.gather(s, 1, o), torch.gather(i, 1, o)
-        o = torch.argsort(torch.where(i >= 0, s, float("-inf")), dim=1, descending=True, stable=True)[:, :k]
-        return torch.gather(s, 1, o), torch.gather(i, 1, o)
+        sh = self.collection.shards[g]
+        with torch.cuda.device(sh.device):
+            q = q32 if q32.device == sh.device else q32.to(sh.device, non_blocking=True)
+            view = sh.view() if (filt is None or sh.n == 0) else self._filtered_view(g, sh, filt)
+            return _search.search_view(view, q, top_k, self.refine_overfetch, cap, _search.escalates(self.refine_exact, sh.slab_type))
 
     def _topk_device(self, q32, top_k: int, filt=None):
-        """q32: fp32 [nq, dim] on the first device -> (scores [nq, k] fp32, sidecar rows [nq, k] int64) there.
-        filt: a filter cache entry (_filter_entry) or None."""
+        """q32: fp32 [nq, dim] on the first device -> (scores [nq, k] fp32, sidecar rows [nq, k] int64) there and the exactness
+        tally of THIS search, whatever its path (see __init__).  filt: a filter cache entry (_filter_entry) or None."""
         import torch
         col = self.collection
         nq = q32.shape[0]
-        parts = []
-        for g, sh in enumerate(col.shards):   # launches are asynchronous: the devices scan their shards concurrently
-            with torch.cuda.device(sh.device):
-                q = q32 if q32.device == sh.device else q32.to(sh.device, non_blocking=True)
-                parts.append(self._search_shard(sh, q, top_k, filt, g=g))
-        # certificate bookkeeping (the one host wait of a refined search; search_batch reads the results right after anyway):
-        # status 2 = an escalated query's band held more rows than the list -- repeat that shard with a longer list.
-        # The tally describes THIS search whatever its path (see __init__)
-        refined = any(sh.refine_fp32 for sh in col.shards)
-        if not refined:
-            tally = {"queries": 0, "certified": 0, "escalated": 0, "unproven": 0, "mode": "slab"}
-        elif top_k > nat.MAX_K_CERT:
-            tally = {"queries": nq, "certified": 0, "escalated": 0, "unproven": nq, "mode": "rerank"}
-        else:
-            tally = {"queries": nq, "certified": nq, "escalated": 0, "unproven": 0, "mode": "certificate"}
-        worst = None
-        for g, sh in enumerate(col.shards):
-            if parts[g][2] is None:
-                continue
-            st = parts[g][2].cpu().numpy()
-            cap = self._cap(top_k)
-            while (st == 2).any() and cap < nat.EXACT_MAX_CAP:
-                cap = min(nat.EXACT_MAX_CAP, cap * 4)
-                with torch.cuda.device(sh.device):
-                    q = q32 if q32.device == sh.device else q32.to(sh.device)
-                    parts[g] = self._search_shard(sh, q, top_k, filt, cap=cap, g=g)
-                st = parts[g][2].cpu().numpy()
-            if (st == 2).any():
-                logger.warning(f"{int((st == 2).sum())} queries have more than {nat.EXACT_MAX_CAP} rows within the error band of "
-                               f"their top-{top_k} (near-identical chunks): their lists are the fp32 re-rank of the over-fetch, unproven")
-            if not self._escalates(sh):
-                st = np.where(st == 1, 2, st)          # not escalated: unproven
-            worst = st if worst is None else np.maximum(worst, st)
-        if worst is not None:          # a query counts once: by its worst shard (no shard with rows to search: nothing to miss)
-            tally.update(certified=int((worst == 0).sum()), escalated=int((worst == 1).sum()), unproven=int((worst == 2).sum()))
-        self.last_exactness = tally
-        parts = [(s_, i_) for s_, i_, _ in parts]
+        cap = self._cap(top_k)
+        # launches are asynchronous: the devices scan their shards concurrently; then, shard by shard, the one host wait of a
+        # refined search (search_batch reads the results right after anyway) and the repeats with a longer escalation list
+        parts = [self._search_shard(g, q32, top_k, filt, cap) for g in range(len(col.shards))]
+        parts = [_search.resolve_overflow(part, lambda c, g=g: self._search_shard(g, q32, top_k, filt, c), cap, top_k)
+                 for g, part in enumerate(parts)]
+        tally = _search.tally([st for _, _, st in parts], nq, top_k, col.refine_fp32,
+                              _search.escalates(self.refine_exact, col.slab_type))
         if len(parts) > 1:             # one process, N devices: partial lists to the first device, merge there
             dev0 = col.device
             with torch.cuda.device(dev0):
-                gs = torch.stack([s.to(dev0) for s, _ in parts]).contiguous()
-                gi = torch.stack([i.to(dev0) for _, i in parts]).contiguous()
-                if top_k <= nat.MAX_K:
-                    s, i = nat.merge_topk(gs, gi, top_k)
-                elif top_k <= nat.MAX_K_CERT and len(parts) <= nat.MERGE_SORTED_MAX_LISTS:
-                    s, i = nat.merge_sorted(gs, gi, top_k)      # every shard's list arrives sorted (score desc, row asc): co-ranking
-                else:
-                    s, i = self._order(gs.permute(1, 0, 2).reshape(nq, -1), gi.permute(1, 0, 2).reshape(nq, -1), top_k)
+                s, i = _search.merge_lists(torch.stack([s.to(dev0) for s, _, _ in parts]).contiguous(),
+                                           torch.stack([i.to(dev0) for _, i, _ in parts]).contiguous(), top_k)
         else:
-            s, i = parts[0]
+            s, i, _ = parts[0]
         dist = self._dist()
         if dist is not None:           # SPMD: ONE all-gather of the wire blocks, k-way merge on every rank
             if top_k > nat.MAX_K_CERT:
@@ -1078,10 +925,10 @@ class VectorStore:
                 wb = self._wire[key] = nat.WireBlock(nq, top_k, col.device, dist.get_world_size())
             wb.scores.copy_(s)
             wb.ids.copy_(i)
-            # above MAX_K the shards' lists (certified, escalated or _topk_large's) arrive sorted: the co-ranking merge
+            # above MAX_K the shards' lists (certified, escalated or the GEMM path's) arrive sorted: the co-ranking merge
             s, i = _shard.allgather_merge(dist, wb.buf, wb.gathered, nq, top_k, top_k,
                                           nat.merge_topk_wire if top_k <= nat.MAX_K else nat.merge_sorted_wire)
-        return s, i
+        return s, i, tally
 
     def _filter_entry(self, where: Optional[dict], where_document: Optional[dict]):
         """Cache entry of a distinct (where, where_document) pair: the allowed sidecar rows (SlabCollection.rows_matching:
@@ -1125,26 +972,26 @@ class VectorStore:
             logger.error(f"Search failed: {e}")
             raise
 
+    def _sole_shard(self, fp32: bool = False):
+        """The one shard of a store whose local rows ARE the sidecar rows (fp32: and that keeps the fp32 rows), or None."""
+        col = self.collection
+        if col is None or len(col.shards) != 1 or not col.shards[0].identity or (fp32 and col.shards[0].shadow is None):
+            return None
+        return col.shards[0]
+
     def engine_view(self):
         """This store as ONE device shard for rag._engine.RetrievalEngine, or None when its layout needs the general path
         (several devices, SPMD sharding, a non-identity row map)."""
-        col = self.collection
-        if col is None or len(col.shards) != 1 or self.sharded or col.n == 0:
-            return None
-        sh = col.shards[0]
-        if not sh.identity:
-            return None
-        from rag._engine import ShardView
-        return ShardView(sh.slab, sh.scales, sh.shadow if sh.refine_fp32 else None, sh.n, sh.dim, sh.slab_type, 0, sh.row_err_max())
+        sh = self._sole_shard()
+        return None if (sh is None or self.sharded or sh.n == 0) else sh.view()
 
     def rows_f32(self, rows):
         """The fp32 rows the store kept for these sidecar rows (numpy [len(rows), dim]; the normalised encoder output of the
         chunks as indexed), or None when it keeps none / the layout is not a single identity shard."""
         import torch
-        col = self.collection
-        if col is None or len(col.shards) != 1 or not col.shards[0].identity or col.shards[0].shadow is None:
+        sh = self._sole_shard(fp32=True)
+        if sh is None:
             return None
-        sh = col.shards[0]
         idx = torch.as_tensor(np.asarray(rows, dtype=np.int64), device=sh.device)
         return sh.shadow[idx].cpu().numpy()
 
@@ -1155,13 +1002,12 @@ class VectorStore:
         three arrays, one launch over the fp32 rows in place, one readback.  None when the store cannot serve it (the
         conditions of rows_f32: no fp32 rows kept, or not a single identity shard) or a list is longer than MAX_K."""
         import torch
-        col = self.collection
-        if col is None or len(col.shards) != 1 or not col.shards[0].identity or col.shards[0].shadow is None:
+        sh = self._sole_shard(fp32=True)
+        if sh is None:
             return None
         rows = np.ascontiguousarray(rows, dtype=np.int64)
         if rows.ndim != 2 or not 1 <= rows.shape[1] <= nat.MAX_K:
             return None
-        sh = col.shards[0]
         nq, m_max = rows.shape
         # one host block -> one copy: [rows int64 | rel fp64 | counts int32 (padded to 8 bytes)]
         block = np.empty(2 * nq * m_max + (nq + 1) // 2, dtype=np.int64)
@@ -1175,49 +1021,44 @@ class VectorStore:
                                   dev[2 * nq * m_max:].view(torch.int32)[:nq], float(lam))
         return order.cpu().numpy()
 
-    def search_rows(self, query_embeddings, top_k: int):
-        """search_batch without the sidecar lookup: (scores fp32 [nq, k], sidecar rows int64 [nq, k]) as numpy, best first,
-        -1 rows = fewer than k hits.  (retrieve_batch builds its dicts straight from these.)"""
-        import torch
+    def _search_rows(self, query_embeddings, top_k: int, where: Optional[dict] = None, where_document: Optional[dict] = None):
+        """The search behind search_rows / search_batch: query_embeddings fp32 [nq, d] (numpy or tensor) -> (scores fp32
+        [nq, k], sidecar rows int64 [nq, k], exactness tally) as numpy + dict, k = top_k clipped to the row count; k = 0 and no
+        tally when there is nothing to search (no rows, no queries, a filter nothing passes)."""
         if self.collection is None:
             raise ValueError("No collection available. Create index first.")
         col = self.collection
         nq = len(query_embeddings)
+        nothing = np.zeros((nq, 0), dtype=np.float32), np.zeros((nq, 0), dtype=np.int64), None
         if col.count() == 0 or nq == 0:
-            return np.zeros((nq, 0), dtype=np.float32), np.zeros((nq, 0), dtype=np.int64)
-        top_k = min(top_k, col.count())
-        if isinstance(query_embeddings, torch.Tensor):
-            q32 = query_embeddings.to(device=col.device, dtype=torch.float32).contiguous()
-        else:
-            q32 = torch.from_numpy(np.ascontiguousarray(query_embeddings, dtype=np.float32)).to(col.device)
+            return nothing
+        q32 = self._as_f32(query_embeddings).to(col.device).contiguous()
         if q32.shape[1] != col.dim:
             raise ValueError(f"Query dimension {q32.shape[1]} doesn't match the index dimension {col.dim}")
-        scores, rows = self._topk_device(q32, top_k, None)
-        return scores.cpu().numpy(), rows.cpu().numpy()
+        filt = self._filter_entry(where, where_document)
+        if filt is not None and len(filt["rows"]) == 0:
+            return nothing
+        scores, rows, tally = self._topk_device(q32, min(top_k, col.count()), filt)
+        return scores.cpu().numpy(), rows.cpu().numpy(), tally
+
+    def search_rows(self, query_embeddings, top_k: int):
+        """search_batch without the sidecar lookup: (scores fp32 [nq, k], sidecar rows int64 [nq, k]) as numpy, best first,
+        -1 rows = fewer than k hits.  (retrieve_batch builds its dicts straight from these.)"""
+        scores, rows, tally = self._search_rows(query_embeddings, top_k)
+        if tally is not None:
+            self.last_exactness = tally
+        return scores, rows
 
     def search_batch(self, query_embeddings, top_k: int = 5, where: Optional[dict] = None,
                      where_document: Optional[dict] = None) -> Dict[str, Any]:
         """Many queries per launch: query_embeddings fp32 [nq, d] (numpy or cuda tensor).
         Same dict as ``search`` with one inner list per query."""
-        import torch
-        if self.collection is None:
-            raise ValueError("No collection available. Create index first.")
-        col = self.collection
+        sh, rh, tally = self._search_rows(query_embeddings, top_k, where, where_document)
         nq = len(query_embeddings)
-        if col.count() == 0 or nq == 0:
+        if tally is None:
             return {k: [[] for _ in range(max(nq, 1))] for k in _EMPTY}
-        top_k = min(top_k, col.count())
-        if isinstance(query_embeddings, torch.Tensor):
-            q32 = query_embeddings.to(device=col.device, dtype=torch.float32).contiguous()
-        else:
-            q32 = torch.from_numpy(np.ascontiguousarray(query_embeddings, dtype=np.float32)).to(col.device)
-        if q32.shape[1] != col.dim:
-            raise ValueError(f"Query dimension {q32.shape[1]} doesn't match the index dimension {col.dim}")
-        filt = self._filter_entry(where, where_document)
-        if filt is not None and len(filt["rows"]) == 0:
-            return {k: [[] for _ in range(nq)] for k in _EMPTY}
-        scores, rows = self._topk_device(q32, top_k, filt)
-        sh, rh = scores.cpu().numpy(), rows.cpu().numpy()
+        self.last_exactness = tally
+        col = self.collection
         dist = (np.float32(1.0) - sh).astype(np.float64)          # one vectorised pass; float(np.float32) per hit was the cost
         ids_l, docs_l, metas_l = col.ids, col.documents, col.metadatas
         out = {'ids': [], 'documents': [], 'metadatas': [], 'distances': []}

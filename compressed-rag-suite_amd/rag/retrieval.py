@@ -21,6 +21,7 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
+from rag import _search
 from rag.indexing import VectorStore
 from rag.embedding import EmbeddingModel
 
@@ -182,28 +183,19 @@ class ContextRetriever:
                     lens[r] = len(t)
                 yield ids, lens
 
-        tally = {"queries": len(queries), "certified": 0, "escalated": 0, "unproven": 0, "mode": "certificate"}
-        if not eng.refine:
-            tally = {"queries": 0, "certified": 0, "escalated": 0, "unproven": 0, "mode": "slab"}
+        total = None
         for s, r, st, q_over in eng.search_token_batches(batches(), overflow_queries=True):
+            tally = _search.tally(st, len(st), eng.k, eng.refine, eng.exact)
             if q_over is not None:
                 # status 2 (more rows in a query's band than the engine's escalation list holds): the store's own search
                 # repeats those queries with longer lists, as search_batch does; they count by their final status
                 over = np.nonzero(st == 2)[0]
-                s2, r2 = store.search_rows(q_over, s.shape[1])
                 s, r = s.copy(), r.copy()
-                s[over], r[over] = s2, r2
-                sub = store.last_exactness
-                tally["certified"] += sub["certified"]
-                tally["escalated"] += sub["escalated"]
-                tally["unproven"] += sub["unproven"]
-                st = np.where(st == 2, -1, st)
-            if eng.refine:
-                tally["certified"] += int((st == 0).sum())
-                tally["escalated"] += int((st == 1).sum()) if eng.exact else 0
-                tally["unproven"] += int((st == 2).sum()) + (0 if eng.exact else int((st == 1).sum()))
+                s[over], r[over], again = store._search_rows(q_over, s.shape[1])
+                tally = _search.retried_tally(tally, again)
+            total = tally if total is None else _search.add_tallies(total, tally)
             yield [(s[i], r[i]) for i in range(s.shape[0])]
-        store.last_exactness = tally
+        store.last_exactness = total
 
     def retrieve_batch(self, queries: List[str], top_k: Optional[int] = None) -> List[List[Dict]]:
         """``[retrieve(q) for q in queries]`` for many queries at once: the encoder forwards and scans of the whole list

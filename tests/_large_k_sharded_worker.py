@@ -13,7 +13,7 @@ D = 128
 N = 2300
 ADDS = ((0, 1100), (1100, 1101), (1101, 2300))       # every add is split over the ranks
 NQ = 5
-# (name, VectorStore config): the certified path (fp16 and int8, escalating) and a store without the fp32 shadow (_topk_large)
+# (name, VectorStore config): the certified path (fp16 and int8, escalating) and a store without the fp32 shadow (rag._search.topk_gemm)
 CONFIGS = (("fp16", {"index_dtype": "fp16", "refine_fp32": True, "refine_exact": True}),
            ("int8", {"index_dtype": "int8", "refine_fp32": True, "refine_exact": True}),
            ("fp16-slab", {"index_dtype": "fp16", "refine_fp32": False}))

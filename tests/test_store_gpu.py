@@ -174,7 +174,7 @@ def test_filters_use_the_inverted_index_and_cached_subslabs(cuda):
     assert len(store._filters) == 6 and all(("shards" in e) for e in store._filters.values())
     ent = store._filter_entry({"page_number": 2}, None)
     sub = ent["shards"][0]
-    assert sub["n"] == len(ent["rows"]) and sub["slab"].shape[0] == sub["n"]         # compacted once, kept
+    assert sub.n == len(ent["rows"]) and sub.slab.shape[0] == sub.n                   # compacted once, kept
     assert store._filter_entry({"page_number": 2}, None) is ent                       # ... and reused
     batch = store.search_batch(q, top_k=5, where={"page_number": 2})
     assert [batch["ids"][i] for i in range(6)] == [ref.search(q[i], top_k=5, where={"page_number": 2})["ids"][0] for i in range(6)]
