@@ -412,6 +412,23 @@ int crs_mmr_order(const float* vecs_dev, int64_t n_rows, int dim, const int64_t*
   return e ? hip_fail((hipError_t)e, "mmr_order launch") : CRS_OK;
 }
 
+int crs_rerank_lexical(const float* scores_dev, const int64_t* rows_dev, int nq, int m_max, const int64_t* doc_offsets_dev,
+                       const int32_t* doc_tokens_dev, int64_t n_rows, int64_t n_doc_tokens, const int64_t* q_offsets_dev,
+                       const int32_t* q_tokens_dev, int64_t n_q_tokens, const int32_t* q_norm_dev, int k, double threshold,
+                       int32_t* order_dev, int32_t* count_dev, double* sim_dev, double* rr_dev, int32_t* reranked_dev, void* stream) {
+  if (nq < 0 || n_rows < 0 || n_doc_tokens < 0 || n_q_tokens < 0) return fail(CRS_EINVAL, "bad nq/n_rows/n_doc_tokens/n_q_tokens");
+  if (m_max < 1 || m_max > CRS_MAX_K) return fail(CRS_EINVAL, "bad m_max (1 <= m_max <= CRS_MAX_K)");
+  if (k < 1) return fail(CRS_EINVAL, "bad k (k >= 1)");
+  if (!scores_dev || !rows_dev || !doc_offsets_dev || !q_offsets_dev || !q_norm_dev || !order_dev || !count_dev || !sim_dev || !rr_dev ||
+      !reranked_dev || (n_doc_tokens > 0 && !doc_tokens_dev) || (n_q_tokens > 0 && !q_tokens_dev))
+    return fail(CRS_EINVAL, "null pointer");
+  if (nq == 0) return CRS_OK;
+  const int e = crs::rerank_lexical_launch(scores_dev, rows_dev, nq, m_max, doc_offsets_dev, doc_tokens_dev, n_rows, n_doc_tokens,
+                                           q_offsets_dev, q_tokens_dev, n_q_tokens, q_norm_dev, k, threshold, order_dev, count_dev,
+                                           sim_dev, rr_dev, reranked_dev, (hipStream_t)stream);
+  return e ? hip_fail((hipError_t)e, "rerank_lexical launch") : CRS_OK;
+}
+
 int crs_rescore_f32(const float* q32_dev, int nq, int dim, const float* shadow_dev, int64_t n_rows,
                     int64_t id_base, int k, float* scores_dev, int64_t* ids_dev, void* stream) {
   if (nq <= 0 || dim <= 0 || k <= 0 || k > 64 || n_rows <= 0) return fail(CRS_EINVAL, "bad sizes (k <= 64)");

@@ -94,6 +94,11 @@ int merge_sorted_launch_wire(const void* wire, size_t block_bytes, size_t scores
 int mmr_order_launch(const float* vecs, int64_t n_rows, int dim, const int64_t* rows, const double* rel, const int* counts, int nq,
                      int m_max, double lam, int* order, hipStream_t stream);
 
+// rerank.hip: score, threshold and lexical re-rank of lists of <= CRS_MAX_K candidates, one wave per list
+int rerank_lexical_launch(const float* scores, const int64_t* rows, int nq, int m_max, const int64_t* doc_off, const int* doc_tok,
+                          int64_t n_rows, int64_t n_doc_tok, const int64_t* q_off, const int* q_tok, int64_t n_q_tok, const int* q_norm,
+                          int k, double threshold, int* order, int* out_count, double* sim, double* rr, int* reranked, hipStream_t stream);
+
 // convert.hip
 int refine_f32_launch(const float* q32, int nq, int dim, const float* shadow, int64_t n_rows, int64_t id_base,
                       const int64_t* cand, int k_in, int k_out, float* out_s, int64_t* out_i, hipStream_t stream);

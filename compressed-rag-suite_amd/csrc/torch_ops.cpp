@@ -17,6 +17,7 @@
 //   crs::merge_topk / crs::merge_topk_wire   cross-shard merge                (new vs the reference)
 //   crs::merge_sorted / crs::merge_sorted_wire   the same for sorted lists, k 65 .. 1024
 //   crs::mmr_order         replaces the greedy MMR loop of _apply_diversity  (reference rag/retrieval.py:219-277)
+//   crs::rerank_lexical    replaces the scoring, threshold and _rerank loops of retrieve_batch  (reference rag/retrieval.py:75-77, 196-217)
 // Tensors are torch-owned; every op launches on the CURRENT HIP stream of the tensors' device, so the ops
 // compose with torch streams and hipGraph capture.  Errors of the C ABI surface as RuntimeError (TORCH_CHECK)
 // carrying crs_last_error(); the Python wrappers (rag/_native.py) translate where the reference's types differ.
@@ -466,6 +467,44 @@ void mmr_order_out(const Tensor& vecs, int64_t n_rows, const Tensor& rows, const
      "crs::mmr_order");
 }
 
+// ---- lexical re-rank (csrc/rerank.hip) ----------------------------------------------------------------------------
+// scores fp32 / rows int64 / order int32 / sim, rr fp64 [nq, m_max]; doc_offsets int64 [>= n_rows + 1], doc_tokens int32 (the rows'
+// token CSR); q_offsets int64 [nq + 1], q_tokens int32 (the queries' known tokens); q_norm / count / reranked int32 [nq]
+void rerank_lexical(const Tensor& scores, const Tensor& rows, const Tensor& doc_offsets, const Tensor& doc_tokens, int64_t n_rows,
+                    const Tensor& q_offsets, const Tensor& q_tokens, const Tensor& q_norm, int64_t k, double threshold, Tensor order,
+                    Tensor count, Tensor sim, Tensor rr, Tensor reranked) {
+  want(scores, at::kFloat, "scores");
+  want(rows, at::kLong, "rows");
+  want(doc_offsets, at::kLong, "doc_offsets");
+  want(doc_tokens, at::kInt, "doc_tokens");
+  want(q_offsets, at::kLong, "q_offsets");
+  want(q_tokens, at::kInt, "q_tokens");
+  want(q_norm, at::kInt, "q_norm");
+  want(order, at::kInt, "order");
+  want(count, at::kInt, "count");
+  want(sim, at::kDouble, "sim");
+  want(rr, at::kDouble, "rr");
+  want(reranked, at::kInt, "reranked");
+  same_device(scores, {&rows, &doc_offsets, &doc_tokens, &q_offsets, &q_tokens, &q_norm, &order, &count, &sim, &rr, &reranked},
+              "crs::rerank_lexical");
+  TORCH_CHECK(rows.dim() == 2 && scores.sizes() == rows.sizes() && order.sizes() == rows.sizes() && sim.sizes() == rows.sizes() &&
+              rr.sizes() == rows.sizes(), "scores / rows / order / sim / rr must be [nq, m_max]");
+  const int64_t nq = rows.size(0);
+  TORCH_CHECK(nq <= 0x7fffffff, "too many lists");
+  TORCH_CHECK(n_rows >= 0 && doc_offsets.dim() == 1 && doc_offsets.numel() >= n_rows + 1, "doc_offsets must be int64 [>= n_rows + 1]");
+  TORCH_CHECK(q_offsets.dim() == 1 && q_offsets.numel() == nq + 1, "q_offsets must be int64 [nq + 1]");
+  TORCH_CHECK(q_norm.numel() == nq && count.numel() == nq && reranked.numel() == nq, "q_norm / count / reranked must be int32 [nq]");
+  TORCH_CHECK(k >= 1 && k <= 0x7fffffff, "k must be at least 1");
+  if (nq == 0) return;
+  c10::hip::HIPGuardMasqueradingAsCUDA g(scores.device());
+  ok(crs_rerank_lexical(scores.data_ptr<float>(), rows.data_ptr<int64_t>(), (int)nq, (int)rows.size(1), doc_offsets.data_ptr<int64_t>(),
+                        doc_tokens.numel() ? doc_tokens.data_ptr<int32_t>() : nullptr, n_rows, doc_tokens.numel(),
+                        q_offsets.data_ptr<int64_t>(), q_tokens.numel() ? q_tokens.data_ptr<int32_t>() : nullptr, q_tokens.numel(),
+                        q_norm.data_ptr<int32_t>(), (int)k, threshold, order.data_ptr<int32_t>(), count.data_ptr<int32_t>(),
+                        sim.data_ptr<double>(), rr.data_ptr<double>(), reranked.data_ptr<int32_t>(), cur_stream(scores)),
+     "crs::rerank_lexical");
+}
+
 // ---- encoder -------------------------------------------------------------------------------------------------
 // desc = [vocab_size, hidden, layers, heads, ffn, max_pos, pooling, flags (CRS_ENC_*, optional)]; weights = [word_emb, pos_emb, type_emb, emb_ln_g, emb_ln_b]
 // followed by 12 tensors per layer in crs_encoder_layer order (w_qkv b_qkv w_o b_o ln1_g ln1_b w_up b_up w_down b_down ln2_g ln2_b).
@@ -545,6 +584,8 @@ TORCH_LIBRARY(crs, m) {
   m.def("merge_sorted_out(Tensor scores, Tensor ids, int k_out, Tensor(a!) out_scores, Tensor(b!) out_ids) -> ()");
   m.def("merge_sorted_wire_out(Tensor wire, int nlists, int nq, int k_in, int k_out, Tensor(a!) out_scores, Tensor(b!) out_ids) -> ()");
   m.def("mmr_order_out(Tensor vecs, int n_rows, Tensor rows, Tensor rel, Tensor counts, float lam, Tensor(a!) order) -> ()");
+  m.def("rerank_lexical(Tensor scores, Tensor rows, Tensor doc_offsets, Tensor doc_tokens, int n_rows, Tensor q_offsets, Tensor q_tokens, "
+        "Tensor q_norm, int k, float threshold, Tensor(a!) order, Tensor(b!) count, Tensor(c!) sim, Tensor(d!) rr, Tensor(e!) reranked) -> ()");
   m.def("encoder_forward(Tensor ids, Tensor lens, Tensor[] weights, int[] desc, float ln_eps, Tensor(a!) workspace, Tensor(b!) out, "
         "Tensor(c!)? q16_out, int slab_type, bool normalize, Tensor(d!)? hidden_out) -> ()");
 }
@@ -570,5 +611,6 @@ TORCH_LIBRARY_IMPL(crs, CUDA, m) {   // the HIP backend of torch-ROCm dispatches
   m.impl("merge_sorted_out", &merge_sorted_out);
   m.impl("merge_sorted_wire_out", &merge_sorted_wire_out);
   m.impl("mmr_order_out", &mmr_order_out);
+  m.impl("rerank_lexical", &rerank_lexical);
   m.impl("encoder_forward", &encoder_forward);
 }

@@ -48,6 +48,8 @@ _SIGNATURES = {
                                c_void_p]),
     "crs_merge_sorted": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "crs_mmr_order": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_void_p, c_void_p]),
+    "crs_rerank_lexical": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64,
+                                   c_void_p, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "crs_rescore_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p,
                                 c_void_p, c_void_p]),
     "crs_score_rows_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
@@ -296,6 +298,28 @@ def mmr_order(vecs, n_rows: int, rows, rel, counts, lam: float, out=None):
         out = torch.empty(rows.shape, dtype=torch.int32, device=vecs.device)
     with _translate():
         ops().mmr_order_out(vecs, int(n_rows), rows, rel, counts, float(lam), out)
+    return out
+
+
+def has_rerank_lexical() -> bool:
+    """Whether the loaded libcrs_torch.so carries crs::rerank_lexical (a library built before csrc/rerank.hip does not)."""
+    return hasattr(ops(), "rerank_lexical")
+
+
+def rerank_lexical(scores, rows, doc_offsets, doc_tokens, n_rows: int, q_offsets, q_tokens, q_norm, k: int, threshold: float, out=None):
+    """Score, threshold and lexically re-rank nq result lists in one launch (crs_rerank_lexical, csrc/rerank.hip): scores fp32 /
+    rows int64 [nq, m_max <= MAX_K] (sidecar rows, -1 = empty slot); doc_offsets int64 [>= n_rows + 1] / doc_tokens int32 the rows'
+    token CSR; q_offsets int64 [nq + 1] / q_tokens int32 the queries' known token ids; q_norm int32 [nq] -> (order int32 [nq, m_max],
+    count int32 [nq], sim fp64 [nq, m_max], rr fp64 [nq, m_max], reranked int32 [nq]), all cuda, in the host rule's bits.  `out`:
+    those five tensors, preallocated.  No host sync."""
+    import torch
+    if out is None:
+        nq, dev = rows.shape[0], rows.device
+        out = (torch.empty(rows.shape, dtype=torch.int32, device=dev), torch.empty(nq, dtype=torch.int32, device=dev),
+               torch.empty(rows.shape, dtype=torch.float64, device=dev), torch.empty(rows.shape, dtype=torch.float64, device=dev),
+               torch.empty(nq, dtype=torch.int32, device=dev))
+    with _translate():
+        ops().rerank_lexical(scores, rows, doc_offsets, doc_tokens, int(n_rows), q_offsets, q_tokens, q_norm, int(k), float(threshold), *out)
     return out
 
 

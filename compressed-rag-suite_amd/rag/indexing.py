@@ -43,6 +43,14 @@ New, additive surface (all keys absent from the reference config.json default so
                                   updated in place, the others appended in their given order
                               ``mutation_epoch`` counts the calls that changed something.  With persist_directory each such call
                               rewrites the files as a new generation (O(index) disk I/O: batch ids into one call)
+  ``rerank_lexical``          the post-search half of ContextRetriever.retrieve_batch (score, similarity_threshold, the
+                              token-overlap re-rank and its stable sort) for many result lists in one launch (csrc/rerank.hip), bit
+                              for bit the host rule; the retriever's opt-in ``lexical_rerank: 'device'`` calls it.  It needs the
+                              token ids of every chunk: a vocabulary (str -> int, exact, first-seen order) and a CSR of each row's
+                              sorted distinct ids (SlabCollection._token_csr), derived data built by ONE Python pass over the
+                              documents on first use, extended as rows arrive, dropped when a document changes, and mirrored on the
+                              first device at 4 bytes per distinct token per chunk (+ 8 bytes per row of offsets); the sidecars are
+                              replicated on every layout, so it serves sharded and multi-device stores alike
 ``where`` / ``where_document`` filters work on every layout (the sidecars are replicated; each shard scans the
 allowed rows it owns).  ``top_k`` is unlimited as in the reference: up to 1024 a refined shard is over-fetched by
 partition (64 candidates from each of up to 64 row chunks, crs::cosine_topk_large_cert) and certified like top_k <= 64;
@@ -171,6 +179,87 @@ def compact_windows(n_rows: int, m: int, window_rows: int, first_row: int = 0):
     return [(d0, min(W, n_out - d0)) for d0 in range(int(first_row) // W * W, n_out, W)]
 
 
+class _TokenCSR:
+    """The token ids of every sidecar row, for the device's lexical re-rank: `vocab` str -> int32 id (ids in first-seen order,
+    exact: no hashing), and per row the sorted distinct ids of set(document.lower().split()) -- the set ContextRetriever._tokens_of
+    builds -- as a CSR: offsets int64 [rows + 1], token_ids int32 [total].  The host arrays and their device mirror grow
+    geometrically; extend() tokenises only the new rows and device() uploads only what the mirror lacks."""
+
+    def __init__(self):
+        self.vocab: Dict[str, int] = {}
+        self.rows = 0                      # rows tokenised so far
+        self.total = 0                     # token ids they hold
+        self._offsets = np.zeros(1024, dtype=np.int64)
+        self._tokens = np.zeros(8192, dtype=np.int32)
+        self._dev = None                   # (device, offsets tensor, tokens tensor)
+        self._dev_rows, self._dev_total = 0, 0
+
+    @property
+    def offsets(self) -> np.ndarray:
+        return self._offsets[: self.rows + 1]
+
+    @property
+    def token_ids(self) -> np.ndarray:
+        return self._tokens[: self.total]
+
+    def row(self, r: int) -> np.ndarray:
+        return self._tokens[self._offsets[r]: self._offsets[r + 1]]
+
+    @staticmethod
+    def _grown(arr, need: int):
+        if need <= arr.shape[0]:
+            return arr
+        new = np.zeros(max(need, arr.shape[0] * 3 // 2), dtype=arr.dtype)
+        new[: arr.shape[0]] = arr
+        return new
+
+    def extend(self, documents: Sequence[str]) -> None:
+        """Tokenise documents[self.rows:] (the rows that arrived since the last call)."""
+        vocab = self.vocab
+        fresh = [sorted({vocab.setdefault(w, len(vocab)) for w in doc.lower().split()}) for doc in documents[self.rows:]]
+        if not fresh:
+            return
+        if len(vocab) > 0x7fffffff:
+            raise ValueError("more than 2^31 - 1 distinct tokens")
+        lens = np.fromiter((len(ids) for ids in fresh), dtype=np.int64, count=len(fresh))
+        self._offsets = self._grown(self._offsets, self.rows + len(fresh) + 1)
+        self._tokens = self._grown(self._tokens, self.total + int(lens.sum()))
+        self._offsets[self.rows + 1: self.rows + len(fresh) + 1] = self.total + np.cumsum(lens)
+        flat = np.fromiter((t for ids in fresh for t in ids), dtype=np.int32, count=int(lens.sum()))
+        self._tokens[self.total: self.total + flat.size] = flat
+        self.rows += len(fresh)
+        self.total += int(flat.size)
+
+    def query_ids(self, query: str):
+        """(sorted known ids of set(query.lower().split()), max(len(that set), 1)): the re-rank's `wanted` and `norm`."""
+        wanted = set(query.lower().split())
+        vocab = self.vocab
+        return sorted(vocab[w] for w in wanted if w in vocab), max(len(wanted), 1)
+
+    def device(self, device):
+        """(offsets int64 [rows + 1], token_ids int32 [total]) on `device`: views of a mirror that only ever receives the tail
+        the host gained since the last call (a larger mirror is allocated, and the old one copied on the device, when it is full)."""
+        import torch
+        if self._dev is None or self._dev[0] != device:
+            self._dev = (device, torch.zeros(self._offsets.shape[0], dtype=torch.int64, device=device),
+                         torch.zeros(self._tokens.shape[0], dtype=torch.int32, device=device))
+            self._dev_rows, self._dev_total = 0, 0
+        _, off, tok = self._dev
+        if off.shape[0] < self.rows + 1 or tok.shape[0] < self.total:
+            new_off = torch.zeros(self._offsets.shape[0], dtype=torch.int64, device=device)
+            new_tok = torch.zeros(self._tokens.shape[0], dtype=torch.int32, device=device)
+            new_off[: self._dev_rows + 1].copy_(off[: self._dev_rows + 1])
+            new_tok[: self._dev_total].copy_(tok[: self._dev_total])
+            off, tok = new_off, new_tok
+            self._dev = (device, off, tok)
+        if self._dev_rows < self.rows:
+            off[self._dev_rows + 1: self.rows + 1].copy_(torch.from_numpy(self._offsets[self._dev_rows + 1: self.rows + 1]))
+            if self._dev_total < self.total:
+                tok[self._dev_total: self.total].copy_(torch.from_numpy(self._tokens[self._dev_total: self.total]))
+            self._dev_rows, self._dev_total = self.rows, self.total
+        return off[: self.rows + 1], tok[: self.total]
+
+
 class SlabCollection:
     """What ``VectorStore.collection`` exposes (the retriever reads ``.metadata`` and the harness ``.count()``,
     reference rag/retrieval.py:48-50).  Owns the per-device shards and the host sidecars."""
@@ -248,13 +337,27 @@ class SlabCollection:
         self.__dict__["_idmap_rows"] = len(self.ids)
         return idmap
 
-    def _drop_derived(self, ids_changed: bool):
-        """Forget what was derived from the sidecars: the inverted metadata index, and (rows renumbered) the id map."""
-        self.__dict__.pop("_inv", None)
-        self.__dict__.pop("_inv_rows", None)
+    def _drop_derived(self, ids_changed: bool, metadata_changed: bool = True, documents_changed: bool = True):
+        """Forget what was derived from the sidecars: the inverted metadata index, (rows renumbered) the id map, and (a document
+        changed, or rows renumbered) the token CSR with its device mirror."""
+        if metadata_changed or ids_changed:
+            self.__dict__.pop("_inv", None)
+            self.__dict__.pop("_inv_rows", None)
         if ids_changed:
             self.__dict__.pop("_idmap", None)
             self.__dict__.pop("_idmap_rows", None)
+        if documents_changed or ids_changed:
+            self.__dict__.pop("_tok", None)
+
+    def _token_csr(self) -> _TokenCSR:
+        """The token ids of every row (see _TokenCSR): built by one pass over the documents on first use, extended by the rows
+        that arrived since, like _inverted / _id_rows; dropped by _drop_derived when a document changes or rows are renumbered."""
+        csr = self.__dict__.get("_tok")
+        if csr is None:
+            csr = self.__dict__["_tok"] = _TokenCSR()
+        if csr.rows < len(self.documents):
+            csr.extend(self.documents)
+        return csr
 
     # -- metadata filters: value -> rows, built once and extended as rows arrive (the per-query loop over all metadatas is gone)
     def _inverted(self):
@@ -678,14 +781,15 @@ class VectorStore:
             return embeddings.to(dtype=torch.float32)
         return torch.from_numpy(np.ascontiguousarray(embeddings, dtype=np.float32))
 
-    def _mutated(self, ids_changed: bool, sidecars_changed: bool = True):
+    def _mutated(self, ids_changed: bool, sidecars_changed: bool = True, documents_changed: bool = True):
         """Everything derived from rows dies: filter sub-slabs (keyed by row COUNT only: an update, or a delete followed by an
-        equal add, would serve a stale one), the inverted metadata index, the id map (delete), the SPMD wire blocks, the cached
-        row error.  mutation_epoch tells the retriever's engine (graphs captured with the old row error) to rebuild."""
+        equal add, would serve a stale one), the inverted metadata index, the id map (delete), the token CSR (a document changed),
+        the SPMD wire blocks, the cached row error.  mutation_epoch tells the retriever's engine (graphs captured with the old row
+        error) to rebuild."""
         self._filters = {}
         self._wire = {}
-        if sidecars_changed or ids_changed:
-            self.collection._drop_derived(ids_changed)
+        if sidecars_changed or documents_changed or ids_changed:
+            self.collection._drop_derived(ids_changed, metadata_changed=sidecars_changed, documents_changed=documents_changed)
         for sh in self.collection.shards:
             sh._row_err_host = None
         self.mutation_epoch += 1
@@ -824,7 +928,7 @@ class VectorStore:
         if rows.size == 0 or (emb is None and documents is None and metadatas is None):
             return
         self._apply_update(rows, emb, documents, metadatas)
-        self._mutated(ids_changed=False, sidecars_changed=metadatas is not None)
+        self._mutated(ids_changed=False, sidecars_changed=metadatas is not None, documents_changed=documents is not None)
 
     def upsert(self, chunks: List[Chunk], embeddings, metadata_fields: Optional[List[str]] = None) -> None:
         """create_index's signature: chunks whose chunk_id exists are updated in place (embedding, text, metadata), the others
@@ -1020,6 +1124,66 @@ class VectorStore:
                                   dev[nq * m_max:2 * nq * m_max].view(torch.float64).view(nq, m_max),
                                   dev[2 * nq * m_max:].view(torch.int32)[:nq], float(lam))
         return order.cpu().numpy()
+
+    def rerank_lexical(self, queries: Sequence[str], scores, rows, k: int, threshold: float):
+        """The post-search steps of ContextRetriever.retrieve_batch for many result lists at once, on the device
+        (crs_rerank_lexical, csrc/rerank.hip): queries [nq] strings, scores fp32 / rows int64 [nq, m_max <= MAX_K] (the store's
+        cosine scores and sidecar rows in list order, -1 rows = empty slots), k the list length wanted, threshold the
+        similarity_threshold -> numpy (order int32 [nq, m_max]: input positions, -1 past the count; count int32 [nq]; sim fp64
+        [nq, m_max] by input position; rr fp64 [nq, m_max]: the re-rank score where reranked; reranked int32 [nq]), in the bits of
+        the host rule.  The queries are tokenised against the collection's vocabulary (SlabCollection._token_csr); one host block
+        up, one launch, one block back.  Works on every layout (the rows are sidecar rows).  None when a list is longer than
+        MAX_K or the native library was built without the kernel."""
+        import torch
+        col = self.collection
+        if col is None:
+            raise ValueError("No collection available. Create index first.")
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        scores = np.ascontiguousarray(scores, dtype=np.float32)
+        if rows.ndim != 2 or scores.shape != rows.shape or not 1 <= rows.shape[1] <= nat.MAX_K or not nat.has_rerank_lexical():
+            return None
+        nq, m_max = rows.shape
+        if len(queries) != nq:
+            raise ValueError(f"Query count ({len(queries)}) doesn't match list count ({nq})")
+        if nq == 0:
+            return (np.zeros((0, m_max), np.int32), np.zeros(0, np.int32), np.zeros((0, m_max)), np.zeros((0, m_max)), np.zeros(0, np.int32))
+        csr = col._token_csr()
+        q_ids, q_norm = zip(*(csr.query_ids(q) for q in queries))
+        q_off = np.zeros(nq + 1, dtype=np.int64)
+        np.cumsum([len(ids) for ids in q_ids], out=q_off[1:])
+        n_tok, cells = int(q_off[-1]), nq * m_max
+        # one host block -> one copy: [rows int64 | q_offsets int64 | scores fp32 | q_norm int32 | q_tokens int32], int64 words
+        w_sc, w_norm, w_tok = (cells + 1) // 2, (nq + 1) // 2, (n_tok + 1) // 2
+        o_off = cells
+        o_sc = o_off + nq + 1
+        o_norm = o_sc + w_sc
+        o_tok = o_norm + w_norm
+        block = np.zeros(o_tok + w_tok, dtype=np.int64)
+        block[:cells] = rows.ravel()
+        block[o_off:o_sc] = q_off
+        block[o_sc:o_norm].view(np.float32)[:cells] = scores.ravel()
+        block[o_norm:o_tok].view(np.int32)[:nq] = q_norm
+        block[o_tok:].view(np.int32)[:n_tok] = np.fromiter((t for ids in q_ids for t in ids), dtype=np.int32, count=n_tok)
+        dev = col.device
+        with torch.cuda.device(dev):
+            doc_off, doc_tok = csr.device(dev)
+            d = torch.from_numpy(block).to(dev)
+            # one device block <- the five outputs: [sim fp64 | rr fp64 | order int32 | count int32 | reranked int32]
+            w_ord, w_cnt = (cells + 1) // 2, (nq + 1) // 2
+            out = torch.empty(2 * cells + w_ord + 2 * w_cnt, dtype=torch.int64, device=dev)
+            sim_d = out[:cells].view(torch.float64).view(nq, m_max)
+            rr_d = out[cells:2 * cells].view(torch.float64).view(nq, m_max)
+            ord_d = out[2 * cells:2 * cells + w_ord].view(torch.int32)[:cells].view(nq, m_max)
+            cnt_d = out[2 * cells + w_ord:2 * cells + w_ord + w_cnt].view(torch.int32)[:nq]
+            rer_d = out[2 * cells + w_ord + w_cnt:].view(torch.int32)[:nq]
+            nat.rerank_lexical(d[o_sc:o_norm].view(torch.float32)[:cells].view(nq, m_max), d[:cells].view(nq, m_max), doc_off, doc_tok,
+                               len(col.documents), d[o_off:o_sc], d[o_tok:].view(torch.int32)[:n_tok], d[o_norm:o_tok].view(torch.int32)[:nq],
+                               int(k), float(threshold), out=(ord_d, cnt_d, sim_d, rr_d, rer_d))
+            host = out.cpu().numpy()
+        return (host[2 * cells:2 * cells + w_ord].view(np.int32)[:cells].reshape(nq, m_max),
+                host[2 * cells + w_ord:2 * cells + w_ord + w_cnt].view(np.int32)[:nq],
+                host[:cells].view(np.float64).reshape(nq, m_max), host[cells:2 * cells].view(np.float64).reshape(nq, m_max),
+                host[2 * cells + w_ord + w_cnt:].view(np.int32)[:nq])
 
     def _search_rows(self, query_embeddings, top_k: int, where: Optional[dict] = None, where_document: Optional[dict] = None):
         """The search behind search_rows / search_batch: query_embeddings fp32 [nq, d] (numpy or tensor) -> (scores fp32

@@ -7,8 +7,10 @@ lexical rerank and MMR steps are a few hundred scalar operations per query and b
 the host in fp64 Python exactly like the reference; the heavy steps they call (``embed``,
 ``search``) run on the GPU.  Opt-in, ``mmr_vectors: 'device'``: ``retrieve_batch`` orders the MMR
 lists of all its queries with one kernel launch over the store's fp32 rows (csrc/mmr.hip) instead
-of the Python loop -- same rule, cosines in fp32 on the device; scoring, threshold and the lexical
-rerank stay on the host.
+of the Python loop -- same rule, cosines in fp32 on the device.  Opt-in, ``lexical_rerank: 'device'``:
+``retrieve_batch`` scores, thresholds and lexically re-ranks the lists of each device batch with one
+kernel launch (csrc/rerank.hip, VectorStore.rerank_lexical) and builds only the surviving dicts --
+the host rule in fp64, bit for bit.
 
 Additive: ``retrieve_batch`` embeds and searches many queries in one launch each and then applies
 the identical per-query post-processing; ``reuse_index_embeddings`` is NOT offered because the
@@ -49,6 +51,14 @@ class ContextRetriever:
         if self.mmr_vectors not in ('auto', 'reembed', 'index', 'device'):
             raise ValueError(f"mmr_vectors must be 'auto', 'reembed', 'index' or 'device', got {self.mmr_vectors!r}")
         self.last_mmr = {'mode': 'host', 'lists': 0}      # which path ordered the lists of the last retrieve_batch call
+        # additive: where retrieve_batch runs the steps between the search and the MMR step (score, similarity_threshold, the
+        # token-overlap re-rank, its stable sort).  'host' = the Python loop below, as the reference; 'device' = ONE kernel launch per
+        # device batch (VectorStore.rerank_lexical) with bit-identical results, taken when rerank is on, the metric is cosine and
+        # 2 * top_k <= 64; anything else, and a store that answers None, runs as 'host'.  retrieve() always runs on the host
+        self.lexical_rerank = config.get('lexical_rerank', 'host')
+        if self.lexical_rerank not in ('host', 'device'):
+            raise ValueError(f"lexical_rerank must be 'host' or 'device', got {self.lexical_rerank!r}")
+        self.last_rerank = {'mode': 'host', 'lists': 0}   # which path scored and re-ranked the lists of the last retrieve_batch call
         self._token_sets: Dict[str, frozenset] = {}       # _rerank: text -> its lower-cased token set
         self._engine, self._engine_key = None, None
         self.distance_metric = self._get_distance_metric()
@@ -215,7 +225,16 @@ class ContextRetriever:
         row_of: Dict[int, int] = {}           # id(chunk dict) -> sidecar row (our store only)
         ids_l, docs_l, metas_l = getattr(col, 'ids', None), getattr(col, 'documents', None), getattr(col, 'metadatas', None)
         queries = list(queries)
+        on_device = (self.lexical_rerank == 'device' and bool(self.rerank) and self.distance_metric == 'cosine' and fetch <= 64
+                     and ids_l is not None and hasattr(store, 'rerank_lexical'))
+        host_pieces = 0
         for piece in self._search_many(queries, fetch):      # one device batch at a time: its dicts are built while the next ones run
+            if on_device and not isinstance(piece, dict):
+                built = self._rerank_on_device(queries[len(per_query):len(per_query) + len(piece)], piece, k, row_of)
+                if built is not None:
+                    per_query.extend(built)
+                    continue
+            host_pieces += 1
             if isinstance(piece, dict):       # a duck-typed store's search_batch dict: lists per query
                 ids_l = docs_l = metas_l = None
                 piece = [(np.asarray(piece['distances'][p], dtype=np.float64), (piece['ids'][p], piece['documents'][p],
@@ -255,6 +274,7 @@ class ContextRetriever:
                 else:
                     chunks = chunks[:k]
                 per_query.append(chunks)
+        self.last_rerank = {'mode': 'device' if on_device and not host_pieces else 'host', 'lists': len(per_query) if self.rerank else 0}
         self.last_mmr = {'mode': 'host', 'lists': sum(1 for chunks in per_query if len(chunks) > 1) if self.diversity_penalty > 0 else 0}
         if self.diversity_penalty > 0 and self.mmr_vectors == 'device' and ids_l is not None and self._mmr_on_device(per_query, row_of):
             return per_query
@@ -283,6 +303,45 @@ class ContextRetriever:
                 per_query = [self._apply_diversity(chunks, vectors=vectors[[index[c['text']] for c in chunks]])
                              if len(chunks) > 1 else chunks for chunks in per_query]
         return per_query
+
+    def _rerank_on_device(self, queries: List[str], piece, k: int, row_of: Dict[int, int]) -> Optional[List[List[Dict]]]:
+        """The chunk lists of one piece of _search_many (per query: scores fp32, sidecar rows int64, best first), scored,
+        thresholded and lexically re-ranked by ONE VectorStore.rerank_lexical call: a padded [queries, longest] block up, the
+        order, scores and re-rank scores back, and only the surviving <= k dicts per query built -- the keys and values the host
+        loop of retrieve_batch produces.  None (nothing done) when a list is longer than 64 or the store answers None."""
+        col = self.vector_store.collection
+        m_max = max((len(sc) for sc, _ in piece), default=0)
+        if not 1 <= m_max <= 64:
+            return None
+        scores = np.zeros((len(piece), m_max), dtype=np.float32)
+        rows = np.full((len(piece), m_max), -1, dtype=np.int64)
+        for i, (sc, r) in enumerate(piece):
+            scores[i, :len(sc)], rows[i, :len(r)] = sc, r
+        got = self.vector_store.rerank_lexical(queries, scores, rows, k, self.similarity_threshold)
+        if got is None:
+            return None
+        order, count, sim, rr, reranked = got
+        dist = (np.float32(1.0) - scores).astype(np.float64)         # the store's distances, as search() returns them
+        ids_l, docs_l, metas_l = col.ids, col.documents, col.metadatas
+        out = []
+        for i in range(len(piece)):
+            n = int(count[i])
+            if n == 0:
+                logger.warning("No results found for query" if not (rows[i] >= 0).any()
+                               else f"No chunks passed similarity threshold of {self.similarity_threshold}")
+                out.append([])
+                continue
+            at = order[i, :n].tolist()
+            r_i, s_i, d_i = rows[i, at].tolist(), sim[i, at].tolist(), dist[i, at].tolist()
+            chunks = [{'text': docs_l[r], 'score': s_, 'distance': d_, 'metadata': metas_l[r] if metas_l else {}, 'chunk_id': ids_l[r]}
+                      for r, s_, d_ in zip(r_i, s_i, d_i)]
+            if reranked[i]:
+                for c_, v in zip(chunks, rr[i, at].tolist()):
+                    c_['rerank_score'] = v
+            for c_, r in zip(chunks, r_i):
+                row_of[id(c_)] = r
+            out.append(chunks)
+        return out
 
     def _mmr_on_device(self, per_query: List[List[Dict]], row_of: Dict[int, int]) -> bool:
         """Re-order, in place, every list of `per_query` with more than one chunk by the store's MMR kernel: one padded

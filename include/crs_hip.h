@@ -228,6 +228,33 @@ int crs_refine_large_cert(const float* q32_dev, const void* q16_dev, int nq, int
 int crs_mmr_order(const float* vecs_dev, int64_t n_rows, int dim, const int64_t* rows_dev, const double* rel_dev,
                   const int32_t* counts_dev, int nq, int m_max, double lam, int32_t* order_dev, void* stream);
 
+/* ---- lexical re-rank: replaces the scoring, threshold and _rerank loops of ContextRetriever.retrieve_batch -- rag/retrieval.py ----
+ * (additive to ABI 3; csrc/rerank.hip).  Processes `nq` result lists of at most m_max <= CRS_MAX_K candidates in one launch, one
+ * wave per list, with the host's fp64 arithmetic (every operation rounded on its own), so the outputs carry the host's bits:
+ *   scores_dev       fp32 [nq, m_max]   the store's cosine scores, list order
+ *   rows_dev         int64 [nq, m_max]  sidecar row of each candidate; a negative row is an empty slot; a row >= n_rows is never
+ *                                       dereferenced and has no hits
+ *   doc_offsets_dev  int64 [n_rows + 1] CSR over doc_tokens_dev: row r holds the ascending distinct token ids of its document
+ *   doc_tokens_dev   int32 [n_doc_tokens]  (may be null when n_doc_tokens is 0); offsets are clamped into [0, n_doc_tokens]
+ *   q_offsets_dev    int64 [nq + 1]     CSR over q_tokens_dev: the ascending distinct KNOWN token ids of each query
+ *   q_tokens_dev     int32 [n_q_tokens] (may be null when n_q_tokens is 0); offsets are clamped into [0, n_q_tokens]
+ *   q_norm_dev       int32 [nq]         max(distinct tokens of the query, 1), tokens no document holds included
+ *   k, threshold     list length wanted (>= 1) and similarity_threshold
+ * Per list: dist = (double)(1.0f - score); d = min(max(dist, 0), 2); sim = min(max(1 - d * d / 2, 0), 1) (NaN stays NaN); a
+ * candidate is kept iff sim >= threshold.  More than k kept: rr = sim * 0.7 + (hits / q_norm) * 0.3 with hits = the number of query
+ * ids among the row's ids, ordered by rr descending, equal rr by list position ascending, cut to k, reranked = 1.  Otherwise the
+ * first min(kept, k) kept positions in list order, reranked = 0.
+ *   order_dev        int32 [nq, m_max]  out: input positions, -1 past the count
+ *   count_dev        int32 [nq]         out: entries of order
+ *   sim_dev          fp64 [nq, m_max]   out, by input position (0 for an empty slot)
+ *   rr_dev           fp64 [nq, m_max]   out, by input position: the re-rank score of the kept candidates of a reranked list, else 0
+ *   reranked_dev     int32 [nq]         out
+ * No host synchronisation, no workspace. */
+int crs_rerank_lexical(const float* scores_dev, const int64_t* rows_dev, int nq, int m_max, const int64_t* doc_offsets_dev,
+                       const int32_t* doc_tokens_dev, int64_t n_rows, int64_t n_doc_tokens, const int64_t* q_offsets_dev,
+                       const int32_t* q_tokens_dev, int64_t n_q_tokens, const int32_t* q_norm_dev, int k, double threshold,
+                       int32_t* order_dev, int32_t* count_dev, double* sim_dev, double* rr_dev, int32_t* reranked_dev, void* stream);
+
 /* ---- one-collective exchange (ONE all-gather per query batch) ------------------
  * A rank's per-shard result travels as one contiguous "wire block":
  *     [ ids int64 [nq, k] | scores fp32 [nq, k] | pad to 8 bytes ]        crs_wire_bytes(nq, k) bytes
