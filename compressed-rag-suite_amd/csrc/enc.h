@@ -55,6 +55,11 @@ int gemm_rowln2_launch(const _Float16* a, const _Float16* w, const float* bias, 
 int attention_launch(const _Float16* qkv, const int* lens, _Float16* ctx, int batch, int seq, int hidden,
                      int heads, hipStream_t stream);
 
+// enc_attn_relbias.hip: the same with bias[h][key - query] added to every score before the softmax.  rel_bias is fp32
+// [heads, 2 span - 1], entry (key - query) + span - 1; span >= seq, seq <= 512 (-1 otherwise).  <= 21 KB of LDS.
+int attention_relbias_launch(const _Float16* qkv, const int* lens, const float* rel_bias, int span, _Float16* ctx, int batch,
+                             int seq, int hidden, int heads, hipStream_t stream);
+
 // enc_misc.hip
 int embed_ln_launch(const int* ids, const float* word, const float* pos, const float* type0, const float* g,
                     const float* b, float eps, int tokens, int seq, int hidden, int vocab, float* x32,

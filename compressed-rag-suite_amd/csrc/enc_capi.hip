@@ -128,11 +128,18 @@ int crs_gemm_f16(const void* a_dev, const void* w_dev, const float* bias_dev, co
 static int encoder_forward(const crs_encoder_desc* d, const crs_encoder_weights* w, const int32_t* ids_dev,
                            const int32_t* lens_dev, int batch, int seq, void* workspace_dev,
                            size_t workspace_bytes, float* out_dev, int normalize, float* hidden_out_dev,
-                           _Float16* q16_out_dev, int q16_row_elems, void* stream) {
+                           _Float16* q16_out_dev, int q16_row_elems, void* stream, const crs_encoder_ext* ext) {
   const int rc = check_desc(d);
   if (rc) return rc;
+  const float* rel_bias = ext ? ext->rel_bias_dev : nullptr;   // additive relative-position bias (crs_encoder_ext)
+  const int rel_span = rel_bias ? ext->rel_span : 0;
   if (!w || !w->layers || !ids_dev || !lens_dev || !workspace_dev || !out_dev) return crs::set_error(CRS_EINVAL, "null pointer");
   if (batch <= 0 || seq <= 0 || seq > d->max_pos) return crs::set_error(CRS_EINVAL, "bad batch/seq (seq <= max_pos)");
+  if (rel_bias && (rel_span < seq || seq > 512)) {
+    char m[160];
+    snprintf(m, sizeof m, "relative bias: rel_span %d must be >= seq %d, and seq <= 512", rel_span, seq);
+    return crs::set_error(CRS_EINVAL, m);
+  }
   const Layout l = make_layout(d, batch, seq);
   if (workspace_bytes < l.total) return crs::set_error(CRS_ENOSPC, "encoder workspace too small");
   hipStream_t st = (hipStream_t)stream;
@@ -162,7 +169,7 @@ static int encoder_forward(const crs_encoder_desc* d, const crs_encoder_weights*
   const int s8_h = (!panel_h) ? crs::gemm8_splitk(T, H, H) : 0, s8_f = (!panel_f) ? crs::gemm8_splitk(T, H, F) : 0;
   // short sequences in the launch-bound regime: QKV projection + attention as one kernel (enc_qkvattn.hip)
   const int small = (d->flags & CRS_ENC_SMALL_LDS) ? 1 : 0;
-  const bool fuse_qa = T <= kPanelMaxTokens && !small && qa_enabled() && crs::qkv_attn_supported(H, d->heads, seq);
+  const bool fuse_qa = !rel_bias && T <= kPanelMaxTokens && !small && qa_enabled() && crs::qkv_attn_supported(H, d->heads, seq);
   for (int li = 0; li < d->layers; ++li) {
     const crs_encoder_layer& L = w->layers[li];
     if (fuse_qa) {
@@ -170,7 +177,8 @@ static int encoder_forward(const crs_encoder_desc* d, const crs_encoder_weights*
     } else {
     if (single_h) CRS_TRY(crs::gemm_panel_launch(x16, (const _Float16*)L.w_qkv, L.b_qkv, qkv, T, 3 * H, H, 0, small, st), "qkv gemm");
     else CRS_TRY(crs::gemm_f16_launch(x16, (const _Float16*)L.w_qkv, L.b_qkv, nullptr, qkv, T, 3 * H, H, 0, st), "qkv gemm");
-    CRS_TRY(crs::attention_launch(qkv, lens_dev, ctx, batch, seq, H, d->heads, st), "attention");
+    if (rel_bias) CRS_TRY(crs::attention_relbias_launch(qkv, lens_dev, rel_bias, rel_span, ctx, batch, seq, H, d->heads, st), "attention (relative bias)");
+    else CRS_TRY(crs::attention_launch(qkv, lens_dev, ctx, batch, seq, H, d->heads, st), "attention");
     }
     if (big_ln_h) {
       CRS_TRY(crs::gemm_rowln2_launch(ctx, (const _Float16*)L.w_o, L.b_o, x32, L.ln1_g, L.ln1_b, d->ln_eps, T, H, H, x32, x16, st), "out projection + layernorm 1");
@@ -207,23 +215,39 @@ static int encoder_forward(const crs_encoder_desc* d, const crs_encoder_weights*
   return CRS_OK;
 }
 
+int crs_encoder_forward_ex(const crs_encoder_desc* d, const crs_encoder_weights* w, const int32_t* ids_dev,
+                           const int32_t* lens_dev, int batch, int seq, void* workspace_dev,
+                           size_t workspace_bytes, float* out_dev, int normalize, float* hidden_out_dev,
+                           void* stream, const crs_encoder_ext* ext) {
+  return encoder_forward(d, w, ids_dev, lens_dev, batch, seq, workspace_dev, workspace_bytes, out_dev, normalize,
+                         hidden_out_dev, nullptr, 0, stream, ext);
+}
+
 int crs_encoder_forward(const crs_encoder_desc* d, const crs_encoder_weights* w, const int32_t* ids_dev,
                         const int32_t* lens_dev, int batch, int seq, void* workspace_dev,
                         size_t workspace_bytes, float* out_dev, int normalize, float* hidden_out_dev,
                         void* stream) {
-  return encoder_forward(d, w, ids_dev, lens_dev, batch, seq, workspace_dev, workspace_bytes, out_dev, normalize,
-                         hidden_out_dev, nullptr, 0, stream);
+  return crs_encoder_forward_ex(d, w, ids_dev, lens_dev, batch, seq, workspace_dev, workspace_bytes, out_dev, normalize,
+                                hidden_out_dev, stream, nullptr);
+}
+
+int crs_encoder_forward_queries_ex(const crs_encoder_desc* d, const crs_encoder_weights* w, const int32_t* ids_dev,
+                                   const int32_t* lens_dev, int batch, int seq, void* workspace_dev,
+                                   size_t workspace_bytes, float* out_dev, void* q16_out_dev, int slab_type,
+                                   void* stream, const crs_encoder_ext* ext) {
+  if (!q16_out_dev) return crs::set_error(CRS_EINVAL, "null pointer");
+  if (slab_type != CRS_SLAB_F16 && slab_type != CRS_SLAB_I8) return crs::set_error(CRS_EINVAL, "bad slab_type");
+  if (!d) return crs::set_error(CRS_EINVAL, "null descriptor");
+  return encoder_forward(d, w, ids_dev, lens_dev, batch, seq, workspace_dev, workspace_bytes, out_dev, 1, nullptr,
+                         reinterpret_cast<_Float16*>(q16_out_dev), crs_row_elems(d->hidden, slab_type), stream, ext);
 }
 
 int crs_encoder_forward_queries(const crs_encoder_desc* d, const crs_encoder_weights* w, const int32_t* ids_dev,
                                 const int32_t* lens_dev, int batch, int seq, void* workspace_dev,
                                 size_t workspace_bytes, float* out_dev, void* q16_out_dev, int slab_type,
                                 void* stream) {
-  if (!q16_out_dev) return crs::set_error(CRS_EINVAL, "null pointer");
-  if (slab_type != CRS_SLAB_F16 && slab_type != CRS_SLAB_I8) return crs::set_error(CRS_EINVAL, "bad slab_type");
-  if (!d) return crs::set_error(CRS_EINVAL, "null descriptor");
-  return encoder_forward(d, w, ids_dev, lens_dev, batch, seq, workspace_dev, workspace_bytes, out_dev, 1, nullptr,
-                         reinterpret_cast<_Float16*>(q16_out_dev), crs_row_elems(d->hidden, slab_type), stream);
+  return crs_encoder_forward_queries_ex(d, w, ids_dev, lens_dev, batch, seq, workspace_dev, workspace_bytes, out_dev,
+                                        q16_out_dev, slab_type, stream, nullptr);
 }
 
 }  // extern "C"

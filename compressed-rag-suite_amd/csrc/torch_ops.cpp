@@ -508,8 +508,10 @@ void rerank_lexical(const Tensor& scores, const Tensor& rows, const Tensor& doc_
 // ---- encoder -------------------------------------------------------------------------------------------------
 // desc = [vocab_size, hidden, layers, heads, ffn, max_pos, pooling, flags (CRS_ENC_*, optional)]; weights = [word_emb, pos_emb, type_emb, emb_ln_g, emb_ln_b]
 // followed by 12 tensors per layer in crs_encoder_layer order (w_qkv b_qkv w_o b_o ln1_g ln1_b w_up b_up w_down b_down ln2_g ln2_b).
-void encoder_forward(const Tensor& ids, const Tensor& lens, at::TensorList weights, at::IntArrayRef desc, double ln_eps, Tensor workspace,
-                     Tensor out, c10::optional<Tensor> q16_out, int64_t slab_type, bool normalize, c10::optional<Tensor> hidden_out) {
+// encoder_forward_ex adds rel_bias (optional): fp32 [heads, 2 * span - 1], the additive relative-position bias of crs_encoder_ext.
+void encoder_forward_ex(const Tensor& ids, const Tensor& lens, at::TensorList weights, at::IntArrayRef desc, double ln_eps, Tensor workspace,
+                        Tensor out, c10::optional<Tensor> q16_out, int64_t slab_type, bool normalize, c10::optional<Tensor> hidden_out,
+                        c10::optional<Tensor> rel_bias) {
   want(ids, at::kInt, "ids");
   want(lens, at::kInt, "lens");
   want(out, at::kFloat, "out");
@@ -530,13 +532,21 @@ void encoder_forward(const Tensor& ids, const Tensor& lens, at::TensorList weigh
   crs_encoder_weights cw{(const float*)weights[0].data_ptr(), (const float*)weights[1].data_ptr(), (const float*)weights[2].data_ptr(),
                          (const float*)weights[3].data_ptr(), (const float*)weights[4].data_ptr(), layers.data()};
   const int b = (int)ids.size(0), s = (int)ids.size(1);
+  crs_encoder_ext ext{nullptr, 0};
+  if (rel_bias.has_value() && rel_bias->defined()) {
+    want(*rel_bias, at::kFloat, "rel_bias");
+    same_device(ids, {opt_t(rel_bias)}, "crs::encoder_forward_ex");
+    TORCH_CHECK(rel_bias->dim() == 2 && rel_bias->size(0) == d.heads && (rel_bias->size(1) & 1) == 1, "rel_bias must be [heads, 2 * span - 1]");
+    ext.rel_bias_dev = rel_bias->data_ptr<float>();
+    ext.rel_span = (int32_t)((rel_bias->size(1) + 1) / 2);
+  }
   c10::hip::HIPGuardMasqueradingAsCUDA g(ids.device());
   if (q16_out.has_value() && q16_out->defined()) {
     want(*q16_out, at::kHalf, "q16_out");
     TORCH_CHECK(normalize && !(hidden_out.has_value() && hidden_out->defined()), "q16_out needs normalize=True and no hidden_out");
     TORCH_CHECK(q16_out->numel() == (int64_t)b * crs_row_elems(d.hidden, (int)slab_type), "q16_out must be [B, crs_row_elems(H, slab_type)]");
-    ok(crs_encoder_forward_queries(&d, &cw, ids.data_ptr<int32_t>(), lens.data_ptr<int32_t>(), b, s, workspace.data_ptr(),
-                                   (size_t)workspace.nbytes(), out.data_ptr<float>(), q16_out->data_ptr(), (int)slab_type, cur_stream(ids)),
+    ok(crs_encoder_forward_queries_ex(&d, &cw, ids.data_ptr<int32_t>(), lens.data_ptr<int32_t>(), b, s, workspace.data_ptr(),
+                                      (size_t)workspace.nbytes(), out.data_ptr<float>(), q16_out->data_ptr(), (int)slab_type, cur_stream(ids), &ext),
        "crs::encoder_forward");
     return;
   }
@@ -546,8 +556,13 @@ void encoder_forward(const Tensor& ids, const Tensor& lens, at::TensorList weigh
     TORCH_CHECK(hidden_out->numel() == (int64_t)b * s * d.hidden, "hidden_out must be [B, S, H]");
     hid = hidden_out->data_ptr<float>();
   }
-  ok(crs_encoder_forward(&d, &cw, ids.data_ptr<int32_t>(), lens.data_ptr<int32_t>(), b, s, workspace.data_ptr(), (size_t)workspace.nbytes(),
-                         out.data_ptr<float>(), normalize ? 1 : 0, hid, cur_stream(ids)), "crs::encoder_forward");
+  ok(crs_encoder_forward_ex(&d, &cw, ids.data_ptr<int32_t>(), lens.data_ptr<int32_t>(), b, s, workspace.data_ptr(), (size_t)workspace.nbytes(),
+                            out.data_ptr<float>(), normalize ? 1 : 0, hid, cur_stream(ids), &ext), "crs::encoder_forward");
+}
+
+void encoder_forward(const Tensor& ids, const Tensor& lens, at::TensorList weights, at::IntArrayRef desc, double ln_eps, Tensor workspace,
+                     Tensor out, c10::optional<Tensor> q16_out, int64_t slab_type, bool normalize, c10::optional<Tensor> hidden_out) {
+  encoder_forward_ex(ids, lens, weights, desc, ln_eps, workspace, out, q16_out, slab_type, normalize, hidden_out, c10::nullopt);
 }
 
 }  // namespace
@@ -588,6 +603,8 @@ TORCH_LIBRARY(crs, m) {
         "Tensor q_norm, int k, float threshold, Tensor(a!) order, Tensor(b!) count, Tensor(c!) sim, Tensor(d!) rr, Tensor(e!) reranked) -> ()");
   m.def("encoder_forward(Tensor ids, Tensor lens, Tensor[] weights, int[] desc, float ln_eps, Tensor(a!) workspace, Tensor(b!) out, "
         "Tensor(c!)? q16_out, int slab_type, bool normalize, Tensor(d!)? hidden_out) -> ()");
+  m.def("encoder_forward_ex(Tensor ids, Tensor lens, Tensor[] weights, int[] desc, float ln_eps, Tensor(a!) workspace, Tensor(b!) out, "
+        "Tensor(c!)? q16_out, int slab_type, bool normalize, Tensor(d!)? hidden_out, Tensor? rel_bias=None) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(crs, CUDA, m) {   // the HIP backend of torch-ROCm dispatches under the "CUDA" key
@@ -613,4 +630,5 @@ TORCH_LIBRARY_IMPL(crs, CUDA, m) {   // the HIP backend of torch-ROCm dispatches
   m.impl("mmr_order_out", &mmr_order_out);
   m.impl("rerank_lexical", &rerank_lexical);
   m.impl("encoder_forward", &encoder_forward);
+  m.impl("encoder_forward_ex", &encoder_forward_ex);
 }

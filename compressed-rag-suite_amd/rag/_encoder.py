@@ -1,8 +1,10 @@
 """ctypes binding of the encoder half of libcrs_hip.so (include/crs_encoder.h) + weight upload.
 
-``HipEncoder`` owns the device copies of a BERT-family checkpoint (HuggingFace state-dict names,
-fp32 numpy in; matrices are cast to fp16 and Q/K/V stacked on upload) and runs the forward
-through ``crs_encoder_forward``.  Token ids in, pooled sentence embeddings out; no CPU fallback.
+``HipEncoder`` owns the device copies of a BERT-family checkpoint (HuggingFace BertModel state-dict
+names, fp32 numpy in; matrices are cast to fp16 and Q/K/V stacked on upload) and runs the forward
+through ``crs_encoder_forward_ex``.  MPNet checkpoints come in under the same names plus
+``encoder.relative_attention_bias.weight`` (rag/embedding.py maps them), with ``ModelShape.rel_buckets``
+and ``pos_offset`` set: the bias is resolved per offset on the host and handed to the library.  Token ids in, pooled sentence embeddings out; no CPU fallback.
 """
 from __future__ import annotations
 
@@ -34,12 +36,21 @@ class EncoderWeights(Structure):
                 ("emb_ln_b", c_void_p), ("layers", POINTER(EncoderLayer))]
 
 
+class EncoderExt(Structure):      # crs_encoder_ext
+    _fields_ = [("rel_bias_dev", c_void_p), ("rel_span", c_int32)]
+
+
 nat.register_signatures({
     "crs_encoder_workspace_bytes": (c_int, [POINTER(EncoderDesc), c_int, c_int, POINTER(c_size_t)]),
     "crs_encoder_forward": (c_int, [POINTER(EncoderDesc), POINTER(EncoderWeights), c_void_p, c_void_p, c_int,
                                     c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p]),
     "crs_encoder_forward_queries": (c_int, [POINTER(EncoderDesc), POINTER(EncoderWeights), c_void_p, c_void_p, c_int,
                                             c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_void_p]),
+    "crs_encoder_forward_ex": (c_int, [POINTER(EncoderDesc), POINTER(EncoderWeights), c_void_p, c_void_p, c_int,
+                                       c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, POINTER(EncoderExt)]),
+    "crs_encoder_forward_queries_ex": (c_int, [POINTER(EncoderDesc), POINTER(EncoderWeights), c_void_p, c_void_p, c_int,
+                                               c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_void_p,
+                                               POINTER(EncoderExt)]),
     "crs_gemm_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                              c_void_p]),
 })
@@ -56,6 +67,37 @@ class ModelShape:
     ln_eps: float = 1e-12
     pooling: str = "mean"
     max_seq: int = 256
+    rel_buckets: int = 0          # > 0: MPNet's bucketed relative-position bias ("encoder.relative_attention_bias.weight")
+    rel_max_distance: int = 128
+    pos_offset: int = 0           # first position id (MPNet: pad_token_id + 1 = 2); max_pos counts the table's rows
+
+
+def relative_position_bucket(rel, num_buckets: int = 32, max_distance: int = 128):
+    """MPNet's bidirectional bucket of the offsets `rel` = key - query (int array) -> int64 numpy array.  With
+    n = query - key: half the buckets per sign (keys after the query add num_buckets / 2); within a half |n| < max_exact
+    = num_buckets / 4 maps to itself, larger |n| to max_exact + floor(log(|n| / max_exact) / log(max_distance /
+    max_exact) * (half - max_exact)), capped at half - 1.  The logarithm is evaluated in fp32 with torch's kernels, as
+    the published model does: at |n| = 32, 128 the exact value is a whole number and the fp32 rounding decides the bucket."""
+    import math
+    import torch
+    n = -torch.as_tensor(np.asarray(rel, dtype=np.int64))
+    half = num_buckets // 2
+    ret = (n < 0).to(torch.long) * half
+    n = n.abs()
+    max_exact = half // 2
+    large = max_exact + (torch.log(n.float() / max_exact) / math.log(max_distance / max_exact) * (half - max_exact)).to(torch.long)
+    large = torch.minimum(large, torch.full_like(large, half - 1))
+    return (ret + torch.where(n < max_exact, n, large)).numpy()
+
+
+def relative_bias_table(weight, span: int, num_buckets: int, max_distance: int = 128) -> np.ndarray:
+    """relative_attention_bias.weight [buckets, heads] -> fp32 [heads, 2 * span - 1]: entry (key - query) + span - 1
+    is the bias of that offset (what crs_encoder_ext.rel_bias_dev takes)."""
+    w = np.asarray(weight, dtype=np.float32)
+    if w.ndim != 2 or w.shape[0] != num_buckets:
+        raise ValueError(f"relative_attention_bias.weight must be [{num_buckets}, heads], got {w.shape}")
+    bucket = relative_position_bucket(np.arange(-(span - 1), span), num_buckets, max_distance)
+    return np.ascontiguousarray(w[bucket].T)
 
 
 def gemm_f16(a, w, bias=None, residual=None, mode: int = 0):
@@ -94,8 +136,11 @@ class HipEncoder:
             self._keep.append(t)
             return t
 
-        self.desc = EncoderDesc(shape.vocab_size, shape.hidden, shape.layers, shape.heads, shape.ffn, shape.max_pos,
-                                shape.ln_eps, POOL_CLS if shape.pooling == "cls" else POOL_MEAN, 0)
+        # position ids start at pos_offset: the kernels index the table from its row pos_offset on
+        if not 0 <= shape.pos_offset < shape.max_pos:
+            raise ValueError("pos_offset must be inside the position table")
+        self.desc = EncoderDesc(shape.vocab_size, shape.hidden, shape.layers, shape.heads, shape.ffn,
+                                shape.max_pos - shape.pos_offset, shape.ln_eps, POOL_CLS if shape.pooling == "cls" else POOL_MEAN, 0)
         self._layers = (EncoderLayer * shape.layers)()
         for i in range(shape.layers):
             p = f"encoder.layer.{i}."
@@ -112,7 +157,7 @@ class HipEncoder:
                 setattr(self._layers[i], fname, t.data_ptr())
         self.weights = EncoderWeights(
             dev32("embeddings.word_embeddings.weight").data_ptr(),
-            dev32("embeddings.position_embeddings.weight").data_ptr(),
+            dev32("embeddings.position_embeddings.weight")[shape.pos_offset:].data_ptr(),
             dev32("embeddings.token_type_embeddings.weight").data_ptr(),
             dev32("embeddings.LayerNorm.weight").data_ptr(),
             dev32("embeddings.LayerNorm.bias").data_ptr(),
@@ -121,6 +166,17 @@ class HipEncoder:
         # the same tensors in the order torch.ops.crs.encoder_forward takes them (csrc/torch_ops.cpp)
         self._wlist = self._keep[-5:] + self._keep[:-5]     # embeddings first, then 12 tensors per layer
         assert len(self._wlist) == 5 + 12 * shape.layers
+        if shape.pos_offset:
+            self._wlist[1] = self._wlist[1][shape.pos_offset:]       # (a contiguous view of the kept tensor)
+        # additive relative-position bias, resolved per offset once: fp32 [heads, 2 * max_seq - 1] (crs_encoder_ext)
+        self.rel_bias = None
+        if shape.rel_buckets > 0:
+            span = min(shape.max_seq, shape.max_pos - shape.pos_offset)
+            table = relative_bias_table(weights["encoder.relative_attention_bias.weight"], span, shape.rel_buckets,
+                                        shape.rel_max_distance)
+            if table.shape[0] != shape.heads:
+                raise ValueError("relative_attention_bias.weight must have one column per head")
+            self.rel_bias = torch.from_numpy(table).to(self.device)
 
     @property
     def _desc_list(self):
@@ -168,6 +224,6 @@ class HipEncoder:
         if small_lds:          # per call, not process-wide: the role-lane engine asks for it, everyone else gets the default forms
             desc = desc[:7] + [desc[7] | ENC_SMALL_LDS]
         with nat._translate():
-            nat.ops().encoder_forward(ids, lens, self._wlist, desc, float(self.desc.ln_eps), ws, out, q16_out,
-                                      int(slab_type), bool(normalize), hidden)
+            nat.ops().encoder_forward_ex(ids, lens, self._wlist, desc, float(self.desc.ln_eps), ws, out, q16_out,
+                                         int(slab_type), bool(normalize), hidden, self.rel_bias)
         return (out, hidden) if return_hidden else out

@@ -10,7 +10,7 @@ Model resolution, offline by construction (the reference fetches by hub name, wh
 here): ``model_path`` (additive key) or ``model_name`` may be a LOCAL sentence-transformers
 directory (config.json, model.safetensors, vocab.txt, optional sentence_bert_config.json and
 1_Pooling/config.json); else ``$CRS_MODEL_DIR/<basename of model_name>`` is tried; else, when
-``model_name`` is ``synthetic:<minilm|bge|tiny>`` or ``CRS_ALLOW_SYNTHETIC_WEIGHTS=1`` is set,
+``model_name`` is ``synthetic:<minilm|bge|tiny|mpnet|tiny-mpnet>`` or ``CRS_ALLOW_SYNTHETIC_WEIGHTS=1`` is set,
 seeded random weights of the named architecture are used with a hash tokeniser (plumbing and
 benchmarks only -- embeddings are then meaningless as language).  Anything else raises.
 """
@@ -36,12 +36,21 @@ _KNOWN = {
     "bge-base-en-v1.5": dict(vocab_size=30522, hidden=768, layers=12, heads=12, ffn=3072, max_pos=512,
                              pooling="cls", max_seq=512),
     "tiny": dict(vocab_size=1000, hidden=64, layers=2, heads=4, ffn=256, max_pos=64, pooling="mean", max_seq=64),
+    # MPNet: BERT's layer stack + a bucketed relative-position bias in attention; position ids start at 2 (max_pos rows
+    # in the table, the first two unused), no token types, <s> </s> <pad> <unk> in the WordPiece vocabulary
+    "all-mpnet-base-v2": dict(vocab_size=30527, hidden=768, layers=12, heads=12, ffn=3072, max_pos=514, pooling="mean",
+                              max_seq=384, ln_eps=1e-5, rel_buckets=32, pos_offset=2),
+    "tiny-mpnet": dict(vocab_size=1000, hidden=64, layers=2, heads=4, ffn=256, max_pos=66, pooling="mean", max_seq=64,
+                       rel_buckets=32, pos_offset=2),
 }
-_ALIASES = {"minilm": "all-minilm-l6-v2", "bge": "bge-base-en-v1.5", "bge-base": "bge-base-en-v1.5"}
+_ALIASES = {"minilm": "all-minilm-l6-v2", "bge": "bge-base-en-v1.5", "bge-base": "bge-base-en-v1.5", "mpnet": "all-mpnet-base-v2"}
+REL_BIAS = "encoder.relative_attention_bias.weight"      # [buckets, heads], shared by all layers (MPNet)
 
 
 def synthetic_weights(shape, seed: int = 0, scale: float = 0.05) -> Dict[str, np.ndarray]:
-    """Seeded random checkpoint with HuggingFace BertModel tensor names (one PCG64 stream per tensor)."""
+    """Seeded random checkpoint with HuggingFace BertModel tensor names (one PCG64 stream per tensor).  Shapes with
+    `rel_buckets` (MPNet) also get the relative-position bias table (~N(0, 0.5): real tables are O(1)) and, having no
+    token types, a zero token-type table."""
     h, f = shape.hidden, shape.ffn
     names = [("embeddings.word_embeddings.weight", (shape.vocab_size, h)),
              ("embeddings.position_embeddings.weight", (shape.max_pos, h)),
@@ -57,6 +66,8 @@ def synthetic_weights(shape, seed: int = 0, scale: float = 0.05) -> Dict[str, np
                   (p + "intermediate.dense.weight", (f, h)), (p + "intermediate.dense.bias", (f,)),
                   (p + "output.dense.weight", (h, f)), (p + "output.dense.bias", (h,)),
                   (p + "output.LayerNorm.weight", (h,)), (p + "output.LayerNorm.bias", (h,))]
+    if getattr(shape, "rel_buckets", 0) > 0:      # last: the other tensors keep their streams
+        names.append((REL_BIAS, (shape.rel_buckets, shape.heads)))
     out = {}
     for idx, (name, shp) in enumerate(names):
         rng = np.random.Generator(np.random.PCG64([seed, idx]))
@@ -64,9 +75,36 @@ def synthetic_weights(shape, seed: int = 0, scale: float = 0.05) -> Dict[str, np
             a = 1.0 + 0.05 * rng.standard_normal(shp, dtype=np.float32)
         elif name.endswith(".bias"):
             a = 0.02 * rng.standard_normal(shp, dtype=np.float32)
+        elif name == REL_BIAS:
+            a = 0.5 * rng.standard_normal(shp, dtype=np.float32)
         else:
             a = scale * rng.standard_normal(shp, dtype=np.float32)
         out[name] = a.astype(np.float32)
+    if getattr(shape, "rel_buckets", 0) > 0:
+        out["embeddings.token_type_embeddings.weight"][:] = 0.0
+    return out
+
+
+# MPNetModel's tensor names -> the internal (BertModel) ones, inside "encoder.layer.<i>."
+_MPNET_LAYER_NAMES = {"attention.attn.q.": "attention.self.query.", "attention.attn.k.": "attention.self.key.",
+                      "attention.attn.v.": "attention.self.value.", "attention.attn.o.": "attention.output.dense.",
+                      "attention.LayerNorm.": "attention.output.LayerNorm."}
+
+
+def _mpnet_weights(raw: Dict[str, np.ndarray], hidden: int) -> Dict[str, np.ndarray]:
+    """An MPNet state dict (with or without the leading "mpnet.") under the internal names, plus a zero token-type row."""
+    out = {}
+    for k, v in raw.items():
+        k = k[6:] if k.startswith("mpnet.") else k
+        if k.startswith("encoder.layer."):
+            head, rest = k.split(".", 3)[:3], k.split(".", 3)[3]
+            for old, new in _MPNET_LAYER_NAMES.items():
+                if rest.startswith(old):
+                    rest = new + rest[len(old):]
+                    break
+            k = ".".join(head) + "." + rest
+        out[k] = np.asarray(v, dtype=np.float32)
+    out["embeddings.token_type_embeddings.weight"] = np.zeros((1, hidden), dtype=np.float32)
     return out
 
 
@@ -115,16 +153,28 @@ def _load_local_dir(path: str):
             pooling = "cls"
         elif modes not in ([], ["mean_tokens"]):
             raise NotImplementedError(f"pooling mode(s) {modes} are not supported (mean and CLS are)")
+    model_type = cfg.get("model_type", "bert")
+    if model_type not in ("bert", "mpnet"):
+        raise NotImplementedError(f"model_type '{model_type}' is not supported by this encoder (bert and mpnet are)")
+    rel_buckets = pos_offset = 0
+    if model_type == "mpnet":
+        rel_buckets = int(cfg.get("relative_attention_num_buckets", 32))
+        pos_offset = int(cfg.get("pad_token_id", 1)) + 1       # position ids count from padding_idx + 1
     shape = ModelShape(cfg["vocab_size"], cfg["hidden_size"], cfg["num_hidden_layers"], cfg["num_attention_heads"],
-                       cfg["intermediate_size"], cfg["max_position_embeddings"], cfg.get("layer_norm_eps", 1e-12),
-                       pooling, min(max_seq, cfg["max_position_embeddings"]))
+                       cfg["intermediate_size"], cfg["max_position_embeddings"],
+                       cfg.get("layer_norm_eps", 1e-5 if model_type == "mpnet" else 1e-12),
+                       pooling, min(max_seq, cfg["max_position_embeddings"] - pos_offset),
+                       rel_buckets=rel_buckets, pos_offset=pos_offset)
     raw = load_file(os.path.join(tr_dir, "model.safetensors"))
-    weights = {(k[5:] if k.startswith("bert.") else k): np.asarray(v, dtype=np.float32) for k, v in raw.items()}
+    if model_type == "mpnet":
+        weights = _mpnet_weights(raw, shape.hidden)
+    else:
+        weights = {(k[5:] if k.startswith("bert.") else k): np.asarray(v, dtype=np.float32) for k, v in raw.items()}
     return shape, weights, tokenizer_from_model_dir(tr_dir), pre_lower, has_normalize
 
 
 class EmbeddingModel:
-    """Sentence encoder wrapper (BERT-family checkpoints) running on the GPU."""
+    """Sentence encoder wrapper (BERT and MPNet checkpoints) running on the GPU."""
 
     def __init__(self, config: dict):
         self.model_name = config.get('model_name', 'sentence-transformers/all-MiniLM-L6-v2')
@@ -136,7 +186,7 @@ class EmbeddingModel:
         shape, weights, self.tokenizer = self._resolve(config)
         if config.get('max_seq_length'):
             from dataclasses import replace
-            shape = replace(shape, max_seq=min(int(config['max_seq_length']), shape.max_pos))
+            shape = replace(shape, max_seq=min(int(config['max_seq_length']), shape.max_pos - shape.pos_offset))
         if config.get('pooling'):
             from dataclasses import replace
             shape = replace(shape, pooling=config['pooling'])
@@ -168,16 +218,18 @@ class EmbeddingModel:
         key = _ALIASES.get(key.lower(), key.lower())
         if key in _KNOWN and (name.startswith("synthetic:") or os.environ.get("CRS_ALLOW_SYNTHETIC_WEIGHTS") == "1"):
             logger.warning(f"Using SYNTHETIC weights for architecture '{key}' (no checkpoint available offline)")
-            shape = ModelShape(ln_eps=1e-12, **_KNOWN[key])
+            shape = ModelShape(**{"ln_eps": 1e-12, **_KNOWN[key]})
             seed = int(config.get('synthetic_seed', 0))
-            return shape, synthetic_weights(shape, seed), HashTokenizer(shape.vocab_size)
+            # MPNet vocabularies open with <s> <pad> </s> <unk>
+            tok = HashTokenizer(shape.vocab_size, special=(0, 2, 1)) if shape.rel_buckets else HashTokenizer(shape.vocab_size)
+            return shape, synthetic_weights(shape, seed), tok
         raise FileNotFoundError(
             f"No local checkpoint for '{name}': pass a sentence-transformers directory as model_name/model_path, "
             f"set CRS_MODEL_DIR, or use 'synthetic:minilm' (models cannot be downloaded here)")
 
     # ---- encoding ------------------------------------------------------------------------------
     def tokenize(self, texts: List[str]):
-        """-> list of id lists ([CLS] ... [SEP], truncated to max_seq).  Text is stripped (and lower-cased when the
+        """-> list of id lists ([CLS] ... [SEP] or the model's own <s> ... </s>, truncated to max_seq).  Text is stripped (and lower-cased when the
         model's sentence_bert_config.json says so) first, as sentence-transformers' Transformer.tokenize does."""
         texts = [str(t).strip() for t in texts]
         if self._pre_lower:

@@ -3,8 +3,8 @@
 The reference gets this from tokenizers==0.22.1 via sentence-transformers (rag/embedding.py:33,65;
 requirements.txt:148); the algorithm restated here is the published BERT one: clean -> lower-case
 + accent strip -> whitespace / punctuation split -> longest-match-first WordPiece with '##'
-continuations, words longer than 100 chars -> [UNK], then [CLS] ... [SEP] with truncation to the
-model's max_seq_length.  ``HashTokenizer`` stands in when no vocab.txt exists (synthetic weights):
+continuations, words longer than 100 chars -> [UNK], then [CLS] ... [SEP] (or the special tokens the
+model directory names: MPNet's <s> ... </s>) with truncation to the model's max_seq_length.  ``HashTokenizer`` stands in when no vocab.txt exists (synthetic weights):
 same splitting, ids from a stable hash, so plumbing and benchmarks run fully offline.
 """
 from __future__ import annotations
@@ -83,10 +83,10 @@ class WordPieceTokenizer:
         self.pad_id = vocab.get(pad, 0)
 
     @classmethod
-    def from_vocab_file(cls, path: str, lower: bool = True, strip_accents=None) -> "WordPieceTokenizer":
+    def from_vocab_file(cls, path: str, lower: bool = True, strip_accents=None, special=None) -> "WordPieceTokenizer":
         with open(path, encoding="utf-8") as fh:
             vocab = {line.rstrip("\n"): i for i, line in enumerate(fh)}
-        return cls(vocab, lower=lower, strip_accents=strip_accents)
+        return cls(vocab, lower=lower, strip_accents=strip_accents, **(special or {}))
 
     def _wordpiece(self, word: str) -> List[int]:
         if len(word) > 100:
@@ -127,15 +127,17 @@ class FastWordPieceTokenizer:
         self._max_len = None
 
     @classmethod
-    def from_tokenizer_json(cls, path: str) -> "FastWordPieceTokenizer":
+    def from_tokenizer_json(cls, path: str, special=None) -> "FastWordPieceTokenizer":
         """The model directory's own tokenizer.json, exactly as the reference's backend loads it (normaliser,
-        casing and accent rules included); padding off, truncation set per call."""
+        casing and accent rules included); padding off, truncation set per call.  `special` names the model's
+        special tokens (special_tokens_from_model_dir; default: read from the directory of `path`)."""
         from tokenizers import Tokenizer
         tok = Tokenizer.from_file(path)
         tok.no_padding()
-        ids = [tok.token_to_id(t) for t in ("[CLS]", "[SEP]", "[PAD]")]
+        sp = special or special_tokens_from_model_dir(os.path.dirname(path))
+        ids = [tok.token_to_id(sp[t]) for t in ("cls", "sep", "pad")]
         if ids[0] is None or ids[1] is None:
-            raise ValueError(f"{path}: not a BERT-style tokenizer ([CLS]/[SEP] missing)")
+            raise ValueError(f"{path}: not a WordPiece tokenizer of this family ({sp['cls']} / {sp['sep']} missing)")
         return cls(tok, ids[0], ids[1], ids[2] if ids[2] is not None else 0)
 
     @classmethod
@@ -154,10 +156,13 @@ class FastWordPieceTokenizer:
         return cls(tok, vocab[cls_tok], vocab[sep], vocab.get(pad, 0))
 
     @classmethod
-    def from_vocab_file(cls, path: str, lower: bool = True, strip_accents=None) -> "FastWordPieceTokenizer":
+    def from_vocab_file(cls, path: str, lower: bool = True, strip_accents=None, special=None) -> "FastWordPieceTokenizer":
         with open(path, encoding="utf-8") as fh:
             vocab = {line.rstrip("\n"): i for i, line in enumerate(fh)}
-        return cls.from_vocab(vocab, lower=lower, strip_accents=strip_accents)
+        sp = dict(special or {})
+        if "cls" in sp:
+            sp["cls_tok"] = sp.pop("cls")
+        return cls.from_vocab(vocab, lower=lower, strip_accents=strip_accents, **sp)
 
     def _limit(self, max_len: int):
         if self._max_len != max_len:
@@ -173,28 +178,74 @@ class FastWordPieceTokenizer:
         return [e.ids for e in self._tok.encode_batch(list(texts))]
 
 
-def make_wordpiece_tokenizer(vocab_path: str, lower: bool = True, strip_accents=None):
+def make_wordpiece_tokenizer(vocab_path: str, lower: bool = True, strip_accents=None, special=None):
     """FastWordPieceTokenizer when the `tokenizers` library is importable (CRS_TOKENIZER=python forces the pure
-    Python restatement), else WordPieceTokenizer."""
+    Python restatement), else WordPieceTokenizer.  `special`: {"cls", "sep", "pad", "unk"} token strings (BERT's
+    by default)."""
     if os.environ.get("CRS_TOKENIZER", "") != "python":
         try:
-            return FastWordPieceTokenizer.from_vocab_file(vocab_path, lower=lower, strip_accents=strip_accents)
+            return FastWordPieceTokenizer.from_vocab_file(vocab_path, lower=lower, strip_accents=strip_accents, special=special)
         except ImportError:
             pass
-    return WordPieceTokenizer.from_vocab_file(vocab_path, lower=lower, strip_accents=strip_accents)
+    return WordPieceTokenizer.from_vocab_file(vocab_path, lower=lower, strip_accents=strip_accents, special=special)
+
+
+_BERT_SPECIAL = {"cls": "[CLS]", "sep": "[SEP]", "pad": "[PAD]", "unk": "[UNK]"}
+
+
+def special_tokens_from_model_dir(path: str) -> Dict[str, str]:
+    """{"cls", "sep", "pad", "unk"} -> token string, as the model directory names them: special_tokens_map.json
+    (cls_token / sep_token / pad_token / unk_token, plain strings or {"content": ...}), then what tokenizer.json
+    itself says (the post-processor's first and last special token, the WordPiece model's unk_token, the padding
+    block), then BERT's names.  MPNet directories give <s> </s> <pad> <unk>."""
+    import json
+    out: Dict[str, str] = {}
+    sm = os.path.join(path, "special_tokens_map.json")
+    if os.path.exists(sm):
+        with open(sm, encoding="utf-8") as fh:
+            m = json.load(fh)
+        for key in ("cls", "sep", "pad", "unk"):
+            v = m.get(key + "_token")
+            v = v.get("content") if isinstance(v, dict) else v
+            if isinstance(v, str):
+                out[key] = v
+    tj = os.path.join(path, "tokenizer.json")
+    if len(out) < 4 and os.path.exists(tj):
+        with open(tj, encoding="utf-8") as fh:
+            t = json.load(fh)
+        post = t.get("post_processor") or {}
+        if post.get("type") == "TemplateProcessing":
+            sp = [p["SpecialToken"]["id"] for p in post.get("single", []) if "SpecialToken" in p]
+            if len(sp) >= 2:
+                out.setdefault("cls", sp[0])
+                out.setdefault("sep", sp[-1])
+        elif isinstance(post.get("cls"), list) and isinstance(post.get("sep"), list):     # BertProcessing / RobertaProcessing
+            out.setdefault("cls", post["cls"][0])
+            out.setdefault("sep", post["sep"][0])
+        unk = (t.get("model") or {}).get("unk_token")
+        if isinstance(unk, str):
+            out.setdefault("unk", unk)
+        pad = (t.get("padding") or {}).get("pad_token")
+        if isinstance(pad, str):
+            out.setdefault("pad", pad)
+        elif "pad" not in out and out.get("cls", "[CLS]").startswith("<"):
+            out["pad"] = "<pad>"
+    return {**_BERT_SPECIAL, **out}
 
 
 def tokenizer_from_model_dir(path: str):
-    """The tokeniser a HuggingFace BERT checkpoint directory describes.  Casing comes from the TOKENIZER's own
+    """The tokeniser a HuggingFace BERT or MPNet checkpoint directory describes (WordPiece; the special tokens are the
+    directory's own: special_tokens_from_model_dir).  Casing comes from the TOKENIZER's own
     files, as in the reference stack (sentence-transformers hands the text to the HF tokenizer; the published
     all-MiniLM-L6-v2 ships sentence_bert_config.json do_lower_case=false next to an uncased vocab whose tokenizer
     lower-cases): tokenizer.json when the `tokenizers` library can load it, else vocab.txt with
     tokenizer_config.json's do_lower_case / strip_accents (absent -> lower-case, the uncased default)."""
     import json
     tj = os.path.join(path, "tokenizer.json")
+    special = special_tokens_from_model_dir(path)
     if os.path.exists(tj) and os.environ.get("CRS_TOKENIZER", "") != "python":
         try:
-            return FastWordPieceTokenizer.from_tokenizer_json(tj)
+            return FastWordPieceTokenizer.from_tokenizer_json(tj, special=special)
         except ImportError:
             pass
     lower, strip = True, None
@@ -204,16 +255,17 @@ def tokenizer_from_model_dir(path: str):
             cfg = json.load(fh)
         lower = bool(cfg.get("do_lower_case", True))
         strip = cfg.get("strip_accents", None)
-    return make_wordpiece_tokenizer(os.path.join(path, "vocab.txt"), lower=lower, strip_accents=strip)
+    return make_wordpiece_tokenizer(os.path.join(path, "vocab.txt"), lower=lower, strip_accents=strip, special=special)
 
 
 class HashTokenizer:
     """vocab-free stand-in: one id per basic token, crc32 into [1000, vocab)."""
 
-    def __init__(self, vocab_size: int):
+    def __init__(self, vocab_size: int, special=None):
+        """`special` = (cls, sep, pad) ids; default BERT's (101, 102, 0), or (1, 2, 0) in a toy vocabulary."""
         self.vocab_size = vocab_size
-        self.cls_id, self.sep_id, self.pad_id = (101, 102, 0) if vocab_size > 1000 else (1, 2, 0)
-        self.lo = 1000 if vocab_size > 2000 else 3
+        self.cls_id, self.sep_id, self.pad_id = special or ((101, 102, 0) if vocab_size > 1000 else (1, 2, 0))
+        self.lo = 1000 if vocab_size > 2000 else max(3, max(self.cls_id, self.sep_id, self.pad_id) + 1)
 
     def encode(self, text: str, max_len: int) -> List[int]:
         span = self.vocab_size - self.lo

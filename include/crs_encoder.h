@@ -90,6 +90,29 @@ int crs_encoder_forward_queries(const crs_encoder_desc* d, const crs_encoder_wei
                                 size_t workspace_bytes, float* out_dev, void* q16_out_dev, int slab_type,
                                 void* stream);
 
+/* Optional inputs of the _ex entry points (a NULL pointer to it, or a NULL rel_bias_dev, is exactly the forward above).
+ * rel_bias_dev: additive relative-position bias of the attention scores, shared by all layers and already resolved
+ * per offset -- fp32 [heads, 2 * rel_span - 1], entry (key - query) + rel_span - 1 is added to score(query, key) of that
+ * head before the softmax (MPNet: the bucketed relative_attention_bias; bucketing stays on the host).  rel_span >= seq
+ * and seq <= 512, else CRS_EINVAL.  Every layer then runs the relative-bias attention kernel (<= 21 KB of LDS, so also
+ * under CRS_ENC_SMALL_LDS); the fused QKV + attention kernel and the other attention forms are not selected.
+ * Models whose position ids start at an offset p (MPNet: 2) need no more than pos_emb + p * H and max_pos - p in the
+ * descriptor; models without token-type embeddings pass a zero row as type_emb. */
+typedef struct crs_encoder_ext {
+  const float* rel_bias_dev;
+  int32_t rel_span;
+} crs_encoder_ext;
+
+int crs_encoder_forward_ex(const crs_encoder_desc* d, const crs_encoder_weights* w, const int32_t* ids_dev,
+                           const int32_t* lens_dev, int batch, int seq, void* workspace_dev,
+                           size_t workspace_bytes, float* out_dev, int normalize, float* hidden_out_dev,
+                           void* stream, const crs_encoder_ext* ext);
+
+int crs_encoder_forward_queries_ex(const crs_encoder_desc* d, const crs_encoder_weights* w, const int32_t* ids_dev,
+                                   const int32_t* lens_dev, int batch, int seq, void* workspace_dev,
+                                   size_t workspace_bytes, float* out_dev, void* q16_out_dev, int slab_type,
+                                   void* stream, const crs_encoder_ext* ext);
+
 /* Building block exported for parity tests and for users with their own layer stack:
  *   C[M, N] = epilogue(A[M, K] (fp16) x W[N, K]^T (fp16) + bias[N])
  *   mode 0: fp16 out;  mode 1: erf-GELU, fp16 out;  mode 2: + residual fp32 [M, N], fp32 out. */
