@@ -71,4 +71,15 @@ int layernorm_launch(const float* y, int nsplit, const float* bias, const float*
 int pool_launch(const float* x32, const int* lens, int batch, int seq, int hidden, int pooling, int normalize,
                 float* out, _Float16* out16, int pdim16, hipStream_t stream);
 
+// enc_pair.hip: embed_ln_launch with a token-type row per token (type_ids int32 [tokens], clamped to [0, type_rows)); an all-zero
+// block gives the bits of embed_ln_launch
+int embed_ln_types_launch(const int* ids, const int* type_ids, const float* word, const float* pos, const float* type_tab,
+                          int type_rows, const float* g, const float* b, float eps, int tokens, int seq, int hidden, int vocab,
+                          float* x32, _Float16* x16, hipStream_t stream);
+// scores[b] = w_cls . tanh(w_pool hidden32[b, 0, :] + b_pool) + b_cls[0] (activation 1: then 1 / (1 + exp(-score))), all fp32;
+// pooled_out (may be null): the tanh vectors [batch, hidden].  -1: hidden not a multiple of 64 up to 1024
+int pair_head_launch(const float* hidden32, int batch, int seq, int hidden, const float* w_pool, const float* b_pool,
+                     const float* w_cls, const float* b_cls, int activation, float* scores, float* pooled_out,
+                     hipStream_t stream);
+
 }  // namespace crs

@@ -8,7 +8,8 @@
 //   ffn  = gelu(x16 Wup^T + b)                gemm mode 1      [T, F] fp16
 //   y32  = ffn Wdown^T + b + x32              gemm mode 2
 //   x    = LayerNorm(y32)
-// then pooling + L2 normalise.  The launch function allocates nothing and never synchronises, so
+// then pooling + L2 normalise -- or, for crs_encoder_score_pairs, the pair head (enc_pair.hip) on the [CLS] rows; its embedding
+// step takes a token-type row per token.  The launch function allocates nothing and never synchronises, so
 // a caller may capture it into a hipGraph for the launch-bound single-query case.
 #include "../../include/crs_encoder.h"
 #include "../../include/crs_hip.h"
@@ -96,6 +97,15 @@ int check_desc(const crs_encoder_desc* d) {
   return CRS_OK;
 }
 
+// what crs_encoder_score_pairs adds to the forward: per-token type ids at the embedding step (null: row 0, the kernels of the
+// plain forward) and the pair head in place of pooling
+struct PairTail {
+  const crs_encoder_head* head;
+  const int32_t* type_ids;
+  float* scores;
+  float* pooled_out;
+};
+
 #define CRS_TRY(expr, what)                                                             \
   do {                                                                                  \
     const int e_ = (expr);                                                              \
@@ -128,12 +138,13 @@ int crs_gemm_f16(const void* a_dev, const void* w_dev, const float* bias_dev, co
 static int encoder_forward(const crs_encoder_desc* d, const crs_encoder_weights* w, const int32_t* ids_dev,
                            const int32_t* lens_dev, int batch, int seq, void* workspace_dev,
                            size_t workspace_bytes, float* out_dev, int normalize, float* hidden_out_dev,
-                           _Float16* q16_out_dev, int q16_row_elems, void* stream, const crs_encoder_ext* ext) {
+                           _Float16* q16_out_dev, int q16_row_elems, void* stream, const crs_encoder_ext* ext,
+                           const PairTail* pair = nullptr) {
   const int rc = check_desc(d);
   if (rc) return rc;
   const float* rel_bias = ext ? ext->rel_bias_dev : nullptr;   // additive relative-position bias (crs_encoder_ext)
   const int rel_span = rel_bias ? ext->rel_span : 0;
-  if (!w || !w->layers || !ids_dev || !lens_dev || !workspace_dev || !out_dev) return crs::set_error(CRS_EINVAL, "null pointer");
+  if (!w || !w->layers || !ids_dev || !lens_dev || !workspace_dev || !(pair ? (void*)pair->scores : (void*)out_dev)) return crs::set_error(CRS_EINVAL, "null pointer");
   if (batch <= 0 || seq <= 0 || seq > d->max_pos) return crs::set_error(CRS_EINVAL, "bad batch/seq (seq <= max_pos)");
   if (rel_bias && (rel_span < seq || seq > 512)) {
     char m[160];
@@ -152,8 +163,12 @@ static int encoder_forward(const crs_encoder_desc* d, const crs_encoder_weights*
   _Float16* ffn = reinterpret_cast<_Float16*>(ws + l.ffn);
   const int T = batch * seq, H = d->hidden, F = d->ffn;
 
-  CRS_TRY(crs::embed_ln_launch(ids_dev, w->word_emb, w->pos_emb, w->type_emb, w->emb_ln_g, w->emb_ln_b, d->ln_eps, T,
-                               seq, H, d->vocab_size, x32, x16, st), "embed_ln");
+  if (pair && pair->type_ids)
+    CRS_TRY(crs::embed_ln_types_launch(ids_dev, pair->type_ids, w->word_emb, w->pos_emb, w->type_emb, pair->head->type_rows, w->emb_ln_g,
+                                       w->emb_ln_b, d->ln_eps, T, seq, H, d->vocab_size, x32, x16, st), "embed_ln (token types)");
+  else
+    CRS_TRY(crs::embed_ln_launch(ids_dev, w->word_emb, w->pos_emb, w->type_emb, w->emb_ln_g, w->emb_ln_b, d->ln_eps, T,
+                                 seq, H, d->vocab_size, x32, x16, st), "embed_ln");
   const bool panel_h = use_panel(T, H), panel_f = use_panel(T, F);
   // index-build side (large token counts), hidden = 384: projection + bias + residual + LayerNorm in one pipelined kernel
   const bool big_ln = T > kPanelMaxTokens && bigln_enabled();
@@ -211,8 +226,35 @@ static int encoder_forward(const crs_encoder_desc* d, const crs_encoder_weights*
     const hipError_t e = hipMemcpyAsync(hidden_out_dev, x32, (size_t)T * H * 4, hipMemcpyDeviceToDevice, st);
     if (e != hipSuccess) return crs::set_error(CRS_EHIP, hipGetErrorString(e));
   }
+  if (pair) {
+    const crs_encoder_head* hd = pair->head;
+    CRS_TRY(crs::pair_head_launch(x32, batch, seq, H, hd->w_pool, hd->b_pool, hd->w_cls, hd->b_cls, hd->activation, pair->scores,
+                                  pair->pooled_out, st), "pair head");
+    return CRS_OK;
+  }
   CRS_TRY(crs::pool_launch(x32, lens_dev, batch, seq, H, d->pooling, normalize, out_dev, q16_out_dev, q16_row_elems, st), "pool");
   return CRS_OK;
+}
+
+int crs_encoder_score_pairs(const crs_encoder_desc* d, const crs_encoder_weights* w, const crs_encoder_head* head,
+                            const int32_t* ids_dev, const int32_t* type_ids_dev, const int32_t* lens_dev, int batch, int seq,
+                            void* workspace_dev, size_t workspace_bytes, float* scores_dev, float* pooled_out_dev,
+                            float* hidden_out_dev, void* stream) {
+  const int rc = check_desc(d);
+  if (rc) return rc;
+  if (!head) return crs::set_error(CRS_EINVAL, "score_pairs: null head");
+  if (!head->w_pool || !head->b_pool || !head->w_cls || !head->b_cls) return crs::set_error(CRS_EINVAL, "score_pairs: null pointer in the head (w_pool, b_pool, w_cls, b_cls)");
+  if (head->type_rows < 1) return crs::set_error(CRS_EINVAL, "score_pairs: type_rows must be >= 1");
+  if (head->activation != 0 && head->activation != 1) return crs::set_error(CRS_EINVAL, "score_pairs: activation must be 0 (identity) or 1 (sigmoid)");
+  if (batch < 1) return crs::set_error(CRS_EINVAL, "score_pairs: batch must be >= 1");
+  if (seq < 1 || seq > d->max_pos) {
+    char m[160];
+    snprintf(m, sizeof m, "score_pairs: seq %d must be in [1, max_pos %d]", seq, d->max_pos);
+    return crs::set_error(CRS_EINVAL, m);
+  }
+  const PairTail pair{head, type_ids_dev, scores_dev, pooled_out_dev};
+  return encoder_forward(d, w, ids_dev, lens_dev, batch, seq, workspace_dev, workspace_bytes, nullptr, 0, hidden_out_dev, nullptr, 0,
+                         stream, nullptr, &pair);
 }
 
 int crs_encoder_forward_ex(const crs_encoder_desc* d, const crs_encoder_weights* w, const int32_t* ids_dev,

@@ -5,75 +5,14 @@
 // GEMM reads, so no separate cast pass exists.
 
 #include "enc.h"
+#include "enc_ln.h"
 
 namespace crs {
 namespace {
 
 constexpr int kMaxPerLane = 16;  // hidden <= 1024 (generic instantiation); hot shapes get exact counts
 
-__device__ __forceinline__ float wave_sum(float x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-  return x;
-}
-
-// v[] holds this lane's strided elements (index c = lane + 64*i); normalise and store
-template <int PL>
-__device__ __forceinline__ void ln_store(float (&v)[PL], int hidden, int lane, const float* g,
-                                         const float* b, float eps, float* x32, _Float16* x16) {
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < PL; ++i) s += (lane + 64 * i < hidden) ? v[i] : 0.f;
-  const float mean = wave_sum(s) / hidden;
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < PL; ++i) {
-    const float d = v[i] - mean;
-    q += (lane + 64 * i < hidden) ? d * d : 0.f;
-  }
-  const float rstd = 1.0f / sqrtf(wave_sum(q) / hidden + eps);
-#pragma unroll
-  for (int i = 0; i < PL; ++i) {
-    const int c = lane + 64 * i;
-    if (c < hidden) {
-      const float o = (v[i] - mean) * rstd * g[c] + b[c];
-      x32[c] = o;
-      x16[c] = (_Float16)o;
-    }
-  }
-}
-
-// ---- float2 forms (hidden a multiple of 128): a lane owns columns 128 i + 2 lane + {0, 1}.  These kernels are
-// bound by vector-memory ISSUE, not bytes -- a wave pays ~100 cycles per load/store instruction whatever its
-// width, and the 4-byte form needs 48 of them per token at four split-K partials -- so 8 bytes per lane
-// halves their time on the retrieve path (16 bytes would leave a third of the lanes without work at 384).
-template <int P2>
-__device__ __forceinline__ void ln_store2(float (&v)[P2][2], int hidden, int lane, const float* g, const float* b,
-                                          float eps, float* x32, _Float16* x16) {
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < P2; ++i) s += v[i][0] + v[i][1];
-  const float mean = wave_sum(s) / hidden;
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < P2; ++i) {
-    const float d0 = v[i][0] - mean, d1 = v[i][1] - mean;
-    q += d0 * d0 + d1 * d1;
-  }
-  const float rstd = 1.0f / sqrtf(wave_sum(q) / hidden + eps);
-#pragma unroll
-  for (int i = 0; i < P2; ++i) {
-    const int c = 128 * i + 2 * lane;
-    const float2 gg = *reinterpret_cast<const float2*>(g + c), bb = *reinterpret_cast<const float2*>(b + c);
-    float2 o;
-    o.x = (v[i][0] - mean) * rstd * gg.x + bb.x;
-    o.y = (v[i][1] - mean) * rstd * gg.y + bb.y;
-    *reinterpret_cast<float2*>(x32 + c) = o;
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    h2 h = {(_Float16)o.x, (_Float16)o.y};
-    *reinterpret_cast<h2*>(x16 + c) = h;
-  }
-}
+// wave_sum, ln_store<PL> (4-byte columns lane + 64 i) and ln_store2<P2> (8-byte column pairs 128 i + 2 lane): enc_ln.h
 
 template <int P2>
 __global__ __launch_bounds__(256) void embed_ln2_kernel(const int* __restrict__ ids, const float* __restrict__ word,

@@ -509,28 +509,42 @@ void rerank_lexical(const Tensor& scores, const Tensor& rows, const Tensor& doc_
 // desc = [vocab_size, hidden, layers, heads, ffn, max_pos, pooling, flags (CRS_ENC_*, optional)]; weights = [word_emb, pos_emb, type_emb, emb_ln_g, emb_ln_b]
 // followed by 12 tensors per layer in crs_encoder_layer order (w_qkv b_qkv w_o b_o ln1_g ln1_b w_up b_up w_down b_down ln2_g ln2_b).
 // encoder_forward_ex adds rel_bias (optional): fp32 [heads, 2 * span - 1], the additive relative-position bias of crs_encoder_ext.
+// desc + weights of a call as the C structs (the layer array lives in `layers`)
+struct EncArgs {
+  crs_encoder_desc d;
+  std::vector<crs_encoder_layer> layers;
+  crs_encoder_weights cw;
+};
+
+void enc_args(const Tensor& ids, at::TensorList weights, at::IntArrayRef desc, double ln_eps, EncArgs& a) {
+  TORCH_CHECK(desc.size() == 7 || desc.size() == 8, "desc = [vocab_size, hidden, layers, heads, ffn, max_pos, pooling(, flags)]");
+  a.d = crs_encoder_desc{(int32_t)desc[0], (int32_t)desc[1], (int32_t)desc[2], (int32_t)desc[3], (int32_t)desc[4], (int32_t)desc[5],
+                         (float)ln_eps, (int32_t)desc[6], desc.size() == 8 ? (int32_t)desc[7] : 0};
+  TORCH_CHECK((int64_t)weights.size() == 5 + 12 * (int64_t)a.d.layers, "weights must hold 5 + 12 * layers tensors");
+  for (const Tensor& t : weights) TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.device() == ids.device(), "weights must be contiguous tensors on the device of ids");
+  a.layers.resize((size_t)a.d.layers);
+  for (int l = 0; l < a.d.layers; ++l) {
+    const Tensor* w = &weights[5 + 12 * l];
+    a.layers[l] = crs_encoder_layer{w[0].data_ptr(), (const float*)w[1].data_ptr(), w[2].data_ptr(), (const float*)w[3].data_ptr(),
+                                    (const float*)w[4].data_ptr(), (const float*)w[5].data_ptr(), w[6].data_ptr(), (const float*)w[7].data_ptr(),
+                                    w[8].data_ptr(), (const float*)w[9].data_ptr(), (const float*)w[10].data_ptr(), (const float*)w[11].data_ptr()};
+  }
+  a.cw = crs_encoder_weights{(const float*)weights[0].data_ptr(), (const float*)weights[1].data_ptr(), (const float*)weights[2].data_ptr(),
+                             (const float*)weights[3].data_ptr(), (const float*)weights[4].data_ptr(), a.layers.data()};
+}
+
 void encoder_forward_ex(const Tensor& ids, const Tensor& lens, at::TensorList weights, at::IntArrayRef desc, double ln_eps, Tensor workspace,
                         Tensor out, c10::optional<Tensor> q16_out, int64_t slab_type, bool normalize, c10::optional<Tensor> hidden_out,
                         c10::optional<Tensor> rel_bias) {
   want(ids, at::kInt, "ids");
   want(lens, at::kInt, "lens");
   want(out, at::kFloat, "out");
-  TORCH_CHECK(desc.size() == 7 || desc.size() == 8, "desc = [vocab_size, hidden, layers, heads, ffn, max_pos, pooling(, flags)]");
-  crs_encoder_desc d{(int32_t)desc[0], (int32_t)desc[1], (int32_t)desc[2], (int32_t)desc[3], (int32_t)desc[4], (int32_t)desc[5],
-                     (float)ln_eps, (int32_t)desc[6], desc.size() == 8 ? (int32_t)desc[7] : 0};
-  TORCH_CHECK((int64_t)weights.size() == 5 + 12 * (int64_t)d.layers, "weights must hold 5 + 12 * layers tensors");
+  EncArgs ea;
+  enc_args(ids, weights, desc, ln_eps, ea);
+  const crs_encoder_desc& d = ea.d;
+  const crs_encoder_weights& cw = ea.cw;
   TORCH_CHECK(ids.dim() == 2 && lens.numel() == ids.size(0) && out.numel() == ids.size(0) * d.hidden, "ids [B, S], lens [B], out [B, H]");
-  for (const Tensor& t : weights) TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.device() == ids.device(), "weights must be contiguous tensors on the device of ids");
   same_device(ids, {&lens, &workspace, &out, opt_t(q16_out), opt_t(hidden_out)}, "crs::encoder_forward");
-  std::vector<crs_encoder_layer> layers((size_t)d.layers);
-  for (int l = 0; l < d.layers; ++l) {
-    const Tensor* w = &weights[5 + 12 * l];
-    layers[l] = crs_encoder_layer{w[0].data_ptr(), (const float*)w[1].data_ptr(), w[2].data_ptr(), (const float*)w[3].data_ptr(),
-                                  (const float*)w[4].data_ptr(), (const float*)w[5].data_ptr(), w[6].data_ptr(), (const float*)w[7].data_ptr(),
-                                  w[8].data_ptr(), (const float*)w[9].data_ptr(), (const float*)w[10].data_ptr(), (const float*)w[11].data_ptr()};
-  }
-  crs_encoder_weights cw{(const float*)weights[0].data_ptr(), (const float*)weights[1].data_ptr(), (const float*)weights[2].data_ptr(),
-                         (const float*)weights[3].data_ptr(), (const float*)weights[4].data_ptr(), layers.data()};
   const int b = (int)ids.size(0), s = (int)ids.size(1);
   crs_encoder_ext ext{nullptr, 0};
   if (rel_bias.has_value() && rel_bias->defined()) {
@@ -563,6 +577,52 @@ void encoder_forward_ex(const Tensor& ids, const Tensor& lens, at::TensorList we
 void encoder_forward(const Tensor& ids, const Tensor& lens, at::TensorList weights, at::IntArrayRef desc, double ln_eps, Tensor workspace,
                      Tensor out, c10::optional<Tensor> q16_out, int64_t slab_type, bool normalize, c10::optional<Tensor> hidden_out) {
   encoder_forward_ex(ids, lens, weights, desc, ln_eps, workspace, out, q16_out, slab_type, normalize, hidden_out, c10::nullopt);
+}
+
+// Sentence-pair scores (crs_encoder_score_pairs): weights / desc as encoder_forward; head = [w_pool [H, H], b_pool [H], w_cls [H] (or
+// [1, H]), b_cls [1]], all fp32; type_ids (optional) int32 [B, S]; activation 0 logit, 1 sigmoid.  type_rows is weights[2]'s row count.
+void encoder_score_pairs(const Tensor& ids, c10::optional<Tensor> type_ids, const Tensor& lens, at::TensorList weights, at::TensorList head,
+                         at::IntArrayRef desc, double ln_eps, int64_t activation, Tensor workspace, Tensor scores,
+                         c10::optional<Tensor> pooled_out, c10::optional<Tensor> hidden_out) {
+  want(ids, at::kInt, "ids");
+  want(lens, at::kInt, "lens");
+  want(scores, at::kFloat, "scores");
+  EncArgs ea;
+  enc_args(ids, weights, desc, ln_eps, ea);
+  const int64_t H = ea.d.hidden;
+  TORCH_CHECK(ids.dim() == 2 && lens.numel() == ids.size(0) && scores.numel() == ids.size(0), "ids [B, S], lens [B], scores [B]");
+  same_device(ids, {&lens, &workspace, &scores, opt_t(type_ids), opt_t(pooled_out), opt_t(hidden_out)}, "crs::encoder_score_pairs");
+  TORCH_CHECK(head.size() == 4, "head = [w_pool, b_pool, w_cls, b_cls]");
+  for (const Tensor& t : head) {
+    want(t, at::kFloat, "head tensor");
+    same_device(ids, {&t}, "crs::encoder_score_pairs");
+  }
+  TORCH_CHECK(head[0].numel() == H * H && head[1].numel() == H && head[2].numel() == H && head[3].numel() == 1,
+              "head must be w_pool [H, H], b_pool [H], w_cls [H], b_cls [1] (one label)");
+  TORCH_CHECK(weights[2].dim() == 2 && weights[2].size(1) == H, "weights[2] (token types) must be [rows, H]");
+  const int b = (int)ids.size(0), s = (int)ids.size(1);
+  const int32_t* types = nullptr;
+  if (has(type_ids)) {
+    want(*type_ids, at::kInt, "type_ids");
+    TORCH_CHECK(type_ids->numel() == ids.numel(), "type_ids must be [B, S]");
+    types = type_ids->data_ptr<int32_t>();
+  }
+  float *pooled = nullptr, *hid = nullptr;
+  if (has(pooled_out)) {
+    want(*pooled_out, at::kFloat, "pooled_out");
+    TORCH_CHECK(pooled_out->numel() == (int64_t)b * H, "pooled_out must be [B, H]");
+    pooled = pooled_out->data_ptr<float>();
+  }
+  if (has(hidden_out)) {
+    want(*hidden_out, at::kFloat, "hidden_out");
+    TORCH_CHECK(hidden_out->numel() == (int64_t)b * s * H, "hidden_out must be [B, S, H]");
+    hid = hidden_out->data_ptr<float>();
+  }
+  const crs_encoder_head hd{head[0].data_ptr<float>(), head[1].data_ptr<float>(), head[2].data_ptr<float>(), head[3].data_ptr<float>(),
+                            (int32_t)weights[2].size(0), (int32_t)activation};
+  c10::hip::HIPGuardMasqueradingAsCUDA g(ids.device());
+  ok(crs_encoder_score_pairs(&ea.d, &ea.cw, &hd, ids.data_ptr<int32_t>(), types, lens.data_ptr<int32_t>(), b, s, workspace.data_ptr(),
+                             (size_t)workspace.nbytes(), scores.data_ptr<float>(), pooled, hid, cur_stream(ids)), "crs::encoder_score_pairs");
 }
 
 }  // namespace
@@ -605,6 +665,8 @@ TORCH_LIBRARY(crs, m) {
         "Tensor(c!)? q16_out, int slab_type, bool normalize, Tensor(d!)? hidden_out) -> ()");
   m.def("encoder_forward_ex(Tensor ids, Tensor lens, Tensor[] weights, int[] desc, float ln_eps, Tensor(a!) workspace, Tensor(b!) out, "
         "Tensor(c!)? q16_out, int slab_type, bool normalize, Tensor(d!)? hidden_out, Tensor? rel_bias=None) -> ()");
+  m.def("encoder_score_pairs(Tensor ids, Tensor? type_ids, Tensor lens, Tensor[] weights, Tensor[] head, int[] desc, float ln_eps, "
+        "int activation, Tensor(a!) workspace, Tensor(b!) scores, Tensor(c!)? pooled_out, Tensor(d!)? hidden_out) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(crs, CUDA, m) {   // the HIP backend of torch-ROCm dispatches under the "CUDA" key
@@ -631,4 +693,5 @@ TORCH_LIBRARY_IMPL(crs, CUDA, m) {   // the HIP backend of torch-ROCm dispatches
   m.impl("rerank_lexical", &rerank_lexical);
   m.impl("encoder_forward", &encoder_forward);
   m.impl("encoder_forward_ex", &encoder_forward_ex);
+  m.impl("encoder_score_pairs", &encoder_score_pairs);
 }

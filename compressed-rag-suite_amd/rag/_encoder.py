@@ -2,7 +2,8 @@
 
 ``HipEncoder`` owns the device copies of a BERT-family checkpoint (HuggingFace BertModel state-dict
 names, fp32 numpy in; matrices are cast to fp16 and Q/K/V stacked on upload) and runs the forward
-through ``crs_encoder_forward_ex``.  MPNet checkpoints come in under the same names plus
+through ``crs_encoder_forward_ex``.  A weights dict that also carries ``pooler.dense.*`` and ``classifier.*`` (one label: a
+BertForSequenceClassification cross-encoder) gets its head uploaded too, and ``score_pairs`` runs ``crs_encoder_score_pairs``.  MPNet checkpoints come in under the same names plus
 ``encoder.relative_attention_bias.weight`` (rag/embedding.py maps them), with ``ModelShape.rel_buckets``
 and ``pos_offset`` set: the bias is resolved per offset on the host and handed to the library.  Token ids in, pooled sentence embeddings out; no CPU fallback.
 """
@@ -40,6 +41,15 @@ class EncoderExt(Structure):      # crs_encoder_ext
     _fields_ = [("rel_bias_dev", c_void_p), ("rel_span", c_int32)]
 
 
+class EncoderHead(Structure):     # crs_encoder_head
+    _fields_ = [("w_pool", c_void_p), ("b_pool", c_void_p), ("w_cls", c_void_p), ("b_cls", c_void_p),
+                ("type_rows", c_int32), ("activation", c_int32)]
+
+
+HEAD_NAMES = ("pooler.dense.weight", "pooler.dense.bias", "classifier.weight", "classifier.bias")
+ACTIVATIONS = {"identity": 0, "sigmoid": 1}
+
+
 nat.register_signatures({
     "crs_encoder_workspace_bytes": (c_int, [POINTER(EncoderDesc), c_int, c_int, POINTER(c_size_t)]),
     "crs_encoder_forward": (c_int, [POINTER(EncoderDesc), POINTER(EncoderWeights), c_void_p, c_void_p, c_int,
@@ -51,6 +61,8 @@ nat.register_signatures({
     "crs_encoder_forward_queries_ex": (c_int, [POINTER(EncoderDesc), POINTER(EncoderWeights), c_void_p, c_void_p, c_int,
                                                c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_void_p,
                                                POINTER(EncoderExt)]),
+    "crs_encoder_score_pairs": (c_int, [POINTER(EncoderDesc), POINTER(EncoderWeights), POINTER(EncoderHead), c_void_p, c_void_p,
+                                        c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     "crs_gemm_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                              c_void_p]),
 })
@@ -177,6 +189,19 @@ class HipEncoder:
             if table.shape[0] != shape.heads:
                 raise ValueError("relative_attention_bias.weight must have one column per head")
             self.rel_bias = torch.from_numpy(table).to(self.device)
+        # pair-classifier head (cross-encoders): [w_pool [H, H], b_pool [H], w_cls [H], b_cls [1]], fp32 as stored
+        self.head = None
+        if all(n in weights for n in HEAD_NAMES):
+            if shape.rel_buckets > 0:
+                raise ValueError("a pair head needs token types: MPNet shapes have none")
+            h = shape.hidden
+            want = {HEAD_NAMES[0]: (h, h), HEAD_NAMES[1]: (h,), HEAD_NAMES[2]: (1, h), HEAD_NAMES[3]: (1,)}
+            for name, shp in want.items():
+                if tuple(np.shape(weights[name])) != shp:
+                    raise ValueError(f"{name} must be {shp} (one label), got {tuple(np.shape(weights[name]))}")
+            self.head = [torch.from_numpy(np.ascontiguousarray(weights[n], dtype=np.float32).reshape(-1 if i else (h, h))).to(self.device)
+                         for i, n in enumerate(HEAD_NAMES)]
+            self.type_rows = int(np.shape(weights["embeddings.token_type_embeddings.weight"])[0])
 
     @property
     def _desc_list(self):
@@ -227,3 +252,46 @@ class HipEncoder:
             nat.ops().encoder_forward_ex(ids, lens, self._wlist, desc, float(self.desc.ln_eps), ws, out, q16_out,
                                          int(slab_type), bool(normalize), hidden, self.rel_bias)
         return (out, hidden) if return_hidden else out
+
+    def score_pairs(self, ids, type_ids, lens, activation="identity", return_pooled: bool = False, return_hidden: bool = False,
+                    workspace=None, small_lds: bool = False):
+        """Relevance scores of sentence pairs.  ids: int32 [B, S] rows "[CLS] a [SEP] b [SEP]" (numpy or cuda tensor, right
+        padded); type_ids: int32 [B, S] segment ids (0 / 1; padding 0) or None for all 0; lens: int32 [B].  activation:
+        'identity' (the logit) or 'sigmoid'.  Returns cuda fp32 [B]; with return_pooled / return_hidden a tuple that also
+        holds the pooler output [B, H] and / or the final hidden states [B, S, H], in that order."""
+        import torch
+        if self.head is None:
+            raise ValueError("this encoder has no pair head: its weights carry no pooler.dense.* / classifier.* (one label)")
+        if activation not in ACTIVATIONS and activation not in (0, 1):
+            raise ValueError(f"activation must be 'identity' or 'sigmoid', got {activation!r}")
+
+        def dev_i32(a):
+            if not isinstance(a, torch.Tensor):
+                a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32))
+            return a.to(device=self.device, dtype=torch.int32).contiguous()
+
+        ids, lens = dev_i32(ids), dev_i32(lens)
+        if type_ids is not None:
+            type_ids = dev_i32(type_ids)
+            if type_ids.shape != ids.shape:
+                raise ValueError("type_ids must have the shape of ids")
+        b, s = ids.shape
+        need = self.workspace_bytes(b, s)
+        ws = workspace
+        if ws is None:
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            ws = self._ws
+        elif ws.numel() < need:
+            raise ValueError(f"encoder workspace too small: {ws.numel()} < {need}")
+        scores = torch.empty((b,), dtype=torch.float32, device=self.device)
+        pooled = torch.empty((b, self.shape.hidden), dtype=torch.float32, device=self.device) if return_pooled else None
+        hidden = torch.empty((b, s, self.shape.hidden), dtype=torch.float32, device=self.device) if return_hidden else None
+        desc = self._desc_list
+        if small_lds:
+            desc = desc[:7] + [desc[7] | ENC_SMALL_LDS]
+        with nat._translate():
+            nat.ops().encoder_score_pairs(ids, type_ids, lens, self._wlist, self.head, desc, float(self.desc.ln_eps),
+                                          int(ACTIVATIONS.get(activation, activation)), ws, scores, pooled, hidden)
+        extra = tuple(t for t in (pooled, hidden) if t is not None)
+        return (scores,) + extra if extra else scores

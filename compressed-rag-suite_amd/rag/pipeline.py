@@ -153,4 +153,6 @@ class RAGPipeline:
             stats['retrieval'] = {'top_k': r.top_k, 'similarity_threshold': r.similarity_threshold,
                                   'rerank': r.rerank, 'diversity_penalty': r.diversity_penalty,
                                   'distance_metric': r.distance_metric}
+            if getattr(r, 'cross_encoder', None) is not None:     # retrieval.rerank_model (additive): the cross-encoder in use
+                stats['retrieval']['rerank_model'] = r.cross_encoder.model_name
         return stats

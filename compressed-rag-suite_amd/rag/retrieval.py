@@ -10,7 +10,10 @@ lists of all its queries with one kernel launch over the store's fp32 rows (csrc
 of the Python loop -- same rule, cosines in fp32 on the device.  Opt-in, ``lexical_rerank: 'device'``:
 ``retrieve_batch`` scores, thresholds and lexically re-ranks the lists of each device batch with one
 kernel launch (csrc/rerank.hip, VectorStore.rerank_lexical) and builds only the surviving dicts --
-the host rule in fp64, bit for bit.
+the host rule in fp64, bit for bit.  Opt-in, ``rerank_model`` (a rag/reranking.py config dict, or a model name): with ``rerank``
+on, a BERT cross-encoder scores every (query, chunk text) pair that passed the threshold -- ``rerank_score`` is its score, the list
+is sorted on it (stable, descending) and cut to ``top_k``; the search, the ``2 * top_k`` fetch, the threshold and the MMR step
+(on ``score``) are as without it.
 
 Additive: ``retrieve_batch`` embeds and searches many queries in one launch each and then applies
 the identical per-query post-processing; ``reuse_index_embeddings`` is NOT offered because the
@@ -59,6 +62,14 @@ class ContextRetriever:
         if self.lexical_rerank not in ('host', 'device'):
             raise ValueError(f"lexical_rerank must be 'host' or 'device', got {self.lexical_rerank!r}")
         self.last_rerank = {'mode': 'host', 'lists': 0}   # which path scored and re-ranked the lists of the last retrieve_batch call
+        # additive: a cross-encoder in place of the token-overlap rule (rag/reranking.py; a config dict, or a string used as its
+        # model_name).  Resolved here, so an unknown model fails at construction; used only while `rerank` is on.  Every non-empty
+        # list that passed the threshold is scored (also one that needs no cut: its order and rerank_score are the model's), all
+        # pairs of a retrieve_batch piece in one predict call; lexical_rerank: 'device' is then not taken
+        self.cross_encoder = None
+        if config.get('rerank_model'):
+            from rag.reranking import CrossEncoderReranker
+            self.cross_encoder = CrossEncoderReranker(config['rerank_model'])
         self._token_sets: Dict[str, frozenset] = {}       # _rerank: text -> its lower-cased token set
         self._engine, self._engine_key = None, None
         self.distance_metric = self._get_distance_metric()
@@ -109,7 +120,10 @@ class ContextRetriever:
         if not chunks:
             logger.warning(f"No chunks passed similarity threshold of {self.similarity_threshold}")
             return []
-        if self.rerank and len(chunks) > k:
+        if self.rerank and self.cross_encoder is not None:
+            chunks = self._rerank_cross([query], [chunks], k)[0]
+            self.last_rerank = {'mode': 'cross-encoder', 'lists': 1}
+        elif self.rerank and len(chunks) > k:
             chunks = self._rerank(query, chunks, k)
         else:
             chunks = chunks[:k]
@@ -225,10 +239,12 @@ class ContextRetriever:
         row_of: Dict[int, int] = {}           # id(chunk dict) -> sidecar row (our store only)
         ids_l, docs_l, metas_l = getattr(col, 'ids', None), getattr(col, 'documents', None), getattr(col, 'metadatas', None)
         queries = list(queries)
+        cross = self.cross_encoder if self.rerank else None
         on_device = (self.lexical_rerank == 'device' and bool(self.rerank) and self.distance_metric == 'cosine' and fetch <= 64
-                     and ids_l is not None and hasattr(store, 'rerank_lexical'))
+                     and ids_l is not None and hasattr(store, 'rerank_lexical') and cross is None)
         host_pieces = 0
         for piece in self._search_many(queries, fetch):      # one device batch at a time: its dicts are built while the next ones run
+            piece_start = len(per_query)
             if on_device and not isinstance(piece, dict):
                 built = self._rerank_on_device(queries[len(per_query):len(per_query) + len(piece)], piece, k, row_of)
                 if built is not None:
@@ -269,12 +285,13 @@ class ContextRetriever:
                     logger.warning(f"No chunks passed similarity threshold of {self.similarity_threshold}")
                     per_query.append([])
                     continue
-                if self.rerank and len(chunks) > k:
-                    chunks = self._rerank(query, chunks, k)
-                else:
-                    chunks = chunks[:k]
+                if cross is None:                         # (the cross-encoder takes the whole piece at once, below)
+                    chunks = self._rerank(query, chunks, k) if self.rerank and len(chunks) > k else chunks[:k]
                 per_query.append(chunks)
-        self.last_rerank = {'mode': 'device' if on_device and not host_pieces else 'host', 'lists': len(per_query) if self.rerank else 0}
+            if cross is not None:
+                per_query[piece_start:] = self._rerank_cross(queries[piece_start:len(per_query)], per_query[piece_start:], k)
+        self.last_rerank = {'mode': 'cross-encoder' if cross is not None else 'device' if on_device and not host_pieces else 'host',
+                            'lists': len(per_query) if self.rerank else 0}
         self.last_mmr = {'mode': 'host', 'lists': sum(1 for chunks in per_query if len(chunks) > 1) if self.diversity_penalty > 0 else 0}
         if self.diversity_penalty > 0 and self.mmr_vectors == 'device' and ids_l is not None and self._mmr_on_device(per_query, row_of):
             return per_query
@@ -398,6 +415,21 @@ class ContextRetriever:
             chunk['rerank_score'] = chunk['score'] * 0.7 + (hits / norm) * 0.3
         chunks.sort(key=lambda c: c.get('rerank_score', c['score']), reverse=True)
         return chunks[:top_k]
+
+    def _rerank_cross(self, queries: List[str], lists: List[List[Dict]], top_k: int) -> List[List[Dict]]:
+        """The cross-encoder in place of _rerank, for the chunk lists of several queries at once: ONE predict call over every
+        (query, chunk text) pair, rerank_score = the model's score, each list sorted on it (stable, descending) and cut."""
+        pairs = [(q, c['text']) for q, chunks in zip(queries, lists) for c in chunks]
+        if not pairs:
+            return [chunks[:top_k] for chunks in lists]
+        scores = self.cross_encoder.predict(pairs).tolist()
+        out, at = [], 0
+        for chunks in lists:
+            for c in chunks:
+                c['rerank_score'] = scores[at]
+                at += 1
+            out.append(sorted(chunks, key=lambda c: c['rerank_score'], reverse=True)[:top_k])
+        return out
 
     def _apply_diversity(self, chunks: List[Dict], vectors=None) -> List[Dict]:
         """Greedy maximal-marginal-relevance re-ordering over re-embedded chunk texts:

@@ -75,7 +75,50 @@ def basic_tokenize(text: str, lower: bool = True, strip_accents=None) -> List[st
     return words
 
 
-class WordPieceTokenizer:
+def pair_lengths(n_a: int, n_b: int, budget: int) -> Tuple[int, int]:
+    """Tokens each side of a pair keeps under transformers' truncation='longest_first' when `budget` tokens may remain in all
+    (max_seq minus the three special tokens), as the `tokenizers` backend of transformers computes it: nothing is cut when the
+    pair fits; else the shorter side is kept whole and the longer one cut to the rest, unless the shorter side is itself longer
+    than the other's share -- then both are cut to budget // 2, and when the budget is odd the extra token goes to the side that
+    was LONGER.  Tie rule: sides of equal length give the extra token to the SECOND text.  (Dropping one
+    token at a time from the longer side, as the pure-Python tokenizers of older transformers did, ends within one token of
+    this; the closed form is what the installed library computes, and tests/test_crossenc_cpu.py pins it against that.)"""
+    if n_a + n_b <= budget:
+        return n_a, n_b
+    swap = n_a > n_b
+    n1, n2 = (n_b, n_a) if swap else (n_a, n_b)            # n1 <= n2
+    n2 = n1 if n1 > budget else max(n1, budget - n1)
+    if n1 + n2 > budget:
+        n1 = budget // 2
+        n2 = n1 + budget % 2
+    return (n2, n1) if swap else (n1, n2)
+
+
+def join_pair(a_ids: Sequence[int], b_ids: Sequence[int], cls_id: int, sep_id: int, max_seq: int,
+              n_a: int = None, n_b: int = None) -> Tuple[List[int], List[int]]:
+    """[CLS] a [SEP] b [SEP] with token types 0 0 .. 0 1 .. 1 from the two sides' ids WITHOUT special tokens, cut by
+    pair_lengths to max_seq tokens in all.  n_a / n_b: the sides' full token counts when a_ids / b_ids are already cut (to no
+    fewer than max_seq - 3 tokens) -- the rule looks at the full lengths."""
+    if max_seq < 5:
+        raise ValueError("a pair needs max_seq >= 5: three special tokens and room for a token of each side")
+    k_a, k_b = pair_lengths(len(a_ids) if n_a is None else n_a, len(b_ids) if n_b is None else n_b, max_seq - 3)
+    a, b = list(a_ids[:k_a]), list(b_ids[:k_b])
+    return [cls_id] + a + [sep_id] + b + [sep_id], [0] * (len(a) + 2) + [1] * (len(b) + 1)
+
+
+class _PairMixin:
+    """encode_pair for any tokenizer with encode(text, max_len) -> [cls] ids [sep] and cls_id / sep_id."""
+
+    def encode_body(self, text: str) -> List[int]:
+        """All token ids of `text`, no special tokens, no truncation."""
+        return self.encode(text, 1 << 30)[1:-1]
+
+    def encode_pair(self, a: str, b: str, max_seq: int) -> Tuple[List[int], List[int]]:
+        """(ids, type_ids) of [CLS] a [SEP] b [SEP], truncated to max_seq by the 'longest_first' rule (pair_lengths)."""
+        return join_pair(self.encode_body(a), self.encode_body(b), self.cls_id, self.sep_id, max_seq)
+
+
+class WordPieceTokenizer(_PairMixin):
     def __init__(self, vocab: Dict[str, int], lower: bool = True, unk="[UNK]", cls="[CLS]", sep="[SEP]", pad="[PAD]",
                  strip_accents=None):
         self.vocab, self.lower, self.strip_accents = vocab, lower, strip_accents
@@ -115,7 +158,7 @@ class WordPieceTokenizer:
         return [self.cls_id] + ids[: max_len - 2] + [self.sep_id]
 
 
-class FastWordPieceTokenizer:
+class FastWordPieceTokenizer(_PairMixin):
     """The same tokenisation through the `tokenizers` library (the reference's own backend: requirements.txt:148,
     via sentence-transformers) when it is importable: BertNormalizer + BertPreTokenizer + WordPiece, or the model
     directory's tokenizer.json as shipped.  Two orders of magnitude faster than the restatement above, which
@@ -258,7 +301,7 @@ def tokenizer_from_model_dir(path: str):
     return make_wordpiece_tokenizer(os.path.join(path, "vocab.txt"), lower=lower, strip_accents=strip, special=special)
 
 
-class HashTokenizer:
+class HashTokenizer(_PairMixin):
     """vocab-free stand-in: one id per basic token, crc32 into [1000, vocab)."""
 
     def __init__(self, vocab_size: int, special=None):

@@ -65,7 +65,7 @@ typedef struct crs_encoder_layer {
 typedef struct crs_encoder_weights {
   const float* word_emb;  /* fp32 [vocab, H] */
   const float* pos_emb;   /* fp32 [max_pos, H] */
-  const float* type_emb;  /* fp32 [>=1, H]; row 0 is added to every token */
+  const float* type_emb;  /* fp32 [>=1, H]; row 0 is added to every token (crs_encoder_score_pairs: the row its type ids name) */
   const float* emb_ln_g;
   const float* emb_ln_b;
   const crs_encoder_layer* layers;  /* HOST array of `layers` entries holding device pointers */
@@ -112,6 +112,31 @@ int crs_encoder_forward_queries_ex(const crs_encoder_desc* d, const crs_encoder_
                                    const int32_t* lens_dev, int batch, int seq, void* workspace_dev,
                                    size_t workspace_bytes, float* out_dev, void* q16_out_dev, int slab_type,
                                    void* stream, const crs_encoder_ext* ext);
+
+/* Sentence-pair scoring (cross-encoder re-ranking): BertForSequenceClassification with one label.  The rows of ids_dev hold
+ * "[CLS] a [SEP] b [SEP]" (tokenised and truncated on the host), type_ids_dev int32 [batch, seq] names the token-type row of every
+ * token (0 for "[CLS] a [SEP]", 1 for "b [SEP]", anything for padding; values outside [0, type_rows) are clamped, as token ids
+ * are); NULL means all 0 and launches exactly the kernels of crs_encoder_forward.  The layer stack is that of
+ * crs_encoder_forward (the descriptor's pooling field is not used; CRS_ENC_SMALL_LDS is honoured); then, per pair and in fp32,
+ *   pooled = tanh(w_pool h + b_pool)      h: final hidden state of token 0; w_pool fp32 [H, H] row-major (out, in), b_pool [H]
+ *   score  = w_cls . pooled + b_cls[0]    w_cls fp32 [H]; activation 1: score = 1 / (1 + exp(-score))
+ * scores_dev fp32 [batch].  pooled_out_dev (may be NULL): fp32 [batch, H]; hidden_out_dev (may be NULL): fp32 [batch, seq, H],
+ * both for parity tests.  The workspace is the one crs_encoder_workspace_bytes(d, batch, seq) sizes: the head keeps its operands
+ * in LDS and needs no device scratch.  A pair's score does not depend on which other pairs share the call's head launch.
+ * CRS_EINVAL, with a message and before any launch: a NULL head or a NULL pointer inside it, type_rows < 1, activation outside
+ * {0, 1}, batch < 1, seq > max_pos. */
+typedef struct crs_encoder_head {
+  const float* w_pool; const float* b_pool;   /* bert.pooler.dense */
+  const float* w_cls;  const float* b_cls;    /* classifier, num_labels == 1 */
+  int32_t type_rows;                          /* rows of weights->type_emb */
+  int32_t activation;                         /* 0 identity (logit), 1 sigmoid */
+} crs_encoder_head;
+
+int crs_encoder_score_pairs(const crs_encoder_desc* d, const crs_encoder_weights* w, const crs_encoder_head* head,
+                            const int32_t* ids_dev, const int32_t* type_ids_dev /* may be NULL = all 0 */,
+                            const int32_t* lens_dev, int batch, int seq, void* workspace_dev, size_t workspace_bytes,
+                            float* scores_dev, float* pooled_out_dev /* may be NULL */, float* hidden_out_dev /* may be NULL */,
+                            void* stream);
 
 /* Building block exported for parity tests and for users with their own layer stack:
  *   C[M, N] = epilogue(A[M, K] (fp16) x W[N, K]^T (fp16) + bias[N])
