@@ -52,18 +52,17 @@ int gemm_rowln2_launch(const _Float16* a, const _Float16* w, const float* bias, 
 
 // enc_attn.hip: ctx[T, H] = softmax(QK^T / sqrt(hd) + padding mask) V per (batch, head);
 // qkv is [T, 3H] fp16 (Q | K | V column blocks), lens[b] real tokens per row (right padding).
-int attention_launch(const _Float16* qkv, const int* lens, _Float16* ctx, int batch, int seq, int hidden,
-                     int heads, hipStream_t stream);
-
-// enc_attn_relbias.hip: the same with bias[h][key - query] added to every score before the softmax.  rel_bias is fp32
-// [heads, 2 span - 1], entry (key - query) + span - 1; span >= seq, seq <= 512 (-1 otherwise).  <= 21 KB of LDS.
-int attention_relbias_launch(const _Float16* qkv, const int* lens, const float* rel_bias, int span, _Float16* ctx, int batch,
-                             int seq, int hidden, int heads, hipStream_t stream);
+// rel_bias (may be null): bias[h][key - query] added to every score before the softmax, fp32 [heads, 2 span - 1], entry
+// (key - query) + span - 1; span >= seq, seq <= 512 (-1 otherwise).  <= 21 KB of LDS.
+int attention_launch(const _Float16* qkv, const int* lens, _Float16* ctx, int batch, int seq, int hidden, int heads,
+                     const float* rel_bias, int span, hipStream_t stream);
 
 // enc_misc.hip
-int embed_ln_launch(const int* ids, const float* word, const float* pos, const float* type0, const float* g,
-                    const float* b, float eps, int tokens, int seq, int hidden, int vocab, float* x32,
-                    _Float16* x16, hipStream_t stream);
+// type_ids (may be null: row 0 of type_tab for every token): int32 [tokens], clamped to [0, type_rows); an all-zero block
+// gives the bits of the null form
+int embed_ln_launch(const int* ids, const int* type_ids, const float* word, const float* pos, const float* type_tab,
+                    int type_rows, const float* g, const float* b, float eps, int tokens, int seq, int hidden, int vocab,
+                    float* x32, _Float16* x16, hipStream_t stream);
 // LayerNorm( sum_{s<nsplit} y[s] + bias + residual ): bias / residual may be null (already folded in)
 int layernorm_launch(const float* y, int nsplit, const float* bias, const float* residual, const float* g,
                      const float* b, float eps, int tokens, int hidden, float* x32, _Float16* x16,
@@ -71,11 +70,7 @@ int layernorm_launch(const float* y, int nsplit, const float* bias, const float*
 int pool_launch(const float* x32, const int* lens, int batch, int seq, int hidden, int pooling, int normalize,
                 float* out, _Float16* out16, int pdim16, hipStream_t stream);
 
-// enc_pair.hip: embed_ln_launch with a token-type row per token (type_ids int32 [tokens], clamped to [0, type_rows)); an all-zero
-// block gives the bits of embed_ln_launch
-int embed_ln_types_launch(const int* ids, const int* type_ids, const float* word, const float* pos, const float* type_tab,
-                          int type_rows, const float* g, const float* b, float eps, int tokens, int seq, int hidden, int vocab,
-                          float* x32, _Float16* x16, hipStream_t stream);
+// enc_pair.hip
 // scores[b] = w_cls . tanh(w_pool hidden32[b, 0, :] + b_pool) + b_cls[0] (activation 1: then 1 / (1 + exp(-score))), all fp32;
 // pooled_out (may be null): the tanh vectors [batch, hidden].  -1: hidden not a multiple of 64 up to 1024
 int pair_head_launch(const float* hidden32, int batch, int seq, int hidden, const float* w_pool, const float* b_pool,

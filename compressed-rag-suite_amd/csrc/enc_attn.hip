@@ -17,6 +17,8 @@
 
 #include <stdlib.h>
 
+#include <type_traits>
+
 namespace crs {
 namespace {
 
@@ -27,15 +29,26 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kThreads = 256;
 constexpr int KB = 64;   // keys per block
 constexpr int QB = 64;   // query rows per workgroup
+constexpr int kMaxSeq = 512;    // relative bias: the staged table holds 2 * 512 - 1 offsets
+constexpr float kLog2e = 1.44269504088896341f;
 
-// One online-softmax step for this lane's query over the 16 scores it holds of a 64-key block (raw Q.K products in s).
-// Works in the base-2 domain with the 1/sqrt(hd) scale folded into one constant c = log2(e) / sqrt(hd): per score a
-// max on the raw product, one fma and one v_exp_f32 (the softmax, not the MFMAs, bounds this kernel: 16 scores per
-// lane and block against 16 small MFMAs per wave).  Keys >= len (right padding, last block only) are set to -1e30
-// before the max, so their weight is exp2(-huge) = 0; every query sees key 0, so the running max is finite.
-__device__ __forceinline__ void softmax_step(f32x4 (&s)[4], int key0, int len, float c, float& m_run, float& l_run,
-                                             float& alpha, f16x4 (&pf)[4]) {
-  float mx = -1e30f;
+// One online-softmax step for this lane's query over the 16 scores it holds of a 64-key block (raw Q.K products of keys
+// key0 + 16 ct + i in s).  Works in the base-2 domain with the 1/sqrt(hd) scale folded into one constant c = log2(e) / sqrt(hd).
+// Keys >= len (right padding, last block only) are set to -1e30 before the max, so their weight is exp2(-huge) = 0; every
+// query sees key 0, so the running max is finite.  The two arms round differently and each keeps its own form:
+//   plain  per score a max on the raw product, one fma and one v_exp_f32 (the softmax, not the MFMAs, bounds this kernel: 16
+//          scores per lane and block against 16 small MFMAs per wave);
+//   BIAS   bias = this lane's window of the staged table (entry 16 ct + i belongs to that key, already times log2(e)):
+//          t = s * c + bias first, and the max is taken AFTER the bias is added (the bias can outweigh the product).
+template <bool BIAS>
+__device__ __forceinline__ void softmax_step(f32x4 (&s)[4], const float* __restrict__ bias, int key0, int len, float c,
+                                             float& m_run, float& l_run, float& alpha, f16x4 (&pf)[4]) {
+  if constexpr (BIAS) {
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) s[ct][i] = fmaf(s[ct][i], c, bias[ct * 16 + i]);
+  }
   if (key0 - (key0 & 15) + KB > len) {     // block reaches past len (wave-uniform: key0 = kb + 4 g)
 #pragma unroll
     for (int ct = 0; ct < 4; ++ct)
@@ -43,13 +56,15 @@ __device__ __forceinline__ void softmax_step(f32x4 (&s)[4], int key0, int len, f
       for (int i = 0; i < 4; ++i)
         if (key0 + ct * 16 + i >= len) s[ct][i] = -1e30f;
   }
+  float mx = -1e30f;
 #pragma unroll
   for (int ct = 0; ct < 4; ++ct)
 #pragma unroll
     for (int i = 0; i < 4; ++i) mx = fmaxf(mx, s[ct][i]);
   mx = fmaxf(mx, __shfl_xor(mx, 16));
   mx = fmaxf(mx, __shfl_xor(mx, 32));
-  const float mn = fmaxf(m_run, mx * c);
+  float mn;
+  if constexpr (BIAS) mn = fmaxf(m_run, mx); else mn = fmaxf(m_run, mx * c);
   alpha = __builtin_amdgcn_exp2f(m_run - mn);
   m_run = mn;
   float rs = 0.f;
@@ -57,7 +72,8 @@ __device__ __forceinline__ void softmax_step(f32x4 (&s)[4], int key0, int len, f
   for (int ct = 0; ct < 4; ++ct) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const float p = __builtin_amdgcn_exp2f(fmaf(s[ct][i], c, -mn));
+      float p;
+      if constexpr (BIAS) p = __builtin_amdgcn_exp2f(s[ct][i] - mn); else p = __builtin_amdgcn_exp2f(fmaf(s[ct][i], c, -mn));
       rs += p;
       pf[ct][i] = (_Float16)p;
     }
@@ -67,10 +83,103 @@ __device__ __forceinline__ void softmax_step(f32x4 (&s)[4], int key0, int len, f
   l_run = l_run * alpha + rs;
 }
 
+// ---- the steps every kernel below is composed from (base = the (batch, head)'s Q column block of qkv; K at + hidden, V at
+// + 2 hidden; rows >= seq read as zero)
+
+// Q fragments of query row qr (B operand of S^T): lane group g holds Q[qr][hd N (4 ks + g) .. + N], N = 4 halves for the
+// 16-deep MFMA (f16x4) and 8 for the 32-deep one (f16x8).
+template <int KS, typename Frag>
+__device__ __forceinline__ void load_q_frags(Frag (&qf)[KS], const _Float16* __restrict__ base, size_t row_stride, int qr, int seq, int g) {
+  constexpr int N = sizeof(Frag) / sizeof(_Float16);
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    const Frag z = {};
+    qf[ks] = (qr < seq) ? *reinterpret_cast<const Frag*>(base + (size_t)qr * row_stride + ks * 4 * N + g * N) : z;
+  }
+}
+
+// K rows k0 .. k0 + nkeys - 1 -> sK[0 .. nkeys) row-major with pitch KROW: one 16-byte chunk per thread and pass, stored
+// whole where the pitch keeps rows 16-byte aligned (KROW % 8 == 0) and as two 8-byte halves otherwise.
+template <int HD, int KROW, int NTHR>
+__device__ __forceinline__ void stage_k(_Float16* sK, const _Float16* __restrict__ base, size_t row_stride, int hidden, int seq,
+                                        int k0, int nkeys, int tid) {
+  constexpr int CH = HD / 8;  // 16-byte chunks per key row
+  for (int id = tid; id < nkeys * CH; id += NTHR) {
+    const int key = id / CH, c = id % CH;
+    const int kr = k0 + key;
+    f16x8 kv = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (kr < seq) kv = *reinterpret_cast<const f16x8*>(base + (size_t)kr * row_stride + c * 8 + hidden);
+    if constexpr (KROW % 8 == 0) {
+      *reinterpret_cast<f16x8*>(&sK[key * KROW + c * 8]) = kv;
+    } else {
+      *reinterpret_cast<f16x4*>(&sK[key * KROW + c * 8]) = f16x4{kv[0], kv[1], kv[2], kv[3]};
+      *reinterpret_cast<f16x4*>(&sK[key * KROW + c * 8 + 4]) = f16x4{kv[4], kv[5], kv[6], kv[7]};
+    }
+  }
+}
+
+// V rows k0 .. k0 + nkeys - 1 -> sVt[hd][0 .. nkeys) TRANSPOSED with pitch VROW: a thread takes 4 consecutive keys x 8
+// head-dim columns and writes eight 8-byte pieces (4 keys of one column) instead of 32 two-byte stores.  PERM32: the
+// key order inside every 32-key group that attention_seq32_kernel's 32-deep second product wants (see there).
+template <int HD, int VROW, int NTHR, bool PERM32>
+__device__ __forceinline__ void stage_vt(_Float16* sVt, const _Float16* __restrict__ base, size_t row_stride, int hidden, int seq,
+                                         int k0, int nkeys, int tid) {
+  constexpr int CH = HD / 8;
+  for (int id = tid; id < (nkeys / 4) * CH; id += NTHR) {
+    const int kg = id / CH, c = id % CH;        // keys k0 + 4 kg .. + 3, head-dim elements 8 c .. 8 c + 7
+    f16x8 vv[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int kr = k0 + kg * 4 + j;
+      const f16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+      vv[j] = (kr < seq) ? *reinterpret_cast<const f16x8*>(base + (size_t)kr * row_stride + c * 8 + 2 * hidden) : z;
+    }
+    int pos = kg * 4;
+    if constexpr (PERM32) {
+      const int kk = pos & 31;
+      pos = (pos & ~31) + ((kk & 15) >> 2) * 8 + (kk >> 4) * 4;
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      *reinterpret_cast<f16x4*>(&sVt[(c * 8 + e) * VROW + pos]) = f16x4{vv[0][e], vv[1][e], vv[2][e], vv[3][e]};
+  }
+}
+
+// Normalise and store the O^T tiles of query row qr (this lane's column): head-dim columns 16 n + 4 g .. + 4, 8-byte stores.
 template <int HD>
+__device__ __forceinline__ void store_o(const f32x4 (&o)[HD / 16], float l_run, _Float16* __restrict__ ctx, int b, int h, int qr,
+                                        int seq, int hidden, int g) {
+  constexpr int NT = HD / 16;
+  if (qr < seq) {
+    const float inv = 1.0f / l_run;
+    _Float16* dst = ctx + ((size_t)b * seq + qr) * hidden + h * HD;
+#pragma unroll
+    for (int n = 0; n < NT; ++n) {
+      const f16x4 v = {(_Float16)(o[n][0] * inv), (_Float16)(o[n][1] * inv), (_Float16)(o[n][2] * inv), (_Float16)(o[n][3] * inv)};
+      *reinterpret_cast<f16x4*>(dst + n * 16 + 4 * g) = v;
+    }
+  }
+}
+
+// (batch, head) unit of a whole-sequence workgroup.  Workgroups go round-robin over the 8 XCDs (id % 8), and two heads that are
+// neighbours in a token's Q / K / V row share 128-byte lines when head_dim is 32: units 2p and 2p + 1 are given to the SAME
+// XCD back to back (ids 16 j + x and 16 j + 8 + x), so the second one's K / V come out of that XCD's L2.
+__device__ __forceinline__ int xcd_paired_unit(int id, int total) {
+  return (total & 15) == 0 ? (((id >> 4) << 3) + (id & 7)) * 2 + ((id >> 3) & 1) : id;
+}
+
+// BIAS: an additive relative-position bias on every score,
+//   ctx[b, s, h*hd : (h+1)*hd] = softmax(Q K^T / sqrt(hd) + bias[h][key - query] + mask) V
+// (what MPNet's layers compute; the bias arrives RESOLVED per offset -- fp32 rel_bias[heads][2 span - 1], entry
+// (key - query) + span - 1, span >= seq -- so the bucket rule stays on the host).  The workgroup stages its head's bias
+// once: sBias[j] holds log2(e) * bias[h][j - (SP - 1)] for the offsets |j - (SP - 1)| < seq and 0 beyond, SP = seq rounded
+// up to 64 -- every (query, key) pair of the padded tiles indexes inside the array, no clamp in the loop.  Everything else,
+// the fp16 rounding points included, is the plain kernel; + 4 KB of LDS.  Without BIAS rel_bias and span are not read.
+template <int HD, bool BIAS>
 __global__ __launch_bounds__(kThreads) void attention_kernel(const _Float16* __restrict__ qkv,
                                                             const int* __restrict__ lens,
-                                                            _Float16* __restrict__ ctx, int seq, int hidden) {
+                                                            _Float16* __restrict__ ctx, int seq, int hidden,
+                                                            const float* __restrict__ rel_bias, int span) {
   constexpr int KS = HD / 16;          // k-steps of the Q K^T contraction
   constexpr int NT = HD / 16;          // 16-row tiles of O^T (head-dim index)
   constexpr int KROW = HD + 4;         // padded K row (halves)
@@ -85,23 +194,33 @@ __global__ __launch_bounds__(kThreads) void attention_kernel(const _Float16* __r
   const int len = min(max(lens[b], 1), seq);
   const size_t row_stride = (size_t)3 * hidden;
   const _Float16* base = qkv + (size_t)b * seq * row_stride + h * HD;
-  const float scale = 1.44269504088896341f / sqrtf((float)HD);   // log2(e) / sqrt(hd): softmax_step works in base 2
+  const float scale = kLog2e / sqrtf((float)HD);   // log2(e) / sqrt(hd): softmax_step works in base 2
+
+  const float* bias = nullptr;          // BIAS: this lane's window of the staged table at key block 0
+  if constexpr (BIAS) {
+    // ---- stage the head's bias, times log2(e): offsets -(SP - 1) .. SP - 1, zero where no (query, key) pair of real rows
+    // has that offset (|offset| >= seq: rows of the padded tiles only).  Visible to every wave after the first barrier of
+    // the key loop (len >= 1: the loop runs at least once).
+    __shared__ float sBias[2 * kMaxSeq];
+    const int sp = (seq + KB - 1) / KB * KB;         // <= 512: the launcher checks seq
+    const float* hb = rel_bias + (size_t)h * (2 * span - 1) + (span - 1);     // offset 0 of this head
+    for (int j = tid; j < 2 * sp - 1; j += kThreads) {
+      const int d = j - (sp - 1);
+      sBias[j] = (d > -seq && d < seq) ? hb[d] * kLog2e : 0.f;
+    }
+    // this lane's keys of block kb are kb + 4 g + 16 ct + i, its query q0 + lr: staged entry (key - query) + sp - 1.
+    // q0 + lr <= sp - 1 and key <= sp - 1, so the entries are within [0, 2 sp - 2]
+    bias = sBias + (4 * g - (q0 + lr) + sp - 1);
+  }
 
   // Everything is computed TRANSPOSED: S^T = K Q^T and O^T = V^T P^T.  With the 16x16x16 accumulator layout
   // (column = lane & 15, rows 4 (lane >> 4) + i) a lane then holds the scores of ONE query (lane & 15) for 16
   // keys per block, so the softmax row reductions are 15 register ops + two cross-lane steps instead of four
   // shuffle steps per row, the per-query rescaling is a per-lane scalar, and P^T leaves the accumulators in
   // exactly the B-operand layout of the second product (4 consecutive keys of one query): no LDS round trip
-  // for P.  Q fragments (B operand of S^T): lane holds Q[query lr][hd 16 ks + 4 g .. + 4].
+  // for P.
   f16x4 qf[KS];
-  {
-    const int qr = q0 + lr;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      f16x4 z = {0, 0, 0, 0};
-      qf[ks] = (qr < seq) ? *reinterpret_cast<const f16x4*>(base + (size_t)qr * row_stride + ks * 16 + g * 4) : z;
-    }
-  }
+  load_q_frags<KS>(qf, base, row_stride, q0 + lr, seq, g);
   f32x4 o[NT];                          // O^T tile n: rows = head-dim 16 n + 4 g + i, column = query lr
 #pragma unroll
   for (int n = 0; n < NT; ++n) o[n] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -109,31 +228,8 @@ __global__ __launch_bounds__(kThreads) void attention_kernel(const _Float16* __r
 
   for (int kb = 0; kb < len; kb += KB) {
     __syncthreads();  // previous block's K / V^T fully consumed
-    // ---- stage K (row-major): one 16-byte chunk per thread and pass
-    constexpr int CH = HD / 8;  // 16-byte chunks per key row
-    for (int id = tid; id < KB * CH; id += kThreads) {
-      const int key = id / CH, c = id % CH;
-      const int kr = kb + key;
-      f16x8 kv = {0, 0, 0, 0, 0, 0, 0, 0};
-      if (kr < seq) kv = *reinterpret_cast<const f16x8*>(base + (size_t)kr * row_stride + c * 8 + hidden);
-      *reinterpret_cast<f16x4*>(&sK[key * KROW + c * 8]) = f16x4{kv[0], kv[1], kv[2], kv[3]};
-      *reinterpret_cast<f16x4*>(&sK[key * KROW + c * 8 + 4]) = f16x4{kv[4], kv[5], kv[6], kv[7]};
-    }
-    // ---- stage V transposed: a thread takes 4 consecutive keys x 8 head-dim columns and writes eight
-    // 8-byte pieces (4 keys of one column) instead of 32 two-byte stores
-    for (int id = tid; id < (KB / 4) * CH; id += kThreads) {
-      const int kg = id / CH, c = id % CH;
-      f16x8 vv[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int kr = kb + kg * 4 + j;
-        const f16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-        vv[j] = (kr < seq) ? *reinterpret_cast<const f16x8*>(base + (size_t)kr * row_stride + c * 8 + 2 * hidden) : z;
-      }
-#pragma unroll
-      for (int e = 0; e < 8; ++e)
-        *reinterpret_cast<f16x4*>(&sVt[(c * 8 + e) * VROW + kg * 4]) = f16x4{vv[0][e], vv[1][e], vv[2][e], vv[3][e]};
-    }
+    stage_k<HD, KROW, kThreads>(sK, base, row_stride, hidden, seq, kb, KB, tid);
+    stage_vt<HD, VROW, kThreads, false>(sVt, base, row_stride, hidden, seq, kb, KB, tid);
     __syncthreads();
 
     // ---- S^T = K Q^T for 4 tiles of 16 keys: lane holds keys kb + 16 ct + 4 g + i of query lr
@@ -149,7 +245,7 @@ __global__ __launch_bounds__(kThreads) void attention_kernel(const _Float16* __r
     }
     float alpha;
     f16x4 pf[4];
-    softmax_step(s, kb + 4 * g, len, scale, m_run, l_run, alpha, pf);
+    softmax_step<BIAS>(s, BIAS ? bias + kb : nullptr, kb + 4 * g, len, scale, m_run, l_run, alpha, pf);
     // ---- O^T = O^T alpha + V^T P^T   (A = V^T[hd 16 n + lr][key 16 ct + 4 g + j], B = P^T from the registers)
 #pragma unroll
     for (int n = 0; n < NT; ++n) {
@@ -162,17 +258,7 @@ __global__ __launch_bounds__(kThreads) void attention_kernel(const _Float16* __r
       }
     }
   }
-  // ---- normalise and store: this lane's query q0 + lr, head-dim columns 16 n + 4 g .. + 4 (8-byte stores)
-  const int qr = q0 + lr;
-  if (qr < seq) {
-    const float inv = 1.0f / l_run;
-    _Float16* dst = ctx + ((size_t)b * seq + qr) * hidden + h * HD;
-#pragma unroll
-    for (int n = 0; n < NT; ++n) {
-      const f16x4 v = {(_Float16)(o[n][0] * inv), (_Float16)(o[n][1] * inv), (_Float16)(o[n][2] * inv), (_Float16)(o[n][3] * inv)};
-      *reinterpret_cast<f16x4*>(dst + n * 16 + 4 * g) = v;
-    }
-  }
+  store_o<HD>(o, l_run, ctx, b, h, q0 + lr, seq, hidden, g);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -195,50 +281,22 @@ __global__ __launch_bounds__(NW * 64) void attention_seq_kernel(const _Float16* 
   _Float16* sVt = sK + SMAX * KROW;                                            // [HD][VROW]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lr = lane & 15, g = lane >> 4;
-  // (batch, head) unit of this workgroup.  Workgroups go round-robin over the 8 XCDs (id % 8), and two heads that are
-  // neighbours in a token's Q / K / V row share 128-byte lines when head_dim is 32: units 2p and 2p + 1 are given to
-  // the SAME XCD back to back (ids 16 j + x and 16 j + 8 + x), so the second one's K / V come out of that XCD's L2.
   const int heads = hidden / HD;
-  int unit = blockIdx.x;
-  if ((gridDim.x & 15) == 0) unit = (((unit >> 4) << 3) + (unit & 7)) * 2 + ((unit >> 3) & 1);
+  const int unit = xcd_paired_unit(blockIdx.x, gridDim.x);
   const int b = unit / heads, h = unit % heads;
   const int len = min(max(lens[b], 1), seq);
   const size_t row_stride = (size_t)3 * hidden;
   const _Float16* base = qkv + (size_t)b * seq * row_stride + h * HD;
-  const float scale = 1.44269504088896341f / sqrtf((float)HD);   // log2(e) / sqrt(hd): softmax_step works in base 2
+  const float scale = kLog2e / sqrtf((float)HD);   // log2(e) / sqrt(hd): softmax_step works in base 2
   const int kend = (len + KB - 1) / KB * KB;       // keys staged: whole 64-key blocks up to len (rows >= seq are zero)
 
-  constexpr int CH = HD / 8;
-  for (int id = tid; id < kend * CH; id += kThreads) {
-    const int key = id / CH, c = id % CH;
-    f16x8 kv = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (key < seq) kv = *reinterpret_cast<const f16x8*>(base + (size_t)key * row_stride + c * 8 + hidden);
-    *reinterpret_cast<f16x4*>(&sK[key * KROW + c * 8]) = f16x4{kv[0], kv[1], kv[2], kv[3]};
-    *reinterpret_cast<f16x4*>(&sK[key * KROW + c * 8 + 4]) = f16x4{kv[4], kv[5], kv[6], kv[7]};
-  }
-  for (int id = tid; id < (kend / 4) * CH; id += kThreads) {
-    const int kg = id / CH, c = id % CH;
-    f16x8 vv[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int kr = kg * 4 + j;
-      const f16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-      vv[j] = (kr < seq) ? *reinterpret_cast<const f16x8*>(base + (size_t)kr * row_stride + c * 8 + 2 * hidden) : z;
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      *reinterpret_cast<f16x4*>(&sVt[(c * 8 + e) * VROW + kg * 4]) = f16x4{vv[0][e], vv[1][e], vv[2][e], vv[3][e]};
-  }
+  stage_k<HD, KROW, kThreads>(sK, base, row_stride, hidden, seq, 0, kend, tid);
+  stage_vt<HD, VROW, kThreads, false>(sVt, base, row_stride, hidden, seq, 0, kend, tid);
   __syncthreads();
 
   for (int q0 = wave * 16; q0 < seq; q0 += NW * 16) {
     f16x4 qf[KS];
-    const int qr = q0 + lr;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      f16x4 z = {0, 0, 0, 0};
-      qf[ks] = (qr < seq) ? *reinterpret_cast<const f16x4*>(base + (size_t)qr * row_stride + ks * 16 + g * 4) : z;
-    }
+    load_q_frags<KS>(qf, base, row_stride, q0 + lr, seq, g);
     f32x4 o[NT];
 #pragma unroll
     for (int n = 0; n < NT; ++n) o[n] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -256,7 +314,7 @@ __global__ __launch_bounds__(NW * 64) void attention_seq_kernel(const _Float16* 
       }
       float alpha;
       f16x4 pf[4];
-      softmax_step(sc, kb + 4 * g, len, scale, m_run, l_run, alpha, pf);
+      softmax_step<false>(sc, nullptr, kb + 4 * g, len, scale, m_run, l_run, alpha, pf);
 #pragma unroll
       for (int n = 0; n < NT; ++n) {
 #pragma unroll
@@ -268,15 +326,7 @@ __global__ __launch_bounds__(NW * 64) void attention_seq_kernel(const _Float16* 
         }
       }
     }
-    if (qr < seq) {
-      const float inv = 1.0f / l_run;
-      _Float16* dst = ctx + ((size_t)b * seq + qr) * hidden + h * HD;
-#pragma unroll
-      for (int n = 0; n < NT; ++n) {
-        const f16x4 v = {(_Float16)(o[n][0] * inv), (_Float16)(o[n][1] * inv), (_Float16)(o[n][2] * inv), (_Float16)(o[n][3] * inv)};
-        *reinterpret_cast<f16x4*>(dst + n * 16 + 4 * g) = v;
-      }
-    }
+    store_o<HD>(o, l_run, ctx, b, h, q0 + lr, seq, hidden, g);
   }
 }
 
@@ -296,8 +346,6 @@ __global__ __launch_bounds__(NW * 64) void attention_seq_kernel(const _Float16* 
 //   * row pitches HD + 8 and SMAX + 8 halves: 16-byte aligned rows whose 16 lanes land on 16 distinct 4-bank groups.
 // Same masking, scaling and online softmax (softmax_step, per query tile); accumulation ORDER differs from the kernel above
 // (32-deep products), so results agree to fp32 rounding, not bit for bit.
-typedef _Float16 f16x8v __attribute__((ext_vector_type(8)));
-
 template <int HD, int SMAX, int NW, int QT>
 __global__ __launch_bounds__(NW * 64) void attention_seq32_kernel(const _Float16* __restrict__ qkv, const int* __restrict__ lens,
                                                                  _Float16* __restrict__ ctx, int seq, int hidden) {
@@ -310,50 +358,22 @@ __global__ __launch_bounds__(NW * 64) void attention_seq32_kernel(const _Float16
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lr = lane & 15, g = lane >> 4;
   const int heads = hidden / HD;
-  int unit = blockIdx.x;
-  if ((gridDim.x & 15) == 0) unit = (((unit >> 4) << 3) + (unit & 7)) * 2 + ((unit >> 3) & 1);   // neighbouring heads on one XCD (see above)
+  const int unit = xcd_paired_unit(blockIdx.x, gridDim.x);
   const int b = unit / heads, h = unit % heads;
   const int len = min(max(lens[b], 1), seq);
   const size_t row_stride = (size_t)3 * hidden;
   const _Float16* base = qkv + (size_t)b * seq * row_stride + h * HD;
-  const float scale = 1.44269504088896341f / sqrtf((float)HD);
+  const float scale = kLog2e / sqrtf((float)HD);
   const int kend = (len + KB - 1) / KB * KB;
 
-  constexpr int CH = HD / 8;
-  for (int id = tid; id < kend * CH; id += kThr) {
-    const int key = id / CH, c = id % CH;
-    f16x8 kv = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (key < seq) kv = *reinterpret_cast<const f16x8*>(base + (size_t)key * row_stride + c * 8 + hidden);
-    *reinterpret_cast<f16x8*>(&sK[key * KROW + c * 8]) = kv;
-  }
-  for (int id = tid; id < (kend / 4) * CH; id += kThr) {
-    const int kg = id / CH, c = id % CH;        // keys 4 kg .. 4 kg + 3, head-dim elements 8 c .. 8 c + 7
-    f16x8 vv[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int kr = kg * 4 + j;
-      const f16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-      vv[j] = (kr < seq) ? *reinterpret_cast<const f16x8*>(base + (size_t)kr * row_stride + c * 8 + 2 * hidden) : z;
-    }
-    const int k0 = kg * 4, kk = k0 & 31;
-    const int pos = (k0 & ~31) + ((kk & 15) >> 2) * 8 + (kk >> 4) * 4;
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      *reinterpret_cast<f16x4*>(&sVt[(c * 8 + e) * VROW + pos]) = f16x4{vv[0][e], vv[1][e], vv[2][e], vv[3][e]};
-  }
+  stage_k<HD, KROW, kThr>(sK, base, row_stride, hidden, seq, 0, kend, tid);          // (16-byte rows: whole-chunk stores)
+  stage_vt<HD, VROW, kThr, true>(sVt, base, row_stride, hidden, seq, 0, kend, tid);  // (keys permuted per 32-key group)
   __syncthreads();
 
   for (int q0 = wave * (16 * QT); q0 < seq; q0 += NW * 16 * QT) {
     f16x8 qf[QT][KS];
 #pragma unroll
-    for (int t = 0; t < QT; ++t) {
-      const int qr = q0 + t * 16 + lr;
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        const f16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-        qf[t][ks] = (qr < seq) ? *reinterpret_cast<const f16x8*>(base + (size_t)qr * row_stride + ks * 32 + g * 8) : z;
-      }
-    }
+    for (int t = 0; t < QT; ++t) load_q_frags<KS>(qf[t], base, row_stride, q0 + t * 16 + lr, seq, g);
     f32x4 o[QT][NT];
     float m_run[QT], l_run[QT];
 #pragma unroll
@@ -381,7 +401,7 @@ __global__ __launch_bounds__(NW * 64) void attention_seq32_kernel(const _Float16
       for (int t = 0; t < QT; ++t) {
         float alpha;
         f16x4 pf[4];
-        softmax_step(sc[t], kb + 4 * g, len, scale, m_run[t], l_run[t], alpha, pf);
+        softmax_step<false>(sc[t], nullptr, kb + 4 * g, len, scale, m_run[t], l_run[t], alpha, pf);
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2)
           pb[t][s2] = f16x8{pf[2 * s2][0], pf[2 * s2][1], pf[2 * s2][2], pf[2 * s2][3],
@@ -402,18 +422,7 @@ __global__ __launch_bounds__(NW * 64) void attention_seq32_kernel(const _Float16
       }
     }
 #pragma unroll
-    for (int t = 0; t < QT; ++t) {
-      const int qr = q0 + t * 16 + lr;
-      if (qr < seq) {
-        const float inv = 1.0f / l_run[t];
-        _Float16* dst = ctx + ((size_t)b * seq + qr) * hidden + h * HD;
-#pragma unroll
-        for (int n = 0; n < NT; ++n) {
-          const f16x4 v = {(_Float16)(o[t][n][0] * inv), (_Float16)(o[t][n][1] * inv), (_Float16)(o[t][n][2] * inv), (_Float16)(o[t][n][3] * inv)};
-          *reinterpret_cast<f16x4*>(dst + n * 16 + 4 * g) = v;
-        }
-      }
-    }
+    for (int t = 0; t < QT; ++t) store_o<HD>(o[t], l_run[t], ctx, b, h, q0 + t * 16 + lr, seq, hidden, g);
   }
 }
 
@@ -496,9 +505,24 @@ __global__ __launch_bounds__(256) void attention_short_kernel(const _Float16* __
 
 }  // namespace
 
-int attention_launch(const _Float16* qkv, const int* lens, _Float16* ctx, int batch, int seq, int hidden,
-                     int heads, hipStream_t stream) {
+int attention_launch(const _Float16* qkv, const int* lens, _Float16* ctx, int batch, int seq, int hidden, int heads,
+                     const float* rel_bias, int span, hipStream_t stream) {
   const int hd = hidden / heads;
+  const dim3 grid((seq + QB - 1) / QB, heads, batch);
+  auto blocked = [&](auto with_bias) -> int {
+    constexpr bool BIAS = decltype(with_bias)::value;
+    switch (hd) {
+      case 16: hipLaunchKernelGGL((attention_kernel<16, BIAS>), grid, dim3(kThreads), 0, stream, qkv, lens, ctx, seq, hidden, rel_bias, span); break;
+      case 32: hipLaunchKernelGGL((attention_kernel<32, BIAS>), grid, dim3(kThreads), 0, stream, qkv, lens, ctx, seq, hidden, rel_bias, span); break;
+      case 64: hipLaunchKernelGGL((attention_kernel<64, BIAS>), grid, dim3(kThreads), 0, stream, qkv, lens, ctx, seq, hidden, rel_bias, span); break;
+      default: return -1;
+    }
+    return (int)hipGetLastError();
+  };
+  if (rel_bias) {   // the blocked kernel at every sequence length: the short and whole-sequence kernels carry no bias
+    if (seq < 1 || seq > kMaxSeq || span < seq || batch < 1 || batch > 65535) return -1;
+    return blocked(std::true_type{});
+  }
   // whole sequence per workgroup when it is long enough to matter and short enough for LDS (CRS_ATTN_SEQ=0: off)
   static int seq_on = -1;
   if (seq_on < 0) { const char* e = getenv("CRS_ATTN_SEQ"); seq_on = (e && e[0] == '0') ? 0 : 1; }
@@ -532,14 +556,7 @@ int attention_launch(const _Float16* qkv, const int* lens, _Float16* ctx, int ba
     if (hd == 64 && seq <= 512 && seq > 256) return launch(&attention_seq_kernel<64, 512, 8>, 512, (512 * 68 + 64 * 516) * 2);
     if (hd == 64 && seq <= 256) return launch(&attention_seq_kernel<64, 256, 4>, 256, (256 * 68 + 64 * 260) * 2);
   }
-  dim3 grid((seq + QB - 1) / QB, heads, batch);
-  switch (hd) {
-    case 16: hipLaunchKernelGGL((attention_kernel<16>), grid, dim3(kThreads), 0, stream, qkv, lens, ctx, seq, hidden); break;
-    case 32: hipLaunchKernelGGL((attention_kernel<32>), grid, dim3(kThreads), 0, stream, qkv, lens, ctx, seq, hidden); break;
-    case 64: hipLaunchKernelGGL((attention_kernel<64>), grid, dim3(kThreads), 0, stream, qkv, lens, ctx, seq, hidden); break;
-    default: return -1;
-  }
-  return (int)hipGetLastError();
+  return blocked(std::false_type{});
 }
 
 }  // namespace crs

@@ -9,7 +9,7 @@
 //   y32  = ffn Wdown^T + b + x32              gemm mode 2
 //   x    = LayerNorm(y32)
 // then pooling + L2 normalise -- or, for crs_encoder_score_pairs, the pair head (enc_pair.hip) on the [CLS] rows; its embedding
-// step takes a token-type row per token.  The launch function allocates nothing and never synchronises, so
+// step takes a token-type row per token (embed_ln_launch with type_ids).  The launch function allocates nothing and never synchronises, so
 // a caller may capture it into a hipGraph for the launch-bound single-query case.
 #include "../../include/crs_encoder.h"
 #include "../../include/crs_hip.h"
@@ -163,12 +163,9 @@ static int encoder_forward(const crs_encoder_desc* d, const crs_encoder_weights*
   _Float16* ffn = reinterpret_cast<_Float16*>(ws + l.ffn);
   const int T = batch * seq, H = d->hidden, F = d->ffn;
 
-  if (pair && pair->type_ids)
-    CRS_TRY(crs::embed_ln_types_launch(ids_dev, pair->type_ids, w->word_emb, w->pos_emb, w->type_emb, pair->head->type_rows, w->emb_ln_g,
-                                       w->emb_ln_b, d->ln_eps, T, seq, H, d->vocab_size, x32, x16, st), "embed_ln (token types)");
-  else
-    CRS_TRY(crs::embed_ln_launch(ids_dev, w->word_emb, w->pos_emb, w->type_emb, w->emb_ln_g, w->emb_ln_b, d->ln_eps, T,
-                                 seq, H, d->vocab_size, x32, x16, st), "embed_ln");
+  CRS_TRY(crs::embed_ln_launch(ids_dev, pair ? pair->type_ids : nullptr, w->word_emb, w->pos_emb, w->type_emb,
+                               pair ? pair->head->type_rows : 1, w->emb_ln_g, w->emb_ln_b, d->ln_eps, T, seq, H, d->vocab_size, x32,
+                               x16, st), "embed_ln");
   const bool panel_h = use_panel(T, H), panel_f = use_panel(T, F);
   // index-build side (large token counts), hidden = 384: projection + bias + residual + LayerNorm in one pipelined kernel
   const bool big_ln = T > kPanelMaxTokens && bigln_enabled();
@@ -192,8 +189,7 @@ static int encoder_forward(const crs_encoder_desc* d, const crs_encoder_weights*
     } else {
     if (single_h) CRS_TRY(crs::gemm_panel_launch(x16, (const _Float16*)L.w_qkv, L.b_qkv, qkv, T, 3 * H, H, 0, small, st), "qkv gemm");
     else CRS_TRY(crs::gemm_f16_launch(x16, (const _Float16*)L.w_qkv, L.b_qkv, nullptr, qkv, T, 3 * H, H, 0, st), "qkv gemm");
-    if (rel_bias) CRS_TRY(crs::attention_relbias_launch(qkv, lens_dev, rel_bias, rel_span, ctx, batch, seq, H, d->heads, st), "attention (relative bias)");
-    else CRS_TRY(crs::attention_launch(qkv, lens_dev, ctx, batch, seq, H, d->heads, st), "attention");
+    CRS_TRY(crs::attention_launch(qkv, lens_dev, ctx, batch, seq, H, d->heads, rel_bias, rel_span, st), "attention");
     }
     if (big_ln_h) {
       CRS_TRY(crs::gemm_rowln2_launch(ctx, (const _Float16*)L.w_o, L.b_o, x32, L.ln1_g, L.ln1_b, d->ln_eps, T, H, H, x32, x16, st), "out projection + layernorm 1");

@@ -1,4 +1,4 @@
-// The row LayerNorm of the encoder's HBM-bound kernels (enc_misc.hip, enc_pair.hip): one wave64 per token row, statistics in
+// The row LayerNorm of the encoder's HBM-bound kernels (enc_misc.hip; wave_sum also in enc_pair.hip): one wave64 per token row, statistics in
 // fp32 with a two-pass (mean, then centred variance) form, eps inside the sqrt exactly as torch.nn.LayerNorm.  Each form writes
 // the fp32 residual stream AND the fp16 copy the next GEMM reads.  One definition, so that kernels which build the same row the
 // same way (the embedding kernels with and without per-token type ids) give the same bits.

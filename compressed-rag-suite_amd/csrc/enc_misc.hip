@@ -14,18 +14,25 @@ constexpr int kMaxPerLane = 16;  // hidden <= 1024 (generic instantiation); hot 
 
 // wave_sum, ln_store<PL> (4-byte columns lane + 64 i) and ln_store2<P2> (8-byte column pairs 128 i + 2 lane): enc_ln.h
 
-template <int P2>
+__device__ __forceinline__ int clamp_row(int i, int rows) { return i < 0 ? 0 : (i >= rows ? rows - 1 : i); }
+
+// Embedding gather + LayerNorm, two forms (float2 column pairs at hidden 384 / 768, 4-byte columns otherwise).  TYPES: the
+// token-type row is looked up per token (type_ids[t] clamped to [0, type_rows): the segment ids of "[CLS] a [SEP] b [SEP]");
+// without it row 0 is added and type_ids / type_rows are not read.  Same sum order either way, so an all-zero type block
+// gives the bits of the plain form.
+template <int P2, bool TYPES>
 __global__ __launch_bounds__(256) void embed_ln2_kernel(const int* __restrict__ ids, const float* __restrict__ word,
-                                                       const float* __restrict__ pos, const float* __restrict__ type0,
+                                                       const float* __restrict__ pos, const float* __restrict__ type_tab,
                                                        const float* __restrict__ g, const float* __restrict__ b,
                                                        float eps, int tokens, int seq, int hidden, int vocab,
-                                                       float* __restrict__ x32, _Float16* __restrict__ x16) {
+                                                       float* __restrict__ x32, _Float16* __restrict__ x16,
+                                                       const int* __restrict__ type_ids, int type_rows) {
   const int lane = threadIdx.x & 63;
   const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (t >= tokens) return;
-  int id = ids[t];
-  id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
-  const float* w = word + (size_t)id * hidden;
+  const float* w = word + (size_t)clamp_row(ids[t], vocab) * hidden;
+  const float* type0 = type_tab;
+  if constexpr (TYPES) type0 += (size_t)clamp_row(type_ids[t], type_rows) * hidden;
   const float* p = pos + (size_t)(t % seq) * hidden;
   float v[P2][2];
 #pragma unroll
@@ -71,18 +78,19 @@ __global__ __launch_bounds__(256) void layernorm2_kernel(const float* __restrict
   ln_store2<P2>(v, hidden, lane, g, b, eps, x32 + (size_t)t * hidden, x16 + (size_t)t * hidden);
 }
 
-template <int PL>
+template <int PL, bool TYPES>
 __global__ __launch_bounds__(256) void embed_ln_kernel(const int* __restrict__ ids, const float* __restrict__ word,
-                                                      const float* __restrict__ pos, const float* __restrict__ type0,
+                                                      const float* __restrict__ pos, const float* __restrict__ type_tab,
                                                       const float* __restrict__ g, const float* __restrict__ b,
                                                       float eps, int tokens, int seq, int hidden, int vocab,
-                                                      float* __restrict__ x32, _Float16* __restrict__ x16) {
+                                                      float* __restrict__ x32, _Float16* __restrict__ x16,
+                                                      const int* __restrict__ type_ids, int type_rows) {
   const int lane = threadIdx.x & 63;
   const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (t >= tokens) return;
-  int id = ids[t];
-  id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
-  const float* w = word + (size_t)id * hidden;
+  const float* w = word + (size_t)clamp_row(ids[t], vocab) * hidden;
+  const float* type0 = type_tab;
+  if constexpr (TYPES) type0 += (size_t)clamp_row(type_ids[t], type_rows) * hidden;
   const float* p = pos + (size_t)(t % seq) * hidden;
   float v[PL];
 #pragma unroll
@@ -206,15 +214,19 @@ __global__ __launch_bounds__(256) void pool_kernel(const float* __restrict__ x32
 
 }  // namespace
 
-int embed_ln_launch(const int* ids, const float* word, const float* pos, const float* type0, const float* g,
-                    const float* b, float eps, int tokens, int seq, int hidden, int vocab, float* x32,
-                    _Float16* x16, hipStream_t stream) {
-#define CRS_EMB(PL) hipLaunchKernelGGL((embed_ln_kernel<PL>), dim3((tokens + 3) / 4), dim3(256), 0, stream, ids, word, \
-                                      pos, type0, g, b, eps, tokens, seq, hidden, vocab, x32, x16)
-#define CRS_EMB2(P2) hipLaunchKernelGGL((embed_ln2_kernel<P2>), dim3((tokens + 3) / 4), dim3(256), 0, stream, ids, word, \
-                                       pos, type0, g, b, eps, tokens, seq, hidden, vocab, x32, x16)
-  if (hidden == 384) CRS_EMB2(3); else if (hidden == 768) CRS_EMB2(6); else if (hidden <= 64) CRS_EMB(1); else CRS_EMB(16);
-#undef CRS_EMB2
+int embed_ln_launch(const int* ids, const int* type_ids, const float* word, const float* pos, const float* type_tab,
+                    int type_rows, const float* g, const float* b, float eps, int tokens, int seq, int hidden, int vocab,
+                    float* x32, _Float16* x16, hipStream_t stream) {
+#define CRS_EMB(KERNEL, N)                                                                                                  \
+  do {                                                                                                                      \
+    if (type_ids) hipLaunchKernelGGL((KERNEL<N, true>), dim3((tokens + 3) / 4), dim3(256), 0, stream, ids, word, pos,       \
+                                     type_tab, g, b, eps, tokens, seq, hidden, vocab, x32, x16, type_ids, type_rows);       \
+    else hipLaunchKernelGGL((KERNEL<N, false>), dim3((tokens + 3) / 4), dim3(256), 0, stream, ids, word, pos, type_tab, g,  \
+                            b, eps, tokens, seq, hidden, vocab, x32, x16, type_ids, type_rows);                             \
+  } while (0)
+  // the form per hidden size: with and without type ids the sums meet in the same order
+  if (hidden == 384) CRS_EMB(embed_ln2_kernel, 3); else if (hidden == 768) CRS_EMB(embed_ln2_kernel, 6);
+  else if (hidden <= 64) CRS_EMB(embed_ln_kernel, 1); else CRS_EMB(embed_ln_kernel, 16);
 #undef CRS_EMB
   return (int)hipGetLastError();
 }

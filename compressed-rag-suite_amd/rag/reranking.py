@@ -4,7 +4,7 @@ What users of a retrieve-then-read pipeline mean by ``rerank: true``: a BERT seq
 ``[CLS] query [SEP] chunk [SEP]`` and emits one relevance logit (``cross-encoder/ms-marco-MiniLM-L-6-v2`` and its L-12 /
 TinyBERT siblings; sentence-transformers' ``CrossEncoder.predict``).  Here: host WordPiece pair encoding
 (rag/tokenizer.py ``join_pair``) -> ``crs_encoder_score_pairs`` (the hand-written encoder's layer stack with per-token type
-ids, then the pooler + classifier head kernel; csrc/enc_pair.hip).  No CPU path.
+ids, then the pooler + classifier head kernel; csrc/enc_misc.hip, csrc/enc_pair.hip).  No CPU path.
 
 Config keys: ``model_name`` / ``model_path``, ``batch_size`` (pairs per launch, default 128), ``max_seq_length``,
 ``activation`` (``'auto' | 'identity' | 'sigmoid'``), ``device``, ``synthetic_seed``.

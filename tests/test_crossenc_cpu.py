@@ -91,11 +91,16 @@ def test_argument_validation_without_gpu():
 
 
 def test_new_kernels_use_no_scratch():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_resources.py"), "--list", "enc_pair.hip"], capture_output=True,
-                       text=True, timeout=600)
+    """The pair head (enc_pair.hip: 2 kernels) and the TYPES instantiations of the embedding kernels (enc_misc.hip: 37 kernels)."""
+    import re
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_resources.py"), "--list", "enc_misc.hip", "enc_pair.hip"],
+                       capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
-    assert "0 violation(s)" in r.stdout and "6 kernels in 1 files" in r.stdout, r.stdout
-    assert "pair_head_kernel" in r.stdout and "embed_ln2_types_kernel" in r.stdout
+    assert "0 violation(s)" in r.stdout and "39 kernels in 2 files" in r.stdout, r.stdout
+    assert "pair_head_kernel" in r.stdout
+    for kernel, n in (("embed_ln2_kernel", 3), ("embed_ln2_kernel", 6), ("embed_ln_kernel", 1), ("embed_ln_kernel", 16)):
+        # <N, true>, demangled or (where the demangler does not know _Float16) as the mangled name spells it
+        assert re.search(r"%s(<%d, true>|ILi%dELb1EE)" % (kernel, n, n), r.stdout), (kernel, n, r.stdout)
 
 
 # ---- pair encoding ---------------------------------------------------------------------------------------------------------------

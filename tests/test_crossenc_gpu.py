@@ -1,5 +1,5 @@
 """GPU: cross-encoder re-ranking.  crs_encoder_score_pairs (per-token type ids at the embedding step, the pooler + classifier head
-kernel; csrc/enc_pair.hip) against transformers' BertForSequenceClassification in fp64 (tests/golden/crossenc.npz, written by
+kernel; csrc/enc_misc.hip, csrc/enc_pair.hip) against transformers' BertForSequenceClassification in fp64 (tests/golden/crossenc.npz, written by
 tools/make_crossenc_golden.py), the head alone against a bound computed from its own inputs, the all-zero and out-of-range type
 ids, CrossEncoderReranker.predict and the retriever's rerank_model switch.
 

@@ -1,4 +1,4 @@
-"""GPU parity of the relative-position-bias attention (csrc/enc_attn_relbias.hip) and of everything above it: the _ex
+"""GPU parity of the relative-position-bias attention (attention_kernel<HD, true>, csrc/enc_attn.hip) and of everything above it: the _ex
 forward against transformers.MPNetModel in fp64 (tests/golden/encoder_mpnet.npz, tools/make_mpnet_golden.py), against
 the project's own oracle with an all-zero bias, the rel_span check, the two kernel selections, and the graph-captured
 query forward of the retrieval engine.  Tolerances: tests/test_encoder_gpu.py's (same arithmetic + one fp32 add per score)."""
@@ -83,6 +83,45 @@ def test_zero_bias_forward_matches_the_oracle(cuda, name, cfg, seed, batch, seq)
         assert (1.0 - _cos(out, ref)).max() < 2e-4
         assert np.abs(out - ref).max() < 3e-3
         assert np.abs(out @ out.T - ref @ ref.T).max() < 1e-3
+
+
+# (config, seq): the shapes at which the bias kernel's indexing can go wrong and that no case above reaches.  TINY at 1 and 64:
+# a single query / exactly one key block, the staged table at its smallest padded span (64).  MID at 65 (a second key block
+# of one key), 129 (a third block of one key, past the distance clamp at 128) and 256 (its max_seq: a whole number of key
+# blocks).  BASE at 65.
+KEY_BLOCK_EDGES = [(mc.TINY, 1), (mc.TINY, 64), (mc.MID, 65), (mc.MID, 129), (mc.MID, 256), (mc.BASE, 65)]
+
+
+@pytest.mark.parametrize("cfg,seq", KEY_BLOCK_EDGES, ids=[f"{c.name}-{s}" for c, s in KEY_BLOCK_EDGES])
+def test_relbias_key_block_edges_match_fp64(cuda, cfg, seq):
+    """The _ex forward against _mpnet_cases.encode_ref (fp64, the asymmetric random table) at the key-block edges: batch 2,
+    one full row and one row of a single token.  Bounds: those of test_forward_matches_transformers_mpnet (encode_ref in
+    fp32 against itself in fp64 stays inside them at these shapes by two orders of magnitude)."""
+    import torch
+    from _encoder_cases import pool
+    seed = 300 + seq
+    w = mc.make_weights(cfg, seed)
+    enc = _mpnet_encoder(cfg, seed, cuda)
+    ids = np.random.default_rng(seed + 1).integers(4, cfg.vocab_size, size=(2, seq)).astype(np.int32)
+    lens = np.array([seq, 1], dtype=np.int32)
+    mask = (np.arange(seq)[None, :] < lens[:, None]).astype(np.int32)
+    ids[:, 0], ids[1, 1:] = mc.CLS_ID, mc.PAD_ID                  # <s> ... </s> | <s> <pad> ...
+    if seq > 1:
+        ids[0, seq - 1] = mc.SEP_ID
+    ref_h = mc.encode_ref(ids, mask, w, cfg, enc.rel_bias.cpu().numpy())
+    mean, hidden = enc.forward(ids, lens, return_hidden=True)
+    enc.desc.pooling = 1
+    cls = enc.forward(ids, lens)
+    torch.cuda.synchronize()
+    valid = mask.astype(bool)
+    figures = dict(hidden=np.abs(hidden.cpu().numpy()[valid] - ref_h[valid]).max())
+    for name, got in (("mean", mean.cpu().numpy()), ("cls", cls.cpu().numpy())):
+        ref = pool(ref_h, mask, name, True)
+        figures[name + "_cos"], figures[name + "_abs"] = (1.0 - _cos(got, ref)).max(), np.abs(got - ref).max()
+    print(cfg.name, seq, {k: float(v) for k, v in figures.items()})
+    assert figures["hidden"] < 3e-2
+    assert figures["mean_cos"] < 2e-4 and figures["cls_cos"] < 2e-4
+    assert figures["mean_abs"] < 3e-3 and figures["cls_abs"] < 3e-3
 
 
 def test_rel_span_shorter_than_seq_is_einval_without_a_launch(cuda):

@@ -10,12 +10,13 @@ tokens long, 128 pairs per launch.
   rocprofv3 --kernel-trace --stats -d DIR -o ce -- python tools/bench_crossenc.py --once
   python tools/bench_crossenc.py --stats DIR/.../ce_kernel_stats.csv --out profiles/crossenc_bench.json
       a run of its own for the profiler (one predict per length, no timing), then the share of device time spent in the two new
-      kernels (embed_ln*_types_kernel, pair_head_kernel) read from its kernel statistics and merged into the same file
+      kernels (embed_ln*_kernel<N, true>, pair_head_kernel) read from its kernel statistics and merged into the same file
 Anything not measured is written as "unmeasured"."""
 import argparse
 import csv
 import json
 import os
+import re
 import statistics
 import sys
 import time
@@ -82,7 +83,7 @@ def kernel_share(path):
             name = row.get("Name", "")
             if "pair_head_kernel" in name:
                 new["pair_head"] += ns
-            elif "_types_kernel" in name:
+            elif re.search(r"embed_ln2?_kernel(<\d+, true>|ILi\d+ELb1EE)", name):      # the TYPES instantiations (csrc/enc_misc.hip)
                 new["embed_ln_types"] += ns
     if total <= 0:
         return "unmeasured"
