@@ -412,6 +412,24 @@ int crs_mmr_order(const float* vecs_dev, int64_t n_rows, int dim, const int64_t*
   return e ? hip_fail((hipError_t)e, "mmr_order launch") : CRS_OK;
 }
 
+int crs_token_match(const float* a_dev, const int32_t* len_a_dev, int seq_a, const float* b_dev, const int32_t* len_b_dev, int seq_b,
+                    int n_pairs, int hidden, const float* w_a_dev, const float* w_b_dev, float* out_dev, void* stream) {
+  if (seq_a < 1 || seq_a > 512) return fail(CRS_EINVAL, "seq_a must be in 1..512");
+  if (seq_b < 1 || seq_b > 512) return fail(CRS_EINVAL, "seq_b must be in 1..512");
+  if (hidden < 64 || hidden > 1024 || hidden % 64) return fail(CRS_EINVAL, "hidden must be a multiple of 64 in 64..1024");
+  if (n_pairs < 0) return fail(CRS_EINVAL, "n_pairs must be >= 0");
+  if (!a_dev) return fail(CRS_EINVAL, "a_dev is null");
+  if (!len_a_dev) return fail(CRS_EINVAL, "len_a_dev is null");
+  if (!b_dev) return fail(CRS_EINVAL, "b_dev is null");
+  if (!len_b_dev) return fail(CRS_EINVAL, "len_b_dev is null");
+  if (!out_dev) return fail(CRS_EINVAL, "out_dev is null");
+  if (((uintptr_t)a_dev | (uintptr_t)b_dev) & 15) return fail(CRS_EINVAL, "a_dev / b_dev must be 16-byte aligned");
+  if (n_pairs == 0) return CRS_OK;
+  const int e = crs::token_match_launch(a_dev, len_a_dev, seq_a, b_dev, len_b_dev, seq_b, n_pairs, hidden, w_a_dev, w_b_dev, out_dev,
+                                        (hipStream_t)stream);
+  return e ? hip_fail((hipError_t)e, "token_match launch") : CRS_OK;
+}
+
 int crs_rerank_lexical(const float* scores_dev, const int64_t* rows_dev, int nq, int m_max, const int64_t* doc_offsets_dev,
                        const int32_t* doc_tokens_dev, int64_t n_rows, int64_t n_doc_tokens, const int64_t* q_offsets_dev,
                        const int32_t* q_tokens_dev, int64_t n_q_tokens, const int32_t* q_norm_dev, int k, double threshold,

@@ -99,6 +99,10 @@ int rerank_lexical_launch(const float* scores, const int64_t* rows, int nq, int 
                           int64_t n_rows, int64_t n_doc_tok, const int64_t* q_off, const int* q_tok, int64_t n_q_tok, const int* q_norm,
                           int k, double threshold, int* order, int* out_count, double* sim, double* rr, int* reranked, hipStream_t stream);
 
+// token_match.hip: BERTScore's greedy matching of pairs of token-state matrices, one workgroup per pair
+int token_match_launch(const float* a, const int* len_a, int seq_a, const float* b, const int* len_b, int seq_b, int n_pairs, int hidden,
+                       const float* w_a, const float* w_b, float* out, hipStream_t stream);
+
 // convert.hip
 int refine_f32_launch(const float* q32, int nq, int dim, const float* shadow, int64_t n_rows, int64_t id_base,
                       const int64_t* cand, int k_in, int k_out, float* out_s, int64_t* out_i, hipStream_t stream);

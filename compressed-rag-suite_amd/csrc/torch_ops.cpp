@@ -17,6 +17,7 @@
 //   crs::merge_topk / crs::merge_topk_wire   cross-shard merge                (new vs the reference)
 //   crs::merge_sorted / crs::merge_sorted_wire   the same for sorted lists, k 65 .. 1024
 //   crs::mmr_order         replaces the greedy MMR loop of _apply_diversity  (reference rag/retrieval.py:219-277)
+//   crs::token_match       the greedy matching behind bert_score.score  (reference evaluation/retrieval/rag_metrics.py:179-207)
 //   crs::rerank_lexical    replaces the scoring, threshold and _rerank loops of retrieve_batch  (reference rag/retrieval.py:75-77, 196-217)
 // Tensors are torch-owned; every op launches on the CURRENT HIP stream of the tensors' device, so the ops
 // compose with torch streams and hipGraph capture.  Errors of the C ABI surface as RuntimeError (TORCH_CHECK)
@@ -467,6 +468,35 @@ void mmr_order_out(const Tensor& vecs, int64_t n_rows, const Tensor& rows, const
      "crs::mmr_order");
 }
 
+// ---- BERTScore token matching (csrc/token_match.hip) ---------------------------------------------------------------
+// a fp32 [n, seq_a, hidden], b fp32 [n, seq_b, hidden]; len_a / len_b int32 [n]; w_a fp32 [n, seq_a] / w_b fp32 [n, seq_b] (optional);
+// out fp32 [n, 3]
+void token_match_out(const Tensor& a, const Tensor& len_a, const Tensor& b, const Tensor& len_b, c10::optional<Tensor> w_a,
+                     c10::optional<Tensor> w_b, Tensor out) {
+  want(a, at::kFloat, "a");
+  want(len_a, at::kInt, "len_a");
+  want(b, at::kFloat, "b");
+  want(len_b, at::kInt, "len_b");
+  want(out, at::kFloat, "out");
+  if (has(w_a)) want(*w_a, at::kFloat, "w_a");
+  if (has(w_b)) want(*w_b, at::kFloat, "w_b");
+  same_device(a, {&len_a, &b, &len_b, opt_t(w_a), opt_t(w_b), &out}, "crs::token_match");
+  TORCH_CHECK(a.dim() == 3 && b.dim() == 3 && a.size(0) == b.size(0) && a.size(2) == b.size(2),
+              "a must be fp32 [n, seq_a, hidden] and b fp32 [n, seq_b, hidden]");
+  const int64_t n = a.size(0);
+  TORCH_CHECK(n <= 0x7fffffff, "too many pairs");
+  TORCH_CHECK(len_a.dim() == 1 && len_a.size(0) == n && len_b.dim() == 1 && len_b.size(0) == n, "len_a / len_b must be int32 [n]");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == n && out.size(1) == 3, "out must be fp32 [n, 3]");
+  if (has(w_a)) TORCH_CHECK(w_a->dim() == 2 && w_a->size(0) == n && w_a->size(1) == a.size(1), "w_a must be fp32 [n, seq_a]");
+  if (has(w_b)) TORCH_CHECK(w_b->dim() == 2 && w_b->size(0) == n && w_b->size(1) == b.size(1), "w_b must be fp32 [n, seq_b]");
+  TORCH_CHECK(a.size(1) <= 0x7fffffff && b.size(1) <= 0x7fffffff && a.size(2) <= 0x7fffffff, "sizes out of range");
+  if (n == 0) return;
+  c10::hip::HIPGuardMasqueradingAsCUDA g(a.device());
+  ok(crs_token_match(a.data_ptr<float>(), len_a.data_ptr<int32_t>(), (int)a.size(1), b.data_ptr<float>(), len_b.data_ptr<int32_t>(),
+                     (int)b.size(1), (int)n, (int)a.size(2), (const float*)opt_ptr(w_a), (const float*)opt_ptr(w_b),
+                     out.data_ptr<float>(), cur_stream(a)), "crs::token_match");
+}
+
 // ---- lexical re-rank (csrc/rerank.hip) ----------------------------------------------------------------------------
 // scores fp32 / rows int64 / order int32 / sim, rr fp64 [nq, m_max]; doc_offsets int64 [>= n_rows + 1], doc_tokens int32 (the rows'
 // token CSR); q_offsets int64 [nq + 1], q_tokens int32 (the queries' known tokens); q_norm / count / reranked int32 [nq]
@@ -659,6 +689,7 @@ TORCH_LIBRARY(crs, m) {
   m.def("merge_sorted_out(Tensor scores, Tensor ids, int k_out, Tensor(a!) out_scores, Tensor(b!) out_ids) -> ()");
   m.def("merge_sorted_wire_out(Tensor wire, int nlists, int nq, int k_in, int k_out, Tensor(a!) out_scores, Tensor(b!) out_ids) -> ()");
   m.def("mmr_order_out(Tensor vecs, int n_rows, Tensor rows, Tensor rel, Tensor counts, float lam, Tensor(a!) order) -> ()");
+  m.def("token_match_out(Tensor a, Tensor len_a, Tensor b, Tensor len_b, Tensor? w_a, Tensor? w_b, Tensor(a!) out) -> ()");
   m.def("rerank_lexical(Tensor scores, Tensor rows, Tensor doc_offsets, Tensor doc_tokens, int n_rows, Tensor q_offsets, Tensor q_tokens, "
         "Tensor q_norm, int k, float threshold, Tensor(a!) order, Tensor(b!) count, Tensor(c!) sim, Tensor(d!) rr, Tensor(e!) reranked) -> ()");
   m.def("encoder_forward(Tensor ids, Tensor lens, Tensor[] weights, int[] desc, float ln_eps, Tensor(a!) workspace, Tensor(b!) out, "
@@ -690,6 +721,7 @@ TORCH_LIBRARY_IMPL(crs, CUDA, m) {   // the HIP backend of torch-ROCm dispatches
   m.impl("merge_sorted_out", &merge_sorted_out);
   m.impl("merge_sorted_wire_out", &merge_sorted_wire_out);
   m.impl("mmr_order_out", &mmr_order_out);
+  m.impl("token_match_out", &token_match_out);
   m.impl("rerank_lexical", &rerank_lexical);
   m.impl("encoder_forward", &encoder_forward);
   m.impl("encoder_forward_ex", &encoder_forward_ex);

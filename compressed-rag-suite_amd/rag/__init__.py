@@ -9,6 +9,7 @@ from rag.embedding import EmbeddingModel
 from rag.indexing import VectorStore
 from rag.retrieval import ContextRetriever
 from rag.generation import RAGGenerator
+from rag.bertscore import BertScorer
 
 __all__ = [
     'RAGPipeline',
@@ -19,4 +20,5 @@ __all__ = [
     'VectorStore',
     'ContextRetriever',
     'RAGGenerator',
+    'BertScorer',
 ]

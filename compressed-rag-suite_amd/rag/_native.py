@@ -48,6 +48,7 @@ _SIGNATURES = {
                                c_void_p]),
     "crs_merge_sorted": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "crs_mmr_order": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_void_p, c_void_p]),
+    "crs_token_match": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "crs_rerank_lexical": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64,
                                    c_void_p, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "crs_rescore_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p,
@@ -298,6 +299,18 @@ def mmr_order(vecs, n_rows: int, rows, rel, counts, lam: float, out=None):
         out = torch.empty(rows.shape, dtype=torch.int32, device=vecs.device)
     with _translate():
         ops().mmr_order_out(vecs, int(n_rows), rows, rel, counts, float(lam), out)
+    return out
+
+
+def token_match(a, len_a, b, len_b, w_a=None, w_b=None, out=None):
+    """BERTScore's greedy matching of n pairs of token states in one launch (crs_token_match, csrc/token_match.hip): a cuda fp32
+    [n, seq_a, hidden] (candidates), b [n, seq_b, hidden] (references), len_a / len_b int32 [n], w_a / w_b fp32 [n, seq] token
+    weights or None (1 on every real token) -> fp32 [n, 3] = P, R, F.  seq <= 512, hidden a multiple of 64 up to 1024.  No host sync."""
+    import torch
+    if out is None:
+        out = torch.empty((a.shape[0], 3), dtype=torch.float32, device=a.device)
+    with _translate():
+        ops().token_match_out(a, len_a, b, len_b, w_a, w_b, out)
     return out
 
 

@@ -255,6 +255,26 @@ int crs_rerank_lexical(const float* scores_dev, const int64_t* rows_dev, int nq,
                        const int32_t* q_tokens_dev, int64_t n_q_tokens, const int32_t* q_norm_dev, int k, double threshold,
                        int32_t* order_dev, int32_t* count_dev, double* sim_dev, double* rr_dev, int32_t* reranked_dev, void* stream);
 
+/* ---- BERTScore token matching: the step behind the encoder in bert_score.score -- evaluation/retrieval/rag_metrics.py:179-207 ----
+ * (additive to ABI 3; csrc/token_match.hip).  Scores `n_pairs` (candidate, reference) pairs of token states in one launch, one
+ * workgroup per pair:
+ *   a_dev      fp32 [n_pairs, seq_a, hidden]  candidate token states, 16-byte aligned; rows at or past len_a are never read
+ *   len_a_dev  int32 [n_pairs]                real tokens of each candidate (clamped to [0, seq_a])
+ *   b_dev      fp32 [n_pairs, seq_b, hidden]  reference token states, 16-byte aligned; rows at or past len_b are never read
+ *   len_b_dev  int32 [n_pairs]                real tokens of each reference (clamped to [0, seq_b])
+ *   w_a_dev    fp32 [n_pairs, seq_a] or null  token weights of the candidates (idf); null = 1 on every real token
+ *   w_b_dev    fp32 [n_pairs, seq_b] or null  token weights of the references
+ *   out_dev    fp32 [n_pairs, 3]              out: P, R, F
+ * sim[i][j] = <a_i, b_j> / (|a_i| |b_j|) over i < len_a, j < len_b, fp32 products and fp32 accumulation (f32-input MFMA: an fmaf
+ * chain over hidden), 0 when either norm is 0, never NaN from a zero row.  P = sum_i w_a[i] max_j sim[i][j] / sum_i w_a[i],
+ * R = sum_j w_b[j] max_i sim[i][j] / sum_j w_b[j]; a side whose weight sum is not positive, and both sides of a pair with an empty
+ * sentence, give 0.  F = 2PR / (P + R), 0 when P + R is 0 or not finite.  A pair's three numbers do not depend on n_pairs, on the
+ * other pairs of the launch, on seq_a / seq_b or on anything stored in the padding rows.
+ * Limits (CRS_EINVAL otherwise): 1 <= seq_a, seq_b <= 512; hidden a multiple of 64 in 64..1024; n_pairs >= 0 (0: no launch).
+ * No host synchronisation, no workspace. */
+int crs_token_match(const float* a_dev, const int32_t* len_a_dev, int seq_a, const float* b_dev, const int32_t* len_b_dev, int seq_b,
+                    int n_pairs, int hidden, const float* w_a_dev, const float* w_b_dev, float* out_dev, void* stream);
+
 /* ---- one-collective exchange (ONE all-gather per query batch) ------------------
  * A rank's per-shard result travels as one contiguous "wire block":
  *     [ ids int64 [nq, k] | scores fp32 [nq, k] | pad to 8 bytes ]        crs_wire_bytes(nq, k) bytes
