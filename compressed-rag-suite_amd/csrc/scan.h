@@ -26,6 +26,7 @@ struct ScanArgs {
   int t_dyn;              //   first dynamically scheduled tile (a multiple of nwg, >= 2 nwg); n_tiles when the schedule is static
   int dyn_mask;           //   a ticket stands for dyn_mask + 1 consecutive tiles (a power of two)
   int nt;                 // scan_tb.hip / scan_i8.hip: 1 = slab tiles streamed with the non-temporal policy (lds_dma16_nt)
+  int no_stagger;         // scan_wide.hip, 24- / 32-slot forms: 1 = CRS_WIDE_STAGGER=0 (set by scan_launch_wide, read by nothing else)
 };
 
 // the exactness workspace of a batch (capi.hip carves it): per-query escalation threshold and row counter, the escalation

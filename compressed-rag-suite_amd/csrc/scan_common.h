@@ -62,10 +62,12 @@ __device__ __forceinline__ int grid_stream(const ScanArgs& a) {
 
 // tools/scan_wide_probe.hip, tools/scan_tb_probe.hip: per-wave cycle accumulators (diagnostic build only)
 #ifdef CRS_STAMPS
-#define WP_DECL unsigned long long wp_[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long wp_t_ = __builtin_amdgcn_s_memtime(); const unsigned long long wp_t0_ = wp_t_
-#define WP_LAP(slot) do { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); wp_[slot] += n_ - wp_t_; wp_t_ = n_; } while (0)
+// (32-bit accumulators: a launch is far below 2^32 cycles, and twelve 64-bit ones pushed scan_wide_kernel<384,8,24>'s scalars -- and with them
+// two vector registers -- out into scratch, whose reloads wait for the tile transfers in flight)
+#define WP_DECL unsigned wp_[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; unsigned wp_t_ = (unsigned)__builtin_amdgcn_s_memtime(); const unsigned wp_t0_ = wp_t_
+#define WP_LAP(slot) do { const unsigned n_ = (unsigned)__builtin_amdgcn_s_memtime(); wp_[slot] += n_ - wp_t_; wp_t_ = n_; } while (0)
 #define WP_COUNT(slot) do { ++wp_[slot]; } while (0)
-#define WP_STORE(nw_) do { if (a.stamps && lane == 0) { wp_[11] = __builtin_amdgcn_s_memtime() - wp_t0_; for (int i_ = 0; i_ < 12; ++i_) a.stamps[((size_t)blockIdx.x * (nw_) + wave) * 12 + i_] = wp_[i_]; } } while (0)
+#define WP_STORE(nw_) do { if (a.stamps && lane == 0) { wp_[11] = (unsigned)__builtin_amdgcn_s_memtime() - wp_t0_; for (int i_ = 0; i_ < 12; ++i_) a.stamps[((size_t)blockIdx.x * (nw_) + wave) * 12 + i_] = wp_[i_]; } } while (0)
 #else
 #define WP_DECL do {} while (0)
 #define WP_LAP(slot) do {} while (0)

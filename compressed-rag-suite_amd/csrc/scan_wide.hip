@@ -15,9 +15,11 @@
 //     16 rows of the tile per lane, a query's scores live in a lane PAIR (l, l ^ 32);
 //   * selection is "tile best" (scan_refine.hip): per tile the lane pair reduces its 2 x 16 scores to the
 //     tile's best row (one xor-shuffle), and that single candidate is inserted into a register-resident
-//     sorted list of the K best so far (a branch-free compare-exchange chain, 5 VALU per slot).  The two
-//     lanes of a pair take turns -- lane half h inserts the tiles of parity h -- so the chain runs once
-//     per TWO tiles; nothing is filtered against a threshold, no LDS lists, no compaction.
+//     sorted list of the K best so far (a branch-free compare-exchange chain, 5 VALU per slot).  Nothing is
+//     filtered against a threshold, no LDS lists, no compaction.  Chains of up to 16 slots: the two lanes of
+//     a pair take turns -- lane half h inserts the tiles of parity h into its own K-slot list -- so the
+//     chain runs once per TWO tiles.  Chains of 24 / 32 slots: ONE K-slot list per lane pair, split across
+//     it ("Split list" below) -- K / 2 slots per lane, the chain runs every tile on both halves at once;
 //     The first version of this kernel used scan.hip's per-lane LDS candidate lists + wave compaction:
 //     measured on C4 with 256 queries (tools/scan_wide_probe), of 1.13 M cycles per wave 0.38 M went to
 //     compactions (15 k cycles each, and with 8 waves behind one barrier every one of them stalls the
@@ -32,6 +34,19 @@
 // 32-slot forms run one query block per launch in practice, so they also take scan_tb.hip's non-temporal slab stream and its
 // ticketed dynamic tile schedule behind the same plan fields (ScanArgs::nt, ticket / t_dyn / dyn_mask); the shorter chains are
 // compiled without either, exactly as they were measured.
+//
+// Split list (K = 24, 32).  The lower half of a lane pair (h = 0) holds ranks 0 .. K/2 - 1 of the pair's list, the upper half
+// ranks K/2 .. K - 1.  Per tile the upper half fetches the lower half's LAST slot as it is before the insertion (one
+// v_permlane32_swap each for score and row), the lower half inserts the tile's (x, row), and the upper half inserts what the lower
+// half pushes out: its old last slot where x > that slot, else x itself.  Both halves insert by SHIFTING (insert_shift below): every
+// slot that x beats (strict >: a later tile goes behind an equal earlier one) moves down one place, whatever it holds -- the compare-
+// exchange chain of the shorter forms lets a displaced entry step over an equal one, and then what falls off a half's end is no longer
+// its last slot.  The shift keeps the pair's list in the order (score desc, earlier tile first) exactly: a pushed-out slot is >= every
+// entry of the upper half and earlier than the equal ones, x beats all of those, so it lands in front of them; until the lower half
+// is full the upper half is handed (-inf, -1), a no-op.  The K best tiles of the shard that a workgroup saw are among that one
+// list as they were among its two parity lists.  VALU per tile is what it was (K/2 x 5 every tile against K x 5 every second tile,
+// + 6 for the exchange); the list's registers halve, which is what lets <384, 8, 24> keep the deferred accumulators of the stagger
+// (wide_stagger<>).
 
 #include "scan_common.h"
 
@@ -56,11 +71,21 @@ constexpr int wide_rb() { return (NW == 8 && D <= 384) ? 2 : 1; }
 // the forms with chains longer than 16 slots: nt stream + dynamic tile schedule compiled in (header)
 template <int K>
 constexpr bool wide_streamed() { return K > 16; }
+// the same forms keep one K-slot list per lane pair, K / 2 slots in each half (header: "Split list")
+template <int K>
+constexpr bool wide_split() { return K > 16; }
+template <int K>
+constexpr int wide_lane_slots() { return wide_split<K>() ? K / 2 : K; }
 // Waves 4..7 defer a tile's selection by one iteration (the stagger below) where the deferred accumulators fit: two waves per
 // SIMD leave 256 registers per lane, VGPRs and AGPRs together.  384-element rows: 96 of query fragments, 32 + 32 of current and
-// deferred accumulators and 2 K of chain -- 16 slots and more would spill (profiles/r07_wide_resources.txt).
+// deferred accumulators and 2 x (slots per lane) of chain -- 16 slots per lane and more would spill
+// (profiles/r07_wide_resources.txt).  The split list leaves <384, 8, 24> 12 slots per lane: 256 registers, no scratch
+// (profiles/r12_wide_resources.txt).  The other forms keep the value they were measured with.
 template <int D, int NW, int K>
-constexpr bool wide_stagger() { return NW == 8 && D <= 384 && !(D == 384 && K >= 16) && !(D == 256 && K >= 32); }
+constexpr bool wide_stagger() {
+  if (D == 384 && NW == 8 && K == 24) return true;
+  return NW == 8 && D <= 384 && !(D == 384 && K >= 16) && !(D == 256 && K >= 32);
+}
 
 template <int D, int NW>
 struct WCfg {
@@ -205,18 +230,20 @@ __global__ __launch_bounds__(NW * 64, 2) void scan_wide_kernel(const ScanArgs a)
 #pragma unroll
   for (int j = 0; j < 8; ++j) a_off[j] = qn * (C::kCpr * 16) + (((2 * j + h) ^ qn) & 15) * 16;
 
-  // this lane's K best tiles so far as (best score, first row), sorted: score desc, earlier tile first on ties
-  float ts[K];
-  int tr[K];
+  // this lane's KL best tiles so far as (best score, first row), sorted by score; split forms: this half's KL ranks of the pair's list
+  constexpr bool kSplit = wide_split<K>();
+  constexpr int KL = wide_lane_slots<K>();
+  float ts[KL];
+  int tr[KL];
 #pragma unroll
-  for (int j = 0; j < K; ++j) { ts[j] = kNegInf; tr[j] = -1; }
+  for (int j = 0; j < KL; ++j) { ts[j] = kNegInf; tr[j] = -1; }
 
-  float px = kNegInf;   // pending candidate of this lane (see the loop)
+  float px = kNegInf;   // pending candidate of this lane (parity forms; see the loop)
   int pr = -1;
   // insert into the sorted list: one compare-exchange per slot, the loser moves on
   auto insert = [&](float x, int xr) {
 #pragma unroll
-    for (int j = 0; j < K; ++j) {
+    for (int j = 0; j < KL; ++j) {
       const bool c = x > ts[j];
       const float s_old = ts[j];
       const int r_old = tr[j];
@@ -224,6 +251,21 @@ __global__ __launch_bounds__(NW * 64, 2) void scan_wide_kernel(const ScanArgs a)
       tr[j] = c ? xr : r_old;
       x = c ? s_old : x;
       xr = c ? r_old : xr;
+    }
+  };
+
+  // split forms: (v, vr) goes in front of the first slot that x does NOT beat, and every slot x beats moves down one place (v is x
+  // itself, or in the upper half the slot the lower half pushes out, which x beats too); the compares do not depend on each other
+  auto insert_shift = [&](float x, float v, int vr) {
+#pragma unroll
+    for (int j = 0; j < KL; ++j) {   // (v, vr) is what moves into the next slot x beats: the new entry, then each slot's old content
+      const bool c = x > ts[j];
+      const float s_old = ts[j];
+      const int r_old = tr[j];
+      ts[j] = c ? v : s_old;
+      tr[j] = c ? vr : r_old;
+      v = c ? s_old : v;
+      vr = c ? r_old : vr;
     }
   };
 
@@ -236,7 +278,8 @@ __global__ __launch_bounds__(NW * 64, 2) void scan_wide_kernel(const ScanArgs a)
   // both in the VALU selection with the matrix pipe idle -- measured 3.7 k cycles per tile against 1.5 k
   // of MFMA work.  So waves 4..7 defer the selection of a tile by one iteration (its 16 accumulators stay
   // in registers across the barrier): on every SIMD one wave multiplies while the other selects.
-  const bool late = wide_stagger<D, NW, K>() && wave >= 4;   // wave-uniform; off where the deferred accumulators would spill
+  // (split forms: CRS_WIDE_STAGGER=0 arrives as a.no_stagger, a kernel argument -- A/B runs; the lists do not depend on it)
+  const bool late = wide_stagger<D, NW, K>() && wave >= 4 && !(kSplit && a.no_stagger);   // wave-uniform; off where the deferred accumulators would spill
   struct Acc { f32x16 a[RB]; };
   Acc acc_prev;
 #pragma unroll
@@ -282,11 +325,19 @@ __global__ __launch_bounds__(NW * 64, 2) void scan_wide_kernel(const ScanArgs a)
       }
     }
     x = pair_max(x);                              // both halves: the tile's best
-    if ((ie & 1) == h) { px = x; pr = te * WTR; } // lane half h is responsible for the tiles of parity h
-    if (ie & 1) {
-      insert(px, pr);
-      px = kNegInf;
-      pr = -1;
+    if constexpr (kSplit) {
+      // the lower half's last slot as it stands, in the upper half's lanes (low-half broadcast of v_permlane32_swap)
+      const float ps = __uint_as_float(__builtin_amdgcn_permlane32_swap(__float_as_uint(ts[KL - 1]), __float_as_uint(ts[KL - 1]), false, false)[0]);
+      const int prow = (int)__builtin_amdgcn_permlane32_swap((unsigned)tr[KL - 1], (unsigned)tr[KL - 1], false, false)[0];
+      const bool c = h && x > ps;                 // upper half: what the lower half pushes out -- its old last slot, or x itself
+      insert_shift(x, c ? ps : x, c ? prow : te * WTR);
+    } else {
+      if ((ie & 1) == h) { px = x; pr = te * WTR; } // lane half h is responsible for the tiles of parity h
+      if (ie & 1) {
+        insert(px, pr);
+        px = kNegInf;
+        pr = -1;
+      }
     }
   };
 
@@ -346,13 +397,26 @@ __global__ __launch_bounds__(NW * 64, 2) void scan_wide_kernel(const ScanArgs a)
   }
 
   if (wave_active && late && it > 0) select(acc_prev, t_prev, it - 1);   // the deferred last tile
-  if (wave_active && (it & 1)) insert(px, pr);   // odd tile count: the last (even) tile is still pending
-  if (wave_active && q_valid) {   // [nq, nwg, kp = 2 K]: lane half h owns slots h K .. h K + K - 1
-    const size_t o = ((size_t)qi * nwg + stream) * a.kp + (size_t)h * K;
+  if constexpr (kSplit) {
+    if (wave_active && q_valid) {   // [nq, nwg, kp = 2 K]: ranks h KL .. h KL + KL - 1 of the pair's list, then K empty slots
+      const size_t o = ((size_t)qi * nwg + stream) * a.kp + (size_t)h * KL;
 #pragma unroll
-    for (int j = 0; j < K; ++j) {
-      a.part_scores[o + j] = ts[j];
-      a.part_rows[o + j] = tr[j];
+      for (int j = 0; j < KL; ++j) {
+        a.part_scores[o + j] = ts[j];
+        a.part_rows[o + j] = tr[j];
+        a.part_scores[o + K + j] = kNegInf;
+        a.part_rows[o + K + j] = -1;
+      }
+    }
+  } else {
+    if (wave_active && (it & 1)) insert(px, pr);   // odd tile count: the last (even) tile is still pending
+    if (wave_active && q_valid) {   // [nq, nwg, kp = 2 K]: lane half h owns slots h K .. h K + K - 1
+      const size_t o = ((size_t)qi * nwg + stream) * a.kp + (size_t)h * K;
+#pragma unroll
+      for (int j = 0; j < K; ++j) {
+        a.part_scores[o + j] = ts[j];
+        a.part_rows[o + j] = tr[j];
+      }
     }
   }
   WP_LAP(10);   // final flush
@@ -414,7 +478,11 @@ bool scan_wide_streamed(int k) { return scan_wide_slots(k) > 16; }
 // resident workgroups per CU: the query fragments cost D/4 registers per lane -> two waves per SIMD
 int scan_wide_wg_per_cu(int nw, int pdim) { return nw == 8 ? 1 : 2; }
 
-int scan_launch_wide(const ScanArgs& a, int pdim, int nw, hipStream_t stream) {
+// CRS_WIDE_STAGGER=0: waves 4..7 of the split forms select in step with waves 0..3 (A/B runs).  Read per call.
+int scan_launch_wide(const ScanArgs& a_, int pdim, int nw, hipStream_t stream) {
+  ScanArgs a = a_;
+  const char* se = getenv("CRS_WIDE_STAGGER");
+  a.no_stagger = (se && se[0] == '0') ? 1 : 0;
   switch (pdim) {
     case 128: return launch_wide_d<128>(a, nw, stream);
     case 256: return launch_wide_d<256>(a, nw, stream);

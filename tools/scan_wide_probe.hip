@@ -1,6 +1,8 @@
 // scan_wide_probe.hip -- diagnostic build of scan_wide.hip with per-wave s_memtime accumulators.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -o scan_wide_probe scan_wide_probe.hip
 //   ./scan_wide_probe <rows> <dim> <nq> <k>
+// The 24- / 32-slot forms run as the product launches them: nt stream for slabs of 1 GB and more, ticketed tile schedule on long
+// streams (85 % of the tiles in granules of 8; CRS_WIDE_DYN=0: static stride), CRS_WIDE_STAGGER as in the library.
 #define CRS_STAMPS 1
 #include "../compressed-rag-suite_amd/csrc/scan_wide.hip"
 
@@ -23,26 +25,44 @@ int main(int argc, char** argv) {
   int nwg = prop.multiProcessorCount * crs::scan_wide_wg_per_cu(nw, dim) / nqb;
   if (nqb > 1) nwg &= ~7;
   nwg = std::min(nwg, n_tiles);
-  std::vector<_Float16> h((size_t)rows * dim), hq((size_t)nq * dim);
+  // (the selection is branch-free: the laps do not depend on the data, so the host fills at most 1 M rows and the slab repeats them)
+  const size_t gen_rows = std::min<size_t>((size_t)rows, (size_t)1 << 20);
+  std::vector<_Float16> h(gen_rows * dim), hq((size_t)nq * dim);
   unsigned s = 12345;
   auto rnd = [&]() { s = s * 1664525u + 1013904223u; float u = 0; for (int i = 0; i < 4; ++i) { s = s * 1664525u + 1013904223u; u += ((s >> 8) & 0xffff) / 65536.0f - 0.5f; } return u; };
   const float sc = 1.0f / sqrtf((float)dim / 3.0f);
   for (auto& x : h) x = (_Float16)(rnd() * sc);
   for (auto& x : hq) x = (_Float16)(rnd() * sc);
   _Float16 *slab, *q; float* ps; int* pr; unsigned long long* st;
-  hipMalloc(&slab, h.size() * 2); hipMalloc(&q, hq.size() * 2);
-  hipMalloc(&ps, (size_t)nwg * nq * 32 * 4); hipMalloc(&pr, (size_t)nwg * nq * 32 * 4);
+  const int kp = 2 * crs::scan_wide_slots(k);
+  hipMalloc(&slab, (size_t)rows * dim * 2); hipMalloc(&q, hq.size() * 2);
+  hipMalloc(&ps, (size_t)nwg * nq * kp * 4); hipMalloc(&pr, (size_t)nwg * nq * kp * 4);
   const size_t nst = (size_t)nwg * nqb * nw * 12;
   hipMalloc(&st, nst * 8);
-  hipMemcpy(slab, h.data(), h.size() * 2, hipMemcpyHostToDevice);
+  for (size_t r0 = 0; r0 < (size_t)rows; r0 += gen_rows)
+    hipMemcpy(slab + r0 * dim, h.data(), std::min(gen_rows, (size_t)rows - r0) * dim * 2, hipMemcpyHostToDevice);
   hipMemcpy(q, hq.data(), hq.size() * 2, hipMemcpyHostToDevice);
   crs::ScanArgs a{};
   a.q = q; a.slab = slab; a.part_scores = ps; a.part_rows = pr; a.stamps = st;
-  a.n_rows = rows; a.n_tiles = n_tiles; a.nq = nq; a.k = k; a.kp = 2 * crs::scan_wide_slots(k); a.nwg = nwg; a.nqb = nqb; a.sched = 2;
+  a.n_rows = rows; a.n_tiles = n_tiles; a.nq = nq; a.k = k; a.kp = kp; a.nwg = nwg; a.nqb = nqb; a.sched = 2;
+  a.t_dyn = n_tiles;
+  unsigned* ticket = nullptr;
+  if (crs::scan_wide_streamed(k)) {   // the plan fields of capi.hip's make_plan / run_scan
+    a.nt = ((size_t)rows * dim * 2 >= ((size_t)1 << 30) && nqb == 1) ? 1 : 0;
+    const char* de = getenv("CRS_WIDE_DYN");
+    const int rounds = n_tiles / nwg;
+    if (!(de && de[0] == '0') && nqb == 1 && rounds >= 96) {
+      int stat = (int)((long long)rounds * 15 / 100);
+      if (stat < 2) stat = 2;
+      hipMalloc(&ticket, 256);
+      a.t_dyn = stat * nwg; a.ticket = ticket; a.dyn_mask = 7;
+    }
+  }
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
   float ms = 0;
   for (int rep = 0; rep < 4; ++rep) {
     hipMemset(st, 0, nst * 8);
+    if (ticket) hipMemset(ticket, 0, 4);
     hipEventRecord(e0, 0);
     int e = crs::scan_launch_wide(a, dim, nw, 0);
     hipEventRecord(e1, 0);
@@ -52,17 +72,26 @@ int main(int argc, char** argv) {
   }
   std::vector<unsigned long long> hs(nst);
   hipMemcpy(hs.data(), st, nst * 8, hipMemcpyDeviceToHost);
-  printf("rows %d dim %d nq %d k %d | waves/wg %d nqb %d streams %d tiles/stream %.1f | kernel %.1f us (with stamps)\n", rows, dim, nq, k, nw, nqb, nwg,
-         (double)n_tiles / nwg, ms * 1e3);
+  const char* se = getenv("CRS_WIDE_STAGGER");
+  printf("rows %d dim %d nq %d k %d | waves/wg %d nqb %d streams %d tiles/stream %.1f nt %d tickets %s stagger-knob %s | kernel %.1f us (with stamps)\n", rows, dim, nq,
+         k, nw, nqb, nwg, (double)n_tiles / nwg, a.nt, ticket ? "on" : "off", (se && se[0] == '0') ? "0" : "default", ms * 1e3);
   // slots 2 / 4: the selection of waves 4..7 (deferred one tile) / of waves 0..3; 5, 8, 9: unused since the tile-best rewrite
   const char* names[12] = {"prologue", "tile-load issue", "selection (waves 4-7, deferred)", "MFMA sweep", "selection (waves 0-3)", "(unused)",
                            "wait next tile + LDS store", "barrier", "(unused)", "(unused)", "final flush", "TOTAL"};
   const size_t nwaves = nst / 12;
+  // cycles per wave over the launch, and per tile of the wave's stream (mean); waves 0..3 and 4..7 of a workgroup apart
+  const double tps = (double)n_tiles / nwg;
   for (int i = 0; i < 12; ++i) {
-    std::vector<double> v; for (size_t w = 0; w < nwaves; ++w) v.push_back((double)hs[w * 12 + i]);
+    std::vector<double> v; double half[2] = {0, 0}; size_t nh[2] = {0, 0};
+    for (size_t w = 0; w < nwaves; ++w) {
+      v.push_back((double)hs[w * 12 + i]);
+      const int g = (nw == 8 && (w % nw) >= 4) ? 1 : 0;
+      half[g] += (double)hs[w * 12 + i]; ++nh[g];
+    }
     std::sort(v.begin(), v.end());
     double sum = 0; for (double x : v) sum += x;
-    printf("  %-28s mean %9.0f  median %9.0f  max %9.0f\n", names[i], sum / nwaves, v[nwaves / 2], v.back());
+    printf("  %-31s mean %9.0f  median %9.0f  max %9.0f | per tile: waves 0-3 %7.0f  waves 4-7 %7.0f\n", names[i], sum / nwaves, v[nwaves / 2], v.back(),
+           half[0] / (nh[0] ? nh[0] : 1) / tps, half[1] / (nh[1] ? nh[1] : 1) / tps);
   }
   return 0;
 }
