@@ -1,0 +1,269 @@
+// bm25.hip -- exact, flat, doc-at-a-time BM25 top-k over the token CSR of a collection (gfx950): crs_bm25_topk.
+//
+// The lexical twin of the dense scan: every row is streamed once, the top-k of each query is selected in the kernel, the
+// per-workgroup lists are joined by merge.hip.  What is streamed is the token CSR rag/indexing.py keeps beside the sidecars
+// (SlabCollection._token_csr: per row the ascending distinct token ids, their term frequencies, the row's length).
+//
+// Arithmetic (fp32, every operation rounded on its own: the file is compiled with fp contraction off and the division is the
+// correctly rounded one), for a row d and a query q, over the tokens t both hold, in ascending token id:
+//     dn    = c0 + c1 * (float)len_d
+//     num   = (float)tf * k1p1;   den = (float)tf + dn;   term = (w_t * num) / den
+//     score = (((0 + term_1) + term_2) + ...)
+// w_t, c0, c1, k1p1 arrive as fp32, rounded once by the host from fp64.  A row with no token in common with the query is no hit
+// and never enters a list, whatever its score would round to.
+//
+// Two kernels and the merge:
+//   bm25_pairs_kernel  one workgroup: the <= CRS_BM25_MAX_PAIRS (query, token) pairs of the launch, sorted by (token, query) with
+//                      a bitonic network in LDS, written to the workspace as three parallel arrays (token, weight, query).
+//   bm25_scan_kernel   one wave per workgroup; a workgroup owns a contiguous range of 64-row tiles.  The pair table sits in LDS.
+//                      Lane d owns row d of the tile: the tile's token segment is contiguous in the CSR and is staged into LDS in
+//                      fixed chunks with coalesced loads (a row longer than a chunk simply spans several rounds of the loop); the
+//                      lane walks its row's part of the chunk, binary-searches the pair table, and on a match reads the row's tf
+//                      and adds the term into acc[q * 64 + d] -- column d is touched by lane d alone, on bank d.  After a tile,
+//                      for every query some lane hit, the lanes that beat the query's current k-th are inserted, in row order,
+//                      into the query's sorted list (held one slot per lane while it is updated, kept in LDS between tiles).  Rows
+//                      only ascend inside a workgroup, so an equal score never displaces an earlier row: ties by lower row.
+//   merge.hip          joins the [n_workgroups, nq, k] lists (score descending, row ascending; slots with id < 0 ignored).
+//
+// Every CSR offset is clamped into its array before it becomes an address; the queries of the pair table are < nq by
+// construction; a malformed CSR or query table can give wrong scores, never an access outside the buffers.  No atomics, no
+// scratch, no workgroup waits on another.
+#include "../../include/crs_hip.h"
+
+#include <hip/hip_runtime.h>
+
+#include "scan.h"
+
+#pragma clang fp contract(off)
+
+namespace crs {
+namespace {
+
+constexpr int kLanes = 64;                     // rows per tile: one lane per row
+constexpr int kMaxPairs = CRS_BM25_MAX_PAIRS;  // (query, token) pairs per launch
+constexpr int kChunk = 2048;                   // tokens staged per round
+constexpr int kMinTiles = 4;                   // tiles per workgroup at least (short collections: fewer lists to merge)
+constexpr int kMaxWg = 2048;                   // workgroups at most
+constexpr int kSortThreads = 256;
+constexpr unsigned long long kNoPair = ~0ull;
+constexpr float kNegInf = -__builtin_huge_valf();
+static_assert((kMaxPairs & (kMaxPairs - 1)) == 0 && kMaxPairs <= 4096, "pair index fits the 12 low bits of a sort key");
+static_assert(CRS_MAX_K <= kLanes, "one lane per list slot");
+
+__device__ __forceinline__ int64_t clamp_i64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// ---- the pair table: (token, query, weight) sorted by token, then query ----------------------------------------------------------
+// Pair p IS entry p of q_tok / q_w (n_pairs = their length <= kMaxPairs); its query is the one whose clamped offsets hold p.  An
+// entry no query holds sorts last as (0xffffffff, query 0, weight 0).
+__global__ __launch_bounds__(kSortThreads) void bm25_pairs_kernel(const int64_t* __restrict__ q_off, const int* __restrict__ q_tok,
+                                                                 const float* __restrict__ q_w, int nq, int n_pairs,
+                                                                 unsigned* __restrict__ pt_tok, float* __restrict__ pt_w,
+                                                                 int* __restrict__ pt_q) {
+  __shared__ unsigned long long key[kMaxPairs];
+  __shared__ int off[kLanes + 1];
+  const int tid = threadIdx.x;
+  for (int q = tid; q <= nq; q += kSortThreads) off[q] = (int)clamp_i64(q_off[q], 0, n_pairs);
+  __syncthreads();
+  int n2 = 1;
+  while (n2 < n_pairs) n2 <<= 1;
+  for (int p = tid; p < n2; p += kSortThreads) {
+    unsigned long long kk = kNoPair;
+    if (p < n_pairs) {
+      int lo = 0, hi = nq;                     // the last q in [0, nq) with off[q] <= p
+      while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (off[mid] <= p) lo = mid; else hi = mid;
+      }
+      if (off[lo] <= p && p < off[lo + 1]) kk = ((unsigned long long)(unsigned)q_tok[p] << 12) | (unsigned)p;
+    }
+    key[p] = kk;
+  }
+  __syncthreads();
+  for (int size = 2; size <= n2; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int i = tid; i < (n2 >> 1); i += kSortThreads) {
+        const int a = ((i & ~(stride - 1)) << 1) | (i & (stride - 1)), b = a | stride;
+        const bool up = (a & size) == 0;
+        const unsigned long long x = key[a], y = key[b];
+        if ((x > y) == up) { key[a] = y; key[b] = x; }
+      }
+      __syncthreads();
+    }
+  }
+  for (int i = tid; i < n_pairs; i += kSortThreads) {
+    const unsigned long long kk = key[i];
+    if (kk == kNoPair) {
+      pt_tok[i] = 0xffffffffu; pt_w[i] = 0.0f; pt_q[i] = 0;
+    } else {
+      const int p = (int)(kk & 4095ull);
+      int lo = 0, hi = nq;
+      while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (off[mid] <= p) lo = mid; else hi = mid;
+      }
+      pt_tok[i] = (unsigned)(kk >> 12); pt_w[i] = q_w[p]; pt_q[i] = lo;
+    }
+  }
+}
+
+// ---- the scan --------------------------------------------------------------------------------------------------------------------
+// dynamic LDS: [pair tokens u32 [n_pairs] | pair weights f32 [n_pairs] | acc f32 [nq, 64] | list scores f32 [nq, k] |
+//               list rows i32 [nq, k] | staged tokens u32 [kChunk] | pair queries u8 [n_pairs]]
+__host__ __device__ inline size_t bm25_lds_bytes(int nq, int k, int n_pairs) {
+  return (size_t)n_pairs * 8 + (size_t)nq * kLanes * 4 + (size_t)nq * k * 8 + (size_t)kChunk * 4 + (((size_t)n_pairs + 3) & ~(size_t)3);
+}
+
+__global__ __launch_bounds__(kLanes) void bm25_scan_kernel(const int64_t* __restrict__ doc_off, const int* __restrict__ doc_tok,
+                                                          const int* __restrict__ doc_tf, const int* __restrict__ doc_len, int n_rows,
+                                                          int64_t n_doc_tok, const unsigned* __restrict__ pt_tok,
+                                                          const float* __restrict__ pt_w, const int* __restrict__ pt_q, int n_pairs,
+                                                          int nq, float c0, float c1, float k1p1, int k, int tiles_per_wg,
+                                                          float* __restrict__ part_s, int64_t* __restrict__ part_i) {
+  extern __shared__ __attribute__((aligned(16))) char bm25_smem[];
+  unsigned* s_tok = reinterpret_cast<unsigned*>(bm25_smem);
+  float* s_w = reinterpret_cast<float*>(s_tok + n_pairs);
+  float* acc = s_w + n_pairs;
+  float* ls_s = acc + (size_t)nq * kLanes;
+  int* ls_r = reinterpret_cast<int*>(ls_s + (size_t)nq * k);
+  unsigned* stage = reinterpret_cast<unsigned*>(ls_r + (size_t)nq * k);
+  unsigned char* s_q = reinterpret_cast<unsigned char*>(stage + kChunk);
+
+  const int lane = threadIdx.x;
+  for (int i = lane; i < n_pairs; i += kLanes) { s_tok[i] = pt_tok[i]; s_w[i] = pt_w[i]; s_q[i] = (unsigned char)pt_q[i]; }
+  for (int i = lane; i < nq * k; i += kLanes) { ls_s[i] = kNegInf; ls_r[i] = -1; }
+  __syncthreads();
+
+  const int n_tiles = (n_rows + kLanes - 1) / kLanes;
+  const int tile0 = blockIdx.x * tiles_per_wg;
+  const int tile1 = (n_tiles - tile0 < tiles_per_wg) ? n_tiles : tile0 + tiles_per_wg;
+  for (int tile = tile0; tile < tile1 && n_pairs > 0; ++tile) {
+    const int row = tile * kLanes + lane;
+    const bool live = row < n_rows;
+    int64_t lo = 0, hi = 0;
+    float dn = c0;
+    if (live) {
+      lo = clamp_i64(doc_off[row], 0, n_doc_tok);
+      hi = clamp_i64(doc_off[row + 1], lo, n_doc_tok);
+      const float scaled = c1 * (float)doc_len[row];
+      dn = c0 + scaled;
+    }
+    // the tile's segment of the token array: [smallest lo, largest hi) over the rows that hold tokens
+    int64_t seg_lo = lo < hi ? lo : n_doc_tok, seg_hi = lo < hi ? hi : 0;
+    for (int s = 32; s > 0; s >>= 1) {
+      const int64_t a = __shfl_xor(seg_lo, s), b = __shfl_xor(seg_hi, s);
+      seg_lo = a < seg_lo ? a : seg_lo;
+      seg_hi = b > seg_hi ? b : seg_hi;
+    }
+    if (seg_lo >= seg_hi) continue;                    // (uniform) a tile of empty rows
+    for (int q = 0; q < nq; ++q) acc[q * kLanes + lane] = 0.0f;
+    unsigned long long mine = 0ull;                    // the queries this row hit
+    for (int64_t base = seg_lo; base < seg_hi; base += kChunk) {
+      const int n = (int)(seg_hi - base < kChunk ? seg_hi - base : kChunk);
+      __syncthreads();                                 // the previous chunk has been read
+      for (int i = lane; i < n; i += kLanes) stage[i] = (unsigned)doc_tok[base + i];
+      __syncthreads();
+      const int64_t a = lo > base ? lo : base, b = hi < base + n ? hi : base + n;
+      for (int64_t t = a; t < b; ++t) {
+        const unsigned tok = stage[t - base];
+        int i = 0, j = n_pairs;
+        while (i < j) {
+          const int mid = (i + j) >> 1;
+          if (s_tok[mid] < tok) i = mid + 1; else j = mid;
+        }
+        if (i < n_pairs && s_tok[i] == tok) {
+          const float tf = (float)doc_tf[t];
+          const float num = tf * k1p1, den = tf + dn;
+          do {
+            const int q = s_q[i];
+            const float prod = s_w[i] * num;
+            const float term = prod / den;
+            acc[q * kLanes + lane] = acc[q * kLanes + lane] + term;
+            mine |= 1ull << q;
+            ++i;
+          } while (i < n_pairs && s_tok[i] == tok);
+        }
+      }
+    }
+    // ---- selection: the rows of this tile that enter a query's list, in row order ----
+    for (int q = 0; q < nq; ++q) {
+      const bool hit = (mine >> q) & 1ull;
+      if (!__ballot(hit)) continue;                    // (uniform)
+      const float s = acc[q * kLanes + lane];
+      float my_s = lane < k ? ls_s[q * k + lane] : kNegInf;     // slot `lane` of the query's list
+      int my_r = lane < k ? ls_r[q * k + lane] : -1;
+      float kth_s = __shfl(my_s, k - 1);
+      int kth_r = __shfl(my_r, k - 1);
+      unsigned long long todo = __ballot(hit && (kth_r < 0 || s > kth_s));
+      bool changed = false;
+      while (todo) {
+        const int src = __ffsll((long long)todo) - 1;
+        todo &= todo - 1ull;
+        const float cs = __shfl(s, src);
+        if (!(kth_r < 0 || cs > kth_s)) continue;
+        const int pos = __popcll(__ballot(lane < k && my_r >= 0 && my_s >= cs));   // entries that stay ahead: an equal score is an earlier row
+        const float up_s = __shfl_up(my_s, 1);
+        const int up_r = __shfl_up(my_r, 1);
+        if (pos >= k) continue;
+        if (lane == pos) { my_s = cs; my_r = tile * kLanes + src; }
+        else if (lane > pos && lane < k) { my_s = up_s; my_r = up_r; }
+        kth_s = __shfl(my_s, k - 1);
+        kth_r = __shfl(my_r, k - 1);
+        changed = true;
+      }
+      if (changed && lane < k) { ls_s[q * k + lane] = my_s; ls_r[q * k + lane] = my_r; }
+    }
+  }
+  __syncthreads();
+  const size_t out0 = (size_t)blockIdx.x * nq * k;
+  for (int i = lane; i < nq * k; i += kLanes) { part_s[out0 + i] = ls_s[i]; part_i[out0 + i] = (int64_t)ls_r[i]; }
+}
+
+}  // namespace
+
+// geometry of a launch: workgroups and tiles per workgroup for n_rows rows
+static void bm25_plan(int64_t n_rows, int* n_wg, int* tiles_per_wg) {
+  const int64_t n_tiles = (n_rows + kLanes - 1) / kLanes;
+  int64_t per = (n_tiles + kMaxWg - 1) / kMaxWg;
+  if (per < kMinTiles) per = kMinTiles;
+  *tiles_per_wg = (int)per;
+  *n_wg = (int)((n_tiles + per - 1) / per);
+  if (*n_wg < 1) *n_wg = 1;
+}
+
+static size_t bm25_align(size_t x) { return (x + 255) / 256 * 256; }
+
+// workspace: [pair tokens | pair weights | pair queries (kMaxPairs each) | partial scores f32 [n_wg, nq, k] | partial rows i64 [n_wg, nq, k]]
+size_t bm25_workspace_bytes(int nq, int k, int64_t n_rows) {
+  int n_wg, per;
+  bm25_plan(n_rows, &n_wg, &per);
+  const size_t cells = (size_t)n_wg * nq * k;
+  return 3 * bm25_align((size_t)kMaxPairs * 4) + bm25_align(cells * 4) + bm25_align(cells * 8);
+}
+
+int bm25_topk_launch(const int64_t* doc_off, const int* doc_tok, const int* doc_tf, const int* doc_len, int64_t n_rows, int64_t n_doc_tok,
+                     const int64_t* q_off, const int* q_tok, const float* q_w, int nq, int n_pairs, float c0, float c1, float k1p1, int k,
+                     void* workspace, float* out_s, int64_t* out_i, hipStream_t stream) {
+  int n_wg, per;
+  bm25_plan(n_rows, &n_wg, &per);
+  const size_t cells = (size_t)n_wg * nq * k;
+  char* w = reinterpret_cast<char*>(workspace);
+  unsigned* pt_tok = reinterpret_cast<unsigned*>(w);
+  float* pt_w = reinterpret_cast<float*>(w + bm25_align((size_t)kMaxPairs * 4));
+  int* pt_q = reinterpret_cast<int*>(w + 2 * bm25_align((size_t)kMaxPairs * 4));
+  float* part_s = reinterpret_cast<float*>(w + 3 * bm25_align((size_t)kMaxPairs * 4));
+  int64_t* part_i = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(part_s) + bm25_align(cells * 4));
+  if (n_pairs > 0)
+    hipLaunchKernelGGL(bm25_pairs_kernel, dim3(1), dim3(kSortThreads), 0, stream, q_off, q_tok, q_w, nq, n_pairs, pt_tok, pt_w, pt_q);
+  const size_t lds = bm25_lds_bytes(nq, k, n_pairs);
+  if (lds > 48 * 1024) {     // beyond the default dynamic-LDS limit (at most ~100 KiB of the CU's 160: 4096 pairs, 64 queries, k = 64)
+    const hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void*>(&bm25_scan_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (ae != hipSuccess) return (int)ae;
+  }
+  hipLaunchKernelGGL(bm25_scan_kernel, dim3((unsigned)n_wg), dim3(kLanes), lds, stream, doc_off, doc_tok, doc_tf, doc_len, (int)n_rows,
+                     n_doc_tok, pt_tok, pt_w, pt_q, n_pairs, nq, c0, c1, k1p1, k, per, part_s, part_i);
+  const int e = (int)hipGetLastError();
+  if (e) return e;
+  return merge_launch_i64(part_s, part_i, n_wg, nq, k, k, out_s, out_i, stream);
+}
+
+}  // namespace crs

@@ -447,6 +447,54 @@ int crs_rerank_lexical(const float* scores_dev, const int64_t* rows_dev, int nq,
   return e ? hip_fail((hipError_t)e, "rerank_lexical launch") : CRS_OK;
 }
 
+static const char* bm25_sizes_bad(int nq, int k, int64_t n_rows) {
+  if (nq < 1 || nq > 64) return "bad nq (1 <= nq <= 64)";
+  if (k < 1 || k > CRS_MAX_K) return "bad k (1 <= k <= CRS_MAX_K)";
+  if (n_rows < 0 || n_rows >= 0x7fffffffll - 64) return "bad n_rows (0 <= n_rows < 2^31 - 64)";
+  return nullptr;
+}
+
+int crs_bm25_workspace_bytes(int nq, int k, int64_t n_rows, size_t* bytes) {
+  if (!bytes) return fail(CRS_EINVAL, "null pointer");
+  if (const char* bad = bm25_sizes_bad(nq, k, n_rows)) return fail(CRS_EINVAL, "%s", bad);
+  *bytes = crs::bm25_workspace_bytes(nq, k, n_rows);
+  return CRS_OK;
+}
+
+int crs_bm25_topk(const int64_t* doc_offsets_dev, const int32_t* doc_tokens_dev, const int32_t* doc_tf_dev, const int32_t* doc_len_dev,
+                  int64_t n_rows, int64_t n_doc_tokens, const int64_t* q_offsets_dev, const int32_t* q_tokens_dev,
+                  const float* q_weights_dev, int nq, int64_t n_q_tokens, float c0, float c1, float k1p1, int k, void* workspace_dev,
+                  size_t workspace_bytes, float* out_scores_dev, int64_t* out_rows_dev, void* stream) {
+  if (const char* bad = bm25_sizes_bad(nq, k, n_rows)) return fail(CRS_EINVAL, "%s", bad);
+  if (n_doc_tokens < 0) return fail(CRS_EINVAL, "bad n_doc_tokens");
+  if (n_q_tokens < 0 || n_q_tokens > CRS_BM25_MAX_PAIRS) return fail(CRS_EINVAL, "bad n_q_tokens (0 <= n_q_tokens <= CRS_BM25_MAX_PAIRS)");
+  if (!doc_offsets_dev || !q_offsets_dev || !out_scores_dev || !out_rows_dev || (n_rows > 0 && !doc_len_dev) ||
+      (n_doc_tokens > 0 && (!doc_tokens_dev || !doc_tf_dev)) || (n_q_tokens > 0 && (!q_tokens_dev || !q_weights_dev)))
+    return fail(CRS_EINVAL, "null pointer");
+  if (!workspace_dev || ((uintptr_t)workspace_dev & 255)) return fail(CRS_EINVAL, "workspace must be a 256-byte aligned device pointer");
+  if (workspace_bytes < crs::bm25_workspace_bytes(nq, k, n_rows)) return fail(CRS_ENOSPC, "workspace smaller than crs_bm25_workspace_bytes");
+  const int e = crs::bm25_topk_launch(doc_offsets_dev, doc_tokens_dev, doc_tf_dev, doc_len_dev, n_rows, n_doc_tokens, q_offsets_dev,
+                                      q_tokens_dev, q_weights_dev, nq, (int)n_q_tokens, c0, c1, k1p1, k, workspace_dev, out_scores_dev,
+                                      out_rows_dev, (hipStream_t)stream);
+  return e ? hip_fail((hipError_t)e, "bm25_topk launch") : CRS_OK;
+}
+
+int crs_fuse_rrf(const int64_t* dense_rows_dev, int m_dense, const int64_t* lex_rows_dev, int m_lex, int nq, double c, double w_dense,
+                 double w_lex, int k_out, int64_t* rows_dev, double* fused_dev, int32_t* dense_pos_dev, int32_t* lex_pos_dev,
+                 int32_t* count_dev, void* stream) {
+  if (nq < 0) return fail(CRS_EINVAL, "bad nq");
+  if (m_dense < 1 || m_dense > CRS_MAX_K || m_lex < 1 || m_lex > CRS_MAX_K) return fail(CRS_EINVAL, "bad m_dense / m_lex (1 <= m <= CRS_MAX_K)");
+  if (k_out < 1 || k_out > 2 * CRS_MAX_K) return fail(CRS_EINVAL, "bad k_out (1 <= k_out <= 2 CRS_MAX_K)");
+  if (!(c >= 0.0) || !(c <= 1e300)) return fail(CRS_EINVAL, "c must be finite and >= 0");
+  if (!(w_dense >= 0.0 && w_dense <= 1e300 && w_lex >= 0.0 && w_lex <= 1e300)) return fail(CRS_EINVAL, "weights must be finite and >= 0");
+  if (!dense_rows_dev || !lex_rows_dev || !rows_dev || !fused_dev || !dense_pos_dev || !lex_pos_dev || !count_dev)
+    return fail(CRS_EINVAL, "null pointer");
+  if (nq == 0) return CRS_OK;
+  const int e = crs::fuse_rrf_launch(dense_rows_dev, m_dense, lex_rows_dev, m_lex, nq, c, w_dense, w_lex, k_out, rows_dev, fused_dev,
+                                     dense_pos_dev, lex_pos_dev, count_dev, (hipStream_t)stream);
+  return e ? hip_fail((hipError_t)e, "fuse_rrf launch") : CRS_OK;
+}
+
 int crs_rescore_f32(const float* q32_dev, int nq, int dim, const float* shadow_dev, int64_t n_rows,
                     int64_t id_base, int k, float* scores_dev, int64_t* ids_dev, void* stream) {
   if (nq <= 0 || dim <= 0 || k <= 0 || k > 64 || n_rows <= 0) return fail(CRS_EINVAL, "bad sizes (k <= 64)");

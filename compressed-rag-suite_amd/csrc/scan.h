@@ -100,6 +100,16 @@ int rerank_lexical_launch(const float* scores, const int64_t* rows, int nq, int 
                           int64_t n_rows, int64_t n_doc_tok, const int64_t* q_off, const int* q_tok, int64_t n_q_tok, const int* q_norm,
                           int k, double threshold, int* order, int* out_count, double* sim, double* rr, int* reranked, hipStream_t stream);
 
+// bm25.hip: exact BM25 top-k of <= 64 queries over the token CSR: pair table, scan (one wave per workgroup), merge
+size_t bm25_workspace_bytes(int nq, int k, int64_t n_rows);
+int bm25_topk_launch(const int64_t* doc_off, const int* doc_tok, const int* doc_tf, const int* doc_len, int64_t n_rows, int64_t n_doc_tok,
+                     const int64_t* q_off, const int* q_tok, const float* q_w, int nq, int n_pairs, float c0, float c1, float k1p1, int k,
+                     void* workspace, float* out_s, int64_t* out_i, hipStream_t stream);
+
+// fuse.hip: reciprocal rank fusion of a dense and a lexical list of <= CRS_MAX_K rows each, one wave per query
+int fuse_rrf_launch(const int64_t* dense, int m_dense, const int64_t* lex, int m_lex, int nq, double c, double w_dense, double w_lex,
+                    int k_out, int64_t* out_rows, double* out_fused, int* out_dpos, int* out_lpos, int* out_count, hipStream_t stream);
+
 // token_match.hip: BERTScore's greedy matching of pairs of token-state matrices, one workgroup per pair
 int token_match_launch(const float* a, const int* len_a, int seq_a, const float* b, const int* len_b, int seq_b, int n_pairs, int hidden,
                        const float* w_a, const float* w_b, float* out, hipStream_t stream);

@@ -18,6 +18,7 @@
 //   crs::merge_sorted / crs::merge_sorted_wire   the same for sorted lists, k 65 .. 1024
 //   crs::mmr_order         replaces the greedy MMR loop of _apply_diversity  (reference rag/retrieval.py:219-277)
 //   crs::token_match       the greedy matching behind bert_score.score  (reference evaluation/retrieval/rag_metrics.py:179-207)
+//   crs::bm25_topk / crs::fuse_rrf   hybrid retrieval: exact BM25 scan over the token CSR, reciprocal rank fusion (new vs the reference)
 //   crs::rerank_lexical    replaces the scoring, threshold and _rerank loops of retrieve_batch  (reference rag/retrieval.py:75-77, 196-217)
 // Tensors are torch-owned; every op launches on the CURRENT HIP stream of the tensors' device, so the ops
 // compose with torch streams and hipGraph capture.  Errors of the C ABI surface as RuntimeError (TORCH_CHECK)
@@ -535,6 +536,66 @@ void rerank_lexical(const Tensor& scores, const Tensor& rows, const Tensor& doc_
      "crs::rerank_lexical");
 }
 
+// ---- hybrid retrieval: BM25 scan (csrc/bm25.hip) and rank fusion (csrc/fuse.hip) ------------------------------------------------------
+// doc_offsets int64 [>= n_rows + 1], doc_tokens / doc_tf int32 (same length), doc_len int32 [>= n_rows]; q_offsets int64 [nq + 1],
+// q_tokens int32 / q_weights fp32 (same length); workspace uint8 (crs_bm25_workspace_bytes); out_scores fp32 / out_rows int64 [nq, k]
+void bm25_topk(const Tensor& doc_offsets, const Tensor& doc_tokens, const Tensor& doc_tf, const Tensor& doc_len, int64_t n_rows,
+               const Tensor& q_offsets, const Tensor& q_tokens, const Tensor& q_weights, double c0, double c1, double k1p1, int64_t k,
+               Tensor workspace, Tensor out_scores, Tensor out_rows) {
+  want(doc_offsets, at::kLong, "doc_offsets");
+  want(doc_tokens, at::kInt, "doc_tokens");
+  want(doc_tf, at::kInt, "doc_tf");
+  want(doc_len, at::kInt, "doc_len");
+  want(q_offsets, at::kLong, "q_offsets");
+  want(q_tokens, at::kInt, "q_tokens");
+  want(q_weights, at::kFloat, "q_weights");
+  want(workspace, at::kByte, "workspace");
+  want(out_scores, at::kFloat, "out_scores");
+  want(out_rows, at::kLong, "out_rows");
+  same_device(doc_offsets, {&doc_tokens, &doc_tf, &doc_len, &q_offsets, &q_tokens, &q_weights, &workspace, &out_scores, &out_rows},
+              "crs::bm25_topk");
+  TORCH_CHECK(n_rows >= 0 && doc_offsets.dim() == 1 && doc_offsets.numel() >= n_rows + 1, "doc_offsets must be int64 [>= n_rows + 1]");
+  TORCH_CHECK(doc_len.dim() == 1 && doc_len.numel() >= n_rows, "doc_len must be int32 [>= n_rows]");
+  TORCH_CHECK(doc_tokens.dim() == 1 && doc_tf.dim() == 1 && doc_tf.numel() == doc_tokens.numel(), "doc_tokens / doc_tf must be int32 of one length");
+  TORCH_CHECK(q_offsets.dim() == 1 && q_offsets.numel() >= 2, "q_offsets must be int64 [nq + 1]");
+  const int64_t nq = q_offsets.numel() - 1;
+  TORCH_CHECK(q_tokens.dim() == 1 && q_weights.dim() == 1 && q_weights.numel() == q_tokens.numel(), "q_tokens / q_weights must be of one length");
+  TORCH_CHECK(nq <= 64 && k >= 1 && k <= CRS_MAX_K, "at most 64 queries per launch, 1 <= k <= 64");
+  TORCH_CHECK(out_scores.numel() == nq * k && out_rows.numel() == nq * k, "outputs must hold [nq, k]");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(doc_offsets.device());
+  ok(crs_bm25_topk(doc_offsets.data_ptr<int64_t>(), doc_tokens.numel() ? doc_tokens.data_ptr<int32_t>() : nullptr,
+                   doc_tf.numel() ? doc_tf.data_ptr<int32_t>() : nullptr, doc_len.numel() ? doc_len.data_ptr<int32_t>() : nullptr, n_rows,
+                   doc_tokens.numel(), q_offsets.data_ptr<int64_t>(), q_tokens.numel() ? q_tokens.data_ptr<int32_t>() : nullptr,
+                   q_weights.numel() ? q_weights.data_ptr<float>() : nullptr, (int)nq, q_tokens.numel(), (float)c0, (float)c1, (float)k1p1,
+                   (int)k, workspace.data_ptr(), (size_t)workspace.numel(), out_scores.data_ptr<float>(), out_rows.data_ptr<int64_t>(),
+                   cur_stream(doc_offsets)), "crs::bm25_topk");
+}
+
+// dense_rows int64 [nq, m_dense], lex_rows int64 [nq, m_lex]; rows int64 / fused fp64 / dense_pos, lex_pos int32 [nq, k_out]; count int32 [nq]
+void fuse_rrf(const Tensor& dense_rows, const Tensor& lex_rows, double c, double w_dense, double w_lex, Tensor rows, Tensor fused,
+              Tensor dense_pos, Tensor lex_pos, Tensor count) {
+  want(dense_rows, at::kLong, "dense_rows");
+  want(lex_rows, at::kLong, "lex_rows");
+  want(rows, at::kLong, "rows");
+  want(fused, at::kDouble, "fused");
+  want(dense_pos, at::kInt, "dense_pos");
+  want(lex_pos, at::kInt, "lex_pos");
+  want(count, at::kInt, "count");
+  same_device(dense_rows, {&lex_rows, &rows, &fused, &dense_pos, &lex_pos, &count}, "crs::fuse_rrf");
+  TORCH_CHECK(dense_rows.dim() == 2 && lex_rows.dim() == 2 && lex_rows.size(0) == dense_rows.size(0), "dense_rows [nq, m_dense], lex_rows [nq, m_lex]");
+  const int64_t nq = dense_rows.size(0);
+  TORCH_CHECK(nq <= 0x7fffffff, "too many lists");
+  TORCH_CHECK(rows.dim() == 2 && rows.size(0) == nq && fused.sizes() == rows.sizes() && dense_pos.sizes() == rows.sizes() &&
+              lex_pos.sizes() == rows.sizes(), "rows / fused / dense_pos / lex_pos must be [nq, k_out]");
+  TORCH_CHECK(count.numel() == nq, "count must be int32 [nq]");
+  TORCH_CHECK(dense_rows.size(1) <= 0x7fffffff && lex_rows.size(1) <= 0x7fffffff && rows.size(1) <= 0x7fffffff, "sizes out of range");
+  if (nq == 0) return;
+  c10::hip::HIPGuardMasqueradingAsCUDA g(dense_rows.device());
+  ok(crs_fuse_rrf(dense_rows.data_ptr<int64_t>(), (int)dense_rows.size(1), lex_rows.data_ptr<int64_t>(), (int)lex_rows.size(1), (int)nq, c,
+                  w_dense, w_lex, (int)rows.size(1), rows.data_ptr<int64_t>(), fused.data_ptr<double>(), dense_pos.data_ptr<int32_t>(),
+                  lex_pos.data_ptr<int32_t>(), count.data_ptr<int32_t>(), cur_stream(dense_rows)), "crs::fuse_rrf");
+}
+
 // ---- encoder -------------------------------------------------------------------------------------------------
 // desc = [vocab_size, hidden, layers, heads, ffn, max_pos, pooling, flags (CRS_ENC_*, optional)]; weights = [word_emb, pos_emb, type_emb, emb_ln_g, emb_ln_b]
 // followed by 12 tensors per layer in crs_encoder_layer order (w_qkv b_qkv w_o b_o ln1_g ln1_b w_up b_up w_down b_down ln2_g ln2_b).
@@ -692,6 +753,10 @@ TORCH_LIBRARY(crs, m) {
   m.def("token_match_out(Tensor a, Tensor len_a, Tensor b, Tensor len_b, Tensor? w_a, Tensor? w_b, Tensor(a!) out) -> ()");
   m.def("rerank_lexical(Tensor scores, Tensor rows, Tensor doc_offsets, Tensor doc_tokens, int n_rows, Tensor q_offsets, Tensor q_tokens, "
         "Tensor q_norm, int k, float threshold, Tensor(a!) order, Tensor(b!) count, Tensor(c!) sim, Tensor(d!) rr, Tensor(e!) reranked) -> ()");
+  m.def("bm25_topk(Tensor doc_offsets, Tensor doc_tokens, Tensor doc_tf, Tensor doc_len, int n_rows, Tensor q_offsets, Tensor q_tokens, "
+        "Tensor q_weights, float c0, float c1, float k1p1, int k, Tensor(a!) workspace, Tensor(b!) out_scores, Tensor(c!) out_rows) -> ()");
+  m.def("fuse_rrf(Tensor dense_rows, Tensor lex_rows, float c, float w_dense, float w_lex, Tensor(a!) rows, Tensor(b!) fused, "
+        "Tensor(c!) dense_pos, Tensor(d!) lex_pos, Tensor(e!) count) -> ()");
   m.def("encoder_forward(Tensor ids, Tensor lens, Tensor[] weights, int[] desc, float ln_eps, Tensor(a!) workspace, Tensor(b!) out, "
         "Tensor(c!)? q16_out, int slab_type, bool normalize, Tensor(d!)? hidden_out) -> ()");
   m.def("encoder_forward_ex(Tensor ids, Tensor lens, Tensor[] weights, int[] desc, float ln_eps, Tensor(a!) workspace, Tensor(b!) out, "
@@ -723,6 +788,8 @@ TORCH_LIBRARY_IMPL(crs, CUDA, m) {   // the HIP backend of torch-ROCm dispatches
   m.impl("mmr_order_out", &mmr_order_out);
   m.impl("token_match_out", &token_match_out);
   m.impl("rerank_lexical", &rerank_lexical);
+  m.impl("bm25_topk", &bm25_topk);
+  m.impl("fuse_rrf", &fuse_rrf);
   m.impl("encoder_forward", &encoder_forward);
   m.impl("encoder_forward_ex", &encoder_forward_ex);
   m.impl("encoder_score_pairs", &encoder_score_pairs);

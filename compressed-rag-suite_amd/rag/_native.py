@@ -25,6 +25,8 @@ MERGE_SORTED_MAX_LISTS = 64   # crs_merge_sorted: lists per query (csrc/merge_so
 LARGE_K_MAX_PARTS = 64     # chunks of the partition (x 64 candidates: at most 4096 per query)
 EXACT_MAX_CAP = 13312      # CRS_EXACT_MAX_CAP: longest per-query row list of crs_escalate_exact
 EXACT_CAP = 1024           # default list length (12 KB of LDS per query in the re-rank)
+BM25_MAX_QUERIES = 64      # queries of one crs_bm25_topk launch
+BM25_MAX_PAIRS = 4096      # CRS_BM25_MAX_PAIRS: (query, known token) pairs of one crs_bm25_topk launch
 
 # name -> (restype, argtypes); mirrors include/crs_hip.h one to one
 _SIGNATURES = {
@@ -51,6 +53,11 @@ _SIGNATURES = {
     "crs_token_match": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "crs_rerank_lexical": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64,
                                    c_void_p, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "crs_bm25_workspace_bytes": (c_int, [c_int, c_int, c_int64, POINTER(c_size_t)]),
+    "crs_bm25_topk": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int64,
+                              c_float, c_float, c_float, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "crs_fuse_rrf": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int, c_void_p,
+                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "crs_rescore_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p,
                                 c_void_p, c_void_p]),
     "crs_score_rows_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
@@ -333,6 +340,54 @@ def rerank_lexical(scores, rows, doc_offsets, doc_tokens, n_rows: int, q_offsets
                torch.empty(nq, dtype=torch.int32, device=dev))
     with _translate():
         ops().rerank_lexical(scores, rows, doc_offsets, doc_tokens, int(n_rows), q_offsets, q_tokens, q_norm, int(k), float(threshold), *out)
+    return out
+
+
+def has_bm25() -> bool:
+    """Whether the loaded libcrs_torch.so carries crs::bm25_topk and crs::fuse_rrf (a library built before csrc/bm25.hip does not)."""
+    return hasattr(ops(), "bm25_topk") and hasattr(ops(), "fuse_rrf")
+
+
+def bm25_workspace_bytes(nq: int, k: int, n_rows: int) -> int:
+    out = c_size_t(0)
+    check(load().crs_bm25_workspace_bytes(int(nq), int(k), int(n_rows), byref(out)))
+    return int(out.value)
+
+
+def bm25_topk(doc_offsets, doc_tokens, doc_tf, doc_len, n_rows: int, q_offsets, q_tokens, q_weights, c0: float, c1: float, k1p1: float,
+              k: int, workspace=None, out_scores=None, out_rows=None):
+    """Exact BM25 top-k of nq <= 64 queries over the token CSR in one launch chain (crs_bm25_topk, csrc/bm25.hip): doc_offsets int64
+    [>= n_rows + 1] / doc_tokens, doc_tf int32 / doc_len int32 [>= n_rows] the rows' tokens, term frequencies and lengths; q_offsets
+    int64 [nq + 1] / q_tokens int32 / q_weights fp32 the queries' ascending distinct known ids and their idf weights (at most
+    BM25_MAX_PAIRS of them); c0, c1, k1p1 already rounded to fp32 -> (scores fp32 [nq, k], rows int64 [nq, k]), best first, ties by
+    lower row, (-inf, -1) past the hits.  All cuda.  No host sync."""
+    import torch
+    nq, dev = q_offsets.shape[0] - 1, doc_offsets.device
+    if workspace is None:
+        workspace = torch.empty(bm25_workspace_bytes(nq, k, n_rows), dtype=torch.uint8, device=dev)
+    if out_scores is None:
+        out_scores = torch.empty((nq, k), dtype=torch.float32, device=dev)
+    if out_rows is None:
+        out_rows = torch.empty((nq, k), dtype=torch.int64, device=dev)
+    with _translate():
+        ops().bm25_topk(doc_offsets, doc_tokens, doc_tf, doc_len, int(n_rows), q_offsets, q_tokens, q_weights, float(c0), float(c1),
+                        float(k1p1), int(k), workspace, out_scores, out_rows)
+    return out_scores, out_rows
+
+
+def fuse_rrf(dense_rows, lex_rows, k_out: int, c: float = 60.0, w_dense: float = 1.0, w_lex: float = 1.0, out=None):
+    """Weighted reciprocal rank fusion of nq (dense, lexical) list pairs in one launch (crs_fuse_rrf, csrc/fuse.hip): dense_rows int64
+    [nq, m_dense <= MAX_K], lex_rows int64 [nq, m_lex <= MAX_K] (rank order, -1 = empty slot) -> (rows int64, fused fp64, dense_pos
+    int32, lex_pos int32, each [nq, k_out]; count int32 [nq]), all cuda, in the host rule's bits.  `out`: those five tensors,
+    preallocated.  No host sync."""
+    import torch
+    if out is None:
+        nq, dev = dense_rows.shape[0], dense_rows.device
+        out = (torch.empty((nq, k_out), dtype=torch.int64, device=dev), torch.empty((nq, k_out), dtype=torch.float64, device=dev),
+               torch.empty((nq, k_out), dtype=torch.int32, device=dev), torch.empty((nq, k_out), dtype=torch.int32, device=dev),
+               torch.empty(nq, dtype=torch.int32, device=dev))
+    with _translate():
+        ops().fuse_rrf(dense_rows, lex_rows, float(c), float(w_dense), float(w_lex), *out)
     return out
 
 

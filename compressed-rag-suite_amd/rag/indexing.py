@@ -51,6 +51,11 @@ New, additive surface (all keys absent from the reference config.json default so
                               documents on first use, extended as rows arrive, dropped when a document changes, and mirrored on the
                               first device at 4 bytes per distinct token per chunk (+ 8 bytes per row of offsets); the sidecars are
                               replicated on every layout, so it serves sharded and multi-device stores alike
+  ``bm25_rows`` / ``search_lexical_batch`` / ``fuse_rrf``   hybrid retrieval: an exact BM25 top-k over the whole collection (a flat
+                              scan of the token CSR with its term frequencies and row lengths, csrc/bm25.hip) and the weighted
+                              reciprocal rank fusion of a dense and a lexical list (csrc/fuse.hip); the retriever's opt-in
+                              ``hybrid`` calls both.  The statistics share the token CSR's lifecycle (+ 4 bytes per distinct token
+                              per chunk and 4 bytes per row on the first device)
 ``where`` / ``where_document`` filters work on every layout (the sidecars are replicated; each shard scans the
 allowed rows it owns).  ``top_k`` is unlimited as in the reference: up to 1024 a refined shard is over-fetched by
 partition (64 candidates from each of up to 64 row chunks, crs::cosine_topk_large_cert) and certified like top_k <= 64;
@@ -183,7 +188,12 @@ class _TokenCSR:
     """The token ids of every sidecar row, for the device's lexical re-rank: `vocab` str -> int32 id (ids in first-seen order,
     exact: no hashing), and per row the sorted distinct ids of set(document.lower().split()) -- the set ContextRetriever._tokens_of
     builds -- as a CSR: offsets int64 [rows + 1], token_ids int32 [total].  The host arrays and their device mirror grow
-    geometrically; extend() tokenises only the new rows and device() uploads only what the mirror lacks."""
+    geometrically; extend() tokenises only the new rows and device() uploads only what the mirror lacks.
+
+    Beside them, filled by the same pass, the statistics BM25 needs (VectorStore.bm25_rows, csrc/bm25.hip): `tfs` int32 parallel to
+    token_ids (occurrences of that token in that row), `doc_len` int32 [rows] (len(document.lower().split())), `df` int64
+    [len(vocab)] (rows that hold the token) and `total_len` (the sum of doc_len); device_stats() mirrors tfs and doc_len like
+    device() mirrors the ids."""
 
     def __init__(self):
         self.vocab: Dict[str, int] = {}
@@ -193,6 +203,12 @@ class _TokenCSR:
         self._tokens = np.zeros(8192, dtype=np.int32)
         self._dev = None                   # (device, offsets tensor, tokens tensor)
         self._dev_rows, self._dev_total = 0, 0
+        self.total_len = 0                 # sum of doc_len
+        self._tfs = np.zeros(8192, dtype=np.int32)
+        self._doc_len = np.zeros(1024, dtype=np.int32)
+        self._df = np.zeros(1024, dtype=np.int64)
+        self._dev_st = None                # (device, tfs tensor, doc_len tensor)
+        self._dev_st_rows, self._dev_st_total = 0, 0
 
     @property
     def offsets(self) -> np.ndarray:
@@ -201,6 +217,18 @@ class _TokenCSR:
     @property
     def token_ids(self) -> np.ndarray:
         return self._tokens[: self.total]
+
+    @property
+    def tfs(self) -> np.ndarray:
+        return self._tfs[: self.total]
+
+    @property
+    def doc_len(self) -> np.ndarray:
+        return self._doc_len[: self.rows]
+
+    @property
+    def df(self) -> np.ndarray:
+        return self._df[: len(self.vocab)]
 
     def row(self, r: int) -> np.ndarray:
         return self._tokens[self._offsets[r]: self._offsets[r + 1]]
@@ -216,17 +244,36 @@ class _TokenCSR:
     def extend(self, documents: Sequence[str]) -> None:
         """Tokenise documents[self.rows:] (the rows that arrived since the last call)."""
         vocab = self.vocab
-        fresh = [sorted({vocab.setdefault(w, len(vocab)) for w in doc.lower().split()}) for doc in documents[self.rows:]]
+        fresh, counts_of, n_words = [], [], []
+        for doc in documents[self.rows:]:
+            words = doc.lower().split()
+            counts: Dict[int, int] = {}
+            for w in words:
+                t = vocab.setdefault(w, len(vocab))
+                counts[t] = counts.get(t, 0) + 1
+            ids = sorted(counts)
+            fresh.append(ids)
+            counts_of.append([counts[t] for t in ids])
+            n_words.append(len(words))
         if not fresh:
             return
         if len(vocab) > 0x7fffffff:
             raise ValueError("more than 2^31 - 1 distinct tokens")
         lens = np.fromiter((len(ids) for ids in fresh), dtype=np.int64, count=len(fresh))
+        added = int(lens.sum())
         self._offsets = self._grown(self._offsets, self.rows + len(fresh) + 1)
-        self._tokens = self._grown(self._tokens, self.total + int(lens.sum()))
+        self._tokens = self._grown(self._tokens, self.total + added)
+        self._tfs = self._grown(self._tfs, self.total + added)
+        self._doc_len = self._grown(self._doc_len, self.rows + len(fresh))
+        self._df = self._grown(self._df, len(vocab))
         self._offsets[self.rows + 1: self.rows + len(fresh) + 1] = self.total + np.cumsum(lens)
-        flat = np.fromiter((t for ids in fresh for t in ids), dtype=np.int32, count=int(lens.sum()))
+        flat = np.fromiter((t for ids in fresh for t in ids), dtype=np.int32, count=added)
         self._tokens[self.total: self.total + flat.size] = flat
+        self._tfs[self.total: self.total + flat.size] = np.fromiter((c for cs in counts_of for c in cs), dtype=np.int32, count=added)
+        self._doc_len[self.rows: self.rows + len(fresh)] = n_words
+        if added:
+            self._df[: len(vocab)] += np.bincount(flat, minlength=len(vocab))      # ids are distinct within a row: one per row
+        self.total_len += int(sum(n_words))
         self.rows += len(fresh)
         self.total += int(flat.size)
 
@@ -258,6 +305,30 @@ class _TokenCSR:
                 tok[self._dev_total: self.total].copy_(torch.from_numpy(self._tokens[self._dev_total: self.total]))
             self._dev_rows, self._dev_total = self.rows, self.total
         return off[: self.rows + 1], tok[: self.total]
+
+    def device_stats(self, device):
+        """(tfs int32 [total], doc_len int32 [rows]) on `device`: the mirror of the BM25 statistics, with device()'s discipline
+        (only the tail the host gained since the last call is uploaded; a full mirror is replaced by a larger one, copied on the
+        device)."""
+        import torch
+        if self._dev_st is None or self._dev_st[0] != device:
+            self._dev_st = (device, torch.zeros(self._tfs.shape[0], dtype=torch.int32, device=device),
+                            torch.zeros(self._doc_len.shape[0], dtype=torch.int32, device=device))
+            self._dev_st_rows, self._dev_st_total = 0, 0
+        _, tf, dl = self._dev_st
+        if tf.shape[0] < self.total or dl.shape[0] < self.rows:
+            new_tf = torch.zeros(self._tfs.shape[0], dtype=torch.int32, device=device)
+            new_dl = torch.zeros(self._doc_len.shape[0], dtype=torch.int32, device=device)
+            new_tf[: self._dev_st_total].copy_(tf[: self._dev_st_total])
+            new_dl[: self._dev_st_rows].copy_(dl[: self._dev_st_rows])
+            tf, dl = new_tf, new_dl
+            self._dev_st = (device, tf, dl)
+        if self._dev_st_rows < self.rows:
+            dl[self._dev_st_rows: self.rows].copy_(torch.from_numpy(self._doc_len[self._dev_st_rows: self.rows]))
+            if self._dev_st_total < self.total:
+                tf[self._dev_st_total: self.total].copy_(torch.from_numpy(self._tfs[self._dev_st_total: self.total]))
+            self._dev_st_rows, self._dev_st_total = self.rows, self.total
+        return tf[: self.total], dl[: self.rows]
 
 
 class SlabCollection:
@@ -1184,6 +1255,154 @@ class VectorStore:
                 host[2 * cells + w_ord:2 * cells + w_ord + w_cnt].view(np.int32)[:nq],
                 host[:cells].view(np.float64).reshape(nq, m_max), host[cells:2 * cells].view(np.float64).reshape(nq, m_max),
                 host[2 * cells + w_ord + w_cnt:].view(np.int32)[:nq])
+
+    # -- hybrid retrieval: the lexical list (csrc/bm25.hip) and the fusion of the two lists (csrc/fuse.hip) -------------------------
+    @staticmethod
+    def _device_guard(dev):
+        """torch.cuda.device(dev) for a HIP device, nothing for any other (the host-side tests run the callers of the native
+        wrappers with those wrappers replaced, on CPU tensors)."""
+        import contextlib
+        import torch
+        return torch.cuda.device(dev) if torch.device(dev).type == "cuda" else contextlib.nullcontext()
+
+    @staticmethod
+    def bm25_constants(n_rows: int, total_len: int, k1: float, b: float):
+        """(c0, c1, k1 + 1) of crs_bm25_topk, each computed in fp64 and rounded once to fp32: dn = c0 + c1 * len with
+        c0 = k1 (1 - b), c1 = k1 b / avgdl, avgdl = total_len / n_rows (c1 = 0 when every document is empty)."""
+        k1, b = float(k1), float(b)
+        c1 = k1 * b / (total_len / n_rows) if total_len > 0 and n_rows > 0 else 0.0
+        return np.float32(k1 * (1.0 - b)), np.float32(c1), np.float32(k1 + 1.0)
+
+    @staticmethod
+    def bm25_weight(n_rows: int, df: int) -> np.float32:
+        """w_t = ln(1 + (N - df + 0.5) / (df + 0.5)) in fp64 (Lucene's non-negative idf), rounded once to fp32."""
+        import math
+        return np.float32(math.log(1.0 + (n_rows - df + 0.5) / (df + 0.5)))
+
+    @staticmethod
+    def _bm25_launches(lengths: Sequence[int]):
+        """Cut a query batch into launches: consecutive (lo, hi) ranges of at most BM25_MAX_QUERIES queries and BM25_MAX_PAIRS
+        (query, known token) pairs.  A single query above the pair cap cannot be served: ValueError."""
+        out, lo, pairs = [], 0, 0
+        for i, n in enumerate(lengths):
+            if n > nat.BM25_MAX_PAIRS:
+                raise ValueError(f"query {i} has {n} distinct known tokens; one BM25 launch takes at most {nat.BM25_MAX_PAIRS}")
+            if i - lo == nat.BM25_MAX_QUERIES or pairs + n > nat.BM25_MAX_PAIRS:
+                out.append((lo, i))
+                lo, pairs = i, 0
+            pairs += n
+        if lo < len(lengths):
+            out.append((lo, len(lengths)))
+        return out
+
+    def bm25_rows(self, queries: Sequence[str], top_k: int, k1: float = 1.5, b: float = 0.75):
+        """Exact Okapi BM25 top-k of every query over the WHOLE collection, on the device (crs_bm25_topk, csrc/bm25.hip): queries
+        [nq] strings -> (scores fp32 [nq, top_k], sidecar rows int64 [nq, top_k]) as numpy, best first, ties by lower row, (-inf, -1)
+        past the hits (a row that shares no token with the query is no hit).  The queries are tokenised against the collection's
+        vocabulary (SlabCollection._token_csr: lower().split(), the retriever's own rule); idf weights, N, df and avgdl are taken
+        over the whole collection and computed in fp64; the kernel's fp32 arithmetic is a pure function of its inputs
+        (include/crs_hip.h).  The batch is cut at 64 queries and at BM25_MAX_PAIRS (query, token) pairs per launch; one host
+        block up per launch, one readback for the whole call.  Runs on the first device over the sidecar rows, so it serves
+        every layout.  1 <= top_k <= MAX_K."""
+        import torch
+        col = self.collection
+        if col is None:
+            raise ValueError("No collection available. Create index first.")
+        if not isinstance(top_k, (int, np.integer)) or isinstance(top_k, bool) or not 1 <= top_k <= nat.MAX_K:
+            raise ValueError(f"top_k must be an integer in 1..{nat.MAX_K} for a lexical search, got {top_k!r}")
+        if not (k1 >= 0 and np.isfinite(k1)) or not 0.0 <= b <= 1.0:
+            raise ValueError(f"BM25 needs a finite k1 >= 0 and 0 <= b <= 1, got k1={k1!r}, b={b!r}")
+        queries = list(queries)
+        nq, k = len(queries), int(top_k)
+        scores = np.full((nq, k), -np.inf, dtype=np.float32)
+        rows = np.full((nq, k), -1, dtype=np.int64)
+        csr = col._token_csr()
+        n_rows = csr.rows
+        if nq == 0 or n_rows == 0:
+            return scores, rows
+        q_ids = [csr.query_ids(q)[0] for q in queries]
+        launches = self._bm25_launches([len(ids) for ids in q_ids])
+        c0, c1, k1p1 = self.bm25_constants(n_rows, csr.total_len, k1, b)
+        df = csr.df
+        dev = col.device
+        with self._device_guard(dev):
+            doc_off, doc_tok = csr.device(dev)
+            doc_tf, doc_len = csr.device_stats(dev)
+            # one device block <- both outputs of every launch: [rows int64 [nq, k] | scores fp32 [nq, k]]
+            out = torch.empty(nq * k + (nq * k + 1) // 2, dtype=torch.int64, device=dev)
+            out_r = out[: nq * k].view(nq, k)
+            out_s = out[nq * k:].view(torch.float32)[: nq * k].view(nq, k)
+            for lo, hi in launches:
+                n, ids = hi - lo, q_ids[lo:hi]
+                n_tok = sum(len(t) for t in ids)
+                # one host block -> one copy: [q_offsets int64 [n + 1] | q_tokens int32 | q_weights fp32], int64 words
+                w_tok = (n_tok + 1) // 2
+                block = np.zeros(n + 1 + 2 * w_tok, dtype=np.int64)
+                np.cumsum([len(t) for t in ids], out=block[1:n + 1])
+                flat = np.fromiter((t for ts in ids for t in ts), dtype=np.int32, count=n_tok)
+                block[n + 1:n + 1 + w_tok].view(np.int32)[:n_tok] = flat
+                block[n + 1 + w_tok:].view(np.float32)[:n_tok] = [self.bm25_weight(n_rows, int(df[t])) for t in flat.tolist()]
+                d = torch.from_numpy(block).to(dev)
+                nat.bm25_topk(doc_off, doc_tok, doc_tf, doc_len, n_rows, d[: n + 1], d[n + 1:n + 1 + w_tok].view(torch.int32)[:n_tok],
+                              d[n + 1 + w_tok:].view(torch.float32)[:n_tok], float(c0), float(c1), float(k1p1), k,
+                              out_scores=out_s[lo:hi], out_rows=out_r[lo:hi])
+            host = out.cpu().numpy()
+        rows[:] = host[: nq * k].reshape(nq, k)
+        scores[:] = host[nq * k:].view(np.float32)[: nq * k].reshape(nq, k)
+        return scores, rows
+
+    def search_lexical_batch(self, queries: Sequence[str], top_k: int = 5) -> Dict[str, Any]:
+        """search_batch for the lexical list (bm25_rows): the same dict with 'scores' (BM25, best first) in place of 'distances'."""
+        sc, rh = self.bm25_rows(queries, top_k)
+        col = self.collection
+        out = {'ids': [], 'documents': [], 'metadatas': [], 'scores': []}
+        for a in range(len(rh)):
+            valid = [r for r in rh[a].tolist() if r >= 0]
+            out['ids'].append([col.ids[r] for r in valid])
+            out['documents'].append([col.documents[r] for r in valid])
+            out['metadatas'].append([col.metadatas[r] for r in valid])
+            out['scores'].append(sc[a, : len(valid)].astype(np.float64).tolist())
+        return out
+
+    def fuse_rrf(self, dense_rows, lex_rows, k_out: int, c: float = 60.0, weights=(1.0, 1.0)):
+        """Weighted reciprocal rank fusion of a dense and a lexical list per query, on the device (crs_fuse_rrf, csrc/fuse.hip):
+        dense_rows int64 [nq, m_dense <= MAX_K], lex_rows int64 [nq, m_lex <= MAX_K] (sidecar rows in rank order, -1 = empty slot)
+        -> numpy (rows int64, fused fp64, dense_pos int32, lex_pos int32, each [nq, k_out]; count int32 [nq]): fused =
+        weights[0] / (c + i + 1) + weights[1] / (c + j + 1) for a row at 0-based positions i and j (a row in one list only: that
+        term alone), ordered by fused descending, then dense position, then lexical position; past the count (-1, 0, -1, -1).
+        One block up, one launch, one block back."""
+        import torch
+        col = self.collection
+        if col is None:
+            raise ValueError("No collection available. Create index first.")
+        dense_rows = np.ascontiguousarray(dense_rows, dtype=np.int64)
+        lex_rows = np.ascontiguousarray(lex_rows, dtype=np.int64)
+        if dense_rows.ndim != 2 or lex_rows.ndim != 2 or dense_rows.shape[0] != lex_rows.shape[0]:
+            raise ValueError("dense_rows and lex_rows must be [nq, m_dense] and [nq, m_lex]")
+        if not (1 <= dense_rows.shape[1] <= nat.MAX_K and 1 <= lex_rows.shape[1] <= nat.MAX_K and 1 <= int(k_out) <= 2 * nat.MAX_K):
+            raise ValueError(f"fuse_rrf takes lists of 1..{nat.MAX_K} rows and 1 <= k_out <= {2 * nat.MAX_K}")
+        w_d, w_l = (float(w) for w in weights)
+        nq, k_out = dense_rows.shape[0], int(k_out)
+        cells, w_pos, w_cnt = nq * k_out, (nq * k_out + 1) // 2, (nq + 1) // 2
+        if nq == 0:
+            return (np.zeros((0, k_out), np.int64), np.zeros((0, k_out)), np.zeros((0, k_out), np.int32), np.zeros((0, k_out), np.int32),
+                    np.zeros(0, np.int32))
+        dev = col.device
+        with self._device_guard(dev):
+            d = torch.from_numpy(np.concatenate([dense_rows.ravel(), lex_rows.ravel()])).to(dev)
+            # one device block <- the five outputs: [rows int64 | fused fp64 | dense_pos int32 | lex_pos int32 | count int32]
+            out = torch.empty(2 * cells + 2 * w_pos + w_cnt, dtype=torch.int64, device=dev)
+            tens = (out[:cells].view(nq, k_out), out[cells:2 * cells].view(torch.float64).view(nq, k_out),
+                    out[2 * cells:2 * cells + w_pos].view(torch.int32)[:cells].view(nq, k_out),
+                    out[2 * cells + w_pos:2 * cells + 2 * w_pos].view(torch.int32)[:cells].view(nq, k_out),
+                    out[2 * cells + 2 * w_pos:].view(torch.int32)[:nq])
+            nat.fuse_rrf(d[: dense_rows.size].view(dense_rows.shape), d[dense_rows.size:].view(lex_rows.shape), k_out, float(c), w_d, w_l,
+                         out=tens)
+            host = out.cpu().numpy()
+        return (host[:cells].reshape(nq, k_out), host[cells:2 * cells].view(np.float64).reshape(nq, k_out),
+                host[2 * cells:2 * cells + w_pos].view(np.int32)[:cells].reshape(nq, k_out),
+                host[2 * cells + w_pos:2 * cells + 2 * w_pos].view(np.int32)[:cells].reshape(nq, k_out),
+                host[2 * cells + 2 * w_pos:].view(np.int32)[:nq])
 
     def _search_rows(self, query_embeddings, top_k: int, where: Optional[dict] = None, where_document: Optional[dict] = None):
         """The search behind search_rows / search_batch: query_embeddings fp32 [nq, d] (numpy or tensor) -> (scores fp32

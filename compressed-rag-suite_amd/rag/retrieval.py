@@ -15,6 +15,11 @@ on, a BERT cross-encoder scores every (query, chunk text) pair that passed the t
 is sorted on it (stable, descending) and cut to ``top_k``; the search, the ``2 * top_k`` fetch, the threshold and the MMR step
 (on ``score``) are as without it.
 
+Opt-in, ``hybrid`` (``true``, or a dict of ``rrf_k``, ``weights``, ``k1``, ``b``): ``retrieve_batch`` fuses the thresholded dense list of every
+query with an exact BM25 list over the whole collection (VectorStore.bm25_rows, csrc/bm25.hip) by weighted reciprocal rank fusion
+(VectorStore.fuse_rrf, csrc/fuse.hip), so a chunk the encoder ranks far down still surfaces when it matches the query's words;
+the re-rank, the cut and the MMR step then run on the fused lists as before.  ``retrieve`` goes through ``retrieve_batch``.
+
 Additive: ``retrieve_batch`` embeds and searches many queries in one launch each and then applies
 the identical per-query post-processing; ``reuse_index_embeddings`` is NOT offered because the
 reference re-embeds chunk texts for MMR (:238-239) and near-ties could reorder otherwise.
@@ -70,10 +75,51 @@ class ContextRetriever:
         if config.get('rerank_model'):
             from rag.reranking import CrossEncoderReranker
             self.cross_encoder = CrossEncoderReranker(config['rerank_model'])
+        # additive: hybrid retrieval.  False (default) | True | {'rrf_k': 60, 'weights': [1, 1], 'k1': 1.5, 'b': 0.75}: retrieve_batch
+        # fuses each thresholded dense list with the BM25 list of the same query over the whole collection (same `fetch`) by
+        # weighted reciprocal rank fusion: fused = w_dense / (rrf_k + i + 1) + w_lex / (rrf_k + j + 1) over the 0-based ranks; 'score'
+        # becomes fused / ((w_dense + w_lex) / (rrf_k + 1)), in (0, 1].  lexical_rerank: 'device' is then not taken (its inputs are
+        # cosine scores); retrieve() goes through retrieve_batch and refuses metadata filters
+        self.hybrid = self._parse_hybrid(config.get('hybrid', False))
+        self.last_hybrid = {'lists': 0, 'lexical_only_hits': 0}     # what the last retrieve_batch call fused
         self._token_sets: Dict[str, frozenset] = {}       # _rerank: text -> its lower-cased token set
         self._engine, self._engine_key = None, None
         self.distance_metric = self._get_distance_metric()
         logger.info(f"Using distance metric: {self.distance_metric}")
+
+    @staticmethod
+    def _parse_hybrid(value) -> Optional[dict]:
+        """The `hybrid` config value as {'rrf_k', 'weights', 'k1', 'b'} floats, or None when off; anything else raises ValueError."""
+        if value is None or value is False:
+            return None
+        out = {'rrf_k': 60.0, 'weights': (1.0, 1.0), 'k1': 1.5, 'b': 0.75}
+        if value is True:
+            return out
+        if not isinstance(value, dict):
+            raise ValueError(f"hybrid must be false, true or a dict of rrf_k / weights / k1 / b, got {value!r}")
+        unknown = sorted(set(value) - set(out))
+        if unknown:
+            raise ValueError(f"hybrid: unknown key(s) {unknown}; known: b, k1, rrf_k, weights")
+
+        def number(key, lo, hi):
+            v = value[key]
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not (lo <= float(v) <= hi):
+                raise ValueError(f"hybrid: {key} must be a number in [{lo}, {hi}], got {v!r}")
+            return float(v)
+        if 'rrf_k' in value:
+            out['rrf_k'] = number('rrf_k', 0.0, 1e9)
+        if 'k1' in value:
+            out['k1'] = number('k1', 0.0, 1e6)
+        if 'b' in value:
+            out['b'] = number('b', 0.0, 1.0)
+        if 'weights' in value:
+            w = value['weights']
+            if (not isinstance(w, (list, tuple)) or len(w) != 2
+                    or any(isinstance(x, bool) or not isinstance(x, (int, float)) or not (0.0 <= float(x) <= 1e9) for x in w)
+                    or float(w[0]) + float(w[1]) <= 0.0):
+                raise ValueError(f"hybrid: weights must be two numbers >= 0 (dense, lexical), not both 0, got {w!r}")
+            out['weights'] = (float(w[0]), float(w[1]))
+        return out
 
     def _get_distance_metric(self) -> str:
         """The store's space ('cosine' unless the collection says otherwise or does not exist yet)."""
@@ -136,6 +182,10 @@ class ContextRetriever:
         """List of dicts with 'text', 'score', 'distance', 'metadata', 'chunk_id' (+ 'rerank_score'
         when re-ranked), at most k of them."""
         k = top_k or self.top_k
+        if self.hybrid is not None:
+            if filters is not None:
+                raise ValueError("hybrid retrieval does not take metadata filters: the lexical list is not filtered")
+            return self.retrieve_batch([query], top_k=top_k)[0]
         try:
             query_embedding = self.embedding_model.embed(query)
             results = self.vector_store.search(query_embedding=query_embedding,
@@ -235,16 +285,35 @@ class ContextRetriever:
         if col is None:
             raise ValueError("No collection available. Create index first.")
         fetch = k * 2 if self.rerank else k
+        hybrid = self.hybrid
+        if hybrid is not None:
+            if fetch > 64:
+                raise ValueError(f"hybrid retrieval fetches at most 64 rows per list, got {fetch} (top_k {k}, rerank {bool(self.rerank)})")
+            if not (hasattr(store, 'bm25_rows') and hasattr(store, 'fuse_rrf') and hasattr(store, 'search_rows')):
+                raise ValueError("hybrid retrieval needs a store with search_rows, bm25_rows and fuse_rrf")
+            self.last_hybrid = {'lists': 0, 'lexical_only_hits': 0}
         per_query: List[List[Dict]] = []
         row_of: Dict[int, int] = {}           # id(chunk dict) -> sidecar row (our store only)
         ids_l, docs_l, metas_l = getattr(col, 'ids', None), getattr(col, 'documents', None), getattr(col, 'metadatas', None)
         queries = list(queries)
         cross = self.cross_encoder if self.rerank else None
         on_device = (self.lexical_rerank == 'device' and bool(self.rerank) and self.distance_metric == 'cosine' and fetch <= 64
-                     and ids_l is not None and hasattr(store, 'rerank_lexical') and cross is None)
+                     and ids_l is not None and hasattr(store, 'rerank_lexical') and cross is None and hybrid is None)
         host_pieces = 0
         for piece in self._search_many(queries, fetch):      # one device batch at a time: its dicts are built while the next ones run
             piece_start = len(per_query)
+            if hybrid is not None:
+                if isinstance(piece, dict):
+                    raise ValueError("hybrid retrieval needs a store with search_rows, bm25_rows and fuse_rrf")
+                host_pieces += 1
+                piece_queries = queries[piece_start:piece_start + len(piece)]
+                for query, chunks in zip(piece_queries, self._hybrid_lists(piece_queries, piece, fetch, row_of)):
+                    if chunks and cross is None:
+                        chunks = self._rerank(query, chunks, k) if self.rerank and len(chunks) > k else chunks[:k]
+                    per_query.append(chunks)
+                if cross is not None:
+                    per_query[piece_start:] = self._rerank_cross(piece_queries, per_query[piece_start:], k)
+                continue
             if on_device and not isinstance(piece, dict):
                 built = self._rerank_on_device(queries[len(per_query):len(per_query) + len(piece)], piece, k, row_of)
                 if built is not None:
@@ -320,6 +389,56 @@ class ContextRetriever:
                 per_query = [self._apply_diversity(chunks, vectors=vectors[[index[c['text']] for c in chunks]])
                              if len(chunks) > 1 else chunks for chunks in per_query]
         return per_query
+
+    def _hybrid_lists(self, queries: List[str], piece, fetch: int, row_of: Dict[int, int]) -> List[List[Dict]]:
+        """The fused chunk lists of one piece of _search_many (per query: scores fp32, sidecar rows int64, best first): the dense
+        lists go through the cosine score and similarity_threshold as in retrieve_batch's host loop, VectorStore.bm25_rows gives
+        the lexical lists of the same queries (same `fetch`), and ONE VectorStore.fuse_rrf call fuses each pair to at most
+        `fetch` rows.  A dict carries 'score' = fused / ((w_dense + w_lex) / (rrf_k + 1)), 'distance' (None for a lexical-only hit),
+        'dense_score' (the cosine-mapped score or None), 'bm25_score' (0.0 when absent), 'dense_rank' / 'lexical_rank' (or None)."""
+        store, hy = self.vector_store, self.hybrid
+        col = store.collection
+        nq = len(piece)
+        m_dense = max(1, max((len(sc) for sc, _ in piece), default=1))
+        dense = np.full((nq, m_dense), -1, dtype=np.int64)
+        d_dist = np.zeros((nq, m_dense), dtype=np.float64)
+        d_score = np.zeros((nq, m_dense), dtype=np.float64)
+        for i, (sc, rows) in enumerate(piece):
+            valid = rows >= 0
+            rows, sc = rows[valid], sc[valid]
+            dist = (np.float32(1.0) - sc.astype(np.float32)).astype(np.float64)    # the store's distances, as search() returns them
+            if self.distance_metric == 'cosine':                                      # _distance_to_similarity, vectorised (same fp64 ops)
+                d = np.minimum(np.maximum(dist, 0.0), 2.0)
+                score = np.minimum(np.maximum(1.0 - (d * d / 2.0), 0.0), 1.0)
+            else:
+                score = np.array([self._distance_to_similarity(float(x)) for x in dist], dtype=np.float64)
+            keep = score >= self.similarity_threshold
+            n = int(keep.sum())
+            dense[i, :n], d_dist[i, :n], d_score[i, :n] = rows[keep], dist[keep], score[keep]
+        lex_scores, lex_rows = store.bm25_rows(queries, fetch, k1=hy['k1'], b=hy['b'])
+        w_dense, w_lex = hy['weights']
+        rows, fused, dpos, lpos, count = store.fuse_rrf(dense, lex_rows, fetch, c=hy['rrf_k'], weights=(w_dense, w_lex))
+        norm = (w_dense + w_lex) / (hy['rrf_k'] + 1.0)
+        ids_l, docs_l, metas_l = col.ids, col.documents, col.metadatas
+        out = []
+        for i in range(nq):
+            n = int(count[i])
+            chunks = []
+            for r, f, dp, lp in zip(rows[i, :n].tolist(), fused[i, :n].tolist(), dpos[i, :n].tolist(), lpos[i, :n].tolist()):
+                c_ = {'text': docs_l[r], 'score': f / norm, 'distance': float(d_dist[i, dp]) if dp >= 0 else None,
+                      'metadata': metas_l[r] if metas_l else {}, 'chunk_id': ids_l[r],
+                      'dense_score': float(d_score[i, dp]) if dp >= 0 else None,
+                      'bm25_score': float(lex_scores[i, lp]) if lp >= 0 else 0.0,
+                      'dense_rank': dp if dp >= 0 else None, 'lexical_rank': lp if lp >= 0 else None}
+                row_of[id(c_)] = r
+                chunks.append(c_)
+                if dp < 0:
+                    self.last_hybrid['lexical_only_hits'] += 1
+            if not chunks:
+                logger.warning("No results found for query")
+            self.last_hybrid['lists'] += 1
+            out.append(chunks)
+        return out
 
     def _rerank_on_device(self, queries: List[str], piece, k: int, row_of: Dict[int, int]) -> Optional[List[List[Dict]]]:
         """The chunk lists of one piece of _search_many (per query: scores fp32, sidecar rows int64, best first), scored,

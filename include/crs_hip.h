@@ -255,6 +255,48 @@ int crs_rerank_lexical(const float* scores_dev, const int64_t* rows_dev, int nq,
                        const int32_t* q_tokens_dev, int64_t n_q_tokens, const int32_t* q_norm_dev, int k, double threshold,
                        int32_t* order_dev, int32_t* count_dev, double* sim_dev, double* rr_dev, int32_t* reranked_dev, void* stream);
 
+/* ---- hybrid retrieval, lexical half: exact BM25 top-k over the token CSR -- no reference call site (the reference retrieves by
+ * cosine alone) (additive to ABI 3; csrc/bm25.hip).  A flat doc-at-a-time scan: every row of the CSR is streamed once for the
+ * whole query batch, each query's top-k is selected in the kernel and the per-workgroup lists are joined as crs_merge_topk does.
+ *   doc_offsets_dev  int64 [n_rows + 1]    CSR over doc_tokens_dev / doc_tf_dev; offsets are clamped into [0, n_doc_tokens]
+ *   doc_tokens_dev   int32 [n_doc_tokens]  per row the ascending distinct token ids of its document (may be null when empty)
+ *   doc_tf_dev       int32 [n_doc_tokens]  parallel: occurrences of that token in that row
+ *   doc_len_dev      int32 [n_rows]        tokens of the row's document, repeats counted
+ *   q_offsets_dev    int64 [nq + 1]        CSR over q_tokens_dev / q_weights_dev; offsets are clamped into [0, n_q_tokens]
+ *   q_tokens_dev     int32 [n_q_tokens]    per query its ascending distinct KNOWN token ids (may be null when empty)
+ *   q_weights_dev    fp32 [n_q_tokens]     parallel: w_t = ln(1 + (N - df_t + 0.5) / (df_t + 0.5)), computed in fp64, rounded once
+ *   c0, c1, k1p1     k1 (1 - b), k1 b / avgdl and k1 + 1, computed in fp64, rounded once
+ * score(q, d) over the tokens t both hold, in ascending token id, all fp32, every operation rounded on its own (no fused
+ * multiply-add, correctly rounded division):
+ *     dn = c0 + c1 * (float)len_d;   term_t = (w_t * ((float)tf * k1p1)) / ((float)tf + dn);   score = ((0 + term_1) + term_2) + ...
+ * so the scores are a pure function of the inputs (tests/_bm25_ref.py restates them bit for bit in numpy).  A row that shares no
+ * token with the query is not a hit, whatever its score would be, and never enters a list.
+ *   out_scores_dev fp32 [nq, k] descending, out_rows_dev int64 [nq, k]; ties -> lower row first; empty slots (-inf, -1).
+ * Limits (CRS_EINVAL otherwise): 1 <= nq <= 64; 1 <= k <= CRS_MAX_K; 0 <= n_q_tokens <= CRS_BM25_MAX_PAIRS (the (query, token)
+ * pairs of one launch: cut a longer batch into several launches); 0 <= n_rows < 2^31 - 64.  A malformed CSR gives wrong scores,
+ * never an access outside the buffers.  Workspace: crs_bm25_workspace_bytes() bytes, 256-byte aligned, contents don't-care.
+ * No host synchronisation. */
+#define CRS_BM25_MAX_PAIRS 4096
+int crs_bm25_workspace_bytes(int nq, int k, int64_t n_rows, size_t* bytes);
+int crs_bm25_topk(const int64_t* doc_offsets_dev, const int32_t* doc_tokens_dev, const int32_t* doc_tf_dev, const int32_t* doc_len_dev,
+                  int64_t n_rows, int64_t n_doc_tokens, const int64_t* q_offsets_dev, const int32_t* q_tokens_dev,
+                  const float* q_weights_dev, int nq, int64_t n_q_tokens, float c0, float c1, float k1p1, int k, void* workspace_dev,
+                  size_t workspace_bytes, float* out_scores_dev, int64_t* out_rows_dev, void* stream);
+
+/* ---- hybrid retrieval, fusion: weighted reciprocal rank fusion of a dense and a lexical list per query (additive to ABI 3;
+ * csrc/fuse.hip).  One wave per query, `nq` queries per launch.
+ *   dense_rows_dev   int64 [nq, m_dense]   rows in rank order, a negative row = empty slot; valid rows distinct within a list
+ *   lex_rows_dev     int64 [nq, m_lex]     likewise; 1 <= m_dense, m_lex <= CRS_MAX_K
+ * A row at 0-based position i of the dense list and j of the lexical list scores, in fp64 with every operation rounded on its own,
+ *     fused = w_dense / ((c + i) + 1) + w_lex / ((c + j) + 1)      (dense term first; a row in one list only: that term alone)
+ * Order: fused descending, ties by the smaller dense position (absent = infinite), then the smaller lexical position.
+ *   rows_dev int64, fused_dev fp64, dense_pos_dev int32, lex_pos_dev int32 (-1 = absent), each [nq, k_out], 1 <= k_out <= 2 CRS_MAX_K;
+ *   past the count: (-1, 0.0, -1, -1).  count_dev int32 [nq] = min(distinct rows, k_out).
+ * c >= 0 and the weights finite and >= 0.  Rows are compared, never dereferenced.  No host synchronisation, no workspace. */
+int crs_fuse_rrf(const int64_t* dense_rows_dev, int m_dense, const int64_t* lex_rows_dev, int m_lex, int nq, double c, double w_dense,
+                 double w_lex, int k_out, int64_t* rows_dev, double* fused_dev, int32_t* dense_pos_dev, int32_t* lex_pos_dev,
+                 int32_t* count_dev, void* stream);
+
 /* ---- BERTScore token matching: the step behind the encoder in bert_score.score -- evaluation/retrieval/rag_metrics.py:179-207 ----
  * (additive to ABI 3; csrc/token_match.hip).  Scores `n_pairs` (candidate, reference) pairs of token states in one launch, one
  * workgroup per pair:
