@@ -110,6 +110,12 @@ int bm25_topk_launch(const int64_t* doc_off, const int* doc_tok, const int* doc_
 int fuse_rrf_launch(const int64_t* dense, int m_dense, const int64_t* lex, int m_lex, int nq, double c, double w_dense, double w_lex,
                     int k_out, int64_t* out_rows, double* out_fused, int* out_dpos, int* out_lpos, int* out_count, hipStream_t stream);
 
+// wordpiece.hip: BERT basic tokenisation + WordPiece (or the hash rule) of UTF-8 texts, one workgroup per text
+int wordpiece_encode_launch(const uint8_t* text, const int64_t* offsets, int n_texts, int64_t n_bytes, const uint32_t* table,
+                            int64_t table_len, const uint32_t* rep, int64_t rep_len, const int32_t* slots, int64_t n_slots,
+                            const uint32_t* pool, int64_t pool_len, int max_probe, int lmax, int mode, int unk, int cls, int sep, int pad,
+                            int hash_lo, int hash_span, int max_len, int* ids, int* lens, int* flags, hipStream_t stream);
+
 // token_match.hip: BERTScore's greedy matching of pairs of token-state matrices, one workgroup per pair
 int token_match_launch(const float* a, const int* len_a, int seq_a, const float* b, const int* len_b, int seq_b, int n_pairs, int hidden,
                        const float* w_a, const float* w_b, float* out, hipStream_t stream);

@@ -26,6 +26,7 @@ LARGE_K_MAX_PARTS = 64     # chunks of the partition (x 64 candidates: at most 4
 EXACT_MAX_CAP = 13312      # CRS_EXACT_MAX_CAP: longest per-query row list of crs_escalate_exact
 EXACT_CAP = 1024           # default list length (12 KB of LDS per query in the re-rank)
 BM25_MAX_QUERIES = 64      # queries of one crs_bm25_topk launch
+WORDPIECE_TILE_BYTES = 1024   # CRS_WORDPIECE_TILE_BYTES: bytes of a text that crs_wordpiece_encode stages at a time
 BM25_MAX_PAIRS = 4096      # CRS_BM25_MAX_PAIRS: (query, known token) pairs of one crs_bm25_topk launch
 
 # name -> (restype, argtypes); mirrors include/crs_hip.h one to one
@@ -58,6 +59,9 @@ _SIGNATURES = {
                               c_float, c_float, c_float, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     "crs_fuse_rrf": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int, c_void_p,
                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "crs_wordpiece_encode": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                     c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                     c_void_p, c_void_p]),
     "crs_rescore_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p,
                                 c_void_p, c_void_p]),
     "crs_score_rows_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
@@ -388,6 +392,23 @@ def fuse_rrf(dense_rows, lex_rows, k_out: int, c: float = 60.0, w_dense: float =
                torch.empty(nq, dtype=torch.int32, device=dev))
     with _translate():
         ops().fuse_rrf(dense_rows, lex_rows, float(c), float(w_dense), float(w_lex), *out)
+    return out
+
+
+def wordpiece_encode(text, offsets, n_bytes: int, table, rep_pool, slots, vocab_pool, max_probe: int, lmax: int, mode: int, unk_id: int,
+                     cls_id: int, sep_id: int, pad_id: int, hash_lo: int, hash_span: int, max_len: int, out=None):
+    """Tokenise n UTF-8 texts in one launch (crs_wordpiece_encode, csrc/wordpiece.hip): text uint8 [>= n_bytes] the texts' bytes end to
+    end, offsets int64 [n + 1]; table / rep_pool / slots / vocab_pool the int32 tensors of rag/_wordpiece.py; mode 0 WordPiece, 1 the
+    HashTokenizer rule -> (ids int32 [n, max_len]: cls, ids, sep, pad; lens int32 [n]; flags int32 [n]: 1 = tokenise this text on the
+    host instead).  All cuda.  `out`: those three, preallocated.  No host sync; a missing kernel raises."""
+    import torch
+    n, dev = offsets.shape[0] - 1, text.device
+    if out is None:
+        out = (torch.empty((n, int(max_len)), dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
+               torch.empty(n, dtype=torch.int32, device=dev))
+    with _translate():
+        ops().wordpiece_encode(text, offsets, int(n_bytes), table, rep_pool, slots, vocab_pool, int(max_probe), int(lmax), int(mode),
+                               int(unk_id), int(cls_id), int(sep_id), int(pad_id), int(hash_lo), int(hash_span), *out)
     return out
 
 

@@ -177,6 +177,9 @@ class EmbeddingModel:
     """Sentence encoder wrapper (BERT and MPNet checkpoints) running on the GPU."""
 
     def __init__(self, config: dict):
+        self.tokenize_mode = config.get('tokenize', 'host')     # additive key: 'device' = csrc/wordpiece.hip feeds the encoder
+        if self.tokenize_mode not in ('host', 'device'):
+            raise ValueError(f"rag.embedding.tokenize must be 'host' or 'device', got {self.tokenize_mode!r}")
         self.model_name = config.get('model_name', 'sentence-transformers/all-MiniLM-L6-v2')
         self.batch_size = config.get('batch_size', 32)
         self.normalize = config.get('normalize', True)
@@ -184,6 +187,10 @@ class EmbeddingModel:
         logger.info(f"Loading embedding model: {self.model_name}")
         self._pre_lower = False      # sentence_bert_config.json do_lower_case: an extra str.lower() before the tokenizer
         shape, weights, self.tokenizer = self._resolve(config)
+        self._device_tokenizer = None
+        if self.tokenize_mode == 'device':
+            from rag._wordpiece import tokenizer_spec
+            tokenizer_spec(self.tokenizer)      # NotImplementedError for a tokenizer the kernel does not restate; tables on first use
         if config.get('max_seq_length'):
             from dataclasses import replace
             shape = replace(shape, max_seq=min(int(config['max_seq_length']), shape.max_pos - shape.pos_offset))
@@ -238,6 +245,102 @@ class EmbeddingModel:
             return self.tokenizer.encode_batch(texts, self.shape.max_seq)
         return [self.tokenizer.encode(t, self.shape.max_seq) for t in texts]
 
+    TOKENIZE_GROUP_BYTES = 64 << 20      # UTF-8 bytes of one crs_wordpiece_encode launch (and one lens / flags read-back)
+
+    def _tokenize_device(self, texts: List[str], timings: Optional[dict] = None):
+        """(ids cuda int32 [n, max_seq], lens as a host int32 array [n]): csrc/wordpiece.hip on groups of texts bounded by
+        TOKENIZE_GROUP_BYTES, one launch and one read-back of lens / flags per group; the texts the kernel flags (a code point
+        outside its table's reach) go through self.tokenize and their rows are written in."""
+        import time
+        import torch
+        from rag._wordpiece import DeviceTokenizer
+        dev = self.model.device
+        if self._device_tokenizer is None:
+            self._device_tokenizer = DeviceTokenizer(self.tokenizer, dev)
+        texts = [str(t).strip() for t in texts]
+        if self._pre_lower:
+            texts = [t.lower() for t in texts]
+        max_seq, pad = self.shape.max_seq, getattr(self.tokenizer, "pad_id", 0)
+        ids_parts, lens_parts, lo = [], [], 0
+        while lo < len(texts):
+            hi, size = lo, 0
+            while hi < len(texts) and (hi == lo or size + len(texts[hi]) <= self.TOKENIZE_GROUP_BYTES // 4):   # <= 4 bytes a character
+                size += len(texts[hi])
+                hi += 1
+            ids, lens, flags, host = self._device_tokenizer.encode(texts[lo:hi], max_seq, timings)
+            t0 = time.perf_counter()
+            back = torch.stack((lens, flags)).cpu().numpy()
+            if timings is not None:
+                timings["readback_s"] = timings.get("readback_s", 0.0) + (time.perf_counter() - t0)
+            lens_h = back[0].copy()
+            redo = sorted(set(np.nonzero(back[1])[0].tolist()) | set(host))
+            if redo:
+                rows, rlen = pad_batch(self.tokenize([texts[lo + i] for i in redo]), pad)
+                block = np.full((len(redo), max_seq), pad, dtype=np.int32)
+                block[:, : rows.shape[1]] = rows
+                ids[torch.as_tensor(redo, device=dev)] = torch.from_numpy(block).to(dev)
+                lens_h[redo] = rlen
+            ids_parts.append(ids)
+            lens_parts.append(lens_h)
+            lo = hi
+        if not ids_parts:
+            return torch.empty((0, max_seq), dtype=torch.int32, device=dev), np.zeros(0, dtype=np.int32)
+        return (ids_parts[0] if len(ids_parts) == 1 else torch.cat(ids_parts)), np.concatenate(lens_parts)
+
+    def tokenize_device(self, texts: List[str]):
+        """-> (ids cuda int32 [n, max_seq]: what self.tokenize gives, right-padded with the pad id; lens cuda int32 [n]), tokenised
+        by the device kernel whatever rag.embedding.tokenize says (additive)."""
+        import torch
+        from rag._wordpiece import tokenizer_spec
+        tokenizer_spec(self.tokenizer)
+        ids, lens = self._tokenize_device(list(texts))
+        return ids, torch.from_numpy(lens).to(ids.device)
+
+    def _embed_device_tokens(self, texts: List[str], out):
+        """embed_device with rag.embedding.tokenize 'device': the same order (longest text first), batches and widths as the
+        host branch, so every batch's (ids, lens) block is the tensor pad_batch would have built; the blocks are cut on the device."""
+        import torch
+        n, dev = len(texts), out.device
+        ids_all, lens_h = self._tokenize_device(texts)
+        steps = tuple(st for st in (16, 32, 64) if st <= self.shape.max_seq)
+
+        def width_of(lens):
+            width = int(lens.max())
+            for step in steps:
+                if width <= step:
+                    return step
+            return width
+
+        if n <= self.batch_size:
+            return self.model.forward(ids_all[:, : width_of(lens_h)].contiguous(), lens_h, normalize=bool(self.normalize), out=out)
+        order = sorted(range(n), key=lambda i: -len(texts[i]))
+        lens_all = torch.from_numpy(lens_h).to(dev)
+        cur = torch.cuda.current_stream(dev)
+        lanes = [torch.cuda.Stream(device=dev) for _ in range(2)]
+        lane_ws = [None, None]
+        ready = torch.cuda.Event()
+        ready.record(cur)              # after the tokeniser's launches and row writes, which ran on `cur`
+        for b, lo in enumerate(range(0, n, self.batch_size)):
+            sel = order[lo: lo + self.batch_size]
+            width = width_of(lens_h[sel])
+            st = lanes[b & 1]
+            with torch.cuda.stream(st):
+                if b < 2:
+                    st.wait_event(ready)
+                sel_t = torch.as_tensor(sel, device=dev)
+                ids = ids_all[sel_t, :width].contiguous()
+                need = self.model.workspace_bytes(len(sel), width)
+                if lane_ws[b & 1] is None or lane_ws[b & 1].numel() < need:
+                    lane_ws[b & 1] = torch.empty(need, dtype=torch.uint8, device=dev)
+                emb = self.model.forward(ids, lens_all[sel_t], normalize=bool(self.normalize), workspace=lane_ws[b & 1])
+                out[sel_t] = emb
+        for st in lanes:
+            out.record_stream(st)
+            ids_all.record_stream(st)
+            lens_all.record_stream(st)
+            cur.wait_stream(st)
+        return out
+
     def embed_device(self, texts: Union[str, List[str]]):
         """Embeddings as a cuda fp32 tensor [n, d] in input order (additive, zero-copy index build)."""
         import torch
@@ -247,6 +350,8 @@ class EmbeddingModel:
         out = torch.empty((n, self.dimension), dtype=torch.float32, device=self.model.device)
         if n == 0:
             return out
+        if self.tokenize_mode == 'device':
+            return self._embed_device_tokens(list(texts), out)
         token_ids = self.tokenize(texts)
         if n <= self.batch_size:   # one batch: no length sort, no scatter (its index tensor is a blocking H2D copy per call)
             ids, lens = pad_batch(token_ids, getattr(self.tokenizer, "pad_id", 0),

@@ -297,6 +297,38 @@ int crs_fuse_rrf(const int64_t* dense_rows_dev, int m_dense, const int64_t* lex_
                  double w_lex, int k_out, int64_t* rows_dev, double* fused_dev, int32_t* dense_pos_dev, int32_t* lex_pos_dev,
                  int32_t* count_dev, void* stream);
 
+/* ---- tokenisation: BERT basic tokenisation + WordPiece of a batch of UTF-8 texts -- the tokenizer inside SentenceTransformer.encode,
+ * rag/embedding.py:65 (additive to ABI 3; csrc/wordpiece.hip).  One workgroup per text; the tables are built by rag/_wordpiece.py.
+ *   text_dev       uint8 [n_bytes]          the texts' UTF-8 bytes, one after the other
+ *   offsets_dev    int64 [n_texts + 1]      text i is bytes [offsets[i], offsets[i + 1]); clamped into [0, n_bytes]
+ *   table_dev      uint32 [table_len]       one entry per code point: bits 0-2 class (0 drop, 1 white space, 2 a word of its own,
+ *                                           3 keep, 4 fallback) | bits 3-4 n, the replacement's length (0-3) | bits 5-7 "is
+ *                                           punctuation" of each replacement code point | bits 8-31 the replacement (n = 1) or
+ *                                           its offset in rep_pool_dev (n >= 2).  A code point >= table_len counts as fallback
+ *   rep_pool_dev   uint32 [rep_pool_len]    the replacements of two and three code points
+ *   slots_dev      int32 [n_slots, 4]       the vocabulary, open addressing with linear probing, n_slots a power of two, 16-byte
+ *                                           aligned: {offset in vocab_pool_dev, length | continuation << 31, id, hash}; length 0 =
+ *                                           empty.  hash = FNV-1a (32 bit) over the code points from 2166136261 (a word's first
+ *                                           piece) or 2166136261 ^ 0x9E3779B9 (a '##' piece); home slot (hash ^ hash >> 15) & (n_slots - 1)
+ *   vocab_pool_dev uint32 [vocab_pool_len]  the pieces' code points, without the '##'
+ *   max_probe      slots a lookup looks at before it gives up (the longest probe sequence of the built table); 1..n_slots
+ *   lmax           code points of the longest piece; 1..100
+ *   mode           0 WordPiece (a word of more than 100 code points, or with a position no piece matches, is unk_id);
+ *                  1 one id per word, hash_lo + crc32(the word's UTF-8) % hash_span (zlib's CRC-32); the vocabulary is not read
+ *   ids_dev   int32 [n_texts, max_len]  out: cls_id, the first max_len - 2 ids, sep_id, then pad_id
+ *   lens_dev  int32 [n_texts]           out: ids before the padding (2..max_len)
+ *   flags_dev int32 [n_texts]           out: 1 = the text holds a fallback code point in the part that was read; its row is to be
+ *                                       ignored and the text tokenised on the host
+ * A text is read only until max_len - 2 ids exist.  Malformed UTF-8 or tables give wrong ids, never an access outside the buffers.
+ * Limits (CRS_EINVAL otherwise): n_texts >= 0 (0: no launch); 2 <= max_len <= 65536; hash_span >= 1 in mode 1.
+ * Deterministic; no workspace, no host synchronisation. */
+#define CRS_WORDPIECE_TILE_BYTES 1024   /* bytes of a text staged at a time (tests aim at the boundaries) */
+int crs_wordpiece_encode(const uint8_t* text_dev, const int64_t* offsets_dev, int n_texts, int64_t n_bytes, const uint32_t* table_dev,
+                         int64_t table_len, const uint32_t* rep_pool_dev, int64_t rep_pool_len, const int32_t* slots_dev, int64_t n_slots,
+                         const uint32_t* vocab_pool_dev, int64_t vocab_pool_len, int max_probe, int lmax, int mode, int unk_id, int cls_id,
+                         int sep_id, int pad_id, int hash_lo, int hash_span, int max_len, int32_t* ids_dev, int32_t* lens_dev,
+                         int32_t* flags_dev, void* stream);
+
 /* ---- BERTScore token matching: the step behind the encoder in bert_score.score -- evaluation/retrieval/rag_metrics.py:179-207 ----
  * (additive to ABI 3; csrc/token_match.hip).  Scores `n_pairs` (candidate, reference) pairs of token states in one launch, one
  * workgroup per pair:
