@@ -48,6 +48,24 @@
 // + 6 for the exchange); the list's registers halve, which is what lets <384, 8, 24> keep the deferred accumulators of the stagger
 // (wide_stagger<>).
 
+//
+// 16x16x32 form (scan_wide16_kernel; the split-list forms of the 8-wave kernel on 256- / 384-element rows).  The same launch on
+// v_mfma_f32_16x16x32_f16: staging, tile schedule, tickets, nt stream, stagger and the partial-list layout are those above (one
+// body, scan_wide_body<.., S16>); what differs is the arithmetic's shape and, with it, which lanes hold what.
+//   * a wave's 32 queries are two column groups g of 16; lane (n = l & 15, kq = l >> 4) holds Q[16 g + n][32 ks + 8 kq .. + 8]
+//     for both groups and every k-step ks < D / 32 -- the same D / 4 registers;
+//   * the A fragment is scan_tb.hip's: row 16 rt + (l & 15) of the tile's four 16-row blocks, chunk 4 ks + kq through the same
+//     swizzle; every fragment read feeds two MFMAs, one per group.  The k-step is the OUTER loop, so eight accumulators
+//     (4 row blocks x 2 groups) are in flight and no MFMA waits for its neighbour, and the fragments of k-step ks + 1 are read
+//     while those of ks are multiplied (pinned with sched_group_barrier: one ds_read_b128 per pair of MFMAs);
+//   * each accumulator sums its k-steps in ascending order from zero: tile_rescore_f16's arithmetic (tail_steps.h), so a
+//     representative is bit for bit the score the tail's re-score gives its row;
+//   * result layout: lane (n, kq) holds rows 16 rt + 4 kq + i of the tile for queries n and 16 + n.  The lane quad of column n
+//     serves both: lanes kq = 0, 1 keep the split list of group 0's query, lanes 2, 3 of group 1's -- the pair is (l, l ^ 16),
+//     kq & 1 the half, and the lower half's last slot crosses by v_permlane16_swap instead of v_permlane32_swap.  The list
+//     algorithm (insert_shift) and its proof are unchanged: they only speak of "the two lanes of the pair".
+// Which shape a form runs is wide_default_mfma() below, set from A/B runs by wall time; CRS_WIDE_MFMA=16 | 32 overrides it.
+
 #include "scan_common.h"
 
 #include <stdlib.h>
@@ -102,10 +120,24 @@ struct WCfg {
   static_assert(kTileBytes % (kThreadsW * 16) == 0, "tile must split into whole 16-byte loads");
 };
 
-// (one look-ahead tile per workgroup: a second one measured no faster -- the kernel is LDS- / barrier-bound, below)
+// The forms that exist in both MFMA shapes ("16x16x32 form" in the header): the split-list forms of the 8-wave kernel on 256- and
+// 384-element rows, i.e. what a sweep group launches.
 template <int D, int NW, int K>
-__global__ __launch_bounds__(NW * 64, 2) void scan_wide_kernel(const ScanArgs a) {
+constexpr bool wide_has_16() { return NW == 8 && (D == 256 || D == 384) && wide_split<K>(); }
+
+// a tile's scores in one wave: 32x32x16 -- RB blocks of 32 rows x 32 queries; 16x16x32 -- 2 RB blocks of 16 rows x 2 groups of 16 queries
+template <int RB, bool S16>
+struct WAcc { f32x16 a[RB]; };
+template <int RB>
+struct WAcc<RB, true> { f32x4 a[2 * RB][2]; };
+
+// The body of both kernels; S16 picks the compute form (MFMA shape, fragment layout, which lanes hold a query's list).
+// The arguments come by value as they come to a kernel: taken by reference, scan_wide_kernel<384, 8, 24> spilled 20 bytes per lane.
+// (one look-ahead tile per workgroup: a second one measured no faster -- the kernel is LDS- / barrier-bound, below)
+template <int D, int NW, int K, bool S16>
+__device__ __forceinline__ void scan_wide_body(const ScanArgs a) {
   using C = WCfg<D, NW>;
+  static_assert(!S16 || wide_has_16<D, NW, K>(), "the 16x16x32 form exists for the split-list forms of 64-row tiles only");
   constexpr int kT = C::kThreadsW;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* tile_buf = smem;
@@ -168,10 +200,15 @@ __global__ __launch_bounds__(NW * 64, 2) void scan_wide_kernel(const ScanArgs a)
   int tn = t + nwg;     // the look-ahead tile (t_dyn >= 2 nwg: static for the first iteration)
   dma_tile(t, 0);   // goes out before the query fragments are fetched, so the two latencies overlap
 
-  // ---- this wave's 32 queries, full depth, as B fragments: lane (n = l & 31, h = l >> 5) holds
-  // Q[n][16 ks + 8 h .. + 8] for every k-step
-  const int qn = lane & 31, h = lane >> 5;
-  const int qi = qblock * (NW * 32) + wave * 32 + qn;
+  // ---- this wave's 32 queries, full depth, as B fragments.  32x32x16: lane (n = l & 31, h = l >> 5) holds
+  // Q[n][16 ks + 8 h .. + 8] for every k-step ks < D / 16.  16x16x32: two column groups g of 16 queries; lane (n = l & 15,
+  // kq = l >> 4) holds Q[16 g + n][32 ks + 8 kq .. + 8] for both groups and every k-step ks < D / 32, group g at qf[g * D/32 + ks]
+  // -- the same D / 4 registers.  The query whose LIST the lane keeps (qi) is query n of the wave in the lane pair (l, l ^ 32),
+  // resp. query 16 (kq >> 1) + n in the lane pair (l, l ^ 16); h is the lane's half of that pair.
+  constexpr int KS16 = D / 32;
+  const int kq = lane >> 4;
+  const int qn = S16 ? (lane & 15) : (lane & 31), h = S16 ? (kq & 1) : (lane >> 5);
+  const int qi = qblock * (NW * 32) + wave * 32 + (S16 ? 16 * (kq >> 1) : 0) + qn;
   const bool q_valid = qi < a.nq;
   f16x8 qf[C::kKsteps];
   {
@@ -209,11 +246,24 @@ __global__ __launch_bounds__(NW * 64, 2) void scan_wide_kernel(const ScanArgs a)
             const int c = j * 64 + lane, q = c >> 3, col = c & 7;
             *reinterpret_cast<u32x4*>(qs + q * 128 + ((col ^ ((q >> 1) & 7)) * 16)) = tmp[p * 4 + j];
           }
+          if constexpr (S16) {   // chunk 4 kk + kq of the block, rows n and 16 + n; a group's fragments are zero from its first query past nq
 #pragma unroll
-          for (int ksl = 0; ksl < 4; ++ksl) {
-            const int col = 2 * ksl + h;
-            const f16x8 v = *reinterpret_cast<const f16x8*>(qs + qn * 128 + ((col ^ ((qn >> 1) & 7)) * 16));
-            qf[(g0 + p) * 4 + ksl] = q_valid ? v : z;
+            for (int g = 0; g < 2; ++g) {
+              const int row = 16 * g + qn;
+#pragma unroll
+              for (int kk = 0; kk < 2; ++kk) {
+                const int col = 4 * kk + kq;
+                const f16x8 v = *reinterpret_cast<const f16x8*>(qs + row * 128 + ((col ^ ((row >> 1) & 7)) * 16));
+                qf[g * KS16 + (g0 + p) * 2 + kk] = (q0 + row < a.nq) ? v : z;
+              }
+            }
+          } else {
+#pragma unroll
+            for (int ksl = 0; ksl < 4; ++ksl) {
+              const int col = 2 * ksl + h;
+              const f16x8 v = *reinterpret_cast<const f16x8*>(qs + qn * 128 + ((col ^ ((qn >> 1) & 7)) * 16));
+              qf[(g0 + p) * 4 + ksl] = q_valid ? v : z;
+            }
           }
         }
       }
@@ -225,10 +275,11 @@ __global__ __launch_bounds__(NW * 64, 2) void scan_wide_kernel(const ScanArgs a)
       qf[ks] = x;
     }
   }
-  // A fragment of k-step ks: row (l & 31) of the tile, 16-byte chunk 2 ks + h, through the swizzle
-  int a_off[8];
+  // A fragment of k-step ks: row (l & 31) of the tile, 16-byte chunk 2 ks + h, through the swizzle; 16x16x32 (as scan_tb.hip):
+  // row 16 rt + (l & 15) of the tile's four 16-row blocks, chunk 4 ks + kq
+  int a_off[S16 ? 4 : 8];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) a_off[j] = qn * (C::kCpr * 16) + (((2 * j + h) ^ qn) & 15) * 16;
+  for (int j = 0; j < (S16 ? 4 : 8); ++j) a_off[j] = qn * (C::kCpr * 16) + ((((S16 ? 4 * j + kq : 2 * j + h)) ^ qn) & 15) * 16;
 
   // this lane's KL best tiles so far as (best score, first row), sorted by score; split forms: this half's KL ranks of the pair's list
   constexpr bool kSplit = wide_split<K>();
@@ -280,22 +331,58 @@ __global__ __launch_bounds__(NW * 64, 2) void scan_wide_kernel(const ScanArgs a)
   // in registers across the barrier): on every SIMD one wave multiplies while the other selects.
   // (split forms: CRS_WIDE_STAGGER=0 arrives as a.no_stagger, a kernel argument -- A/B runs; the lists do not depend on it)
   const bool late = wide_stagger<D, NW, K>() && wave >= 4 && !(kSplit && a.no_stagger);   // wave-uniform; off where the deferred accumulators would spill
-  struct Acc { f32x16 a[RB]; };
+  using Acc = WAcc<RB, S16>;
+  auto zero = [&](Acc& acc) {
+    if constexpr (S16) {
+#pragma unroll
+      for (int rt = 0; rt < 2 * RB; ++rt)
+#pragma unroll
+        for (int g = 0; g < 2; ++g) acc.a[rt][g] = f32x4{0.f, 0.f, 0.f, 0.f};
+    } else {
+#pragma unroll
+      for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc.a[rb][r] = 0.f;
+    }
+  };
   Acc acc_prev;
-#pragma unroll
-  for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc_prev.a[rb][r] = 0.f;
+  zero(acc_prev);
   auto sweep = [&](const char* buf) {
     Acc acc;
+    zero(acc);
+    if constexpr (S16) {
+      // k-step outermost: 2 RB x 2 accumulators in flight, neighbouring MFMAs never depend on each other, and every A fragment
+      // feeds two of them (one per query group).  Each accumulator sums its k-steps in ascending order from zero, which is the
+      // arithmetic of the tail's re-score (tail_steps.h, tile_rescore_f16): a representative is bit for bit its row's re-score.
+      // The fragments of k-step ks + 1 are fetched while those of ks are multiplied (two sets of 2 RB); the group barriers pin
+      // that order, one ds_read_b128 in front of each pair of MFMAs -- left to itself the scheduler fetches a dozen fragments
+      // ahead and then funnels the rest through one register quad, a read, a full wait and two MFMAs at a time.
+      auto frag = [&](int ks, int rt) {
+        return *reinterpret_cast<const f16x8*>(buf + rt * 16 * (C::kCpr * 16) + a_off[ks & 3] + (ks >> 2) * 256);
+      };
+      f16x8 af[2][2 * RB];
 #pragma unroll
-    for (int rb = 0; rb < RB; ++rb) {
+      for (int rt = 0; rt < 2 * RB; ++rt) af[0][rt] = frag(0, rt);
+      __builtin_amdgcn_sched_group_barrier(0x100, 2 * RB, 0);   // the first set's reads
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc.a[rb][r] = 0.f;
+      for (int ks = 0; ks < KS16; ++ks) {
 #pragma unroll
-      for (int ks = 0; ks < C::kKsteps; ++ks) {
-        const f16x8 af = *reinterpret_cast<const f16x8*>(buf + rb * 32 * (C::kCpr * 16) + a_off[ks & 7] + (ks >> 3) * 256);
-        acc.a[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, qf[ks], acc.a[rb], 0, 0, 0);
+        for (int rt = 0; rt < 2 * RB; ++rt) {
+          if (ks + 1 < KS16) af[(ks + 1) & 1][rt] = frag(ks + 1, rt);
+          acc.a[rt][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[ks & 1][rt], qf[ks], acc.a[rt][0], 0, 0, 0);
+          acc.a[rt][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[ks & 1][rt], qf[KS16 + ks], acc.a[rt][1], 0, 0, 0);
+          if (ks + 1 < KS16) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // one LDS read
+          __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);                      // two MFMAs
+        }
+      }
+    } else {
+#pragma unroll
+      for (int rb = 0; rb < RB; ++rb) {
+#pragma unroll
+        for (int ks = 0; ks < C::kKsteps; ++ks) {
+          const f16x8 af = *reinterpret_cast<const f16x8*>(buf + rb * 32 * (C::kCpr * 16) + a_off[ks & 7] + (ks >> 3) * 256);
+          acc.a[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, qf[ks], acc.a[rb], 0, 0, 0);
+        }
       }
     }
     return acc;
@@ -305,38 +392,77 @@ __global__ __launch_bounds__(NW * 64, 2) void scan_wide_kernel(const ScanArgs a)
   // equal scores the lower tile holds the lower rows and no arg-max is needed (scan_refine.hip).
   auto select = [&](const Acc& accs, int te, int ie) {
     float x = kNegInf;
+    if constexpr (S16) {
+      // lane (n, kq) holds rows 16 rt + 4 kq + i of the tile for queries n (group 0) and 16 + n (group 1)
+      float xg[2] = {kNegInf, kNegInf};
 #pragma unroll
-    for (int rb = 0; rb < RB; ++rb) {
-      const f32x16& acc = accs.a[rb];
-      if (te < n_full) {
-        const float m0 = __builtin_fmaxf(__builtin_fmaxf(acc[0], acc[1]), acc[2]);
-        const float m1 = __builtin_fmaxf(__builtin_fmaxf(acc[3], acc[4]), acc[5]);
-        const float m2 = __builtin_fmaxf(__builtin_fmaxf(acc[6], acc[7]), acc[8]);
-        const float m3 = __builtin_fmaxf(__builtin_fmaxf(acc[9], acc[10]), acc[11]);
-        const float m4 = __builtin_fmaxf(__builtin_fmaxf(acc[12], acc[13]), acc[14]);
-        x = __builtin_fmaxf(x, __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(m0, m1), __builtin_fmaxf(m2, m3)), __builtin_fmaxf(m4, acc[15])));
-      } else {   // ragged last tile: rows past the end must not win
-        const int row_base = te * WTR + rb * 32 + 4 * h;
+      for (int g = 0; g < 2; ++g) {
+        if (te < n_full) {
+          float m[2 * RB];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = row_base + 8 * (r >> 2) + (r & 3);
-          x = (row < a.n_rows) ? __builtin_fmaxf(x, acc[r]) : x;
+          for (int rt = 0; rt < 2 * RB; ++rt) {
+            const f32x4& c = accs.a[rt][g];
+            m[rt] = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(c[0], c[1]), c[2]), c[3]);
+          }
+#pragma unroll
+          for (int rt = 0; rt < 2 * RB; rt += 2) xg[g] = __builtin_fmaxf(__builtin_fmaxf(xg[g], m[rt]), m[rt + 1]);
+        } else {   // ragged last tile: rows past the end must not win
+#pragma unroll
+          for (int rt = 0; rt < 2 * RB; ++rt) {
+            const int row0 = te * WTR + 16 * rt + 4 * kq;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) xg[g] = (row0 + i < a.n_rows) ? __builtin_fmaxf(xg[g], accs.a[rt][g][i]) : xg[g];
+          }
         }
       }
-    }
-    x = pair_max(x);                              // both halves: the tile's best
-    if constexpr (kSplit) {
-      // the lower half's last slot as it stands, in the upper half's lanes (low-half broadcast of v_permlane32_swap)
-      const float ps = __uint_as_float(__builtin_amdgcn_permlane32_swap(__float_as_uint(ts[KL - 1]), __float_as_uint(ts[KL - 1]), false, false)[0]);
-      const int prow = (int)__builtin_amdgcn_permlane32_swap((unsigned)tr[KL - 1], (unsigned)tr[KL - 1], false, false)[0];
-      const bool c = h && x > ps;                 // upper half: what the lower half pushes out -- its old last slot, or x itself
+      // The lane quad of column n serves both queries: lanes kq = 0, 1 keep the list of group 0's, lanes 2, 3 of group 1's.
+      // Per group the max over (l, l ^ 16) in all four lanes, then ONE half exchange hands each half of the wave the other half's
+      // value of the group it keeps: lanes 32 .. 63 of y0 <-> lanes 0 .. 31 of y1.  (a quad_max per group, one swap less)
+      const auto r0 = __builtin_amdgcn_permlane16_swap(__float_as_uint(xg[0]), __float_as_uint(xg[0]), false, false);
+      const auto r1 = __builtin_amdgcn_permlane16_swap(__float_as_uint(xg[1]), __float_as_uint(xg[1]), false, false);
+      const float y0 = __builtin_fmaxf(__uint_as_float(r0[0]), __uint_as_float(r0[1]));
+      const float y1 = __builtin_fmaxf(__uint_as_float(r1[0]), __uint_as_float(r1[1]));
+      const auto rr = __builtin_amdgcn_permlane32_swap(__float_as_uint(y0), __float_as_uint(y1), false, false);
+      x = __builtin_fmaxf(__uint_as_float(rr[0]), __uint_as_float(rr[1]));   // all four rows of lanes: the tile's best for the lane's query
+      // the lower half's last slot as it stands, in both lanes of the pair (l, l ^ 16): the even-row value of v_permlane16_swap
+      const float ps = __uint_as_float(__builtin_amdgcn_permlane16_swap(__float_as_uint(ts[KL - 1]), __float_as_uint(ts[KL - 1]), false, false)[0]);
+      const int prow = (int)__builtin_amdgcn_permlane16_swap((unsigned)tr[KL - 1], (unsigned)tr[KL - 1], false, false)[0];
+      const bool c = h && x > ps;                   // upper half: what the lower half pushes out -- its old last slot, or x itself
       insert_shift(x, c ? ps : x, c ? prow : te * WTR);
-    } else {
-      if ((ie & 1) == h) { px = x; pr = te * WTR; } // lane half h is responsible for the tiles of parity h
-      if (ie & 1) {
-        insert(px, pr);
-        px = kNegInf;
-        pr = -1;
+    } else {   // 32x32x16
+#pragma unroll
+      for (int rb = 0; rb < RB; ++rb) {
+        const f32x16& acc = accs.a[rb];
+        if (te < n_full) {
+          const float m0 = __builtin_fmaxf(__builtin_fmaxf(acc[0], acc[1]), acc[2]);
+          const float m1 = __builtin_fmaxf(__builtin_fmaxf(acc[3], acc[4]), acc[5]);
+          const float m2 = __builtin_fmaxf(__builtin_fmaxf(acc[6], acc[7]), acc[8]);
+          const float m3 = __builtin_fmaxf(__builtin_fmaxf(acc[9], acc[10]), acc[11]);
+          const float m4 = __builtin_fmaxf(__builtin_fmaxf(acc[12], acc[13]), acc[14]);
+          x = __builtin_fmaxf(x, __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(m0, m1), __builtin_fmaxf(m2, m3)), __builtin_fmaxf(m4, acc[15])));
+        } else {   // ragged last tile: rows past the end must not win
+          const int row_base = te * WTR + rb * 32 + 4 * h;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int row = row_base + 8 * (r >> 2) + (r & 3);
+            x = (row < a.n_rows) ? __builtin_fmaxf(x, acc[r]) : x;
+          }
+        }
+      }
+      x = pair_max(x);                              // both halves: the tile's best
+      if constexpr (kSplit) {
+        // the lower half's last slot as it stands, in the upper half's lanes (low-half broadcast of v_permlane32_swap)
+        const float ps = __uint_as_float(__builtin_amdgcn_permlane32_swap(__float_as_uint(ts[KL - 1]), __float_as_uint(ts[KL - 1]), false, false)[0]);
+        const int prow = (int)__builtin_amdgcn_permlane32_swap((unsigned)tr[KL - 1], (unsigned)tr[KL - 1], false, false)[0];
+        const bool c = h && x > ps;                 // upper half: what the lower half pushes out -- its old last slot, or x itself
+        insert_shift(x, c ? ps : x, c ? prow : te * WTR);
+      } else {
+        if ((ie & 1) == h) { px = x; pr = te * WTR; } // lane half h is responsible for the tiles of parity h
+        if (ie & 1) {
+          insert(px, pr);
+          px = kNegInf;
+          pr = -1;
+        }
       }
     }
   };
@@ -424,10 +550,23 @@ __global__ __launch_bounds__(NW * 64, 2) void scan_wide_kernel(const ScanArgs a)
 }
 
 template <int D, int NW, int K>
+__global__ __launch_bounds__(NW * 64, 2) void scan_wide_kernel(const ScanArgs a) {
+  scan_wide_body<D, NW, K, false>(a);
+}
+// the 16x16x32 form of the same launch: same grid, same LDS, same partial lists
+template <int D, int NW, int K>
+__global__ __launch_bounds__(NW * 64, 2) void scan_wide16_kernel(const ScanArgs a) {
+  scan_wide_body<D, NW, K, true>(a);
+}
+
+template <int D, int NW, int K, bool S16>
 int launch_wide(const ScanArgs& a, hipStream_t stream) {
   using C = WCfg<D, NW>;
   static bool done = false;
-  auto kernel = &scan_wide_kernel<D, NW, K>;
+  auto kernel = [] {
+    if constexpr (S16) return &scan_wide16_kernel<D, NW, K>;
+    else return &scan_wide_kernel<D, NW, K>;
+  }();
   if (!done) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, C::kLds);
@@ -438,22 +577,43 @@ int launch_wide(const ScanArgs& a, hipStream_t stream) {
   return (int)hipGetLastError();
 }
 
+// MFMA shape of a form that exists in both (wide_has_16): what measured faster by wall time on random data, the shapes
+// alternated on one device, every run of the one ahead of every run of the other and the medians at least 5 x the larger
+// spread apart (profiles/r13_bench_c4_ab.jsonl, profiles/r13_forms_ab.jsonl).  384-element rows
+// cleared that at both chain lengths; 256-element rows were 5 - 8 % faster on 16x16x32 but within 1.4 - 3.2 x the spread, and stay.
+struct WideShape { int d, k, mfma; };
+constexpr WideShape kWideShapes[] = {{384, 24, 16}, {384, 32, 16}, {256, 24, 32}, {256, 32, 32}};
+constexpr int wide_default_mfma(int d, int k) {
+  for (const WideShape& w : kWideShapes)
+    if (w.d == d && w.k == k) return w.mfma;
+  return 32;
+}
+
+// shape: 16 / 32 forces the shape where the form has both (CRS_WIDE_MFMA), 0 = the table above
+template <int D, int NW, int K>
+int launch_wide_s(const ScanArgs& a, int shape, hipStream_t stream) {
+  if constexpr (wide_has_16<D, NW, K>()) {
+    if ((shape ? shape : wide_default_mfma(D, K)) == 16) return launch_wide<D, NW, K, true>(a, stream);
+  }
+  return launch_wide<D, NW, K, false>(a, stream);
+}
+
 template <int D, int NW>
-int launch_wide_k(const ScanArgs& a, hipStream_t stream) {
+int launch_wide_k(const ScanArgs& a, int shape, hipStream_t stream) {
   const int kk = scan_wide_slots(a.k);
-  if (kk == 4) return launch_wide<D, NW, 4>(a, stream);
-  if (kk == 10) return launch_wide<D, NW, 10>(a, stream);
-  if (kk == 16) return launch_wide<D, NW, 16>(a, stream);
+  if (kk == 4) return launch_wide<D, NW, 4, false>(a, stream);
+  if (kk == 10) return launch_wide<D, NW, 10, false>(a, stream);
+  if (kk == 16) return launch_wide<D, NW, 16, false>(a, stream);
   if constexpr (D <= 384) {   // no scratch in any of them: tools/check_resources.py, profiles/r07_wide_resources.txt
-    if (kk == 24) return launch_wide<D, NW, 24>(a, stream);
-    if (kk == 32) return launch_wide<D, NW, 32>(a, stream);
+    if (kk == 24) return launch_wide_s<D, NW, 24>(a, shape, stream);
+    if (kk == 32) return launch_wide_s<D, NW, 32>(a, shape, stream);
   }
   return -1;
 }
 
 template <int D>
-int launch_wide_d(const ScanArgs& a, int nw, hipStream_t stream) {
-  return nw == 8 ? launch_wide_k<D, 8>(a, stream) : launch_wide_k<D, 4>(a, stream);
+int launch_wide_d(const ScanArgs& a, int nw, int shape, hipStream_t stream) {
+  return nw == 8 ? launch_wide_k<D, 8>(a, shape, stream) : launch_wide_k<D, 4>(a, shape, stream);
 }
 
 }  // namespace
@@ -479,15 +639,18 @@ bool scan_wide_streamed(int k) { return scan_wide_slots(k) > 16; }
 int scan_wide_wg_per_cu(int nw, int pdim) { return nw == 8 ? 1 : 2; }
 
 // CRS_WIDE_STAGGER=0: waves 4..7 of the split forms select in step with waves 0..3 (A/B runs).  Read per call.
+// CRS_WIDE_MFMA=16 | 32: the MFMA shape of the forms that exist in both, over the table (A/B runs, tests).  Read per call.
 int scan_launch_wide(const ScanArgs& a_, int pdim, int nw, hipStream_t stream) {
   ScanArgs a = a_;
   const char* se = getenv("CRS_WIDE_STAGGER");
   a.no_stagger = (se && se[0] == '0') ? 1 : 0;
+  const char* me = getenv("CRS_WIDE_MFMA");
+  const int shape = !me ? 0 : (me[0] == '1' && me[1] == '6' && !me[2]) ? 16 : (me[0] == '3' && me[1] == '2' && !me[2]) ? 32 : 0;
   switch (pdim) {
-    case 128: return launch_wide_d<128>(a, nw, stream);
-    case 256: return launch_wide_d<256>(a, nw, stream);
-    case 384: return launch_wide_d<384>(a, nw, stream);
-    case 512: return launch_wide_d<512>(a, nw, stream);
+    case 128: return launch_wide_d<128>(a, nw, shape, stream);
+    case 256: return launch_wide_d<256>(a, nw, shape, stream);
+    case 384: return launch_wide_d<384>(a, nw, shape, stream);
+    case 512: return launch_wide_d<512>(a, nw, shape, stream);
     default: return -1;
   }
 }

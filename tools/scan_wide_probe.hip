@@ -2,7 +2,8 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -o scan_wide_probe scan_wide_probe.hip
 //   ./scan_wide_probe <rows> <dim> <nq> <k>
 // The 24- / 32-slot forms run as the product launches them: nt stream for slabs of 1 GB and more, ticketed tile schedule on long
-// streams (85 % of the tiles in granules of 8; CRS_WIDE_DYN=0: static stride), CRS_WIDE_STAGGER as in the library.
+// streams (85 % of the tiles in granules of 8; CRS_WIDE_DYN=0: static stride), CRS_WIDE_STAGGER and CRS_WIDE_MFMA as in the library.
+// The last line is the clock the chip held inside the kernel: a wave's cycles over the launch / the launch's time.
 #define CRS_STAMPS 1
 #include "../compressed-rag-suite_amd/csrc/scan_wide.hip"
 
@@ -73,8 +74,9 @@ int main(int argc, char** argv) {
   std::vector<unsigned long long> hs(nst);
   hipMemcpy(hs.data(), st, nst * 8, hipMemcpyDeviceToHost);
   const char* se = getenv("CRS_WIDE_STAGGER");
-  printf("rows %d dim %d nq %d k %d | waves/wg %d nqb %d streams %d tiles/stream %.1f nt %d tickets %s stagger-knob %s | kernel %.1f us (with stamps)\n", rows, dim, nq,
-         k, nw, nqb, nwg, (double)n_tiles / nwg, a.nt, ticket ? "on" : "off", (se && se[0] == '0') ? "0" : "default", ms * 1e3);
+  const char* me = getenv("CRS_WIDE_MFMA");
+  printf("rows %d dim %d nq %d k %d | waves/wg %d nqb %d streams %d tiles/stream %.1f nt %d tickets %s stagger-knob %s mfma-knob %s | kernel %.1f us (with stamps)\n", rows, dim, nq,
+         k, nw, nqb, nwg, (double)n_tiles / nwg, a.nt, ticket ? "on" : "off", (se && se[0] == '0') ? "0" : "default", me ? me : "default", ms * 1e3);
   // slots 2 / 4: the selection of waves 4..7 (deferred one tile) / of waves 0..3; 5, 8, 9: unused since the tile-best rewrite
   const char* names[12] = {"prologue", "tile-load issue", "selection (waves 4-7, deferred)", "MFMA sweep", "selection (waves 0-3)", "(unused)",
                            "wait next tile + LDS store", "barrier", "(unused)", "(unused)", "final flush", "TOTAL"};
@@ -92,6 +94,7 @@ int main(int argc, char** argv) {
     double sum = 0; for (double x : v) sum += x;
     printf("  %-31s mean %9.0f  median %9.0f  max %9.0f | per tile: waves 0-3 %7.0f  waves 4-7 %7.0f\n", names[i], sum / nwaves, v[nwaves / 2], v.back(),
            half[0] / (nh[0] ? nh[0] : 1) / tps, half[1] / (nh[1] ? nh[1] : 1) / tps);
+    if (i == 11) printf("  in-kernel clock (median TOTAL cycles / kernel time): %.3f GHz\n", v[nwaves / 2] / (ms * 1e6));
   }
   return 0;
 }
