@@ -3,9 +3,9 @@
 
 #include <hip/hip_runtime.h>
 #include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 
+#include "plan.h"
 #include "scan.h"
 
 namespace {
@@ -36,70 +36,22 @@ int device_cus() {
   return cus[dev];
 }
 
-constexpr int kW1MaxDump = 256;
-// streams shorter than this many tiles keep the static stride (1.25 M x 384 rows = 76 tiles per stream measured no gain)
-constexpr int kDynMinRounds = 96;
+using crs::Plan;
 
-struct Plan {
-  int pdim, tile_rows, n_tiles, nwg, kp;   // nwg = tile streams (workgroups per query block)
-  int nqb;                                 // query blocks (64 queries each; 32 * wide_nw for the wide kernel)
-  int wide_nw;                             // > 0: scan_wide.hip with this many waves per workgroup
-  int w1_qg;                               // > 0: scan_w1.hip, this many queries per workgroup (dump selection)
-  int i8_tb;                               // 1: scan_i8.hip in a tile-best mode (tb_slots: 0 dump, else chain)
-  int tb_nw;                               // > 0: scan_tb.hip with this many waves per workgroup
-  int tb_slots;                            //   its chain length (0: dump mode)
-  int group_best;                          // 1: the scan leaves tile representatives (scan_refine.hip finishes)
-  int nt;                                  // 1: slab tiles streamed non-temporal (scan_tb / scan_i8; scan_nt_policy)
-  size_t part_elems;  // nwg * nq * kp
-};
-
-// slots per (query, workgroup) partial list: k, or 16 when threshold sharing is on (lists may then be
-// dumped unselected)
-int partial_width(int k) { return (crs::scan_share_tau() && k <= 16) ? 16 : k; }
-
-bool tb_long_chain() {   // CRS_SCAN_LONG_CHAIN=0: 16 < k <= 64 on long streams back on the threshold kernels (A/B, tests)
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("CRS_SCAN_LONG_CHAIN"); v = (e && e[0] == '0') ? 0 : 1; }
-  return v == 1;
-}
-// Dynamic tile schedule of the chain-mode tile-best scan (scan_tb.hip): percent of the tiles handed out through the counter and
-// tiles per ticket.  Defaults 85 % in granules of 8 (C4 beside the encoder lanes: 44.9 -> 47.2 k q/s on one box; 20 / 50 / 95 / 100 %
-// and granules of 4 / 16 measured within 1 % of that or worse; a ticket per tile is bound by the ~90 M atomics/s one address
-// takes).  CRS_TB_DYN=0 restores the static stride.  Read per call: tools/tb_dyn_check.py switches it inside one process.
-int tb_dyn_percent() {
-  const char* e = getenv("CRS_TB_DYN");
-  const int v = e ? atoi(e) : 85;
-  return v < 0 ? 0 : v > 100 ? 100 : v;
-}
-int tb_dyn_granule() {
-  const char* e = getenv("CRS_TB_DYN_G");
-  const int v = e ? atoi(e) : 8;
-  return v >= 16 ? 16 : v >= 8 ? 8 : v >= 4 ? 4 : v >= 2 ? 2 : 1;
-}
-// The same schedule in scan_wide.hip's 24- / 32-slot forms.  CRS_WIDE_DYN=0 keeps their static stride (A/B runs).  Read per call.
-bool wide_dyn_enabled() {
-  const char* e = getenv("CRS_WIDE_DYN");
-  return !(e && e[0] == '0');
-}
-bool tb_enabled() {   // CRS_SCAN_TB=0: always use the threshold/compaction kernel for <= 64 queries (A/B runs, tests)
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("CRS_SCAN_TB"); v = (e && e[0] == '0') ? 0 : 1; }
-  return v == 1;
+// the plan of a search on the current device with the environment's knobs; sets the error text
+int plan_for(int nq, int dim, int k, int64_t n_rows, int slab_type, Plan* p) {
+  const char* why = "";
+  const int rc = crs::make_plan(nq, dim, k, n_rows, slab_type, device_cus(), crs::knobs_from_env(), p, &why);
+  return rc ? fail(rc, "%s", why) : CRS_OK;
 }
 
 // The search tail after the scan: finish.hip's one kernel (merge + tile re-score + fp32 re-rank + certificate) where the plan
-// fits it, else the three-kernel chain.  CRS_FUSED_TAIL=0 forces the chain (tests compare the two); read per call.
-bool fused_tail(const Plan& p, int slab_type, int k_in) {
-  return slab_type == CRS_SLAB_F16 && p.group_best && crs::finish_fits(p.nwg, p.kp, k_in, p.tile_rows, p.pdim);
-}
-bool fused_tail_enabled() {
-  const char* e = getenv("CRS_FUSED_TAIL");
-  return !(e && e[0] == '0');
+// fits it, else the three-kernel chain.  CRS_FUSED_TAIL=0 forces the chain (tests compare the two).
+bool fused_tail(const Plan& p, int k_in) {
+  return p.slab_type == CRS_SLAB_F16 && p.group_best() && crs::finish_fits(p.nwg, p.kp, k_in, p.tile_rows, p.pdim);
 }
 
-// scan workspace: [shared thresholds (or the tile ticket) | partial scores | partial rows | stage-1 winners (scores, ids) |
-// two-level merge scratch (scores, ids): one k-entry list per 8192 candidates of a query (merge.hip)], each 256-byte aligned
-size_t inter_lists(size_t part_elems, int nq) { return part_elems / ((size_t)nq * 4096) + 2; }   // >= merge_slices(nwg, kp)
+// the scan workspace (plan.h: WsLayout) carved at base
 struct ScanWs {
   unsigned* tau;
   float* part_s;
@@ -108,104 +60,16 @@ struct ScanWs {
   int64_t* win_i;
   float* inter_s;
   int64_t* inter_i;
-  size_t tau_bytes, bytes;   // of the first block, of all of them
+  size_t tau_bytes;
 };
-ScanWs scan_ws(void* base, size_t part_elems, int nq, int k) {
-  const size_t inter = (size_t)nq * inter_lists(part_elems, nq) * k;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const uintptr_t at = (uintptr_t)base + off; off += align_up(bytes, 256); return at; };
-  ScanWs w;
-  w.tau = reinterpret_cast<unsigned*>(take((size_t)nq * 4));
-  w.tau_bytes = off;
-  w.part_s = reinterpret_cast<float*>(take(part_elems * 4));
-  w.part_r = reinterpret_cast<int*>(take(part_elems * 4));
-  w.win_s = reinterpret_cast<float*>(take((size_t)nq * k * 4));
-  w.win_i = reinterpret_cast<int64_t*>(take((size_t)nq * k * 8));
-  w.inter_s = reinterpret_cast<float*>(take(inter * 4));
-  w.inter_i = reinterpret_cast<int64_t*>(take(inter * 8));
-  w.bytes = off;
-  return w;
+ScanWs scan_ws(void* base, const Plan& p) {
+  const crs::WsLayout l = crs::ws_layout(p.part_elems, p.nq, p.k);
+  char* b = static_cast<char*>(base);
+  return {reinterpret_cast<unsigned*>(b + l.tau), reinterpret_cast<float*>(b + l.part_s), reinterpret_cast<int*>(b + l.part_r),
+          reinterpret_cast<float*>(b + l.win_s), reinterpret_cast<int64_t*>(b + l.win_i), reinterpret_cast<float*>(b + l.inter_s),
+          reinterpret_cast<int64_t*>(b + l.inter_i), l.tau_bytes};
 }
-size_t ws_bytes(size_t part_elems, int nq, int k) { return scan_ws(nullptr, part_elems, nq, k).bytes; }
-
-int make_plan(int nq, int dim, int k, int64_t n_rows, int slab_type, Plan* p) {
-  if (nq <= 0 || dim <= 0 || dim > 1024) return fail(CRS_EINVAL, "nq must be > 0 and 0 < dim <= 1024");
-  if (k <= 0 || k > CRS_MAX_K) return fail(CRS_EINVAL, "k must be in 1..CRS_MAX_K");
-  if (n_rows <= 0 || n_rows > 0x7fffffffLL - 64) return fail(CRS_EINVAL, "n_rows must be in 1..2^31-65");
-  const int cus = device_cus();
-  if (cus <= 0) return fail(CRS_EHIP, "no HIP device available%s");
-  p->pdim = crs_row_elems(dim, slab_type);
-  // kernel family: one of the tile-best kernels, or the classic threshold/compaction scan.  The register-chain forms
-  // hold k <= 16; the dump form (short streams) has no such limit and serves k <= 64.  For k > 16 the family is
-  // therefore only known once the stream length is: plan for tile-best first, fall back to classic if it has to chain.
-  bool allow_w1 = true;
-  for (int attempt = 0; attempt < 3; ++attempt) {
-    const bool allow_tb = attempt < 2 && tb_enabled();
-    p->w1_qg = (allow_tb && allow_w1 && slab_type == CRS_SLAB_F16) ? crs::scan_w1_queries_per_wg(nq, k, p->pdim) : 0;
-    // (16 < k <= 32 on rows of <= 384 elements too: one launch then serves up to 256 queries per sweep at the re-rank's over-fetch)
-    p->wide_nw = (allow_tb && !p->w1_qg && slab_type == CRS_SLAB_F16 && k <= 32) ? crs::scan_wide_waves(nq, k, p->pdim) : 0;
-    p->tb_nw = 0;
-    if (allow_tb && !p->w1_qg && !p->wide_nw && slab_type == CRS_SLAB_F16)
-      p->tb_nw = (nq > 64 && k <= 16 && crs::scan_tb_has_8_waves(p->pdim)) ? 8 : 4;
-    p->i8_tb = (allow_tb && slab_type == CRS_SLAB_I8) ? 1 : 0;   // scan_i8.hip's tile-best modes
-    p->tile_rows = p->w1_qg ? 32 : p->wide_nw ? crs::scan_wide_tile_rows(p->wide_nw, p->pdim) : slab_type == CRS_SLAB_I8 ? crs::scan_i8_tile_rows() : crs::scan_tile_rows(p->pdim);
-    p->n_tiles = (int)((n_rows + p->tile_rows - 1) / p->tile_rows);
-    const int cap = cus * (p->w1_qg ? 1 : p->wide_nw ? crs::scan_wide_wg_per_cu(p->wide_nw, p->pdim)
-                           : p->tb_nw ? crs::scan_tb_wg_per_cu(p->pdim, p->tb_nw) : crs::scan_wg_per_cu());
-    // all query blocks of a tile stream must be co-resident: streams = resident slots / query blocks
-    const int qpb = p->w1_qg ? p->w1_qg : p->wide_nw ? 32 * p->wide_nw : p->tb_nw ? 16 * p->tb_nw : 64;
-    const int nqb = (nq + qpb - 1) / qpb;
-    p->nqb = nqb;
-    int streams = cap / nqb;
-    if (streams < 1) streams = 1;
-    if (nqb > 1 && streams >= 8) streams &= ~7;   // whole rounds over the 8 XCDs (scan_common.h: grid mapping)
-    p->nwg = p->n_tiles < streams ? p->n_tiles : streams;
-    if (nqb > 1 && p->nwg >= 8) p->nwg &= ~7;
-    p->kp = partial_width(k);
-    p->group_best = 0;
-    p->tb_slots = 0;
-    if (p->w1_qg) {                          // dump: every tile's representative goes to the partial list
-      p->kp = (p->n_tiles + p->nwg - 1) / p->nwg;
-      p->group_best = 1;
-      // the dump's workspace and merge input grow with the shard (nq * n_rows / 32 entries): past kW1MaxDump entries per
-      // (query, stream) -- 1 M rows x 768 at 256 queries is 123 -- the bounded 8-wave chain kernels take over
-      // (10 M x 768 at 256 queries would otherwise be 640 MB of workspace and 312 k candidates per query)
-      if (p->kp > kW1MaxDump) { allow_w1 = false; continue; }
-    } else if (p->wide_nw) {   // register chain of the K best tile representatives per lane
-      p->kp = 2 * crs::scan_wide_slots(k);
-      p->group_best = 1;
-    } else if (p->tb_nw || p->i8_tb) {
-      // short streams: every tile's representative goes straight to the partial list ("dump"; merge.hip's
-      // single-pass path takes <= 8192 candidates per query); longer ones keep the K best in registers
-      const int tps = (p->n_tiles + p->nwg - 1) / p->nwg;
-      p->group_best = 1;
-      if ((size_t)tps * p->nwg <= 8192 && tps <= 2 * crs::scan_wide_slots(k)) {
-        p->kp = tps;
-      } else if (k <= 16) {
-        p->tb_slots = crs::scan_wide_slots(k);
-        p->kp = p->tb_slots;
-      } else if (tb_long_chain() && (p->i8_tb ? crs::scan_i8_long_chain_slots(p->pdim, k) : crs::scan_tb_long_chain_slots(p->pdim, p->tb_nw, k)) > 0) {
-        // 16 < k <= 64 on a long stream: the same kernels with a 32- / 64-slot chain instead of the threshold kernels,
-        // where that chain fits the register file (CRS_SCAN_LONG_CHAIN=0 restores the threshold kernels)
-        p->tb_slots = p->i8_tb ? crs::scan_i8_long_chain_slots(p->pdim, k) : crs::scan_tb_long_chain_slots(p->pdim, p->tb_nw, k);
-        p->kp = p->tb_slots;
-      } else {
-        continue;                            // the threshold kernels
-      }
-    }
-    break;
-  }
-  p->part_elems = (size_t)p->nwg * nq * p->kp;
-  // Non-temporal slab stream: a shard's slab far larger than the 256 MB Infinity Cache is read once per launch and replays
-  // from nowhere, so its tiles go nt and stop evicting what the encoder lanes beside the sweep re-read; one query block only
-  // (several blocks of a launch read every tile several times).  A 77 MB slab (C2) replays from the cache and keeps the default.
-  // CRS_SCAN_NT=0 / 1 forces the policy off / on; read per call.
-  const size_t slab_bytes = (size_t)n_rows * p->pdim * (slab_type == CRS_SLAB_I8 ? 1 : 2);
-  const char* ne = getenv("CRS_SCAN_NT");
-  const bool streamed = p->tb_nw || p->i8_tb || (p->wide_nw && crs::scan_wide_streamed(k));
-  p->nt = streamed ? ((ne && ne[0] == '0') ? 0 : (ne && ne[0] == '1') ? 1 : (slab_bytes >= ((size_t)1 << 30) && p->nqb == 1)) : 0;
-  return CRS_OK;
-}
+size_t ws_bytes(const Plan& p) { return crs::ws_layout(p.part_elems, p.nq, p.k).bytes; }
 
 }  // namespace
 
@@ -220,11 +84,7 @@ extern "C" {
 
 const char* crs_last_error(void) { return g_err; }
 int crs_abi_version(void) { return 3; }
-int crs_row_elems(int dim, int slab_type) {
-  if (dim <= 0) return 0;
-  const int g = slab_type == CRS_SLAB_I8 ? 256 : 128;
-  return (dim + g - 1) / g * g;
-}
+int crs_row_elems(int dim, int slab_type) { return crs::row_elems(dim, slab_type); }
 int crs_padded_dim(int dim) { return crs_row_elems(dim, CRS_SLAB_F16); }
 
 int crs_slab_append_f32(const float* emb_dev, int64_t n, int dim, int slab_type, void* slab_dev,
@@ -251,26 +111,14 @@ int crs_queries_to_f16(const float* q_dev, int nq, int dim, int slab_type, void*
 
 int crs_scan_workspace_bytes(int nq, int dim, int k, int64_t n_rows, size_t* bytes) {
   if (!bytes) return fail(CRS_EINVAL, "null pointer");
-  Plan p, p8;
-  int rc = make_plan(nq, dim, k, n_rows, CRS_SLAB_F16, &p);
-  if (rc) return rc;
-  rc = make_plan(nq, dim, k, n_rows, CRS_SLAB_I8, &p8);
-  if (rc) return rc;
-  // the call does not say which slab type will be searched: cover the plans of both, and the largest grid the
-  // threshold kernels can use (resident workgroups), which does not depend on n_rows
-  const size_t cap = (size_t)device_cus() * crs::scan_wg_per_cu();
-  const size_t classic = ws_bytes(cap * nq * partial_width(k), nq, k);
-  size_t planned = ws_bytes(p.part_elems, nq, k);
-  const size_t planned8 = ws_bytes(p8.part_elems, nq, k);
-  if (planned8 > planned) planned = planned8;
-  *bytes = classic > planned ? classic : planned;
-  return CRS_OK;
+  const char* why = "";
+  const int rc = crs::plan_workspace_bytes(nq, dim, k, n_rows, device_cus(), crs::knobs_from_env(), bytes, &why);
+  return rc ? fail(rc, "%s", why) : CRS_OK;
 }
 
-static int run_scan(const Plan& p, const void* q16, int nq, int slab_type, const void* slab,
-                    const float* scales, int64_t n_rows, int k, const ScanWs& ws, hipStream_t st) {
-  const bool share = crs::scan_share_tau();
-  if (share) {
+// fills the kernel arguments from the plan, zeroes what the plan says is read as zero, and calls the family's launcher
+static int run_scan(const Plan& p, const void* q16, const void* slab, const float* scales, int64_t n_rows, const ScanWs& ws, hipStream_t st) {
+  if (p.share_tau) {
     const hipError_t me = hipMemsetAsync(ws.tau, 0, ws.tau_bytes, st);
     if (me != hipSuccess) return (int)me;
   }
@@ -280,66 +128,43 @@ static int run_scan(const Plan& p, const void* q16, int nq, int slab_type, const
   a.scales = scales;
   a.part_scores = ws.part_s;
   a.part_rows = ws.part_r;
+  a.tau_shared = p.share_tau ? ws.tau : nullptr;
   a.stamps = nullptr;
-  a.tau_shared = share ? ws.tau : nullptr;
-  a.kp = p.kp;
-  {
-    static int boot = -1;
-    if (boot < 0) { const char* e = getenv("CRS_SCAN_BOOT"); boot = (e && e[0] == '0') ? 0 : 1; }
-    {
-      static int sched = -1;
-      if (sched < 0) { const char* e = getenv("CRS_SCAN_SCHED"); sched = (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 2; }
-      a.sched = sched;
-    }
-    // short streams only: the bootstrap pays when a workgroup sees few tiles (see scan.hip)
-    a.boot = (boot && p.n_tiles / (p.nwg > 0 ? p.nwg : 1) < 24) ? 1 : 0;
-  }
   a.n_rows = (int)n_rows;
   a.n_tiles = p.n_tiles;
-  a.nq = nq;
-  a.k = k;
+  a.nq = p.nq;
+  a.k = p.k;
+  a.sched = p.sched;
+  a.boot = p.boot;
+  a.kp = p.kp;
   a.nwg = p.nwg;
   a.nqb = p.nqb;
-  a.ticket = nullptr;
-  a.t_dyn = p.n_tiles;
-  a.dyn_mask = 0;
+  a.ticket = p.ticket ? ws.tau : nullptr;   // the counter lives in the (then unused) shared-threshold words
+  a.t_dyn = p.t_dyn;
+  a.dyn_mask = p.dyn_mask;
   a.nt = p.nt;
-  const bool tb_chain = ((slab_type == CRS_SLAB_F16 && p.tb_nw) || (slab_type == CRS_SLAB_I8 && p.i8_tb && p.pdim <= 768)) && p.tb_slots > 0;
-  const bool wide_chain = p.wide_nw && crs::scan_wide_streamed(k) && wide_dyn_enabled();   // scan_wide.hip's 24- / 32-slot forms
-  if ((tb_chain || wide_chain) && p.nqb == 1 && !share) {
-    // (int8 rows of 1024 elements stay static: those instantiations spill, and the ticket's register must not travel through scratch
-    // while its value is in flight)
-    // long chain-mode streams: the last tb_dyn_percent() of the tiles are drawn from a counter (scan_tb.hip, scan_i8.hip), which lives in the
-    // (otherwise unused) shared-threshold words at the head of the workspace and is zeroed in stream order ahead of the scan
-    const int rounds = p.n_tiles / p.nwg, pct = tb_dyn_percent();
-    const char* me = getenv("CRS_TB_DYN_MIN");   // tests: dynamic schedule on short streams too
-    const int min_rounds = me ? atoi(me) : kDynMinRounds;
-    if (pct > 0 && rounds >= (min_rounds < 4 ? 4 : min_rounds)) {
-      int stat = (int)((int64_t)rounds * (100 - pct) / 100);
-      if (stat < 2) stat = 2;
-      a.t_dyn = stat * p.nwg;
-      a.ticket = ws.tau;
-      a.dyn_mask = tb_dyn_granule() - 1;
-      const int ze = crs::scan_ticket_zero(a.ticket, st);
-      if (ze) return ze;
-    }
+  a.no_stagger = p.no_stagger;
+  if (p.ticket) {
+    const int ze = crs::scan_ticket_zero(a.ticket, st);
+    if (ze) return ze;
   }
-  const int e = p.w1_qg ? crs::scan_launch_w1(a, p.pdim, st)
-                : p.wide_nw ? crs::scan_launch_wide(a, p.pdim, p.wide_nw, st)
-                : (slab_type == CRS_SLAB_I8) ? crs::scan_launch_i8(a, p.pdim, p.i8_tb ? p.tb_slots : -1, st)
-                : p.tb_nw ? crs::scan_launch_tb(a, p.pdim, p.tb_nw, p.tb_slots, st)
-                               : crs::scan_launch_f16(a, p.pdim, p.nwg, st);
-  return e;
+  switch (p.family) {
+    case crs::Family::W1: return crs::scan_launch_w1(a, p.pdim, st);
+    case crs::Family::Wide: return crs::scan_launch_wide(a, p.pdim, p.waves, p.mfma, st);
+    default: break;
+  }
+  if (p.slab_type == CRS_SLAB_I8) return crs::scan_launch_i8(a, p.pdim, p.slots, st);
+  return p.family == crs::Family::TileBest ? crs::scan_launch_tb(a, p.pdim, p.waves, p.slots, st) : crs::scan_launch_f16(a, p.pdim, p.variant, st);
 }
 
 // the argument checks of a search (scan + tail into out_scores / out_ids) once its plan is made
-static int search_args_ok(const Plan& p, const void* q16_dev, int nq, int slab_type, const void* slab_dev, const float* scales_dev, int k,
+static int search_args_ok(const Plan& p, const void* q16_dev, const void* slab_dev, const float* scales_dev,
                           const void* workspace_dev, size_t workspace_bytes, const void* out_scores_dev, const void* out_ids_dev) {
   if (!q16_dev || !slab_dev || !workspace_dev || !out_scores_dev || !out_ids_dev)
     return fail(CRS_EINVAL, "null pointer");
-  if (slab_type == CRS_SLAB_I8 && !scales_dev) return fail(CRS_EINVAL, "int8 slab needs scales");
+  if (p.slab_type == CRS_SLAB_I8 && !scales_dev) return fail(CRS_EINVAL, "int8 slab needs scales");
   if (((uintptr_t)q16_dev | (uintptr_t)slab_dev) & 15) return fail(CRS_EINVAL, "q/slab must be 16-byte aligned");
-  if (workspace_bytes < ws_bytes(p.part_elems, nq, k)) return fail(CRS_ENOSPC, "workspace too small");
+  if (workspace_bytes < ws_bytes(p)) return fail(CRS_ENOSPC, "workspace too small");
   return CRS_OK;
 }
 
@@ -349,17 +174,17 @@ int crs_cosine_topk(const void* q16_dev, int nq, int dim, int slab_type, const v
                     int64_t* out_ids_dev, void* stream) {
   if (slab_type != CRS_SLAB_F16 && slab_type != CRS_SLAB_I8) return fail(CRS_EINVAL, "bad slab_type");
   Plan p;
-  int rc = make_plan(nq, dim, k, n_rows, slab_type, &p);
+  int rc = plan_for(nq, dim, k, n_rows, slab_type, &p);
   if (rc) return rc;
-  rc = search_args_ok(p, q16_dev, nq, slab_type, slab_dev, scales_dev, k, workspace_dev, workspace_bytes, out_scores_dev, out_ids_dev);
+  rc = search_args_ok(p, q16_dev, slab_dev, scales_dev, workspace_dev, workspace_bytes, out_scores_dev, out_ids_dev);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  ScanWs w = scan_ws(workspace_dev, p.part_elems, nq, k);
-  int e = run_scan(p, q16_dev, nq, slab_type, slab_dev, scales_dev, n_rows, k, w, st);
+  ScanWs w = scan_ws(workspace_dev, p);
+  int e = run_scan(p, q16_dev, slab_dev, scales_dev, n_rows, w, st);
   if (e == -1) return fail(CRS_EINVAL, "unsupported padded dimension");
   if (e) return hip_fail((hipError_t)e, "scan launch");
-  if ((size_t)crs::merge_slices(p.nwg, p.kp) > inter_lists(p.part_elems, nq)) w.inter_s = nullptr;   // (cannot happen: see inter_lists)
-  if (!p.group_best) {
+  if ((size_t)crs::merge_slices(p.nwg, p.kp) > crs::inter_lists(p.part_elems, nq)) w.inter_s = nullptr;   // (cannot happen: see inter_lists)
+  if (!p.group_best()) {
     e = crs::merge_launch_i32(w.part_s, w.part_r, p.nwg, nq, p.kp, k, id_base, out_scores_dev, out_ids_dev, w.inter_s, w.inter_i, st);
     if (e) return hip_fail((hipError_t)e, "merge launch");
     return CRS_OK;
@@ -628,17 +453,17 @@ int crs_cosine_topk_cert(const void* q16_dev, int nq, int dim, int slab_type, co
                          int cap, void* stream) {
   if (slab_type != CRS_SLAB_F16 && slab_type != CRS_SLAB_I8) return fail(CRS_EINVAL, "bad slab_type");
   Plan p;
-  int rc = make_plan(nq, dim, k_in, n_rows, slab_type, &p);
+  int rc = plan_for(nq, dim, k_in, n_rows, slab_type, &p);
   if (rc) return rc;
   // one set of argument checks for both tails: the search's, then the certificate's
-  rc = search_args_ok(p, q16_dev, nq, slab_type, slab_dev, scales_dev, k_in, workspace_dev, workspace_bytes, cand_scores_dev, cand_ids_dev);
+  rc = search_args_ok(p, q16_dev, slab_dev, scales_dev, workspace_dev, workspace_bytes, cand_scores_dev, cand_ids_dev);
   if (rc) return rc;
   crs::ExactWs ews;
   rc = exact_ws(nq, dim, slab_type, cap, exact_ws_bytes, exact_ws_dev, &ews);
   if (rc) return rc;
   rc = cert_args_ok(n_rows, k_in, k_out, q32_dev, q16_dev, shadow_dev, cand_ids_dev, cand_scores_dev, out_scores_dev, out_ids_dev, status_dev);
   if (rc) return rc;
-  if (!(fused_tail_enabled() && fused_tail(p, slab_type, k_in))) {   // the chain: scan + merge (+ refine), then the certificate
+  if (!(crs::knobs_from_env().fused_tail && fused_tail(p, k_in))) {   // the chain: scan + merge (+ refine), then the certificate
     rc = crs_cosine_topk(q16_dev, nq, dim, slab_type, slab_dev, scales_dev, n_rows, k_in, id_base, workspace_dev, workspace_bytes,
                          cand_scores_dev, cand_ids_dev, stream);
     if (rc) return rc;
@@ -646,8 +471,8 @@ int crs_cosine_topk_cert(const void* q16_dev, int nq, int dim, int slab_type, co
                                k_out, row_err_max, out_scores_dev, out_ids_dev, status_dev, exact_ws_dev, exact_ws_bytes, cap, stream);
   }
   hipStream_t st = (hipStream_t)stream;
-  const ScanWs w = scan_ws(workspace_dev, p.part_elems, nq, k_in);
-  int e = run_scan(p, q16_dev, nq, slab_type, slab_dev, scales_dev, n_rows, k_in, w, st);
+  const ScanWs w = scan_ws(workspace_dev, p);
+  int e = run_scan(p, q16_dev, slab_dev, scales_dev, n_rows, w, st);
   if (e == -1) return fail(CRS_EINVAL, "unsupported padded dimension");
   if (e) return hip_fail((hipError_t)e, "scan launch");
   e = crs::finish_cert_launch(w.part_s, w.part_r, p.nwg, p.kp, reinterpret_cast<const _Float16*>(q16_dev), nq, p.pdim,
@@ -777,17 +602,12 @@ int crs_scan_plan_describe(int nq, int dim, int k, int64_t n_rows, int slab_type
   if (!buf || cap == 0) return fail(CRS_EINVAL, "null buffer");
   if (slab_type != CRS_SLAB_F16 && slab_type != CRS_SLAB_I8) return fail(CRS_EINVAL, "bad slab_type");
   Plan p;
-  const int rc = make_plan(nq, dim, k, n_rows, slab_type, &p);
+  const int rc = plan_for(nq, dim, k, n_rows, slab_type, &p);
   if (rc) return rc;
-  char name[96];
-  if (p.w1_qg) snprintf(name, sizeof name, "scan_w2_kernel<%d> (%d queries/workgroup, dump)", p.pdim, p.w1_qg);
-  else if (p.wide_nw) snprintf(name, sizeof name, "scan_wide_kernel<%d,%d,%d>", p.pdim, p.wide_nw, crs::scan_wide_slots(k));
-  else if (p.tb_nw) snprintf(name, sizeof name, "scan_tb_kernel<%d,%d,%d,%d>", p.pdim, p.tile_rows, p.tb_nw, p.tb_slots);
-  else if (slab_type == CRS_SLAB_I8) snprintf(name, sizeof name, "scan_i8_kernel<%d,%d,%d,%d>", p.pdim, p.tile_rows, (p.i8_tb || k <= 16) ? 16 : 32, p.i8_tb ? p.tb_slots : -1);
-  else snprintf(name, sizeof name, "scan_f16_kernel<%d,%d,%d>", p.pdim, p.tile_rows, k <= 16 ? 16 : 32);
+  char text[192];
+  crs::plan_describe(p, text, sizeof text);
   // the tail crs_cosine_topk_cert takes with this plan (crs_cosine_topk itself always runs merge [+ refine])
-  snprintf(buf, cap, "%s streams=%d qblocks=%d kp=%d%s + merge%s; cert tail: %s", name, p.nwg, p.nqb, p.kp, p.nt ? " nt" : "",
-           p.group_best ? " + refine" : "", fused_tail(p, slab_type, k) ? "fused" : "chain");
+  snprintf(buf, cap, "%s; cert tail: %s", text, fused_tail(p, k) ? "fused" : "chain");
   return CRS_OK;
 }
 
@@ -819,20 +639,20 @@ int crs_time_cosine_topk(const void* q16_dev, int nq, int dim, int slab_type, co
                          void* stream, int iters, float* ms_total, float* ms_scan) {
   if (slab_type != CRS_SLAB_F16 && slab_type != CRS_SLAB_I8) return fail(CRS_EINVAL, "bad slab_type");
   Plan p;
-  int rc = make_plan(nq, dim, k, n_rows, slab_type, &p);
+  int rc = plan_for(nq, dim, k, n_rows, slab_type, &p);
   if (rc) return rc;
   if (iters <= 0 || !ms_total || !ms_scan) return fail(CRS_EINVAL, "bad iters / null outputs");
-  if (workspace_bytes < ws_bytes(p.part_elems, nq, k)) return fail(CRS_ENOSPC, "workspace too small");
+  if (workspace_bytes < ws_bytes(p)) return fail(CRS_ENOSPC, "workspace too small");
   hipStream_t st = (hipStream_t)stream;
   hipEvent_t e0, e1;
   hipError_t he;
   if ((he = hipEventCreate(&e0)) != hipSuccess) return hip_fail(he, "hipEventCreate");
   if ((he = hipEventCreate(&e1)) != hipSuccess) return hip_fail(he, "hipEventCreate");
-  const ScanWs w = scan_ws(workspace_dev, p.part_elems, nq, k);
+  const ScanWs w = scan_ws(workspace_dev, p);
   // scan kernel alone
   hipEventRecord(e0, st);
   for (int i = 0; i < iters; ++i) {
-    const int e = run_scan(p, q16_dev, nq, slab_type, slab_dev, scales_dev, n_rows, k, w, st);
+    const int e = run_scan(p, q16_dev, slab_dev, scales_dev, n_rows, w, st);
     if (e) { hipEventDestroy(e0); hipEventDestroy(e1); return e == -1 ? fail(CRS_EINVAL, "unsupported padded dimension") : hip_fail((hipError_t)e, "scan launch"); }
   }
   hipEventRecord(e1, st);

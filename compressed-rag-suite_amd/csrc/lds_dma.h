@@ -31,7 +31,7 @@ __device__ __forceinline__ void lds_dma16(unsigned lds_dst, unsigned voff, const
                : "=&s"(keep) : "s"(lds_dst), "v"(voff), "s"(sbase) : "memory");
 }
 // The same transfer with the non-temporal policy: for data read once per launch and far larger than the Infinity Cache
-// (the scan's slab tiles on multi-GB shards, capi.hip make_plan), so that it does not evict what the other kernels re-read.
+// (the scan's slab tiles on multi-GB shards, plan.cpp make_plan), so that it does not evict what the other kernels re-read.
 __device__ __forceinline__ void lds_dma16_nt(unsigned lds_dst, unsigned voff, const void* sbase) {
   unsigned keep;
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 2\n\tglobal_load_lds_dwordx4 %2, %3 nt\n\ts_mov_b32 m0, %0"

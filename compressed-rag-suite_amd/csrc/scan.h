@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "scan_forms.h"
+
 namespace crs {
 
 struct ScanArgs {
@@ -19,14 +21,14 @@ struct ScanArgs {
   int k;
   int sched;              // synchronous-compaction schedule: 0 none, 1 {3,4,6,8,12,...}, 2 {4,8,16,...}
   int boot;               // 1: bootstrap the threshold from the first 64 rows in registers (scan.hip)
-  int kp;                 // slots per (query, workgroup) partial list (capi.hip make_plan: k, tiles per stream, or chain slots)
+  int kp;                 // slots per (query, workgroup) partial list (plan.h: k, tiles per stream, or chain slots)
   int nwg;                // tile streams (workgroups per query block)
   int nqb;                // query blocks (64, 128 or 256 queries each); the grid is nqb * nwg workgroups (scan_common.h: grid mapping)
   unsigned* ticket;       // scan_tb.hip chain mode: tiles >= t_dyn are handed out through this counter (zero at launch); else nullptr
   int t_dyn;              //   first dynamically scheduled tile (a multiple of nwg, >= 2 nwg); n_tiles when the schedule is static
   int dyn_mask;           //   a ticket stands for dyn_mask + 1 consecutive tiles (a power of two)
   int nt;                 // scan_tb.hip / scan_i8.hip: 1 = slab tiles streamed with the non-temporal policy (lds_dma16_nt)
-  int no_stagger;         // scan_wide.hip, 24- / 32-slot forms: 1 = CRS_WIDE_STAGGER=0 (set by scan_launch_wide, read by nothing else)
+  int no_stagger;         // scan_wide.hip, 24- / 32-slot forms: 1 = CRS_WIDE_STAGGER=0 (read by nothing else)
 };
 
 // the exactness workspace of a batch (capi.hip carves it): per-query escalation threshold and row counter, the escalation
@@ -45,32 +47,18 @@ int refine_launch(const _Float16* q16, int nq, int pdim, const _Float16* slab, i
 int refine_i8_launch(const _Float16* q16, int nq, int pdim, const void* slab, const float* scales, int n_rows, const float* win_s,
                      const int64_t* win, int k, int tile_rows, int64_t id_base, float* out_s, int64_t* out_i, hipStream_t stream);
 
-int scan_tile_rows(int pdim);
-int scan_i8_tile_rows();
-int scan_wg_per_cu();    // resident workgroups per CU the active scan.hip variant is launched with
-bool scan_share_tau();  // CRS_SCAN_SHARE_TAU=1 enables cross-workgroup threshold sharing (scan.hip; measured slower, off)
-// returns hipError_t as int, -1 for an unsupported padded dimension
-int scan_launch_f16(const ScanArgs& a, int pdim, int nwg, hipStream_t stream);
-// slots: -1 threshold kernel; 0 tile-best dump; 4 / 10 / 16 tile-best chain (finished by merge + refine_i8_launch)
+// The scan launchers (scan.hip, scan_i8.hip, scan_tb.hip, scan_wide.hip, scan_w1.hip): the form comes from a Plan (plan.h), i.e. it
+// satisfies its family's form_exists (scan_forms.h).  Each returns hipError_t as int, -1 for a form that does not exist.
+int scan_launch_f16(const ScanArgs& a, int pdim, int variant, hipStream_t stream);   // variant: Knobs::scan_variant
+// slots: -1 threshold kernel; 0 tile-best dump; else tile-best chain (finished by merge + refine_i8_launch)
 int scan_launch_i8(const ScanArgs& a, int pdim, int slots, hipStream_t stream);
-// scan_tb.hip: tile-best 16x16x32 scan, k <= 16; nw = 4 (64 queries / workgroup) or 8 (128);
-// slots = 0: dump mode (kp = tiles per stream), else chain mode (kp = slots); finished by merge + refine_launch
-int scan_tb_wg_per_cu(int pdim, int nw);
-bool scan_tb_has_8_waves(int pdim);
+// tile-best 16x16x32 scan; nw = 4 (64 queries / workgroup) or 8 (128); slots = 0: dump mode (kp = tiles per stream), else chain
+// mode (kp = slots); finished by merge + refine_launch
 int scan_launch_tb(const ScanArgs& a, int pdim, int nw, int slots, hipStream_t stream);
-int scan_ticket_zero(unsigned* ticket, hipStream_t stream);   // ScanArgs::ticket := 0, in stream order (scan_tb.hip / scan_i8.hip chain modes)
-int scan_tb_long_chain_slots(int pdim, int nw, int k);   // chain length for 16 < k <= 64 on long streams (0: none)
-int scan_i8_long_chain_slots(int pdim, int k);
-// scan_wide.hip: 65+ queries per launch, fp16 slabs, k <= 16 (rows of <= 512 elements) or k <= 32 (<= 384)
-int scan_wide_waves(int nq, int k, int pdim);
-bool scan_wide_streamed(int k);   // the 24- / 32-slot forms: ScanArgs::nt and ticket / t_dyn / dyn_mask apply
-int scan_wide_wg_per_cu(int nw, int pdim);
-int scan_wide_slots(int k);
-int scan_wide_tile_rows(int nw, int pdim);
-int scan_launch_wide(const ScanArgs& a, int pdim, int nw, hipStream_t stream);
-
-// scan_w1.hip: > 64 queries per launch on 768-element fp16 rows, k <= 64: 256 queries per workgroup, dump selection
-int scan_w1_queries_per_wg(int nq, int k, int pdim);   // 0: not applicable; else queries per workgroup (128 or 256)
+int scan_ticket_zero(unsigned* ticket, hipStream_t stream);   // ScanArgs::ticket := 0, in stream order
+// 65+ queries per launch, fp16 slabs; mfma: 16 or 32, the MFMA shape (Plan::mfma)
+int scan_launch_wide(const ScanArgs& a, int pdim, int nw, int mfma, hipStream_t stream);
+// 65+ queries per launch on 768-element fp16 rows: 256 queries per workgroup, dump selection
 int scan_launch_w1(const ScanArgs& a, int pdim, hipStream_t stream);
 
 // merge.hip

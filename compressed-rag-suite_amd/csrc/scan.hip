@@ -27,11 +27,7 @@
 
 #include "scan_common.h"
 
-#include <stdlib.h>
-
 namespace crs {
-
-int scan_variant();
 
 namespace {
 
@@ -220,7 +216,7 @@ struct WaveState {
 // steady-state loop ~10 % slower (C4 177 -> 200 us), while short streams (C2, 6 tiles per workgroup)
 // gain 5 % from it; the launcher picks per launch.
 template <int D, int TR, int L, bool ASM_LOADS, bool BOOT>
-__global__ __launch_bounds__(kThreads, 2) void scan_f16_kernel(const ScanArgs a) {
+__global__ __launch_bounds__(kThreads, classic_wg_per_cu(3)) void scan_f16_kernel(const ScanArgs a) {
   using C = Cfg<D, TR, L>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* tile_buf = smem;
@@ -427,7 +423,7 @@ __global__ __launch_bounds__(kThreads, WGPC) void scan_f16_ring_kernel(const Sca
 }
 
 template <typename K>
-int launch_kernel(K kernel, int lds, const ScanArgs& a, int nwg, hipStream_t stream, bool* attr_done) {
+int launch_kernel(K kernel, int lds, const ScanArgs& a, hipStream_t stream, bool* attr_done) {
   if (!*attr_done) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -440,75 +436,49 @@ int launch_kernel(K kernel, int lds, const ScanArgs& a, int nwg, hipStream_t str
 }
 
 template <int D, int TR, int L>
-int launch_l(const ScanArgs& a, int nwg, hipStream_t stream) {
+int launch_l(const ScanArgs& a, int variant, hipStream_t stream) {
   using C = Cfg<D, TR, L>;
   constexpr int lists = 2 * C::kListBytes;
   static bool done[5] = {false, false, false, false, false};
-  switch (scan_variant()) {
-    case 0: return launch_kernel(&scan_f16_kernel<D, TR, L, false, false>, 2 * C::kTileBytes + lists, a, nwg, stream, &done[0]);
+  switch (variant) {
+    case 0: return launch_kernel(&scan_f16_kernel<D, TR, L, false, false>, 2 * C::kTileBytes + lists, a, stream, &done[0]);
     case 3:
       if (a.boot && L == 16 && TR == 32)
-        return launch_kernel(&scan_f16_kernel<D, TR, L, true, (L == 16 && TR == 32)>, 2 * C::kTileBytes + lists, a, nwg, stream, &done[4]);
+        return launch_kernel(&scan_f16_kernel<D, TR, L, true, (L == 16 && TR == 32)>, 2 * C::kTileBytes + lists, a, stream, &done[4]);
       // 32-slot lists (k > 16) on rows of >= 512 elements run out of registers and spill a few; an inline-asm
       // load whose destination the compiler then copies or spills before the data has landed would hand
       // garbage on, so those instantiations keep compiler-visible loads
       if constexpr (L == 32 && D >= 512)
-        return launch_kernel(&scan_f16_kernel<D, TR, L, false, false>, 2 * C::kTileBytes + lists, a, nwg, stream, &done[0]);
+        return launch_kernel(&scan_f16_kernel<D, TR, L, false, false>, 2 * C::kTileBytes + lists, a, stream, &done[0]);
       else
-        return launch_kernel(&scan_f16_kernel<D, TR, L, true, false>, 2 * C::kTileBytes + lists, a, nwg, stream, &done[3]);
-    case 2: return launch_kernel(&scan_f16_ring_kernel<D, TR, L, 2, 2>, 2 * C::kTileBytes + lists, a, nwg, stream, &done[2]);
+        return launch_kernel(&scan_f16_kernel<D, TR, L, true, false>, 2 * C::kTileBytes + lists, a, stream, &done[3]);
+    case 2: return launch_kernel(&scan_f16_ring_kernel<D, TR, L, 2, classic_wg_per_cu(2)>, 2 * C::kTileBytes + lists, a, stream, &done[2]);
     default: {
       constexpr int NS = (L == 16) ? 4 : 3;
-      return launch_kernel(&scan_f16_ring_kernel<D, TR, L, NS, 1>, NS * C::kTileBytes + lists, a, nwg, stream, &done[1]);
+      return launch_kernel(&scan_f16_ring_kernel<D, TR, L, NS, classic_wg_per_cu(1)>, NS * C::kTileBytes + lists, a, stream, &done[1]);
     }
   }
 }
 
 template <int D, int TR>
-int launch_d(const ScanArgs& a, int nwg, hipStream_t stream) {
-  if (a.k <= 16) return launch_l<D, TR, 16>(a, nwg, stream);
-  return launch_l<D, TR, 32>(a, nwg, stream);
+int launch_d(const ScanArgs& a, int variant, hipStream_t stream) {
+  static_assert(TR == classic_tile_rows(D) && classic_form_exists(D, 16) && classic_form_exists(D, 32));
+  if (classic_list_slots(a.k) == 16) return launch_l<D, TR, 16>(a, variant, stream);
+  return launch_l<D, TR, 32>(a, variant, stream);
 }
 
 }  // namespace
 
-// 0 = register-staged double buffer (plain loads), 3 = same with asm early loads (2 workgroups/CU);
-// 1 = LDS-DMA ring, 1 workgroup/CU; 2 = LDS-DMA double buffer, 2 workgroups/CU.
-// CRS_SCAN_VARIANT overrides the default; read once.
-int scan_variant() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("CRS_SCAN_VARIANT");
-    v = (e && e[0] >= '0' && e[0] <= '3') ? (e[0] - '0') : 3;
-  }
-  return v;
-}
-int scan_wg_per_cu() { return scan_variant() == 1 ? 1 : 2; }
-// Cross-workgroup threshold sharing (scan_common.h) is OFF by default: measured on MI355X it cut the
-// in-loop compactions per wave from 2 to 1 at C2, but the per-tile L1-bypassing poll of the shared
-// word sits in the same in-order vmcnt queue as the tile loads and cost more than it saved
-// (C2 28.8 -> 38.0 us, C4 174 -> 257 us).  CRS_SCAN_SHARE_TAU=1 re-enables it for experiments.
-bool scan_share_tau() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("CRS_SCAN_SHARE_TAU");
-    v = (e && e[0] == '1') ? 1 : 0;
-  }
-  return v == 1;
-}
-
-int scan_tile_rows(int pdim) { return pdim <= 512 ? 32 : 16; }
-
-int scan_launch_f16(const ScanArgs& a, int pdim, int nwg, hipStream_t stream) {
+int scan_launch_f16(const ScanArgs& a, int pdim, int variant, hipStream_t stream) {
   switch (pdim) {
-    case 128: return launch_d<128, 32>(a, nwg, stream);
-    case 256: return launch_d<256, 32>(a, nwg, stream);
-    case 384: return launch_d<384, 32>(a, nwg, stream);
-    case 512: return launch_d<512, 32>(a, nwg, stream);
-    case 640: return launch_d<640, 16>(a, nwg, stream);
-    case 768: return launch_d<768, 16>(a, nwg, stream);
-    case 896: return launch_d<896, 16>(a, nwg, stream);
-    case 1024: return launch_d<1024, 16>(a, nwg, stream);
+    case 128: return launch_d<128, 32>(a, variant, stream);
+    case 256: return launch_d<256, 32>(a, variant, stream);
+    case 384: return launch_d<384, 32>(a, variant, stream);
+    case 512: return launch_d<512, 32>(a, variant, stream);
+    case 640: return launch_d<640, 16>(a, variant, stream);
+    case 768: return launch_d<768, 16>(a, variant, stream);
+    case 896: return launch_d<896, 16>(a, variant, stream);
+    case 1024: return launch_d<1024, 16>(a, variant, stream);
     default: return -1;
   }
 }

@@ -22,8 +22,6 @@
 
 #include "scan_common.h"
 
-#include <stdlib.h>
-
 namespace crs {
 namespace {
 
@@ -38,13 +36,10 @@ struct TbCfg {
   static constexpr int kKsteps = D / 32;
   static constexpr int kRt = TR / 16;
   static constexpr int kLds = 2 * kTileBytes;
-  // resident workgroups per CU the kernel is built for (LDS and a 512 / waves-per-SIMD register budget)
-  // one look-ahead tile per workgroup and two workgroups per CU: 48 KB in flight per CU is where a plain sweep of
-  // HBM peaks as well; a second look-ahead tile or a third workgroup only lengthen the memory queues (C4:
-  // 5.6-5.8 TB/s against 6.05).  128-element rows (8 KB tiles) take three.
-  static constexpr int kWgpc = NW == 8 ? (D <= 384 ? 2 : 1) : (D <= 128 ? 3 : 2);
+  static constexpr int kWgpc = tb_wg_per_cu(D, NW);   // resident workgroups per CU the kernel is built for (scan_forms.h)
   static_assert(D % 128 == 0 && TR % 16 == 0, "row length: multiple of 128 elements; tile rows: multiple of 16");
   static_assert(kTileBytes % (kT * 16) == 0, "tile must split into whole 16-byte loads");
+  static_assert(TR == tb_tile_rows(D) && tb_form_exists(D, NW, 0), "scan_forms.h says this geometry does not exist");
 };
 
 template <int D, int TR, int NW, int K>
@@ -291,69 +286,42 @@ int launch_tb(const ScanArgs& a, hipStream_t stream) {
   return (int)hipGetLastError();
 }
 
+// the form if scan_forms.h has it
+template <int D, int TR, int NW, int K>
+int launch_tb_if(const ScanArgs& a, hipStream_t stream) {
+  if constexpr (tb_form_exists(D, NW, K)) return launch_tb<D, TR, NW, K>(a, stream);
+  else return -1;
+}
+
 template <int D, int TR, int NW>
 int launch_tb_k(const ScanArgs& a, int slots, hipStream_t stream) {
   switch (slots) {
-    case 0: return launch_tb<D, TR, NW, 0>(a, stream);
-    case 4: return launch_tb<D, TR, NW, 4>(a, stream);
-    case 10: return launch_tb<D, TR, NW, 10>(a, stream);
-    case 16: return launch_tb<D, TR, NW, 16>(a, stream);
-    // 16 < k <= 64 on long streams: a 32- or 64-slot chain (5 VALU per slot and tile, still under the tile's memory time)
-    // instead of the threshold kernels.  32 slots (64 registers) fit beside the query fragments of every row length at two
-    // waves per SIMD; 64 slots only for 256- / 384-element rows (they spill from 512 on).  10 M x 384, 64 queries, k = 17 / 32:
-    // scan 2.36 / 2.13 ms on the threshold kernels -> 1.23 ms, whole search 2.09 / 2.16 -> 1.31 / 1.32.
-    case 24: if constexpr (NW == 4) return launch_tb<D, TR, NW, 24>(a, stream); else return -1;   // the store's over-fetch on large shards
-    case 32: if constexpr (NW == 4) return launch_tb<D, TR, NW, 32>(a, stream); else return -1;
-    // register budgets checked by tools/check_resources.py (no plan-selectable instantiation may touch scratch): 64 slots
-    // fit 256-element rows only (384: 20 bytes / lane of scratch), 56 / 48 slots 384-element rows, 48 slots 512 / 640, 40 slots
-    // (the reference's 2 k = 40 with rerank on) 768
-    case 64: if constexpr (NW == 4 && D == 256) return launch_tb<D, TR, NW, 64>(a, stream); else return -1;
-    case 56: if constexpr (NW == 4 && D == 384) return launch_tb<D, TR, NW, 56>(a, stream); else return -1;
-    case 48: if constexpr (NW == 4 && D >= 384 && D <= 640) return launch_tb<D, TR, NW, 48>(a, stream); else return -1;
-    case 40: if constexpr (NW == 4 && D == 768) return launch_tb<D, TR, NW, 40>(a, stream); else return -1;
+    case 0: return launch_tb_if<D, TR, NW, 0>(a, stream);
+    case 4: return launch_tb_if<D, TR, NW, 4>(a, stream);
+    case 10: return launch_tb_if<D, TR, NW, 10>(a, stream);
+    case 16: return launch_tb_if<D, TR, NW, 16>(a, stream);
+    // 16 < k <= 64 on long streams: a longer chain (5 VALU per slot and tile, still under the tile's memory time) instead of the
+    // threshold kernels.  10 M x 384, 64 queries, k = 17 / 32: scan 2.36 / 2.13 ms on the threshold kernels -> 1.23 ms, whole
+    // search 2.09 / 2.16 -> 1.31 / 1.32.  24: the store's over-fetch on large shards.
+    case 24: return launch_tb_if<D, TR, NW, 24>(a, stream);
+    case 32: return launch_tb_if<D, TR, NW, 32>(a, stream);
+    case 64: return launch_tb_if<D, TR, NW, 64>(a, stream);
+    case 56: return launch_tb_if<D, TR, NW, 56>(a, stream);
+    case 48: return launch_tb_if<D, TR, NW, 48>(a, stream);
+    case 40: return launch_tb_if<D, TR, NW, 40>(a, stream);
     default: return -1;
   }
 }
 
 template <int D, int TR>
 int launch_tb_d(const ScanArgs& a, int nw, int slots, hipStream_t stream) {
-  if constexpr ((TR * D * 2) % (8 * 64 * 16) == 0) {
+  if constexpr (scan_tb_has_8_waves(D)) {
     if (nw == 8) return launch_tb_k<D, TR, 8>(a, slots, stream);
   }
   return nw == 4 ? launch_tb_k<D, TR, 4>(a, slots, stream) : -1;
 }
 
 }  // namespace
-
-// 8 waves need a tile that splits into whole 16-byte loads over 512 threads (not 640- / 896-element rows)
-bool scan_tb_has_8_waves(int pdim) { return pdim != 640 && pdim != 896; }
-
-int scan_tb_wg_per_cu(int pdim, int nw) {
-  if (nw == 8 && !scan_tb_has_8_waves(pdim)) nw = 4;
-  switch (pdim) {
-    case 128: return nw == 8 ? TbCfg<128, 32, 8>::kWgpc : TbCfg<128, 32, 4>::kWgpc;
-    case 256: return nw == 8 ? TbCfg<256, 32, 8>::kWgpc : TbCfg<256, 32, 4>::kWgpc;
-    case 384: return nw == 8 ? TbCfg<384, 32, 8>::kWgpc : TbCfg<384, 32, 4>::kWgpc;
-    case 512: return nw == 8 ? TbCfg<512, 32, 8>::kWgpc : TbCfg<512, 32, 4>::kWgpc;
-    case 640: return TbCfg<640, 16, 4>::kWgpc;
-    case 768: return nw == 8 ? TbCfg<768, 16, 8>::kWgpc : TbCfg<768, 16, 4>::kWgpc;
-    case 896: return TbCfg<896, 16, 4>::kWgpc;
-    case 1024: return nw == 8 ? TbCfg<1024, 16, 8>::kWgpc : TbCfg<1024, 16, 4>::kWgpc;
-    default: return 2;
-  }
-}
-
-// chain length for 16 < k <= 64 on long streams (0: none -- the threshold kernels take the search)
-int scan_tb_long_chain_slots(int pdim, int nw, int k) {
-  if (nw != 4 || k <= 16 || k > 64) return 0;
-  if (k <= 24) return 24;
-  if (k <= 32) return 32;
-  if (pdim == 256) return 64;
-  if (pdim == 384) return k <= 48 ? 48 : (k <= 56 ? 56 : 0);
-  if (pdim == 512 || pdim == 640) return k <= 48 ? 48 : 0;
-  if (pdim == 768) return k <= 40 ? 40 : 0;
-  return 0;
-}
 
 // slots = 0: dump mode (kp = tiles per stream); else chain mode with that many slots (kp = slots)
 // the ticket counter is zeroed by a kernel of our own, in stream order: a kernel node in a captured graph like the scan itself

@@ -27,8 +27,6 @@
 // 1.3-1.6 GHz under this load; the transfer skeleton alone moves 3.9 TB/s).
 #include "scan_common.h"
 
-#include <stdlib.h>
-
 namespace crs {
 namespace {
 
@@ -325,6 +323,7 @@ __global__ __launch_bounds__(512, 2) void scan_w2_kernel(const ScanArgs a) {
 
 template <int D>
 int launch_w2(const ScanArgs& a, hipStream_t stream) {
+  static_assert(w1_form_exists(D));
   using C = W2Cfg<D>;
   static bool done = false;
   auto kernel = &scan_w2_kernel<D>;
@@ -338,17 +337,6 @@ int launch_w2(const ScanArgs& a, hipStream_t stream) {
 }
 
 }  // namespace
-
-// Queries per workgroup when this kernel takes the launch (0: it does not).  CRS_SCAN_W1=0 hands 768-element rows to
-// scan_tb.hip's eight-wave form instead (A/B runs).
-int scan_w1_queries_per_wg(int nq, int k, int pdim) {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("CRS_SCAN_W1");
-    on = (e && e[0] == '0') ? 0 : 1;
-  }
-  return (on && nq > 64 && k <= 64 && pdim == 768) ? 256 : 0;
-}
 
 int scan_launch_w1(const ScanArgs& a, int pdim, hipStream_t stream) {
   switch (pdim) {

@@ -64,14 +64,11 @@
 //     serves both: lanes kq = 0, 1 keep the split list of group 0's query, lanes 2, 3 of group 1's -- the pair is (l, l ^ 16),
 //     kq & 1 the half, and the lower half's last slot crosses by v_permlane16_swap instead of v_permlane32_swap.  The list
 //     algorithm (insert_shift) and its proof are unchanged: they only speak of "the two lanes of the pair".
-// Which shape a form runs is wide_default_mfma() below, set from A/B runs by wall time; CRS_WIDE_MFMA=16 | 32 overrides it.
+// Which shape a form runs is wide_default_mfma() (scan_forms.h), set from A/B runs by wall time; CRS_WIDE_MFMA=16 | 32 overrides it.
 
 #include "scan_common.h"
 
-#include <stdlib.h>
-
 namespace crs {
-int scan_wide_slots(int k);
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -84,7 +81,7 @@ typedef __attribute__((address_space(3))) void* lds_ptr_t;
 // allow: the per-tile costs that are not MFMAs (barrier, selection chain, load issue, LDS store: ~1.9 k cycles
 // per wave and 32-row tile against 1.5 k of matrix work) are then paid once per 64 rows.
 template <int D, int NW>
-constexpr int wide_rb() { return (NW == 8 && D <= 384) ? 2 : 1; }
+constexpr int wide_rb() { return scan_wide_tile_rows(NW, D) / 32; }
 
 // the forms with chains longer than 16 slots: nt stream + dynamic tile schedule compiled in (header)
 template <int K>
@@ -120,11 +117,6 @@ struct WCfg {
   static_assert(kTileBytes % (kThreadsW * 16) == 0, "tile must split into whole 16-byte loads");
 };
 
-// The forms that exist in both MFMA shapes ("16x16x32 form" in the header): the split-list forms of the 8-wave kernel on 256- and
-// 384-element rows, i.e. what a sweep group launches.
-template <int D, int NW, int K>
-constexpr bool wide_has_16() { return NW == 8 && (D == 256 || D == 384) && wide_split<K>(); }
-
 // a tile's scores in one wave: 32x32x16 -- RB blocks of 32 rows x 32 queries; 16x16x32 -- 2 RB blocks of 16 rows x 2 groups of 16 queries
 template <int RB, bool S16>
 struct WAcc { f32x16 a[RB]; };
@@ -137,7 +129,7 @@ struct WAcc<RB, true> { f32x4 a[2 * RB][2]; };
 template <int D, int NW, int K, bool S16>
 __device__ __forceinline__ void scan_wide_body(const ScanArgs a) {
   using C = WCfg<D, NW>;
-  static_assert(!S16 || wide_has_16<D, NW, K>(), "the 16x16x32 form exists for the split-list forms of 64-row tiles only");
+  static_assert(!S16 || wide_has_16(D, NW, K), "the 16x16x32 form exists for the split-list forms of 64-row tiles only");
   constexpr int kT = C::kThreadsW;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* tile_buf = smem;
@@ -577,80 +569,40 @@ int launch_wide(const ScanArgs& a, hipStream_t stream) {
   return (int)hipGetLastError();
 }
 
-// MFMA shape of a form that exists in both (wide_has_16): what measured faster by wall time on random data, the shapes
-// alternated on one device, every run of the one ahead of every run of the other and the medians at least 5 x the larger
-// spread apart (profiles/r13_bench_c4_ab.jsonl, profiles/r13_forms_ab.jsonl).  384-element rows
-// cleared that at both chain lengths; 256-element rows were 5 - 8 % faster on 16x16x32 but within 1.4 - 3.2 x the spread, and stay.
-struct WideShape { int d, k, mfma; };
-constexpr WideShape kWideShapes[] = {{384, 24, 16}, {384, 32, 16}, {256, 24, 32}, {256, 32, 32}};
-constexpr int wide_default_mfma(int d, int k) {
-  for (const WideShape& w : kWideShapes)
-    if (w.d == d && w.k == k) return w.mfma;
-  return 32;
-}
-
-// shape: 16 / 32 forces the shape where the form has both (CRS_WIDE_MFMA), 0 = the table above
+// the form if scan_forms.h has it
 template <int D, int NW, int K>
-int launch_wide_s(const ScanArgs& a, int shape, hipStream_t stream) {
-  if constexpr (wide_has_16<D, NW, K>()) {
-    if ((shape ? shape : wide_default_mfma(D, K)) == 16) return launch_wide<D, NW, K, true>(a, stream);
+int launch_wide_if(const ScanArgs& a, int mfma, hipStream_t stream) {
+  if constexpr (wide_form_exists(D, NW, K, 16)) {
+    if (mfma == 16) return launch_wide<D, NW, K, true>(a, stream);
   }
-  return launch_wide<D, NW, K, false>(a, stream);
+  if constexpr (wide_form_exists(D, NW, K, 32)) return launch_wide<D, NW, K, false>(a, stream);
+  else return -1;
 }
 
 template <int D, int NW>
-int launch_wide_k(const ScanArgs& a, int shape, hipStream_t stream) {
-  const int kk = scan_wide_slots(a.k);
-  if (kk == 4) return launch_wide<D, NW, 4, false>(a, stream);
-  if (kk == 10) return launch_wide<D, NW, 10, false>(a, stream);
-  if (kk == 16) return launch_wide<D, NW, 16, false>(a, stream);
-  if constexpr (D <= 384) {   // no scratch in any of them: tools/check_resources.py, profiles/r07_wide_resources.txt
-    if (kk == 24) return launch_wide_s<D, NW, 24>(a, shape, stream);
-    if (kk == 32) return launch_wide_s<D, NW, 32>(a, shape, stream);
+int launch_wide_k(const ScanArgs& a, int mfma, hipStream_t stream) {
+  switch (scan_wide_slots(a.k)) {
+    case 4: return launch_wide_if<D, NW, 4>(a, mfma, stream);
+    case 10: return launch_wide_if<D, NW, 10>(a, mfma, stream);
+    case 16: return launch_wide_if<D, NW, 16>(a, mfma, stream);
+    case 24: return launch_wide_if<D, NW, 24>(a, mfma, stream);
+    default: return launch_wide_if<D, NW, 32>(a, mfma, stream);
   }
-  return -1;
 }
 
 template <int D>
-int launch_wide_d(const ScanArgs& a, int nw, int shape, hipStream_t stream) {
-  return nw == 8 ? launch_wide_k<D, 8>(a, shape, stream) : launch_wide_k<D, 4>(a, shape, stream);
+int launch_wide_d(const ScanArgs& a, int nw, int mfma, hipStream_t stream) {
+  return nw == 8 ? launch_wide_k<D, 8>(a, mfma, stream) : launch_wide_k<D, 4>(a, mfma, stream);
 }
 
 }  // namespace
 
-// Waves per workgroup the wide kernel would use for this launch, 0 = not applicable (use scan.hip).
-// CRS_SCAN_WIDE=0 disables it (A/B runs).
-int scan_wide_waves(int nq, int k, int pdim) {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("CRS_SCAN_WIDE");
-    on = (e && e[0] == '0') ? 0 : 1;
-  }
-  if (!on || nq <= 64 || k > 32 || pdim > 512 || (k > 16 && pdim > 384)) return 0;
-  return nq > 128 ? 8 : 4;
-}
-// rows per tile of the configuration scan_wide_waves() picks
-int scan_wide_tile_rows(int nw, int pdim) { return (nw == 8 && pdim <= 384) ? 64 : 32; }
-// list slots per lane the kernel is instantiated for (>= k); the partial lists are 2 * this wide
-int scan_wide_slots(int k) { return k <= 4 ? 4 : k <= 10 ? 10 : k <= 16 ? 16 : k <= 24 ? 24 : 32; }
-// the 24- / 32-slot forms carry the non-temporal slab stream and the ticketed tile schedule (ScanArgs::nt / ticket)
-bool scan_wide_streamed(int k) { return scan_wide_slots(k) > 16; }
-// resident workgroups per CU: the query fragments cost D/4 registers per lane -> two waves per SIMD
-int scan_wide_wg_per_cu(int nw, int pdim) { return nw == 8 ? 1 : 2; }
-
-// CRS_WIDE_STAGGER=0: waves 4..7 of the split forms select in step with waves 0..3 (A/B runs).  Read per call.
-// CRS_WIDE_MFMA=16 | 32: the MFMA shape of the forms that exist in both, over the table (A/B runs, tests).  Read per call.
-int scan_launch_wide(const ScanArgs& a_, int pdim, int nw, hipStream_t stream) {
-  ScanArgs a = a_;
-  const char* se = getenv("CRS_WIDE_STAGGER");
-  a.no_stagger = (se && se[0] == '0') ? 1 : 0;
-  const char* me = getenv("CRS_WIDE_MFMA");
-  const int shape = !me ? 0 : (me[0] == '1' && me[1] == '6' && !me[2]) ? 16 : (me[0] == '3' && me[1] == '2' && !me[2]) ? 32 : 0;
+int scan_launch_wide(const ScanArgs& a, int pdim, int nw, int mfma, hipStream_t stream) {
   switch (pdim) {
-    case 128: return launch_wide_d<128>(a, nw, shape, stream);
-    case 256: return launch_wide_d<256>(a, nw, shape, stream);
-    case 384: return launch_wide_d<384>(a, nw, shape, stream);
-    case 512: return launch_wide_d<512>(a, nw, shape, stream);
+    case 128: return launch_wide_d<128>(a, nw, mfma, stream);
+    case 256: return launch_wide_d<256>(a, nw, mfma, stream);
+    case 384: return launch_wide_d<384>(a, nw, mfma, stream);
+    case 512: return launch_wide_d<512>(a, nw, mfma, stream);
     default: return -1;
   }
 }

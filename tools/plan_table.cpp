@@ -1,0 +1,36 @@
+// plan_table.cpp -- the scan planner (csrc/plan.cpp) as a stand-alone program: no HIP, no device.
+//   g++ -O2 -std=c++17 -o plan_table tools/plan_table.cpp compressed-rag-suite_amd/csrc/plan.cpp
+//   ./plan_table <CUs> < cases            one case per line: nq dim k n_rows slab_type (0 fp16, 1 int8)
+// The knobs come from the environment (CRS_SCAN_TB=0 ./plan_table 256 ...), as in the library.  One tab-separated line per case:
+//   family waves slots tile_rows n_tiles streams qblocks kp nt ticket t_dyn dyn_mask boot sched no_stagger mfma form_exists
+//   workspace_bytes describe-text
+// (workspace_bytes is what crs_scan_workspace_bytes answers; the text is crs_scan_plan_describe's up to "; cert tail:").
+// tests/test_plan_cpu.py drives it; for a sanitizer run add -fsanitize=address,undefined to the g++ line.
+#include <stdio.h>
+#include <stdlib.h>
+
+#include "../compressed-rag-suite_amd/csrc/plan.h"
+
+int main(int argc, char** argv) {
+  if (argc != 2 || atoi(argv[1]) <= 0) { fprintf(stderr, "usage: plan_table <CUs> < cases\n"); return 2; }
+  const int cus = atoi(argv[1]);
+  static const char* const kFamily[] = {"Classic", "TileBest", "Wide", "W1"};
+  int nq, dim, k, slab_type;
+  long long n_rows;
+  while (scanf("%d %d %d %lld %d", &nq, &dim, &k, &n_rows, &slab_type) == 5) {
+    const crs::Knobs kn = crs::knobs_from_env();
+    crs::Plan p;
+    const char* why = "";
+    size_t ws = 0;
+    char text[192];
+    if (crs::make_plan(nq, dim, k, n_rows, slab_type, cus, kn, &p, &why) || crs::plan_workspace_bytes(nq, dim, k, n_rows, cus, kn, &ws, &why)) {
+      printf("error\t%s\n", why);
+      continue;
+    }
+    crs::plan_describe(p, text, sizeof text);
+    printf("%s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%zu\t%s\n", kFamily[(int)p.family], p.waves, p.slots, p.tile_rows,
+           p.n_tiles, p.nwg, p.nqb, p.kp, p.nt, (int)p.ticket, p.t_dyn, p.dyn_mask, p.boot, p.sched, p.no_stagger, p.mfma, (int)p.form_exists(),
+           ws, text);
+  }
+  return 0;
+}

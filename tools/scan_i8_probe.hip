@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <stdio.h>
+#include <stdlib.h>
 #include <vector>
 
 int main(int argc, char** argv) {
@@ -13,7 +14,7 @@ int main(int argc, char** argv) {
   const int nq = argc > 3 ? atoi(argv[3]) : 64;
   const int k = argc > 4 ? atoi(argv[4]) : 10;
   const int wgpc = argc > 5 ? atoi(argv[5]) : 2;
-  const int tr = crs::scan_i8_tile_rows();
+  const int tr = crs::i8_tile_rows();
   const int n_tiles = (rows + tr - 1) / tr;
   hipDeviceProp_t prop; hipGetDeviceProperties(&prop, 0);
   const int nwg = std::min(n_tiles, prop.multiProcessorCount * wgpc);

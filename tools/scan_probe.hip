@@ -5,21 +5,23 @@
 #define CRS_STAMPS 1
 #include "../compressed-rag-suite_amd/csrc/scan.hip"
 #include "../compressed-rag-suite_amd/csrc/scan_i8.hip"
+#include "../compressed-rag-suite_amd/csrc/plan.cpp"   // knobs_from_env
 
 #include <algorithm>
 #include <stdio.h>
 #include <vector>
 
 int main(int argc, char** argv) {
+  const crs::Knobs kn = crs::knobs_from_env();
   const int rows = argc > 1 ? atoi(argv[1]) : 100000;
   const int dim = argc > 2 ? atoi(argv[2]) : 384;
   const int nq = argc > 3 ? atoi(argv[3]) : 64;
   const int k = argc > 4 ? atoi(argv[4]) : 10;
   if (argc > 5) setenv("CRS_SCAN_VARIANT", argv[5], 1);
-  const int tr = crs::scan_tile_rows(dim);
+  const int tr = crs::classic_tile_rows(dim);
   const int n_tiles = (rows + tr - 1) / tr;
   hipDeviceProp_t prop; hipGetDeviceProperties(&prop, 0);
-  const int nwg = std::min(n_tiles, prop.multiProcessorCount * crs::scan_wg_per_cu());
+  const int nwg = std::min(n_tiles, prop.multiProcessorCount * crs::classic_wg_per_cu(kn.scan_variant));
   std::vector<_Float16> h((size_t)rows * dim), hq((size_t)nq * dim);
   unsigned s = 12345;
   auto rnd = [&]() { s = s * 1664525u + 1013904223u; return ((s >> 8) & 0xffff) / 65536.0f - 0.5f; };
@@ -33,12 +35,12 @@ int main(int argc, char** argv) {
   hipMemcpy(q, hq.data(), hq.size() * 2, hipMemcpyHostToDevice);
   unsigned* tau; hipMalloc(&tau, nq * 4);
   crs::ScanArgs a{};
-  a.q = q; a.slab = slab; a.scales = nullptr; a.part_scores = ps; a.part_rows = pr; a.tau_shared = crs::scan_share_tau() ? tau : nullptr;
+  a.q = q; a.slab = slab; a.scales = nullptr; a.part_scores = ps; a.part_rows = pr; a.tau_shared = kn.share_tau ? tau : nullptr;
   a.stamps = st; a.n_rows = rows; a.n_tiles = n_tiles; a.nq = nq; a.k = k; a.nqb = (nq + 63) / 64; a.nwg = nwg; a.kp = k; a.sched = getenv("CRS_SCAN_SCHED") ? atoi(getenv("CRS_SCAN_SCHED")) : 1; a.boot = getenv("CRS_SCAN_BOOT") && getenv("CRS_SCAN_BOOT")[0] == '0' ? 0 : 1;
   for (int rep = 0; rep < 3; ++rep) {
     hipMemset(st, 0, (size_t)nwg * 4 * 64 * 8);
     hipMemset(tau, 0, nq * 4);
-    int e = crs::scan_launch_f16(a, dim, nwg, 0);
+    int e = crs::scan_launch_f16(a, dim, kn.scan_variant, 0);
     hipDeviceSynchronize();
     if (e) { printf("launch error %d\n", e); return 1; }
   }
@@ -50,7 +52,7 @@ int main(int argc, char** argv) {
   auto mx = [](std::vector<double> v) { return *std::max_element(v.begin(), v.end()); };
   auto mn = [](std::vector<double> v) { return *std::min_element(v.begin(), v.end()); };
   auto diff = [&](int a_, int b_) { auto x = col(a_), y = col(b_); std::vector<double> d; for (size_t i = 0; i < x.size(); ++i) if (x[i] && y[i]) d.push_back(y[i] - x[i]); return d; };
-  printf("rows %d dim %d nq %d k %d  nwg %d tiles/wg %.2f variant %d\n", rows, dim, nq, k, nwg, (double)n_tiles / nwg, crs::scan_variant());
+  printf("rows %d dim %d nq %d k %d  nwg %d tiles/wg %.2f variant %d\n", rows, dim, nq, k, nwg, (double)n_tiles / nwg, kn.scan_variant);
   auto r0 = col(62), r1 = col(63);
   const double t0 = mn(r0);
   std::vector<double> starts, ends; for (int b = 0; b < nwg; ++b) { starts.push_back((r0[b] - t0) * 10.0); ends.push_back((r1[b] - t0) * 10.0); }

@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <stdio.h>
+#include <stdlib.h>
 #include <vector>
 
 int main(int argc, char** argv) {
@@ -12,7 +13,7 @@ int main(int argc, char** argv) {
   const int dim = argc > 2 ? atoi(argv[2]) : 384;
   const int nq = argc > 3 ? atoi(argv[3]) : 64;
   const int k = argc > 4 ? atoi(argv[4]) : 10;
-  const int wgpc = argc > 5 ? atoi(argv[5]) : crs::scan_tb_wg_per_cu(dim, 4);
+  const int wgpc = argc > 5 ? atoi(argv[5]) : crs::tb_wg_per_cu(dim, 4);
   const int tr = dim <= 512 ? 32 : 16;
   const int n_tiles = (rows + tr - 1) / tr;
   hipDeviceProp_t prop; hipGetDeviceProperties(&prop, 0);

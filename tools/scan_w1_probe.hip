@@ -6,13 +6,14 @@
 #include <algorithm>
 #include <math.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <vector>
 
 int main(int argc, char** argv) {
   const int rows = argc > 1 ? atoi(argv[1]) : 1000000;
   const int dim = argc > 2 ? atoi(argv[2]) : 768;
   const int nq = argc > 3 ? atoi(argv[3]) : 256;
-  const int qpw = crs::scan_w1_queries_per_wg(nq, 16, dim);
+  const int qpw = (nq > 64 && crs::w1_form_exists(dim)) ? crs::kW1Queries : 0;
   if (!qpw) { printf("w1 kernel not applicable\n"); return 1; }
   const int nwaves_wg = (getenv("CRS_SCAN_W1") && getenv("CRS_SCAN_W1")[0] == '1') ? 4 : 8;
   const int qg = qpw;

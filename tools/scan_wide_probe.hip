@@ -6,6 +6,7 @@
 // The last line is the clock the chip held inside the kernel: a wave's cycles over the launch / the launch's time.
 #define CRS_STAMPS 1
 #include "../compressed-rag-suite_amd/csrc/scan_wide.hip"
+#include "../compressed-rag-suite_amd/csrc/plan.cpp"   // knobs_from_env
 
 #include <algorithm>
 #include <math.h>
@@ -17,13 +18,14 @@ int main(int argc, char** argv) {
   const int dim = argc > 2 ? atoi(argv[2]) : 384;
   const int nq = argc > 3 ? atoi(argv[3]) : 256;
   const int k = argc > 4 ? atoi(argv[4]) : 10;
-  const int nw = crs::scan_wide_waves(nq, k, dim);
+  const crs::Knobs kn = crs::knobs_from_env();
+  const int nw = (nq > 64 && crs::wide_serves(k, dim)) ? (nq > 128 ? 8 : 4) : 0;
   if (!nw) { printf("wide kernel not applicable\n"); return 1; }
   const int tile_rows = crs::scan_wide_tile_rows(nw, dim);
   const int n_tiles = (rows + tile_rows - 1) / tile_rows;
   hipDeviceProp_t prop; hipGetDeviceProperties(&prop, 0);
   const int nqb = (nq + 32 * nw - 1) / (32 * nw);
-  int nwg = prop.multiProcessorCount * crs::scan_wide_wg_per_cu(nw, dim) / nqb;
+  int nwg = prop.multiProcessorCount * crs::scan_wide_wg_per_cu(nw) / nqb;
   if (nqb > 1) nwg &= ~7;
   nwg = std::min(nwg, n_tiles);
   // (the selection is branch-free: the laps do not depend on the data, so the host fills at most 1 M rows and the slab repeats them)
@@ -48,11 +50,13 @@ int main(int argc, char** argv) {
   a.n_rows = rows; a.n_tiles = n_tiles; a.nq = nq; a.k = k; a.kp = kp; a.nwg = nwg; a.nqb = nqb; a.sched = 2;
   a.t_dyn = n_tiles;
   unsigned* ticket = nullptr;
-  if (crs::scan_wide_streamed(k)) {   // the plan fields of capi.hip's make_plan / run_scan
+  const int slots = crs::scan_wide_slots(k);
+  const int mfma = !crs::wide_has_16(dim, nw, slots) ? 32 : kn.wide_mfma ? kn.wide_mfma : crs::wide_default_mfma(dim, slots);
+  a.no_stagger = kn.wide_stagger ? 0 : 1;
+  if (crs::scan_wide_streamed(k)) {   // the plan fields of plan.cpp's finish_plan
     a.nt = ((size_t)rows * dim * 2 >= ((size_t)1 << 30) && nqb == 1) ? 1 : 0;
-    const char* de = getenv("CRS_WIDE_DYN");
     const int rounds = n_tiles / nwg;
-    if (!(de && de[0] == '0') && nqb == 1 && rounds >= 96) {
+    if (kn.wide_dyn && nqb == 1 && rounds >= 96) {
       int stat = (int)((long long)rounds * 15 / 100);
       if (stat < 2) stat = 2;
       hipMalloc(&ticket, 256);
@@ -65,7 +69,7 @@ int main(int argc, char** argv) {
     hipMemset(st, 0, nst * 8);
     if (ticket) hipMemset(ticket, 0, 4);
     hipEventRecord(e0, 0);
-    int e = crs::scan_launch_wide(a, dim, nw, 0);
+    int e = crs::scan_launch_wide(a, dim, nw, mfma, 0);
     hipEventRecord(e1, 0);
     hipDeviceSynchronize();
     if (e) { printf("launch error %d\n", e); return 1; }
@@ -73,10 +77,8 @@ int main(int argc, char** argv) {
   }
   std::vector<unsigned long long> hs(nst);
   hipMemcpy(hs.data(), st, nst * 8, hipMemcpyDeviceToHost);
-  const char* se = getenv("CRS_WIDE_STAGGER");
-  const char* me = getenv("CRS_WIDE_MFMA");
-  printf("rows %d dim %d nq %d k %d | waves/wg %d nqb %d streams %d tiles/stream %.1f nt %d tickets %s stagger-knob %s mfma-knob %s | kernel %.1f us (with stamps)\n", rows, dim, nq,
-         k, nw, nqb, nwg, (double)n_tiles / nwg, a.nt, ticket ? "on" : "off", (se && se[0] == '0') ? "0" : "default", me ? me : "default", ms * 1e3);
+  printf("rows %d dim %d nq %d k %d | waves/wg %d nqb %d streams %d tiles/stream %.1f nt %d tickets %s stagger-knob %s mfma %d | kernel %.1f us (with stamps)\n", rows, dim, nq,
+         k, nw, nqb, nwg, (double)n_tiles / nwg, a.nt, ticket ? "on" : "off", kn.wide_stagger ? "default" : "0", mfma, ms * 1e3);
   // slots 2 / 4: the selection of waves 4..7 (deferred one tile) / of waves 0..3; 5, 8, 9: unused since the tile-best rewrite
   const char* names[12] = {"prologue", "tile-load issue", "selection (waves 4-7, deferred)", "MFMA sweep", "selection (waves 0-3)", "(unused)",
                            "wait next tile + LDS store", "barrier", "(unused)", "(unused)", "final flush", "TOTAL"};
