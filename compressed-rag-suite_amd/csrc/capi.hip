@@ -8,6 +8,22 @@
 #include "plan.h"
 #include "scan.h"
 
+namespace crs {
+// CUs of the current device, queried once per device (0: no device); the one CU source of both planners (enc_capi.hip too)
+int device_cus() {
+  static int cus[64] = {0};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 0;
+  if (dev < 0 || dev >= 64) return 256;
+  if (cus[dev] == 0) {
+    hipDeviceProp_t p;
+    if (hipGetDeviceProperties(&p, dev) != hipSuccess) return 0;
+    cus[dev] = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
+  }
+  return cus[dev];
+}
+}  // namespace crs
+
 namespace {
 
 thread_local char g_err[512] = "";
@@ -23,19 +39,7 @@ int hip_fail(hipError_t e, const char* where) {
 
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-int device_cus() {
-  static int cus[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 0;
-  if (dev < 0 || dev >= 64) return 256;
-  if (cus[dev] == 0) {
-    hipDeviceProp_t p;
-    if (hipGetDeviceProperties(&p, dev) != hipSuccess) return 0;
-    cus[dev] = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
-  }
-  return cus[dev];
-}
-
+using crs::device_cus;
 using crs::Plan;
 
 // the plan of a search on the current device with the environment's knobs; sets the error text

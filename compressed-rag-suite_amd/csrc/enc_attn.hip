@@ -26,10 +26,10 @@ typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kThreads = 256;
+constexpr int kThreads = forms::kAttnThreads;
 constexpr int KB = 64;   // keys per block
-constexpr int QB = 64;   // query rows per workgroup
-constexpr int kMaxSeq = 512;    // relative bias: the staged table holds 2 * 512 - 1 offsets
+constexpr int QB = forms::kAttnQ;   // query rows per workgroup
+constexpr int kMaxSeq = forms::kAttnMaxBiasSeq;    // relative bias: the staged table holds 2 * 512 - 1 offsets
 constexpr float kLog2e = 1.44269504088896341f;
 
 // One online-softmax step for this lane's query over the 16 scores it holds of a 64-key block (raw Q.K products of keys
@@ -505,13 +505,12 @@ __global__ __launch_bounds__(256) void attention_short_kernel(const _Float16* __
 
 }  // namespace
 
-int attention_launch(const _Float16* qkv, const int* lens, _Float16* ctx, int batch, int seq, int hidden, int heads,
+int attention_launch(const AttnPlan& p, const _Float16* qkv, const int* lens, _Float16* ctx, int batch, int seq, int hidden, int heads,
                      const float* rel_bias, int span, hipStream_t stream) {
-  const int hd = hidden / heads;
-  const dim3 grid((seq + QB - 1) / QB, heads, batch);
+  const dim3 grid(p.d.gx, p.d.gy, p.d.gz);
   auto blocked = [&](auto with_bias) -> int {
     constexpr bool BIAS = decltype(with_bias)::value;
-    switch (hd) {
+    switch (p.hd) {
       case 16: hipLaunchKernelGGL((attention_kernel<16, BIAS>), grid, dim3(kThreads), 0, stream, qkv, lens, ctx, seq, hidden, rel_bias, span); break;
       case 32: hipLaunchKernelGGL((attention_kernel<32, BIAS>), grid, dim3(kThreads), 0, stream, qkv, lens, ctx, seq, hidden, rel_bias, span); break;
       case 64: hipLaunchKernelGGL((attention_kernel<64, BIAS>), grid, dim3(kThreads), 0, stream, qkv, lens, ctx, seq, hidden, rel_bias, span); break;
@@ -519,44 +518,39 @@ int attention_launch(const _Float16* qkv, const int* lens, _Float16* ctx, int ba
     }
     return (int)hipGetLastError();
   };
-  if (rel_bias) {   // the blocked kernel at every sequence length: the short and whole-sequence kernels carry no bias
-    if (seq < 1 || seq > kMaxSeq || span < seq || batch < 1 || batch > 65535) return -1;
-    return blocked(std::true_type{});
-  }
-  // whole sequence per workgroup when it is long enough to matter and short enough for LDS (CRS_ATTN_SEQ=0: off)
-  static int seq_on = -1;
-  if (seq_on < 0) { const char* e = getenv("CRS_ATTN_SEQ"); seq_on = (e && e[0] == '0') ? 0 : 1; }
-  static int short_on = -1;   // CRS_ATTN_SHORT=0: query-length sequences on the blocked kernel (A/B runs)
-  if (short_on < 0) { const char* e = getenv("CRS_ATTN_SHORT"); short_on = (e && e[0] == '0') ? 0 : 1; }
-  if (short_on && seq <= 16 && (hd == 32 || hd == 64)) {
-    const int units = heads * batch;
-    if (hd == 32) hipLaunchKernelGGL((attention_short_kernel<32>), dim3((units + 3) / 4), dim3(256), 0, stream, qkv, lens, ctx, seq, hidden, units);
-    else hipLaunchKernelGGL((attention_short_kernel<64>), dim3((units + 3) / 4), dim3(256), 0, stream, qkv, lens, ctx, seq, hidden, units);
+  auto whole = [&](auto kernel) -> int {   // whole sequence per workgroup
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, p.d.lds);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(kernel, grid, dim3(p.d.threads), p.d.lds, stream, qkv, lens, ctx, seq, hidden);
     return (int)hipGetLastError();
-  }
-  if (seq_on && seq > 64) {
-    dim3 g2(heads * batch);
-    auto launch = [&](auto kernel, int threads, int lds) -> int {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      if (e != hipSuccess) return (int)e;
-      hipLaunchKernelGGL(kernel, g2, dim3(threads), lds, stream, qkv, lens, ctx, seq, hidden);
+  };
+  const auto is = [&](int hd, int smax, int qt) { return p.hd == hd && p.smax == smax && p.qt == qt; };   // the instantiations
+  switch (p.form) {
+    case AttnForm::Blocked:
+      if (!p.bias) return blocked(std::false_type{});
+      if (!rel_bias || seq < 1 || seq > kMaxSeq || span < seq || batch < 1 || batch > 65535) return -1;
+      return blocked(std::true_type{});
+    case AttnForm::Short: {
+      const int units = heads * batch;
+      if (p.hd == 32) hipLaunchKernelGGL((attention_short_kernel<32>), grid, dim3(256), 0, stream, qkv, lens, ctx, seq, hidden, units);
+      else hipLaunchKernelGGL((attention_short_kernel<64>), grid, dim3(256), 0, stream, qkv, lens, ctx, seq, hidden, units);
       return (int)hipGetLastError();
-    };
-    static int x32 = -1;   // CRS_ATTN_X32=0: the 16x16x16 whole-sequence kernel (A/B runs)
-    if (x32 < 0) { const char* e = getenv("CRS_ATTN_X32"); x32 = (e && e[0] == '0') ? 0 : 1; }
-    static int qt4 = -1;   // CRS_ATTN_QT=4: four query tiles per wave (A/B)
-    if (qt4 < 0) { const char* e = getenv("CRS_ATTN_QT"); qt4 = (e && e[0] == '4') ? 1 : 0; }
-    if (x32 && qt4 && hd == 32 && seq <= 256) return launch(&attention_seq32_kernel<32, 256, 4, 4>, 256, (256 * 40 + 32 * 264) * 2);
-    if (x32 && qt4 && hd == 64 && seq <= 512 && seq > 256) return launch(&attention_seq32_kernel<64, 512, 8, 4>, 512, (512 * 72 + 64 * 520) * 2);
-    if (x32 && hd == 32 && seq <= 256) return launch(&attention_seq32_kernel<32, 256, 4, 2>, 256, (256 * 40 + 32 * 264) * 2);
-    if (x32 && hd == 64 && seq <= 512 && seq > 256) return launch(&attention_seq32_kernel<64, 512, 8, 2>, 512, (512 * 72 + 64 * 520) * 2);
-    if (x32 && hd == 64 && seq <= 256) return launch(&attention_seq32_kernel<64, 256, 4, 2>, 256, (256 * 72 + 64 * 264) * 2);
-    if (hd == 32 && seq <= 256) return launch(&attention_seq_kernel<32, 256, 4>, 256, (256 * 36 + 32 * 260) * 2);
-    if (hd == 16 && seq <= 256) return launch(&attention_seq_kernel<16, 256, 4>, 256, (256 * 20 + 16 * 260) * 2);
-    if (hd == 64 && seq <= 512 && seq > 256) return launch(&attention_seq_kernel<64, 512, 8>, 512, (512 * 68 + 64 * 516) * 2);
-    if (hd == 64 && seq <= 256) return launch(&attention_seq_kernel<64, 256, 4>, 256, (256 * 68 + 64 * 260) * 2);
+    }
+    case AttnForm::Seq32:
+      if (is(32, 256, 4)) return whole(&attention_seq32_kernel<32, 256, 4, 4>);
+      if (is(64, 512, 4)) return whole(&attention_seq32_kernel<64, 512, 8, 4>);
+      if (is(32, 256, 2)) return whole(&attention_seq32_kernel<32, 256, 4, 2>);
+      if (is(64, 512, 2)) return whole(&attention_seq32_kernel<64, 512, 8, 2>);
+      if (is(64, 256, 2)) return whole(&attention_seq32_kernel<64, 256, 4, 2>);
+      return -1;
+    case AttnForm::Seq:
+      if (is(32, 256, 0)) return whole(&attention_seq_kernel<32, 256, 4>);
+      if (is(16, 256, 0)) return whole(&attention_seq_kernel<16, 256, 4>);
+      if (is(64, 512, 0)) return whole(&attention_seq_kernel<64, 512, 8>);
+      if (is(64, 256, 0)) return whole(&attention_seq_kernel<64, 256, 4>);
+      return -1;
+    default: return -1;
   }
-  return blocked(std::false_type{});
 }
 
 }  // namespace crs

@@ -11,78 +11,29 @@
 // then pooling + L2 normalise -- or, for crs_encoder_score_pairs, the pair head (enc_pair.hip) on the [CLS] rows; its embedding
 // step takes a token-type row per token (embed_ln_launch with type_ids).  The launch function allocates nothing and never synchronises, so
 // a caller may capture it into a hipGraph for the launch-bound single-query case.
+// Which kernel each of these steps runs on is the plan's business (enc_plan.cpp: make_enc_plan, once per call); this file walks it.
 #include "../../include/crs_encoder.h"
 #include "../../include/crs_hip.h"
 
 #include <stdio.h>
-#include <stdlib.h>
 
 #include "enc.h"
 
 namespace crs {
 int set_error(int code, const char* msg);  // capi.hip
+int device_cus();                          // capi.hip: per device, 0 without one
 }
 
 namespace {
 
-size_t up256(size_t x) { return (x + 255) / 256 * 256; }
-
-bool bigln_enabled() {   // CRS_ENC_BIGLN=0: tiled GEMM + separate LayerNorm on the index-build side (A/B runs)
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("CRS_ENC_BIGLN"); v = (e && e[0] == '0') ? 0 : 1; }
-  return v == 1;
+// the knobs are read once, at the first encoder plan of the process
+const crs::EncKnobs& knobs() {
+  static const crs::EncKnobs kn = crs::enc_knobs_from_env();
+  return kn;
 }
 
-bool qa_enabled() {   // CRS_ENC_QKVATTN=0: separate QKV GEMM and attention launches (A/B runs, tests)
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("CRS_ENC_QKVATTN"); v = (e && e[0] == '0') ? 0 : 1; }
-  return v == 1;
-}
-
-struct Layout {
-  size_t x32, y32, x16, ctx, qkv, ffn, total;
-  int max_split;
-};
-
-// Small token counts are latency-bound: use the one-shot panel GEMM (+ split-K partials reduced in
-// the LayerNorm); large ones (index build) use the pipelined 128 x 128 kernel.
-constexpr int kPanelMaxTokens = 4096;
-// split-K panels (fp32 partials summed by the LayerNorm): round 1 measured them losing at 4096 tokens of bge (C3 step 2.79 ms
-// against 2.05 through the tiled kernel's fused epilogue) -- with one-shot 384-column staging and 2 / 8 slabs.  With the
-// workgroups walking their K range in 128-column pieces and the slab count capped by the row count (gemm_panel_splits) a
-// SINGLE forward at 4096 tokens is faster through split-K panels (bge-base 256 x 16 tokens: 1996 -> 1855 us, one stream), but
-// with eight batches in flight the extra slab traffic costs more than the latency it saves (C3: 2.21 against 2.11 ms per
-// batch, tools/ab_c3.sh) -- so the limit stays at 2048 tokens (bge-base 128 x 16: 1500 -> 1140 us); CRS_SPLITK_MAX_TOKENS
-// moves it
-constexpr int kSplitKMaxTokens = 2048;
-bool use_panel(int tokens, int k) {
-  const int kc = crs::gemm_panel_chunk(k);
-  if (tokens > kPanelMaxTokens || kc == 0) return false;
-  static int splitk_max_tokens = -1;   // CRS_SPLITK_MAX_TOKENS: A/B runs
-  if (splitk_max_tokens < 0) { const char* e = getenv("CRS_SPLITK_MAX_TOKENS"); splitk_max_tokens = e ? atoi(e) : kSplitKMaxTokens; }
-  if (k / kc > 1 && tokens > splitk_max_tokens) return false;
-  const int ns = crs::gemm_panel_splits(k, tokens);   // slab counts the LayerNorm kernel is instantiated for
-  return ns == 1 || ns == 2 || ns == 3 || ns == 4 || ns == 6 || ns == 8;
-}
-
-Layout make_layout(const crs_encoder_desc* d, int batch, int seq) {
-  const size_t t = (size_t)batch * seq, h = d->hidden, f = d->ffn;
-  Layout l;
-  size_t off = 0;
-  int split = 1;
-  if (use_panel((int)t, (int)f)) split = crs::gemm_panel_splits((int)f, (int)t);
-  if (use_panel((int)t, (int)h) && crs::gemm_panel_splits((int)h, (int)t) > split) split = crs::gemm_panel_splits((int)h, (int)t);
-  if (crs::gemm8_splitk((int)t, (int)h, (int)f) > split) split = crs::gemm8_splitk((int)t, (int)h, (int)f);
-  if (crs::gemm8_splitk((int)t, (int)h, (int)h) > split) split = crs::gemm8_splitk((int)t, (int)h, (int)h);
-  l.max_split = split;
-  l.x32 = off; off += up256(t * h * 4);
-  l.y32 = off; off += up256(t * h * 4 * split);
-  l.x16 = off; off += up256(t * h * 2);
-  l.ctx = off; off += up256(t * h * 2);
-  l.qkv = off; off += up256(t * 3 * h * 2);
-  l.ffn = off; off += up256(t * f * 2);
-  l.total = off;
-  return l;
+crs::EncPlan plan_for(const crs_encoder_desc* d, int batch, int seq, int rel_bias, int pair, int cus) {
+  return crs::make_enc_plan(d->hidden, d->heads, d->ffn, d->flags, batch, seq, rel_bias, pair, cus, knobs());
 }
 
 int check_desc(const crs_encoder_desc* d) {
@@ -121,7 +72,7 @@ int crs_encoder_workspace_bytes(const crs_encoder_desc* d, int batch, int seq, s
   const int rc = check_desc(d);
   if (rc) return rc;
   if (!bytes || batch <= 0 || seq <= 0 || seq > d->max_pos) return crs::set_error(CRS_EINVAL, "bad batch/seq (seq <= max_pos)");
-  *bytes = make_layout(d, batch, seq).total;
+  *bytes = plan_for(d, batch, seq, 0, 0, 1).total;   // the layout depends on no CU count: a pure host call
   return CRS_OK;
 }
 
@@ -130,9 +81,20 @@ int crs_gemm_f16(const void* a_dev, const void* w_dev, const float* bias_dev, co
   if (!a_dev || !w_dev || !out_dev || m <= 0 || n <= 0 || k <= 0) return crs::set_error(CRS_EINVAL, "bad gemm arguments");
   if (k % 64) return crs::set_error(CRS_EINVAL, "gemm K must be a multiple of 64");
   if (mode < 0 || mode > 2 || (mode == 2 && !residual_dev)) return crs::set_error(CRS_EINVAL, "bad gemm mode / missing residual");
-  CRS_TRY(crs::gemm_f16_launch((const _Float16*)a_dev, (const _Float16*)w_dev, bias_dev, residual_dev, out_dev, m, n,
-                               k, mode, (hipStream_t)stream), "gemm");
+  const int cus = crs::device_cus();
+  if (cus <= 0) return crs::set_error(CRS_EHIP, "gemm: no device");
+  CRS_TRY(crs::gemm_launch(crs::plan_gemm(m, n, k, mode, 0, cus, knobs()), (const _Float16*)a_dev, (const _Float16*)w_dev, bias_dev,
+                           residual_dev, out_dev, (hipStream_t)stream), "gemm");
   return CRS_OK;
+}
+
+int crs_encoder_plan_describe(const crs_encoder_desc* d, int batch, int seq, int rel_bias, int pair, char* buf, size_t cap) {
+  const int rc = check_desc(d);
+  if (rc) return rc;
+  if (batch <= 0 || seq <= 0 || seq > d->max_pos || pair < 0 || pair > 2 || (cap && !buf)) return crs::set_error(CRS_EINVAL, "bad batch/seq (seq <= max_pos), pair or buffer");
+  const int cus = crs::device_cus();
+  if (cus <= 0) return crs::set_error(CRS_EHIP, "plan describe: no device");
+  return crs::enc_plan_describe(plan_for(d, batch, seq, rel_bias != 0, pair, cus), buf, cap);
 }
 
 static int encoder_forward(const crs_encoder_desc* d, const crs_encoder_weights* w, const int32_t* ids_dev,
@@ -151,72 +113,45 @@ static int encoder_forward(const crs_encoder_desc* d, const crs_encoder_weights*
     snprintf(m, sizeof m, "relative bias: rel_span %d must be >= seq %d, and seq <= 512", rel_span, seq);
     return crs::set_error(CRS_EINVAL, m);
   }
-  const Layout l = make_layout(d, batch, seq);
-  if (workspace_bytes < l.total) return crs::set_error(CRS_ENOSPC, "encoder workspace too small");
+  const int cus = crs::device_cus();
+  if (cus <= 0) return crs::set_error(CRS_EHIP, "encoder forward: no device");
+  // integer arithmetic only: no allocation, no device call, legal inside graph capture
+  const crs::EncPlan p = plan_for(d, batch, seq, rel_bias != nullptr, pair ? (pair->type_ids ? 1 : 2) : 0, cus);
+  if (workspace_bytes < p.total) return crs::set_error(CRS_ENOSPC, "encoder workspace too small");
   hipStream_t st = (hipStream_t)stream;
   char* ws = reinterpret_cast<char*>(workspace_dev);
-  float* x32 = reinterpret_cast<float*>(ws + l.x32);
-  float* y32 = reinterpret_cast<float*>(ws + l.y32);
-  _Float16* x16 = reinterpret_cast<_Float16*>(ws + l.x16);
-  _Float16* ctx = reinterpret_cast<_Float16*>(ws + l.ctx);
-  _Float16* qkv = reinterpret_cast<_Float16*>(ws + l.qkv);
-  _Float16* ffn = reinterpret_cast<_Float16*>(ws + l.ffn);
-  const int T = batch * seq, H = d->hidden, F = d->ffn;
+  float* x32 = reinterpret_cast<float*>(ws + p.x32);
+  float* y32 = reinterpret_cast<float*>(ws + p.y32);
+  _Float16* x16 = reinterpret_cast<_Float16*>(ws + p.x16);
+  _Float16* ctx = reinterpret_cast<_Float16*>(ws + p.ctx);
+  _Float16* qkv = reinterpret_cast<_Float16*>(ws + p.qkv_off);
+  _Float16* ffn = reinterpret_cast<_Float16*>(ws + p.ffn_off);
+  const int T = p.tokens, H = d->hidden, F = d->ffn;
+
+  // out-projection / FFN-down + LayerNorm into x32 / x16: one fused launch, or the GEMM (fp32 slabs in y32, or bias + residual
+  // folded in) and the LayerNorm that sums the slabs
+  auto proj_ln = [&](const crs::ProjLnPlan& s, const _Float16* a, const void* wt, const float* bias, const float* g, const float* b, int k) -> int {
+    if (s.rowln2) return crs::gemm_rowln2_launch(s, a, (const _Float16*)wt, bias, x32, g, b, d->ln_eps, T, k, x32, x16, st);
+    const bool folded = s.gemm.mode == 2;
+    const int e = crs::gemm_launch(s.gemm, a, (const _Float16*)wt, folded ? bias : nullptr, folded ? x32 : nullptr, y32, st);
+    if (e) return e;
+    return crs::layernorm_launch(y32, s.gemm.slabs, folded ? nullptr : bias, folded ? nullptr : x32, g, b, d->ln_eps, T, H, x32, x16, st);
+  };
 
   CRS_TRY(crs::embed_ln_launch(ids_dev, pair ? pair->type_ids : nullptr, w->word_emb, w->pos_emb, w->type_emb,
                                pair ? pair->head->type_rows : 1, w->emb_ln_g, w->emb_ln_b, d->ln_eps, T, seq, H, d->vocab_size, x32,
                                x16, st), "embed_ln");
-  const bool panel_h = use_panel(T, H), panel_f = use_panel(T, F);
-  // index-build side (large token counts), hidden = 384: projection + bias + residual + LayerNorm in one pipelined kernel
-  const bool big_ln = T > kPanelMaxTokens && bigln_enabled();
-  const bool big_ln_h = big_ln && crs::gemm_rowln2_supported(H, H), big_ln_f = big_ln && crs::gemm_rowln2_supported(H, F);
-  // fp16-epilogue projections (QKV, FFN-up) on the panel kernel: K = H in one chunk, or (CRS_ENC_PANEL_MULTI != 0) walked in
-  // chunks by the workgroup -- bge-base at query-batch sizes, where the row-streaming kernel pays a 196 KB weight prologue
-  // per workgroup for a handful of tiles
-  static int panel_multi = -1;
-  if (panel_multi < 0) { const char* e = getenv("CRS_ENC_PANEL_MULTI"); panel_multi = (e && e[0] == '0') ? 0 : 1; }
-  // (the phase-scheduled 256 x 256 kernel takes QKV / FFN-up as soon as it has a chip's worth of tiles: bge-base from 4096 tokens)
-  const bool single_h = T <= kPanelMaxTokens && crs::gemm_panel_chunk(H) != 0 && (crs::gemm_panel_chunk(H) == H || panel_multi) &&
-                        !crs::gemm8_applies(T, 3 * H, H, 0);
-  const int s8_h = (!panel_h) ? crs::gemm8_splitk(T, H, H) : 0, s8_f = (!panel_f) ? crs::gemm8_splitk(T, H, F) : 0;
-  // short sequences in the launch-bound regime: QKV projection + attention as one kernel (enc_qkvattn.hip)
-  const int small = (d->flags & CRS_ENC_SMALL_LDS) ? 1 : 0;
-  const bool fuse_qa = !rel_bias && T <= kPanelMaxTokens && !small && qa_enabled() && crs::qkv_attn_supported(H, d->heads, seq);
   for (int li = 0; li < d->layers; ++li) {
     const crs_encoder_layer& L = w->layers[li];
-    if (fuse_qa) {
-      CRS_TRY(crs::qkv_attn_launch(x16, (const _Float16*)L.w_qkv, L.b_qkv, lens_dev, ctx, batch, seq, H, d->heads, st), "qkv + attention");
+    if (p.attn.form == crs::AttnForm::Fused) {
+      CRS_TRY(crs::qkv_attn_launch(p.attn, x16, (const _Float16*)L.w_qkv, L.b_qkv, lens_dev, ctx, T, seq, H, st), "qkv + attention");
     } else {
-    if (single_h) CRS_TRY(crs::gemm_panel_launch(x16, (const _Float16*)L.w_qkv, L.b_qkv, qkv, T, 3 * H, H, 0, small, st), "qkv gemm");
-    else CRS_TRY(crs::gemm_f16_launch(x16, (const _Float16*)L.w_qkv, L.b_qkv, nullptr, qkv, T, 3 * H, H, 0, st), "qkv gemm");
-    CRS_TRY(crs::attention_launch(qkv, lens_dev, ctx, batch, seq, H, d->heads, rel_bias, rel_span, st), "attention");
+      CRS_TRY(crs::gemm_launch(p.qkv, x16, (const _Float16*)L.w_qkv, L.b_qkv, nullptr, qkv, st), "qkv gemm");
+      CRS_TRY(crs::attention_launch(p.attn, qkv, lens_dev, ctx, batch, seq, H, d->heads, rel_bias, rel_span, st), "attention");
     }
-    if (big_ln_h) {
-      CRS_TRY(crs::gemm_rowln2_launch(ctx, (const _Float16*)L.w_o, L.b_o, x32, L.ln1_g, L.ln1_b, d->ln_eps, T, H, H, x32, x16, st), "out projection + layernorm 1");
-    } else if (panel_h) {
-      CRS_TRY(crs::gemm_panel_launch(ctx, (const _Float16*)L.w_o, nullptr, y32, T, H, H, 3, small, st), "out gemm");
-      CRS_TRY(crs::layernorm_launch(y32, crs::gemm_panel_splits(H, T), L.b_o, x32, L.ln1_g, L.ln1_b, d->ln_eps, T, H, x32, x16, st), "layernorm 1");
-    } else if (s8_h) {
-      CRS_TRY(crs::gemm8_splitk_launch(ctx, (const _Float16*)L.w_o, y32, T, H, H, s8_h, st), "out gemm (split-K)");
-      CRS_TRY(crs::layernorm_launch(y32, s8_h, L.b_o, x32, L.ln1_g, L.ln1_b, d->ln_eps, T, H, x32, x16, st), "layernorm 1");
-    } else {
-      CRS_TRY(crs::gemm_f16_launch(ctx, (const _Float16*)L.w_o, L.b_o, x32, y32, T, H, H, 2, st), "out gemm");
-      CRS_TRY(crs::layernorm_launch(y32, 1, nullptr, nullptr, L.ln1_g, L.ln1_b, d->ln_eps, T, H, x32, x16, st), "layernorm 1");
-    }
-    if (single_h) CRS_TRY(crs::gemm_panel_launch(x16, (const _Float16*)L.w_up, L.b_up, ffn, T, F, H, 1, small, st), "ffn up gemm");
-    else CRS_TRY(crs::gemm_f16_launch(x16, (const _Float16*)L.w_up, L.b_up, nullptr, ffn, T, F, H, 1, st), "ffn up gemm");
-    if (big_ln_f) {
-      CRS_TRY(crs::gemm_rowln2_launch(ffn, (const _Float16*)L.w_down, L.b_down, x32, L.ln2_g, L.ln2_b, d->ln_eps, T, H, F, x32, x16, st), "ffn down projection + layernorm 2");
-    } else if (panel_f) {
-      CRS_TRY(crs::gemm_panel_launch(ffn, (const _Float16*)L.w_down, nullptr, y32, T, H, F, 3, small, st), "ffn down gemm");
-      CRS_TRY(crs::layernorm_launch(y32, crs::gemm_panel_splits(F, T), L.b_down, x32, L.ln2_g, L.ln2_b, d->ln_eps, T, H, x32, x16, st), "layernorm 2");
-    } else if (s8_f) {
-      CRS_TRY(crs::gemm8_splitk_launch(ffn, (const _Float16*)L.w_down, y32, T, H, F, s8_f, st), "ffn down gemm (split-K)");
-      CRS_TRY(crs::layernorm_launch(y32, s8_f, L.b_down, x32, L.ln2_g, L.ln2_b, d->ln_eps, T, H, x32, x16, st), "layernorm 2");
-    } else {
-      CRS_TRY(crs::gemm_f16_launch(ffn, (const _Float16*)L.w_down, L.b_down, x32, y32, T, H, F, 2, st), "ffn down gemm");
-      CRS_TRY(crs::layernorm_launch(y32, 1, nullptr, nullptr, L.ln2_g, L.ln2_b, d->ln_eps, T, H, x32, x16, st), "layernorm 2");
-    }
+    CRS_TRY(proj_ln(p.out, ctx, L.w_o, L.b_o, L.ln1_g, L.ln1_b, H), "out projection + layernorm 1");
+    CRS_TRY(crs::gemm_launch(p.up, x16, (const _Float16*)L.w_up, L.b_up, nullptr, ffn, st), "ffn up gemm");
+    CRS_TRY(proj_ln(p.down, ffn, L.w_down, L.b_down, L.ln2_g, L.ln2_b, F), "ffn down projection + layernorm 2");
   }
   if (hidden_out_dev) {
     const hipError_t e = hipMemcpyAsync(hidden_out_dev, x32, (size_t)T * H * 4, hipMemcpyDeviceToDevice, st);

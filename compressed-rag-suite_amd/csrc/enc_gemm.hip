@@ -29,8 +29,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int BM = 128, BN = 128, BK = 64;
-constexpr int kThreads = 256;
+constexpr int BM = forms::kTiledM, BN = forms::kTiledN, BK = 64;
+constexpr int kThreads = forms::kTiledThreads;
 constexpr int kStageBytes = (BM + BN) * BK * 2;  // 32 KiB
 
 __device__ __forceinline__ int lds_off(int row, int chunk) {  // 128-byte rows, 8 x 16-byte chunks
@@ -198,12 +198,12 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_f16_kernel(const _Float16* _
 // LDS image: rows of kc halves, 16-byte chunks XOR-swizzled by row inside each 256-byte group;
 // the DMA writes LDS linearly, so the swizzle is applied to the per-lane SOURCE address.
 typedef float f32x4v __attribute__((ext_vector_type(4)));
-constexpr int PN = 64, PKC = 384;
+constexpr int PN = forms::kPanelN, PKC = forms::kPanelMaxChunk;
 
 // MODE 0: +bias -> fp16; 1: +bias, GELU -> fp16; 3: raw fp32 partial tile -> out[z][M][N].
 // TM = rows of A per workgroup: 64 (most workgroups, for tiny M) or 128 (halves the operand re-reads
 // and the workgroup count -- one wave of workgroups on 256 CUs for the 1024-token query batch).
-constexpr int kPanelThreads = 512;   // 8 waves: the LDS-DMA issue (1 KiB per wave-instruction) is the long
+constexpr int kPanelThreads = forms::kPanelThreads;   // 512, 8 waves: the LDS-DMA issue (1 KiB per wave-instruction) is the long
                                       // pole of a one-shot panel fetch, so it is spread over more waves
 
 template <int MODE, int TM>
@@ -324,113 +324,52 @@ __global__ __launch_bounds__(kPanelThreads, 1) void gemm_panel_kernel(const _Flo
   }
 }
 
+// the plan (plan_gemm_panel) chose the row tile, the staged chunk kc and the chunks walked per workgroup kin
 template <int MODE, int TM>
-int launch_panel_t(const _Float16* a, const _Float16* w, const float* bias, void* out, int m, int n, int k, int kc,
-                   int splitk, int kin_req, int small_lds, hipStream_t stream) {
+int launch_panel_t(const GemmPlan& p, const _Float16* a, const _Float16* w, const float* bias, void* out, hipStream_t stream) {
   static bool attr_done = false;
-  // small_lds (crs_encoder_desc.flags & CRS_ENC_SMALL_LDS): stage the K range in 128-column chunks (<= 48 KB of LDS: the
-  // forward can then run beside a scan's resident workgroups).  CRS_PANEL_KC=128|256|384 forces a chunk size (A/B runs).
-  static int kc_env = -1;
-  if (kc_env < 0) { const char* e = getenv("CRS_PANEL_KC"); kc_env = e ? atoi(e) : 0; if (kc_env != 128 && kc_env != 256 && kc_env != 384) kc_env = 0; }
-  const int kc_cap = kc_env ? kc_env : (small_lds ? 128 : 0);
-  // A launch of more workgroups than CUs stages 128 columns at a time: 48 KB of LDS, up to three workgroups resident
-  // per CU, one workgroup's transfers under another's MFMAs (bge-base at query-batch sizes: QKV 288, FFN-up 384, FFN-down
-  // 768 workgroups).  Measured on the bge-base query chain (tools/enc_chain_profile.py): 64 x 16 tokens 945 -> ~800 us per
-  // forward, 16 x 16: 793 -> 584, 256 x 16: 2222 -> 2000.  A single wave of workgroups keeps the one-shot fetch (MiniLM:
-  // every launch <= 192 workgroups; 237 us one-shot against 244-253 in 128-column pieces).  CRS_PANEL_KC forces a size.
-  const long wgs = (long)((n + PN - 1) / PN) * ((m + TM - 1) / TM) * splitk;
-  int kin = kin_req;
-  if (kc_cap && kc > kc_cap && kc % kc_cap == 0) { kin *= kc / kc_cap; kc = kc_cap; }
-  else if (!kc_cap && wgs > 256 && kc > 128 && kc % 128 == 0) { kin *= kc / 128; kc = 128; }
-  const int lds = (TM + PN) * kc * 2;
-  const int ep = (MODE == 3 ? 36 * 4 : 40 * 2) * 32 * ((TM / 32) * (PN / 32));   // the epilogue's wave-private tiles re-use the buffer
   if (!attr_done) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_panel_kernel<MODE, TM>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (TM + PN) * PKC * 2);
     if (e != hipSuccess) return (int)e;
     attr_done = true;
   }
-  dim3 grid((n + PN - 1) / PN, (m + TM - 1) / TM, splitk);
-  hipLaunchKernelGGL((gemm_panel_kernel<MODE, TM>), grid, dim3(kPanelThreads), lds > ep ? lds : ep, stream, a, w, bias, out, m, n, k, kc, kin);
+  hipLaunchKernelGGL((gemm_panel_kernel<MODE, TM>), dim3(p.d.gx, p.d.gy, p.d.gz), dim3(kPanelThreads), p.d.lds, stream, a, w, bias, out,
+                     p.m, p.n, p.k, p.kc, p.kin);
   return (int)hipGetLastError();
 }
 
-// 128-row tiles once 64-row tiles would need more than one wave of workgroups on the chip
 template <int MODE>
-int launch_panel(const _Float16* a, const _Float16* w, const float* bias, void* out, int m, int n, int k, int kc,
-                 int splitk, int kin, int small_lds, hipStream_t stream) {
-  const long wgs64 = (long)((n + PN - 1) / PN) * ((m + 63) / 64) * splitk;
-  // (forcing 64- or 128-row tiles everywhere measured within 2 % either way on both models' query chains)
-  if (wgs64 > 256 && m > 64) return launch_panel_t<MODE, 128>(a, w, bias, out, m, n, k, kc, splitk, kin, small_lds, stream);
-  return launch_panel_t<MODE, 64>(a, w, bias, out, m, n, k, kc, splitk, kin, small_lds, stream);
+int launch_panel(const GemmPlan& p, const _Float16* a, const _Float16* w, const float* bias, void* out, hipStream_t stream) {
+  return p.tm == 128 ? launch_panel_t<MODE, 128>(p, a, w, bias, out, stream) : launch_panel_t<MODE, 64>(p, a, w, bias, out, stream);
 }
 
 }  // namespace
 
-static bool stream_enabled() {   // CRS_GEMM_STREAM=0: always the tiled kernel (A/B runs)
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("CRS_GEMM_STREAM"); v = (e && e[0] == '0') ? 0 : 1; }
-  return v == 1;
-}
-
-int gemm_f16_launch(const _Float16* a, const _Float16* w, const float* bias, const float* residual,
-                    void* out, int m, int n, int k, int mode, hipStream_t stream) {
-  // short contraction, many rows, wide output (the index-build side's QKV and FFN-up projections): the tiled kernel
-  // below spends as long in its prologue and epilogue as in its K / 64 steps; stream rows past resident W
-  if (gemm8_applies(m, n, k, mode)) return gemm8_launch(a, w, bias, residual, out, m, n, k, mode, stream);
-  if (gemm_big_block_n(m, n, k, mode) != 0) return gemm_big_launch(a, w, bias, residual, out, m, n, k, mode, stream);
-  if (m >= 512 && n >= 512 && mode != 2 && gemm_stream_supported(k) && stream_enabled())
-    return gemm_stream_launch(a, w, bias, residual, out, m, n, k, mode, stream);
-  dim3 grid(((n + BN - 1) / BN) * ((m + BM - 1) / BM));
-  switch (mode) {
-    case 0: hipLaunchKernelGGL((gemm_f16_kernel<0>), grid, dim3(kThreads), 0, stream, a, w, bias, residual, out, m, n, k); break;
-    case 1: hipLaunchKernelGGL((gemm_f16_kernel<1>), grid, dim3(kThreads), 0, stream, a, w, bias, residual, out, m, n, k); break;
-    case 2: hipLaunchKernelGGL((gemm_f16_kernel<2>), grid, dim3(kThreads), 0, stream, a, w, bias, residual, out, m, n, k); break;
-    default: return -1;
-  }
-  return (int)hipGetLastError();
-}
-
-}  // namespace crs
-
-namespace crs {
-
-// Chunk length for the panel kernel: the largest multiple of 128 that is <= 384 and divides K (0 = none)
-int gemm_panel_chunk(int k) {
-  for (int kc = 384; kc >= 128; kc -= 128)
-    if (k % kc == 0) return kc;
-  return 0;
-}
-
-// How many fp32 partial slabs a mode-3 launch of m rows over contraction length k leaves (the LayerNorm kernel that
-// follows sums them): k / chunk, capped -- past the cap the workgroups walk several chunks each (kernel: kin).  The
-// cap falls with the row count, because the slabs are m x N x 4 bytes each and the launch no longer lacks workgroups
-// (bge-base FFN-down, K = 3072, tools/enc_chain_profile.py, whole forward): 1024 tokens: 8 / 4 / 2 slabs = 806 / 792 /
-// 850 us; 2048 tokens: - / 1138 / 1132; 4096 tokens: 2109 / 1945 / 1855 (and 1996 through the 128 x 128 kernel).
-int gemm_panel_splits(int k, int m) {
-  const int kc = gemm_panel_chunk(k);
-  if (kc == 0) return 0;
-  static int cap_env = -1;   // CRS_PANEL_MAX_SPLIT: A/B runs
-  if (cap_env < 0) { const char* e = getenv("CRS_PANEL_MAX_SPLIT"); cap_env = e ? atoi(e) : 0; }
-  const int cap = cap_env > 0 ? cap_env : (m <= 1024 ? 4 : 2);
-  int s = k / kc;
-  while (s > cap && (s % 2) == 0) s /= 2;
-  return s;
-}
-
-// out: mode 0/1 fp16 [M,N] (any k that is a multiple of the chunk: the workgroup walks the chunks); mode 3 fp32
-// [gemm_panel_splits(k, m)][M][N] partials
-int gemm_panel_launch(const _Float16* a, const _Float16* w, const float* bias, void* out, int m, int n, int k,
-                      int mode, int small_lds, hipStream_t stream) {
-  const int kc = gemm_panel_chunk(k);
-  if (kc == 0) return -1;
-  const int chunks = k / kc;
-  switch (mode) {
-    case 0: return launch_panel<0>(a, w, bias, out, m, n, k, kc, 1, chunks, small_lds, stream);
-    case 1: return launch_panel<1>(a, w, bias, out, m, n, k, kc, 1, chunks, small_lds, stream);
-    case 3: {
-      const int splitk = gemm_panel_splits(k, m);
-      return launch_panel<3>(a, w, bias, out, m, n, k, kc, splitk, chunks / splitk, small_lds, stream);
+int gemm_launch(const GemmPlan& p, const _Float16* a, const _Float16* w, const float* bias, const float* residual, void* out,
+                hipStream_t stream) {
+  switch (p.family) {
+    case GemmFamily::Gemm8:
+    case GemmFamily::Gemm8SplitK: return gemm8_launch(p, a, w, bias, residual, out, stream);
+    case GemmFamily::Big: return gemm_big_launch(p, a, w, bias, residual, out, stream);
+    case GemmFamily::Stream:
+    case GemmFamily::StreamKS: return gemm_stream_launch(p, a, w, bias, residual, out, stream);
+    case GemmFamily::Panel:   // out: mode 0 / 1 fp16 [M, N]; mode 3 fp32 [slabs][M][N] partials
+      switch (p.mode) {
+        case 0: return launch_panel<0>(p, a, w, bias, out, stream);
+        case 1: return launch_panel<1>(p, a, w, bias, out, stream);
+        case 3: return launch_panel<3>(p, a, w, bias, out, stream);
+        default: return -1;
+      }
+    case GemmFamily::Tiled: {
+      const dim3 grid(p.d.gx);
+      switch (p.mode) {
+        case 0: hipLaunchKernelGGL((gemm_f16_kernel<0>), grid, dim3(kThreads), 0, stream, a, w, bias, residual, out, p.m, p.n, p.k); break;
+        case 1: hipLaunchKernelGGL((gemm_f16_kernel<1>), grid, dim3(kThreads), 0, stream, a, w, bias, residual, out, p.m, p.n, p.k); break;
+        case 2: hipLaunchKernelGGL((gemm_f16_kernel<2>), grid, dim3(kThreads), 0, stream, a, w, bias, residual, out, p.m, p.n, p.k); break;
+        default: return -1;
+      }
+      return (int)hipGetLastError();
     }
     default: return -1;
   }

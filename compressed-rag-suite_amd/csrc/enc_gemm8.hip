@@ -37,14 +37,15 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int PM = 256, PN = 256, PK = 64;
-constexpr int kP8Threads = 512;
+constexpr int PM = forms::kG8M, PN = forms::kG8N, PK = forms::kG8K;
+constexpr int kP8Threads = forms::kG8Threads;
 constexpr int kHalf = 128 * PK * 2;            // one half tile: 128 rows x 128 bytes = 16 KB
 constexpr int kBuf = 4 * kHalf;                // one k-tile: [A0 | A1 | W0 | W1] = 64 KB
 constexpr int kLdsMain = 2 * kBuf;             // 128 KB
-constexpr int kEpiRow16 = 144;                 // epilogue staging rows: 128 bytes of payload, 16-byte aligned, bank-spread
+constexpr int kEpiRow16 = forms::kG8EpiRow16;                 // epilogue staging rows: 128 bytes of payload, 16-byte aligned, bank-spread
 constexpr int kEpiStage = 16 * kEpiRow16;      // one wave's staging tile: 16 rows (2304 bytes)
 constexpr int kLds8 = kLdsMain + 8 * kEpiStage;   // 146 KB: the staging tiles sit BEHIND the k-tile buffers
+static_assert(kLds8 == forms::kG8Lds, "enc_forms.h states the LDS image of this kernel");
 
 template <int N>
 __device__ __forceinline__ void wait_vm8() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
@@ -270,99 +271,45 @@ __global__ __launch_bounds__(kP8Threads, 2) void gemm8_kernel(const _Float16* __
   if (VAR != 3 && wm == 0) __builtin_amdgcn_s_barrier();   // the barrier row group 1 executed first: both groups end even
 }
 
+// the plan (plan_gemm8) chose persistent or one workgroup per item, the variant, the items and the contraction length per item
 template <int MODE, int VAR>
-int launch8v(const _Float16* a, const _Float16* w, const float* bias, const float* residual, void* out, int m, int n, int k,
-             int splits, int cus, hipStream_t stream) {
-  const int items = ((n + PN - 1) / PN) * (m / PM) * (MODE == 3 ? splits : 1);
-  // the stream pays for the fp16 epilogues (bias / GELU; + 8 % at K = 768 and 384: their VALU and stores sit beside the next item's
-  // first phases) and measured 4 % slower for the fp32 + residual ones (the residual loads of the 16-row passes drain behind the
-  // transfers in flight): those keep one workgroup per item.  CRS_GEMM8_VAR=1: one workgroup per item everywhere (A/B)
-  const bool persist = VAR != 1 && items > cus && MODE < 2;
-  const void* kernel = persist ? reinterpret_cast<const void*>(&gemm8_kernel<MODE, true, VAR>) : reinterpret_cast<const void*>(&gemm8_kernel<MODE, false, VAR>);
+int launch8v(const GemmPlan& p, const _Float16* a, const _Float16* w, const float* bias, const float* residual, void* out, hipStream_t stream) {
+  const void* kernel = p.persist ? reinterpret_cast<const void*>(&gemm8_kernel<MODE, true, VAR>) : reinterpret_cast<const void*>(&gemm8_kernel<MODE, false, VAR>);
   static bool done[2] = {false, false};
-  if (!done[persist]) {
+  if (!done[p.persist]) {
     hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLds8);
     if (e != hipSuccess) return (int)e;
-    done[persist] = true;
+    done[p.persist] = true;
   }
-  const int ksplit = k / (MODE == 3 ? splits : 1);
-  if (persist)
-    hipLaunchKernelGGL((gemm8_kernel<MODE, true, VAR>), dim3(cus), dim3(kP8Threads), kLds8, stream, a, w, bias, residual, out, m, n, k, ksplit, items);
+  if (p.persist)
+    hipLaunchKernelGGL((gemm8_kernel<MODE, true, VAR>), dim3(p.d.gx), dim3(kP8Threads), p.d.lds, stream, a, w, bias, residual, out, p.m, p.n, p.k, p.ksplit, p.items);
   else
-    hipLaunchKernelGGL((gemm8_kernel<MODE, false, VAR>), dim3(items), dim3(kP8Threads), kLds8, stream, a, w, bias, residual, out, m, n, k, ksplit, items);
+    hipLaunchKernelGGL((gemm8_kernel<MODE, false, VAR>), dim3(p.d.gx), dim3(kP8Threads), p.d.lds, stream, a, w, bias, residual, out, p.m, p.n, p.k, p.ksplit, p.items);
   return (int)hipGetLastError();
 }
 
-int gemm8_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) cus = p.multiProcessorCount;
-    else cus = 256;
-  }
-  return cus;
-}
-
 template <int MODE>
-int launch8(const _Float16* a, const _Float16* w, const float* bias, const float* residual, void* out, int m, int n, int k,
-            int splits, hipStream_t stream) {
-  static int var = -1;
-  if (var < 0) { const char* e = getenv("CRS_GEMM8_VAR"); var = (e && e[0] >= '0' && e[0] <= '3') ? e[0] - '0' : 0; }
-  const int cus = gemm8_cus();
-  switch (var) {
-    case 1: return launch8v<MODE, 1>(a, w, bias, residual, out, m, n, k, splits, cus, stream);
-    case 2: return launch8v<MODE, 2>(a, w, bias, residual, out, m, n, k, splits, cus, stream);
-    case 3: return launch8v<MODE, 3>(a, w, bias, residual, out, m, n, k, splits, cus, stream);
-    default: return launch8v<MODE, 0>(a, w, bias, residual, out, m, n, k, splits, cus, stream);
+int launch8(const GemmPlan& p, const _Float16* a, const _Float16* w, const float* bias, const float* residual, void* out, hipStream_t stream) {
+  switch (p.var) {
+    case 1: return launch8v<MODE, 1>(p, a, w, bias, residual, out, stream);
+    case 2: return launch8v<MODE, 2>(p, a, w, bias, residual, out, stream);
+    case 3: return launch8v<MODE, 3>(p, a, w, bias, residual, out, stream);
+    default: return launch8v<MODE, 0>(p, a, w, bias, residual, out, stream);
   }
 }
 
 }  // namespace
 
-// Shapes the phase-scheduled kernel takes: whole 256 x 256 tiles, K a multiple of 128 and >= 256 (two k-tiles in the
-// prologue), 16-byte aligned rows.  CRS_GEMM8=0 disables it (A/B runs); CRS_GEMM8_MIN_WGS moves the lower limit.
-bool gemm8_applies(int m, int n, int k, int mode) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("CRS_GEMM8"); on = (e && e[0] == '0') ? 0 : 1; }
-  // (N: whole 256-column blocks, or -- round 3, CRS_GEMM8_HALF=0 off -- a last block of 128: MiniLM's 384 / 1152)
-  static int half = -1;
-  if (half < 0) { const char* e = getenv("CRS_GEMM8_HALF"); half = (e && e[0] == '0') ? 0 : 1; }
-  const bool n_ok = n % PN == 0 || (half && n % 128 == 0 && n > PN);
-  if (!on || m % PM || !n_ok || k % 128 || k < 256) return false;
-  static long min_wgs = -1;
-  if (min_wgs < 0) { const char* e = getenv("CRS_GEMM8_MIN_WGS"); min_wgs = e ? atol(e) : 128; }
-  return (long)(m / PM) * ((n + PN - 1) / PN) >= min_wgs;
-}
-
-int gemm8_launch(const _Float16* a, const _Float16* w, const float* bias, const float* residual, void* out, int m, int n, int k, int mode,
+// mode 3 (Gemm8SplitK): out is the fp32 slabs [slabs][M][N], bias and residual are not read
+int gemm8_launch(const GemmPlan& p, const _Float16* a, const _Float16* w, const float* bias, const float* residual, void* out,
                  hipStream_t stream) {
-  switch (mode) {
-    case 0: return launch8<0>(a, w, bias, residual, out, m, n, k, 1, stream);
-    case 1: return launch8<1>(a, w, bias, residual, out, m, n, k, 1, stream);
-    case 2: return launch8<2>(a, w, bias, residual, out, m, n, k, 1, stream);
+  switch (p.mode) {
+    case 0: return launch8<0>(p, a, w, bias, residual, out, stream);
+    case 1: return launch8<1>(p, a, w, bias, residual, out, stream);
+    case 2: return launch8<2>(p, a, w, bias, residual, out, stream);
+    case 3: return launch8<3>(p, a, w, bias, residual, out, stream);
     default: return -1;
   }
-}
-
-// Split-K form for projections whose output has too few 256 x 256 tiles to fill the chip (bge-base's N = 768 at a few
-// thousand tokens): the number of K slabs (0 = not applicable) such that tiles x slabs >= 128 workgroups, every slab a
-// multiple of 128 columns and >= 256; the LayerNorm kernel that follows sums the fp32 slabs (it is instantiated for
-// 2 / 3 / 4 / 6 / 8 of them).
-int gemm8_splitk(int m, int n, int k) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("CRS_GEMM8"); on = (e && e[0] == '0') ? 0 : 1; }
-  if (!on || m % PM || n % PN || m < 2048) return 0;
-  const long tiles = (long)(m / PM) * (n / PN);
-  if (tiles >= 128) return 0;
-  const int cand[5] = {2, 3, 4, 6, 8};
-  for (int s : cand)
-    if (k % s == 0 && (k / s) % 128 == 0 && k / s >= 256 && tiles * s >= 128) return s;
-  return 0;
-}
-
-int gemm8_splitk_launch(const _Float16* a, const _Float16* w, float* partials, int m, int n, int k, int splits, hipStream_t stream) {
-  return launch8<3>(a, w, nullptr, nullptr, partials, m, n, k, splits, stream);
 }
 
 }  // namespace crs

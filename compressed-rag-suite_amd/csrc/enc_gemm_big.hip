@@ -32,8 +32,8 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
-constexpr int GM = 256, GK = 32, GS = 4;   // rows per workgroup; contraction depth per stage; LDS stages (three in flight)
-constexpr int kBigThreads = 512;
+constexpr int GM = forms::kBigM, GK = forms::kBigK, GS = forms::kBigStages;   // rows per workgroup; contraction depth per stage; LDS stages (three in flight)
+constexpr int kBigThreads = forms::kBigThreads;
 
 // 64-byte LDS rows (GK = 32 halves), 4 x 16-byte chunks: rows 4 apart share banks, so the chunk index is XORed with
 // (row >> 2) & 3 -- the 16 rows a 16-lane read group touches then cover all 64 banks
@@ -172,9 +172,8 @@ __global__ __launch_bounds__(kBigThreads, 2) void gemm_big_kernel(const _Float16
 }
 
 template <int MODE, int BN>
-int launch_big(const _Float16* a, const _Float16* w, const float* bias, const float* residual, void* out, int m, int n, int k,
-               hipStream_t stream) {
-  constexpr int lds = GS * (GM + BN) * GK * 2;
+int launch_big(const GemmPlan& p, const _Float16* a, const _Float16* w, const float* bias, const float* residual, void* out, hipStream_t stream) {
+  constexpr int lds = forms::big_lds(BN);
   static bool done = false;
   auto kernel = &gemm_big_kernel<MODE, BN>;
   if (!done) {
@@ -182,47 +181,20 @@ int launch_big(const _Float16* a, const _Float16* w, const float* bias, const fl
     if (e != hipSuccess) return (int)e;
     done = true;
   }
-  const int grid = ((n + BN - 1) / BN) * ((m + GM - 1) / GM);
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBigThreads), lds, stream, a, w, bias, residual, out, m, n, k);
+  hipLaunchKernelGGL(kernel, dim3(p.d.gx), dim3(kBigThreads), lds, stream, a, w, bias, residual, out, p.m, p.n, p.k);
   return (int)hipGetLastError();
-}
-
-template <int BN>
-int launch_big_mode(const _Float16* a, const _Float16* w, const float* bias, const float* residual, void* out, int m, int n, int k, int mode,
-                    hipStream_t stream) {
-  switch (mode) {
-    case 0: return launch_big<0, BN>(a, w, bias, residual, out, m, n, k, stream);
-    case 1: return launch_big<1, BN>(a, w, bias, residual, out, m, n, k, stream);
-    case 2: return launch_big<2, BN>(a, w, bias, residual, out, m, n, k, stream);
-    default: return -1;
-  }
 }
 
 }  // namespace
 
-// Shapes the 256 x 256 tiles take (measured, tools/bench_gemm.py, same box): fp16-epilogue projections with N a multiple
-// of 256 and K >= 512 at index-build row counts -- bge-base QKV 32768 x 2304 x 768: 457 -> 686 TFLOP/s, FFN-up
-// 32768 x 3072 x 768: 507 -> 659 (both were on the row-streaming kernel); 4096^3: 742 -> 970.  NOT taken: the fp32 +
-// residual epilogue at N = 768 (three column blocks = 384 workgroups = one and a half waves of the chip: 582 against
-// 667 for the 128 x 128 kernel's 1536 workgroups), and MiniLM's K = 384 shapes (six k-steps: the row-streaming kernel's
-// resident weights win, 733 / 541 against 419 / 439 with 256 x 128 tiles).  CRS_GEMM_BIG=0 disables it (A/B runs).
-// It is taken from 128 workgroups on (CRS_GEMM_BIG_MIN_WGS): at 4096 tokens of bge-base (C3's query batch) 144 / 192
-// workgroups of 256 x 256 beat the row-streaming kernel's 144 (QKV 42.0 -> 35.9 us, FFN-up 57.4 -> 41.5); at 2048 tokens
-// (72 / 96 workgroups) they lose (25.7 -> 31.5, 33.1 -> 36.6).
-int gemm_big_block_n(int m, int n, int k, int mode) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("CRS_GEMM_BIG"); on = (e && e[0] == '0') ? 0 : 1; }
-  if (!on || mode == 2 || k % 64 != 0 || k < 512 || n % 256 != 0) return 0;
-  const long wgs = (long)(n / 256) * ((m + GM - 1) / GM);
-  static long min_wgs = -1;
-  if (min_wgs < 0) { const char* e = getenv("CRS_GEMM_BIG_MIN_WGS"); min_wgs = e ? atol(e) : 128; }
-  return wgs >= min_wgs ? 256 : 0;
-}
-
-int gemm_big_launch(const _Float16* a, const _Float16* w, const float* bias, const float* residual, void* out, int m, int n, int k, int mode,
+int gemm_big_launch(const GemmPlan& p, const _Float16* a, const _Float16* w, const float* bias, const float* residual, void* out,
                     hipStream_t stream) {
-  if (gemm_big_block_n(m, n, k, mode) != 256) return -1;
-  return launch_big_mode<256>(a, w, bias, residual, out, m, n, k, mode, stream);
+  switch (p.mode) {
+    case 0: return launch_big<0, forms::kBigN>(p, a, w, bias, residual, out, stream);
+    case 1: return launch_big<1, forms::kBigN>(p, a, w, bias, residual, out, stream);
+    case 2: return launch_big<2, forms::kBigN>(p, a, w, bias, residual, out, stream);
+    default: return -1;
+  }
 }
 
 }  // namespace crs

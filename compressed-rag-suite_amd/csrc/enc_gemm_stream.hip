@@ -31,10 +31,10 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kThreads = 256;
-constexpr int TR = 32;     // A rows per tile
-constexpr int WN = 128;    // output columns per workgroup (4 waves x 32)
-constexpr int kEpiStride = 40;   // halves per row of the wave-private epilogue tile (32 + 8: 80-byte rows, 16-byte aligned)
+constexpr int kThreads = forms::kStreamThreads;
+constexpr int TR = forms::kStreamRows;     // A rows per tile
+constexpr int WN = forms::kStreamN;    // output columns per workgroup (4 waves x 32)
+constexpr int kEpiStride = forms::kStreamEpiStride;   // halves per row of the wave-private epilogue tile (32 + 8: 80-byte rows, 16-byte aligned)
 
 template <int K, int MODE>
 __global__ __launch_bounds__(kThreads, 2) void gemm_stream_kernel(const _Float16* __restrict__ A,
@@ -183,7 +183,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_stream_kernel(const _Float16
 // over through a double-buffered LDS tile before the tile barrier, wave p adds them to its own (kept across
 // the barrier) and runs the epilogue one tile late -- one wave of a SIMD multiplies while the other stores.
 // fp16 outputs (modes 0 / 1) only; 128 columns per workgroup, one workgroup per CU.
-constexpr int kKsThreads = 512;
+constexpr int kKsThreads = forms::kStreamKsThreads;
 
 template <int K, int MODE>
 __global__ __launch_bounds__(kKsThreads, 2) void gemm_stream_ks_kernel(const _Float16* __restrict__ A,
@@ -329,9 +329,10 @@ __global__ __launch_bounds__(kKsThreads, 2) void gemm_stream_ks_kernel(const _Fl
   if (kh == 0 && it > 0) finish(acc_prev, t - nstreams, it - 1);
 }
 
+// the plan (plan_stream) chose the column blocks and the row streams per block
 template <int K, int MODE>
-int launch_ks(const _Float16* a, const _Float16* w, const float* bias, void* out, int m, int n, int cus, hipStream_t stream) {
-  constexpr int lds = 2 * TR * K * 2 + 4 * 2 * 16 * 64 * 4 + 4 * 32 * kEpiStride * 2;
+int launch_ks(const GemmPlan& p, const _Float16* a, const _Float16* w, const float* bias, void* out, hipStream_t stream) {
+  constexpr int lds = forms::stream_ks_lds(K);
   static bool attr_done = false;
   if (!attr_done) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_stream_ks_kernel<K, MODE>),
@@ -339,21 +340,14 @@ int launch_ks(const _Float16* a, const _Float16* w, const float* bias, void* out
     if (e != hipSuccess) return (int)e;
     attr_done = true;
   }
-  const int colblocks = (n + WN - 1) / WN;
-  const int n_tiles = (m + TR - 1) / TR;
-  int streams = cus / colblocks;            // one workgroup per CU
-  if (streams < 1) streams = 1;
-  if (streams > n_tiles) streams = n_tiles;
-  if (streams >= 8) streams &= ~7;
-  hipLaunchKernelGGL((gemm_stream_ks_kernel<K, MODE>), dim3(colblocks * streams), dim3(kKsThreads), lds, stream, a, w, bias,
-                     reinterpret_cast<_Float16*>(out), m, n, colblocks, streams);
+  hipLaunchKernelGGL((gemm_stream_ks_kernel<K, MODE>), dim3(p.d.gx), dim3(kKsThreads), lds, stream, a, w, bias,
+                     reinterpret_cast<_Float16*>(out), p.m, p.n, p.colblocks, p.streams);
   return (int)hipGetLastError();
 }
 
 template <int K, int MODE>
-int launch_k(const _Float16* a, const _Float16* w, const float* bias, const float* residual, void* out, int m, int n,
-             int cus, hipStream_t stream) {
-  constexpr int lds = 2 * TR * K * 2 + 4 * 32 * kEpiStride * 2;
+int launch_k(const GemmPlan& p, const _Float16* a, const _Float16* w, const float* bias, const float* residual, void* out, hipStream_t stream) {
+  constexpr int lds = forms::stream_lds(K);
   static bool attr_done = false;
   if (!attr_done) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_stream_kernel<K, MODE>),
@@ -361,50 +355,33 @@ int launch_k(const _Float16* a, const _Float16* w, const float* bias, const floa
     if (e != hipSuccess) return (int)e;
     attr_done = true;
   }
-  const int colblocks = (n + WN - 1) / WN;
-  const int n_tiles = (m + TR - 1) / TR;
-  int streams = (cus * 2) / colblocks;      // 2 workgroups / CU resident; column blocks of a stream run together
-  if (streams < 1) streams = 1;
-  if (streams > n_tiles) streams = n_tiles;
-  if (streams >= 8) streams &= ~7;          // whole rounds over the 8 XCDs
-  dim3 grid(colblocks * streams);
-  hipLaunchKernelGGL((gemm_stream_kernel<K, MODE>), grid, dim3(kThreads), lds, stream, a, w, bias, residual, out, m, n,
-                     colblocks, streams);
+  hipLaunchKernelGGL((gemm_stream_kernel<K, MODE>), dim3(p.d.gx), dim3(kThreads), lds, stream, a, w, bias, residual, out, p.m, p.n,
+                     p.colblocks, p.streams);
   return (int)hipGetLastError();
 }
 
 template <int K>
-int launch_mode(const _Float16* a, const _Float16* w, const float* bias, const float* residual, void* out, int m,
-                int n, int mode, int cus, hipStream_t stream) {
-  switch (mode) {
-    case 0: return launch_k<K, 0>(a, w, bias, residual, out, m, n, cus, stream);
-    case 1: return launch_k<K, 1>(a, w, bias, residual, out, m, n, cus, stream);
-    case 2: return launch_k<K, 2>(a, w, bias, residual, out, m, n, cus, stream);
+int launch_mode(const GemmPlan& p, const _Float16* a, const _Float16* w, const float* bias, const float* residual, void* out, hipStream_t stream) {
+  switch (p.mode) {
+    case 0: return launch_k<K, 0>(p, a, w, bias, residual, out, stream);
+    case 1: return launch_k<K, 1>(p, a, w, bias, residual, out, stream);
+    case 2: return launch_k<K, 2>(p, a, w, bias, residual, out, stream);
     default: return -1;
   }
 }
 
 }  // namespace
 
-bool gemm_stream_supported(int k) { return k == 128 || k == 256 || k == 384 || k == 512 || k == 768; }   // 768: fp16 outputs only
-
-int gemm_stream_launch(const _Float16* a, const _Float16* w, const float* bias, const float* residual, void* out,
-                       int m, int n, int k, int mode, hipStream_t stream) {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return (int)hipErrorInvalidDevice;
-    cus = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
-  }
-  switch (k) {
-    case 128: return launch_mode<128>(a, w, bias, residual, out, m, n, mode, cus, stream);
-    case 256: return launch_mode<256>(a, w, bias, residual, out, m, n, mode, cus, stream);
-    case 384: return launch_mode<384>(a, w, bias, residual, out, m, n, mode, cus, stream);
-    case 512: return launch_mode<512>(a, w, bias, residual, out, m, n, mode, cus, stream);
-    case 768:
-      if (mode == 0) return launch_ks<768, 0>(a, w, bias, out, m, n, cus, stream);
-      if (mode == 1) return launch_ks<768, 1>(a, w, bias, out, m, n, cus, stream);
+int gemm_stream_launch(const GemmPlan& p, const _Float16* a, const _Float16* w, const float* bias, const float* residual, void* out,
+                       hipStream_t stream) {
+  switch (p.k) {
+    case 128: return launch_mode<128>(p, a, w, bias, residual, out, stream);
+    case 256: return launch_mode<256>(p, a, w, bias, residual, out, stream);
+    case 384: return launch_mode<384>(p, a, w, bias, residual, out, stream);
+    case 512: return launch_mode<512>(p, a, w, bias, residual, out, stream);
+    case 768:   // the K-split form: fp16 outputs only
+      if (p.mode == 0) return launch_ks<768, 0>(p, a, w, bias, out, stream);
+      if (p.mode == 1) return launch_ks<768, 1>(p, a, w, bias, out, stream);
       return -1;
     default: return -1;
   }

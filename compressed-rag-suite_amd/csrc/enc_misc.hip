@@ -234,37 +234,15 @@ int embed_ln_launch(const int* ids, const int* type_ids, const float* word, cons
 int layernorm_launch(const float* y, int nsplit, const float* bias, const float* residual, const float* g,
                      const float* b, float eps, int tokens, int hidden, float* x32, _Float16* x16,
                      hipStream_t stream) {
-#define CRS_LN2(PL, NS) hipLaunchKernelGGL((layernorm_kernel<PL, NS>), dim3((tokens + 3) / 4), dim3(256), 0, stream, y, \
-                                         bias, residual, g, b, eps, tokens, hidden, x32, x16)
-#define CRS_LN(PL)                                                                    \
-  switch (nsplit) {                                                                   \
-    case 1: CRS_LN2(PL, 1); break;                                                    \
-    case 2: CRS_LN2(PL, 2); break;                                                    \
-    case 3: CRS_LN2(PL, 3); break;                                                    \
-    case 4: CRS_LN2(PL, 4); break;                                                    \
-    case 6: CRS_LN2(PL, 6); break;                                                    \
-    case 8: CRS_LN2(PL, 8); break;                                                    \
-    case 16: CRS_LN2(PL, 16); break;                                                  \
-    default: return -1;                                                               \
-  }
-#define CRS_LNV2(P2, NS) hipLaunchKernelGGL((layernorm2_kernel<P2, NS>), dim3((tokens + 3) / 4), dim3(256), 0, stream, y, \
-                                          bias, residual, g, b, eps, tokens, hidden, x32, x16)
-#define CRS_LNV(P2)                                                                   \
-  switch (nsplit) {                                                                   \
-    case 1: CRS_LNV2(P2, 1); break;                                                   \
-    case 2: CRS_LNV2(P2, 2); break;                                                   \
-    case 3: CRS_LNV2(P2, 3); break;                                                   \
-    case 4: CRS_LNV2(P2, 4); break;                                                   \
-    case 6: CRS_LNV2(P2, 6); break;                                                   \
-    case 8: CRS_LNV2(P2, 8); break;                                                   \
-    case 16: CRS_LNV2(P2, 16); break;                                                 \
-    default: return -1;                                                               \
-  }
-  if (hidden == 384) { CRS_LNV(3); } else if (hidden == 768) { CRS_LNV(6); } else if (hidden <= 64) { CRS_LN(1); } else { CRS_LN(16); }
-#undef CRS_LNV
-#undef CRS_LNV2
+#define CRS_LN_CASE(KERNEL, PL, NS)                                                                                        \
+  case NS: hipLaunchKernelGGL((KERNEL<PL, NS>), dim3((tokens + 3) / 4), dim3(256), 0, stream, y, bias, residual, g, b, eps, tokens, \
+                              hidden, x32, x16); break;
+#define CRS_LN(KERNEL, PL) switch (nsplit) { CRS_LN_SLABS(CRS_LN_CASE, KERNEL, PL) default: return -1; }
+  // the form per hidden size (forms::row_form), every slab count of enc_forms.h
+  if (hidden == 384) { CRS_LN(layernorm2_kernel, 3) } else if (hidden == 768) { CRS_LN(layernorm2_kernel, 6) }
+  else if (hidden <= 64) { CRS_LN(layernorm_kernel, 1) } else { CRS_LN(layernorm_kernel, 16) }
 #undef CRS_LN
-#undef CRS_LN2
+#undef CRS_LN_CASE
   return (int)hipGetLastError();
 }
 

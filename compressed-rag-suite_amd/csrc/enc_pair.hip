@@ -15,7 +15,7 @@ namespace {
 // reduction leaves every lane with the full dot products; tanh, and the classifier's term w_c[j] * pooled[j] is added to the
 // wave's running sum of each pair.  The four waves' sums meet in LDS in a fixed order.  A pair's result does not depend on its
 // place in the group or on the batch it came in.
-constexpr int kPairGroup = 8;
+constexpr int kPairGroup = forms::kPairGroup;
 
 template <int VEC>
 __global__ __launch_bounds__(256) void pair_head_kernel(const float* __restrict__ hidden32, int batch, int seq, int hidden,

@@ -31,8 +31,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
-constexpr int kQaThreads = 512;
-constexpr int QM = 64;   // tokens per workgroup
+constexpr int kQaThreads = forms::kQaThreads;
+constexpr int QM = forms::kQaTokens;   // tokens per workgroup
 
 template <int HD>
 struct QaCfg {
@@ -204,11 +204,11 @@ __global__ __launch_bounds__(kQaThreads, 1) void qkv_attn_kernel(const _Float16*
 }
 
 template <int HD>
-int launch_qa(const _Float16* x16, const _Float16* w, const float* bias, const int* lens, _Float16* ctx, int T, int seq,
-              int H, int heads, hipStream_t stream) {
+int launch_qa(const AttnPlan& p, const _Float16* x16, const _Float16* w, const float* bias, const int* lens, _Float16* ctx, int T, int seq,
+              int H, hipStream_t stream) {
   using C = QaCfg<HD>;
-  const int lds = (QM + C::NC) * H * 2 + C::kQkvBytes + C::kPBytes;
-  if (lds > 160 * 1024) return -1;
+  static_assert(forms::qa_lds(384, HD) == (QM + C::NC) * 384 * 2 + C::kQkvBytes + C::kPBytes, "enc_forms.h states the LDS image of this kernel");
+  const int lds = p.d.lds;
   static int attr_lds = 0;
   auto kernel = &qkv_attn_kernel<HD>;
   if (lds > attr_lds) {
@@ -216,27 +216,17 @@ int launch_qa(const _Float16* x16, const _Float16* w, const float* bias, const i
     if (e != hipSuccess) return (int)e;
     attr_lds = lds;
   }
-  hipLaunchKernelGGL(kernel, dim3((T + QM - 1) / QM, heads), dim3(kQaThreads), lds, stream, x16, w, bias, lens, ctx, T, seq, H);
+  hipLaunchKernelGGL(kernel, dim3(p.d.gx, p.d.gy), dim3(kQaThreads), lds, stream, x16, w, bias, lens, ctx, T, seq, H);
   return (int)hipGetLastError();
 }
 
 }  // namespace
 
-bool qkv_attn_supported(int hidden, int heads, int seq) {
-  if (hidden > 384 || hidden % 128) return false;
-  const int hd = hidden / heads;
-  if (hd != 32 && hd != 64) return false;
-  const int lds = (QM + 3 * hd) * hidden * 2 + (hd == 32 ? QaCfg<32>::kQkvBytes + QaCfg<32>::kPBytes : QaCfg<64>::kQkvBytes + QaCfg<64>::kPBytes);
-  if (lds > 160 * 1024) return false;
-  return seq == 16 || seq == 32 || seq == 64;
-}
-
-int qkv_attn_launch(const _Float16* x16, const _Float16* w_qkv, const float* b_qkv, const int* lens, _Float16* ctx, int batch,
-                    int seq, int hidden, int heads, hipStream_t stream) {
-  if (!qkv_attn_supported(hidden, heads, seq)) return -1;
-  const int T = batch * seq;
-  if (hidden / heads == 32) return launch_qa<32>(x16, w_qkv, b_qkv, lens, ctx, T, seq, hidden, heads, stream);
-  return launch_qa<64>(x16, w_qkv, b_qkv, lens, ctx, T, seq, hidden, heads, stream);
+int qkv_attn_launch(const AttnPlan& p, const _Float16* x16, const _Float16* w_qkv, const float* b_qkv, const int* lens, _Float16* ctx,
+                    int tokens, int seq, int hidden, hipStream_t stream) {
+  if (p.form != AttnForm::Fused) return -1;
+  if (p.hd == 32) return launch_qa<32>(p, x16, w_qkv, b_qkv, lens, ctx, tokens, seq, hidden, stream);
+  return launch_qa<64>(p, x16, w_qkv, b_qkv, lens, ctx, tokens, seq, hidden, stream);
 }
 
 }  // namespace crs

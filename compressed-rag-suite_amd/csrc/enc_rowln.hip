@@ -19,7 +19,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
-constexpr int kRlThreads = 512;
+constexpr int kRlThreads = forms::kRowlnThreads;
 
 __device__ __forceinline__ float wave_sum_rl(float x) {
 #pragma unroll
@@ -42,7 +42,7 @@ __device__ __forceinline__ float wave_sum_rl(float x) {
 // comes from L2; neither deeper prefetch, nor 128-byte pieces, nor rotating the K walk per workgroup moved it by
 // more than a few per cent.
 constexpr int kStageInstrPerWave(int kc) { return (128 + 384) * (kc / 8) / 64 / 8; }   // 4 (KC 32) or 8 (KC 64)
-constexpr int kR2Rows = 128, kR2H = 384;
+constexpr int kR2Rows = forms::kRowlnRows, kR2H = forms::kRowlnHidden;
 constexpr int kR2StageRows = kR2Rows + kR2H;                  // 512
 template <int KC, int NST>
 struct R2 {
@@ -216,27 +216,23 @@ __global__ __launch_bounds__(kRlThreads, 1) void gemm_rowln2_kernel(const _Float
 
 }  // namespace
 
-bool gemm_rowln2_supported(int hidden, int k) { return hidden == kR2H && k % 64 == 0 && k >= 192; }
-
-int gemm_rowln2_launch(const _Float16* a, const _Float16* w, const float* bias, const float* residual, const float* g,
-                       const float* b, float eps, int m, int hidden, int k, float* x32, _Float16* x16, hipStream_t stream) {
-  if (!gemm_rowln2_supported(hidden, k)) return -1;
-  constexpr int lds = 128 * 1024;   // 4 x 32 KB or 2 x 64 KB (the 64 x 388 fp32 tile re-uses it)
-  static int variant = -1;
-  // default: 128-byte row pieces, two stages (3.79 ms per 65 536-token MiniLM forward against 3.86 ms for the
+int gemm_rowln2_launch(const ProjLnPlan& p, const _Float16* a, const _Float16* w, const float* bias, const float* residual,
+                       const float* g, const float* b, float eps, int m, int k, float* x32, _Float16* x16, hipStream_t stream) {
+  if (!p.rowln2) return -1;
+  constexpr int lds = forms::kRowlnLds;   // 4 x 32 KB or 2 x 64 KB (the 64 x 388 fp32 tile re-uses it)
+  // variant 1 (default): 128-byte row pieces, two stages (3.79 ms per 65 536-token MiniLM forward against 3.86 ms for the
   // four-stage ring of 64-byte pieces); CRS_ROWLN2_VARIANT=0 selects the latter
-  if (variant < 0) { const char* e = getenv("CRS_ROWLN2_VARIANT"); variant = (e && e[0] == '0') ? 0 : 1; }
   static bool done[2] = {false, false};
   auto k0 = &gemm_rowln2_kernel<32, 4>;
   auto k1 = &gemm_rowln2_kernel<64, 2>;
-  const void* fn = variant ? reinterpret_cast<const void*>(k1) : reinterpret_cast<const void*>(k0);
-  if (!done[variant]) {
+  const void* fn = p.variant ? reinterpret_cast<const void*>(k1) : reinterpret_cast<const void*>(k0);
+  if (!done[p.variant]) {
     hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return (int)e;
-    done[variant] = true;
+    done[p.variant] = true;
   }
-  if (variant) hipLaunchKernelGGL(k1, dim3((m + kR2Rows - 1) / kR2Rows), dim3(kRlThreads), lds, stream, a, w, bias, residual, g, b, eps, m, k, x32, x16);
-  else hipLaunchKernelGGL(k0, dim3((m + kR2Rows - 1) / kR2Rows), dim3(kRlThreads), lds, stream, a, w, bias, residual, g, b, eps, m, k, x32, x16);
+  if (p.variant) hipLaunchKernelGGL(k1, dim3(p.d.gx), dim3(kRlThreads), lds, stream, a, w, bias, residual, g, b, eps, m, k, x32, x16);
+  else hipLaunchKernelGGL(k0, dim3(p.d.gx), dim3(kRlThreads), lds, stream, a, w, bias, residual, g, b, eps, m, k, x32, x16);
   return (int)hipGetLastError();
 }
 

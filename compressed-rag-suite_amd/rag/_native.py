@@ -62,6 +62,7 @@ _SIGNATURES = {
     "crs_wordpiece_encode": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                      c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                      c_void_p, c_void_p]),
+    "crs_encoder_plan_describe": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t]),   # crs_encoder_desc by pointer
     "crs_rescore_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p,
                                 c_void_p, c_void_p]),
     "crs_score_rows_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
@@ -646,6 +647,20 @@ def scan_plan_describe(nq: int, dim: int, k: int, n_rows: int, slab_type: int = 
     buf = ctypes.create_string_buffer(256)
     check(load().crs_scan_plan_describe(nq, dim, k, n_rows, slab_type, buf, 256))
     return buf.value.decode()
+
+
+def encoder_plan_describe(desc, batch: int, seq: int, rel_bias: bool = False, pair: int = 0) -> str:
+    """One line per launch of embedding, one layer and the tail of a forward, in launch order (crs_encoder_plan_describe): kernel with
+    its template arguments, grid in workgroups, workgroup size, dynamic LDS bytes.  desc: the ctypes crs_encoder_desc (HipEncoder.desc);
+    pair: 0 pooling tail, 1 pair head with type ids, 2 pair head without."""
+    cap = 2048
+    while True:
+        buf = ctypes.create_string_buffer(cap)
+        need = load().crs_encoder_plan_describe(byref(desc), int(batch), int(seq), int(bool(rel_bias)), int(pair), buf, cap)
+        check(min(need, 0))
+        if need < cap:
+            return buf.value.decode()
+        cap = need + 1
 
 
 def time_cosine_topk(q16, slab, n_rows: int, dim: int, k: int, iters: int, *, slab_type: int = SLAB_F16,

@@ -138,6 +138,13 @@ int crs_encoder_score_pairs(const crs_encoder_desc* d, const crs_encoder_weights
                             float* scores_dev, float* pooled_out_dev /* may be NULL */, float* hidden_out_dev /* may be NULL */,
                             void* stream);
 
+/* Which kernels a forward of this shape launches on the current device: one line per launch of the embedding step, ONE layer and
+ * the tail, in launch order -- "<kernel><template arguments> grid=XxYxZ wg=Nx1x1 lds=BYTES\n", the grid in workgroups, the dynamic
+ * LDS in bytes.  rel_bias != 0: with a relative-position bias (crs_encoder_ext); pair: 0 the pooling tail, 1 crs_encoder_score_pairs
+ * with type ids, 2 without.  d->flags counts (CRS_ENC_SMALL_LDS).  Writes at most cap bytes, the terminating 0 included, and returns
+ * the length of the whole text (as snprintf does: >= cap means it was cut), or a negative error code.  It launches nothing. */
+int crs_encoder_plan_describe(const crs_encoder_desc* d, int batch, int seq, int rel_bias, int pair, char* buf, size_t cap);
+
 /* Building block exported for parity tests and for users with their own layer stack:
  *   C[M, N] = epilogue(A[M, K] (fp16) x W[N, K]^T (fp16) + bias[N])
  *   mode 0: fp16 out;  mode 1: erf-GELU, fp16 out;  mode 2: + residual fp32 [M, N], fp32 out. */

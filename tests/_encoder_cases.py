@@ -15,8 +15,10 @@ inequality (GPU to its numerics model, model to truth); it is not a tuning knob.
 the hidden state is <= COND_CAP = 3e-2 / 2, i.e. the bound is never looser than the 3e-2 of test_encoder_gpu.py;
 test_encoder_ref_cpu.py enforces that for every case below, without a GPU.
 
-The `why` of a case names the dispatch branch (csrc/enc_capi.hip, enc_attn.hip, enc_gemm.hip, enc_misc.hip) it is in the
-table for; profiles/enc_cases_kernels.txt holds the kernel names each case launched on an MI355X.
+The `why` of a case names the branch of the planner (csrc/enc_plan.cpp: make_enc_plan, plan_gemm) it is in the table for.
+tests/test_enc_plan_cpu.py checks, without a GPU, that the planner gives every case the kernels it launched on an MI355X
+(tests/golden/enc_plans.json.xz; profiles/enc_cases_kernels.txt is that list in words) and that every (step, kernel family) pair
+the planner can produce is reached by a case: a moved threshold that changes what a case exercises fails there.
 """
 from __future__ import annotations
 
@@ -109,6 +111,7 @@ H512_16 = _small(512, 16, 2048)
 H640 = _small(640, 10, 2560)
 H768_6144 = _small(768, 12, 6144)
 H1024, H1024_2 = _small(1024, 16, 4096), _small(1024, 16, 4096, layers=2)
+H1024_6144, H1024_256 = _small(1024, 16, 6144), _small(1024, 16, 256)
 MINI1_LONG = MINI1     # max_pos 512 allows seq 300 / 512
 
 SHAPE_CASES = [
@@ -120,7 +123,7 @@ SHAPE_CASES = [
     Case("h256x4-7x16r", H256_4, 7, 16, 206, "... and attention_short<64> at seq 16", "ragged1", query_batch=True),
     Case("h256x16-3x100", H256_16, 3, 100, 207, "attention_seq_kernel<16, 256, 4> (head_dim 16, seq > 64)", "ragged"),
     Case("h256x16-2x300", H256_16, 2, 300, 208, "blocked attention_kernel<16> over 5 key blocks (online rescale)", "ragged"),
-    Case("h320-5x32r", H320, 5, 32, 209, "gemm_panel_chunk(320) == 0: every GEMM on the tiled kernel, N = 960 / 320 not multiples of 128; ffn 1280 = 5 chunks refused", "ragged1", query_batch=True),
+    Case("h320-5x32r", H320, 5, 32, 209, "panel_chunk(320) == 0: every GEMM on the tiled kernel, N = 960 / 320 not multiples of 128; ffn 1280 = 5 chunks refused", "ragged1", query_batch=True),
     Case("h384f1088-5x32r", H384_1088, 5, 32, 210, "ffn 1088 = 64 mod 128: FFN-down on the tiled kernel, FFN-up panel with N = 17 x 64", "ragged1", query_batch=True),
     Case("h384f1088-29x160", H384_1088, 29, 160, 211, "gemm_rowln2 with K = 1088 (neither 384 nor 1536), 4640 tokens", "ragged"),
     Case("h384f2304-5x32r", H384_2304, 5, 32, 212, "ffn 2304 = 6 chunks -> 3 slabs: layernorm2<3, 3>", "ragged1", query_batch=True),
@@ -145,6 +148,10 @@ SHAPE_CASES = [
     Case("h512-9x256", H512, 9, 256, 239, "2304 tokens: gemm8_splitk 8 slabs (K = 2048) on the generic layernorm<16, 8>", "ragged"),
     Case("h512f3072-11x256", H512_3072, 11, 256, 240, "2816 tokens: gemm8_splitk 6 slabs (K = 3072) on layernorm<16, 6>", "ragged"),
     Case("h512f1152-5x32r", H512_1152, 5, 32, 241, "ffn 1152 = 3 chunks of 384: layernorm<16, 3>", "ragged1", query_batch=True),
+    # forms that tests/test_enc_plan_cpu.py found no case for, each at the fewest tokens the planner gives them (256 CUs)
+    Case("h1024f6144-11x256", H1024_6144, 11, 256, 242, "2816 tokens: persistent gemm8 for FFN-up (24 x 11 = 264 items > 256 CUs); QKV 12 x 11 = 132 tiles, one workgroup per item", "ragged"),
+    Case("h1024f256-22x256", H1024_256, 22, 256, 243, "5632 tokens: persistent gemm8 for QKV (12 x 22 = 264 items)", "ragged"),
+    Case("h1024f256-32x256", H1024_256, 32, 256, 244, "8192 tokens: out-projection and FFN-down (K = 256) on whole-K gemm8 mode 2 (4 x 32 = 128 tiles), layernorm<16, 1>", "ragged"),
 ]
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -368,7 +375,7 @@ def check_case_on_gpu(case: Case, cuda, small_lds: bool = False, report=None):
 
 
 def fused_qkv_attention_applies(case: Case) -> bool:
-    """qkv_attn_supported (csrc/enc_qkvattn.hip) and the token limit of enc_capi.hip, restated: the one kernel the
+    """qkv_attn_supported and the token limit of make_enc_plan (csrc/enc_plan.cpp), restated: the one kernel the
     CRS_ENC_SMALL_LDS flag replaces by kernels of another accumulation order."""
     h, hd = case.cfg.hidden, case.cfg.head_dim
     if h > 384 or h % 128 or hd not in (32, 64) or case.seq not in (16, 32, 64) or case.tokens > 4096:

@@ -24,7 +24,7 @@ def test_hard_case_small_lds(cuda, case):
     ec.check_small_lds_on_gpu(case, cuda)
 
 
-# (m, n, k) -> kernel of gemm_f16_launch: tiled 128 x 128; row-streaming (m, n >= 512, K = 128); phase-scheduled 256 x 256
+# (m, n, k) -> kernel plan_gemm (csrc/enc_plan.cpp) picks: tiled 128 x 128; row-streaming (m, n >= 512, K = 128); phase-scheduled 256 x 256
 # (whole tiles, >= 128 of them); 256-row tiles (K >= 512, n % 256 == 0, m not a multiple of 256)
 @pytest.mark.parametrize("m,n,k", [(200, 192, 64), (1024, 512, 128), (4096, 2048, 256), (4100, 2048, 512)])
 def test_gelu_epilogue_against_fp64_erf(cuda, m, n, k):

@@ -1,0 +1,57 @@
+// enc_plan_table.cpp -- the encoder's planner (csrc/enc_plan.cpp) as a stand-alone program: no HIP, no device.
+//   g++ -O1 -std=c++17 -o enc_plan_table tools/enc_plan_table.cpp compressed-rag-suite_amd/csrc/enc_plan.cpp
+//   ./enc_plan_table <CUs> < cases      one case per line:  fwd hidden heads ffn flags batch seq rel_bias pair  |  gemm m n k mode
+// The knobs come from the environment (CRS_GEMM8=0 ./enc_plan_table 256 ...), as in the library.  One line per case: key=value
+// fields separated by blanks, a tab, and the describe text with ';' for its line ends.  A GEMM step's fields are
+// family/slabs/tm/kc/kin/persist/items/ksplit/colblocks/streams.  tests/test_enc_plan_cpu.py drives it, built with
+// -fsanitize=address,undefined.
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "../compressed-rag-suite_amd/csrc/enc_plan.h"
+
+static const char* const kFamily[] = {"None", "Tiled", "Panel", "Stream", "StreamKS", "Big", "Gemm8", "Gemm8SplitK"};
+static const char* const kAttn[] = {"Fused", "Blocked", "Short", "Seq", "Seq32"};
+
+static void gemm_fields(const char* step, const crs::GemmPlan& g) {
+  printf("%s=%s/%d/%d/%d/%d/%d/%d/%d/%d/%d %s_lds=%d %s_wgs=%ld ", step, kFamily[(int)g.family], g.slabs, g.tm, g.kc, g.kin, (int)g.persist,
+         g.items, g.ksplit, g.colblocks, g.streams, step, g.d.lds, step, (long)g.d.gx * g.d.gy * g.d.gz);
+}
+
+static void text_out(char* text) {
+  for (char* c = text; *c; ++c)
+    if (*c == '\n') *c = ';';
+  printf("\t%s\n", text);
+}
+
+int main(int argc, char** argv) {
+  if (argc != 2 || atoi(argv[1]) <= 0) { fprintf(stderr, "usage: enc_plan_table <CUs> < cases\n"); return 2; }
+  const int cus = atoi(argv[1]);
+  const crs::EncKnobs kn = crs::enc_knobs_from_env();
+  char kind[8], text[2048];
+  while (scanf("%7s", kind) == 1) {
+    if (!strcmp(kind, "gemm")) {
+      int m, n, k, mode;
+      if (scanf("%d %d %d %d", &m, &n, &k, &mode) != 4) return 2;
+      const crs::GemmPlan g = crs::plan_gemm(m, n, k, mode, 0, cus, kn);
+      gemm_fields("gemm", g);
+      crs::gemm_plan_describe(g, text, sizeof text);
+      text_out(text);
+      continue;
+    }
+    int hidden, heads, ffn, flags, batch, seq, rel, pair;
+    if (strcmp(kind, "fwd") || scanf("%d %d %d %d %d %d %d %d", &hidden, &heads, &ffn, &flags, &batch, &seq, &rel, &pair) != 8) return 2;
+    const crs::EncPlan p = crs::make_enc_plan(hidden, heads, ffn, flags, batch, seq, rel, pair, cus, kn);
+    printf("total=%zu max_split=%d attn=%s attn_lds=%d ", p.total, p.max_split, kAttn[(int)p.attn.form], p.attn.d.lds);
+    gemm_fields("qkv", p.qkv);
+    gemm_fields("up", p.up);
+    printf("out_rowln2=%d down_rowln2=%d rowln2_variant=%d ", (int)p.out.rowln2, (int)p.down.rowln2, p.out.rowln2 ? p.out.variant : p.down.variant);
+    gemm_fields("out", p.out.gemm);
+    gemm_fields("down", p.down.gemm);
+    const int need = crs::enc_plan_describe(p, text, sizeof text);
+    if (need >= (int)sizeof text) return 3;
+    text_out(text);
+  }
+  return 0;
+}
