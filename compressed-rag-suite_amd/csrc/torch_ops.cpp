@@ -7,6 +7,8 @@
 //   crs::slab_write_rows / crs::slab_compact   in-place update and delete of rows (csrc/mutate.hip; the reference's ChromaDB
 //                          collection offers update / delete, its own code never calls them)
 //   crs::queries_to_f16    query side of the same conversion                  (reference rag/indexing.py:156-168)
+//   crs::rows_norm_max / slab_append_space / slab_write_rows_space / slab_rescale_space / queries_to_space / space_distances
+//                          hnsw:space 'ip' and 'l2' on the same scan (csrc/space.hip; ChromaDB's spaces, reference rag/indexing.py:83)
 //   crs::cosine_topk       replaces collection.query(query_embeddings, n)     (reference rag/indexing.py:171-176)
 //   crs::refine_f32        over-fetch re-rank against the fp32 shadow         
 //   crs::refine_f32_cert / crs::escalate_exact   the same with a per-query exactness proof, and the in-stream
@@ -151,6 +153,125 @@ void queries_to_f16(const Tensor& q32, Tensor out16, int64_t slab_type) {
   c10::hip::HIPGuardMasqueradingAsCUDA g(q32.device());
   ok(crs_queries_to_f16(q32.data_ptr<float>(), (int)q32.size(0), (int)q32.size(1), (int)slab_type, out16.data_ptr(), cur_stream(q32)),
      "crs::queries_to_f16");
+}
+
+// ---- inner-product / squared-L2 spaces (csrc/space.hip; include/crs_hip.h holds the contracts) ------------------------------------
+void want_scale(const Tensor& norm_scale) {
+  want(norm_scale, at::kFloat, "norm_scale");
+  TORCH_CHECK(norm_scale.numel() >= 1, "norm_scale must hold one fp32");
+}
+void want_space(int64_t space) { TORCH_CHECK(space == CRS_SPACE_IP || space == CRS_SPACE_L2, "space must be CRS_SPACE_IP or CRS_SPACE_L2"); }
+
+// the checks every space row writer shares: slab / scales / shadow shaped for `rows` rows of the transformed dimension
+int space_slab_checks(int dim, int64_t space, const Tensor& slab, const c10::optional<Tensor>& scales, const c10::optional<Tensor>& shadow,
+                      int64_t rows) {
+  want_space(space);
+  TORCH_CHECK(slab.dim() == 2 && slab.is_cuda() && slab.is_contiguous(), "slab [cap, pdim]");
+  const int st = slab_type_of(slab);
+  const int sdim = crs_space_row_dim(dim, (int)space);
+  TORCH_CHECK(sdim > 0 && sdim <= 1024, "dim out of range for this space");
+  TORCH_CHECK(slab.size(1) == crs_row_elems(sdim, st), "slab row length must be crs_row_elems(crs_space_row_dim(dim, space), slab_type)");
+  TORCH_CHECK(rows >= 0 && rows <= slab.size(0), "rows exceed the slab");
+  if (st == CRS_SLAB_I8) {
+    TORCH_CHECK(has(scales), "int8 slab needs scales");
+    want(*scales, at::kFloat, "scales");
+    TORCH_CHECK(scales->numel() >= rows, "scales too short");
+  }
+  if (has(shadow)) {
+    want(*shadow, at::kFloat, "shadow");
+    TORCH_CHECK(shadow->dim() == 2 && shadow->size(1) == sdim && shadow->size(0) >= rows, "shadow must be fp32 [>= rows, crs_space_row_dim]");
+  }
+  return st;
+}
+
+void rows_norm_max(const Tensor& emb, Tensor norm_max) {
+  want(emb, at::kFloat, "emb");
+  want(norm_max, at::kFloat, "norm_max");
+  same_device(emb, {&norm_max}, "crs::rows_norm_max");
+  TORCH_CHECK(emb.dim() == 2 && norm_max.numel() >= 1, "emb [n, dim], norm_max one fp32");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(emb.device());
+  ok(crs_rows_norm_max(emb.data_ptr<float>(), emb.size(0), (int)emb.size(1), norm_max.data_ptr<float>(), nullptr, cur_stream(emb)),
+     "crs::rows_norm_max");
+}
+
+void slab_append_space(const Tensor& emb, int64_t space, const Tensor& norm_scale, Tensor slab, c10::optional<Tensor> scales,
+                       c10::optional<Tensor> shadow, int64_t row0, c10::optional<Tensor> row_err) {
+  want(emb, at::kFloat, "emb");
+  want_scale(norm_scale);
+  same_device(emb, {&norm_scale, &slab, opt_t(scales), opt_t(shadow), opt_t(row_err)}, "crs::slab_append_space");
+  if (has(row_err)) { want(*row_err, at::kFloat, "row_err"); TORCH_CHECK(row_err->numel() >= 1, "row_err must hold one fp32"); }
+  TORCH_CHECK(emb.dim() == 2 && row0 >= 0, "emb [n, dim], row0 >= 0");
+  const int dim = (int)emb.size(1);
+  const int st = space_slab_checks(dim, space, slab, scales, shadow, row0 + emb.size(0));
+  c10::hip::HIPGuardMasqueradingAsCUDA g(emb.device());
+  ok(crs_slab_append_space_f32(emb.data_ptr<float>(), emb.size(0), dim, (int)space, st, norm_scale.data_ptr<float>(), slab.data_ptr(),
+                               (float*)opt_ptr(scales), (float*)opt_ptr(shadow), row0, (float*)opt_ptr(row_err), cur_stream(emb)),
+     "crs::slab_append_space");
+}
+
+void slab_write_rows_space(const Tensor& emb, const Tensor& rows, int64_t space, const Tensor& norm_scale, Tensor slab,
+                           c10::optional<Tensor> scales, c10::optional<Tensor> shadow, int64_t n_rows, c10::optional<Tensor> row_err) {
+  want(emb, at::kFloat, "emb");
+  want(rows, at::kLong, "rows");
+  want_scale(norm_scale);
+  same_device(emb, {&rows, &norm_scale, &slab, opt_t(scales), opt_t(shadow), opt_t(row_err)}, "crs::slab_write_rows_space");
+  if (has(row_err)) { want(*row_err, at::kFloat, "row_err"); TORCH_CHECK(row_err->numel() >= 1, "row_err must hold one fp32"); }
+  TORCH_CHECK(emb.dim() == 2 && rows.dim() == 1 && rows.size(0) == emb.size(0), "emb [m, dim], rows int64 [m]");
+  const int dim = (int)emb.size(1);
+  const int st = space_slab_checks(dim, space, slab, scales, shadow, n_rows);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(emb.device());
+  ok(crs_slab_write_rows_space_f32(emb.data_ptr<float>(), rows.data_ptr<int64_t>(), emb.size(0), dim, (int)space, st,
+                                   norm_scale.data_ptr<float>(), slab.data_ptr(), (float*)opt_ptr(scales), (float*)opt_ptr(shadow), n_rows,
+                                   (float*)opt_ptr(row_err), cur_stream(emb)), "crs::slab_write_rows_space");
+}
+
+void slab_rescale_space(int64_t n_rows, int64_t dim, int64_t space, int64_t shift, Tensor slab, c10::optional<Tensor> scales, Tensor shadow,
+                        c10::optional<Tensor> row_err) {
+  same_device(slab, {opt_t(scales), &shadow, opt_t(row_err)}, "crs::slab_rescale_space");
+  if (has(row_err)) { want(*row_err, at::kFloat, "row_err"); TORCH_CHECK(row_err->numel() >= 1, "row_err must hold one fp32"); }
+  TORCH_CHECK(dim > 0 && dim <= 1024, "bad dim");
+  const int st = space_slab_checks((int)dim, space, slab, scales, c10::optional<Tensor>(shadow), n_rows);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(slab.device());
+  ok(crs_slab_rescale_space(n_rows, (int)dim, (int)space, st, (int)shift, slab.data_ptr(), (float*)opt_ptr(scales), shadow.data_ptr<float>(),
+                            (float*)opt_ptr(row_err), cur_stream(slab)), "crs::slab_rescale_space");
+}
+
+void queries_to_space(const Tensor& q, int64_t space, int64_t slab_type, const Tensor& norm_scale, Tensor out32, Tensor out16) {
+  want(q, at::kFloat, "q");
+  want(out32, at::kFloat, "out32");
+  want(out16, at::kHalf, "out16");
+  want_scale(norm_scale);
+  want_space(space);
+  same_device(q, {&norm_scale, &out32, &out16}, "crs::queries_to_space");
+  TORCH_CHECK(q.dim() == 2 && out32.dim() == 2 && out16.dim() == 2, "q [nq, dim], out32 [nq, d'], out16 [nq, pdim]");
+  const int sdim = crs_space_row_dim((int)q.size(1), (int)space);
+  TORCH_CHECK(sdim > 0 && sdim <= 1024, "dim out of range for this space");
+  TORCH_CHECK(out32.size(0) == q.size(0) && out32.size(1) == sdim && out16.size(0) == q.size(0) &&
+                  out16.size(1) == crs_row_elems(sdim, (int)slab_type), "out32 must be [nq, d'], out16 [nq, crs_row_elems(d', slab_type)]");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(q.device());
+  ok(crs_queries_to_space(q.data_ptr<float>(), (int)q.size(0), (int)q.size(1), (int)space, (int)slab_type, norm_scale.data_ptr<float>(),
+                          out32.data_ptr<float>(), out16.data_ptr(), cur_stream(q)), "crs::queries_to_space");
+}
+
+void space_distances(const Tensor& q, int64_t space, const Tensor& shadow, int64_t n_rows, int64_t id_base, const Tensor& norm_scale,
+                     const Tensor& ids, Tensor out_dist, Tensor out_ids) {
+  want(q, at::kFloat, "q");
+  want(shadow, at::kFloat, "shadow");
+  want(ids, at::kLong, "ids");
+  want(out_dist, at::kFloat, "out_dist");
+  want(out_ids, at::kLong, "out_ids");
+  want_scale(norm_scale);
+  want_space(space);
+  same_device(q, {&shadow, &norm_scale, &ids, &out_dist, &out_ids}, "crs::space_distances");
+  TORCH_CHECK(q.dim() == 2 && shadow.dim() == 2 && ids.dim() == 2 && ids.size(0) == q.size(0), "q [nq, dim], shadow [rows, d'], ids [nq, k]");
+  TORCH_CHECK(shadow.size(1) == crs_space_row_dim((int)q.size(1), (int)space) && n_rows >= 0 && n_rows <= shadow.size(0),
+              "shadow must be fp32 [>= n_rows, crs_space_row_dim(dim, space)]");
+  TORCH_CHECK(out_dist.sizes() == ids.sizes() && out_ids.sizes() == ids.sizes(), "out_dist / out_ids must be [nq, k]");
+  if (ids.numel() == 0) return;
+  c10::hip::HIPGuardMasqueradingAsCUDA g(q.device());
+  ok(crs_space_distances(q.data_ptr<float>(), (int)q.size(0), (int)q.size(1), (int)space, shadow.data_ptr<float>(), n_rows, id_base,
+                         norm_scale.data_ptr<float>(), ids.data_ptr<int64_t>(), (int)ids.size(1), out_dist.data_ptr<float>(),
+                         out_ids.data_ptr<int64_t>(), cur_stream(q)), "crs::space_distances");
 }
 
 // ---- search --------------------------------------------------------------------------------------------------
@@ -758,6 +879,16 @@ TORCH_LIBRARY(crs, m) {
   m.def("slab_compact(Tensor dead, int n_rows, Tensor(a!) slab, Tensor(b!)? scales, Tensor(c!)? shadow, Tensor(d!)? rows_global, "
         "Tensor(e!) bounce, int first_row=0) -> ()");
   m.def("queries_to_f16(Tensor q32, Tensor(a!) out16, int slab_type) -> ()");
+  m.def("rows_norm_max(Tensor emb, Tensor(a!) norm_max) -> ()");
+  m.def("slab_append_space(Tensor emb, int space, Tensor norm_scale, Tensor(a!) slab, Tensor(b!)? scales, Tensor(c!)? shadow, int row0, "
+        "Tensor(d!)? row_err=None) -> ()");
+  m.def("slab_write_rows_space(Tensor emb, Tensor rows, int space, Tensor norm_scale, Tensor(a!) slab, Tensor(b!)? scales, Tensor(c!)? shadow, "
+        "int n_rows, Tensor(d!)? row_err=None) -> ()");
+  m.def("slab_rescale_space(int n_rows, int dim, int space, int shift, Tensor(a!) slab, Tensor(b!)? scales, Tensor(c!) shadow, "
+        "Tensor(d!)? row_err=None) -> ()");
+  m.def("queries_to_space(Tensor q, int space, int slab_type, Tensor norm_scale, Tensor(a!) out32, Tensor(b!) out16) -> ()");
+  m.def("space_distances(Tensor q, int space, Tensor shadow, int n_rows, int id_base, Tensor norm_scale, Tensor ids, Tensor(a!) out_dist, "
+        "Tensor(b!) out_ids) -> ()");
   m.def("cosine_topk(Tensor q16, Tensor slab, Tensor? scales, int n_rows, int dim, int k, int id_base) -> (Tensor, Tensor)");
   m.def("cosine_topk_out(Tensor q16, Tensor slab, Tensor? scales, int n_rows, int dim, int k, int id_base, Tensor(a!) workspace, "
         "Tensor(b!) out_scores, Tensor(c!) out_ids) -> ()");
@@ -807,6 +938,12 @@ TORCH_LIBRARY_IMPL(crs, CUDA, m) {   // the HIP backend of torch-ROCm dispatches
   m.impl("slab_write_rows", &slab_write_rows);
   m.impl("slab_compact", &slab_compact);
   m.impl("queries_to_f16", &queries_to_f16);
+  m.impl("rows_norm_max", &rows_norm_max);
+  m.impl("slab_append_space", &slab_append_space);
+  m.impl("slab_write_rows_space", &slab_write_rows_space);
+  m.impl("slab_rescale_space", &slab_rescale_space);
+  m.impl("queries_to_space", &queries_to_space);
+  m.impl("space_distances", &space_distances);
   m.impl("cosine_topk", &cosine_topk);
   m.impl("cosine_topk_out", &cosine_topk_out);
   m.impl("refine_f32", &refine_f32);

@@ -133,6 +133,9 @@ class RetrievalEngine:
         proxy_encode_shard (diagnostic, one rank): encode Qb / W queries and tile them in place of that all-gather.
         encode=False (diagnostic): the caller fills ``ctx.q_out`` / uses set_queries(); no encoder in the batch."""
         import torch
+        if getattr(view, "space", nat.SPACE_COSINE) != nat.SPACE_COSINE:
+            # the captured segments convert queries with queries_to_f16 and return scores (DESIGN 3.12, 7)
+            raise ValueError("RetrievalEngine serves cosine stores only: a store of space 'ip' / 'l2' is searched through VectorStore.search_batch")
         nat.require_gpu()
         self.torch = torch
         self.enc, self.view = encoder, view

@@ -28,6 +28,8 @@ EXACT_CAP = 1024           # default list length (12 KB of LDS per query in the 
 BM25_MAX_QUERIES = 64      # queries of one crs_bm25_topk launch
 WORDPIECE_TILE_BYTES = 1024   # CRS_WORDPIECE_TILE_BYTES: bytes of a text that crs_wordpiece_encode stages at a time
 BM25_MAX_PAIRS = 4096      # CRS_BM25_MAX_PAIRS: (query, known token) pairs of one crs_bm25_topk launch
+SPACE_COSINE, SPACE_IP, SPACE_L2 = 0, 1, 2     # CRS_SPACE_*: a collection's hnsw:space
+SPACES = {"cosine": SPACE_COSINE, "ip": SPACE_IP, "l2": SPACE_L2}
 
 # name -> (restype, argtypes); mirrors include/crs_hip.h one to one
 _SIGNATURES = {
@@ -44,6 +46,16 @@ _SIGNATURES = {
     "crs_slab_compact": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_size_t, c_void_p]),
     "crs_queries_to_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "crs_space_row_dim": (c_int, [c_int, c_int]),
+    "crs_rows_norm_max": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "crs_slab_append_space_f32": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                          c_void_p, c_void_p]),
+    "crs_slab_write_rows_space_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_int64, c_void_p, c_void_p]),
+    "crs_slab_rescale_space": (c_int, [c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "crs_queries_to_space": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "crs_space_distances": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int, c_void_p,
+                                    c_void_p, c_void_p]),
     "crs_scan_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int64, POINTER(c_size_t)]),
     "crs_cosine_topk": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int,
                                 c_int64, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
@@ -253,6 +265,86 @@ def queries_to_f16(q32, slab_type: int = SLAB_F16, out=None):
         with _translate():
             ops().queries_to_f16(q32, out, int(slab_type))
     return out
+
+
+# ---- hnsw:space 'ip' / 'l2' (csrc/space.hip; include/crs_hip.h holds the contracts, DESIGN 3.12 the transform)
+def space_row_dim(dim: int, space: int) -> int:
+    """d': the coordinates a stored row and a converted query have (dim, or dim + 1 for l2).  Host arithmetic, no library."""
+    return int(dim) + (1 if int(space) == SPACE_L2 else 0)
+
+
+def norm_scale_for(norm: float) -> float:
+    """The smallest power of two >= norm (1.0 for a zero norm): the store's R for a largest row norm."""
+    import math
+    if not norm > 0.0:
+        return 1.0
+    m, e = math.frexp(float(norm))                 # norm = m 2^e, 0.5 <= m < 1
+    return math.ldexp(1.0, e - 1 if m == 0.5 else e)
+
+
+def rows_norm_max(emb) -> float:
+    """The largest |x|_2 of emb (cuda fp32 [n, dim]) as a host float: one launch, one 4-byte readback; inf when a norm is not
+    finite."""
+    import torch
+    if emb.shape[0] == 0:
+        return 0.0
+    out = torch.zeros(1, dtype=torch.float32, device=emb.device)
+    with _translate():
+        ops().rows_norm_max(emb, out)
+    return float(out.item())
+
+
+def slab_append_space_f32(emb, space: int, norm_scale, slab, row0: int, scales=None, shadow=None, row_err=None) -> None:
+    """slab_append_f32 for a store of space ip / l2: emb cuda fp32 [n, dim] -> rows row0.. of slab [cap, padded d'], scales, shadow
+    [cap, d'] under the scale norm_scale (cuda fp32 [1], a power of two >= every norm of emb).  Rows are not normalised."""
+    if emb.shape[0] == 0:
+        return
+    with _translate():
+        ops().slab_append_space(emb, int(space), norm_scale, slab, scales, shadow, int(row0), row_err)
+
+
+def slab_write_rows_space_f32(emb, rows, space: int, norm_scale, slab, n_rows: int, scales=None, shadow=None, row_err=None) -> None:
+    """The scatter form of slab_append_space_f32 (same per-row device function, same bits)."""
+    if emb.shape[0] == 0:
+        return
+    with _translate():
+        ops().slab_write_rows_space(emb, rows, int(space), norm_scale, slab, scales, shadow, int(n_rows), row_err)
+
+
+def slab_rescale_space(n_rows: int, dim: int, space: int, shift: int, slab, shadow, scales=None, row_err=None) -> None:
+    """The scale grew by 2^shift: rows [0, n_rows) of shadow are multiplied by 2^-shift (l2's last coordinate by 2^-2 shift) and the
+    slab rows and int8 scales rebuilt from them, exactly.  dim is the caller's dimension.  One launch."""
+    if n_rows <= 0 or shift <= 0:
+        return
+    with _translate():
+        ops().slab_rescale_space(int(n_rows), int(dim), int(space), int(shift), slab, scales, shadow, row_err)
+
+
+def queries_to_space(q, space: int, slab_type: int, norm_scale, out32=None, out16=None):
+    """q cuda fp32 [nq, dim], any norm -> (unit fp32 [nq, d'], fp16 [nq, padded d']): the q32 / q16 of a certified search."""
+    import torch
+    nq, dim = q.shape
+    sdim = space_row_dim(dim, space)
+    if out32 is None:
+        out32 = torch.empty((nq, sdim), dtype=torch.float32, device=q.device)
+    if out16 is None:
+        out16 = torch.empty((nq, padded_dim(sdim, slab_type)), dtype=torch.float16, device=q.device)
+    if nq:
+        with _translate():
+            ops().queries_to_space(q, int(space), int(slab_type), norm_scale, out32, out16)
+    return out32, out16
+
+
+def space_distances(q, space: int, shadow, n_rows: int, id_base: int, norm_scale, ids):
+    """The distances of finished lists: q cuda fp32 [nq, dim] (the caller's queries), ids int64 [nq, k <= MAX_K_CERT] (rows +
+    id_base of the view whose shadow / n_rows are given) -> (distances fp32 [nq, k], ids [nq, k]) ordered (distance asc, id asc),
+    empty slots (+inf, -1) last.  ip: 1 - <q, x>; l2: sum (q - x)^2, computed from the recovered vectors."""
+    import torch
+    out_d = torch.empty(ids.shape, dtype=torch.float32, device=q.device)
+    out_i = torch.empty(ids.shape, dtype=torch.int64, device=q.device)
+    with _translate():
+        ops().space_distances(q, int(space), shadow, int(n_rows), int(id_base), norm_scale, ids.contiguous(), out_d, out_i)
+    return out_d, out_i
 
 
 def scan_workspace_bytes(nq: int, dim: int, k: int, n_rows: int) -> int:

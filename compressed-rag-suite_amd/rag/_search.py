@@ -26,6 +26,8 @@ class ShardView:
     id_base: int = 0             # added to local rows: the shard's first global row
     row_err_max: float = -1.0    # tracked |stored row - fp32 row|_2 maximum (< 0: the analytic worst case)
     row_map: object = None       # cuda int64 [n]: local row -> sidecar row (None: identity)
+    space: int = 0               # nat.SPACE_*: cosine, or rows stored for 'ip' / 'l2' (dim is then the STORED row's: d + 1 for l2)
+    norm_scale: object = None    # cuda fp32 [1]: the store's R (spaces 'ip' / 'l2')
 
     def sidecar_rows(self, rows):
         """Local rows of a result (-1: empty slot) -> sidecar rows."""
@@ -147,7 +149,16 @@ def search_view(view: ShardView, q32, top_k: int, overfetch: int, cap: int, esca
         return (torch.full((nq, top_k), float("-inf"), dtype=torch.float32, device=q32.device),
                 torch.full((nq, top_k), -1, dtype=torch.int64, device=q32.device), None)
     status = None
-    if view.shadow is not None and top_k <= nat.MAX_K_CERT:
+    if view.space != nat.SPACE_COSINE:
+        # the same certified search over the transformed rows, then the space's own distances, computed from the
+        # caller's queries and the recovered vectors and ordered (distance asc, row asc): the first array returned holds DISTANCES
+        if view.shadow is None or top_k > nat.MAX_K_CERT:
+            raise ValueError(f"a search in space 'ip' / 'l2' needs the fp32 shadow and top_k <= {nat.MAX_K_CERT}")
+        qt, q16 = nat.queries_to_space(q32, view.space, view.slab_type, view.norm_scale)
+        k_scan = nat.overfetch(nq, top_k, overfetch, view.n, view.slab_type) if top_k <= nat.MAX_K else top_k
+        _, i, status = search_certified(view, qt, q16, k_scan, top_k, cap, escalate)
+        s, i = nat.space_distances(q32, view.space, view.shadow, view.n, view.id_base, view.norm_scale, i)
+    elif view.shadow is not None and top_k <= nat.MAX_K_CERT:
         q16 = nat.queries_to_f16(q32, view.slab_type)
         qn = torch.nn.functional.normalize(q32, p=2, dim=1, eps=1e-12).contiguous()
         k_scan = nat.overfetch(nq, top_k, overfetch, view.n, view.slab_type) if top_k <= nat.MAX_K else top_k

@@ -186,6 +186,7 @@ class EmbeddingModel:
         self.device = self._get_device(config.get('device', 'cuda'))
         logger.info(f"Loading embedding model: {self.model_name}")
         self._pre_lower = False      # sentence_bert_config.json do_lower_case: an extra str.lower() before the tokenizer
+        self.has_normalize_module = None   # a sentence-transformers directory: whether its modules.json lists Normalize (else None)
         shape, weights, self.tokenizer = self._resolve(config)
         self._device_tokenizer = None
         if self.tokenize_mode == 'device':
@@ -219,7 +220,7 @@ class EmbeddingModel:
                      os.path.join(os.environ.get("CRS_MODEL_DIR", ""), os.path.basename(name)) if os.environ.get("CRS_MODEL_DIR") else None):
             if cand and os.path.isdir(cand) and os.path.exists(os.path.join(cand, "model.safetensors")):
                 logger.info(f"Loading local checkpoint {cand}")
-                shape, weights, tok, self._pre_lower, _has_norm = _load_local_dir(cand)
+                shape, weights, tok, self._pre_lower, self.has_normalize_module = _load_local_dir(cand)
                 return shape, weights, tok
         key = name.split(":", 1)[1] if name.startswith("synthetic:") else os.path.basename(name)
         key = _ALIASES.get(key.lower(), key.lower())

@@ -24,6 +24,23 @@ New, additive surface (all keys absent from the reference config.json default so
                               holds and escalating would cost a second sweep for most batches: int8 stays
                               EMPIRICAL (re-rank only) unless refine_exact=True.  ``last_exactness`` reports the counts
                               of the last search and its mode (top_k > 1024: re-rank without proof, counted unproven)
+  ``space``                   'cosine' (default) | 'ip' | 'l2': ChromaDB's hnsw:space, reported by ``collection.metadata``.  The scan is the
+                              cosine scan in all three: an 'ip' / 'l2' store does NOT normalise its rows, it stores them divided by one
+                              power of two R >= every row norm seen ('l2': by 2R, plus one coordinate |v|^2, so a 384-d collection
+                              scans 512-element rows), converts queries to match (crs::queries_to_space) and, once the certified list
+                              exists, computes ChromaDB's distance -- 1 - <q, x>, or sum (q - x)^2 -- in fp32 from the caller's own
+                              vectors and orders the list by (distance, row) (crs::space_distances).  Certificate, escalation and
+                              ``last_exactness`` mean what they mean for cosine; top_k up to 1024; dimensions up to 1023 ('l2').
+                              ('l2' over rows whose norms spread widely amplifies the slab's error by 4 R^2: on 1 M isotropic rows
+                              every query escalated at a log-normal sigma of 0.25 and came back UNPROVEN at 0.5 -- DESIGN 3.12.)  An
+                              add or update whose largest norm exceeds R doubles R as needed and rescales the stored rows exactly
+                              (crs::slab_rescale_space), so the store equals, bit for bit, one that was given all rows at once;
+                              ``rows_f32`` returns the caller's vectors.  Vectors with a non-finite norm raise ValueError before
+                              anything is written; coordinates whose value divided by 2R leaves the fp32 normal range (|x_i| below
+                              ~1e-38 R) are outside the bit-for-bit and exact-recovery guarantees.  Needs the fp32 shadow
+                              (refine_fp32: False raises) and ONE device (sharded / num_gpus / devices raise NotImplementedError:
+                              a shared R across ranks needs a collective); the throughput engine is not used (retrieve_batch embeds,
+                              then calls search_batch's search)
   ``num_gpus`` / ``devices``  ONE process driving N devices: contiguous row shards, per-device scans, partial lists
                               copied to the first device and merged there -- RAGPipeline stays one object
   ``sharded``                 SPMD (one process per GPU, torch.distributed): each rank keeps a row shard; ONE RCCL
@@ -84,20 +101,27 @@ _EMPTY = {'ids': [[]], 'documents': [[]], 'metadatas': [[]], 'distances': [[]]}
 class _Shard:
     """The rows one device holds: slab (+ scales, + fp32 shadow) and, per local row, the global sidecar row."""
 
-    def __init__(self, index_dtype: str, refine_fp32: bool, device):
+    def __init__(self, index_dtype: str, refine_fp32: bool, device, space: int = nat.SPACE_COSINE):
         import torch
         self.index_dtype, self.refine_fp32, self.device = index_dtype, refine_fp32, device
+        # hnsw:space 'ip' / 'l2' (module docstring, DESIGN 3.12): rows are stored scaled by R = norm_scale, the smallest power of two
+        # >= every row norm seen, NOT normalised; an l2 row carries one more coordinate.  The kernels read R from the device scalar,
+        # the host mirror decides when it grows (0.0: no row seen yet)
+        self.space = space
+        self.norm_scale = torch.zeros(1, dtype=torch.float32, device=device)
+        self.norm_scale_host = 0.0
+        self.sdim: Optional[int] = None  # coordinates of a stored row: dim, or dim + 1 (l2)
         # largest |stored row - fp32 row|_2 of this shard, raised by every crs::slab_append: the row term of the
         # exactness certificate (csrc/exact.hip).  Lives on the device; read back lazily (row_err_max()).
         self.row_err = torch.zeros(1, dtype=torch.float32, device=device)
         self._row_err_host = None
-        self.dim: Optional[int] = None
+        self.dim: Optional[int] = None   # the caller's dimension
         self.pdim: Optional[int] = None
         self.n = 0
         self.capacity = 0
         self.slab = None               # torch [capacity, pdim] fp16 | int8
         self.scales = None             # torch [capacity] fp32 (int8 only)
-        self.shadow = None             # torch [capacity, dim] fp32 (refine_fp32 only)
+        self.shadow = None             # torch [capacity, sdim] fp32 (refine_fp32 only)
         self.rows_global = None        # torch [capacity] int64: sidecar row of each local row
         self.identity = True           # rows_global[i] == i for every row (single shard, unsharded): no mapping needed
 
@@ -115,7 +139,10 @@ class _Shard:
     def reserve(self, rows: int, dim: int):
         import torch
         if self.dim is None:
-            self.dim, self.pdim = dim, nat.padded_dim(dim, self.slab_type)
+            sdim = nat.space_row_dim(dim, self.space)
+            if sdim > 1024:
+                raise ValueError(f"Embedding dimension {dim} is too large for space 'l2' (at most 1023: a row stores one more coordinate)")
+            self.dim, self.sdim, self.pdim = dim, sdim, nat.padded_dim(sdim, self.slab_type)
         elif dim != self.dim:
             raise ValueError(f"Embedding dimension {dim} doesn't match the index dimension {self.dim}")
         if rows <= self.capacity:
@@ -125,7 +152,7 @@ class _Shard:
         if self.slab_type == nat.SLAB_I8:
             self.scales = self._grow(self.scales, (cap,), torch.float32)
         if self.refine_fp32:
-            self.shadow = self._grow(self.shadow, (cap, self.dim), torch.float32)
+            self.shadow = self._grow(self.shadow, (cap, self.sdim), torch.float32)
         self.rows_global = self._grow(self.rows_global, (cap,), torch.int64)
         self.capacity = cap
 
@@ -137,13 +164,37 @@ class _Shard:
         if m == 0:
             return
         with torch.cuda.device(self.device):
-            nat.slab_append_f32(emb, self.slab, self.n, self.slab_type, scales=self.scales, shadow=self.shadow,
-                                row_err=self.row_err)
+            if self.space == nat.SPACE_COSINE:
+                nat.slab_append_f32(emb, self.slab, self.n, self.slab_type, scales=self.scales, shadow=self.shadow,
+                                    row_err=self.row_err)
+            else:                 # the caller (VectorStore._grow_scale) has made norm_scale cover this batch
+                nat.slab_append_space_f32(emb, self.space, self.norm_scale, self.slab, self.n, scales=self.scales, shadow=self.shadow,
+                                          row_err=self.row_err)
             self._row_err_host = None
             self.rows_global[self.n: self.n + m] = torch.arange(first_global_row, first_global_row + m, device=self.device)
         if first_global_row != self.n:
             self.identity = False
         self.n += m
+
+    def grow_scale(self, norm_max: float) -> bool:
+        """Make R cover a batch whose largest row norm is norm_max (finite): when R has to grow from R to R 2^j, every stored row is
+        rescaled by the exact power of two first (crs::slab_rescale_space: one launch), so that it equals the same vector stored
+        under the new R bit for bit.  True when stored rows were rescaled."""
+        import math
+        import torch
+        new = nat.norm_scale_for(norm_max)
+        if new <= self.norm_scale_host:
+            return False
+        rescaled = False
+        with torch.cuda.device(self.device):
+            if self.norm_scale_host > 0.0 and self.n:
+                shift = int(round(math.log2(new / self.norm_scale_host)))
+                nat.slab_rescale_space(self.n, self.dim, self.space, shift, self.slab, self.shadow, scales=self.scales, row_err=self.row_err)
+                self._row_err_host = None
+                rescaled = True
+            self.norm_scale.fill_(new)
+        self.norm_scale_host = new
+        return rescaled
 
     def row_err_max(self) -> float:
         """The tracked row error as a host float (one 4-byte D2H after an append, cached until the next one)."""
@@ -156,8 +207,8 @@ class _Shard:
 
     def view(self) -> _search.ShardView:
         """These rows as a search sees them (the tensors are shared, not copied)."""
-        return _search.ShardView(self.slab, self.scales, self.shadow, self.n, self.dim, self.slab_type, 0, self.row_err_max(),
-                                 None if (self.identity or not self.n) else self.rows_global[:self.n])
+        return _search.ShardView(self.slab, self.scales, self.shadow, self.n, self.sdim, self.slab_type, 0, self.row_err_max(),
+                                 None if (self.identity or not self.n) else self.rows_global[:self.n], self.space, self.norm_scale)
 
 
 def survivor_rows(n: int, dead) -> np.ndarray:
@@ -335,12 +386,13 @@ class SlabCollection:
     """What ``VectorStore.collection`` exposes (the retriever reads ``.metadata`` and the harness ``.count()``,
     reference rag/retrieval.py:48-50).  Owns the per-device shards and the host sidecars."""
 
-    def __init__(self, name: str, index_dtype: str, refine_fp32: bool, devices: Sequence):
+    def __init__(self, name: str, index_dtype: str, refine_fp32: bool, devices: Sequence, space: str = "cosine"):
         self.name = name
-        self.metadata = {"hnsw:space": "cosine"}
+        self.metadata = {"hnsw:space": space}
+        self.space = nat.SPACES[space]
         self.index_dtype = index_dtype
         self.refine_fp32 = refine_fp32
-        self.shards: List[_Shard] = [_Shard(index_dtype, refine_fp32, d) for d in devices]
+        self.shards: List[_Shard] = [_Shard(index_dtype, refine_fp32, d, self.space) for d in devices]
         self.ids: List[str] = []
         self.documents: List[str] = []
         self.metadatas: List[dict] = []
@@ -357,6 +409,10 @@ class SlabCollection:
     @property
     def dim(self):
         return self.shards[0].dim
+
+    @property
+    def sdim(self):
+        return self.shards[0].sdim
 
     @property
     def pdim(self):
@@ -530,6 +586,12 @@ class VectorStore:
             raise ValueError(f"index_dtype must be 'fp16' or 'int8', got {self.index_dtype!r}")
         refine = config.get('refine_fp32', 'auto')
         self.refine_fp32 = True if refine == 'auto' else bool(refine)
+        self.space = config.get('space', 'cosine')
+        if self.space not in nat.SPACES:
+            raise ValueError(f"space must be 'cosine', 'ip' or 'l2', got {self.space!r}")
+        if self.space != 'cosine' and not self.refine_fp32:
+            raise ValueError(f"space {self.space!r} needs the fp32 shadow (the distances and the caller's vectors are recovered from it): "
+                             "refine_fp32 must not be False")
         self.refine_overfetch = int(config.get('refine_overfetch', 24))
         exact = config.get('refine_exact', 'auto')
         if exact not in ('auto', True, False):
@@ -546,6 +608,12 @@ class VectorStore:
         self._device = config.get('device', None)
         self._devices_cfg = config.get('devices', None)
         self.num_gpus = int(config.get('num_gpus', 0) or 0)
+        if self.space != 'cosine':
+            # one scale R is shared by every row: across ranks or devices that needs a collective
+            for layout, on in (("sharded=True", self.sharded), ("num_gpus > 1", self.num_gpus > 1), ("devices", bool(self._devices_cfg))):
+                if on:
+                    raise NotImplementedError(f"space {self.space!r} is not supported with {layout}: the rows of such a store share one "
+                                              "norm scale, which a single-device store keeps")
         if self.sharded and (self.num_gpus > 1 or self._devices_cfg):
             raise ValueError("'sharded' (one process per GPU) and 'num_gpus'/'devices' (one process, N devices) are exclusive")
         if self.sharded and self.persist_directory:
@@ -585,7 +653,7 @@ class VectorStore:
         return dist if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 else None
 
     def _new_collection(self) -> SlabCollection:
-        return self._adopt(SlabCollection(self.collection_name, self.index_dtype, self.refine_fp32, self._torch_devices()))
+        return self._adopt(SlabCollection(self.collection_name, self.index_dtype, self.refine_fp32, self._torch_devices(), self.space))
 
     def _adopt(self, col: SlabCollection) -> SlabCollection:
         import weakref
@@ -594,10 +662,11 @@ class VectorStore:
 
     # -- persistence (the PersistentClient analogue, reference rag/indexing.py:32-34): APPEND-ONLY files, so that an add
     # costs O(batch), not O(index):
-    #     <name>.meta.json    header {format, n, dim, pdim, index_dtype, shadow, row_err_max}; rewritten (tmp + rename) LAST
+    #     <name>.meta.json    header {format, n, dim, pdim, index_dtype, shadow, row_err_max}; rewritten (tmp + rename) LAST;
+    #                         + {space, norm_scale} when the space is not cosine (a cosine store's header is unchanged)
     #     <name>.slab.bin     rows [n, pdim] fp16 | int8, raw little-endian, in sidecar order
     #     <name>.scales.bin   fp32 [n]            (int8)
-    #     <name>.shadow.bin   fp32 [n, dim]       (refine_fp32)
+    #     <name>.shadow.bin   fp32 [n, dim]       (refine_fp32; space l2: [n, dim + 1], the rows as stored)
     #     <name>.docs.jsonl   one {"id", "document", "metadata"} line per row
     # The header's n is the truth: bytes or lines past it (a crash between the appends and the header) are ignored and
     # overwritten by the next add; files SHORTER than the header says mean corruption and raise.  The round-2 format
@@ -628,7 +697,7 @@ class VectorStore:
             if hit and (int(hit.group(1)) if hit.group(1) else None) != (int(keep) if keep else None):
                 os.remove(os.path.join(self.persist_directory, name))
 
-    def _load_rows_into(self, col, n, dim, rows, refine, row_err):
+    def _load_rows_into(self, col, n, dim, rows, refine, row_err, norm_scale: float = 0.0):
         import torch
         for g, (lo, hi) in enumerate(_shard.batch_slices(n, len(col.shards))):
             sh = col.shards[g]
@@ -643,6 +712,9 @@ class VectorStore:
             sh.n = hi - lo
             sh.identity = (lo == 0)
             sh.row_err.fill_(row_err)
+            if col.space != nat.SPACE_COSINE:
+                sh.norm_scale.fill_(norm_scale)
+                sh.norm_scale_host = float(norm_scale)
 
     def _initialize_collection(self):
         """Re-open a persisted collection if there is one (reference: get_collection, :46-55)."""
@@ -672,6 +744,9 @@ class VectorStore:
                 self._gen = int(meta["gen"]) if meta.get("gen") else None
                 paths = self._persist_paths()
                 n, dim, pdim, dtype = int(meta["n"]), int(meta["dim"]), int(meta["pdim"]), str(meta["index_dtype"])
+                stored_space = str(meta.get("space", "cosine"))
+                if stored_space not in nat.SPACES:
+                    raise ValueError(f"unknown space {stored_space!r}")
                 elem = np.int8 if dtype == "int8" else np.float16
 
                 def raw(key, np_dtype, width):
@@ -682,7 +757,7 @@ class VectorStore:
 
                 rows = {"slab": raw("slab", elem, pdim),
                         "scales": raw("scales", np.float32, 1).reshape(-1) if dtype == "int8" else None,
-                        "shadow": raw("shadow", np.float32, dim) if meta.get("shadow") else None}
+                        "shadow": raw("shadow", np.float32, nat.space_row_dim(dim, nat.SPACES[stored_space])) if meta.get("shadow") else None}
                 row_err = meta.get("row_err_max")
                 ids, docs, metas = [], [], []
                 with open(paths["docs"], "rb") as fh:
@@ -698,15 +773,21 @@ class VectorStore:
         except Exception as e:
             # a truncated / foreign file must not silently become an empty store that the next add overwrites
             raise RuntimeError(f"persisted collection '{self.collection_name}' under {self.persist_directory} is unreadable: {e}") from e
+        stored_space = "cosine" if legacy else stored_space
+        if stored_space != self.space:
+            raise ValueError(f"persisted collection '{self.collection_name}' was built with space {stored_space!r}; "
+                             f"this store asks for {self.space!r}")
+        if self.space != 'cosine' and rows["shadow"] is None:
+            raise ValueError(f"persisted collection '{self.collection_name}' of space {self.space!r} has no fp32 shadow")
         self.index_dtype = dtype
         refine = self.refine_fp32 and rows["shadow"] is not None
         if self.refine_fp32 and not refine:
             logger.warning("persisted collection has no fp32 shadow; refine_fp32 disabled")
-        col = self._adopt(SlabCollection(self.collection_name, dtype, refine, self._torch_devices()))
+        col = self._adopt(SlabCollection(self.collection_name, dtype, refine, self._torch_devices(), self.space))
         # the certificate's row term: the persisted maximum, or the analytic worst case for files written before it existed
         if row_err is None:
             row_err = nat.exact_row_error_bound(dim, nat.SLAB_I8 if dtype == "int8" else nat.SLAB_F16)
-        self._load_rows_into(col, n, dim, rows, refine, float(row_err))
+        self._load_rows_into(col, n, dim, rows, refine, float(row_err), 0.0 if legacy else float(meta.get("norm_scale", 0.0)))
         col.ids, col.documents, col.metadatas = ids, docs, metas
         self.collection = col
         # appends continue the files only when they hold exactly what this store keeps (same shadow choice); else the next
@@ -762,7 +843,7 @@ class VectorStore:
         if col.slab_type == nat.SLAB_I8:
             write("scales", new_rows("scales"), 4)
         if col.refine_fp32:
-            write("shadow", new_rows("shadow"), dim * 4)
+            write("shadow", new_rows("shadow"), col.sdim * 4)
         elif not append and os.path.exists(paths["shadow"]):
             os.remove(paths["shadow"])
         # sidecar lines: keep the bytes the header vouches for (the first `lo` rows), replace the rest
@@ -779,6 +860,8 @@ class VectorStore:
             self._docs_bytes = docs_bytes
         meta = {"format": 2, "n": n, "dim": dim, "pdim": pdim, "index_dtype": col.index_dtype, "shadow": bool(col.refine_fp32),
                 "row_err_max": max(sh.row_err_max() for sh in col.shards), "docs_bytes": docs_bytes}
+        if col.space != nat.SPACE_COSINE:
+            meta["space"], meta["norm_scale"] = self.space, col.shards[0].norm_scale_host
         if new_gen:
             meta["gen"] = int(new_gen)
         tmp = paths["meta"] + ".tmp"
@@ -826,6 +909,10 @@ class VectorStore:
             logger.info(f"Adding {len(chunks)} chunks to index...")
             start = len(col.ids)
             dist = self._dist()
+            if col.space != nat.SPACE_COSINE:     # one device (__init__): the scale covers the batch before a row is written
+                if col.dim is not None and emb.shape[1] != col.dim:
+                    raise ValueError(f"Embedding dimension {emb.shape[1]} doesn't match the index dimension {col.dim}")
+                emb = self._grow_scale(col.shards[0], emb)
             if dist is not None:      # SPMD: this rank keeps rows [lo, hi) of the batch on its GPU
                 lo, hi = _shard.shard_slice(len(chunks), dist.get_world_size(), dist.get_rank())
                 col.shards[0].append(emb[lo:hi].to(col.shards[0].device).contiguous(), start + lo)
@@ -851,6 +938,24 @@ class VectorStore:
         if isinstance(embeddings, torch.Tensor):
             return embeddings.to(dtype=torch.float32)
         return torch.from_numpy(np.ascontiguousarray(embeddings, dtype=np.float32))
+
+    def _grow_scale(self, sh: _Shard, emb):
+        """emb: fp32 [m, dim] anywhere -> the same rows, contiguous on the shard's device, after the shard's norm scale has been
+        made to cover them: the batch's largest norm (crs::rows_norm_max: one launch, a 4-byte readback), ValueError before
+        anything is written when it is not finite, and a rescale of the stored rows when the scale grows (which drops the filter
+        cache, as an add does: the compacted sub-slabs hold rows under the old scale)."""
+        import torch
+        emb = emb.to(sh.device).contiguous()
+        if emb.shape[0] == 0:
+            return emb
+        with torch.cuda.device(sh.device):
+            top = nat.rows_norm_max(emb)
+        if not np.isfinite(top):
+            raise ValueError("an embedding has a non-finite norm; nothing was written")
+        if sh.grow_scale(top):
+            self._filters = {}
+            self._persisted_rows = None        # the files hold the rows under the old scale: the next persist rewrites them whole
+        return emb
 
     def _mutated(self, ids_changed: bool, sidecars_changed: bool = True, documents_changed: bool = True):
         """Everything derived from rows dies: filter sub-slabs (keyed by row COUNT only: an update, or a delete followed by an
@@ -979,7 +1084,11 @@ class VectorStore:
                     continue
                 with torch.cuda.device(sh.device):
                     sel, local = self._local_rows(sh, torch.from_numpy(rows).to(sh.device))
-                    if sel.numel():
+                    if sel.numel() and sh.space != nat.SPACE_COSINE:
+                        mine = self._grow_scale(sh, emb.to(sh.device)[sel])
+                        nat.slab_write_rows_space_f32(mine, local.contiguous(), sh.space, sh.norm_scale, sh.slab, sh.n, scales=sh.scales,
+                                                      shadow=sh.shadow, row_err=sh.row_err)
+                    elif sel.numel():
                         mine = emb.to(sh.device)[sel].contiguous()
                         nat.slab_write_rows_f32(mine, local.contiguous(), sh.slab, sh.n, scales=sh.scales, shadow=sh.shadow,
                                                 row_err=sh.row_err)
@@ -1128,7 +1237,8 @@ class VectorStore:
     def search(self, query_embedding, top_k: int = 5, where: Optional[dict] = None,
                where_document: Optional[dict] = None) -> Dict[str, Any]:
         """Nearest chunks for ONE query.  Returns {'ids','documents','metadatas','distances'} as
-        lists of one list each; distances are cosine distances (1 - cos), ascending."""
+        lists of one list each; distances are cosine distances (1 - cos), ascending (space 'ip': 1 - <q, x>, 'l2': the squared
+        Euclidean distance -- ChromaDB's, computed in fp32 from the caller's vectors; equal distances: lower row first)."""
         if self.collection is None:
             raise ValueError("No collection available. Create index first.")
         if self.collection.count() == 0:
@@ -1158,17 +1268,23 @@ class VectorStore:
         """This store as ONE device shard for rag._engine.RetrievalEngine, or None when its layout needs the general path
         (several devices, SPMD sharding, a non-identity row map)."""
         sh = self._sole_shard()
-        return None if (sh is None or self.sharded or sh.n == 0) else sh.view()
+        if sh is None or self.sharded or sh.n == 0 or sh.space != nat.SPACE_COSINE:   # the engine's graphs convert queries for cosine
+            return None
+        return sh.view()
 
     def rows_f32(self, rows):
         """The fp32 rows the store kept for these sidecar rows (numpy [len(rows), dim]; the normalised encoder output of the
-        chunks as indexed), or None when it keeps none / the layout is not a single identity shard."""
+        chunks as indexed), or None when it keeps none / the layout is not a single identity shard.  Space 'ip' / 'l2': the
+        caller's own vectors x, recovered exactly from the stored rows (x = R u, x = 2R v: a power of two)."""
         import torch
         sh = self._sole_shard(fp32=True)
         if sh is None:
             return None
         idx = torch.as_tensor(np.asarray(rows, dtype=np.int64), device=sh.device)
-        return sh.shadow[idx].cpu().numpy()
+        if sh.space == nat.SPACE_COSINE:
+            return sh.shadow[idx].cpu().numpy()
+        back = sh.norm_scale_host * (2.0 if sh.space == nat.SPACE_L2 else 1.0)
+        return (sh.shadow[idx, :sh.dim] * back).cpu().numpy()
 
     def mmr_order(self, rows, rel, counts, lam: float):
         """Greedy MMR order of many result lists at once, on the device (crs_mmr_order, csrc/mmr.hip): rows int64 / rel fp64
@@ -1178,7 +1294,7 @@ class VectorStore:
         conditions of rows_f32: no fp32 rows kept, or not a single identity shard) or a list is longer than MAX_K."""
         import torch
         sh = self._sole_shard(fp32=True)
-        if sh is None:
+        if sh is None or sh.space != nat.SPACE_COSINE:      # the kernel reads the shadow as unit rows of `dim` coordinates
             return None
         rows = np.ascontiguousarray(rows, dtype=np.int64)
         if rows.ndim != 2 or not 1 <= rows.shape[1] <= nat.MAX_K:
@@ -1407,7 +1523,8 @@ class VectorStore:
     def _search_rows(self, query_embeddings, top_k: int, where: Optional[dict] = None, where_document: Optional[dict] = None):
         """The search behind search_rows / search_batch: query_embeddings fp32 [nq, d] (numpy or tensor) -> (scores fp32
         [nq, k], sidecar rows int64 [nq, k], exactness tally) as numpy + dict, k = top_k clipped to the row count; k = 0 and no
-        tally when there is nothing to search (no rows, no queries, a filter nothing passes)."""
+        tally when there is nothing to search (no rows, no queries, a filter nothing passes).  Space 'ip' / 'l2': the first array
+        holds the DISTANCES (crs::space_distances), ascending, +inf in empty slots."""
         if self.collection is None:
             raise ValueError("No collection available. Create index first.")
         col = self.collection
@@ -1421,16 +1538,27 @@ class VectorStore:
         filt = self._filter_entry(where, where_document)
         if filt is not None and len(filt["rows"]) == 0:
             return nothing
+        if col.space != nat.SPACE_COSINE and min(top_k, col.count()) > nat.MAX_K_CERT:
+            raise ValueError(f"top_k {top_k} > {nat.MAX_K_CERT} is not supported in space {self.space!r}")
         scores, rows, tally = self._topk_device(q32, min(top_k, col.count()), filt)
         return scores.cpu().numpy(), rows.cpu().numpy(), tally
 
     def search_rows(self, query_embeddings, top_k: int):
         """search_batch without the sidecar lookup: (scores fp32 [nq, k], sidecar rows int64 [nq, k]) as numpy, best first,
-        -1 rows = fewer than k hits.  (retrieve_batch builds its dicts straight from these.)"""
+        -1 rows = fewer than k hits.  (retrieve_batch builds its dicts straight from these.)  Space 'ip' / 'l2': distances in
+        place of scores, see distances_of."""
         scores, rows, tally = self._search_rows(query_embeddings, top_k)
         if tally is not None:
             self.last_exactness = tally
         return scores, rows
+
+    def distances_of(self, scores) -> np.ndarray:
+        """The fp64 distances search / search_batch report for the first array of search_rows: 1 - score in fp32 (cosine); the
+        array itself in the spaces whose searches return distances ('ip': 1 - <q, x>, 'l2': sum (q - x)^2, ChromaDB's)."""
+        scores = np.asarray(scores, dtype=np.float32)
+        if self.space != 'cosine':
+            return scores.astype(np.float64)
+        return (np.float32(1.0) - scores).astype(np.float64)
 
     def search_batch(self, query_embeddings, top_k: int = 5, where: Optional[dict] = None,
                      where_document: Optional[dict] = None) -> Dict[str, Any]:
@@ -1442,7 +1570,7 @@ class VectorStore:
             return {k: [[] for _ in range(max(nq, 1))] for k in _EMPTY}
         self.last_exactness = tally
         col = self.collection
-        dist = (np.float32(1.0) - sh).astype(np.float64)          # one vectorised pass; float(np.float32) per hit was the cost
+        dist = self.distances_of(sh)                              # one vectorised pass; float(np.float32) per hit was the cost
         ids_l, docs_l, metas_l = col.ids, col.documents, col.metadatas
         out = {'ids': [], 'documents': [], 'metadatas': [], 'distances': []}
         for a in range(nq):

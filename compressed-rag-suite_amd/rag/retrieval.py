@@ -86,6 +86,10 @@ class ContextRetriever:
         self._engine, self._engine_key = None, None
         self.distance_metric = self._get_distance_metric()
         logger.info(f"Using distance metric: {self.distance_metric}")
+        if getattr(embedding_model, 'has_normalize_module', None) is False and getattr(vector_store, 'space', 'cosine') == 'cosine':
+            logger.warning("the embedding model's sentence-transformers pipeline has no Normalize module (it is trained for dot-product "
+                           "scoring, where the length of a vector carries relevance) but the vector store ranks by cosine: consider "
+                           "vector_store space 'ip' with embedding normalize False")
 
     @staticmethod
     def _parse_hybrid(value) -> Optional[dict]:
@@ -122,14 +126,14 @@ class ContextRetriever:
         return out
 
     def _get_distance_metric(self) -> str:
-        """The store's space ('cosine' unless the collection says otherwise or does not exist yet)."""
+        """The store's space: the collection's hnsw:space, or what the store is configured to create it with."""
         try:
             collection = self.vector_store.collection
             if collection:
                 return collection.metadata.get('hnsw:space', 'cosine')
         except Exception:
             pass
-        return 'cosine'
+        return getattr(self.vector_store, 'space', 'cosine')     # no collection yet: the space the store will create it with
 
     # ---- scoring ---------------------------------------------------------------------------------
     def _distance_to_similarity(self, distance: float) -> float:
@@ -146,6 +150,14 @@ class ContextRetriever:
             return max(0.0, min(1.0, (distance + 2.0) / 2.0))
         logger.warning(f"Unknown distance metric: {metric}, using default conversion")
         return max(0.0, 1.0 - (distance / 2.0))
+
+    def _store_distances(self, sc) -> np.ndarray:
+        """The fp64 distances of the first array of VectorStore.search_rows: 1 - score in fp32 for cosine; a store of space
+        'ip' / 'l2' returns its distances there and converts them itself (VectorStore.distances_of)."""
+        store = self.vector_store
+        if hasattr(store, 'distances_of'):
+            return store.distances_of(sc)
+        return (np.float32(1.0) - sc.astype(np.float32)).astype(np.float64)
 
     def _hits_to_chunks(self, ids, documents, metadatas, distances) -> List[Dict]:
         chunks = []
@@ -332,7 +344,7 @@ class ContextRetriever:
                 else:
                     valid = rows >= 0
                     rows, sc = rows[valid], sc[valid]
-                    dist = (np.float32(1.0) - sc.astype(np.float32)).astype(np.float64)  # the store's distances, as search() returns them
+                    dist = self._store_distances(sc)                                     # the store's distances, as search() returns them
                     h_ids, h_docs, h_metas = ids_l, docs_l, metas_l
                 if rows.size == 0:
                     logger.warning("No results found for query")
@@ -362,7 +374,10 @@ class ContextRetriever:
         self.last_rerank = {'mode': 'cross-encoder' if cross is not None else 'device' if on_device and not host_pieces else 'host',
                             'lists': len(per_query) if self.rerank else 0}
         self.last_mmr = {'mode': 'host', 'lists': sum(1 for chunks in per_query if len(chunks) > 1) if self.diversity_penalty > 0 else 0}
-        if self.diversity_penalty > 0 and self.mmr_vectors == 'device' and ids_l is not None and self._mmr_on_device(per_query, row_of):
+        # the MMR kernel reads the store's fp32 rows as they are stored: cosine only (as the lexical kernel above); in the other
+        # spaces 'device' falls back to 'index', whose rows_f32 returns the caller's vectors
+        if (self.diversity_penalty > 0 and self.mmr_vectors == 'device' and self.distance_metric == 'cosine' and ids_l is not None
+                and self._mmr_on_device(per_query, row_of)):
             return per_query
         from_index = self.mmr_vectors in ('auto', 'index', 'device') and ids_l is not None and hasattr(store, 'rows_f32')
         if self.diversity_penalty > 0 and from_index:
@@ -406,7 +421,7 @@ class ContextRetriever:
         for i, (sc, rows) in enumerate(piece):
             valid = rows >= 0
             rows, sc = rows[valid], sc[valid]
-            dist = (np.float32(1.0) - sc.astype(np.float32)).astype(np.float64)    # the store's distances, as search() returns them
+            dist = self._store_distances(sc)                                       # the store's distances, as search() returns them
             if self.distance_metric == 'cosine':                                      # _distance_to_similarity, vectorised (same fp64 ops)
                 d = np.minimum(np.maximum(dist, 0.0), 2.0)
                 score = np.minimum(np.maximum(1.0 - (d * d / 2.0), 0.0), 1.0)

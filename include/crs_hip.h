@@ -84,6 +84,53 @@ int64_t crs_slab_compact_window_rows(int dim, int slab_type, int has_shadow, siz
 /* Query side of the same conversion: fp32 [nq, dim] -> normalised fp16 [nq, crs_row_elems(dim, slab_type)]. */
 int crs_queries_to_f16(const float* q_dev, int nq, int dim, int slab_type, void* q16_dev, void* stream);
 
+/* ---- inner-product and squared-L2 spaces (additive to ABI 3; csrc/space.hip) -- ChromaDB's hnsw:space 'ip' / 'l2',
+ * which the reference's collection accepts (rag/indexing.py:83) --------------------------------------------------------------
+ * The scan computes <fp16 query row, slab row>.  A store of one of these spaces keeps ONE scale R = 2^e >= the largest row norm
+ * it has seen, as a device fp32 (`norm_scale_dev`, read by the kernels: growing it invalidates no captured graph), and stores
+ *     ip:  u = x * (1/R)                                   d' = dim        query q / max(|q|, 1e-12)
+ *     l2:  (v, t), v = x * (1/(2R)), t = fl(sum v_i^2)      d' = dim + 1    query (q / R, -1), normalised
+ * so that the scan's descending score is the space's ascending distance, every stored row has norm <= 1 and the certificate and the
+ * escalation of the cosine path hold as they are, over d' = crs_space_row_dim(dim, space) coordinates (slab rows:
+ * crs_row_elems(d', slab_type) elements, shadow rows: d' floats).  Rows are NOT normalised.  `dim` is always the caller's
+ * dimension: 1..1024 (ip), 1..1023 (l2).  Coordinates whose scaled value leaves the fp32 normal range are outside every "exact"
+ * below.  The cosine space has no entry here: it is the functions above.
+ *
+ * crs_rows_norm_max raises *norm_max_dev (fp32 the caller zeroed) to the largest |x|_2 of n rows; a norm that is not finite leaves
+ * +inf there and sets *flag_dev (int32, may be NULL) to 1.
+ * crs_slab_append_space_f32 / crs_slab_write_rows_space_f32 are crs_slab_append_f32 / crs_slab_write_rows_f32 for these spaces:
+ * the same arguments plus the scale, ONE per-row device function behind both (an updated row equals the same vector appended, bit
+ * for bit), row_err_max raised over all d' coordinates.  The caller has made *norm_scale_dev a power of two >= every norm of the
+ * batch before the call.
+ * crs_slab_rescale_space follows a growth of the scale from R to R 2^shift: every shadow row [0, n_rows) is multiplied by
+ * 2^-shift (t by 2^-2 shift), the slab row and int8 scale are rebuilt from it by that same per-row function, row_err_max is raised.
+ * All of it is exact, so a rescaled row equals the same vector stored under the new scale bit for bit.  One launch.
+ * crs_queries_to_space writes the unit fp32 queries q32 [nq, d'] and their scan block q16 [nq, crs_row_elems(d', slab_type)], zero
+ * padded: what crs_cosine_topk_cert and its kin take as q32 / q16.
+ * crs_space_distances turns a finished list into ChromaDB's distances: for ids [nq, k] (rows + id_base of the view the search ran
+ * over; its shadow, n_rows and id_base are passed as to the certificate) and the caller's own queries q [nq, dim] it recovers
+ * x = R u (ip) / 2R v (l2) exactly and computes 1 - <q, x> (ip) or sum (q_i - x_i)^2 (l2) in fp32, directly, not from the score;
+ * out_dist / out_ids [nq, k] leave ordered by (distance asc, id asc), ids < 0 or outside the view as (+inf, -1) at the tail.
+ * 1 <= k <= CRS_MAX_K_CERT; out_ids must not alias ids.  One workgroup per query, no workspace, no host synchronisation. */
+#define CRS_SPACE_COSINE 0
+#define CRS_SPACE_IP 1
+#define CRS_SPACE_L2 2
+int crs_space_row_dim(int dim, int space);      /* d' (0: bad arguments) */
+int crs_rows_norm_max(const float* emb_dev, int64_t n, int dim, float* norm_max_dev, int32_t* flag_dev, void* stream);
+int crs_slab_append_space_f32(const float* emb_dev, int64_t n, int dim, int space, int slab_type, const float* norm_scale_dev,
+                              void* slab_dev, float* scales_dev, float* shadow_f32_dev, int64_t row0, float* row_err_max_dev,
+                              void* stream);
+int crs_slab_write_rows_space_f32(const float* emb_dev, const int64_t* rows_dev, int64_t m, int dim, int space, int slab_type,
+                                  const float* norm_scale_dev, void* slab_dev, float* scales_dev, float* shadow_f32_dev, int64_t n_rows,
+                                  float* row_err_max_dev, void* stream);
+int crs_slab_rescale_space(int64_t n_rows, int dim, int space, int slab_type, int shift, void* slab_dev, float* scales_dev,
+                           float* shadow_f32_dev, float* row_err_max_dev, void* stream);
+int crs_queries_to_space(const float* q_dev, int nq, int dim, int space, int slab_type, const float* norm_scale_dev, float* q32_dev,
+                         void* q16_dev, void* stream);
+int crs_space_distances(const float* q_dev, int nq, int dim, int space, const float* shadow_f32_dev, int64_t n_rows, int64_t id_base,
+                        const float* norm_scale_dev, const int64_t* ids_dev, int k, float* out_dist_dev, int64_t* out_ids_dev,
+                        void* stream);
+
 /* ---- search: replaces collection.query(query_embeddings, n_results) -- rag/indexing.py:171-176
  * Exact cosine top-k of `nq` fp16 queries against `n_rows` slab rows on the current device.
  *   q16_dev   fp16 [nq, pdim]  (pdim = crs_row_elems(dim, slab_type)), unit rows, zero padded
