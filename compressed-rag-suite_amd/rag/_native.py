@@ -282,6 +282,15 @@ def norm_scale_for(norm: float) -> float:
     return math.ldexp(1.0, e - 1 if m == 0.5 else e)
 
 
+def covering_norm(norm_max: float, dim: int) -> float:
+    """An upper bound of the TRUE largest norm behind rows_norm_max's fp32 result.  That norm is ceil(dim/64) fmas and six
+    butterfly additions of non-negative terms and one square root: it can fall short of the true norm by the relative
+    ((ceil(dim/64) + 7) / 2 + 1) 2^-24, and round down onto a power of two.  Inflating it by (ceil(dim/64) + 8) 2^-24
+    -- more than that bound -- before it is mapped to R keeps every stored row's norm <= 1; a norm of exactly 2^e then gets
+    R = 2^(e + 1), which is correct and harmless."""
+    return float(norm_max) * (1.0 + (-(-int(dim) // 64) + 8) * 2.0 ** -24)
+
+
 def rows_norm_max(emb) -> float:
     """The largest |x|_2 of emb (cuda fp32 [n, dim]) as a host float: one launch, one 4-byte readback; inf when a norm is not
     finite."""

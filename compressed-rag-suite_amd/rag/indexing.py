@@ -786,7 +786,9 @@ class VectorStore:
         col = self._adopt(SlabCollection(self.collection_name, dtype, refine, self._torch_devices(), self.space))
         # the certificate's row term: the persisted maximum, or the analytic worst case for files written before it existed
         if row_err is None:
-            row_err = nat.exact_row_error_bound(dim, nat.SLAB_I8 if dtype == "int8" else nat.SLAB_F16)
+            # (over the STORED row's coordinates: an l2 row has one more than the caller's dimension)
+            row_err = nat.exact_row_error_bound(nat.space_row_dim(dim, nat.SPACES[self.space]),
+                                                nat.SLAB_I8 if dtype == "int8" else nat.SLAB_F16)
         self._load_rows_into(col, n, dim, rows, refine, float(row_err), 0.0 if legacy else float(meta.get("norm_scale", 0.0)))
         col.ids, col.documents, col.metadatas = ids, docs, metas
         self.collection = col
@@ -952,7 +954,8 @@ class VectorStore:
             top = nat.rows_norm_max(emb)
         if not np.isfinite(top):
             raise ValueError("an embedding has a non-finite norm; nothing was written")
-        if sh.grow_scale(top):
+        # R must cover the TRUE norms: the fp32 norm can fall short of them and round down onto a power of two (nat.covering_norm)
+        if sh.grow_scale(nat.covering_norm(top, emb.shape[1])):
             self._filters = {}
             self._persisted_rows = None        # the files hold the rows under the old scale: the next persist rewrites them whole
         return emb

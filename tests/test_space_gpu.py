@@ -336,6 +336,124 @@ def test_kernels_against_numpy(cuda):
             assert torch.equal(q16[:, :sdim], q32.half()) and not q16[:, sdim:].any()
 
 
+LARGE_N = 1100
+LARGE_KS = (65, 128, 1000, 1024)
+
+
+@functools.lru_cache(maxsize=None)
+def _large_case(d, space):
+    """1100 rows and 70 queries whose fp64 gaps at k = 65, 128, 1000, 1024 exceed twice the swap bound (at 4133 rows and d = 384
+    no such queries exist: keep n = 1100)."""
+    x = sr.make_rows(LARGE_N, d, seed=7 + d)
+    q = sr.pick_queries(x, space, 2.0, 70, LARGE_KS, seed=11 + d)
+    metric, tol = sr.metric64(q, x, space), sr.swap_tol(q, d, space, 2.0)
+    for a in (x, q, metric, tol):
+        a.setflags(write=False)
+    return x, q, metric, tol
+
+
+@pytest.mark.parametrize("d", [100, 384])
+@pytest.mark.parametrize("space", sr.SPACES)
+def test_top_k_65_to_1024(cuda, space, d):
+    """The partitioned over-fetch and its certificate (csrc/large_k.hip) under ip / l2, and crs_space_distances' LDS ranking at
+    k up to 1024, through the store."""
+    x, q, metric, tol = _large_case(d, space)
+    assert sr.norm_scale_for(sr.row_norm_max(x)) == 2.0
+    assert (sr.kth_gaps(metric, LARGE_KS) > tol[:, None]).all()      # the tolerance is not what makes the test pass
+    store = _store(space, "fp16")
+    store.create_index(_chunks(LARGE_N), x.copy())
+    assert store.collection.shards[0].norm_scale_host == 2.0
+    for nq in NQS:
+        for k in LARGE_KS:
+            res = store.search_batch(q[:nq].copy(), top_k=k)
+            tag = (space, d, nq, k)
+            _check_lists(res, q[:nq], x, space, k, metric[:nq], tol[:nq], tag)
+            ex = store.last_exactness
+            # the escalation list holds more rows than the store has: nothing can stay unproven here
+            assert ex["mode"] == "certificate" and ex["queries"] == nq and ex["unproven"] == 0, (tag, ex)
+            assert ex["certified"] + ex["escalated"] == nq, (tag, ex)
+
+
+@pytest.mark.parametrize("dtype", ["fp16", "int8"])
+@pytest.mark.parametrize("space", sr.SPACES)
+def test_top_k_above_the_row_count(cuda, space, dtype):
+    d, n = 100, 60
+    x = sr.make_rows(n, d, seed=23)
+    q = sr.pick_queries(x, space, 2.0, 5, (10,), seed=29)
+    metric, tol = sr.metric64(q, x, space), sr.swap_tol(q, d, space, 2.0)
+    store = _store(space, dtype)
+    store.create_index(_chunks(n), x)
+    for k in (61, 100, 1024):
+        res = store.search_batch(q, top_k=k)
+        # all 60 rows, each once, in metric order (up to the near-tie bound) with ascending distances: no -1, no inf
+        _check_lists(res, q, x, space, n, metric, tol, (space, dtype, k))
+        for r in range(len(q)):
+            assert sorted(_rows_of(res)[r]) == list(range(n)) and np.isfinite(res["distances"][r]).all(), (space, dtype, k, r)
+
+
+@pytest.mark.parametrize("dtype", ["fp16", "int8"])
+@pytest.mark.parametrize("space,d", [("l2", 1), ("l2", 127), ("l2", 1023), ("ip", 1), ("ip", 1024)])
+def test_edge_dimensions(cuda, space, d, dtype):
+    n, k = 300, 10
+    x = sr.make_rows(n, d, seed=7 + d)
+    q = sr.pick_queries(x, space, 2.0, 5, (k,), seed=11 + d)
+    metric, tol = sr.metric64(q, x, space), sr.swap_tol(q, d, space, 2.0)
+    assert (sr.kth_gaps(metric, (k,)) > tol[:, None]).all()
+    store = _store(space, dtype)
+    store.create_index(_chunks(n), x)
+    col = store.collection
+    assert col.shards[0].norm_scale_host == 2.0 and col.dim == d and col.sdim == d + (space == "l2")
+    _check_lists(store.search_batch(q, top_k=k), q, x, space, k, metric, tol, (space, d, dtype))
+
+
+def test_l2_refuses_1024_dimensions(cuda):
+    x = sr.make_rows(8, 1024, seed=3)
+    for how in ("create_index", "upsert"):           # the dimension arrives with the first rows, whichever call brings them
+        store = _store("l2", "fp16")
+        with pytest.raises(ValueError, match="too large for space 'l2'"):
+            getattr(store, how)(_chunks(8), x)
+        assert store.collection is None or store.collection.count() == 0
+    ok = _store("ip", "fp16")
+    ok.create_index(_chunks(8), x)
+    assert ok.collection.count() == 8
+
+
+@pytest.mark.parametrize("space", sr.SPACES)
+def test_rows_at_a_power_of_two_norm(cuda, space):
+    """R must cover the TRUE norm of every row (every stored row has norm <= 1, the premise of the certificate's
+    bound).  The first planted row has its mass in lane 0 of the norm kernel, whose fp32 chain returns exactly 2.0 for a true
+    norm of 2 (1 + 3.7e-8): a scale chosen from the fp32 norm alone is R = 2 and stores a row of norm 1 + 3.7e-8."""
+    import _space_build_ref as br
+    d = 384
+    lane0 = br.lane0_power_of_two_row(d)
+    axis = np.zeros(d, np.float32)
+    axis[5] = 2.0
+    rng = np.random.default_rng(13)
+    rnd = rng.standard_normal((50, d))
+    rnd = (rnd * (rng.uniform(0.2, 0.99, size=(50, 1)) / np.sqrt((rnd * rnd).sum(axis=1, keepdims=True)))).astype(np.float32)
+    x = np.concatenate([rnd, lane0[None, :], axis[None, :]])
+    norms = np.sqrt((x.astype(np.float64) ** 2).sum(axis=1))
+    assert norms[:50].max() < 1.0 and norms[50] > 2.0 and norms[51] == 2.0
+    store = _store(space, "fp16")
+    store.create_index(_chunks(50), rnd)                         # R = 1
+    store.create_index(_chunks(2, first=50), x[50:])             # the planted rows arrive: a rescale
+    sh = store.collection.shards[0]
+    R = sh.norm_scale_host
+    assert R == float(sh.norm_scale.item())
+    rows = sh.shadow[: sh.n].cpu().numpy().astype(np.float64)
+    assert rows.shape == (52, d + (space == "l2"))
+    if space == "ip":
+        worst = np.sqrt((rows * rows).sum(axis=1)).max()
+        assert worst <= 1.0, f"|u| - 1 = {worst - 1.0:.3e}"
+    else:
+        v = np.sqrt((rows[:, :d] ** 2).sum(axis=1)).max()
+        assert v <= 0.5, f"|v| - 1/2 = {v - 0.5:.3e}"
+        assert (rows * rows).sum(axis=1).max() <= 0.25 + 1.0 / 16
+    assert R >= norms.max(), (R, norms.max())                    # R covers the fp64 norm of every row ever given
+    assert np.array_equal(store.rows_f32(np.arange(52)).view(np.uint32), x.view(np.uint32))
+    assert R == 4.0                                              # a norm of exactly 2^e gets R = 2^(e + 1): correct and harmless
+
+
 def test_retriever_on_an_ip_store(cuda):
     from rag import RAGPipeline
     from rag.chunking import Chunk
