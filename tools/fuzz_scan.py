@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Randomised parity sweep of crs_cosine_topk against the oracle over (rows, dim, queries, k, slab type): exercises
 every kernel family make_plan can pick (dump / chain / wide / wide_ks / 8-wave / int8 / threshold), ragged tiles,
-several query blocks, planted duplicates.   python tools/fuzz_scan.py [cases] [seed]"""
+several query blocks, planted duplicates.   python tools/fuzz_scan.py [cases] [seed]
+A tool for random shapes, not the suite's coverage of the kernels: its k and row counts cannot select most chain lengths.
+tests/test_scan_forms_gpu.py runs every instantiation the planner can pick once, from the table in tests/_scan_form_cases.py."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "compressed-rag-suite_amd")); sys.path.insert(0, os.path.join(ROOT, "tests"))
