@@ -148,6 +148,7 @@ static int run_scan(const Plan& p, const void* q16, const void* slab, const floa
   a.dyn_mask = p.dyn_mask;
   a.nt = p.nt;
   a.no_stagger = p.no_stagger;
+  a.no_defer = p.no_defer;
   if (p.ticket) {
     const int ze = crs::scan_ticket_zero(a.ticket, st);
     if (ze) return ze;

@@ -97,6 +97,7 @@ int finish_plan(Plan* p, int64_t n_rows, const Knobs& kn) {
   p->boot = (kn.scan_boot && rounds < 24) ? 1 : 0;
   p->sched = kn.scan_sched;
   p->no_stagger = (wide && !kn.wide_stagger) ? 1 : 0;
+  p->no_defer = (wide && !kn.wide_defer) ? 1 : 0;
   p->mfma = !wide ? 0 : !wide_has_16(p->pdim, p->waves, p->slots) ? 32 : kn.wide_mfma ? kn.wide_mfma : wide_default_mfma(p->pdim, p->slots);
   return CRS_OK;
 }
@@ -113,6 +114,7 @@ Knobs knobs_from_env() {
   kn.scan_nt = env_digit("CRS_SCAN_NT", 1, -1);
   kn.fused_tail = env_on("CRS_FUSED_TAIL");
   kn.wide_stagger = env_on("CRS_WIDE_STAGGER");
+  kn.wide_defer = env_on("CRS_WIDE_DEFER");
   const char* me = getenv("CRS_WIDE_MFMA");
   kn.wide_mfma = !me ? 0 : (me[0] == '1' && me[1] == '6' && !me[2]) ? 16 : (me[0] == '3' && me[1] == '2' && !me[2]) ? 32 : 0;
   return kn;

@@ -28,6 +28,7 @@ struct Knobs {
   int scan_nt = -1;         // CRS_SCAN_NT            per call  0 / 1: non-temporal slab stream off / on; -1: by slab size
   bool fused_tail = true;   // CRS_FUSED_TAIL         per call  0: crs_cosine_topk_cert always takes the three-kernel chain
   bool wide_stagger = true; // CRS_WIDE_STAGGER       per call  0: waves 4..7 of the wide split forms select in step with 0..3
+  bool wide_defer = true;   // CRS_WIDE_DEFER         per call  0: the wide split forms insert every tile at once (no pending slot)
   int wide_mfma = 0;        // CRS_WIDE_MFMA          per call  16 / 32: MFMA shape where a wide form has both; 0: the measured one
 };
 Knobs knobs_from_env();
@@ -51,6 +52,7 @@ struct Plan {
   int t_dyn, dyn_mask;
   int boot, sched;   // ScanArgs::boot / sched (scan.hip)
   int no_stagger;    // Wide: ScanArgs::no_stagger
+  int no_defer;      // Wide: ScanArgs::no_defer
   int mfma;          // Wide: 16 or 32, the MFMA shape launched; else 0
   size_t part_elems; // nwg * nq * kp
   // every family but Classic leaves tile representatives: merge, then scan_refine.hip re-opens the winning tiles

@@ -29,6 +29,7 @@ struct ScanArgs {
   int dyn_mask;           //   a ticket stands for dyn_mask + 1 consecutive tiles (a power of two)
   int nt;                 // scan_tb.hip / scan_i8.hip: 1 = slab tiles streamed with the non-temporal policy (lds_dma16_nt)
   int no_stagger;         // scan_wide.hip, 24- / 32-slot forms: 1 = CRS_WIDE_STAGGER=0 (read by nothing else)
+  int no_defer;           // scan_wide.hip, the forms of wide_defer<>: 1 = CRS_WIDE_DEFER=0, the chain runs on every tile (read by nothing else)
 };
 
 // the exactness workspace of a batch (capi.hip carves it): per-query escalation threshold and row counter, the escalation

@@ -47,6 +47,22 @@
 // list as they were among its two parity lists.  VALU per tile is what it was (K/2 x 5 every tile against K x 5 every second tile,
 // + 6 for the exchange); the list's registers halve, which is what lets <384, 8, 24> keep the deferred accumulators of the stagger
 // (wide_stagger<>).
+//
+// Deferred insertion (the split forms of wide_defer<>).  The chain above runs for every lane on every tile, yet tile i of a stream
+// enters a K-slot list with probability about K / i.  So each lane keeps ONE pending tile (pend_s, pend_r) and a bound thr: the
+// upper half's last slot -- the pair's K-th score -- as it stood after the last chain run, in both lanes of the pair (-inf until the
+// list is full, so the first K tiles of a stream run the chain every tile as before).  Per tile: x is a candidate where x > thr
+// (strict).  If any lane of the WAVE has a candidate and a taken slot (one ballot, a scalar branch), the whole wave first runs the
+// chain on its pending entries ("flush"; an empty slot inserts (-inf, -1), which beats nothing), refreshes thr by one more swap and
+// re-tests; the candidates are then stashed.  One flush after the last tile (for waves 4 .. 7: after the deferred last tile).
+// The lists stay bit for bit what the chain on every tile leaves.  (1) A tile that is not stashed has x <= thr, and thr <= every
+// slot of the pair's list now and later, because the K-th score only rises: insert_shift moves nothing for such an x (its compares
+// are the same strict >), nor for a NaN, which is never a candidate either.  (2) A lane's stashed tiles reach the chain in the order
+// of their tiles, each before any later tile of that lane is stashed, and insert_shift's result for an entry depends only on the
+// list it meets -- which by (1) is the list the undeferred code would hold at that tile, skipped tiles being no-ops there.  So the
+// sequence of insertions that change the list, and with it the order of equal scores, is the undeferred one.  A wave-wide skip
+// alone does not pay (32 lists per wave: on 610-tile streams 9 tiles in 10 have a candidate somewhere); with the slot the chain runs
+// on about half the tiles.  CRS_WIDE_DEFER=0 (ScanArgs::no_defer) runs the chain on every tile: A/B runs, and the tests' reference.
 
 //
 // 16x16x32 form (scan_wide16_kernel; the split-list forms of the 8-wave kernel on 256- / 384-element rows).  The same launch on
@@ -100,6 +116,19 @@ template <int D, int NW, int K>
 constexpr bool wide_stagger() {
   if (D == 384 && NW == 8 && K == 24) return true;
   return NW == 8 && D <= 384 && !(D == 384 && K >= 16) && !(D == 256 && K >= 32);
+}
+// The split forms whose chain is deferred behind a pending slot per lane (header: "Deferred insertion"): the ones measured faster
+// with it by the rule of DESIGN.md section 7 item 6; every other form is compiled with the chain on every tile, as it was measured.
+// -DCRS_WIDE_DEFER_ALL=1 compiles the deferral into every split form (A/B builds of tools/scan_wide_probe and tools/wide_defer_ab).
+#ifndef CRS_WIDE_DEFER_ALL
+#define CRS_WIDE_DEFER_ALL 0
+#endif
+// The 32x32x16 form of <384, 8, 24> sits at 256 registers: the three of the pending slot spill (8 bytes per lane), so it never defers.
+template <int D, int NW, int K, bool S16>
+constexpr bool wide_defer() {
+  if (!wide_split<K>() || (!S16 && D == 384 && NW == 8 && K == 24)) return false;
+  if (CRS_WIDE_DEFER_ALL) return true;
+  return S16 && D == 384 && NW == 8 && K == 24;
 }
 
 template <int D, int NW>
@@ -311,6 +340,48 @@ __device__ __forceinline__ void scan_wide_body(const ScanArgs a) {
       vr = c ? r_old : vr;
     }
   };
+  // split forms: one tile's (x, xr) into the pair's list (header: "Split list").  The lower half's last slot as it stands crosses
+  // to the upper half: the low-half / even-row value of v_permlane32_swap / v_permlane16_swap, in both lanes of the pair.
+  auto pair_bcast = [&](unsigned v, int half) {
+    if constexpr (S16) return __builtin_amdgcn_permlane16_swap(v, v, false, false)[half];
+    else return __builtin_amdgcn_permlane32_swap(v, v, false, false)[half];
+  };
+  auto pair_insert = [&](float x, int xr) {
+    const float ps = __uint_as_float(pair_bcast(__float_as_uint(ts[KL - 1]), 0));
+    const int prow = (int)pair_bcast((unsigned)tr[KL - 1], 0);
+    const bool c = h && x > ps;                   // upper half: what the lower half pushes out -- its old last slot, or x itself
+    insert_shift(x, c ? ps : x, c ? prow : xr);
+  };
+  // Deferred insertion (header): the tile waiting for the chain, and a lower bound of the pair's K-th score -- the upper half's last
+  // slot as it stood after the last flush, in both lanes of the pair.  (CRS_WIDE_DEFER=0 arrives as a.no_defer: A/B runs)
+  constexpr bool kDefer = wide_defer<D, NW, K, S16>();
+  const bool defer = kDefer && !a.no_defer;       // a kernel argument: wave-uniform
+  float pend_s = kNegInf, thr = kNegInf;
+  int pend_r = -1;
+  auto flush = [&]() {
+    WP_COUNT(5);
+    pair_insert(pend_s, pend_r);                  // an empty slot inserts (-inf, -1): beats nothing, moves nothing
+    thr = __uint_as_float(pair_bcast(__float_as_uint(ts[KL - 1]), 1));
+    pend_s = kNegInf;
+    pend_r = -1;
+  };
+  // One chain site serves both settings of the knob -- with a second one the compiler kept the list in other registers on that path
+  // and copied all 2 KL of them over and back on EVERY tile, flush or not.  Knob off: the tile itself is the pending entry and the
+  // chain runs at once, which is the undeferred order.
+  auto pair_tile = [&](float x, int xr) {
+    if constexpr (kDefer) {
+      pend_s = defer ? pend_s : x;
+      pend_r = defer ? pend_r : xr;
+      // strict, as the chain's compares: an equal later tile never enters, nor does a NaN
+      const bool run = !defer || __builtin_amdgcn_ballot_w64(x > thr && pend_r >= 0) != 0;
+      if (run) flush();                           // some lane's slot is taken: the chain runs, for the whole wave
+      const bool cand = defer && x > thr;         // against the refreshed bound
+      pend_s = cand ? x : pend_s;
+      pend_r = cand ? xr : pend_r;
+    } else {
+      pair_insert(x, xr);
+    }
+  };
 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();   // the first tile has landed, and every wave has its fragments: the second buffer is free
@@ -416,11 +487,7 @@ __device__ __forceinline__ void scan_wide_body(const ScanArgs a) {
       const float y1 = __builtin_fmaxf(__uint_as_float(r1[0]), __uint_as_float(r1[1]));
       const auto rr = __builtin_amdgcn_permlane32_swap(__float_as_uint(y0), __float_as_uint(y1), false, false);
       x = __builtin_fmaxf(__uint_as_float(rr[0]), __uint_as_float(rr[1]));   // all four rows of lanes: the tile's best for the lane's query
-      // the lower half's last slot as it stands, in both lanes of the pair (l, l ^ 16): the even-row value of v_permlane16_swap
-      const float ps = __uint_as_float(__builtin_amdgcn_permlane16_swap(__float_as_uint(ts[KL - 1]), __float_as_uint(ts[KL - 1]), false, false)[0]);
-      const int prow = (int)__builtin_amdgcn_permlane16_swap((unsigned)tr[KL - 1], (unsigned)tr[KL - 1], false, false)[0];
-      const bool c = h && x > ps;                   // upper half: what the lower half pushes out -- its old last slot, or x itself
-      insert_shift(x, c ? ps : x, c ? prow : te * WTR);
+      pair_tile(x, te * WTR);                       // the pair is (l, l ^ 16)
     } else {   // 32x32x16
 #pragma unroll
       for (int rb = 0; rb < RB; ++rb) {
@@ -443,11 +510,7 @@ __device__ __forceinline__ void scan_wide_body(const ScanArgs a) {
       }
       x = pair_max(x);                              // both halves: the tile's best
       if constexpr (kSplit) {
-        // the lower half's last slot as it stands, in the upper half's lanes (low-half broadcast of v_permlane32_swap)
-        const float ps = __uint_as_float(__builtin_amdgcn_permlane32_swap(__float_as_uint(ts[KL - 1]), __float_as_uint(ts[KL - 1]), false, false)[0]);
-        const int prow = (int)__builtin_amdgcn_permlane32_swap((unsigned)tr[KL - 1], (unsigned)tr[KL - 1], false, false)[0];
-        const bool c = h && x > ps;                 // upper half: what the lower half pushes out -- its old last slot, or x itself
-        insert_shift(x, c ? ps : x, c ? prow : te * WTR);
+        pair_tile(x, te * WTR);                     // the pair is (l, l ^ 32)
       } else {
         if ((ie & 1) == h) { px = x; pr = te * WTR; } // lane half h is responsible for the tiles of parity h
         if (ie & 1) {
@@ -516,6 +579,9 @@ __device__ __forceinline__ void scan_wide_body(const ScanArgs a) {
 
   if (wave_active && late && it > 0) select(acc_prev, t_prev, it - 1);   // the deferred last tile
   if constexpr (kSplit) {
+    if constexpr (kDefer) {
+      if (wave_active) flush();   // what still waits for the chain
+    }
     if (wave_active && q_valid) {   // [nq, nwg, kp = 2 K]: ranks h KL .. h KL + KL - 1 of the pair's list, then K empty slots
       const size_t o = ((size_t)qi * nwg + stream) * a.kp + (size_t)h * KL;
 #pragma unroll

@@ -4,6 +4,9 @@
 // The 24- / 32-slot forms run as the product launches them: nt stream for slabs of 1 GB and more, ticketed tile schedule on long
 // streams (85 % of the tiles in granules of 8; CRS_WIDE_DYN=0: static stride), CRS_WIDE_STAGGER and CRS_WIDE_MFMA as in the library.
 // The last line is the clock the chip held inside the kernel: a wave's cycles over the launch / the launch's time.
+// Slot 5 is not a lap but a count: how often a wave ran the insertion chain of the deferred split forms (CRS_WIDE_DEFER, scan_wide.hip
+// "Deferred insertion"; one more than the flushes in the loop: the flush at the end).  That count depends on the data, so the slab is
+// filled on the device with rows that do not repeat.
 #define CRS_STAMPS 1
 #include "../compressed-rag-suite_amd/csrc/scan_wide.hip"
 #include "../compressed-rag-suite_amd/csrc/plan.cpp"   // knobs_from_env
@@ -12,6 +15,21 @@
 #include <math.h>
 #include <stdio.h>
 #include <vector>
+
+// one thread per 8 elements: a sum of four hashed uniforms per element, scaled like the host's queries
+__global__ void fill_rows(_Float16* slab, size_t n8, float sc) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n8) return;
+  for (int e = 0; e < 8; ++e) {
+    unsigned long long z = (i * 8 + e) * 0x9E3779B97F4A7C15ull + 0x632BE59BD9B4E019ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    float u = 0;
+    for (int j = 0; j < 4; ++j) u += ((z >> (16 * j)) & 0xffff) / 65536.0f - 0.5f;
+    slab[i * 8 + e] = (_Float16)(u * sc);
+  }
+}
 
 int main(int argc, char** argv) {
   const int rows = argc > 1 ? atoi(argv[1]) : 1250000;
@@ -28,13 +46,10 @@ int main(int argc, char** argv) {
   int nwg = prop.multiProcessorCount * crs::scan_wide_wg_per_cu(nw) / nqb;
   if (nqb > 1) nwg &= ~7;
   nwg = std::min(nwg, n_tiles);
-  // (the selection is branch-free: the laps do not depend on the data, so the host fills at most 1 M rows and the slab repeats them)
-  const size_t gen_rows = std::min<size_t>((size_t)rows, (size_t)1 << 20);
-  std::vector<_Float16> h(gen_rows * dim), hq((size_t)nq * dim);
+  std::vector<_Float16> hq((size_t)nq * dim);
   unsigned s = 12345;
   auto rnd = [&]() { s = s * 1664525u + 1013904223u; float u = 0; for (int i = 0; i < 4; ++i) { s = s * 1664525u + 1013904223u; u += ((s >> 8) & 0xffff) / 65536.0f - 0.5f; } return u; };
   const float sc = 1.0f / sqrtf((float)dim / 3.0f);
-  for (auto& x : h) x = (_Float16)(rnd() * sc);
   for (auto& x : hq) x = (_Float16)(rnd() * sc);
   _Float16 *slab, *q; float* ps; int* pr; unsigned long long* st;
   const int kp = 2 * crs::scan_wide_slots(k);
@@ -42,8 +57,8 @@ int main(int argc, char** argv) {
   hipMalloc(&ps, (size_t)nwg * nq * kp * 4); hipMalloc(&pr, (size_t)nwg * nq * kp * 4);
   const size_t nst = (size_t)nwg * nqb * nw * 12;
   hipMalloc(&st, nst * 8);
-  for (size_t r0 = 0; r0 < (size_t)rows; r0 += gen_rows)
-    hipMemcpy(slab + r0 * dim, h.data(), std::min(gen_rows, (size_t)rows - r0) * dim * 2, hipMemcpyHostToDevice);
+  const size_t n8 = (size_t)rows * dim / 8;   // dim is a multiple of 128
+  fill_rows<<<dim3((unsigned)((n8 + 255) / 256)), dim3(256)>>>(slab, n8, sc);
   hipMemcpy(q, hq.data(), hq.size() * 2, hipMemcpyHostToDevice);
   crs::ScanArgs a{};
   a.q = q; a.slab = slab; a.part_scores = ps; a.part_rows = pr; a.stamps = st;
@@ -53,6 +68,7 @@ int main(int argc, char** argv) {
   const int slots = crs::scan_wide_slots(k);
   const int mfma = !crs::wide_has_16(dim, nw, slots) ? 32 : kn.wide_mfma ? kn.wide_mfma : crs::wide_default_mfma(dim, slots);
   a.no_stagger = kn.wide_stagger ? 0 : 1;
+  a.no_defer = kn.wide_defer ? 0 : 1;
   if (crs::scan_wide_streamed(k)) {   // the plan fields of plan.cpp's finish_plan
     a.nt = ((size_t)rows * dim * 2 >= ((size_t)1 << 30) && nqb == 1) ? 1 : 0;
     const int rounds = n_tiles / nwg;
@@ -77,10 +93,10 @@ int main(int argc, char** argv) {
   }
   std::vector<unsigned long long> hs(nst);
   hipMemcpy(hs.data(), st, nst * 8, hipMemcpyDeviceToHost);
-  printf("rows %d dim %d nq %d k %d | waves/wg %d nqb %d streams %d tiles/stream %.1f nt %d tickets %s stagger-knob %s mfma %d | kernel %.1f us (with stamps)\n", rows, dim, nq,
-         k, nw, nqb, nwg, (double)n_tiles / nwg, a.nt, ticket ? "on" : "off", kn.wide_stagger ? "default" : "0", mfma, ms * 1e3);
-  // slots 2 / 4: the selection of waves 4..7 (deferred one tile) / of waves 0..3; 5, 8, 9: unused since the tile-best rewrite
-  const char* names[12] = {"prologue", "tile-load issue", "selection (waves 4-7, deferred)", "MFMA sweep", "selection (waves 0-3)", "(unused)",
+  printf("rows %d dim %d nq %d k %d | waves/wg %d nqb %d streams %d tiles/stream %.1f nt %d tickets %s stagger-knob %s defer-knob %s mfma %d | kernel %.1f us (with stamps)\n", rows, dim, nq,
+         k, nw, nqb, nwg, (double)n_tiles / nwg, a.nt, ticket ? "on" : "off", kn.wide_stagger ? "default" : "0", kn.wide_defer ? "default" : "0", mfma, ms * 1e3);
+  // slots 2 / 4: the selection of waves 4..7 (deferred one tile) / of waves 0..3; 5: a count, not a lap; 8, 9: unused since the tile-best rewrite
+  const char* names[12] = {"prologue", "tile-load issue", "selection (waves 4-7, deferred)", "MFMA sweep", "selection (waves 0-3)", "chain runs (a count)",
                            "wait next tile + LDS store", "barrier", "(unused)", "(unused)", "final flush", "TOTAL"};
   const size_t nwaves = nst / 12;
   // cycles per wave over the launch, and per tile of the wave's stream (mean); waves 0..3 and 4..7 of a workgroup apart
@@ -94,8 +110,9 @@ int main(int argc, char** argv) {
     }
     std::sort(v.begin(), v.end());
     double sum = 0; for (double x : v) sum += x;
-    printf("  %-31s mean %9.0f  median %9.0f  max %9.0f | per tile: waves 0-3 %7.0f  waves 4-7 %7.0f\n", names[i], sum / nwaves, v[nwaves / 2], v.back(),
-           half[0] / (nh[0] ? nh[0] : 1) / tps, half[1] / (nh[1] ? nh[1] : 1) / tps);
+    printf(i == 5 ? "  %-31s mean %9.0f  median %9.0f  max %9.0f | per tile: waves 0-3 %7.3f  waves 4-7 %7.3f\n"
+                  : "  %-31s mean %9.0f  median %9.0f  max %9.0f | per tile: waves 0-3 %7.0f  waves 4-7 %7.0f\n",
+           names[i], sum / nwaves, v[nwaves / 2], v.back(), half[0] / (nh[0] ? nh[0] : 1) / tps, half[1] / (nh[1] ? nh[1] : 1) / tps);
     if (i == 11) printf("  in-kernel clock (median TOTAL cycles / kernel time): %.3f GHz\n", v[nwaves / 2] / (ms * 1e6));
   }
   return 0;
