@@ -277,6 +277,43 @@ int crs_rerank_lexical(const float* scores_dev, const int64_t* rows_dev, int nq,
   return e ? hip_fail((hipError_t)e, "rerank_lexical launch") : CRS_OK;
 }
 
+int crs_pairs_above_f16(const void* slab_dev, int64_t n_rows, int dim, int64_t a_first, int64_t a_rows, int64_t b_first, int64_t b_rows,
+                        float thr, int64_t* pairs_out_dev, float* scores_out_dev, int64_t cap, int64_t* count_dev, void* stream) {
+  if (dim < 1 || dim > 1024) return fail(CRS_EINVAL, "bad dim (1 <= dim <= 1024)");
+  if (n_rows < 0) return fail(CRS_EINVAL, "bad n_rows (n_rows >= 0)");
+  if (a_first < 0 || a_rows < 0 || a_first > n_rows || a_rows > n_rows - a_first) return fail(CRS_EINVAL, "range a leaves [0, n_rows)");
+  if (b_first < 0 || b_rows < 0 || b_first > n_rows || b_rows > n_rows - b_first) return fail(CRS_EINVAL, "range b leaves [0, n_rows)");
+  if (!(thr == thr) || thr - thr != 0.0f) return fail(CRS_EINVAL, "thr must be finite");
+  if (cap < 0) return fail(CRS_EINVAL, "bad cap (cap >= 0)");
+  if (!slab_dev) return fail(CRS_EINVAL, "slab_dev is null");
+  if (!count_dev) return fail(CRS_EINVAL, "count_dev is null");
+  if (cap > 0 && (!pairs_out_dev || !scores_out_dev)) return fail(CRS_EINVAL, "pairs_out_dev / scores_out_dev is null");
+  if (((uintptr_t)slab_dev | (uintptr_t)pairs_out_dev) & 15) return fail(CRS_EINVAL, "slab_dev / pairs_out_dev must be 16-byte aligned");
+  if ((uintptr_t)count_dev & 7) return fail(CRS_EINVAL, "count_dev must be 8-byte aligned");
+  const int64_t n_at = (a_rows + CRS_PAIRS_TILE - 1) / CRS_PAIRS_TILE, n_bt = (b_rows + CRS_PAIRS_TILE - 1) / CRS_PAIRS_TILE;
+  if (n_at * ((n_bt + 7) / 8 * 8) > CRS_PAIRS_MAX_TILES) return fail(CRS_EINVAL, "too many tile pairs for one launch (CRS_PAIRS_MAX_TILES): stripe the ranges");
+  if (a_rows == 0 || b_rows == 0) return CRS_OK;
+  const int e = crs::pairs_above_launch(slab_dev, crs_padded_dim(dim), a_first, a_rows, b_first, b_rows, thr, pairs_out_dev, scores_out_dev,
+                                        cap, count_dev, (hipStream_t)stream);
+  return e ? hip_fail((hipError_t)e, "pairs_above launch") : CRS_OK;
+}
+
+int crs_pairs_verify_f32(const int64_t* pairs_dev, int64_t m, const float* shadow_f32_dev, int64_t n_rows, int dim, float thr,
+                         int64_t* rows_a_dev, int64_t* rows_b_dev, float* sims_dev, int64_t* count_dev, void* stream) {
+  if (dim < 1 || dim > 1024) return fail(CRS_EINVAL, "bad dim (1 <= dim <= 1024)");
+  if (n_rows < 0) return fail(CRS_EINVAL, "bad n_rows (n_rows >= 0)");
+  if (m < 0 || m > (int64_t)1 << 31) return fail(CRS_EINVAL, "bad m (0 <= m <= 2^31)");
+  if (!(thr == thr)) return fail(CRS_EINVAL, "thr must not be NaN");
+  if (!count_dev) return fail(CRS_EINVAL, "count_dev is null");
+  if (m > 0 && (!pairs_dev || !shadow_f32_dev || !rows_a_dev || !rows_b_dev || !sims_dev)) return fail(CRS_EINVAL, "null pointer");
+  if ((uintptr_t)pairs_dev & 15) return fail(CRS_EINVAL, "pairs_dev must be 16-byte aligned");
+  if ((uintptr_t)count_dev & 7) return fail(CRS_EINVAL, "count_dev must be 8-byte aligned");
+  if (m == 0) return CRS_OK;
+  const int e = crs::pairs_verify_launch(pairs_dev, m, shadow_f32_dev, n_rows, dim, thr, rows_a_dev, rows_b_dev, sims_dev, count_dev,
+                                         (hipStream_t)stream);
+  return e ? hip_fail((hipError_t)e, "pairs_verify launch") : CRS_OK;
+}
+
 static const char* bm25_sizes_bad(int nq, int k, int64_t n_rows) {
   if (nq < 1 || nq > 64) return "bad nq (1 <= nq <= 64)";
   if (k < 1 || k > CRS_MAX_K) return "bad k (1 <= k <= CRS_MAX_K)";

@@ -109,6 +109,13 @@ int wordpiece_encode_launch(const uint8_t* text, const int64_t* offsets, int n_t
 int token_match_launch(const float* a, const int* len_a, int seq_a, const float* b, const int* len_b, int seq_b, int n_pairs, int hidden,
                        const float* w_a, const float* w_b, float* out, hipStream_t stream);
 
+// join.hip: thresholded self-join of an fp16 slab (pairs i < j with slab score >= thr, 256 x 256 tiles) and the fp32 check of its
+// candidates against the shadow, a quarter wave per pair
+int pairs_above_launch(const void* slab, int pdim, int64_t a_first, int64_t a_rows, int64_t b_first, int64_t b_rows, float thr,
+                       int64_t* pairs_out, float* scores_out, int64_t cap, int64_t* counter, hipStream_t stream);
+int pairs_verify_launch(const int64_t* pairs, int64_t m, const float* shadow, int64_t n_rows, int d, float thr, int64_t* rows_a,
+                        int64_t* rows_b, float* sims, int64_t* counter, hipStream_t stream);
+
 // convert.hip
 int refine_f32_launch(const float* q32, int nq, int dim, const float* shadow, int64_t n_rows, int64_t id_base,
                       const int64_t* cand, int k_in, int k_out, float* out_s, int64_t* out_i, hipStream_t stream);

@@ -22,6 +22,7 @@
 //   crs::token_match       the greedy matching behind bert_score.score  (reference evaluation/retrieval/rag_metrics.py:179-207)
 //   crs::wordpiece_encode           BERT basic tokenisation + WordPiece of UTF-8 texts on the device (the tokenizer inside SentenceTransformer.encode)
 //   crs::bm25_topk / crs::fuse_rrf   hybrid retrieval: exact BM25 scan over the token CSR, reciprocal rank fusion (new vs the reference)
+//   crs::pairs_above / crs::pairs_verify   near-duplicate detection: thresholded self-join of the slab, fp32 check (new vs the reference)
 //   crs::rerank_lexical    replaces the scoring, threshold and _rerank loops of retrieve_batch  (reference rag/retrieval.py:75-77, 196-217)
 // Tensors are torch-owned; every op launches on the CURRENT HIP stream of the tensors' device, so the ops
 // compose with torch streams and hipGraph capture.  Errors of the C ABI surface as RuntimeError (TORCH_CHECK)
@@ -658,6 +659,52 @@ void rerank_lexical(const Tensor& scores, const Tensor& rows, const Tensor& doc_
      "crs::rerank_lexical");
 }
 
+// ---- near-duplicate join (csrc/join.hip) ---------------------------------------------------------------------------
+// slab fp16 [>= n_rows, pdim]; pairs int64 [cap, 2], scores fp32 [cap]; count int64 [1], zeroed by the caller, receives the number
+// of qualifying pairs (count > cap: overflow)
+void pairs_above_out(const Tensor& slab, int64_t n_rows, int64_t dim, int64_t a_first, int64_t a_rows, int64_t b_first, int64_t b_rows,
+                     double thr, Tensor pairs, Tensor scores, Tensor count) {
+  want(slab, at::kHalf, "slab");
+  want(pairs, at::kLong, "pairs");
+  want(scores, at::kFloat, "scores");
+  want(count, at::kLong, "count");
+  same_device(slab, {&pairs, &scores, &count}, "crs::pairs_above");
+  TORCH_CHECK(dim >= 1 && dim <= 1024, "dim must be in 1..1024");
+  TORCH_CHECK(slab.dim() == 2 && slab.size(1) == crs_padded_dim((int)dim), "slab must be fp16 [rows, crs_padded_dim(dim)]");
+  TORCH_CHECK(n_rows >= 0 && n_rows <= slab.size(0), "n_rows exceeds the slab");
+  TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2 && scores.dim() == 1 && scores.size(0) == pairs.size(0),
+              "pairs must be int64 [cap, 2] and scores fp32 [cap]");
+  TORCH_CHECK(count.numel() == 1, "count must hold one int64");
+  const int64_t cap = pairs.size(0);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(slab.device());
+  ok(crs_pairs_above_f16(slab.data_ptr(), n_rows, (int)dim, a_first, a_rows, b_first, b_rows, (float)thr,
+                         cap ? pairs.data_ptr<int64_t>() : nullptr, cap ? scores.data_ptr<float>() : nullptr, cap, count.data_ptr<int64_t>(),
+                         cur_stream(slab)), "crs::pairs_above");
+}
+
+// pairs int64 [m, 2]; shadow fp32 [>= n_rows, dim]; rows_a / rows_b int64 [>= m], sims fp32 [>= m]; count int64 [1], zeroed by the caller
+void pairs_verify_out(const Tensor& pairs, const Tensor& shadow, int64_t n_rows, double thr, Tensor rows_a, Tensor rows_b, Tensor sims,
+                      Tensor count) {
+  want(pairs, at::kLong, "pairs");
+  want(shadow, at::kFloat, "shadow");
+  want(rows_a, at::kLong, "rows_a");
+  want(rows_b, at::kLong, "rows_b");
+  want(sims, at::kFloat, "sims");
+  want(count, at::kLong, "count");
+  same_device(pairs, {&shadow, &rows_a, &rows_b, &sims, &count}, "crs::pairs_verify");
+  TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2, "pairs must be int64 [m, 2]");
+  TORCH_CHECK(shadow.dim() == 2 && shadow.size(1) >= 1 && shadow.size(1) <= 1024 && n_rows >= 0 && n_rows <= shadow.size(0),
+              "shadow must be fp32 [>= n_rows, dim], dim in 1..1024");
+  const int64_t m = pairs.size(0);
+  TORCH_CHECK(rows_a.numel() >= m && rows_b.numel() >= m && sims.numel() >= m, "rows_a / rows_b / sims must hold m entries");
+  TORCH_CHECK(count.numel() == 1, "count must hold one int64");
+  if (m == 0) return;
+  c10::hip::HIPGuardMasqueradingAsCUDA g(pairs.device());
+  ok(crs_pairs_verify_f32(pairs.data_ptr<int64_t>(), m, shadow.data_ptr<float>(), n_rows, (int)shadow.size(1), (float)thr,
+                          rows_a.data_ptr<int64_t>(), rows_b.data_ptr<int64_t>(), sims.data_ptr<float>(), count.data_ptr<int64_t>(),
+                          cur_stream(pairs)), "crs::pairs_verify");
+}
+
 // ---- hybrid retrieval: BM25 scan (csrc/bm25.hip) and rank fusion (csrc/fuse.hip) ------------------------------------------------------
 // doc_offsets int64 [>= n_rows + 1], doc_tokens / doc_tf int32 (same length), doc_len int32 [>= n_rows]; q_offsets int64 [nq + 1],
 // q_tokens int32 / q_weights fp32 (same length); workspace uint8 (crs_bm25_workspace_bytes); out_scores fp32 / out_rows int64 [nq, k]
@@ -918,6 +965,10 @@ TORCH_LIBRARY(crs, m) {
   m.def("token_match_out(Tensor a, Tensor len_a, Tensor b, Tensor len_b, Tensor? w_a, Tensor? w_b, Tensor(a!) out) -> ()");
   m.def("rerank_lexical(Tensor scores, Tensor rows, Tensor doc_offsets, Tensor doc_tokens, int n_rows, Tensor q_offsets, Tensor q_tokens, "
         "Tensor q_norm, int k, float threshold, Tensor(a!) order, Tensor(b!) count, Tensor(c!) sim, Tensor(d!) rr, Tensor(e!) reranked) -> ()");
+  m.def("pairs_above_out(Tensor slab, int n_rows, int dim, int a_first, int a_rows, int b_first, int b_rows, float thr, "
+        "Tensor(a!) pairs, Tensor(b!) scores, Tensor(c!) count) -> ()");
+  m.def("pairs_verify_out(Tensor pairs, Tensor shadow, int n_rows, float thr, Tensor(a!) rows_a, Tensor(b!) rows_b, Tensor(c!) sims, "
+        "Tensor(d!) count) -> ()");
   m.def("bm25_topk(Tensor doc_offsets, Tensor doc_tokens, Tensor doc_tf, Tensor doc_len, int n_rows, Tensor q_offsets, Tensor q_tokens, "
         "Tensor q_weights, float c0, float c1, float k1p1, int k, Tensor(a!) workspace, Tensor(b!) out_scores, Tensor(c!) out_rows) -> ()");
   m.def("fuse_rrf(Tensor dense_rows, Tensor lex_rows, float c, float w_dense, float w_lex, Tensor(a!) rows, Tensor(b!) fused, "
@@ -962,6 +1013,8 @@ TORCH_LIBRARY_IMPL(crs, CUDA, m) {   // the HIP backend of torch-ROCm dispatches
   m.impl("mmr_order_out", &mmr_order_out);
   m.impl("token_match_out", &token_match_out);
   m.impl("rerank_lexical", &rerank_lexical);
+  m.impl("pairs_above_out", &pairs_above_out);
+  m.impl("pairs_verify_out", &pairs_verify_out);
   m.impl("bm25_topk", &bm25_topk);
   m.impl("fuse_rrf", &fuse_rrf);
   m.impl("wordpiece_encode", &wordpiece_encode);

@@ -28,7 +28,9 @@ EXACT_CAP = 1024           # default list length (12 KB of LDS per query in the 
 BM25_MAX_QUERIES = 64      # queries of one crs_bm25_topk launch
 WORDPIECE_TILE_BYTES = 1024   # CRS_WORDPIECE_TILE_BYTES: bytes of a text that crs_wordpiece_encode stages at a time
 BM25_MAX_PAIRS = 4096      # CRS_BM25_MAX_PAIRS: (query, known token) pairs of one crs_bm25_topk launch
-SPACE_COSINE, SPACE_IP, SPACE_L2 = 0, 1, 2     # CRS_SPACE_*: a collection's hnsw:space
+PAIRS_TILE = 256           # CRS_PAIRS_TILE: tile edge of the near-duplicate join (csrc/join.hip)
+PAIRS_MAX_TILES = 1 << 22  # CRS_PAIRS_MAX_TILES: tile pairs of one crs_pairs_above_f16 launch
+SPACE_COSINE, SPACE_IP, SPACE_L2 = 0, 1, 2    # CRS_SPACE_*: a collection's hnsw:space
 SPACES = {"cosine": SPACE_COSINE, "ip": SPACE_IP, "l2": SPACE_L2}
 
 # name -> (restype, argtypes); mirrors include/crs_hip.h one to one
@@ -66,6 +68,9 @@ _SIGNATURES = {
     "crs_token_match": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "crs_rerank_lexical": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64,
                                    c_void_p, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "crs_pairs_above_f16": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, c_int64, c_float, c_void_p, c_void_p, c_int64,
+                                    c_void_p, c_void_p]),
+    "crs_pairs_verify_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "crs_bm25_workspace_bytes": (c_int, [c_int, c_int, c_int64, POINTER(c_size_t)]),
     "crs_bm25_topk": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int64,
                               c_float, c_float, c_float, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
@@ -446,6 +451,58 @@ def rerank_lexical(scores, rows, doc_offsets, doc_tokens, n_rows: int, q_offsets
                torch.empty(nq, dtype=torch.int32, device=dev))
     with _translate():
         ops().rerank_lexical(scores, rows, doc_offsets, doc_tokens, int(n_rows), q_offsets, q_tokens, q_norm, int(k), float(threshold), *out)
+    return out
+
+
+def pairs_epsilon(row_err: float, pdim: int) -> float:
+    """The band that joins the two stages of the near-duplicate join: a pair whose fp32 similarity sim32 is at least
+    t has a slab score of at least t - eps, eps = (2 E + E^2)(1 + 1e-4) + (1.5 pdim + 8) 2^-23 with E = row_err the slab's tracked
+    row error (|stored row - fp32 row|_2) and pdim its padded row length.  The first term is <c^_i, c^_j> - <c_i, c_j> =
+    <c^_i - c_i, c^_j> + <c_i, c^_j - c_j> <= E (1 + E) + E for unit rows (the factor covers norms that are 1 only to fp32
+    rounding); the second is the certificate's arithmetic term (csrc/exact.hip exact_err_arith): the fp32 accumulation of the
+    slab score and of sim32."""
+    e = float(row_err)
+    return (2.0 * e + e * e) * (1.0 + 1e-4) + (1.5 * int(pdim) + 8.0) * 2.0 ** -23
+
+
+def pairs_thresholds(threshold: float, eps: float):
+    """(stage 1, stage 2) thresholds as the fp32 values the kernels compare with: the largest fp32 <= threshold - eps, and the
+    smallest fp32 >= threshold (sim32 is an fp32: sim32 >= threshold holds exactly when it is at least that value)."""
+    import numpy as np
+    lo = np.float32(threshold - eps)
+    if float(lo) > threshold - eps:
+        lo = np.nextafter(lo, np.float32(-np.inf))
+    hi = np.float32(threshold)
+    if float(hi) < threshold:
+        hi = np.nextafter(hi, np.float32(np.inf))
+    return float(lo), float(hi)
+
+
+def pairs_above(slab, n_rows: int, dim: int, a_range, b_range, thr: float, cap: int, out=None):
+    """Stage 1 of the near-duplicate join (crs_pairs_above_f16, csrc/join.hip): every pair i < j, i in a_range = (first, rows),
+    j in b_range, whose fp16 slab score is >= thr -> (pairs int64 [cap, 2], scores fp32 [cap], count int64 [1]), all cuda; count
+    holds the number of qualifying pairs, of which the first min(count, cap) slots are filled in unspecified order (count > cap:
+    overflow, re-run with a larger cap).  `out`: the three tensors preallocated, count zeroed.  No host sync."""
+    import torch
+    if out is None:
+        out = (torch.empty((int(cap), 2), dtype=torch.int64, device=slab.device), torch.empty(int(cap), dtype=torch.float32, device=slab.device),
+               torch.zeros(1, dtype=torch.int64, device=slab.device))
+    with _translate():
+        ops().pairs_above_out(slab, int(n_rows), int(dim), int(a_range[0]), int(a_range[1]), int(b_range[0]), int(b_range[1]), float(thr), *out)
+    return out
+
+
+def pairs_verify(pairs, shadow, n_rows: int, thr: float, out=None):
+    """Stage 2 (crs_pairs_verify_f32): pairs cuda int64 [m, 2] against the fp32 shadow [>= n_rows, dim] -> (rows_a int64 [m], rows_b
+    int64 [m], sims fp32 [m], count int64 [1]): the pairs with sim32 >= thr compacted into the first count slots, in unspecified
+    order; sim32 is a fixed-order fp32 dot, bitwise independent of the launch.  `out`: preallocated, count zeroed.  No host sync."""
+    import torch
+    if out is None:
+        m, dev = pairs.shape[0], pairs.device
+        out = (torch.empty(m, dtype=torch.int64, device=dev), torch.empty(m, dtype=torch.int64, device=dev),
+               torch.empty(m, dtype=torch.float32, device=dev), torch.zeros(1, dtype=torch.int64, device=dev))
+    with _translate():
+        ops().pairs_verify_out(pairs, shadow, int(n_rows), float(thr), *out)
     return out
 
 

@@ -73,6 +73,18 @@ New, additive surface (all keys absent from the reference config.json default so
                               reciprocal rank fusion of a dense and a lexical list (csrc/fuse.hip); the retriever's opt-in
                               ``hybrid`` calls both.  The statistics share the token CSR's lifecycle (+ 4 bytes per distinct token
                               per chunk and 4 bytes per row on the first device)
+  ``near_duplicates`` / ``duplicate_of`` / ``deduplicate`` / ``dedup_threshold``   exact near-duplicate detection: every pair of
+                              rows whose cosine is at least a threshold, each pair once -- a thresholded self-join of the slab on
+                              the matrix cores (csrc/join.hip) at threshold - epsilon, then an fp32 check of the candidates against
+                              the shadow, so the answer is the fp32 one: exactly {i < j : sim32(i, j) >= t}.
+                              ``duplicate_of`` applies greedy keep-first in row order (keep_first), ``deduplicate`` removes the
+                              marked rows through delete's path.  Config key ``dedup_threshold`` (default None: nothing changes):
+                              create_index joins all rows x the new batch and drops the batch's near-duplicates (old rows are always
+                              kept) before sidecars and files see them -- one O(batch) append of the survivors, no generation
+                              rewrite, mutation_epoch does not move; ``last_dedup`` = {'added', 'dropped'} of the last call;
+                              ``dedup_max_pairs`` (4 M) bounds the pairs such a join may list.  fp16 cosine stores with the fp32
+                              shadow on one device: int8, 'ip' / 'l2', sharded / num_gpus / devices raise NotImplementedError,
+                              refine_fp32: False raises ValueError
 ``where`` / ``where_document`` filters work on every layout (the sidecars are replicated; each shard scans the
 allowed rows it owns).  ``top_k`` is unlimited as in the reference: up to 1024 a refined shard is over-fetched by
 partition (64 candidates from each of up to 64 row chunks, crs::cosine_topk_large_cert) and certified like top_k <= 64;
@@ -233,6 +245,26 @@ def compact_windows(n_rows: int, m: int, window_rows: int, first_row: int = 0):
     if m <= 0 or n_out <= 0 or W <= 0:
         return []
     return [(d0, min(W, n_out - d0)) for d0 in range(int(first_row) // W * W, n_out, W)]
+
+
+def keep_first(n: int, rows_a, rows_b) -> np.ndarray:
+    """Greedy keep-first over a list of near-duplicate pairs (a < b; any order): int64 [n], entry r = -1 for a kept row, otherwise
+    the kept row r duplicates.  Rows are visited in row order; row j is dropped iff some KEPT i < j forms a pair with it, and its
+    entry is the smallest such i.  Not the transitive closure: of a chain a~b~c with a !~ c, b is dropped (for a) and c is kept,
+    because its only partner b is gone.  A row that is no pair's second row is always kept."""
+    dup = np.full(int(n), -1, dtype=np.int64)
+    a = np.asarray(rows_a, dtype=np.int64)
+    b = np.asarray(rows_b, dtype=np.int64)
+    if a.size == 0:
+        return dup
+    if a.shape != b.shape or np.any(a >= b) or a.min() < 0 or b.max() >= n:
+        raise ValueError("pairs must be (a, b) with 0 <= a < b < n")
+    order = np.lexsort((a, b))                        # by b, then a: a row's partners are contiguous and ascending
+    a, b = a[order].tolist(), b[order].tolist()
+    for i, j in zip(a, b):
+        if dup[j] < 0 and dup[i] < 0:                 # j still kept, i kept (final: i < j was decided before j's group began)
+            dup[j] = i
+    return dup
 
 
 class _TokenCSR:
@@ -614,6 +646,15 @@ class VectorStore:
                 if on:
                     raise NotImplementedError(f"space {self.space!r} is not supported with {layout}: the rows of such a store share one "
                                               "norm scale, which a single-device store keeps")
+        # near-duplicate removal at index time (module docstring): None = nothing changes anywhere
+        self.dedup_threshold = config.get('dedup_threshold', None)
+        self.dedup_max_pairs = int(config.get('dedup_max_pairs', 1 << 22))
+        self.last_dedup = {"added": 0, "dropped": 0}      # rows the last create_index kept / dropped as near-duplicates
+        self.last_join = {"stripes": 0, "reruns": 0, "candidates": 0}   # of the last near-duplicate join
+        self._join_stripe_rows = 1 << 18                  # rows per stripe edge: (2^18 / 256)^2 = 2^20 tile pairs per launch
+        self._join_first_cap = 1 << 16                    # candidate slots a stripe is first given (it is re-run when they overflow)
+        if self.dedup_threshold is not None:
+            self.dedup_threshold = self._join_refusals(self.dedup_threshold)
         if self.sharded and (self.num_gpus > 1 or self._devices_cfg):
             raise ValueError("'sharded' (one process per GPU) and 'num_gpus'/'devices' (one process, N devices) are exclusive")
         if self.sharded and self.persist_directory:
@@ -921,6 +962,14 @@ class VectorStore:
             else:                     # one process: shard g of the batch goes to device g (one shard: everything)
                 for sh, (lo, hi) in zip(col.shards, _shard.batch_slices(len(chunks), len(col.shards))):
                     sh.append(emb[lo:hi].to(sh.device).contiguous(), start + lo)
+            if self.dedup_threshold is not None:
+                # the device arrays hold the batch, the sidecars do not yet: drop its near-duplicates (of older rows, and of
+                # earlier rows of the batch) BEFORE either sidecars or files see them -- one O(batch) append of the survivors
+                dropped = set(self._drop_new_duplicates(start, len(chunks)).tolist())
+                self.last_dedup = {"added": len(chunks) - len(dropped), "dropped": len(dropped)}
+                if dropped:
+                    logger.info(f"dedup_threshold {self.dedup_threshold}: dropped {len(dropped)} near-duplicate chunks of {len(chunks)}")
+                    chunks = [c for at, c in enumerate(chunks) if at not in dropped]
             col.ids.extend(chunk.chunk_id for chunk in chunks)
             col.documents.extend(chunk.text for chunk in chunks)
             col.metadatas.extend(self._chunk_metadata(chunk, fields) for chunk in chunks)
@@ -1021,6 +1070,15 @@ class VectorStore:
     def _delete_rows(self, dead: np.ndarray):
         """dead: ascending distinct sidecar rows.  Every shard compacts the rows it owns (crs::slab_compact) and renumbers its
         row map; the host sidecars lose the same rows in one pass."""
+        col = self.collection
+        self._compact_shards(dead)
+        keep = survivor_rows(len(col.ids), dead).tolist()
+        col.ids = [col.ids[r] for r in keep]
+        col.documents = [col.documents[r] for r in keep]
+        col.metadatas = [col.metadatas[r] for r in keep]
+
+    def _compact_shards(self, dead: np.ndarray):
+        """The device half of _delete_rows: every shard drops the rows of `dead` (ascending distinct sidecar rows) it owns."""
         import torch
         col = self.collection
         for sh in col.shards:
@@ -1042,10 +1100,136 @@ class VectorStore:
                     # new sidecar row = old - deleted sidecar rows below it (an identity shard's map is 0, 1, 2, ... before and after)
                     rg = sh.rows_global[: sh.n]
                     rg.sub_(torch.searchsorted(dead_t, rg))
-        keep = survivor_rows(len(col.ids), dead).tolist()
-        col.ids = [col.ids[r] for r in keep]
-        col.documents = [col.documents[r] for r in keep]
-        col.metadatas = [col.metadatas[r] for r in keep]
+
+    # -- near-duplicate detection (module docstring: near_duplicates / duplicate_of / deduplicate / dedup_threshold) ---------------
+    def _join_refusals(self, threshold) -> float:
+        """Everything that rules the join out, raised before any device work -> the threshold as a float."""
+        if self.index_dtype == 'int8':
+            raise NotImplementedError("near-duplicate detection is not supported with index_dtype 'int8': the int8 row error makes "
+                                      "the candidate band wide, and the join needs an integer kernel of its own")
+        if self.space != 'cosine':
+            raise NotImplementedError(f"near-duplicate detection is not supported in space {self.space!r}: the threshold is a cosine")
+        for layout, on in (("sharded=True", self.sharded), ("num_gpus > 1", self.num_gpus > 1), ("devices", bool(self._devices_cfg))):
+            if on:
+                raise NotImplementedError(f"near-duplicate detection is not supported with {layout}: a pair's rows would have to "
+                                          "cross devices")
+        if not self.refine_fp32:
+            raise ValueError("near-duplicate detection needs the fp32 shadow (candidates are verified against it): refine_fp32 must "
+                             "not be False")
+        try:
+            t = float(threshold)
+        except (TypeError, ValueError):
+            raise ValueError(f"threshold must be a number in (-1, 1], got {threshold!r}") from None
+        if not (np.isfinite(t) and -1.0 < t <= 1.0):
+            raise ValueError(f"threshold must be finite and in (-1, 1], got {threshold!r}")
+        return t
+
+    def _join(self, threshold: float, b_first: int, b_rows: int, max_pairs: int, n_rows: Optional[int] = None):
+        """The two-stage join of the sole shard: every pair i < j, j in [b_first, b_first + b_rows), whose fp32 similarity is at
+        least `threshold` -> (rows_a, rows_b int64, similarities fp32, sorted by (a, b); candidates; epsilon).  Stage 1
+        (crs::pairs_above) runs over the slab at threshold - epsilon, stage 2 (crs::pairs_verify) over the fp32 shadow at the
+        threshold.  The ranges are cut into stripes of _join_stripe_rows rows so that no launch exceeds the grid limit; a stripe
+        whose candidates overflow its buffer is re-run once with a buffer of the reported size; more than max_pairs candidates in
+        all raise ValueError naming the count.  One 8-byte readback per stripe launch."""
+        import torch
+        sh = self.collection.shards[0]
+        n = sh.n if n_rows is None else int(n_rows)
+        eps = nat.pairs_epsilon(sh.row_err_max(), sh.pdim)
+        thr1, thr2 = nat.pairs_thresholds(threshold, eps)
+        S = max(nat.PAIRS_TILE, int(self._join_stripe_rows) // nat.PAIRS_TILE * nat.PAIRS_TILE)
+        out_a, out_b, out_s = [], [], []
+        tally = {"stripes": 0, "reruns": 0, "candidates": 0}
+        b_end = b_first + b_rows
+        with torch.cuda.device(sh.device):
+            for b0 in range(b_first, b_end, S):
+                b1 = min(b0 + S, b_end)
+                for a0 in range(0, b1 - 1, S):                       # i < j: rows at or past the stripe's last j pair with nothing
+                    a1 = min(a0 + S, b1 - 1)
+                    cap = max(0, min(int(self._join_first_cap), max_pairs - tally["candidates"]))
+                    pairs, scores, count = nat.pairs_above(sh.slab, n, sh.dim, (a0, a1 - a0), (b0, b1 - b0), thr1, cap)
+                    found = int(count.item())
+                    tally["stripes"] += 1
+                    if tally["candidates"] + found > max_pairs:
+                        raise ValueError(f"near-duplicate join: at least {tally['candidates'] + found} candidate pairs at threshold "
+                                         f"{threshold}, more than max_pairs = {max_pairs}; raise max_pairs or the threshold")
+                    if found > cap:                                  # the stripe overflowed: once more, with room for all of it
+                        tally["reruns"] += 1
+                        pairs, scores, count = nat.pairs_above(sh.slab, n, sh.dim, (a0, a1 - a0), (b0, b1 - b0), thr1, found)
+                        if int(count.item()) != found:
+                            raise nat.NativeError("near-duplicate join: a stripe's candidate count changed between two runs")
+                    tally["candidates"] += found
+                    if found:
+                        ra, rb, sims, kept = nat.pairs_verify(pairs[:found], sh.shadow, n, thr2)
+                        k = int(kept.item())
+                        out_a.append(ra[:k].cpu().numpy()); out_b.append(rb[:k].cpu().numpy()); out_s.append(sims[:k].cpu().numpy())
+        self.last_join = tally
+        a = np.concatenate(out_a) if out_a else np.zeros(0, dtype=np.int64)
+        b = np.concatenate(out_b) if out_b else np.zeros(0, dtype=np.int64)
+        s = np.concatenate(out_s) if out_s else np.zeros(0, dtype=np.float32)
+        order = np.lexsort((b, a))
+        return a[order], b[order], s[order], tally["candidates"], eps
+
+    def _join_range(self, rows, n: int):
+        if rows is None:
+            return 0, n
+        try:
+            first, count = (int(v) for v in rows)
+        except (TypeError, ValueError):
+            raise ValueError(f"rows must be (first, count), got {rows!r}") from None
+        if first < 0 or count < 0 or first + count > n:
+            raise ValueError(f"rows = ({first}, {count}) leaves the collection's {n} rows")
+        return first, count
+
+    def near_duplicates(self, threshold: float, rows=None, max_pairs: int = 1 << 20) -> Dict[str, Any]:
+        """Every pair of rows i < j whose cosine is at least `threshold`, each pair once (a thresholded self-join of the slab,
+        csrc/join.hip).  GUARANTEE: the returned set is exactly {i < j : sim32(i, j) >= threshold}, sim32 being the verify
+        kernel's fp32 dot of the two fp32 shadow rows (a fixed summation order); the fp16 stage runs at threshold - epsilon,
+        epsilon = nat.pairs_epsilon(tracked row error, pdim), so it cannot miss a qualifying pair.
+        rows=(first, count) restricts j to that range (i is any row below j): the incremental form, e.g. the new tail.
+        Returns {'rows_a', 'rows_b' (int64, sidecar rows, sorted by (a, b)), 'similarities' (fp32), 'ids_a', 'ids_b',
+        'candidates' (pairs the fp16 stage listed), 'epsilon'}.  More than max_pairs candidate pairs raise ValueError naming the
+        count -- nothing is truncated silently.  fp16 cosine stores with the fp32 shadow on one device only."""
+        t = self._join_refusals(threshold)
+        if self.collection is None or self.collection.count() == 0:
+            raise ValueError("No collection available. Create index first.")
+        col = self.collection
+        first, count = self._join_range(rows, col.count())
+        a, b, s, cand, eps = self._join(t, first, count, int(max_pairs))
+        return {"rows_a": a, "rows_b": b, "similarities": s, "ids_a": [col.ids[r] for r in a.tolist()],
+                "ids_b": [col.ids[r] for r in b.tolist()], "candidates": cand, "epsilon": eps}
+
+    def duplicate_of(self, threshold: float, rows=None) -> np.ndarray:
+        """int64 [n]: -1 for a kept row, otherwise the kept row it duplicates -- greedy keep-first in row order over the pairs of
+        near_duplicates(threshold, rows) (keep_first).  rows=(first, count): only rows of that range can be dropped."""
+        found = self.near_duplicates(threshold, rows=rows, max_pairs=self.dedup_max_pairs)
+        return keep_first(self.collection.count(), found["rows_a"], found["rows_b"])
+
+    def deduplicate(self, threshold: float) -> int:
+        """Remove every row duplicate_of(threshold) marks, through delete's path: the store is afterwards, row for row, what
+        create_index of the survivors would have built.  Returns the number of rows removed."""
+        dead = np.flatnonzero(self.duplicate_of(threshold) >= 0).astype(np.int64)
+        if dead.size == 0:
+            return 0
+        self._delete_rows(dead)
+        self._mutated(ids_changed=True)
+        return int(dead.size)
+
+    def _drop_new_duplicates(self, start: int, m: int) -> np.ndarray:
+        """create_index with dedup_threshold: the shard already holds the m new rows [start, start + m), the sidecars do not.
+        Joins all rows x the new tail, applies keep-first (old rows always kept), compacts the dropped rows out of the tail and
+        returns their positions in the batch (ascending).  A failure takes the new rows off the shard again."""
+        sh = self.collection.shards[0]
+        try:
+            a, b, _, _, _ = self._join(self._join_refusals(self.dedup_threshold), start, m, self.dedup_max_pairs, n_rows=start + m)
+            dead = np.flatnonzero(keep_first(start + m, a, b) >= 0).astype(np.int64)
+            if dead.size:
+                self._compact_shards(dead)
+            return dead - start
+        except Exception:
+            for arr in (sh.slab, sh.shadow):
+                arr[start: start + m].zero_()
+            sh.n = start
+            raise
 
     def _plan_update(self, ids, embeddings, documents, metadatas):
         """Every check of update(), before anything changes -> (sidecar rows int64 [m], fp32 torch embeddings or None)."""

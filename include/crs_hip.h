@@ -396,6 +396,37 @@ int crs_wordpiece_encode(const uint8_t* text_dev, const int64_t* offsets_dev, in
 int crs_token_match(const float* a_dev, const int32_t* len_a_dev, int seq_a, const float* b_dev, const int32_t* len_b_dev, int seq_b,
                     int n_pairs, int hidden, const float* w_a_dev, const float* w_b_dev, float* out_dev, void* stream);
 
+/* ---- near-duplicate detection: thresholded self-join of the slab (additive to ABI 3; csrc/join.hip) -- no reference
+ * call site: the reference's chunker produces the duplicates (chunk_overlap, repeated boiler-plate), nothing in it removes them ----
+ * crs_pairs_above_f16 (stage 1) finds every pair (i, j) with i in [a_first, a_first + a_rows), j in [b_first, b_first + b_rows),
+ * i < j and slab score <fp16 row i, fp16 row j> >= thr (fp32 accumulation over all crs_padded_dim(dim) elements, the padding being
+ * the zeros the slab holds):
+ *   slab_dev        fp16 [n_rows, crs_padded_dim(dim)], 16-byte aligned (CRS_SLAB_F16 only); both ranges lie inside [0, n_rows)
+ *   pairs_out_dev   int64 [cap, 2], 16-byte aligned: (i, j) of each pair, once;  scores_out_dev fp32 [cap]: its slab score
+ *   count_dev       ONE int64 the caller zeroed: the number of qualifying pairs is ADDED to it whether or not they fitted --
+ *                   count > cap is the overflow signal, nothing is written at or past cap, and which pairs fitted is unspecified
+ * Pair order is unspecified.  A = B = all rows is the whole self-join, A = all rows and B = the new tail the incremental one;
+ * stripes of either bound the buffers and the grid: one launch takes at most CRS_PAIRS_MAX_TILES tile pairs,
+ * ceil(a_rows / CRS_PAIRS_TILE) * (ceil(b_rows / CRS_PAIRS_TILE) rounded up to a multiple of 8) (CRS_EINVAL above that).  One
+ * 512-thread workgroup per 256 x 256 tile pair (v_mfma_f32_16x16x32_f16; tile pairs without an i < j leave at once); a workgroup
+ * with hits issues ONE returned atomic.  An empty range: no launch.  thr must be finite.
+ *
+ * crs_pairs_verify_f32 (stage 2) scores `m` candidate pairs (pairs_dev int64 [m, 2], 16-byte aligned) against the fp32 shadow
+ * [n_rows, dim]: sim32 = one fmaf chain per lane of a quarter wave (lane l: coordinates l, l + 16, ...) and an xor butterfly -- a
+ * fixed order, bitwise independent of m and of the other pairs.  Pairs with sim32 >= thr are compacted into rows_a_dev / rows_b_dev
+ * (int64) / sims_dev (fp32), each [>= m], in unspecified order; their number is ADDED to count_dev (ONE int64 the caller zeroed).
+ * A pair with a row outside [0, n_rows) is dropped, never dereferenced.  m = 0: no launch.
+ *
+ * With thr1 = t - eps for stage 1 and t for stage 2, eps = (2 E + E^2)(1 + 1e-4) + (1.5 pdim + 8) 2^-23 and E the slab's tracked
+ * row error (row_err_max above), the result is exactly {i < j : sim32(i, j) >= t} (DESIGN 3.13 has the derivation).
+ * No workspace, no host synchronisation. */
+#define CRS_PAIRS_TILE 256               /* rows per tile edge of the join (tests aim at the boundaries) */
+#define CRS_PAIRS_MAX_TILES (1 << 22)    /* tile pairs of one crs_pairs_above_f16 launch */
+int crs_pairs_above_f16(const void* slab_dev, int64_t n_rows, int dim, int64_t a_first, int64_t a_rows, int64_t b_first, int64_t b_rows,
+                        float thr, int64_t* pairs_out_dev, float* scores_out_dev, int64_t cap, int64_t* count_dev, void* stream);
+int crs_pairs_verify_f32(const int64_t* pairs_dev, int64_t m, const float* shadow_f32_dev, int64_t n_rows, int dim, float thr,
+                         int64_t* rows_a_dev, int64_t* rows_b_dev, float* sims_dev, int64_t* count_dev, void* stream);
+
 /* ---- one-collective exchange (ONE all-gather per query batch) ------------------
  * A rank's per-shard result travels as one contiguous "wire block":
  *     [ ids int64 [nq, k] | scores fp32 [nq, k] | pad to 8 bytes ]        crs_wire_bytes(nq, k) bytes
