@@ -82,6 +82,10 @@ int set_error(int code, const char* msg) {  // shared with enc_capi.hip
   snprintf(g_err, sizeof g_err, "%s", msg);
   return code;
 }
+int launch_status(const char* what) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? CRS_OK : hip_fail(e, what);
+}
 }  // namespace crs
 
 extern "C" {
@@ -90,28 +94,6 @@ const char* crs_last_error(void) { return g_err; }
 int crs_abi_version(void) { return 3; }
 int crs_row_elems(int dim, int slab_type) { return crs::row_elems(dim, slab_type); }
 int crs_padded_dim(int dim) { return crs_row_elems(dim, CRS_SLAB_F16); }
-
-int crs_slab_append_f32(const float* emb_dev, int64_t n, int dim, int slab_type, void* slab_dev,
-                        float* scales_dev, float* shadow_f32_dev, int64_t row0, float* row_err_max_dev, void* stream) {
-  if (n < 0 || dim <= 0 || dim > 1024 || row0 < 0) return fail(CRS_EINVAL, "bad n/dim/row0");
-  if (slab_type != CRS_SLAB_F16 && slab_type != CRS_SLAB_I8) return fail(CRS_EINVAL, "bad slab_type");
-  if (n == 0) return CRS_OK;
-  if (!emb_dev || !slab_dev) return fail(CRS_EINVAL, "null pointer");
-  if (slab_type == CRS_SLAB_I8 && !scales_dev) return fail(CRS_EINVAL, "int8 slab needs scales");
-  const int e = crs::slab_append_launch(emb_dev, n, dim, crs_row_elems(dim, slab_type), slab_type, slab_dev,
-                                        scales_dev, shadow_f32_dev, row0, row_err_max_dev, (hipStream_t)stream);
-  return e ? hip_fail((hipError_t)e, "slab_append") : CRS_OK;
-}
-
-int crs_queries_to_f16(const float* q_dev, int nq, int dim, int slab_type, void* q16_dev, void* stream) {
-  if (nq < 0 || dim <= 0 || dim > 1024) return fail(CRS_EINVAL, "bad nq/dim");
-  if (slab_type != CRS_SLAB_F16 && slab_type != CRS_SLAB_I8) return fail(CRS_EINVAL, "bad slab_type");
-  if (nq == 0) return CRS_OK;
-  if (!q_dev || !q16_dev) return fail(CRS_EINVAL, "null pointer");
-  const int e = crs::queries_to_f16_launch(q_dev, nq, dim, crs_row_elems(dim, slab_type),
-                                           reinterpret_cast<_Float16*>(q16_dev), (hipStream_t)stream);
-  return e ? hip_fail((hipError_t)e, "queries_to_f16") : CRS_OK;
-}
 
 int crs_scan_workspace_bytes(int nq, int dim, int k, int64_t n_rows, size_t* bytes) {
   if (!bytes) return fail(CRS_EINVAL, "null pointer");

@@ -1,33 +1,15 @@
-// convert.hip -- slab build / query conversion / exact re-score kernels (gfx950, HBM-bound).
+// convert.hip -- exact re-score kernels (gfx950, HBM-bound).
 //
-//   slab_append : fp32 embeddings -> L2-normalised fp16 or int8(+scale) slab rows, optional fp32
-//                 shadow.  Replaces collection.add(embeddings=embeddings.tolist(), ...)
-//                 (reference rag/indexing.py:114-119): no Python lists, no sqlite, one pass.
-//   queries_to_f16 : the same normalise+cast for a query batch (rag/indexing.py:156-168 flatten
-//                 + ChromaDB's cosine-space normalisation).
 //   rescore     : exact fp32 <q, shadow[id]> for over-fetched candidates + per-row re-sort.
+//   refine      : the over-fetch re-rank of one query per workgroup.
 //
-// One wave64 per row; rows are <= 1024 elements so a lane owns <= 16 strided elements.
+// One wave64 per candidate row.
 
 #include "scan.h"
-#include "slab_row.h"
 #include "tail_steps.h"
 
 namespace crs {
 namespace {
-
-// grid: one wave per row, 4 waves per block
-template <bool I8>
-__global__ __launch_bounds__(256) void slab_append_kernel(const float* __restrict__ emb, int64_t n,
-                                                         int dim, int pdim, void* __restrict__ slab,
-                                                         float* __restrict__ scales,
-                                                         float* __restrict__ shadow, int64_t row0,
-                                                         float* __restrict__ row_err_max) {
-  const int lane = threadIdx.x & 63;
-  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= n) return;
-  slab_store_row<I8>(emb + r * dim, dim, pdim, slab, scales, shadow, row0 + r, row_err_max, lane);   // slab_row.h
-}
 
 // one wave per (query, slot)
 __global__ __launch_bounds__(256) void rescore_dot_kernel(const float* __restrict__ q32, int nq,
@@ -109,24 +91,6 @@ int refine_f32_launch(const float* q32, int nq, int dim, const float* shadow, in
   hipLaunchKernelGGL(refine_f32_kernel, dim3(nq), dim3(256), 0, stream, q32, dim, shadow, n_rows, id_base, cand,
                      k_in, k_out, out_s, out_i);
   return (int)hipGetLastError();
-}
-
-int slab_append_launch(const float* emb, int64_t n, int dim, int pdim, int slab_type, void* slab,
-                       float* scales, float* shadow, int64_t row0, float* row_err_max, hipStream_t stream) {
-  if (n <= 0) return 0;
-  const unsigned blocks = (unsigned)((n + 3) / 4);
-  if (slab_type == 1)
-    hipLaunchKernelGGL((slab_append_kernel<true>), dim3(blocks), dim3(256), 0, stream, emb, n, dim,
-                       pdim, slab, scales, shadow, row0, row_err_max);
-  else
-    hipLaunchKernelGGL((slab_append_kernel<false>), dim3(blocks), dim3(256), 0, stream, emb, n, dim,
-                       pdim, slab, scales, shadow, row0, row_err_max);
-  return (int)hipGetLastError();
-}
-
-int queries_to_f16_launch(const float* q, int nq, int dim, int pdim, _Float16* out,
-                          hipStream_t stream) {
-  return slab_append_launch(q, nq, dim, pdim, 0, out, nullptr, nullptr, 0, nullptr, stream);
 }
 
 // fp32 scores of arbitrary candidate lists (any k): out[e] = <q32[e / k], shadow[ids[e] - id_base]>, -inf for ids < 0

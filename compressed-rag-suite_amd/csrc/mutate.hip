@@ -1,8 +1,6 @@
-// mutate.hip -- in-place mutation of a shard's arrays (gfx950, HBM-bound): stable compaction after a delete, and the
-// scatter form of the append for updates.  Declared in include/crs_hip.h (additive to ABI 3).
+// mutate.hip -- in-place mutation of a shard's arrays (gfx950, HBM-bound): stable compaction after a delete.  Declared in
+// include/crs_hip.h (additive to ABI 3).  (The scatter update of rows is a job of row_build.hip.)
 //
-//   write_rows : emb[i] -> row rows[i] of slab / scales / shadow through slab_store_row (slab_row.h), the per-row function
-//                the append kernel calls: same bits as an append of the same vector.
 //   compact    : remove the sorted rows dead[0..m) and close the gaps, keeping the order of the survivors.  Destination
 //                row d is filled from source row s = d + j, j = #{i : dead[i] - i <= d} (dead[i] - i, the number of
 //                survivors below dead[i], is non-decreasing: one binary search per wave, then one probe per row).
@@ -24,14 +22,11 @@
 #include "../../include/crs_hip.h"
 
 #include <hip/hip_runtime.h>
-#include <stdio.h>
 
 #include "scan.h"
-#include "slab_row.h"
+#include "tail_steps.h"   // f32x4
 
 namespace crs {
-int set_error(int code, const char* msg);   // capi.hip (thread-local message of crs_last_error)
-
 namespace {
 
 constexpr int kRowsPerWave = 8;
@@ -39,20 +34,6 @@ constexpr int kWavesPerBlock = 4;
 constexpr int kRowsPerBlock = kRowsPerWave * kWavesPerBlock;
 constexpr int64_t kMinWindowRows = 1024;
 constexpr size_t kSectionAlign = 256;
-
-// grid: one wave per updated row, 4 waves per block
-template <bool I8>
-__global__ __launch_bounds__(256) void slab_write_rows_kernel(const float* __restrict__ emb, const int64_t* __restrict__ rows,
-                                                             int64_t m, int dim, int pdim, void* __restrict__ slab,
-                                                             float* __restrict__ scales, float* __restrict__ shadow,
-                                                             int64_t n_rows, float* __restrict__ row_err_max) {
-  const int lane = threadIdx.x & 63;
-  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= m) return;
-  const int64_t dr = rows[r];
-  if (dr < 0 || dr >= n_rows) return;     // never write outside the shard, whatever the caller passed
-  slab_store_row<I8>(emb + r * dim, dim, pdim, slab, scales, shadow, dr, row_err_max, lane);
-}
 
 // The bounce buffer of one window: four sections, each kSectionAlign-aligned (the shadow section has 16 bytes of room for
 // the mod-16 placement).
@@ -172,39 +153,9 @@ int64_t window_rows(int row_bytes, int dim, bool has_shadow, size_t bounce_bytes
 
 }  // namespace
 
-int slab_write_rows_launch(const float* emb, const int64_t* rows, int64_t m, int dim, int pdim, int slab_type, void* slab, float* scales,
-                           float* shadow, int64_t n_rows, float* row_err_max, hipStream_t stream) {
-  if (m <= 0) return 0;
-  const unsigned blocks = (unsigned)((m + 3) / 4);
-  if (slab_type == 1)
-    hipLaunchKernelGGL((slab_write_rows_kernel<true>), dim3(blocks), dim3(256), 0, stream, emb, rows, m, dim, pdim, slab, scales, shadow,
-                       n_rows, row_err_max);
-  else
-    hipLaunchKernelGGL((slab_write_rows_kernel<false>), dim3(blocks), dim3(256), 0, stream, emb, rows, m, dim, pdim, slab, scales, shadow,
-                       n_rows, row_err_max);
-  return (int)hipGetLastError();
-}
-
 }  // namespace crs
 
 extern "C" {
-
-int crs_slab_write_rows_f32(const float* emb_dev, const int64_t* rows_dev, int64_t m, int dim, int slab_type, void* slab_dev,
-                            float* scales_dev, float* shadow_f32_dev, int64_t n_rows, float* row_err_max_dev, void* stream) {
-  if (m < 0 || dim <= 0 || dim > 1024 || n_rows < 0) return crs::set_error(CRS_EINVAL, "bad m/dim/n_rows");
-  if (slab_type != CRS_SLAB_F16 && slab_type != CRS_SLAB_I8) return crs::set_error(CRS_EINVAL, "bad slab_type");
-  if (m == 0) return CRS_OK;
-  if (!emb_dev || !rows_dev || !slab_dev) return crs::set_error(CRS_EINVAL, "null pointer");
-  if (slab_type == CRS_SLAB_I8 && !scales_dev) return crs::set_error(CRS_EINVAL, "int8 slab needs scales");
-  const int e = crs::slab_write_rows_launch(emb_dev, rows_dev, m, dim, crs_row_elems(dim, slab_type), slab_type, slab_dev, scales_dev,
-                                            shadow_f32_dev, n_rows, row_err_max_dev, (hipStream_t)stream);
-  if (e) {
-    char msg[256];
-    snprintf(msg, sizeof msg, "slab_write_rows: %s", hipGetErrorString((hipError_t)e));
-    return crs::set_error(CRS_EHIP, msg);
-  }
-  return CRS_OK;
-}
 
 size_t crs_slab_compact_bounce_bytes(int dim, int slab_type, int has_shadow) {
   if (dim <= 0 || dim > 1024 || (slab_type != CRS_SLAB_F16 && slab_type != CRS_SLAB_I8)) return 0;
@@ -251,13 +202,7 @@ int crs_slab_compact(const int64_t* dead_dev, int64_t m, int64_t n_rows, int64_t
     hipLaunchKernelGGL((crs::compact_window_kernel<true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
     hipLaunchKernelGGL((crs::compact_window_kernel<false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    char msg[256];
-    snprintf(msg, sizeof msg, "slab_compact: %s", hipGetErrorString(e));
-    return crs::set_error(CRS_EHIP, msg);
-  }
-  return CRS_OK;
+  return crs::launch_status("slab_compact");
 }
 
 }  // extern "C"

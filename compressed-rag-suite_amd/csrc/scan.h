@@ -7,6 +7,11 @@
 
 namespace crs {
 
+// capi.hip: the thread-local message of crs_last_error.  set_error returns `code`; launch_status turns hipGetLastError() after the
+// launches of `what` into CRS_OK or CRS_EHIP ("what: <HIP's text>")
+int set_error(int code, const char* msg);
+int launch_status(const char* what);
+
 struct ScanArgs {
   const _Float16* q;      // [nq, D] fp16, zero padded to D
   const void* slab;       // [n_rows, D] fp16 (or int8)
@@ -119,9 +124,6 @@ int pairs_verify_launch(const int64_t* pairs, int64_t m, const float* shadow, in
 // convert.hip
 int refine_f32_launch(const float* q32, int nq, int dim, const float* shadow, int64_t n_rows, int64_t id_base,
                       const int64_t* cand, int k_in, int k_out, float* out_s, int64_t* out_i, hipStream_t stream);
-int slab_append_launch(const float* emb, int64_t n, int dim, int pdim, int slab_type, void* slab,
-                       float* scales, float* shadow, int64_t row0, float* row_err_max, hipStream_t stream);
-int queries_to_f16_launch(const float* q, int nq, int dim, int pdim, _Float16* out, hipStream_t stream);
 int score_rows_launch(const float* q32, int nq, int dim, const float* shadow, int64_t n_rows, int64_t id_base, int k, const int64_t* ids,
                       float* scores, hipStream_t stream);
 int rescore_launch(const float* q32, int nq, int dim, const float* shadow, int64_t n_rows,

@@ -5,8 +5,8 @@
 // with hnsw:space 'ip' / 'l2' keeps one scale R = 2^e >= every row norm it has seen (a device fp32 the kernels read, so a captured
 // graph stays valid when it grows) and transforms rows on the way in, queries on the way in and distances on the way out:
 //   rows_norm_max     fp32 [n, d] -> the largest |x|_2, atomicMax on the bit pattern (non-negative floats order like their bits)
-//   append / write    x -> u = x / R (ip) or (v, t) = (x / 2R, fl(sum v^2)) (l2) through slab_store_row_space (space_row.h)
-//   rescale           R grew by 2^j: shadow rows times 2^-j (t: recomputed, = times 2^-2j), slab rows rebuilt from them
+//   append / write    x -> u = x / R (ip) or (v, t) = (x / 2R, fl(sum v^2)) (l2): jobs of row_build.hip, rows by slab_store_row
+//   rescale           R grew by 2^j: shadow rows times 2^-j (t: recomputed, = times 2^-2j), slab rows rebuilt from them (likewise)
 //   queries_to_space  q -> unit fp32 [nq, d'] and fp16 [nq, pdim]: q / |q| (ip), (q / R, -1) / |.| (l2)
 //   space_distances   the certified list's rows -> 1 - <q, x> (ip) or sum (q - x)^2 (l2) from the recovered x = R u / 2R v, in
 //                     fp32, ordered (distance asc, row asc)
@@ -15,14 +15,11 @@
 #include "../../include/crs_hip.h"
 
 #include <hip/hip_runtime.h>
-#include <stdio.h>
 
 #include "scan.h"
-#include "space_row.h"
+#include "tail_steps.h"
 
 namespace crs {
-int set_error(int code, const char* msg);   // capi.hip (thread-local message of crs_last_error)
-
 namespace {
 
 constexpr int kDistMaxK = CRS_MAX_K_CERT;
@@ -46,52 +43,6 @@ __global__ __launch_bounds__(256) void rows_norm_max_kernel(const float* __restr
   }
 }
 
-// the multiplier of a caller's vector under scale R: 1/R (ip), 1/(2R) (l2); exact, R is a power of two
-template <int SPACE>
-__device__ __forceinline__ float row_mul(const float* __restrict__ norm_scale) {
-  return (SPACE == kSpaceL2 ? 0.5f : 1.0f) / *norm_scale;
-}
-
-// grid: one wave per row, 4 waves per block
-template <bool I8, int SPACE>
-__global__ __launch_bounds__(256) void slab_append_space_kernel(const float* __restrict__ emb, int64_t n, int dim, int pdim,
-                                                               const float* __restrict__ norm_scale, void* __restrict__ slab,
-                                                               float* __restrict__ scales, float* __restrict__ shadow, int64_t row0,
-                                                               float* __restrict__ row_err_max) {
-  const int lane = threadIdx.x & 63;
-  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= n) return;
-  slab_store_row_space<I8, SPACE>(emb + r * dim, dim, row_mul<SPACE>(norm_scale), pdim, slab, scales, shadow, row0 + r, row_err_max, lane);
-}
-
-// the scatter twin (slab_write_rows_kernel, mutate.hip): one wave per updated row
-template <bool I8, int SPACE>
-__global__ __launch_bounds__(256) void slab_write_rows_space_kernel(const float* __restrict__ emb, const int64_t* __restrict__ rows,
-                                                                   int64_t m, int dim, int pdim, const float* __restrict__ norm_scale,
-                                                                   void* __restrict__ slab, float* __restrict__ scales,
-                                                                   float* __restrict__ shadow, int64_t n_rows,
-                                                                   float* __restrict__ row_err_max) {
-  const int lane = threadIdx.x & 63;
-  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= m) return;
-  const int64_t dr = rows[r];
-  if (dr < 0 || dr >= n_rows) return;     // never write outside the shard, whatever the caller passed
-  slab_store_row_space<I8, SPACE>(emb + r * dim, dim, row_mul<SPACE>(norm_scale), pdim, slab, scales, shadow, dr, row_err_max, lane);
-}
-
-// rows [0, n): shadow row times `factor` (an exact power of two), slab row and int8 scale rebuilt from it.  The source IS the
-// shadow row (no __restrict__ on it here or in slab_store_row_space).
-template <bool I8, int SPACE>
-__global__ __launch_bounds__(256) void slab_rescale_space_kernel(int64_t n, int dim, int pdim, float factor, void* __restrict__ slab,
-                                                                float* __restrict__ scales, float* shadow,
-                                                                float* __restrict__ row_err_max) {
-  const int lane = threadIdx.x & 63;
-  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= n) return;
-  const int sdim = dim + (SPACE == kSpaceL2 ? 1 : 0);
-  slab_store_row_space<I8, SPACE>(shadow + r * sdim, dim, factor, pdim, slab, scales, shadow, r, row_err_max, lane);
-}
-
 // one wave per query: unit fp32 [nq, sdim] and fp16 [nq, pdim], zero padded
 template <int SPACE>
 __global__ __launch_bounds__(256) void queries_to_space_kernel(const float* __restrict__ q, int nq, int dim, int pdim,
@@ -100,8 +51,8 @@ __global__ __launch_bounds__(256) void queries_to_space_kernel(const float* __re
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= nq) return;
-  const int sdim = dim + (SPACE == kSpaceL2 ? 1 : 0);
-  const float mul = SPACE == kSpaceL2 ? 1.0f / *norm_scale : 1.0f;     // l2: p = q / R (exact)
+  const int sdim = dim + (SPACE == CRS_SPACE_L2 ? 1 : 0);
+  const float mul = SPACE == CRS_SPACE_L2 ? 1.0f / *norm_scale : 1.0f;     // l2: p = q / R (exact)
   const float* src = q + (size_t)r * dim;
   float ss = 0.f;
   for (int c = lane; c < dim; c += 64) {
@@ -109,12 +60,12 @@ __global__ __launch_bounds__(256) void queries_to_space_kernel(const float* __re
     ss = fmaf(x, x, ss);
   }
   ss = wsum(ss);
-  if (SPACE == kSpaceL2) ss += 1.0f;                                    // the appended -1
+  if (SPACE == CRS_SPACE_L2) ss += 1.0f;                                    // the appended -1
   const float den = fmaxf(sqrtf(ss), 1e-12f);
   for (int c = lane; c < pdim; c += 64) {
     float x = 0.f;
     if (c < dim) x = (src[c] * mul) / den;
-    else if (SPACE == kSpaceL2 && c == dim) x = -1.0f / den;
+    else if (SPACE == CRS_SPACE_L2 && c == dim) x = -1.0f / den;
     if (c < sdim) out32[(size_t)r * sdim + c] = x;
     out16[(size_t)r * pdim + c] = (_Float16)x;
   }
@@ -133,8 +84,8 @@ __global__ __launch_bounds__(256) void space_distances_kernel(const float* __res
   __shared__ int64_t sh_i[kDistMaxK];
   const int qi = blockIdx.x;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int sdim = dim + (SPACE == kSpaceL2 ? 1 : 0);
-  const float back = (SPACE == kSpaceL2 ? 2.0f : 1.0f) * *norm_scale;
+  const int sdim = dim + (SPACE == CRS_SPACE_L2 ? 1 : 0);
+  const float back = (SPACE == CRS_SPACE_L2 ? 2.0f : 1.0f) * *norm_scale;
   const float* a = q + (size_t)qi * dim;
   for (int c = wave; c < k; c += 4) {
     const int64_t id = ids[(size_t)qi * k + c];
@@ -145,13 +96,13 @@ __global__ __launch_bounds__(256) void space_distances_kernel(const float* __res
       const float* b = shadow + (size_t)row * sdim;
       for (int e = lane; e < dim; e += 64) {
         const float x = b[e] * back;
-        if (SPACE == kSpaceL2) { const float df = a[e] - x; acc = fmaf(df, df, acc); }
+        if (SPACE == CRS_SPACE_L2) { const float df = a[e] - x; acc = fmaf(df, df, acc); }
         else acc = fmaf(a[e], x, acc);
       }
       acc = wsum(acc);
     }
     if (lane == 0) {
-      sh_d[c] = ok ? (SPACE == kSpaceL2 ? acc : 1.0f - acc) : __builtin_huge_valf();
+      sh_d[c] = ok ? (SPACE == CRS_SPACE_L2 ? acc : 1.0f - acc) : __builtin_huge_valf();
       sh_i[c] = ok ? id : (int64_t)-1;
     }
   }
@@ -179,26 +130,6 @@ bool bad_slab(int slab_type) { return slab_type != CRS_SLAB_F16 && slab_type != 
 // the caller's dimension: 1 .. 1024 (ip), 1 .. 1023 (l2: the stored row has one more coordinate)
 bool bad_dim(int dim, int space) { return dim <= 0 || dim + (space == CRS_SPACE_L2 ? 1 : 0) > 1024; }
 
-int finish(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return CRS_OK;
-  char msg[256];
-  snprintf(msg, sizeof msg, "%s: %s", what, hipGetErrorString(e));
-  return set_error(CRS_EHIP, msg);
-}
-
-// launch K<I8, SPACE> for the run-time (slab_type, space)
-#define CRS_SPACE_DISPATCH(KERNEL, slab_type, space, blocks, stream, ...)                                                           \
-  do {                                                                                                                              \
-    if ((slab_type) == CRS_SLAB_I8) {                                                                                               \
-      if ((space) == CRS_SPACE_L2) hipLaunchKernelGGL((KERNEL<true, crs::kSpaceL2>), dim3(blocks), dim3(256), 0, stream, __VA_ARGS__);  \
-      else hipLaunchKernelGGL((KERNEL<true, crs::kSpaceIP>), dim3(blocks), dim3(256), 0, stream, __VA_ARGS__);                          \
-    } else {                                                                                                                        \
-      if ((space) == CRS_SPACE_L2) hipLaunchKernelGGL((KERNEL<false, crs::kSpaceL2>), dim3(blocks), dim3(256), 0, stream, __VA_ARGS__); \
-      else hipLaunchKernelGGL((KERNEL<false, crs::kSpaceIP>), dim3(blocks), dim3(256), 0, stream, __VA_ARGS__);                         \
-    }                                                                                                                               \
-  } while (0)
-
 }  // namespace
 }  // namespace crs
 
@@ -216,56 +147,7 @@ int crs_rows_norm_max(const float* emb_dev, int64_t n, int dim, float* norm_max_
   if (!emb_dev || !norm_max_dev) return crs::set_error(CRS_EINVAL, "null pointer");
   hipLaunchKernelGGL(crs::rows_norm_max_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, emb_dev, n, dim,
                      norm_max_dev, flag_dev);
-  return crs::finish("rows_norm_max");
-}
-
-int crs_slab_append_space_f32(const float* emb_dev, int64_t n, int dim, int space, int slab_type, const float* norm_scale_dev,
-                              void* slab_dev, float* scales_dev, float* shadow_f32_dev, int64_t row0, float* row_err_max_dev,
-                              void* stream) {
-  if (crs::bad_space(space)) return crs::set_error(CRS_EINVAL, "bad space (CRS_SPACE_IP or CRS_SPACE_L2)");
-  if (n < 0 || crs::bad_dim(dim, space) || row0 < 0) return crs::set_error(CRS_EINVAL, "bad n/dim/row0");
-  if (crs::bad_slab(slab_type)) return crs::set_error(CRS_EINVAL, "bad slab_type");
-  if (n == 0) return CRS_OK;
-  if (!emb_dev || !slab_dev || !norm_scale_dev) return crs::set_error(CRS_EINVAL, "null pointer");
-  if (slab_type == CRS_SLAB_I8 && !scales_dev) return crs::set_error(CRS_EINVAL, "int8 slab needs scales");
-  const int pdim = crs_row_elems(crs_space_row_dim(dim, space), slab_type);
-  const unsigned blocks = (unsigned)((n + 3) / 4);
-  CRS_SPACE_DISPATCH(crs::slab_append_space_kernel, slab_type, space, blocks, (hipStream_t)stream, emb_dev, n, dim, pdim, norm_scale_dev,
-                     slab_dev, scales_dev, shadow_f32_dev, row0, row_err_max_dev);
-  return crs::finish("slab_append_space");
-}
-
-int crs_slab_write_rows_space_f32(const float* emb_dev, const int64_t* rows_dev, int64_t m, int dim, int space, int slab_type,
-                                  const float* norm_scale_dev, void* slab_dev, float* scales_dev, float* shadow_f32_dev, int64_t n_rows,
-                                  float* row_err_max_dev, void* stream) {
-  if (crs::bad_space(space)) return crs::set_error(CRS_EINVAL, "bad space (CRS_SPACE_IP or CRS_SPACE_L2)");
-  if (m < 0 || crs::bad_dim(dim, space) || n_rows < 0) return crs::set_error(CRS_EINVAL, "bad m/dim/n_rows");
-  if (crs::bad_slab(slab_type)) return crs::set_error(CRS_EINVAL, "bad slab_type");
-  if (m == 0) return CRS_OK;
-  if (!emb_dev || !rows_dev || !slab_dev || !norm_scale_dev) return crs::set_error(CRS_EINVAL, "null pointer");
-  if (slab_type == CRS_SLAB_I8 && !scales_dev) return crs::set_error(CRS_EINVAL, "int8 slab needs scales");
-  const int pdim = crs_row_elems(crs_space_row_dim(dim, space), slab_type);
-  const unsigned blocks = (unsigned)((m + 3) / 4);
-  CRS_SPACE_DISPATCH(crs::slab_write_rows_space_kernel, slab_type, space, blocks, (hipStream_t)stream, emb_dev, rows_dev, m, dim, pdim,
-                     norm_scale_dev, slab_dev, scales_dev, shadow_f32_dev, n_rows, row_err_max_dev);
-  return crs::finish("slab_write_rows_space");
-}
-
-int crs_slab_rescale_space(int64_t n_rows, int dim, int space, int slab_type, int shift, void* slab_dev, float* scales_dev,
-                           float* shadow_f32_dev, float* row_err_max_dev, void* stream) {
-  if (crs::bad_space(space)) return crs::set_error(CRS_EINVAL, "bad space (CRS_SPACE_IP or CRS_SPACE_L2)");
-  if (n_rows < 0 || crs::bad_dim(dim, space)) return crs::set_error(CRS_EINVAL, "bad n_rows/dim");
-  if (crs::bad_slab(slab_type)) return crs::set_error(CRS_EINVAL, "bad slab_type");
-  if (shift < 0 || shift > 126) return crs::set_error(CRS_EINVAL, "shift must be in 0..126");
-  if (n_rows == 0 || shift == 0) return CRS_OK;
-  if (!slab_dev || !shadow_f32_dev) return crs::set_error(CRS_EINVAL, "null pointer (the rescale reads the fp32 shadow)");
-  if (slab_type == CRS_SLAB_I8 && !scales_dev) return crs::set_error(CRS_EINVAL, "int8 slab needs scales");
-  const int pdim = crs_row_elems(crs_space_row_dim(dim, space), slab_type);
-  const float factor = __builtin_ldexpf(1.0f, -shift);
-  const unsigned blocks = (unsigned)((n_rows + 3) / 4);
-  CRS_SPACE_DISPATCH(crs::slab_rescale_space_kernel, slab_type, space, blocks, (hipStream_t)stream, n_rows, dim, pdim, factor, slab_dev,
-                     scales_dev, shadow_f32_dev, row_err_max_dev);
-  return crs::finish("slab_rescale_space");
+  return crs::launch_status("rows_norm_max");
 }
 
 int crs_queries_to_space(const float* q_dev, int nq, int dim, int space, int slab_type, const float* norm_scale_dev, float* q32_dev,
@@ -278,12 +160,12 @@ int crs_queries_to_space(const float* q_dev, int nq, int dim, int space, int sla
   const int pdim = crs_row_elems(crs_space_row_dim(dim, space), slab_type);
   const unsigned blocks = (unsigned)((nq + 3) / 4);
   if (space == CRS_SPACE_L2)
-    hipLaunchKernelGGL((crs::queries_to_space_kernel<crs::kSpaceL2>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, q_dev, nq, dim, pdim,
+    hipLaunchKernelGGL((crs::queries_to_space_kernel<CRS_SPACE_L2>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, q_dev, nq, dim, pdim,
                        norm_scale_dev, q32_dev, reinterpret_cast<_Float16*>(q16_dev));
   else
-    hipLaunchKernelGGL((crs::queries_to_space_kernel<crs::kSpaceIP>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, q_dev, nq, dim, pdim,
+    hipLaunchKernelGGL((crs::queries_to_space_kernel<CRS_SPACE_IP>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, q_dev, nq, dim, pdim,
                        norm_scale_dev, q32_dev, reinterpret_cast<_Float16*>(q16_dev));
-  return crs::finish("queries_to_space");
+  return crs::launch_status("queries_to_space");
 }
 
 int crs_space_distances(const float* q_dev, int nq, int dim, int space, const float* shadow_f32_dev, int64_t n_rows, int64_t id_base,
@@ -297,12 +179,12 @@ int crs_space_distances(const float* q_dev, int nq, int dim, int space, const fl
     return crs::set_error(CRS_EINVAL, "null pointer");
   if (ids_dev == out_ids_dev) return crs::set_error(CRS_EINVAL, "out_ids must not be ids");
   if (space == CRS_SPACE_L2)
-    hipLaunchKernelGGL((crs::space_distances_kernel<crs::kSpaceL2>), dim3(nq), dim3(256), 0, (hipStream_t)stream, q_dev, dim,
+    hipLaunchKernelGGL((crs::space_distances_kernel<CRS_SPACE_L2>), dim3(nq), dim3(256), 0, (hipStream_t)stream, q_dev, dim,
                        shadow_f32_dev, n_rows, id_base, norm_scale_dev, ids_dev, k, out_dist_dev, out_ids_dev);
   else
-    hipLaunchKernelGGL((crs::space_distances_kernel<crs::kSpaceIP>), dim3(nq), dim3(256), 0, (hipStream_t)stream, q_dev, dim,
+    hipLaunchKernelGGL((crs::space_distances_kernel<CRS_SPACE_IP>), dim3(nq), dim3(256), 0, (hipStream_t)stream, q_dev, dim,
                        shadow_f32_dev, n_rows, id_base, norm_scale_dev, ids_dev, k, out_dist_dev, out_ids_dev);
-  return crs::finish("space_distances");
+  return crs::launch_status("space_distances");
 }
 
 }  // extern "C"

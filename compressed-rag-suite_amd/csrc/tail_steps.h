@@ -228,7 +228,7 @@ __device__ __forceinline__ void tile_rescore_f16(const f16x8 (&qf)[D / 32], cons
 //     |.| <= dq (1 + E) + |q| E + arith
 //     dq    = |q16 - q|_2 computed from the very two query blocks the scan and the re-rank read
 //             (+ sqrt(pdim) max|q16| / 65024 for int8 slabs: the scan moves the query to 16-bit fixed point, scan_i8.hip)
-//     E     = max over the shard's rows of |c^_j - c_j|_2, tracked by slab_append (convert.hip) in a device scalar
+//     E     = max over the shard's rows of |c^_j - c_j|_2, tracked by slab_store_row (slab_row.h) in a device scalar
 //     arith = (1.5 pdim + 8) 2^-23: pdim exact products summed in fp32 in any order with truncation (<= pdim 2^-23
 //             sum |a_i b_i| <= pdim 2^-23) plus the fp32 FMA chain of the re-rank (<= dim 2^-24 + the butterfly)
 //

@@ -4,11 +4,11 @@
 // ops".  TORCH_LIBRARY(crs, ...) registers, for the HIP ("CUDA" dispatch key on torch-ROCm) backend:
 //   crs::encoder_forward   replaces SentenceTransformer.encode's forward      (reference rag/embedding.py:65-71)
 //   crs::slab_append       replaces collection.add(embeddings=...)            (reference rag/indexing.py:114-119)
-//   crs::slab_write_rows / crs::slab_compact   in-place update and delete of rows (csrc/mutate.hip; the reference's ChromaDB
-//                          collection offers update / delete, its own code never calls them)
+//   crs::slab_write_rows / crs::slab_compact   in-place update and delete of rows (csrc/row_build.hip, csrc/mutate.hip; the
+//                          reference's ChromaDB collection offers update / delete, its own code never calls them)
 //   crs::queries_to_f16    query side of the same conversion                  (reference rag/indexing.py:156-168)
 //   crs::rows_norm_max / slab_append_space / slab_write_rows_space / slab_rescale_space / queries_to_space / space_distances
-//                          hnsw:space 'ip' and 'l2' on the same scan (csrc/space.hip; ChromaDB's spaces, reference rag/indexing.py:83)
+//                          hnsw:space 'ip' and 'l2' on the same scan (csrc/row_build.hip, csrc/space.hip; ChromaDB's spaces, reference rag/indexing.py:83)
 //   crs::cosine_topk       replaces collection.query(query_embeddings, n)     (reference rag/indexing.py:171-176)
 //   crs::refine_f32        over-fetch re-rank against the fp32 shadow         
 //   crs::refine_f32_cert / crs::escalate_exact   the same with a per-query exactness proof, and the in-stream
@@ -69,59 +69,57 @@ int slab_type_of(const Tensor& slab) {
   return slab.scalar_type() == at::kChar ? CRS_SLAB_I8 : CRS_SLAB_F16;
 }
 
-// ---- index build ---------------------------------------------------------------------------------------------
+// ---- index build and row updates (csrc/row_build.hip) --------------------------------------------------------------
+// the checks every row writer shares: row_err, and slab / scales / shadow shaped for `rows` rows of the space's stored dimension
+int row_writer_checks(int64_t dim, int64_t space, const Tensor& slab, const c10::optional<Tensor>& scales, const c10::optional<Tensor>& shadow,
+                      const c10::optional<Tensor>& row_err, int64_t rows) {
+  if (has(row_err)) { want(*row_err, at::kFloat, "row_err"); TORCH_CHECK(row_err->numel() >= 1, "row_err must hold one fp32"); }
+  TORCH_CHECK(slab.dim() == 2 && slab.is_cuda() && slab.is_contiguous(), "slab [cap, pdim]");
+  const int st = slab_type_of(slab);
+  TORCH_CHECK(dim > 0 && dim <= 1024, "bad dim");
+  const int sdim = crs_space_row_dim((int)dim, (int)space);
+  TORCH_CHECK(sdim > 0 && sdim <= 1024, "dim out of range for this space");
+  TORCH_CHECK(slab.size(1) == crs_row_elems(sdim, st), "slab row length must be crs_row_elems(crs_space_row_dim(dim, space), slab_type)");
+  TORCH_CHECK(rows >= 0 && rows <= slab.size(0), "rows exceed the slab");
+  if (st == CRS_SLAB_I8) {
+    TORCH_CHECK(has(scales), "int8 slab needs scales");
+    want(*scales, at::kFloat, "scales");
+    TORCH_CHECK(scales->numel() >= rows, "scales too short");
+  }
+  if (has(shadow)) {
+    want(*shadow, at::kFloat, "shadow");
+    TORCH_CHECK(shadow->dim() == 2 && shadow->size(1) == sdim && shadow->size(0) >= rows, "shadow must be fp32 [>= rows, crs_space_row_dim]");
+  }
+  return st;
+}
+
 void slab_append(const Tensor& emb, Tensor slab, c10::optional<Tensor> scales, c10::optional<Tensor> shadow, int64_t row0,
                  c10::optional<Tensor> row_err) {
   want(emb, at::kFloat, "emb");
   same_device(emb, {&slab, opt_t(scales), opt_t(shadow), opt_t(row_err)}, "crs::slab_append");
-  if (has(row_err)) { want(*row_err, at::kFloat, "row_err"); TORCH_CHECK(row_err->numel() >= 1, "row_err must hold one fp32"); }
-  TORCH_CHECK(emb.dim() == 2 && slab.dim() == 2 && slab.is_cuda() && slab.is_contiguous(), "emb [n, dim], slab [cap, pdim]");
-  const int st = slab_type_of(slab);
+  TORCH_CHECK(emb.dim() == 2 && row0 >= 0, "emb [n, dim], row0 >= 0");
   const int64_t n = emb.size(0);
   const int dim = (int)emb.size(1);
-  TORCH_CHECK(slab.size(1) == crs_row_elems(dim, st), "slab row length must be crs_row_elems(dim, slab_type)");
-  TORCH_CHECK(row0 >= 0 && row0 + n <= slab.size(0), "rows [row0, row0 + n) exceed the slab");
-  if (st == CRS_SLAB_I8) {
-    TORCH_CHECK(scales.has_value(), "int8 slab needs scales");
-    want(*scales, at::kFloat, "scales");
-    TORCH_CHECK(scales->numel() >= row0 + n, "scales too short");
-  }
-  if (shadow.has_value() && shadow->defined()) {
-    want(*shadow, at::kFloat, "shadow");
-    TORCH_CHECK(shadow->dim() == 2 && shadow->size(1) == dim && shadow->size(0) >= row0 + n, "shadow must be fp32 [>= row0 + n, dim]");
-  }
+  const int st = row_writer_checks(dim, CRS_SPACE_COSINE, slab, scales, shadow, row_err, row0 + n);
   c10::hip::HIPGuardMasqueradingAsCUDA g(emb.device());
   ok(crs_slab_append_f32(emb.data_ptr<float>(), n, dim, st, slab.data_ptr(), (float*)opt_ptr(scales), (float*)opt_ptr(shadow), row0,
                          (float*)opt_ptr(row_err), cur_stream(emb)), "crs::slab_append");
 }
 
-// ---- in-place mutation (csrc/mutate.hip) ------------------------------------------------------------------------
 void slab_write_rows(const Tensor& emb, const Tensor& rows, Tensor slab, c10::optional<Tensor> scales, c10::optional<Tensor> shadow,
                      int64_t n_rows, c10::optional<Tensor> row_err) {
   want(emb, at::kFloat, "emb");
   want(rows, at::kLong, "rows");
   same_device(emb, {&rows, &slab, opt_t(scales), opt_t(shadow), opt_t(row_err)}, "crs::slab_write_rows");
-  if (has(row_err)) { want(*row_err, at::kFloat, "row_err"); TORCH_CHECK(row_err->numel() >= 1, "row_err must hold one fp32"); }
-  TORCH_CHECK(emb.dim() == 2 && slab.dim() == 2 && slab.is_cuda() && slab.is_contiguous(), "emb [m, dim], slab [cap, pdim]");
-  TORCH_CHECK(rows.dim() == 1 && rows.size(0) == emb.size(0), "rows must be int64 [m]");
-  const int st = slab_type_of(slab);
+  TORCH_CHECK(emb.dim() == 2 && rows.dim() == 1 && rows.size(0) == emb.size(0), "emb [m, dim], rows int64 [m]");
   const int dim = (int)emb.size(1);
-  TORCH_CHECK(slab.size(1) == crs_row_elems(dim, st), "slab row length must be crs_row_elems(dim, slab_type)");
-  TORCH_CHECK(n_rows >= 0 && n_rows <= slab.size(0), "n_rows exceeds the slab");
-  if (st == CRS_SLAB_I8) {
-    TORCH_CHECK(has(scales), "int8 slab needs scales");
-    want(*scales, at::kFloat, "scales");
-    TORCH_CHECK(scales->numel() >= n_rows, "scales too short");
-  }
-  if (has(shadow)) {
-    want(*shadow, at::kFloat, "shadow");
-    TORCH_CHECK(shadow->dim() == 2 && shadow->size(1) == dim && shadow->size(0) >= n_rows, "shadow must be fp32 [>= n_rows, dim]");
-  }
+  const int st = row_writer_checks(dim, CRS_SPACE_COSINE, slab, scales, shadow, row_err, n_rows);
   c10::hip::HIPGuardMasqueradingAsCUDA g(emb.device());
   ok(crs_slab_write_rows_f32(emb.data_ptr<float>(), rows.data_ptr<int64_t>(), emb.size(0), dim, st, slab.data_ptr(), (float*)opt_ptr(scales),
                              (float*)opt_ptr(shadow), n_rows, (float*)opt_ptr(row_err), cur_stream(emb)), "crs::slab_write_rows");
 }
 
+// ---- in-place mutation (csrc/mutate.hip) ------------------------------------------------------------------------
 void slab_compact(const Tensor& dead, int64_t n_rows, Tensor slab, c10::optional<Tensor> scales, c10::optional<Tensor> shadow,
                   c10::optional<Tensor> rows_global, Tensor bounce, int64_t first_row) {
   want(dead, at::kLong, "dead");
@@ -156,34 +154,12 @@ void queries_to_f16(const Tensor& q32, Tensor out16, int64_t slab_type) {
      "crs::queries_to_f16");
 }
 
-// ---- inner-product / squared-L2 spaces (csrc/space.hip; include/crs_hip.h holds the contracts) ------------------------------------
+// ---- inner-product / squared-L2 spaces (csrc/row_build.hip, csrc/space.hip; include/crs_hip.h holds the contracts) --------------
 void want_scale(const Tensor& norm_scale) {
   want(norm_scale, at::kFloat, "norm_scale");
   TORCH_CHECK(norm_scale.numel() >= 1, "norm_scale must hold one fp32");
 }
 void want_space(int64_t space) { TORCH_CHECK(space == CRS_SPACE_IP || space == CRS_SPACE_L2, "space must be CRS_SPACE_IP or CRS_SPACE_L2"); }
-
-// the checks every space row writer shares: slab / scales / shadow shaped for `rows` rows of the transformed dimension
-int space_slab_checks(int dim, int64_t space, const Tensor& slab, const c10::optional<Tensor>& scales, const c10::optional<Tensor>& shadow,
-                      int64_t rows) {
-  want_space(space);
-  TORCH_CHECK(slab.dim() == 2 && slab.is_cuda() && slab.is_contiguous(), "slab [cap, pdim]");
-  const int st = slab_type_of(slab);
-  const int sdim = crs_space_row_dim(dim, (int)space);
-  TORCH_CHECK(sdim > 0 && sdim <= 1024, "dim out of range for this space");
-  TORCH_CHECK(slab.size(1) == crs_row_elems(sdim, st), "slab row length must be crs_row_elems(crs_space_row_dim(dim, space), slab_type)");
-  TORCH_CHECK(rows >= 0 && rows <= slab.size(0), "rows exceed the slab");
-  if (st == CRS_SLAB_I8) {
-    TORCH_CHECK(has(scales), "int8 slab needs scales");
-    want(*scales, at::kFloat, "scales");
-    TORCH_CHECK(scales->numel() >= rows, "scales too short");
-  }
-  if (has(shadow)) {
-    want(*shadow, at::kFloat, "shadow");
-    TORCH_CHECK(shadow->dim() == 2 && shadow->size(1) == sdim && shadow->size(0) >= rows, "shadow must be fp32 [>= rows, crs_space_row_dim]");
-  }
-  return st;
-}
 
 void rows_norm_max(const Tensor& emb, Tensor norm_max) {
   want(emb, at::kFloat, "emb");
@@ -200,10 +176,10 @@ void slab_append_space(const Tensor& emb, int64_t space, const Tensor& norm_scal
   want(emb, at::kFloat, "emb");
   want_scale(norm_scale);
   same_device(emb, {&norm_scale, &slab, opt_t(scales), opt_t(shadow), opt_t(row_err)}, "crs::slab_append_space");
-  if (has(row_err)) { want(*row_err, at::kFloat, "row_err"); TORCH_CHECK(row_err->numel() >= 1, "row_err must hold one fp32"); }
+  want_space(space);
   TORCH_CHECK(emb.dim() == 2 && row0 >= 0, "emb [n, dim], row0 >= 0");
   const int dim = (int)emb.size(1);
-  const int st = space_slab_checks(dim, space, slab, scales, shadow, row0 + emb.size(0));
+  const int st = row_writer_checks(dim, space, slab, scales, shadow, row_err, row0 + emb.size(0));
   c10::hip::HIPGuardMasqueradingAsCUDA g(emb.device());
   ok(crs_slab_append_space_f32(emb.data_ptr<float>(), emb.size(0), dim, (int)space, st, norm_scale.data_ptr<float>(), slab.data_ptr(),
                                (float*)opt_ptr(scales), (float*)opt_ptr(shadow), row0, (float*)opt_ptr(row_err), cur_stream(emb)),
@@ -216,10 +192,10 @@ void slab_write_rows_space(const Tensor& emb, const Tensor& rows, int64_t space,
   want(rows, at::kLong, "rows");
   want_scale(norm_scale);
   same_device(emb, {&rows, &norm_scale, &slab, opt_t(scales), opt_t(shadow), opt_t(row_err)}, "crs::slab_write_rows_space");
-  if (has(row_err)) { want(*row_err, at::kFloat, "row_err"); TORCH_CHECK(row_err->numel() >= 1, "row_err must hold one fp32"); }
+  want_space(space);
   TORCH_CHECK(emb.dim() == 2 && rows.dim() == 1 && rows.size(0) == emb.size(0), "emb [m, dim], rows int64 [m]");
   const int dim = (int)emb.size(1);
-  const int st = space_slab_checks(dim, space, slab, scales, shadow, n_rows);
+  const int st = row_writer_checks(dim, space, slab, scales, shadow, row_err, n_rows);
   c10::hip::HIPGuardMasqueradingAsCUDA g(emb.device());
   ok(crs_slab_write_rows_space_f32(emb.data_ptr<float>(), rows.data_ptr<int64_t>(), emb.size(0), dim, (int)space, st,
                                    norm_scale.data_ptr<float>(), slab.data_ptr(), (float*)opt_ptr(scales), (float*)opt_ptr(shadow), n_rows,
@@ -229,9 +205,8 @@ void slab_write_rows_space(const Tensor& emb, const Tensor& rows, int64_t space,
 void slab_rescale_space(int64_t n_rows, int64_t dim, int64_t space, int64_t shift, Tensor slab, c10::optional<Tensor> scales, Tensor shadow,
                         c10::optional<Tensor> row_err) {
   same_device(slab, {opt_t(scales), &shadow, opt_t(row_err)}, "crs::slab_rescale_space");
-  if (has(row_err)) { want(*row_err, at::kFloat, "row_err"); TORCH_CHECK(row_err->numel() >= 1, "row_err must hold one fp32"); }
-  TORCH_CHECK(dim > 0 && dim <= 1024, "bad dim");
-  const int st = space_slab_checks((int)dim, space, slab, scales, c10::optional<Tensor>(shadow), n_rows);
+  want_space(space);
+  const int st = row_writer_checks(dim, space, slab, scales, c10::optional<Tensor>(shadow), row_err, n_rows);
   c10::hip::HIPGuardMasqueradingAsCUDA g(slab.device());
   ok(crs_slab_rescale_space(n_rows, (int)dim, (int)space, st, (int)shift, slab.data_ptr(), (float*)opt_ptr(scales), shadow.data_ptr<float>(),
                             (float*)opt_ptr(row_err), cur_stream(slab)), "crs::slab_rescale_space");

@@ -272,7 +272,7 @@ def queries_to_f16(q32, slab_type: int = SLAB_F16, out=None):
     return out
 
 
-# ---- hnsw:space 'ip' / 'l2' (csrc/space.hip; include/crs_hip.h holds the contracts, DESIGN 3.12 the transform)
+# ---- hnsw:space 'ip' / 'l2' (csrc/space.hip, csrc/row_build.hip; include/crs_hip.h holds the contracts, DESIGN 3.12 the transform)
 def space_row_dim(dim: int, space: int) -> int:
     """d': the coordinates a stored row and a converted query have (dim, or dim + 1 for l2).  Host arithmetic, no library."""
     return int(dim) + (1 if int(space) == SPACE_L2 else 0)

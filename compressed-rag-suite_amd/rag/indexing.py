@@ -168,6 +168,23 @@ class _Shard:
         self.rows_global = self._grow(self.rows_global, (cap,), torch.int64)
         self.capacity = cap
 
+    def store_rows(self, emb, local_rows=None):
+        """emb: fp32 [m, dim] on this device (contiguous) -> rows self.n.. (an append into reserved capacity), or the rows
+        `local_rows` (int64 [m] on this device, distinct, < self.n), in the shard's own space.  One per-row device function is
+        behind all of it, so an updated row equals the same vector appended bit for bit.  In the spaces 'ip' / 'l2' the caller
+        (VectorStore._grow_scale) has made norm_scale cover emb."""
+        kw = dict(scales=self.scales, shadow=self.shadow, row_err=self.row_err)
+        if self.space == nat.SPACE_COSINE:
+            if local_rows is None:
+                nat.slab_append_f32(emb, self.slab, self.n, self.slab_type, **kw)
+            else:
+                nat.slab_write_rows_f32(emb, local_rows, self.slab, self.n, **kw)
+        elif local_rows is None:
+            nat.slab_append_space_f32(emb, self.space, self.norm_scale, self.slab, self.n, **kw)
+        else:
+            nat.slab_write_rows_space_f32(emb, local_rows, self.space, self.norm_scale, self.slab, self.n, **kw)
+        self._row_err_host = None
+
     def append(self, emb, first_global_row: int):
         """emb: fp32 [m, dim] on this device (contiguous) -> m more rows; they are sidecar rows first_global_row.."""
         import torch
@@ -176,13 +193,7 @@ class _Shard:
         if m == 0:
             return
         with torch.cuda.device(self.device):
-            if self.space == nat.SPACE_COSINE:
-                nat.slab_append_f32(emb, self.slab, self.n, self.slab_type, scales=self.scales, shadow=self.shadow,
-                                    row_err=self.row_err)
-            else:                 # the caller (VectorStore._grow_scale) has made norm_scale cover this batch
-                nat.slab_append_space_f32(emb, self.space, self.norm_scale, self.slab, self.n, scales=self.scales, shadow=self.shadow,
-                                          row_err=self.row_err)
-            self._row_err_host = None
+            self.store_rows(emb)
             self.rows_global[self.n: self.n + m] = torch.arange(first_global_row, first_global_row + m, device=self.device)
         if first_global_row != self.n:
             self.identity = False
@@ -994,10 +1005,10 @@ class VectorStore:
         """emb: fp32 [m, dim] anywhere -> the same rows, contiguous on the shard's device, after the shard's norm scale has been
         made to cover them: the batch's largest norm (crs::rows_norm_max: one launch, a 4-byte readback), ValueError before
         anything is written when it is not finite, and a rescale of the stored rows when the scale grows (which drops the filter
-        cache, as an add does: the compacted sub-slabs hold rows under the old scale)."""
+        cache, as an add does: the compacted sub-slabs hold rows under the old scale).  A cosine shard has no scale."""
         import torch
         emb = emb.to(sh.device).contiguous()
-        if emb.shape[0] == 0:
+        if emb.shape[0] == 0 or sh.space == nat.SPACE_COSINE:
             return emb
         with torch.cuda.device(sh.device):
             top = nat.rows_norm_max(emb)
@@ -1271,14 +1282,8 @@ class VectorStore:
                     continue
                 with torch.cuda.device(sh.device):
                     sel, local = self._local_rows(sh, torch.from_numpy(rows).to(sh.device))
-                    if sel.numel() and sh.space != nat.SPACE_COSINE:
-                        mine = self._grow_scale(sh, emb.to(sh.device)[sel])
-                        nat.slab_write_rows_space_f32(mine, local.contiguous(), sh.space, sh.norm_scale, sh.slab, sh.n, scales=sh.scales,
-                                                      shadow=sh.shadow, row_err=sh.row_err)
-                    elif sel.numel():
-                        mine = emb.to(sh.device)[sel].contiguous()
-                        nat.slab_write_rows_f32(mine, local.contiguous(), sh.slab, sh.n, scales=sh.scales, shadow=sh.shadow,
-                                                row_err=sh.row_err)
+                    if sel.numel():
+                        sh.store_rows(self._grow_scale(sh, emb.to(sh.device)[sel]), local.contiguous())
         for at, row in enumerate(rows.tolist()):
             if documents is not None:
                 col.documents[row] = documents[at]

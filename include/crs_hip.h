@@ -41,7 +41,7 @@ int crs_abi_version(void);
 int crs_row_elems(int dim, int slab_type);
 int crs_padded_dim(int dim);
 
-/* ---- index build: replaces collection.add(embeddings=...) -- rag/indexing.py:114-119 ------
+/* ---- index build (csrc/row_build.hip): replaces collection.add(embeddings=...) -- rag/indexing.py:114-119 ------
  * Converts `n` fp32 embedding rows (dev, row stride `dim`) into slab rows starting at row
  * `row0` of `slab` (dev, row stride crs_padded_dim(dim) elements).  Rows are L2-normalised in
  * fp32 first (x / max(||x||, 1e-12)): ChromaDB's cosine space does the same, and it is the
@@ -55,11 +55,11 @@ int crs_padded_dim(int dim);
 int crs_slab_append_f32(const float* emb_dev, int64_t n, int dim, int slab_type, void* slab_dev,
                         float* scales_dev, float* shadow_f32_dev, int64_t row0, float* row_err_max_dev, void* stream);
 
-/* ---- in-place mutation (additive to ABI 3; csrc/mutate.hip) -- no reference call site: the reference's ChromaDB collection
+/* ---- in-place mutation (additive to ABI 3; csrc/row_build.hip, csrc/mutate.hip) -- no reference call site: the reference's ChromaDB collection
  * offers delete / update / upsert, its own code never calls them --------------------------------------------------------------
  * crs_slab_write_rows_f32 is the scatter form of crs_slab_append_f32: row rows[i] (dev int64 [m], distinct, each < n_rows;
- * rows outside [0, n_rows) are skipped) of slab / scales / shadow is rewritten from emb[i] by the SAME per-row device function
- * the append kernel calls, so an updated row equals the same vector appended bit for bit; row_err_max is raised likewise.
+ * rows outside [0, n_rows) are skipped) of slab / scales / shadow is rewritten from emb[i] by the SAME kernel and per-row device
+ * function as the append, so an updated row equals the same vector appended bit for bit; row_err_max is raised likewise.
  *
  * crs_slab_compact removes the `m` rows dead[0] < dead[1] < ... (dev int64, strictly ascending, all < n_rows) from the arrays
  * of one shard IN PLACE, keeping the order of the others: afterwards rows [0, n_rows - m) of slab, scales (may be NULL),
@@ -81,10 +81,11 @@ int crs_slab_compact(const int64_t* dead_dev, int64_t m, int64_t n_rows, int64_t
 /* Host arithmetic of the above, for tests and callers that size buffers: rows per window for a bounce size (0 = too small). */
 int64_t crs_slab_compact_window_rows(int dim, int slab_type, int has_shadow, size_t bounce_bytes);
 
-/* Query side of the same conversion: fp32 [nq, dim] -> normalised fp16 [nq, crs_row_elems(dim, slab_type)]. */
+/* Query side of the same conversion: fp32 [nq, dim] -> normalised fp16 [nq, crs_row_elems(dim, slab_type)] (the fp16 append
+ * without shadow). */
 int crs_queries_to_f16(const float* q_dev, int nq, int dim, int slab_type, void* q16_dev, void* stream);
 
-/* ---- inner-product and squared-L2 spaces (additive to ABI 3; csrc/space.hip) -- ChromaDB's hnsw:space 'ip' / 'l2',
+/* ---- inner-product and squared-L2 spaces (additive to ABI 3; csrc/space.hip, row writers in csrc/row_build.hip) -- ChromaDB's hnsw:space 'ip' / 'l2',
  * which the reference's collection accepts (rag/indexing.py:83) --------------------------------------------------------------
  * The scan computes <fp16 query row, slab row>.  A store of one of these spaces keeps ONE scale R = 2^e >= the largest row norm
  * it has seen, as a device fp32 (`norm_scale_dev`, read by the kernels: growing it invalidates no captured graph), and stores
@@ -99,8 +100,8 @@ int crs_queries_to_f16(const float* q_dev, int nq, int dim, int slab_type, void*
  * crs_rows_norm_max raises *norm_max_dev (fp32 the caller zeroed) to the largest |x|_2 of n rows; a norm that is not finite leaves
  * +inf there and sets *flag_dev (int32, may be NULL) to 1.
  * crs_slab_append_space_f32 / crs_slab_write_rows_space_f32 are crs_slab_append_f32 / crs_slab_write_rows_f32 for these spaces:
- * the same arguments plus the scale, ONE per-row device function behind both (an updated row equals the same vector appended, bit
- * for bit), row_err_max raised over all d' coordinates.  The caller has made *norm_scale_dev a power of two >= every norm of the
+ * the same arguments plus the scale, the same kernel and per-row device function behind all four (an updated row equals the same
+ * vector appended, bit for bit), row_err_max raised over all d' coordinates.  The caller has made *norm_scale_dev a power of two >= every norm of the
  * batch before the call.
  * crs_slab_rescale_space follows a growth of the scale from R to R 2^shift: every shadow row [0, n_rows) is multiplied by
  * 2^-shift (t by 2^-2 shift), the slab row and int8 scale are rebuilt from it by that same per-row function, row_err_max is raised.

@@ -1,5 +1,5 @@
-"""The row build of the spaces 'ip' / 'l2' (csrc/space_row.h, csrc/space.hip) restated for the tests: a numpy fp32 stand-in of
-slab_store_row_space in the kernel's operation order that the CPU tests break on purpose, the assertions the GPU tests and the
+"""The row build of the spaces 'ip' / 'l2' (csrc/slab_row.h, csrc/row_build.hip, csrc/space.hip) restated for the tests: a numpy fp32 stand-in of
+slab_store_row (ip / l2) in the kernel's operation order that the CPU tests break on purpose, the assertions the GPU tests and the
 CPU self-tests share, the bounds of the query conversion and of the distances, and the input rows.
 
 A space is named 'ip' / 'l2' here (as in tests/_space_ref.py); sdim = dim, or dim + 1 for l2.  u = 2^-24, the fp32 unit roundoff.
@@ -92,14 +92,14 @@ def make_space_rows(n: int, dim: int, R: float, seed: int):
     return x, kinds[:n]
 
 
-# --------------------------------------------------------------------------------------- fp32 stand-in of slab_store_row_space
+# --------------------------------------------------------------------------------------- fp32 stand-in of slab_store_row (ip / l2)
 MUTATIONS = ("t_without_a_lane", "t_not_in_amax", "shadow_stride_dim", "no_padding", "E_over_dim_only", "E_without_last_wave",
              "f16_truncate", "rescale_t_linear")
 
 
 def store_rows_space_standin(src, dim: int, space: str, mul, pdim: int, slab_type: int, slab, scales, shadow, rows, E: float,
                              mutate: str | None = None) -> float:
-    """numpy fp32 stand-in of slab_store_row_space in the kernel's operation order.  src [n, >= dim] fp32 (the caller's vectors,
+    """numpy fp32 stand-in of slab_store_row (ip / l2) in the kernel's operation order.  src [n, >= dim] fp32 (the caller's vectors,
     or the shadow rows themselves for a rescale), mul an exact power of two; writes rows `rows` of slab [cap, pdim] / scales
     [cap] / shadow [cap, sdim] in place and returns the raised E.
       v = src * mul; t = the lane-strided fma chain of v^2, then the butterfly, placed at column dim under l2; amax over all sdim

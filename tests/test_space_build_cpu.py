@@ -1,6 +1,6 @@
 """CPU: the assertions of the ip / l2 row-build tests (tests/_space_build_ref.py) can fail.
 
-A numpy fp32 stand-in of slab_store_row_space passes the assertions the GPU tests apply to the kernels, eight deliberately broken
+A numpy fp32 stand-in of slab_store_row (ip / l2) passes the assertions the GPU tests apply to the kernels, eight deliberately broken
 stand-ins each fail one, a stand-in rescale equals a stand-in append under the grown scale bit for bit, and the row whose fp32 norm
 rounds down onto a power of two is pinned without a GPU.
 """

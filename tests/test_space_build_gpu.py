@@ -1,4 +1,4 @@
-"""GPU: the kernels of the spaces 'ip' / 'l2' (csrc/space.hip, csrc/space_row.h) each on its own against fp64 -- the row build
+"""GPU: the kernels of the spaces 'ip' / 'l2' (csrc/space.hip, csrc/row_build.hip, csrc/slab_row.h) each on its own against fp64 -- the row build
 through crs_slab_append_space_f32, crs_slab_write_rows_space_f32 and crs_slab_rescale_space, crs_rows_norm_max,
 crs_queries_to_space and crs_space_distances.
 

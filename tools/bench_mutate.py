@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Timing of the in-place mutation kernels (csrc/mutate.hip) against what a user of the write-once store could do.
+"""Timing of the in-place mutation kernels (csrc/mutate.hip, csrc/row_build.hip) against what a user of the write-once store could do.
 
 Store: ROWS x DIM fp16 + fp32 shadow on one device.  Cases: delete of 10 random rows, 1 % random, 50 % random, the first row only;
 update of 1 000 and 100 000 rows.  Per case, REPS repetitions after one warm-up, each on a freshly re-filled store, alternating
