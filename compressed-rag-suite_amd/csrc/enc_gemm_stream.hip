@@ -65,12 +65,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_stream_kernel(const _Float16
   // tile in VGPRs through inline-asm loads with a separate counted wait -- a register the compiler may copy or spill
   // before the data has landed; that bug class produced one wrong answer in the scan and is gone from the library.)
   unsigned src_off[kLoads];
-#pragma unroll
-  for (int j = 0; j < kLoads; ++j) {
-    const int P = j * kThreads + tid;
-    const int r = P / kCpr, c = P % kCpr;
-    src_off[j] = (unsigned)(r * kCpr + ((c & ~15) | ((c ^ r) & 15))) * 16u;
-  }
+  swizzled_src_offsets<kThreads, kCpr>(src_off, tid);
   const char* a_bytes = reinterpret_cast<const char*>(A);
   typedef __attribute__((address_space(3))) void* lds_ptr_t;
   const unsigned lds_wave = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_ptr_t)smem + (unsigned)wave * 1024u);
@@ -217,12 +212,7 @@ __global__ __launch_bounds__(kKsThreads, 2) void gemm_stream_ks_kernel(const _Fl
   // tile in VGPRs through inline-asm loads with a separate counted wait -- a register the compiler may copy or spill
   // before the data has landed; that bug class produced one wrong answer in the scan and is gone from the library.)
   unsigned src_off[kLoads];
-#pragma unroll
-  for (int j = 0; j < kLoads; ++j) {
-    const int P = j * kKsThreads + tid;
-    const int r = P / kCpr, c = P % kCpr;
-    src_off[j] = (unsigned)(r * kCpr + ((c & ~15) | ((c ^ r) & 15))) * 16u;
-  }
+  swizzled_src_offsets<kKsThreads, kCpr>(src_off, tid);
   const char* a_bytes = reinterpret_cast<const char*>(A);
   typedef __attribute__((address_space(3))) void* lds_ptr_t;
   const unsigned lds_wave = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_ptr_t)smem + (unsigned)wave * 1024u);

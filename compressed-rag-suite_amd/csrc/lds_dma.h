@@ -43,5 +43,19 @@ __device__ __forceinline__ void lds_dma16(unsigned lds_dst, const void* vaddr) {
                : "=&s"(keep) : "s"(lds_dst), "v"(vaddr) : "memory");
 }
 
+// The LDS side of a transfer is linear (lane i lands at base + 16 i), so a tile's XOR swizzle is applied on the SOURCE side:
+// position P = j * kT + tid of the tile buffer (kT threads, kLoads transfers per lane) receives the tile's 16-byte chunk swz(P)
+// -- chunk cp of row r (kCpr chunks per row) sits at chunk (cp & ~15) | ((cp ^ r) & 15) of the row's LDS image.  src_off[j] is
+// the byte offset of that chunk from the tile's first byte.
+template <int kT, int kCpr, int kLoads>
+__device__ __forceinline__ void swizzled_src_offsets(unsigned (&src_off)[kLoads], int tid) {
+#pragma unroll
+  for (int j = 0; j < kLoads; ++j) {
+    const int P = j * kT + tid;
+    const int r = P / kCpr, cp = P % kCpr;
+    src_off[j] = (unsigned)(r * kCpr + ((cp & ~15) | ((cp ^ r) & 15))) * 16u;
+  }
+}
+
 }  // namespace
 }  // namespace crs

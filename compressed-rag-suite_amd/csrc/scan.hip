@@ -25,7 +25,7 @@
 //
 // HBM-bound by design: algorithmic bytes per launch = n_rows * D * sizeof(elem).
 
-#include "scan_common.h"
+#include "scan_stream.h"
 
 namespace crs {
 
@@ -422,40 +422,26 @@ __global__ __launch_bounds__(kThreads, WGPC) void scan_f16_ring_kernel(const Sca
   if (wave_active) w.finish(a, wave);
 }
 
-template <typename K>
-int launch_kernel(K kernel, int lds, const ScanArgs& a, hipStream_t stream, bool* attr_done) {
-  if (!*attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return (int)e;
-    *attr_done = true;
-  }
-  dim3 grid(a.nqb * a.nwg);           // 1-D; (query block, tile stream) from scan_common.h's grid mapping
-  hipLaunchKernelGGL(kernel, grid, dim3(kThreads), lds, stream, a);
-  return (int)hipGetLastError();
-}
-
 template <int D, int TR, int L>
 int launch_l(const ScanArgs& a, int variant, hipStream_t stream) {
   using C = Cfg<D, TR, L>;
   constexpr int lists = 2 * C::kListBytes;
-  static bool done[5] = {false, false, false, false, false};
   switch (variant) {
-    case 0: return launch_kernel(&scan_f16_kernel<D, TR, L, false, false>, 2 * C::kTileBytes + lists, a, stream, &done[0]);
+    case 0: return launch_scan<&scan_f16_kernel<D, TR, L, false, false>>(2 * C::kTileBytes + lists, kThreads, a, stream);
     case 3:
       if (a.boot && L == 16 && TR == 32)
-        return launch_kernel(&scan_f16_kernel<D, TR, L, true, (L == 16 && TR == 32)>, 2 * C::kTileBytes + lists, a, stream, &done[4]);
+        return launch_scan<&scan_f16_kernel<D, TR, L, true, (L == 16 && TR == 32)>>(2 * C::kTileBytes + lists, kThreads, a, stream);
       // 32-slot lists (k > 16) on rows of >= 512 elements run out of registers and spill a few; an inline-asm
       // load whose destination the compiler then copies or spills before the data has landed would hand
       // garbage on, so those instantiations keep compiler-visible loads
       if constexpr (L == 32 && D >= 512)
-        return launch_kernel(&scan_f16_kernel<D, TR, L, false, false>, 2 * C::kTileBytes + lists, a, stream, &done[0]);
+        return launch_scan<&scan_f16_kernel<D, TR, L, false, false>>(2 * C::kTileBytes + lists, kThreads, a, stream);
       else
-        return launch_kernel(&scan_f16_kernel<D, TR, L, true, false>, 2 * C::kTileBytes + lists, a, stream, &done[3]);
-    case 2: return launch_kernel(&scan_f16_ring_kernel<D, TR, L, 2, classic_wg_per_cu(2)>, 2 * C::kTileBytes + lists, a, stream, &done[2]);
+        return launch_scan<&scan_f16_kernel<D, TR, L, true, false>>(2 * C::kTileBytes + lists, kThreads, a, stream);
+    case 2: return launch_scan<&scan_f16_ring_kernel<D, TR, L, 2, classic_wg_per_cu(2)>>(2 * C::kTileBytes + lists, kThreads, a, stream);
     default: {
       constexpr int NS = (L == 16) ? 4 : 3;
-      return launch_kernel(&scan_f16_ring_kernel<D, TR, L, NS, classic_wg_per_cu(1)>, NS * C::kTileBytes + lists, a, stream, &done[1]);
+      return launch_scan<&scan_f16_ring_kernel<D, TR, L, NS, classic_wg_per_cu(1)>>(NS * C::kTileBytes + lists, kThreads, a, stream);
     }
   }
 }

@@ -19,13 +19,12 @@
 // together with the tile they belong to, one tile ahead.
 // Algorithmic bytes per launch = n_rows * (D + 4).
 
-#include "scan_common.h"
+#include "scan_stream.h"
 
 namespace crs {
 namespace {
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 template <int D, int TR, int L>
 struct CfgI8 {
@@ -61,8 +60,9 @@ __global__ __launch_bounds__(kThreads, 2) void scan_i8_kernel(const ScanArgs a) 
   float* sbuf = sbuf_all + wave * (L * 64);
   int* ibuf = ibuf_all + wave * (L * 64);
 
-  // ---- tile transfer (as scan_tb.hip): global memory -> LDS directly; LDS position P = j * 256 + tid receives the
-  // tile's chunk swz(P) (the swizzle is applied on the source side, the LDS side of the transfer is linear)
+  // ---- tile transfer: scan_stream.h's stream_tile with the row scales' transfer inside its branches, and lds_dma.h's
+  // swizzled_src_offsets, both written out -- through the helpers this file's kernels schedule differently and two of the
+  // allow-listed ones spill more (DESIGN.md section 3.1 has the counts)
   unsigned src_off[C::kLoads];
 #pragma unroll
   for (int j = 0; j < C::kLoads; ++j) {
@@ -178,18 +178,7 @@ __global__ __launch_bounds__(kThreads, 2) void scan_i8_kernel(const ScanArgs a) 
 #pragma unroll
   for (int j = 0; j < KK; ++j) { ts[j] = kNegInf; tr[j] = -1; }
   int it = 0;
-  auto insert = [&](float x, int xr) {
-#pragma unroll
-    for (int j = 0; j < KK; ++j) {
-      const bool c = x > ts[j];
-      const float s_old = ts[j];
-      const int r_old = tr[j];
-      ts[j] = c ? x : s_old;
-      tr[j] = c ? xr : r_old;
-      x = c ? s_old : x;
-      xr = c ? r_old : xr;
-    }
-  };
+  auto insert = [&](float x, int xr) { chain_insert(ts, tr, x, xr); };   // (a lambda: scan_tb.hip says why)
   const size_t po = ((size_t)(q_valid ? qi : 0) * nwg + CRS_STREAM) * a.kp;   // this query's partial list [nq, nwg, kp]
 
   park_tile();
@@ -205,14 +194,10 @@ __global__ __launch_bounds__(kThreads, 2) void scan_i8_kernel(const ScanArgs a) 
     const bool has_next = tn < a.n_tiles;
     if (has_next) load_tile(tn, cur ^ 1);
     const bool in_dyn = TBK > 0 && tn >= t_dyn;
-    const bool draw = TBK > 0 && a.ticket != nullptr && (in_dyn ? ((tn - t_dyn) & a.dyn_mask) == a.dyn_mask : tn + nwg >= t_dyn);
-    if constexpr (TBK > 0) {   // one lane draws the granule after tn's (scan_tb.hip explains the asm form)
-      const unsigned mask = __builtin_amdgcn_readfirstlane((draw && has_next && wave == 0) ? 1u : 0u);
-      unsigned long long keep;
-      const unsigned zero = 0u, one = 1u;
+    const bool draw = TBK > 0 && a.ticket != nullptr && ticket_due(in_dyn, tn, nwg, t_dyn, a.dyn_mask);
+    if constexpr (TBK > 0) {   // one lane draws the granule after tn's
       tk = 0;
-      asm volatile("s_mov_b64 %1, exec\n\ts_mov_b32 exec_lo, %2\n\ts_mov_b32 exec_hi, 0\n\tglobal_atomic_add %0, %3, %4, %5 sc0\n\ts_mov_b64 exec, %1"
-                   : "+v"(tk), "=&s"(keep) : "s"(mask), "v"(zero), "v"(one), "s"(a.ticket) : "memory");
+      ticket_draw(tk, draw && has_next && wave == 0, a.ticket);
     }
     WP_LAP(1);   // look-ahead issue
     if (tau_pub) {
@@ -269,14 +254,11 @@ __global__ __launch_bounds__(kThreads, 2) void scan_i8_kernel(const ScanArgs a) 
       asm volatile("" : "+v"(x));
       tau = fmaxf(tau, foreign_tau(x));
     }
-    if (TBK > 0 && draw && has_next && tid == 0) sh_next[it & 1] = t_dyn + (int)tk * (a.dyn_mask + 1);
+    if (TBK > 0 && draw && has_next && tid == 0) ticket_publish(sh_next, it, tk, t_dyn, a.dyn_mask);
     __syncthreads();
     WP_LAP(7);   // barrier
     int tnn = in_dyn ? tn + 1 : tn + nwg;
-    if (TBK > 0 && draw && has_next) {
-      tnn = __builtin_amdgcn_readfirstlane(sh_next[it & 1]);
-      tnn = (unsigned)tnn < (unsigned)a.n_tiles ? tnn : a.n_tiles;   // a poisoned counter must not become an address
-    }
+    if (TBK > 0 && draw && has_next) tnn = ticket_take(sh_next, it, a.n_tiles);
     cur ^= 1;
     ++it;
     t = tn;
@@ -286,20 +268,9 @@ __global__ __launch_bounds__(kThreads, 2) void scan_i8_kernel(const ScanArgs a) 
     if constexpr (TBK < 0) {
       flush_lists<L>(sbuf, ibuf, lane, cnt, tau, a.k, a.kp, a.part_scores + po, a.part_rows + po, q_valid);
     } else if constexpr (TBK == 0) {
-      if (q_valid) {   // slots of tiles this (shorter) stream does not have
-        for (int p = it + kq; p < a.kp; p += 4) {
-          a.part_scores[po + p] = kNegInf;
-          a.part_rows[po + p] = -1;
-        }
-      }
+      if (q_valid) dump_pad(a.part_scores, a.part_rows, po, it + kq, a.kp);
     } else {
-      if (q_valid && kq == 0) {
-#pragma unroll
-        for (int j = 0; j < KK; ++j) {
-          a.part_scores[po + j] = ts[j];
-          a.part_rows[po + j] = tr[j];
-        }
-      }
+      if (q_valid && kq == 0) chain_store(a.part_scores, a.part_rows, po, ts, tr);
     }
   }
   WP_LAP(10);
@@ -310,16 +281,7 @@ template <int D, int TR, int L, int TBK>
 int launch_i8(const ScanArgs& a, hipStream_t stream) {
   using C = CfgI8<D, TR, L>;
   constexpr int lds = (TBK < 0 ? C::kLds : 2 * C::kTileBytes) + 2 * TR * 4 + 16;   // + the row-scale slots + the next-tile slots
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&scan_i8_kernel<D, TR, L, TBK>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return (int)e;
-    attr_done = true;
-  }
-  dim3 grid(a.nqb * a.nwg);           // 1-D; (query block, tile stream) from scan_common.h's grid mapping
-  hipLaunchKernelGGL((scan_i8_kernel<D, TR, L, TBK>), grid, dim3(kThreads), lds, stream, a);
-  return (int)hipGetLastError();
+  return launch_scan<&scan_i8_kernel<D, TR, L, TBK>>(lds, kThreads, a, stream);
 }
 
 // the form if scan_forms.h has it

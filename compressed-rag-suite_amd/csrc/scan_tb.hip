@@ -20,12 +20,10 @@
 // staged copy of the tile (rows wider than 512 elements, where scan_wide.hip's 32-query fragments no
 // longer fit the register file).
 
-#include "scan_common.h"
+#include "scan_stream.h"
 
 namespace crs {
 namespace {
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 template <int D, int TR, int NW>
 struct TbCfg {
@@ -57,11 +55,8 @@ __global__ __launch_bounds__(NW * 64, (TbCfg<D, TR, NW>::kWgpc * NW) / 4) void s
   const int qbase = CRS_QBLOCK * (NW * 16) + wave * 16;
   const bool wave_active = qbase < a.nq;
 
-  // ---- tile transfer: global memory -> LDS directly (global_load_lds_dwordx4, 16 bytes per lane; no staging
-  // registers, no LDS stores).  The LDS side of the transfer is linear -- position P = j * kT + tid of the tile
-  // buffer -- so the XOR swizzle of the 16-byte chunks is applied on the SOURCE side: P receives chunk swz(P).
-  // Written in asm: the compiler's own waitcnt insertion puts a vmcnt(0) in front of every LDS read that may alias
-  // an in-flight transfer, i.e. in front of every fragment read.
+  // ---- tile transfer (scan_stream.h).  The offsets are lds_dma.h's swizzled_src_offsets written out: through the helper two
+  // kernels of this file lose waits (DESIGN.md section 3.1 has the counts)
   unsigned src_off[C::kLoads];
 #pragma unroll
   for (int j = 0; j < C::kLoads; ++j) {
@@ -72,29 +67,10 @@ __global__ __launch_bounds__(NW * 64, (TbCfg<D, TR, NW>::kWgpc * NW) / 4) void s
   const char* slab = reinterpret_cast<const char*>(a.slab);
   const size_t last_chunk = (size_t)a.n_rows * (D * 2) - 16;
   const int n_full = a.n_rows / TR;
-  const unsigned lds_wave = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_ptr_t)tile_buf + (unsigned)wave * 1024u);
-  auto dma_tile = [&](int tile_, int buf) {
-    const int tile = __builtin_amdgcn_readfirstlane(tile_);
-    const unsigned dst0 = lds_wave + (unsigned)(buf * C::kTileBytes);
-    if (tile < n_full) {
-      const char* base = uniform_ptr(slab + (size_t)tile * C::kTileBytes);
-      if (a.nt) {   // (a kernel argument: a scalar branch)
-#pragma unroll
-        for (int j = 0; j < C::kLoads; ++j) lds_dma16_nt(dst0 + (unsigned)(j * kT * 16), src_off[j], base);
-      } else {
-#pragma unroll
-        for (int j = 0; j < C::kLoads; ++j) lds_dma16(dst0 + (unsigned)(j * kT * 16), src_off[j], base);
-      }
-    } else {   // the ragged last tile: clamp every lane to the slab's last 16 bytes (rows past the end never rank)
-#pragma unroll
-      for (int j = 0; j < C::kLoads; ++j) {
-        size_t off = (size_t)tile * C::kTileBytes + src_off[j];
-        off = off > last_chunk ? last_chunk : off;
-        const char* p = slab + off;
-        const unsigned dst = dst0 + (unsigned)(j * kT * 16);
-        lds_dma16(dst, p);
-      }
-    }
+  const unsigned lds_wave = tile_lds_wave(tile_buf, wave);
+  auto dma_tile = [&](int tile, int buf) {
+    stream_tile<kT, C::kTileBytes>(slab, __builtin_amdgcn_readfirstlane(tile), n_full, last_chunk,
+                                   lds_wave + (unsigned)(buf * C::kTileBytes), src_off, a.nt);
   };
 
 #ifdef CRS_TB_CONTIG   /* timing experiment (tools/scan_tb_probe): every stream walks ONE contiguous run of tiles */
@@ -105,13 +81,7 @@ __global__ __launch_bounds__(NW * 64, (TbCfg<D, TR, NW>::kWgpc * NW) / 4) void s
   const int tstep = nwg, tend = a.n_tiles;
   int t = stream;
 #endif
-  // Tile order.  Static part: tiles stream, stream + nwg, ... below t_dyn.  Dynamic part (chain mode, long streams): granules of
-  // dyn_mask + 1 consecutive tiles from t_dyn + ticket * (dyn_mask + 1), the ticket drawn from a device-wide counter (one address
-  // takes ~90 M atomics/s on this part: a ticket per tile would be the bottleneck) -- a workgroup that was held up (an encoder kernel on its CU, a
-  // slower HBM channel) then simply draws fewer tiles instead of making the whole launch wait for its fixed share.  The tile
-  // AFTER the look-ahead tile is requested at the top of an iteration (thread 0, one atomic) and handed to the workgroup through
-  // LDS behind the iteration's barrier: a ticket has a whole tile time (~2 us) to come back.  Any assignment gives the same lists
-  // after the merge: a workgroup still sees its tiles in increasing order (ties keep the earlier tile, as before).
+  // Tile order: static stride below t_dyn, then (chain mode, long streams) ticketed granules -- scan_stream.h, "Tile order"
   __shared__ int sh_next[2];
   const int t_dyn = K > 0 ? a.t_dyn : a.n_tiles;
   int tn = t + tstep;     // the look-ahead tile (t_dyn >= 2 nwg: static for the first iteration)
@@ -148,18 +118,8 @@ __global__ __launch_bounds__(NW * 64, (TbCfg<D, TR, NW>::kWgpc * NW) / 4) void s
   int tr[KK];
 #pragma unroll
   for (int j = 0; j < KK; ++j) { ts[j] = kNegInf; tr[j] = -1; }
-  auto insert = [&](float x, int xr) {
-#pragma unroll
-    for (int j = 0; j < KK; ++j) {
-      const bool c = x > ts[j];
-      const float s_old = ts[j];
-      const int r_old = tr[j];
-      ts[j] = c ? x : s_old;
-      tr[j] = c ? xr : r_old;
-      x = c ? s_old : x;
-      xr = c ? r_old : xr;
-    }
-  };
+  // (through a lambda, as the local chain was: called from the loop directly, the chain forms grow by up to 24 scalar instructions)
+  auto insert = [&](float x, int xr) { chain_insert(ts, tr, x, xr); };
 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -170,21 +130,10 @@ __global__ __launch_bounds__(NW * 64, (TbCfg<D, TR, NW>::kWgpc * NW) / 4) void s
   while (t < tend) {
     const bool has_next = tn < tend;
     if (has_next) dma_tile(tn, cur ^ 1);
-    // the tile after tn: static stride, the next tile of tn's granule, or -- tn is the last static tile / the last tile of its
-    // granule -- the first tile of the granule the counter hands out (wave-uniform)
     const bool in_dyn = K > 0 && tn >= t_dyn;
-    const bool draw = K > 0 && a.ticket != nullptr && (in_dyn ? ((tn - t_dyn) & a.dyn_mask) == a.dyn_mask : tn + tstep >= t_dyn);
-    unsigned tk = 0;
-    if constexpr (K > 0) {
-      // one lane draws; written as asm under a hand-set exec mask: hipcc's atomicAdd waits for the returned value on the spot
-      // (its wave-aggregation rewrite reads it at once), i.e. for the look-ahead transfer issued just above as well -- transfer
-      // and multiplication of the dynamic tiles would no longer overlap.  The value is first read behind the vmcnt(0) below.
-      const unsigned mask = __builtin_amdgcn_readfirstlane((draw && has_next && wave == 0) ? 1u : 0u);   // lane 0 of wave 0, or nobody
-      unsigned long long keep;
-      const unsigned zero = 0u, one = 1u;
-      asm volatile("s_mov_b64 %1, exec\n\ts_mov_b32 exec_lo, %2\n\ts_mov_b32 exec_hi, 0\n\tglobal_atomic_add %0, %3, %4, %5 sc0\n\ts_mov_b64 exec, %1"
-                   : "+v"(tk), "=&s"(keep) : "s"(mask), "v"(zero), "v"(one), "s"(a.ticket) : "memory");
-    }
+    const bool draw = K > 0 && a.ticket != nullptr && ticket_due(in_dyn, tn, tstep, t_dyn, a.dyn_mask);
+    unsigned tk = 0;   // the ticket in flight: first read behind the vmcnt(0) below
+    if constexpr (K > 0) ticket_draw(tk, draw && has_next && wave == 0, a.ticket);
     WP_LAP(1);   // look-ahead issue
 #if defined(CRS_TB_EXPERIMENT) && CRS_TB_EXPERIMENT <= 2   /* tools/scan_tb_probe.hip: timing-only builds (1: no MFMA / selection, 3: fragment reads without MFMA, 4: MFMA without fragment reads) */
     if (false) {
@@ -232,13 +181,10 @@ __global__ __launch_bounds__(NW * 64, (TbCfg<D, TR, NW>::kWgpc * NW) / 4) void s
     if (has_next) {
       asm volatile("s_waitcnt vmcnt(0)" : "+v"(tk) : : "memory");
       WP_LAP(5);   // wait for the look-ahead tile (and for the ticket)
-      if (K > 0 && draw && tid == 0) sh_next[it & 1] = t_dyn + (int)tk * (a.dyn_mask + 1);
+      if (K > 0 && draw && tid == 0) ticket_publish(sh_next, it, tk, t_dyn, a.dyn_mask);
       __syncthreads();
       WP_LAP(7);   // barrier
-      if (K > 0 && draw) {   // two slots: iteration it + 1 writes the other one
-        tnn = __builtin_amdgcn_readfirstlane(sh_next[it & 1]);
-        tnn = (unsigned)tnn < (unsigned)tend ? tnn : tend;   // a poisoned counter must not become an address
-      }
+      if (K > 0 && draw) tnn = ticket_take(sh_next, it, tend);
     }
     cur ^= 1;
     ++it;
@@ -247,20 +193,9 @@ __global__ __launch_bounds__(NW * 64, (TbCfg<D, TR, NW>::kWgpc * NW) / 4) void s
   }
   if (wave_active) {
     if constexpr (K == 0) {
-      if (q_valid) {   // slots of tiles this (shorter) stream does not have
-        for (int p = it + kq; p < a.kp; p += 4) {
-          out_s[p] = kNegInf;
-          out_i[p] = -1;
-        }
-      }
+      if (q_valid) dump_pad(out_s, out_i, 0, it + kq, a.kp);
     } else {
-      if (q_valid && kq == 0) {    // kp = K
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-          out_s[j] = ts[j];
-          out_i[j] = tr[j];
-        }
-      }
+      if (q_valid && kq == 0) chain_store(out_s, out_i, 0, ts, tr);
     }
   }
   WP_LAP(10);   // final fold + write
@@ -273,17 +208,7 @@ __global__ void tb_zero_ticket_kernel(unsigned* ticket) {
 
 template <int D, int TR, int NW, int K>
 int launch_tb(const ScanArgs& a, hipStream_t stream) {
-  using C = TbCfg<D, TR, NW>;
-  static bool done = false;
-  auto kernel = &scan_tb_kernel<D, TR, NW, K>;
-  if (!done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, C::kLds);
-    if (e != hipSuccess) return (int)e;
-    done = true;
-  }
-  hipLaunchKernelGGL(kernel, dim3(a.nqb * a.nwg), dim3(NW * 64), C::kLds, stream, a);
-  return (int)hipGetLastError();
+  return launch_scan<&scan_tb_kernel<D, TR, NW, K>>(TbCfg<D, TR, NW>::kLds, NW * 64, a, stream);
 }
 
 // the form if scan_forms.h has it

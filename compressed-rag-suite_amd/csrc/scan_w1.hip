@@ -25,7 +25,7 @@
 // replaces -- a tie; what was learned on the way is in DESIGN.md section 7 (a 1 KB transfer instruction holds the issuing
 // wave ~95 cycles whatever the queue state, so one wave per SIMD cannot hide transfer issue; the clock sits at
 // 1.3-1.6 GHz under this load; the transfer skeleton alone moves 3.9 TB/s).
-#include "scan_common.h"
+#include "scan_stream.h"
 
 namespace crs {
 namespace {
@@ -325,15 +325,7 @@ template <int D>
 int launch_w2(const ScanArgs& a, hipStream_t stream) {
   static_assert(w1_form_exists(D));
   using C = W2Cfg<D>;
-  static bool done = false;
-  auto kernel = &scan_w2_kernel<D>;
-  if (!done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, C::kLds);
-    if (e != hipSuccess) return (int)e;
-    done = true;
-  }
-  hipLaunchKernelGGL(kernel, dim3(a.nqb * a.nwg), dim3(512), C::kLds, stream, a);
-  return (int)hipGetLastError();
+  return launch_scan<&scan_w2_kernel<D>>(C::kLds, 512, a, stream);
 }
 
 }  // namespace

@@ -82,16 +82,12 @@
 //     algorithm (insert_shift) and its proof are unchanged: they only speak of "the two lanes of the pair".
 // Which shape a form runs is wide_default_mfma() (scan_forms.h), set from A/B runs by wall time; CRS_WIDE_MFMA=16 | 32 overrides it.
 
-#include "scan_common.h"
+#include "scan_stream.h"
 
 namespace crs {
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-
-
 
 // rows per tile: 32 * RB (RB 32x32 MFMA row blocks).  The 8-wave kernel takes 64-row tiles where the registers
 // allow: the per-tile costs that are not MFMAs (barrier, selection chain, load issue, LDS store: ~1.9 k cycles
@@ -170,9 +166,8 @@ __device__ __forceinline__ void scan_wide_body(const ScanArgs a) {
   WP_DECL;
   const bool wave_active = (qblock * (NW * 32) + wave * 32) < a.nq;   // wave-uniform
 
-  // tile transfer as in scan_tb.hip: global memory -> LDS directly, LDS position P = j * kT + tid receives the
-  // tile's chunk swz(P) (source-side swizzle); asm, because the compiler would wait for every transfer before
-  // every fragment read
+  // ---- tile transfer (scan_stream.h).  The offsets are lds_dma.h's swizzled_src_offsets written out: through the helper this
+  // file's kernels schedule differently (DESIGN.md section 3.1 has the counts)
   unsigned src_off[C::kLoads];
 #pragma unroll
   for (int j = 0; j < C::kLoads; ++j) {
@@ -184,35 +179,13 @@ __device__ __forceinline__ void scan_wide_body(const ScanArgs a) {
   const size_t last_chunk = (size_t)a.n_rows * (D * 2) - 16;
   constexpr int RB = C::RB, WTR = C::TR;
   const int n_full = a.n_rows / WTR;
-  const unsigned lds_wave = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_ptr_t)tile_buf + (unsigned)wave * 1024u);
-  auto dma_tile = [&](int tile_, int buf) {
-    const int tile = __builtin_amdgcn_readfirstlane(tile_);
-    const unsigned dst0 = lds_wave + (unsigned)(buf * C::kTileBytes);
-    if (tile < n_full) {
-      const char* base = uniform_ptr(slab + (size_t)tile * C::kTileBytes);
-      if (wide_streamed<K>() && a.nt) {   // (a kernel argument: a scalar branch)
-#pragma unroll
-        for (int j = 0; j < C::kLoads; ++j) lds_dma16_nt(dst0 + (unsigned)(j * kT * 16), src_off[j], base);
-      } else {
-#pragma unroll
-        for (int j = 0; j < C::kLoads; ++j) lds_dma16(dst0 + (unsigned)(j * kT * 16), src_off[j], base);
-      }
-    } else {   // the ragged last tile: clamp every lane to the slab's last 16 bytes (rows past the end never rank)
-#pragma unroll
-      for (int j = 0; j < C::kLoads; ++j) {
-        size_t off = (size_t)tile * C::kTileBytes + src_off[j];
-        off = off > last_chunk ? last_chunk : off;
-        const char* p = slab + off;
-        const unsigned dst = dst0 + (unsigned)(j * kT * 16);
-        lds_dma16(dst, p);
-      }
-    }
+  const unsigned lds_wave = tile_lds_wave(tile_buf, wave);
+  auto dma_tile = [&](int tile, int buf) {
+    stream_tile<kT, C::kTileBytes>(slab, __builtin_amdgcn_readfirstlane(tile), n_full, last_chunk,
+                                   lds_wave + (unsigned)(buf * C::kTileBytes), src_off, wide_streamed<K>() ? a.nt : 0);
   };
 
-  // Tile order: static stride below t_dyn, then (24- / 32-slot forms) granules of dyn_mask + 1 consecutive tiles drawn from a
-  // device-wide counter, exactly scan_tb.hip's schedule ("Tile order" there): the ticket for the tile AFTER the look-ahead tile
-  // is requested at the top of an iteration and handed round through LDS behind the iteration's barrier.  A workgroup still
-  // sees its tiles in increasing order, so any assignment leaves the same lists after the merge.
+  // Tile order: static stride below t_dyn, then (24- / 32-slot forms) ticketed granules -- scan_stream.h, "Tile order"
   __shared__ int sh_next[2];
   constexpr bool kDyn = wide_streamed<K>();
   const int tend = a.n_tiles;
@@ -312,19 +285,6 @@ __device__ __forceinline__ void scan_wide_body(const ScanArgs a) {
 
   float px = kNegInf;   // pending candidate of this lane (parity forms; see the loop)
   int pr = -1;
-  // insert into the sorted list: one compare-exchange per slot, the loser moves on
-  auto insert = [&](float x, int xr) {
-#pragma unroll
-    for (int j = 0; j < KL; ++j) {
-      const bool c = x > ts[j];
-      const float s_old = ts[j];
-      const int r_old = tr[j];
-      ts[j] = c ? x : s_old;
-      tr[j] = c ? xr : r_old;
-      x = c ? s_old : x;
-      xr = c ? r_old : xr;
-    }
-  };
 
   // split forms: (v, vr) goes in front of the first slot that x does NOT beat, and every slot x beats moves down one place (v is x
   // itself, or in the upper half the slot the lower half pushes out, which x beats too); the compares do not depend on each other
@@ -514,7 +474,7 @@ __device__ __forceinline__ void scan_wide_body(const ScanArgs a) {
       } else {
         if ((ie & 1) == h) { px = x; pr = te * WTR; } // lane half h is responsible for the tiles of parity h
         if (ie & 1) {
-          insert(px, pr);
+          chain_insert(ts, tr, px, pr);
           px = kNegInf;
           pr = -1;
         }
@@ -527,20 +487,10 @@ __device__ __forceinline__ void scan_wide_body(const ScanArgs a) {
   while (t < tend) {
     const bool has_next = tn < tend;
     if (has_next) dma_tile(tn, cur ^ 1);
-    // the tile after tn: static stride, the next tile of tn's granule, or -- tn is the last static tile / the last tile of its
-    // granule -- the first tile of the granule the counter hands out (wave-uniform)
     const bool in_dyn = kDyn && tn >= t_dyn;
-    const bool draw = kDyn && a.ticket != nullptr && has_next && (in_dyn ? ((tn - t_dyn) & a.dyn_mask) == a.dyn_mask : tn + nwg >= t_dyn);
-    unsigned tk = 0;
-    if constexpr (kDyn) {
-      // one lane draws, under a hand-set exec mask (scan_tb.hip: hipcc's atomicAdd would wait for the value, and with it for the
-      // look-ahead transfer, on the spot).  The value is first read behind the vmcnt(0) below.
-      const unsigned mask = __builtin_amdgcn_readfirstlane((draw && wave == 0) ? 1u : 0u);   // lane 0 of wave 0, or nobody
-      unsigned long long keep;
-      const unsigned zero = 0u, one = 1u;
-      asm volatile("s_mov_b64 %1, exec\n\ts_mov_b32 exec_lo, %2\n\ts_mov_b32 exec_hi, 0\n\tglobal_atomic_add %0, %3, %4, %5 sc0\n\ts_mov_b64 exec, %1"
-                   : "+v"(tk), "=&s"(keep) : "s"(mask), "v"(zero), "v"(one), "s"(a.ticket) : "memory");
-    }
+    const bool draw = kDyn && a.ticket != nullptr && has_next && ticket_due(in_dyn, tn, nwg, t_dyn, a.dyn_mask);
+    unsigned tk = 0;   // the ticket in flight: first read behind the vmcnt(0) below
+    if constexpr (kDyn) ticket_draw(tk, draw && wave == 0, a.ticket);
     if (wave_active) {
       WP_LAP(1);   // tile-load issue
       const char* buf = tile_buf + cur * C::kTileBytes;
@@ -559,17 +509,14 @@ __device__ __forceinline__ void scan_wide_body(const ScanArgs a) {
     int tnn = in_dyn ? tn + 1 : tn + nwg;
     if constexpr (kDyn) {
       asm volatile("s_waitcnt vmcnt(0)" : "+v"(tk) : : "memory");
-      if (draw && tid == 0) sh_next[it & 1] = t_dyn + (int)tk * (a.dyn_mask + 1);
+      if (draw && tid == 0) ticket_publish(sh_next, it, tk, t_dyn, a.dyn_mask);
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     WP_LAP(6);   // wait for the next tile (and for the ticket)
     __syncthreads();
     WP_LAP(7);   // barrier
-    if (kDyn && draw) {   // two slots: iteration it + 1 writes the other one
-      tnn = __builtin_amdgcn_readfirstlane(sh_next[it & 1]);
-      tnn = (unsigned)tnn < (unsigned)tend ? tnn : tend;   // a poisoned counter must not become an address
-    }
+    if (kDyn && draw) tnn = ticket_take(sh_next, it, tend);
     cur ^= 1;
     ++it;
     t_prev = t;
@@ -593,7 +540,7 @@ __device__ __forceinline__ void scan_wide_body(const ScanArgs a) {
       }
     }
   } else {
-    if (wave_active && (it & 1)) insert(px, pr);   // odd tile count: the last (even) tile is still pending
+    if (wave_active && (it & 1)) chain_insert(ts, tr, px, pr);   // odd tile count: the last (even) tile is still pending
     if (wave_active && q_valid) {   // [nq, nwg, kp = 2 K]: lane half h owns slots h K .. h K + K - 1
       const size_t o = ((size_t)qi * nwg + stream) * a.kp + (size_t)h * K;
 #pragma unroll
@@ -619,20 +566,8 @@ __global__ __launch_bounds__(NW * 64, 2) void scan_wide16_kernel(const ScanArgs 
 
 template <int D, int NW, int K, bool S16>
 int launch_wide(const ScanArgs& a, hipStream_t stream) {
-  using C = WCfg<D, NW>;
-  static bool done = false;
-  auto kernel = [] {
-    if constexpr (S16) return &scan_wide16_kernel<D, NW, K>;
-    else return &scan_wide_kernel<D, NW, K>;
-  }();
-  if (!done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, C::kLds);
-    if (e != hipSuccess) return (int)e;
-    done = true;
-  }
-  hipLaunchKernelGGL(kernel, dim3(a.nqb * a.nwg), dim3(NW * 64), C::kLds, stream, a);
-  return (int)hipGetLastError();
+  if constexpr (S16) return launch_scan<&scan_wide16_kernel<D, NW, K>>(WCfg<D, NW>::kLds, NW * 64, a, stream);
+  else return launch_scan<&scan_wide_kernel<D, NW, K>>(WCfg<D, NW>::kLds, NW * 64, a, stream);
 }
 
 // the form if scan_forms.h has it

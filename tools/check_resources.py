@@ -7,7 +7,8 @@
 1. Scratch.  Compiles each translation unit for gfx950 with -Rpass-analysis=kernel-resource-usage and fails when a kernel
    uses scratch memory (register spills) unless it is on the ALLOW list below -- the list names the cold instantiations that
    are known to spill, with the reason; every kernel a BASELINE configuration or a default plan selects must be clean.
-3. Tickets (scan_tb.hip / scan_i8.hip / scan_wide.hip): the asm global_atomic_add's destination register is untouched until the vmcnt(0) behind it.
+3. Tickets (scan_tb.hip / scan_i8.hip / scan_wide.hip; the asm is scan_stream.h's ticket_draw): the asm global_atomic_add's destination
+   register is untouched until the vmcnt(0) behind it.  A listed file in which no such atomic is found at all is a violation too.
 2. Counted waits.  scan_w2_kernel (csrc/scan_w1.hip), gemm_big_kernel and gemm8_kernel pace their LDS reads / LDS-DMA with
    hand-counted s_waitcnt lgkmcnt(N) / vmcnt(N).  Those counts are only right while the compiler puts no SMEM load, scratch
    access or buffer instruction of its own between the counted statements: the device assembly of these kernels must have
@@ -36,7 +37,7 @@ COUNTED = {"scan_w1.hip": ["scan_w2_kernel"], "enc_gemm_big.hip": ["gemm_big_ker
 # 3. Tickets.  scan_tb_kernel / scan_i8_kernel / scan_wide_kernel (24- / 32-slot forms) draw their dynamic tiles with an asm global_atomic_add whose returned value is first
 #    read behind a later s_waitcnt vmcnt(0) (the compiler does not count the asm's memory operation): between the atomic and that
 #    wait no instruction may touch the destination register (a copy or spill there would carry garbage).
-TICKETS = {"scan_tb.hip": "scan_tb_kernel", "scan_i8.hip": "scan_i8_kernel", "scan_wide.hip": "scan_wide_kernel"}
+TICKETS = {"scan_tb.hip": "scan_tb_kernel", "scan_i8.hip": "scan_i8_kernel", "scan_wide.hip": "scan_wide(?:16)?_kernel"}
 
 
 def demangle(names):
@@ -70,12 +71,14 @@ def analyse(path):
                     asm_bad.append((m.group(1), ["private_segment_fixed_size %s" % m.group(2)]))
     if base in TICKETS:
         s = subprocess.run([HIPCC, *FLAGS, "-S", path, "-o", "-"], capture_output=True, text=True).stdout
-        for m in re.finditer(r"^(_Z\S*%s\S*):\n(.*?)s_endpgm" % TICKETS[base], s, flags=re.S | re.M):
+        audited = 0
+        for m in re.finditer(r"^(_Z\S*%s\S*):[^\n]*\n(.*?)^\.Lfunc_end" % TICKETS[base], s, flags=re.S | re.M):   # (the label line ends in a comment)
             lines = m.group(2).splitlines()
             for i, ln in enumerate(lines):
                 am = re.match(r"\s*global_atomic_add\s+(v\d+),", ln)
                 if not am:
                     continue
+                audited += 1
                 reg = am.group(1)
                 for nxt in lines[i + 1:]:
                     if re.match(r"\s*s_waitcnt\s+vmcnt\(0\)", nxt):
@@ -83,6 +86,8 @@ def analyse(path):
                     if re.search(r"\b%s\b" % reg, nxt) and not nxt.lstrip().startswith(";"):
                         asm_bad.append((m.group(1), ["ticket register %s touched before its wait: %s" % (reg, nxt.strip())]))
                         break
+        if not audited:      # the instantiations moved, or the asm no longer matches: the audit must not pass on nothing
+            asm_bad.append((TICKETS[base], ["no asm global_atomic_add found in any %s of %s: the ticket audit checked nothing" % (TICKETS[base], base)]))
     return path, rows, asm_bad
 
 
