@@ -367,6 +367,31 @@ int crs_wordpiece_encode(const uint8_t* text_dev, const int64_t* offsets_dev, in
   return e ? hip_fail((hipError_t)e, "wordpiece_encode launch") : CRS_OK;
 }
 
+int crs_unigram_encode(const uint8_t* text_dev, const int64_t* offsets_dev, int n_texts, int64_t n_bytes, const uint32_t* table_dev,
+                       int64_t table_len, const uint32_t* rep_pool_dev, int64_t rep_pool_len, const int32_t* slots_dev,
+                       const double* slot_scores_dev, int64_t n_slots, const uint32_t* vocab_pool_dev, int64_t vocab_pool_len,
+                       int max_probe, int lmax, double unk_score, int opts, int unk_id, int cls_id, int sep_id, int pad_id, int max_len,
+                       int32_t* ids_dev, int32_t* lens_dev, int32_t* flags_dev, void* stream) {
+  if (n_texts < 0 || n_bytes < 0) return fail(CRS_EINVAL, "bad n_texts / n_bytes");
+  if (max_len < 2 || max_len > 65536) return fail(CRS_EINVAL, "bad max_len (2 <= max_len <= 65536)");
+  if (opts < 0 || opts > 15) return fail(CRS_EINVAL, "bad opts (CRS_UNIGRAM_* bits)");
+  if (table_len < 0 || rep_pool_len < 0 || vocab_pool_len < 0) return fail(CRS_EINVAL, "bad table sizes");
+  if (n_slots < 1 || n_slots > (1ll << 30) || (n_slots & (n_slots - 1))) return fail(CRS_EINVAL, "n_slots must be a power of two");
+  if (max_probe < 1 || max_probe > n_slots || lmax < 1 || lmax > CRS_UNIGRAM_MAX_WORD)
+    return fail(CRS_EINVAL, "bad max_probe / lmax (1 <= max_probe <= n_slots, 1 <= lmax <= CRS_UNIGRAM_MAX_WORD)");
+  if (!(unk_score == unk_score)) return fail(CRS_EINVAL, "unk_score is NaN");
+  if (!offsets_dev || !slots_dev || !slot_scores_dev || !ids_dev || !lens_dev || !flags_dev || (n_bytes > 0 && !text_dev) ||
+      (table_len > 0 && !table_dev) || (rep_pool_len > 0 && !rep_pool_dev) || (vocab_pool_len > 0 && !vocab_pool_dev))
+    return fail(CRS_EINVAL, "null pointer");
+  if (((uintptr_t)slots_dev & 15) || ((uintptr_t)slot_scores_dev & 7)) return fail(CRS_EINVAL, "slots must be 16-byte, slot_scores 8-byte aligned");
+  if (n_texts == 0) return CRS_OK;
+  const int e = crs::unigram_encode_launch(text_dev, offsets_dev, n_texts, n_bytes, table_dev, table_len, rep_pool_dev, rep_pool_len,
+                                           slots_dev, slot_scores_dev, n_slots, vocab_pool_dev, vocab_pool_len, max_probe, lmax,
+                                           unk_score, opts, unk_id, cls_id, sep_id, pad_id, max_len, ids_dev, lens_dev, flags_dev,
+                                           (hipStream_t)stream);
+  return e ? hip_fail((hipError_t)e, "unigram_encode launch") : CRS_OK;
+}
+
 int crs_rescore_f32(const float* q32_dev, int nq, int dim, const float* shadow_dev, int64_t n_rows,
                     int64_t id_base, int k, float* scores_dev, int64_t* ids_dev, void* stream) {
   if (nq <= 0 || dim <= 0 || k <= 0 || k > 64 || n_rows <= 0) return fail(CRS_EINVAL, "bad sizes (k <= 64)");

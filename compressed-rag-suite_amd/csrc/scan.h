@@ -109,6 +109,11 @@ int wordpiece_encode_launch(const uint8_t* text, const int64_t* offsets, int n_t
                             int64_t table_len, const uint32_t* rep, int64_t rep_len, const int32_t* slots, int64_t n_slots,
                             const uint32_t* pool, int64_t pool_len, int max_probe, int lmax, int mode, int unk, int cls, int sep, int pad,
                             int hash_lo, int hash_span, int max_len, int* ids, int* lens, int* flags, hipStream_t stream);
+// unigram.hip: SentencePiece Unigram (normaliser table, Metaspace words, fp64 Viterbi) of UTF-8 texts, one workgroup per text
+int unigram_encode_launch(const uint8_t* text, const int64_t* offsets, int n_texts, int64_t n_bytes, const uint32_t* table,
+                          int64_t table_len, const uint32_t* rep, int64_t rep_len, const int32_t* slots, const double* slot_scores,
+                          int64_t n_slots, const uint32_t* pool, int64_t pool_len, int max_probe, int lmax, double unk_score, int opts,
+                          int unk, int cls, int sep, int pad, int max_len, int* ids, int* lens, int* flags, hipStream_t stream);
 
 // token_match.hip: BERTScore's greedy matching of pairs of token-state matrices, one workgroup per pair
 int token_match_launch(const float* a, const int* len_a, int seq_a, const float* b, const int* len_b, int seq_b, int n_pairs, int hidden,

@@ -20,7 +20,8 @@
 //   crs::merge_sorted / crs::merge_sorted_wire   the same for sorted lists, k 65 .. 1024
 //   crs::mmr_order         replaces the greedy MMR loop of _apply_diversity  (reference rag/retrieval.py:219-277)
 //   crs::token_match       the greedy matching behind bert_score.score  (reference evaluation/retrieval/rag_metrics.py:179-207)
-//   crs::wordpiece_encode           BERT basic tokenisation + WordPiece of UTF-8 texts on the device (the tokenizer inside SentenceTransformer.encode)
+//   crs::unigram_encode             SentencePiece Unigram tokenisation of UTF-8 texts on the device (XLM-RoBERTa's tokenizer.json)
+//   crs::wordpiece_encode          BERT basic tokenisation + WordPiece of UTF-8 texts on the device (the tokenizer inside SentenceTransformer.encode)
 //   crs::bm25_topk / crs::fuse_rrf   hybrid retrieval: exact BM25 scan over the token CSR, reciprocal rank fusion (new vs the reference)
 //   crs::pairs_above / crs::pairs_verify   near-duplicate detection: thresholded self-join of the slab, fp32 check (new vs the reference)
 //   crs::rerank_lexical    replaces the scoring, threshold and _rerank loops of retrieve_batch  (reference rag/retrieval.py:75-77, 196-217)
@@ -773,6 +774,39 @@ void wordpiece_encode(const Tensor& text, const Tensor& offsets, int64_t n_bytes
      "crs::wordpiece_encode");
 }
 
+// csrc/unigram.hip: the same tensors; slot_scores fp64 [n_slots]; opts = CRS_UNIGRAM_* bits
+void unigram_encode(const Tensor& text, const Tensor& offsets, int64_t n_bytes, const Tensor& table, const Tensor& rep_pool,
+                    const Tensor& slots, const Tensor& slot_scores, const Tensor& vocab_pool, int64_t max_probe, int64_t lmax,
+                    double unk_score, int64_t opts, int64_t unk_id, int64_t cls_id, int64_t sep_id, int64_t pad_id, Tensor ids, Tensor lens,
+                    Tensor flags) {
+  want(text, at::kByte, "text");
+  want(offsets, at::kLong, "offsets");
+  want(table, at::kInt, "table");
+  want(rep_pool, at::kInt, "rep_pool");
+  want(slots, at::kInt, "slots");
+  want(slot_scores, at::kDouble, "slot_scores");
+  want(vocab_pool, at::kInt, "vocab_pool");
+  want(ids, at::kInt, "ids");
+  want(lens, at::kInt, "lens");
+  want(flags, at::kInt, "flags");
+  same_device(text, {&offsets, &table, &rep_pool, &slots, &slot_scores, &vocab_pool, &ids, &lens, &flags}, "crs::unigram_encode");
+  TORCH_CHECK(offsets.dim() == 1 && offsets.numel() >= 1, "offsets must be int64 [n + 1]");
+  const int64_t n = offsets.numel() - 1;
+  TORCH_CHECK(n <= 0x7fffffff, "too many texts");
+  TORCH_CHECK(n_bytes >= 0 && n_bytes <= text.numel(), "n_bytes exceeds text");
+  TORCH_CHECK(slots.dim() == 2 && slots.size(1) == 4, "slots must be int32 [n_slots, 4]");
+  TORCH_CHECK(slot_scores.numel() == slots.size(0), "slot_scores must be fp64 [n_slots]");
+  TORCH_CHECK(ids.dim() == 2 && ids.size(0) == n && lens.numel() == n && flags.numel() == n, "ids [n, max_len], lens [n], flags [n]");
+  TORCH_CHECK(ids.size(1) <= 0x7fffffff, "max_len out of range");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(text.device());
+  ok(crs_unigram_encode(text.data_ptr<uint8_t>(), offsets.data_ptr<int64_t>(), (int)n, n_bytes, (const uint32_t*)table.data_ptr<int32_t>(),
+                        table.numel(), (const uint32_t*)rep_pool.data_ptr<int32_t>(), rep_pool.numel(), slots.data_ptr<int32_t>(),
+                        slot_scores.data_ptr<double>(), slots.size(0), (const uint32_t*)vocab_pool.data_ptr<int32_t>(), vocab_pool.numel(),
+                        (int)max_probe, (int)lmax, unk_score, (int)opts, (int)unk_id, (int)cls_id, (int)sep_id, (int)pad_id,
+                        (int)ids.size(1), ids.data_ptr<int32_t>(), lens.data_ptr<int32_t>(), flags.data_ptr<int32_t>(), cur_stream(text)),
+     "crs::unigram_encode");
+}
+
 // ---- encoder -------------------------------------------------------------------------------------------------
 // desc = [vocab_size, hidden, layers, heads, ffn, max_pos, pooling, flags (CRS_ENC_*, optional)]; weights = [word_emb, pos_emb, type_emb, emb_ln_g, emb_ln_b]
 // followed by 12 tensors per layer in crs_encoder_layer order (w_qkv b_qkv w_o b_o ln1_g ln1_b w_up b_up w_down b_down ln2_g ln2_b).
@@ -951,6 +985,9 @@ TORCH_LIBRARY(crs, m) {
   m.def("wordpiece_encode(Tensor text, Tensor offsets, int n_bytes, Tensor table, Tensor rep_pool, Tensor slots, Tensor vocab_pool, "
         "int max_probe, int lmax, int mode, int unk_id, int cls_id, int sep_id, int pad_id, int hash_lo, int hash_span, Tensor(a!) ids, "
         "Tensor(b!) lens, Tensor(c!) flags) -> ()");
+  m.def("unigram_encode(Tensor text, Tensor offsets, int n_bytes, Tensor table, Tensor rep_pool, Tensor slots, Tensor slot_scores, "
+        "Tensor vocab_pool, int max_probe, int lmax, float unk_score, int opts, int unk_id, int cls_id, int sep_id, int pad_id, "
+        "Tensor(a!) ids, Tensor(b!) lens, Tensor(c!) flags) -> ()");
   m.def("encoder_forward(Tensor ids, Tensor lens, Tensor[] weights, int[] desc, float ln_eps, Tensor(a!) workspace, Tensor(b!) out, "
         "Tensor(c!)? q16_out, int slab_type, bool normalize, Tensor(d!)? hidden_out) -> ()");
   m.def("encoder_forward_ex(Tensor ids, Tensor lens, Tensor[] weights, int[] desc, float ln_eps, Tensor(a!) workspace, Tensor(b!) out, "
@@ -993,6 +1030,7 @@ TORCH_LIBRARY_IMPL(crs, CUDA, m) {   // the HIP backend of torch-ROCm dispatches
   m.impl("bm25_topk", &bm25_topk);
   m.impl("fuse_rrf", &fuse_rrf);
   m.impl("wordpiece_encode", &wordpiece_encode);
+  m.impl("unigram_encode", &unigram_encode);
   m.impl("encoder_forward", &encoder_forward);
   m.impl("encoder_forward_ex", &encoder_forward_ex);
   m.impl("encoder_score_pairs", &encoder_score_pairs);

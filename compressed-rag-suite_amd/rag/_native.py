@@ -27,6 +27,9 @@ EXACT_MAX_CAP = 13312      # CRS_EXACT_MAX_CAP: longest per-query row list of cr
 EXACT_CAP = 1024           # default list length (12 KB of LDS per query in the re-rank)
 BM25_MAX_QUERIES = 64      # queries of one crs_bm25_topk launch
 WORDPIECE_TILE_BYTES = 1024   # CRS_WORDPIECE_TILE_BYTES: bytes of a text that crs_wordpiece_encode stages at a time
+UNIGRAM_TILE_BYTES = 1024     # CRS_UNIGRAM_TILE_BYTES: the same for crs_unigram_encode
+UNIGRAM_MAX_WORD = 128        # CRS_UNIGRAM_MAX_WORD: code points of the longest word it walks (U+2581 included); longer: the host's
+UNIGRAM_COLLAPSE, UNIGRAM_SINGLE_META, UNIGRAM_RUN_META, UNIGRAM_CRLF = 1, 2, 4, 8    # CRS_UNIGRAM_* option bits
 BM25_MAX_PAIRS = 4096      # CRS_BM25_MAX_PAIRS: (query, known token) pairs of one crs_bm25_topk launch
 PAIRS_TILE = 256           # CRS_PAIRS_TILE: tile edge of the near-duplicate join (csrc/join.hip)
 PAIRS_MAX_TILES = 1 << 22  # CRS_PAIRS_MAX_TILES: tile pairs of one crs_pairs_above_f16 launch
@@ -79,6 +82,9 @@ _SIGNATURES = {
     "crs_wordpiece_encode": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                      c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                      c_void_p, c_void_p]),
+    "crs_unigram_encode": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                   c_void_p, c_int64, c_int, c_int, ctypes.c_double, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                   c_void_p, c_void_p, c_void_p]),
     "crs_encoder_plan_describe": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t]),   # crs_encoder_desc by pointer
     "crs_rescore_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p,
                                 c_void_p, c_void_p]),
@@ -568,6 +574,23 @@ def wordpiece_encode(text, offsets, n_bytes: int, table, rep_pool, slots, vocab_
     with _translate():
         ops().wordpiece_encode(text, offsets, int(n_bytes), table, rep_pool, slots, vocab_pool, int(max_probe), int(lmax), int(mode),
                                int(unk_id), int(cls_id), int(sep_id), int(pad_id), int(hash_lo), int(hash_span), *out)
+    return out
+
+
+def unigram_encode(text, offsets, n_bytes: int, table, rep_pool, slots, slot_scores, vocab_pool, max_probe: int, lmax: int,
+                   unk_score: float, opts: int, unk_id: int, cls_id: int, sep_id: int, pad_id: int, max_len: int, out=None):
+    """Tokenise n UTF-8 texts in one launch (crs_unigram_encode, csrc/unigram.hip): text / offsets as wordpiece_encode; table /
+    rep_pool / slots / vocab_pool int32 and slot_scores fp64, the tensors of rag/_unigram.py; opts the UNIGRAM_* bits -> (ids int32
+    [n, max_len]: <s>, ids, </s>, pad; lens int32 [n]; flags int32 [n]: 1 = tokenise this text on the host instead).  All cuda.
+    No host sync; a missing kernel raises."""
+    import torch
+    n, dev = offsets.shape[0] - 1, text.device
+    if out is None:
+        out = (torch.empty((n, int(max_len)), dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
+               torch.empty(n, dtype=torch.int32, device=dev))
+    with _translate():
+        ops().unigram_encode(text, offsets, int(n_bytes), table, rep_pool, slots, slot_scores, vocab_pool, int(max_probe), int(lmax),
+                             float(unk_score), int(opts), int(unk_id), int(cls_id), int(sep_id), int(pad_id), *out)
     return out
 
 

@@ -164,7 +164,7 @@ class VocabHash:
     def __init__(self, vocab: Dict[str, int], prefix: str = "##"):
         items = []
         for tok, idx in vocab.items():
-            cont = tok.startswith(prefix) and len(tok) > len(prefix)
+            cont = bool(prefix) and tok.startswith(prefix) and len(tok) > len(prefix)     # prefix None: no continuation pieces (Unigram)
             body = tok[len(prefix):] if cont else tok
             if body:
                 items.append((tuple(ord(c) for c in body), cont, int(idx)))

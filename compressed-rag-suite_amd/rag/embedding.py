@@ -10,7 +10,7 @@ Model resolution, offline by construction (the reference fetches by hub name, wh
 here): ``model_path`` (additive key) or ``model_name`` may be a LOCAL sentence-transformers
 directory (config.json, model.safetensors, vocab.txt, optional sentence_bert_config.json and
 1_Pooling/config.json); else ``$CRS_MODEL_DIR/<basename of model_name>`` is tried; else, when
-``model_name`` is ``synthetic:<minilm|bge|tiny|mpnet|tiny-mpnet>`` or ``CRS_ALLOW_SYNTHETIC_WEIGHTS=1`` is set,
+``model_name`` is ``synthetic:<minilm|bge|tiny|mpnet|tiny-mpnet|tiny-xlmr|multilingual-minilm|multilingual-e5-base>`` or ``CRS_ALLOW_SYNTHETIC_WEIGHTS=1`` is set,
 seeded random weights of the named architecture are used with a hash tokeniser (plumbing and
 benchmarks only -- embeddings are then meaningless as language).  Anything else raises.
 """
@@ -42,6 +42,15 @@ _KNOWN = {
                               max_seq=384, ln_eps=1e-5, rel_buckets=32, pos_offset=2),
     "tiny-mpnet": dict(vocab_size=1000, hidden=64, layers=2, heads=4, ffn=256, max_pos=66, pooling="mean", max_seq=64,
                        rel_buckets=32, pos_offset=2),
+    # XLM-RoBERTa: BERT's layer stack, position ids from 2, one token-type row, <s> <pad> </s> <unk> in a SentencePiece Unigram
+    # vocabulary.  The two real shapes (paraphrase-multilingual-MiniLM-L12-v2, intfloat/multilingual-e5-base) are quoted from
+    # memory of the public config.json files: they only size synthetic weights
+    "tiny-xlmr": dict(vocab_size=1000, hidden=64, layers=2, heads=4, ffn=256, max_pos=66, pooling="mean", max_seq=64,
+                      ln_eps=1e-5, pos_offset=2),
+    "multilingual-minilm": dict(vocab_size=250037, hidden=384, layers=12, heads=12, ffn=1536, max_pos=514, pooling="mean",
+                                max_seq=128, ln_eps=1e-5, pos_offset=2),
+    "multilingual-e5-base": dict(vocab_size=250002, hidden=768, layers=12, heads=12, ffn=3072, max_pos=514, pooling="mean",
+                                 max_seq=512, ln_eps=1e-5, pos_offset=2),
 }
 _ALIASES = {"minilm": "all-minilm-l6-v2", "bge": "bge-base-en-v1.5", "bge-base": "bge-base-en-v1.5", "mpnet": "all-mpnet-base-v2"}
 REL_BIAS = "encoder.relative_attention_bias.weight"      # [buckets, heads], shared by all layers (MPNet)
@@ -154,27 +163,30 @@ def _load_local_dir(path: str):
         elif modes not in ([], ["mean_tokens"]):
             raise NotImplementedError(f"pooling mode(s) {modes} are not supported (mean and CLS are)")
     model_type = cfg.get("model_type", "bert")
-    if model_type not in ("bert", "mpnet"):
-        raise NotImplementedError(f"model_type '{model_type}' is not supported by this encoder (bert and mpnet are)")
+    if model_type not in ("bert", "mpnet", "xlm-roberta"):
+        raise NotImplementedError(f"model_type '{model_type}' is not supported by this encoder (bert, mpnet and xlm-roberta are)")
     rel_buckets = pos_offset = 0
     if model_type == "mpnet":
         rel_buckets = int(cfg.get("relative_attention_num_buckets", 32))
+    if model_type in ("mpnet", "xlm-roberta"):
         pos_offset = int(cfg.get("pad_token_id", 1)) + 1       # position ids count from padding_idx + 1
     shape = ModelShape(cfg["vocab_size"], cfg["hidden_size"], cfg["num_hidden_layers"], cfg["num_attention_heads"],
                        cfg["intermediate_size"], cfg["max_position_embeddings"],
-                       cfg.get("layer_norm_eps", 1e-5 if model_type == "mpnet" else 1e-12),
+                       cfg.get("layer_norm_eps", 1e-12 if model_type == "bert" else 1e-5),
                        pooling, min(max_seq, cfg["max_position_embeddings"] - pos_offset),
                        rel_buckets=rel_buckets, pos_offset=pos_offset)
     raw = load_file(os.path.join(tr_dir, "model.safetensors"))
     if model_type == "mpnet":
         weights = _mpnet_weights(raw, shape.hidden)
+    elif model_type == "xlm-roberta":     # XLMRobertaModel's names are BertModel's; the token-type table (one row) as shipped
+        weights = {(k[8:] if k.startswith("roberta.") else k): np.asarray(v, dtype=np.float32) for k, v in raw.items()}
     else:
         weights = {(k[5:] if k.startswith("bert.") else k): np.asarray(v, dtype=np.float32) for k, v in raw.items()}
     return shape, weights, tokenizer_from_model_dir(tr_dir), pre_lower, has_normalize
 
 
 class EmbeddingModel:
-    """Sentence encoder wrapper (BERT and MPNet checkpoints) running on the GPU."""
+    """Sentence encoder wrapper (BERT, MPNet and XLM-RoBERTa checkpoints) running on the GPU."""
 
     def __init__(self, config: dict):
         self.tokenize_mode = config.get('tokenize', 'host')     # additive key: 'device' = csrc/wordpiece.hip feeds the encoder
@@ -190,7 +202,7 @@ class EmbeddingModel:
         shape, weights, self.tokenizer = self._resolve(config)
         self._device_tokenizer = None
         if self.tokenize_mode == 'device':
-            from rag._wordpiece import tokenizer_spec
+            from rag._unigram import tokenizer_spec
             tokenizer_spec(self.tokenizer)      # NotImplementedError for a tokenizer the kernel does not restate; tables on first use
         if config.get('max_seq_length'):
             from dataclasses import replace
@@ -228,8 +240,8 @@ class EmbeddingModel:
             logger.warning(f"Using SYNTHETIC weights for architecture '{key}' (no checkpoint available offline)")
             shape = ModelShape(**{"ln_eps": 1e-12, **_KNOWN[key]})
             seed = int(config.get('synthetic_seed', 0))
-            # MPNet vocabularies open with <s> <pad> </s> <unk>
-            tok = HashTokenizer(shape.vocab_size, special=(0, 2, 1)) if shape.rel_buckets else HashTokenizer(shape.vocab_size)
+            # MPNet and XLM-RoBERTa vocabularies open with <s> <pad> </s> <unk>
+            tok = HashTokenizer(shape.vocab_size, special=(0, 2, 1)) if shape.pos_offset else HashTokenizer(shape.vocab_size)
             return shape, synthetic_weights(shape, seed), tok
         raise FileNotFoundError(
             f"No local checkpoint for '{name}': pass a sentence-transformers directory as model_name/model_path, "
@@ -254,10 +266,10 @@ class EmbeddingModel:
         outside its table's reach) go through self.tokenize and their rows are written in."""
         import time
         import torch
-        from rag._wordpiece import DeviceTokenizer
+        from rag._unigram import device_tokenizer
         dev = self.model.device
         if self._device_tokenizer is None:
-            self._device_tokenizer = DeviceTokenizer(self.tokenizer, dev)
+            self._device_tokenizer = device_tokenizer(self.tokenizer, dev)      # csrc/wordpiece.hip or csrc/unigram.hip, by type
         texts = [str(t).strip() for t in texts]
         if self._pre_lower:
             texts = [t.lower() for t in texts]
@@ -292,7 +304,7 @@ class EmbeddingModel:
         """-> (ids cuda int32 [n, max_seq]: what self.tokenize gives, right-padded with the pad id; lens cuda int32 [n]), tokenised
         by the device kernel whatever rag.embedding.tokenize says (additive)."""
         import torch
-        from rag._wordpiece import tokenizer_spec
+        from rag._unigram import tokenizer_spec
         tokenizer_spec(self.tokenizer)
         ids, lens = self._tokenize_device(list(texts))
         return ids, torch.from_numpy(lens).to(ids.device)

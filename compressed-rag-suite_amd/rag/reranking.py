@@ -32,8 +32,13 @@ _KNOWN_CE = {
     "tiny-ce": dict(vocab_size=1000, hidden=64, layers=2, heads=4, ffn=256, max_pos=64, pooling="cls", max_seq=64),
     # cross-encoder/ms-marco-MiniLM-L-6-v2 (public model card / config.json)
     "minilm-ce": dict(vocab_size=30522, hidden=384, layers=6, heads=12, ffn=1536, max_pos=512, pooling="cls", max_seq=512),
+    # tiny-ce as an XLM-RoBERTa classifier: position ids from 2, pairs <s> a </s></s> b </s> with every type id 0
+    "tiny-xlmr-ce": dict(vocab_size=1000, hidden=64, layers=2, heads=4, ffn=256, max_pos=66, pooling="cls", max_seq=64, ln_eps=1e-5,
+                         pos_offset=2),
 }
 _HEAD = ("pooler.dense.weight", "pooler.dense.bias", "classifier.weight", "classifier.bias")
+# XLMRobertaForSequenceClassification's head -> the internal names (classifier.dense first: classifier.out_proj shares its prefix)
+_XLMR_HEAD_NAMES = {"classifier.dense.": "pooler.dense.", "classifier.out_proj.": "classifier."}
 
 
 def synthetic_ce_weights(shape, seed: int = 0) -> Dict[str, np.ndarray]:
@@ -77,25 +82,42 @@ def load_cross_encoder_dir(path: str):
     with open(os.path.join(path, "config.json")) as fh:
         cfg = json.load(fh)
     model_type = cfg.get("model_type", "bert")
-    if model_type != "bert":
-        raise NotImplementedError(f"cross-encoder model_type '{model_type}' is not supported (bert is: RoBERTa, XLM-R and MPNet "
-                                  f"cross-encoders need another pair tokenizer and have no token types)")
+    if model_type not in ("bert", "xlm-roberta"):
+        raise NotImplementedError(f"cross-encoder model_type '{model_type}' is not supported (bert and xlm-roberta are: RoBERTa "
+                                  f"cross-encoders need a byte-level BPE tokenizer, MPNet ones have no token types)")
     labels = cfg.get("num_labels")
     if labels is None:
         labels = len(cfg["id2label"]) if "id2label" in cfg else 2          # transformers' default is two labels
     if int(labels) != 1:
         raise NotImplementedError(f"cross-encoder with {labels} labels is not supported (one relevance label is)")
     raw = load_file(os.path.join(path, "model.safetensors"))
-    weights = {(k[5:] if k.startswith("bert.") else k): np.asarray(v, dtype=np.float32) for k, v in raw.items()}
+    pos_offset = 0
+    if model_type == "xlm-roberta":
+        # RobertaClassificationHead (classifier.dense -> tanh -> classifier.out_proj on <s>) is the pooler + classifier head
+        # under other names; such checkpoints ship no roberta.pooler and need none
+        weights = {}
+        for k, v in raw.items():
+            for old, new in _XLMR_HEAD_NAMES.items():
+                if k.startswith(old):
+                    k = new + k[len(old):]
+                    break
+            else:
+                k = k[8:] if k.startswith("roberta.") else k
+            weights[k] = np.asarray(v, dtype=np.float32)
+        pos_offset = int(cfg.get("pad_token_id", 1)) + 1
+    else:
+        weights = {(k[5:] if k.startswith("bert.") else k): np.asarray(v, dtype=np.float32) for k, v in raw.items()}
     missing = [n for n in _HEAD if n not in weights]
     if missing:
-        raise NotImplementedError(f"{path}: not a BERT sequence classifier, {', '.join(missing)} missing "
-                                  f"(a cross-encoder needs bert.pooler.dense.* and classifier.*)")
+        raise NotImplementedError(f"{path}: not a BERT or XLM-RoBERTa sequence classifier, {', '.join(missing)} missing "
+                                  f"(a cross-encoder needs bert.pooler.dense.* and classifier.*, or classifier.dense.* and "
+                                  f"classifier.out_proj.*)")
     if weights["classifier.weight"].shape[0] != 1:
         raise NotImplementedError(f"cross-encoder with {weights['classifier.weight'].shape[0]} labels is not supported (one relevance label is)")
     max_pos = cfg["max_position_embeddings"]
     shape = ModelShape(cfg["vocab_size"], cfg["hidden_size"], cfg["num_hidden_layers"], cfg["num_attention_heads"],
-                       cfg["intermediate_size"], max_pos, cfg.get("layer_norm_eps", 1e-12), "cls", max_pos)
+                       cfg["intermediate_size"], max_pos, cfg.get("layer_norm_eps", 1e-12 if model_type == "bert" else 1e-5), "cls",
+                       max_pos - pos_offset, pos_offset=pos_offset)
     return shape, weights, tokenizer_from_model_dir(path), cfg
 
 
@@ -114,14 +136,16 @@ class CrossEncoderReranker:
         shape, weights, self.tokenizer, cfg = self._resolve(config)
         if config.get("max_seq_length"):
             from dataclasses import replace
-            shape = replace(shape, max_seq=min(int(config["max_seq_length"]), shape.max_pos))
+            shape = replace(shape, max_seq=min(int(config["max_seq_length"]), shape.max_pos - shape.pos_offset))
         if shape.max_seq < 5:
             raise ValueError("max_seq_length must be >= 5 for sentence pairs")
         self.activation = resolve_activation(config.get("activation", "auto"), cfg)
         self.shape = shape
         self._weights, self._device_pref = weights, config.get("device")
         self._model = None
-        self._tokens: Dict[str, Tuple[List[int], int]] = {}   # text -> (its first max_seq - 3 token ids, its full token count)
+        # special tokens of a pair: 3 in [CLS] a [SEP] b [SEP], 4 in XLM-RoBERTa's <s> a </s></s> b </s>
+        self._pair_seps, self._pair_typed = getattr(self.tokenizer, "pair_seps", 1), getattr(self.tokenizer, "pair_typed", True)
+        self._tokens: Dict[str, Tuple[List[int], int]] = {}   # text -> (its first max_seq - specials token ids, its full token count)
 
     def _resolve(self, config: dict):
         from rag._encoder import ModelShape
@@ -137,10 +161,13 @@ class CrossEncoderReranker:
             shape = ModelShape(**{"ln_eps": 1e-12, **_KNOWN_CE[key]})
             # a random model has no trained activation: logits, as the ms-marco checkpoints are configured
             cfg = {"sbert_ce_default_activation_function": "torch.nn.modules.linear.Identity"}
-            return shape, synthetic_ce_weights(shape, int(config.get("synthetic_seed", 0))), HashTokenizer(shape.vocab_size), cfg
+            tok = (HashTokenizer(shape.vocab_size, special=(0, 2, 1), pair_seps=2, pair_typed=False) if shape.pos_offset
+                   else HashTokenizer(shape.vocab_size))
+            return shape, synthetic_ce_weights(shape, int(config.get("synthetic_seed", 0))), tok, cfg
         raise FileNotFoundError(
             f"No local cross-encoder for '{name}': pass a BertForSequenceClassification directory as model_name/model_path, "
-            f"set CRS_MODEL_DIR, or use 'synthetic:tiny-ce' / 'synthetic:minilm-ce' (models cannot be downloaded here)")
+            f"set CRS_MODEL_DIR, or use 'synthetic:tiny-ce' / 'synthetic:minilm-ce' / 'synthetic:tiny-xlmr-ce' (models cannot be "
+            f"downloaded here)")
 
     @property
     def model(self):
@@ -159,7 +186,7 @@ class CrossEncoderReranker:
             if len(self._tokens) >= self.TOKEN_CACHE_CAP:
                 self._tokens.clear()
             ids = self.tokenizer.encode_body(str(text).strip())
-            got = self._tokens[text] = (ids[: self.shape.max_seq - 3], len(ids))
+            got = self._tokens[text] = (ids[: self.shape.max_seq - 2 - self._pair_seps], len(ids))
         return got
 
     def tokenize_pairs(self, pairs: Sequence[Tuple[str, str]]):
@@ -167,7 +194,7 @@ class CrossEncoderReranker:
         tok, out_ids, out_types = self.tokenizer, [], []
         for a, b in pairs:
             (ia, na), (ib, nb) = self._body(a), self._body(b)
-            ids, types = join_pair(ia, ib, tok.cls_id, tok.sep_id, self.shape.max_seq, na, nb)
+            ids, types = join_pair(ia, ib, tok.cls_id, tok.sep_id, self.shape.max_seq, na, nb, seps=self._pair_seps, typed=self._pair_typed)
             out_ids.append(ids)
             out_types.append(types)
         return out_ids, out_types

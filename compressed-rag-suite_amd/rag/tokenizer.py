@@ -95,19 +95,22 @@ def pair_lengths(n_a: int, n_b: int, budget: int) -> Tuple[int, int]:
 
 
 def join_pair(a_ids: Sequence[int], b_ids: Sequence[int], cls_id: int, sep_id: int, max_seq: int,
-              n_a: int = None, n_b: int = None) -> Tuple[List[int], List[int]]:
+              n_a: int = None, n_b: int = None, seps: int = 1, typed: bool = True) -> Tuple[List[int], List[int]]:
     """[CLS] a [SEP] b [SEP] with token types 0 0 .. 0 1 .. 1 from the two sides' ids WITHOUT special tokens, cut by
     pair_lengths to max_seq tokens in all.  n_a / n_b: the sides' full token counts when a_ids / b_ids are already cut (to no
-    fewer than max_seq - 3 tokens) -- the rule looks at the full lengths."""
+    fewer than max_seq - 3 tokens) -- the rule looks at the full lengths.  `seps=2, typed=False` is XLM-RoBERTa's pair,
+    <s> a </s></s> b </s> with every type id 0: four special tokens."""
     if max_seq < 5:
         raise ValueError("a pair needs max_seq >= 5: three special tokens and room for a token of each side")
-    k_a, k_b = pair_lengths(len(a_ids) if n_a is None else n_a, len(b_ids) if n_b is None else n_b, max_seq - 3)
+    k_a, k_b = pair_lengths(len(a_ids) if n_a is None else n_a, len(b_ids) if n_b is None else n_b, max_seq - 2 - seps)
     a, b = list(a_ids[:k_a]), list(b_ids[:k_b])
-    return [cls_id] + a + [sep_id] + b + [sep_id], [0] * (len(a) + 2) + [1] * (len(b) + 1)
+    return ([cls_id] + a + [sep_id] * seps + b + [sep_id],
+            [0] * (len(a) + 1 + seps) + [1 if typed else 0] * (len(b) + 1))
 
 
 class _PairMixin:
     """encode_pair for any tokenizer with encode(text, max_len) -> [cls] ids [sep] and cls_id / sep_id."""
+    pair_seps, pair_typed = 1, True           # join_pair's format: BERT's; the Unigram (XLM-RoBERTa) tokenisers say 2, False
 
     def encode_body(self, text: str) -> List[int]:
         """All token ids of `text`, no special tokens, no truncation."""
@@ -115,7 +118,8 @@ class _PairMixin:
 
     def encode_pair(self, a: str, b: str, max_seq: int) -> Tuple[List[int], List[int]]:
         """(ids, type_ids) of [CLS] a [SEP] b [SEP], truncated to max_seq by the 'longest_first' rule (pair_lengths)."""
-        return join_pair(self.encode_body(a), self.encode_body(b), self.cls_id, self.sep_id, max_seq)
+        return join_pair(self.encode_body(a), self.encode_body(b), self.cls_id, self.sep_id, max_seq, seps=self.pair_seps,
+                         typed=self.pair_typed)
 
 
 class WordPieceTokenizer(_PairMixin):
@@ -277,8 +281,8 @@ def special_tokens_from_model_dir(path: str) -> Dict[str, str]:
 
 
 def tokenizer_from_model_dir(path: str):
-    """The tokeniser a HuggingFace BERT or MPNet checkpoint directory describes (WordPiece; the special tokens are the
-    directory's own: special_tokens_from_model_dir).  Casing comes from the TOKENIZER's own
+    """The tokeniser a HuggingFace BERT, MPNet or XLM-RoBERTa checkpoint directory describes (WordPiece, or Unigram when
+    tokenizer.json's model.type says so; the special tokens are the directory's own: special_tokens_from_model_dir).  Casing comes from the TOKENIZER's own
     files, as in the reference stack (sentence-transformers hands the text to the HF tokenizer; the published
     all-MiniLM-L6-v2 ships sentence_bert_config.json do_lower_case=false next to an uncased vocab whose tokenizer
     lower-cases): tokenizer.json when the `tokenizers` library can load it, else vocab.txt with
@@ -286,6 +290,10 @@ def tokenizer_from_model_dir(path: str):
     import json
     tj = os.path.join(path, "tokenizer.json")
     special = special_tokens_from_model_dir(path)
+    if os.path.exists(tj):
+        with open(tj, encoding="utf-8") as fh:
+            if (json.load(fh).get("model") or {}).get("type") == "Unigram":      # XLM-RoBERTa's SentencePiece model
+                return make_unigram_tokenizer(tj, special=special)
     if os.path.exists(tj) and os.environ.get("CRS_TOKENIZER", "") != "python":
         try:
             return FastWordPieceTokenizer.from_tokenizer_json(tj, special=special)
@@ -304,9 +312,10 @@ def tokenizer_from_model_dir(path: str):
 class HashTokenizer(_PairMixin):
     """vocab-free stand-in: one id per basic token, crc32 into [1000, vocab)."""
 
-    def __init__(self, vocab_size: int, special=None):
-        """`special` = (cls, sep, pad) ids; default BERT's (101, 102, 0), or (1, 2, 0) in a toy vocabulary."""
-        self.vocab_size = vocab_size
+    def __init__(self, vocab_size: int, special=None, pair_seps: int = 1, pair_typed: bool = True):
+        """`special` = (cls, sep, pad) ids; default BERT's (101, 102, 0), or (1, 2, 0) in a toy vocabulary.  pair_seps /
+        pair_typed: the pair format (join_pair); 2, False stands in for an XLM-RoBERTa tokeniser."""
+        self.vocab_size, self.pair_seps, self.pair_typed = vocab_size, pair_seps, pair_typed
         self.cls_id, self.sep_id, self.pad_id = special or ((101, 102, 0) if vocab_size > 1000 else (1, 2, 0))
         self.lo = 1000 if vocab_size > 2000 else max(3, max(self.cls_id, self.sep_id, self.pad_id) + 1)
 
@@ -331,3 +340,296 @@ def pad_batch(seqs: Sequence[Sequence[int]], pad_id: int = 0, short_steps: Seque
     for r, s in enumerate(seqs):
         out[r, : len(s)] = s
     return out, lens
+
+
+# ---- Unigram (SentencePiece) tokenisation: XLM-RoBERTa checkpoints -------------------------------------------------------------------
+META = "▁"
+# Rust's char::is_whitespace (the White_Space property), which WhitespaceSplit splits on; str.isspace() also takes U+001C-1F
+RUST_WHITESPACE = frozenset([0x09, 0x0A, 0x0B, 0x0C, 0x0D, 0x20, 0x85, 0xA0, 0x1680, 0x2028, 0x2029, 0x202F, 0x205F, 0x3000]
+                            + list(range(0x2000, 0x200B)))
+UNK_PENALTY = 10.0             # the unknown candidate's score is min_score - 10 (kUnkPenalty)
+
+
+def _unsupported(field: str, got) -> NotImplementedError:
+    return NotImplementedError(f"this Unigram tokenizer.json is not restated: {field} = {got!r}")
+
+
+class UnigramPipeline:
+    """What a Unigram tokenizer.json says, field by field (unigram_pipeline)."""
+
+    def __init__(self):
+        self.steps: List[tuple] = []        # ("nfkc",) ("nfc",) ("lower",) ("strip", left, right) ("replace", pattern, content) ("precompiled", b64)
+        self.ws_split = False               # WhitespaceSplit in front of Metaspace
+        self.prepend = "always"             # Metaspace prepend_scheme
+        self.vocab: List[Tuple[str, float]] = []
+        self.unk_id = 0
+        self.single: List[tuple] = []       # ("special", id) / ("seq", "A")
+        self.pair: List[tuple] = []         # the same with type ids: ("special", id, type) / ("seq", "A" | "B", type)
+        self.added: List[dict] = []
+
+
+def unigram_pipeline(cfg: dict) -> UnigramPipeline:
+    """The restated fields of a tokenizer.json with model.type Unigram; NotImplementedError, naming the field, for any other."""
+    p = UnigramPipeline()
+    norm = cfg.get("normalizer")
+    norms = [] if norm is None else norm["normalizers"] if norm.get("type") == "Sequence" else [norm]
+    for i, n in enumerate(norms):
+        kind, where = n.get("type"), f"normalizer[{i}]"
+        if kind == "NFKC":
+            p.steps.append(("nfkc",))
+        elif kind == "NFC":
+            p.steps.append(("nfc",))
+        elif kind == "Lowercase":
+            p.steps.append(("lower",))
+        elif kind == "Strip":
+            p.steps.append(("strip", bool(n.get("strip_left", True)), bool(n.get("strip_right", True))))
+        elif kind == "Precompiled":
+            p.steps.append(("precompiled", n.get("precompiled_charsmap")))
+        elif kind == "Replace":
+            pat = n.get("pattern") or {}
+            if pat != {"Regex": " {2,}"}:
+                raise _unsupported(where + ".pattern", pat)
+            if n.get("content") not in (META, " "):
+                raise _unsupported(where + ".content", n.get("content"))
+            p.steps.append(("replace", " {2,}", n["content"]))
+        else:
+            raise _unsupported(where + ".type", kind)
+    pre = cfg.get("pre_tokenizer") or {}
+    pres = pre.get("pretokenizers", []) if pre.get("type") == "Sequence" else [pre]
+    if len(pres) == 2 and pres[0].get("type") == "WhitespaceSplit":
+        p.ws_split, pres = True, pres[1:]
+    if len(pres) != 1 or pres[0].get("type") != "Metaspace":
+        raise _unsupported("pre_tokenizer.type", [x.get("type") for x in pres] if len(pres) != 1 else pres[0].get("type"))
+    ms = pres[0]
+    if ms.get("replacement", META) != META:
+        raise _unsupported("pre_tokenizer.replacement", ms.get("replacement"))
+    if "prepend_scheme" in ms:
+        p.prepend = ms["prepend_scheme"]
+    elif "add_prefix_space" in ms:                     # the spelling of tokenizers < 0.15
+        p.prepend = "always" if ms["add_prefix_space"] else "never"
+    if p.prepend not in ("always", "never", "first"):
+        raise _unsupported("pre_tokenizer.prepend_scheme", p.prepend)
+    if ms.get("split", True) is not True:
+        raise _unsupported("pre_tokenizer.split", ms.get("split"))
+    model = cfg.get("model") or {}
+    if model.get("type") != "Unigram":
+        raise _unsupported("model.type", model.get("type"))
+    if model.get("byte_fallback", False):
+        raise _unsupported("model.byte_fallback", model.get("byte_fallback"))
+    if model.get("unk_id") is None:
+        raise _unsupported("model.unk_id", None)
+    p.vocab = [(str(t), float(sc)) for t, sc in model["vocab"]]
+    p.unk_id = int(model["unk_id"])
+    post = cfg.get("post_processor") or {}
+    if post.get("type") != "TemplateProcessing":
+        raise _unsupported("post_processor.type", post.get("type"))
+    ids = {k: v["ids"] for k, v in (post.get("special_tokens") or {}).items()}
+    for key, dst in (("single", p.single), ("pair", p.pair)):
+        for part in post.get(key) or []:
+            if "SpecialToken" in part:
+                sp = part["SpecialToken"]
+                if len(ids.get(sp["id"], ())) != 1:
+                    raise _unsupported(f"post_processor.special_tokens[{sp['id']}].ids", ids.get(sp["id"]))
+                dst.append(("special", int(ids[sp["id"]][0]), int(sp.get("type_id", 0))))
+            else:
+                dst.append(("seq", part["Sequence"]["id"], int(part["Sequence"].get("type_id", 0))))
+    kinds = [x[0] for x in p.single]
+    if kinds != ["special", "seq", "special"]:
+        raise _unsupported("post_processor.single", post.get("single"))
+    p.added = [a for a in cfg.get("added_tokens") or [] if a.get("content")]
+    for a in p.added:
+        if a.get("normalized") or a.get("single_word"):
+            raise _unsupported(f"added_tokens[{a['content']}]", {k: a.get(k) for k in ("normalized", "single_word")})
+    return p
+
+
+def _library_normalizer(steps):
+    """The `tokenizers` normaliser object of `steps` without their Replace entries (those look at neighbours)."""
+    import base64
+    from tokenizers import normalizers as N
+    objs = []
+    for st in steps:
+        if st[0] == "nfkc":
+            objs.append(N.NFKC())
+        elif st[0] == "nfc":
+            objs.append(N.NFC())
+        elif st[0] == "lower":
+            objs.append(N.Lowercase())
+        elif st[0] == "strip":
+            objs.append(N.Strip(left=st[1], right=st[2]))
+        elif st[0] == "precompiled":
+            objs.append(N.Precompiled(base64.b64decode(st[1])))
+    return N.Sequence(objs)
+
+
+def unigram_viterbi(word: str, pieces: Dict[str, Tuple[int, float]], lmax: int, unk_id: int, unk_score: float,
+                    add=lambda a, b: a + b) -> List[int]:
+    """The ids of one pre-token, as the library's Unigram::encode_optimized walks it: best[end] takes a candidate only when it is
+    strictly greater, candidates come by start ascending (so among equal sums the earliest start wins); a start with no
+    one-character piece gets an unknown candidate of one character at unk_score; unknown ids next to each other fuse into one.
+    `add` sums two scores (fp64 by default: what the library does; the near-tie test passes an fp32 one)."""
+    n = len(word)
+    best: List[float] = [0.0] * (n + 1)
+    back: List[int] = [-1] * (n + 1)
+    tok: List[int] = [0] * (n + 1)
+    for s in range(n):
+        single = False
+        for e in range(s + 1, min(n, s + lmax) + 1):
+            hit = pieces.get(word[s:e])
+            if hit is None:
+                continue
+            cand = add(best[s], hit[1])
+            if back[e] < 0 or cand > best[e]:
+                best[e], back[e], tok[e] = cand, s, hit[0]
+            if e == s + 1:
+                single = True
+        if not single:
+            cand = add(best[s], unk_score)
+            if back[s + 1] < 0 or cand > best[s + 1]:
+                best[s + 1], back[s + 1], tok[s + 1] = cand, s, unk_id
+    out: List[int] = []
+    e = n
+    while e > 0:
+        if not (tok[e] == unk_id and out and out[-1] == unk_id):
+            out.append(tok[e])
+        e = back[e]
+    return out[::-1]
+
+
+class UnigramTokenizer(_PairMixin):
+    """The specification: a Unigram tokenizer.json in plain Python (normaliser, WhitespaceSplit + Metaspace, Viterbi over the
+    fp64 scores, TemplateProcessing).  `Precompiled` (SentencePiece's charsmap) goes through the `tokenizers` library's own
+    normaliser object and raises ImportError without it.  Added tokens are cut out of the raw text before normalisation (their
+    lstrip / rstrip flags are not restated)."""
+    pair_seps, pair_typed = 2, False
+
+    def __init__(self, cfg: dict, special: Dict[str, str] = None):
+        self.pipeline = p = unigram_pipeline(cfg)
+        self.pieces: Dict[str, Tuple[int, float]] = {}
+        for i, (t, sc) in enumerate(p.vocab):
+            self.pieces[t] = (i, sc)              # a repeated piece keeps its last id, as the library's map does
+        self.lmax = max((len(t) for t in self.pieces), default=1)
+        self.unk_id = p.unk_id
+        self.unk_score = min(sc for _, sc in p.vocab) - UNK_PENALTY
+        self.cls_id, self.sep_id = p.single[0][1], p.single[2][1]
+        sp = special or {}
+        self.pad_id = self.pieces.get(sp.get("pad", "<pad>"), (0, 0.0))[0]
+        if "cls" in sp and self.pieces.get(sp["cls"], (self.cls_id,))[0] != self.cls_id:
+            raise ValueError(f"the post-processor opens with id {self.cls_id}, the model directory names {sp['cls']!r}")
+        if p.pair:
+            self.pair_seps = sum(1 for x in p.pair if x[0] == "special") - 2
+            self.pair_typed = any(x[2] for x in p.pair)
+        self._lib_norm = _library_normalizer(p.steps) if any(st[0] == "precompiled" for st in p.steps) else None
+        self._added_rx = re.compile("(" + "|".join(re.escape(a["content"]) for a in p.added) + ")") if p.added else None
+
+    @classmethod
+    def from_tokenizer_json(cls, path: str, special=None) -> "UnigramTokenizer":
+        import json
+        with open(path, encoding="utf-8") as fh:
+            return cls(json.load(fh), special or special_tokens_from_model_dir(os.path.dirname(path)))
+
+    def normalize(self, text: str) -> str:
+        steps = self.pipeline.steps
+        if self._lib_norm is not None:            # every step but Replace in the library, then the Replace steps
+            text = self._lib_norm.normalize_str(text)
+            steps = [st for st in steps if st[0] == "replace"]
+        for st in steps:
+            if st[0] == "nfkc":
+                text = unicodedata.normalize("NFKC", text)
+            elif st[0] == "nfc":
+                text = unicodedata.normalize("NFC", text)
+            elif st[0] == "lower":
+                text = text.lower()
+            elif st[0] == "strip":
+                ws = "".join(map(chr, sorted(RUST_WHITESPACE)))
+                text = text.lstrip(ws) if st[1] else text
+                text = text.rstrip(ws) if st[2] else text
+            elif st[0] == "replace":
+                text = re.sub(st[1], st[2], text)
+        return text
+
+    def pre_tokenize(self, text: str, first: bool = True) -> List[str]:
+        """The pre-tokens of a normalised text: each opens with the metaspace (unless the prepend scheme leaves it off)."""
+        p = self.pipeline
+        if p.ws_split:
+            words, cur = [], ""
+            for ch in text:
+                if ord(ch) in RUST_WHITESPACE:
+                    if cur:
+                        words.append(cur)
+                    cur = ""
+                else:
+                    cur += ch
+            if cur:
+                words.append(cur)
+        else:
+            words = [text] if text else []
+        out: List[str] = []
+        for i, w in enumerate(words):
+            w = w.replace(" ", META)
+            if (p.prepend == "always" or (p.prepend == "first" and first and i == 0)) and not w.startswith(META):
+                w = META + w
+            cur = ""
+            for ch in w:                          # split in front of every metaspace (MergedWithNext)
+                if ch == META and cur:
+                    out.append(cur)
+                    cur = ""
+                cur += ch
+            if cur:
+                out.append(cur)
+        return out
+
+    def _ids(self, text: str, limit: int) -> List[int]:
+        ids: List[int] = []
+        parts = self._added_rx.split(text) if self._added_rx is not None else [text]
+        for k, part in enumerate(parts):
+            if k & 1:                             # an added token, as written
+                ids.append(self.pieces[part][0])
+                continue
+            for w in self.pre_tokenize(self.normalize(part), first=(k == 0)):
+                ids.extend(unigram_viterbi(w, self.pieces, self.lmax, self.unk_id, self.unk_score))
+                if len(ids) >= limit:
+                    return ids[:limit]
+        return ids[:limit]
+
+    def encode_body(self, text: str) -> List[int]:
+        return self._ids(text, 1 << 30)
+
+    def encode(self, text: str, max_len: int) -> List[int]:
+        return [self.cls_id] + self._ids(text, max_len - 2) + [self.sep_id]
+
+    def encode_batch(self, texts: Sequence[str], max_len: int) -> List[List[int]]:
+        return [self.encode(t, max_len) for t in texts]
+
+
+class FastUnigramTokenizer(FastWordPieceTokenizer):
+    """tokenizer.json as shipped, through the `tokenizers` library: what the product uses when the library is importable.
+    `UnigramTokenizer` stays the specification and the fallback; tests/test_unigram_cpu.py holds the two to identical ids."""
+    pair_seps, pair_typed = 2, False
+
+    @classmethod
+    def from_tokenizer_json(cls, path: str, special=None) -> "FastUnigramTokenizer":
+        from tokenizers import Tokenizer
+        tok = Tokenizer.from_file(path)
+        tok.no_padding()
+        sp = special or special_tokens_from_model_dir(os.path.dirname(path))
+        ids = [tok.token_to_id(sp[t]) for t in ("cls", "sep", "pad")]
+        if ids[0] is None or ids[1] is None:
+            raise ValueError(f"{path}: {sp['cls']} / {sp['sep']} are not in the vocabulary")
+        return cls(tok, ids[0], ids[1], ids[2] if ids[2] is not None else 0)
+
+    def encode_body(self, text: str) -> List[int]:
+        self._tok.no_truncation()
+        self._max_len = None
+        return self._tok.encode(text, add_special_tokens=False).ids
+
+
+def make_unigram_tokenizer(tokenizer_json: str, special=None):
+    """FastUnigramTokenizer when the `tokenizers` library is importable (CRS_TOKENIZER=python forces the restatement), else
+    UnigramTokenizer."""
+    if os.environ.get("CRS_TOKENIZER", "") != "python":
+        try:
+            return FastUnigramTokenizer.from_tokenizer_json(tokenizer_json, special=special)
+        except ImportError:
+            pass
+    return UnigramTokenizer.from_tokenizer_json(tokenizer_json, special=special)

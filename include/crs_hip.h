@@ -377,6 +377,38 @@ int crs_wordpiece_encode(const uint8_t* text_dev, const int64_t* offsets_dev, in
                          int sep_id, int pad_id, int hash_lo, int hash_span, int max_len, int32_t* ids_dev, int32_t* lens_dev,
                          int32_t* flags_dev, void* stream);
 
+/* ---- tokenisation: SentencePiece Unigram of a batch of UTF-8 texts, as the `tokenizers` library runs XLM-RoBERTa's tokenizer.json
+ * (normaliser, Replace(" {2,}"), WhitespaceSplit + Metaspace, Unigram, <s> $A </s>) -- the tokenizer inside SentenceTransformer.encode,
+ * /root/reference/rag/embedding.py:65-71, when the model is a multilingual one (additive to ABI 3; csrc/unigram.hip).  One workgroup
+ * per text; the tables are built by rag/_unigram.py.  text_dev, offsets_dev, ids_dev, lens_dev, flags_dev: as crs_wordpiece_encode.
+ *   table_dev        uint32 [table_len]     one entry per code point: bits 0-2 class (0 drop, 3 keep, 4 fallback) | bits 3-4 n, the
+ *                                           replacement's length (0-3) | bits 5-10 the kind of each replacement code point, two bits
+ *                                           each (0 character, 1 U+0020, 2 other white space, 3 U+2581) | bits 11-31 the replacement
+ *                                           (n = 1) or its offset in rep_pool_dev (n >= 2).  A code point >= table_len is fallback
+ *   slots_dev        int32 [n_slots, 4]     the pieces, laid out as crs_wordpiece_encode's slots; no continuation bit, every hash
+ *                                           starts from 2166136261
+ *   slot_scores_dev  fp64 [n_slots]         the score of the piece in each slot (tokenizer.json's, unrounded)
+ *   lmax             code points of the longest piece; 1..CRS_UNIGRAM_MAX_WORD
+ *   unk_score        the score of an unknown character: the smallest piece score - 10
+ *   opts             CRS_UNIGRAM_* bits
+ * Per word (U+2581 + its characters): best[end] is replaced only by a strictly greater fp64 sum best[start] + score, starts
+ * ascending; a start with no one-character piece gets a one-character candidate of unk_id at unk_score; unk_ids next to each other
+ * in a word fuse into one.  flags_dev: 1 = a fallback code point, or a word of more than CRS_UNIGRAM_MAX_WORD code points (U+2581
+ * included), in the part that was read: tokenise the text on the host.  Malformed UTF-8 or tables give wrong ids, never an access
+ * outside the buffers.  Limits (CRS_EINVAL otherwise): n_texts >= 0; 2 <= max_len <= 65536; slot_scores_dev 8-byte aligned.
+ * Deterministic; no workspace, no host synchronisation. */
+#define CRS_UNIGRAM_TILE_BYTES 1024    /* bytes of a text staged at a time */
+#define CRS_UNIGRAM_MAX_WORD 128       /* code points of the longest word the kernel walks, its U+2581 included */
+#define CRS_UNIGRAM_COLLAPSE 1         /* a run of two or more U+0020 counts as one thing (a Replace(" {2,}") step exists) */
+#define CRS_UNIGRAM_SINGLE_META 2      /* a lone U+0020 is a metaspace (no WhitespaceSplit); else it ends a word */
+#define CRS_UNIGRAM_RUN_META 4         /* such a run is a metaspace; else it ends a word */
+#define CRS_UNIGRAM_CRLF 8             /* CR in front of LF adds nothing: the normaliser turns the two into what LF alone gives */
+int crs_unigram_encode(const uint8_t* text_dev, const int64_t* offsets_dev, int n_texts, int64_t n_bytes, const uint32_t* table_dev,
+                       int64_t table_len, const uint32_t* rep_pool_dev, int64_t rep_pool_len, const int32_t* slots_dev,
+                       const double* slot_scores_dev, int64_t n_slots, const uint32_t* vocab_pool_dev, int64_t vocab_pool_len,
+                       int max_probe, int lmax, double unk_score, int opts, int unk_id, int cls_id, int sep_id, int pad_id, int max_len,
+                       int32_t* ids_dev, int32_t* lens_dev, int32_t* flags_dev, void* stream);
+
 /* ---- BERTScore token matching: the step behind the encoder in bert_score.score -- evaluation/retrieval/rag_metrics.py:179-207 ----
  * (additive to ABI 3; csrc/token_match.hip).  Scores `n_pairs` (candidate, reference) pairs of token states in one launch, one
  * workgroup per pair:

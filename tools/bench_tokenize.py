@@ -14,6 +14,11 @@ the punctuation, so frequent words are one id and rare ones split.
     tokens/s counts the ids handed to the encoder (special tokens included).  One more device pass with a synchronise after every
     stage gives the split host encode / upload / kernel / read-back.
 (b) embed_device of synthetic:minilm over the same texts under tokenize 'host' and 'device', alternating: texts/s.
+--unigram runs the Unigram leg alone (csrc/unigram.hip): a SentencePiece-style vocabulary over the same corpus (`▁word` for the
+20 000 most frequent words, suffixes, letters; scores -log of a Zipf rank), XLM-R's pipeline with NFKC, max_seq 256.  It reports
+texts/s and tokens/s of the device path (UTF-8 encode, upload, kernel, read-back of lens / flags) and of the kernel alone, of the
+`tokenizers` library's encode_batch on RAYON_NUM_THREADS threads (16 unless set), of the Python restatement on a sample, and the
+share of texts the kernel flags for the host.
 A JSON array, one record per line, to --out (and stdout)."""
 import argparse
 import json
@@ -83,6 +88,109 @@ def make_corpus(n_texts, chars, foreign_pct, seed=0):
     return texts, {v: i for i, v in enumerate(out)}
 
 
+def unigram_config(words):
+    """A tokenizer.json (as a dict) over the corpus' words: XLM-R's pipeline with NFKC in place of the Precompiled charsmap."""
+    import math
+    meta = "\u2581"
+    vocab = [("<s>", 0.0), ("<pad>", 0.0), ("</s>", 0.0), ("<unk>", 0.0), (meta, -3.0)]
+    vocab += [(meta + w, -math.log(r + 2.0) - 2.0) for r, w in enumerate(words[:20_000])]
+    suffixes = sorted({w[k:] for w in words[20_000:] for k in (2, 3, 4) if len(w) > k})[:4_000]
+    vocab += [(x, -9.0 - 0.001 * i) for i, x in enumerate(suffixes)]
+    vocab += [(meta + w[:k], -10.0 - 0.0001 * i) for i, w in enumerate(words[20_000:24_000]) for k in (2, 3)]
+    singles = list("abcdefghijklmnopqrstuvwxyz0123456789.,!?-'") + ["\u4e2d", "\u6587", "\u5206", "\u8bcd", "\u00e9", "\u00ef", "\u00fc", "\u00df"]
+    vocab += [(c, -12.0 - 0.01 * i) for i, c in enumerate(singles)] + [(c.upper(), -13.0 - 0.01 * i) for i, c in enumerate(singles[:26])]
+    seen, out = set(), []
+    for t, sc in vocab:
+        if t not in seen:
+            seen.add(t)
+            out.append([t, sc])
+    special = lambda t: {"SpecialToken": {"id": t, "type_id": 0}}      # noqa: E731
+    seq = lambda t: {"Sequence": {"id": t, "type_id": 0}}              # noqa: E731
+    return {"version": "1.0", "truncation": None, "padding": None,
+            "added_tokens": [{"id": i, "content": t, "single_word": False, "lstrip": False, "rstrip": False, "normalized": False,
+                              "special": True} for i, t in enumerate(("<s>", "<pad>", "</s>", "<unk>"))],
+            "normalizer": {"type": "Sequence", "normalizers": [{"type": "NFKC"}, {"type": "Replace", "pattern": {"Regex": " {2,}"}, "content": meta}]},
+            "pre_tokenizer": {"type": "Sequence", "pretokenizers": [{"type": "WhitespaceSplit"},
+                                                                    {"type": "Metaspace", "replacement": meta, "prepend_scheme": "always", "split": True}]},
+            "post_processor": {"type": "TemplateProcessing", "single": [special("<s>"), seq("A"), special("</s>")],
+                               "pair": [special("<s>"), seq("A"), special("</s>"), special("</s>"), seq("B"), special("</s>")],
+                               "special_tokens": {"<s>": {"id": "<s>", "ids": [0], "tokens": ["<s>"]}, "</s>": {"id": "</s>", "ids": [2], "tokens": ["</s>"]}}},
+            "decoder": None, "model": {"type": "Unigram", "unk_id": 3, "vocab": out, "byte_fallback": False}}
+
+
+def unigram_leg(args):
+    """The Unigram records (see the module's docstring)."""
+    os.environ.setdefault("RAYON_NUM_THREADS", "16")
+    os.environ.setdefault("TOKENIZERS_PARALLELISM", "true")
+    import numpy as np
+    import torch
+    from rag import _native as nat
+    from rag import _unigram as ug
+    from rag.tokenizer import FastUnigramTokenizer, UnigramTokenizer
+    nat.require_gpu()
+    rng = np.random.default_rng(0)
+    words = make_words(rng, 30_000)                   # the first draw of make_corpus(seed=0): the corpus' own words
+    texts, _ = make_corpus(args.texts, args.chars, args.foreign)
+    texts = [t.strip() for t in texts]
+    cfg = unigram_config(words)
+    special = {"cls": "<s>", "sep": "</s>", "pad": "<pad>", "unk": "<unk>"}
+    py_tok = UnigramTokenizer(cfg, special)
+    lib_tok = None
+    try:
+        from tokenizers import Tokenizer
+        lib = Tokenizer.from_str(json.dumps(cfg))
+        lib.no_padding()
+        lib_tok = FastUnigramTokenizer(lib, 0, 2, 1)
+    except ImportError:
+        pass
+    max_seq = 256
+    n_bytes = sum(len(t.encode("utf-8")) for t in texts)
+    records = [{"what": "corpus", "texts": len(texts), "utf8_bytes": n_bytes, "vocab": len(cfg["model"]["vocab"]), "max_seq": max_seq}]
+    t0 = time.perf_counter()
+    dt = ug.device_tokenizer(lib_tok or py_tok, "cuda")
+    built = time.perf_counter() - t0
+
+    def device_pass(timings=None):
+        ids, lens, flags, host = dt.encode(texts, max_seq, timings)
+        back = torch.stack((lens, flags)).cpu().numpy()
+        return ids, back
+
+    ids, back = device_pass()
+    n_tokens, flagged = int(back[0].sum()), int(back[1].sum())
+    sample = list(range(0, len(texts), max(1, len(texts) // 256)))[:256]
+    t0 = time.perf_counter()
+    want = [py_tok.encode(texts[i], max_seq) for i in sample]
+    py_s = time.perf_counter() - t0
+    got = ids.cpu().numpy()
+    wrong = sum(1 for i, w in zip(sample, want) if not back[1][i] and got[i, : back[0][i]].tolist() != w)
+    dev_t, lib_t, kernel_t = [], [], []
+    for _ in range(args.reps):
+        t0 = time.perf_counter()
+        device_pass()
+        dev_t.append(time.perf_counter() - t0)
+        split = {}
+        device_pass(split)
+        kernel_t.append(split["kernel_s"])
+        if lib_tok is not None:
+            t0 = time.perf_counter()
+            lib_ids = lib_tok.encode_batch(texts, max_seq)
+            lib_t.append(time.perf_counter() - t0)
+    rec = {"what": "unigram", "host_class": type(lib_tok or py_tok).__name__, "tokens": n_tokens, "flagged_texts": flagged,
+           "flagged_share": round(flagged / len(texts), 4), "sample_rows_differing_from_restatement": wrong,
+           "tables_s": round(built, 3), "device": spread(dev_t), "kernel": spread(kernel_t), "device_split_s": {k: round(v, 5) for k, v in split.items()},
+           "device_texts_per_s": round(len(texts) / statistics.median(dev_t)), "device_tokens_per_s": round(n_tokens / statistics.median(dev_t)),
+           "kernel_texts_per_s": round(len(texts) / statistics.median(kernel_t)), "kernel_tokens_per_s": round(n_tokens / statistics.median(kernel_t)),
+           "python_texts_per_s": round(len(sample) / py_s, 1), "python_tokens_per_s": round(sum(len(w) for w in want) / py_s)}
+    if lib_t:
+        lib_tokens = sum(len(x) for x in lib_ids)
+        rec.update({"library": spread(lib_t), "library_threads": int(os.environ["RAYON_NUM_THREADS"]),
+                    "library_texts_per_s": round(len(texts) / statistics.median(lib_t)),
+                    "library_tokens_per_s": round(lib_tokens / statistics.median(lib_t))})
+    records.append(rec)
+    print(json.dumps(rec), flush=True)
+    return records
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--texts", type=int, default=4096)
@@ -90,7 +198,15 @@ def main():
     ap.add_argument("--foreign", type=float, default=3.0)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tokenize_bench.json"))
+    ap.add_argument("--unigram", action="store_true", help="run the Unigram leg alone (default --out: profiles/tokenize_unigram_bench.json)")
     args = ap.parse_args()
+    if args.unigram:
+        out = args.out if args.out != ap.get_default("out") else os.path.join(ROOT, "profiles", "tokenize_unigram_bench.json")
+        records = unigram_leg(args)
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, "w") as fh:
+            fh.write("[\n" + ",\n".join(json.dumps(r) for r in records) + "\n]\n")
+        return
 
     import numpy as np
     import torch
