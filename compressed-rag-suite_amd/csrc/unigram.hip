@@ -15,11 +15,11 @@
 //      of one character at unk_score where no one-character piece matches; then the back-pointers are walked, unknowns next to
 //      each other fusing into one id.  Best sum, piece id and back-pointer sit in LDS arrays parallel to the word array;
 //   5. a third scan, over the words' id counts, places the ids in the output row.
-// The word that the tile's end cuts is carried to the front of the raw array (metaspace first), and so is a run of U+0020 at the
-// tile's end, as one or two elements.  A word of more than kMaxWord code points (its metaspace included) flags the text for the
-// host: Unigram has no rule that shortens a word.  The walk stops once max_len - 2 ids exist.  Every loop is bounded: tiles by the
-// text's length, starts and ends by the word's length, lengths by lmax, probes by max_probe.  No atomics on global memory, no
-// workspace; the same input gives the same output.
+// The word that the tile's end cuts is carried to the front of the raw array (metaspace first), be it a lone metaspace; where
+// runs of U+0020 collapse (CRS_UNIGRAM_COLLAPSE), a run at the tile's end is carried instead, as one or two elements.  A word of
+// more than kMaxWord code points (its metaspace included) flags the text for the host: Unigram has no rule that shortens a word.
+// The walk stops once max_len - 2 ids exist.  Every loop is bounded: tiles by the text's length, starts and ends by the word's
+// length, lengths by lmax, probes by max_probe.  No atomics on global memory, no workspace; the same input gives the same output.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -184,11 +184,12 @@ __global__ __launch_bounds__(kThreads) void unigram_kernel(const Args a) {
     if (n_raw > kRaw) n_raw = kRaw;        // cannot happen with a table from rag/_unigram.py; keeps a malformed one in bounds
     __syncthreads();
 
-    // 3. roles.  A run of U+0020 at the tile's end waits for the next tile: its length is not known yet
+    // 3. roles.  Where runs collapse, a run of U+0020 at the tile's end waits for the next tile: its length is not known yet.
+    // Where they do not, every U+0020 has its role at once, and holding a run back as two elements would lose the others
     for (int i = tid; i < n_raw; i += kThreads)
       if (!is_sp(s_raw[i])) atomicMax(&s_last_nonsp, i);
     __syncthreads();
-    const int n_proc = last_tile ? n_raw : s_last_nonsp + 1;
+    const int n_proc = (last_tile || !collapse) ? n_raw : s_last_nonsp + 1;
     const int tail_sp = n_raw - n_proc;
     // what raw element i puts into the word array: 0, 1 or 2 code points
     auto sp_is_meta = [&](int i) {           // s_raw[i] is U+0020: does its run (or it alone) stand for a metaspace?
@@ -236,6 +237,9 @@ __global__ __launch_bounds__(kThreads) void unigram_kernel(const Args a) {
     if (n_fin > kFin) n_fin = kFin;
     const uint32_t sp0 = (tail_sp > 0) ? s_raw[n_proc] : 0;       // the waiting run, read before s_raw becomes s_out
     const uint32_t last_kind = (n_proc > 0) ? s_raw[n_proc - 1] >> kKindShift : kBrk;
+    // does the tile's last element leave a word open?  A U+0020 ends a tile that is not the last only where runs do not collapse,
+    // and there it opens a word, as U+2581 itself does, when it stands for a metaspace
+    const bool open_end = last_kind == kChar || last_kind == kMeta || (last_kind == kSp && single_meta);
     __syncthreads();
 
     // 4. words
@@ -247,7 +251,7 @@ __global__ __launch_bounds__(kThreads) void unigram_kernel(const Args a) {
     __syncthreads();
     const int last_start = s_last_start;
     // the last word is cut by the tile's end unless the text ends here or something behind it ended it
-    const bool cut = !last_tile && last_start >= 0 && tail_sp == 0 && (last_kind == kChar || last_kind == kMeta);
+    const bool cut = !last_tile && last_start >= 0 && tail_sp == 0 && open_end;
     for (int i = tid; i < n_fin; i += kThreads) {
       if (s_fin[i] != kMetaCp) continue;
       const uint32_t* w = s_fin + i;

@@ -98,6 +98,121 @@ def random_texts(n: int, seed: int, allowed: np.ndarray):
     return out
 
 
+# ---- tile boundaries and option sets -------------------------------------------------------------------------------------------------
+# filler words: 2- and 3-byte characters and two that expand under NFKC, so a byte offset is no element offset
+WORDS = ("ab", "the", "hello", "world", "fox", "cd", "é", "über", "привет", "мир", "日本", "中文", "ﬁn", "½", "a½b", "日ﬁ")
+UNITS = ([(f"sp{n}", " " * n) for n in (1, 2, 3, 4, 7)]
+         + [("tab", "\t"), ("crlf", "\r\n"), ("cr", "\r"), ("lf", "\n"), ("nbsp", "\u00a0"), ("u3000", "\u3000"),
+            ("meta", META), ("meta2", META + META), ("2byte", "é"), ("3byte", "日"), ("4byte", "\U0001d41a"),
+            ("fi", "ﬁ"), ("half", "½"), ("kabu", "㈱"),                      # 1 code point -> 2, 3, 3
+            ("zwsp", "\u200b"), ("del", "\u007f"), ("shy", "\u00ad"),       # nmt_nfkc: a space, dropped, kept
+            ("unknown", "x"), ("hello", "hello"), ("world", "world")])
+TAIL = "b ab"
+DROPPED = "\u007f"          # nmt_nfkc drops it; NFKC keeps it as a character no piece holds
+
+
+def option_configs():
+    """[(name, tokenizer.json dict)]: unigram_nfkc.json edited into every pipeline `rag._unigram.unigram_spec` accepts:
+    WhitespaceSplit + Metaspace or Metaspace alone (prepend_scheme always / first), Replace(" {2,}") absent, -> " ", -> "▁"."""
+    base = load_json(NFKC_JSON)
+    assert [n["type"] for n in base["normalizer"]["normalizers"]] == ["NFKC", "Replace"]
+    assert [p["type"] for p in base["pre_tokenizer"]["pretokenizers"]] == ["WhitespaceSplit", "Metaspace"]
+    out = []
+    for pre in ("split", "alone-always", "alone-first"):
+        for rep in (None, " ", META):
+            cfg = json.loads(json.dumps(base))
+            norms = cfg["normalizer"]["normalizers"]
+            if rep is None:
+                del norms[1]
+            else:
+                norms[1]["content"] = rep
+            if pre != "split":
+                cfg["pre_tokenizer"] = cfg["pre_tokenizer"]["pretokenizers"][1]
+                cfg["pre_tokenizer"]["prepend_scheme"] = pre.split("-")[1]
+            out.append((f"{pre}.{'none' if rep is None else 'space' if rep == ' ' else 'meta'}", cfg))
+    return out
+
+
+CONFIG_NAMES = tuple(f"{pre}.{rep}" for pre in ("split", "alone-always", "alone-first") for rep in ("none", "space", "meta")) + ("spm",)
+# one pipeline per value of the kernel's option bits: 0, COLLAPSE, COLLAPSE|RUN_META, SINGLE_META, all three, and CRLF on top
+OPTION_SETS = {"split.none": 0, "split.space": 1, "split.meta": 5, "alone-always.none": 2, "alone-always.meta": 7, "spm": 13}
+_SIDES = {}
+
+
+def config(name):
+    """The tokenizer.json dict of a name in CONFIG_NAMES (`spm`: the Precompiled fixture, which needs the `tokenizers` library)."""
+    return load_json(SPM_JSON) if name == "spm" else dict(option_configs())[name]
+
+
+def side(name):
+    """(restatement, spec, table, vocabulary, the kernel's opts) of a name in CONFIG_NAMES, built once per process."""
+    if name not in _SIDES:
+        from rag import _native as nat
+        from rag import _unigram as ug
+        from rag.tokenizer import UnigramTokenizer
+        tok = UnigramTokenizer(config(name), SPECIAL)
+        spec = ug.unigram_spec(tok)
+        table = ug.table_for_spec(spec)
+        _SIDES[name] = (tok, spec, table, ug.UnigramVocab(spec.pipeline.vocab), spec.opts | (nat.UNIGRAM_CRLF if table.crlf else 0))
+    return _SIDES[name]
+
+
+def library_of(name):
+    """The `tokenizers` library's own Tokenizer of a name in CONFIG_NAMES, neither padding nor truncating."""
+    from tokenizers import Tokenizer
+    tok = Tokenizer.from_str(json.dumps(config(name)))
+    tok.no_padding()
+    tok.no_truncation()
+    return tok
+
+
+def boundary_sweep(tile: int, cap: int):
+    """[(name, text)]: every unit at every offset around the first two tile ends, the carried word at cap - 2 .. cap code points
+    (`overcap-*`: at cap + 1, which the kernel flags), and the whole-tile cases, each with a third tile behind it."""
+    import _tile_cases as tc
+    out = tc.sweep(UNITS, WORDS, (tile, 2 * tile), TAIL, seed=31)
+    rng = np.random.default_rng(32)
+    fill = lambda n, end_space: tc.mixed_filler(n, rng, end_space, WORDS)          # noqa: E731
+    for b in (tile, 2 * tile):
+        for j in (1, 2, 3):
+            for k in (0, 1, 2):                        # cap - k code points with the metaspace in front
+                out.append((f"cap-{k}@{b}-{j}", tc.word_at(b, j, cap - 1 - k, WORDS, rng, " ab")))
+            out.append((f"overcap-1@{b}-{j}", tc.word_at(b, j, cap, WORDS, rng, " ab")))
+    third = lambda: "ab " + fill(tile + tile // 4, True) + "the fox"               # noqa: E731
+    out += [("tile-of-spaces", fill(tile, False) + " " * tile + third()),
+            ("tile-of-dropped", fill(tile - 2, True) + "he" + DROPPED * tile + "llo " + third()),
+            ("tile-ends-in-tab", fill(tile - 1, False) + "\t" + third()),
+            ("run-over-two-ends", fill(tile - 3, False) + " " * (tile + 6) + third())]
+    assert all(len(t.encode()) > 2 * tile for n, t in out[-4:])
+    return out
+
+
+def sweep_flagged(names, dropped_is_dropped: bool):
+    """The names of boundary_sweep the kernel flags: the words over the cap, and the tile of DEL where DEL is a character."""
+    return {n for n in names if n.startswith("overcap-")} | (set() if dropped_is_dropped else {"tile-of-dropped"})
+
+
+def _allowed_units(allowed):
+    ok = set(np.asarray(allowed).tolist())
+    words = [w for w in WORDS if all(ord(c) in ok for c in w)]
+    units = [u for _, u in UNITS if all(ord(c) in ok for c in u)]
+    return words, units
+
+
+def random_long_texts(n: int, seed: int, allowed, cap: int = 128):
+    """n texts of 1 to 3.5 KB from WORDS and UNITS (those whose code points are all in `allowed`); no word exceeds `cap`."""
+    import _tile_cases as tc
+    words, units = _allowed_units(allowed)
+    return tc.random_texts(n, seed, words, units, 1024, 3584, cap)
+
+
+def random_short_texts(n: int, seed: int, allowed):
+    """n texts of 4 to 72 bytes from the same alphabet, words of any length: for a tiled model with tiles of 8 to 32 bytes."""
+    import _tile_cases as tc
+    words, units = _allowed_units(allowed)
+    return tc.random_texts(n, seed, words, units, 4, 72, None)
+
+
 def load_json(path):
     with (lzma.open(path, "rt", encoding="utf-8") if path.endswith(".xz") else open(path, encoding="utf-8")) as fh:
         return json.load(fh)

@@ -64,6 +64,43 @@ def edge_corpus():
     return tuple(texts)
 
 
+# ---- tile boundaries ----------------------------------------------------------------------------------------------------------------
+# filler words: 2- and 3-byte characters, CJK (a word of its own per character), Hangul and U+0130 (one code point -> three / two
+# elements), so a byte offset is no element offset
+SWEEP_WORDS = ("retrieval", "augmented", "the", "fox", "jumpsing", "café", "naïve", "Über", "İstanbul", "中文",
+               "한국어", "tokenization", "a", "xyzzy", "3.14", "FOX")
+SWEEP_UNITS = (("sp1", " "), ("sp2", "  "), ("sp3", "   "), ("tab", "\t"), ("crlf", "\r\n"), ("nbsp", "\u00a0"), ("u3000", "\u3000"),
+               ("2byte", "\u00e9"), ("3byte", "\u4e2d"), ("4byte", "\U0001f600"), ("hangul", "\ud55c"), ("hangul2", "\ud55c\uad6d"),
+               ("dotted-i", "\u0130"), ("dz", "\u01c6"), ("sharp-s", "\u00df"), ("combining", "e\u0301"), ("punct", "!"), ("dots", "..."),
+               ("hashes", "##"), ("cjk-stop", "\u3002"), ("zwsp", "\u200b"), ("nul", "\x00"), ("replacement", "\ufffd"),
+               ("word", "augmented"), ("pieces", "foxes"), ("unknown", "xyzzy"))
+SWEEP_TAIL = "b tail"
+
+
+@functools.lru_cache(maxsize=None)
+def boundary_sweep():
+    """(name, text) pairs: every unit of SWEEP_UNITS with its first byte at every offset from B - len(unit) - 2 to B + 1 for B in
+    (TILE, 2 * TILE) behind a mixed filler, and a word of 100 and of 101 characters (max_input_chars_per_word is 100) that starts
+    1 to 3 bytes in front of B."""
+    import numpy as np
+    import _tile_cases as tc
+    out = tc.sweep(SWEEP_UNITS, SWEEP_WORDS, (TILE, 2 * TILE), SWEEP_TAIL, seed=61)
+    rng = np.random.default_rng(62)
+    for b in (TILE, 2 * TILE):
+        for j in (1, 2, 3):
+            for n in (100, 101):
+                out.append((f"word-{n}@{b}-{j}", tc.word_at(b, j, n, SWEEP_WORDS, rng, " tail of the text", letters="a")))
+    return tuple(out)
+
+
+@functools.lru_cache(maxsize=None)
+def random_long_texts(n: int = 300, seed: int = 63):
+    """n seeded texts of 1 to 3.5 KB from SWEEP_WORDS and SWEEP_UNITS, no word of more than 100 elements (a code point counts as the
+    three elements a Hangul syllable becomes)."""
+    import _tile_cases as tc
+    return tuple(tc.random_texts(n, seed, SWEEP_WORDS, [u for _, u in SWEEP_UNITS], 1024, 3584, 100))
+
+
 @functools.lru_cache(maxsize=None)
 def megabyte_text():
     return ("retrieval augmented generation embeds chunks of text, " * 20000)[: 1 << 20]

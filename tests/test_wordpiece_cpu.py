@@ -182,6 +182,39 @@ def test_emulated_hash_mode_equals_hash_tokenizer():
                 assert got == tok.encode(text, 64), text[:60]
 
 
+@pytest.mark.parametrize("lower,strip", cases.FLAG_PAIRS)
+def test_boundary_sweep_is_laid_out_and_emulated(lower, strip):
+    """What tests/test_wordpiece_tiles_gpu.py launches: every unit stands at its byte offset, the filler in front of it is mixed,
+    no text holds a FALLBACK code point, and the emulation (no tiles) gives WordPieceTokenizer's ids for it."""
+    from rag import _wordpiece as wp
+    from rag.tokenizer import WordPieceTokenizer
+    vocab = cases.make_vocab()
+    tok = WordPieceTokenizer(vocab, lower=lower, strip_accents=strip)
+    table, vh = wp.norm_table(lower, strip), wp.VocabHash(vocab)
+    sweep = dict(cases.boundary_sweep())
+    assert len(sweep) == len(cases.boundary_sweep()) and 350 <= len(sweep) <= 520
+    for label, unit in cases.SWEEP_UNITS:
+        nb = len(unit.encode())
+        for b in (cases.TILE, 2 * cases.TILE):
+            for off in range(b - nb - 2, b + 2):
+                t = sweep[f"{label}@{b}{off - b:+d}"].encode()
+                assert t[off: off + nb] == unit.encode() and t[off + nb:] == cases.SWEEP_TAIL.encode()
+    for b in (cases.TILE, 2 * cases.TILE):
+        for j in (1, 2, 3):
+            for n in (100, 101):
+                t = sweep[f"word-{n}@{b}-{j}"].encode()
+                assert t[b - j - 1: b - j + n + 1] == b" " + b"a" * n + b" "
+    head = sweep[f"sp3@{2 * cases.TILE}+0"]
+    assert {len(c.encode()) for c in head} >= {1, 2, 3} and "한" in head and "İ" in head
+    long_texts = cases.random_long_texts()
+    sizes = [len(t.encode()) for t in long_texts]
+    assert len(long_texts) == 300 and min(sizes) >= 1024 and 3 * 1024 < max(sizes) < 3700
+    for text in list(sweep.values()) + list(long_texts[:60]):
+        assert not any(table.lookup(ord(c))[0] == wp.FALLBACK for c in set(text))
+        got = wp.emulate_encode(text, table, 2048, vocab=vh, unk_id=tok.unk_id, cls_id=tok.cls_id, sep_id=tok.sep_id)
+        assert got == tok.encode(text, 2048) and len(got) < 2048, text[-40:]
+
+
 def test_symbols_declared_exported_bound():
     from rag import _native as nat
     header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "crs_hip.h")).read(), flags=re.S)
