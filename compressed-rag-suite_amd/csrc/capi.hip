@@ -137,7 +137,8 @@ static int run_scan(const Plan& p, const void* q16, const void* slab, const floa
   }
   switch (p.family) {
     case crs::Family::W1: return crs::scan_launch_w1(a, p.pdim, st);
-    case crs::Family::Wide: return crs::scan_launch_wide(a, p.pdim, p.waves, p.mfma, st);
+    case crs::Family::Wide:
+      return p.ring ? crs::scan_launch_wide_ring(a, p.pdim, p.waves, p.mfma, st) : crs::scan_launch_wide(a, p.pdim, p.waves, p.mfma, st);
     default: break;
   }
   if (p.slab_type == CRS_SLAB_I8) return crs::scan_launch_i8(a, p.pdim, p.slots, st);

@@ -1,6 +1,7 @@
 // plan.cpp -- the planner of a search's scan (plan.h).  Plain C++17: builds into libcrs_hip.so and alone with g++.
 #include "plan.h"
 
+#include <assert.h>
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -63,7 +64,7 @@ int tile_best_slots(const Plan& p, const Knobs& kn) {
 }
 
 // What is left once family, form and grid are chosen: the slab stream's cache policy, the dynamic tile schedule, scan.hip's
-// bootstrap and schedule, the wide kernel's stagger and MFMA shape.
+// bootstrap and schedule, the wide kernel's stagger, MFMA shape and buffer scheme.
 int finish_plan(Plan* p, int64_t n_rows, const Knobs& kn) {
   const bool tile_best = p->family == Family::TileBest, wide = p->family == Family::Wide;
   p->part_elems = (size_t)p->nwg * p->nq * p->kp;
@@ -83,22 +84,28 @@ int finish_plan(Plan* p, int64_t n_rows, const Knobs& kn) {
   const bool tb_chain = tile_best && p->slots > 0 && !(p->slab_type == CRS_SLAB_I8 && p->pdim > 768);
   const bool wide_chain = wide && scan_wide_streamed(p->k) && kn.wide_dyn;
   const int rounds = p->n_tiles / p->nwg;
+  // (the wide kernel's shape and buffer scheme first: the ring wants one more static round)
+  p->mfma = !wide ? 0 : !wide_has_16(p->pdim, p->waves, p->slots) ? 32 : kn.wide_mfma ? kn.wide_mfma : wide_default_mfma(p->pdim, p->slots);
+  p->ring = wide && kn.wide_ring && wide_ring_form(p->pdim, p->waves, p->slots, p->mfma);
+  p->lds = wide ? scan_wide_lds_bytes(p->pdim, p->waves, p->ring) : 0;
   p->ticket = (tb_chain || wide_chain) && p->nqb == 1 && !kn.share_tau && kn.tb_dyn > 0 &&
               rounds >= (kn.tb_dyn_min < 4 ? 4 : kn.tb_dyn_min);
   p->t_dyn = p->n_tiles;
   p->dyn_mask = 0;
   if (p->ticket) {
     int stat = (int)((int64_t)rounds * (100 - kn.tb_dyn) / 100);   // static rounds ahead of the ticketed ones
-    if (stat < 2) stat = 2;
+    // the kernels know the look-ahead tile of their first iteration without a ticket; the ring kernel looks two tiles ahead
+    const int stat_min = p->ring ? 3 : 2;
+    if (stat < stat_min) stat = stat_min;
     p->t_dyn = stat * p->nwg;
     p->dyn_mask = kn.tb_dyn_g - 1;
+    assert(p->t_dyn >= stat_min * p->nwg && p->t_dyn <= p->n_tiles);
   }
   // short streams only: the bootstrap pays when a workgroup sees few tiles (see scan.hip)
   p->boot = (kn.scan_boot && rounds < 24) ? 1 : 0;
   p->sched = kn.scan_sched;
   p->no_stagger = (wide && !kn.wide_stagger) ? 1 : 0;
   p->no_defer = (wide && !kn.wide_defer) ? 1 : 0;
-  p->mfma = !wide ? 0 : !wide_has_16(p->pdim, p->waves, p->slots) ? 32 : kn.wide_mfma ? kn.wide_mfma : wide_default_mfma(p->pdim, p->slots);
   return CRS_OK;
 }
 
@@ -115,6 +122,7 @@ Knobs knobs_from_env() {
   kn.fused_tail = env_on("CRS_FUSED_TAIL");
   kn.wide_stagger = env_on("CRS_WIDE_STAGGER");
   kn.wide_defer = env_on("CRS_WIDE_DEFER");
+  kn.wide_ring = env_on("CRS_WIDE_RING");
   const char* me = getenv("CRS_WIDE_MFMA");
   kn.wide_mfma = !me ? 0 : (me[0] == '1' && me[1] == '6' && !me[2]) ? 16 : (me[0] == '3' && me[1] == '2' && !me[2]) ? 32 : 0;
   return kn;

@@ -30,6 +30,7 @@ struct Knobs {
   bool wide_stagger = true; // CRS_WIDE_STAGGER       per call  0: waves 4..7 of the wide split forms select in step with 0..3
   bool wide_defer = true;   // CRS_WIDE_DEFER         per call  0: the wide split forms insert every tile at once (no pending slot)
   int wide_mfma = 0;        // CRS_WIDE_MFMA          per call  16 / 32: MFMA shape where a wide form has both; 0: the measured one
+  bool wide_ring = true;    // CRS_WIDE_RING          per call  0: the wide forms of wide_ring_form() run their two-buffer kernel
 };
 Knobs knobs_from_env();
 
@@ -54,6 +55,8 @@ struct Plan {
   int no_stagger;    // Wide: ScanArgs::no_stagger
   int no_defer;      // Wide: ScanArgs::no_defer
   int mfma;          // Wide: 16 or 32, the MFMA shape launched; else 0
+  bool ring;         // Wide: the ring kernel of the form is launched (scan_forms.h: wide_ring_form)
+  int lds;           // Wide: dynamic LDS bytes of the launch; else 0
   size_t part_elems; // nwg * nq * kp
   // every family but Classic leaves tile representatives: merge, then scan_refine.hip re-opens the winning tiles
   bool group_best() const { return family != Family::Classic; }

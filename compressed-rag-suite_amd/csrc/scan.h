@@ -30,7 +30,7 @@ struct ScanArgs {
   int nwg;                // tile streams (workgroups per query block)
   int nqb;                // query blocks (64, 128 or 256 queries each); the grid is nqb * nwg workgroups (scan_common.h: grid mapping)
   unsigned* ticket;       // scan_tb.hip chain mode: tiles >= t_dyn are handed out through this counter (zero at launch); else nullptr
-  int t_dyn;              //   first dynamically scheduled tile (a multiple of nwg, >= 2 nwg); n_tiles when the schedule is static
+  int t_dyn;              //   first dynamically scheduled tile (a multiple of nwg, >= 2 nwg, ring kernels >= 3 nwg); n_tiles when the schedule is static
   int dyn_mask;           //   a ticket stands for dyn_mask + 1 consecutive tiles (a power of two)
   int nt;                 // scan_tb.hip / scan_i8.hip: 1 = slab tiles streamed with the non-temporal policy (lds_dma16_nt)
   int no_stagger;         // scan_wide.hip, 24- / 32-slot forms: 1 = CRS_WIDE_STAGGER=0 (read by nothing else)
@@ -64,6 +64,8 @@ int scan_launch_tb(const ScanArgs& a, int pdim, int nw, int slots, hipStream_t s
 int scan_ticket_zero(unsigned* ticket, hipStream_t stream);   // ScanArgs::ticket := 0, in stream order
 // 65+ queries per launch, fp16 slabs; mfma: 16 or 32, the MFMA shape (Plan::mfma)
 int scan_launch_wide(const ScanArgs& a, int pdim, int nw, int mfma, hipStream_t stream);
+// the ring kernels of the same forms (scan_wide_ring.hip; Plan::ring, i.e. wide_ring_form holds)
+int scan_launch_wide_ring(const ScanArgs& a, int pdim, int nw, int mfma, hipStream_t stream);
 // 65+ queries per launch on 768-element fp16 rows: 256 queries per workgroup, dump selection
 int scan_launch_w1(const ScanArgs& a, int pdim, hipStream_t stream);
 

@@ -101,6 +101,24 @@ constexpr bool wide_form_exists(int pdim, int nw, int slots, int mfma) {
   return mfma == 32 || (mfma == 16 && wide_has_16(pdim, nw, slots));
 }
 
+// Ring form (scan_wide.hip header: "Ring form"; the kernels live in scan_wide_ring.hip): three tile buffers, the transfer of the
+// tile after next issued off-phase per wave half, a raw barrier.  On for the forms measured faster with it by the rule of DESIGN.md
+// section 7 item 6 -- none so far beyond the flagship's; -DCRS_WIDE_RING_ALL=1 compiles it into every 8-wave split form (A/B builds).
+#ifndef CRS_WIDE_RING_ALL
+#define CRS_WIDE_RING_ALL 0
+#endif
+constexpr bool wide_ring_form(int pdim, int nw, int slots, int mfma) {
+  if (!wide_form_exists(pdim, nw, slots, mfma) || nw != 8 || slots <= 16) return false;
+  if (CRS_WIDE_RING_ALL) return true;
+  return pdim == 384 && slots == 24 && mfma == 16;
+}
+// dynamic LDS of a launch: the tile buffers (two; ring: three), the last of which also stages the prologue's query transpose
+// (4 KB per wave) while it is still idle
+constexpr int scan_wide_lds_bytes(int pdim, int nw, bool ring) {
+  const int tile = scan_wide_tile_rows(nw, pdim) * pdim * 2, qstage = nw * 4096, nbuf = ring ? 3 : 2;
+  return nbuf * tile > (nbuf - 1) * tile + qstage ? nbuf * tile : (nbuf - 1) * tile + qstage;
+}
+
 // ---- W1 (scan_w1.hip): 256 queries per workgroup, 8 waves, one workgroup per CU ---------------------------------------------
 constexpr int kW1TileRows = 32, kW1WgPerCu = 1, kW1Queries = 256;
 constexpr bool w1_form_exists(int pdim) { return pdim == 768; }

@@ -103,6 +103,15 @@ __device__ __forceinline__ int ticket_take(const int* sh_next, int it, int tend)
   return (unsigned)tnn < (unsigned)tend ? tnn : tend;
 }
 
+// The same pair with the slot named by the caller (scan_wide.hip's ring form keeps a slot per tile buffer: `slot` is its ring index)
+__device__ __forceinline__ void ticket_publish_slot(int* sh_next, int slot, unsigned tk, int t_dyn, int dyn_mask) {
+  sh_next[slot] = t_dyn + (int)tk * (dyn_mask + 1);
+}
+__device__ __forceinline__ int ticket_take_slot(const int* sh_next, int slot, int tend) {
+  const int tnn = __builtin_amdgcn_readfirstlane(sh_next[slot]);
+  return (unsigned)tnn < (unsigned)tend ? tnn : tend;
+}
+
 // ---------------------------------------------------------------- partial-list epilogues (scan_tb.hip, scan_i8.hip)
 // The query's list starts at slot o of the partial lists [nq, nwg, kp].
 // dump form: the slots of tiles this (shorter) stream does not have, shared out over the query's four lanes (first = it + kq)

@@ -81,6 +81,29 @@
 //     kq & 1 the half, and the lower half's last slot crosses by v_permlane16_swap instead of v_permlane32_swap.  The list
 //     algorithm (insert_shift) and its proof are unchanged: they only speak of "the two lanes of the pair".
 // Which shape a form runs is wide_default_mfma() (scan_forms.h), set from A/B runs by wall time; CRS_WIDE_MFMA=16 | 32 overrides it.
+//
+// Ring form (wide_ring<>; the kernels are compiled in scan_wide_ring.hip, which includes this file).  The loop above keeps two tile
+// buffers and ends every iteration in s_waitcnt vmcnt(0) + __syncthreads(): all eight waves issue their six transfers of the
+// look-ahead tile together at the top of an iteration, straight behind the barrier.  Both waves of every SIMD then sit in transfer
+// issue at once (no MFMA runs on the CU meanwhile), and waves 4 .. 7 queue behind waves 0 .. 3 in the CU's one texture addresser --
+// time that waves 0 .. 3 then spend at the barrier (profiles/r14_wide_probe.txt: issue 794 / 1470 cycles, barrier 920 / 337 of a
+// 4.88 k-cycle tile).  The ring form changes where the transfers are issued and how the buffers rotate, nothing else:
+//   * three tile buffers; iteration i multiplies tile T[i] out of buffer i mod 3, and the transfer of T[i + 2] is issued DURING
+//     iteration i into buffer (i + 2) mod 3, whose last reads (of T[i - 1]) lie behind barrier i - 1, which every wave has passed;
+//   * each wave keeps "s_waitcnt vmcnt(0), then issue my six transfers of T[i + 2]": at most one tile in flight per wave, but it
+//     stays in flight across the barrier.  Waves 0 .. 3 do it behind their selection (in what was barrier wait), waves 4 .. 7
+//     between their deferred selection and their MFMA sweep: on every SIMD one wave multiplies while its partner is held in issue,
+//     and the halves no longer meet in the texture addresser.  A wave's vmcnt(0) in iteration i retires its share of T[i + 1],
+//     issued a whole iteration earlier; it precedes barrier i and T[i + 1] is first read behind that barrier;
+//   * the iteration ends in s_waitcnt lgkmcnt(0) + a raw s_barrier: __syncthreads()'s fence waits vmcnt(0), which would drain the
+//     transfer just issued.  Every wave reaches the barrier on every iteration (idle waves issue their share of each tile too);
+//   * tickets: (t, tn, tnn) are known at the top of an iteration and wave 0 draws the tile after tnn there, ahead of its
+//     transfers in program order; its vmcnt(0) in front of its issue is the one that names the ticket's register, the drawing
+//     thread publishes behind it and ahead of the barrier (one slot per tile buffer), every thread takes behind the barrier.  The
+//     first three tiles of a stream are static (plan.cpp: t_dyn >= 3 nwg for these plans);
+//   * streams of one or two tiles issue nothing past their end; nothing is in flight when the loop is left.
+// The lists are those of the two-buffer kernel bit for bit: tiles reach select() in the same order with the same accumulators.
+// CRS_WIDE_RING=0 (Plan::ring) launches the form's two-buffer kernel: A/B runs, and the tests' reference.
 
 #include "scan_stream.h"
 
@@ -127,6 +150,10 @@ constexpr bool wide_defer() {
   return S16 && D == 384 && NW == 8 && K == 24;
 }
 
+// The forms that have a ring kernel (header: "Ring form"; scan_forms.h decides, so that the planner knows them too)
+template <int D, int NW, int K, bool S16>
+constexpr bool wide_ring() { return wide_ring_form(D, NW, K, S16 ? 16 : 32); }
+
 template <int D, int NW>
 struct WCfg {
   static constexpr int kThreadsW = NW * 64;
@@ -136,8 +163,10 @@ struct WCfg {
   static constexpr int kTileBytes = TR * D * 2;
   static constexpr int kLoads = kTileBytes / (kThreadsW * 16);
   static constexpr int kKsteps = D / 16;
-  static constexpr int kQStage = NW * 4096;   // prologue: 4 KB per wave for the query transpose, in the second tile buffer
+  static constexpr int kQStage = NW * 4096;   // prologue: 4 KB per wave for the query transpose, in the last tile buffer
   static constexpr int kLds = 2 * kTileBytes > kTileBytes + kQStage ? 2 * kTileBytes : kTileBytes + kQStage;
+  static constexpr int kLdsRing = scan_wide_lds_bytes(D, NW, true);   // three buffers
+  static_assert(kLds == scan_wide_lds_bytes(D, NW, false), "the planner's LDS bytes are the launch's");
   static_assert(D % 128 == 0, "row length must be a multiple of 128 elements");
   static_assert(kTileBytes % (kThreadsW * 16) == 0, "tile must split into whole 16-byte loads");
 };
@@ -150,10 +179,12 @@ struct WAcc<RB, true> { f32x4 a[2 * RB][2]; };
 
 // The body of both kernels; S16 picks the compute form (MFMA shape, fragment layout, which lanes hold a query's list).
 // The arguments come by value as they come to a kernel: taken by reference, scan_wide_kernel<384, 8, 24> spilled 20 bytes per lane.
-// (one look-ahead tile per workgroup: a second one measured no faster -- the kernel is LDS- / barrier-bound, below)
-template <int D, int NW, int K, bool S16>
+// RING: the three-buffer loop (header: "Ring form").  (A second look-ahead tile behind the two-buffer loop's vmcnt(0) +
+// __syncthreads() measured no faster, but that barrier drains every transfer in flight, so it never tested a transfer that spans it.)
+template <int D, int NW, int K, bool S16, bool RING = false>
 __device__ __forceinline__ void scan_wide_body(const ScanArgs a) {
   using C = WCfg<D, NW>;
+  static_assert(!RING || (wide_ring<D, NW, K, S16>() && wide_streamed<K>()), "no ring kernel for this form");
   static_assert(!S16 || wide_has_16(D, NW, K), "the 16x16x32 form exists for the split-list forms of 64-row tiles only");
   constexpr int kT = C::kThreadsW;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -186,13 +217,16 @@ __device__ __forceinline__ void scan_wide_body(const ScanArgs a) {
   };
 
   // Tile order: static stride below t_dyn, then (24- / 32-slot forms) ticketed granules -- scan_stream.h, "Tile order"
-  __shared__ int sh_next[2];
+  __shared__ int sh_next[RING ? 3 : 2];
   constexpr bool kDyn = wide_streamed<K>();
   const int tend = a.n_tiles;
   const int t_dyn = kDyn ? a.t_dyn : a.n_tiles;
   int t = stream, t_prev = stream;
   int tn = t + nwg;     // the look-ahead tile (t_dyn >= 2 nwg: static for the first iteration)
   dma_tile(t, 0);   // goes out before the query fragments are fetched, so the two latencies overlap
+  if constexpr (RING) {
+    if (tn < tend) dma_tile(tn, 1);   // the ring starts with two tiles landed; a one-tile stream issues nothing past its end
+  }
 
   // ---- this wave's 32 queries, full depth, as B fragments.  32x32x16: lane (n = l & 31, h = l >> 5) holds
   // Q[n][16 ks + 8 h .. + 8] for every k-step ks < D / 16.  16x16x32: two column groups g of 16 queries; lane (n = l & 15,
@@ -210,11 +244,11 @@ __device__ __forceinline__ void scan_wide_body(const ScanArgs a) {
     // lines per instruction, D/16 instructions per wave: 12 k cycles of the texture addresser per workgroup,
     // 42 % of a 128-query launch over 100 k rows (tools/scan_wide_probe).  So the wave's 32 query rows come in
     // as whole 128-byte column blocks (8 lanes per row), pass through a wave-private 4 KB of the still idle
-    // SECOND tile buffer (chunk XOR-swizzled by (row >> 1) & 7) and are read back as fragments.  LDS operations of a
+    // SECOND (ring form: third) tile buffer (chunk XOR-swizzled by (row >> 1) & 7) and are read back as fragments.  LDS operations of a
     // wave execute in order, so the block's reads see its writes and the next block's writes come after them.
     constexpr int kBlocks = C::kCpr / 8;   // 128-byte column blocks of a query row
     constexpr int kGroup = 3;              // blocks whose loads are in flight together (12 x 16 bytes per lane)
-    char* qs = tile_buf + C::kTileBytes + wave * 4096;
+    char* qs = tile_buf + (RING ? 2 : 1) * C::kTileBytes + wave * 4096;
     const int q0 = qblock * (NW * 32) + wave * 32;
     const char* qbytes = reinterpret_cast<const char*>(a.q);
     const f16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -344,7 +378,7 @@ __device__ __forceinline__ void scan_wide_body(const ScanArgs a) {
   };
 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();   // the first tile has landed, and every wave has its fragments: the second buffer is free
+  __syncthreads();   // the first tile has landed (ring form: the first two), and every wave has its fragments: the last buffer is free
   WP_LAP(0);   // prologue
 
   // Stagger (MI355X_MICROARCH.md, "two waves per SIMD", item 9).  Waves w and w + 4 share a SIMD, and with
@@ -483,6 +517,62 @@ __device__ __forceinline__ void scan_wide_body(const ScanArgs a) {
   };
 
   int cur = 0, it = 0;
+  if constexpr (RING) {
+    // one iteration: tile t sits in buffer `cur` of three, tn has landed or is landing in the next one, and the transfer of tnn
+    // goes out during the iteration into the one after that (header: "Ring form")
+    int tnn = tn + nwg;   // t_dyn >= 3 nwg: static, like tn
+    while (t < tend) {
+      const bool has_nn = tnn < tend;
+      const int nbuf = cur ? cur - 1 : 2;   // (cur + 2) mod 3: last read in the iteration before this one
+      const bool in_dyn = tnn >= t_dyn;
+      const bool draw = a.ticket != nullptr && has_nn && ticket_due(in_dyn, tnn, nwg, t_dyn, a.dyn_mask);
+      // The ticket in flight.  Wave 0 draws, and wave 0 is never idle nor late, so the wait of that path alone names tk and the
+      // drawing thread publishes right there: named by the other paths' waits too, tk reached them through a copy made AHEAD of the wait.
+      unsigned tk = 0;
+      ticket_draw(tk, draw && wave == 0, a.ticket);
+      // behind a wave's vmcnt(0) its share of tn has landed; then its share of tnn goes out and stays in flight across the barrier
+      auto issue = [&]() {
+        WP_LAP(6);   // wait for the next tile (and for the ticket)
+        if (has_nn) dma_tile(tnn, nbuf);
+        WP_LAP(1);   // tile-load issue
+      };
+      const char* buf = tile_buf + cur * C::kTileBytes;
+      if (!wave_active) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        issue();
+      } else if (!late) {   // waves 0..3: the issue falls into what is barrier wait in the two-buffer loop
+        const Acc acc = sweep(buf);
+        WP_LAP(3);   // MFMA sweep
+        select(acc, t, it);
+        WP_LAP(4);   // selection (waves 0..3)
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(tk) : : "memory");
+        issue();
+        if (draw && tid == 0) ticket_publish_slot(sh_next, cur, tk, t_dyn, a.dyn_mask);
+      } else {              // waves 4..7: held in issue while the SIMD's other wave multiplies
+        if (it > 0) select(acc_prev, t_prev, it - 1);
+        WP_LAP(2);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        issue();
+        acc_prev = sweep(buf);
+        WP_LAP(3);
+      }
+      int t3 = in_dyn ? tnn + 1 : tnn + nwg;
+      // LDS reads and the published ticket only: a vmcnt(0) here (__syncthreads()'s fence has one) would drain the transfer of tnn
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      WP_LAP(7);   // barrier
+      if (draw) t3 = ticket_take_slot(sh_next, cur, tend);
+      cur = cur == 2 ? 0 : cur + 1;
+      ++it;
+      t_prev = t;
+      t = tn;
+      tn = tnn;
+      tnn = t3;
+    }
+    // tiles come in increasing order, so the last two iterations issued nothing: no transfer is in flight (the wait is a guard)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  } else {
   // one iteration: tile t sits in LDS buffer `cur`, the look-ahead tile tn streams into the other one
   while (t < tend) {
     const bool has_next = tn < tend;
@@ -523,6 +613,7 @@ __device__ __forceinline__ void scan_wide_body(const ScanArgs a) {
     t = tn;
     tn = tnn;
   }
+  }
 
   if (wave_active && late && it > 0) select(acc_prev, t_prev, it - 1);   // the deferred last tile
   if constexpr (kSplit) {
@@ -554,6 +645,13 @@ __device__ __forceinline__ void scan_wide_body(const ScanArgs a) {
   WP_STORE(NW);
 }
 
+// Which kernels a translation unit holds: 0 (scan_wide.hip itself) the two-buffer kernels of every form, 1 (scan_wide_ring.hip) the
+// ring kernels, 2 (tools/scan_wide_probe.hip) both
+#ifndef CRS_WIDE_TU
+#define CRS_WIDE_TU 0
+#endif
+
+#if CRS_WIDE_TU != 1
 template <int D, int NW, int K>
 __global__ __launch_bounds__(NW * 64, 2) void scan_wide_kernel(const ScanArgs a) {
   scan_wide_body<D, NW, K, false>(a);
@@ -596,8 +694,46 @@ int launch_wide_d(const ScanArgs& a, int nw, int mfma, hipStream_t stream) {
   return nw == 8 ? launch_wide_k<D, 8>(a, mfma, stream) : launch_wide_k<D, 4>(a, mfma, stream);
 }
 
+#endif   // CRS_WIDE_TU != 1
+
+#if CRS_WIDE_TU != 0
+// The ring kernels of the forms of wide_ring<>: same grid and partial lists, three tile buffers of LDS.  They carry their form's
+// kernel names inside a namespace of their own, so a launch trace keeps naming the form: ring::scan_wide16_kernel<384, 8, 24>.
+namespace ring {
+template <int D, int NW, int K>
+__global__ __launch_bounds__(NW * 64, 2) void scan_wide_kernel(const ScanArgs a) {
+  scan_wide_body<D, NW, K, false, true>(a);
+}
+template <int D, int NW, int K>
+__global__ __launch_bounds__(NW * 64, 2) void scan_wide16_kernel(const ScanArgs a) {
+  scan_wide_body<D, NW, K, true, true>(a);
+}
+}  // namespace ring
+
+template <int D, int K>
+int launch_ring_if(const ScanArgs& a, int mfma, hipStream_t stream) {
+  if constexpr (wide_ring<D, 8, K, true>()) {
+    if (mfma == 16) return launch_scan<&ring::scan_wide16_kernel<D, 8, K>>(WCfg<D, 8>::kLdsRing, 8 * 64, a, stream);
+  }
+  if constexpr (wide_ring<D, 8, K, false>()) {
+    if (mfma == 32) return launch_scan<&ring::scan_wide_kernel<D, 8, K>>(WCfg<D, 8>::kLdsRing, 8 * 64, a, stream);
+  }
+  return -1;
+}
+
+template <int D>
+int launch_ring_d(const ScanArgs& a, int mfma, hipStream_t stream) {
+  switch (scan_wide_slots(a.k)) {
+    case 24: return launch_ring_if<D, 24>(a, mfma, stream);
+    case 32: return launch_ring_if<D, 32>(a, mfma, stream);
+    default: return -1;
+  }
+}
+#endif   // CRS_WIDE_TU != 0
+
 }  // namespace
 
+#if CRS_WIDE_TU != 1
 int scan_launch_wide(const ScanArgs& a, int pdim, int nw, int mfma, hipStream_t stream) {
   switch (pdim) {
     case 128: return launch_wide_d<128>(a, nw, mfma, stream);
@@ -607,5 +743,18 @@ int scan_launch_wide(const ScanArgs& a, int pdim, int nw, int mfma, hipStream_t 
     default: return -1;
   }
 }
+#endif
+
+#if CRS_WIDE_TU != 0
+int scan_launch_wide_ring(const ScanArgs& a, int pdim, int nw, int mfma, hipStream_t stream) {
+  if (nw != 8) return -1;
+  switch (pdim) {
+    case 128: return launch_ring_d<128>(a, mfma, stream);
+    case 256: return launch_ring_d<256>(a, mfma, stream);
+    case 384: return launch_ring_d<384>(a, mfma, stream);
+    default: return -1;
+  }
+}
+#endif
 
 }  // namespace crs

@@ -2,6 +2,7 @@
 //   g++ -O2 -std=c++17 -o plan_table tools/plan_table.cpp compressed-rag-suite_amd/csrc/plan.cpp
 //   ./plan_table <CUs> < cases            one case per line: nq dim k n_rows slab_type (0 fp16, 1 int8)
 //   ./plan_table --forms                  one line per kernel instantiation the predicates of csrc/scan_forms.h admit
+//   ./plan_table --ring <CUs> < cases     per case: ring lds ticket t_dyn dyn_mask describe-text (the wide kernel's buffer scheme)
 // The knobs come from the environment (CRS_SCAN_TB=0 ./plan_table 256 ...), as in the library.  One tab-separated line per case:
 //   family waves slots tile_rows n_tiles streams qblocks kp nt ticket t_dyn dyn_mask boot sched no_stagger mfma form_exists
 //   workspace_bytes describe-text
@@ -40,7 +41,9 @@ static int list_forms() {
 
 int main(int argc, char** argv) {
   if (argc == 2 && !strcmp(argv[1], "--forms")) return list_forms();
-  if (argc != 2 || atoi(argv[1]) <= 0) { fprintf(stderr, "usage: plan_table <CUs> < cases | plan_table --forms\n"); return 2; }
+  const bool ring_cols = argc == 3 && !strcmp(argv[1], "--ring");
+  if (ring_cols) { --argc; ++argv; }
+  if (argc != 2 || atoi(argv[1]) <= 0) { fprintf(stderr, "usage: plan_table [--ring] <CUs> < cases | plan_table --forms\n"); return 2; }
   const int cus = atoi(argv[1]);
   static const char* const kFamily[] = {"Classic", "TileBest", "Wide", "W1"};
   int nq, dim, k, slab_type;
@@ -56,6 +59,10 @@ int main(int argc, char** argv) {
       continue;
     }
     crs::plan_describe(p, text, sizeof text);
+    if (ring_cols) {
+      printf("%d\t%d\t%d\t%d\t%d\t%s\n", (int)p.ring, p.lds, (int)p.ticket, p.t_dyn, p.dyn_mask, text);
+      continue;
+    }
     printf("%s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%zu\t%s\n", kFamily[(int)p.family], p.waves, p.slots, p.tile_rows,
            p.n_tiles, p.nwg, p.nqb, p.kp, p.nt, (int)p.ticket, p.t_dyn, p.dyn_mask, p.boot, p.sched, p.no_stagger, p.mfma, (int)p.form_exists(),
            ws, text);

@@ -2,12 +2,16 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -o scan_wide_probe scan_wide_probe.hip
 //   ./scan_wide_probe <rows> <dim> <nq> <k>
 // The 24- / 32-slot forms run as the product launches them: nt stream for slabs of 1 GB and more, ticketed tile schedule on long
-// streams (85 % of the tiles in granules of 8; CRS_WIDE_DYN=0: static stride), CRS_WIDE_STAGGER and CRS_WIDE_MFMA as in the library.
+// streams (85 % of the tiles in granules of 8; CRS_WIDE_DYN=0: static stride), CRS_WIDE_STAGGER, CRS_WIDE_MFMA and CRS_WIDE_RING as in the
+// library.  In the ring kernels (scan_wide.hip, "Ring form") the laps follow the new issue points: "wait next tile" and "tile-load issue"
+// lie behind the selection (waves 0-3) resp. between the deferred selection and the MFMA sweep (waves 4-7), and "barrier" is the raw
+// barrier at the iteration's end.
 // The last line is the clock the chip held inside the kernel: a wave's cycles over the launch / the launch's time.
 // Slot 5 is not a lap but a count: how often a wave ran the insertion chain of the deferred split forms (CRS_WIDE_DEFER, scan_wide.hip
 // "Deferred insertion"; one more than the flushes in the loop: the flush at the end).  That count depends on the data, so the slab is
 // filled on the device with rows that do not repeat.
 #define CRS_STAMPS 1
+#define CRS_WIDE_TU 2   // the two-buffer kernels and the ring kernels
 #include "../compressed-rag-suite_amd/csrc/scan_wide.hip"
 #include "../compressed-rag-suite_amd/csrc/plan.cpp"   // knobs_from_env
 
@@ -69,12 +73,13 @@ int main(int argc, char** argv) {
   const int mfma = !crs::wide_has_16(dim, nw, slots) ? 32 : kn.wide_mfma ? kn.wide_mfma : crs::wide_default_mfma(dim, slots);
   a.no_stagger = kn.wide_stagger ? 0 : 1;
   a.no_defer = kn.wide_defer ? 0 : 1;
+  const bool ring = kn.wide_ring && crs::wide_ring_form(dim, nw, slots, mfma);
   if (crs::scan_wide_streamed(k)) {   // the plan fields of plan.cpp's finish_plan
     a.nt = ((size_t)rows * dim * 2 >= ((size_t)1 << 30) && nqb == 1) ? 1 : 0;
     const int rounds = n_tiles / nwg;
     if (kn.wide_dyn && nqb == 1 && rounds >= 96) {
       int stat = (int)((long long)rounds * 15 / 100);
-      if (stat < 2) stat = 2;
+      if (stat < (ring ? 3 : 2)) stat = ring ? 3 : 2;
       hipMalloc(&ticket, 256);
       a.t_dyn = stat * nwg; a.ticket = ticket; a.dyn_mask = 7;
     }
@@ -85,7 +90,7 @@ int main(int argc, char** argv) {
     hipMemset(st, 0, nst * 8);
     if (ticket) hipMemset(ticket, 0, 4);
     hipEventRecord(e0, 0);
-    int e = crs::scan_launch_wide(a, dim, nw, mfma, 0);
+    int e = ring ? crs::scan_launch_wide_ring(a, dim, nw, mfma, 0) : crs::scan_launch_wide(a, dim, nw, mfma, 0);
     hipEventRecord(e1, 0);
     hipDeviceSynchronize();
     if (e) { printf("launch error %d\n", e); return 1; }
@@ -93,8 +98,8 @@ int main(int argc, char** argv) {
   }
   std::vector<unsigned long long> hs(nst);
   hipMemcpy(hs.data(), st, nst * 8, hipMemcpyDeviceToHost);
-  printf("rows %d dim %d nq %d k %d | waves/wg %d nqb %d streams %d tiles/stream %.1f nt %d tickets %s stagger-knob %s defer-knob %s mfma %d | kernel %.1f us (with stamps)\n", rows, dim, nq,
-         k, nw, nqb, nwg, (double)n_tiles / nwg, a.nt, ticket ? "on" : "off", kn.wide_stagger ? "default" : "0", kn.wide_defer ? "default" : "0", mfma, ms * 1e3);
+  printf("rows %d dim %d nq %d k %d | waves/wg %d nqb %d streams %d tiles/stream %.1f nt %d tickets %s stagger-knob %s defer-knob %s mfma %d ring %d | kernel %.1f us (with stamps)\n", rows, dim, nq,
+         k, nw, nqb, nwg, (double)n_tiles / nwg, a.nt, ticket ? "on" : "off", kn.wide_stagger ? "default" : "0", kn.wide_defer ? "default" : "0", mfma, (int)ring, ms * 1e3);
   // slots 2 / 4: the selection of waves 4..7 (deferred one tile) / of waves 0..3; 5: a count, not a lap; 8, 9: unused since the tile-best rewrite
   const char* names[12] = {"prologue", "tile-load issue", "selection (waves 4-7, deferred)", "MFMA sweep", "selection (waves 0-3)", "chain runs (a count)",
                            "wait next tile + LDS store", "barrier", "(unused)", "(unused)", "final flush", "TOTAL"};
