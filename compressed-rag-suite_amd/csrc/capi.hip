@@ -260,6 +260,43 @@ int crs_rerank_lexical(const float* scores_dev, const int64_t* rows_dev, int nq,
   return e ? hip_fail((hipError_t)e, "rerank_lexical launch") : CRS_OK;
 }
 
+int crs_token_project(const float* hidden_dev, const void* w16_dev, const float* bias_dev, const int64_t* dst_dev, void* out16_dev,
+                      int64_t n_tok, int hidden, int dim, void* stream) {
+  if (dim < 1 || dim > 128) return fail(CRS_EINVAL, "dim must be in 1..128");
+  if (hidden < 32 || hidden > 1024 || hidden % 32) return fail(CRS_EINVAL, "hidden must be a multiple of 32 in 32..1024");
+  if (n_tok < 0 || n_tok > ((int64_t)1 << 36)) return fail(CRS_EINVAL, "n_tok must be in 0..2^36");
+  if (!hidden_dev) return fail(CRS_EINVAL, "hidden_dev is null");
+  if (!w16_dev) return fail(CRS_EINVAL, "w16_dev is null");
+  if (!dst_dev) return fail(CRS_EINVAL, "dst_dev is null");
+  if (!out16_dev) return fail(CRS_EINVAL, "out16_dev is null");
+  if (((uintptr_t)hidden_dev | (uintptr_t)w16_dev) & 15) return fail(CRS_EINVAL, "hidden_dev / w16_dev must be 16-byte aligned");
+  if (n_tok == 0) return CRS_OK;
+  const int e = crs::token_project_launch(hidden_dev, w16_dev, bias_dev, dst_dev, out16_dev, n_tok, hidden, dim, (hipStream_t)stream);
+  if (e == -1) return fail(CRS_EINVAL, "unsupported dim");
+  return e ? hip_fail((hipError_t)e, "token_project launch") : CRS_OK;
+}
+
+int crs_maxsim(const void* q16_dev, const int32_t* q_len_dev, int nq, int lq_max, const void* tok16_dev, const int64_t* offsets_dev,
+               int64_t n_rows, int64_t n_tokens, const int64_t* rows_dev, int m_max, int dimp, float* out_dev, void* stream) {
+  if (lq_max < 1 || lq_max > CRS_MAXSIM_MAX_QUERY) return fail(CRS_EINVAL, "lq_max must be in 1..CRS_MAXSIM_MAX_QUERY");
+  if (dimp != 32 && dimp != 64 && dimp != 96 && dimp != 128) return fail(CRS_EINVAL, "dimp must be 32, 64, 96 or 128");
+  if (nq < 0 || nq > 65535) return fail(CRS_EINVAL, "nq must be in 0..65535");
+  if (m_max < 1) return fail(CRS_EINVAL, "bad m_max (m_max >= 1)");
+  if (n_rows < 0 || n_tokens < 0) return fail(CRS_EINVAL, "bad n_rows/n_tokens");
+  if (!q16_dev) return fail(CRS_EINVAL, "q16_dev is null");
+  if (!q_len_dev) return fail(CRS_EINVAL, "q_len_dev is null");
+  if (!offsets_dev) return fail(CRS_EINVAL, "offsets_dev is null");
+  if (!rows_dev) return fail(CRS_EINVAL, "rows_dev is null");
+  if (!out_dev) return fail(CRS_EINVAL, "out_dev is null");
+  if (n_tokens > 0 && !tok16_dev) return fail(CRS_EINVAL, "tok16_dev is null");
+  if (((uintptr_t)q16_dev | (uintptr_t)tok16_dev) & 15) return fail(CRS_EINVAL, "q16_dev / tok16_dev must be 16-byte aligned");
+  if (nq == 0) return CRS_OK;
+  const int e = crs::maxsim_launch(q16_dev, q_len_dev, nq, lq_max, tok16_dev, offsets_dev, n_rows, n_tokens, rows_dev, m_max, dimp,
+                                   out_dev, (hipStream_t)stream);
+  if (e == -1) return fail(CRS_EINVAL, "unsupported dimp");
+  return e ? hip_fail((hipError_t)e, "maxsim launch") : CRS_OK;
+}
+
 int crs_pairs_above_f16(const void* slab_dev, int64_t n_rows, int dim, int64_t a_first, int64_t a_rows, int64_t b_first, int64_t b_rows,
                         float thr, int64_t* pairs_out_dev, float* scores_out_dev, int64_t cap, int64_t* count_dev, void* stream) {
   if (dim < 1 || dim > 1024) return fail(CRS_EINVAL, "bad dim (1 <= dim <= 1024)");

@@ -121,6 +121,13 @@ int unigram_encode_launch(const uint8_t* text, const int64_t* offsets, int n_tex
 int token_match_launch(const float* a, const int* len_a, int seq_a, const float* b, const int* len_b, int seq_b, int n_pairs, int hidden,
                        const float* w_a, const float* w_b, float* out, hipStream_t stream);
 
+// maxsim.hip: late-interaction scores of [nq, m_max] candidate rows over a token-vector CSR, one wave per pair; -1 = bad dimp
+int maxsim_launch(const void* q16, const int* q_len, int nq, int lq_max, const void* tok16, const int64_t* offsets, int64_t n_rows,
+                  int64_t n_tokens, const int64_t* rows, int m_max, int dimp, float* out, hipStream_t stream);
+// token_project.hip: hidden states -> packed unit-length fp16 token vectors, one wave per 16 tokens; -1 = bad dim
+int token_project_launch(const float* hidden, const void* w16, const float* bias, const int64_t* dst, void* out16, int64_t n_tok,
+                         int H, int dim, hipStream_t stream);
+
 // join.hip: thresholded self-join of an fp16 slab (pairs i < j with slab score >= thr, 256 x 256 tiles) and the fp32 check of its
 // candidates against the shadow, a quarter wave per pair
 int pairs_above_launch(const void* slab, int pdim, int64_t a_first, int64_t a_rows, int64_t b_first, int64_t b_rows, float thr,

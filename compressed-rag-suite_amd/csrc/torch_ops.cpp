@@ -24,6 +24,7 @@
 //   crs::wordpiece_encode          BERT basic tokenisation + WordPiece of UTF-8 texts on the device (the tokenizer inside SentenceTransformer.encode)
 //   crs::bm25_topk / crs::fuse_rrf   hybrid retrieval: exact BM25 scan over the token CSR, reciprocal rank fusion (new vs the reference)
 //   crs::pairs_above / crs::pairs_verify   near-duplicate detection: thresholded self-join of the slab, fp32 check (new vs the reference)
+//   crs::token_project / crs::maxsim   late interaction (ColBERT): per-token projection and MaxSim scoring of candidate lists (new vs the reference)
 //   crs::rerank_lexical    replaces the scoring, threshold and _rerank loops of retrieve_batch  (reference rag/retrieval.py:75-77, 196-217)
 // Tensors are torch-owned; every op launches on the CURRENT HIP stream of the tensors' device, so the ops
 // compose with torch streams and hipGraph capture.  Errors of the C ABI surface as RuntimeError (TORCH_CHECK)
@@ -635,6 +636,55 @@ void rerank_lexical(const Tensor& scores, const Tensor& rows, const Tensor& doc_
      "crs::rerank_lexical");
 }
 
+// ---- late interaction (csrc/token_project.hip, csrc/maxsim.hip) ------------------------------------------------------
+// hidden fp32 [n_tok, H]; w16 fp16 [dim, H]; bias fp32 [dim] (optional); dst int64 [n_tok], < 0 = drop, else a row of out16 (the
+// caller builds it on the host and keeps it below out16's rows); out16 fp16 [rows, dim rounded up to 32]
+void token_project(const Tensor& hidden, const Tensor& w16, c10::optional<Tensor> bias, const Tensor& dst, Tensor out16) {
+  want(hidden, at::kFloat, "hidden");
+  want(w16, at::kHalf, "w16");
+  want(dst, at::kLong, "dst");
+  want(out16, at::kHalf, "out16");
+  if (has(bias)) want(*bias, at::kFloat, "bias");
+  same_device(hidden, {&w16, opt_t(bias), &dst, &out16}, "crs::token_project");
+  TORCH_CHECK(hidden.dim() == 2 && w16.dim() == 2 && w16.size(1) == hidden.size(1), "hidden must be fp32 [n_tok, H] and w16 fp16 [dim, H]");
+  const int64_t n_tok = hidden.size(0), H = hidden.size(1), dim = w16.size(0);
+  TORCH_CHECK(dim >= 1 && dim <= 128 && H <= 1024, "dim must be in 1..128 and H at most 1024");
+  TORCH_CHECK(dst.dim() == 1 && dst.size(0) == n_tok, "dst must be int64 [n_tok]");
+  TORCH_CHECK(out16.dim() == 2 && out16.size(1) == (dim + 31) / 32 * 32, "out16 must be fp16 [rows, dim rounded up to 32]");
+  if (has(bias)) TORCH_CHECK(bias->numel() == dim, "bias must be fp32 [dim]");
+  if (n_tok == 0) return;
+  c10::hip::HIPGuardMasqueradingAsCUDA g(hidden.device());
+  ok(crs_token_project(hidden.data_ptr<float>(), w16.data_ptr(), (const float*)opt_ptr(bias), dst.data_ptr<int64_t>(), out16.data_ptr(),
+                       n_tok, (int)H, (int)dim, cur_stream(hidden)), "crs::token_project");
+}
+
+// q16 fp16 [nq, lq_max, dimp]; q_len int32 [nq]; tok16 fp16 [>= n_tokens, dimp]; offsets int64 [>= n_rows + 1]; rows int64 /
+// out fp32 [nq, m_max]
+void maxsim(const Tensor& q16, const Tensor& q_len, const Tensor& tok16, int64_t n_tokens, const Tensor& offsets, int64_t n_rows,
+            const Tensor& rows, Tensor out) {
+  want(q16, at::kHalf, "q16");
+  want(q_len, at::kInt, "q_len");
+  want(tok16, at::kHalf, "tok16");
+  want(offsets, at::kLong, "offsets");
+  want(rows, at::kLong, "rows");
+  want(out, at::kFloat, "out");
+  same_device(q16, {&q_len, &tok16, &offsets, &rows, &out}, "crs::maxsim");
+  TORCH_CHECK(q16.dim() == 3 && q16.size(1) >= 1 && q16.size(1) <= CRS_MAXSIM_MAX_QUERY, "q16 must be fp16 [nq, lq_max <= 64, dimp]");
+  const int64_t nq = q16.size(0), dimp = q16.size(2);
+  TORCH_CHECK(nq <= 65535, "too many queries");
+  TORCH_CHECK(dimp == 32 || dimp == 64 || dimp == 96 || dimp == 128, "dimp must be 32, 64, 96 or 128");
+  TORCH_CHECK(q_len.dim() == 1 && q_len.size(0) == nq, "q_len must be int32 [nq]");
+  TORCH_CHECK(tok16.dim() == 2 && tok16.size(1) == dimp && n_tokens >= 0 && n_tokens <= tok16.size(0), "tok16 must be fp16 [>= n_tokens, dimp]");
+  TORCH_CHECK(n_rows >= 0 && offsets.dim() == 1 && offsets.numel() >= n_rows + 1, "offsets must be int64 [>= n_rows + 1]");
+  TORCH_CHECK(rows.dim() == 2 && rows.size(0) == nq && rows.size(1) >= 1 && rows.size(1) <= 0x7fffffff && out.sizes() == rows.sizes(),
+              "rows / out must be [nq, m_max >= 1]");
+  if (nq == 0) return;
+  c10::hip::HIPGuardMasqueradingAsCUDA g(q16.device());
+  ok(crs_maxsim(q16.data_ptr(), q_len.data_ptr<int32_t>(), (int)nq, (int)q16.size(1), n_tokens ? tok16.data_ptr() : nullptr,
+                offsets.data_ptr<int64_t>(), n_rows, n_tokens, rows.data_ptr<int64_t>(), (int)rows.size(1), (int)dimp,
+                out.data_ptr<float>(), cur_stream(q16)), "crs::maxsim");
+}
+
 // ---- near-duplicate join (csrc/join.hip) ---------------------------------------------------------------------------
 // slab fp16 [>= n_rows, pdim]; pairs int64 [cap, 2], scores fp32 [cap]; count int64 [1], zeroed by the caller, receives the number
 // of qualifying pairs (count > cap: overflow)
@@ -974,6 +1024,8 @@ TORCH_LIBRARY(crs, m) {
   m.def("token_match_out(Tensor a, Tensor len_a, Tensor b, Tensor len_b, Tensor? w_a, Tensor? w_b, Tensor(a!) out) -> ()");
   m.def("rerank_lexical(Tensor scores, Tensor rows, Tensor doc_offsets, Tensor doc_tokens, int n_rows, Tensor q_offsets, Tensor q_tokens, "
         "Tensor q_norm, int k, float threshold, Tensor(a!) order, Tensor(b!) count, Tensor(c!) sim, Tensor(d!) rr, Tensor(e!) reranked) -> ()");
+  m.def("token_project(Tensor hidden, Tensor w16, Tensor? bias, Tensor dst, Tensor(a!) out16) -> ()");
+  m.def("maxsim(Tensor q16, Tensor q_len, Tensor tok16, int n_tokens, Tensor offsets, int n_rows, Tensor rows, Tensor(a!) out) -> ()");
   m.def("pairs_above_out(Tensor slab, int n_rows, int dim, int a_first, int a_rows, int b_first, int b_rows, float thr, "
         "Tensor(a!) pairs, Tensor(b!) scores, Tensor(c!) count) -> ()");
   m.def("pairs_verify_out(Tensor pairs, Tensor shadow, int n_rows, float thr, Tensor(a!) rows_a, Tensor(b!) rows_b, Tensor(c!) sims, "
@@ -1025,6 +1077,8 @@ TORCH_LIBRARY_IMPL(crs, CUDA, m) {   // the HIP backend of torch-ROCm dispatches
   m.impl("mmr_order_out", &mmr_order_out);
   m.impl("token_match_out", &token_match_out);
   m.impl("rerank_lexical", &rerank_lexical);
+  m.impl("token_project", &token_project);
+  m.impl("maxsim", &maxsim);
   m.impl("pairs_above_out", &pairs_above_out);
   m.impl("pairs_verify_out", &pairs_verify_out);
   m.impl("bm25_topk", &bm25_topk);

@@ -31,6 +31,7 @@ UNIGRAM_TILE_BYTES = 1024     # CRS_UNIGRAM_TILE_BYTES: the same for crs_unigram
 UNIGRAM_MAX_WORD = 128        # CRS_UNIGRAM_MAX_WORD: code points of the longest word it walks (U+2581 included); longer: the host's
 UNIGRAM_COLLAPSE, UNIGRAM_SINGLE_META, UNIGRAM_RUN_META, UNIGRAM_CRLF = 1, 2, 4, 8    # CRS_UNIGRAM_* option bits
 BM25_MAX_PAIRS = 4096      # CRS_BM25_MAX_PAIRS: (query, known token) pairs of one crs_bm25_topk launch
+MAXSIM_MAX_QUERY = 64      # CRS_MAXSIM_MAX_QUERY: query tokens of crs_maxsim (csrc/maxsim.hip)
 PAIRS_TILE = 256           # CRS_PAIRS_TILE: tile edge of the near-duplicate join (csrc/join.hip)
 PAIRS_MAX_TILES = 1 << 22  # CRS_PAIRS_MAX_TILES: tile pairs of one crs_pairs_above_f16 launch
 SPACE_COSINE, SPACE_IP, SPACE_L2 = 0, 1, 2    # CRS_SPACE_*: a collection's hnsw:space
@@ -71,6 +72,9 @@ _SIGNATURES = {
     "crs_token_match": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "crs_rerank_lexical": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64,
                                    c_void_p, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "crs_token_project": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "crs_maxsim": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_int, c_void_p,
+                           c_void_p]),
     "crs_pairs_above_f16": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, c_int64, c_float, c_void_p, c_void_p, c_int64,
                                     c_void_p, c_void_p]),
     "crs_pairs_verify_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -457,6 +461,34 @@ def rerank_lexical(scores, rows, doc_offsets, doc_tokens, n_rows: int, q_offsets
                torch.empty(nq, dtype=torch.int32, device=dev))
     with _translate():
         ops().rerank_lexical(scores, rows, doc_offsets, doc_tokens, int(n_rows), q_offsets, q_tokens, q_norm, int(k), float(threshold), *out)
+    return out
+
+
+def token_dim_padded(dim: int) -> int:
+    """Row length of a token-vector array: dim rounded up to a multiple of 32 (crs_token_project, crs_maxsim)."""
+    return (int(dim) + 31) // 32 * 32
+
+
+def token_project(hidden, w16, bias, dst, out16):
+    """Hidden states to packed unit-length fp16 token vectors (crs_token_project, csrc/token_project.hip): hidden cuda fp32
+    [n_tok, H], w16 fp16 [dim <= 128, H], bias fp32 [dim] or None, dst int64 [n_tok] (output row of each token, < 0 = drop: that
+    hidden row is never read) -> out16 fp16 [rows, token_dim_padded(dim)], written in place: row dst = W h (+ b) scaled to unit
+    length, zeros past dim.  The caller keeps every dst below out16's rows (it builds the table on the host).  No host sync."""
+    with _translate():
+        ops().token_project(hidden, w16, bias, dst, out16)
+    return out16
+
+
+def maxsim(q16, q_len, tok16, n_tokens: int, offsets, n_rows: int, rows, out=None):
+    """Late-interaction scores of nq candidate lists in one launch (crs_maxsim, csrc/maxsim.hip): q16 cuda fp16 [nq, lq_max <= 64,
+    dimp], q_len int32 [nq], tok16 fp16 [>= n_tokens, dimp] with the CSR offsets int64 [>= n_rows + 1], rows int64 [nq, m_max] ->
+    fp32 [nq, m_max]: sum over the query's tokens of the best dot product with a token of the row's document; -inf for a row outside
+    [0, n_rows), 0 for an empty document or query.  No host sync."""
+    import torch
+    if out is None:
+        out = torch.empty(rows.shape, dtype=torch.float32, device=rows.device)
+    with _translate():
+        ops().maxsim(q16, q_len, tok16, int(n_tokens), offsets, int(n_rows), rows, out)
     return out
 
 

@@ -85,6 +85,17 @@ New, additive surface (all keys absent from the reference config.json default so
                               ``dedup_max_pairs`` (4 M) bounds the pairs such a join may list.  fp16 cosine stores with the fp32
                               shadow on one device: int8, 'ip' / 'l2', sharded / num_gpus / devices raise NotImplementedError,
                               refine_fp32: False raises ValueError
+  ``attach_token_encoder`` / ``token_index`` / ``max_index_bytes``   late-interaction re-ranking (rag/late_interaction.py, the
+                              retriever's opt-in ``late_interaction``): a per-token index of every chunk -- fp16 [n_tokens, dimp]
+                              unit vectors on the device, grown by doubling, and int64 offsets [n_rows + 1] on the host and on the
+                              device -- that crs_maxsim reads through lists of sidecar rows (csrc/maxsim.hip).  Derived data, handled
+                              like the token CSR: built on first use (one encoder pass over every document), extended by the rows
+                              that arrived since (rows already held are never re-encoded by an append), and DROPPED WHOLE by a
+                              delete, a document update or an upsert that changes a document -- the next use re-encodes every
+                              document, an O(index) encoder pass: batch such calls.  NOT persisted (a re-opened store rebuilds it on
+                              first use) and ONE device only (sharded / num_gpus / devices raise NotImplementedError).  Before any
+                              encoding the bytes the index would take (host-side token counts x dimp x 2) are compared with
+                              ``max_index_bytes`` (config key; default: half the device's total memory): more raises ValueError
 ``where`` / ``where_document`` filters work on every layout (the sidecars are replicated; each shard scans the
 allowed rows it owns).  ``top_k`` is unlimited as in the reference: up to 1024 a refined shard is over-fetched by
 partition (64 candidates from each of up to 64 row chunks, crs::cosine_topk_large_cert) and certified like top_k <= 64;
@@ -425,6 +436,60 @@ class _TokenCSR:
         return tf[: self.total], dl[: self.rows]
 
 
+class _TokenIndex:
+    """The late-interaction token vectors of every row, for crs_maxsim (csrc/maxsim.hip): ``tok16`` cuda fp16 [capacity, dimp],
+    the first ``n_tokens`` rows in use (row r's tokens are [offsets[r], offsets[r + 1])), grown by doubling; ``offsets`` int64
+    [n_rows + 1] on the host, ``offsets_dev`` its device copy.  Extended in place as rows arrive: an append encodes the new rows
+    alone."""
+
+    def __init__(self, encoder, device):
+        self.encoder, self.device, self.dimp = encoder, device, encoder.dimp
+        self.tok16 = None
+        self.n_tokens = 0
+        self.offsets = np.zeros(1, dtype=np.int64)
+        self.offsets_dev = None
+
+    @property
+    def n_rows(self) -> int:
+        return len(self.offsets) - 1
+
+    def extend(self, documents: Sequence[str], max_bytes: int) -> None:
+        """Encode documents[n_rows:] and append their token vectors; ValueError (before any encoding) when the tokens in use would
+        then take more than max_bytes.  The new rows are tokenised once and encoded straight into `tok16` (no temporary copy of
+        them).  Memory beyond the guarded figure: the capacity grows by doubling, but never past max_bytes' worth of tokens unless
+        the tokens in use need it, so the array itself stays within max(max_bytes, bytes in use); WHILE it grows the old and the
+        new array exist side by side, so the peak of an append that grows an index of b bytes to capacity c is b + c, up to
+        b + max_bytes; and the encoder's own workspace and hidden states of one batch come on top.  With the default limit of
+        half the device's memory an index close to the limit can therefore still run out of memory when it grows: build it in
+        one call (one allocation of the exact size) or set max_index_bytes lower."""
+        import torch
+        new = list(documents[self.n_rows:])
+        if not new and self.offsets_dev is not None:
+            return
+        ids = self.encoder.tokenize_docs(new)
+        counts = self.encoder.doc_token_counts(new, ids=ids)
+        total = self.n_tokens + int(counts.sum())
+        need = total * self.dimp * 2
+        if need > max_bytes:
+            raise ValueError(f"the late-interaction token index would take {need} bytes ({total} tokens x {self.dimp} x 2) for "
+                             f"{len(documents)} rows, more than max_index_bytes = {int(max_bytes)}")
+        with torch.cuda.device(self.device):
+            held = self.tok16.shape[0] if self.tok16 is not None else 0
+            if new and total > held:
+                cap = max(total, min(2 * held, int(max_bytes) // (self.dimp * 2)), 1)
+                grown = torch.zeros((cap, self.dimp), dtype=torch.float16, device=self.device)
+                if self.n_tokens:
+                    grown[:self.n_tokens] = self.tok16[:self.n_tokens]
+                self.tok16 = grown
+            if new:
+                self.encoder.encode_docs_device(new, ids=ids, out=self.tok16, first_slot=self.n_tokens)
+                self.offsets = np.concatenate([self.offsets, self.n_tokens + np.cumsum(counts)]).astype(np.int64)
+                self.n_tokens = total
+            if self.tok16 is None:
+                self.tok16 = torch.zeros((1, self.dimp), dtype=torch.float16, device=self.device)
+            self.offsets_dev = torch.from_numpy(self.offsets).to(self.device)
+
+
 class SlabCollection:
     """What ``VectorStore.collection`` exposes (the retriever reads ``.metadata`` and the harness ``.count()``,
     reference rag/retrieval.py:48-50).  Owns the per-device shards and the host sidecars."""
@@ -509,7 +574,7 @@ class SlabCollection:
 
     def _drop_derived(self, ids_changed: bool, metadata_changed: bool = True, documents_changed: bool = True):
         """Forget what was derived from the sidecars: the inverted metadata index, (rows renumbered) the id map, and (a document
-        changed, or rows renumbered) the token CSR with its device mirror."""
+        changed, or rows renumbered) the token CSR with its device mirror and the late-interaction token index."""
         if metadata_changed or ids_changed:
             self.__dict__.pop("_inv", None)
             self.__dict__.pop("_inv_rows", None)
@@ -518,6 +583,7 @@ class SlabCollection:
             self.__dict__.pop("_idmap_rows", None)
         if documents_changed or ids_changed:
             self.__dict__.pop("_tok", None)
+            self.__dict__.pop("_li", None)       # the late-interaction token index: the next use re-encodes every document
 
     def _token_csr(self) -> _TokenCSR:
         """The token ids of every row (see _TokenCSR): built by one pass over the documents on first use, extended by the rows
@@ -528,6 +594,16 @@ class SlabCollection:
         if csr.rows < len(self.documents):
             csr.extend(self.documents)
         return csr
+
+    def _token_index(self, encoder, max_bytes: int) -> _TokenIndex:
+        """The late-interaction token vectors of every row (see _TokenIndex), for `encoder`: built on first use, extended by the
+        rows that arrived since, like _token_csr; dropped by _drop_derived, and when another encoder asks."""
+        index = self.__dict__.get("_li")
+        if index is None or index.encoder is not encoder:
+            index = self.__dict__["_li"] = _TokenIndex(encoder, self.device)
+        if index.n_rows < len(self.documents) or index.offsets_dev is None:
+            index.extend(self.documents, max_bytes)
+        return index
 
     # -- metadata filters: value -> rows, built once and extended as rows arrive (the per-query loop over all metadatas is gone)
     def _inverted(self):
@@ -671,6 +747,9 @@ class VectorStore:
         if self.sharded and self.persist_directory:
             raise NotImplementedError("persist_directory is not supported with sharded=True (each rank holds only its rows); "
                                       "use num_gpus for a persisted multi-GPU store")
+        # late-interaction token index (module docstring): the encoder comes through attach_token_encoder
+        self.max_index_bytes = config.get('max_index_bytes', None)     # None: half the device's total memory, read on first use
+        self._token_encoder = None
         self._filters = {}      # filter key -> {"n": rows when built, "rows": allowed sidecar rows, "shards": {g: compacted sub-slab}}
         self._persisted_rows = None   # rows the append-only files hold (None: nothing / legacy format on disk)
         self._docs_bytes = 0          # length of the sidecar file the header vouches for
@@ -1477,6 +1556,31 @@ class VectorStore:
             return sh.shadow[idx].cpu().numpy()
         back = sh.norm_scale_host * (2.0 if sh.space == nat.SPACE_L2 else 1.0)
         return (sh.shadow[idx, :sh.dim] * back).cpu().numpy()
+
+    def attach_token_encoder(self, reranker) -> None:
+        """The LateInteractionReranker (rag/late_interaction.py) whose token vectors token_index() holds.  Attaching another one
+        forgets the index built with the previous one."""
+        self._token_encoder = reranker
+
+    def token_index(self, reranker=None) -> _TokenIndex:
+        """The late-interaction token index of the collection (_TokenIndex: tok16, n_tokens, offsets, offsets_dev, n_rows) for the
+        attached encoder (`reranker`, when given, is attached first).  Built on first use; afterwards only the rows that arrived
+        since are encoded.  A delete, a document update or an upsert drops it (SlabCollection._drop_derived) and the next call
+        re-encodes every document.  Not persisted; one device only.  ValueError when it would exceed max_index_bytes."""
+        import torch
+        if reranker is not None and reranker is not self._token_encoder:
+            self.attach_token_encoder(reranker)
+        if self._token_encoder is None:
+            raise ValueError("no token encoder attached: call attach_token_encoder(LateInteractionReranker(...)) first")
+        col = self.collection
+        if col is None:
+            raise ValueError("No collection available. Create index first.")
+        if self.sharded or len(col.shards) != 1:
+            raise NotImplementedError("the late-interaction token index lives on one device: sharded / num_gpus / devices are not supported")
+        limit = self.max_index_bytes
+        if limit is None:
+            limit = torch.cuda.get_device_properties(col.device).total_memory // 2
+        return col._token_index(self._token_encoder, int(limit))
 
     def mmr_order(self, rows, rel, counts, lam: float):
         """Greedy MMR order of many result lists at once, on the device (crs_mmr_order, csrc/mmr.hip): rows int64 / rel fp64

@@ -155,4 +155,6 @@ class RAGPipeline:
                                   'distance_metric': r.distance_metric}
             if getattr(r, 'cross_encoder', None) is not None:     # retrieval.rerank_model (additive): the cross-encoder in use
                 stats['retrieval']['rerank_model'] = r.cross_encoder.model_name
+            if getattr(r, 'late_interaction', None) is not None:  # retrieval.late_interaction (additive): the ColBERT model in use
+                stats['retrieval']['late_interaction'] = r.late_interaction.model_name
         return stats

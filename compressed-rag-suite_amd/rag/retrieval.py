@@ -15,6 +15,12 @@ on, a BERT cross-encoder scores every (query, chunk text) pair that passed the t
 is sorted on it (stable, descending) and cut to ``top_k``; the search, the ``2 * top_k`` fetch, the threshold and the MMR step
 (on ``score``) are as without it.
 
+Opt-in, ``late_interaction`` (a rag/late_interaction.py config dict, or a model name; exclusive with ``rerank_model``): with
+``rerank`` on, the lists of every device batch are scored by late interaction (ColBERT's MaxSim) in ONE kernel launch
+(csrc/maxsim.hip) over the store's per-token index (VectorStore.token_index: every chunk encoded once, at index time) -- only the
+queries are encoded at query time.  ``rerank_score`` is the MaxSim score, the list is sorted on it (stable, descending) and cut to
+``top_k``, as with ``rerank_model``; the hybrid lists and ``retrieve``'s filtered lists go through the same scoring.
+
 Opt-in, ``hybrid`` (``true``, or a dict of ``rrf_k``, ``weights``, ``k1``, ``b``): ``retrieve_batch`` fuses the thresholded dense list of every
 query with an exact BM25 list over the whole collection (VectorStore.bm25_rows, csrc/bm25.hip) by weighted reciprocal rank fusion
 (VectorStore.fuse_rrf, csrc/fuse.hip), so a chunk the encoder ranks far down still surfaces when it matches the query's words;
@@ -75,6 +81,18 @@ class ContextRetriever:
         if config.get('rerank_model'):
             from rag.reranking import CrossEncoderReranker
             self.cross_encoder = CrossEncoderReranker(config['rerank_model'])
+        # additive: late interaction in place of the token-overlap rule (rag/late_interaction.py; a config dict, or a string used as
+        # its model_name).  Resolved here and attached to the store, whose token index is built on the first re-ranked query (or by
+        # VectorStore.token_index()); used only while `rerank` is on; lexical_rerank: 'device' is then not taken
+        self.late_interaction = None
+        if config.get('late_interaction'):
+            if config.get('rerank_model'):
+                raise ValueError("late_interaction and rerank_model are exclusive: one model re-ranks a list")
+            if not hasattr(vector_store, 'token_index'):
+                raise ValueError("late_interaction needs a store with a token index (VectorStore.token_index)")
+            from rag.late_interaction import LateInteractionReranker
+            self.late_interaction = LateInteractionReranker(config['late_interaction'])
+            vector_store.attach_token_encoder(self.late_interaction)
         # additive: hybrid retrieval.  False (default) | True | {'rrf_k': 60, 'weights': [1, 1], 'k1': 1.5, 'b': 0.75}: retrieve_batch
         # fuses each thresholded dense list with the BM25 list of the same query over the whole collection (same `fetch`) by
         # weighted reciprocal rank fusion: fused = w_dense / (rrf_k + i + 1) + w_lex / (rrf_k + j + 1) over the 0-based ranks; 'score'
@@ -181,6 +199,9 @@ class ContextRetriever:
         if self.rerank and self.cross_encoder is not None:
             chunks = self._rerank_cross([query], [chunks], k)[0]
             self.last_rerank = {'mode': 'cross-encoder', 'lists': 1}
+        elif self.rerank and self.late_interaction is not None:
+            chunks = self._rerank_late([query], [chunks], k, self._rows_of_chunks(chunks))[0]
+            self.last_rerank = {'mode': 'late-interaction', 'lists': 1}
         elif self.rerank and len(chunks) > k:
             chunks = self._rerank(query, chunks, k)
         else:
@@ -197,6 +218,8 @@ class ContextRetriever:
         if self.hybrid is not None:
             if filters is not None:
                 raise ValueError("hybrid retrieval does not take metadata filters: the lexical list is not filtered")
+            return self.retrieve_batch([query], top_k=top_k)[0]
+        if self.late_interaction is not None and self.rerank and filters is None:
             return self.retrieve_batch([query], top_k=top_k)[0]
         try:
             query_embedding = self.embedding_model.embed(query)
@@ -309,8 +332,11 @@ class ContextRetriever:
         ids_l, docs_l, metas_l = getattr(col, 'ids', None), getattr(col, 'documents', None), getattr(col, 'metadatas', None)
         queries = list(queries)
         cross = self.cross_encoder if self.rerank else None
+        late = self.late_interaction if self.rerank else None
+        if late is not None and ids_l is None:
+            raise ValueError("late_interaction needs a store that returns sidecar rows (search_rows)")
         on_device = (self.lexical_rerank == 'device' and bool(self.rerank) and self.distance_metric == 'cosine' and fetch <= 64
-                     and ids_l is not None and hasattr(store, 'rerank_lexical') and cross is None and hybrid is None)
+                     and ids_l is not None and hasattr(store, 'rerank_lexical') and cross is None and late is None and hybrid is None)
         host_pieces = 0
         for piece in self._search_many(queries, fetch):      # one device batch at a time: its dicts are built while the next ones run
             piece_start = len(per_query)
@@ -320,11 +346,13 @@ class ContextRetriever:
                 host_pieces += 1
                 piece_queries = queries[piece_start:piece_start + len(piece)]
                 for query, chunks in zip(piece_queries, self._hybrid_lists(piece_queries, piece, fetch, row_of)):
-                    if chunks and cross is None:
+                    if chunks and cross is None and late is None:
                         chunks = self._rerank(query, chunks, k) if self.rerank and len(chunks) > k else chunks[:k]
                     per_query.append(chunks)
                 if cross is not None:
                     per_query[piece_start:] = self._rerank_cross(piece_queries, per_query[piece_start:], k)
+                elif late is not None:
+                    per_query[piece_start:] = self._rerank_late(piece_queries, per_query[piece_start:], k, row_of)
                 continue
             if on_device and not isinstance(piece, dict):
                 built = self._rerank_on_device(queries[len(per_query):len(per_query) + len(piece)], piece, k, row_of)
@@ -366,12 +394,15 @@ class ContextRetriever:
                     logger.warning(f"No chunks passed similarity threshold of {self.similarity_threshold}")
                     per_query.append([])
                     continue
-                if cross is None:                         # (the cross-encoder takes the whole piece at once, below)
+                if cross is None and late is None:        # (a model takes the whole piece at once, below)
                     chunks = self._rerank(query, chunks, k) if self.rerank and len(chunks) > k else chunks[:k]
                 per_query.append(chunks)
             if cross is not None:
                 per_query[piece_start:] = self._rerank_cross(queries[piece_start:len(per_query)], per_query[piece_start:], k)
-        self.last_rerank = {'mode': 'cross-encoder' if cross is not None else 'device' if on_device and not host_pieces else 'host',
+            elif late is not None:                    # (ids_l is not None: checked before the loop)
+                per_query[piece_start:] = self._rerank_late(queries[piece_start:len(per_query)], per_query[piece_start:], k, row_of)
+        self.last_rerank = {'mode': 'cross-encoder' if cross is not None else 'late-interaction' if late is not None
+                            else 'device' if on_device and not host_pieces else 'host',
                             'lists': len(per_query) if self.rerank else 0}
         self.last_mmr = {'mode': 'host', 'lists': sum(1 for chunks in per_query if len(chunks) > 1) if self.diversity_penalty > 0 else 0}
         # the MMR kernel reads the store's fp32 rows as they are stored: cosine only (as the lexical kernel above); in the other
@@ -562,6 +593,35 @@ class ContextRetriever:
             for c in chunks:
                 c['rerank_score'] = scores[at]
                 at += 1
+            out.append(sorted(chunks, key=lambda c: c['rerank_score'], reverse=True)[:top_k])
+        return out
+
+    def _rows_of_chunks(self, chunks: List[Dict]) -> Dict[int, int]:
+        """id(chunk dict) -> sidecar row for chunks that came back from VectorStore.search (retrieve's filtered path): the row
+        whose id is the chunk's and whose document is its text (create_index accepts duplicate ids)."""
+        col = self.vector_store.collection
+        idmap = col._id_rows()
+        out = {}
+        for c in chunks:
+            rows = idmap.get(c['chunk_id'], [])
+            out[id(c)] = next((r for r in rows if col.documents[r] == c['text']), rows[0] if rows else -1)
+        return out
+
+    def _rerank_late(self, queries: List[str], lists: List[List[Dict]], top_k: int, row_of: Dict[int, int]) -> List[List[Dict]]:
+        """Late interaction in place of _rerank, for the chunk lists of several queries at once: ONE LateInteractionReranker.score_rows
+        call (the queries' encoder forward + one crs_maxsim launch over the store's token index) for a padded [queries, longest]
+        block of sidecar rows; rerank_score = the MaxSim score, each list sorted on it (stable, descending) and cut."""
+        m_max = max((len(chunks) for chunks in lists), default=0)
+        if m_max == 0:
+            return [chunks[:top_k] for chunks in lists]
+        rows = np.full((len(lists), m_max), -1, dtype=np.int64)
+        for i, chunks in enumerate(lists):
+            rows[i, :len(chunks)] = [row_of[id(c)] for c in chunks]
+        scores = self.late_interaction.score_rows(queries, rows, self.vector_store).cpu().numpy()
+        out = []
+        for i, chunks in enumerate(lists):
+            for c, v in zip(chunks, scores[i, :len(chunks)].tolist()):
+                c['rerank_score'] = v
             out.append(sorted(chunks, key=lambda c: c['rerank_score'], reverse=True)[:top_k])
         return out
 

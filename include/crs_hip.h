@@ -460,6 +460,39 @@ int crs_pairs_above_f16(const void* slab_dev, int64_t n_rows, int dim, int64_t a
 int crs_pairs_verify_f32(const int64_t* pairs_dev, int64_t m, const float* shadow_f32_dev, int64_t n_rows, int dim, float thr,
                          int64_t* rows_a_dev, int64_t* rows_b_dev, float* sims_dev, int64_t* count_dev, void* stream);
 
+/* ---- late interaction (ColBERT): per-token projection and MaxSim scoring of candidate lists -- no reference call site: the
+ * reference re-ranks by token overlap alone (rag/retrieval.py:_rerank) (additive to ABI 3; csrc/token_project.hip, csrc/maxsim.hip,
+ * DESIGN 3.15) ----
+ * crs_token_project turns final hidden states into packed unit-length fp16 token vectors, dimp = dim rounded up to a multiple of 32:
+ *   hidden_dev  fp32 [n_tok, hidden]   16-byte aligned; a row whose dst is negative is NEVER read (a padding position)
+ *   w16_dev     fp16 [dim, hidden]     row-major (out, in), 16-byte aligned
+ *   bias_dev    fp32 [dim] or null
+ *   dst_dev     int64 [n_tok]          output slot of each token, < 0 = drop; the caller keeps the slots inside out16_dev
+ *   out16_dev   fp16 [*, dimp]         out: row dst = y, zeros in [dim, dimp)
+ * v = W h (+ b) with h rounded to fp16 on load and fp32 accumulation (v_mfma_f32_16x16x32_f16), y = v / |v| with the norm and the
+ * scaling in fp32, rounded to fp16 once; y is all zeros when |v| is 0.  A token's output does not depend on what else is in the launch.
+ * Limits (CRS_EINVAL otherwise, before any launch): 1 <= dim <= 128; hidden a multiple of 32 in 32..1024; 0 <= n_tok <= 2^36
+ * (0: no launch).  No workspace, no host synchronisation.
+ *
+ * crs_maxsim scores nq lists of m_max candidate rows in one launch, one wave per (query, candidate):
+ *   q16_dev      fp16 [nq, lq_max, dimp]  query token vectors, 16-byte aligned; rows at or past q_len are never read
+ *   q_len_dev    int32 [nq]               query tokens (clamped to [0, lq_max])
+ *   tok16_dev    fp16 [n_tokens, dimp]    the index's token vectors, 16-byte aligned (may be null when n_tokens is 0)
+ *   offsets_dev  int64 [n_rows + 1]       CSR over tok16_dev: row r holds tokens [offsets[r], offsets[r + 1]); clamped into
+ *                                         [0, n_tokens]
+ *   rows_dev     int64 [nq, m_max]        candidate rows
+ *   out_dev      fp32 [nq, m_max]         out[q][c] = sum_{i < q_len[q]} max_{j in doc} <q_i, d_j>, fp32 accumulation; the row
+ *                                         maxima are added in a fixed order
+ * A row < 0 or >= n_rows is never dereferenced and scores -inf; otherwise a document with no tokens, and q_len == 0, score 0.
+ * A pair's score is bitwise independent of nq, m_max, lq_max and of what else shares the launch.
+ * Limits (CRS_EINVAL otherwise, before any launch): 1 <= lq_max <= CRS_MAXSIM_MAX_QUERY; dimp in {32, 64, 96, 128}; 0 <= nq <= 65535
+ * (0: no launch); m_max >= 1.  No workspace, no atomics, no host synchronisation. */
+#define CRS_MAXSIM_MAX_QUERY 64          /* query tokens of crs_maxsim: four row blocks of 16 held in registers */
+int crs_token_project(const float* hidden_dev, const void* w16_dev, const float* bias_dev, const int64_t* dst_dev, void* out16_dev,
+                      int64_t n_tok, int hidden, int dim, void* stream);
+int crs_maxsim(const void* q16_dev, const int32_t* q_len_dev, int nq, int lq_max, const void* tok16_dev, const int64_t* offsets_dev,
+               int64_t n_rows, int64_t n_tokens, const int64_t* rows_dev, int m_max, int dimp, float* out_dev, void* stream);
+
 /* ---- one-collective exchange (ONE all-gather per query batch) ------------------
  * A rank's per-shard result travels as one contiguous "wire block":
  *     [ ids int64 [nq, k] | scores fp32 [nq, k] | pad to 8 bytes ]        crs_wire_bytes(nq, k) bytes
