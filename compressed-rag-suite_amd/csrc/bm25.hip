@@ -13,8 +13,9 @@
 // and never enters a list, whatever its score would round to.
 //
 // Two kernels and the merge:
-//   bm25_pairs_kernel  one workgroup: the <= CRS_BM25_MAX_PAIRS (query, token) pairs of the launch, sorted by (token, query) with
-//                      a bitonic network in LDS, written to the workspace as three parallel arrays (token, weight, query).
+//   csr_pairs_kernel   (csr_scan.h, shared with sparse_scan.hip) one workgroup: the <= CRS_BM25_MAX_PAIRS (query, token) pairs of the
+//                      launch, sorted by (token, query) with a bitonic network in LDS, written to the workspace as three parallel
+//                      arrays (token, weight, query).
 //   bm25_scan_kernel   one wave per workgroup; a workgroup owns a contiguous range of 64-row tiles.  The pair table sits in LDS.
 //                      Lane d owns row d of the tile: the tile's token segment is contiguous in the CSR and is staged into LDS in
 //                      fixed chunks with coalesced loads (a row longer than a chunk simply spans several rounds of the loop); the
@@ -32,6 +33,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "csr_scan.h"
 #include "scan.h"
 
 #pragma clang fp contract(off)
@@ -39,80 +41,8 @@
 namespace crs {
 namespace {
 
-constexpr int kLanes = 64;                     // rows per tile: one lane per row
-constexpr int kMaxPairs = CRS_BM25_MAX_PAIRS;  // (query, token) pairs per launch
-constexpr int kChunk = 2048;                   // tokens staged per round
-constexpr int kMinTiles = 4;                   // tiles per workgroup at least (short collections: fewer lists to merge)
-constexpr int kMaxWg = 2048;                   // workgroups at most
-constexpr int kSortThreads = 256;
-constexpr unsigned long long kNoPair = ~0ull;
-constexpr float kNegInf = -__builtin_huge_valf();
-static_assert((kMaxPairs & (kMaxPairs - 1)) == 0 && kMaxPairs <= 4096, "pair index fits the 12 low bits of a sort key");
-static_assert(CRS_MAX_K <= kLanes, "one lane per list slot");
-
-__device__ __forceinline__ int64_t clamp_i64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// ---- the pair table: (token, query, weight) sorted by token, then query ----------------------------------------------------------
-// Pair p IS entry p of q_tok / q_w (n_pairs = their length <= kMaxPairs); its query is the one whose clamped offsets hold p.  An
-// entry no query holds sorts last as (0xffffffff, query 0, weight 0).
-__global__ __launch_bounds__(kSortThreads) void bm25_pairs_kernel(const int64_t* __restrict__ q_off, const int* __restrict__ q_tok,
-                                                                 const float* __restrict__ q_w, int nq, int n_pairs,
-                                                                 unsigned* __restrict__ pt_tok, float* __restrict__ pt_w,
-                                                                 int* __restrict__ pt_q) {
-  __shared__ unsigned long long key[kMaxPairs];
-  __shared__ int off[kLanes + 1];
-  const int tid = threadIdx.x;
-  for (int q = tid; q <= nq; q += kSortThreads) off[q] = (int)clamp_i64(q_off[q], 0, n_pairs);
-  __syncthreads();
-  int n2 = 1;
-  while (n2 < n_pairs) n2 <<= 1;
-  for (int p = tid; p < n2; p += kSortThreads) {
-    unsigned long long kk = kNoPair;
-    if (p < n_pairs) {
-      int lo = 0, hi = nq;                     // the last q in [0, nq) with off[q] <= p
-      while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (off[mid] <= p) lo = mid; else hi = mid;
-      }
-      if (off[lo] <= p && p < off[lo + 1]) kk = ((unsigned long long)(unsigned)q_tok[p] << 12) | (unsigned)p;
-    }
-    key[p] = kk;
-  }
-  __syncthreads();
-  for (int size = 2; size <= n2; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int i = tid; i < (n2 >> 1); i += kSortThreads) {
-        const int a = ((i & ~(stride - 1)) << 1) | (i & (stride - 1)), b = a | stride;
-        const bool up = (a & size) == 0;
-        const unsigned long long x = key[a], y = key[b];
-        if ((x > y) == up) { key[a] = y; key[b] = x; }
-      }
-      __syncthreads();
-    }
-  }
-  for (int i = tid; i < n_pairs; i += kSortThreads) {
-    const unsigned long long kk = key[i];
-    if (kk == kNoPair) {
-      pt_tok[i] = 0xffffffffu; pt_w[i] = 0.0f; pt_q[i] = 0;
-    } else {
-      const int p = (int)(kk & 4095ull);
-      int lo = 0, hi = nq;
-      while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (off[mid] <= p) lo = mid; else hi = mid;
-      }
-      pt_tok[i] = (unsigned)(kk >> 12); pt_w[i] = q_w[p]; pt_q[i] = lo;
-    }
-  }
-}
-
 // ---- the scan --------------------------------------------------------------------------------------------------------------------
-// dynamic LDS: [pair tokens u32 [n_pairs] | pair weights f32 [n_pairs] | acc f32 [nq, 64] | list scores f32 [nq, k] |
-//               list rows i32 [nq, k] | staged tokens u32 [kChunk] | pair queries u8 [n_pairs]]
-__host__ __device__ inline size_t bm25_lds_bytes(int nq, int k, int n_pairs) {
-  return (size_t)n_pairs * 8 + (size_t)nq * kLanes * 4 + (size_t)nq * k * 8 + (size_t)kChunk * 4 + (((size_t)n_pairs + 3) & ~(size_t)3);
-}
-
+// dynamic LDS: csr_scan.h's csr_scan_lds_bytes
 __global__ __launch_bounds__(kLanes) void bm25_scan_kernel(const int64_t* __restrict__ doc_off, const int* __restrict__ doc_tok,
                                                           const int* __restrict__ doc_tf, const int* __restrict__ doc_len, int n_rows,
                                                           int64_t n_doc_tok, const unsigned* __restrict__ pt_tok,
@@ -184,34 +114,7 @@ __global__ __launch_bounds__(kLanes) void bm25_scan_kernel(const int64_t* __rest
         }
       }
     }
-    // ---- selection: the rows of this tile that enter a query's list, in row order ----
-    for (int q = 0; q < nq; ++q) {
-      const bool hit = (mine >> q) & 1ull;
-      if (!__ballot(hit)) continue;                    // (uniform)
-      const float s = acc[q * kLanes + lane];
-      float my_s = lane < k ? ls_s[q * k + lane] : kNegInf;     // slot `lane` of the query's list
-      int my_r = lane < k ? ls_r[q * k + lane] : -1;
-      float kth_s = __shfl(my_s, k - 1);
-      int kth_r = __shfl(my_r, k - 1);
-      unsigned long long todo = __ballot(hit && (kth_r < 0 || s > kth_s));
-      bool changed = false;
-      while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1ull;
-        const float cs = __shfl(s, src);
-        if (!(kth_r < 0 || cs > kth_s)) continue;
-        const int pos = __popcll(__ballot(lane < k && my_r >= 0 && my_s >= cs));   // entries that stay ahead: an equal score is an earlier row
-        const float up_s = __shfl_up(my_s, 1);
-        const int up_r = __shfl_up(my_r, 1);
-        if (pos >= k) continue;
-        if (lane == pos) { my_s = cs; my_r = tile * kLanes + src; }
-        else if (lane > pos && lane < k) { my_s = up_s; my_r = up_r; }
-        kth_s = __shfl(my_s, k - 1);
-        kth_r = __shfl(my_r, k - 1);
-        changed = true;
-      }
-      if (changed && lane < k) { ls_s[q * k + lane] = my_s; ls_r[q * k + lane] = my_r; }
-    }
+    csr_select_tile(acc, mine, nq, k, tile, lane, ls_s, ls_r);
   }
   __syncthreads();
   const size_t out0 = (size_t)blockIdx.x * nq * k;
@@ -220,50 +123,26 @@ __global__ __launch_bounds__(kLanes) void bm25_scan_kernel(const int64_t* __rest
 
 }  // namespace
 
-// geometry of a launch: workgroups and tiles per workgroup for n_rows rows
-static void bm25_plan(int64_t n_rows, int* n_wg, int* tiles_per_wg) {
-  const int64_t n_tiles = (n_rows + kLanes - 1) / kLanes;
-  int64_t per = (n_tiles + kMaxWg - 1) / kMaxWg;
-  if (per < kMinTiles) per = kMinTiles;
-  *tiles_per_wg = (int)per;
-  *n_wg = (int)((n_tiles + per - 1) / per);
-  if (*n_wg < 1) *n_wg = 1;
-}
-
-static size_t bm25_align(size_t x) { return (x + 255) / 256 * 256; }
-
-// workspace: [pair tokens | pair weights | pair queries (kMaxPairs each) | partial scores f32 [n_wg, nq, k] | partial rows i64 [n_wg, nq, k]]
-size_t bm25_workspace_bytes(int nq, int k, int64_t n_rows) {
-  int n_wg, per;
-  bm25_plan(n_rows, &n_wg, &per);
-  const size_t cells = (size_t)n_wg * nq * k;
-  return 3 * bm25_align((size_t)kMaxPairs * 4) + bm25_align(cells * 4) + bm25_align(cells * 8);
-}
+size_t bm25_workspace_bytes(int nq, int k, int64_t n_rows) { return csr_scan_workspace_bytes(nq, k, n_rows); }
 
 int bm25_topk_launch(const int64_t* doc_off, const int* doc_tok, const int* doc_tf, const int* doc_len, int64_t n_rows, int64_t n_doc_tok,
                      const int64_t* q_off, const int* q_tok, const float* q_w, int nq, int n_pairs, float c0, float c1, float k1p1, int k,
                      void* workspace, float* out_s, int64_t* out_i, hipStream_t stream) {
   int n_wg, per;
-  bm25_plan(n_rows, &n_wg, &per);
-  const size_t cells = (size_t)n_wg * nq * k;
-  char* w = reinterpret_cast<char*>(workspace);
-  unsigned* pt_tok = reinterpret_cast<unsigned*>(w);
-  float* pt_w = reinterpret_cast<float*>(w + bm25_align((size_t)kMaxPairs * 4));
-  int* pt_q = reinterpret_cast<int*>(w + 2 * bm25_align((size_t)kMaxPairs * 4));
-  float* part_s = reinterpret_cast<float*>(w + 3 * bm25_align((size_t)kMaxPairs * 4));
-  int64_t* part_i = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(part_s) + bm25_align(cells * 4));
+  csr_scan_plan(n_rows, &n_wg, &per);
+  const CsrScanWs ws = csr_scan_ws(workspace, n_wg, nq, k);
   if (n_pairs > 0)
-    hipLaunchKernelGGL(bm25_pairs_kernel, dim3(1), dim3(kSortThreads), 0, stream, q_off, q_tok, q_w, nq, n_pairs, pt_tok, pt_w, pt_q);
-  const size_t lds = bm25_lds_bytes(nq, k, n_pairs);
+    hipLaunchKernelGGL(csr_pairs_kernel, dim3(1), dim3(kSortThreads), 0, stream, q_off, q_tok, q_w, nq, n_pairs, ws.pt_tok, ws.pt_w, ws.pt_q);
+  const size_t lds = csr_scan_lds_bytes(nq, k, n_pairs);
   if (lds > 48 * 1024) {     // beyond the default dynamic-LDS limit (at most ~100 KiB of the CU's 160: 4096 pairs, 64 queries, k = 64)
     const hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void*>(&bm25_scan_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (ae != hipSuccess) return (int)ae;
   }
   hipLaunchKernelGGL(bm25_scan_kernel, dim3((unsigned)n_wg), dim3(kLanes), lds, stream, doc_off, doc_tok, doc_tf, doc_len, (int)n_rows,
-                     n_doc_tok, pt_tok, pt_w, pt_q, n_pairs, nq, c0, c1, k1p1, k, per, part_s, part_i);
+                     n_doc_tok, ws.pt_tok, ws.pt_w, ws.pt_q, n_pairs, nq, c0, c1, k1p1, k, per, ws.part_s, ws.part_i);
   const int e = (int)hipGetLastError();
   if (e) return e;
-  return merge_launch_i64(part_s, part_i, n_wg, nq, k, k, out_s, out_i, stream);
+  return merge_launch_i64(ws.part_s, ws.part_i, n_wg, nq, k, k, out_s, out_i, stream);
 }
 
 }  // namespace crs

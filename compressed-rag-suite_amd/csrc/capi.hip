@@ -366,6 +366,43 @@ int crs_bm25_topk(const int64_t* doc_offsets_dev, const int32_t* doc_tokens_dev,
   return e ? hip_fail((hipError_t)e, "bm25_topk launch") : CRS_OK;
 }
 
+int crs_sparse_compact(const float* weights_dev, int batch, int vocab, int vp, int cap, const int32_t* skip_ids_dev, int n_skip,
+                       int32_t* ids_dev, float* out_weights_dev, int32_t* counts_dev, void* stream) {
+  if (batch < 1) return fail(CRS_EINVAL, "bad batch (batch >= 1)");
+  if (vocab < 1 || vp < vocab) return fail(CRS_EINVAL, "bad vocab / vp (1 <= vocab <= vp)");
+  if (cap < 1 || cap > CRS_SPARSE_MAX_TERMS) return fail(CRS_EINVAL, "bad cap (1 <= cap <= CRS_SPARSE_MAX_TERMS)");
+  if (n_skip < 0 || n_skip > CRS_SPARSE_MAX_SKIP) return fail(CRS_EINVAL, "bad n_skip (0 <= n_skip <= CRS_SPARSE_MAX_SKIP)");
+  if (!weights_dev || !ids_dev || !out_weights_dev || !counts_dev || (n_skip > 0 && !skip_ids_dev)) return fail(CRS_EINVAL, "null pointer");
+  const int e = crs::sparse_compact_launch(weights_dev, batch, vocab, vp, cap, skip_ids_dev, n_skip, ids_dev, out_weights_dev, counts_dev,
+                                           (hipStream_t)stream);
+  return e ? hip_fail((hipError_t)e, "sparse_compact launch") : CRS_OK;
+}
+
+int crs_sparse_workspace_bytes(int nq, int k, int64_t n_rows, size_t* bytes) {
+  if (!bytes) return fail(CRS_EINVAL, "null pointer");
+  if (const char* bad = bm25_sizes_bad(nq, k, n_rows)) return fail(CRS_EINVAL, "%s", bad);
+  *bytes = crs::sparse_workspace_bytes(nq, k, n_rows);
+  return CRS_OK;
+}
+
+int crs_sparse_topk(const int64_t* doc_offsets_dev, const int32_t* doc_tokens_dev, const float* doc_weights_dev, int64_t n_rows,
+                    int64_t n_doc_tokens, const int64_t* q_offsets_dev, const int32_t* q_tokens_dev, const float* q_weights_dev, int nq,
+                    int64_t n_q_tokens, int k, void* workspace_dev, size_t workspace_bytes, float* out_scores_dev,
+                    int64_t* out_rows_dev, void* stream) {
+  if (const char* bad = bm25_sizes_bad(nq, k, n_rows)) return fail(CRS_EINVAL, "%s", bad);
+  if (n_doc_tokens < 0) return fail(CRS_EINVAL, "bad n_doc_tokens");
+  if (n_q_tokens < 0 || n_q_tokens > CRS_BM25_MAX_PAIRS) return fail(CRS_EINVAL, "bad n_q_tokens (0 <= n_q_tokens <= CRS_BM25_MAX_PAIRS)");
+  if (!doc_offsets_dev || !q_offsets_dev || !out_scores_dev || !out_rows_dev || (n_doc_tokens > 0 && (!doc_tokens_dev || !doc_weights_dev)) ||
+      (n_q_tokens > 0 && (!q_tokens_dev || !q_weights_dev)))
+    return fail(CRS_EINVAL, "null pointer");
+  if (!workspace_dev || ((uintptr_t)workspace_dev & 255)) return fail(CRS_EINVAL, "workspace must be a 256-byte aligned device pointer");
+  if (workspace_bytes < crs::sparse_workspace_bytes(nq, k, n_rows)) return fail(CRS_ENOSPC, "workspace smaller than crs_sparse_workspace_bytes");
+  const int e = crs::sparse_topk_launch(doc_offsets_dev, doc_tokens_dev, doc_weights_dev, n_rows, n_doc_tokens, q_offsets_dev, q_tokens_dev,
+                                        q_weights_dev, nq, (int)n_q_tokens, k, workspace_dev, out_scores_dev, out_rows_dev,
+                                        (hipStream_t)stream);
+  return e ? hip_fail((hipError_t)e, "sparse_topk launch") : CRS_OK;
+}
+
 int crs_fuse_rrf(const int64_t* dense_rows_dev, int m_dense, const int64_t* lex_rows_dev, int m_lex, int nq, double c, double w_dense,
                  double w_lex, int k_out, int64_t* rows_dev, double* fused_dev, int32_t* dense_pos_dev, int32_t* lex_pos_dev,
                  int32_t* count_dev, void* stream) {

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/crs_encoder.h"
 #include "enc_plan.h"
 
 namespace crs {
@@ -66,5 +67,12 @@ int pool_launch(const float* x32, const int* lens, int batch, int seq, int hidde
 int pair_head_launch(const float* hidden32, int batch, int seq, int hidden, const float* w_pool, const float* b_pool,
                      const float* w_cls, const float* b_cls, int activation, float* scores, float* pooled_out,
                      hipStream_t stream);
+
+// mlm_pool.hip
+// out[b, v] = log1p(max(0, max_{i < lens[b]} (t_i . Wd_v + bias_v))), t = LayerNorm(GELU(W_t h + b_t)) left as fp16 in t16
+// [p.tokens_padded, hidden] (the workspace); four launches walking the plan (mlm_plan.h).  -1: a hidden the transform has no
+// instantiation for
+int mlm_sparse_pool_launch(const crs_mlm_plan& p, const float* hidden32, const int* lens, int batch, int seq, const crs_mlm_head& head,
+                           _Float16* t16, float* out, int vp, hipStream_t stream);
 
 }  // namespace crs

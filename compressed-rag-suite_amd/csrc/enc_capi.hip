@@ -18,6 +18,7 @@
 #include <stdio.h>
 
 #include "enc.h"
+#include "mlm_plan.h"
 
 namespace crs {
 int set_error(int code, const char* msg);  // capi.hip
@@ -221,6 +222,43 @@ int crs_encoder_forward_queries(const crs_encoder_desc* d, const crs_encoder_wei
                                 void* stream) {
   return crs_encoder_forward_queries_ex(d, w, ids_dev, lens_dev, batch, seq, workspace_dev, workspace_bytes, out_dev,
                                         q16_out_dev, slab_type, stream, nullptr);
+}
+
+// ---- the masked-language-model head with the max-pool epilogue (mlm_pool.hip; the geometry is mlm_plan.cpp's) ----
+int crs_mlm_pool_plan(int batch, int seq, int hidden, int vocab, crs_mlm_plan* plan) {
+  if (!plan) return crs::set_error(CRS_EINVAL, "null pointer");
+  const char* why = "";
+  if (crs::make_mlm_plan(batch, seq, hidden, vocab, plan, &why)) return crs::set_error(CRS_EINVAL, why);
+  return CRS_OK;
+}
+
+int crs_mlm_workspace_bytes(int batch, int seq, int hidden, int vocab, size_t* bytes) {
+  if (!bytes) return crs::set_error(CRS_EINVAL, "null pointer");
+  crs_mlm_plan p;
+  const int rc = crs_mlm_pool_plan(batch, seq, hidden, vocab, &p);
+  if (rc) return rc;
+  *bytes = p.workspace_bytes;
+  return CRS_OK;
+}
+
+int crs_mlm_sparse_pool(const float* hidden_dev, const int32_t* lens_dev, int batch, int seq, const crs_mlm_head* head,
+                        void* workspace_dev, size_t workspace_bytes, float* out_dev, int vp, void* stream) {
+  if (!head) return crs::set_error(CRS_EINVAL, "null head");
+  if (!hidden_dev || !lens_dev || !out_dev || !head->transform_w16 || !head->transform_bias || !head->ln_gamma || !head->ln_beta ||
+      !head->decoder_w16 || !head->decoder_bias)
+    return crs::set_error(CRS_EINVAL, "null pointer");
+  crs_mlm_plan p;
+  const int rc = crs_mlm_pool_plan(batch, seq, head->hidden, head->vocab, &p);
+  if (rc) return rc;
+  if (seq > head->max_pos) return crs::set_error(CRS_EINVAL, "bad seq (seq <= max_pos)");
+  if (vp < head->vocab) return crs::set_error(CRS_EINVAL, "bad vp (vp >= vocab)");
+  if (((uintptr_t)hidden_dev | (uintptr_t)head->transform_w16 | (uintptr_t)head->decoder_w16) & 15)
+    return crs::set_error(CRS_EINVAL, "hidden_dev / transform_w16 / decoder_w16 must be 16-byte aligned");
+  if (!workspace_dev || ((uintptr_t)workspace_dev & 255)) return crs::set_error(CRS_EINVAL, "workspace must be a 256-byte aligned device pointer");
+  if (workspace_bytes < p.workspace_bytes) return crs::set_error(CRS_ENOSPC, "workspace smaller than crs_mlm_workspace_bytes");
+  CRS_TRY(crs::mlm_sparse_pool_launch(p, hidden_dev, lens_dev, batch, seq, *head, reinterpret_cast<_Float16*>(workspace_dev), out_dev, vp,
+                                      (hipStream_t)stream), "mlm_sparse_pool");
+  return CRS_OK;
 }
 
 }  // extern "C"

@@ -102,6 +102,15 @@ int bm25_topk_launch(const int64_t* doc_off, const int* doc_tok, const int* doc_
                      const int64_t* q_off, const int* q_tok, const float* q_w, int nq, int n_pairs, float c0, float c1, float k1p1, int k,
                      void* workspace, float* out_s, int64_t* out_i, hipStream_t stream);
 
+// sparse_scan.hip: exact impact (dot product) top-k of <= 64 queries over a weighted token CSR: bm25.hip's scan with another term
+size_t sparse_workspace_bytes(int nq, int k, int64_t n_rows);
+int sparse_topk_launch(const int64_t* doc_off, const int* doc_tok, const float* doc_w, int64_t n_rows, int64_t n_doc_tok,
+                       const int64_t* q_off, const int* q_tok, const float* q_w, int nq, int n_pairs, int k, void* workspace, float* out_s,
+                       int64_t* out_i, hipStream_t stream);
+// sparse_compact.hip: dense non-negative weight rows -> the <= cap largest (id, weight) per row in id order, one workgroup per row
+int sparse_compact_launch(const float* weights, int batch, int V, int Vp, int cap, const int* skip_ids, int n_skip, int* out_ids,
+                          float* out_w, int* counts, hipStream_t stream);
+
 // fuse.hip: reciprocal rank fusion of a dense and a lexical list of <= CRS_MAX_K rows each, one wave per query
 int fuse_rrf_launch(const int64_t* dense, int m_dense, const int64_t* lex, int m_lex, int nq, double c, double w_dense, double w_lex,
                     int k_out, int64_t* out_rows, double* out_fused, int* out_dpos, int* out_lpos, int* out_count, hipStream_t stream);

@@ -24,6 +24,7 @@
 //   crs::wordpiece_encode          BERT basic tokenisation + WordPiece of UTF-8 texts on the device (the tokenizer inside SentenceTransformer.encode)
 //   crs::bm25_topk / crs::fuse_rrf   hybrid retrieval: exact BM25 scan over the token CSR, reciprocal rank fusion (new vs the reference)
 //   crs::pairs_above / crs::pairs_verify   near-duplicate detection: thresholded self-join of the slab, fp32 check (new vs the reference)
+//   crs::mlm_sparse_pool / crs::sparse_compact / crs::sparse_topk   learned sparse retrieval (SPLADE): MLM head with max-pool epilogue, compaction, impact scan (new vs the reference)
 //   crs::token_project / crs::maxsim   late interaction (ColBERT): per-token projection and MaxSim scoring of candidate lists (new vs the reference)
 //   crs::rerank_lexical    replaces the scoring, threshold and _rerank loops of retrieve_batch  (reference rag/retrieval.py:75-77, 196-217)
 // Tensors are torch-owned; every op launches on the CURRENT HIP stream of the tensors' device, so the ops
@@ -766,6 +767,106 @@ void bm25_topk(const Tensor& doc_offsets, const Tensor& doc_tokens, const Tensor
                    cur_stream(doc_offsets)), "crs::bm25_topk");
 }
 
+// ---- learned sparse retrieval (csrc/mlm_pool.hip, csrc/sparse_compact.hip, csrc/sparse_scan.hip) ------------------------------------
+// hidden fp32 [batch, seq, H] (final hidden states; padding positions are never read); lens int32 [batch]; transform_w16 fp16 [H, H],
+// transform_bias / ln_gamma / ln_beta fp32 [H]; decoder_w16 fp16 [V, H]; decoder_bias fp32 [V]; workspace uint8
+// (crs_mlm_workspace_bytes; afterwards it begins with t as fp16 [tokens_padded, H]); out fp32 [batch, Vp >= V], columns [0, V) written
+void mlm_sparse_pool(const Tensor& hidden, const Tensor& lens, const Tensor& transform_w16, const Tensor& transform_bias,
+                     const Tensor& ln_gamma, const Tensor& ln_beta, double ln_eps, const Tensor& decoder_w16, const Tensor& decoder_bias,
+                     int64_t max_pos, Tensor workspace, Tensor out) {
+  want(hidden, at::kFloat, "hidden");
+  want(lens, at::kInt, "lens");
+  want(transform_w16, at::kHalf, "transform_w16");
+  want(transform_bias, at::kFloat, "transform_bias");
+  want(ln_gamma, at::kFloat, "ln_gamma");
+  want(ln_beta, at::kFloat, "ln_beta");
+  want(decoder_w16, at::kHalf, "decoder_w16");
+  want(decoder_bias, at::kFloat, "decoder_bias");
+  want(workspace, at::kByte, "workspace");
+  want(out, at::kFloat, "out");
+  same_device(hidden, {&lens, &transform_w16, &transform_bias, &ln_gamma, &ln_beta, &decoder_w16, &decoder_bias, &workspace, &out},
+              "crs::mlm_sparse_pool");
+  TORCH_CHECK(hidden.dim() == 3 && hidden.size(0) >= 1 && hidden.size(1) >= 1, "hidden must be fp32 [batch >= 1, seq >= 1, H]");
+  const int64_t batch = hidden.size(0), seq = hidden.size(1), H = hidden.size(2);
+  TORCH_CHECK(batch * seq <= (1 << 22), "too many tokens (batch * seq <= 2^22)");
+  TORCH_CHECK(lens.dim() == 1 && lens.size(0) == batch, "lens must be int32 [batch]");
+  TORCH_CHECK(transform_w16.dim() == 2 && transform_w16.size(0) == H && transform_w16.size(1) == H, "transform_w16 must be fp16 [H, H]");
+  TORCH_CHECK(transform_bias.numel() == H && ln_gamma.numel() == H && ln_beta.numel() == H, "transform_bias / ln_gamma / ln_beta must be fp32 [H]");
+  TORCH_CHECK(decoder_w16.dim() == 2 && decoder_w16.size(1) == H && decoder_w16.size(0) >= 1 && decoder_w16.size(0) <= (1 << 20),
+              "decoder_w16 must be fp16 [V, H]");
+  const int64_t V = decoder_w16.size(0);
+  TORCH_CHECK(decoder_bias.numel() == V, "decoder_bias must be fp32 [V]");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == batch && out.size(1) >= V && out.size(1) <= 0x7fffffff, "out must be fp32 [batch, Vp >= V]");
+  crs_mlm_head head;
+  head.hidden = (int32_t)H;
+  head.vocab = (int32_t)V;
+  head.max_pos = (int32_t)max_pos;
+  head.ln_eps = (float)ln_eps;
+  head.transform_w16 = transform_w16.data_ptr();
+  head.transform_bias = transform_bias.data_ptr<float>();
+  head.ln_gamma = ln_gamma.data_ptr<float>();
+  head.ln_beta = ln_beta.data_ptr<float>();
+  head.decoder_w16 = decoder_w16.data_ptr();
+  head.decoder_bias = decoder_bias.data_ptr<float>();
+  c10::hip::HIPGuardMasqueradingAsCUDA g(hidden.device());
+  ok(crs_mlm_sparse_pool(hidden.data_ptr<float>(), lens.data_ptr<int32_t>(), (int)batch, (int)seq, &head, workspace.data_ptr(),
+                         (size_t)workspace.numel(), out.data_ptr<float>(), (int)out.size(1), cur_stream(hidden)), "crs::mlm_sparse_pool");
+}
+
+// weights fp32 [batch, Vp >= vocab]; skip_ids int32 [<= CRS_SPARSE_MAX_SKIP] (optional); ids int32 / out_weights fp32 [batch, cap];
+// counts int32 [batch]
+void sparse_compact(const Tensor& weights, int64_t vocab, c10::optional<Tensor> skip_ids, Tensor ids, Tensor out_weights, Tensor counts) {
+  want(weights, at::kFloat, "weights");
+  want(ids, at::kInt, "ids");
+  want(out_weights, at::kFloat, "out_weights");
+  want(counts, at::kInt, "counts");
+  if (has(skip_ids)) want(*skip_ids, at::kInt, "skip_ids");
+  same_device(weights, {opt_t(skip_ids), &ids, &out_weights, &counts}, "crs::sparse_compact");
+  TORCH_CHECK(weights.dim() == 2 && weights.size(0) >= 1 && weights.size(1) <= 0x7fffffff && weights.size(0) <= 0x7fffffff,
+              "weights must be fp32 [batch >= 1, Vp]");
+  const int64_t batch = weights.size(0);
+  TORCH_CHECK(vocab >= 1 && vocab <= weights.size(1), "vocab must be in 1..Vp");
+  TORCH_CHECK(ids.dim() == 2 && ids.size(0) == batch && ids.size(1) >= 1 && ids.size(1) <= CRS_SPARSE_MAX_TERMS && out_weights.sizes() == ids.sizes(),
+              "ids / out_weights must be [batch, 1 <= cap <= CRS_SPARSE_MAX_TERMS]");
+  TORCH_CHECK(counts.dim() == 1 && counts.size(0) == batch, "counts must be int32 [batch]");
+  const int64_t n_skip = has(skip_ids) ? skip_ids->numel() : 0;
+  TORCH_CHECK(n_skip <= CRS_SPARSE_MAX_SKIP, "at most CRS_SPARSE_MAX_SKIP skip ids");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(weights.device());
+  ok(crs_sparse_compact(weights.data_ptr<float>(), (int)batch, (int)vocab, (int)weights.size(1), (int)ids.size(1),
+                        n_skip ? skip_ids->data_ptr<int32_t>() : nullptr, (int)n_skip, ids.data_ptr<int32_t>(), out_weights.data_ptr<float>(),
+                        counts.data_ptr<int32_t>(), cur_stream(weights)), "crs::sparse_compact");
+}
+
+// doc_offsets int64 [>= n_rows + 1], doc_tokens int32 / doc_weights fp32 (same length); q_offsets int64 [nq + 1], q_tokens int32 /
+// q_weights fp32 (same length); workspace uint8 (crs_sparse_workspace_bytes); out_scores fp32 / out_rows int64 [nq, k]
+void sparse_topk(const Tensor& doc_offsets, const Tensor& doc_tokens, const Tensor& doc_weights, int64_t n_rows, const Tensor& q_offsets,
+                 const Tensor& q_tokens, const Tensor& q_weights, int64_t k, Tensor workspace, Tensor out_scores, Tensor out_rows) {
+  want(doc_offsets, at::kLong, "doc_offsets");
+  want(doc_tokens, at::kInt, "doc_tokens");
+  want(doc_weights, at::kFloat, "doc_weights");
+  want(q_offsets, at::kLong, "q_offsets");
+  want(q_tokens, at::kInt, "q_tokens");
+  want(q_weights, at::kFloat, "q_weights");
+  want(workspace, at::kByte, "workspace");
+  want(out_scores, at::kFloat, "out_scores");
+  want(out_rows, at::kLong, "out_rows");
+  same_device(doc_offsets, {&doc_tokens, &doc_weights, &q_offsets, &q_tokens, &q_weights, &workspace, &out_scores, &out_rows}, "crs::sparse_topk");
+  TORCH_CHECK(n_rows >= 0 && doc_offsets.dim() == 1 && doc_offsets.numel() >= n_rows + 1, "doc_offsets must be int64 [>= n_rows + 1]");
+  TORCH_CHECK(doc_tokens.dim() == 1 && doc_weights.dim() == 1 && doc_weights.numel() == doc_tokens.numel(),
+              "doc_tokens / doc_weights must be of one length");
+  TORCH_CHECK(q_offsets.dim() == 1 && q_offsets.numel() >= 2, "q_offsets must be int64 [nq + 1]");
+  const int64_t nq = q_offsets.numel() - 1;
+  TORCH_CHECK(q_tokens.dim() == 1 && q_weights.dim() == 1 && q_weights.numel() == q_tokens.numel(), "q_tokens / q_weights must be of one length");
+  TORCH_CHECK(nq <= 64 && k >= 1 && k <= CRS_MAX_K, "at most 64 queries per launch, 1 <= k <= 64");
+  TORCH_CHECK(out_scores.numel() == nq * k && out_rows.numel() == nq * k, "outputs must hold [nq, k]");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(doc_offsets.device());
+  ok(crs_sparse_topk(doc_offsets.data_ptr<int64_t>(), doc_tokens.numel() ? doc_tokens.data_ptr<int32_t>() : nullptr,
+                     doc_weights.numel() ? doc_weights.data_ptr<float>() : nullptr, n_rows, doc_tokens.numel(), q_offsets.data_ptr<int64_t>(),
+                     q_tokens.numel() ? q_tokens.data_ptr<int32_t>() : nullptr, q_weights.numel() ? q_weights.data_ptr<float>() : nullptr,
+                     (int)nq, q_tokens.numel(), (int)k, workspace.data_ptr(), (size_t)workspace.numel(), out_scores.data_ptr<float>(),
+                     out_rows.data_ptr<int64_t>(), cur_stream(doc_offsets)), "crs::sparse_topk");
+}
+
 // dense_rows int64 [nq, m_dense], lex_rows int64 [nq, m_lex]; rows int64 / fused fp64 / dense_pos, lex_pos int32 [nq, k_out]; count int32 [nq]
 void fuse_rrf(const Tensor& dense_rows, const Tensor& lex_rows, double c, double w_dense, double w_lex, Tensor rows, Tensor fused,
               Tensor dense_pos, Tensor lex_pos, Tensor count) {
@@ -1034,6 +1135,11 @@ TORCH_LIBRARY(crs, m) {
         "Tensor q_weights, float c0, float c1, float k1p1, int k, Tensor(a!) workspace, Tensor(b!) out_scores, Tensor(c!) out_rows) -> ()");
   m.def("fuse_rrf(Tensor dense_rows, Tensor lex_rows, float c, float w_dense, float w_lex, Tensor(a!) rows, Tensor(b!) fused, "
         "Tensor(c!) dense_pos, Tensor(d!) lex_pos, Tensor(e!) count) -> ()");
+  m.def("mlm_sparse_pool(Tensor hidden, Tensor lens, Tensor transform_w16, Tensor transform_bias, Tensor ln_gamma, Tensor ln_beta, "
+        "float ln_eps, Tensor decoder_w16, Tensor decoder_bias, int max_pos, Tensor(a!) workspace, Tensor(b!) out) -> ()");
+  m.def("sparse_compact(Tensor weights, int vocab, Tensor? skip_ids, Tensor(a!) ids, Tensor(b!) out_weights, Tensor(c!) counts) -> ()");
+  m.def("sparse_topk(Tensor doc_offsets, Tensor doc_tokens, Tensor doc_weights, int n_rows, Tensor q_offsets, Tensor q_tokens, "
+        "Tensor q_weights, int k, Tensor(a!) workspace, Tensor(b!) out_scores, Tensor(c!) out_rows) -> ()");
   m.def("wordpiece_encode(Tensor text, Tensor offsets, int n_bytes, Tensor table, Tensor rep_pool, Tensor slots, Tensor vocab_pool, "
         "int max_probe, int lmax, int mode, int unk_id, int cls_id, int sep_id, int pad_id, int hash_lo, int hash_span, Tensor(a!) ids, "
         "Tensor(b!) lens, Tensor(c!) flags) -> ()");
@@ -1083,6 +1189,9 @@ TORCH_LIBRARY_IMPL(crs, CUDA, m) {   // the HIP backend of torch-ROCm dispatches
   m.impl("pairs_verify_out", &pairs_verify_out);
   m.impl("bm25_topk", &bm25_topk);
   m.impl("fuse_rrf", &fuse_rrf);
+  m.impl("mlm_sparse_pool", &mlm_sparse_pool);
+  m.impl("sparse_compact", &sparse_compact);
+  m.impl("sparse_topk", &sparse_topk);
   m.impl("wordpiece_encode", &wordpiece_encode);
   m.impl("unigram_encode", &unigram_encode);
   m.impl("encoder_forward", &encoder_forward);

@@ -31,11 +31,20 @@ UNIGRAM_TILE_BYTES = 1024     # CRS_UNIGRAM_TILE_BYTES: the same for crs_unigram
 UNIGRAM_MAX_WORD = 128        # CRS_UNIGRAM_MAX_WORD: code points of the longest word it walks (U+2581 included); longer: the host's
 UNIGRAM_COLLAPSE, UNIGRAM_SINGLE_META, UNIGRAM_RUN_META, UNIGRAM_CRLF = 1, 2, 4, 8    # CRS_UNIGRAM_* option bits
 BM25_MAX_PAIRS = 4096      # CRS_BM25_MAX_PAIRS: (query, known token) pairs of one crs_bm25_topk launch
+SPARSE_MAX_TERMS = 1024    # CRS_SPARSE_MAX_TERMS: terms of one text after crs_sparse_compact (csrc/sparse_compact.hip)
+SPARSE_MAX_SKIP = 16       # CRS_SPARSE_MAX_SKIP: ids crs_sparse_compact always drops
 MAXSIM_MAX_QUERY = 64      # CRS_MAXSIM_MAX_QUERY: query tokens of crs_maxsim (csrc/maxsim.hip)
 PAIRS_TILE = 256           # CRS_PAIRS_TILE: tile edge of the near-duplicate join (csrc/join.hip)
 PAIRS_MAX_TILES = 1 << 22  # CRS_PAIRS_MAX_TILES: tile pairs of one crs_pairs_above_f16 launch
 SPACE_COSINE, SPACE_IP, SPACE_L2 = 0, 1, 2    # CRS_SPACE_*: a collection's hnsw:space
 SPACES = {"cosine": SPACE_COSINE, "ip": SPACE_IP, "l2": SPACE_L2}
+
+class MlmPlan(ctypes.Structure):
+    """crs_mlm_plan (include/crs_encoder.h): the launch geometry of crs_mlm_sparse_pool."""
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        "tile_m", "tile_n", "tile_k", "tokens", "tokens_padded", "grid_m", "grid_n", "pool_grid", "pool_threads", "pool_lds_bytes",
+        "xform_grid", "xform_threads", "xform_lds_bytes", "ew_grid_x", "ew_threads")] + [("t16_bytes", c_size_t), ("workspace_bytes", c_size_t)]
+
 
 # name -> (restype, argtypes); mirrors include/crs_hip.h one to one
 _SIGNATURES = {
@@ -81,6 +90,13 @@ _SIGNATURES = {
     "crs_bm25_workspace_bytes": (c_int, [c_int, c_int, c_int64, POINTER(c_size_t)]),
     "crs_bm25_topk": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int64,
                               c_float, c_float, c_float, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "crs_sparse_compact": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "crs_sparse_workspace_bytes": (c_int, [c_int, c_int, c_int64, POINTER(c_size_t)]),
+    "crs_sparse_topk": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p,
+                                c_size_t, c_void_p, c_void_p, c_void_p]),
+    "crs_mlm_pool_plan": (c_int, [c_int, c_int, c_int, c_int, POINTER(MlmPlan)]),
+    "crs_mlm_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
+    "crs_mlm_sparse_pool": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
     "crs_fuse_rrf": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int, c_void_p,
                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "crs_wordpiece_encode": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
@@ -573,6 +589,86 @@ def bm25_topk(doc_offsets, doc_tokens, doc_tf, doc_len, n_rows: int, q_offsets, 
     with _translate():
         ops().bm25_topk(doc_offsets, doc_tokens, doc_tf, doc_len, int(n_rows), q_offsets, q_tokens, q_weights, float(c0), float(c1),
                         float(k1p1), int(k), workspace, out_scores, out_rows)
+    return out_scores, out_rows
+
+
+def has_sparse() -> bool:
+    """Whether the loaded libcrs_torch.so carries the learned-sparse ops (crs::mlm_sparse_pool, crs::sparse_compact, crs::sparse_topk)."""
+    return all(hasattr(ops(), n) for n in ("mlm_sparse_pool", "sparse_compact", "sparse_topk"))
+
+
+def mlm_pool_plan(batch: int, seq: int, hidden: int, vocab: int) -> dict:
+    """The launch geometry of crs_mlm_sparse_pool for these sizes (crs_mlm_pool_plan: a pure host call, no device needed)."""
+    p = MlmPlan()
+    check(load().crs_mlm_pool_plan(int(batch), int(seq), int(hidden), int(vocab), byref(p)))
+    return {n: int(getattr(p, n)) for n, _ in MlmPlan._fields_}
+
+
+def mlm_workspace_bytes(batch: int, seq: int, hidden: int, vocab: int) -> int:
+    out = c_size_t(0)
+    check(load().crs_mlm_workspace_bytes(int(batch), int(seq), int(hidden), int(vocab), byref(out)))
+    return int(out.value)
+
+
+def mlm_sparse_pool(hidden, lens, transform_w16, transform_bias, ln_gamma, ln_beta, ln_eps: float, decoder_w16, decoder_bias,
+                    max_pos: int, workspace=None, out=None):
+    """The MLM head of a learned sparse encoder with the max-pool in the projection's epilogue (crs_mlm_sparse_pool,
+    csrc/mlm_pool.hip): hidden cuda fp32 [batch, seq, H] final hidden states (padding positions are never read), lens int32 [batch];
+    transform_w16 fp16 [H, H], transform_bias / ln_gamma / ln_beta fp32 [H]; decoder_w16 fp16 [V, H], decoder_bias fp32 [V] ->
+    out fp32 [batch, Vp >= V] with out[b, v] = log1p(max(0, max_{i < lens[b]} logit[b, i, v])) in columns [0, V); a given `out` keeps
+    its other columns.  `workspace` (uint8, mlm_workspace_bytes) afterwards begins with the transform's output as fp16
+    [tokens_padded, H].  No host sync."""
+    import torch
+    batch, seq, H = hidden.shape
+    V = decoder_w16.shape[0]
+    if workspace is None:
+        workspace = torch.empty(mlm_workspace_bytes(batch, seq, H, V), dtype=torch.uint8, device=hidden.device)
+    if out is None:
+        out = torch.empty((batch, V), dtype=torch.float32, device=hidden.device)
+    with _translate():
+        ops().mlm_sparse_pool(hidden, lens, transform_w16, transform_bias, ln_gamma, ln_beta, float(ln_eps), decoder_w16, decoder_bias,
+                              int(max_pos), workspace, out)
+    return out
+
+
+def sparse_compact(weights, vocab: int, cap: int, skip_ids=None, out=None):
+    """Dense non-negative weight rows to bounded sparse rows (crs_sparse_compact, csrc/sparse_compact.hip): weights cuda fp32
+    [batch, Vp >= vocab]; per row the ids with weight > 0 that are not in skip_ids (int32, at most SPARSE_MAX_SKIP), the `cap` largest
+    when there are more (ties by lower id), in ascending id order -> (ids int32 [batch, cap], weights fp32 [batch, cap], counts int32
+    [batch]); unused slots are (-1, 0).  Exact.  No host sync."""
+    import torch
+    batch, dev = weights.shape[0], weights.device
+    if out is None:
+        out = (torch.empty((batch, cap), dtype=torch.int32, device=dev), torch.empty((batch, cap), dtype=torch.float32, device=dev),
+               torch.empty(batch, dtype=torch.int32, device=dev))
+    with _translate():
+        ops().sparse_compact(weights, int(vocab), skip_ids, *out)
+    return out
+
+
+def sparse_workspace_bytes(nq: int, k: int, n_rows: int) -> int:
+    out = c_size_t(0)
+    check(load().crs_sparse_workspace_bytes(int(nq), int(k), int(n_rows), byref(out)))
+    return int(out.value)
+
+
+def sparse_topk(doc_offsets, doc_tokens, doc_weights, n_rows: int, q_offsets, q_tokens, q_weights, k: int, workspace=None,
+                out_scores=None, out_rows=None):
+    """Exact impact (sparse dot product) top-k of nq <= 64 queries over a weighted token CSR in one launch chain (crs_sparse_topk,
+    csrc/sparse_scan.hip): doc_offsets int64 [>= n_rows + 1] / doc_tokens int32 / doc_weights fp32 the rows' ascending ids and their
+    weights; q_offsets int64 [nq + 1] / q_tokens int32 / q_weights fp32 the queries' (at most BM25_MAX_PAIRS entries) -> (scores fp32
+    [nq, k], rows int64 [nq, k]), best first, ties by lower row, (-inf, -1) past the hits.  All cuda.  No host sync."""
+    import torch
+    nq, dev = q_offsets.shape[0] - 1, doc_offsets.device
+    if workspace is None:
+        workspace = torch.empty(sparse_workspace_bytes(nq, k, n_rows), dtype=torch.uint8, device=dev)
+    if out_scores is None:
+        out_scores = torch.empty((nq, k), dtype=torch.float32, device=dev)
+    if out_rows is None:
+        out_rows = torch.empty((nq, k), dtype=torch.int64, device=dev)
+    with _translate():
+        ops().sparse_topk(doc_offsets, doc_tokens, doc_weights, int(n_rows), q_offsets, q_tokens, q_weights, int(k), workspace, out_scores,
+                          out_rows)
     return out_scores, out_rows
 
 

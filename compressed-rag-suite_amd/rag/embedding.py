@@ -56,6 +56,48 @@ _ALIASES = {"minilm": "all-minilm-l6-v2", "bge": "bge-base-en-v1.5", "bge-base":
 REL_BIAS = "encoder.relative_attention_bias.weight"      # [buckets, heads], shared by all layers (MPNet)
 
 
+TOKENIZE_GROUP_BYTES = 64 << 20      # UTF-8 bytes of one crs_wordpiece_encode launch (and one lens / flags read-back)
+
+
+def tokenize_on_device(device_tok, tokenizer, dev, texts: List[str], max_seq: int, host_tokenize, pre_lower: bool = False,
+                       group_bytes: int = TOKENIZE_GROUP_BYTES, timings: Optional[dict] = None):
+    """(ids cuda int32 [n, max_seq], lens as a host int32 array [n]): the device tokeniser `device_tok` (rag._unigram.device_tokenizer
+    of `tokenizer`) on groups of texts bounded by group_bytes, one launch and one read-back of lens / flags per group; the texts
+    the kernel flags (a code point outside its table's reach) go through host_tokenize(texts) -> id lists and their rows are
+    written in.  Shared by EmbeddingModel and rag.sparse.SparseEncoder."""
+    import time
+    import torch
+    texts = [str(t).strip() for t in texts]
+    if pre_lower:
+        texts = [t.lower() for t in texts]
+    pad = getattr(tokenizer, "pad_id", 0)
+    ids_parts, lens_parts, lo = [], [], 0
+    while lo < len(texts):
+        hi, size = lo, 0
+        while hi < len(texts) and (hi == lo or size + len(texts[hi]) <= group_bytes // 4):   # <= 4 bytes a character
+            size += len(texts[hi])
+            hi += 1
+        ids, lens, flags, host = device_tok.encode(texts[lo:hi], max_seq, timings)
+        t0 = time.perf_counter()
+        back = torch.stack((lens, flags)).cpu().numpy()
+        if timings is not None:
+            timings["readback_s"] = timings.get("readback_s", 0.0) + (time.perf_counter() - t0)
+        lens_h = back[0].copy()
+        redo = sorted(set(np.nonzero(back[1])[0].tolist()) | set(host))
+        if redo:
+            rows, rlen = pad_batch(host_tokenize([texts[lo + i] for i in redo]), pad)
+            block = np.full((len(redo), max_seq), pad, dtype=np.int32)
+            block[:, : rows.shape[1]] = rows
+            ids[torch.as_tensor(redo, device=dev)] = torch.from_numpy(block).to(dev)
+            lens_h[redo] = rlen
+        ids_parts.append(ids)
+        lens_parts.append(lens_h)
+        lo = hi
+    if not ids_parts:
+        return torch.empty((0, max_seq), dtype=torch.int32, device=dev), np.zeros(0, dtype=np.int32)
+    return (ids_parts[0] if len(ids_parts) == 1 else torch.cat(ids_parts)), np.concatenate(lens_parts)
+
+
 def synthetic_weights(shape, seed: int = 0, scale: float = 0.05) -> Dict[str, np.ndarray]:
     """Seeded random checkpoint with HuggingFace BertModel tensor names (one PCG64 stream per tensor).  Shapes with
     `rel_buckets` (MPNet) also get the relative-position bias table (~N(0, 0.5): real tables are O(1)) and, having no
@@ -258,47 +300,16 @@ class EmbeddingModel:
             return self.tokenizer.encode_batch(texts, self.shape.max_seq)
         return [self.tokenizer.encode(t, self.shape.max_seq) for t in texts]
 
-    TOKENIZE_GROUP_BYTES = 64 << 20      # UTF-8 bytes of one crs_wordpiece_encode launch (and one lens / flags read-back)
+    TOKENIZE_GROUP_BYTES = TOKENIZE_GROUP_BYTES
 
     def _tokenize_device(self, texts: List[str], timings: Optional[dict] = None):
-        """(ids cuda int32 [n, max_seq], lens as a host int32 array [n]): csrc/wordpiece.hip on groups of texts bounded by
-        TOKENIZE_GROUP_BYTES, one launch and one read-back of lens / flags per group; the texts the kernel flags (a code point
-        outside its table's reach) go through self.tokenize and their rows are written in."""
-        import time
-        import torch
+        """tokenize_on_device with this model's tokenizer, device, max_seq and casing."""
         from rag._unigram import device_tokenizer
         dev = self.model.device
         if self._device_tokenizer is None:
             self._device_tokenizer = device_tokenizer(self.tokenizer, dev)      # csrc/wordpiece.hip or csrc/unigram.hip, by type
-        texts = [str(t).strip() for t in texts]
-        if self._pre_lower:
-            texts = [t.lower() for t in texts]
-        max_seq, pad = self.shape.max_seq, getattr(self.tokenizer, "pad_id", 0)
-        ids_parts, lens_parts, lo = [], [], 0
-        while lo < len(texts):
-            hi, size = lo, 0
-            while hi < len(texts) and (hi == lo or size + len(texts[hi]) <= self.TOKENIZE_GROUP_BYTES // 4):   # <= 4 bytes a character
-                size += len(texts[hi])
-                hi += 1
-            ids, lens, flags, host = self._device_tokenizer.encode(texts[lo:hi], max_seq, timings)
-            t0 = time.perf_counter()
-            back = torch.stack((lens, flags)).cpu().numpy()
-            if timings is not None:
-                timings["readback_s"] = timings.get("readback_s", 0.0) + (time.perf_counter() - t0)
-            lens_h = back[0].copy()
-            redo = sorted(set(np.nonzero(back[1])[0].tolist()) | set(host))
-            if redo:
-                rows, rlen = pad_batch(self.tokenize([texts[lo + i] for i in redo]), pad)
-                block = np.full((len(redo), max_seq), pad, dtype=np.int32)
-                block[:, : rows.shape[1]] = rows
-                ids[torch.as_tensor(redo, device=dev)] = torch.from_numpy(block).to(dev)
-                lens_h[redo] = rlen
-            ids_parts.append(ids)
-            lens_parts.append(lens_h)
-            lo = hi
-        if not ids_parts:
-            return torch.empty((0, max_seq), dtype=torch.int32, device=dev), np.zeros(0, dtype=np.int32)
-        return (ids_parts[0] if len(ids_parts) == 1 else torch.cat(ids_parts)), np.concatenate(lens_parts)
+        return tokenize_on_device(self._device_tokenizer, self.tokenizer, dev, texts, self.shape.max_seq, self.tokenize,
+                                  pre_lower=self._pre_lower, group_bytes=self.TOKENIZE_GROUP_BYTES, timings=timings)
 
     def tokenize_device(self, texts: List[str]):
         """-> (ids cuda int32 [n, max_seq]: what self.tokenize gives, right-padded with the pad id; lens cuda int32 [n]), tokenised

@@ -96,6 +96,14 @@ New, additive surface (all keys absent from the reference config.json default so
                               first use) and ONE device only (sharded / num_gpus / devices raise NotImplementedError).  Before any
                               encoding the bytes the index would take (host-side token counts x dimp x 2) are compared with
                               ``max_index_bytes`` (config key; default: half the device's total memory): more raises ValueError
+  ``attach_sparse_encoder`` / ``sparse_index`` / ``sparse_rows`` / ``search_sparse_batch``   learned sparse retrieval (rag/sparse.py, the
+                              retriever's opt-in ``sparse_model``): per row the at most ``sparse_doc_terms`` (256) largest weights of
+                              its SPLADE vector as a device CSR -- int64 offsets, int32 vocabulary ids, fp32 weights, grown by doubling
+                              -- that crs_sparse_topk scans for the queries' own sparse vectors (csrc/sparse_scan.hip; at most
+                              ``sparse_query_terms`` = 64 terms a query).  Derived data with the token index's life cycle: built on
+                              first use, extended by appends, DROPPED WHOLE by a delete, a document update or an upsert, NOT persisted,
+                              ONE device only; ``max_index_bytes`` is compared with rows x sparse_doc_terms x 8 before any encoding
+                              and with the exact size after compaction
 ``where`` / ``where_document`` filters work on every layout (the sidecars are replicated; each shard scans the
 allowed rows it owns).  ``top_k`` is unlimited as in the reference: up to 1024 a refined shard is over-fetched by
 partition (64 candidates from each of up to 64 row chunks, crs::cosine_topk_large_cert) and certified like top_k <= 64;
@@ -490,6 +498,65 @@ class _TokenIndex:
             self.offsets_dev = torch.from_numpy(self.offsets).to(self.device)
 
 
+class _SparseIndex:
+    """The learned-sparse vectors of every row as a device CSR, for crs_sparse_topk (csrc/sparse_scan.hip): ``tokens`` cuda int32 /
+    ``weights`` cuda fp32 [capacity], the first ``n_terms`` entries in use (row r's terms are [offsets[r], offsets[r + 1]), ascending
+    vocabulary ids), grown by doubling; ``offsets`` int64 [n_rows + 1] on the host, ``offsets_dev`` its device copy.  Extended in
+    place as rows arrive: an append encodes the new rows alone."""
+
+    GROUP = 4096          # documents encoded and compacted at a time: bounds the padded [GROUP, max_terms] block beside the index
+
+    def __init__(self, encoder, device, max_terms: int):
+        self.encoder, self.device, self.max_terms = encoder, device, int(max_terms)
+        self.tokens = self.weights = None
+        self.n_terms = 0
+        self.offsets = np.zeros(1, dtype=np.int64)
+        self.offsets_dev = None
+
+    @property
+    def n_rows(self) -> int:
+        return len(self.offsets) - 1
+
+    def extend(self, documents: Sequence[str], max_bytes: int) -> None:
+        """Encode documents[n_rows:] and append their terms.  ValueError BEFORE any encoding when the estimate -- the terms held
+        plus max_terms for every new row, 8 bytes each -- exceeds max_bytes; the exact size is checked again after each group's
+        compaction, before the arrays grow.  While they grow the old and the new arrays exist side by side."""
+        import torch
+        new = list(documents[self.n_rows:])
+        if not new and self.offsets_dev is not None:
+            return
+        estimate = (self.n_terms + len(new) * self.max_terms) * 8
+        if estimate > max_bytes:
+            raise ValueError(f"the sparse index could take {estimate} bytes ({self.n_terms} terms held + {len(new)} new rows x "
+                             f"{self.max_terms} terms, 8 bytes each), more than max_index_bytes = {int(max_bytes)}")
+        with VectorStore._device_guard(self.device):
+            for lo in range(0, len(new), self.GROUP):
+                ids, w, counts = self.encoder.encode_docs_device(new[lo: lo + self.GROUP], self.max_terms)
+                counts_h = counts.cpu().numpy().astype(np.int64)
+                total = self.n_terms + int(counts_h.sum())
+                if total * 8 > max_bytes:
+                    raise ValueError(f"the sparse index would take {total * 8} bytes ({total} terms), more than max_index_bytes = "
+                                     f"{int(max_bytes)}")
+                held = self.tokens.shape[0] if self.tokens is not None else 0
+                if total > held:
+                    cap = max(total, min(2 * held, int(max_bytes) // 8), 1)
+                    tokens = torch.zeros(cap, dtype=torch.int32, device=self.device)
+                    weights = torch.zeros(cap, dtype=torch.float32, device=self.device)
+                    if self.n_terms:
+                        tokens[:self.n_terms] = self.tokens[:self.n_terms]
+                        weights[:self.n_terms] = self.weights[:self.n_terms]
+                    self.tokens, self.weights = tokens, weights
+                keep = ids >= 0                                        # row-major: rows in order, ids ascending inside a row
+                self.tokens[self.n_terms:total] = ids[keep]
+                self.weights[self.n_terms:total] = w[keep]
+                self.offsets = np.concatenate([self.offsets, self.n_terms + np.cumsum(counts_h)]).astype(np.int64)
+                self.n_terms = total
+            if self.tokens is None:
+                self.tokens = torch.zeros(1, dtype=torch.int32, device=self.device)
+                self.weights = torch.zeros(1, dtype=torch.float32, device=self.device)
+            self.offsets_dev = torch.from_numpy(self.offsets).to(self.device)
+
+
 class SlabCollection:
     """What ``VectorStore.collection`` exposes (the retriever reads ``.metadata`` and the harness ``.count()``,
     reference rag/retrieval.py:48-50).  Owns the per-device shards and the host sidecars."""
@@ -574,7 +641,7 @@ class SlabCollection:
 
     def _drop_derived(self, ids_changed: bool, metadata_changed: bool = True, documents_changed: bool = True):
         """Forget what was derived from the sidecars: the inverted metadata index, (rows renumbered) the id map, and (a document
-        changed, or rows renumbered) the token CSR with its device mirror and the late-interaction token index."""
+        changed, or rows renumbered) the token CSR with its device mirror, the late-interaction token index and the sparse index."""
         if metadata_changed or ids_changed:
             self.__dict__.pop("_inv", None)
             self.__dict__.pop("_inv_rows", None)
@@ -584,6 +651,7 @@ class SlabCollection:
         if documents_changed or ids_changed:
             self.__dict__.pop("_tok", None)
             self.__dict__.pop("_li", None)       # the late-interaction token index: the next use re-encodes every document
+            self.__dict__.pop("_sp", None)       # the learned-sparse index: likewise
 
     def _token_csr(self) -> _TokenCSR:
         """The token ids of every row (see _TokenCSR): built by one pass over the documents on first use, extended by the rows
@@ -601,6 +669,16 @@ class SlabCollection:
         index = self.__dict__.get("_li")
         if index is None or index.encoder is not encoder:
             index = self.__dict__["_li"] = _TokenIndex(encoder, self.device)
+        if index.n_rows < len(self.documents) or index.offsets_dev is None:
+            index.extend(self.documents, max_bytes)
+        return index
+
+    def _sparse_index(self, encoder, max_terms: int, max_bytes: int) -> _SparseIndex:
+        """The learned-sparse vectors of every row (see _SparseIndex), for `encoder`: built on first use, extended by the rows that
+        arrived since, like _token_index; dropped by _drop_derived, and when another encoder or term cap asks."""
+        index = self.__dict__.get("_sp")
+        if index is None or index.encoder is not encoder or index.max_terms != int(max_terms):
+            index = self.__dict__["_sp"] = _SparseIndex(encoder, self.device, max_terms)
         if index.n_rows < len(self.documents) or index.offsets_dev is None:
             index.extend(self.documents, max_bytes)
         return index
@@ -750,6 +828,14 @@ class VectorStore:
         # late-interaction token index (module docstring): the encoder comes through attach_token_encoder
         self.max_index_bytes = config.get('max_index_bytes', None)     # None: half the device's total memory, read on first use
         self._token_encoder = None
+        # learned sparse retrieval (module docstring): the encoder comes through attach_sparse_encoder
+        self._sparse_encoder = None
+        self.sparse_doc_terms = int(config.get('sparse_doc_terms', 256))       # terms kept per document (<= SPARSE_MAX_TERMS)
+        self.sparse_query_terms = int(config.get('sparse_query_terms', 64))    # terms kept per query: 64 x 64 = one launch's pair cap
+        for name in ('sparse_doc_terms', 'sparse_query_terms'):
+            if not 1 <= getattr(self, name) <= nat.SPARSE_MAX_TERMS:
+                raise ValueError(f"{name} must be in 1..{nat.SPARSE_MAX_TERMS}, got {getattr(self, name)}")
+        self.last_sparse = {'queries': 0, 'query_terms': 0, 'launches': 0}     # what the last sparse_rows call ran
         self._filters = {}      # filter key -> {"n": rows when built, "rows": allowed sidecar rows, "shards": {g: compacted sub-slab}}
         self._persisted_rows = None   # rows the append-only files hold (None: nothing / legacy format on disk)
         self._docs_bytes = 0          # length of the sidecar file the header vouches for
@@ -1582,6 +1668,73 @@ class VectorStore:
             limit = torch.cuda.get_device_properties(col.device).total_memory // 2
         return col._token_index(self._token_encoder, int(limit))
 
+    def attach_sparse_encoder(self, encoder) -> None:
+        """The SparseEncoder (rag/sparse.py) whose document vectors sparse_index() holds and whose queries sparse_rows() encodes.
+        Attaching another one forgets the index built with the previous one."""
+        self._sparse_encoder = encoder
+
+    def sparse_index(self, encoder=None) -> _SparseIndex:
+        """The learned-sparse index of the collection (_SparseIndex: tokens, weights, n_terms, offsets, offsets_dev, n_rows) for the
+        attached encoder (`encoder`, when given, is attached first).  Built on first use; afterwards only the rows that arrived
+        since are encoded.  A delete, a document update or an upsert drops it (SlabCollection._drop_derived) and the next call
+        re-encodes every document.  Not persisted; one device only.  ValueError, before any encoding, when rows x sparse_doc_terms
+        x 8 bytes would exceed max_index_bytes."""
+        import torch
+        if encoder is not None and encoder is not self._sparse_encoder:
+            self.attach_sparse_encoder(encoder)
+        if self._sparse_encoder is None:
+            raise ValueError("no sparse encoder attached: call attach_sparse_encoder(SparseEncoder(...)) first")
+        col = self.collection
+        if col is None:
+            raise ValueError("No collection available. Create index first.")
+        if self.sharded or len(col.shards) != 1:
+            raise NotImplementedError("the sparse index lives on one device: sharded / num_gpus / devices are not supported")
+        limit = self.max_index_bytes
+        if limit is None:
+            limit = torch.cuda.get_device_properties(col.device).total_memory // 2
+        return col._sparse_index(self._sparse_encoder, self.sparse_doc_terms, int(limit))
+
+    def sparse_rows(self, queries: Sequence[str], top_k: int):
+        """Exact learned-sparse top-k of every query over the WHOLE collection, on the device (crs_sparse_topk,
+        csrc/sparse_scan.hip): queries [nq] strings -> (scores fp32 [nq, top_k], sidecar rows int64 [nq, top_k]) as numpy, best
+        first, ties by lower row, (-inf, -1) past the hits (a row that shares no term with the query is no hit).  The queries are
+        encoded on the device to at most sparse_query_terms terms each and go to the scan as they are: a query's padded slots
+        (-1, 0) are pairs no row matches, so nothing comes back to the host in between.  The batch is cut as bm25_rows cuts it
+        (_bm25_launches: 64 queries, BM25_MAX_PAIRS pairs, every query counting sparse_query_terms); one readback for the whole
+        call.  1 <= top_k <= MAX_K."""
+        import torch
+        if not isinstance(top_k, (int, np.integer)) or isinstance(top_k, bool) or not 1 <= top_k <= nat.MAX_K:
+            raise ValueError(f"top_k must be an integer in 1..{nat.MAX_K} for a sparse search, got {top_k!r}")
+        index = self.sparse_index()
+        queries = list(queries)
+        nq, k, cap = len(queries), int(top_k), self.sparse_query_terms
+        scores = np.full((nq, k), -np.inf, dtype=np.float32)
+        rows = np.full((nq, k), -1, dtype=np.int64)
+        self.last_sparse = {'queries': nq, 'query_terms': cap, 'launches': 0}
+        if nq == 0 or index.n_rows == 0:
+            return scores, rows
+        launches = self._bm25_launches([cap] * nq)
+        dev = index.device
+        with self._device_guard(dev):
+            q_ids, q_w, _ = self._sparse_encoder.encode_queries_device(queries, cap)
+            out = torch.empty(nq * k + (nq * k + 1) // 2, dtype=torch.int64, device=dev)
+            out_r = out[: nq * k].view(nq, k)
+            out_s = out[nq * k:].view(torch.float32)[: nq * k].view(nq, k)
+            q_off = torch.arange(0, (nat.BM25_MAX_QUERIES + 1) * cap, cap, dtype=torch.int64, device=dev)
+            for lo, hi in launches:
+                n = hi - lo
+                nat.sparse_topk(index.offsets_dev, index.tokens, index.weights, index.n_rows, q_off[: n + 1],
+                                q_ids[lo:hi].reshape(-1), q_w[lo:hi].reshape(-1), k, out_scores=out_s[lo:hi], out_rows=out_r[lo:hi])
+            host = out.cpu().numpy()
+        self.last_sparse['launches'] = len(launches)
+        rows[:] = host[: nq * k].reshape(nq, k)
+        scores[:] = host[nq * k:].view(np.float32)[: nq * k].reshape(nq, k)
+        return scores, rows
+
+    def search_sparse_batch(self, queries: Sequence[str], top_k: int = 5) -> Dict[str, Any]:
+        """search_lexical_batch for the learned-sparse list (sparse_rows): the same dict, 'scores' the sparse dot products."""
+        return self._rows_dict(*self.sparse_rows(queries, top_k))
+
     def mmr_order(self, rows, rel, counts, lam: float):
         """Greedy MMR order of many result lists at once, on the device (crs_mmr_order, csrc/mmr.hip): rows int64 / rel fp64
         [nq, m_max <= MAX_K] (sidecar rows and their relevance, list order), counts [nq], lam = 1 - diversity_penalty -> numpy
@@ -1765,7 +1918,9 @@ class VectorStore:
 
     def search_lexical_batch(self, queries: Sequence[str], top_k: int = 5) -> Dict[str, Any]:
         """search_batch for the lexical list (bm25_rows): the same dict with 'scores' (BM25, best first) in place of 'distances'."""
-        sc, rh = self.bm25_rows(queries, top_k)
+        return self._rows_dict(*self.bm25_rows(queries, top_k))
+
+    def _rows_dict(self, sc, rh) -> Dict[str, Any]:
         col = self.collection
         out = {'ids': [], 'documents': [], 'metadatas': [], 'scores': []}
         for a in range(len(rh)):

@@ -25,6 +25,8 @@ Opt-in, ``hybrid`` (``true``, or a dict of ``rrf_k``, ``weights``, ``k1``, ``b``
 query with an exact BM25 list over the whole collection (VectorStore.bm25_rows, csrc/bm25.hip) by weighted reciprocal rank fusion
 (VectorStore.fuse_rrf, csrc/fuse.hip), so a chunk the encoder ranks far down still surfaces when it matches the query's words;
 the re-rank, the cut and the MMR step then run on the fused lists as before.  ``retrieve`` goes through ``retrieve_batch``.
+With ``sparse_model`` (a rag/sparse.py config dict, or a model name; needs ``hybrid``) the lexical list is the learned-sparse one
+(VectorStore.sparse_rows, csrc/sparse_scan.hip over the SPLADE vectors of every chunk) instead of BM25's.
 
 Additive: ``retrieve_batch`` embeds and searches many queries in one launch each and then applies
 the identical per-query post-processing; ``reuse_index_embeddings`` is NOT offered because the
@@ -100,6 +102,19 @@ class ContextRetriever:
         # cosine scores); retrieve() goes through retrieve_batch and refuses metadata filters
         self.hybrid = self._parse_hybrid(config.get('hybrid', False))
         self.last_hybrid = {'lists': 0, 'lexical_only_hits': 0}     # what the last retrieve_batch call fused
+        # additive: a learned sparse encoder (rag/sparse.py; a config dict, or a string used as its model_name) in place of BM25 as the
+        # lexical list of `hybrid`: VectorStore.sparse_rows instead of bm25_rows (k1 and b are then unused), everything downstream --
+        # fusion, the dict keys ('bm25_score' then holds the sparse dot product), thresholds, re-rankers -- unchanged
+        self.sparse_encoder = None
+        self.last_sparse = {'queries': 0, 'query_terms': 0, 'launches': 0}   # the sparse_rows calls of the last retrieve_batch call
+        if config.get('sparse_model'):
+            if self.hybrid is None:
+                raise ValueError("sparse_model needs hybrid: it replaces the lexical list that hybrid fuses with the dense one")
+            if not hasattr(vector_store, 'sparse_rows'):
+                raise ValueError("sparse_model needs a store with a sparse index (VectorStore.sparse_rows)")
+            from rag.sparse import SparseEncoder
+            self.sparse_encoder = SparseEncoder(config['sparse_model'])
+            vector_store.attach_sparse_encoder(self.sparse_encoder)
         self._token_sets: Dict[str, frozenset] = {}       # _rerank: text -> its lower-cased token set
         self._engine, self._engine_key = None, None
         self.distance_metric = self._get_distance_metric()
@@ -327,6 +342,7 @@ class ContextRetriever:
             if not (hasattr(store, 'bm25_rows') and hasattr(store, 'fuse_rrf') and hasattr(store, 'search_rows')):
                 raise ValueError("hybrid retrieval needs a store with search_rows, bm25_rows and fuse_rrf")
             self.last_hybrid = {'lists': 0, 'lexical_only_hits': 0}
+            self.last_sparse = {'queries': 0, 'query_terms': 0, 'launches': 0}
         per_query: List[List[Dict]] = []
         row_of: Dict[int, int] = {}           # id(chunk dict) -> sidecar row (our store only)
         ids_l, docs_l, metas_l = getattr(col, 'ids', None), getattr(col, 'documents', None), getattr(col, 'metadatas', None)
@@ -461,7 +477,13 @@ class ContextRetriever:
             keep = score >= self.similarity_threshold
             n = int(keep.sum())
             dense[i, :n], d_dist[i, :n], d_score[i, :n] = rows[keep], dist[keep], score[keep]
-        lex_scores, lex_rows = store.bm25_rows(queries, fetch, k1=hy['k1'], b=hy['b'])
+        if self.sparse_encoder is not None:
+            lex_scores, lex_rows = store.sparse_rows(queries, fetch)
+            ran = store.last_sparse
+            self.last_sparse = {'queries': self.last_sparse['queries'] + ran['queries'], 'query_terms': ran['query_terms'],
+                                'launches': self.last_sparse['launches'] + ran['launches']}
+        else:
+            lex_scores, lex_rows = store.bm25_rows(queries, fetch, k1=hy['k1'], b=hy['b'])
         w_dense, w_lex = hy['weights']
         rows, fused, dpos, lpos, count = store.fuse_rrf(dense, lex_rows, fetch, c=hy['rrf_k'], weights=(w_dense, w_lex))
         norm = (w_dense + w_lex) / (hy['rrf_k'] + 1.0)

@@ -151,6 +151,54 @@ int crs_encoder_plan_describe(const crs_encoder_desc* d, int batch, int seq, int
 int crs_gemm_f16(const void* a_dev, const void* w_dev, const float* bias_dev, const float* residual_dev,
                  void* out_dev, int m, int n, int k, int mode, void* stream);
 
+/* ---- learned sparse retrieval (SPLADE): the masked-language-model head with the max-pool in its epilogue (additive to ABI 3;
+ * csrc/mlm_pool.hip).  For every text b of a batch and every vocabulary id v,
+ *     t_i       = LayerNorm(GELU(W_t h_i + b_t))              i < lens[b]; BertForMaskedLM's cls.predictions.transform
+ *     out[b, v] = log1p(max(0, max_i (t_i . Wd_v + bias_v)))  the decoder and cls.predictions.bias
+ *   hidden_dev  fp32 [batch, seq, hidden]  final hidden states as crs_encoder_forward leaves them in hidden_out_dev, 16-byte aligned.
+ *                                          Positions at or past lens[b] are padding: they are NEVER read, so they may hold anything
+ *   lens_dev    int32 [batch]              real tokens per text, clamped to [0, seq] (0: an all-zero row)
+ *   out_dev     fp32 [batch, vp]           vp >= vocab; columns [vocab, vp) are not written
+ * Numerics: h rounded to fp16 on load, W_t fp16, fp32 accumulation (v_mfma_f32_16x16x32_f16), bias, erf-GELU and LayerNorm in fp32,
+ * t rounded to fp16 once; the vocabulary projection is fp16 x fp16 with fp32 accumulation in ascending k, the bias added in fp32;
+ * the maximum is exact (an integer maximum over the bit patterns of the non-negative candidates, so it does not depend on the
+ * order in which tiles finish) and log1p is evaluated in fp64 and rounded once.  The [tokens, vocab] logits never exist in
+ * memory.  A text's row is a pure function of its own real tokens, bit for bit, whatever else shares the call and wherever it
+ * sits in the batch.  Rows of the decoder at or past vocab are never read.
+ * Workspace: crs_mlm_workspace_bytes() bytes, 256-byte aligned; after the call it begins with t as fp16 [tokens_padded, hidden]
+ * (zeros at padding positions), which parity tests read.  crs_mlm_pool_plan() gives the geometry of the launches for these sizes
+ * on any host (it touches no device).
+ * CRS_EINVAL, with a message and before any launch: a NULL pointer (in the head too), batch < 1, seq < 1, seq > head->max_pos,
+ * vocab < 1 or > 2^20, vp < vocab, batch * seq > 2^22, hidden not one of 64, 128, 256, 384, 512, 768, 1024, a pointer that is
+ * not 16-byte aligned.  No host synchronisation. */
+typedef struct crs_mlm_head {
+  int32_t hidden;
+  int32_t vocab;
+  int32_t max_pos;             /* of the encoder in front: the longest seq */
+  float ln_eps;
+  const void* transform_w16;   /* fp16 [hidden, hidden] row-major (out, in): cls.predictions.transform.dense.weight */
+  const float* transform_bias; /* [hidden] */
+  const float* ln_gamma;       /* cls.predictions.transform.LayerNorm */
+  const float* ln_beta;
+  const void* decoder_w16;     /* fp16 [vocab, hidden]: cls.predictions.decoder.weight (or a fp16 copy of the word embeddings) */
+  const float* decoder_bias;   /* fp32 [vocab] */
+} crs_mlm_head;
+
+typedef struct crs_mlm_plan {
+  int32_t tile_m, tile_n, tile_k;            /* the vocabulary projection's tile: token rows, vocabulary columns, k per step */
+  int32_t tokens, tokens_padded;             /* batch * seq, and that rounded up to whole row tiles */
+  int32_t grid_m, grid_n;                    /* row tiles and column tiles; the projection launches grid_m * grid_n workgroups */
+  int32_t pool_grid, pool_threads, pool_lds_bytes;
+  int32_t xform_grid, xform_threads, xform_lds_bytes;   /* the transform: one workgroup per 32 token rows */
+  int32_t ew_grid_x, ew_threads;             /* zeroing before and log1p after: grid (ew_grid_x, batch) */
+  size_t t16_bytes, workspace_bytes;
+} crs_mlm_plan;
+
+int crs_mlm_pool_plan(int batch, int seq, int hidden, int vocab, crs_mlm_plan* plan);
+int crs_mlm_workspace_bytes(int batch, int seq, int hidden, int vocab, size_t* bytes);
+int crs_mlm_sparse_pool(const float* hidden_dev, const int32_t* lens_dev, int batch, int seq, const crs_mlm_head* head,
+                        void* workspace_dev, size_t workspace_bytes, float* out_dev, int vp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -493,6 +493,34 @@ int crs_token_project(const float* hidden_dev, const void* w16_dev, const float*
 int crs_maxsim(const void* q16_dev, const int32_t* q_len_dev, int nq, int lq_max, const void* tok16_dev, const int64_t* offsets_dev,
                int64_t n_rows, int64_t n_tokens, const int64_t* rows_dev, int m_max, int dimp, float* out_dev, void* stream);
 
+/* ---- learned sparse retrieval (SPLADE): compaction of a dense weight row, impact top-k over a weighted token CSR -- no reference
+ * call site (additive to ABI 3; csrc/sparse_compact.hip, csrc/sparse_scan.hip; the head that produces the dense rows
+ * is crs_mlm_sparse_pool, crs_encoder.h) ----
+ * crs_sparse_compact turns each row of weights_dev fp32 [batch, vp] (columns [0, vocab) count) into a bounded sparse row:
+ *   the ids whose weight is > 0 (a NaN or -0 is not) and that are not in skip_ids_dev int32 [n_skip] (may be null when n_skip is 0);
+ *   when more than `cap` remain, the cap largest weights, ties at the threshold by lower id; emitted in ascending id order as
+ *   ids_dev int32 [batch, cap] / out_weights_dev fp32 [batch, cap], unused slots (-1, 0); counts_dev int32 [batch] = ids kept.
+ * Exact and deterministic (no floating-point arithmetic: a positive float orders as its bit pattern).  One workgroup per text.
+ * Limits (CRS_EINVAL otherwise, before any launch): batch >= 1; 1 <= vocab <= vp; 1 <= cap <= CRS_SPARSE_MAX_TERMS;
+ * 0 <= n_skip <= CRS_SPARSE_MAX_SKIP.  No workspace, no host synchronisation.
+ *
+ * crs_sparse_topk is crs_bm25_topk with a weight per (row, token) in place of the term frequency and the row length:
+ *   doc_weights_dev  fp32 [n_doc_tokens]  parallel to doc_tokens_dev
+ * score(q, d) over the tokens t both hold, in ascending token id, all fp32, every operation rounded on its own (no fused
+ * multiply-add):   score = ((0 + q_w1 * d_w1) + q_w2 * d_w2) + ...      (tests/_sparse_ref.py restates it bit for bit in numpy)
+ * Everything else -- the other arguments, the limits (1 <= nq <= 64, 1 <= k <= CRS_MAX_K, 0 <= n_q_tokens <= CRS_BM25_MAX_PAIRS,
+ * 0 <= n_rows < 2^31 - 64), "a row sharing no token is no hit", ties by lower row, empty slots (-inf, -1), offsets clamped before
+ * they become addresses, the workspace rule (crs_sparse_workspace_bytes) and the merge -- is crs_bm25_topk's. */
+#define CRS_SPARSE_MAX_TERMS 1024
+#define CRS_SPARSE_MAX_SKIP 16
+int crs_sparse_compact(const float* weights_dev, int batch, int vocab, int vp, int cap, const int32_t* skip_ids_dev, int n_skip,
+                       int32_t* ids_dev, float* out_weights_dev, int32_t* counts_dev, void* stream);
+int crs_sparse_workspace_bytes(int nq, int k, int64_t n_rows, size_t* bytes);
+int crs_sparse_topk(const int64_t* doc_offsets_dev, const int32_t* doc_tokens_dev, const float* doc_weights_dev, int64_t n_rows,
+                    int64_t n_doc_tokens, const int64_t* q_offsets_dev, const int32_t* q_tokens_dev, const float* q_weights_dev, int nq,
+                    int64_t n_q_tokens, int k, void* workspace_dev, size_t workspace_bytes, float* out_scores_dev,
+                    int64_t* out_rows_dev, void* stream);
+
 /* ---- one-collective exchange (ONE all-gather per query batch) ------------------
  * A rank's per-shard result travels as one contiguous "wire block":
  *     [ ids int64 [nq, k] | scores fp32 [nq, k] | pad to 8 bytes ]        crs_wire_bytes(nq, k) bytes
