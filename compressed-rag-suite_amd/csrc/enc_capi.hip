@@ -65,6 +65,51 @@ struct PairTail {
     if (e_) { char m_[160]; snprintf(m_, sizeof m_, what ": %s", hipGetErrorString((hipError_t)e_)); return crs::set_error(CRS_EHIP, m_); } \
   } while (0)
 
+// route: which planner function makes the GemmPlan (the launchers still decide nothing).  *why: the message of a refusal
+crs::GemmPlan routed_plan(int m, int n, int k, int mode, int route, int flags, int cus, const char** why) {
+  crs::GemmPlan p;
+  const int small = flags & 1;
+  *why = "bad gemm arguments";
+  if (m <= 0 || n <= 0 || k <= 0) return p;
+  *why = "gemm K must be a multiple of 64";
+  if (k % 64) return p;
+  if (route == 0) {
+    *why = "bad gemm mode / missing residual";
+    if (mode < 0 || mode > 2) return p;
+    return crs::plan_gemm(m, n, k, mode, small, cus, knobs());
+  }
+  if (route == 1) {
+    *why = "panel gemm: modes 0, 1 and 3, K a multiple of 128";
+    if (mode != 0 && mode != 1 && mode != 3) return p;
+    return crs::plan_gemm_panel(m, n, k, mode, small, knobs());   // family None where K has no chunk
+  }
+  if (route == 2) {
+    *why = "gemm8 split-K: mode 3, and a shape gemm8_splitk takes (m >= 2048 in whole 256-row tiles, n in whole 256-column blocks, < 128 tiles)";
+    const int s8 = mode == 3 ? crs::gemm8_splitk(m, n, k, knobs()) : 0;
+    if (!s8) return p;
+    return crs::plan_gemm8(m, n, k, 3, s8, cus, knobs());
+  }
+  *why = "bad gemm route";
+  return p;
+}
+
+// out-projection / FFN-down + LayerNorm into x32 / x16: one fused launch, or the GEMM (fp32 slabs in y32, or bias + residual
+// folded in) and the LayerNorm that sums the slabs.  The residual is x32, updated in place.  Returns as the launchers do.
+int proj_ln_run(const crs::ProjLnPlan& s, const _Float16* a, const void* wt, const float* bias, const float* g, const float* b,
+                float eps, int T, int H, int k, float* x32, float* y32, _Float16* x16, hipStream_t st) {
+  if (s.rowln2) return crs::gemm_rowln2_launch(s, a, (const _Float16*)wt, bias, x32, g, b, eps, T, k, x32, x16, st);
+  const bool folded = s.gemm.mode == 2;
+  const int e = crs::gemm_launch(s.gemm, a, (const _Float16*)wt, folded ? bias : nullptr, folded ? x32 : nullptr, y32, st);
+  if (e) return e;
+  return crs::layernorm_launch(y32, s.gemm.slabs, folded ? nullptr : bias, folded ? nullptr : x32, g, b, eps, T, H, x32, x16, st);
+}
+
+int check_proj_ln(int tokens, int hidden, int k) {
+  if (tokens <= 0 || hidden <= 0 || hidden > 1024 || hidden % 64) return crs::set_error(CRS_EINVAL, "proj_ln: tokens > 0, hidden a multiple of 64, <= 1024");
+  if (k <= 0 || k % 64) return crs::set_error(CRS_EINVAL, "proj_ln: K must be a multiple of 64");
+  return CRS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -77,16 +122,66 @@ int crs_encoder_workspace_bytes(const crs_encoder_desc* d, int batch, int seq, s
   return CRS_OK;
 }
 
-int crs_gemm_f16(const void* a_dev, const void* w_dev, const float* bias_dev, const float* residual_dev,
-                 void* out_dev, int m, int n, int k, int mode, void* stream) {
-  if (!a_dev || !w_dev || !out_dev || m <= 0 || n <= 0 || k <= 0) return crs::set_error(CRS_EINVAL, "bad gemm arguments");
-  if (k % 64) return crs::set_error(CRS_EINVAL, "gemm K must be a multiple of 64");
-  if (mode < 0 || mode > 2 || (mode == 2 && !residual_dev)) return crs::set_error(CRS_EINVAL, "bad gemm mode / missing residual");
+int crs_gemm_f16_routed(const void* a_dev, const void* w_dev, const float* bias_dev, const float* residual_dev, void* out_dev,
+                        int m, int n, int k, int mode, int route, int flags, void* stream) {
+  if (!a_dev || !w_dev || !out_dev) return crs::set_error(CRS_EINVAL, "bad gemm arguments");
+  if (mode == 2 && !residual_dev) return crs::set_error(CRS_EINVAL, "bad gemm mode / missing residual");
+  if (mode == 3 && bias_dev) return crs::set_error(CRS_EINVAL, "gemm mode 3 takes no bias (the LayerNorm that sums the slabs adds it)");
+  if (((uintptr_t)a_dev | (uintptr_t)w_dev | (uintptr_t)out_dev | (uintptr_t)bias_dev | (uintptr_t)residual_dev) & 15)
+    return crs::set_error(CRS_EINVAL, "gemm pointers must be 16-byte aligned");
   const int cus = crs::device_cus();
   if (cus <= 0) return crs::set_error(CRS_EHIP, "gemm: no device");
-  CRS_TRY(crs::gemm_launch(crs::plan_gemm(m, n, k, mode, 0, cus, knobs()), (const _Float16*)a_dev, (const _Float16*)w_dev, bias_dev,
-                           residual_dev, out_dev, (hipStream_t)stream), "gemm");
+  const char* why = "";
+  const crs::GemmPlan p = routed_plan(m, n, k, mode, route, flags, cus, &why);
+  if (p.family == crs::GemmFamily::None) return crs::set_error(CRS_EINVAL, why);
+  CRS_TRY(crs::gemm_launch(p, (const _Float16*)a_dev, (const _Float16*)w_dev, bias_dev, mode == 2 ? residual_dev : nullptr, out_dev,
+                           (hipStream_t)stream), "gemm");
   return CRS_OK;
+}
+
+int crs_gemm_f16(const void* a_dev, const void* w_dev, const float* bias_dev, const float* residual_dev,
+                 void* out_dev, int m, int n, int k, int mode, void* stream) {
+  if (mode < 0 || mode > 2) return crs::set_error(CRS_EINVAL, "bad gemm mode / missing residual");
+  return crs_gemm_f16_routed(a_dev, w_dev, bias_dev, residual_dev, out_dev, m, n, k, mode, 0, 0, stream);
+}
+
+int crs_gemm_plan_describe(int m, int n, int k, int mode, int route, int flags, int* slabs, char* buf, size_t cap) {
+  if (cap && !buf) return crs::set_error(CRS_EINVAL, "plan describe: null buffer");
+  const int cus = crs::device_cus();
+  if (cus <= 0) return crs::set_error(CRS_EHIP, "plan describe: no device");
+  const char* why = "";
+  const crs::GemmPlan p = routed_plan(m, n, k, mode, route, flags, cus, &why);
+  if (p.family == crs::GemmFamily::None) return crs::set_error(CRS_EINVAL, why);
+  if (slabs) *slabs = p.slabs;
+  return crs::gemm_plan_describe(p, buf, cap);
+}
+
+int crs_proj_ln_f16(const void* a_dev, const void* w_dev, const float* bias_dev, const float* g_dev, const float* b_dev, float eps,
+                    int tokens, int hidden, int k, int flags, int big_ln, float* y32_ws_dev, float* x32_inout_dev, void* x16_out_dev,
+                    void* stream) {
+  const int rc = check_proj_ln(tokens, hidden, k);
+  if (rc) return rc;
+  if (!a_dev || !w_dev || !bias_dev || !g_dev || !b_dev || !y32_ws_dev || !x32_inout_dev || !x16_out_dev) return crs::set_error(CRS_EINVAL, "proj_ln: null pointer");
+  if (((uintptr_t)a_dev | (uintptr_t)w_dev | (uintptr_t)bias_dev | (uintptr_t)g_dev | (uintptr_t)b_dev | (uintptr_t)y32_ws_dev |
+       (uintptr_t)x32_inout_dev | (uintptr_t)x16_out_dev) & 15)
+    return crs::set_error(CRS_EINVAL, "proj_ln pointers must be 16-byte aligned");
+  const int cus = crs::device_cus();
+  if (cus <= 0) return crs::set_error(CRS_EHIP, "proj_ln: no device");
+  const crs::ProjLnPlan s = crs::plan_proj_ln(tokens, hidden, k, big_ln != 0, flags & 1, cus, knobs());
+  CRS_TRY(proj_ln_run(s, (const _Float16*)a_dev, w_dev, bias_dev, g_dev, b_dev, eps, tokens, hidden, k, x32_inout_dev, y32_ws_dev,
+                      (_Float16*)x16_out_dev, (hipStream_t)stream), "projection + layernorm");
+  return CRS_OK;
+}
+
+int crs_proj_ln_plan_describe(int tokens, int hidden, int k, int flags, int big_ln, int* slabs, char* buf, size_t cap) {
+  const int rc = check_proj_ln(tokens, hidden, k);
+  if (rc) return rc;
+  if (cap && !buf) return crs::set_error(CRS_EINVAL, "plan describe: null buffer");
+  const int cus = crs::device_cus();
+  if (cus <= 0) return crs::set_error(CRS_EHIP, "plan describe: no device");
+  const crs::ProjLnPlan s = crs::plan_proj_ln(tokens, hidden, k, big_ln != 0, flags & 1, cus, knobs());
+  if (slabs) *slabs = s.rowln2 ? 1 : s.gemm.slabs;
+  return crs::proj_ln_plan_describe(s, hidden, buf, cap);
 }
 
 int crs_encoder_plan_describe(const crs_encoder_desc* d, int batch, int seq, int rel_bias, int pair, char* buf, size_t cap) {
@@ -129,14 +224,8 @@ static int encoder_forward(const crs_encoder_desc* d, const crs_encoder_weights*
   _Float16* ffn = reinterpret_cast<_Float16*>(ws + p.ffn_off);
   const int T = p.tokens, H = d->hidden, F = d->ffn;
 
-  // out-projection / FFN-down + LayerNorm into x32 / x16: one fused launch, or the GEMM (fp32 slabs in y32, or bias + residual
-  // folded in) and the LayerNorm that sums the slabs
   auto proj_ln = [&](const crs::ProjLnPlan& s, const _Float16* a, const void* wt, const float* bias, const float* g, const float* b, int k) -> int {
-    if (s.rowln2) return crs::gemm_rowln2_launch(s, a, (const _Float16*)wt, bias, x32, g, b, d->ln_eps, T, k, x32, x16, st);
-    const bool folded = s.gemm.mode == 2;
-    const int e = crs::gemm_launch(s.gemm, a, (const _Float16*)wt, folded ? bias : nullptr, folded ? x32 : nullptr, y32, st);
-    if (e) return e;
-    return crs::layernorm_launch(y32, s.gemm.slabs, folded ? nullptr : bias, folded ? nullptr : x32, g, b, d->ln_eps, T, H, x32, x16, st);
+    return proj_ln_run(s, a, wt, bias, g, b, d->ln_eps, T, H, k, x32, y32, x16, st);
   };
 
   CRS_TRY(crs::embed_ln_launch(ids_dev, pair ? pair->type_ids : nullptr, w->word_emb, w->pos_emb, w->type_emb,

@@ -122,7 +122,9 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_f16_kernel(const _Float16* _
   // sixteen dependent round trips per thread with the matrix pipe idle; same finding as in enc_rowln.hip.)
   constexpr int kIt2 = BM * (BN / 4) / kThreads;   // 16
   const int c4 = (tid % (BN / 4)) * 4, gc2 = n0 + c4;          // this thread's column group is the same in every pass
-  const bool cols_in = gc2 + 3 < N;
+  // 16-byte accesses only where every row starts 16-byte aligned (N a multiple of 4 here, of 8 for the fp16 stores below), as in the
+  // panel and streaming kernels; any other N goes element by element
+  const bool cols_in = gc2 + 3 < N && (N & 3) == 0;
   f32x4 rs[kIt2];
   f32x4 b4 = {0.f, 0.f, 0.f, 0.f};
   if (MODE == 2) {
@@ -174,7 +176,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_f16_kernel(const _Float16* _
         v[e + 1] = x[1];
       }
       const size_t at = (size_t)gr * N + gc;
-      if (gc + 7 < N) {
+      if (gc + 7 < N && (N & 7) == 0) {
         f16x8 h;
 #pragma unroll
         for (int e = 0; e < 8; ++e) h[e] = (_Float16)v[e];

@@ -83,6 +83,8 @@ bool gemm8_applies(int m, int n, int k, const EncKnobs& kn) {
   return (long)(m / kG8M) * cdiv(n, kG8N) >= kn.gemm8_min_wgs;
 }
 
+}  // namespace
+
 // Split-K form for projections whose output has too few 256 x 256 tiles to fill the chip (bge-base's N = 768 at a few
 // thousand tokens): the number of K slabs (0 = not applicable) such that tiles x slabs >= 128 workgroups, every slab a
 // multiple of 128 columns and >= 256; the LayerNorm kernel that follows sums the fp32 slabs.
@@ -108,6 +110,8 @@ GemmPlan plan_gemm8(int m, int n, int k, int mode, int splits, int cus, const En
   p.d = {p.persist ? cus : p.items, 1, 1, kG8Threads, kG8Lds};
   return p;
 }
+
+namespace {
 
 // Shapes the 256 x 256 tiles of enc_gemm_big.hip take (measured, tools/bench_gemm.py, same box): fp16-epilogue projections with
 // N a multiple of 256 and K >= 512 at index-build row counts -- bge-base QKV 32768 x 2304 x 768: 457 -> 686 TFLOP/s, FFN-up
@@ -166,6 +170,8 @@ bool qkv_attn_supported(int hidden, int heads, int seq) {
   return seq == 16 || seq == 32 || seq == 64;
 }
 
+}  // namespace
+
 ProjLnPlan plan_proj_ln(int tokens, int hidden, int k, bool big_ln, int small_lds, int cus, const EncKnobs& kn) {
   ProjLnPlan p;
   p.ln = {cdiv(tokens, kRowTokens), 1, 1, kRowThreads, 0};
@@ -181,8 +187,6 @@ ProjLnPlan plan_proj_ln(int tokens, int hidden, int k, bool big_ln, int small_ld
   }
   return p;
 }
-
-}  // namespace
 
 GemmPlan plan_gemm_panel(int m, int n, int k, int mode, int small_lds, const EncKnobs& kn) {
   GemmPlan p;
@@ -319,6 +323,12 @@ void proj_ln_lines(Text& t, const ProjLnPlan& s, int hidden) {
 int gemm_plan_describe(const GemmPlan& p, char* buf, size_t cap) {
   Text t{buf, cap};
   gemm_line(t, p);
+  return t.len;
+}
+
+int proj_ln_plan_describe(const ProjLnPlan& p, int hidden, char* buf, size_t cap) {
+  Text t{buf, cap};
+  proj_ln_lines(t, p, hidden);
   return t.len;
 }
 

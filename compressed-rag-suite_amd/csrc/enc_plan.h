@@ -58,6 +58,11 @@ GemmPlan plan_gemm(int m, int n, int k, int mode, int small_lds, int cus, const 
 // The panel kernel on modes 0 / 1 / 3 (family None where K has no chunk); the caller decides that the shape is one for it.
 GemmPlan plan_gemm_panel(int m, int n, int k, int mode, int small_lds, const EncKnobs& kn);
 
+// The phase-scheduled 256 x 256 kernel's split-K form (mode 3, fp32 slabs summed by the LayerNorm): gemm8_splitk answers the slab
+// count of a shape, 0 where the form does not apply (then no plan may be made); plan_gemm8 with mode 3 and that count is its plan.
+int gemm8_splitk(int m, int n, int k, const EncKnobs& kn);
+GemmPlan plan_gemm8(int m, int n, int k, int mode, int splits, int cus, const EncKnobs& kn);
+
 enum class AttnForm { Fused, Blocked, Short, Seq, Seq32 };
 struct AttnPlan {
   AttnForm form = AttnForm::Blocked;   // Fused: QKV projection + attention in one kernel (enc_qkvattn.hip), no QKV GEMM
@@ -75,6 +80,10 @@ struct ProjLnPlan {
   GemmPlan gemm;       // mode 3 (the LayerNorm adds bias and residual) or mode 2 (already folded in, slabs = 1)
   Dims ln;
 };
+
+// big_ln: the index-build side (make_enc_plan: more than 4096 tokens and CRS_ENC_BIGLN); then rowln2 where it has the shape, else
+// panel slabs, else gemm8 split-K, else the mode-2 GEMM of plan_gemm
+ProjLnPlan plan_proj_ln(int tokens, int hidden, int k, bool big_ln, int small_lds, int cus, const EncKnobs& kn);
 
 struct EncPlan {
   int hidden, heads, ffn, batch, seq, tokens;
@@ -97,6 +106,7 @@ EncPlan make_enc_plan(int hidden, int heads, int ffn, int flags, int batch, int 
 // One line per launch of embedding, ONE layer and the tail, in launch order: "<kernel><template arguments> grid=XxYxZ wg=Nx1x1 lds=BYTES\n"
 // (grid in workgroups, dynamic LDS).  Returns the length of the whole text (snprintf): > cap - 1 means it was cut.
 int gemm_plan_describe(const GemmPlan& p, char* buf, size_t cap);
+int proj_ln_plan_describe(const ProjLnPlan& p, int hidden, char* buf, size_t cap);   // rowln2: one line; else the GEMM's and the LayerNorm's
 int enc_plan_describe(const EncPlan& p, char* buf, size_t cap);
 
 }  // namespace crs

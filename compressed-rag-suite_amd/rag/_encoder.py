@@ -65,6 +65,13 @@ nat.register_signatures({
                                         c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     "crs_gemm_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                              c_void_p]),
+    # test-facing: one GEMM family / one projection + LayerNorm step on its own (include/crs_encoder.h)
+    "crs_gemm_f16_routed": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                    c_void_p]),
+    "crs_gemm_plan_describe": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int), c_void_p, c_size_t]),
+    "crs_proj_ln_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_int, c_int,
+                                c_void_p, c_void_p, c_void_p, c_void_p]),
+    "crs_proj_ln_plan_describe": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_int), c_void_p, c_size_t]),
 })
 
 
@@ -121,6 +128,46 @@ def gemm_f16(a, w, bias=None, residual=None, mode: int = 0):
     nat.check(nat.load().crs_gemm_f16(nat._ptr(a), nat._ptr(w), nat._ptr(bias), nat._ptr(residual), nat._ptr(out),
                                       m, n, k, mode, nat._stream_ptr()))
     return out
+
+
+def _describe(call):
+    """(text, slabs) of a describe entry: call(slabs_ref, buf, cap) -> length or error code"""
+    cap, slabs = 512, c_int(0)
+    while True:
+        buf = ctypes.create_string_buffer(cap)
+        need = call(byref(slabs), buf, cap)
+        nat.check(min(need, 0))
+        if need < cap:
+            return buf.value.decode(), int(slabs.value)
+        cap = need + 1
+
+
+def gemm_plan_describe(m: int, n: int, k: int, mode: int, route: int = 0, flags: int = 0):
+    """(launch line, slabs) of gemm_f16_routed for these sizes on the current device (crs_gemm_plan_describe)."""
+    lib = nat.load()
+    return _describe(lambda sl, buf, cap: lib.crs_gemm_plan_describe(m, n, k, mode, route, flags, sl, buf, cap))
+
+
+def gemm_f16_routed(a, w, bias, residual, out, mode: int, route: int = 0, flags: int = 0) -> None:
+    """crs_gemm_f16_routed into `out`: cuda fp16 [M, N] (modes 0 / 1), fp32 [M, N] (mode 2) or fp32 [slabs, M, N] (mode 3, no bias);
+    route 0 plan_gemm, 1 the panel kernel, 2 the 256 x 256 kernel's split-K form."""
+    m, k = a.shape
+    nat.check(nat.load().crs_gemm_f16_routed(nat._ptr(a), nat._ptr(w), nat._ptr(bias), nat._ptr(residual), nat._ptr(out),
+                                             m, w.shape[0], k, mode, route, flags, nat._stream_ptr()))
+
+
+def proj_ln_plan_describe(tokens: int, hidden: int, k: int, flags: int = 0, big_ln: bool = False):
+    """(launch lines, slabs) of proj_ln_f16 for these sizes on the current device (crs_proj_ln_plan_describe)."""
+    lib = nat.load()
+    return _describe(lambda sl, buf, cap: lib.crs_proj_ln_plan_describe(tokens, hidden, k, flags, int(big_ln), sl, buf, cap))
+
+
+def proj_ln_f16(a, w, bias, g, b, eps: float, y32_ws, x32, x16, flags: int = 0, big_ln: bool = False) -> None:
+    """crs_proj_ln_f16: x32 (cuda fp32 [T, H], the residual) <- LayerNorm(a w^T + bias + x32) in place, x16 its fp16 copy;
+    y32_ws: cuda fp32 scratch of slabs * T * H elements."""
+    t, k = a.shape
+    nat.check(nat.load().crs_proj_ln_f16(nat._ptr(a), nat._ptr(w), nat._ptr(bias), nat._ptr(g), nat._ptr(b), float(eps), t, w.shape[0],
+                                         k, flags, int(big_ln), nat._ptr(y32_ws), nat._ptr(x32), nat._ptr(x16), nat._stream_ptr()))
 
 
 class HipEncoder:

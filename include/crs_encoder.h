@@ -147,9 +147,45 @@ int crs_encoder_plan_describe(const crs_encoder_desc* d, int batch, int seq, int
 
 /* Building block exported for parity tests and for users with their own layer stack:
  *   C[M, N] = epilogue(A[M, K] (fp16) x W[N, K]^T (fp16) + bias[N])
- *   mode 0: fp16 out;  mode 1: erf-GELU, fp16 out;  mode 2: + residual fp32 [M, N], fp32 out. */
+ *   mode 0: fp16 out;  mode 1: erf-GELU, fp16 out;  mode 2: + residual fp32 [M, N], fp32 out.
+ * Any n > 0: every kernel family makes its 16-byte epilogue accesses only where n keeps the rows 16-byte aligned (a multiple of 8
+ * for fp16 outputs, of 4 for fp32 ones) and goes element by element otherwise.  K a multiple of 64; all pointers 16-byte aligned
+ * (CRS_EINVAL otherwise).  This is crs_gemm_f16_routed with route 0 and flags 0. */
 int crs_gemm_f16(const void* a_dev, const void* w_dev, const float* bias_dev, const float* residual_dev,
                  void* out_dev, int m, int n, int k, int mode, void* stream);
+
+/* Test-facing (additive to ABI 3): the same launch with the planner function named by the caller, so that every GEMM kernel family
+ * can be run on its own.  route 0: plan_gemm (modes 0..2: the phase-scheduled 256 x 256 kernel, the 256-row pipelined kernel, the
+ * row-streaming kernels or the tiled 128 x 128 kernel, by the sizes, the CU count and the CRS_* knobs); route 1: plan_gemm_panel, the
+ * panel kernel, modes 0 / 1 / 3, K a multiple of 128; route 2: the split-K form of the 256 x 256 kernel, mode 3 only, CRS_EINVAL for
+ * a shape that form does not take (csrc/enc_plan.cpp: gemm8_splitk).  flags & 1: the small-LDS forms (CRS_ENC_SMALL_LDS).
+ * mode 3 takes no bias (bias_dev must be NULL) and writes the raw fp32 partial products as out_dev[slabs][m][n]; slab z of the
+ * panel kernel holds the contraction over columns [z * K / slabs, (z + 1) * K / slabs) of K, and so does slab z of the 256 x 256
+ * kernel; crs_gemm_plan_describe answers the slab count.  The entry only chooses which planner function makes the plan; the
+ * launchers decide nothing. */
+int crs_gemm_f16_routed(const void* a_dev, const void* w_dev, const float* bias_dev, const float* residual_dev, void* out_dev,
+                        int m, int n, int k, int mode, int route, int flags, void* stream);
+
+/* The launch crs_gemm_f16_routed would make on the current device (its CU count; the knobs), as one line of
+ * crs_encoder_plan_describe's form; *slabs (may be NULL): the fp32 slabs a mode-3 launch writes, else 1.  Returns the length of the
+ * text as snprintf does, or a negative error code (CRS_EINVAL where crs_gemm_f16_routed would refuse).  It launches nothing. */
+int crs_gemm_plan_describe(int m, int n, int k, int mode, int route, int flags, int* slabs, char* buf, size_t cap);
+
+/* Test-facing (additive to ABI 3): the out-projection / FFN-down step of a layer exactly as the forward runs it,
+ *   x = LayerNorm(a[tokens, k] (fp16) x w[hidden, k]^T (fp16) + bias + x32) -> x32_inout (fp32, in place), x16_out (fp16),
+ * on the route the planner picks (csrc/enc_plan.cpp: plan_proj_ln): with big_ln != 0 and hidden 384, k a multiple of 64 from 192 on,
+ * the fused projection + LayerNorm kernel; else split-K panel slabs + LayerNorm, split-K slabs of the 256 x 256 kernel +
+ * LayerNorm, or the mode-2 GEMM of crs_gemm_f16 + LayerNorm.  (The forward passes big_ln = tokens > 4096, unless CRS_ENC_BIGLN=0.)
+ * y32_ws_dev: slabs * tokens * hidden floats of scratch, slabs as crs_proj_ln_plan_describe answers (1 for the fused kernel, which
+ * does not touch it).  g / b: the LayerNorm's gain and bias; flags & 1: CRS_ENC_SMALL_LDS.  hidden a multiple of 64 up to 1024, k a
+ * multiple of 64, no NULL pointer, all pointers 16-byte aligned (CRS_EINVAL otherwise). */
+int crs_proj_ln_f16(const void* a_dev, const void* w_dev, const float* bias_dev, const float* g_dev, const float* b_dev, float eps,
+                    int tokens, int hidden, int k, int flags, int big_ln, float* y32_ws_dev, float* x32_inout_dev, void* x16_out_dev,
+                    void* stream);
+
+/* The launches of crs_proj_ln_f16 for these sizes on the current device, one line each (crs_encoder_plan_describe's form), and
+ * *slabs (may be NULL).  Returns the length of the text, or a negative error code.  It launches nothing. */
+int crs_proj_ln_plan_describe(int tokens, int hidden, int k, int flags, int big_ln, int* slabs, char* buf, size_t cap);
 
 /* ---- learned sparse retrieval (SPLADE): the masked-language-model head with the max-pool in its epilogue (additive to ABI 3;
  * csrc/mlm_pool.hip).  For every text b of a batch and every vocabulary id v,

@@ -1,6 +1,9 @@
 // enc_plan_table.cpp -- the encoder's planner (csrc/enc_plan.cpp) as a stand-alone program: no HIP, no device.
 //   g++ -O1 -std=c++17 -o enc_plan_table tools/enc_plan_table.cpp compressed-rag-suite_amd/csrc/enc_plan.cpp
 //   ./enc_plan_table <CUs> < cases      one case per line:  fwd hidden heads ffn flags batch seq rel_bias pair  |  gemm m n k mode
+//                                        |  route m n k mode route flags  |  projln tokens hidden k flags big_ln
+// (route, projln: what crs_gemm_plan_describe and crs_proj_ln_plan_describe answer; route 0 plan_gemm, 1 plan_gemm_panel, 2 the gemm8
+// split-K plan, family None where it does not apply)
 // The knobs come from the environment (CRS_GEMM8=0 ./enc_plan_table 256 ...), as in the library.  One line per case: key=value
 // fields separated by blanks, a tab, and the describe text with ';' for its line ends.  A GEMM step's fields are
 // family/slabs/tm/kc/kin/persist/items/ksplit/colblocks/streams.  tests/test_enc_plan_cpu.py drives it, built with
@@ -37,6 +40,28 @@ int main(int argc, char** argv) {
       const crs::GemmPlan g = crs::plan_gemm(m, n, k, mode, 0, cus, kn);
       gemm_fields("gemm", g);
       crs::gemm_plan_describe(g, text, sizeof text);
+      text_out(text);
+      continue;
+    }
+    if (!strcmp(kind, "route")) {
+      int m, n, k, mode, route, fl;
+      if (scanf("%d %d %d %d %d %d", &m, &n, &k, &mode, &route, &fl) != 6) return 2;
+      crs::GemmPlan g;
+      if (route == 0) g = crs::plan_gemm(m, n, k, mode, fl & 1, cus, kn);
+      else if (route == 1) g = crs::plan_gemm_panel(m, n, k, mode, fl & 1, kn);
+      else if (route == 2 && mode == 3 && crs::gemm8_splitk(m, n, k, kn)) g = crs::plan_gemm8(m, n, k, 3, crs::gemm8_splitk(m, n, k, kn), cus, kn);
+      gemm_fields("gemm", g);
+      crs::gemm_plan_describe(g, text, sizeof text);
+      text_out(text);
+      continue;
+    }
+    if (!strcmp(kind, "projln")) {
+      int tokens, hid, k, fl, big;
+      if (scanf("%d %d %d %d %d", &tokens, &hid, &k, &fl, &big) != 5) return 2;
+      const crs::ProjLnPlan s = crs::plan_proj_ln(tokens, hid, k, big != 0, fl & 1, cus, kn);
+      printf("rowln2=%d variant=%d ", (int)s.rowln2, s.variant);
+      gemm_fields("gemm", s.gemm);
+      crs::proj_ln_plan_describe(s, hid, text, sizeof text);
       text_out(text);
       continue;
     }
