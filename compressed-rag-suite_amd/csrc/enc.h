@@ -21,7 +21,8 @@ __device__ __forceinline__ int xcd_chunked_id(int id, int total) {
 // or -1 for a plan of another file's family.
 
 // enc_gemm.hip: C = epilogue(A[M,K] W[N,K]^T + bias) on the plan's family (GemmPlan: modes and families).  residual: mode 2 only;
-// mode 3 takes no bias and writes out as fp32 [slabs][M][N], summed by layernorm_launch.
+// mode 3 takes no bias and writes out as fp32 [slabs][M][N], summed by layernorm_launch; mode 4 (gemm8, tiled and panel families only:
+// the planner routes it nowhere else) writes fp16 [M, N / 2].
 int gemm_launch(const GemmPlan& p, const _Float16* a, const _Float16* w, const float* bias, const float* residual, void* out,
                 hipStream_t stream);
 // the families of the other files, reached through gemm_launch: enc_gemm8.hip (256 x 256 x 64 tiles, eight-barrier phase
@@ -48,9 +49,13 @@ int gemm_rowln2_launch(const ProjLnPlan& p, const _Float16* a, const _Float16* w
 int attention_launch(const AttnPlan& p, const _Float16* qkv, const int* lens, _Float16* ctx, int batch, int seq, int hidden, int heads,
                      const float* rel_bias, int span, hipStream_t stream);
 
+// enc_rope.hip: rotates the Q and K column blocks of qkv [tokens, 3 hidden] fp16 in place against table fp32 [positions, hd]
+// (cos half | sin half, include/crs_encoder.h: CRS_ENC_ROTARY); d: EncPlan::rope; the caller checked positions >= seq.  No LDS.
+int rope_qk_launch(const Dims& d, int hd, _Float16* qkv, const float* table, int tokens, int seq, int hidden, hipStream_t stream);
+
 // enc_misc.hip
 // type_ids (may be null: row 0 of type_tab for every token): int32 [tokens], clamped to [0, type_rows); an all-zero block
-// gives the bits of the null form
+// gives the bits of the null form.  pos may be null: no position row is added (rotary models)
 int embed_ln_launch(const int* ids, const int* type_ids, const float* word, const float* pos, const float* type_tab,
                     int type_rows, const float* g, const float* b, float eps, int tokens, int seq, int hidden, int vocab,
                     float* x32, _Float16* x16, hipStream_t stream);

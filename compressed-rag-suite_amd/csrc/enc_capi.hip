@@ -8,6 +8,8 @@
 //   ffn  = gelu(x16 Wup^T + b)                gemm mode 1      [T, F] fp16
 //   y32  = ffn Wdown^T + b + x32              gemm mode 2
 //   x    = LayerNorm(y32)
+// Rotary models (CRS_ENC_ROTARY): one rope_qk launch on qkv between the first two steps; gated ones (CRS_ENC_GATED_SILU):
+//   ffn  = silu(x16 Wgate^T + b) * (x16 Wup^T + b)   gemm mode 4 over the interleaved [2F, H] weight      [T, F] fp16
 // then pooling + L2 normalise -- or, for crs_encoder_score_pairs, the pair head (enc_pair.hip) on the [CLS] rows; its embedding
 // step takes a token-type row per token (embed_ln_launch with type_ids).  The launch function allocates nothing and never synchronises, so
 // a caller may capture it into a hipGraph for the launch-bound single-query case.
@@ -46,8 +48,12 @@ int check_desc(const crs_encoder_desc* d) {
   if (d->ffn <= 0 || d->ffn % 64) return crs::set_error(CRS_EINVAL, "ffn must be a multiple of 64");
   if (d->layers <= 0 || d->vocab_size <= 0 || d->max_pos <= 0) return crs::set_error(CRS_EINVAL, "bad layers/vocab/max_pos");
   if (d->pooling != CRS_POOL_MEAN && d->pooling != CRS_POOL_CLS) return crs::set_error(CRS_EINVAL, "bad pooling mode");
+  // (ffn % 64 above is what CRS_ENC_GATED_SILU needs: whole [16 gate | 16 up] blocks in every 128-row tile of the 2 ffn rows)
   return CRS_OK;
 }
+
+// mode 4: n rows of interleaved gate / up weights, n / 2 output columns in whole blocks of 16 pairs
+bool gated_n_ok(int n) { return n % 2 == 0 && (n / 2) % 32 == 0; }
 
 // what crs_encoder_score_pairs adds to the forward: per-token type ids at the embedding step (null: row 0, the kernels of the
 // plain forward) and the pair head in place of pooling
@@ -73,6 +79,12 @@ crs::GemmPlan routed_plan(int m, int n, int k, int mode, int route, int flags, i
   if (m <= 0 || n <= 0 || k <= 0) return p;
   *why = "gemm K must be a multiple of 64";
   if (k % 64) return p;
+  if (mode == 4 && route <= 1) {
+    *why = "gemm mode 4 (gated): n must be even and n / 2 a multiple of 32";
+    if (!gated_n_ok(n)) return p;
+    *why = "panel gemm: modes 0, 1, 3 and 4, K a multiple of 128";
+    return route == 0 ? crs::plan_gemm(m, n, k, 4, small, cus, knobs()) : crs::plan_gemm_panel(m, n, k, 4, small, knobs());
+  }
   if (route == 0) {
     *why = "bad gemm mode / missing residual";
     if (mode < 0 || mode > 2) return p;
@@ -197,9 +209,18 @@ static int encoder_forward(const crs_encoder_desc* d, const crs_encoder_weights*
                            const int32_t* lens_dev, int batch, int seq, void* workspace_dev,
                            size_t workspace_bytes, float* out_dev, int normalize, float* hidden_out_dev,
                            _Float16* q16_out_dev, int q16_row_elems, void* stream, const crs_encoder_ext* ext,
-                           const PairTail* pair = nullptr) {
+                           const PairTail* pair = nullptr, const crs_encoder_rope* rope = nullptr) {
   const int rc = check_desc(d);
   if (rc) return rc;
+  const bool rotary = (d->flags & CRS_ENC_ROTARY) != 0;
+  const float* rope_table = rope ? rope->table_dev : nullptr;
+  if (rotary && !rope_table) return crs::set_error(CRS_EINVAL, "CRS_ENC_ROTARY needs a rope table (crs_encoder_forward_rope / crs_encoder_forward_queries_rope)");
+  if (rotary && ext && ext->rel_bias_dev) return crs::set_error(CRS_EINVAL, "CRS_ENC_ROTARY does not combine with a relative-position bias");
+  if (rotary && (rope->positions < seq || ((uintptr_t)rope_table & 15))) {
+    char m[160];
+    snprintf(m, sizeof m, "rope table: positions %d must be >= seq %d, and the table 16-byte aligned", rope->positions, seq);
+    return crs::set_error(CRS_EINVAL, m);
+  }
   const float* rel_bias = ext ? ext->rel_bias_dev : nullptr;   // additive relative-position bias (crs_encoder_ext)
   const int rel_span = rel_bias ? ext->rel_span : 0;
   if (!w || !w->layers || !ids_dev || !lens_dev || !workspace_dev || !(pair ? (void*)pair->scores : (void*)out_dev)) return crs::set_error(CRS_EINVAL, "null pointer");
@@ -237,6 +258,7 @@ static int encoder_forward(const crs_encoder_desc* d, const crs_encoder_weights*
       CRS_TRY(crs::qkv_attn_launch(p.attn, x16, (const _Float16*)L.w_qkv, L.b_qkv, lens_dev, ctx, T, seq, H, st), "qkv + attention");
     } else {
       CRS_TRY(crs::gemm_launch(p.qkv, x16, (const _Float16*)L.w_qkv, L.b_qkv, nullptr, qkv, st), "qkv gemm");
+      if (p.rotary) CRS_TRY(crs::rope_qk_launch(p.rope, p.attn.hd, qkv, rope_table, T, seq, H, st), "rope");
       CRS_TRY(crs::attention_launch(p.attn, qkv, lens_dev, ctx, batch, seq, H, d->heads, rel_bias, rel_span, st), "attention");
     }
     CRS_TRY(proj_ln(p.out, ctx, L.w_o, L.b_o, L.ln1_g, L.ln1_b, H), "out projection + layernorm 1");
@@ -278,12 +300,20 @@ int crs_encoder_score_pairs(const crs_encoder_desc* d, const crs_encoder_weights
                          stream, nullptr, &pair);
 }
 
+int crs_encoder_forward_rope(const crs_encoder_desc* d, const crs_encoder_weights* w, const int32_t* ids_dev,
+                             const int32_t* lens_dev, int batch, int seq, void* workspace_dev,
+                             size_t workspace_bytes, float* out_dev, int normalize, float* hidden_out_dev,
+                             void* stream, const crs_encoder_ext* ext, const crs_encoder_rope* rope) {
+  return encoder_forward(d, w, ids_dev, lens_dev, batch, seq, workspace_dev, workspace_bytes, out_dev, normalize,
+                         hidden_out_dev, nullptr, 0, stream, ext, nullptr, rope);
+}
+
 int crs_encoder_forward_ex(const crs_encoder_desc* d, const crs_encoder_weights* w, const int32_t* ids_dev,
                            const int32_t* lens_dev, int batch, int seq, void* workspace_dev,
                            size_t workspace_bytes, float* out_dev, int normalize, float* hidden_out_dev,
                            void* stream, const crs_encoder_ext* ext) {
-  return encoder_forward(d, w, ids_dev, lens_dev, batch, seq, workspace_dev, workspace_bytes, out_dev, normalize,
-                         hidden_out_dev, nullptr, 0, stream, ext);
+  return crs_encoder_forward_rope(d, w, ids_dev, lens_dev, batch, seq, workspace_dev, workspace_bytes, out_dev, normalize,
+                                  hidden_out_dev, stream, ext, nullptr);
 }
 
 int crs_encoder_forward(const crs_encoder_desc* d, const crs_encoder_weights* w, const int32_t* ids_dev,
@@ -294,15 +324,34 @@ int crs_encoder_forward(const crs_encoder_desc* d, const crs_encoder_weights* w,
                                 hidden_out_dev, stream, nullptr);
 }
 
-int crs_encoder_forward_queries_ex(const crs_encoder_desc* d, const crs_encoder_weights* w, const int32_t* ids_dev,
-                                   const int32_t* lens_dev, int batch, int seq, void* workspace_dev,
-                                   size_t workspace_bytes, float* out_dev, void* q16_out_dev, int slab_type,
-                                   void* stream, const crs_encoder_ext* ext) {
+int crs_encoder_forward_queries_rope(const crs_encoder_desc* d, const crs_encoder_weights* w, const int32_t* ids_dev,
+                                     const int32_t* lens_dev, int batch, int seq, void* workspace_dev,
+                                     size_t workspace_bytes, float* out_dev, void* q16_out_dev, int slab_type,
+                                     void* stream, const crs_encoder_ext* ext, const crs_encoder_rope* rope) {
   if (!q16_out_dev) return crs::set_error(CRS_EINVAL, "null pointer");
   if (slab_type != CRS_SLAB_F16 && slab_type != CRS_SLAB_I8) return crs::set_error(CRS_EINVAL, "bad slab_type");
   if (!d) return crs::set_error(CRS_EINVAL, "null descriptor");
   return encoder_forward(d, w, ids_dev, lens_dev, batch, seq, workspace_dev, workspace_bytes, out_dev, 1, nullptr,
-                         reinterpret_cast<_Float16*>(q16_out_dev), crs_row_elems(d->hidden, slab_type), stream, ext);
+                         reinterpret_cast<_Float16*>(q16_out_dev), crs_row_elems(d->hidden, slab_type), stream, ext, nullptr, rope);
+}
+
+int crs_encoder_forward_queries_ex(const crs_encoder_desc* d, const crs_encoder_weights* w, const int32_t* ids_dev,
+                                   const int32_t* lens_dev, int batch, int seq, void* workspace_dev,
+                                   size_t workspace_bytes, float* out_dev, void* q16_out_dev, int slab_type,
+                                   void* stream, const crs_encoder_ext* ext) {
+  return crs_encoder_forward_queries_rope(d, w, ids_dev, lens_dev, batch, seq, workspace_dev, workspace_bytes, out_dev, q16_out_dev,
+                                          slab_type, stream, ext, nullptr);
+}
+
+int crs_rope_qk_f16(void* qkv_dev, const float* table_dev, int positions, int batch, int seq, int hidden, int heads, void* stream) {
+  if (!qkv_dev || !table_dev || (((uintptr_t)qkv_dev | (uintptr_t)table_dev) & 15)) return crs::set_error(CRS_EINVAL, "rope: NULL or misaligned (16 bytes) pointer");
+  if (batch < 1 || seq < 1 || heads < 1 || hidden < 1 || hidden % heads) return crs::set_error(CRS_EINVAL, "rope: bad batch / seq / hidden / heads");
+  const int hd = hidden / heads;
+  if (hd != 16 && hd != 32 && hd != 64) return crs::set_error(CRS_EINVAL, "rope: head_dim must be 16, 32 or 64");
+  if (positions < seq) return crs::set_error(CRS_EINVAL, "rope: positions must be >= seq");
+  if ((long)batch * seq > (1L << 24)) return crs::set_error(CRS_EINVAL, "rope: more than 2^24 tokens");
+  CRS_TRY(crs::rope_qk_launch(crs::plan_rope(batch * seq, hidden), hd, (_Float16*)qkv_dev, table_dev, batch * seq, seq, hidden, (hipStream_t)stream), "rope");
+  return CRS_OK;
 }
 
 int crs_encoder_forward_queries(const crs_encoder_desc* d, const crs_encoder_weights* w, const int32_t* ids_dev,

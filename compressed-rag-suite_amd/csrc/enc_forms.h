@@ -18,9 +18,9 @@ constexpr int panel_chunk(int k) {                 // 0: none
     if (k % kc == 0) return kc;
   return 0;
 }
-// staged A and W chunks; the epilogue's wave-private tiles (fp32 rows of 36 floats in mode 3, fp16 rows of 40 halves) re-use the buffer
+// staged A and W chunks; the epilogue's wave-private tiles (fp32 rows of 36 floats in modes 3 and 4, fp16 rows of 40 halves) re-use the buffer
 constexpr int panel_lds(int tm, int kc, int mode) {
-  const int stage = (tm + kPanelN) * kc * 2, ep = (mode == 3 ? 36 * 4 : 40 * 2) * 32 * ((tm / 32) * (kPanelN / 32));
+  const int stage = (tm + kPanelN) * kc * 2, ep = (mode >= 3 ? 36 * 4 : 40 * 2) * 32 * ((tm / 32) * (kPanelN / 32));
   return stage > ep ? stage : ep;
 }
 
@@ -67,6 +67,10 @@ constexpr int qa_lds(int hidden, int hd) {
   return (kQaTokens + 3 * hd) * hidden * 2 + (2 * kQaTokens * (hd + 8) + hd * (kQaTokens + 8)) * 2 + 4 * 16 * (64 + 8) * 2;
 }
 constexpr int kMaxLds = 160 * 1024;
+
+// enc_rope.hip: a thread rotates 8 column pairs (j, j + hd / 2) of one head of Q or K: hidden / 8 threads per token, no LDS
+constexpr int kRopeThreads = 256;
+constexpr long rope_items(long tokens, int hidden) { return tokens * (hidden / 8); }
 
 // enc_pair.hip: 8 pairs per workgroup, their [CLS] rows in LDS
 constexpr int kPairGroup = 8, kPairThreads = 256;

@@ -35,6 +35,14 @@ __device__ __forceinline__ gelu_f32x2 gelu_erf2(gelu_f32x2 x) {
   return hx * (p * r) + hx;
 }
 
+// SiLU for the gated epilogue (GEMM mode 4): x / (1 + exp(-x)) in fp32.  v_exp_f32 and v_rcp_f32 are accurate to about one
+// ulp each; the argument is clamped where exp(-x) would overflow (x < -88: the quotient is below 1e-36 either way, and the
+// product rounds to fp16 zero).
+__device__ __forceinline__ float silu_f32(float x) {
+  const float e = __expf(-fmaxf(x, -87.0f));
+  return x * __builtin_amdgcn_rcpf(1.0f + e);
+}
+
 __device__ __forceinline__ float gelu_erf(float x) {
   const gelu_f32x2 r = gelu_erf2(gelu_f32x2{x, x});
   return r[0];

@@ -14,6 +14,7 @@
 //   0  + bias                      -> fp16      (QKV projection)
 //   1  + bias, erf-GELU            -> fp16      (FFN up)
 //   2  + bias + residual (fp32)    -> fp32      (attention out / FFN down; LayerNorm follows)
+//   4  + bias, silu(gate) * up     -> fp16 [M, N / 2]   (gated FFN up: W rows interleaved [16 gate | 16 up], crs_encoder.h)
 // MFMA-bound for index-build batches (thousands of tokens); launch-bound for a single short query.
 
 #include "enc.h"
@@ -160,6 +161,26 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_f16_kernel(const _Float16* _
         for (int e = 0; e < 4 && gc2 + e < N; ++e) o[at + e] = v[e] + (bias ? bias[gc2 + e] : 0.f) + residual[at + e];
       }
     }
+  } else if (MODE == 4) {
+    // gated epilogue: the tile's 128 columns are 4 blocks of [16 gate | 16 up] columns (include/crs_encoder.h) = 64 output
+    // columns; a thread finishes 8 consecutive output columns of a row, all of one block.  N / 2 is a multiple of 32 (checked by
+    // the caller), so an 8-column group is inside the output or outside it as a whole and every row is 16-byte aligned.
+    _Float16* o = reinterpret_cast<_Float16*>(out);
+    const int NO = N >> 1, o0 = n0 >> 1;
+    for (int id = tid; id < BM * (BN / 16); id += kThreads) {
+      const int row = id / (BN / 16), c8 = (id % (BN / 16)) * 8;
+      const int gr = m0 + row, gc = o0 + c8;
+      if (gr >= M || gc >= NO) continue;
+      const int tg = 32 * (c8 >> 4) + (c8 & 15);   // the gate's column in the tile; the up value sits 16 columns on
+      f16x8 h;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float gt = tile[row * BN + tg + e] + (bias ? bias[n0 + tg + e] : 0.f);
+        const float up = tile[row * BN + tg + 16 + e] + (bias ? bias[n0 + tg + 16 + e] : 0.f);
+        h[e] = (_Float16)(silu_f32(gt) * up);
+      }
+      *reinterpret_cast<f16x8*>(o + (size_t)gr * NO + gc) = h;
+    }
   } else {
     _Float16* o = reinterpret_cast<_Float16*>(out);
     for (int id = tid; id < BM * (BN / 8); id += kThreads) {
@@ -202,7 +223,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_f16_kernel(const _Float16* _
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 constexpr int PN = forms::kPanelN, PKC = forms::kPanelMaxChunk;
 
-// MODE 0: +bias -> fp16; 1: +bias, GELU -> fp16; 3: raw fp32 partial tile -> out[z][M][N].
+// MODE 0: +bias -> fp16; 1: +bias, GELU -> fp16; 3: raw fp32 partial tile -> out[z][M][N]; 4: +bias, silu(gate) * up -> fp16 [M, N / 2].
 // TM = rows of A per workgroup: 64 (most workgroups, for tiny M) or 128 (halves the operand re-reads
 // and the workgroup count -- one wave of workgroups on 256 CUs for the 1024-token query batch).
 constexpr int kPanelThreads = forms::kPanelThreads;   // 512, 8 waves: the LDS-DMA issue (1 KiB per wave-instruction) is the long
@@ -298,6 +319,30 @@ __global__ __launch_bounds__(kPanelThreads, 1) void gemm_panel_kernel(const _Flo
         for (int e = 0; e < 4 && c0 + lc + e < N; ++e) dst[e] = v[e];
       }
     }
+  } else if (MODE == 4) {
+    // gated epilogue: a wave's 32 columns are one block of [16 gate | 16 up] columns (include/crs_encoder.h) = 16 output columns.
+    // The biased accumulators go through the wave-private fp32 tile (mode 3's); a lane then finishes 8 output columns of a row:
+    // one 16-byte store.  N / 2 is a multiple of 32 (checked by the caller): a wave's block is inside the output or outside it.
+    constexpr int TS = 36;
+    float* my = reinterpret_cast<float*>(psm) + wave * (32 * TS);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) my[((r & 3) + 8 * (r >> 2) + 4 * fh) * TS + fr] = acc[r] + b;
+    __builtin_amdgcn_wave_barrier();
+    if (c0 >= N) return;
+    _Float16* o = reinterpret_cast<_Float16*>(out);
+    const int NO = N >> 1, lrow = lane >> 1, lc = (lane & 1) * 8;
+    const int row = r0 + lrow;
+    if (row < M) {
+      const f32x4v g0 = *reinterpret_cast<const f32x4v*>(&my[lrow * TS + lc]), g1 = *reinterpret_cast<const f32x4v*>(&my[lrow * TS + lc + 4]);
+      const f32x4v u0 = *reinterpret_cast<const f32x4v*>(&my[lrow * TS + 16 + lc]), u1 = *reinterpret_cast<const f32x4v*>(&my[lrow * TS + 20 + lc]);
+      f16x8 h;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        h[e] = (_Float16)(silu_f32(g0[e]) * u0[e]);
+        h[e + 4] = (_Float16)(silu_f32(g1[e]) * u1[e]);
+      }
+      *reinterpret_cast<f16x8*>(o + (size_t)row * NO + (c0 >> 1) + lc) = h;
+    }
   } else {
     constexpr int TS = 40;   // halves per tile row (80 bytes)
     _Float16* my = reinterpret_cast<_Float16*>(psm) + wave * (32 * TS);
@@ -356,11 +401,12 @@ int gemm_launch(const GemmPlan& p, const _Float16* a, const _Float16* w, const f
     case GemmFamily::Big: return gemm_big_launch(p, a, w, bias, residual, out, stream);
     case GemmFamily::Stream:
     case GemmFamily::StreamKS: return gemm_stream_launch(p, a, w, bias, residual, out, stream);
-    case GemmFamily::Panel:   // out: mode 0 / 1 fp16 [M, N]; mode 3 fp32 [slabs][M][N] partials
+    case GemmFamily::Panel:   // out: mode 0 / 1 fp16 [M, N]; mode 3 fp32 [slabs][M][N] partials; mode 4 fp16 [M, N / 2]
       switch (p.mode) {
         case 0: return launch_panel<0>(p, a, w, bias, out, stream);
         case 1: return launch_panel<1>(p, a, w, bias, out, stream);
         case 3: return launch_panel<3>(p, a, w, bias, out, stream);
+        case 4: return launch_panel<4>(p, a, w, bias, out, stream);
         default: return -1;
       }
     case GemmFamily::Tiled: {
@@ -369,6 +415,7 @@ int gemm_launch(const GemmPlan& p, const _Float16* a, const _Float16* w, const f
         case 0: hipLaunchKernelGGL((gemm_f16_kernel<0>), grid, dim3(kThreads), 0, stream, a, w, bias, residual, out, p.m, p.n, p.k); break;
         case 1: hipLaunchKernelGGL((gemm_f16_kernel<1>), grid, dim3(kThreads), 0, stream, a, w, bias, residual, out, p.m, p.n, p.k); break;
         case 2: hipLaunchKernelGGL((gemm_f16_kernel<2>), grid, dim3(kThreads), 0, stream, a, w, bias, residual, out, p.m, p.n, p.k); break;
+        case 4: hipLaunchKernelGGL((gemm_f16_kernel<4>), grid, dim3(kThreads), 0, stream, a, w, bias, residual, out, p.m, p.n, p.k); break;
         default: return -1;
       }
       return (int)hipGetLastError();

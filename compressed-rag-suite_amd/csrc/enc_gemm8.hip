@@ -1,6 +1,7 @@
 // enc_gemm8.hip -- 256 x 256 x 64 MFMA GEMM with an eight-barrier-per-k-tile phase schedule (gfx950).
 //
-//   C[M, N] = epilogue( A[M, K] x W[N, K]^T + bias[N] )        mode 0: fp16; 1: erf-GELU, fp16; 2: + residual fp32, fp32
+//   C[M, N] = epilogue( A[M, K] x W[N, K]^T + bias[N] )        mode 0: fp16; 1: erf-GELU, fp16; 2: + residual fp32, fp32;
+//                                                               4: silu(gate) * up over interleaved W rows, fp16 [M, N / 2]
 //
 // The structure the CDNA4 guide measures at ~1.3 PFLOP/s on random fp16/bf16 data (cdna_hip_programming.md section 5,
 // "256^2 8-phase template"), written for this library's operand layout (W stored [N, K] like torch.nn.Linear):
@@ -206,7 +207,30 @@ __global__ __launch_bounds__(kP8Threads, 2) void gemm8_kernel(const _Float16* __
     for (int j = 0; j < 4; ++j)
       bv[j] = (bias && MODE != 3) ? *reinterpret_cast<const f32x4*>(bias + bs.n0 + wn * 64 + j * 16 + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
     const int row_g0 = bs.m0 + wm * 128, col_g0 = bs.n0 + wn * 64;
-    if (MODE < 2) {
+    if (MODE == 4) {
+      // gated epilogue (W rows interleaved [16 gate | 16 up], include/crs_encoder.h): column tile 2 b of the wave holds the gates
+      // and tile 2 b + 1 the up values of the SAME 16 output columns, in the same lane and element -- the product is a register
+      // operation.  A 16-row block leaves as 32 fp16 columns: 64 contiguous bytes per row, one 16-byte store per lane.
+      _Float16* o = reinterpret_cast<_Float16*>(out);
+      const int NO = N >> 1;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+#pragma unroll
+        for (int jb = 0; jb < 2; ++jb) {
+          const f32x4 g = acc[i][2 * jb] + bv[2 * jb], u = acc[i][2 * jb + 1] + bv[2 * jb + 1];
+          const f16x4 hv = {(_Float16)(silu_f32(g[0]) * u[0]), (_Float16)(silu_f32(g[1]) * u[1]), (_Float16)(silu_f32(g[2]) * u[2]),
+                            (_Float16)(silu_f32(g[3]) * u[3])};
+          *reinterpret_cast<f16x4*>(stage + c * kEpiRow16 + (jb * 16 + 4 * q) * 2) = hv;
+          acc[i][2 * jb] = f32x4{0.f, 0.f, 0.f, 0.f};
+          acc[i][2 * jb + 1] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        __builtin_amdgcn_wave_barrier();
+        const int lrow = lane >> 2, ch = lane & 3;
+        const f16x8 v = *reinterpret_cast<const f16x8*>(stage + lrow * kEpiRow16 + ch * 16);
+        *reinterpret_cast<f16x8*>(o + (size_t)(row_g0 + i * 16 + lrow) * NO + (col_g0 >> 1) + ch * 8) = v;
+        __builtin_amdgcn_wave_barrier();
+      }
+    } else if (MODE < 2) {
       _Float16* o = reinterpret_cast<_Float16*>(out);
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
@@ -308,6 +332,7 @@ int gemm8_launch(const GemmPlan& p, const _Float16* a, const _Float16* w, const 
     case 1: return launch8<1>(p, a, w, bias, residual, out, stream);
     case 2: return launch8<2>(p, a, w, bias, residual, out, stream);
     case 3: return launch8<3>(p, a, w, bias, residual, out, stream);
+    case 4: return launch8<4>(p, a, w, bias, residual, out, stream);   // out: fp16 [M, N / 2]
     default: return -1;
   }
 }

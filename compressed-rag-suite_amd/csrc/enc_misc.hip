@@ -33,13 +33,13 @@ __global__ __launch_bounds__(256) void embed_ln2_kernel(const int* __restrict__ 
   const float* w = word + (size_t)clamp_row(ids[t], vocab) * hidden;
   const float* type0 = type_tab;
   if constexpr (TYPES) type0 += (size_t)clamp_row(type_ids[t], type_rows) * hidden;
-  const float* p = pos + (size_t)(t % seq) * hidden;
+  const float* p = pos ? pos + (size_t)(t % seq) * hidden : nullptr;   // null: no position row (rotary models)
   float v[P2][2];
 #pragma unroll
   for (int i = 0; i < P2; ++i) {
     const int c = 128 * i + 2 * lane;
     const float2 a = *reinterpret_cast<const float2*>(w + c), ty = *reinterpret_cast<const float2*>(type0 + c),
-                 pp = *reinterpret_cast<const float2*>(p + c);
+                 pp = p ? *reinterpret_cast<const float2*>(p + c) : float2{0.f, 0.f};
     v[i][0] = (a.x + ty.x) + pp.x;   // (word + token_type) + position, as modeling_bert
     v[i][1] = (a.y + ty.y) + pp.y;
   }
@@ -91,12 +91,12 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int* __restrict__ i
   const float* w = word + (size_t)clamp_row(ids[t], vocab) * hidden;
   const float* type0 = type_tab;
   if constexpr (TYPES) type0 += (size_t)clamp_row(type_ids[t], type_rows) * hidden;
-  const float* p = pos + (size_t)(t % seq) * hidden;
+  const float* p = pos ? pos + (size_t)(t % seq) * hidden : nullptr;   // null: no position row (rotary models)
   float v[PL];
 #pragma unroll
   for (int i = 0; i < PL; ++i) {
     const int c = lane + 64 * i;
-    v[i] = (c < hidden) ? (w[c] + type0[c]) + p[c] : 0.f;   // (word + token_type) + position, as modeling_bert
+    v[i] = (c < hidden) ? (w[c] + type0[c]) + (p ? p[c] : 0.f) : 0.f;   // (word + token_type) + position, as modeling_bert
   }
   ln_store<PL>(v, hidden, lane, g, b, eps, x32 + (size_t)t * hidden, x16 + (size_t)t * hidden);
 }

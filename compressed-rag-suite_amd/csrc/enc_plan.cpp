@@ -105,7 +105,7 @@ GemmPlan plan_gemm8(int m, int n, int k, int mode, int splits, int cus, const En
   // the stream pays for the fp16 epilogues (bias / GELU; + 8 % at K = 768 and 384: their VALU and stores sit beside the next item's
   // first phases) and measured 4 % slower for the fp32 + residual ones (the residual loads of the 16-row passes drain behind the
   // transfers in flight): those keep one workgroup per item.  CRS_GEMM8_VAR=1: one workgroup per item everywhere (A/B)
-  p.persist = p.var != 1 && p.items > cus && mode < 2;
+  p.persist = p.var != 1 && p.items > cus && (mode < 2 || mode == 4);   // (4: an fp16 epilogue too)
   p.ksplit = k / p.slabs;
   p.d = {p.persist ? cus : p.items, 1, 1, kG8Threads, kG8Lds};
   return p;
@@ -172,6 +172,10 @@ bool qkv_attn_supported(int hidden, int heads, int seq) {
 
 }  // namespace
 
+Dims plan_rope(int tokens, int hidden) {
+  return {(int)((rope_items(tokens, hidden) + kRopeThreads - 1) / kRopeThreads), 1, 1, kRopeThreads, 0};
+}
+
 ProjLnPlan plan_proj_ln(int tokens, int hidden, int k, bool big_ln, int small_lds, int cus, const EncKnobs& kn) {
   ProjLnPlan p;
   p.ln = {cdiv(tokens, kRowTokens), 1, 1, kRowThreads, 0};
@@ -191,7 +195,7 @@ ProjLnPlan plan_proj_ln(int tokens, int hidden, int k, bool big_ln, int small_ld
 GemmPlan plan_gemm_panel(int m, int n, int k, int mode, int small_lds, const EncKnobs& kn) {
   GemmPlan p;
   int kc = panel_chunk(k);
-  if (kc == 0 || (mode != 0 && mode != 1 && mode != 3)) return p;
+  if (kc == 0 || (mode != 0 && mode != 1 && mode != 3 && mode != 4)) return p;
   p.family = GemmFamily::Panel;
   p.m = m, p.n = n, p.k = k, p.mode = mode;
   p.slabs = mode == 3 ? panel_splits(k, m, kn) : 1;
@@ -219,6 +223,15 @@ GemmPlan plan_gemm_panel(int m, int n, int k, int mode, int small_lds, const Enc
 GemmPlan plan_gemm(int m, int n, int k, int mode, int small_lds, int cus, const EncKnobs& kn) {
   (void)small_lds;   // none of these families has a small-LDS form
   GemmPlan p;
+  if (mode == 4) {
+    // the gated epilogue exists on the 256 x 256 phase-scheduled kernel, the tiled kernel (and the panel kernel, plan_gemm_panel):
+    // every mode-4 plan made here is Gemm8 or Tiled, whatever the shape and the knobs, so the 256-row and row-streaming
+    // families never see the mode
+    if (gemm8_applies(m, n, k, kn)) return plan_gemm8(m, n, k, mode, 1, cus, kn);
+    p.m = m, p.n = n, p.k = k, p.mode = mode, p.family = GemmFamily::Tiled;
+    p.d = {cdiv(n, kTiledN) * cdiv(m, kTiledM), 1, 1, kTiledThreads, 0};
+    return p;
+  }
   if (mode < 0 || mode > 2) return p;
   if (gemm8_applies(m, n, k, kn)) return plan_gemm8(m, n, k, mode, 1, cus, kn);
   p.m = m, p.n = n, p.k = k, p.mode = mode;
@@ -240,6 +253,7 @@ EncPlan make_enc_plan(int hidden, int heads, int ffn, int flags, int batch, int 
   const int T = batch * seq, H = hidden, F = ffn, hd = H / heads, small = (flags & 1) ? 1 : 0;   // CRS_ENC_SMALL_LDS
   p.hidden = H, p.heads = heads, p.ffn = F, p.batch = batch, p.seq = seq, p.tokens = T;
   p.typed = pair == 1, p.pair = pair;
+  p.rotary = (flags & 2) != 0, p.gated = (flags & 4) != 0;   // CRS_ENC_ROTARY, CRS_ENC_GATED_SILU
   p.embed = {cdiv(T, kRowTokens), 1, 1, kRowThreads, 0};
   p.tail = pair ? Dims{cdiv(batch, kPairGroup), 1, 1, kPairThreads, kPairGroup * H * 4} : Dims{batch, 1, 1, 256, 0};
   // fp16-epilogue projections (QKV, FFN-up) on the panel kernel: K = H in one chunk, or (CRS_ENC_PANEL_MULTI != 0) walked in
@@ -249,16 +263,20 @@ EncPlan make_enc_plan(int hidden, int heads, int ffn, int flags, int batch, int 
   const bool single_h = T <= kPanelMaxTokens && panel_chunk(H) != 0 && (panel_chunk(H) == H || kn.panel_multi) &&
                         !gemm8_applies(T, 3 * H, H, kn);
   // short sequences in the launch-bound regime: QKV projection + attention as one kernel (enc_qkvattn.hip)
-  if (!rel_bias && T <= kPanelMaxTokens && !small && kn.qkvattn && qkv_attn_supported(H, heads, seq)) {
+  // (never for a rotary model: the rotation runs between the projection and attention)
+  if (!rel_bias && !p.rotary && T <= kPanelMaxTokens && !small && kn.qkvattn && qkv_attn_supported(H, heads, seq)) {
     p.attn.form = AttnForm::Fused, p.attn.hd = hd;
     p.attn.d = {cdiv(T, kQaTokens), heads, 1, kQaThreads, qa_lds(H, hd)};
   } else {
     p.qkv = single_h ? plan_gemm_panel(T, 3 * H, H, 0, small, kn) : plan_gemm(T, 3 * H, H, 0, small, cus, kn);
     p.attn = plan_attention(batch, seq, heads, hd, rel_bias != 0, kn);
   }
+  if (p.rotary) p.rope = plan_rope(T, H);
   const bool big_ln = T > kPanelMaxTokens && kn.bigln;
   p.out = plan_proj_ln(T, H, H, big_ln, small, cus, kn);
-  p.up = single_h ? plan_gemm_panel(T, F, H, 1, small, kn) : plan_gemm(T, F, H, 1, small, cus, kn);
+  // gated: W holds 2 F interleaved gate / up rows and the epilogue (mode 4) leaves F columns; ffn_off is T x F either way
+  if (p.gated) p.up = single_h ? plan_gemm_panel(T, 2 * F, H, 4, small, kn) : plan_gemm(T, 2 * F, H, 4, small, cus, kn);
+  else p.up = single_h ? plan_gemm_panel(T, F, H, 1, small, kn) : plan_gemm(T, F, H, 1, small, cus, kn);
   p.down = plan_proj_ln(T, H, F, big_ln, small, cus, kn);
 
   // The workspace's slab count: an UPPER BOUND of the slab counts above (out.gemm.slabs, down.gemm.slabs), kept as the rule
@@ -337,6 +355,7 @@ int enc_plan_describe(const EncPlan& p, char* buf, size_t cap) {
   const char* two = row_form2(p.hidden) ? "2" : "";
   t.line(p.embed, "embed_ln%s_kernel<%d, %s>", two, row_form(p.hidden), p.typed ? "true" : "false");
   gemm_line(t, p.qkv);
+  if (p.rotary) t.line(p.rope, "rope_qk_kernel<%d>", p.attn.hd);
   const AttnPlan& a = p.attn;
   switch (a.form) {
     case AttnForm::Fused: t.line(a.d, "qkv_attn_kernel<%d>", a.hd); break;

@@ -39,7 +39,8 @@ struct Dims { int gx = 0, gy = 1, gz = 1, threads = 0, lds = 0; };   // grid in 
 enum class GemmFamily { None, Tiled, Panel, Stream, StreamKS, Big, Gemm8, Gemm8SplitK };
 
 // C = epilogue(A[M,K] W[N,K]^T): mode 0 fp16 (+ bias), 1 GELU fp16, 2 + bias + residual fp32, 3 fp32 partial slabs [slabs][M][N]
-// without bias (the LayerNorm that follows sums them and adds bias and residual)
+// without bias (the LayerNorm that follows sums them and adds bias and residual), 4 silu(gate) * up fp16 [M, N / 2] (gate / up rows
+// of W interleaved in blocks of 16, include/crs_encoder.h: CRS_ENC_GATED_SILU)
 struct GemmPlan {
   GemmFamily family = GemmFamily::None;
   int m = 0, n = 0, k = 0, mode = 0;
@@ -54,8 +55,9 @@ struct GemmPlan {
 };
 
 // What crs_gemm_f16 and the encoder's fp16 / fp32 + residual projections run (modes 0..2): gemm8, then big, then stream, then tiled.
+// Mode 4: gemm8, else tiled (the big and stream families have no gated epilogue and are never planned for it).
 GemmPlan plan_gemm(int m, int n, int k, int mode, int small_lds, int cus, const EncKnobs& kn);
-// The panel kernel on modes 0 / 1 / 3 (family None where K has no chunk); the caller decides that the shape is one for it.
+// The panel kernel on modes 0 / 1 / 3 / 4 (family None where K has no chunk); the caller decides that the shape is one for it.
 GemmPlan plan_gemm_panel(int m, int n, int k, int mode, int small_lds, const EncKnobs& kn);
 
 // The phase-scheduled 256 x 256 kernel's split-K form (mode 3, fp32 slabs summed by the LayerNorm): gemm8_splitk answers the slab
@@ -85,9 +87,14 @@ struct ProjLnPlan {
 // panel slabs, else gemm8 split-K, else the mode-2 GEMM of plan_gemm
 ProjLnPlan plan_proj_ln(int tokens, int hidden, int k, bool big_ln, int small_lds, int cus, const EncKnobs& kn);
 
+// rope_qk_kernel's launch: hidden / 8 threads per token (enc_forms.h), no LDS; a function of the two sizes alone
+Dims plan_rope(int tokens, int hidden);
+
 struct EncPlan {
   int hidden, heads, ffn, batch, seq, tokens;
   bool typed;          // embedding with a token-type row per token (pair forward with type ids)
+  bool rotary, gated;  // CRS_ENC_ROTARY: rope between qkv and attn, never Fused; CRS_ENC_GATED_SILU: up is mode 4 over 2 ffn rows
+  Dims rope;           // rotary only
   int pair;            // 0: pooling tail; else the pair head
   Dims embed, tail;
   AttnPlan attn;
@@ -99,7 +106,7 @@ struct EncPlan {
   int max_split;
 };
 
-// flags: crs_encoder_desc.flags; rel_bias: 1 with a relative-position bias; pair: 0 pooling tail, 1 pair head with type ids,
+// flags: crs_encoder_desc.flags (SMALL_LDS 1, ROTARY 2, GATED_SILU 4); rel_bias: 1 with a relative-position bias; pair: 0 pooling tail, 1 pair head with type ids,
 // 2 pair head without.  The sizes are check_desc's (hidden % 64 == 0 <= 1024, head_dim 16 / 32 / 64, ffn % 64 == 0).
 EncPlan make_enc_plan(int hidden, int heads, int ffn, int flags, int batch, int seq, int rel_bias, int pair, int cus, const EncKnobs& kn);
 

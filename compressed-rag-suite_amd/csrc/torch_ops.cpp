@@ -962,6 +962,8 @@ void unigram_encode(const Tensor& text, const Tensor& offsets, int64_t n_bytes, 
 // desc = [vocab_size, hidden, layers, heads, ffn, max_pos, pooling, flags (CRS_ENC_*, optional)]; weights = [word_emb, pos_emb, type_emb, emb_ln_g, emb_ln_b]
 // followed by 12 tensors per layer in crs_encoder_layer order (w_qkv b_qkv w_o b_o ln1_g ln1_b w_up b_up w_down b_down ln2_g ln2_b).
 // encoder_forward_ex adds rel_bias (optional): fp32 [heads, 2 * span - 1], the additive relative-position bias of crs_encoder_ext.
+// encoder_forward_rope adds rope_table (optional): fp32 [positions, head_dim], crs_encoder_rope's table (descriptors with CRS_ENC_ROTARY);
+// an EMPTY pos_emb tensor (weights[1]) is passed as NULL: no position row is added at the embedding step.
 // desc + weights of a call as the C structs (the layer array lives in `layers`)
 struct EncArgs {
   crs_encoder_desc d;
@@ -979,16 +981,18 @@ void enc_args(const Tensor& ids, at::TensorList weights, at::IntArrayRef desc, d
   for (int l = 0; l < a.d.layers; ++l) {
     const Tensor* w = &weights[5 + 12 * l];
     a.layers[l] = crs_encoder_layer{w[0].data_ptr(), (const float*)w[1].data_ptr(), w[2].data_ptr(), (const float*)w[3].data_ptr(),
-                                    (const float*)w[4].data_ptr(), (const float*)w[5].data_ptr(), w[6].data_ptr(), (const float*)w[7].data_ptr(),
+                                    (const float*)w[4].data_ptr(), (const float*)w[5].data_ptr(), w[6].data_ptr(),
+                                    w[7].numel() ? (const float*)w[7].data_ptr() : nullptr,   // an EMPTY b_up is NULL (CRS_ENC_GATED_SILU without bias)
                                     w[8].data_ptr(), (const float*)w[9].data_ptr(), (const float*)w[10].data_ptr(), (const float*)w[11].data_ptr()};
   }
-  a.cw = crs_encoder_weights{(const float*)weights[0].data_ptr(), (const float*)weights[1].data_ptr(), (const float*)weights[2].data_ptr(),
+  a.cw = crs_encoder_weights{(const float*)weights[0].data_ptr(), weights[1].numel() ? (const float*)weights[1].data_ptr() : nullptr,
+                             (const float*)weights[2].data_ptr(),
                              (const float*)weights[3].data_ptr(), (const float*)weights[4].data_ptr(), a.layers.data()};
 }
 
-void encoder_forward_ex(const Tensor& ids, const Tensor& lens, at::TensorList weights, at::IntArrayRef desc, double ln_eps, Tensor workspace,
-                        Tensor out, c10::optional<Tensor> q16_out, int64_t slab_type, bool normalize, c10::optional<Tensor> hidden_out,
-                        c10::optional<Tensor> rel_bias) {
+void encoder_forward_rope(const Tensor& ids, const Tensor& lens, at::TensorList weights, at::IntArrayRef desc, double ln_eps, Tensor workspace,
+                          Tensor out, c10::optional<Tensor> q16_out, int64_t slab_type, bool normalize, c10::optional<Tensor> hidden_out,
+                          c10::optional<Tensor> rel_bias, c10::optional<Tensor> rope_table) {
   want(ids, at::kInt, "ids");
   want(lens, at::kInt, "lens");
   want(out, at::kFloat, "out");
@@ -1007,13 +1011,22 @@ void encoder_forward_ex(const Tensor& ids, const Tensor& lens, at::TensorList we
     ext.rel_bias_dev = rel_bias->data_ptr<float>();
     ext.rel_span = (int32_t)((rel_bias->size(1) + 1) / 2);
   }
+  crs_encoder_rope rope{nullptr, 0};
+  if (rope_table.has_value() && rope_table->defined()) {
+    want(*rope_table, at::kFloat, "rope_table");
+    same_device(ids, {opt_t(rope_table)}, "crs::encoder_forward_rope");
+    TORCH_CHECK(rope_table->dim() == 2 && rope_table->size(1) * d.heads == d.hidden, "rope_table must be [positions, head_dim]");
+    rope.table_dev = rope_table->data_ptr<float>();
+    rope.positions = (int32_t)rope_table->size(0);
+  }
   c10::hip::HIPGuardMasqueradingAsCUDA g(ids.device());
   if (q16_out.has_value() && q16_out->defined()) {
     want(*q16_out, at::kHalf, "q16_out");
     TORCH_CHECK(normalize && !(hidden_out.has_value() && hidden_out->defined()), "q16_out needs normalize=True and no hidden_out");
     TORCH_CHECK(q16_out->numel() == (int64_t)b * crs_row_elems(d.hidden, (int)slab_type), "q16_out must be [B, crs_row_elems(H, slab_type)]");
-    ok(crs_encoder_forward_queries_ex(&d, &cw, ids.data_ptr<int32_t>(), lens.data_ptr<int32_t>(), b, s, workspace.data_ptr(),
-                                      (size_t)workspace.nbytes(), out.data_ptr<float>(), q16_out->data_ptr(), (int)slab_type, cur_stream(ids), &ext),
+    ok(crs_encoder_forward_queries_rope(&d, &cw, ids.data_ptr<int32_t>(), lens.data_ptr<int32_t>(), b, s, workspace.data_ptr(),
+                                        (size_t)workspace.nbytes(), out.data_ptr<float>(), q16_out->data_ptr(), (int)slab_type, cur_stream(ids), &ext,
+                                        &rope),
        "crs::encoder_forward");
     return;
   }
@@ -1023,8 +1036,14 @@ void encoder_forward_ex(const Tensor& ids, const Tensor& lens, at::TensorList we
     TORCH_CHECK(hidden_out->numel() == (int64_t)b * s * d.hidden, "hidden_out must be [B, S, H]");
     hid = hidden_out->data_ptr<float>();
   }
-  ok(crs_encoder_forward_ex(&d, &cw, ids.data_ptr<int32_t>(), lens.data_ptr<int32_t>(), b, s, workspace.data_ptr(), (size_t)workspace.nbytes(),
-                            out.data_ptr<float>(), normalize ? 1 : 0, hid, cur_stream(ids), &ext), "crs::encoder_forward");
+  ok(crs_encoder_forward_rope(&d, &cw, ids.data_ptr<int32_t>(), lens.data_ptr<int32_t>(), b, s, workspace.data_ptr(), (size_t)workspace.nbytes(),
+                              out.data_ptr<float>(), normalize ? 1 : 0, hid, cur_stream(ids), &ext, &rope), "crs::encoder_forward");
+}
+
+void encoder_forward_ex(const Tensor& ids, const Tensor& lens, at::TensorList weights, at::IntArrayRef desc, double ln_eps, Tensor workspace,
+                        Tensor out, c10::optional<Tensor> q16_out, int64_t slab_type, bool normalize, c10::optional<Tensor> hidden_out,
+                        c10::optional<Tensor> rel_bias) {
+  encoder_forward_rope(ids, lens, weights, desc, ln_eps, workspace, out, q16_out, slab_type, normalize, hidden_out, rel_bias, c10::nullopt);
 }
 
 void encoder_forward(const Tensor& ids, const Tensor& lens, at::TensorList weights, at::IntArrayRef desc, double ln_eps, Tensor workspace,
@@ -1150,6 +1169,8 @@ TORCH_LIBRARY(crs, m) {
         "Tensor(c!)? q16_out, int slab_type, bool normalize, Tensor(d!)? hidden_out) -> ()");
   m.def("encoder_forward_ex(Tensor ids, Tensor lens, Tensor[] weights, int[] desc, float ln_eps, Tensor(a!) workspace, Tensor(b!) out, "
         "Tensor(c!)? q16_out, int slab_type, bool normalize, Tensor(d!)? hidden_out, Tensor? rel_bias=None) -> ()");
+  m.def("encoder_forward_rope(Tensor ids, Tensor lens, Tensor[] weights, int[] desc, float ln_eps, Tensor(a!) workspace, Tensor(b!) out, "
+        "Tensor(c!)? q16_out, int slab_type, bool normalize, Tensor(d!)? hidden_out, Tensor? rel_bias=None, Tensor? rope_table=None) -> ()");
   m.def("encoder_score_pairs(Tensor ids, Tensor? type_ids, Tensor lens, Tensor[] weights, Tensor[] head, int[] desc, float ln_eps, "
         "int activation, Tensor(a!) workspace, Tensor(b!) scores, Tensor(c!)? pooled_out, Tensor(d!)? hidden_out) -> ()");
 }
@@ -1196,5 +1217,6 @@ TORCH_LIBRARY_IMPL(crs, CUDA, m) {   // the HIP backend of torch-ROCm dispatches
   m.impl("unigram_encode", &unigram_encode);
   m.impl("encoder_forward", &encoder_forward);
   m.impl("encoder_forward_ex", &encoder_forward_ex);
+  m.impl("encoder_forward_rope", &encoder_forward_rope);
   m.impl("encoder_score_pairs", &encoder_score_pairs);
 }

@@ -5,7 +5,11 @@ names, fp32 numpy in; matrices are cast to fp16 and Q/K/V stacked on upload) and
 through ``crs_encoder_forward_ex``.  A weights dict that also carries ``pooler.dense.*`` and ``classifier.*`` (one label: a
 BertForSequenceClassification cross-encoder) gets its head uploaded too, and ``score_pairs`` runs ``crs_encoder_score_pairs``.  MPNet checkpoints come in under the same names plus
 ``encoder.relative_attention_bias.weight`` (rag/embedding.py maps them), with ``ModelShape.rel_buckets``
-and ``pos_offset`` set: the bias is resolved per offset on the host and handed to the library.  Token ids in, pooled sentence embeddings out; no CPU fallback.
+and ``pos_offset`` set: the bias is resolved per offset on the host and handed to the library.  Rotary, gated encoders
+(nomic-embed-text: ``ModelShape.rotary_theta`` > 0 and ``gated``) come in under transformers' NomicBertModel names
+(``layers.N.self_attn.q_proj`` ..., ``mlp.gate_proj`` / ``up_proj`` / ``down_proj``): the gate and up matrices are interleaved
+into one ``w_up`` (``interleave_gate_up``), the cos / sin table is built on the host (``rope_table``) and the forward goes
+through ``torch.ops.crs.encoder_forward_rope``.  Token ids in, pooled sentence embeddings out; no CPU fallback.
 """
 from __future__ import annotations
 
@@ -20,6 +24,9 @@ from rag import _native as nat
 
 POOL_MEAN, POOL_CLS = 0, 1
 ENC_SMALL_LDS = 1      # CRS_ENC_SMALL_LDS: kernel forms of <= 48 KB of LDS (forwards that run beside a scan)
+ENC_ROTARY = 2         # CRS_ENC_ROTARY: rope_qk_kernel between the QKV projection and attention, no position table
+ENC_GATED_SILU = 4     # CRS_ENC_GATED_SILU: w_up holds interleaved gate / up rows, FFN-up runs GEMM mode 4
+GATE_UP_BLOCK = 16     # rows of a gate (or up) block of the interleaved layout (include/crs_encoder.h)
 
 
 class EncoderDesc(Structure):
@@ -39,6 +46,10 @@ class EncoderWeights(Structure):
 
 class EncoderExt(Structure):      # crs_encoder_ext
     _fields_ = [("rel_bias_dev", c_void_p), ("rel_span", c_int32)]
+
+
+class EncoderRope(Structure):     # crs_encoder_rope
+    _fields_ = [("table_dev", c_void_p), ("positions", c_int32)]
 
 
 class EncoderHead(Structure):     # crs_encoder_head
@@ -72,6 +83,14 @@ nat.register_signatures({
     "crs_proj_ln_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_int, c_int,
                                 c_void_p, c_void_p, c_void_p, c_void_p]),
     "crs_proj_ln_plan_describe": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_int), c_void_p, c_size_t]),
+    # rotary models (the forward reaches them through torch.ops.crs.encoder_forward_rope)
+    "crs_encoder_forward_rope": (c_int, [POINTER(EncoderDesc), POINTER(EncoderWeights), c_void_p, c_void_p, c_int,
+                                         c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, POINTER(EncoderExt),
+                                         POINTER(EncoderRope)]),
+    "crs_encoder_forward_queries_rope": (c_int, [POINTER(EncoderDesc), POINTER(EncoderWeights), c_void_p, c_void_p, c_int,
+                                                 c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_void_p,
+                                                 POINTER(EncoderExt), POINTER(EncoderRope)]),
+    "crs_rope_qk_f16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
 })
 
 
@@ -89,6 +108,38 @@ class ModelShape:
     rel_buckets: int = 0          # > 0: MPNet's bucketed relative-position bias ("encoder.relative_attention_bias.weight")
     rel_max_distance: int = 128
     pos_offset: int = 0           # first position id (MPNet: pad_token_id + 1 = 2); max_pos counts the table's rows
+    rotary_theta: float = 0.0     # > 0: rotary position embedding of Q and K with this base, no position table (nomic: 1000)
+    gated: bool = False           # SwiGLU feed-forward: silu(x Wgate^T) * (x Wup^T) in place of GELU(x W^T + b)
+
+
+def interleave_gate_up(gate, up) -> np.ndarray:
+    """gate, up: [F, ...] (F a multiple of 16) -> [2F, ...] in the layout CRS_ENC_GATED_SILU takes: rows [32 b, 32 b + 16) are
+    rows [16 b, 16 b + 16) of gate (the half SiLU acts on), rows [32 b + 16, 32 b + 32) the same rows of up."""
+    g, u = np.asarray(gate), np.asarray(up)
+    if g.shape != u.shape or g.shape[0] % GATE_UP_BLOCK:
+        raise ValueError(f"gate and up must have one shape with a multiple of {GATE_UP_BLOCK} rows, got {g.shape} and {u.shape}")
+    blocks = (g.shape[0] // GATE_UP_BLOCK, GATE_UP_BLOCK) + g.shape[1:]
+    return np.ascontiguousarray(np.stack([g.reshape(blocks), u.reshape(blocks)], axis=1).reshape((2 * g.shape[0],) + g.shape[1:]))
+
+
+def split_gate_up(w):
+    """The inverse of interleave_gate_up: [2F, ...] -> (gate, up)."""
+    w = np.asarray(w)
+    if w.shape[0] % (2 * GATE_UP_BLOCK):
+        raise ValueError(f"an interleaved gate / up array has a multiple of {2 * GATE_UP_BLOCK} rows, got {w.shape}")
+    b = w.reshape((w.shape[0] // (2 * GATE_UP_BLOCK), 2, GATE_UP_BLOCK) + w.shape[1:])
+    half = (w.shape[0] // 2,) + w.shape[1:]
+    return np.ascontiguousarray(b[:, 0].reshape(half)), np.ascontiguousarray(b[:, 1].reshape(half))
+
+
+def rope_table(positions: int, head_dim: int, theta: float) -> np.ndarray:
+    """fp32 [positions, head_dim], what crs_encoder_rope.table_dev takes: row p holds cos(p * theta^(-2 j / head_dim)) for
+    j < head_dim / 2 in its first half and the sines of the same angles in its second half; fp64 on the host, rounded once."""
+    if positions < 1 or head_dim % 2 or theta <= 0:
+        raise ValueError("rope_table: positions >= 1, an even head_dim and theta > 0")
+    inv = np.float64(theta) ** (-2.0 * np.arange(head_dim // 2, dtype=np.float64) / head_dim)
+    ang = np.arange(positions, dtype=np.float64)[:, None] * inv[None, :]
+    return np.ascontiguousarray(np.concatenate([np.cos(ang), np.sin(ang)], axis=1).astype(np.float32))
 
 
 def relative_position_bucket(rel, num_buckets: int = 32, max_distance: int = 128):
@@ -156,6 +207,13 @@ def gemm_f16_routed(a, w, bias, residual, out, mode: int, route: int = 0, flags:
                                              m, w.shape[0], k, mode, route, flags, nat._stream_ptr()))
 
 
+def rope_qk_f16(qkv, table, batch: int, seq: int, heads: int) -> None:
+    """crs_rope_qk_f16: rotates the Q and K column blocks of qkv (cuda fp16 [batch * seq, 3 H]) in place against table (cuda fp32
+    [positions, H / heads], rope_table's layout)."""
+    nat.check(nat.load().crs_rope_qk_f16(nat._ptr(qkv), nat._ptr(table), int(table.shape[0]), int(batch), int(seq), int(qkv.shape[1]) // 3,
+                                         int(heads), nat._stream_ptr()))
+
+
 def proj_ln_plan_describe(tokens: int, hidden: int, k: int, flags: int = 0, big_ln: bool = False):
     """(launch lines, slabs) of proj_ln_f16 for these sizes on the current device (crs_proj_ln_plan_describe)."""
     lib = nat.load()
@@ -198,12 +256,49 @@ class HipEncoder:
         # position ids start at pos_offset: the kernels index the table from its row pos_offset on
         if not 0 <= shape.pos_offset < shape.max_pos:
             raise ValueError("pos_offset must be inside the position table")
+        self.rope_table = None        # cuda fp32 [min(max_seq, max_pos), head_dim] of a rotary model
+        rotary, gated = shape.rotary_theta > 0, bool(shape.gated)
+        if rotary != gated:
+            raise NotImplementedError("rotary_theta and gated come together (nomic-embed-text): no loader builds one without the other")
+        if rotary and (shape.rel_buckets or shape.pos_offset):
+            raise ValueError("a rotary model has no position table: rel_buckets and pos_offset must be 0")
+        flags = (ENC_ROTARY if rotary else 0) | (ENC_GATED_SILU if gated else 0)
         self.desc = EncoderDesc(shape.vocab_size, shape.hidden, shape.layers, shape.heads, shape.ffn,
-                                shape.max_pos - shape.pos_offset, shape.ln_eps, POOL_CLS if shape.pooling == "cls" else POOL_MEAN, 0)
+                                shape.max_pos - shape.pos_offset, shape.ln_eps, POOL_CLS if shape.pooling == "cls" else POOL_MEAN, flags)
         self._layers = (EncoderLayer * shape.layers)()
-        for i in range(shape.layers):
+
+        def keep(arr, dtype=None):
+            t = torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float32)).to(self.device)
+            t = t.to(dtype).contiguous() if dtype is not None else t
+            self._keep.append(t)
+            return t
+
+        def bias_or_zeros(name, n):      # a checkpoint without this bias: a zero vector, so no kernel changes
+            return keep(weights[name] if name in weights else np.zeros(n, dtype=np.float32))
+
+        def nomic_layer(i):
+            """the 12 tensors of crs_encoder_layer from NomicBertModel's names; biases only where the checkpoint carries them: zero
+            vectors for b_qkv / b_o / b_down otherwise, and an EMPTY b_up (NULL for the library)"""
+            p, h = f"layers.{i}.", shape.hidden
+            bq = [np.asarray(weights.get(p + f"self_attn.{n}_proj.bias", np.zeros(h)), dtype=np.float32) for n in "qkv"]
+            if p + "mlp.gate_proj.bias" in weights and p + "mlp.up_proj.bias" in weights:
+                b_up = interleave_gate_up(weights[p + "mlp.gate_proj.bias"], weights[p + "mlp.up_proj.bias"])
+            else:
+                b_up = np.zeros(0, dtype=np.float32)
+            return [
+                dev16(p + "self_attn.q_proj.weight", p + "self_attn.k_proj.weight", p + "self_attn.v_proj.weight"),
+                keep(np.concatenate(bq)),
+                dev16(p + "self_attn.o_proj.weight"), bias_or_zeros(p + "self_attn.o_proj.bias", h),
+                dev32(p + "post_attention_layernorm.weight"), dev32(p + "post_attention_layernorm.bias"),
+                keep(interleave_gate_up(weights[p + "mlp.gate_proj.weight"], weights[p + "mlp.up_proj.weight"]), torch.float16),
+                keep(b_up),
+                dev16(p + "mlp.down_proj.weight"), bias_or_zeros(p + "mlp.down_proj.bias", h),
+                dev32(p + "post_mlp_layernorm.weight"), dev32(p + "post_mlp_layernorm.bias"),
+            ]
+
+        def bert_layer(i):
             p = f"encoder.layer.{i}."
-            vals = [
+            return [
                 dev16(p + "attention.self.query.weight", p + "attention.self.key.weight", p + "attention.self.value.weight"),
                 cat32(p + "attention.self.query.bias", p + "attention.self.key.bias", p + "attention.self.value.bias"),
                 dev16(p + "attention.output.dense.weight"), dev32(p + "attention.output.dense.bias"),
@@ -212,21 +307,27 @@ class HipEncoder:
                 dev16(p + "output.dense.weight"), dev32(p + "output.dense.bias"),
                 dev32(p + "output.LayerNorm.weight"), dev32(p + "output.LayerNorm.bias"),
             ]
+
+        layer_tensors = []
+        for i in range(shape.layers):
+            vals = nomic_layer(i) if rotary else bert_layer(i)
+            layer_tensors += vals
             for (fname, _), t in zip(EncoderLayer._fields_, vals):
-                setattr(self._layers[i], fname, t.data_ptr())
-        self.weights = EncoderWeights(
-            dev32("embeddings.word_embeddings.weight").data_ptr(),
-            dev32("embeddings.position_embeddings.weight")[shape.pos_offset:].data_ptr(),
-            dev32("embeddings.token_type_embeddings.weight").data_ptr(),
-            dev32("embeddings.LayerNorm.weight").data_ptr(),
-            dev32("embeddings.LayerNorm.bias").data_ptr(),
-            ctypes.cast(self._layers, POINTER(EncoderLayer)))
+                setattr(self._layers[i], fname, t.data_ptr() if t.numel() else None)
+        if rotary:      # an EMPTY position table: NULL for the library, which then adds no position row
+            pos = keep(np.zeros((0, shape.hidden), dtype=np.float32))
+        else:           # (a contiguous view of the kept tensor from its row pos_offset on)
+            pos = dev32("embeddings.position_embeddings.weight")[shape.pos_offset:]
+        emb = [dev32("embeddings.word_embeddings.weight"), pos, dev32("embeddings.token_type_embeddings.weight"),
+               dev32("embeddings.LayerNorm.weight"), dev32("embeddings.LayerNorm.bias")]
+        self.weights = EncoderWeights(*[t.data_ptr() if t.numel() else None for t in emb], ctypes.cast(self._layers, POINTER(EncoderLayer)))
         self._ws = None
-        # the same tensors in the order torch.ops.crs.encoder_forward takes them (csrc/torch_ops.cpp)
-        self._wlist = self._keep[-5:] + self._keep[:-5]     # embeddings first, then 12 tensors per layer
+        # the same tensors in the order torch.ops.crs.encoder_forward takes them (csrc/torch_ops.cpp): embeddings, then 12 per layer
+        self._wlist = emb + layer_tensors
         assert len(self._wlist) == 5 + 12 * shape.layers
-        if shape.pos_offset:
-            self._wlist[1] = self._wlist[1][shape.pos_offset:]       # (a contiguous view of the kept tensor)
+        if rotary:
+            self.rope_table = torch.from_numpy(rope_table(min(shape.max_seq, shape.max_pos), shape.hidden // shape.heads,
+                                                          shape.rotary_theta)).to(self.device)
         # additive relative-position bias, resolved per offset once: fp32 [heads, 2 * max_seq - 1] (crs_encoder_ext)
         self.rel_bias = None
         if shape.rel_buckets > 0:
@@ -296,8 +397,12 @@ class HipEncoder:
         if small_lds:          # per call, not process-wide: the role-lane engine asks for it, everyone else gets the default forms
             desc = desc[:7] + [desc[7] | ENC_SMALL_LDS]
         with nat._translate():
-            nat.ops().encoder_forward_ex(ids, lens, self._wlist, desc, float(self.desc.ln_eps), ws, out, q16_out,
-                                         int(slab_type), bool(normalize), hidden, self.rel_bias)
+            if self.desc.flags & ENC_ROTARY:
+                nat.ops().encoder_forward_rope(ids, lens, self._wlist, desc, float(self.desc.ln_eps), ws, out, q16_out,
+                                               int(slab_type), bool(normalize), hidden, self.rel_bias, self.rope_table)
+            else:
+                nat.ops().encoder_forward_ex(ids, lens, self._wlist, desc, float(self.desc.ln_eps), ws, out, q16_out,
+                                             int(slab_type), bool(normalize), hidden, self.rel_bias)
         return (out, hidden) if return_hidden else out
 
     def score_pairs(self, ids, type_ids, lens, activation="identity", return_pooled: bool = False, return_hidden: bool = False,

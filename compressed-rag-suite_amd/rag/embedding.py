@@ -10,9 +10,14 @@ Model resolution, offline by construction (the reference fetches by hub name, wh
 here): ``model_path`` (additive key) or ``model_name`` may be a LOCAL sentence-transformers
 directory (config.json, model.safetensors, vocab.txt, optional sentence_bert_config.json and
 1_Pooling/config.json); else ``$CRS_MODEL_DIR/<basename of model_name>`` is tried; else, when
-``model_name`` is ``synthetic:<minilm|bge|tiny|mpnet|tiny-mpnet|tiny-xlmr|multilingual-minilm|multilingual-e5-base>`` or ``CRS_ALLOW_SYNTHETIC_WEIGHTS=1`` is set,
+``model_name`` is ``synthetic:<minilm|bge|tiny|mpnet|tiny-mpnet|tiny-xlmr|multilingual-minilm|multilingual-e5-base|tiny-nomic|nomic-embed-text>`` or ``CRS_ALLOW_SYNTHETIC_WEIGHTS=1`` is set,
 seeded random weights of the named architecture are used with a hash tokeniser (plumbing and
 benchmarks only -- embeddings are then meaningless as language).  Anything else raises.
+
+Task prefixes (additive keys ``query_prefix`` / ``document_prefix``, default ""): models trained with them (nomic-embed-text:
+"search_query: " / "search_document: "; E5: "query: " / "passage: ") get the prefix prepended to every text of that kind before
+tokenisation; ``embed`` / ``embed_device`` / ``tokenize`` / ``tokenize_device`` take ``kind=None | 'query' | 'document'`` and the
+chunk methods are 'document'.  Nothing is read from config_sentence_transformers.json.
 """
 from __future__ import annotations
 
@@ -51,8 +56,15 @@ _KNOWN = {
                                 max_seq=128, ln_eps=1e-5, pos_offset=2),
     "multilingual-e5-base": dict(vocab_size=250002, hidden=768, layers=12, heads=12, ffn=3072, max_pos=514, pooling="mean",
                                  max_seq=512, ln_eps=1e-5, pos_offset=2),
+    # nomic-embed-text-v1 / v1.5: BERT's post-LayerNorm layer order and WordPiece vocabulary, rotary Q / K (base 1000) in place of a
+    # position table, SwiGLU feed-forward, no biases; published with 8192 positions (trained to 2048)
+    "tiny-nomic": dict(vocab_size=1000, hidden=64, layers=2, heads=4, ffn=256, max_pos=128, pooling="mean", max_seq=128,
+                       rotary_theta=1000.0, gated=True),
+    "nomic-embed-text": dict(vocab_size=30528, hidden=768, layers=12, heads=12, ffn=3072, max_pos=8192, pooling="mean", max_seq=512,
+                             rotary_theta=1000.0, gated=True),
 }
-_ALIASES = {"minilm": "all-minilm-l6-v2", "bge": "bge-base-en-v1.5", "bge-base": "bge-base-en-v1.5", "mpnet": "all-mpnet-base-v2"}
+_ALIASES = {"minilm": "all-minilm-l6-v2", "bge": "bge-base-en-v1.5", "bge-base": "bge-base-en-v1.5", "mpnet": "all-mpnet-base-v2",
+            "nomic": "nomic-embed-text", "nomic-embed-text-v1": "nomic-embed-text", "nomic-embed-text-v1.5": "nomic-embed-text"}
 REL_BIAS = "encoder.relative_attention_bias.weight"      # [buckets, heads], shared by all layers (MPNet)
 
 
@@ -101,8 +113,34 @@ def tokenize_on_device(device_tok, tokenizer, dev, texts: List[str], max_seq: in
 def synthetic_weights(shape, seed: int = 0, scale: float = 0.05) -> Dict[str, np.ndarray]:
     """Seeded random checkpoint with HuggingFace BertModel tensor names (one PCG64 stream per tensor).  Shapes with
     `rel_buckets` (MPNet) also get the relative-position bias table (~N(0, 0.5): real tables are O(1)) and, having no
-    token types, a zero token-type table."""
+    token types, a zero token-type table.  Gated (nomic) shapes: NomicBertModel's names, query / key projections ~N(0, 1 / hidden)."""
     h, f = shape.hidden, shape.ffn
+    if getattr(shape, "gated", False):      # nomic-embed-text under NomicBertModel's names: no position table, no biases
+        names = [("embeddings.word_embeddings.weight", (shape.vocab_size, h)), ("embeddings.token_type_embeddings.weight", (2, h)),
+                 ("embeddings.LayerNorm.weight", (h,)), ("embeddings.LayerNorm.bias", (h,))]
+        for i in range(shape.layers):
+            p = f"layers.{i}."
+            names += [(p + "self_attn.q_proj.weight", (h, h)), (p + "self_attn.k_proj.weight", (h, h)),
+                      (p + "self_attn.v_proj.weight", (h, h)), (p + "self_attn.o_proj.weight", (h, h)),
+                      (p + "post_attention_layernorm.weight", (h,)), (p + "post_attention_layernorm.bias", (h,)),
+                      (p + "mlp.gate_proj.weight", (f, h)), (p + "mlp.up_proj.weight", (f, h)), (p + "mlp.down_proj.weight", (h, f)),
+                      (p + "post_mlp_layernorm.weight", (h,)), (p + "post_mlp_layernorm.bias", (h,))]
+        out = {}
+        for idx, (name, shp) in enumerate(names):
+            rng = np.random.Generator(np.random.PCG64([seed, idx]))
+            if name.endswith("norm.weight"):
+                a = 1.0 + 0.05 * rng.standard_normal(shp, dtype=np.float32)
+            elif name.endswith(".bias"):
+                a = 0.02 * rng.standard_normal(shp, dtype=np.float32)
+            elif ".q_proj." in name or ".k_proj." in name:
+                # ~N(0, 1 / h): attention logits q . k / sqrt(hd) of unit variance at EVERY width.  Rotary positions act only
+                # through these logits; at `scale` a 64-wide model's logits have a standard deviation of 0.16 (the 768-wide
+                # one's: 1.9), its softmax is flat and the rotation could not show in any output
+                a = h ** -0.5 * rng.standard_normal(shp, dtype=np.float32)
+            else:
+                a = scale * rng.standard_normal(shp, dtype=np.float32)
+            out[name] = a.astype(np.float32)
+        return out
     names = [("embeddings.word_embeddings.weight", (shape.vocab_size, h)),
              ("embeddings.position_embeddings.weight", (shape.max_pos, h)),
              ("embeddings.token_type_embeddings.weight", (2, h)),
@@ -159,6 +197,66 @@ def _mpnet_weights(raw: Dict[str, np.ndarray], hidden: int) -> Dict[str, np.ndar
     return out
 
 
+def _nomic_shape_and_weights(cfg: dict, raw: Dict[str, np.ndarray], pooling: str, max_seq):
+    """(ModelShape, weights under NomicBertModel's names) of a model_type "nomic_bert" directory in either dialect: the hub
+    checkpoint (config keys n_embd / n_head / ..., tensors emb_ln, encoder.layers.N.attn.Wqkv, attn.out_proj, mlp.fc11 = up,
+    mlp.fc12 = gate, mlp.fc2, norm1, norm2 -- the renames of transformers' conversion mapping "nomic_bert") or one saved by
+    transformers 5.x (BERT-style config keys + rope_parameters, the names kept as they are)."""
+    from rag._encoder import ModelShape
+    hub = "n_embd" in cfg
+    if hub:
+        if float(cfg.get("rotary_emb_fraction", 1.0)) != 1.0:
+            raise NotImplementedError("nomic_bert: rotary_emb_fraction != 1 (partial rotation) is not supported")
+        if cfg.get("rotary_emb_interleaved", False):
+            raise NotImplementedError("nomic_bert: rotary_emb_interleaved (pairwise rotation) is not supported")
+        if cfg.get("prenorm", False):
+            raise NotImplementedError("nomic_bert: prenorm layers are not supported (post-LayerNorm is)")
+        if cfg.get("rotary_emb_scale_base") is not None:
+            raise NotImplementedError("nomic_bert: rotary_emb_scale_base (xPos scaling of the rotation) is not supported")
+        if cfg.get("rotary_scaling_factor") not in (None, 1, 1.0):
+            raise NotImplementedError("nomic_bert: rope scaling (rotary_scaling_factor) is not supported")
+        act = str(cfg.get("activation_function", "swiglu")).lower()
+        if act != "swiglu":
+            raise NotImplementedError(f"nomic_bert: activation_function '{act}' is not supported (swiglu is)")
+        hidden, heads, layers = int(cfg["n_embd"]), int(cfg["n_head"]), int(cfg["n_layer"])
+        ffn = int(cfg.get("n_inner") or 4 * hidden)
+        max_pos, theta = int(cfg.get("n_positions", 2048)), float(cfg.get("rotary_emb_base", 10000.0))
+        eps = float(cfg.get("layer_norm_epsilon", 1e-12))
+    else:
+        rp = dict(cfg.get("rope_parameters") or {})
+        if rp.get("rope_type", "default") != "default" or rp.get("factor") not in (None, 1, 1.0):
+            raise NotImplementedError(f"nomic_bert: rope_type '{rp.get('rope_type')}' / scaling factor {rp.get('factor')} is not supported")
+        if float(rp.get("partial_rotary_factor", 1.0)) != 1.0:
+            raise NotImplementedError("nomic_bert: partial_rotary_factor != 1 is not supported")
+        act = str(cfg.get("hidden_act", "silu")).lower()
+        if act not in ("silu", "swish", "swiglu"):
+            raise NotImplementedError(f"nomic_bert: hidden_act '{act}' is not supported (the silu-gated feed-forward is)")
+        hidden, heads, layers = int(cfg["hidden_size"]), int(cfg["num_attention_heads"]), int(cfg["num_hidden_layers"])
+        ffn, max_pos = int(cfg["intermediate_size"]), int(cfg.get("max_position_embeddings", 2048))
+        theta, eps = float(rp.get("rope_theta", cfg.get("rope_theta", 1000.0))), float(cfg.get("layer_norm_eps", 1e-12))
+        if cfg.get("head_dim") not in (None, hidden // heads):
+            raise NotImplementedError("nomic_bert: head_dim must be hidden_size / num_attention_heads")
+    weights = {}
+    renames = (("encoder.layers.", "layers."), ("emb_ln.", "embeddings.LayerNorm."), (".attn.out_proj.", ".self_attn.o_proj."),
+               (".mlp.fc11.", ".mlp.up_proj."), (".mlp.fc12.", ".mlp.gate_proj."), (".mlp.fc2.", ".mlp.down_proj."),
+               (".norm1.", ".post_attention_layernorm."), (".norm2.", ".post_mlp_layernorm."))
+    for k, v in raw.items():
+        for pre in ("model.", "bert.", "nomic_bert."):
+            if k.startswith(pre):
+                k = k[len(pre):]
+        for old, new in renames:
+            k = k.replace(old, new)
+        v = np.asarray(v, dtype=np.float32)
+        if ".attn.Wqkv." in k:      # [3H, H] (or [3H]) -> q, k, v, in that order
+            for part, name in zip(np.split(v, 3, axis=0), "qkv"):
+                weights[k.replace(".attn.Wqkv.", f".self_attn.{name}_proj.")] = np.ascontiguousarray(part)
+        else:
+            weights[k] = v
+    shape = ModelShape(int(cfg["vocab_size"]), hidden, layers, heads, ffn, max_pos, eps, pooling, min(int(max_seq or max_pos), max_pos),
+                       rotary_theta=theta, gated=True)
+    return shape, weights
+
+
 def _load_local_dir(path: str):
     """(ModelShape, weights dict, tokenizer, pre_lower, normalize_module) from a sentence-transformers directory.
 
@@ -188,11 +286,13 @@ def _load_local_dir(path: str):
     with open(os.path.join(tr_dir, "config.json")) as fh:
         cfg = json.load(fh)
     max_seq, pooling, pre_lower = cfg.get("max_position_embeddings", 512), "mean", False
+    sbc_max_seq = None       # sentence_bert_config.json's own limit, for configs without max_position_embeddings (nomic_bert)
     sb = os.path.join(tr_dir, "sentence_bert_config.json")
     if os.path.exists(sb):
         with open(sb) as fh:
             sbc = json.load(fh)
         max_seq = sbc.get("max_seq_length", max_seq) or max_seq
+        sbc_max_seq = sbc.get("max_seq_length") or None
         pre_lower = bool(sbc.get("do_lower_case", False))
     pc = os.path.join(pool_dir, "config.json")
     if os.path.exists(pc):
@@ -205,8 +305,12 @@ def _load_local_dir(path: str):
         elif modes not in ([], ["mean_tokens"]):
             raise NotImplementedError(f"pooling mode(s) {modes} are not supported (mean and CLS are)")
     model_type = cfg.get("model_type", "bert")
+    if model_type == "nomic_bert":
+        raw = load_file(os.path.join(tr_dir, "model.safetensors"))
+        shape, weights = _nomic_shape_and_weights(cfg, raw, pooling, sbc_max_seq)
+        return shape, weights, tokenizer_from_model_dir(tr_dir), pre_lower, has_normalize
     if model_type not in ("bert", "mpnet", "xlm-roberta"):
-        raise NotImplementedError(f"model_type '{model_type}' is not supported by this encoder (bert, mpnet and xlm-roberta are)")
+        raise NotImplementedError(f"model_type '{model_type}' is not supported by this encoder (bert, mpnet and xlm-roberta are, and nomic_bert)")
     rel_buckets = pos_offset = 0
     if model_type == "mpnet":
         rel_buckets = int(cfg.get("relative_attention_num_buckets", 32))
@@ -228,7 +332,7 @@ def _load_local_dir(path: str):
 
 
 class EmbeddingModel:
-    """Sentence encoder wrapper (BERT, MPNet and XLM-RoBERTa checkpoints) running on the GPU."""
+    """Sentence encoder wrapper (BERT, MPNet, XLM-RoBERTa and nomic-embed-text checkpoints) running on the GPU."""
 
     def __init__(self, config: dict):
         self.tokenize_mode = config.get('tokenize', 'host')     # additive key: 'device' = csrc/wordpiece.hip feeds the encoder
@@ -237,6 +341,9 @@ class EmbeddingModel:
         self.model_name = config.get('model_name', 'sentence-transformers/all-MiniLM-L6-v2')
         self.batch_size = config.get('batch_size', 32)
         self.normalize = config.get('normalize', True)
+        # additive keys: the task prefix of each kind of text ("" = none)
+        self.query_prefix = str(config.get('query_prefix', '') or '')
+        self.document_prefix = str(config.get('document_prefix', '') or '')
         self.device = self._get_device(config.get('device', 'cuda'))
         logger.info(f"Loading embedding model: {self.model_name}")
         self._pre_lower = False      # sentence_bert_config.json do_lower_case: an extra str.lower() before the tokenizer
@@ -290,10 +397,18 @@ class EmbeddingModel:
             f"set CRS_MODEL_DIR, or use 'synthetic:minilm' (models cannot be downloaded here)")
 
     # ---- encoding ------------------------------------------------------------------------------
-    def tokenize(self, texts: List[str]):
+    def _with_prefix(self, texts, kind: Optional[str]):
+        """texts with the prefix of `kind` (None | 'query' | 'document') in front; the list itself where there is none."""
+        if kind not in (None, 'query', 'document'):
+            raise ValueError(f"kind must be None, 'query' or 'document', got {kind!r}")
+        prefix = self.query_prefix if kind == 'query' else self.document_prefix if kind == 'document' else ''
+        return [prefix + str(t) for t in texts] if prefix else texts
+
+    def tokenize(self, texts: List[str], kind: Optional[str] = None):
         """-> list of id lists ([CLS] ... [SEP] or the model's own <s> ... </s>, truncated to max_seq).  Text is stripped (and lower-cased when the
-        model's sentence_bert_config.json says so) first, as sentence-transformers' Transformer.tokenize does."""
-        texts = [str(t).strip() for t in texts]
+        model's sentence_bert_config.json says so) first, as sentence-transformers' Transformer.tokenize does.  kind: the task
+        prefix put in front of every text first ('query' / 'document'; None: none)."""
+        texts = [str(t).strip() for t in self._with_prefix(texts, kind)]
         if self._pre_lower:
             texts = [t.lower() for t in texts]
         if hasattr(self.tokenizer, "encode_batch"):
@@ -311,13 +426,13 @@ class EmbeddingModel:
         return tokenize_on_device(self._device_tokenizer, self.tokenizer, dev, texts, self.shape.max_seq, self.tokenize,
                                   pre_lower=self._pre_lower, group_bytes=self.TOKENIZE_GROUP_BYTES, timings=timings)
 
-    def tokenize_device(self, texts: List[str]):
+    def tokenize_device(self, texts: List[str], kind: Optional[str] = None):
         """-> (ids cuda int32 [n, max_seq]: what self.tokenize gives, right-padded with the pad id; lens cuda int32 [n]), tokenised
-        by the device kernel whatever rag.embedding.tokenize says (additive)."""
+        by the device kernel whatever rag.embedding.tokenize says (additive).  kind: as tokenize."""
         import torch
         from rag._unigram import tokenizer_spec
         tokenizer_spec(self.tokenizer)
-        ids, lens = self._tokenize_device(list(texts))
+        ids, lens = self._tokenize_device(list(self._with_prefix(texts, kind)))
         return ids, torch.from_numpy(lens).to(ids.device)
 
     def _embed_device_tokens(self, texts: List[str], out):
@@ -365,11 +480,13 @@ class EmbeddingModel:
             cur.wait_stream(st)
         return out
 
-    def embed_device(self, texts: Union[str, List[str]]):
-        """Embeddings as a cuda fp32 tensor [n, d] in input order (additive, zero-copy index build)."""
+    def embed_device(self, texts: Union[str, List[str]], kind: Optional[str] = None):
+        """Embeddings as a cuda fp32 tensor [n, d] in input order (additive, zero-copy index build).  kind: the task prefix
+        put in front of every text ('query' / 'document'; None: none)."""
         import torch
         if isinstance(texts, str):
             texts = [texts]
+        texts = self._with_prefix(texts, kind)
         n = len(texts)
         out = torch.empty((n, self.dimension), dtype=torch.float32, device=self.model.device)
         if n == 0:
@@ -409,16 +526,16 @@ class EmbeddingModel:
             cur.wait_stream(st)
         return out
 
-    def embed(self, texts: Union[str, List[str]], show_progress: bool = False) -> np.ndarray:
-        """Embeddings for text(s): numpy float32 [n, d] (n = 1 for a single string)."""
-        return self.embed_device(texts).cpu().numpy()
+    def embed(self, texts: Union[str, List[str]], show_progress: bool = False, kind: Optional[str] = None) -> np.ndarray:
+        """Embeddings for text(s): numpy float32 [n, d] (n = 1 for a single string).  kind: as embed_device."""
+        return self.embed_device(texts, kind=kind).cpu().numpy()
 
     def embed_chunks(self, chunks: List[Chunk], show_progress: bool = True) -> np.ndarray:
-        return self.embed([chunk.text for chunk in chunks], show_progress=show_progress)
+        return self.embed([chunk.text for chunk in chunks], show_progress=show_progress, kind='document')
 
     def embed_chunks_device(self, chunks: List[Chunk], show_progress: bool = True):
         """embed_chunks without leaving the device (additive): cuda fp32 [n, d] for VectorStore.create_index."""
-        return self.embed_device([chunk.text for chunk in chunks])
+        return self.embed_device([chunk.text for chunk in chunks], kind='document')
 
     def get_dimension(self) -> int:
         return self.dimension

@@ -46,6 +46,12 @@ from rag.embedding import EmbeddingModel
 logger = logging.getLogger(__name__)
 
 
+def _kind(model, kind: str) -> dict:
+    """The `kind=` keyword ('query' for questions, 'document' for chunk texts) for embedding models that know task prefixes
+    (rag.embedding.EmbeddingModel: query_prefix / document_prefix); nothing for a duck-typed model that does not."""
+    return {'kind': kind} if hasattr(model, 'query_prefix') else {}
+
+
 class ContextRetriever:
     """Retrieve relevant context for queries (with re-ranking and diversity mechanisms)."""
 
@@ -237,7 +243,7 @@ class ContextRetriever:
         if self.late_interaction is not None and self.rerank and filters is None:
             return self.retrieve_batch([query], top_k=top_k)[0]
         try:
-            query_embedding = self.embedding_model.embed(query)
+            query_embedding = self.embedding_model.embed(query, **_kind(self.embedding_model, 'query'))
             results = self.vector_store.search(query_embedding=query_embedding,
                                                top_k=k * 2 if self.rerank else k, where=filters)
             if not results['ids'][0]:
@@ -284,12 +290,13 @@ class ContextRetriever:
         qb = self.batch_queries
         eng = None
         if len(queries) >= qb and hasattr(store, 'engine_view') and store.collection is not None and store.collection.count() > 0:
-            token_ids = model.tokenize(list(queries))
+            token_ids = model.tokenize(list(queries), **_kind(model, 'query'))
             longest = max(len(t) for t in token_ids)
             seq = next((st for st in (16, 32, 64) if longest <= st and st <= model.shape.max_seq), None)
             eng = self._engine_for(min(fetch, store.collection.count()), seq, -(-len(queries) // qb)) if seq else None
         if eng is None:                       # general path: one encoder pass + one search launch for the whole list
-            emb = model.embed_device(list(queries)) if hasattr(model, "embed_device") else model.embed(list(queries))
+            emb = (model.embed_device(list(queries), **_kind(model, 'query')) if hasattr(model, "embed_device")
+                   else model.embed(list(queries), **_kind(model, 'query')))
             if not hasattr(store, "search_rows"):          # any store with the additive search_batch (duck-typed)
                 yield store.search_batch(emb, top_k=fetch)
                 return
@@ -447,7 +454,7 @@ class ContextRetriever:
                             index[c['text']] = len(texts)
                             texts.append(c['text'])
             if texts:
-                vectors = self.embedding_model.embed(texts)
+                vectors = self.embedding_model.embed(texts, **_kind(self.embedding_model, 'document'))
                 per_query = [self._apply_diversity(chunks, vectors=vectors[[index[c['text']] for c in chunks]])
                              if len(chunks) > 1 else chunks for chunks in per_query]
         return per_query
@@ -661,7 +668,7 @@ class ContextRetriever:
             return chunks
         lam = 1.0 - self.diversity_penalty
         if vectors is None:
-            vectors = self.embedding_model.embed([c['text'] for c in chunks])
+            vectors = self.embedding_model.embed([c['text'] for c in chunks], **_kind(self.embedding_model, 'document'))
         norms = [np.linalg.norm(v) for v in vectors]
         order = [0]
         pending = list(range(1, len(chunks)))

@@ -45,6 +45,27 @@ typedef struct crs_encoder_desc {
  * the forward runs alone. */
 #define CRS_ENC_SMALL_LDS 1
 
+/* Rotary encoders (nomic-embed-text; additive to ABI 3).
+ * CRS_ENC_ROTARY: no learned position table (weights->pos_emb may be NULL: no position row is added at the embedding step);
+ * instead one rope_qk_kernel launch between the QKV projection and attention rotates the Q and K column blocks of the
+ * [T, 3H] fp16 QKV buffer in place, per head, "rotate-half" form (not interleaved), over the whole head dimension:
+ *     t'[j]          = t[j]          * cos[pos, j] - t[j + hd/2] * sin[pos, j]          j < hd/2
+ *     t'[j + hd/2]   = t[j + hd/2]   * cos[pos, j] + t[j]        * sin[pos, j]
+ * read as fp16, computed in fp32, rounded once to fp16; V is not touched.  pos is the token's index in its sequence.  The
+ * table is crs_encoder_rope.table_dev: fp32 [positions, hd], row pos holding cos(pos * theta^(-2 j / hd)) for j < hd/2 in
+ * its first half and the sines of the same angles in its second half (built on the host in fp64, rounded once to fp32).
+ * The flag needs one of the _rope entry points with a table of positions >= seq; it excludes a relative-position bias, and
+ * the fused QKV + attention kernel is never selected.  The kernel uses no LDS (CRS_ENC_SMALL_LDS is honoured; under that flag
+ * mode 4 runs the panel kernel's <= 48 KB form, except at a hidden size that kernel has no chunk for -- no multiple of 128 --
+ * where FFN-up falls to the tiled kernel and its 64 KB of static LDS, as modes 0 / 1 do).
+ * CRS_ENC_GATED_SILU: the feed-forward block is gated (SwiGLU): x <- LayerNorm(x + (silu(x Wgate^T + bg) * (x Wup^T + bu)) Wdown^T + b).
+ * w_up is then fp16 [2F, H] and b_up fp32 [2F] or NULL, gate and up rows INTERLEAVED IN BLOCKS OF 16: for every block b of
+ * 16 output columns, rows [32 b, 32 b + 16) are rows [16 b, 16 b + 16) of Wgate (the half SiLU acts on) and rows
+ * [32 b + 16, 32 b + 32) are the same rows of Wup; b_up likewise.  The FFN-up projection runs GEMM mode 4 (below); the
+ * [T, 2F] product never exists in memory and the workspace is unchanged.  ffn must be a multiple of 64. */
+#define CRS_ENC_ROTARY 2
+#define CRS_ENC_GATED_SILU 4
+
 /* Per-layer device pointers.  Matrices are fp16 row-major [out_features, in_features] exactly as
  * torch.nn.Linear stores them (y = x W^T + b); vectors are fp32. */
 typedef struct crs_encoder_layer {
@@ -113,6 +134,30 @@ int crs_encoder_forward_queries_ex(const crs_encoder_desc* d, const crs_encoder_
                                    size_t workspace_bytes, float* out_dev, void* q16_out_dev, int slab_type,
                                    void* stream, const crs_encoder_ext* ext);
 
+/* The forwards above for descriptors with CRS_ENC_ROTARY (they also serve every other descriptor: a NULL rope, or a NULL
+ * table in it, is exactly the _ex entry).  CRS_EINVAL, with a message and before any launch: CRS_ENC_ROTARY without a
+ * table, positions < seq, CRS_ENC_ROTARY together with a relative-position bias.  The other entry points of this file refuse
+ * a CRS_ENC_ROTARY descriptor (they carry no table). */
+typedef struct crs_encoder_rope {
+  const float* table_dev;   /* fp32 [positions, head_dim]: cos half | sin half (CRS_ENC_ROTARY above) */
+  int32_t positions;
+} crs_encoder_rope;
+
+int crs_encoder_forward_rope(const crs_encoder_desc* d, const crs_encoder_weights* w, const int32_t* ids_dev,
+                             const int32_t* lens_dev, int batch, int seq, void* workspace_dev,
+                             size_t workspace_bytes, float* out_dev, int normalize, float* hidden_out_dev,
+                             void* stream, const crs_encoder_ext* ext, const crs_encoder_rope* rope);
+
+int crs_encoder_forward_queries_rope(const crs_encoder_desc* d, const crs_encoder_weights* w, const int32_t* ids_dev,
+                                     const int32_t* lens_dev, int batch, int seq, void* workspace_dev,
+                                     size_t workspace_bytes, float* out_dev, void* q16_out_dev, int slab_type,
+                                     void* stream, const crs_encoder_ext* ext, const crs_encoder_rope* rope);
+
+/* Test-facing (additive to ABI 3): the rotation step on its own.  qkv_dev: fp16 [batch * seq, 3 * hidden], rotated in place in
+ * its Q and K column blocks (columns [0, 2 * hidden)); table_dev / positions as crs_encoder_rope.  CRS_EINVAL: a NULL or
+ * misaligned (16 bytes) pointer, head_dim not 16 / 32 / 64, batch or seq < 1, positions < seq. */
+int crs_rope_qk_f16(void* qkv_dev, const float* table_dev, int positions, int batch, int seq, int hidden, int heads, void* stream);
+
 /* Sentence-pair scoring (cross-encoder re-ranking): BertForSequenceClassification with one label.  The rows of ids_dev hold
  * "[CLS] a [SEP] b [SEP]" (tokenised and truncated on the host), type_ids_dev int32 [batch, seq] names the token-type row of every
  * token (0 for "[CLS] a [SEP]", 1 for "b [SEP]", anything for padding; values outside [0, type_rows) are clamped, as token ids
@@ -148,6 +193,11 @@ int crs_encoder_plan_describe(const crs_encoder_desc* d, int batch, int seq, int
 /* Building block exported for parity tests and for users with their own layer stack:
  *   C[M, N] = epilogue(A[M, K] (fp16) x W[N, K]^T (fp16) + bias[N])
  *   mode 0: fp16 out;  mode 1: erf-GELU, fp16 out;  mode 2: + residual fp32 [M, N], fp32 out.
+ *   (crs_gemm_f16_routed only) mode 4, the gated epilogue: W has n rows in the interleaved gate / up layout of CRS_ENC_GATED_SILU
+ *   and the output is fp16 [M, n / 2]:  out[m, j] = fp16(silu(acc[m, g] + bias[g]) * (acc[m, g + 16] + bias[g + 16])),
+ *   g = 32 (j / 16) + j % 16, silu(x) = x / (1 + exp(-x)) in fp32, one rounding; bias fp32 [n] or NULL; n even and n / 2 a
+ *   multiple of 32 (CRS_EINVAL otherwise).  Routes 0 (the phase-scheduled 256 x 256 kernel where plan_gemm takes it for
+ *   modes 0 / 1, else the tiled 128 x 128 kernel; never the 256-row or row-streaming kernels) and 1 (the panel kernel).
  * Any n > 0: every kernel family makes its 16-byte epilogue accesses only where n keeps the rows 16-byte aligned (a multiple of 8
  * for fp16 outputs, of 4 for fp32 ones) and goes element by element otherwise.  K a multiple of 64; all pointers 16-byte aligned
  * (CRS_EINVAL otherwise).  This is crs_gemm_f16_routed with route 0 and flags 0. */
@@ -158,7 +208,7 @@ int crs_gemm_f16(const void* a_dev, const void* w_dev, const float* bias_dev, co
  * can be run on its own.  route 0: plan_gemm (modes 0..2: the phase-scheduled 256 x 256 kernel, the 256-row pipelined kernel, the
  * row-streaming kernels or the tiled 128 x 128 kernel, by the sizes, the CU count and the CRS_* knobs); route 1: plan_gemm_panel, the
  * panel kernel, modes 0 / 1 / 3, K a multiple of 128; route 2: the split-K form of the 256 x 256 kernel, mode 3 only, CRS_EINVAL for
- * a shape that form does not take (csrc/enc_plan.cpp: gemm8_splitk).  flags & 1: the small-LDS forms (CRS_ENC_SMALL_LDS).
+ * a shape that form does not take (csrc/enc_plan.cpp: gemm8_splitk).  Mode 4 (above): routes 0 and 1.  flags & 1: the small-LDS forms (CRS_ENC_SMALL_LDS).
  * mode 3 takes no bias (bias_dev must be NULL) and writes the raw fp32 partial products as out_dev[slabs][m][n]; slab z of the
  * panel kernel holds the contraction over columns [z * K / slabs, (z + 1) * K / slabs) of K, and so does slab z of the 256 x 256
  * kernel; crs_gemm_plan_describe answers the slab count.  The entry only chooses which planner function makes the plan; the

@@ -6,7 +6,9 @@
 // split-K plan, family None where it does not apply)
 // The knobs come from the environment (CRS_GEMM8=0 ./enc_plan_table 256 ...), as in the library.  One line per case: key=value
 // fields separated by blanks, a tab, and the describe text with ';' for its line ends.  A GEMM step's fields are
-// family/slabs/tm/kc/kin/persist/items/ksplit/colblocks/streams.  tests/test_enc_plan_cpu.py drives it, built with
+// family/slabs/tm/kc/kin/persist/items/ksplit/colblocks/streams.  flags: 1 small LDS, 2 rotary (a rope_wgs field and the
+// rope_qk_kernel line are added), 4 gated (the up step is mode 4 over 2 ffn rows); gemm / route take mode 4 too (n = 2 ffn).
+// tests/test_enc_plan_cpu.py drives it, built with
 // -fsanitize=address,undefined.
 #include <stdio.h>
 #include <stdlib.h>
@@ -74,6 +76,7 @@ int main(int argc, char** argv) {
     printf("out_rowln2=%d down_rowln2=%d rowln2_variant=%d ", (int)p.out.rowln2, (int)p.down.rowln2, p.out.rowln2 ? p.out.variant : p.down.variant);
     gemm_fields("out", p.out.gemm);
     gemm_fields("down", p.down.gemm);
+    if (p.rotary) printf("rope_wgs=%d ", p.rope.gx);
     const int need = crs::enc_plan_describe(p, text, sizeof text);
     if (need >= (int)sizeof text) return 3;
     text_out(text);
