@@ -122,6 +122,22 @@ int check_proj_ln(int tokens, int hidden, int k) {
   return CRS_OK;
 }
 
+// the attention step on its own (crs_attention_f16, crs_qkv_attn_f16): what both refuse by the sizes, and the knobs of a route
+const char* attn_sizes_refusal(int batch, int seq, int hidden, int heads) {
+  if (heads < 1 || hidden < 1 || hidden % heads) return "attention: hidden must divide by heads";
+  const int hd = hidden / heads;
+  if (hd != 16 && hd != 32 && hd != 64) return "attention: head_dim must be 16, 32 or 64";
+  if (batch < 1 || batch > 65535) return "attention: batch must be in [1, 65535]";
+  if (seq < 1) return "attention: seq must be >= 1";
+  return nullptr;
+}
+
+const char* attn_bias_refusal(int seq, int rel_span) {
+  return (seq > crs::forms::kAttnMaxBiasSeq || rel_span < seq) ? "attention: a relative bias needs seq <= 512 and rel_span >= seq" : nullptr;
+}
+
+crs::EncKnobs attn_knobs(int route) { return route < 0 ? knobs() : crs::attn_route_knobs(route); }
+
 }  // namespace
 
 extern "C" {
@@ -352,6 +368,49 @@ int crs_rope_qk_f16(void* qkv_dev, const float* table_dev, int positions, int ba
   if ((long)batch * seq > (1L << 24)) return crs::set_error(CRS_EINVAL, "rope: more than 2^24 tokens");
   CRS_TRY(crs::rope_qk_launch(crs::plan_rope(batch * seq, hidden), hd, (_Float16*)qkv_dev, table_dev, batch * seq, seq, hidden, (hipStream_t)stream), "rope");
   return CRS_OK;
+}
+
+// ---- the attention step on its own: the plan is plan_attention's (or plan_qkv_attn's), the launch attention_launch's ----
+int crs_attention_f16(const void* qkv_dev, const int32_t* lens_dev, void* ctx_dev, int batch, int seq, int hidden, int heads,
+                      const float* rel_bias_dev, int rel_span, int route, void* stream) {
+  if (!qkv_dev || !lens_dev || !ctx_dev) return crs::set_error(CRS_EINVAL, "attention: null pointer");
+  if (((uintptr_t)qkv_dev | (uintptr_t)lens_dev | (uintptr_t)ctx_dev | (uintptr_t)rel_bias_dev) & 15)
+    return crs::set_error(CRS_EINVAL, "attention pointers must be 16-byte aligned");
+  const char* why = attn_sizes_refusal(batch, seq, hidden, heads);
+  if (!why && rel_bias_dev) why = attn_bias_refusal(seq, rel_span);
+  if (!why && route > 15) why = "attention: route must be < 0 (the process's knobs) or a sum of 1, 2, 4, 8";
+  if (why) return crs::set_error(CRS_EINVAL, why);
+  const crs::AttnPlan p = crs::plan_attention(batch, seq, heads, hidden / heads, rel_bias_dev != nullptr, attn_knobs(route));
+  CRS_TRY(crs::attention_launch(p, (const _Float16*)qkv_dev, lens_dev, (_Float16*)ctx_dev, batch, seq, hidden, heads, rel_bias_dev,
+                                rel_bias_dev ? rel_span : 0, (hipStream_t)stream), "attention");
+  return CRS_OK;
+}
+
+int crs_qkv_attn_f16(const void* x16_dev, const void* w_qkv_dev, const float* b_qkv_dev, const int32_t* lens_dev, void* ctx_dev,
+                     int batch, int seq, int hidden, int heads, void* stream) {
+  if (!x16_dev || !w_qkv_dev || !b_qkv_dev || !lens_dev || !ctx_dev) return crs::set_error(CRS_EINVAL, "qkv + attention: null pointer");
+  if (((uintptr_t)x16_dev | (uintptr_t)w_qkv_dev | (uintptr_t)b_qkv_dev | (uintptr_t)lens_dev | (uintptr_t)ctx_dev) & 15)
+    return crs::set_error(CRS_EINVAL, "qkv + attention pointers must be 16-byte aligned");
+  const char* why = attn_sizes_refusal(batch, seq, hidden, heads);
+  if (!why && (!crs::qkv_attn_supported(hidden, heads, seq) || (long)batch * seq > 4096))
+    why = "qkv + attention: hidden 128 / 256 / 384, head_dim 32 / 64 within the LDS image, seq 16 / 32 / 64, batch * seq <= 4096";
+  if (why) return crs::set_error(CRS_EINVAL, why);
+  const crs::AttnPlan p = crs::plan_qkv_attn(batch * seq, hidden, heads);
+  CRS_TRY(crs::qkv_attn_launch(p, (const _Float16*)x16_dev, (const _Float16*)w_qkv_dev, b_qkv_dev, lens_dev, (_Float16*)ctx_dev,
+                               batch * seq, seq, hidden, (hipStream_t)stream), "qkv + attention");
+  return CRS_OK;
+}
+
+int crs_attention_plan_describe(int batch, int seq, int hidden, int heads, int rel_bias, int route, char* buf, size_t cap) {
+  if (cap && !buf) return crs::set_error(CRS_EINVAL, "plan describe: null buffer");
+  const char* why = attn_sizes_refusal(batch, seq, hidden, heads);
+  if (!why && route > 16) why = "attention: route must be < 0, a sum of 1, 2, 4, 8, or 16 (crs_qkv_attn_f16's launch)";
+  if (!why && route == 16 && (rel_bias || !crs::qkv_attn_supported(hidden, heads, seq) || (long)batch * seq > 4096))
+    why = "qkv + attention: no bias, hidden 128 / 256 / 384, head_dim 32 / 64 within the LDS image, seq 16 / 32 / 64, batch * seq <= 4096";
+  if (!why && route != 16 && rel_bias && seq > crs::forms::kAttnMaxBiasSeq) why = "attention: a relative bias needs seq <= 512";
+  if (why) return crs::set_error(CRS_EINVAL, why);
+  if (route == 16) return crs::attn_plan_describe(crs::plan_qkv_attn(batch * seq, hidden, heads), buf, cap);
+  return crs::attn_plan_describe(crs::plan_attention(batch, seq, heads, hidden / heads, rel_bias != 0, attn_knobs(route)), buf, cap);
 }
 
 int crs_encoder_forward_queries(const crs_encoder_desc* d, const crs_encoder_weights* w, const int32_t* ids_dev,

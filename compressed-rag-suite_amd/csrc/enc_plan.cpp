@@ -143,6 +143,8 @@ GemmPlan plan_stream(int m, int n, int k, int mode, int cus) {
   return p;
 }
 
+}  // namespace
+
 AttnPlan plan_attention(int batch, int seq, int heads, int hd, bool bias, const EncKnobs& kn) {
   AttnPlan a;
   a.hd = hd;
@@ -170,7 +172,12 @@ bool qkv_attn_supported(int hidden, int heads, int seq) {
   return seq == 16 || seq == 32 || seq == 64;
 }
 
-}  // namespace
+AttnPlan plan_qkv_attn(int tokens, int hidden, int heads) {
+  AttnPlan a;
+  a.form = AttnForm::Fused, a.hd = hidden / heads;
+  a.d = {cdiv(tokens, kQaTokens), heads, 1, kQaThreads, qa_lds(hidden, a.hd)};
+  return a;
+}
 
 Dims plan_rope(int tokens, int hidden) {
   return {(int)((rope_items(tokens, hidden) + kRopeThreads - 1) / kRopeThreads), 1, 1, kRopeThreads, 0};
@@ -265,8 +272,7 @@ EncPlan make_enc_plan(int hidden, int heads, int ffn, int flags, int batch, int 
   // short sequences in the launch-bound regime: QKV projection + attention as one kernel (enc_qkvattn.hip)
   // (never for a rotary model: the rotation runs between the projection and attention)
   if (!rel_bias && !p.rotary && T <= kPanelMaxTokens && !small && kn.qkvattn && qkv_attn_supported(H, heads, seq)) {
-    p.attn.form = AttnForm::Fused, p.attn.hd = hd;
-    p.attn.d = {cdiv(T, kQaTokens), heads, 1, kQaThreads, qa_lds(H, hd)};
+    p.attn = plan_qkv_attn(T, H, heads);
   } else {
     p.qkv = single_h ? plan_gemm_panel(T, 3 * H, H, 0, small, kn) : plan_gemm(T, 3 * H, H, 0, small, cus, kn);
     p.attn = plan_attention(batch, seq, heads, hd, rel_bias != 0, kn);
@@ -330,6 +336,16 @@ void gemm_line(Text& t, const GemmPlan& g) {
   }
 }
 
+void attn_line(Text& t, const AttnPlan& a) {
+  switch (a.form) {
+    case AttnForm::Fused: t.line(a.d, "qkv_attn_kernel<%d>", a.hd); break;
+    case AttnForm::Blocked: t.line(a.d, "attention_kernel<%d, %s>", a.hd, a.bias ? "true" : "false"); break;
+    case AttnForm::Short: t.line(a.d, "attention_short_kernel<%d>", a.hd); break;
+    case AttnForm::Seq: t.line(a.d, "attention_seq_kernel<%d, %d, %d>", a.hd, a.smax, a.nw); break;
+    case AttnForm::Seq32: t.line(a.d, "attention_seq32_kernel<%d, %d, %d, %d>", a.hd, a.smax, a.nw, a.qt); break;
+  }
+}
+
 void proj_ln_lines(Text& t, const ProjLnPlan& s, int hidden) {
   if (s.rowln2) { t.line(s.d, s.variant ? "gemm_rowln2_kernel<64, 2>" : "gemm_rowln2_kernel<32, 4>"); return; }
   gemm_line(t, s.gemm);
@@ -350,20 +366,28 @@ int proj_ln_plan_describe(const ProjLnPlan& p, int hidden, char* buf, size_t cap
   return t.len;
 }
 
+int attn_plan_describe(const AttnPlan& p, char* buf, size_t cap) {
+  Text t{buf, cap};
+  attn_line(t, p);
+  return t.len;
+}
+
+EncKnobs attn_route_knobs(int route) {
+  EncKnobs k;
+  if (route & 1) k.attn_seq = false;
+  if (route & 2) k.attn_short = false;
+  if (route & 4) k.attn_x32 = false;
+  if (route & 8) k.attn_qt4 = true;
+  return k;
+}
+
 int enc_plan_describe(const EncPlan& p, char* buf, size_t cap) {
   Text t{buf, cap};
   const char* two = row_form2(p.hidden) ? "2" : "";
   t.line(p.embed, "embed_ln%s_kernel<%d, %s>", two, row_form(p.hidden), p.typed ? "true" : "false");
   gemm_line(t, p.qkv);
   if (p.rotary) t.line(p.rope, "rope_qk_kernel<%d>", p.attn.hd);
-  const AttnPlan& a = p.attn;
-  switch (a.form) {
-    case AttnForm::Fused: t.line(a.d, "qkv_attn_kernel<%d>", a.hd); break;
-    case AttnForm::Blocked: t.line(a.d, "attention_kernel<%d, %s>", a.hd, a.bias ? "true" : "false"); break;
-    case AttnForm::Short: t.line(a.d, "attention_short_kernel<%d>", a.hd); break;
-    case AttnForm::Seq: t.line(a.d, "attention_seq_kernel<%d, %d, %d>", a.hd, a.smax, a.nw); break;
-    case AttnForm::Seq32: t.line(a.d, "attention_seq32_kernel<%d, %d, %d, %d>", a.hd, a.smax, a.nw, a.qt); break;
-  }
+  attn_line(t, p.attn);
   proj_ln_lines(t, p.out, p.hidden);
   gemm_line(t, p.up);
   proj_ln_lines(t, p.down, p.hidden);

@@ -74,6 +74,18 @@ struct AttnPlan {
   Dims d;
 };
 
+// What the forward's attention step runs on when it is not Fused (crs_attention_f16 launches exactly this): the blocked kernel with
+// a bias at every length; else the short kernel up to 16 tokens (head_dim 32 / 64), a whole-sequence kernel from 65 tokens up to the
+// length its LDS image holds (256, or 512 at head_dim 64), the blocked kernel otherwise -- as the attn_* knobs allow.
+AttnPlan plan_attention(int batch, int seq, int heads, int hd, bool bias, const EncKnobs& kn);
+// The shapes qkv_attn_kernel takes (hidden a multiple of 128 up to 384, head_dim 32 / 64, its LDS image within kMaxLds, 16 / 32 / 64
+// tokens per sequence) and its plan, the one make_enc_plan puts into EncPlan::attn; the caller checked qkv_attn_supported.
+bool qkv_attn_supported(int hidden, int heads, int seq);
+AttnPlan plan_qkv_attn(int tokens, int hidden, int heads);
+// Default knobs with the attention bits of a test route applied: 1 attn_seq off, 2 attn_short off, 4 attn_x32 off, 8 attn_qt4 on
+// (include/crs_encoder.h: crs_attention_f16).
+EncKnobs attn_route_knobs(int route);
+
 // out-projection / FFN-down + LayerNorm: one rowln2 launch, or a GEMM and the LayerNorm summing its slabs
 struct ProjLnPlan {
   bool rowln2 = false;
@@ -114,6 +126,7 @@ EncPlan make_enc_plan(int hidden, int heads, int ffn, int flags, int batch, int 
 // (grid in workgroups, dynamic LDS).  Returns the length of the whole text (snprintf): > cap - 1 means it was cut.
 int gemm_plan_describe(const GemmPlan& p, char* buf, size_t cap);
 int proj_ln_plan_describe(const ProjLnPlan& p, int hidden, char* buf, size_t cap);   // rowln2: one line; else the GEMM's and the LayerNorm's
+int attn_plan_describe(const AttnPlan& p, char* buf, size_t cap);                    // the attention step's line, any form
 int enc_plan_describe(const EncPlan& p, char* buf, size_t cap);
 
 }  // namespace crs

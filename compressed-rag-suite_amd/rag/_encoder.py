@@ -91,6 +91,10 @@ nat.register_signatures({
                                                  c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_void_p,
                                                  POINTER(EncoderExt), POINTER(EncoderRope)]),
     "crs_rope_qk_f16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    # test-facing: the attention step / the fused QKV + attention kernel on its own
+    "crs_attention_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "crs_qkv_attn_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "crs_attention_plan_describe": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t]),
 })
 
 
@@ -205,6 +209,31 @@ def gemm_f16_routed(a, w, bias, residual, out, mode: int, route: int = 0, flags:
     m, k = a.shape
     nat.check(nat.load().crs_gemm_f16_routed(nat._ptr(a), nat._ptr(w), nat._ptr(bias), nat._ptr(residual), nat._ptr(out),
                                              m, w.shape[0], k, mode, route, flags, nat._stream_ptr()))
+
+
+ATTN_ROUTE_FUSED = 16  # attention_plan_describe only: the launch of qkv_attn_f16
+
+
+def attention_plan_describe(batch: int, seq: int, hidden: int, heads: int, rel_bias: bool = False, route: int = -1) -> str:
+    """The launch line of attention_f16 (route 16: of qkv_attn_f16) for these sizes (crs_attention_plan_describe); needs no device."""
+    lib = nat.load()
+    return _describe(lambda sl, buf, cap: lib.crs_attention_plan_describe(batch, seq, hidden, heads, int(bool(rel_bias)), route, buf, cap))[0]
+
+
+def attention_f16(qkv, lens, ctx, batch: int, seq: int, heads: int, rel_bias=None, route: int = -1) -> None:
+    """crs_attention_f16: ctx (cuda fp16 [batch * seq, H]) <- attention of qkv (cuda fp16 [batch * seq, 3 H]) under lens (cuda int32
+    [batch]); rel_bias: cuda fp32 [heads, 2 span - 1] or None; route < 0 the process's knobs, else bits 1 attn_seq off, 2 attn_short
+    off, 4 attn_x32 off, 8 attn_qt4 on over the defaults."""
+    span = (int(rel_bias.shape[1]) + 1) // 2 if rel_bias is not None else 0
+    nat.check(nat.load().crs_attention_f16(nat._ptr(qkv), nat._ptr(lens), nat._ptr(ctx), int(batch), int(seq), int(qkv.shape[1]) // 3,
+                                           int(heads), nat._ptr(rel_bias), span, int(route), nat._stream_ptr()))
+
+
+def qkv_attn_f16(x16, w_qkv, b_qkv, lens, ctx, batch: int, seq: int, heads: int) -> None:
+    """crs_qkv_attn_f16: ctx (cuda fp16 [batch * seq, H]) <- attention of the projection x16 w_qkv^T + b_qkv in one kernel; x16 cuda
+    fp16 [batch * seq, H], w_qkv cuda fp16 [3 H, H], b_qkv cuda fp32 [3 H]."""
+    nat.check(nat.load().crs_qkv_attn_f16(nat._ptr(x16), nat._ptr(w_qkv), nat._ptr(b_qkv), nat._ptr(lens), nat._ptr(ctx), int(batch),
+                                          int(seq), int(x16.shape[1]), int(heads), nat._stream_ptr()))
 
 
 def rope_qk_f16(qkv, table, batch: int, seq: int, heads: int) -> None:

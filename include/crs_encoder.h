@@ -158,6 +158,33 @@ int crs_encoder_forward_queries_rope(const crs_encoder_desc* d, const crs_encode
  * misaligned (16 bytes) pointer, head_dim not 16 / 32 / 64, batch or seq < 1, positions < seq. */
 int crs_rope_qk_f16(void* qkv_dev, const float* table_dev, int positions, int batch, int seq, int hidden, int heads, void* stream);
 
+/* Test-facing (additive to ABI 3): the attention step on its own, exactly as the forward launches it,
+ *   ctx[b, s, h*hd : (h+1)*hd] = softmax(Q K^T / sqrt(hd) + bias[h][key - query] + padding mask) V       per (batch, head)
+ * qkv_dev: fp16 [batch * seq, 3 * hidden] (Q | K | V column blocks), only read; lens_dev: int32 [batch], clamped to [1, seq]; ctx_dev:
+ * fp16 [batch * seq, hidden], every row written (a padding query attends the real keys).  rel_bias_dev (may be NULL: no bias):
+ * fp32 [heads, 2 * rel_span - 1] as crs_encoder_ext takes it.  The kernel is the one the planner answers (csrc/enc_plan.h:
+ * plan_attention) for these sizes and knobs, and the entry decides nothing else, so no kernel starts at a shape the planner would
+ * not give it.  route < 0: the process's CRS_ATTN_* knobs; route >= 0: the default knobs with these bits applied -- 1 no
+ * whole-sequence kernels, 2 no short kernel, 4 the 16-deep whole-sequence kernel, 8 four query tiles per wave -- so that every
+ * form is reachable in one process.  With a bias every route gives the blocked kernel.
+ * CRS_EINVAL before any launch: a NULL qkv / lens / ctx, a pointer that is not 16-byte aligned, hidden % heads != 0, head_dim not
+ * 16 / 32 / 64, batch outside [1, 65535], seq < 1, route > 15, a bias with seq > 512 or rel_span < seq. */
+int crs_attention_f16(const void* qkv_dev, const int32_t* lens_dev, void* ctx_dev, int batch, int seq, int hidden, int heads,
+                      const float* rel_bias_dev, int rel_span, int route, void* stream);
+
+/* Test-facing (additive to ABI 3): the fused QKV projection + attention kernel of short sequences on its own, with the plan the
+ * forward makes for it.  x16_dev: fp16 [batch * seq, hidden]; w_qkv_dev: fp16 [3 * hidden, hidden]; b_qkv_dev: fp32 [3 * hidden];
+ * ctx_dev: fp16 [batch * seq, hidden].  It launches only where the forward may: hidden 128 / 256 / 384 with head_dim 32 / 64 whose
+ * LDS image fits (csrc/enc_plan.h: qkv_attn_supported), seq 16 / 32 / 64, batch * seq <= 4096; CRS_EINVAL otherwise, and for the
+ * pointer, batch, seq and head_dim conditions of crs_attention_f16. */
+int crs_qkv_attn_f16(const void* x16_dev, const void* w_qkv_dev, const float* b_qkv_dev, const int32_t* lens_dev, void* ctx_dev,
+                     int batch, int seq, int hidden, int heads, void* stream);
+
+/* The launch crs_attention_f16 would make (route as there; rel_bias != 0: with a bias), as one line of crs_encoder_plan_describe's
+ * form; route 16: the launch of crs_qkv_attn_f16.  The grid depends on batch, heads and seq alone: it needs no device.  Returns the
+ * length of the text as snprintf does, or a negative error code (CRS_EINVAL where the launching entry would refuse the sizes). */
+int crs_attention_plan_describe(int batch, int seq, int hidden, int heads, int rel_bias, int route, char* buf, size_t cap);
+
 /* Sentence-pair scoring (cross-encoder re-ranking): BertForSequenceClassification with one label.  The rows of ids_dev hold
  * "[CLS] a [SEP] b [SEP]" (tokenised and truncated on the host), type_ids_dev int32 [batch, seq] names the token-type row of every
  * token (0 for "[CLS] a [SEP]", 1 for "b [SEP]", anything for padding; values outside [0, type_rows) are clamped, as token ids

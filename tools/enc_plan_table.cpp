@@ -2,6 +2,9 @@
 //   g++ -O1 -std=c++17 -o enc_plan_table tools/enc_plan_table.cpp compressed-rag-suite_amd/csrc/enc_plan.cpp
 //   ./enc_plan_table <CUs> < cases      one case per line:  fwd hidden heads ffn flags batch seq rel_bias pair  |  gemm m n k mode
 //                                        |  route m n k mode route flags  |  projln tokens hidden k flags big_ln
+//                                        |  attn batch seq hidden heads rel_bias route
+// (attn: the line crs_attention_plan_describe answers: route < 0 the environment's knobs, else default knobs with bits 1 attn_seq off,
+// 2 attn_short off, 4 attn_x32 off, 8 attn_qt4 on; 16 the fused QKV + attention kernel's launch)
 // (route, projln: what crs_gemm_plan_describe and crs_proj_ln_plan_describe answer; route 0 plan_gemm, 1 plan_gemm_panel, 2 the gemm8
 // split-K plan, family None where it does not apply)
 // The knobs come from the environment (CRS_GEMM8=0 ./enc_plan_table 256 ...), as in the library.  One line per case: key=value
@@ -64,6 +67,21 @@ int main(int argc, char** argv) {
       printf("rowln2=%d variant=%d ", (int)s.rowln2, s.variant);
       gemm_fields("gemm", s.gemm);
       crs::proj_ln_plan_describe(s, hid, text, sizeof text);
+      text_out(text);
+      continue;
+    }
+    if (!strcmp(kind, "attn")) {
+      int batch, seq, hid, hds, rel, route;
+      if (scanf("%d %d %d %d %d %d", &batch, &seq, &hid, &hds, &rel, &route) != 6 || hds < 1 || hid % hds) return 2;
+      crs::AttnPlan a;
+      if (route == 16) {
+        if (!crs::qkv_attn_supported(hid, hds, seq) || (long)batch * seq > 4096) return 2;
+        a = crs::plan_qkv_attn(batch * seq, hid, hds);
+      } else {
+        a = crs::plan_attention(batch, seq, hds, hid / hds, rel != 0, route < 0 ? kn : crs::attn_route_knobs(route));
+      }
+      printf("attn=%s attn_lds=%d attn_wgs=%ld ", kAttn[(int)a.form], a.d.lds, (long)a.d.gx * a.d.gy * a.d.gz);
+      crs::attn_plan_describe(a, text, sizeof text);
       text_out(text);
       continue;
     }
