@@ -19,6 +19,8 @@
 
 #include <stdio.h>
 
+#include <initializer_list>
+
 #include "enc.h"
 #include "mlm_plan.h"
 
@@ -137,6 +139,18 @@ const char* attn_bias_refusal(int seq, int rel_span) {
 }
 
 crs::EncKnobs attn_knobs(int route) { return route < 0 ? knobs() : crs::attn_route_knobs(route); }
+
+// the row kernels on their own (crs_embed_ln_f32, crs_layernorm_f32, crs_pool_f32, crs_pair_head_f32): the hidden sizes they are
+// written for, and the alignment of every pointer given (a null optional pointer passes)
+const char* row_hidden_refusal(int hidden) {
+  return (hidden <= 0 || hidden > 1024 || hidden % 64) ? "hidden must be a multiple of 64, <= 1024" : nullptr;
+}
+
+bool row_misaligned(std::initializer_list<const void*> ptrs) {
+  uintptr_t bits = 0;
+  for (const void* p : ptrs) bits |= (uintptr_t)p;
+  return (bits & 15) != 0;
+}
 
 }  // namespace
 
@@ -411,6 +425,76 @@ int crs_attention_plan_describe(int batch, int seq, int hidden, int heads, int r
   if (why) return crs::set_error(CRS_EINVAL, why);
   if (route == 16) return crs::attn_plan_describe(crs::plan_qkv_attn(batch * seq, hidden, heads), buf, cap);
   return crs::attn_plan_describe(crs::plan_attention(batch, seq, heads, hidden / heads, rel_bias != 0, attn_knobs(route)), buf, cap);
+}
+
+// ---- the row kernels on their own (enc_misc.hip, enc_pair.hip): each entry checks its arguments and calls the launcher the forward calls ----
+int crs_embed_ln_f32(const int32_t* ids_dev, const int32_t* type_ids_dev, int type_rows, const float* word_dev, const float* pos_dev,
+                     const float* type_dev, const float* g_dev, const float* b_dev, float eps, int tokens, int seq, int hidden,
+                     int vocab, float* x32_dev, void* x16_dev, void* stream) {
+  if (!ids_dev || !word_dev || !type_dev || !g_dev || !b_dev || !x32_dev || !x16_dev) return crs::set_error(CRS_EINVAL, "embed_ln: null pointer");
+  if (row_misaligned({ids_dev, type_ids_dev, word_dev, pos_dev, type_dev, g_dev, b_dev, x32_dev, x16_dev}))
+    return crs::set_error(CRS_EINVAL, "embed_ln pointers must be 16-byte aligned");
+  const char* why = row_hidden_refusal(hidden);
+  if (!why && (tokens < 1 || seq < 1)) why = "embed_ln: tokens and seq must be >= 1";
+  if (!why && vocab < 1) why = "embed_ln: vocab must be >= 1";
+  if (!why && type_ids_dev && type_rows < 1) why = "embed_ln: type_rows must be >= 1";
+  if (why) return crs::set_error(CRS_EINVAL, why);
+  CRS_TRY(crs::embed_ln_launch(ids_dev, type_ids_dev, word_dev, pos_dev, type_dev, type_rows, g_dev, b_dev, eps, tokens, seq, hidden,
+                               vocab, x32_dev, (_Float16*)x16_dev, (hipStream_t)stream), "embed_ln");
+  return CRS_OK;
+}
+
+int crs_layernorm_f32(const float* y_dev, int nsplit, const float* bias_dev, const float* residual_dev, const float* g_dev,
+                      const float* b_dev, float eps, int tokens, int hidden, float* x32_dev, void* x16_dev, void* stream) {
+  if (!y_dev || !g_dev || !b_dev || !x32_dev || !x16_dev) return crs::set_error(CRS_EINVAL, "layernorm: null pointer");
+  if (row_misaligned({y_dev, bias_dev, residual_dev, g_dev, b_dev, x32_dev, x16_dev}))
+    return crs::set_error(CRS_EINVAL, "layernorm pointers must be 16-byte aligned");
+  const char* why = row_hidden_refusal(hidden);
+  if (!why && tokens < 1) why = "layernorm: tokens must be >= 1";
+  if (!why && !crs::forms::ln_slabs_ok(nsplit)) why = "layernorm: nsplit must be 1, 2, 3, 4, 6, 8 or 16";
+  if (why) return crs::set_error(CRS_EINVAL, why);
+  CRS_TRY(crs::layernorm_launch(y_dev, nsplit, bias_dev, residual_dev, g_dev, b_dev, eps, tokens, hidden, x32_dev, (_Float16*)x16_dev,
+                                (hipStream_t)stream), "layernorm");
+  return CRS_OK;
+}
+
+int crs_pool_f32(const float* x32_dev, const int32_t* lens_dev, int batch, int seq, int hidden, int pooling, int normalize,
+                 float* out_dev, void* out16_dev, int slab_type, void* stream) {
+  if (!x32_dev || !lens_dev || !out_dev) return crs::set_error(CRS_EINVAL, "pool: null pointer");
+  if (row_misaligned({x32_dev, lens_dev, out_dev, out16_dev})) return crs::set_error(CRS_EINVAL, "pool pointers must be 16-byte aligned");
+  const char* why = row_hidden_refusal(hidden);
+  if (!why && (batch < 1 || seq < 1)) why = "pool: batch and seq must be >= 1";
+  if (!why && pooling != CRS_POOL_MEAN && pooling != CRS_POOL_CLS) why = "bad pooling mode";
+  if (!why && slab_type != CRS_SLAB_F16 && slab_type != CRS_SLAB_I8) why = "bad slab_type";
+  if (why) return crs::set_error(CRS_EINVAL, why);
+  CRS_TRY(crs::pool_launch(x32_dev, lens_dev, batch, seq, hidden, pooling, normalize, out_dev, (_Float16*)out16_dev,
+                           crs_row_elems(hidden, slab_type), (hipStream_t)stream), "pool");
+  return CRS_OK;
+}
+
+int crs_pair_head_f32(const float* hidden_dev, int batch, int seq, int hidden, const float* w_pool_dev, const float* b_pool_dev,
+                      const float* w_cls_dev, const float* b_cls_dev, int activation, float* scores_dev, float* pooled_out_dev,
+                      void* stream) {
+  if (!hidden_dev || !w_pool_dev || !b_pool_dev || !w_cls_dev || !b_cls_dev || !scores_dev) return crs::set_error(CRS_EINVAL, "pair_head: null pointer");
+  if (row_misaligned({hidden_dev, w_pool_dev, b_pool_dev, w_cls_dev, b_cls_dev, scores_dev, pooled_out_dev}))
+    return crs::set_error(CRS_EINVAL, "pair_head pointers must be 16-byte aligned");
+  const char* why = row_hidden_refusal(hidden);
+  if (!why && (batch < 1 || seq < 1)) why = "pair_head: batch and seq must be >= 1";
+  if (!why && activation != 0 && activation != 1) why = "pair_head: activation must be 0 (identity) or 1 (sigmoid)";
+  if (why) return crs::set_error(CRS_EINVAL, why);
+  CRS_TRY(crs::pair_head_launch(hidden_dev, batch, seq, hidden, w_pool_dev, b_pool_dev, w_cls_dev, b_cls_dev, activation, scores_dev,
+                                pooled_out_dev, (hipStream_t)stream), "pair head");
+  return CRS_OK;
+}
+
+int crs_row_plan_describe(int kind, int rows, int hidden, int arg, char* buf, size_t cap) {
+  if (cap && !buf) return crs::set_error(CRS_EINVAL, "plan describe: null buffer");
+  const char* why = row_hidden_refusal(hidden);
+  if (!why && (kind < crs::kRowEmbed || kind > crs::kRowPairHead)) why = "row plan describe: kind must be 0 (embedding), 1 (LayerNorm), 2 (pool) or 3 (pair head)";
+  if (!why && rows < 1) why = "row plan describe: rows (tokens, or the batch of the pool and pair-head kernels) must be >= 1";
+  if (!why && kind == crs::kRowLayerNorm && !crs::forms::ln_slabs_ok(arg)) why = "layernorm: nsplit must be 1, 2, 3, 4, 6, 8 or 16";
+  if (why) return crs::set_error(CRS_EINVAL, why);
+  return crs::row_plan_describe(kind, rows, hidden, arg, buf, cap);
 }
 
 int crs_encoder_forward_queries(const crs_encoder_desc* d, const crs_encoder_weights* w, const int32_t* ids_dev,

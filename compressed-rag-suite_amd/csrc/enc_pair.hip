@@ -14,7 +14,10 @@ namespace {
 // (VEC = 2: 8-byte column pairs, H a multiple of 128; VEC = 1 otherwise), multiply it into the kPairGroup vectors, and a wave
 // reduction leaves every lane with the full dot products; tanh, and the classifier's term w_c[j] * pooled[j] is added to the
 // wave's running sum of each pair.  The four waves' sums meet in LDS in a fixed order.  A pair's result does not depend on its
-// place in the group or on the batch it came in.
+// place in the group or on the batch it came in: every multiply-add of a pair is written as fmaf, so that all kPairGroup
+// accumulators run the same arithmetic (left to "a += b * c", the compiler fused six of them and gave the last two a separate
+// multiply and add, and slots 6 and 7 of a group differed from slots 0 to 5 in the last bits;
+// tests/test_row_kernels_gpu.py::test_a_pair_does_not_depend_on_its_place).
 constexpr int kPairGroup = forms::kPairGroup;
 
 template <int VEC>
@@ -46,20 +49,20 @@ __global__ __launch_bounds__(256) void pair_head_kernel(const float* __restrict_
 #pragma unroll
         for (int gi = 0; gi < kPairGroup; ++gi) {
           const float2 h2 = *reinterpret_cast<const float2*>(hs + gi * hidden + c);
-          acc[gi] += w2.x * h2.x;
-          acc[gi] += w2.y * h2.y;
+          acc[gi] = fmaf(w2.x, h2.x, acc[gi]);
+          acc[gi] = fmaf(w2.y, h2.y, acc[gi]);
         }
       } else {
         const float w1 = wr[c];
 #pragma unroll
-        for (int gi = 0; gi < kPairGroup; ++gi) acc[gi] += w1 * hs[gi * hidden + c];
+        for (int gi = 0; gi < kPairGroup; ++gi) acc[gi] = fmaf(w1, hs[gi * hidden + c], acc[gi]);
       }
     }
     const float bj = b_pool[j], wj = w_cls[j];
 #pragma unroll
     for (int gi = 0; gi < kPairGroup; ++gi) {
       const float pooled = tanhf(wave_sum(acc[gi]) + bj);
-      cls[gi] += wj * pooled;
+      cls[gi] = fmaf(wj, pooled, cls[gi]);
       if (pooled_out && lane == 0 && gi < np) pooled_out[(size_t)(p0 + gi) * hidden + j] = pooled;
     }
   }

@@ -183,9 +183,13 @@ Dims plan_rope(int tokens, int hidden) {
   return {(int)((rope_items(tokens, hidden) + kRopeThreads - 1) / kRopeThreads), 1, 1, kRopeThreads, 0};
 }
 
+Dims plan_rows(int tokens) { return {cdiv(tokens, kRowTokens), 1, 1, kRowThreads, 0}; }
+Dims plan_pool(int batch) { return {batch, 1, 1, 256, 0}; }
+Dims plan_pair_head(int batch, int hidden) { return {cdiv(batch, kPairGroup), 1, 1, kPairThreads, kPairGroup * hidden * 4}; }
+
 ProjLnPlan plan_proj_ln(int tokens, int hidden, int k, bool big_ln, int small_lds, int cus, const EncKnobs& kn) {
   ProjLnPlan p;
-  p.ln = {cdiv(tokens, kRowTokens), 1, 1, kRowThreads, 0};
+  p.ln = plan_rows(tokens);
   if (big_ln && rowln2_supported(hidden, k)) {
     // index-build side (large token counts), hidden = 384: projection + bias + residual + LayerNorm in one pipelined kernel
     p.rowln2 = true, p.variant = kn.rowln2_variant, p.d = {cdiv(tokens, kRowlnRows), 1, 1, kRowlnThreads, kRowlnLds};
@@ -261,8 +265,8 @@ EncPlan make_enc_plan(int hidden, int heads, int ffn, int flags, int batch, int 
   p.hidden = H, p.heads = heads, p.ffn = F, p.batch = batch, p.seq = seq, p.tokens = T;
   p.typed = pair == 1, p.pair = pair;
   p.rotary = (flags & 2) != 0, p.gated = (flags & 4) != 0;   // CRS_ENC_ROTARY, CRS_ENC_GATED_SILU
-  p.embed = {cdiv(T, kRowTokens), 1, 1, kRowThreads, 0};
-  p.tail = pair ? Dims{cdiv(batch, kPairGroup), 1, 1, kPairThreads, kPairGroup * H * 4} : Dims{batch, 1, 1, 256, 0};
+  p.embed = plan_rows(T);
+  p.tail = pair ? plan_pair_head(batch, H) : plan_pool(batch);
   // fp16-epilogue projections (QKV, FFN-up) on the panel kernel: K = H in one chunk, or (CRS_ENC_PANEL_MULTI != 0) walked in
   // chunks by the workgroup -- bge-base at query-batch sizes, where the row-streaming kernel pays a 196 KB weight prologue
   // per workgroup for a handful of tiles
@@ -346,10 +350,24 @@ void attn_line(Text& t, const AttnPlan& a) {
   }
 }
 
+// the row kernels' lines: enc_plan_describe, proj_ln_plan_describe and row_plan_describe print them through these
+void embed_line(Text& t, const Dims& d, int hidden, bool typed) {
+  t.line(d, "embed_ln%s_kernel<%d, %s>", row_form2(hidden) ? "2" : "", row_form(hidden), typed ? "true" : "false");
+}
+
+void ln_line(Text& t, const Dims& d, int hidden, int slabs) {
+  t.line(d, "layernorm%s_kernel<%d, %d>", row_form2(hidden) ? "2" : "", row_form(hidden), slabs);
+}
+
+void tail_line(Text& t, const Dims& d, int hidden, bool pair) {
+  if (pair) t.line(d, "pair_head_kernel<%d>", hidden % 128 == 0 ? 2 : 1);
+  else t.line(d, "pool_kernel");
+}
+
 void proj_ln_lines(Text& t, const ProjLnPlan& s, int hidden) {
   if (s.rowln2) { t.line(s.d, s.variant ? "gemm_rowln2_kernel<64, 2>" : "gemm_rowln2_kernel<32, 4>"); return; }
   gemm_line(t, s.gemm);
-  t.line(s.ln, "layernorm%s_kernel<%d, %d>", row_form2(hidden) ? "2" : "", row_form(hidden), s.gemm.slabs);
+  ln_line(t, s.ln, hidden, s.gemm.slabs);
 }
 
 }  // namespace
@@ -383,16 +401,26 @@ EncKnobs attn_route_knobs(int route) {
 
 int enc_plan_describe(const EncPlan& p, char* buf, size_t cap) {
   Text t{buf, cap};
-  const char* two = row_form2(p.hidden) ? "2" : "";
-  t.line(p.embed, "embed_ln%s_kernel<%d, %s>", two, row_form(p.hidden), p.typed ? "true" : "false");
+  embed_line(t, p.embed, p.hidden, p.typed);
   gemm_line(t, p.qkv);
   if (p.rotary) t.line(p.rope, "rope_qk_kernel<%d>", p.attn.hd);
   attn_line(t, p.attn);
   proj_ln_lines(t, p.out, p.hidden);
   gemm_line(t, p.up);
   proj_ln_lines(t, p.down, p.hidden);
-  if (p.pair) t.line(p.tail, "pair_head_kernel<%d>", p.hidden % 128 == 0 ? 2 : 1);
-  else t.line(p.tail, "pool_kernel");
+  tail_line(t, p.tail, p.hidden, p.pair != 0);
+  return t.len;
+}
+
+int row_plan_describe(int kind, int rows, int hidden, int arg, char* buf, size_t cap) {
+  Text t{buf, cap};
+  switch (kind) {
+    case kRowEmbed: embed_line(t, plan_rows(rows), hidden, arg != 0); break;
+    case kRowLayerNorm: ln_line(t, plan_rows(rows), hidden, arg); break;
+    case kRowPool: tail_line(t, plan_pool(rows), hidden, false); break;
+    case kRowPairHead: tail_line(t, plan_pair_head(rows, hidden), hidden, true); break;
+    default: break;
+  }
   return t.len;
 }
 

@@ -102,6 +102,13 @@ ProjLnPlan plan_proj_ln(int tokens, int hidden, int k, bool big_ln, int small_ld
 // rope_qk_kernel's launch: hidden / 8 threads per token (enc_forms.h), no LDS; a function of the two sizes alone
 Dims plan_rope(int tokens, int hidden);
 
+// The launches of the row kernels (enc_misc.hip, enc_pair.hip), functions of the sizes alone: the embedding and LayerNorm kernels
+// give a wave to each token row, four rows per workgroup; pool_kernel a workgroup per sentence; pair_head_kernel a workgroup
+// and kPairGroup x hidden floats of LDS per kPairGroup pairs.  make_enc_plan and plan_proj_ln take their Dims from these.
+Dims plan_rows(int tokens);
+Dims plan_pool(int batch);
+Dims plan_pair_head(int batch, int hidden);
+
 struct EncPlan {
   int hidden, heads, ffn, batch, seq, tokens;
   bool typed;          // embedding with a token-type row per token (pair forward with type ids)
@@ -128,5 +135,10 @@ int gemm_plan_describe(const GemmPlan& p, char* buf, size_t cap);
 int proj_ln_plan_describe(const ProjLnPlan& p, int hidden, char* buf, size_t cap);   // rowln2: one line; else the GEMM's and the LayerNorm's
 int attn_plan_describe(const AttnPlan& p, char* buf, size_t cap);                    // the attention step's line, any form
 int enc_plan_describe(const EncPlan& p, char* buf, size_t cap);
+// One row kernel's line, as enc_plan_describe and proj_ln_plan_describe print it (include/crs_encoder.h: crs_row_plan_describe).
+// kind 0: embedding, rows = tokens, arg != 0 with type ids; 1: LayerNorm, rows = tokens, arg = slabs; 2: pooling, rows = batch;
+// 3: pair head, rows = batch.  The caller has checked the sizes; an unknown kind gives the empty text.
+enum RowKind { kRowEmbed = 0, kRowLayerNorm = 1, kRowPool = 2, kRowPairHead = 3 };
+int row_plan_describe(int kind, int rows, int hidden, int arg, char* buf, size_t cap);
 
 }  // namespace crs

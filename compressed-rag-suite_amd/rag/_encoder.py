@@ -95,6 +95,15 @@ nat.register_signatures({
     "crs_attention_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     "crs_qkv_attn_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "crs_attention_plan_describe": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t]),
+    # test-facing: the row kernels (embedding + LayerNorm, LayerNorm, pooling, pair head) on their own
+    "crs_embed_ln_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int,
+                                 c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "crs_layernorm_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_void_p, c_void_p,
+                                  c_void_p]),
+    "crs_pool_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "crs_pair_head_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                  c_void_p]),
+    "crs_row_plan_describe": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_size_t]),
 })
 
 
@@ -241,6 +250,49 @@ def rope_qk_f16(qkv, table, batch: int, seq: int, heads: int) -> None:
     [positions, H / heads], rope_table's layout)."""
     nat.check(nat.load().crs_rope_qk_f16(nat._ptr(qkv), nat._ptr(table), int(table.shape[0]), int(batch), int(seq), int(qkv.shape[1]) // 3,
                                          int(heads), nat._stream_ptr()))
+
+
+ROW_EMBED, ROW_LAYERNORM, ROW_POOL, ROW_PAIR_HEAD = 0, 1, 2, 3   # crs_row_plan_describe's kinds
+
+
+def row_plan_describe(kind: int, rows: int, hidden: int, arg: int = 0) -> str:
+    """The launch line of embed_ln_f32 (kind 0, rows = tokens, arg: typed), layernorm_f32 (1, tokens, arg = nsplit), pool_f32 (2, rows =
+    batch) or pair_head_f32 (3, batch) for these sizes (crs_row_plan_describe); needs no device."""
+    lib = nat.load()
+    return _describe(lambda sl, buf, cap: lib.crs_row_plan_describe(int(kind), int(rows), int(hidden), int(arg), buf, cap))[0]
+
+
+def embed_ln_f32(ids, type_ids, word, pos, type_tab, g, b, eps: float, seq: int, x32, x16) -> None:
+    """crs_embed_ln_f32: x32 (cuda fp32 [tokens, H]) and x16 (fp16) <- LayerNorm((word[ids] + type_tab[type_ids]) + pos[t % seq]); ids cuda
+    int32 [tokens]; type_ids cuda int32 [tokens] or None (row 0); pos cuda fp32 [>= seq, H] or None."""
+    nat.check(nat.load().crs_embed_ln_f32(nat._ptr(ids), nat._ptr(type_ids), int(type_tab.shape[0]), nat._ptr(word), nat._ptr(pos),
+                                          nat._ptr(type_tab), nat._ptr(g), nat._ptr(b), float(eps), int(ids.numel()), int(seq),
+                                          int(word.shape[1]), int(word.shape[0]), nat._ptr(x32), nat._ptr(x16), nat._stream_ptr()))
+
+
+def layernorm_f32(y, bias, residual, g, b, eps: float, x32, x16) -> None:
+    """crs_layernorm_f32: x32 (cuda fp32 [tokens, H]) and x16 (fp16) <- LayerNorm(sum of the slabs of y (cuda fp32 [nsplit, tokens, H]) +
+    bias + residual); bias / residual may be None, residual may be x32."""
+    nsplit, tokens, hidden = y.shape
+    nat.check(nat.load().crs_layernorm_f32(nat._ptr(y), int(nsplit), nat._ptr(bias), nat._ptr(residual), nat._ptr(g), nat._ptr(b),
+                                           float(eps), int(tokens), int(hidden), nat._ptr(x32), nat._ptr(x16), nat._stream_ptr()))
+
+
+def pool_f32(x32, lens, pooling: int, normalize: bool, out, out16=None, slab_type: int = nat.SLAB_F16) -> None:
+    """crs_pool_f32: out (cuda fp32 [batch, H]) <- mean (pooling 0) or [CLS] (1) pooling of x32 (cuda fp32 [batch, seq, H]) under lens
+    (cuda int32 [batch]), L2-normalised if asked; out16 (cuda fp16 [batch, padded_dim(H, slab_type)] or None): the query block."""
+    batch, seq, hidden = x32.shape
+    nat.check(nat.load().crs_pool_f32(nat._ptr(x32), nat._ptr(lens), int(batch), int(seq), int(hidden), int(pooling), int(bool(normalize)),
+                                      nat._ptr(out), nat._ptr(out16), int(slab_type), nat._stream_ptr()))
+
+
+def pair_head_f32(hidden32, w_pool, b_pool, w_cls, b_cls, activation: int, scores, pooled_out=None) -> None:
+    """crs_pair_head_f32: scores (cuda fp32 [batch]) <- w_cls . tanh(w_pool h + b_pool) + b_cls of token 0 of every pair of hidden32 (cuda
+    fp32 [batch, seq, H]), activation 1: then the sigmoid; pooled_out (cuda fp32 [batch, H] or None): the tanh layer."""
+    batch, seq, hidden = hidden32.shape
+    nat.check(nat.load().crs_pair_head_f32(nat._ptr(hidden32), int(batch), int(seq), int(hidden), nat._ptr(w_pool), nat._ptr(b_pool),
+                                           nat._ptr(w_cls), nat._ptr(b_cls), int(activation), nat._ptr(scores), nat._ptr(pooled_out),
+                                           nat._stream_ptr()))
 
 
 def proj_ln_plan_describe(tokens: int, hidden: int, k: int, flags: int = 0, big_ln: bool = False):

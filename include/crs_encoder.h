@@ -185,6 +185,50 @@ int crs_qkv_attn_f16(const void* x16_dev, const void* w_qkv_dev, const float* b_
  * length of the text as snprintf does, or a negative error code (CRS_EINVAL where the launching entry would refuse the sizes). */
 int crs_attention_plan_describe(int batch, int seq, int hidden, int heads, int rel_bias, int route, char* buf, size_t cap);
 
+/* Test-facing (additive to ABI 3): the encoder's HBM-bound row kernels on their own (csrc/enc_misc.hip, csrc/enc_pair.hip).  Each entry
+ * checks its arguments and calls the launcher the forward calls, nothing else.  All of them refuse with CRS_EINVAL before any launch: a
+ * NULL required pointer; a pointer that is not 16-byte aligned; hidden outside the multiples of 64 up to 1024; tokens, batch or seq
+ * < 1; and what each lists below.
+ *
+ * crs_embed_ln_f32: x = LayerNorm((word[id] + type[type id]) + pos[t % seq]) per token t < tokens -> x32_dev fp32 [tokens, hidden] and
+ * x16_dev fp16 [tokens, hidden].  ids_dev int32 [tokens], clamped to [0, vocab); type_ids_dev int32 [tokens] clamped to [0, type_rows),
+ * or NULL: row 0 of type_dev for every token (type_rows is then not read); word_dev fp32 [vocab, hidden]; pos_dev fp32 [>= seq, hidden]
+ * or NULL: no position row (rotary models); type_dev fp32 [type_rows, hidden]; g_dev / b_dev: the LayerNorm's gain and bias.
+ * Also CRS_EINVAL: vocab < 1, type ids with type_rows < 1. */
+int crs_embed_ln_f32(const int32_t* ids_dev, const int32_t* type_ids_dev, int type_rows, const float* word_dev, const float* pos_dev,
+                     const float* type_dev, const float* g_dev, const float* b_dev, float eps, int tokens, int seq, int hidden,
+                     int vocab, float* x32_dev, void* x16_dev, void* stream);
+
+/* crs_layernorm_f32: x = LayerNorm(((y[0] + y[1] + ... + y[nsplit - 1]) + bias) + residual), summed in that order, -> x32_dev, x16_dev as
+ * above.  y_dev fp32 [nsplit, tokens, hidden] (the split-K slabs of a GEMM); bias_dev fp32 [hidden] or NULL; residual_dev fp32
+ * [tokens, hidden] or NULL, and it may be x32_dev (in place, as the forward runs it).  Also CRS_EINVAL: an nsplit outside 1, 2, 3, 4, 6,
+ * 8, 16 (csrc/enc_forms.h: ln_slabs_ok). */
+int crs_layernorm_f32(const float* y_dev, int nsplit, const float* bias_dev, const float* residual_dev, const float* g_dev,
+                      const float* b_dev, float eps, int tokens, int hidden, float* x32_dev, void* x16_dev, void* stream);
+
+/* crs_pool_f32: the forward's tail.  x32_dev fp32 [batch, seq, hidden]; lens_dev int32 [batch], clamped to [0, seq]; pooling CRS_POOL_MEAN
+ * (the mean of tokens [0, len); len 0: the zero vector) or CRS_POOL_CLS (token 0, whatever len); normalize != 0: x / max(||x||, 1e-12).
+ * out_dev fp32 [batch, hidden]; out16_dev (may be NULL): the fp16 query block [batch, crs_row_elems(hidden, slab_type)], columns
+ * [hidden, row length) written as +0, exactly as crs_encoder_forward_queries_rope asks for it.  Tokens at positions >= max(len, 1) are
+ * never read.  Also CRS_EINVAL: a pooling mode other than the two, an unknown slab_type (with or without out16_dev). */
+int crs_pool_f32(const float* x32_dev, const int32_t* lens_dev, int batch, int seq, int hidden, int pooling, int normalize,
+                 float* out_dev, void* out16_dev, int slab_type, void* stream);
+
+/* crs_pair_head_f32: the head of crs_encoder_score_pairs (below) on hidden states given by the caller.  hidden_dev fp32
+ * [batch, seq, hidden], of which only token 0 of every pair is read; w_pool_dev fp32 [hidden, hidden], b_pool_dev [hidden], w_cls_dev
+ * [hidden], b_cls_dev [1]; scores_dev fp32 [batch]; pooled_out_dev (may be NULL) fp32 [batch, hidden].  Also CRS_EINVAL: activation
+ * outside {0, 1}. */
+int crs_pair_head_f32(const float* hidden_dev, int batch, int seq, int hidden, const float* w_pool_dev, const float* b_pool_dev,
+                      const float* w_cls_dev, const float* b_cls_dev, int activation, float* scores_dev, float* pooled_out_dev,
+                      void* stream);
+
+/* The launch one of the four entries above makes, as one line of crs_encoder_plan_describe's form, built from the expressions the
+ * forward's plan is built from.  kind 0: crs_embed_ln_f32, rows = tokens, arg != 0: with type ids; 1: crs_layernorm_f32, rows = tokens,
+ * arg = nsplit; 2: crs_pool_f32, rows = batch; 3: crs_pair_head_f32, rows = batch (arg is not read by kinds 2 and 3).  It needs no
+ * device.  Returns the length of the text as snprintf does, or a negative error code (CRS_EINVAL for an unknown kind and where the
+ * launching entry would refuse the sizes). */
+int crs_row_plan_describe(int kind, int rows, int hidden, int arg, char* buf, size_t cap);
+
 /* Sentence-pair scoring (cross-encoder re-ranking): BertForSequenceClassification with one label.  The rows of ids_dev hold
  * "[CLS] a [SEP] b [SEP]" (tokenised and truncated on the host), type_ids_dev int32 [batch, seq] names the token-type row of every
  * token (0 for "[CLS] a [SEP]", 1 for "b [SEP]", anything for padding; values outside [0, type_rows) are clamped, as token ids
