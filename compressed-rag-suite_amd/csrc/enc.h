@@ -49,6 +49,10 @@ int gemm_rowln2_launch(const ProjLnPlan& p, const _Float16* a, const _Float16* w
 int attention_launch(const AttnPlan& p, const _Float16* qkv, const int* lens, _Float16* ctx, int batch, int seq, int hidden, int heads,
                      const float* rel_bias, int span, hipStream_t stream);
 
+// AttnForm::Window (plan_attention_window): the blocked kernel restricted to the keys with |key - query| <= p.window; a query without
+// any allowed key (padding at q >= len + window) gets a zero row.  No bias.  -1 for another form or a head_dim other than 16 / 32 / 64.
+int attention_window_launch(const AttnPlan& p, const _Float16* qkv, const int* lens, _Float16* ctx, int seq, int hidden, hipStream_t stream);
+
 // enc_rope.hip: rotates the Q and K column blocks of qkv [tokens, 3 hidden] fp16 in place against table fp32 [positions, hd]
 // (cos half | sin half, include/crs_encoder.h: CRS_ENC_ROTARY); d: EncPlan::rope; the caller checked positions >= seq.  No LDS.
 int rope_qk_launch(const Dims& d, int hd, _Float16* qkv, const float* table, int tokens, int seq, int hidden, hipStream_t stream);
@@ -65,6 +69,12 @@ int layernorm_launch(const float* y, int nsplit, const float* bias, const float*
                      hipStream_t stream);
 int pool_launch(const float* x32, const int* lens, int batch, int seq, int hidden, int pooling, int normalize,
                 float* out, _Float16* out16, int pdim16, hipStream_t stream);
+// enc_addln.hip
+// The row step of a pre-norm layer: r = (sum_{s<nsplit} y[s] + bias) + residual -> r32 (the new residual stream; residual may be
+// r32, in place), x16 = fp16(LayerNorm(r) g + b), and n32 (may be null; the final norm) = the same normalised row in fp32.
+// bias, residual and b may be null (b: a norm without bias).  -1 for a slab count outside CRS_LN_SLABS.
+int add_layernorm_launch(const float* y, int nsplit, const float* bias, const float* residual, const float* g, const float* b,
+                         float eps, int tokens, int hidden, float* r32, _Float16* x16, float* n32, hipStream_t stream);
 
 // enc_pair.hip
 // scores[b] = w_cls . tanh(w_pool hidden32[b, 0, :] + b_pool) + b_cls[0] (activation 1: then 1 / (1 + exp(-score))), all fp32;

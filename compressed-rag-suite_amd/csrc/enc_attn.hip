@@ -12,6 +12,8 @@
 // Softmax is fp32 with the usual online rescaling.  Sequences are right-padded: keys >= lens[b]
 // get -1e30 before the max (every row sees key 0, so the max is always finite).
 // <= 11 % of the encoder's FLOPs at the BASELINE shapes.
+// attention_window_kernel: the blocked kernel restricted to the keys with |key - query| <= window (ModernBERT's sliding layers);
+// there the claim about key 0 does NOT hold -- see its header for the sentinel and the zero rows.
 
 #include "enc.h"
 
@@ -146,12 +148,12 @@ __device__ __forceinline__ void stage_vt(_Float16* sVt, const _Float16* __restri
 }
 
 // Normalise and store the O^T tiles of query row qr (this lane's column): head-dim columns 16 n + 4 g .. + 4, 8-byte stores.
+// (inv: the reciprocal of the row sum; the windowed kernel passes 0 for a row without any allowed key)
 template <int HD>
-__device__ __forceinline__ void store_o(const f32x4 (&o)[HD / 16], float l_run, _Float16* __restrict__ ctx, int b, int h, int qr,
-                                        int seq, int hidden, int g) {
+__device__ __forceinline__ void store_o_scaled(const f32x4 (&o)[HD / 16], float inv, _Float16* __restrict__ ctx, int b, int h, int qr,
+                                               int seq, int hidden, int g) {
   constexpr int NT = HD / 16;
   if (qr < seq) {
-    const float inv = 1.0f / l_run;
     _Float16* dst = ctx + ((size_t)b * seq + qr) * hidden + h * HD;
 #pragma unroll
     for (int n = 0; n < NT; ++n) {
@@ -159,6 +161,12 @@ __device__ __forceinline__ void store_o(const f32x4 (&o)[HD / 16], float l_run, 
       *reinterpret_cast<f16x4*>(dst + n * 16 + 4 * g) = v;
     }
   }
+}
+
+template <int HD>
+__device__ __forceinline__ void store_o(const f32x4 (&o)[HD / 16], float l_run, _Float16* __restrict__ ctx, int b, int h, int qr,
+                                        int seq, int hidden, int g) {
+  store_o_scaled<HD>(o, 1.0f / l_run, ctx, b, h, qr, seq, hidden, g);
 }
 
 // (batch, head) unit of a whole-sequence workgroup.  Workgroups go round-robin over the 8 XCDs (id % 8), and two heads that are
@@ -259,6 +267,128 @@ __global__ __launch_bounds__(kThreads) void attention_kernel(const _Float16* __r
     }
   }
   store_o<HD>(o, l_run, ctx, b, h, q0 + lr, seq, hidden, g);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Sliding-window variant of the blocked kernel (ModernBERT's local layers): query q attends the keys with |key - q| <= window
+// (both ends included) and key < len,
+//   ctx[b, q, h*hd : (h+1)*hd] = softmax_{|j - q| <= W, j < len}(Q K^T / sqrt(hd)) V
+// Same staging, MFMA shape, fp16 rounding points and online softmax as attention_kernel<HD, false>; a workgroup of 64 queries
+// starting at qb walks only the 64-key blocks that meet [max(0, qb - W), min(len, qb + 64 + W)): at most 2 + ceil(2 W / 64) of
+// them, whatever the sequence length, and none where that range is empty (qb - W >= len).  Inside a visited block a score outside the window or at key >= len gets the padding
+// treatment (-1e30, weight 0); a block that lies wholly inside the window of all 16 queries of the wave and below len skips the test.
+// Two things the plain kernel's comments rule out happen here:
+//   * a query's FIRST visited block can lie wholly outside its window (W = 8: rows 73 .. 127 of query block 1 against key block 0),
+//     so "every row sees key 0, the max is finite" does not hold.  The running maximum then stays at the sentinel -1e30 and that
+//     block's weights are exp2(-1e30 - -1e30) = 1, on finite V values; the first block with an allowed key rescales by
+//     exp2(-1e30 - finite) = 0 exactly, which wipes the accumulator and the row sum.  That needs the masked score, the maximum and
+//     the subtraction to be the SAME fp32 number: the step scales first (t = s c) and masks t, instead of masking the raw product and
+//     folding c into an fma as the plain step does -- fma(-1e30, c, fl(1e30 c)) is the product's rounding error, about 2^70, and
+//     exp2 of that is infinity.  The sentinel is finite on purpose: with -inf the same subtraction is inf - inf = NaN.
+//   * a padding query at q >= len + W has no allowed key at all (and a workgroup whose whole query block is such visits no block).
+//     Its row is written as ZEROS: the row sum would be 0 or a count of masked keys, and a NaN there would poison real rows in
+//     the next layer's MFMAs (0 x NaN) although their weight for this position is 0.  Every real query allows itself.
+__device__ __forceinline__ void softmax_step_window(f32x4 (&s)[4], int key0, int q, int window, int len, bool inside, float c,
+                                                    float& m_run, float& l_run, float& alpha, f16x4 (&pf)[4]) {
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s[ct][i] *= c;
+  if (!inside) {                            // wave-uniform
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int key = key0 + ct * 16 + i, d = key - q;
+        if (key >= len || d > window || d < -window) s[ct][i] = -1e30f;
+      }
+  }
+  float mx = -1e30f;
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) mx = fmaxf(mx, s[ct][i]);
+  mx = fmaxf(mx, __shfl_xor(mx, 16));
+  mx = fmaxf(mx, __shfl_xor(mx, 32));
+  const float mn = fmaxf(m_run, mx);
+  alpha = __builtin_amdgcn_exp2f(m_run - mn);
+  m_run = mn;
+  float rs = 0.f;
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float p = __builtin_amdgcn_exp2f(s[ct][i] - mn);
+      rs += p;
+      pf[ct][i] = (_Float16)p;
+    }
+  }
+  rs += __shfl_xor(rs, 16);
+  rs += __shfl_xor(rs, 32);
+  l_run = l_run * alpha + rs;
+}
+
+template <int HD>
+__global__ __launch_bounds__(kThreads) void attention_window_kernel(const _Float16* __restrict__ qkv, const int* __restrict__ lens,
+                                                                   _Float16* __restrict__ ctx, int seq, int hidden, int window) {
+  constexpr int KS = HD / 16, NT = HD / 16;
+  constexpr int KROW = HD + 4, VROW = KB + 4;
+  __shared__ __attribute__((aligned(16))) _Float16 sK[KB * KROW];
+  __shared__ __attribute__((aligned(16))) _Float16 sVt[HD * VROW];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int lr = lane & 15, g = lane >> 4;
+  const int b = blockIdx.z, h = blockIdx.y;
+  const int qb = blockIdx.x * QB, q0 = qb + wave * 16;
+  const int len = min(max(lens[b], 1), seq);
+  const int w = min(window, seq);                  // (|key - query| < seq anyway; keeps the sums below in range)
+  const size_t row_stride = (size_t)3 * hidden;
+  const _Float16* base = qkv + (size_t)b * seq * row_stride + h * HD;
+  const float scale = kLog2e / sqrtf((float)HD);
+  // the workgroup's key blocks (the same for its four waves: the barriers below are uniform)
+  // (a query block wholly behind len + w -- qb - w >= len -- has no allowed key at all and walks no block)
+  const int k_lo = max(0, qb - w) & ~(KB - 1), k_hi = qb - w >= len ? 0 : min(len, qb + QB + w);
+
+  f16x4 qf[KS];
+  load_q_frags<KS>(qf, base, row_stride, q0 + lr, seq, g);
+  f32x4 o[NT];
+#pragma unroll
+  for (int n = 0; n < NT; ++n) o[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m_run = -1e30f, l_run = 0.f;
+
+  for (int kb = k_lo; kb < k_hi; kb += KB) {
+    __syncthreads();
+    stage_k<HD, KROW, kThreads>(sK, base, row_stride, hidden, seq, kb, KB, tid);
+    stage_vt<HD, VROW, kThreads, false>(sVt, base, row_stride, hidden, seq, kb, KB, tid);
+    __syncthreads();
+    f32x4 s[4];
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) {
+      s[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        const f16x4 kf = *reinterpret_cast<const f16x4*>(&sK[(ct * 16 + lr) * KROW + ks * 16 + g * 4]);
+        s[ct] = __builtin_amdgcn_mfma_f32_16x16x16f16(kf, qf[ks], s[ct], 0, 0, 0);
+      }
+    }
+    // all 64 keys allowed for all 16 queries of the wave: kb >= (q0 + 15) - w, kb + 63 <= q0 + w, kb + 64 <= len
+    const bool inside = kb + w >= q0 + 15 && kb + KB - 1 <= q0 + w && kb + KB <= len;
+    float alpha;
+    f16x4 pf[4];
+    softmax_step_window(s, kb + 4 * g, q0 + lr, w, len, inside, scale, m_run, l_run, alpha, pf);
+#pragma unroll
+    for (int n = 0; n < NT; ++n) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) o[n][i] *= alpha;
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) {
+        const f16x4 vf = *reinterpret_cast<const f16x4*>(&sVt[(n * 16 + lr) * VROW + ct * 16 + g * 4]);
+        o[n] = __builtin_amdgcn_mfma_f32_16x16x16f16(vf, pf[ct], o[n], 0, 0, 0);
+      }
+    }
+  }
+  // a row whose maximum is still the sentinel saw no allowed key (finite scores are far above -1e29): zeros
+  store_o_scaled<HD>(o, m_run > -1e29f ? 1.0f / l_run : 0.f, ctx, b, h, q0 + lr, seq, hidden, g);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -551,6 +681,18 @@ int attention_launch(const AttnPlan& p, const _Float16* qkv, const int* lens, _F
       return -1;
     default: return -1;
   }
+}
+
+int attention_window_launch(const AttnPlan& p, const _Float16* qkv, const int* lens, _Float16* ctx, int seq, int hidden, hipStream_t stream) {
+  if (p.form != AttnForm::Window || p.window < 1) return -1;
+  const dim3 grid(p.d.gx, p.d.gy, p.d.gz);
+  switch (p.hd) {
+    case 16: hipLaunchKernelGGL((attention_window_kernel<16>), grid, dim3(kThreads), 0, stream, qkv, lens, ctx, seq, hidden, p.window); break;
+    case 32: hipLaunchKernelGGL((attention_window_kernel<32>), grid, dim3(kThreads), 0, stream, qkv, lens, ctx, seq, hidden, p.window); break;
+    case 64: hipLaunchKernelGGL((attention_window_kernel<64>), grid, dim3(kThreads), 0, stream, qkv, lens, ctx, seq, hidden, p.window); break;
+    default: return -1;
+  }
+  return (int)hipGetLastError();
 }
 
 }  // namespace crs

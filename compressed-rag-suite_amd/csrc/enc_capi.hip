@@ -10,6 +10,12 @@
 //   x    = LayerNorm(y32)
 // Rotary models (CRS_ENC_ROTARY): one rope_qk launch on qkv between the first two steps; gated ones (CRS_ENC_GATED_SILU):
 //   ffn  = silu(x16 Wgate^T + b) * (x16 Wup^T + b)   gemm mode 4 over the interleaved [2F, H] weight      [T, F] fp16
+// Pre-norm models (CRS_ENC_PRENORM, with CRS_ENC_ROTARY and CRS_ENC_GATED_GELU: ModernBERT) take the second arm of the layer loop:
+//   qkv  = x16 Wqkv^T                          x16 = LN_attn(r) from the previous add_layernorm (layer 0: the embedding norm's output)
+//   rope with the layer type's table; ctx = attention (full layers: plan_attention's kernel) or attention_window (the others)
+//   r, x16 = add_layernorm(ctx Wo^T, r)        r <- r + product, x16 <- fp16(LN_mlp(r))             enc_addln.hip
+//   ffn  = gelu(x16 Wa^T) * (x16 Wb^T)         gemm mode 5 over the interleaved [2F, H] weight
+//   r, x16 = add_layernorm(ffn Wdown^T, r)     x16 <- the NEXT layer's LN_attn(r); after the last layer the final norm, kept in fp32 too
 // then pooling + L2 normalise -- or, for crs_encoder_score_pairs, the pair head (enc_pair.hip) on the [CLS] rows; its embedding
 // step takes a token-type row per token (embed_ln_launch with type_ids).  The launch function allocates nothing and never synchronises, so
 // a caller may capture it into a hipGraph for the launch-bound single-query case.
@@ -37,8 +43,8 @@ const crs::EncKnobs& knobs() {
   return kn;
 }
 
-crs::EncPlan plan_for(const crs_encoder_desc* d, int batch, int seq, int rel_bias, int pair, int cus) {
-  return crs::make_enc_plan(d->hidden, d->heads, d->ffn, d->flags, batch, seq, rel_bias, pair, cus, knobs());
+crs::EncPlan plan_for(const crs_encoder_desc* d, int batch, int seq, int rel_bias, int pair, int cus, int window = 0) {
+  return crs::make_enc_plan(d->hidden, d->heads, d->ffn, d->flags, batch, seq, rel_bias, pair, cus, knobs(), window);
 }
 
 int check_desc(const crs_encoder_desc* d) {
@@ -50,11 +56,12 @@ int check_desc(const crs_encoder_desc* d) {
   if (d->ffn <= 0 || d->ffn % 64) return crs::set_error(CRS_EINVAL, "ffn must be a multiple of 64");
   if (d->layers <= 0 || d->vocab_size <= 0 || d->max_pos <= 0) return crs::set_error(CRS_EINVAL, "bad layers/vocab/max_pos");
   if (d->pooling != CRS_POOL_MEAN && d->pooling != CRS_POOL_CLS) return crs::set_error(CRS_EINVAL, "bad pooling mode");
+  if ((d->flags & CRS_ENC_GATED_SILU) && (d->flags & CRS_ENC_GATED_GELU)) return crs::set_error(CRS_EINVAL, "CRS_ENC_GATED_SILU and CRS_ENC_GATED_GELU exclude each other");
   // (ffn % 64 above is what CRS_ENC_GATED_SILU needs: whole [16 gate | 16 up] blocks in every 128-row tile of the 2 ffn rows)
   return CRS_OK;
 }
 
-// mode 4: n rows of interleaved gate / up weights, n / 2 output columns in whole blocks of 16 pairs
+// modes 4, 5: n rows of interleaved gate / up weights, n / 2 output columns in whole blocks of 16 pairs
 bool gated_n_ok(int n) { return n % 2 == 0 && (n / 2) % 32 == 0; }
 
 // what crs_encoder_score_pairs adds to the forward: per-token type ids at the embedding step (null: row 0, the kernels of the
@@ -81,11 +88,12 @@ crs::GemmPlan routed_plan(int m, int n, int k, int mode, int route, int flags, i
   if (m <= 0 || n <= 0 || k <= 0) return p;
   *why = "gemm K must be a multiple of 64";
   if (k % 64) return p;
-  if (mode == 4 && route <= 1) {
-    *why = "gemm mode 4 (gated): n must be even and n / 2 a multiple of 32";
+  if ((mode == 4 || mode == 5) && route <= 1) {
+    *why = mode == 4 ? "gemm mode 4 (gated): n must be even and n / 2 a multiple of 32"
+                     : "gemm mode 5 (gated): n must be even and n / 2 a multiple of 32";
     if (!gated_n_ok(n)) return p;
-    *why = "panel gemm: modes 0, 1, 3 and 4, K a multiple of 128";
-    return route == 0 ? crs::plan_gemm(m, n, k, 4, small, cus, knobs()) : crs::plan_gemm_panel(m, n, k, 4, small, knobs());
+    *why = "panel gemm: modes 0, 1, 3, 4 and 5, K a multiple of 128";
+    return route == 0 ? crs::plan_gemm(m, n, k, mode, small, cus, knobs()) : crs::plan_gemm_panel(m, n, k, mode, small, knobs());
   }
   if (route == 0) {
     *why = "bad gemm mode / missing residual";
@@ -230,6 +238,7 @@ int crs_encoder_plan_describe(const crs_encoder_desc* d, int batch, int seq, int
   const int rc = check_desc(d);
   if (rc) return rc;
   if (batch <= 0 || seq <= 0 || seq > d->max_pos || pair < 0 || pair > 2 || (cap && !buf)) return crs::set_error(CRS_EINVAL, "bad batch/seq (seq <= max_pos), pair or buffer");
+  if (d->flags & CRS_ENC_PRENORM) return crs::set_error(CRS_EINVAL, "a CRS_ENC_PRENORM descriptor needs crs_encoder_prenorm_plan_describe (it carries the window)");
   const int cus = crs::device_cus();
   if (cus <= 0) return crs::set_error(CRS_EHIP, "plan describe: no device");
   return crs::enc_plan_describe(plan_for(d, batch, seq, rel_bias != 0, pair, cus), buf, cap);
@@ -239,14 +248,37 @@ static int encoder_forward(const crs_encoder_desc* d, const crs_encoder_weights*
                            const int32_t* lens_dev, int batch, int seq, void* workspace_dev,
                            size_t workspace_bytes, float* out_dev, int normalize, float* hidden_out_dev,
                            _Float16* q16_out_dev, int q16_row_elems, void* stream, const crs_encoder_ext* ext,
-                           const PairTail* pair = nullptr, const crs_encoder_rope* rope = nullptr) {
+                           const PairTail* pair = nullptr, const crs_encoder_rope* rope = nullptr,
+                           const crs_encoder_prenorm* pre = nullptr) {
   const int rc = check_desc(d);
   if (rc) return rc;
   const bool rotary = (d->flags & CRS_ENC_ROTARY) != 0;
-  const float* rope_table = rope ? rope->table_dev : nullptr;
+  const bool prenorm = (d->flags & CRS_ENC_PRENORM) != 0;
+  if (prenorm) {
+    if (pair || (ext && ext->rel_bias_dev)) return crs::set_error(CRS_EINVAL, "CRS_ENC_PRENORM does not combine with a relative-position bias or the pair head");
+    if (!rotary) return crs::set_error(CRS_EINVAL, "CRS_ENC_PRENORM needs CRS_ENC_ROTARY");
+    if (!pre || !pre->rope_global_dev || !pre->rope_local_dev) return crs::set_error(CRS_EINVAL, "CRS_ENC_PRENORM needs both rope tables (crs_encoder_forward_prenorm / crs_encoder_forward_queries_prenorm)");
+    if (pre->window < 1) return crs::set_error(CRS_EINVAL, "CRS_ENC_PRENORM: window must be >= 1");
+    if (pre->global_every < 1) return crs::set_error(CRS_EINVAL, "CRS_ENC_PRENORM: global_every must be >= 1");
+    if (!pre->final_ln_g) return crs::set_error(CRS_EINVAL, "CRS_ENC_PRENORM needs the final norm's gain");
+    if (pre->positions < seq || (((uintptr_t)pre->rope_global_dev | (uintptr_t)pre->rope_local_dev) & 15)) {
+      char m[160];
+      snprintf(m, sizeof m, "rope tables: positions %d must be >= seq %d, and the tables 16-byte aligned", pre->positions, seq);
+      return crs::set_error(CRS_EINVAL, m);
+    }
+    if (w && w->layers) {
+      // layer 0 has no attention norm: its QKV projection reads the embedding norm's output, and a norm given there would be ignored
+      if (w->layers[0].ln1_g || w->layers[0].ln1_b) return crs::set_error(CRS_EINVAL, "CRS_ENC_PRENORM: layer 0 has no attention norm (ln1_g and ln1_b must be NULL)");
+      for (int li = 1; li < d->layers; ++li)
+        if (!w->layers[li].ln1_g) return crs::set_error(CRS_EINVAL, "CRS_ENC_PRENORM: only layer 0 may have a NULL ln1_g (identity)");
+    }
+  } else if (pre) {
+    return crs::set_error(CRS_EINVAL, "the _prenorm entry points need a CRS_ENC_PRENORM descriptor");
+  }
+  const float* rope_table = prenorm ? pre->rope_global_dev : rope ? rope->table_dev : nullptr;
   if (rotary && !rope_table) return crs::set_error(CRS_EINVAL, "CRS_ENC_ROTARY needs a rope table (crs_encoder_forward_rope / crs_encoder_forward_queries_rope)");
   if (rotary && ext && ext->rel_bias_dev) return crs::set_error(CRS_EINVAL, "CRS_ENC_ROTARY does not combine with a relative-position bias");
-  if (rotary && (rope->positions < seq || ((uintptr_t)rope_table & 15))) {
+  if (rotary && !prenorm && (rope->positions < seq || ((uintptr_t)rope_table & 15))) {
     char m[160];
     snprintf(m, sizeof m, "rope table: positions %d must be >= seq %d, and the table 16-byte aligned", rope->positions, seq);
     return crs::set_error(CRS_EINVAL, m);
@@ -263,7 +295,7 @@ static int encoder_forward(const crs_encoder_desc* d, const crs_encoder_weights*
   const int cus = crs::device_cus();
   if (cus <= 0) return crs::set_error(CRS_EHIP, "encoder forward: no device");
   // integer arithmetic only: no allocation, no device call, legal inside graph capture
-  const crs::EncPlan p = plan_for(d, batch, seq, rel_bias != nullptr, pair ? (pair->type_ids ? 1 : 2) : 0, cus);
+  const crs::EncPlan p = plan_for(d, batch, seq, rel_bias != nullptr, pair ? (pair->type_ids ? 1 : 2) : 0, cus, prenorm ? pre->window : 0);
   if (workspace_bytes < p.total) return crs::set_error(CRS_ENOSPC, "encoder workspace too small");
   hipStream_t st = (hipStream_t)stream;
   char* ws = reinterpret_cast<char*>(workspace_dev);
@@ -282,7 +314,31 @@ static int encoder_forward(const crs_encoder_desc* d, const crs_encoder_weights*
   CRS_TRY(crs::embed_ln_launch(ids_dev, pair ? pair->type_ids : nullptr, w->word_emb, w->pos_emb, w->type_emb,
                                pair ? pair->head->type_rows : 1, w->emb_ln_g, w->emb_ln_b, d->ln_eps, T, seq, H, d->vocab_size, x32,
                                x16, st), "embed_ln");
-  for (int li = 0; li < d->layers; ++li) {
+  // pre-norm: x32 is the un-normalised residual stream r; a block's GEMM leaves its product in y32 (slabs, or bias + r folded in) and
+  // add_layernorm writes r back and the NEXT block's normalised input to x16.  Layer 0's attention reads the embedding norm's x16.
+  // The final norm's fp32 rows go to the (then free) QKV buffer: 6 T H bytes hold the 4 T H.
+  auto add_ln = [&](const crs::ProjLnPlan& s, const _Float16* a, const void* wt, const float* bias, const float* g, const float* b, float* n32) -> int {
+    const bool folded = s.gemm.mode == 2;
+    const int e = crs::gemm_launch(s.gemm, a, (const _Float16*)wt, folded ? bias : nullptr, folded ? x32 : nullptr, y32, st);
+    if (e) return e;
+    return crs::add_layernorm_launch(y32, s.gemm.slabs, folded ? nullptr : bias, folded ? nullptr : x32, g, b, d->ln_eps, T, H, x32, x16, n32, st);
+  };
+  const float* final32 = x32;   // what pooling and hidden_out read
+  for (int li = 0; prenorm && li < d->layers; ++li) {
+    const crs_encoder_layer& L = w->layers[li];
+    const bool full = li % pre->global_every == 0, last = li + 1 == d->layers;
+    CRS_TRY(crs::gemm_launch(p.qkv, x16, (const _Float16*)L.w_qkv, L.b_qkv, nullptr, qkv, st), "qkv gemm");
+    CRS_TRY(crs::rope_qk_launch(p.rope, p.attn.hd, qkv, full ? pre->rope_global_dev : pre->rope_local_dev, T, seq, H, st), "rope");
+    if (full) CRS_TRY(crs::attention_launch(p.attn, qkv, lens_dev, ctx, batch, seq, H, d->heads, nullptr, 0, st), "attention");
+    else CRS_TRY(crs::attention_window_launch(p.win, qkv, lens_dev, ctx, seq, H, st), "windowed attention");
+    CRS_TRY(add_ln(p.out, ctx, L.w_o, L.b_o, L.ln2_g, L.ln2_b, nullptr), "out projection + add + mlp norm");
+    CRS_TRY(crs::gemm_launch(p.up, x16, (const _Float16*)L.w_up, L.b_up, nullptr, ffn, st), "ffn up gemm");
+    float* n32 = last ? reinterpret_cast<float*>(qkv) : nullptr;
+    CRS_TRY(add_ln(p.down, ffn, L.w_down, L.b_down, last ? pre->final_ln_g : w->layers[li + 1].ln1_g,
+                   last ? pre->final_ln_b : w->layers[li + 1].ln1_b, n32), "ffn down projection + add + next norm");
+    if (last) final32 = n32;
+  }
+  for (int li = 0; !prenorm && li < d->layers; ++li) {
     const crs_encoder_layer& L = w->layers[li];
     if (p.attn.form == crs::AttnForm::Fused) {
       CRS_TRY(crs::qkv_attn_launch(p.attn, x16, (const _Float16*)L.w_qkv, L.b_qkv, lens_dev, ctx, T, seq, H, st), "qkv + attention");
@@ -296,7 +352,7 @@ static int encoder_forward(const crs_encoder_desc* d, const crs_encoder_weights*
     CRS_TRY(proj_ln(p.down, ffn, L.w_down, L.b_down, L.ln2_g, L.ln2_b, F), "ffn down projection + layernorm 2");
   }
   if (hidden_out_dev) {
-    const hipError_t e = hipMemcpyAsync(hidden_out_dev, x32, (size_t)T * H * 4, hipMemcpyDeviceToDevice, st);
+    const hipError_t e = hipMemcpyAsync(hidden_out_dev, final32, (size_t)T * H * 4, hipMemcpyDeviceToDevice, st);
     if (e != hipSuccess) return crs::set_error(CRS_EHIP, hipGetErrorString(e));
   }
   if (pair) {
@@ -305,8 +361,38 @@ static int encoder_forward(const crs_encoder_desc* d, const crs_encoder_weights*
                                   pair->pooled_out, st), "pair head");
     return CRS_OK;
   }
-  CRS_TRY(crs::pool_launch(x32, lens_dev, batch, seq, H, d->pooling, normalize, out_dev, q16_out_dev, q16_row_elems, st), "pool");
+  CRS_TRY(crs::pool_launch(final32, lens_dev, batch, seq, H, d->pooling, normalize, out_dev, q16_out_dev, q16_row_elems, st), "pool");
   return CRS_OK;
+}
+
+int crs_encoder_forward_prenorm(const crs_encoder_desc* d, const crs_encoder_weights* w, const int32_t* ids_dev,
+                                const int32_t* lens_dev, int batch, int seq, void* workspace_dev, size_t workspace_bytes,
+                                float* out_dev, int normalize, float* hidden_out_dev, void* stream, const crs_encoder_prenorm* pre) {
+  if (!pre) return crs::set_error(CRS_EINVAL, "CRS_ENC_PRENORM needs both rope tables (crs_encoder_prenorm)");
+  return encoder_forward(d, w, ids_dev, lens_dev, batch, seq, workspace_dev, workspace_bytes, out_dev, normalize, hidden_out_dev,
+                         nullptr, 0, stream, nullptr, nullptr, nullptr, pre);
+}
+
+int crs_encoder_forward_queries_prenorm(const crs_encoder_desc* d, const crs_encoder_weights* w, const int32_t* ids_dev,
+                                        const int32_t* lens_dev, int batch, int seq, void* workspace_dev, size_t workspace_bytes,
+                                        float* out_dev, void* q16_out_dev, int slab_type, void* stream,
+                                        const crs_encoder_prenorm* pre) {
+  if (!q16_out_dev) return crs::set_error(CRS_EINVAL, "null pointer");
+  if (slab_type != CRS_SLAB_F16 && slab_type != CRS_SLAB_I8) return crs::set_error(CRS_EINVAL, "bad slab_type");
+  if (!d) return crs::set_error(CRS_EINVAL, "null descriptor");
+  if (!pre) return crs::set_error(CRS_EINVAL, "CRS_ENC_PRENORM needs both rope tables (crs_encoder_prenorm)");
+  return encoder_forward(d, w, ids_dev, lens_dev, batch, seq, workspace_dev, workspace_bytes, out_dev, 1, nullptr,
+                         reinterpret_cast<_Float16*>(q16_out_dev), crs_row_elems(d->hidden, slab_type), stream, nullptr, nullptr, nullptr, pre);
+}
+
+int crs_encoder_prenorm_plan_describe(const crs_encoder_desc* d, int batch, int seq, int window, char* buf, size_t cap) {
+  const int rc = check_desc(d);
+  if (rc) return rc;
+  if (!(d->flags & CRS_ENC_PRENORM) || !(d->flags & CRS_ENC_ROTARY)) return crs::set_error(CRS_EINVAL, "prenorm plan describe: the descriptor needs CRS_ENC_PRENORM and CRS_ENC_ROTARY");
+  if (batch <= 0 || seq <= 0 || seq > d->max_pos || window < 1 || (cap && !buf)) return crs::set_error(CRS_EINVAL, "bad batch/seq (seq <= max_pos), window or buffer");
+  const int cus = crs::device_cus();
+  if (cus <= 0) return crs::set_error(CRS_EHIP, "plan describe: no device");
+  return crs::enc_plan_describe(plan_for(d, batch, seq, 0, 0, cus, window), buf, cap);
 }
 
 int crs_encoder_score_pairs(const crs_encoder_desc* d, const crs_encoder_weights* w, const crs_encoder_head* head,
@@ -400,6 +486,26 @@ int crs_attention_f16(const void* qkv_dev, const int32_t* lens_dev, void* ctx_de
   return CRS_OK;
 }
 
+int crs_attention_window_f16(const void* qkv_dev, const int32_t* lens_dev, void* ctx_dev, int batch, int seq, int hidden, int heads,
+                             int window, void* stream) {
+  if (!qkv_dev || !lens_dev || !ctx_dev) return crs::set_error(CRS_EINVAL, "attention: null pointer");
+  if (((uintptr_t)qkv_dev | (uintptr_t)lens_dev | (uintptr_t)ctx_dev) & 15) return crs::set_error(CRS_EINVAL, "attention pointers must be 16-byte aligned");
+  const char* why = attn_sizes_refusal(batch, seq, hidden, heads);
+  if (!why && window < 1) why = "attention: window must be >= 1";
+  if (why) return crs::set_error(CRS_EINVAL, why);
+  const crs::AttnPlan p = crs::plan_attention_window(batch, seq, heads, hidden / heads, window, knobs());
+  CRS_TRY(crs::attention_window_launch(p, (const _Float16*)qkv_dev, lens_dev, (_Float16*)ctx_dev, seq, hidden, (hipStream_t)stream), "windowed attention");
+  return CRS_OK;
+}
+
+int crs_attention_window_plan_describe(int batch, int seq, int hidden, int heads, int window, char* buf, size_t cap) {
+  if (cap && !buf) return crs::set_error(CRS_EINVAL, "plan describe: null buffer");
+  const char* why = attn_sizes_refusal(batch, seq, hidden, heads);
+  if (!why && window < 1) why = "attention: window must be >= 1";
+  if (why) return crs::set_error(CRS_EINVAL, why);
+  return crs::attn_plan_describe(crs::plan_attention_window(batch, seq, heads, hidden / heads, window, knobs()), buf, cap);
+}
+
 int crs_qkv_attn_f16(const void* x16_dev, const void* w_qkv_dev, const float* b_qkv_dev, const int32_t* lens_dev, void* ctx_dev,
                      int batch, int seq, int hidden, int heads, void* stream) {
   if (!x16_dev || !w_qkv_dev || !b_qkv_dev || !lens_dev || !ctx_dev) return crs::set_error(CRS_EINVAL, "qkv + attention: null pointer");
@@ -458,6 +564,21 @@ int crs_layernorm_f32(const float* y_dev, int nsplit, const float* bias_dev, con
   return CRS_OK;
 }
 
+int crs_add_layernorm_f32(const float* y_dev, int nsplit, const float* bias_dev, const float* residual_dev, const float* g_dev,
+                          const float* b_dev, float eps, int tokens, int hidden, float* r32_dev, void* x16_dev, float* n32_dev,
+                          void* stream) {
+  if (!y_dev || !g_dev || !r32_dev || !x16_dev) return crs::set_error(CRS_EINVAL, "add_layernorm: null pointer");
+  if (row_misaligned({y_dev, bias_dev, residual_dev, g_dev, b_dev, r32_dev, x16_dev, n32_dev}))
+    return crs::set_error(CRS_EINVAL, "add_layernorm pointers must be 16-byte aligned");
+  const char* why = row_hidden_refusal(hidden);
+  if (!why && tokens < 1) why = "add_layernorm: tokens must be >= 1";
+  if (!why && !crs::forms::ln_slabs_ok(nsplit)) why = "add_layernorm: nsplit must be 1, 2, 3, 4, 6, 8 or 16";
+  if (why) return crs::set_error(CRS_EINVAL, why);
+  CRS_TRY(crs::add_layernorm_launch(y_dev, nsplit, bias_dev, residual_dev, g_dev, b_dev, eps, tokens, hidden, r32_dev, (_Float16*)x16_dev,
+                                    n32_dev, (hipStream_t)stream), "add_layernorm");
+  return CRS_OK;
+}
+
 int crs_pool_f32(const float* x32_dev, const int32_t* lens_dev, int batch, int seq, int hidden, int pooling, int normalize,
                  float* out_dev, void* out16_dev, int slab_type, void* stream) {
   if (!x32_dev || !lens_dev || !out_dev) return crs::set_error(CRS_EINVAL, "pool: null pointer");
@@ -490,9 +611,9 @@ int crs_pair_head_f32(const float* hidden_dev, int batch, int seq, int hidden, c
 int crs_row_plan_describe(int kind, int rows, int hidden, int arg, char* buf, size_t cap) {
   if (cap && !buf) return crs::set_error(CRS_EINVAL, "plan describe: null buffer");
   const char* why = row_hidden_refusal(hidden);
-  if (!why && (kind < crs::kRowEmbed || kind > crs::kRowPairHead)) why = "row plan describe: kind must be 0 (embedding), 1 (LayerNorm), 2 (pool) or 3 (pair head)";
+  if (!why && (kind < crs::kRowEmbed || kind > crs::kRowAddLayerNorm)) why = "row plan describe: kind must be 0 (embedding), 1 (LayerNorm), 2 (pool), 3 (pair head) or 4 (add + LayerNorm)";
   if (!why && rows < 1) why = "row plan describe: rows (tokens, or the batch of the pool and pair-head kernels) must be >= 1";
-  if (!why && kind == crs::kRowLayerNorm && !crs::forms::ln_slabs_ok(arg)) why = "layernorm: nsplit must be 1, 2, 3, 4, 6, 8 or 16";
+  if (!why && (kind == crs::kRowLayerNorm || kind == crs::kRowAddLayerNorm) && !crs::forms::ln_slabs_ok(arg)) why = "layernorm: nsplit must be 1, 2, 3, 4, 6, 8 or 16";
   if (why) return crs::set_error(CRS_EINVAL, why);
   return crs::row_plan_describe(kind, rows, hidden, arg, buf, cap);
 }

@@ -48,4 +48,10 @@ __device__ __forceinline__ float gelu_erf(float x) {
   return r[0];
 }
 
+// The activated half of the gated epilogue, by GEMM mode: 4 SiLU (CRS_ENC_GATED_SILU), 5 erf GELU (CRS_ENC_GATED_GELU: GeGLU).
+template <int MODE>
+__device__ __forceinline__ float gate_act(float x) {
+  if constexpr (MODE == 5) return gelu_erf(x); else return silu_f32(x);
+}
+
 }  // namespace crs

@@ -15,6 +15,7 @@
 //   1  + bias, erf-GELU            -> fp16      (FFN up)
 //   2  + bias + residual (fp32)    -> fp32      (attention out / FFN down; LayerNorm follows)
 //   4  + bias, silu(gate) * up     -> fp16 [M, N / 2]   (gated FFN up: W rows interleaved [16 gate | 16 up], crs_encoder.h)
+//   5  + bias, gelu(gate) * up     -> fp16 [M, N / 2]   (mode 4's epilogue with the erf GELU on the activated half: GeGLU)
 // MFMA-bound for index-build batches (thousands of tokens); launch-bound for a single short query.
 
 #include "enc.h"
@@ -161,7 +162,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_f16_kernel(const _Float16* _
         for (int e = 0; e < 4 && gc2 + e < N; ++e) o[at + e] = v[e] + (bias ? bias[gc2 + e] : 0.f) + residual[at + e];
       }
     }
-  } else if (MODE == 4) {
+  } else if (MODE >= 4) {
     // gated epilogue: the tile's 128 columns are 4 blocks of [16 gate | 16 up] columns (include/crs_encoder.h) = 64 output
     // columns; a thread finishes 8 consecutive output columns of a row, all of one block.  N / 2 is a multiple of 32 (checked by
     // the caller), so an 8-column group is inside the output or outside it as a whole and every row is 16-byte aligned.
@@ -177,7 +178,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_f16_kernel(const _Float16* _
       for (int e = 0; e < 8; ++e) {
         const float gt = tile[row * BN + tg + e] + (bias ? bias[n0 + tg + e] : 0.f);
         const float up = tile[row * BN + tg + 16 + e] + (bias ? bias[n0 + tg + 16 + e] : 0.f);
-        h[e] = (_Float16)(silu_f32(gt) * up);
+        h[e] = (_Float16)(gate_act<MODE>(gt) * up);
       }
       *reinterpret_cast<f16x8*>(o + (size_t)gr * NO + gc) = h;
     }
@@ -223,7 +224,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_f16_kernel(const _Float16* _
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 constexpr int PN = forms::kPanelN, PKC = forms::kPanelMaxChunk;
 
-// MODE 0: +bias -> fp16; 1: +bias, GELU -> fp16; 3: raw fp32 partial tile -> out[z][M][N]; 4: +bias, silu(gate) * up -> fp16 [M, N / 2].
+// MODE 0: +bias -> fp16; 1: +bias, GELU -> fp16; 3: raw fp32 partial tile -> out[z][M][N]; 4: +bias, silu(gate) * up -> fp16 [M, N / 2]; 5: the same with gelu(gate).
 // TM = rows of A per workgroup: 64 (most workgroups, for tiny M) or 128 (halves the operand re-reads
 // and the workgroup count -- one wave of workgroups on 256 CUs for the 1024-token query batch).
 constexpr int kPanelThreads = forms::kPanelThreads;   // 512, 8 waves: the LDS-DMA issue (1 KiB per wave-instruction) is the long
@@ -319,7 +320,7 @@ __global__ __launch_bounds__(kPanelThreads, 1) void gemm_panel_kernel(const _Flo
         for (int e = 0; e < 4 && c0 + lc + e < N; ++e) dst[e] = v[e];
       }
     }
-  } else if (MODE == 4) {
+  } else if (MODE >= 4) {
     // gated epilogue: a wave's 32 columns are one block of [16 gate | 16 up] columns (include/crs_encoder.h) = 16 output columns.
     // The biased accumulators go through the wave-private fp32 tile (mode 3's); a lane then finishes 8 output columns of a row:
     // one 16-byte store.  N / 2 is a multiple of 32 (checked by the caller): a wave's block is inside the output or outside it.
@@ -338,8 +339,8 @@ __global__ __launch_bounds__(kPanelThreads, 1) void gemm_panel_kernel(const _Flo
       f16x8 h;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        h[e] = (_Float16)(silu_f32(g0[e]) * u0[e]);
-        h[e + 4] = (_Float16)(silu_f32(g1[e]) * u1[e]);
+        h[e] = (_Float16)(gate_act<MODE>(g0[e]) * u0[e]);
+        h[e + 4] = (_Float16)(gate_act<MODE>(g1[e]) * u1[e]);
       }
       *reinterpret_cast<f16x8*>(o + (size_t)row * NO + (c0 >> 1) + lc) = h;
     }
@@ -407,6 +408,7 @@ int gemm_launch(const GemmPlan& p, const _Float16* a, const _Float16* w, const f
         case 1: return launch_panel<1>(p, a, w, bias, out, stream);
         case 3: return launch_panel<3>(p, a, w, bias, out, stream);
         case 4: return launch_panel<4>(p, a, w, bias, out, stream);
+        case 5: return launch_panel<5>(p, a, w, bias, out, stream);
         default: return -1;
       }
     case GemmFamily::Tiled: {
@@ -416,6 +418,7 @@ int gemm_launch(const GemmPlan& p, const _Float16* a, const _Float16* w, const f
         case 1: hipLaunchKernelGGL((gemm_f16_kernel<1>), grid, dim3(kThreads), 0, stream, a, w, bias, residual, out, p.m, p.n, p.k); break;
         case 2: hipLaunchKernelGGL((gemm_f16_kernel<2>), grid, dim3(kThreads), 0, stream, a, w, bias, residual, out, p.m, p.n, p.k); break;
         case 4: hipLaunchKernelGGL((gemm_f16_kernel<4>), grid, dim3(kThreads), 0, stream, a, w, bias, residual, out, p.m, p.n, p.k); break;
+        case 5: hipLaunchKernelGGL((gemm_f16_kernel<5>), grid, dim3(kThreads), 0, stream, a, w, bias, residual, out, p.m, p.n, p.k); break;
         default: return -1;
       }
       return (int)hipGetLastError();

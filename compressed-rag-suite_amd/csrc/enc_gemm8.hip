@@ -207,7 +207,7 @@ __global__ __launch_bounds__(kP8Threads, 2) void gemm8_kernel(const _Float16* __
     for (int j = 0; j < 4; ++j)
       bv[j] = (bias && MODE != 3) ? *reinterpret_cast<const f32x4*>(bias + bs.n0 + wn * 64 + j * 16 + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
     const int row_g0 = bs.m0 + wm * 128, col_g0 = bs.n0 + wn * 64;
-    if (MODE == 4) {
+    if (MODE >= 4) {
       // gated epilogue (W rows interleaved [16 gate | 16 up], include/crs_encoder.h): column tile 2 b of the wave holds the gates
       // and tile 2 b + 1 the up values of the SAME 16 output columns, in the same lane and element -- the product is a register
       // operation.  A 16-row block leaves as 32 fp16 columns: 64 contiguous bytes per row, one 16-byte store per lane.
@@ -218,8 +218,8 @@ __global__ __launch_bounds__(kP8Threads, 2) void gemm8_kernel(const _Float16* __
 #pragma unroll
         for (int jb = 0; jb < 2; ++jb) {
           const f32x4 g = acc[i][2 * jb] + bv[2 * jb], u = acc[i][2 * jb + 1] + bv[2 * jb + 1];
-          const f16x4 hv = {(_Float16)(silu_f32(g[0]) * u[0]), (_Float16)(silu_f32(g[1]) * u[1]), (_Float16)(silu_f32(g[2]) * u[2]),
-                            (_Float16)(silu_f32(g[3]) * u[3])};
+          const f16x4 hv = {(_Float16)(gate_act<MODE>(g[0]) * u[0]), (_Float16)(gate_act<MODE>(g[1]) * u[1]), (_Float16)(gate_act<MODE>(g[2]) * u[2]),
+                            (_Float16)(gate_act<MODE>(g[3]) * u[3])};
           *reinterpret_cast<f16x4*>(stage + c * kEpiRow16 + (jb * 16 + 4 * q) * 2) = hv;
           acc[i][2 * jb] = f32x4{0.f, 0.f, 0.f, 0.f};
           acc[i][2 * jb + 1] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -333,6 +333,7 @@ int gemm8_launch(const GemmPlan& p, const _Float16* a, const _Float16* w, const 
     case 2: return launch8<2>(p, a, w, bias, residual, out, stream);
     case 3: return launch8<3>(p, a, w, bias, residual, out, stream);
     case 4: return launch8<4>(p, a, w, bias, residual, out, stream);   // out: fp16 [M, N / 2]
+    case 5: return launch8<5>(p, a, w, bias, residual, out, stream);   // (gelu on the activated half)
     default: return -1;
   }
 }

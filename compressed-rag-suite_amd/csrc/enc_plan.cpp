@@ -105,7 +105,7 @@ GemmPlan plan_gemm8(int m, int n, int k, int mode, int splits, int cus, const En
   // the stream pays for the fp16 epilogues (bias / GELU; + 8 % at K = 768 and 384: their VALU and stores sit beside the next item's
   // first phases) and measured 4 % slower for the fp32 + residual ones (the residual loads of the 16-row passes drain behind the
   // transfers in flight): those keep one workgroup per item.  CRS_GEMM8_VAR=1: one workgroup per item everywhere (A/B)
-  p.persist = p.var != 1 && p.items > cus && (mode < 2 || mode == 4);   // (4: an fp16 epilogue too)
+  p.persist = p.var != 1 && p.items > cus && (mode < 2 || mode >= 4);   // (4, 5: fp16 epilogues too)
   p.ksplit = k / p.slabs;
   p.d = {p.persist ? cus : p.items, 1, 1, kG8Threads, kG8Lds};
   return p;
@@ -164,6 +164,14 @@ AttnPlan plan_attention(int batch, int seq, int heads, int hd, bool bias, const 
   return a;
 }
 
+AttnPlan plan_attention_window(int batch, int seq, int heads, int hd, int window, const EncKnobs& kn) {
+  (void)kn;
+  AttnPlan a;
+  a.hd = hd, a.form = AttnForm::Window, a.window = window;
+  a.d = {cdiv(seq, kAttnQ), heads, batch, kAttnThreads, 0};
+  return a;
+}
+
 bool qkv_attn_supported(int hidden, int heads, int seq) {
   if (hidden > 384 || hidden % 128) return false;
   const int hd = hidden / heads;
@@ -190,7 +198,7 @@ Dims plan_pair_head(int batch, int hidden) { return {cdiv(batch, kPairGroup), 1,
 ProjLnPlan plan_proj_ln(int tokens, int hidden, int k, bool big_ln, int small_lds, int cus, const EncKnobs& kn) {
   ProjLnPlan p;
   p.ln = plan_rows(tokens);
-  if (big_ln && rowln2_supported(hidden, k)) {
+  if (big_ln && rowln2_supported(hidden, k)) {   // (a pre-norm plan passes big_ln = false)
     // index-build side (large token counts), hidden = 384: projection + bias + residual + LayerNorm in one pipelined kernel
     p.rowln2 = true, p.variant = kn.rowln2_variant, p.d = {cdiv(tokens, kRowlnRows), 1, 1, kRowlnThreads, kRowlnLds};
   } else if (use_panel(tokens, k, kn)) {
@@ -206,7 +214,7 @@ ProjLnPlan plan_proj_ln(int tokens, int hidden, int k, bool big_ln, int small_ld
 GemmPlan plan_gemm_panel(int m, int n, int k, int mode, int small_lds, const EncKnobs& kn) {
   GemmPlan p;
   int kc = panel_chunk(k);
-  if (kc == 0 || (mode != 0 && mode != 1 && mode != 3 && mode != 4)) return p;
+  if (kc == 0 || (mode != 0 && mode != 1 && mode != 3 && mode != 4 && mode != 5)) return p;
   p.family = GemmFamily::Panel;
   p.m = m, p.n = n, p.k = k, p.mode = mode;
   p.slabs = mode == 3 ? panel_splits(k, m, kn) : 1;
@@ -234,9 +242,9 @@ GemmPlan plan_gemm_panel(int m, int n, int k, int mode, int small_lds, const Enc
 GemmPlan plan_gemm(int m, int n, int k, int mode, int small_lds, int cus, const EncKnobs& kn) {
   (void)small_lds;   // none of these families has a small-LDS form
   GemmPlan p;
-  if (mode == 4) {
-    // the gated epilogue exists on the 256 x 256 phase-scheduled kernel, the tiled kernel (and the panel kernel, plan_gemm_panel):
-    // every mode-4 plan made here is Gemm8 or Tiled, whatever the shape and the knobs, so the 256-row and row-streaming
+  if (mode == 4 || mode == 5) {
+    // the gated epilogue (4: SiLU, 5: GELU on the activated half) exists on the 256 x 256 phase-scheduled kernel, the tiled kernel (and the panel kernel, plan_gemm_panel):
+    // every gated plan made here is Gemm8 or Tiled, whatever the shape and the knobs, so the 256-row and row-streaming
     // families never see the mode
     if (gemm8_applies(m, n, k, kn)) return plan_gemm8(m, n, k, mode, 1, cus, kn);
     p.m = m, p.n = n, p.k = k, p.mode = mode, p.family = GemmFamily::Tiled;
@@ -259,12 +267,15 @@ GemmPlan plan_gemm(int m, int n, int k, int mode, int small_lds, int cus, const 
   return p;
 }
 
-EncPlan make_enc_plan(int hidden, int heads, int ffn, int flags, int batch, int seq, int rel_bias, int pair, int cus, const EncKnobs& kn) {
+EncPlan make_enc_plan(int hidden, int heads, int ffn, int flags, int batch, int seq, int rel_bias, int pair, int cus, const EncKnobs& kn,
+                      int window) {
   EncPlan p{};
   const int T = batch * seq, H = hidden, F = ffn, hd = H / heads, small = (flags & 1) ? 1 : 0;   // CRS_ENC_SMALL_LDS
   p.hidden = H, p.heads = heads, p.ffn = F, p.batch = batch, p.seq = seq, p.tokens = T;
   p.typed = pair == 1, p.pair = pair;
-  p.rotary = (flags & 2) != 0, p.gated = (flags & 4) != 0;   // CRS_ENC_ROTARY, CRS_ENC_GATED_SILU
+  p.rotary = (flags & 2) != 0, p.gated = (flags & (4 | 16)) != 0;   // CRS_ENC_ROTARY, CRS_ENC_GATED_SILU / CRS_ENC_GATED_GELU
+  p.prenorm = (flags & 8) != 0;                                      // CRS_ENC_PRENORM
+  const int gate_mode = (flags & 16) ? 5 : 4;
   p.embed = plan_rows(T);
   p.tail = pair ? plan_pair_head(batch, H) : plan_pool(batch);
   // fp16-epilogue projections (QKV, FFN-up) on the panel kernel: K = H in one chunk, or (CRS_ENC_PANEL_MULTI != 0) walked in
@@ -275,19 +286,23 @@ EncPlan make_enc_plan(int hidden, int heads, int ffn, int flags, int batch, int 
                         !gemm8_applies(T, 3 * H, H, kn);
   // short sequences in the launch-bound regime: QKV projection + attention as one kernel (enc_qkvattn.hip)
   // (never for a rotary model: the rotation runs between the projection and attention)
-  if (!rel_bias && !p.rotary && T <= kPanelMaxTokens && !small && kn.qkvattn && qkv_attn_supported(H, heads, seq)) {
+  if (!rel_bias && !p.rotary && !p.prenorm && T <= kPanelMaxTokens && !small && kn.qkvattn && qkv_attn_supported(H, heads, seq)) {
     p.attn = plan_qkv_attn(T, H, heads);
   } else {
     p.qkv = single_h ? plan_gemm_panel(T, 3 * H, H, 0, small, kn) : plan_gemm(T, 3 * H, H, 0, small, cus, kn);
     p.attn = plan_attention(batch, seq, heads, hd, rel_bias != 0, kn);
   }
   if (p.rotary) p.rope = plan_rope(T, H);
-  const bool big_ln = T > kPanelMaxTokens && kn.bigln;
+  if (p.prenorm) p.win = plan_attention_window(batch, seq, heads, hd, window, kn);
+  // pre-norm: the norm does not follow the projection's residual add in the same stream position (it belongs to the NEXT block), so
+  // the fused projection + LayerNorm kernel is never taken: mode-3 slabs or the mode-2 GEMM, then add_layernorm
+  const bool big_ln = T > kPanelMaxTokens && kn.bigln && !p.prenorm;
   p.out = plan_proj_ln(T, H, H, big_ln, small, cus, kn);
   // gated: W holds 2 F interleaved gate / up rows and the epilogue (mode 4) leaves F columns; ffn_off is T x F either way
-  if (p.gated) p.up = single_h ? plan_gemm_panel(T, 2 * F, H, 4, small, kn) : plan_gemm(T, 2 * F, H, 4, small, cus, kn);
+  if (p.gated) p.up = single_h ? plan_gemm_panel(T, 2 * F, H, gate_mode, small, kn) : plan_gemm(T, 2 * F, H, gate_mode, small, cus, kn);
   else p.up = single_h ? plan_gemm_panel(T, F, H, 1, small, kn) : plan_gemm(T, F, H, 1, small, cus, kn);
   p.down = plan_proj_ln(T, H, F, big_ln, small, cus, kn);
+  p.out.prenorm = p.down.prenorm = p.prenorm;
 
   // The workspace's slab count: an UPPER BOUND of the slab counts above (out.gemm.slabs, down.gemm.slabs), kept as the rule
   // crs_encoder_workspace_bytes has always answered by.  It takes the gemm8 split-K count of a shape even where the panel path
@@ -347,6 +362,7 @@ void attn_line(Text& t, const AttnPlan& a) {
     case AttnForm::Short: t.line(a.d, "attention_short_kernel<%d>", a.hd); break;
     case AttnForm::Seq: t.line(a.d, "attention_seq_kernel<%d, %d, %d>", a.hd, a.smax, a.nw); break;
     case AttnForm::Seq32: t.line(a.d, "attention_seq32_kernel<%d, %d, %d, %d>", a.hd, a.smax, a.nw, a.qt); break;
+    case AttnForm::Window: t.line(a.d, "attention_window_kernel<%d>", a.hd); break;   // (window is a launch argument)
   }
 }
 
@@ -359,6 +375,10 @@ void ln_line(Text& t, const Dims& d, int hidden, int slabs) {
   t.line(d, "layernorm%s_kernel<%d, %d>", row_form2(hidden) ? "2" : "", row_form(hidden), slabs);
 }
 
+void add_ln_line(Text& t, const Dims& d, int hidden, int slabs) {
+  t.line(d, "add_layernorm%s_kernel<%d, %d>", row_form2(hidden) ? "2" : "", row_form(hidden), slabs);
+}
+
 void tail_line(Text& t, const Dims& d, int hidden, bool pair) {
   if (pair) t.line(d, "pair_head_kernel<%d>", hidden % 128 == 0 ? 2 : 1);
   else t.line(d, "pool_kernel");
@@ -367,7 +387,7 @@ void tail_line(Text& t, const Dims& d, int hidden, bool pair) {
 void proj_ln_lines(Text& t, const ProjLnPlan& s, int hidden) {
   if (s.rowln2) { t.line(s.d, s.variant ? "gemm_rowln2_kernel<64, 2>" : "gemm_rowln2_kernel<32, 4>"); return; }
   gemm_line(t, s.gemm);
-  ln_line(t, s.ln, hidden, s.gemm.slabs);
+  if (s.prenorm) add_ln_line(t, s.ln, hidden, s.gemm.slabs); else ln_line(t, s.ln, hidden, s.gemm.slabs);
 }
 
 }  // namespace
@@ -405,6 +425,7 @@ int enc_plan_describe(const EncPlan& p, char* buf, size_t cap) {
   gemm_line(t, p.qkv);
   if (p.rotary) t.line(p.rope, "rope_qk_kernel<%d>", p.attn.hd);
   attn_line(t, p.attn);
+  if (p.prenorm) attn_line(t, p.win);   // the sliding layers run this one in place of the line above
   proj_ln_lines(t, p.out, p.hidden);
   gemm_line(t, p.up);
   proj_ln_lines(t, p.down, p.hidden);
@@ -419,6 +440,7 @@ int row_plan_describe(int kind, int rows, int hidden, int arg, char* buf, size_t
     case kRowLayerNorm: ln_line(t, plan_rows(rows), hidden, arg); break;
     case kRowPool: tail_line(t, plan_pool(rows), hidden, false); break;
     case kRowPairHead: tail_line(t, plan_pair_head(rows, hidden), hidden, true); break;
+    case kRowAddLayerNorm: add_ln_line(t, plan_rows(rows), hidden, arg); break;
     default: break;
   }
   return t.len;

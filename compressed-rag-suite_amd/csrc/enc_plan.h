@@ -40,7 +40,7 @@ enum class GemmFamily { None, Tiled, Panel, Stream, StreamKS, Big, Gemm8, Gemm8S
 
 // C = epilogue(A[M,K] W[N,K]^T): mode 0 fp16 (+ bias), 1 GELU fp16, 2 + bias + residual fp32, 3 fp32 partial slabs [slabs][M][N]
 // without bias (the LayerNorm that follows sums them and adds bias and residual), 4 silu(gate) * up fp16 [M, N / 2] (gate / up rows
-// of W interleaved in blocks of 16, include/crs_encoder.h: CRS_ENC_GATED_SILU)
+// of W interleaved in blocks of 16, include/crs_encoder.h: CRS_ENC_GATED_SILU), 5 gelu(gate) * up in the same layout (CRS_ENC_GATED_GELU)
 struct GemmPlan {
   GemmFamily family = GemmFamily::None;
   int m = 0, n = 0, k = 0, mode = 0;
@@ -55,9 +55,9 @@ struct GemmPlan {
 };
 
 // What crs_gemm_f16 and the encoder's fp16 / fp32 + residual projections run (modes 0..2): gemm8, then big, then stream, then tiled.
-// Mode 4: gemm8, else tiled (the big and stream families have no gated epilogue and are never planned for it).
+// Modes 4 and 5: gemm8, else tiled (the big and stream families have no gated epilogue and are never planned for them).
 GemmPlan plan_gemm(int m, int n, int k, int mode, int small_lds, int cus, const EncKnobs& kn);
-// The panel kernel on modes 0 / 1 / 3 / 4 (family None where K has no chunk); the caller decides that the shape is one for it.
+// The panel kernel on modes 0 / 1 / 3 / 4 / 5 (family None where K has no chunk); the caller decides that the shape is one for it.
 GemmPlan plan_gemm_panel(int m, int n, int k, int mode, int small_lds, const EncKnobs& kn);
 
 // The phase-scheduled 256 x 256 kernel's split-K form (mode 3, fp32 slabs summed by the LayerNorm): gemm8_splitk answers the slab
@@ -65,12 +65,13 @@ GemmPlan plan_gemm_panel(int m, int n, int k, int mode, int small_lds, const Enc
 int gemm8_splitk(int m, int n, int k, const EncKnobs& kn);
 GemmPlan plan_gemm8(int m, int n, int k, int mode, int splits, int cus, const EncKnobs& kn);
 
-enum class AttnForm { Fused, Blocked, Short, Seq, Seq32 };
+enum class AttnForm { Fused, Blocked, Short, Seq, Seq32, Window };
 struct AttnPlan {
   AttnForm form = AttnForm::Blocked;   // Fused: QKV projection + attention in one kernel (enc_qkvattn.hip), no QKV GEMM
   int hd = 0;
   bool bias = false;                   // Blocked only: relative-position bias
   int smax = 0, nw = 0, qt = 0;        // Seq / Seq32: template arguments
+  int window = 0;                      // Window only: the largest allowed |key - query|
   Dims d;
 };
 
@@ -78,6 +79,9 @@ struct AttnPlan {
 // a bias at every length; else the short kernel up to 16 tokens (head_dim 32 / 64), a whole-sequence kernel from 65 tokens up to the
 // length its LDS image holds (256, or 512 at head_dim 64), the blocked kernel otherwise -- as the attn_* knobs allow.
 AttnPlan plan_attention(int batch, int seq, int heads, int hd, bool bias, const EncKnobs& kn);
+// The sliding-window layers of a pre-norm model (attention_window_kernel): the blocked kernel's grid at every length, window >= 1 the
+// largest allowed |key - query|.  No knob moves it today.
+AttnPlan plan_attention_window(int batch, int seq, int heads, int hd, int window, const EncKnobs& kn);
 // The shapes qkv_attn_kernel takes (hidden a multiple of 128 up to 384, head_dim 32 / 64, its LDS image within kMaxLds, 16 / 32 / 64
 // tokens per sequence) and its plan, the one make_enc_plan puts into EncPlan::attn; the caller checked qkv_attn_supported.
 bool qkv_attn_supported(int hidden, int heads, int seq);
@@ -93,6 +97,7 @@ struct ProjLnPlan {
   Dims d;              // rowln2
   GemmPlan gemm;       // mode 3 (the LayerNorm adds bias and residual) or mode 2 (already folded in, slabs = 1)
   Dims ln;
+  bool prenorm = false;   // the row kernel is add_layernorm*_kernel (never rowln2)
 };
 
 // big_ln: the index-build side (make_enc_plan: more than 4096 tokens and CRS_ENC_BIGLN); then rowln2 where it has the shape, else
@@ -112,7 +117,9 @@ Dims plan_pair_head(int batch, int hidden);
 struct EncPlan {
   int hidden, heads, ffn, batch, seq, tokens;
   bool typed;          // embedding with a token-type row per token (pair forward with type ids)
-  bool rotary, gated;  // CRS_ENC_ROTARY: rope between qkv and attn, never Fused; CRS_ENC_GATED_SILU: up is mode 4 over 2 ffn rows
+  bool rotary, gated;  // CRS_ENC_ROTARY: rope between qkv and attn, never Fused; CRS_ENC_GATED_SILU / _GELU: up is mode 4 / 5 over 2 ffn rows
+  bool prenorm;        // CRS_ENC_PRENORM: out / down are a GEMM + add_layernorm (never Fused, never rowln2); win is the sliding layers' attention
+  AttnPlan win;        // prenorm only (form Window); attn is the full-attention layers' plan
   Dims rope;           // rotary only
   int pair;            // 0: pooling tail; else the pair head
   Dims embed, tail;
@@ -125,9 +132,10 @@ struct EncPlan {
   int max_split;
 };
 
-// flags: crs_encoder_desc.flags (SMALL_LDS 1, ROTARY 2, GATED_SILU 4); rel_bias: 1 with a relative-position bias; pair: 0 pooling tail, 1 pair head with type ids,
+// flags: crs_encoder_desc.flags (SMALL_LDS 1, ROTARY 2, GATED_SILU 4, PRENORM 8, GATED_GELU 16); window: PRENORM only, >= 1; rel_bias: 1 with a relative-position bias; pair: 0 pooling tail, 1 pair head with type ids,
 // 2 pair head without.  The sizes are check_desc's (hidden % 64 == 0 <= 1024, head_dim 16 / 32 / 64, ffn % 64 == 0).
-EncPlan make_enc_plan(int hidden, int heads, int ffn, int flags, int batch, int seq, int rel_bias, int pair, int cus, const EncKnobs& kn);
+EncPlan make_enc_plan(int hidden, int heads, int ffn, int flags, int batch, int seq, int rel_bias, int pair, int cus, const EncKnobs& kn,
+                      int window = 0);
 
 // One line per launch of embedding, ONE layer and the tail, in launch order: "<kernel><template arguments> grid=XxYxZ wg=Nx1x1 lds=BYTES\n"
 // (grid in workgroups, dynamic LDS).  Returns the length of the whole text (snprintf): > cap - 1 means it was cut.
@@ -138,7 +146,8 @@ int enc_plan_describe(const EncPlan& p, char* buf, size_t cap);
 // One row kernel's line, as enc_plan_describe and proj_ln_plan_describe print it (include/crs_encoder.h: crs_row_plan_describe).
 // kind 0: embedding, rows = tokens, arg != 0 with type ids; 1: LayerNorm, rows = tokens, arg = slabs; 2: pooling, rows = batch;
 // 3: pair head, rows = batch.  The caller has checked the sizes; an unknown kind gives the empty text.
-enum RowKind { kRowEmbed = 0, kRowLayerNorm = 1, kRowPool = 2, kRowPairHead = 3 };
+// 4: the pre-norm add + LayerNorm, rows = tokens, arg = slabs.
+enum RowKind { kRowEmbed = 0, kRowLayerNorm = 1, kRowPool = 2, kRowPairHead = 3, kRowAddLayerNorm = 4 };
 int row_plan_describe(int kind, int rows, int hidden, int arg, char* buf, size_t cap);
 
 }  // namespace crs

@@ -980,10 +980,10 @@ void enc_args(const Tensor& ids, at::TensorList weights, at::IntArrayRef desc, d
   a.layers.resize((size_t)a.d.layers);
   for (int l = 0; l < a.d.layers; ++l) {
     const Tensor* w = &weights[5 + 12 * l];
-    a.layers[l] = crs_encoder_layer{w[0].data_ptr(), (const float*)w[1].data_ptr(), w[2].data_ptr(), (const float*)w[3].data_ptr(),
-                                    (const float*)w[4].data_ptr(), (const float*)w[5].data_ptr(), w[6].data_ptr(),
-                                    w[7].numel() ? (const float*)w[7].data_ptr() : nullptr,   // an EMPTY b_up is NULL (CRS_ENC_GATED_SILU without bias)
-                                    w[8].data_ptr(), (const float*)w[9].data_ptr(), (const float*)w[10].data_ptr(), (const float*)w[11].data_ptr()};
+    // an EMPTY vector is NULL for the library: b_up (CRS_ENC_GATED_SILU without bias); under CRS_ENC_PRENORM every bias and layer 0's ln1_g
+    const auto vec = [](const Tensor& t) { return t.numel() ? (const float*)t.data_ptr() : nullptr; };
+    a.layers[l] = crs_encoder_layer{w[0].data_ptr(), vec(w[1]), w[2].data_ptr(), vec(w[3]), vec(w[4]), vec(w[5]), w[6].data_ptr(), vec(w[7]),
+                                    w[8].data_ptr(), vec(w[9]), vec(w[10]), vec(w[11])};
   }
   a.cw = crs_encoder_weights{(const float*)weights[0].data_ptr(), weights[1].numel() ? (const float*)weights[1].data_ptr() : nullptr,
                              (const float*)weights[2].data_ptr(),
@@ -1038,6 +1038,56 @@ void encoder_forward_rope(const Tensor& ids, const Tensor& lens, at::TensorList 
   }
   ok(crs_encoder_forward_rope(&d, &cw, ids.data_ptr<int32_t>(), lens.data_ptr<int32_t>(), b, s, workspace.data_ptr(), (size_t)workspace.nbytes(),
                               out.data_ptr<float>(), normalize ? 1 : 0, hid, cur_stream(ids), &ext, &rope), "crs::encoder_forward");
+}
+
+// encoder_forward_prenorm: descriptors with CRS_ENC_PRENORM (crs_encoder_prenorm): the two rope tables fp32 [positions, head_dim], the
+// window, the full-attention period, the final norm's gain and (optional) bias
+void encoder_forward_prenorm(const Tensor& ids, const Tensor& lens, at::TensorList weights, at::IntArrayRef desc, double ln_eps, Tensor workspace,
+                             Tensor out, c10::optional<Tensor> q16_out, int64_t slab_type, bool normalize, c10::optional<Tensor> hidden_out,
+                             const Tensor& rope_global, const Tensor& rope_local, int64_t window, int64_t global_every, const Tensor& final_ln_g,
+                             c10::optional<Tensor> final_ln_b) {
+  want(ids, at::kInt, "ids");
+  want(lens, at::kInt, "lens");
+  want(out, at::kFloat, "out");
+  want(rope_global, at::kFloat, "rope_global");
+  want(rope_local, at::kFloat, "rope_local");
+  want(final_ln_g, at::kFloat, "final_ln_g");
+  EncArgs ea;
+  enc_args(ids, weights, desc, ln_eps, ea);
+  const crs_encoder_desc& d = ea.d;
+  TORCH_CHECK(ids.dim() == 2 && lens.numel() == ids.size(0) && out.numel() == ids.size(0) * d.hidden, "ids [B, S], lens [B], out [B, H]");
+  same_device(ids, {&lens, &workspace, &out, opt_t(q16_out), opt_t(hidden_out), &rope_global, &rope_local, &final_ln_g, opt_t(final_ln_b)},
+              "crs::encoder_forward_prenorm");
+  TORCH_CHECK(rope_global.dim() == 2 && rope_global.size(1) * d.heads == d.hidden && rope_local.sizes() == rope_global.sizes(),
+              "rope_global and rope_local must both be [positions, head_dim]");
+  TORCH_CHECK(final_ln_g.numel() == d.hidden, "final_ln_g must be [H]");
+  TORCH_CHECK(window >= INT32_MIN && window <= INT32_MAX && global_every >= INT32_MIN && global_every <= INT32_MAX, "window / global_every out of range");
+  crs_encoder_prenorm pre{rope_global.data_ptr<float>(), rope_local.data_ptr<float>(), (int32_t)rope_global.size(0), (int32_t)window,
+                          (int32_t)global_every, final_ln_g.data_ptr<float>(), nullptr};
+  if (final_ln_b.has_value() && final_ln_b->defined() && final_ln_b->numel()) {
+    want(*final_ln_b, at::kFloat, "final_ln_b");
+    TORCH_CHECK(final_ln_b->numel() == d.hidden, "final_ln_b must be [H]");
+    pre.final_ln_b = final_ln_b->data_ptr<float>();
+  }
+  const int b = (int)ids.size(0), s = (int)ids.size(1);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(ids.device());
+  if (q16_out.has_value() && q16_out->defined()) {
+    want(*q16_out, at::kHalf, "q16_out");
+    TORCH_CHECK(normalize && !(hidden_out.has_value() && hidden_out->defined()), "q16_out needs normalize=True and no hidden_out");
+    TORCH_CHECK(q16_out->numel() == (int64_t)b * crs_row_elems(d.hidden, (int)slab_type), "q16_out must be [B, crs_row_elems(H, slab_type)]");
+    ok(crs_encoder_forward_queries_prenorm(&d, &ea.cw, ids.data_ptr<int32_t>(), lens.data_ptr<int32_t>(), b, s, workspace.data_ptr(),
+                                           (size_t)workspace.nbytes(), out.data_ptr<float>(), q16_out->data_ptr(), (int)slab_type, cur_stream(ids), &pre),
+       "crs::encoder_forward_prenorm");
+    return;
+  }
+  float* hid = nullptr;
+  if (hidden_out.has_value() && hidden_out->defined()) {
+    want(*hidden_out, at::kFloat, "hidden_out");
+    TORCH_CHECK(hidden_out->numel() == (int64_t)b * s * d.hidden, "hidden_out must be [B, S, H]");
+    hid = hidden_out->data_ptr<float>();
+  }
+  ok(crs_encoder_forward_prenorm(&d, &ea.cw, ids.data_ptr<int32_t>(), lens.data_ptr<int32_t>(), b, s, workspace.data_ptr(), (size_t)workspace.nbytes(),
+                                 out.data_ptr<float>(), normalize ? 1 : 0, hid, cur_stream(ids), &pre), "crs::encoder_forward_prenorm");
 }
 
 void encoder_forward_ex(const Tensor& ids, const Tensor& lens, at::TensorList weights, at::IntArrayRef desc, double ln_eps, Tensor workspace,
@@ -1171,6 +1221,9 @@ TORCH_LIBRARY(crs, m) {
         "Tensor(c!)? q16_out, int slab_type, bool normalize, Tensor(d!)? hidden_out, Tensor? rel_bias=None) -> ()");
   m.def("encoder_forward_rope(Tensor ids, Tensor lens, Tensor[] weights, int[] desc, float ln_eps, Tensor(a!) workspace, Tensor(b!) out, "
         "Tensor(c!)? q16_out, int slab_type, bool normalize, Tensor(d!)? hidden_out, Tensor? rel_bias=None, Tensor? rope_table=None) -> ()");
+  m.def("encoder_forward_prenorm(Tensor ids, Tensor lens, Tensor[] weights, int[] desc, float ln_eps, Tensor(a!) workspace, Tensor(b!) out, "
+        "Tensor(c!)? q16_out, int slab_type, bool normalize, Tensor(d!)? hidden_out, Tensor rope_global, Tensor rope_local, int window, "
+        "int global_every, Tensor final_ln_g, Tensor? final_ln_b=None) -> ()");
   m.def("encoder_score_pairs(Tensor ids, Tensor? type_ids, Tensor lens, Tensor[] weights, Tensor[] head, int[] desc, float ln_eps, "
         "int activation, Tensor(a!) workspace, Tensor(b!) scores, Tensor(c!)? pooled_out, Tensor(d!)? hidden_out) -> ()");
 }
@@ -1218,5 +1271,6 @@ TORCH_LIBRARY_IMPL(crs, CUDA, m) {   // the HIP backend of torch-ROCm dispatches
   m.impl("encoder_forward", &encoder_forward);
   m.impl("encoder_forward_ex", &encoder_forward_ex);
   m.impl("encoder_forward_rope", &encoder_forward_rope);
+  m.impl("encoder_forward_prenorm", &encoder_forward_prenorm);
   m.impl("encoder_score_pairs", &encoder_score_pairs);
 }

@@ -9,7 +9,10 @@ and ``pos_offset`` set: the bias is resolved per offset on the host and handed t
 (nomic-embed-text: ``ModelShape.rotary_theta`` > 0 and ``gated``) come in under transformers' NomicBertModel names
 (``layers.N.self_attn.q_proj`` ..., ``mlp.gate_proj`` / ``up_proj`` / ``down_proj``): the gate and up matrices are interleaved
 into one ``w_up`` (``interleave_gate_up``), the cos / sin table is built on the host (``rope_table``) and the forward goes
-through ``torch.ops.crs.encoder_forward_rope``.  Token ids in, pooled sentence embeddings out; no CPU fallback.
+through ``torch.ops.crs.encoder_forward_rope``.  ModernBERT checkpoints (``ModelShape.prenorm``: pre-norm layers, sliding-window
+attention in the layers that are not a multiple of ``global_every``, two rope thetas, GeGLU) come in under ModernBertModel's
+names (``layers.N.attn.Wqkv`` / ``attn.Wo`` / ``attn_norm`` / ``mlp_norm`` / ``mlp.Wi`` / ``mlp.Wo``, ``final_norm``) and go through
+``torch.ops.crs.encoder_forward_prenorm``.  Token ids in, pooled sentence embeddings out; no CPU fallback.
 """
 from __future__ import annotations
 
@@ -26,6 +29,8 @@ POOL_MEAN, POOL_CLS = 0, 1
 ENC_SMALL_LDS = 1      # CRS_ENC_SMALL_LDS: kernel forms of <= 48 KB of LDS (forwards that run beside a scan)
 ENC_ROTARY = 2         # CRS_ENC_ROTARY: rope_qk_kernel between the QKV projection and attention, no position table
 ENC_GATED_SILU = 4     # CRS_ENC_GATED_SILU: w_up holds interleaved gate / up rows, FFN-up runs GEMM mode 4
+ENC_PRENORM = 8        # CRS_ENC_PRENORM: pre-norm layers + sliding-window attention (crs_encoder_forward_prenorm)
+ENC_GATED_GELU = 16    # CRS_ENC_GATED_GELU: the gated layout with the erf GELU on the activated half (GEMM mode 5)
 GATE_UP_BLOCK = 16     # rows of a gate (or up) block of the interleaved layout (include/crs_encoder.h)
 
 
@@ -50,6 +55,11 @@ class EncoderExt(Structure):      # crs_encoder_ext
 
 class EncoderRope(Structure):     # crs_encoder_rope
     _fields_ = [("table_dev", c_void_p), ("positions", c_int32)]
+
+
+class EncoderPrenorm(Structure):  # crs_encoder_prenorm
+    _fields_ = [("rope_global_dev", c_void_p), ("rope_local_dev", c_void_p), ("positions", c_int32), ("window", c_int32),
+                ("global_every", c_int32), ("final_ln_g", c_void_p), ("final_ln_b", c_void_p)]
 
 
 class EncoderHead(Structure):     # crs_encoder_head
@@ -104,6 +114,16 @@ nat.register_signatures({
     "crs_pair_head_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                   c_void_p]),
     "crs_row_plan_describe": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_size_t]),
+    # pre-norm models (the forward reaches them through torch.ops.crs.encoder_forward_prenorm) and their kernels on their own
+    "crs_encoder_forward_prenorm": (c_int, [POINTER(EncoderDesc), POINTER(EncoderWeights), c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                            c_size_t, c_void_p, c_int, c_void_p, c_void_p, POINTER(EncoderPrenorm)]),
+    "crs_encoder_forward_queries_prenorm": (c_int, [POINTER(EncoderDesc), POINTER(EncoderWeights), c_void_p, c_void_p, c_int, c_int,
+                                                    c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_void_p, POINTER(EncoderPrenorm)]),
+    "crs_encoder_prenorm_plan_describe": (c_int, [POINTER(EncoderDesc), c_int, c_int, c_int, c_void_p, c_size_t]),
+    "crs_attention_window_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "crs_attention_window_plan_describe": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t]),
+    "crs_add_layernorm_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_void_p, c_void_p,
+                                      c_void_p, c_void_p]),
 })
 
 
@@ -123,6 +143,21 @@ class ModelShape:
     pos_offset: int = 0           # first position id (MPNet: pad_token_id + 1 = 2); max_pos counts the table's rows
     rotary_theta: float = 0.0     # > 0: rotary position embedding of Q and K with this base, no position table (nomic: 1000)
     gated: bool = False           # SwiGLU feed-forward: silu(x Wgate^T) * (x Wup^T) in place of GELU(x W^T + b)
+    # ModernBERT: pre-norm layers; rotary_theta is the full-attention layers' base and local_theta the sliding layers'
+    prenorm: bool = False         # x += attn(LN(x)), x += mlp(LN(x)), a final norm after the last layer
+    window: int = 0               # largest |key - query| of a sliding layer (local_attention // 2)
+    global_every: int = 1         # layer i attends the whole sequence when i % global_every == 0
+    local_theta: float = 0.0
+    gelu_gated: bool = False      # GeGLU: Wo(gelu(input) * gate), (input, gate) = Wi(x).chunk(2)
+
+
+def interleave_wi(wi) -> np.ndarray:
+    """ModernBERT's Wi [2F, ...] (its output is chunked into (input, gate): rows [0, F) feed the GELU, rows [F, 2F) multiply) in the
+    layout CRS_ENC_GATED_GELU takes: the activated half in the "gate" rows of interleave_gate_up, the linear half in the "up" rows."""
+    w = np.asarray(wi)
+    if w.shape[0] % 2:
+        raise ValueError(f"Wi must have an even number of rows, got {w.shape}")
+    return interleave_gate_up(w[: w.shape[0] // 2], w[w.shape[0] // 2:])
 
 
 def interleave_gate_up(gate, up) -> np.ndarray:
@@ -253,6 +288,29 @@ def rope_qk_f16(qkv, table, batch: int, seq: int, heads: int) -> None:
 
 
 ROW_EMBED, ROW_LAYERNORM, ROW_POOL, ROW_PAIR_HEAD = 0, 1, 2, 3   # crs_row_plan_describe's kinds
+ROW_ADD_LAYERNORM = 4
+
+
+def attention_window_plan_describe(batch: int, seq: int, hidden: int, heads: int, window: int) -> str:
+    """The launch line of attention_window_f16 for these sizes (crs_attention_window_plan_describe); needs no device."""
+    lib = nat.load()
+    return _describe(lambda sl, buf, cap: lib.crs_attention_window_plan_describe(batch, seq, hidden, heads, int(window), buf, cap))[0]
+
+
+def attention_window_f16(qkv, lens, ctx, batch: int, seq: int, heads: int, window: int) -> None:
+    """crs_attention_window_f16: ctx (cuda fp16 [batch * seq, H]) <- attention of qkv (cuda fp16 [batch * seq, 3 H]) over the keys with
+    |key - query| <= window and key < lens[b]; a query without any allowed key gets a zero row."""
+    nat.check(nat.load().crs_attention_window_f16(nat._ptr(qkv), nat._ptr(lens), nat._ptr(ctx), int(batch), int(seq),
+                                                  int(qkv.shape[1]) // 3, int(heads), int(window), nat._stream_ptr()))
+
+
+def add_layernorm_f32(y, bias, residual, g, b, eps: float, r32, x16, n32=None) -> None:
+    """crs_add_layernorm_f32: r32 (cuda fp32 [tokens, H]) <- sum of the slabs of y (cuda fp32 [nsplit, tokens, H]) + bias + residual;
+    x16 (fp16) and n32 (fp32 or None) <- LayerNorm(r32) g + b.  bias / residual / b may be None, residual may be r32."""
+    nsplit, tokens, hidden = y.shape
+    nat.check(nat.load().crs_add_layernorm_f32(nat._ptr(y), int(nsplit), nat._ptr(bias), nat._ptr(residual), nat._ptr(g), nat._ptr(b),
+                                               float(eps), int(tokens), int(hidden), nat._ptr(r32), nat._ptr(x16), nat._ptr(n32),
+                                               nat._stream_ptr()))
 
 
 def row_plan_describe(kind: int, rows: int, hidden: int, arg: int = 0) -> str:
@@ -338,12 +396,18 @@ class HipEncoder:
         if not 0 <= shape.pos_offset < shape.max_pos:
             raise ValueError("pos_offset must be inside the position table")
         self.rope_table = None        # cuda fp32 [min(max_seq, max_pos), head_dim] of a rotary model
-        rotary, gated = shape.rotary_theta > 0, bool(shape.gated)
+        prenorm = bool(shape.prenorm)
+        rotary, gated = shape.rotary_theta > 0, bool(shape.gated) or bool(shape.gelu_gated)
         if rotary != gated:
             raise NotImplementedError("rotary_theta and gated come together (nomic-embed-text): no loader builds one without the other")
+        if prenorm != bool(shape.gelu_gated) or (prenorm and shape.gated):
+            raise NotImplementedError("prenorm and gelu_gated come together (ModernBERT): no loader builds one without the other")
+        if prenorm and (not rotary or shape.local_theta <= 0 or shape.window < 1 or shape.global_every < 1):
+            raise ValueError("a prenorm model needs rotary_theta > 0, local_theta > 0, window >= 1 and global_every >= 1")
         if rotary and (shape.rel_buckets or shape.pos_offset):
             raise ValueError("a rotary model has no position table: rel_buckets and pos_offset must be 0")
-        flags = (ENC_ROTARY if rotary else 0) | (ENC_GATED_SILU if gated else 0)
+        flags = (ENC_ROTARY if rotary else 0) | (ENC_GATED_SILU if shape.gated else 0)
+        flags |= (ENC_PRENORM | ENC_GATED_GELU) if prenorm else 0
         self.desc = EncoderDesc(shape.vocab_size, shape.hidden, shape.layers, shape.heads, shape.ffn,
                                 shape.max_pos - shape.pos_offset, shape.ln_eps, POOL_CLS if shape.pooling == "cls" else POOL_MEAN, flags)
         self._layers = (EncoderLayer * shape.layers)()
@@ -377,6 +441,30 @@ class HipEncoder:
                 dev32(p + "post_mlp_layernorm.weight"), dev32(p + "post_mlp_layernorm.bias"),
             ]
 
+        empty = np.zeros(0, dtype=np.float32)      # an EMPTY vector is NULL for the library
+
+        def modernbert_layer(i):
+            """the 12 tensors of crs_encoder_layer from ModernBertModel's names: ln1 = attn_norm (absent on layer 0: identity), ln2 =
+            mlp_norm; biases only where the checkpoint carries them, EMPTY (NULL) otherwise"""
+            p = f"layers.{i}."
+
+            def opt(name, arr=None):
+                return keep(weights[name] if arr is None else arr) if name in weights else keep(empty)
+
+            if i > 0 and p + "attn_norm.weight" not in weights:
+                raise ValueError(f"{p}attn_norm.weight is missing (only layer 0 has no attention norm)")
+            if i == 0 and (p + "attn_norm.weight" in weights or p + "attn_norm.bias" in weights):
+                raise ValueError(f"{p}attn_norm.* is present: layer 0 of a pre-norm model has no attention norm, and the forward would ignore it")
+            wi_b = interleave_wi(weights[p + "mlp.Wi.bias"]) if p + "mlp.Wi.bias" in weights else None
+            return [
+                dev16(p + "attn.Wqkv.weight"), opt(p + "attn.Wqkv.bias"),
+                dev16(p + "attn.Wo.weight"), opt(p + "attn.Wo.bias"),
+                opt(p + "attn_norm.weight"), opt(p + "attn_norm.bias"),
+                keep(interleave_wi(weights[p + "mlp.Wi.weight"]), torch.float16), opt(p + "mlp.Wi.bias", wi_b),
+                dev16(p + "mlp.Wo.weight"), opt(p + "mlp.Wo.bias"),
+                dev32(p + "mlp_norm.weight"), opt(p + "mlp_norm.bias"),
+            ]
+
         def bert_layer(i):
             p = f"encoder.layer.{i}."
             return [
@@ -391,7 +479,7 @@ class HipEncoder:
 
         layer_tensors = []
         for i in range(shape.layers):
-            vals = nomic_layer(i) if rotary else bert_layer(i)
+            vals = modernbert_layer(i) if prenorm else nomic_layer(i) if rotary else bert_layer(i)
             layer_tensors += vals
             for (fname, _), t in zip(EncoderLayer._fields_, vals):
                 setattr(self._layers[i], fname, t.data_ptr() if t.numel() else None)
@@ -399,8 +487,12 @@ class HipEncoder:
             pos = keep(np.zeros((0, shape.hidden), dtype=np.float32))
         else:           # (a contiguous view of the kept tensor from its row pos_offset on)
             pos = dev32("embeddings.position_embeddings.weight")[shape.pos_offset:]
-        emb = [dev32("embeddings.word_embeddings.weight"), pos, dev32("embeddings.token_type_embeddings.weight"),
-               dev32("embeddings.LayerNorm.weight"), dev32("embeddings.LayerNorm.bias")]
+        if prenorm:     # ModernBERT: no token types (a zero row), norms without bias unless the checkpoint carries one
+            emb = [dev32("embeddings.tok_embeddings.weight"), pos, keep(np.zeros((1, shape.hidden), dtype=np.float32)),
+                   dev32("embeddings.norm.weight"), bias_or_zeros("embeddings.norm.bias", shape.hidden)]
+        else:
+            emb = [dev32("embeddings.word_embeddings.weight"), pos, dev32("embeddings.token_type_embeddings.weight"),
+                   dev32("embeddings.LayerNorm.weight"), dev32("embeddings.LayerNorm.bias")]
         self.weights = EncoderWeights(*[t.data_ptr() if t.numel() else None for t in emb], ctypes.cast(self._layers, POINTER(EncoderLayer)))
         self._ws = None
         # the same tensors in the order torch.ops.crs.encoder_forward takes them (csrc/torch_ops.cpp): embeddings, then 12 per layer
@@ -409,6 +501,11 @@ class HipEncoder:
         if rotary:
             self.rope_table = torch.from_numpy(rope_table(min(shape.max_seq, shape.max_pos), shape.hidden // shape.heads,
                                                           shape.rotary_theta)).to(self.device)
+        self.rope_local = self.final_ln = None
+        if prenorm:
+            self.rope_local = torch.from_numpy(rope_table(min(shape.max_seq, shape.max_pos), shape.hidden // shape.heads,
+                                                          shape.local_theta)).to(self.device)
+            self.final_ln = (dev32("final_norm.weight"), dev32("final_norm.bias") if "final_norm.bias" in weights else None)
         # additive relative-position bias, resolved per offset once: fp32 [heads, 2 * max_seq - 1] (crs_encoder_ext)
         self.rel_bias = None
         if shape.rel_buckets > 0:
@@ -438,6 +535,12 @@ class HipEncoder:
         switch `desc.pooling` are honoured)."""
         d = self.desc
         return [d.vocab_size, d.hidden, d.layers, d.heads, d.ffn, d.max_pos, d.pooling, d.flags]
+
+    def prenorm_plan_describe(self, batch: int, seq: int) -> str:
+        """The launches of a pre-norm model's forward on the current device, one line each (crs_encoder_prenorm_plan_describe): the
+        full-attention layers' attention line, then the sliding layers'."""
+        lib = nat.load()
+        return _describe(lambda sl, buf, cap: lib.crs_encoder_prenorm_plan_describe(byref(self.desc), batch, seq, int(self.shape.window), buf, cap))[0]
 
     def workspace_bytes(self, batch: int, seq: int) -> int:
         out = c_size_t(0)
@@ -478,7 +581,11 @@ class HipEncoder:
         if small_lds:          # per call, not process-wide: the role-lane engine asks for it, everyone else gets the default forms
             desc = desc[:7] + [desc[7] | ENC_SMALL_LDS]
         with nat._translate():
-            if self.desc.flags & ENC_ROTARY:
+            if self.desc.flags & ENC_PRENORM:
+                nat.ops().encoder_forward_prenorm(ids, lens, self._wlist, desc, float(self.desc.ln_eps), ws, out, q16_out,
+                                                  int(slab_type), bool(normalize), hidden, self.rope_table, self.rope_local,
+                                                  int(self.shape.window), int(self.shape.global_every), self.final_ln[0], self.final_ln[1])
+            elif self.desc.flags & ENC_ROTARY:
                 nat.ops().encoder_forward_rope(ids, lens, self._wlist, desc, float(self.desc.ln_eps), ws, out, q16_out,
                                                int(slab_type), bool(normalize), hidden, self.rel_bias, self.rope_table)
             else:

@@ -10,7 +10,7 @@ Model resolution, offline by construction (the reference fetches by hub name, wh
 here): ``model_path`` (additive key) or ``model_name`` may be a LOCAL sentence-transformers
 directory (config.json, model.safetensors, vocab.txt, optional sentence_bert_config.json and
 1_Pooling/config.json); else ``$CRS_MODEL_DIR/<basename of model_name>`` is tried; else, when
-``model_name`` is ``synthetic:<minilm|bge|tiny|mpnet|tiny-mpnet|tiny-xlmr|multilingual-minilm|multilingual-e5-base|tiny-nomic|nomic-embed-text>`` or ``CRS_ALLOW_SYNTHETIC_WEIGHTS=1`` is set,
+``model_name`` is ``synthetic:<minilm|bge|tiny|mpnet|tiny-mpnet|tiny-xlmr|multilingual-minilm|multilingual-e5-base|tiny-nomic|nomic-embed-text|tiny-modernbert|modernbert-base>`` or ``CRS_ALLOW_SYNTHETIC_WEIGHTS=1`` is set,
 seeded random weights of the named architecture are used with a hash tokeniser (plumbing and
 benchmarks only -- embeddings are then meaningless as language).  Anything else raises.
 
@@ -62,9 +62,17 @@ _KNOWN = {
                        rotary_theta=1000.0, gated=True),
     "nomic-embed-text": dict(vocab_size=30528, hidden=768, layers=12, heads=12, ffn=3072, max_pos=8192, pooling="mean", max_seq=512,
                              rotary_theta=1000.0, gated=True),
+    # ModernBERT (nomic-ai/modernbert-embed-base, Alibaba-NLP/gte-modernbert-base, answerdotai/ModernBERT-base): pre-norm layers,
+    # every third layer attends the whole sequence (rope base 160000) and the others a +-64 window (base 10000), GeGLU, no biases,
+    # byte-level BPE vocabulary of 50368 ids, 8192 positions
+    "tiny-modernbert": dict(vocab_size=1000, hidden=64, layers=4, heads=4, ffn=128, max_pos=256, pooling="mean", max_seq=256,
+                            ln_eps=1e-5, rotary_theta=160000.0, local_theta=10000.0, prenorm=True, gelu_gated=True, window=8, global_every=3),
+    "modernbert-base": dict(vocab_size=50368, hidden=768, layers=22, heads=12, ffn=1152, max_pos=8192, pooling="mean", max_seq=8192,
+                            ln_eps=1e-5, rotary_theta=160000.0, local_theta=10000.0, prenorm=True, gelu_gated=True, window=64, global_every=3),
 }
 _ALIASES = {"minilm": "all-minilm-l6-v2", "bge": "bge-base-en-v1.5", "bge-base": "bge-base-en-v1.5", "mpnet": "all-mpnet-base-v2",
-            "nomic": "nomic-embed-text", "nomic-embed-text-v1": "nomic-embed-text", "nomic-embed-text-v1.5": "nomic-embed-text"}
+            "nomic": "nomic-embed-text", "nomic-embed-text-v1": "nomic-embed-text", "nomic-embed-text-v1.5": "nomic-embed-text",
+            "modernbert": "modernbert-base", "modernbert-embed-base": "modernbert-base", "gte-modernbert-base": "modernbert-base"}
 REL_BIAS = "encoder.relative_attention_bias.weight"      # [buckets, heads], shared by all layers (MPNet)
 
 
@@ -115,6 +123,25 @@ def synthetic_weights(shape, seed: int = 0, scale: float = 0.05) -> Dict[str, np
     `rel_buckets` (MPNet) also get the relative-position bias table (~N(0, 0.5): real tables are O(1)) and, having no
     token types, a zero token-type table.  Gated (nomic) shapes: NomicBertModel's names, query / key projections ~N(0, 1 / hidden)."""
     h, f = shape.hidden, shape.ffn
+    if getattr(shape, "prenorm", False):    # ModernBERT under ModernBertModel's names: no position table, no token types, no biases
+        names = [("embeddings.tok_embeddings.weight", (shape.vocab_size, h)), ("embeddings.norm.weight", (h,))]
+        for i in range(shape.layers):
+            p = f"layers.{i}."
+            names += ([(p + "attn_norm.weight", (h,))] if i else []) + [
+                (p + "attn.Wqkv.weight", (3 * h, h)), (p + "attn.Wo.weight", (h, h)), (p + "mlp_norm.weight", (h,)),
+                (p + "mlp.Wi.weight", (2 * f, h)), (p + "mlp.Wo.weight", (h, f))]
+        names.append(("final_norm.weight", (h,)))
+        out = {}
+        for idx, (name, shp) in enumerate(names):
+            rng = np.random.Generator(np.random.PCG64([seed, idx]))
+            if name.endswith("norm.weight"):
+                a = 1.0 + 0.05 * rng.standard_normal(shp, dtype=np.float32)
+            else:
+                a = scale * rng.standard_normal(shp, dtype=np.float32)
+                if name.endswith("attn.Wqkv.weight"):      # query / key rows ~N(0, 1 / h), as for the nomic shapes below
+                    a[: 2 * h] = h ** -0.5 * rng.standard_normal((2 * h, h), dtype=np.float32)
+            out[name] = a.astype(np.float32)
+        return out
     if getattr(shape, "gated", False):      # nomic-embed-text under NomicBertModel's names: no position table, no biases
         names = [("embeddings.word_embeddings.weight", (shape.vocab_size, h)), ("embeddings.token_type_embeddings.weight", (2, h)),
                  ("embeddings.LayerNorm.weight", (h,)), ("embeddings.LayerNorm.bias", (h,))]
@@ -257,6 +284,71 @@ def _nomic_shape_and_weights(cfg: dict, raw: Dict[str, np.ndarray], pooling: str
     return shape, weights
 
 
+def _modernbert_shape_and_weights(cfg: dict, raw: Dict[str, np.ndarray], pooling: str, max_seq):
+    """(ModelShape, weights under ModernBertModel's names) of a model_type "modernbert" directory; tensor names with or without
+    a leading "model.".  Every option this encoder does not run is refused by name."""
+    from rag._encoder import ModelShape
+    for arch in cfg.get("architectures") or []:
+        if arch != "ModernBertModel":
+            raise NotImplementedError(f"modernbert: architecture '{arch}' (a task head) is not supported: save the bare ModernBertModel "
+                                      f"(a sentence-transformers directory holds one)")
+    act = str(cfg.get("hidden_activation", "gelu")).lower()
+    if act != "gelu":
+        raise NotImplementedError(f"modernbert: hidden_activation '{act}' is not supported (gelu is)")
+    hidden, heads, layers = int(cfg["hidden_size"]), int(cfg["num_attention_heads"]), int(cfg["num_hidden_layers"])
+    ffn, max_pos = int(cfg["intermediate_size"]), int(cfg.get("max_position_embeddings", 8192))
+    # which layers attend the whole sequence: layer_types (transformers 5.x) or global_attn_every_n_layers
+    types = cfg.get("layer_types")
+    if types is not None:
+        if len(types) != layers or any(t not in ("full_attention", "sliding_attention") for t in types):
+            raise NotImplementedError(f"modernbert: layer_types {types} must name full_attention / sliding_attention once per layer")
+        full = [i for i, t in enumerate(types) if t == "full_attention"]
+        every = full[1] if len(full) > 1 else layers
+        if not full or full[0] != 0 or full != list(range(0, layers, every)):
+            raise NotImplementedError(f"modernbert: layer_types {types} are not periodic (full attention in layers 0, n, 2 n, ...)")
+    else:
+        every = int(cfg.get("global_attn_every_n_layers", 3))
+        if every < 1:
+            raise NotImplementedError(f"modernbert: global_attn_every_n_layers {every} is not supported")
+    rp = cfg.get("rope_parameters")
+    if rp:
+        thetas = {}
+        for kind in ("full_attention", "sliding_attention"):
+            one = dict(rp.get(kind) or {}) if ("full_attention" in rp or "sliding_attention" in rp) else dict(rp)
+            if one.get("rope_type", "default") != "default" or one.get("factor") not in (None, 1, 1.0):
+                raise NotImplementedError(f"modernbert: rope scaling ({kind}: rope_type '{one.get('rope_type')}', factor {one.get('factor')}) is not supported")
+            if "rope_theta" not in one:
+                raise NotImplementedError(f"modernbert: rope_parameters has no rope_theta for {kind}")
+            thetas[kind] = float(one["rope_theta"])
+        g_theta, l_theta = thetas["full_attention"], thetas["sliding_attention"]
+    else:
+        if cfg.get("rope_scaling") not in (None, {}):
+            raise NotImplementedError(f"modernbert: rope scaling ({cfg.get('rope_scaling')}) is not supported")
+        g_theta = float(cfg.get("global_rope_theta", 160000.0))
+        l_theta = float(cfg.get("local_rope_theta") or g_theta)
+    window = int(cfg.get("local_attention", 128)) // 2
+    if window < 1:
+        raise NotImplementedError(f"modernbert: local_attention {cfg.get('local_attention')} leaves no window")
+    weights = {(k[6:] if k.startswith("model.") else k): np.asarray(v, dtype=np.float32) for k, v in raw.items()}
+    for k in weights:
+        if k.split(".", 1)[0] in ("head", "decoder", "classifier"):
+            raise NotImplementedError(f"modernbert: tensor '{k}' belongs to a task head (ModernBertForMaskedLM / ForSequenceClassification): not supported")
+    # a bias the config announces must be in the file (the kernels run without one where it is absent, which would be silent)
+    need = [("norm_bias", ["embeddings.norm.bias", "final_norm.bias"] + [f"layers.{i}.mlp_norm.bias" for i in range(layers)]
+             + [f"layers.{i}.attn_norm.bias" for i in range(1, layers)]),
+            ("attention_bias", [f"layers.{i}.attn.{n}.bias" for i in range(layers) for n in ("Wqkv", "Wo")]),
+            ("mlp_bias", [f"layers.{i}.mlp.{n}.bias" for i in range(layers) for n in ("Wi", "Wo")])]
+    for key, names in need:
+        if cfg.get(key, False):
+            for n in names:
+                if n not in weights:
+                    raise NotImplementedError(f"modernbert: config says {key} = true but the checkpoint has no '{n}'")
+    shape = ModelShape(int(cfg["vocab_size"]), hidden, layers, heads, ffn, max_pos, float(cfg.get("norm_eps", 1e-5)), pooling,
+                       min(int(max_seq or max_pos), max_pos), rotary_theta=g_theta, local_theta=l_theta, prenorm=True, gelu_gated=True,
+                       window=window, global_every=every)
+    return shape, weights
+
+
 def _load_local_dir(path: str):
     """(ModelShape, weights dict, tokenizer, pre_lower, normalize_module) from a sentence-transformers directory.
 
@@ -309,8 +401,12 @@ def _load_local_dir(path: str):
         raw = load_file(os.path.join(tr_dir, "model.safetensors"))
         shape, weights = _nomic_shape_and_weights(cfg, raw, pooling, sbc_max_seq)
         return shape, weights, tokenizer_from_model_dir(tr_dir), pre_lower, has_normalize
+    if model_type == "modernbert":
+        raw = load_file(os.path.join(tr_dir, "model.safetensors"))
+        shape, weights = _modernbert_shape_and_weights(cfg, raw, pooling, sbc_max_seq)
+        return shape, weights, tokenizer_from_model_dir(tr_dir), pre_lower, has_normalize
     if model_type not in ("bert", "mpnet", "xlm-roberta"):
-        raise NotImplementedError(f"model_type '{model_type}' is not supported by this encoder (bert, mpnet and xlm-roberta are, and nomic_bert)")
+        raise NotImplementedError(f"model_type '{model_type}' is not supported by this encoder (bert, mpnet and xlm-roberta are, and nomic_bert, modernbert)")
     rel_buckets = pos_offset = 0
     if model_type == "mpnet":
         rel_buckets = int(cfg.get("relative_attention_num_buckets", 32))
@@ -332,7 +428,7 @@ def _load_local_dir(path: str):
 
 
 class EmbeddingModel:
-    """Sentence encoder wrapper (BERT, MPNet, XLM-RoBERTa and nomic-embed-text checkpoints) running on the GPU."""
+    """Sentence encoder wrapper (BERT, MPNet, XLM-RoBERTa, nomic-embed-text and ModernBERT checkpoints) running on the GPU."""
 
     def __init__(self, config: dict):
         self.tokenize_mode = config.get('tokenize', 'host')     # additive key: 'device' = csrc/wordpiece.hip feeds the encoder
@@ -350,6 +446,9 @@ class EmbeddingModel:
         self.has_normalize_module = None   # a sentence-transformers directory: whether its modules.json lists Normalize (else None)
         shape, weights, self.tokenizer = self._resolve(config)
         self._device_tokenizer = None
+        if self.tokenize_mode == 'device' and shape.prenorm:
+            raise NotImplementedError("rag.embedding.tokenize 'device' is not supported for ModernBERT models: their byte-level BPE "
+                                      "tokeniser has no device kernel (use 'host')")
         if self.tokenize_mode == 'device':
             from rag._unigram import tokenizer_spec
             tokenizer_spec(self.tokenizer)      # NotImplementedError for a tokenizer the kernel does not restate; tables on first use

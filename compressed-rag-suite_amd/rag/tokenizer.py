@@ -225,6 +225,25 @@ class FastWordPieceTokenizer(_PairMixin):
         return [e.ids for e in self._tok.encode_batch(list(texts))]
 
 
+class BpeTokenizer(FastWordPieceTokenizer):
+    """A byte-level BPE tokenizer.json (ModernBERT checkpoints) through the `tokenizers` library, as shipped: normaliser,
+    ByteLevel pre-tokeniser, merges and the post-processor that adds [CLS] ... [SEP]; truncation to max_len per call.  There is no
+    restatement in this package and no device kernel: without the library it cannot be loaded."""
+
+    @classmethod
+    def from_tokenizer_json(cls, path: str, special=None) -> "BpeTokenizer":
+        try:
+            return super().from_tokenizer_json(path, special=special)
+        except ImportError as e:
+            raise ImportError(f"{path} is a byte-level BPE tokenizer.json: loading it needs the `tokenizers` library, which is not "
+                              f"installed (this package restates WordPiece and Unigram only)") from e
+
+    def encode_body(self, text: str) -> List[int]:
+        self._tok.no_truncation()
+        self._max_len = None
+        return self._tok.encode(text, add_special_tokens=False).ids
+
+
 def make_wordpiece_tokenizer(vocab_path: str, lower: bool = True, strip_accents=None, special=None):
     """FastWordPieceTokenizer when the `tokenizers` library is importable (CRS_TOKENIZER=python forces the pure
     Python restatement), else WordPieceTokenizer.  `special`: {"cls", "sep", "pad", "unk"} token strings (BERT's
@@ -292,8 +311,11 @@ def tokenizer_from_model_dir(path: str):
     special = special_tokens_from_model_dir(path)
     if os.path.exists(tj):
         with open(tj, encoding="utf-8") as fh:
-            if (json.load(fh).get("model") or {}).get("type") == "Unigram":      # XLM-RoBERTa's SentencePiece model
-                return make_unigram_tokenizer(tj, special=special)
+            model_type = (json.load(fh).get("model") or {}).get("type")
+        if model_type == "Unigram":      # XLM-RoBERTa's SentencePiece model
+            return make_unigram_tokenizer(tj, special=special)
+        if model_type == "BPE":          # ModernBERT's byte-level BPE: the library only
+            return BpeTokenizer.from_tokenizer_json(tj, special=special)
     if os.path.exists(tj) and os.environ.get("CRS_TOKENIZER", "") != "python":
         try:
             return FastWordPieceTokenizer.from_tokenizer_json(tj, special=special)

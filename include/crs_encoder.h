@@ -153,6 +153,72 @@ int crs_encoder_forward_queries_rope(const crs_encoder_desc* d, const crs_encode
                                      size_t workspace_bytes, float* out_dev, void* q16_out_dev, int slab_type,
                                      void* stream, const crs_encoder_ext* ext, const crs_encoder_rope* rope);
 
+/* Pre-norm encoders with sliding-window layers (ModernBERT; additive to ABI 3).
+ * CRS_ENC_PRENORM: every block normalises its INPUT and adds its output to an un-normalised residual stream r,
+ *     r <- r + Wo attention(LN1(r)),   r <- r + Wdown ffn(LN2(r)),   hidden states = LN_final(r) after the last layer,
+ * with r = the embedding step's LayerNorm output (weights->emb_ln_*) before layer 0.  The layer struct is reused: ln1_g / ln1_b is
+ * the norm in front of attention (layer 0 has none: its ln1_g and ln1_b MUST be NULL -- the embedding norm's output feeds its QKV projection -- and every other layer's ln1_g must not),
+ * ln2_g / ln2_b the norm in front of the feed-forward block; ln1_b, ln2_b and every projection bias may be NULL.  The flag needs
+ * CRS_ENC_ROTARY and one of the _prenorm entry points: TWO rope tables (crs_encoder_rope's layout), one for the full-attention
+ * layers and one for the sliding-window layers; layer i attends the whole sequence when i % global_every == 0 and otherwise
+ * only the keys with |key - query| <= window (both ends included; ModernBERT's local_attention / 2).  A padding query further
+ * than window behind the last real token has no key at all: its context row is zero (finite), and it never reaches a real row.
+ * One add_layernorm launch closes a block and opens the next (r is written back and LN(r) leaves as fp16), so a layer has as
+ * many launches as a post-norm one; the fused QKV + attention kernel and the fused projection + LayerNorm kernel are never
+ * selected.  pos_emb may be NULL.  It excludes a relative-position bias and crs_encoder_score_pairs.
+ * CRS_ENC_GATED_GELU: the feed-forward block is GeGLU, Wdown(gelu(x Wa^T) * (x Wb^T)), erf GELU: CRS_ENC_GATED_SILU's layout
+ * and kernels (GEMM mode 5) with GELU on the activated half.  For ModernBERT's Wi [2F, H], whose output is chunked into
+ * (input, gate), rows [0, F) are the activated half ("gate" rows of the interleaved layout) and rows [F, 2F) the linear half.
+ * Not together with CRS_ENC_GATED_SILU. */
+#define CRS_ENC_PRENORM 8
+#define CRS_ENC_GATED_GELU 16
+
+typedef struct crs_encoder_prenorm {
+  const float* rope_global_dev;  /* fp32 [positions, head_dim], full-attention layers (global theta) */
+  const float* rope_local_dev;   /* fp32 [positions, head_dim], sliding-window layers (local theta)  */
+  int32_t positions;             /* rows of both tables, >= seq                                      */
+  int32_t window;                /* >= 1: largest allowed |key - query| of a sliding layer           */
+  int32_t global_every;          /* >= 1: layer i is full-attention when i % global_every == 0       */
+  const float* final_ln_g;       /* [H] gain of the final norm                                        */
+  const float* final_ln_b;       /* [H] or NULL                                                       */
+} crs_encoder_prenorm;
+
+/* crs_encoder_forward / crs_encoder_forward_queries for CRS_ENC_PRENORM descriptors.  CRS_EINVAL, with a message and before any
+ * launch: a descriptor without CRS_ENC_PRENORM or without CRS_ENC_ROTARY, a NULL pre or NULL tables / final gain, window < 1,
+ * global_every < 1, positions < seq, a misaligned (16 bytes) table, a NULL ln1_g on a layer other than 0, a non-NULL ln1_g or ln1_b on layer 0, both gated flags.  Every
+ * OTHER entry point of this file refuses a CRS_ENC_PRENORM descriptor (a relative bias and the pair head do not combine with it). */
+int crs_encoder_forward_prenorm(const crs_encoder_desc* d, const crs_encoder_weights* w, const int32_t* ids_dev,
+                                const int32_t* lens_dev, int batch, int seq, void* workspace_dev, size_t workspace_bytes,
+                                float* out_dev, int normalize, float* hidden_out_dev, void* stream, const crs_encoder_prenorm* pre);
+
+int crs_encoder_forward_queries_prenorm(const crs_encoder_desc* d, const crs_encoder_weights* w, const int32_t* ids_dev,
+                                        const int32_t* lens_dev, int batch, int seq, void* workspace_dev, size_t workspace_bytes,
+                                        float* out_dev, void* q16_out_dev, int slab_type, void* stream,
+                                        const crs_encoder_prenorm* pre);
+
+/* The launches of such a forward (crs_encoder_plan_describe's form; that entry refuses the flag, since it carries no window): the
+ * full-attention line is followed by the sliding layers' attention_window_kernel line. */
+int crs_encoder_prenorm_plan_describe(const crs_encoder_desc* d, int batch, int seq, int window, char* buf, size_t cap);
+
+/* Test-facing (additive to ABI 3): the sliding-window attention step on its own,
+ *   ctx[b, q, h*hd : (h+1)*hd] = softmax over {j : |j - q| <= window, j < len_b} of (Q K^T / sqrt(hd)) V
+ * Arguments as crs_attention_f16 (no bias, no route).  Rows q < len are the attention output; a row q >= len is finite: the
+ * attention over its allowed real keys, or zeros when it has none (q >= len + window).  CRS_EINVAL as crs_attention_f16, and
+ * for window < 1. */
+int crs_attention_window_f16(const void* qkv_dev, const int32_t* lens_dev, void* ctx_dev, int batch, int seq, int hidden, int heads,
+                             int window, void* stream);
+int crs_attention_window_plan_describe(int batch, int seq, int hidden, int heads, int window, char* buf, size_t cap);
+
+/* Test-facing (additive to ABI 3): the row step of a pre-norm layer on its own,
+ *   r = ((y[0] + ... + y[nsplit - 1]) + bias) + residual   -> r32_dev fp32 [tokens, hidden]  (the new residual stream)
+ *   x = LayerNorm(r) g + b                                  -> x16_dev fp16, and n32_dev fp32 where it is not NULL
+ * y_dev / nsplit / bias_dev / residual_dev as crs_layernorm_f32 (residual_dev may be r32_dev: in place); b_dev may be NULL (a
+ * norm without bias); n32_dev may be NULL and must not overlap y_dev.  CRS_EINVAL as crs_layernorm_f32.  Its launch line is
+ * crs_row_plan_describe's kind 4 (rows = tokens, arg = nsplit). */
+int crs_add_layernorm_f32(const float* y_dev, int nsplit, const float* bias_dev, const float* residual_dev, const float* g_dev,
+                          const float* b_dev, float eps, int tokens, int hidden, float* r32_dev, void* x16_dev, float* n32_dev,
+                          void* stream);
+
 /* Test-facing (additive to ABI 3): the rotation step on its own.  qkv_dev: fp16 [batch * seq, 3 * hidden], rotated in place in
  * its Q and K column blocks (columns [0, 2 * hidden)); table_dev / positions as crs_encoder_rope.  CRS_EINVAL: a NULL or
  * misaligned (16 bytes) pointer, head_dim not 16 / 32 / 64, batch or seq < 1, positions < seq. */
@@ -224,7 +290,8 @@ int crs_pair_head_f32(const float* hidden_dev, int batch, int seq, int hidden, c
 
 /* The launch one of the four entries above makes, as one line of crs_encoder_plan_describe's form, built from the expressions the
  * forward's plan is built from.  kind 0: crs_embed_ln_f32, rows = tokens, arg != 0: with type ids; 1: crs_layernorm_f32, rows = tokens,
- * arg = nsplit; 2: crs_pool_f32, rows = batch; 3: crs_pair_head_f32, rows = batch (arg is not read by kinds 2 and 3).  It needs no
+ * arg = nsplit; 2: crs_pool_f32, rows = batch; 3: crs_pair_head_f32, rows = batch (arg is not read by kinds 2 and 3); 4:
+ * crs_add_layernorm_f32, rows = tokens, arg = nsplit.  It needs no
  * device.  Returns the length of the text as snprintf does, or a negative error code (CRS_EINVAL for an unknown kind and where the
  * launching entry would refuse the sizes). */
 int crs_row_plan_describe(int kind, int rows, int hidden, int arg, char* buf, size_t cap);
@@ -269,6 +336,8 @@ int crs_encoder_plan_describe(const crs_encoder_desc* d, int batch, int seq, int
  *   g = 32 (j / 16) + j % 16, silu(x) = x / (1 + exp(-x)) in fp32, one rounding; bias fp32 [n] or NULL; n even and n / 2 a
  *   multiple of 32 (CRS_EINVAL otherwise).  Routes 0 (the phase-scheduled 256 x 256 kernel where plan_gemm takes it for
  *   modes 0 / 1, else the tiled 128 x 128 kernel; never the 256-row or row-streaming kernels) and 1 (the panel kernel).
+ *   (crs_gemm_f16_routed only) mode 5: mode 4 with the erf GELU in place of SiLU on the activated half (CRS_ENC_GATED_GELU):
+ *   out[m, j] = fp16(gelu(acc[m, g] + bias[g]) * (acc[m, g + 16] + bias[g + 16])); same layout, shapes, routes and kernels.
  * Any n > 0: every kernel family makes its 16-byte epilogue accesses only where n keeps the rows 16-byte aligned (a multiple of 8
  * for fp16 outputs, of 4 for fp32 ones) and goes element by element otherwise.  K a multiple of 64; all pointers 16-byte aligned
  * (CRS_EINVAL otherwise).  This is crs_gemm_f16_routed with route 0 and flags 0. */
@@ -279,7 +348,7 @@ int crs_gemm_f16(const void* a_dev, const void* w_dev, const float* bias_dev, co
  * can be run on its own.  route 0: plan_gemm (modes 0..2: the phase-scheduled 256 x 256 kernel, the 256-row pipelined kernel, the
  * row-streaming kernels or the tiled 128 x 128 kernel, by the sizes, the CU count and the CRS_* knobs); route 1: plan_gemm_panel, the
  * panel kernel, modes 0 / 1 / 3, K a multiple of 128; route 2: the split-K form of the 256 x 256 kernel, mode 3 only, CRS_EINVAL for
- * a shape that form does not take (csrc/enc_plan.cpp: gemm8_splitk).  Mode 4 (above): routes 0 and 1.  flags & 1: the small-LDS forms (CRS_ENC_SMALL_LDS).
+ * a shape that form does not take (csrc/enc_plan.cpp: gemm8_splitk).  Modes 4 and 5 (above): routes 0 and 1.  flags & 1: the small-LDS forms (CRS_ENC_SMALL_LDS).
  * mode 3 takes no bias (bias_dev must be NULL) and writes the raw fp32 partial products as out_dev[slabs][m][n]; slab z of the
  * panel kernel holds the contraction over columns [z * K / slabs, (z + 1) * K / slabs) of K, and so does slab z of the 256 x 256
  * kernel; crs_gemm_plan_describe answers the slab count.  The entry only chooses which planner function makes the plan; the

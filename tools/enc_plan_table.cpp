@@ -3,6 +3,8 @@
 //   ./enc_plan_table <CUs> < cases      one case per line:  fwd hidden heads ffn flags batch seq rel_bias pair  |  gemm m n k mode
 //                                        |  route m n k mode route flags  |  projln tokens hidden k flags big_ln
 //                                        |  attn batch seq hidden heads rel_bias route
+//                                        |  fwdw hidden heads ffn flags batch seq rel_bias pair window  |  attnw batch seq hidden heads window
+// (fwdw: fwd with the window of a CRS_ENC_PRENORM descriptor, flags 8 pre-norm and 16 gated GELU; attnw: plan_attention_window)
 // (attn: the line crs_attention_plan_describe answers: route < 0 the environment's knobs, else default knobs with bits 1 attn_seq off,
 // 2 attn_short off, 4 attn_x32 off, 8 attn_qt4 on; 16 the fused QKV + attention kernel's launch)
 // (route, projln: what crs_gemm_plan_describe and crs_proj_ln_plan_describe answer; route 0 plan_gemm, 1 plan_gemm_panel, 2 the gemm8
@@ -20,7 +22,7 @@
 #include "../compressed-rag-suite_amd/csrc/enc_plan.h"
 
 static const char* const kFamily[] = {"None", "Tiled", "Panel", "Stream", "StreamKS", "Big", "Gemm8", "Gemm8SplitK"};
-static const char* const kAttn[] = {"Fused", "Blocked", "Short", "Seq", "Seq32"};
+static const char* const kAttn[] = {"Fused", "Blocked", "Short", "Seq", "Seq32", "Window"};
 
 static void gemm_fields(const char* step, const crs::GemmPlan& g) {
   printf("%s=%s/%d/%d/%d/%d/%d/%d/%d/%d/%d %s_lds=%d %s_wgs=%ld ", step, kFamily[(int)g.family], g.slabs, g.tm, g.kc, g.kin, (int)g.persist,
@@ -85,9 +87,20 @@ int main(int argc, char** argv) {
       text_out(text);
       continue;
     }
-    int hidden, heads, ffn, flags, batch, seq, rel, pair;
-    if (strcmp(kind, "fwd") || scanf("%d %d %d %d %d %d %d %d", &hidden, &heads, &ffn, &flags, &batch, &seq, &rel, &pair) != 8) return 2;
-    const crs::EncPlan p = crs::make_enc_plan(hidden, heads, ffn, flags, batch, seq, rel, pair, cus, kn);
+    if (!strcmp(kind, "attnw")) {
+      int batch, seq, hid, hds, window;
+      if (scanf("%d %d %d %d %d", &batch, &seq, &hid, &hds, &window) != 5 || hds < 1 || hid % hds || window < 1) return 2;
+      const crs::AttnPlan a = crs::plan_attention_window(batch, seq, hds, hid / hds, window, kn);
+      printf("attn=%s attn_lds=%d attn_wgs=%ld ", kAttn[(int)a.form], a.d.lds, (long)a.d.gx * a.d.gy * a.d.gz);
+      crs::attn_plan_describe(a, text, sizeof text);
+      text_out(text);
+      continue;
+    }
+    int hidden, heads, ffn, flags, batch, seq, rel, pair, window = 0;
+    const bool fwdw = !strcmp(kind, "fwdw");
+    if ((!fwdw && strcmp(kind, "fwd")) || scanf("%d %d %d %d %d %d %d %d", &hidden, &heads, &ffn, &flags, &batch, &seq, &rel, &pair) != 8) return 2;
+    if (fwdw && scanf("%d", &window) != 1) return 2;
+    const crs::EncPlan p = crs::make_enc_plan(hidden, heads, ffn, flags, batch, seq, rel, pair, cus, kn, window);
     printf("total=%zu max_split=%d attn=%s attn_lds=%d ", p.total, p.max_split, kAttn[(int)p.attn.form], p.attn.d.lds);
     gemm_fields("qkv", p.qkv);
     gemm_fields("up", p.up);
