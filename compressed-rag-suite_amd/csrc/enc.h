@@ -46,12 +46,10 @@ int gemm_rowln2_launch(const ProjLnPlan& p, const _Float16* a, const _Float16* w
 // qkv is [T, 3H] fp16 (Q | K | V column blocks), lens[b] real tokens per row (right padding).
 // rel_bias (Blocked with bias): bias[h][key - query] added to every score before the softmax, fp32 [heads, 2 span - 1], entry
 // (key - query) + span - 1; span >= seq, seq <= 512 (-1 otherwise).  <= 21 KB of static LDS.
+// AttnForm::Window (plan_attention_window): only the keys with |key - query| <= p.window (>= 1, -1 otherwise); a query without any
+// allowed key (padding at q >= len + window) gets a zero row.  No bias.  -1 for a head_dim other than 16 / 32 / 64.
 int attention_launch(const AttnPlan& p, const _Float16* qkv, const int* lens, _Float16* ctx, int batch, int seq, int hidden, int heads,
                      const float* rel_bias, int span, hipStream_t stream);
-
-// AttnForm::Window (plan_attention_window): the blocked kernel restricted to the keys with |key - query| <= p.window; a query without
-// any allowed key (padding at q >= len + window) gets a zero row.  No bias.  -1 for another form or a head_dim other than 16 / 32 / 64.
-int attention_window_launch(const AttnPlan& p, const _Float16* qkv, const int* lens, _Float16* ctx, int seq, int hidden, hipStream_t stream);
 
 // enc_rope.hip: rotates the Q and K column blocks of qkv [tokens, 3 hidden] fp16 in place against table fp32 [positions, hd]
 // (cos half | sin half, include/crs_encoder.h: CRS_ENC_ROTARY); d: EncPlan::rope; the caller checked positions >= seq.  No LDS.

@@ -12,8 +12,15 @@
 // Softmax is fp32 with the usual online rescaling.  Sequences are right-padded: keys >= lens[b]
 // get -1e30 before the max (every row sees key 0, so the max is always finite).
 // <= 11 % of the encoder's FLOPs at the BASELINE shapes.
-// attention_window_kernel: the blocked kernel restricted to the keys with |key - query| <= window (ModernBERT's sliding layers);
-// there the claim about key 0 does NOT hold -- see its header for the sentinel and the zero rows.
+//
+// The steps the five kernels are composed from exist once: softmax_step<Score> (the online-softmax step in its three score modes:
+// Plain -- padding mask only, Bias -- MPNet's relative-position bias, Window -- ModernBERT's sliding layers, only the keys with
+// |key - query| <= window; in Window mode the claim about key 0 does NOT hold, see the step for the sentinel and the zero rows),
+// make_unit (a (batch, head)'s setup), load_q_frags, stage_k, stage_vt and store_o.
+// The 64-key block step on the 16-deep MFMA (S^T MFMAs, softmax_step, rescale, O^T MFMAs) is still written out in attention_kernel,
+// attention_window_kernel and attention_seq_kernel: sharing it, or the blocked body, moved s_waitcnt counts in the compiled
+// kernels (profiles/attn_refactor_resources.txt has the lines), so each keeps its copy and the bit-equality of the three rests on
+// tests/test_attn_forms_gpu.py and tools/encoder_digest.py.
 
 #include "enc.h"
 
@@ -34,29 +41,58 @@ constexpr int QB = forms::kAttnQ;   // query rows per workgroup
 constexpr int kMaxSeq = forms::kAttnMaxBiasSeq;    // relative bias: the staged table holds 2 * 512 - 1 offsets
 constexpr float kLog2e = 1.44269504088896341f;
 
+enum class Score { Plain, Bias, Window };
+
+// What a step needs beyond the raw products to form and mask its scores.
+struct KeyMask {
+  int len;                 // keys >= len are right padding
+  const float* bias;       // Bias: this lane's window of the staged table at this key block
+  int q, window;           // Window: this lane's query and the largest allowed |key - query|
+  bool inside;             // Window: the whole block is allowed for all 16 queries of the wave (wave-uniform): no test
+};
+
 // One online-softmax step for this lane's query over the 16 scores it holds of a 64-key block (raw Q.K products of keys
 // key0 + 16 ct + i in s).  Works in the base-2 domain with the 1/sqrt(hd) scale folded into one constant c = log2(e) / sqrt(hd).
-// Keys >= len (right padding, last block only) are set to -1e30 before the max, so their weight is exp2(-huge) = 0; every
-// query sees key 0, so the running max is finite.  The two arms round differently and each keeps its own form:
-//   plain  per score a max on the raw product, one fma and one v_exp_f32 (the softmax, not the MFMAs, bounds this kernel: 16
-//          scores per lane and block against 16 small MFMAs per wave);
-//   BIAS   bias = this lane's window of the staged table (entry 16 ct + i belongs to that key, already times log2(e)):
-//          t = s * c + bias first, and the max is taken AFTER the bias is added (the bias can outweigh the product).
-template <bool BIAS>
-__device__ __forceinline__ void softmax_step(f32x4 (&s)[4], const float* __restrict__ bias, int key0, int len, float c,
-                                             float& m_run, float& l_run, float& alpha, f16x4 (&pf)[4]) {
-  if constexpr (BIAS) {
+// A masked key is set to -1e30 before the max, so its weight is exp2(-huge) = 0.  The modes round differently and each keeps its
+// own form; the reductions and the running sum are the same code:
+//   Plain   keys >= len (right padding, last block only) are masked on the RAW product; every query sees key 0, so the running
+//           max is finite.  Per score a max on the raw product, one fma and one v_exp_f32 (the softmax, not the MFMAs, bounds
+//           this kernel: 16 scores per lane and block against 16 small MFMAs per wave);
+//   Bias    m.bias = this lane's window of the staged table (entry 16 ct + i belongs to that key, already times log2(e)):
+//           t = s * c + bias first, then the padding mask, and the max is taken AFTER the bias is added (the bias can outweigh
+//           the product);
+//   Window  t = s * c (a plain multiply), then a score outside the window or at key >= len is masked unless m.inside.
+//           Two things the other modes' comments rule out happen here:
+//     * a query's FIRST visited block can lie wholly outside its window (W = 8: rows 73 .. 127 of query block 1 against key block 0),
+//       so "every row sees key 0, the max is finite" does not hold.  The running maximum then stays at the sentinel -1e30 and that
+//       block's weights are exp2(-1e30 - -1e30) = 1, on finite V values; the first block with an allowed key rescales by
+//       exp2(-1e30 - finite) = 0 exactly, which wipes the accumulator and the row sum.  That needs the masked score, the maximum and
+//       the subtraction to be the SAME fp32 number: the step scales first (t = s c) and masks t, instead of masking the raw product and
+//       folding c into an fma as Plain does -- fma(-1e30, c, fl(1e30 c)) is the product's rounding error, about 2^70, and
+//       exp2 of that is infinity.  The sentinel is finite on purpose: with -inf the same subtraction is inf - inf = NaN.
+//     * a padding query at q >= len + W has no allowed key at all (and a workgroup whose whole query block is such visits no block).
+//       Its row is written as ZEROS (attention_window_kernel's store): the row sum would be 0 or a count of masked keys, and a NaN there
+//       would poison real rows in the next layer's MFMAs (0 x NaN) although their weight for this position is 0.  Every real query
+//       allows itself.
+template <Score MODE>
+__device__ __forceinline__ void softmax_step(f32x4 (&s)[4], const KeyMask m, int key0, float c, float& m_run, float& l_run,
+                                             float& alpha, f16x4 (&pf)[4]) {
+  if constexpr (MODE != Score::Plain) {
 #pragma unroll
     for (int ct = 0; ct < 4; ++ct)
 #pragma unroll
-      for (int i = 0; i < 4; ++i) s[ct][i] = fmaf(s[ct][i], c, bias[ct * 16 + i]);
+      for (int i = 0; i < 4; ++i) s[ct][i] = MODE == Score::Bias ? fmaf(s[ct][i], c, m.bias[ct * 16 + i]) : s[ct][i] * c;
   }
-  if (key0 - (key0 & 15) + KB > len) {     // block reaches past len (wave-uniform: key0 = kb + 4 g)
+  // Plain / Bias: only a block that reaches past len (wave-uniform: key0 = kb + 4 g); Window: every block not inside (wave-uniform)
+  const int len = m.len, q = m.q, window = m.window;
+  if (MODE == Score::Window ? !m.inside : key0 - (key0 & 15) + KB > len) {
 #pragma unroll
     for (int ct = 0; ct < 4; ++ct)
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (key0 + ct * 16 + i >= len) s[ct][i] = -1e30f;
+      for (int i = 0; i < 4; ++i) {
+        const int key = key0 + ct * 16 + i, d = key - q;
+        if (MODE == Score::Window ? key >= len || d > window || d < -window : key >= len) s[ct][i] = -1e30f;
+      }
   }
   float mx = -1e30f;
 #pragma unroll
@@ -65,8 +101,7 @@ __device__ __forceinline__ void softmax_step(f32x4 (&s)[4], const float* __restr
     for (int i = 0; i < 4; ++i) mx = fmaxf(mx, s[ct][i]);
   mx = fmaxf(mx, __shfl_xor(mx, 16));
   mx = fmaxf(mx, __shfl_xor(mx, 32));
-  float mn;
-  if constexpr (BIAS) mn = fmaxf(m_run, mx); else mn = fmaxf(m_run, mx * c);
+  const float mn = fmaxf(m_run, MODE == Score::Plain ? mx * c : mx);
   alpha = __builtin_amdgcn_exp2f(m_run - mn);
   m_run = mn;
   float rs = 0.f;
@@ -74,8 +109,7 @@ __device__ __forceinline__ void softmax_step(f32x4 (&s)[4], const float* __restr
   for (int ct = 0; ct < 4; ++ct) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      float p;
-      if constexpr (BIAS) p = __builtin_amdgcn_exp2f(s[ct][i] - mn); else p = __builtin_amdgcn_exp2f(fmaf(s[ct][i], c, -mn));
+      const float p = __builtin_amdgcn_exp2f(MODE == Score::Plain ? fmaf(s[ct][i], c, -mn) : s[ct][i] - mn);
       rs += p;
       pf[ct][i] = (_Float16)p;
     }
@@ -147,11 +181,11 @@ __device__ __forceinline__ void stage_vt(_Float16* sVt, const _Float16* __restri
   }
 }
 
-// Normalise and store the O^T tiles of query row qr (this lane's column): head-dim columns 16 n + 4 g .. + 4, 8-byte stores.
-// (inv: the reciprocal of the row sum; the windowed kernel passes 0 for a row without any allowed key)
+// Scale by inv and store the O^T tiles of query row qr (this lane's column): head-dim columns 16 n + 4 g .. + 4, 8-byte stores.
+// (inv: the reciprocal of the row sum; Window mode passes 0 for a row without any allowed key)
 template <int HD>
-__device__ __forceinline__ void store_o_scaled(const f32x4 (&o)[HD / 16], float inv, _Float16* __restrict__ ctx, int b, int h, int qr,
-                                               int seq, int hidden, int g) {
+__device__ __forceinline__ void store_o(const f32x4 (&o)[HD / 16], float inv, _Float16* __restrict__ ctx, int b, int h, int qr,
+                                        int seq, int hidden, int g) {
   constexpr int NT = HD / 16;
   if (qr < seq) {
     _Float16* dst = ctx + ((size_t)b * seq + qr) * hidden + h * HD;
@@ -163,17 +197,29 @@ __device__ __forceinline__ void store_o_scaled(const f32x4 (&o)[HD / 16], float 
   }
 }
 
-template <int HD>
-__device__ __forceinline__ void store_o(const f32x4 (&o)[HD / 16], float l_run, _Float16* __restrict__ ctx, int b, int h, int qr,
-                                        int seq, int hidden, int g) {
-  store_o_scaled<HD>(o, 1.0f / l_run, ctx, b, h, qr, seq, hidden, g);
-}
-
 // (batch, head) unit of a whole-sequence workgroup.  Workgroups go round-robin over the 8 XCDs (id % 8), and two heads that are
 // neighbours in a token's Q / K / V row share 128-byte lines when head_dim is 32: units 2p and 2p + 1 are given to the SAME
 // XCD back to back (ids 16 j + x and 16 j + 8 + x), so the second one's K / V come out of that XCD's L2.
 __device__ __forceinline__ int xcd_paired_unit(int id, int total) {
   return (total & 15) == 0 ? (((id >> 4) << 3) + (id & 7)) * 2 + ((id >> 3) & 1) : id;
+}
+
+// What a workgroup (or, in the short kernel, a wave) knows about its (batch, head) unit and its own lanes.
+struct Unit {
+  int tid, wave, lr, g;        // thread, wave of the workgroup; lane = 16 g + lr
+  int b, h, len;               // len: the real tokens, clamped to [1, seq]
+  size_t row_stride;           // of qkv, in halves
+  const _Float16* base;        // the unit's Q column block (K at + hidden, V at + 2 hidden)
+  float scale;                 // log2(e) / sqrt(hd): softmax_step works in base 2
+};
+
+template <int HD>
+__device__ __forceinline__ Unit make_unit(const _Float16* qkv, const int* lens, int b, int h, int seq, int hidden) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int len = min(max(lens[b], 1), seq);
+  const size_t row_stride = (size_t)3 * hidden;
+  return Unit{tid, tid >> 6, lane & 15, lane >> 4, b, h, len, row_stride, qkv + (size_t)b * seq * row_stride + h * HD,
+              kLog2e / sqrtf((float)HD)};
 }
 
 // BIAS: an additive relative-position bias on every score,
@@ -195,14 +241,8 @@ __global__ __launch_bounds__(kThreads) void attention_kernel(const _Float16* __r
   __shared__ __attribute__((aligned(16))) _Float16 sK[KB * KROW];
   __shared__ __attribute__((aligned(16))) _Float16 sVt[HD * VROW];
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int lr = lane & 15, g = lane >> 4;
-  const int b = blockIdx.z, h = blockIdx.y;
-  const int q0 = blockIdx.x * QB + wave * 16;
-  const int len = min(max(lens[b], 1), seq);
-  const size_t row_stride = (size_t)3 * hidden;
-  const _Float16* base = qkv + (size_t)b * seq * row_stride + h * HD;
-  const float scale = kLog2e / sqrtf((float)HD);   // log2(e) / sqrt(hd): softmax_step works in base 2
+  const Unit u = make_unit<HD>(qkv, lens, blockIdx.z, blockIdx.y, seq, hidden);
+  const int q0 = blockIdx.x * QB + u.wave * 16;
 
   const float* bias = nullptr;          // BIAS: this lane's window of the staged table at key block 0
   if constexpr (BIAS) {
@@ -211,14 +251,14 @@ __global__ __launch_bounds__(kThreads) void attention_kernel(const _Float16* __r
     // the key loop (len >= 1: the loop runs at least once).
     __shared__ float sBias[2 * kMaxSeq];
     const int sp = (seq + KB - 1) / KB * KB;         // <= 512: the launcher checks seq
-    const float* hb = rel_bias + (size_t)h * (2 * span - 1) + (span - 1);     // offset 0 of this head
-    for (int j = tid; j < 2 * sp - 1; j += kThreads) {
+    const float* hb = rel_bias + (size_t)u.h * (2 * span - 1) + (span - 1);     // offset 0 of this head
+    for (int j = u.tid; j < 2 * sp - 1; j += kThreads) {
       const int d = j - (sp - 1);
       sBias[j] = (d > -seq && d < seq) ? hb[d] * kLog2e : 0.f;
     }
     // this lane's keys of block kb are kb + 4 g + 16 ct + i, its query q0 + lr: staged entry (key - query) + sp - 1.
     // q0 + lr <= sp - 1 and key <= sp - 1, so the entries are within [0, 2 sp - 2]
-    bias = sBias + (4 * g - (q0 + lr) + sp - 1);
+    bias = sBias + (4 * u.g - (q0 + u.lr) + sp - 1);
   }
 
   // Everything is computed TRANSPOSED: S^T = K Q^T and O^T = V^T P^T.  With the 16x16x16 accumulator layout
@@ -228,16 +268,16 @@ __global__ __launch_bounds__(kThreads) void attention_kernel(const _Float16* __r
   // exactly the B-operand layout of the second product (4 consecutive keys of one query): no LDS round trip
   // for P.
   f16x4 qf[KS];
-  load_q_frags<KS>(qf, base, row_stride, q0 + lr, seq, g);
+  load_q_frags<KS>(qf, u.base, u.row_stride, q0 + u.lr, seq, u.g);
   f32x4 o[NT];                          // O^T tile n: rows = head-dim 16 n + 4 g + i, column = query lr
 #pragma unroll
   for (int n = 0; n < NT; ++n) o[n] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m_run = -1e30f, l_run = 0.f;   // of this lane's query
 
-  for (int kb = 0; kb < len; kb += KB) {
+  for (int kb = 0; kb < u.len; kb += KB) {
     __syncthreads();  // previous block's K / V^T fully consumed
-    stage_k<HD, KROW, kThreads>(sK, base, row_stride, hidden, seq, kb, KB, tid);
-    stage_vt<HD, VROW, kThreads, false>(sVt, base, row_stride, hidden, seq, kb, KB, tid);
+    stage_k<HD, KROW, kThreads>(sK, u.base, u.row_stride, hidden, seq, kb, KB, u.tid);
+    stage_vt<HD, VROW, kThreads, false>(sVt, u.base, u.row_stride, hidden, seq, kb, KB, u.tid);
     __syncthreads();
 
     // ---- S^T = K Q^T for 4 tiles of 16 keys: lane holds keys kb + 16 ct + 4 g + i of query lr
@@ -247,13 +287,13 @@ __global__ __launch_bounds__(kThreads) void attention_kernel(const _Float16* __r
       s[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
-        const f16x4 kf = *reinterpret_cast<const f16x4*>(&sK[(ct * 16 + lr) * KROW + ks * 16 + g * 4]);
+        const f16x4 kf = *reinterpret_cast<const f16x4*>(&sK[(ct * 16 + u.lr) * KROW + ks * 16 + u.g * 4]);
         s[ct] = __builtin_amdgcn_mfma_f32_16x16x16f16(kf, qf[ks], s[ct], 0, 0, 0);
       }
     }
     float alpha;
     f16x4 pf[4];
-    softmax_step<BIAS>(s, BIAS ? bias + kb : nullptr, kb + 4 * g, len, scale, m_run, l_run, alpha, pf);
+    softmax_step<BIAS ? Score::Bias : Score::Plain>(s, KeyMask{u.len, BIAS ? bias + kb : nullptr, 0, 0, false}, kb + 4 * u.g, u.scale, m_run, l_run, alpha, pf);
     // ---- O^T = O^T alpha + V^T P^T   (A = V^T[hd 16 n + lr][key 16 ct + 4 g + j], B = P^T from the registers)
 #pragma unroll
     for (int n = 0; n < NT; ++n) {
@@ -261,73 +301,24 @@ __global__ __launch_bounds__(kThreads) void attention_kernel(const _Float16* __r
       for (int i = 0; i < 4; ++i) o[n][i] *= alpha;
 #pragma unroll
       for (int ct = 0; ct < 4; ++ct) {
-        const f16x4 vf = *reinterpret_cast<const f16x4*>(&sVt[(n * 16 + lr) * VROW + ct * 16 + g * 4]);
+        const f16x4 vf = *reinterpret_cast<const f16x4*>(&sVt[(n * 16 + u.lr) * VROW + ct * 16 + u.g * 4]);
         o[n] = __builtin_amdgcn_mfma_f32_16x16x16f16(vf, pf[ct], o[n], 0, 0, 0);
       }
     }
   }
-  store_o<HD>(o, l_run, ctx, b, h, q0 + lr, seq, hidden, g);
+  store_o<HD>(o, 1.0f / l_run, ctx, u.b, u.h, q0 + u.lr, seq, hidden, u.g);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // Sliding-window variant of the blocked kernel (ModernBERT's local layers): query q attends the keys with |key - q| <= window
 // (both ends included) and key < len,
 //   ctx[b, q, h*hd : (h+1)*hd] = softmax_{|j - q| <= W, j < len}(Q K^T / sqrt(hd)) V
-// Same staging, MFMA shape, fp16 rounding points and online softmax as attention_kernel<HD, false>; a workgroup of 64 queries
-// starting at qb walks only the 64-key blocks that meet [max(0, qb - W), min(len, qb + 64 + W)): at most 2 + ceil(2 W / 64) of
-// them, whatever the sequence length, and none where that range is empty (qb - W >= len).  Inside a visited block a score outside the window or at key >= len gets the padding
-// treatment (-1e30, weight 0); a block that lies wholly inside the window of all 16 queries of the wave and below len skips the test.
-// Two things the plain kernel's comments rule out happen here:
-//   * a query's FIRST visited block can lie wholly outside its window (W = 8: rows 73 .. 127 of query block 1 against key block 0),
-//     so "every row sees key 0, the max is finite" does not hold.  The running maximum then stays at the sentinel -1e30 and that
-//     block's weights are exp2(-1e30 - -1e30) = 1, on finite V values; the first block with an allowed key rescales by
-//     exp2(-1e30 - finite) = 0 exactly, which wipes the accumulator and the row sum.  That needs the masked score, the maximum and
-//     the subtraction to be the SAME fp32 number: the step scales first (t = s c) and masks t, instead of masking the raw product and
-//     folding c into an fma as the plain step does -- fma(-1e30, c, fl(1e30 c)) is the product's rounding error, about 2^70, and
-//     exp2 of that is infinity.  The sentinel is finite on purpose: with -inf the same subtraction is inf - inf = NaN.
-//   * a padding query at q >= len + W has no allowed key at all (and a workgroup whose whole query block is such visits no block).
-//     Its row is written as ZEROS: the row sum would be 0 or a count of masked keys, and a NaN there would poison real rows in
-//     the next layer's MFMAs (0 x NaN) although their weight for this position is 0.  Every real query allows itself.
-__device__ __forceinline__ void softmax_step_window(f32x4 (&s)[4], int key0, int q, int window, int len, bool inside, float c,
-                                                    float& m_run, float& l_run, float& alpha, f16x4 (&pf)[4]) {
-#pragma unroll
-  for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) s[ct][i] *= c;
-  if (!inside) {                            // wave-uniform
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int key = key0 + ct * 16 + i, d = key - q;
-        if (key >= len || d > window || d < -window) s[ct][i] = -1e30f;
-      }
-  }
-  float mx = -1e30f;
-#pragma unroll
-  for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) mx = fmaxf(mx, s[ct][i]);
-  mx = fmaxf(mx, __shfl_xor(mx, 16));
-  mx = fmaxf(mx, __shfl_xor(mx, 32));
-  const float mn = fmaxf(m_run, mx);
-  alpha = __builtin_amdgcn_exp2f(m_run - mn);
-  m_run = mn;
-  float rs = 0.f;
-#pragma unroll
-  for (int ct = 0; ct < 4; ++ct) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float p = __builtin_amdgcn_exp2f(s[ct][i] - mn);
-      rs += p;
-      pf[ct][i] = (_Float16)p;
-    }
-  }
-  rs += __shfl_xor(rs, 16);
-  rs += __shfl_xor(rs, 32);
-  l_run = l_run * alpha + rs;
-}
-
+// Same staging, MFMA shape and fp16 rounding points as attention_kernel<HD, false>, softmax_step in Window mode; a workgroup of 64
+// queries starting at qb walks only the 64-key blocks that meet [max(0, qb - W), min(len, qb + 64 + W)): at most 2 + ceil(2 W / 64)
+// of them, whatever the sequence length, and none where that range is empty (qb - W >= len).  Inside a visited block a score outside
+// the window or at key >= len gets the padding treatment (-1e30, weight 0); a block that lies wholly inside the window of all 16
+// queries of the wave and below len skips the test.  A query's first visited block can lie wholly outside its window, and a padding
+// query at q >= len + W has no allowed key at all and is stored as a ZERO row: softmax_step's Window arm has the reasons.
 template <int HD>
 __global__ __launch_bounds__(kThreads) void attention_window_kernel(const _Float16* __restrict__ qkv, const int* __restrict__ lens,
                                                                    _Float16* __restrict__ ctx, int seq, int hidden, int window) {
@@ -336,21 +327,15 @@ __global__ __launch_bounds__(kThreads) void attention_window_kernel(const _Float
   __shared__ __attribute__((aligned(16))) _Float16 sK[KB * KROW];
   __shared__ __attribute__((aligned(16))) _Float16 sVt[HD * VROW];
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int lr = lane & 15, g = lane >> 4;
-  const int b = blockIdx.z, h = blockIdx.y;
-  const int qb = blockIdx.x * QB, q0 = qb + wave * 16;
-  const int len = min(max(lens[b], 1), seq);
+  const Unit u = make_unit<HD>(qkv, lens, blockIdx.z, blockIdx.y, seq, hidden);
+  const int qb = blockIdx.x * QB, q0 = qb + u.wave * 16;
   const int w = min(window, seq);                  // (|key - query| < seq anyway; keeps the sums below in range)
-  const size_t row_stride = (size_t)3 * hidden;
-  const _Float16* base = qkv + (size_t)b * seq * row_stride + h * HD;
-  const float scale = kLog2e / sqrtf((float)HD);
   // the workgroup's key blocks (the same for its four waves: the barriers below are uniform)
   // (a query block wholly behind len + w -- qb - w >= len -- has no allowed key at all and walks no block)
-  const int k_lo = max(0, qb - w) & ~(KB - 1), k_hi = qb - w >= len ? 0 : min(len, qb + QB + w);
+  const int k_lo = max(0, qb - w) & ~(KB - 1), k_hi = qb - w >= u.len ? 0 : min(u.len, qb + QB + w);
 
   f16x4 qf[KS];
-  load_q_frags<KS>(qf, base, row_stride, q0 + lr, seq, g);
+  load_q_frags<KS>(qf, u.base, u.row_stride, q0 + u.lr, seq, u.g);
   f32x4 o[NT];
 #pragma unroll
   for (int n = 0; n < NT; ++n) o[n] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -358,8 +343,8 @@ __global__ __launch_bounds__(kThreads) void attention_window_kernel(const _Float
 
   for (int kb = k_lo; kb < k_hi; kb += KB) {
     __syncthreads();
-    stage_k<HD, KROW, kThreads>(sK, base, row_stride, hidden, seq, kb, KB, tid);
-    stage_vt<HD, VROW, kThreads, false>(sVt, base, row_stride, hidden, seq, kb, KB, tid);
+    stage_k<HD, KROW, kThreads>(sK, u.base, u.row_stride, hidden, seq, kb, KB, u.tid);
+    stage_vt<HD, VROW, kThreads, false>(sVt, u.base, u.row_stride, hidden, seq, kb, KB, u.tid);
     __syncthreads();
     f32x4 s[4];
 #pragma unroll
@@ -367,28 +352,28 @@ __global__ __launch_bounds__(kThreads) void attention_window_kernel(const _Float
       s[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
-        const f16x4 kf = *reinterpret_cast<const f16x4*>(&sK[(ct * 16 + lr) * KROW + ks * 16 + g * 4]);
+        const f16x4 kf = *reinterpret_cast<const f16x4*>(&sK[(ct * 16 + u.lr) * KROW + ks * 16 + u.g * 4]);
         s[ct] = __builtin_amdgcn_mfma_f32_16x16x16f16(kf, qf[ks], s[ct], 0, 0, 0);
       }
     }
     // all 64 keys allowed for all 16 queries of the wave: kb >= (q0 + 15) - w, kb + 63 <= q0 + w, kb + 64 <= len
-    const bool inside = kb + w >= q0 + 15 && kb + KB - 1 <= q0 + w && kb + KB <= len;
+    const bool inside = kb + w >= q0 + 15 && kb + KB - 1 <= q0 + w && kb + KB <= u.len;
     float alpha;
     f16x4 pf[4];
-    softmax_step_window(s, kb + 4 * g, q0 + lr, w, len, inside, scale, m_run, l_run, alpha, pf);
+    softmax_step<Score::Window>(s, KeyMask{u.len, nullptr, q0 + u.lr, w, inside}, kb + 4 * u.g, u.scale, m_run, l_run, alpha, pf);
 #pragma unroll
     for (int n = 0; n < NT; ++n) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) o[n][i] *= alpha;
 #pragma unroll
       for (int ct = 0; ct < 4; ++ct) {
-        const f16x4 vf = *reinterpret_cast<const f16x4*>(&sVt[(n * 16 + lr) * VROW + ct * 16 + g * 4]);
+        const f16x4 vf = *reinterpret_cast<const f16x4*>(&sVt[(n * 16 + u.lr) * VROW + ct * 16 + u.g * 4]);
         o[n] = __builtin_amdgcn_mfma_f32_16x16x16f16(vf, pf[ct], o[n], 0, 0, 0);
       }
     }
   }
   // a row whose maximum is still the sentinel saw no allowed key (finite scores are far above -1e29): zeros
-  store_o_scaled<HD>(o, m_run > -1e29f ? 1.0f / l_run : 0.f, ctx, b, h, q0 + lr, seq, hidden, g);
+  store_o<HD>(o, m_run > -1e29f ? 1.0f / l_run : 0.f, ctx, u.b, u.h, q0 + u.lr, seq, hidden, u.g);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -409,54 +394,48 @@ __global__ __launch_bounds__(NW * 64) void attention_seq_kernel(const _Float16* 
   extern __shared__ __attribute__((aligned(16))) char attn_smem[];
   _Float16* sK = reinterpret_cast<_Float16*>(attn_smem);                       // [SMAX][KROW]
   _Float16* sVt = sK + SMAX * KROW;                                            // [HD][VROW]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int lr = lane & 15, g = lane >> 4;
   const int heads = hidden / HD;
   const int unit = xcd_paired_unit(blockIdx.x, gridDim.x);
-  const int b = unit / heads, h = unit % heads;
-  const int len = min(max(lens[b], 1), seq);
-  const size_t row_stride = (size_t)3 * hidden;
-  const _Float16* base = qkv + (size_t)b * seq * row_stride + h * HD;
-  const float scale = kLog2e / sqrtf((float)HD);   // log2(e) / sqrt(hd): softmax_step works in base 2
-  const int kend = (len + KB - 1) / KB * KB;       // keys staged: whole 64-key blocks up to len (rows >= seq are zero)
+  const Unit u = make_unit<HD>(qkv, lens, unit / heads, unit % heads, seq, hidden);
+  const int kend = (u.len + KB - 1) / KB * KB;     // keys staged: whole 64-key blocks up to len (rows >= seq are zero)
 
-  stage_k<HD, KROW, kThreads>(sK, base, row_stride, hidden, seq, 0, kend, tid);
-  stage_vt<HD, VROW, kThreads, false>(sVt, base, row_stride, hidden, seq, 0, kend, tid);
+  stage_k<HD, KROW, kThreads>(sK, u.base, u.row_stride, hidden, seq, 0, kend, u.tid);
+  stage_vt<HD, VROW, kThreads, false>(sVt, u.base, u.row_stride, hidden, seq, 0, kend, u.tid);
   __syncthreads();
 
-  for (int q0 = wave * 16; q0 < seq; q0 += NW * 16) {
+  for (int q0 = u.wave * 16; q0 < seq; q0 += NW * 16) {
     f16x4 qf[KS];
-    load_q_frags<KS>(qf, base, row_stride, q0 + lr, seq, g);
+    load_q_frags<KS>(qf, u.base, u.row_stride, q0 + u.lr, seq, u.g);
     f32x4 o[NT];
 #pragma unroll
     for (int n = 0; n < NT; ++n) o[n] = f32x4{0.f, 0.f, 0.f, 0.f};
     float m_run = -1e30f, l_run = 0.f;
-    for (int kb = 0; kb < len; kb += KB) {
+    for (int kb = 0; kb < u.len; kb += KB) {
       f32x4 sc[4];
 #pragma unroll
       for (int ct = 0; ct < 4; ++ct) {
         sc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-          const f16x4 kf = *reinterpret_cast<const f16x4*>(&sK[(kb + ct * 16 + lr) * KROW + ks * 16 + g * 4]);
+          const f16x4 kf = *reinterpret_cast<const f16x4*>(&sK[(kb + ct * 16 + u.lr) * KROW + ks * 16 + u.g * 4]);
           sc[ct] = __builtin_amdgcn_mfma_f32_16x16x16f16(kf, qf[ks], sc[ct], 0, 0, 0);
         }
       }
       float alpha;
       f16x4 pf[4];
-      softmax_step<false>(sc, nullptr, kb + 4 * g, len, scale, m_run, l_run, alpha, pf);
+      softmax_step<Score::Plain>(sc, KeyMask{u.len, nullptr, 0, 0, false}, kb + 4 * u.g, u.scale, m_run, l_run, alpha, pf);
 #pragma unroll
       for (int n = 0; n < NT; ++n) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) o[n][i] *= alpha;
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct) {
-          const f16x4 vf = *reinterpret_cast<const f16x4*>(&sVt[(n * 16 + lr) * VROW + kb + ct * 16 + g * 4]);
+          const f16x4 vf = *reinterpret_cast<const f16x4*>(&sVt[(n * 16 + u.lr) * VROW + kb + ct * 16 + u.g * 4]);
           o[n] = __builtin_amdgcn_mfma_f32_16x16x16f16(vf, pf[ct], o[n], 0, 0, 0);
         }
       }
     }
-    store_o<HD>(o, l_run, ctx, b, h, q0 + lr, seq, hidden, g);
+    store_o<HD>(o, 1.0f / l_run, ctx, u.b, u.h, q0 + u.lr, seq, hidden, u.g);
   }
 }
 
@@ -485,25 +464,20 @@ __global__ __launch_bounds__(NW * 64) void attention_seq32_kernel(const _Float16
   extern __shared__ __attribute__((aligned(16))) char attn_smem[];
   _Float16* sK = reinterpret_cast<_Float16*>(attn_smem);                       // [SMAX][KROW]
   _Float16* sVt = sK + SMAX * KROW;                                            // [HD][VROW], keys permuted per 32-key group
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int lr = lane & 15, g = lane >> 4;
   const int heads = hidden / HD;
   const int unit = xcd_paired_unit(blockIdx.x, gridDim.x);
-  const int b = unit / heads, h = unit % heads;
-  const int len = min(max(lens[b], 1), seq);
-  const size_t row_stride = (size_t)3 * hidden;
-  const _Float16* base = qkv + (size_t)b * seq * row_stride + h * HD;
-  const float scale = kLog2e / sqrtf((float)HD);
-  const int kend = (len + KB - 1) / KB * KB;
+  const Unit u = make_unit<HD>(qkv, lens, unit / heads, unit % heads, seq, hidden);
+  const int lr = u.lr, g = u.g;
+  const int kend = (u.len + KB - 1) / KB * KB;
 
-  stage_k<HD, KROW, kThr>(sK, base, row_stride, hidden, seq, 0, kend, tid);          // (16-byte rows: whole-chunk stores)
-  stage_vt<HD, VROW, kThr, true>(sVt, base, row_stride, hidden, seq, 0, kend, tid);  // (keys permuted per 32-key group)
+  stage_k<HD, KROW, kThr>(sK, u.base, u.row_stride, hidden, seq, 0, kend, u.tid);          // (16-byte rows: whole-chunk stores)
+  stage_vt<HD, VROW, kThr, true>(sVt, u.base, u.row_stride, hidden, seq, 0, kend, u.tid);  // (keys permuted per 32-key group)
   __syncthreads();
 
-  for (int q0 = wave * (16 * QT); q0 < seq; q0 += NW * 16 * QT) {
+  for (int q0 = u.wave * (16 * QT); q0 < seq; q0 += NW * 16 * QT) {
     f16x8 qf[QT][KS];
 #pragma unroll
-    for (int t = 0; t < QT; ++t) load_q_frags<KS>(qf[t], base, row_stride, q0 + t * 16 + lr, seq, g);
+    for (int t = 0; t < QT; ++t) load_q_frags<KS>(qf[t], u.base, u.row_stride, q0 + t * 16 + lr, seq, g);
     f32x4 o[QT][NT];
     float m_run[QT], l_run[QT];
 #pragma unroll
@@ -513,7 +487,7 @@ __global__ __launch_bounds__(NW * 64) void attention_seq32_kernel(const _Float16
 #pragma unroll
       for (int n = 0; n < NT; ++n) o[t][n] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    for (int kb = 0; kb < len; kb += KB) {
+    for (int kb = 0; kb < u.len; kb += KB) {
       f32x4 sc[QT][4];
 #pragma unroll
       for (int ct = 0; ct < 4; ++ct) {
@@ -531,7 +505,7 @@ __global__ __launch_bounds__(NW * 64) void attention_seq32_kernel(const _Float16
       for (int t = 0; t < QT; ++t) {
         float alpha;
         f16x4 pf[4];
-        softmax_step<false>(sc[t], nullptr, kb + 4 * g, len, scale, m_run[t], l_run[t], alpha, pf);
+        softmax_step<Score::Plain>(sc[t], KeyMask{u.len, nullptr, 0, 0, false}, kb + 4 * g, u.scale, m_run[t], l_run[t], alpha, pf);
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2)
           pb[t][s2] = f16x8{pf[2 * s2][0], pf[2 * s2][1], pf[2 * s2][2], pf[2 * s2][3],
@@ -552,7 +526,7 @@ __global__ __launch_bounds__(NW * 64) void attention_seq32_kernel(const _Float16
       }
     }
 #pragma unroll
-    for (int t = 0; t < QT; ++t) store_o<HD>(o[t], l_run[t], ctx, b, h, q0 + t * 16 + lr, seq, hidden, g);
+    for (int t = 0; t < QT; ++t) store_o<HD>(o[t], 1.0f / l_run[t], ctx, u.b, u.h, q0 + t * 16 + lr, seq, hidden, g);
   }
 }
 
@@ -568,21 +542,17 @@ __global__ __launch_bounds__(256) void attention_short_kernel(const _Float16* __
                                                              _Float16* __restrict__ ctx, int seq, int hidden, int n_units) {
   constexpr int KS = HD / 32, NT = HD / 16, VROW = 20;        // V^T rows of 16 keys + 4 halves of padding (8-byte aligned rows)
   __shared__ __attribute__((aligned(16))) _Float16 sVt[4][HD * VROW];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int lr = lane & 15, g = lane >> 4;
-  const int unit = blockIdx.x * 4 + wave;
+  const int unit = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (unit >= n_units) return;                                 // (no workgroup barrier below)
   const int heads = hidden / HD;
-  const int b = unit / heads, h = unit % heads;
-  const int len = min(max(lens[b], 1), seq);
-  const size_t row_stride = (size_t)3 * hidden;
-  const _Float16* base = qkv + (size_t)b * seq * row_stride + h * HD;
-  const float c = 1.44269504088896341f / sqrtf((float)HD);     // log2(e) / sqrt(hd)
+  const Unit u = make_unit<HD>(qkv, lens, unit / heads, unit % heads, seq, hidden);
+  const int lane = u.tid & 63, lr = u.lr, g = u.g;
+  const float c = u.scale;
   const f16x8 z8 = {0, 0, 0, 0, 0, 0, 0, 0};
   f32x4 sc = {0.f, 0.f, 0.f, 0.f};                             // S^T: rows = keys 4 g + i, column = query lr
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
-    const _Float16* rowp = base + (size_t)lr * row_stride + ks * 32 + g * 8;
+    const _Float16* rowp = u.base + (size_t)lr * u.row_stride + ks * 32 + g * 8;
     const f16x8 qf = (lr < seq) ? *reinterpret_cast<const f16x8*>(rowp) : z8;
     const f16x8 kf = (lr < seq) ? *reinterpret_cast<const f16x8*>(rowp + hidden) : z8;
     sc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, qf, sc, 0, 0, 0);
@@ -592,17 +562,17 @@ __global__ __launch_bounds__(256) void attention_short_kernel(const _Float16* __
     const int key = lane >> 2, qt = lane & 3;
     constexpr int PER = HD / 4;                                // 16 (head_dim 64) or 8 (32) elements per lane
 #pragma unroll
-    for (int u = 0; u < PER / 8; ++u) {
-      const f16x8 v = (key < seq) ? *reinterpret_cast<const f16x8*>(base + (size_t)key * row_stride + 2 * hidden + qt * PER + u * 8) : z8;
+    for (int i = 0; i < PER / 8; ++i) {
+      const f16x8 v = (key < seq) ? *reinterpret_cast<const f16x8*>(u.base + (size_t)key * u.row_stride + 2 * hidden + qt * PER + i * 8) : z8;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) sVt[wave][(qt * PER + u * 8 + e) * VROW + key] = v[e];
+      for (int e = 0; e < 8; ++e) sVt[u.wave][(qt * PER + i * 8 + e) * VROW + key] = v[e];
     }
   }
   // softmax over the keys of query lr (keys >= len masked; key 0 is always real, so the maximum is finite)
   float mx = -1e30f;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    if (4 * g + i >= len) sc[i] = -1e30f;
+    if (4 * g + i >= u.len) sc[i] = -1e30f;
     mx = fmaxf(mx, sc[i]);
   }
   mx = fmaxf(mx, __shfl_xor(mx, 16));
@@ -622,15 +592,27 @@ __global__ __launch_bounds__(256) void attention_short_kernel(const _Float16* __
   const float inv = 1.0f / rs;
   // (every lane multiplies: as A operand lane lr is head-dim row 16 n + lr of V^T, whatever the sequence length; only the store
   // -- column = query lr -- depends on it)
-  _Float16* dst = ctx + ((size_t)b * seq + (lr < seq ? lr : 0)) * hidden + h * HD;
+  _Float16* dst = ctx + ((size_t)u.b * seq + (lr < seq ? lr : 0)) * hidden + u.h * HD;
 #pragma unroll
   for (int n = 0; n < NT; ++n) {
-    const f16x4 vf = *reinterpret_cast<const f16x4*>(&sVt[wave][(n * 16 + lr) * VROW + 4 * g]);
+    const f16x4 vf = *reinterpret_cast<const f16x4*>(&sVt[u.wave][(n * 16 + lr) * VROW + 4 * g]);
     f32x4 o = {0.f, 0.f, 0.f, 0.f};
     o = __builtin_amdgcn_mfma_f32_16x16x16f16(vf, pf, o, 0, 0, 0);
     const f16x4 ov = {(_Float16)(o[0] * inv), (_Float16)(o[1] * inv), (_Float16)(o[2] * inv), (_Float16)(o[3] * inv)};
     if (lr < seq) *reinterpret_cast<f16x4*>(dst + n * 16 + 4 * g) = ov;
   }
+}
+
+// The head_dim dispatch of the blocked, bias, window and short launches: f(std::integral_constant<int, HD>) launches its instantiation.
+template <typename F>
+int with_head_dim(int hd, F f) {
+  switch (hd) {
+    case 16: f(std::integral_constant<int, 16>{}); break;
+    case 32: f(std::integral_constant<int, 32>{}); break;
+    case 64: f(std::integral_constant<int, 64>{}); break;
+    default: return -1;
+  }
+  return (int)hipGetLastError();
 }
 
 }  // namespace
@@ -639,14 +621,9 @@ int attention_launch(const AttnPlan& p, const _Float16* qkv, const int* lens, _F
                      const float* rel_bias, int span, hipStream_t stream) {
   const dim3 grid(p.d.gx, p.d.gy, p.d.gz);
   auto blocked = [&](auto with_bias) -> int {
-    constexpr bool BIAS = decltype(with_bias)::value;
-    switch (p.hd) {
-      case 16: hipLaunchKernelGGL((attention_kernel<16, BIAS>), grid, dim3(kThreads), 0, stream, qkv, lens, ctx, seq, hidden, rel_bias, span); break;
-      case 32: hipLaunchKernelGGL((attention_kernel<32, BIAS>), grid, dim3(kThreads), 0, stream, qkv, lens, ctx, seq, hidden, rel_bias, span); break;
-      case 64: hipLaunchKernelGGL((attention_kernel<64, BIAS>), grid, dim3(kThreads), 0, stream, qkv, lens, ctx, seq, hidden, rel_bias, span); break;
-      default: return -1;
-    }
-    return (int)hipGetLastError();
+    return with_head_dim(p.hd, [&](auto hd) {
+      hipLaunchKernelGGL((attention_kernel<decltype(hd)::value, decltype(with_bias)::value>), grid, dim3(kThreads), 0, stream, qkv, lens, ctx, seq, hidden, rel_bias, span);
+    });
   };
   auto whole = [&](auto kernel) -> int {   // whole sequence per workgroup
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, p.d.lds);
@@ -660,12 +637,16 @@ int attention_launch(const AttnPlan& p, const _Float16* qkv, const int* lens, _F
       if (!p.bias) return blocked(std::false_type{});
       if (!rel_bias || seq < 1 || seq > kMaxSeq || span < seq || batch < 1 || batch > 65535) return -1;
       return blocked(std::true_type{});
-    case AttnForm::Short: {
-      const int units = heads * batch;
-      if (p.hd == 32) hipLaunchKernelGGL((attention_short_kernel<32>), grid, dim3(256), 0, stream, qkv, lens, ctx, seq, hidden, units);
-      else hipLaunchKernelGGL((attention_short_kernel<64>), grid, dim3(256), 0, stream, qkv, lens, ctx, seq, hidden, units);
-      return (int)hipGetLastError();
-    }
+    case AttnForm::Window:
+      if (p.window < 1) return -1;
+      return with_head_dim(p.hd, [&](auto hd) {
+        hipLaunchKernelGGL((attention_window_kernel<decltype(hd)::value>), grid, dim3(kThreads), 0, stream, qkv, lens, ctx, seq, hidden, p.window);
+      });
+    case AttnForm::Short:
+      if (p.hd == 16) return -1;             // (the short kernel's first product is 32 deep)
+      return with_head_dim(p.hd, [&](auto hd) {
+        if constexpr (decltype(hd)::value != 16) hipLaunchKernelGGL((attention_short_kernel<decltype(hd)::value>), grid, dim3(256), 0, stream, qkv, lens, ctx, seq, hidden, heads * batch);
+      });
     case AttnForm::Seq32:
       if (is(32, 256, 4)) return whole(&attention_seq32_kernel<32, 256, 4, 4>);
       if (is(64, 512, 4)) return whole(&attention_seq32_kernel<64, 512, 8, 4>);
@@ -681,18 +662,6 @@ int attention_launch(const AttnPlan& p, const _Float16* qkv, const int* lens, _F
       return -1;
     default: return -1;
   }
-}
-
-int attention_window_launch(const AttnPlan& p, const _Float16* qkv, const int* lens, _Float16* ctx, int seq, int hidden, hipStream_t stream) {
-  if (p.form != AttnForm::Window || p.window < 1) return -1;
-  const dim3 grid(p.d.gx, p.d.gy, p.d.gz);
-  switch (p.hd) {
-    case 16: hipLaunchKernelGGL((attention_window_kernel<16>), grid, dim3(kThreads), 0, stream, qkv, lens, ctx, seq, hidden, p.window); break;
-    case 32: hipLaunchKernelGGL((attention_window_kernel<32>), grid, dim3(kThreads), 0, stream, qkv, lens, ctx, seq, hidden, p.window); break;
-    case 64: hipLaunchKernelGGL((attention_window_kernel<64>), grid, dim3(kThreads), 0, stream, qkv, lens, ctx, seq, hidden, p.window); break;
-    default: return -1;
-  }
-  return (int)hipGetLastError();
 }
 
 }  // namespace crs

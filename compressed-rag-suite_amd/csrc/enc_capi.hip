@@ -330,7 +330,7 @@ static int encoder_forward(const crs_encoder_desc* d, const crs_encoder_weights*
     CRS_TRY(crs::gemm_launch(p.qkv, x16, (const _Float16*)L.w_qkv, L.b_qkv, nullptr, qkv, st), "qkv gemm");
     CRS_TRY(crs::rope_qk_launch(p.rope, p.attn.hd, qkv, full ? pre->rope_global_dev : pre->rope_local_dev, T, seq, H, st), "rope");
     if (full) CRS_TRY(crs::attention_launch(p.attn, qkv, lens_dev, ctx, batch, seq, H, d->heads, nullptr, 0, st), "attention");
-    else CRS_TRY(crs::attention_window_launch(p.win, qkv, lens_dev, ctx, seq, H, st), "windowed attention");
+    else CRS_TRY(crs::attention_launch(p.win, qkv, lens_dev, ctx, batch, seq, H, d->heads, nullptr, 0, st), "windowed attention");
     CRS_TRY(add_ln(p.out, ctx, L.w_o, L.b_o, L.ln2_g, L.ln2_b, nullptr), "out projection + add + mlp norm");
     CRS_TRY(crs::gemm_launch(p.up, x16, (const _Float16*)L.w_up, L.b_up, nullptr, ffn, st), "ffn up gemm");
     float* n32 = last ? reinterpret_cast<float*>(qkv) : nullptr;
@@ -494,7 +494,8 @@ int crs_attention_window_f16(const void* qkv_dev, const int32_t* lens_dev, void*
   if (!why && window < 1) why = "attention: window must be >= 1";
   if (why) return crs::set_error(CRS_EINVAL, why);
   const crs::AttnPlan p = crs::plan_attention_window(batch, seq, heads, hidden / heads, window, knobs());
-  CRS_TRY(crs::attention_window_launch(p, (const _Float16*)qkv_dev, lens_dev, (_Float16*)ctx_dev, seq, hidden, (hipStream_t)stream), "windowed attention");
+  CRS_TRY(crs::attention_launch(p, (const _Float16*)qkv_dev, lens_dev, (_Float16*)ctx_dev, batch, seq, hidden, heads, nullptr, 0, (hipStream_t)stream),
+          "windowed attention");
   return CRS_OK;
 }
 
