@@ -2,6 +2,7 @@
 
   f16                round an array to fp16 (nearest even) and give it back in fp64: the operands the device multiplies.
   transform_ref      cls.predictions.transform in fp64: t = LayerNorm(GELU(W_t h + b_t)), erf-form GELU, biased variance.
+  transform_ref_and_bound  the same with the derived bound of the kernel's stored fp16 value, for every H (its docstring).
   pool_ref           out[b, v] = log1p(max(0, max_{i < lens[b]} (t_i . Wd_v + bias_v))) in fp64, and per (b, v) the largest
                      sum_k |t_ik Wd_vk| over the text's real tokens: what the rounding bound of a device result is made of.
   head_ref           the two chained, nothing rounded: the whole head in fp64.
@@ -37,6 +38,66 @@ def transform_ref(hidden, w_t, b_t, gamma, beta, eps):
     mean = x.mean(-1, keepdims=True)
     var = ((x - mean) ** 2).mean(-1, keepdims=True)
     return (x - mean) / np.sqrt(var + float(eps)) * np.asarray(gamma, dtype=np.float64) + np.asarray(beta, dtype=np.float64)
+
+
+def _preact_chain32(h, w, b_t):
+    """W_t h + b_t in plain fp32, the longest chain there is: one accumulator per element, the products (exact in fp32 for fp16
+    operands) added one at a time in ascending k, every addition rounded to fp32, the bias last.  Returned in fp64."""
+    h32, w32 = np.asarray(h, dtype=np.float32), np.ascontiguousarray(np.asarray(w, dtype=np.float32).T)
+    acc = np.zeros((h32.shape[0], w32.shape[1]), dtype=np.float32)
+    for k in range(h32.shape[1]):
+        acc = acc + h32[:, k:k + 1] * w32[k:k + 1]
+    return (acc + np.asarray(b_t, dtype=np.float32)).astype(np.float64)
+
+
+def transform_ref_and_bound(hidden16, w_t, b_t, gamma, beta, eps):
+    """(ref fp64 [tokens, H], bound16 fp64 [tokens, H], second-order fraction) of mlm_transform_kernel<NJ> (csrc/mlm_pool.hip) for
+    every H: what a stored fp16 element of t may differ from transform_ref by.  hidden16 [tokens, H] and w_t [H, H] are the
+    fp16-rounded operands the kernel multiplies (rounded here again, which changes nothing).  Derived by counting the kernel's fp32
+    operations, an operation erring by at most one ulp of its result (2u relative, u = 2^-24; _row_ref.gamma(n) bounds n of them in
+    a row); nothing is fitted to what a device gives.
+
+      pre-activation  x_j = W_t[j] . h + b_t[j].  fp16 x fp16 products are exact in fp32; the accumulator takes H additions, in
+                      whatever order the matrix instruction adds the 32 products of a step, and the bias is one more.  The worst
+                      case of that count is
+                        W_j = gamma(H + 1) (sum_k |w_jk| |h_k| + |b_j|),
+                      which charges every addition an ulp of sum |w| |h| -- 20 times |x_j| at H = 1024, where the partial sums an
+                      addition really rounds are of the size of x_j -- and grows with H besides: behind the LayerNorm it is 2e-4 at
+                      H = 64 and 1e-2 at H = 1024, while the erf and the tanh form of GELU differ by 1e-3 at most, so it could not
+                      tell a wrong activation from a right one at any H (tests/test_mlm_cases_cpu.py asserts that this bound
+                      can).  What stands in its place is the accumulation-order rule of tests/_encoder_cases.py, the one
+                      ln_ref_and_bound uses for its own statistics: the plain fp32 evaluation's distance from fp64 on the same
+                      operands, times 4 because the device's summation order differs from the plain one as that does from fp64.
+                      The plain evaluation is _preact_chain32, the longest chain (H + 1 roundings in a row; the kernel's
+                      accumulator is rounded once per 32-product step at best and no more often than the chain at worst), and the
+                      largest distance over the case is taken for every element:
+                        E_pre = min(W_j, 4 max_ij |chain32_ij - x_ij|).
+                      It comes from the references alone and is the same on every machine (no BLAS in it).
+      GELU            y = GELU(x), erf form.  |GELU'| <= GELU_SLOPE and csrc/enc_gelu.h states GELU_ERR for its rational erf
+                      (both from tests/_gemm_ref.py); the last product rounds once more:
+                        E_y = GELU_SLOPE E_pre + GELU_ERR + 2u |y|.
+      LayerNorm       _row_ref.ln_ref_and_bound on the row values y with error E_y: the first-order bound of a two-pass LayerNorm,
+                      its accumulation-order term, and half an fp16 ulp of the stored value (bound16).  The kernel forms both
+                      statistics from registers: per wave the NJ tiles of a lane, a butterfly over the 16 lanes of a tile, then the
+                      four waves' partial sums added in wave order -- one of the "any order" sums that bound already allows.
+
+    The second-order fraction is that function's; above _row_ref.SECOND_ORDER_LIMIT a case is inadmissible (the tests assert it on
+    the CPU and choose inputs for which it is not)."""
+    import torch
+    import _row_ref as rr
+    from _gemm_ref import GELU_ERR, GELU_SLOPE
+    h, w, b = f16(hidden16), f16(w_t), np.asarray(b_t, dtype=np.float64)
+    H = w.shape[1]
+    x = h @ w.T + b
+    e_pre = rr.gamma(H + 1) * (np.abs(h) @ np.abs(w).T + np.abs(b))
+    chain = 4.0 * np.abs(_preact_chain32(h, w, b_t) - x).max()
+    e_pre = np.minimum(e_pre, chain)
+    y =0.5 * x * (1.0 + _erf(x / math.sqrt(2.0)))
+    e_y = GELU_SLOPE * e_pre + GELU_ERR + 2.0 * U32 * np.abs(y)
+    as_t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt))          # noqa: E731
+    ref, _, bound16, second = rr.ln_ref_and_bound(as_t(y, np.float64), as_t(e_y, np.float64), as_t(gamma, np.float32),
+                                                  as_t(beta, np.float32), float(eps))
+    return ref.numpy(), bound16.numpy(), second
 
 
 def pool_ref(t, lens, w_d, bias):

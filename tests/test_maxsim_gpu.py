@@ -187,8 +187,8 @@ def test_order_equals_the_fp64_order_where_the_gap_allows(cuda):
 
 # ---- the projection ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("with_bias", [False, True], ids=["nobias", "bias"])
-@pytest.mark.parametrize("dim", [32, 90, 96, 128])
-@pytest.mark.parametrize("H", [64, 384, 768])
+@pytest.mark.parametrize("dim", [32, 33, 64, 90, 96, 128])
+@pytest.mark.parametrize("H", [64, 384, 768, 1024])
 def test_token_project_matches_fp64(cuda, H, dim, with_bias):
     """n_tok 150 (three workgroups, the last one ragged, and no multiple of 16): a third of the tokens dropped (their hidden rows
     NaN), the kept ones packed in a shuffled order, one token with a zero hidden row.  dim 96 fills every row of the sixth column

@@ -11,20 +11,12 @@ import numpy as np
 import pytest
 
 import _sparse_ref as ref
+from _mlm_cases import head as _head          # (the seeded weights: shared with tests/test_mlm_pool_shapes_gpu.py)
 
 pytestmark = pytest.mark.gpu
 
 TILE_N = ref.TILE_N
 H = 64
-
-
-def _head(V, Hd, seed):
-    rng = np.random.default_rng(seed)
-    w_t = (rng.standard_normal((Hd, Hd)) / np.sqrt(Hd)).astype(np.float16)
-    w_d = (rng.standard_normal((V, Hd)) * 0.05).astype(np.float16)
-    return dict(w_t=w_t, b_t=(rng.standard_normal(Hd) * 0.1).astype(np.float32), gamma=(1.0 + 0.1 * rng.standard_normal(Hd)).astype(np.float32),
-                beta=(0.1 * rng.standard_normal(Hd)).astype(np.float32), eps=1e-12, w_d=w_d,
-                bias=(rng.standard_normal(V) * 0.2 - 0.1).astype(np.float32))
 
 
 def _dev(cuda, a):
@@ -74,7 +66,14 @@ def _check(out, t16, guard, head, hidden, lens, vp):
         assert (err <= tol).all(), f"transform, text {b}: worst error / tolerance {np.max(err / tol):.3f}"
         assert (t_dev[b, n:] == 0).all(), f"text {b}: padding rows of t are not zero"
     assert (t16[batch * seq:] == 0).all()
-    # the projection + pool: fp64 on the device's own t and the fp16 decoder
+    return _check_pool(out, t16, guard, head, lens, batch, seq, vp)
+
+
+def _check_pool(out, t16, guard, head, lens, batch, seq, vp):
+    """the projection + pool: fp64 on the device's own t and the fp16 decoder"""
+    Hd = t16.shape[1]
+    V = head["w_d"].shape[0]
+    t_dev = t16[: batch * seq].astype(np.float64).reshape(batch, seq, Hd)
     want, absdot = ref.pool_ref(t_dev, lens, head["w_d"], head["bias"])
     bound = ref.pool_bound(absdot, want, Hd)
     got = out[:, :V].astype(np.float64)
