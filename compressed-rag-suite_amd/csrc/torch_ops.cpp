@@ -867,6 +867,62 @@ void sparse_topk(const Tensor& doc_offsets, const Tensor& doc_tokens, const Tens
                      out_rows.data_ptr<int64_t>(), cur_stream(doc_offsets)), "crs::sparse_topk");
 }
 
+// ---- MXFP4 index (csrc/row_build_mxfp4.hip, csrc/scan_mxfp4.hip) ------------------------------------------------------------------
+// emb fp32 [n, dim]; data / scales uint8 (crs_mxfp4_slab_bytes of the capacity); rows int64 [n] (scatter) or none (append at row0);
+// shadow fp32 [cap, dim] / row_err fp32 [cap] optional
+void slab_write_mxfp4(const Tensor& emb, Tensor data, Tensor scales, c10::optional<Tensor> rows, int64_t row0, int64_t n_rows,
+                      c10::optional<Tensor> shadow, c10::optional<Tensor> row_err) {
+  want(emb, at::kFloat, "emb");
+  want(data, at::kByte, "data");
+  want(scales, at::kByte, "scales");
+  if (has(rows)) want(*rows, at::kLong, "rows");
+  if (has(shadow)) want(*shadow, at::kFloat, "shadow");
+  if (has(row_err)) want(*row_err, at::kFloat, "row_err");
+  same_device(emb, {&data, &scales, opt_t(rows), opt_t(shadow), opt_t(row_err)}, "crs::slab_write_mxfp4");
+  TORCH_CHECK(emb.dim() == 2 && emb.size(1) >= 1 && emb.size(1) <= 1024, "emb must be fp32 [n, 1 <= dim <= 1024]");
+  const int64_t n = emb.size(0), dim = emb.size(1);
+  const int64_t cap = has(rows) ? n_rows : row0 + n;      // rows the call may touch
+  TORCH_CHECK(row0 >= 0 && n_rows >= 0, "row0 / n_rows must not be negative");
+  TORCH_CHECK(!has(rows) || (rows->dim() == 1 && rows->numel() == n), "rows must be int64 [n]");
+  size_t db = 0, sb = 0;
+  ok(crs_mxfp4_slab_bytes(cap, (int)dim, &db, &sb), "crs::slab_write_mxfp4");
+  TORCH_CHECK((size_t)data.numel() >= db && (size_t)scales.numel() >= sb, "data / scales are smaller than crs_mxfp4_slab_bytes of the rows written");
+  TORCH_CHECK(!has(shadow) || shadow->numel() >= cap * dim, "shadow must hold [rows, dim]");
+  TORCH_CHECK(!has(row_err) || row_err->numel() >= cap, "row_err must hold [rows]");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(emb.device());
+  float* sh = has(shadow) ? shadow->data_ptr<float>() : nullptr;
+  float* re = has(row_err) ? row_err->data_ptr<float>() : nullptr;
+  if (has(rows))
+    ok(crs_slab_write_rows_mxfp4_f32(emb.data_ptr<float>(), rows->data_ptr<int64_t>(), n, (int)dim, data.data_ptr(), scales.data_ptr(), sh,
+                                     n_rows, re, cur_stream(emb)), "crs::slab_write_mxfp4");
+  else
+    ok(crs_slab_append_mxfp4_f32(emb.data_ptr<float>(), n, (int)dim, data.data_ptr(), scales.data_ptr(), sh, row0, re, cur_stream(emb)),
+       "crs::slab_write_mxfp4");
+}
+
+// q32 fp32 [nq <= 64, dim]; data / scales as above; workspace uint8; out_scores fp32 / out_ids int64 [nq, kp]
+void mxfp4_topk(const Tensor& q32, const Tensor& data, const Tensor& scales, int64_t n_rows, int64_t kp, int64_t id_base, Tensor workspace,
+                Tensor out_scores, Tensor out_ids) {
+  want(q32, at::kFloat, "q32");
+  want(data, at::kByte, "data");
+  want(scales, at::kByte, "scales");
+  want(workspace, at::kByte, "workspace");
+  want(out_scores, at::kFloat, "out_scores");
+  want(out_ids, at::kLong, "out_ids");
+  same_device(q32, {&data, &scales, &workspace, &out_scores, &out_ids}, "crs::mxfp4_topk");
+  TORCH_CHECK(q32.dim() == 2 && q32.size(0) >= 1 && q32.size(0) <= 64 && q32.size(1) >= 1 && q32.size(1) <= 1024,
+              "q32 must be fp32 [1 <= nq <= 64, 1 <= dim <= 1024]");
+  TORCH_CHECK(n_rows >= 1, "n_rows must be >= 1");
+  size_t db = 0, sb = 0;
+  ok(crs_mxfp4_slab_bytes(n_rows, (int)q32.size(1), &db, &sb), "crs::mxfp4_topk");
+  TORCH_CHECK((size_t)data.numel() >= db && (size_t)scales.numel() >= sb, "data / scales are smaller than crs_mxfp4_slab_bytes(n_rows, dim)");
+  TORCH_CHECK(out_scores.numel() == q32.size(0) * kp && out_ids.numel() == q32.size(0) * kp, "outputs must hold [nq, kp]");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(q32.device());
+  ok(crs_mxfp4_topk(q32.data_ptr<float>(), (int)q32.size(0), (int)q32.size(1), data.data_ptr(), scales.data_ptr(), n_rows, (int)kp, id_base,
+                    workspace.data_ptr(), (size_t)workspace.numel(), out_scores.data_ptr<float>(), out_ids.data_ptr<int64_t>(),
+                    cur_stream(q32)), "crs::mxfp4_topk");
+}
+
 // dense_rows int64 [nq, m_dense], lex_rows int64 [nq, m_lex]; rows int64 / fused fp64 / dense_pos, lex_pos int32 [nq, k_out]; count int32 [nq]
 void fuse_rrf(const Tensor& dense_rows, const Tensor& lex_rows, double c, double w_dense, double w_lex, Tensor rows, Tensor fused,
               Tensor dense_pos, Tensor lex_pos, Tensor count) {
@@ -1206,6 +1262,8 @@ TORCH_LIBRARY(crs, m) {
         "Tensor(c!) dense_pos, Tensor(d!) lex_pos, Tensor(e!) count) -> ()");
   m.def("mlm_sparse_pool(Tensor hidden, Tensor lens, Tensor transform_w16, Tensor transform_bias, Tensor ln_gamma, Tensor ln_beta, "
         "float ln_eps, Tensor decoder_w16, Tensor decoder_bias, int max_pos, Tensor(a!) workspace, Tensor(b!) out) -> ()");
+  m.def("slab_write_mxfp4(Tensor emb, Tensor(a!) data, Tensor(b!) scales, Tensor? rows, int row0, int n_rows, Tensor(c!)? shadow, Tensor(d!)? row_err) -> ()");
+  m.def("mxfp4_topk(Tensor q32, Tensor data, Tensor scales, int n_rows, int kp, int id_base, Tensor(a!) workspace, Tensor(b!) out_scores, Tensor(c!) out_ids) -> ()");
   m.def("sparse_compact(Tensor weights, int vocab, Tensor? skip_ids, Tensor(a!) ids, Tensor(b!) out_weights, Tensor(c!) counts) -> ()");
   m.def("sparse_topk(Tensor doc_offsets, Tensor doc_tokens, Tensor doc_weights, int n_rows, Tensor q_offsets, Tensor q_tokens, "
         "Tensor q_weights, int k, Tensor(a!) workspace, Tensor(b!) out_scores, Tensor(c!) out_rows) -> ()");
@@ -1264,6 +1322,8 @@ TORCH_LIBRARY_IMPL(crs, CUDA, m) {   // the HIP backend of torch-ROCm dispatches
   m.impl("bm25_topk", &bm25_topk);
   m.impl("fuse_rrf", &fuse_rrf);
   m.impl("mlm_sparse_pool", &mlm_sparse_pool);
+  m.impl("slab_write_mxfp4", &slab_write_mxfp4);
+  m.impl("mxfp4_topk", &mxfp4_topk);
   m.impl("sparse_compact", &sparse_compact);
   m.impl("sparse_topk", &sparse_topk);
   m.impl("wordpiece_encode", &wordpiece_encode);

@@ -111,6 +111,14 @@ _SIGNATURES = {
     "crs_score_rows_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "crs_refine_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_int64, c_void_p, c_int, c_int,
                                c_void_p, c_void_p, c_void_p]),
+    "crs_mxfp4_row_bytes": (c_int, [c_int]),
+    "crs_mxfp4_slab_bytes": (c_int, [c_int64, c_int, POINTER(c_size_t), POINTER(c_size_t)]),
+    "crs_slab_append_mxfp4_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "crs_slab_write_rows_mxfp4_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "crs_mxfp4_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int64, POINTER(c_size_t)]),
+    "crs_mxfp4_plan_describe": (c_int, [c_int, c_int, c_int, c_int64, c_int, ctypes.c_char_p, c_size_t]),
+    "crs_mxfp4_topk": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p, c_size_t, c_void_p, c_void_p,
+                               c_void_p]),
     "crs_exact_workspace_bytes": (c_size_t, [c_int, c_int]),
     "crs_exact_row_error_bound": (c_float, [c_int, c_int]),
     "crs_refine_f32_cert": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
@@ -774,6 +782,76 @@ def overfetch(nq: int, top_k: int, want: int = 24, n_rows: int = 1 << 62, slab_t
     if n_rows < 4_000_000 or (nq > 64 and top_k <= 16) or slab_type == SLAB_I8:
         want = min(want, 16)
     return min(MAX_K, max(int(top_k), want, -(-8 * int(top_k) // 5)))
+
+
+# ---- MXFP4 index (csrc/row_build_mxfp4.hip, csrc/scan_mxfp4.hip) ----------------------------------------------------
+MXFP4_KP = (32, 64, 128)    # list lengths crs_mxfp4_topk selects
+
+
+def mxfp4_row_bytes(dim: int) -> int:
+    """Bytes of one MXFP4 slab row, elements and block scales together."""
+    return int(load().crs_mxfp4_row_bytes(int(dim)))
+
+
+def mxfp4_slab_bytes(rows: int, dim: int):
+    """(data bytes, scale bytes) of an MXFP4 slab of `rows` rows: whole 16-row tiles."""
+    d, sc = c_size_t(0), c_size_t(0)
+    check(load().crs_mxfp4_slab_bytes(int(rows), int(dim), ctypes.byref(d), ctypes.byref(sc)))
+    return int(d.value), int(sc.value)
+
+
+def mxfp4_alloc(rows: int, dim: int, device):
+    """Zeroed (data, scales) uint8 buffers of an MXFP4 slab with room for `rows` rows."""
+    import torch
+    d, sc = mxfp4_slab_bytes(rows, dim)
+    return torch.zeros(d, dtype=torch.uint8, device=device), torch.zeros(sc, dtype=torch.uint8, device=device)
+
+
+def slab_append_mxfp4(emb, data, scales, row0: int, shadow=None, row_err=None) -> None:
+    """emb cuda fp32 [n, dim] -> rows row0 .. row0 + n of the MXFP4 slab (data, scales); shadow fp32 [cap, dim] receives the unit
+    rows, row_err fp32 [cap] each row's |unit row - dequantised row|_2."""
+    if emb.shape[0] == 0:
+        return
+    with _translate():
+        ops().slab_write_mxfp4(emb, data, scales, None, int(row0), 0, shadow, row_err)
+
+
+def slab_write_rows_mxfp4(emb, rows, data, scales, n_rows: int, shadow=None, row_err=None) -> None:
+    """The scatter form: emb[r] -> row rows[r] (cuda int64, < n_rows), the same bits as the append."""
+    if emb.shape[0] == 0:
+        return
+    with _translate():
+        ops().slab_write_mxfp4(emb, data, scales, rows, 0, int(n_rows), shadow, row_err)
+
+
+def mxfp4_workspace_bytes(nq: int, dim: int, kp: int, n_rows: int) -> int:
+    b = c_size_t(0)
+    check(load().crs_mxfp4_workspace_bytes(int(nq), int(dim), int(kp), int(n_rows), ctypes.byref(b)))
+    return int(b.value)
+
+
+def mxfp4_plan_describe(nq: int, dim: int, kp: int, n_rows: int, cus: int = 256) -> str:
+    """The plan line of an MXFP4 sweep for `cus` compute units (no device needed)."""
+    buf = ctypes.create_string_buffer(256)
+    check(load().crs_mxfp4_plan_describe(int(nq), int(dim), int(kp), int(n_rows), int(cus), buf, 256))
+    return buf.value.decode()
+
+
+def mxfp4_topk(q32, data, scales, n_rows: int, kp: int, id_base: int = 0, workspace=None):
+    """The kp (32, 64 or 128) best slab scores of each of q32's rows (cuda fp32 [nq, dim], any nq: 64 per sweep) over an MXFP4
+    slab: (scores fp32 [nq, kp], ids int64 [nq, kp]) sorted score desc / id asc, empty slots (-inf, -1)."""
+    import torch
+    nq, dim = q32.shape
+    out_s = torch.empty((nq, kp), dtype=torch.float32, device=q32.device)
+    out_i = torch.empty((nq, kp), dtype=torch.int64, device=q32.device)
+    for q0 in range(0, nq, 64):
+        m = min(64, nq - q0)
+        need = mxfp4_workspace_bytes(m, dim, kp, n_rows)
+        if workspace is None or workspace.numel() < need:
+            workspace = torch.empty(need, dtype=torch.uint8, device=q32.device)
+        with _translate():
+            ops().mxfp4_topk(q32[q0:q0 + m].contiguous(), data, scales, int(n_rows), int(kp), int(id_base), workspace, out_s[q0:q0 + m], out_i[q0:q0 + m])
+    return out_s, out_i
 
 
 def exact_workspace_bytes(nq: int, cap: int = EXACT_CAP) -> int:

@@ -10,6 +10,9 @@ ids and metadata stay on the host, indexed by row.
 New, additive surface (all keys absent from the reference config.json default so that it works unmodified):
   ``search_batch``            many queries per launch
   ``index_dtype``             'fp16' (default) | 'int8' (per-row scale)
+                              | 'mxfp4' (OCP microscaling rows, 4-bit elements + one scale per 32, swept by the block-scaled MFMA and
+                              re-ranked in fp32 from ``mxfp4_overfetch`` x top_k candidates; one device, cosine, in memory, top_k <= 64,
+                              no certificate: DESIGN 3.19)
   ``refine_fp32``             (default ON) keep an fp32 shadow of the rows (4 x dim bytes per row beside the fp16 / int8
                               slab), over-fetch ``refine_overfetch`` (24; 16 on shards below 4 M rows; at least 1.6 x top_k
                               above top_k 10: nat.overfetch) candidates and re-rank them in fp32: the ranking an
@@ -113,6 +116,7 @@ There is no CPU fallback: without a GPU or without the native libraries every se
 """
 from __future__ import annotations
 
+import functools
 import json
 import logging
 import os
@@ -155,6 +159,10 @@ class _Shard:
         self.shadow = None             # torch [capacity, sdim] fp32 (refine_fp32 only)
         self.rows_global = None        # torch [capacity] int64: sidecar row of each local row
         self.identity = True           # rows_global[i] == i for every row (single shard, unsharded): no mapping needed
+        # index_dtype 'mxfp4' (DESIGN 3.19): slab = the tiled e2m1 bytes, scales = the e8m0 plane (both uint8, whole 16-row tiles),
+        # row_errs = |unit row - dequantised row|_2 of every row
+        self.mx = index_dtype == "mxfp4"
+        self.row_errs = None
 
     @property
     def slab_type(self) -> int:
@@ -174,11 +182,26 @@ class _Shard:
             if sdim > 1024:
                 raise ValueError(f"Embedding dimension {dim} is too large for space 'l2' (at most 1023: a row stores one more coordinate)")
             self.dim, self.sdim, self.pdim = dim, sdim, nat.padded_dim(sdim, self.slab_type)
+            if self.mx:
+                self.pdim = -(-dim // 128) * 128
         elif dim != self.dim:
             raise ValueError(f"Embedding dimension {dim} doesn't match the index dimension {self.dim}")
         if rows <= self.capacity:
             return
         cap = max(rows, int(self.capacity * 1.5) + 1024)
+        if self.mx:
+            # the layout is tile-major: the bytes of the first n rows' tiles are a prefix of both buffers
+            data, scales = nat.mxfp4_alloc(cap, dim, self.device)
+            if self.n:
+                for new, old, keep in zip((data, scales), (self.slab, self.scales), nat.mxfp4_slab_bytes(self.n, dim)):
+                    new[:keep].copy_(old[:keep])
+            self.slab, self.scales = data, scales
+            self.row_errs = self._grow(self.row_errs, (cap,), torch.float32)
+            if self.refine_fp32:
+                self.shadow = self._grow(self.shadow, (cap, self.sdim), torch.float32)
+            self.rows_global = self._grow(self.rows_global, (cap,), torch.int64)
+            self.capacity = cap
+            return
         self.slab = self._grow(self.slab, (cap, self.pdim), torch.int8 if self.slab_type == nat.SLAB_I8 else torch.float16)
         if self.slab_type == nat.SLAB_I8:
             self.scales = self._grow(self.scales, (cap,), torch.float32)
@@ -193,7 +216,11 @@ class _Shard:
         behind all of it, so an updated row equals the same vector appended bit for bit.  In the spaces 'ip' / 'l2' the caller
         (VectorStore._grow_scale) has made norm_scale cover emb."""
         kw = dict(scales=self.scales, shadow=self.shadow, row_err=self.row_err)
-        if self.space == nat.SPACE_COSINE:
+        if self.mx:
+            if local_rows is not None:
+                raise NotImplementedError("update / upsert is not supported with index_dtype 'mxfp4'")
+            nat.slab_append_mxfp4(emb, self.slab, self.scales, self.n, shadow=self.shadow, row_err=self.row_errs)
+        elif self.space == nat.SPACE_COSINE:
             if local_rows is None:
                 nat.slab_append_f32(emb, self.slab, self.n, self.slab_type, **kw)
             else:
@@ -241,6 +268,9 @@ class _Shard:
     def row_err_max(self) -> float:
         """The tracked row error as a host float (one 4-byte D2H after an append, cached until the next one)."""
         if self._row_err_host is None:
+            if self.mx:
+                self._row_err_host = float(self.row_errs[:self.n].max().item()) if self.n else 0.0
+                return self._row_err_host
             self._row_err_host = float(self.row_err.item())
         return self._row_err_host
 
@@ -249,6 +279,9 @@ class _Shard:
 
     def view(self) -> _search.ShardView:
         """These rows as a search sees them (the tensors are shared, not copied)."""
+        if self.mx:
+            raise NotImplementedError("the engine's fused chunks and the fp16 / int8 search views are not supported with index_dtype "
+                                      "'mxfp4': its rows are searched by VectorStore.search / search_batch / search_rows")
         return _search.ShardView(self.slab, self.scales, self.shadow, self.n, self.sdim, self.slab_type, 0, self.row_err_max(),
                                  None if (self.identity or not self.n) else self.rows_global[:self.n], self.space, self.norm_scale)
 
@@ -771,6 +804,18 @@ class SlabCollection:
         return rows
 
 
+def _not_with_mxfp4(option: str):
+    """Decorator of the VectorStore methods that index_dtype 'mxfp4' does not serve: NotImplementedError naming it."""
+    def wrap(fn):
+        @functools.wraps(fn)
+        def guarded(self, *args, **kwargs):
+            if self.index_dtype == 'mxfp4':
+                raise NotImplementedError(f"{option} is not supported with index_dtype 'mxfp4'")
+            return fn(self, *args, **kwargs)
+        return guarded
+    return wrap
+
+
 class VectorStore:
     """Vector store on an HBM slab.  Handles storage, indexing and exact similarity search."""
 
@@ -779,8 +824,12 @@ class VectorStore:
         self.persist_directory = config.get('persist_directory', None)
         # additive knobs (absent from the reference config.json -> defaults)
         self.index_dtype = config.get('index_dtype', 'fp16')
-        if self.index_dtype not in ('fp16', 'int8'):
-            raise ValueError(f"index_dtype must be 'fp16' or 'int8', got {self.index_dtype!r}")
+        if self.index_dtype not in ('fp16', 'int8', 'mxfp4'):
+            raise ValueError(f"index_dtype must be 'fp16', 'int8' or 'mxfp4', got {self.index_dtype!r}")
+        # mxfp4: the scan fetches the smallest k' of 32 / 64 / 128 that is >= mxfp4_overfetch * top_k for the fp32 re-rank
+        self.mxfp4_overfetch = int(config.get('mxfp4_overfetch', 4))
+        if self.mxfp4_overfetch < 1:
+            raise ValueError(f"mxfp4_overfetch must be >= 1, got {self.mxfp4_overfetch}")
         refine = config.get('refine_fp32', 'auto')
         self.refine_fp32 = True if refine == 'auto' else bool(refine)
         self.space = config.get('space', 'cosine')
@@ -820,6 +869,13 @@ class VectorStore:
         self._join_first_cap = 1 << 16                    # candidate slots a stripe is first given (it is re-run when they overflow)
         if self.dedup_threshold is not None:
             self.dedup_threshold = self._join_refusals(self.dedup_threshold)
+        if self.index_dtype == 'mxfp4':
+            for option, on in (("sharded=True", self.sharded), ("num_gpus > 1", self.num_gpus > 1), ("devices", bool(self._devices_cfg)),
+                               (f"space {self.space!r}", self.space != 'cosine'), ("persist_directory", bool(self.persist_directory)),
+                               ("dedup_threshold", self.dedup_threshold is not None)):
+                if on:
+                    raise NotImplementedError(f"{option} is not supported with index_dtype 'mxfp4' (one device, cosine space, in "
+                                              "memory: DESIGN 3.19)")
         if self.sharded and (self.num_gpus > 1 or self._devices_cfg):
             raise ValueError("'sharded' (one process per GPU) and 'num_gpus'/'devices' (one process, N devices) are exclusive")
         if self.sharded and self.persist_directory:
@@ -1014,6 +1070,7 @@ class VectorStore:
         self._persisted_rows = n if (not legacy and bool(meta.get("shadow")) == bool(refine)) else None
         logger.info(f"Loaded existing collection: {self.collection_name} ({col.count()} rows)")
 
+    @_not_with_mxfp4("persistence (persist)")
     def persist(self, first_new_row: Optional[int] = None, generation: bool = False):
         """Bring the files under persist_directory up to date.  With first_new_row = the files' row count, only rows
         [first_new_row, n) are APPENDED (create_index does this: O(batch)); otherwise everything is rewritten.
@@ -1216,6 +1273,7 @@ class VectorStore:
         sel = (rg[pos] == g_rows).nonzero().flatten()
         return sel, pos[sel]
 
+    @_not_with_mxfp4("delete")
     def delete(self, ids: Optional[Sequence[str]] = None, where: Optional[dict] = None,
                where_document: Optional[dict] = None) -> int:
         """Remove the rows whose id is in `ids` AND that pass the filters (either part may be absent, not all three).  Unknown
@@ -1280,6 +1338,9 @@ class VectorStore:
     # -- near-duplicate detection (module docstring: near_duplicates / duplicate_of / deduplicate / dedup_threshold) ---------------
     def _join_refusals(self, threshold) -> float:
         """Everything that rules the join out, raised before any device work -> the threshold as a float."""
+        if self.index_dtype == 'mxfp4':
+            raise NotImplementedError("near-duplicate detection (near_duplicates / duplicate_of / deduplicate / dedup_threshold) is not "
+                                      "supported with index_dtype 'mxfp4': the join reads fp16 rows")
         if self.index_dtype == 'int8':
             raise NotImplementedError("near-duplicate detection is not supported with index_dtype 'int8': the int8 row error makes "
                                       "the candidate band wide, and the join needs an integer kernel of its own")
@@ -1455,6 +1516,7 @@ class VectorStore:
             if metadatas is not None:
                 col.metadatas[row] = dict(metadatas[at])
 
+    @_not_with_mxfp4("update")
     def update(self, ids: Sequence[str], embeddings=None, documents: Optional[Sequence[str]] = None,
                metadatas: Optional[Sequence[dict]] = None) -> None:
         """Per id, replace what is given: the embedding (the device rows are rewritten by the append's own per-row function),
@@ -1467,6 +1529,7 @@ class VectorStore:
         self._apply_update(rows, emb, documents, metadatas)
         self._mutated(ids_changed=False, sidecars_changed=metadatas is not None, documents_changed=documents is not None)
 
+    @_not_with_mxfp4("upsert")
     def upsert(self, chunks: List[Chunk], embeddings, metadata_fields: Optional[List[str]] = None) -> None:
         """create_index's signature: chunks whose chunk_id exists are updated in place (embedding, text, metadata), the others
         are appended in their given order by create_index."""
@@ -1541,6 +1604,8 @@ class VectorStore:
         import torch
         col = self.collection
         nq = q32.shape[0]
+        if col.index_dtype == 'mxfp4':
+            return self._topk_mxfp4(q32, top_k)
         cap = self._cap(top_k)
         # launches are asynchronous: the devices scan their shards concurrently; then, shard by shard, the one host wait of a
         # refined search (search_batch reads the results right after anyway) and the repeats with a longer escalation list
@@ -1570,6 +1635,22 @@ class VectorStore:
             s, i = _shard.allgather_merge(dist, wb.buf, wb.gathered, nq, top_k, top_k,
                                           nat.merge_topk_wire if top_k <= nat.MAX_K else nat.merge_sorted_wire)
         return s, i, tally
+
+    def _topk_mxfp4(self, q32, top_k: int):
+        """_topk_device of an mxfp4 store: the block-scaled sweep leaves the k' best slab scores, k' the smallest of
+        32 / 64 / 128 that is >= mxfp4_overfetch * top_k (128 when none is); with the fp32 shadow they are re-scored against it and
+        re-ordered, and the best top_k returned with their true fp32 cosines.  No certificate exists: every query counts unproven."""
+        import torch
+        sh = self.collection.shards[0]
+        nq = q32.shape[0]
+        with torch.cuda.device(sh.device):
+            qn = torch.nn.functional.normalize(q32, p=2, dim=1, eps=1e-12).contiguous()
+            kp = next((form for form in nat.MXFP4_KP if form >= self.mxfp4_overfetch * top_k), nat.MXFP4_KP[-1])
+            s, i = nat.mxfp4_topk(qn, sh.slab, sh.scales, sh.n, kp)
+            if sh.shadow is None:
+                return s[:, :top_k].contiguous(), i[:, :top_k].contiguous(), _search.tally(None, nq, top_k, False, False)
+            s, i = self._order(nat.score_rows_f32(qn, sh.shadow, sh.n, 0, i), i, top_k)
+        return s, i, {"queries": nq, "certified": 0, "escalated": 0, "unproven": nq, "mode": "mxfp4"}
 
     def _filter_entry(self, where: Optional[dict], where_document: Optional[dict]):
         """Cache entry of a distinct (where, where_document) pair: the allowed sidecar rows (SlabCollection.rows_matching:
@@ -1625,7 +1706,8 @@ class VectorStore:
         """This store as ONE device shard for rag._engine.RetrievalEngine, or None when its layout needs the general path
         (several devices, SPMD sharding, a non-identity row map)."""
         sh = self._sole_shard()
-        if sh is None or self.sharded or sh.n == 0 or sh.space != nat.SPACE_COSINE:   # the engine's graphs convert queries for cosine
+        # the engine's graphs convert queries for cosine and sweep fp16 / int8 rows: an mxfp4 store takes the general path
+        if sh is None or self.sharded or sh.n == 0 or sh.space != nat.SPACE_COSINE or sh.mx:
             return None
         return sh.view()
 
@@ -1648,6 +1730,7 @@ class VectorStore:
         forgets the index built with the previous one."""
         self._token_encoder = reranker
 
+    @_not_with_mxfp4("the token index (late interaction)")
     def token_index(self, reranker=None) -> _TokenIndex:
         """The late-interaction token index of the collection (_TokenIndex: tok16, n_tokens, offsets, offsets_dev, n_rows) for the
         attached encoder (`reranker`, when given, is attached first).  Built on first use; afterwards only the rows that arrived
@@ -1673,6 +1756,7 @@ class VectorStore:
         Attaching another one forgets the index built with the previous one."""
         self._sparse_encoder = encoder
 
+    @_not_with_mxfp4("the sparse index")
     def sparse_index(self, encoder=None) -> _SparseIndex:
         """The learned-sparse index of the collection (_SparseIndex: tokens, weights, n_terms, offsets, offsets_dev, n_rows) for the
         attached encoder (`encoder`, when given, is attached first).  Built on first use; afterwards only the rows that arrived
@@ -1860,6 +1944,7 @@ class VectorStore:
             out.append((lo, len(lengths)))
         return out
 
+    @_not_with_mxfp4("the token index (BM25)")
     def bm25_rows(self, queries: Sequence[str], top_k: int, k1: float = 1.5, b: float = 0.75):
         """Exact Okapi BM25 top-k of every query over the WHOLE collection, on the device (crs_bm25_topk, csrc/bm25.hip): queries
         [nq] strings -> (scores fp32 [nq, top_k], sidecar rows int64 [nq, top_k]) as numpy, best first, ties by lower row, (-inf, -1)
@@ -1983,6 +2068,11 @@ class VectorStore:
         nothing = np.zeros((nq, 0), dtype=np.float32), np.zeros((nq, 0), dtype=np.int64), None
         if col.count() == 0 or nq == 0:
             return nothing
+        if self.index_dtype == 'mxfp4':
+            if where or where_document:
+                raise NotImplementedError("where / where_document filters are not supported with index_dtype 'mxfp4'")
+            if min(top_k, col.count()) > nat.MAX_K:
+                raise NotImplementedError(f"top_k > {nat.MAX_K} is not supported with index_dtype 'mxfp4'")
         q32 = self._as_f32(query_embeddings).to(col.device).contiguous()
         if q32.shape[1] != col.dim:
             raise ValueError(f"Query dimension {q32.shape[1]} doesn't match the index dimension {col.dim}")
@@ -2061,6 +2151,12 @@ class VectorStore:
         try:
             col = self.collection
             elem = 1 if col.slab_type == nat.SLAB_I8 else 2
+            if col.index_dtype == 'mxfp4':
+                row_bytes = nat.mxfp4_row_bytes(col.dim) if col.dim else 0
+                return {"name": self.collection_name, "count": col.count(), "metadata": col.metadata, "index_dtype": 'mxfp4',
+                        "dimension": col.dim, "rows_on_this_gpu": col.shards[0].n, "rows_per_device": [s.n for s in col.shards],
+                        "bytes_per_row": row_bytes, "slab_bytes": int(col.shards[0].n * row_bytes),
+                        "row_err_max": col.shards[0].row_err_max()}
             return {"name": self.collection_name, "count": col.count(), "metadata": col.metadata,
                     "index_dtype": col.index_dtype, "dimension": col.dim, "rows_on_this_gpu": col.shards[0].n,
                     "rows_per_device": [s.n for s in col.shards],

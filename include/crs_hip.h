@@ -558,6 +558,39 @@ int crs_time_cosine_topk(const void* q16_dev, int nq, int dim, int slab_type, co
                          size_t workspace_bytes, float* out_scores_dev, int64_t* out_ids_dev,
                          void* stream, int iters, float* ms_total, float* ms_scan);
 
+/* ---- MXFP4 index (additive to ABI 3; csrc/row_build_mxfp4.hip, csrc/scan_mxfp4.hip, csrc/mxfp4.h) -- no reference
+ * call site ----
+ * A slab of OCP microscaling rows: pdim = dim rounded up to 128 e2m1 elements (4 bits) plus one e8m0 scale per 32 elements, stored
+ * in tiles of 16 rows in the lane order of gfx950's block-scaled MFMA (csrc/mxfp4.h spells out the byte of every element).  The
+ * slab is two buffers sized by crs_mxfp4_slab_bytes(rows, dim): whole tiles, so allocate for the capacity and zero it once.
+ * crs_mxfp4_row_bytes(dim) = bytes per row of both buffers together (416 at 768: 384 of elements, 32 of scales; against 768 int8 and 1536 fp16).
+ *
+ * crs_slab_append_mxfp4_f32 writes rows [row0, row0 + n) from emb_dev fp32 [n, dim] (any row0, any n: a tile may be filled by
+ * several calls); crs_slab_write_rows_mxfp4_f32 writes row rows_dev[r] (skipped when outside [0, n_rows)).  Both normalise the
+ * row as crs_slab_append_f32 does (the fp32 shadow row, shadow_f32_dev [*, dim] or NULL, carries the same bits), quantise each
+ * block by the MX rule -- scale 2^(floor(log2 max|v|) - 2), an all-zero block the smallest scale; elements to the nearest of
+ * +-{0, .5, 1, 1.5, 2, 3, 4, 6}, ties to even, saturating -- and write row_err_dev[row] = |v - dequantised row|_2 (fp32, or NULL).
+ *
+ * crs_mxfp4_topk: the kp best slab scores of each of nq <= 64 queries, kp = 32, 64 or 128, sorted (score desc, id asc), ids =
+ * row + id_base, empty slots (-inf, -1).  q32_dev fp32 [nq, dim] is quantised inside the call to MX e4m3 (scale
+ * 2^(floor(log2 max|q|) - 8) per 32 elements) as it is given: pass unit queries for cosine scores.  A score is the fp32
+ * accumulation of the products of the DEQUANTISED operands: a first pass, to be re-ranked (crs_rescore_f32); no certificate.
+ * id_base >= 0 and id_base + n_rows fits int64 (a negative id is an empty slot to the merge).
+ * Workspace: crs_mxfp4_workspace_bytes(nq, dim, kp, n_rows); like crs_scan_workspace_bytes it plans for the CU count of the device
+ * that is current at the call: size the workspace on the device the search runs on.  1 <= n_rows < 2^31 - 64.  crs_mxfp4_plan_describe writes the plan's
+ * line for `cus` compute units (0: the current device's), without a device when cus > 0. */
+int crs_mxfp4_row_bytes(int dim);
+int crs_mxfp4_slab_bytes(int64_t rows, int dim, size_t* data_bytes, size_t* scale_bytes);
+int crs_slab_append_mxfp4_f32(const float* emb_dev, int64_t n, int dim, void* data_dev, void* scales_dev, float* shadow_f32_dev,
+                              int64_t row0, float* row_err_dev, void* stream);
+int crs_slab_write_rows_mxfp4_f32(const float* emb_dev, const int64_t* rows_dev, int64_t m, int dim, void* data_dev, void* scales_dev,
+                                  float* shadow_f32_dev, int64_t n_rows, float* row_err_dev, void* stream);
+int crs_mxfp4_workspace_bytes(int nq, int dim, int kp, int64_t n_rows, size_t* bytes);
+int crs_mxfp4_plan_describe(int nq, int dim, int kp, int64_t n_rows, int cus, char* buf, size_t cap);
+int crs_mxfp4_topk(const float* q32_dev, int nq, int dim, const void* data_dev, const void* scales_dev, int64_t n_rows, int kp,
+                   int64_t id_base, void* workspace_dev, size_t workspace_bytes, float* out_scores_dev, int64_t* out_ids_dev,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif
