@@ -24,13 +24,13 @@
 #include "mxfp4.h"
 #include "scan.h"
 #include "scan_common.h"
+#include "wave_sort.h"
 
 namespace crs {
 int device_cus();   // capi.hip
 namespace {
 
 typedef int v8i __attribute__((ext_vector_type(8)));
-typedef unsigned long long u64;
 
 // ---------------------------------------------------------------- query prologue: fp32 -> MX e4m3 in B-operand lane order
 // One wave per query slot of the 16-query groups; slots past nq are zeroed (their columns of D are never read).
@@ -91,40 +91,6 @@ struct MxScanArgs {
   int n_rows, n_tiles, nq, nwg;
 };
 
-__device__ __forceinline__ u64 umax64(u64 a, u64 b) { return a > b ? a : b; }
-__device__ __forceinline__ u64 umin64(u64 a, u64 b) { return a < b ? a : b; }
-
-// element e = lane + 64 u of 64 E keys -> descending
-template <int E>
-__device__ __forceinline__ void wave_sort_keys(u64 (&key)[E], int lane) {
-#pragma unroll
-  for (int k = 2; k <= 64 * E; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      if (j >= 64) {
-#pragma unroll
-        for (int u = 0; u < E; ++u) {
-          const int u2 = u ^ (j >> 6);
-          if (u2 > u) {
-            const bool desc = ((64 * u) & k) == 0;      // lane < 64 <= j < k: the lane bits do not reach k
-            const u64 hi = umax64(key[u], key[u2]), lo = umin64(key[u], key[u2]);
-            key[u] = desc ? hi : lo;
-            key[u2] = desc ? lo : hi;
-          }
-        }
-      } else {
-#pragma unroll
-        for (int u = 0; u < E; ++u) {
-          const int e = lane + 64 * u;
-          const u64 other = __shfl_xor(key[u], j);
-          const bool keep_max = ((e & j) == 0) == ((e & k) == 0);
-          key[u] = keep_max ? umax64(key[u], other) : umin64(key[u], other);
-        }
-      }
-    }
-  }
-}
-
 // Sort query q's buffer, keep its kp best; FINAL writes them out instead (empty slots (-inf, -1)).
 template <int E, bool FINAL>
 __device__ __forceinline__ void compact_query(u64* buf, int q, int lane, int& cnt, float& tau, float* out_s, int64_t* out_i,
@@ -155,11 +121,6 @@ __device__ __forceinline__ void compact_query(u64* buf, int q, int lane, int& cn
     if (n >= KP) tau = float_of_ord((unsigned)(kth >> 32));
     cnt = n < KP ? n : KP;
   }
-}
-
-__device__ __forceinline__ void lds_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
 }
 
 template <int KS>

@@ -26,6 +26,7 @@
 //   crs::pairs_above / crs::pairs_verify   near-duplicate detection: thresholded self-join of the slab, fp32 check (new vs the reference)
 //   crs::mlm_sparse_pool / crs::sparse_compact / crs::sparse_topk   learned sparse retrieval (SPLADE): MLM head with max-pool epilogue, compaction, impact scan (new vs the reference)
 //   crs::token_project / crs::maxsim   late interaction (ColBERT): per-token projection and MaxSim scoring of candidate lists (new vs the reference)
+//   crs::ivf_topk          top-k of the rows of per-query inverted lists of an fp16 slab: grouping + gathered MFMA probe (new vs the reference)
 //   crs::rerank_lexical    replaces the scoring, threshold and _rerank loops of retrieve_batch  (reference rag/retrieval.py:75-77, 196-217)
 // Tensors are torch-owned; every op launches on the CURRENT HIP stream of the tensors' device, so the ops
 // compose with torch streams and hipGraph capture.  Errors of the C ABI surface as RuntimeError (TORCH_CHECK)
@@ -923,6 +924,33 @@ void mxfp4_topk(const Tensor& q32, const Tensor& data, const Tensor& scales, int
                     cur_stream(q32)), "crs::mxfp4_topk");
 }
 
+// q16 fp16 [nq <= 256, pdim]; slab fp16 [>= n_rows, pdim]; list_offsets int32 [nlist + 1]; list_rows int32; probes int32 [nq, nprobe];
+// workspace uint8; out_scores fp32 / out_rows int64 [nq, k]
+void ivf_topk(const Tensor& q16, const Tensor& slab, int64_t n_rows, int64_t dim, const Tensor& list_offsets, const Tensor& list_rows,
+              const Tensor& probes, int64_t k, int64_t kp, Tensor workspace, Tensor out_scores, Tensor out_rows) {
+  want(q16, at::kHalf, "q16");
+  want(slab, at::kHalf, "slab");
+  want(list_offsets, at::kInt, "list_offsets");
+  want(list_rows, at::kInt, "list_rows");
+  want(probes, at::kInt, "probes");
+  want(workspace, at::kByte, "workspace");
+  want(out_scores, at::kFloat, "out_scores");
+  want(out_rows, at::kLong, "out_rows");
+  same_device(q16, {&slab, &list_offsets, &list_rows, &probes, &workspace, &out_scores, &out_rows}, "crs::ivf_topk");
+  TORCH_CHECK(dim >= 1 && dim <= 1024, "dim must be in 1..1024");
+  const int64_t pdim = crs_padded_dim((int)dim);
+  TORCH_CHECK(q16.dim() == 2 && q16.size(1) == pdim, "q16 must be fp16 [nq, crs_padded_dim(dim)]");
+  TORCH_CHECK(slab.dim() == 2 && slab.size(1) == pdim && n_rows >= 1 && n_rows <= slab.size(0), "slab must be fp16 [>= n_rows, crs_padded_dim(dim)]");
+  TORCH_CHECK(probes.dim() == 2 && probes.size(0) == q16.size(0), "probes must be int32 [nq, nprobe]");
+  TORCH_CHECK(list_offsets.dim() == 1 && list_offsets.numel() >= 2, "list_offsets must be int32 [nlist + 1]");
+  TORCH_CHECK(out_scores.numel() == q16.size(0) * k && out_rows.numel() == q16.size(0) * k, "outputs must hold [nq, k]");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(q16.device());
+  ok(crs_ivf_topk(q16.data_ptr(), (int)q16.size(0), (int)dim, slab.data_ptr(), n_rows, list_offsets.data_ptr<int32_t>(),
+                  list_offsets.numel() - 1, list_rows.numel() ? list_rows.data_ptr<int32_t>() : nullptr, list_rows.numel(),
+                  probes.data_ptr<int32_t>(), (int)probes.size(1), (int)k, (int)kp, workspace.data_ptr(), (size_t)workspace.numel(),
+                  out_scores.data_ptr<float>(), out_rows.data_ptr<int64_t>(), cur_stream(q16)), "crs::ivf_topk");
+}
+
 // dense_rows int64 [nq, m_dense], lex_rows int64 [nq, m_lex]; rows int64 / fused fp64 / dense_pos, lex_pos int32 [nq, k_out]; count int32 [nq]
 void fuse_rrf(const Tensor& dense_rows, const Tensor& lex_rows, double c, double w_dense, double w_lex, Tensor rows, Tensor fused,
               Tensor dense_pos, Tensor lex_pos, Tensor count) {
@@ -1264,6 +1292,7 @@ TORCH_LIBRARY(crs, m) {
         "float ln_eps, Tensor decoder_w16, Tensor decoder_bias, int max_pos, Tensor(a!) workspace, Tensor(b!) out) -> ()");
   m.def("slab_write_mxfp4(Tensor emb, Tensor(a!) data, Tensor(b!) scales, Tensor? rows, int row0, int n_rows, Tensor(c!)? shadow, Tensor(d!)? row_err) -> ()");
   m.def("mxfp4_topk(Tensor q32, Tensor data, Tensor scales, int n_rows, int kp, int id_base, Tensor(a!) workspace, Tensor(b!) out_scores, Tensor(c!) out_ids) -> ()");
+  m.def("ivf_topk(Tensor q16, Tensor slab, int n_rows, int dim, Tensor list_offsets, Tensor list_rows, Tensor probes, int k, int kp, Tensor(a!) workspace, Tensor(b!) out_scores, Tensor(c!) out_rows) -> ()");
   m.def("sparse_compact(Tensor weights, int vocab, Tensor? skip_ids, Tensor(a!) ids, Tensor(b!) out_weights, Tensor(c!) counts) -> ()");
   m.def("sparse_topk(Tensor doc_offsets, Tensor doc_tokens, Tensor doc_weights, int n_rows, Tensor q_offsets, Tensor q_tokens, "
         "Tensor q_weights, int k, Tensor(a!) workspace, Tensor(b!) out_scores, Tensor(c!) out_rows) -> ()");
@@ -1324,6 +1353,7 @@ TORCH_LIBRARY_IMPL(crs, CUDA, m) {   // the HIP backend of torch-ROCm dispatches
   m.impl("mlm_sparse_pool", &mlm_sparse_pool);
   m.impl("slab_write_mxfp4", &slab_write_mxfp4);
   m.impl("mxfp4_topk", &mxfp4_topk);
+  m.impl("ivf_topk", &ivf_topk);
   m.impl("sparse_compact", &sparse_compact);
   m.impl("sparse_topk", &sparse_topk);
   m.impl("wordpiece_encode", &wordpiece_encode);

@@ -119,6 +119,10 @@ _SIGNATURES = {
     "crs_mxfp4_plan_describe": (c_int, [c_int, c_int, c_int, c_int64, c_int, ctypes.c_char_p, c_size_t]),
     "crs_mxfp4_topk": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p, c_size_t, c_void_p, c_void_p,
                                c_void_p]),
+    "crs_ivf_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
+    "crs_ivf_plan_describe": (c_int, [c_int, c_int, c_int, c_int, ctypes.c_char_p, c_size_t]),
+    "crs_ivf_topk": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int, c_int,
+                             c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     "crs_exact_workspace_bytes": (c_size_t, [c_int, c_int]),
     "crs_exact_row_error_bound": (c_float, [c_int, c_int]),
     "crs_refine_f32_cert": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
@@ -852,6 +856,43 @@ def mxfp4_topk(q32, data, scales, n_rows: int, kp: int, id_base: int = 0, worksp
         with _translate():
             ops().mxfp4_topk(q32[q0:q0 + m].contiguous(), data, scales, int(n_rows), int(kp), int(id_base), workspace, out_s[q0:q0 + m], out_i[q0:q0 + m])
     return out_s, out_i
+
+
+# ---- IVF probe (csrc/ivf_probe.hip, csrc/ivf.h) ----------------------------------------------------------------------
+IVF_KP = (32, 64)          # list lengths crs_ivf_topk keeps per (query, probed list)
+IVF_MAX_QUERIES = 256      # queries of one crs_ivf_topk call
+IVF_MAX_PROBE = 64         # lists per query
+IVF_MAX_LISTS = 1 << 18
+
+
+def ivf_workspace_bytes(nq: int, dim: int, nprobe: int, kp: int) -> int:
+    b = c_size_t(0)
+    check(load().crs_ivf_workspace_bytes(int(nq), int(dim), int(nprobe), int(kp), ctypes.byref(b)))
+    return int(b.value)
+
+
+def ivf_plan_describe(nq: int, dim: int, nprobe: int, kp: int) -> str:
+    """The plan line of an IVF probe (no device needed)."""
+    buf = ctypes.create_string_buffer(256)
+    check(load().crs_ivf_plan_describe(int(nq), int(dim), int(nprobe), int(kp), buf, 256))
+    return buf.value.decode()
+
+
+def ivf_topk(q16, slab, n_rows: int, dim: int, list_offsets, list_rows, probes, k: int, kp: int, workspace=None):
+    """The k best slab scores of each query among the rows of the lists it probes: q16 cuda fp16 [nq <= 256, pdim]
+    (queries_to_f16), slab cuda fp16 [>= n_rows, pdim], list_offsets int32 [nlist + 1], list_rows int32 (slab rows grouped by
+    list, ascending within a list), probes int32 [nq, nprobe <= 64] (-1 = none, a list at most once per query), kp 32 or 64 kept
+    per (query, list), k <= kp.  Returns (scores fp32 [nq, k], rows int64 [nq, k]) sorted score desc / row asc, (-inf, -1) past
+    the union of the probed lists."""
+    import torch
+    nq = q16.shape[0]
+    out_s = torch.empty((nq, k), dtype=torch.float32, device=q16.device)
+    out_r = torch.empty((nq, k), dtype=torch.int64, device=q16.device)
+    if workspace is None:
+        workspace = torch.empty(ivf_workspace_bytes(nq, dim, probes.shape[1], kp), dtype=torch.uint8, device=q16.device)
+    with _translate():
+        ops().ivf_topk(q16, slab, int(n_rows), int(dim), list_offsets, list_rows, probes, int(k), int(kp), workspace, out_s, out_r)
+    return out_s, out_r
 
 
 def exact_workspace_bytes(nq: int, cap: int = EXACT_CAP) -> int:

@@ -107,6 +107,13 @@ New, additive surface (all keys absent from the reference config.json default so
                               first use, extended by appends, DROPPED WHOLE by a delete, a document update or an upsert, NOT persisted,
                               ONE device only; ``max_index_bytes`` is compared with rows x sparse_doc_terms x 8 before any encoding
                               and with the exact size after compaction
+  ``ivf``                     a dict {nlist, nprobe, train_rows, iters, seed, min_rows} (all optional) = an inverted-file index beside
+                              the exact scan (rag/_ivf.py): spherical k-means lists over the fp16 slab, built on first use
+                              once count >= min_rows (32 nlist), extended by appends, dropped by delete / update / upsert, not
+                              persisted.  A search probes the ``nprobe`` (attribute, 1..64) nearest lists with crs::ivf_topk and
+                              re-ranks against the fp32 shadow; it is approximate (``last_exactness``: mode 'ivf', all unproven).
+                              Filters, top_k > 64 and count < min_rows take the exact path.  index_dtype 'fp16', cosine, one device
+                              (the rest raises NotImplementedError); ``engine_view()`` is None while the index is active
 ``where`` / ``where_document`` filters work on every layout (the sidecars are replicated; each shard scans the
 allowed rows it owns).  ``top_k`` is unlimited as in the reference: up to 1024 a refined shard is over-fetched by
 partition (64 candidates from each of up to 64 row chunks, crs::cosine_topk_large_cert) and certified like top_k <= 64;
@@ -126,7 +133,7 @@ import numpy as np
 
 from rag.chunking import Chunk
 from rag import _native as nat
-from rag import _search, _shard
+from rag import _ivf, _search, _shard
 
 logger = logging.getLogger(__name__)
 
@@ -876,6 +883,14 @@ class VectorStore:
                 if on:
                     raise NotImplementedError(f"{option} is not supported with index_dtype 'mxfp4' (one device, cosine space, in "
                                               "memory: DESIGN 3.19)")
+        # inverted-file index (module docstring): None = every search sweeps the slab, as before
+        self._ivf_cfg = None
+        if config.get('ivf') is not None:
+            for option, on in ((f"index_dtype {self.index_dtype!r}", self.index_dtype != 'fp16'), (f"space {self.space!r}", self.space != 'cosine'),
+                               ("sharded=True", self.sharded), ("num_gpus > 1", self.num_gpus > 1), ("devices", bool(self._devices_cfg))):
+                if on:
+                    raise NotImplementedError(f"{option} is not supported with ivf (index_dtype 'fp16', cosine space, one device: DESIGN 3.20)")
+            self._ivf_cfg = _ivf.parse_config(config['ivf'])
         if self.sharded and (self.num_gpus > 1 or self._devices_cfg):
             raise ValueError("'sharded' (one process per GPU) and 'num_gpus'/'devices' (one process, N devices) are exclusive")
         if self.sharded and self.persist_directory:
@@ -1249,6 +1264,7 @@ class VectorStore:
         error) to rebuild."""
         self._filters = {}
         self._wire = {}
+        self.collection.__dict__.pop("_ivf", None)      # the lists name rows by number and by what they held: retrained lazily
         if sidecars_changed or documents_changed or ids_changed:
             self.collection._drop_derived(ids_changed, metadata_changed=sidecars_changed, documents_changed=documents_changed)
         for sh in self.collection.shards:
@@ -1606,6 +1622,13 @@ class VectorStore:
         nq = q32.shape[0]
         if col.index_dtype == 'mxfp4':
             return self._topk_mxfp4(q32, top_k)
+        if filt is None and top_k <= nat.MAX_K:
+            index = self.ivf_index()
+            if index is not None:
+                sh = col.shards[0]
+                with torch.cuda.device(sh.device):
+                    s, i = index.topk(q32, sh, top_k, self.nprobe, nat.overfetch(nq, top_k, self.refine_overfetch, sh.n))
+                return s, i, {"queries": nq, "certified": 0, "escalated": 0, "unproven": nq, "mode": "ivf"}
         cap = self._cap(top_k)
         # launches are asynchronous: the devices scan their shards concurrently; then, shard by shard, the one host wait of a
         # refined search (search_batch reads the results right after anyway) and the repeats with a longer escalation list
@@ -1635,6 +1658,38 @@ class VectorStore:
             s, i = _shard.allgather_merge(dist, wb.buf, wb.gathered, nq, top_k, top_k,
                                           nat.merge_topk_wire if top_k <= nat.MAX_K else nat.merge_sorted_wire)
         return s, i, tally
+
+    @property
+    def nprobe(self) -> int:
+        """Lists an IVF search visits per query (1..64; config ivf.nprobe).  Settable; meaningless without ``ivf``."""
+        return self._ivf_cfg["nprobe"] if self._ivf_cfg else 0
+
+    @nprobe.setter
+    def nprobe(self, value: int) -> None:
+        if self._ivf_cfg is None:
+            raise ValueError("nprobe needs the ivf option")
+        self._ivf_cfg["nprobe"] = _ivf.check_nprobe(value)
+
+    def _ivf_active(self) -> bool:
+        col = self.collection
+        return self._ivf_cfg is not None and col is not None and col.count() >= max(1, _ivf.min_rows(self._ivf_cfg, col.count()))
+
+    def ivf_index(self):
+        """The inverted-file index of the collection (_ivf.IvfIndex), or None without the ``ivf`` option or below its min_rows.
+        Built on first use (k-means over a sample, then every row assigned), extended by the rows that arrived since (the
+        centroids stay), dropped by delete / update / upsert (_mutated) and retrained by the next call.  Not persisted."""
+        import torch
+        if not self._ivf_active():
+            return None
+        col = self.collection
+        sh = col.shards[0]
+        index = col.__dict__.get("_ivf")
+        with torch.cuda.device(sh.device):
+            if index is None:
+                index = col.__dict__["_ivf"] = _ivf.IvfIndex(self._ivf_cfg, sh)
+            elif index.n_rows < sh.n:
+                index.extend(sh)
+        return index
 
     def _topk_mxfp4(self, q32, top_k: int):
         """_topk_device of an mxfp4 store: the block-scaled sweep leaves the k' best slab scores, k' the smallest of
@@ -1707,7 +1762,7 @@ class VectorStore:
         (several devices, SPMD sharding, a non-identity row map)."""
         sh = self._sole_shard()
         # the engine's graphs convert queries for cosine and sweep fp16 / int8 rows: an mxfp4 store takes the general path
-        if sh is None or self.sharded or sh.n == 0 or sh.space != nat.SPACE_COSINE or sh.mx:
+        if sh is None or self.sharded or sh.n == 0 or sh.space != nat.SPACE_COSINE or sh.mx or self._ivf_active():
             return None
         return sh.view()
 
@@ -2157,10 +2212,15 @@ class VectorStore:
                         "dimension": col.dim, "rows_on_this_gpu": col.shards[0].n, "rows_per_device": [s.n for s in col.shards],
                         "bytes_per_row": row_bytes, "slab_bytes": int(col.shards[0].n * row_bytes),
                         "row_err_max": col.shards[0].row_err_max()}
-            return {"name": self.collection_name, "count": col.count(), "metadata": col.metadata,
-                    "index_dtype": col.index_dtype, "dimension": col.dim, "rows_on_this_gpu": col.shards[0].n,
-                    "rows_per_device": [s.n for s in col.shards],
-                    "slab_bytes": int(sum(s.n for s in col.shards) * (col.pdim or 0) * elem)}
+            stats = {"name": self.collection_name, "count": col.count(), "metadata": col.metadata,
+                     "index_dtype": col.index_dtype, "dimension": col.dim, "rows_on_this_gpu": col.shards[0].n,
+                     "rows_per_device": [s.n for s in col.shards],
+                     "slab_bytes": int(sum(s.n for s in col.shards) * (col.pdim or 0) * elem)}
+            if self._ivf_cfg is not None:
+                index = col.__dict__.get("_ivf")
+                stats["ivf"] = {"nlist": index.nlist if index else _ivf.resolve_nlist(self._ivf_cfg, col.count()), "nprobe": self.nprobe,
+                                "built": index is not None, "largest_list": int(index.sizes_host.max()) if index else 0}
+            return stats
         except Exception as e:
             logger.error(f"Failed to get stats: {e}")
             return {"status": "error", "error": str(e)}

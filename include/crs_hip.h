@@ -591,6 +591,25 @@ int crs_mxfp4_topk(const float* q32_dev, int nq, int dim, const void* data_dev, 
                    int64_t id_base, void* workspace_dev, size_t workspace_bytes, float* out_scores_dev, int64_t* out_ids_dev,
                    void* stream);
 
+/* ---- IVF probe (additive to ABI 3; csrc/ivf_probe.hip, csrc/ivf.h) -- no reference call site ----
+ * An inverted-file index over an fp16 slab is row numbers only: list_offsets_dev int32 [nlist + 1] (monotone, 0 first) and
+ * list_rows_dev int32 [n_list_rows], the slab rows of list l at [list_offsets[l], list_offsets[l + 1]), ascending within a list.
+ * The slab is neither permuted nor copied.
+ *
+ * crs_ivf_topk: for each of nq <= 256 queries (q16_dev fp16 [nq, crs_padded_dim(dim)], as crs_queries_to_f16 writes them) the k
+ * best slab scores among the rows of the lists probes_dev int32 [nq, nprobe] names (1 <= nprobe <= 64; -1 or a number outside
+ * [0, nlist) = no list; a list at most once per query), sorted (score desc, row asc), empty slots (-inf, -1).  Every (query,
+ * list) contributes its kp best (kp = 32 or 64, 1 <= k <= kp), so the answer is the exact top k of the union under the slab's
+ * scores: fp16 products accumulated in fp32 on the matrix cores.  Which rows the lists hold decides what is found: no
+ * certificate.  A list of any length from 0 to n_rows works; a row number outside [0, n_rows) is skipped.  1 <= nlist <= 2^18,
+ * 1 <= n_rows < 2^31.  Workspace: crs_ivf_workspace_bytes(nq, dim, nprobe, kp).  crs_ivf_plan_describe writes the plan's line;
+ * neither needs a device. */
+int crs_ivf_workspace_bytes(int nq, int dim, int nprobe, int kp, size_t* bytes);
+int crs_ivf_plan_describe(int nq, int dim, int nprobe, int kp, char* buf, size_t cap);
+int crs_ivf_topk(const void* q16_dev, int nq, int dim, const void* slab_dev, int64_t n_rows, const int32_t* list_offsets_dev,
+                 int64_t nlist, const int32_t* list_rows_dev, int64_t n_list_rows, const int32_t* probes_dev, int nprobe, int k, int kp,
+                 void* workspace_dev, size_t workspace_bytes, float* out_scores_dev, int64_t* out_rows_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
