@@ -74,6 +74,21 @@ int pool_launch(const float* x32, const int* lens, int batch, int seq, int hidde
 int add_layernorm_launch(const float* y, int nsplit, const float* bias, const float* residual, const float* g, const float* b,
                          float eps, int tokens, int hidden, float* r32, _Float16* x16, float* n32, hipStream_t stream);
 
+// ---- causal RMS pre-norm models (Qwen3-Embedding: CRS_ENC_CAUSAL | CRS_ENC_RMSNORM) ----
+// enc_attn_causal.hip: ctx[T, Hq hd] = causal grouped-query attention of qkv [T, (Hq + 2 Hkv) hd] (Q | K | V blocks); p: plan_attention_causal's
+// (form Causal; hd 64 / 128, group 1 / 2, -1 otherwise).  2 x (K + V^T) images of dynamic LDS.
+int attention_causal_launch(const AttnPlan& p, const _Float16* qkv, const int* lens, _Float16* ctx, int seq, int kv_heads,
+                            hipStream_t stream);
+// enc_rope.hip: RMSNorm over head_dim (gains g_q / g_k, fp32 [hd]) + rotation of the Q and K blocks of that qkv, in place; d: plan_qk_norm
+int qk_norm_rope_launch(const Dims& d, int hd, _Float16* qkv, const float* table, const float* g_q, const float* g_k, float eps,
+                        int tokens, int seq, int q_heads, int kv_heads, hipStream_t stream);
+// enc_addln.hip: add_layernorm_launch's RMS form: r = sum of slabs + residual -> r32, x16 = fp16(RMSNorm(r) g), n32 (may be null)
+int add_rmsnorm_launch(const float* y, int nsplit, const float* residual, const float* g, float eps, int tokens, int hidden, float* r32,
+                       _Float16* x16, float* n32, hipStream_t stream);
+// enc_addln.hip: r32 = word[id] (clamped), x16 = fp16(RMSNorm(r32) g)
+int embed_rmsnorm_launch(const int* ids, const float* word, const float* g, float eps, int tokens, int hidden, int vocab, float* r32,
+                         _Float16* x16, hipStream_t stream);
+
 // enc_pair.hip
 // scores[b] = w_cls . tanh(w_pool hidden32[b, 0, :] + b_pool) + b_cls[0] (activation 1: then 1 / (1 + exp(-score))), all fp32;
 // pooled_out (may be null): the tanh vectors [batch, hidden].  -1: hidden not a multiple of 64 up to 1024

@@ -49,6 +49,7 @@ crs::EncPlan plan_for(const crs_encoder_desc* d, int batch, int seq, int rel_bia
 
 int check_desc(const crs_encoder_desc* d) {
   if (!d) return crs::set_error(CRS_EINVAL, "null descriptor");
+  if (d->flags & (CRS_ENC_RMSNORM | CRS_ENC_CAUSAL)) return crs::set_error(CRS_EINVAL, "a CRS_ENC_RMSNORM / CRS_ENC_CAUSAL descriptor needs the _causal entry points (crs_encoder_forward_causal)");
   if (d->hidden <= 0 || d->hidden > 1024 || d->hidden % 64) return crs::set_error(CRS_EINVAL, "hidden must be a multiple of 64, <= 1024");
   if (d->heads <= 0 || d->hidden % d->heads) return crs::set_error(CRS_EINVAL, "hidden must divide by heads");
   const int hd = d->hidden / d->heads;
@@ -393,6 +394,167 @@ int crs_encoder_prenorm_plan_describe(const crs_encoder_desc* d, int batch, int 
   const int cus = crs::device_cus();
   if (cus <= 0) return crs::set_error(CRS_EHIP, "plan describe: no device");
   return crs::enc_plan_describe(plan_for(d, batch, seq, 0, 0, cus, window), buf, cap);
+}
+
+// ---- causal RMS pre-norm models (Qwen3-Embedding): their own descriptor check, plan and layer loop ----
+static const int kCausalFlags = CRS_ENC_ROTARY | CRS_ENC_GATED_SILU | CRS_ENC_PRENORM | CRS_ENC_RMSNORM | CRS_ENC_CAUSAL;
+
+static const char* causal_group_refusal(int heads, int kv_heads, int hd) {
+  if (heads < 1 || kv_heads < 1 || heads % kv_heads) return "causal attention: heads must be a multiple of kv_heads (both >= 1)";
+  if (!crs::forms::attn_causal_supported(hd, heads / kv_heads)) return "causal attention: head_dim must be 64 or 128 and heads / kv_heads 1 or 2";
+  return nullptr;
+}
+
+static int check_desc_causal(const crs_encoder_desc* d, const crs_encoder_causal* c) {
+  if (!d) return crs::set_error(CRS_EINVAL, "null descriptor");
+  if (!c) return crs::set_error(CRS_EINVAL, "the _causal entry points need a crs_encoder_causal");
+  if ((d->flags & kCausalFlags) != kCausalFlags || (d->flags & CRS_ENC_GATED_GELU))
+    return crs::set_error(CRS_EINVAL, "the _causal entry points need CRS_ENC_CAUSAL, CRS_ENC_RMSNORM, CRS_ENC_PRENORM, CRS_ENC_ROTARY and CRS_ENC_GATED_SILU (and no CRS_ENC_GATED_GELU)");
+  if (d->hidden < 128 || d->hidden > 1024 || d->hidden % 64) return crs::set_error(CRS_EINVAL, "CRS_ENC_CAUSAL: hidden must be a multiple of 64 in [128, 1024]");
+  if (const char* why = causal_group_refusal(d->heads, c->kv_heads, c->head_dim)) return crs::set_error(CRS_EINVAL, why);
+  if (d->ffn <= 0 || d->ffn % 64) return crs::set_error(CRS_EINVAL, "ffn must be a multiple of 64");
+  if (d->layers <= 0 || d->vocab_size <= 0 || d->max_pos <= 0) return crs::set_error(CRS_EINVAL, "bad layers/vocab/max_pos");
+  if (d->pooling != CRS_POOL_MEAN && d->pooling != CRS_POOL_CLS && d->pooling != CRS_POOL_LAST) return crs::set_error(CRS_EINVAL, "bad pooling mode");
+  return CRS_OK;
+}
+
+static crs::CausalPlan causal_plan_for(const crs_encoder_desc* d, const crs_encoder_causal* c, int batch, int seq, int cus) {
+  return crs::make_causal_plan(d->hidden, d->heads, c->kv_heads, c->head_dim, d->ffn, d->flags, batch, seq, cus, knobs());
+}
+
+static int encoder_forward_causal(const crs_encoder_desc* d, const crs_encoder_weights* w, const int32_t* ids_dev, const int32_t* lens_dev,
+                                  int batch, int seq, void* workspace_dev, size_t workspace_bytes, float* out_dev, int normalize,
+                                  float* hidden_out_dev, _Float16* q16_out_dev, int q16_row_elems, void* stream,
+                                  const crs_encoder_causal* c) {
+  const int rc = check_desc_causal(d, c);
+  if (rc) return rc;
+  if (!w || !w->layers || !w->word_emb || !ids_dev || !lens_dev || !workspace_dev || !out_dev) return crs::set_error(CRS_EINVAL, "null pointer");
+  if (!c->rope_dev || !c->g_q || !c->g_k || !c->final_g) return crs::set_error(CRS_EINVAL, "crs_encoder_causal: NULL rope table, gain array or final gain");
+  if (batch <= 0 || batch > 65535 || seq <= 0 || seq > d->max_pos) return crs::set_error(CRS_EINVAL, "bad batch/seq (seq <= max_pos, batch <= 65535)");
+  if (c->positions < seq || ((uintptr_t)c->rope_dev & 15)) {
+    char m[160];
+    snprintf(m, sizeof m, "rope table: positions %d must be >= seq %d, and the table 16-byte aligned", c->positions, seq);
+    return crs::set_error(CRS_EINVAL, m);
+  }
+  for (int li = 0; li < d->layers; ++li) {
+    const crs_encoder_layer& L = w->layers[li];
+    if (!c->g_q[li] || !c->g_k[li]) return crs::set_error(CRS_EINVAL, "crs_encoder_causal: NULL g_q / g_k of a layer");
+    if (!L.w_qkv || !L.w_o || !L.w_up || !L.w_down || !L.ln1_g || !L.ln2_g) return crs::set_error(CRS_EINVAL, "CRS_ENC_CAUSAL: NULL weight or gain (ln1_g and ln2_g are needed on every layer)");
+    if (L.b_qkv || L.b_o || L.b_up || L.b_down || L.ln1_b || L.ln2_b) return crs::set_error(CRS_EINVAL, "CRS_ENC_CAUSAL: every bias must be NULL");
+  }
+  const int cus = crs::device_cus();
+  if (cus <= 0) return crs::set_error(CRS_EHIP, "encoder forward: no device");
+  const crs::CausalPlan p = causal_plan_for(d, c, batch, seq, cus);
+  if (workspace_bytes < p.total) return crs::set_error(CRS_ENOSPC, "encoder workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = reinterpret_cast<char*>(workspace_dev);
+  float* x32 = reinterpret_cast<float*>(ws + p.x32);
+  float* y32 = reinterpret_cast<float*>(ws + p.y32);
+  _Float16* x16 = reinterpret_cast<_Float16*>(ws + p.x16);
+  _Float16* ctx = reinterpret_cast<_Float16*>(ws + p.ctx);
+  _Float16* qkv = reinterpret_cast<_Float16*>(ws + p.qkv_off);
+  _Float16* ffn = reinterpret_cast<_Float16*>(ws + p.ffn_off);
+  const int T = p.tokens, H = d->hidden;
+  // a block's GEMM leaves its product in y32 (slabs, or r folded in) and add_rmsnorm writes r back and the NEXT block's input to x16
+  auto add_rms = [&](const crs::ProjLnPlan& s, const _Float16* a, const void* wt, const float* g, float* n32) -> int {
+    const bool folded = s.gemm.mode == 2;
+    const int e = crs::gemm_launch(s.gemm, a, (const _Float16*)wt, nullptr, folded ? x32 : nullptr, y32, st);
+    if (e) return e;
+    return crs::add_rmsnorm_launch(y32, s.gemm.slabs, folded ? nullptr : x32, g, d->ln_eps, T, H, x32, x16, n32, st);
+  };
+  CRS_TRY(crs::embed_rmsnorm_launch(ids_dev, w->word_emb, w->layers[0].ln1_g, d->ln_eps, T, H, d->vocab_size, x32, x16, st), "embed_rmsnorm");
+  const float* final32 = x32;
+  for (int li = 0; li < d->layers; ++li) {
+    const crs_encoder_layer& L = w->layers[li];
+    const bool last = li + 1 == d->layers;
+    CRS_TRY(crs::gemm_launch(p.qkv, x16, (const _Float16*)L.w_qkv, nullptr, nullptr, qkv, st), "qkv gemm");
+    CRS_TRY(crs::qk_norm_rope_launch(p.qk_norm, p.hd, qkv, c->rope_dev, c->g_q[li], c->g_k[li], d->ln_eps, T, seq, d->heads, c->kv_heads, st), "qk_norm_rope");
+    CRS_TRY(crs::attention_causal_launch(p.attn, qkv, lens_dev, ctx, seq, c->kv_heads, st), "causal attention");
+    CRS_TRY(add_rms(p.out, ctx, L.w_o, L.ln2_g, nullptr), "out projection + add + mlp norm");
+    CRS_TRY(crs::gemm_launch(p.up, x16, (const _Float16*)L.w_up, nullptr, nullptr, ffn, st), "ffn up gemm");
+    float* n32 = last ? reinterpret_cast<float*>(qkv) : nullptr;     // (the QKV buffer is free by then and sized for it)
+    CRS_TRY(add_rms(p.down, ffn, L.w_down, last ? c->final_g : w->layers[li + 1].ln1_g, n32), "ffn down projection + add + next norm");
+    if (last) final32 = n32;
+  }
+  if (hidden_out_dev) {
+    const hipError_t e = hipMemcpyAsync(hidden_out_dev, final32, (size_t)T * H * 4, hipMemcpyDeviceToDevice, st);
+    if (e != hipSuccess) return crs::set_error(CRS_EHIP, hipGetErrorString(e));
+  }
+  CRS_TRY(crs::pool_launch(final32, lens_dev, batch, seq, H, d->pooling, normalize, out_dev, q16_out_dev, q16_row_elems, st), "pool");
+  return CRS_OK;
+}
+
+int crs_encoder_causal_workspace_bytes(const crs_encoder_desc* d, const crs_encoder_causal* c, int batch, int seq, size_t* bytes) {
+  const int rc = check_desc_causal(d, c);
+  if (rc) return rc;
+  if (!bytes || batch <= 0 || seq <= 0 || seq > d->max_pos) return crs::set_error(CRS_EINVAL, "bad batch/seq (seq <= max_pos)");
+  *bytes = causal_plan_for(d, c, batch, seq, 1).total;   // the layout depends on no CU count: a pure host call
+  return CRS_OK;
+}
+
+int crs_encoder_forward_causal(const crs_encoder_desc* d, const crs_encoder_weights* w, const int32_t* ids_dev, const int32_t* lens_dev,
+                               int batch, int seq, void* workspace_dev, size_t workspace_bytes, float* out_dev, int normalize,
+                               float* hidden_out_dev, void* stream, const crs_encoder_causal* c) {
+  return encoder_forward_causal(d, w, ids_dev, lens_dev, batch, seq, workspace_dev, workspace_bytes, out_dev, normalize, hidden_out_dev,
+                                nullptr, 0, stream, c);
+}
+
+int crs_encoder_forward_queries_causal(const crs_encoder_desc* d, const crs_encoder_weights* w, const int32_t* ids_dev,
+                                       const int32_t* lens_dev, int batch, int seq, void* workspace_dev, size_t workspace_bytes,
+                                       float* out_dev, void* q16_out_dev, int slab_type, void* stream, const crs_encoder_causal* c) {
+  if (!q16_out_dev) return crs::set_error(CRS_EINVAL, "null pointer");
+  if (slab_type != CRS_SLAB_F16 && slab_type != CRS_SLAB_I8) return crs::set_error(CRS_EINVAL, "bad slab_type");
+  if (!d) return crs::set_error(CRS_EINVAL, "null descriptor");
+  return encoder_forward_causal(d, w, ids_dev, lens_dev, batch, seq, workspace_dev, workspace_bytes, out_dev, 1, nullptr,
+                                reinterpret_cast<_Float16*>(q16_out_dev), crs_row_elems(d->hidden, slab_type), stream, c);
+}
+
+int crs_encoder_causal_plan_describe(const crs_encoder_desc* d, const crs_encoder_causal* c, int batch, int seq, char* buf, size_t cap) {
+  const int rc = check_desc_causal(d, c);
+  if (rc) return rc;
+  if (batch <= 0 || seq <= 0 || seq > d->max_pos || (cap && !buf)) return crs::set_error(CRS_EINVAL, "bad batch/seq (seq <= max_pos) or buffer");
+  const int cus = crs::device_cus();
+  if (cus <= 0) return crs::set_error(CRS_EHIP, "plan describe: no device");
+  return crs::causal_plan_describe(causal_plan_for(d, c, batch, seq, cus), buf, cap);
+}
+
+int crs_attention_causal_f16(const void* qkv_dev, const int32_t* lens_dev, void* ctx_dev, int batch, int seq, int heads, int kv_heads,
+                             int head_dim, void* stream) {
+  if (!qkv_dev || !lens_dev || !ctx_dev) return crs::set_error(CRS_EINVAL, "attention: null pointer");
+  if (((uintptr_t)qkv_dev | (uintptr_t)lens_dev | (uintptr_t)ctx_dev) & 15) return crs::set_error(CRS_EINVAL, "attention pointers must be 16-byte aligned");
+  const char* why = causal_group_refusal(heads, kv_heads, head_dim);
+  if (!why && (batch < 1 || batch > 65535)) why = "attention: batch must be in [1, 65535]";
+  if (!why && (seq < 1 || seq > (1 << 22))) why = "attention: seq must be in [1, 2^22]";
+  if (why) return crs::set_error(CRS_EINVAL, why);
+  const crs::AttnPlan p = crs::plan_attention_causal(batch, seq, kv_heads, head_dim, heads / kv_heads);
+  CRS_TRY(crs::attention_causal_launch(p, (const _Float16*)qkv_dev, lens_dev, (_Float16*)ctx_dev, seq, kv_heads, (hipStream_t)stream), "causal attention");
+  return CRS_OK;
+}
+
+int crs_qk_norm_rope_f16(void* qkv_dev, const float* table_dev, int positions, const float* g_q_dev, const float* g_k_dev, float eps,
+                         int batch, int seq, int heads, int kv_heads, int head_dim, void* stream) {
+  if (!qkv_dev || !table_dev || !g_q_dev || !g_k_dev || row_misaligned({qkv_dev, table_dev, g_q_dev, g_k_dev}))
+    return crs::set_error(CRS_EINVAL, "qk_norm_rope: NULL or misaligned (16 bytes) pointer");
+  if (batch < 1 || seq < 1 || heads < 1 || kv_heads < 1) return crs::set_error(CRS_EINVAL, "qk_norm_rope: bad batch / seq / heads / kv_heads");
+  if (head_dim != 64 && head_dim != 128) return crs::set_error(CRS_EINVAL, "qk_norm_rope: head_dim must be 64 or 128");
+  if (positions < seq) return crs::set_error(CRS_EINVAL, "qk_norm_rope: positions must be >= seq");
+  if ((long)batch * seq > (1L << 24)) return crs::set_error(CRS_EINVAL, "qk_norm_rope: more than 2^24 tokens");
+  CRS_TRY(crs::qk_norm_rope_launch(crs::plan_qk_norm(batch * seq, heads, kv_heads, head_dim), head_dim, (_Float16*)qkv_dev, table_dev, g_q_dev,
+                                   g_k_dev, eps, batch * seq, seq, heads, kv_heads, (hipStream_t)stream), "qk_norm_rope");
+  return CRS_OK;
+}
+
+int crs_add_rmsnorm_f32(const float* y_dev, int nsplit, const float* residual_dev, const float* g_dev, float eps, int tokens, int hidden,
+                        float* r32_dev, void* x16_dev, float* n32_dev, void* stream) {
+  if (!y_dev || !g_dev || !r32_dev || !x16_dev) return crs::set_error(CRS_EINVAL, "add_rmsnorm: null pointer");
+  if (row_misaligned({y_dev, residual_dev, g_dev, r32_dev, x16_dev, n32_dev})) return crs::set_error(CRS_EINVAL, "add_rmsnorm pointers must be 16-byte aligned");
+  const char* why = row_hidden_refusal(hidden);
+  if (!why && tokens < 1) why = "add_rmsnorm: tokens must be >= 1";
+  if (!why && !crs::forms::ln_slabs_ok(nsplit)) why = "add_rmsnorm: nsplit must be 1, 2, 3, 4, 6, 8 or 16";
+  if (why) return crs::set_error(CRS_EINVAL, why);
+  CRS_TRY(crs::add_rmsnorm_launch(y_dev, nsplit, residual_dev, g_dev, eps, tokens, hidden, r32_dev, (_Float16*)x16_dev, n32_dev,
+                                  (hipStream_t)stream), "add_rmsnorm");
+  return CRS_OK;
 }
 
 int crs_encoder_score_pairs(const crs_encoder_desc* d, const crs_encoder_weights* w, const crs_encoder_head* head,

@@ -61,6 +61,13 @@ constexpr int kAttnQ = 64, kAttnThreads = 256, kAttnMaxBiasSeq = 512;
 constexpr int attn_seq_lds(int hd, int smax) { return (smax * (hd + 4) + hd * (smax + 4)) * 2; }     // 16x16x16 whole-sequence kernel
 constexpr int attn_seq32_lds(int hd, int smax) { return (smax * (hd + 8) + hd * (smax + 8)) * 2; }   // 16x16x32 form
 
+// enc_attn_causal.hip: two [64 keys][hd + 8] K + [hd][64 + 8] V^T images (double buffer); (head_dim, group) instantiations
+constexpr int kCausalVRow = 64 + 8;
+constexpr int causal_krow(int hd) { return hd + 8; }
+constexpr int causal_image_halves(int hd) { return 64 * causal_krow(hd) + hd * kCausalVRow; }
+constexpr int attn_causal_lds(int hd) { return 2 * causal_image_halves(hd) * 2; }
+constexpr bool attn_causal_supported(int hd, int group) { return (hd == 64 || hd == 128) && (group == 1 || group == 2); }
+
 // enc_qkvattn.hip: 64 tokens x one head per workgroup
 constexpr int kQaTokens = 64, kQaThreads = 512;
 constexpr int qa_lds(int hidden, int hd) {
@@ -71,6 +78,10 @@ constexpr int kMaxLds = 160 * 1024;
 // enc_rope.hip: a thread rotates 8 column pairs (j, j + hd / 2) of one head of Q or K: hidden / 8 threads per token, no LDS
 constexpr int kRopeThreads = 256;
 constexpr long rope_items(long tokens, int hidden) { return tokens * (hidden / 8); }
+
+// enc_rope.hip, qk_norm_rope_kernel: a wave per (token, head) at head_dim 128, per two heads at 64; four waves per workgroup
+constexpr int kQkNormThreads = 256;
+constexpr long qk_norm_items(long tokens, int heads_qk, int hd) { return (tokens * heads_qk + (hd == 64 ? 1 : 0)) / (hd == 64 ? 2 : 1); }
 
 // enc_pair.hip: 8 pairs per workgroup, their [CLS] rows in LDS
 constexpr int kPairGroup = 8, kPairThreads = 256;

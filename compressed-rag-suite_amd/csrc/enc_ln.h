@@ -129,4 +129,46 @@ __device__ __forceinline__ void ln_store2_pre(float (&v)[P2][2], int hidden, int
   }
 }
 
+// ---- the RMS forms (add_rmsnorm*_kernel, embed_rmsnorm*_kernel): v[] is the residual row, written to r32 AS IT IS; its RMSNorm
+// v * 1 / sqrt(mean(v^2) + eps) * g -- no mean, no bias, one pass -- goes to x16 and, where n32 is given, to n32 in fp32.
+template <int PL>
+__device__ __forceinline__ void rms_store_pre(float (&v)[PL], int hidden, int lane, const float* g, float eps, float* r32, _Float16* x16,
+                                              float* n32) {
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < PL; ++i) q += (lane + 64 * i < hidden) ? v[i] * v[i] : 0.f;
+  const float rstd = 1.0f / sqrtf(wave_sum(q) / hidden + eps);
+#pragma unroll
+  for (int i = 0; i < PL; ++i) {
+    const int c = lane + 64 * i;
+    if (c < hidden) {
+      const float o = v[i] * rstd * g[c];
+      r32[c] = v[i];
+      x16[c] = (_Float16)o;
+      if (n32) n32[c] = o;
+    }
+  }
+}
+
+// float2 form: hidden == 128 P2 exactly
+template <int P2>
+__device__ __forceinline__ void rms_store2_pre(float (&v)[P2][2], int hidden, int lane, const float* g, float eps, float* r32,
+                                               _Float16* x16, float* n32) {
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < P2; ++i) q += v[i][0] * v[i][0] + v[i][1] * v[i][1];
+  const float rstd = 1.0f / sqrtf(wave_sum(q) / hidden + eps);
+#pragma unroll
+  for (int i = 0; i < P2; ++i) {
+    const int c = 128 * i + 2 * lane;
+    const float2 gg = *reinterpret_cast<const float2*>(g + c);
+    const float2 o = {v[i][0] * rstd * gg.x, v[i][1] * rstd * gg.y};
+    *reinterpret_cast<float2*>(r32 + c) = float2{v[i][0], v[i][1]};
+    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+    h2 h = {(_Float16)o.x, (_Float16)o.y};
+    *reinterpret_cast<h2*>(x16 + c) = h;
+    if (n32) *reinterpret_cast<float2*>(n32 + c) = o;
+  }
+}
+
 }  // namespace crs

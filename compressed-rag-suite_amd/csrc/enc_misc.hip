@@ -152,11 +152,12 @@ __global__ __launch_bounds__(256) void pool_kernel(const float* __restrict__ x32
   int len = lens[bi];
   len = len < 0 ? 0 : (len > seq ? seq : len);
   float v[4] = {0.f, 0.f, 0.f, 0.f};   // hidden <= 1024
-  if (pooling == 1) {
+  if (pooling != 0) {   // 1: the [CLS] row; 2 (CRS_POOL_LAST): the last real token, row max(len, 1) - 1
+    const float* row = base + (pooling == 2 ? (size_t)((len < 1 ? 1 : len) - 1) * hidden : 0);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int c = tid + 256 * i;
-      if (c < hidden) v[i] = base[c];
+      if (c < hidden) v[i] = row[c];
     }
   } else {
     // Mean over the real tokens.  Wave w sums tokens w, w + 4, ...; a lane covers column pairs 2 lane + 128 p (8-byte

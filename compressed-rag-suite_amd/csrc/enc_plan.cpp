@@ -326,6 +326,49 @@ EncPlan make_enc_plan(int hidden, int heads, int ffn, int flags, int batch, int 
   return p;
 }
 
+AttnPlan plan_attention_causal(int batch, int seq, int kv_heads, int hd, int group) {
+  AttnPlan a;
+  a.hd = hd, a.group = group, a.form = AttnForm::Causal;
+  a.d = {batch * kv_heads, cdiv(seq, kAttnQ), 1, kAttnThreads, attn_causal_lds(hd)};
+  return a;
+}
+
+Dims plan_qk_norm(int tokens, int q_heads, int kv_heads, int hd) {
+  const long slots = qk_norm_items(tokens, q_heads + kv_heads, hd);
+  return {(int)((slots + kQkNormThreads / 64 - 1) / (kQkNormThreads / 64)), 1, 1, kQkNormThreads, 0};
+}
+
+CausalPlan make_causal_plan(int hidden, int q_heads, int kv_heads, int hd, int ffn, int flags, int batch, int seq, int cus,
+                            const EncKnobs& kn) {
+  CausalPlan p{};
+  const int T = batch * seq, H = hidden, F = ffn, small = (flags & 1) ? 1 : 0;
+  const int nq = q_heads * hd, nqkv = (q_heads + 2 * kv_heads) * hd;
+  p.hidden = H, p.q_heads = q_heads, p.kv_heads = kv_heads, p.hd = hd, p.ffn = F, p.batch = batch, p.seq = seq, p.tokens = T;
+  p.embed = plan_rows(T);
+  p.qk_norm = plan_qk_norm(T, q_heads, kv_heads, hd);
+  p.tail = plan_pool(batch);
+  p.attn = plan_attention_causal(batch, seq, kv_heads, hd, q_heads / kv_heads);
+  // the fp16-epilogue projections as make_enc_plan routes them: the panel kernel at query-batch token counts, else plan_gemm
+  const bool single_h = T <= kPanelMaxTokens && panel_chunk(H) != 0 && (panel_chunk(H) == H || kn.panel_multi) && !gemm8_applies(T, nqkv, H, kn);
+  p.qkv = single_h ? plan_gemm_panel(T, nqkv, H, 0, small, kn) : plan_gemm(T, nqkv, H, 0, small, cus, kn);
+  p.up = single_h ? plan_gemm_panel(T, 2 * F, H, 4, small, kn) : plan_gemm(T, 2 * F, H, 4, small, cus, kn);
+  p.out = plan_proj_ln(T, H, nq, false, small, cus, kn);
+  p.down = plan_proj_ln(T, H, F, false, small, cus, kn);
+  p.out.prenorm = p.down.prenorm = p.out.rms = p.down.rms = true;
+  p.max_split = p.out.gemm.slabs > p.down.gemm.slabs ? p.out.gemm.slabs : p.down.gemm.slabs;
+  const size_t t = (size_t)T, h = H;
+  const size_t qkv_bytes = t * nqkv * 2 > t * h * 4 ? t * nqkv * 2 : t * h * 4;   // the final norm's fp32 rows land here
+  size_t off = 0;
+  p.x32 = off; off += up256(t * h * 4);
+  p.y32 = off; off += up256(t * h * 4 * p.max_split);
+  p.x16 = off; off += up256(t * h * 2);
+  p.ctx = off; off += up256(t * nq * 2);
+  p.qkv_off = off; off += up256(qkv_bytes);
+  p.ffn_off = off; off += up256(t * F * 2);
+  p.total = off;
+  return p;
+}
+
 namespace {
 
 struct Text {
@@ -363,6 +406,7 @@ void attn_line(Text& t, const AttnPlan& a) {
     case AttnForm::Seq: t.line(a.d, "attention_seq_kernel<%d, %d, %d>", a.hd, a.smax, a.nw); break;
     case AttnForm::Seq32: t.line(a.d, "attention_seq32_kernel<%d, %d, %d, %d>", a.hd, a.smax, a.nw, a.qt); break;
     case AttnForm::Window: t.line(a.d, "attention_window_kernel<%d>", a.hd); break;   // (window is a launch argument)
+    case AttnForm::Causal: t.line(a.d, "attention_causal_kernel<%d, %d>", a.hd, a.group); break;
   }
 }
 
@@ -379,6 +423,12 @@ void add_ln_line(Text& t, const Dims& d, int hidden, int slabs) {
   t.line(d, "add_layernorm%s_kernel<%d, %d>", row_form2(hidden) ? "2" : "", row_form(hidden), slabs);
 }
 
+// the RMS row kernels: the float2 form at hidden 1024, 4-byte columns otherwise (enc_addln.hip)
+void add_rms_line(Text& t, const Dims& d, int hidden, int slabs) {
+  if (hidden == 1024) t.line(d, "add_rmsnorm2_kernel<8, %d>", slabs);
+  else t.line(d, "add_rmsnorm_kernel<%d, %d>", hidden <= 64 ? 1 : 16, slabs);
+}
+
 void tail_line(Text& t, const Dims& d, int hidden, bool pair) {
   if (pair) t.line(d, "pair_head_kernel<%d>", hidden % 128 == 0 ? 2 : 1);
   else t.line(d, "pool_kernel");
@@ -387,7 +437,9 @@ void tail_line(Text& t, const Dims& d, int hidden, bool pair) {
 void proj_ln_lines(Text& t, const ProjLnPlan& s, int hidden) {
   if (s.rowln2) { t.line(s.d, s.variant ? "gemm_rowln2_kernel<64, 2>" : "gemm_rowln2_kernel<32, 4>"); return; }
   gemm_line(t, s.gemm);
-  if (s.prenorm) add_ln_line(t, s.ln, hidden, s.gemm.slabs); else ln_line(t, s.ln, hidden, s.gemm.slabs);
+  if (s.rms) add_rms_line(t, s.ln, hidden, s.gemm.slabs);
+  else if (s.prenorm) add_ln_line(t, s.ln, hidden, s.gemm.slabs);
+  else ln_line(t, s.ln, hidden, s.gemm.slabs);
 }
 
 }  // namespace
@@ -430,6 +482,19 @@ int enc_plan_describe(const EncPlan& p, char* buf, size_t cap) {
   gemm_line(t, p.up);
   proj_ln_lines(t, p.down, p.hidden);
   tail_line(t, p.tail, p.hidden, p.pair != 0);
+  return t.len;
+}
+
+int causal_plan_describe(const CausalPlan& p, char* buf, size_t cap) {
+  Text t{buf, cap};
+  t.line(p.embed, "embed_rmsnorm_kernel<16>");   // (hidden >= 128: the only form)
+  gemm_line(t, p.qkv);
+  t.line(p.qk_norm, "qk_norm_rope_kernel<%d>", p.hd);
+  attn_line(t, p.attn);
+  proj_ln_lines(t, p.out, p.hidden);
+  gemm_line(t, p.up);
+  proj_ln_lines(t, p.down, p.hidden);
+  tail_line(t, p.tail, p.hidden, false);
   return t.len;
 }
 

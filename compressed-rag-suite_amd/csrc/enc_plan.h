@@ -65,10 +65,11 @@ GemmPlan plan_gemm_panel(int m, int n, int k, int mode, int small_lds, const Enc
 int gemm8_splitk(int m, int n, int k, const EncKnobs& kn);
 GemmPlan plan_gemm8(int m, int n, int k, int mode, int splits, int cus, const EncKnobs& kn);
 
-enum class AttnForm { Fused, Blocked, Short, Seq, Seq32, Window };
+enum class AttnForm { Fused, Blocked, Short, Seq, Seq32, Window, Causal };
 struct AttnPlan {
   AttnForm form = AttnForm::Blocked;   // Fused: QKV projection + attention in one kernel (enc_qkvattn.hip), no QKV GEMM
   int hd = 0;
+  int group = 0;                       // Causal only: query heads per key / value head (enc_attn_causal.hip)
   bool bias = false;                   // Blocked only: relative-position bias
   int smax = 0, nw = 0, qt = 0;        // Seq / Seq32: template arguments
   int window = 0;                      // Window only: the largest allowed |key - query|
@@ -98,6 +99,7 @@ struct ProjLnPlan {
   GemmPlan gemm;       // mode 3 (the LayerNorm adds bias and residual) or mode 2 (already folded in, slabs = 1)
   Dims ln;
   bool prenorm = false;   // the row kernel is add_layernorm*_kernel (never rowln2)
+  bool rms = false;       // prenorm only: its RMS form, add_rmsnorm*_kernel
 };
 
 // big_ln: the index-build side (make_enc_plan: more than 4096 tokens and CRS_ENC_BIGLN); then rowln2 where it has the shape, else
@@ -136,6 +138,29 @@ struct EncPlan {
 // 2 pair head without.  The sizes are check_desc's (hidden % 64 == 0 <= 1024, head_dim 16 / 32 / 64, ffn % 64 == 0).
 EncPlan make_enc_plan(int hidden, int heads, int ffn, int flags, int batch, int seq, int rel_bias, int pair, int cus, const EncKnobs& kn,
                       int window = 0);
+
+// ---- causal RMS pre-norm models (Qwen3-Embedding: CRS_ENC_CAUSAL | CRS_ENC_RMSNORM | CRS_ENC_PRENORM | CRS_ENC_ROTARY | CRS_ENC_GATED_SILU) ----
+// attention_causal_kernel<hd, group>: batch * kv_heads units along x, the 64-query blocks along y (the kernel walks them from the last
+// one down), two K + V^T images of dynamic LDS.  The caller checked forms::attn_causal_supported(hd, group).
+AttnPlan plan_attention_causal(int batch, int seq, int kv_heads, int hd, int group);
+// qk_norm_rope_kernel<hd>: a wave per (token, head) of the Q and K blocks (two heads per wave at head_dim 64), four waves per workgroup
+Dims plan_qk_norm(int tokens, int q_heads, int kv_heads, int hd);
+
+// Such a forward's plan: the embedding + norm, then per layer the QKV GEMM over (Hq + 2 Hkv) hd columns, qk_norm_rope, causal
+// attention, out projection (K = Hq hd) + add_rmsnorm, gated FFN-up (mode 4), FFN-down + add_rmsnorm, then pooling.  Out and down go
+// through plan_proj_ln with the pre-norm row kernel in its RMS form; the fused QKV + attention kernel and rowln2 are never selected.
+struct CausalPlan {
+  int hidden, q_heads, kv_heads, hd, ffn, batch, seq, tokens;
+  Dims embed, qk_norm, tail;
+  AttnPlan attn;
+  GemmPlan qkv, up;
+  ProjLnPlan out, down;
+  // workspace: [x32 | y32 (max_split slabs) | x16 | ctx [T, Hq hd] | qkv [T, (Hq + 2 Hkv) hd] (and the final norm's fp32 rows) | ffn]
+  size_t x32, y32, x16, ctx, qkv_off, ffn_off, total;
+  int max_split;
+};
+CausalPlan make_causal_plan(int hidden, int q_heads, int kv_heads, int hd, int ffn, int flags, int batch, int seq, int cus, const EncKnobs& kn);
+int causal_plan_describe(const CausalPlan& p, char* buf, size_t cap);
 
 // One line per launch of embedding, ONE layer and the tail, in launch order: "<kernel><template arguments> grid=XxYxZ wg=Nx1x1 lds=BYTES\n"
 // (grid in workgroups, dynamic LDS).  Returns the length of the whole text (snprintf): > cap - 1 means it was cut.

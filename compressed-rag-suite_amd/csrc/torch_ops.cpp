@@ -1174,6 +1174,58 @@ void encoder_forward_prenorm(const Tensor& ids, const Tensor& lens, at::TensorLi
                                  out.data_ptr<float>(), normalize ? 1 : 0, hid, cur_stream(ids), &pre), "crs::encoder_forward_prenorm");
 }
 
+// encoder_forward_causal: descriptors with CRS_ENC_CAUSAL | CRS_ENC_RMSNORM (crs_encoder_causal): the rope table fp32 [positions, head_dim]
+// (its width IS the head_dim), the key / value head count, one [head_dim] gain per layer for the Q heads and for the K heads, the final
+// norm's gain.  weights as encoder_forward; pos_emb, type_emb, emb_ln_* and every bias are EMPTY tensors (NULL for the library).
+void encoder_forward_causal(const Tensor& ids, const Tensor& lens, at::TensorList weights, at::IntArrayRef desc, double ln_eps, Tensor workspace,
+                            Tensor out, c10::optional<Tensor> q16_out, int64_t slab_type, bool normalize, c10::optional<Tensor> hidden_out,
+                            const Tensor& rope_table, int64_t kv_heads, at::TensorList g_q, at::TensorList g_k, const Tensor& final_g) {
+  want(ids, at::kInt, "ids");
+  want(lens, at::kInt, "lens");
+  want(out, at::kFloat, "out");
+  want(rope_table, at::kFloat, "rope_table");
+  want(final_g, at::kFloat, "final_g");
+  EncArgs ea;
+  enc_args(ids, weights, desc, ln_eps, ea);
+  const crs_encoder_desc& d = ea.d;
+  TORCH_CHECK(ids.dim() == 2 && lens.numel() == ids.size(0) && out.numel() == ids.size(0) * d.hidden, "ids [B, S], lens [B], out [B, H]");
+  same_device(ids, {&lens, &workspace, &out, opt_t(q16_out), opt_t(hidden_out), &rope_table, &final_g}, "crs::encoder_forward_causal");
+  TORCH_CHECK(rope_table.dim() == 2 && final_g.numel() == d.hidden, "rope_table must be [positions, head_dim] and final_g [H]");
+  TORCH_CHECK(kv_heads >= 1 && kv_heads <= INT32_MAX, "kv_heads out of range");
+  TORCH_CHECK((int64_t)g_q.size() == d.layers && (int64_t)g_k.size() == d.layers, "g_q and g_k must hold one tensor per layer");
+  const int64_t hd = rope_table.size(1);
+  std::vector<const float*> gq((size_t)d.layers), gk((size_t)d.layers);
+  for (int l = 0; l < d.layers; ++l) {
+    want(g_q[l], at::kFloat, "g_q");
+    want(g_k[l], at::kFloat, "g_k");
+    same_device(ids, {&g_q[l], &g_k[l]}, "crs::encoder_forward_causal");
+    TORCH_CHECK(g_q[l].numel() == hd && g_k[l].numel() == hd, "g_q / g_k tensors must be [head_dim]");
+    gq[(size_t)l] = g_q[l].data_ptr<float>();
+    gk[(size_t)l] = g_k[l].data_ptr<float>();
+  }
+  const crs_encoder_causal c{(int32_t)kv_heads, (int32_t)hd, rope_table.data_ptr<float>(), (int32_t)rope_table.size(0), gq.data(), gk.data(),
+                             final_g.data_ptr<float>()};
+  const int b = (int)ids.size(0), s = (int)ids.size(1);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(ids.device());
+  if (q16_out.has_value() && q16_out->defined()) {
+    want(*q16_out, at::kHalf, "q16_out");
+    TORCH_CHECK(normalize && !(hidden_out.has_value() && hidden_out->defined()), "q16_out needs normalize=True and no hidden_out");
+    TORCH_CHECK(q16_out->numel() == (int64_t)b * crs_row_elems(d.hidden, (int)slab_type), "q16_out must be [B, crs_row_elems(H, slab_type)]");
+    ok(crs_encoder_forward_queries_causal(&d, &ea.cw, ids.data_ptr<int32_t>(), lens.data_ptr<int32_t>(), b, s, workspace.data_ptr(),
+                                          (size_t)workspace.nbytes(), out.data_ptr<float>(), q16_out->data_ptr(), (int)slab_type, cur_stream(ids), &c),
+       "crs::encoder_forward_causal");
+    return;
+  }
+  float* hid = nullptr;
+  if (hidden_out.has_value() && hidden_out->defined()) {
+    want(*hidden_out, at::kFloat, "hidden_out");
+    TORCH_CHECK(hidden_out->numel() == (int64_t)b * s * d.hidden, "hidden_out must be [B, S, H]");
+    hid = hidden_out->data_ptr<float>();
+  }
+  ok(crs_encoder_forward_causal(&d, &ea.cw, ids.data_ptr<int32_t>(), lens.data_ptr<int32_t>(), b, s, workspace.data_ptr(), (size_t)workspace.nbytes(),
+                                out.data_ptr<float>(), normalize ? 1 : 0, hid, cur_stream(ids), &c), "crs::encoder_forward_causal");
+}
+
 void encoder_forward_ex(const Tensor& ids, const Tensor& lens, at::TensorList weights, at::IntArrayRef desc, double ln_eps, Tensor workspace,
                         Tensor out, c10::optional<Tensor> q16_out, int64_t slab_type, bool normalize, c10::optional<Tensor> hidden_out,
                         c10::optional<Tensor> rel_bias) {
@@ -1311,6 +1363,9 @@ TORCH_LIBRARY(crs, m) {
   m.def("encoder_forward_prenorm(Tensor ids, Tensor lens, Tensor[] weights, int[] desc, float ln_eps, Tensor(a!) workspace, Tensor(b!) out, "
         "Tensor(c!)? q16_out, int slab_type, bool normalize, Tensor(d!)? hidden_out, Tensor rope_global, Tensor rope_local, int window, "
         "int global_every, Tensor final_ln_g, Tensor? final_ln_b=None) -> ()");
+  m.def("encoder_forward_causal(Tensor ids, Tensor lens, Tensor[] weights, int[] desc, float ln_eps, Tensor(a!) workspace, Tensor(b!) out, "
+        "Tensor(c!)? q16_out, int slab_type, bool normalize, Tensor(d!)? hidden_out, Tensor rope_table, int kv_heads, Tensor[] g_q, "
+        "Tensor[] g_k, Tensor final_g) -> ()");
   m.def("encoder_score_pairs(Tensor ids, Tensor? type_ids, Tensor lens, Tensor[] weights, Tensor[] head, int[] desc, float ln_eps, "
         "int activation, Tensor(a!) workspace, Tensor(b!) scores, Tensor(c!)? pooled_out, Tensor(d!)? hidden_out) -> ()");
 }
@@ -1362,5 +1417,6 @@ TORCH_LIBRARY_IMPL(crs, CUDA, m) {   // the HIP backend of torch-ROCm dispatches
   m.impl("encoder_forward_ex", &encoder_forward_ex);
   m.impl("encoder_forward_rope", &encoder_forward_rope);
   m.impl("encoder_forward_prenorm", &encoder_forward_prenorm);
+  m.impl("encoder_forward_causal", &encoder_forward_causal);
   m.impl("encoder_score_pairs", &encoder_score_pairs);
 }

@@ -26,6 +26,11 @@ import numpy as np
 from rag import _native as nat
 
 POOL_MEAN, POOL_CLS = 0, 1
+POOL_LAST = 2          # CRS_POOL_LAST: the last real token's row (the _causal forwards)
+POOLING = {"mean": POOL_MEAN, "cls": POOL_CLS, "last": POOL_LAST}
+ENC_RMSNORM = 32       # CRS_ENC_RMSNORM: every norm an RMSNorm, no embedding norm
+ENC_CAUSAL = 64        # CRS_ENC_CAUSAL: causal grouped-query attention + QK-norm (crs_encoder_forward_causal)
+CAUSAL_SHAPES = ((64, 1), (64, 2), (128, 1), (128, 2))   # (head_dim, query heads per key / value head) attention_causal_kernel has
 ENC_SMALL_LDS = 1      # CRS_ENC_SMALL_LDS: kernel forms of <= 48 KB of LDS (forwards that run beside a scan)
 ENC_ROTARY = 2         # CRS_ENC_ROTARY: rope_qk_kernel between the QKV projection and attention, no position table
 ENC_GATED_SILU = 4     # CRS_ENC_GATED_SILU: w_up holds interleaved gate / up rows, FFN-up runs GEMM mode 4
@@ -60,6 +65,11 @@ class EncoderRope(Structure):     # crs_encoder_rope
 class EncoderPrenorm(Structure):  # crs_encoder_prenorm
     _fields_ = [("rope_global_dev", c_void_p), ("rope_local_dev", c_void_p), ("positions", c_int32), ("window", c_int32),
                 ("global_every", c_int32), ("final_ln_g", c_void_p), ("final_ln_b", c_void_p)]
+
+
+class EncoderCausal(Structure):   # crs_encoder_causal
+    _fields_ = [("kv_heads", c_int32), ("head_dim", c_int32), ("rope_dev", c_void_p), ("positions", c_int32),
+                ("g_q", POINTER(c_void_p)), ("g_k", POINTER(c_void_p)), ("final_g", c_void_p)]
 
 
 class EncoderHead(Structure):     # crs_encoder_head
@@ -124,6 +134,16 @@ nat.register_signatures({
     "crs_attention_window_plan_describe": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t]),
     "crs_add_layernorm_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_void_p, c_void_p,
                                       c_void_p, c_void_p]),
+    # causal RMS pre-norm models (the forward reaches them through torch.ops.crs.encoder_forward_causal) and their kernels on their own
+    "crs_encoder_causal_workspace_bytes": (c_int, [POINTER(EncoderDesc), POINTER(EncoderCausal), c_int, c_int, POINTER(c_size_t)]),
+    "crs_encoder_forward_causal": (c_int, [POINTER(EncoderDesc), POINTER(EncoderWeights), c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                           c_size_t, c_void_p, c_int, c_void_p, c_void_p, POINTER(EncoderCausal)]),
+    "crs_encoder_forward_queries_causal": (c_int, [POINTER(EncoderDesc), POINTER(EncoderWeights), c_void_p, c_void_p, c_int, c_int,
+                                                   c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_void_p, POINTER(EncoderCausal)]),
+    "crs_encoder_causal_plan_describe": (c_int, [POINTER(EncoderDesc), POINTER(EncoderCausal), c_int, c_int, c_void_p, c_size_t]),
+    "crs_attention_causal_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "crs_qk_norm_rope_f16": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "crs_add_rmsnorm_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_float, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
 })
 
 
@@ -149,6 +169,11 @@ class ModelShape:
     global_every: int = 1         # layer i attends the whole sequence when i % global_every == 0
     local_theta: float = 0.0
     gelu_gated: bool = False      # GeGLU: Wo(gelu(input) * gate), (input, gate) = Wi(x).chunk(2)
+    # Qwen3-Embedding: causal grouped-query attention, RMSNorm everywhere (pre-norm order), an RMSNorm over head_dim on every Q and K
+    # head before the rotation, SwiGLU (`gated`), no biases; `heads` query heads of head_dim columns (heads * head_dim != hidden allowed)
+    causal: bool = False
+    kv_heads: int = 0             # key / value heads; heads % kv_heads == 0
+    head_dim: int = 0             # 0: hidden // heads
 
 
 def interleave_wi(wi) -> np.ndarray:
@@ -313,6 +338,28 @@ def add_layernorm_f32(y, bias, residual, g, b, eps: float, r32, x16, n32=None) -
                                                nat._stream_ptr()))
 
 
+def attention_causal_f16(qkv, lens, ctx, batch: int, seq: int, heads: int, kv_heads: int, head_dim: int) -> None:
+    """crs_attention_causal_f16: ctx (cuda fp16 [batch * seq, heads * head_dim]) <- causal grouped-query attention of qkv (cuda fp16
+    [batch * seq, (heads + 2 kv_heads) * head_dim], Q | K | V blocks) under lens: row q attends the keys < min(q + 1, len)."""
+    nat.check(nat.load().crs_attention_causal_f16(nat._ptr(qkv), nat._ptr(lens), nat._ptr(ctx), int(batch), int(seq), int(heads),
+                                                  int(kv_heads), int(head_dim), nat._stream_ptr()))
+
+
+def qk_norm_rope_f16(qkv, table, g_q, g_k, eps: float, batch: int, seq: int, heads: int, kv_heads: int) -> None:
+    """crs_qk_norm_rope_f16: RMSNorm over head_dim (gains g_q / g_k, cuda fp32 [head_dim]) then the rotation against table (cuda fp32
+    [positions, head_dim]) of every Q and K head of qkv (the layout above), in place; V is not touched."""
+    nat.check(nat.load().crs_qk_norm_rope_f16(nat._ptr(qkv), nat._ptr(table), int(table.shape[0]), nat._ptr(g_q), nat._ptr(g_k), float(eps),
+                                              int(batch), int(seq), int(heads), int(kv_heads), int(table.shape[1]), nat._stream_ptr()))
+
+
+def add_rmsnorm_f32(y, residual, g, eps: float, r32, x16, n32=None) -> None:
+    """crs_add_rmsnorm_f32: r32 (cuda fp32 [tokens, H]) <- sum of the slabs of y (cuda fp32 [nsplit, tokens, H]) + residual; x16 (fp16) and
+    n32 (fp32 or None) <- RMSNorm(r32) g.  residual may be None or r32."""
+    nsplit, tokens, hidden = y.shape
+    nat.check(nat.load().crs_add_rmsnorm_f32(nat._ptr(y), int(nsplit), nat._ptr(residual), nat._ptr(g), float(eps), int(tokens), int(hidden),
+                                             nat._ptr(r32), nat._ptr(x16), nat._ptr(n32), nat._stream_ptr()))
+
+
 def row_plan_describe(kind: int, rows: int, hidden: int, arg: int = 0) -> str:
     """The launch line of embed_ln_f32 (kind 0, rows = tokens, arg: typed), layernorm_f32 (1, tokens, arg = nsplit), pool_f32 (2, rows =
     batch) or pair_head_f32 (3, batch) for these sizes (crs_row_plan_describe); needs no device."""
@@ -406,10 +453,23 @@ class HipEncoder:
             raise ValueError("a prenorm model needs rotary_theta > 0, local_theta > 0, window >= 1 and global_every >= 1")
         if rotary and (shape.rel_buckets or shape.pos_offset):
             raise ValueError("a rotary model has no position table: rel_buckets and pos_offset must be 0")
+        causal = bool(shape.causal)
+        head_dim = shape.head_dim or shape.hidden // shape.heads
+        if causal:
+            if not (rotary and shape.gated) or prenorm:
+                raise ValueError("a causal model needs rotary_theta > 0 and gated (SwiGLU), and is not a ModernBERT (prenorm) shape")
+            if shape.kv_heads < 1 or shape.heads % shape.kv_heads or (head_dim, shape.heads // shape.kv_heads) not in CAUSAL_SHAPES:
+                raise NotImplementedError(f"causal attention: head_dim {head_dim} with {shape.heads} query / {shape.kv_heads} key-value heads is not "
+                                          f"supported (head_dim 64 or 128, 1 or 2 query heads per key-value head)")
+        elif shape.pooling == "last":
+            raise NotImplementedError("pooling 'last' (last-token pooling) is only supported for causal models")
+        if shape.pooling not in POOLING:
+            raise ValueError(f"pooling must be one of {sorted(POOLING)}, got {shape.pooling!r}")
         flags = (ENC_ROTARY if rotary else 0) | (ENC_GATED_SILU if shape.gated else 0)
         flags |= (ENC_PRENORM | ENC_GATED_GELU) if prenorm else 0
+        flags |= (ENC_PRENORM | ENC_RMSNORM | ENC_CAUSAL) if causal else 0
         self.desc = EncoderDesc(shape.vocab_size, shape.hidden, shape.layers, shape.heads, shape.ffn,
-                                shape.max_pos - shape.pos_offset, shape.ln_eps, POOL_CLS if shape.pooling == "cls" else POOL_MEAN, flags)
+                                shape.max_pos - shape.pos_offset, shape.ln_eps, POOLING[shape.pooling], flags)
         self._layers = (EncoderLayer * shape.layers)()
 
         def keep(arr, dtype=None):
@@ -465,6 +525,19 @@ class HipEncoder:
                 dev32(p + "mlp_norm.weight"), opt(p + "mlp_norm.bias"),
             ]
 
+        def qwen3_layer(i):
+            """the 12 tensors of crs_encoder_layer from Qwen3Model's names: w_qkv = q, k, v rows stacked ([(Hq + 2 Hkv) hd, H]), ln1 =
+            input_layernorm, ln2 = post_attention_layernorm, w_up = interleaved gate / up; every bias EMPTY (NULL)"""
+            p = f"layers.{i}."
+            return [
+                dev16(p + "self_attn.q_proj.weight", p + "self_attn.k_proj.weight", p + "self_attn.v_proj.weight"), keep(empty),
+                dev16(p + "self_attn.o_proj.weight"), keep(empty),
+                dev32(p + "input_layernorm.weight"), keep(empty),
+                keep(interleave_gate_up(weights[p + "mlp.gate_proj.weight"], weights[p + "mlp.up_proj.weight"]), torch.float16), keep(empty),
+                dev16(p + "mlp.down_proj.weight"), keep(empty),
+                dev32(p + "post_attention_layernorm.weight"), keep(empty),
+            ]
+
         def bert_layer(i):
             p = f"encoder.layer.{i}."
             return [
@@ -479,7 +552,7 @@ class HipEncoder:
 
         layer_tensors = []
         for i in range(shape.layers):
-            vals = modernbert_layer(i) if prenorm else nomic_layer(i) if rotary else bert_layer(i)
+            vals = qwen3_layer(i) if causal else modernbert_layer(i) if prenorm else nomic_layer(i) if rotary else bert_layer(i)
             layer_tensors += vals
             for (fname, _), t in zip(EncoderLayer._fields_, vals):
                 setattr(self._layers[i], fname, t.data_ptr() if t.numel() else None)
@@ -487,7 +560,9 @@ class HipEncoder:
             pos = keep(np.zeros((0, shape.hidden), dtype=np.float32))
         else:           # (a contiguous view of the kept tensor from its row pos_offset on)
             pos = dev32("embeddings.position_embeddings.weight")[shape.pos_offset:]
-        if prenorm:     # ModernBERT: no token types (a zero row), norms without bias unless the checkpoint carries one
+        if causal:      # Qwen3: the token table alone (no position row, no token types, no embedding norm)
+            emb = [dev32("embed_tokens.weight"), pos, keep(empty), keep(empty), keep(empty)]
+        elif prenorm:   # ModernBERT: no token types (a zero row), norms without bias unless the checkpoint carries one
             emb = [dev32("embeddings.tok_embeddings.weight"), pos, keep(np.zeros((1, shape.hidden), dtype=np.float32)),
                    dev32("embeddings.norm.weight"), bias_or_zeros("embeddings.norm.bias", shape.hidden)]
         else:
@@ -499,8 +574,13 @@ class HipEncoder:
         self._wlist = emb + layer_tensors
         assert len(self._wlist) == 5 + 12 * shape.layers
         if rotary:
-            self.rope_table = torch.from_numpy(rope_table(min(shape.max_seq, shape.max_pos), shape.hidden // shape.heads,
-                                                          shape.rotary_theta)).to(self.device)
+            self.rope_table = torch.from_numpy(rope_table(min(shape.max_seq, shape.max_pos), head_dim, shape.rotary_theta)).to(self.device)
+        self.causal = None            # crs_encoder_causal's shape fields (workspace size, plan text); the forward passes the tensors
+        if causal:
+            self.causal = EncoderCausal(shape.kv_heads, head_dim, None, 0, None, None, None)
+            self.qk_gains = ([dev32(f"layers.{i}.self_attn.q_norm.weight") for i in range(shape.layers)],
+                             [dev32(f"layers.{i}.self_attn.k_norm.weight") for i in range(shape.layers)])
+            self.final_g = dev32("norm.weight")
         self.rope_local = self.final_ln = None
         if prenorm:
             self.rope_local = torch.from_numpy(rope_table(min(shape.max_seq, shape.max_pos), shape.hidden // shape.heads,
@@ -542,9 +622,17 @@ class HipEncoder:
         lib = nat.load()
         return _describe(lambda sl, buf, cap: lib.crs_encoder_prenorm_plan_describe(byref(self.desc), batch, seq, int(self.shape.window), buf, cap))[0]
 
+    def causal_plan_describe(self, batch: int, seq: int) -> str:
+        """The launches of a causal model's forward on the current device, one line each (crs_encoder_causal_plan_describe)."""
+        lib = nat.load()
+        return _describe(lambda sl, buf, cap: lib.crs_encoder_causal_plan_describe(byref(self.desc), byref(self.causal), batch, seq, buf, cap))[0]
+
     def workspace_bytes(self, batch: int, seq: int) -> int:
         out = c_size_t(0)
-        nat.check(nat.load().crs_encoder_workspace_bytes(byref(self.desc), batch, seq, byref(out)))
+        if self.causal is not None:
+            nat.check(nat.load().crs_encoder_causal_workspace_bytes(byref(self.desc), byref(self.causal), batch, seq, byref(out)))
+        else:
+            nat.check(nat.load().crs_encoder_workspace_bytes(byref(self.desc), batch, seq, byref(out)))
         return int(out.value)
 
     def forward(self, ids, lens, normalize: bool = True, return_hidden: bool = False, out=None, workspace=None,
@@ -581,7 +669,11 @@ class HipEncoder:
         if small_lds:          # per call, not process-wide: the role-lane engine asks for it, everyone else gets the default forms
             desc = desc[:7] + [desc[7] | ENC_SMALL_LDS]
         with nat._translate():
-            if self.desc.flags & ENC_PRENORM:
+            if self.desc.flags & ENC_CAUSAL:
+                nat.ops().encoder_forward_causal(ids, lens, self._wlist, desc, float(self.desc.ln_eps), ws, out, q16_out, int(slab_type),
+                                                 bool(normalize), hidden, self.rope_table, int(self.shape.kv_heads), self.qk_gains[0],
+                                                 self.qk_gains[1], self.final_g)
+            elif self.desc.flags & ENC_PRENORM:
                 nat.ops().encoder_forward_prenorm(ids, lens, self._wlist, desc, float(self.desc.ln_eps), ws, out, q16_out,
                                                   int(slab_type), bool(normalize), hidden, self.rope_table, self.rope_local,
                                                   int(self.shape.window), int(self.shape.global_every), self.final_ln[0], self.final_ln[1])

@@ -10,12 +10,13 @@ Model resolution, offline by construction (the reference fetches by hub name, wh
 here): ``model_path`` (additive key) or ``model_name`` may be a LOCAL sentence-transformers
 directory (config.json, model.safetensors, vocab.txt, optional sentence_bert_config.json and
 1_Pooling/config.json); else ``$CRS_MODEL_DIR/<basename of model_name>`` is tried; else, when
-``model_name`` is ``synthetic:<minilm|bge|tiny|mpnet|tiny-mpnet|tiny-xlmr|multilingual-minilm|multilingual-e5-base|tiny-nomic|nomic-embed-text|tiny-modernbert|modernbert-base>`` or ``CRS_ALLOW_SYNTHETIC_WEIGHTS=1`` is set,
+``model_name`` is ``synthetic:<minilm|bge|tiny|mpnet|tiny-mpnet|tiny-xlmr|multilingual-minilm|multilingual-e5-base|tiny-nomic|nomic-embed-text|tiny-modernbert|modernbert-base|tiny-qwen3|qwen3-embedding-0.6b>`` or ``CRS_ALLOW_SYNTHETIC_WEIGHTS=1`` is set,
 seeded random weights of the named architecture are used with a hash tokeniser (plumbing and
 benchmarks only -- embeddings are then meaningless as language).  Anything else raises.
 
 Task prefixes (additive keys ``query_prefix`` / ``document_prefix``, default ""): models trained with them (nomic-embed-text:
-"search_query: " / "search_document: "; E5: "query: " / "passage: ") get the prefix prepended to every text of that kind before
+"search_query: " / "search_document: "; E5: "query: " / "passage: "; Qwen3-Embedding: queries
+"Instruct: Given a web search query, retrieve relevant passages that answer the query\nQuery:", documents none) get the prefix prepended to every text of that kind before
 tokenisation; ``embed`` / ``embed_device`` / ``tokenize`` / ``tokenize_device`` take ``kind=None | 'query' | 'document'`` and the
 chunk methods are 'document'.  Nothing is read from config_sentence_transformers.json.
 """
@@ -69,6 +70,14 @@ _KNOWN = {
                             ln_eps=1e-5, rotary_theta=160000.0, local_theta=10000.0, prenorm=True, gelu_gated=True, window=8, global_every=3),
     "modernbert-base": dict(vocab_size=50368, hidden=768, layers=22, heads=12, ffn=1152, max_pos=8192, pooling="mean", max_seq=8192,
                             ln_eps=1e-5, rotary_theta=160000.0, local_theta=10000.0, prenorm=True, gelu_gated=True, window=64, global_every=3),
+    # Qwen3-Embedding-0.6B: a causal decoder used as an embedder -- grouped-query attention (16 query / 8 key-value heads of 128 columns,
+    # so heads * head_dim = 2048 != hidden), RMSNorm in pre-norm order, an RMSNorm over head_dim on every Q and K head before the
+    # rotation (base 1e6), SwiGLU, no biases, last-token pooling.  Its instruction prompt is `query_prefix` (the model card's
+    # "Instruct: Given a web search query, retrieve relevant passages that answer the query\nQuery:"); documents take none.
+    "tiny-qwen3": dict(vocab_size=1000, hidden=128, layers=2, heads=2, ffn=256, max_pos=256, pooling="last", max_seq=256, ln_eps=1e-6,
+                       rotary_theta=1e6, gated=True, causal=True, kv_heads=1, head_dim=128),
+    "qwen3-embedding-0.6b": dict(vocab_size=151669, hidden=1024, layers=28, heads=16, ffn=3072, max_pos=32768, pooling="last", max_seq=8192,
+                                 ln_eps=1e-6, rotary_theta=1e6, gated=True, causal=True, kv_heads=8, head_dim=128),
 }
 _ALIASES = {"minilm": "all-minilm-l6-v2", "bge": "bge-base-en-v1.5", "bge-base": "bge-base-en-v1.5", "mpnet": "all-mpnet-base-v2",
             "nomic": "nomic-embed-text", "nomic-embed-text-v1": "nomic-embed-text", "nomic-embed-text-v1.5": "nomic-embed-text",
@@ -123,6 +132,27 @@ def synthetic_weights(shape, seed: int = 0, scale: float = 0.05) -> Dict[str, np
     `rel_buckets` (MPNet) also get the relative-position bias table (~N(0, 0.5): real tables are O(1)) and, having no
     token types, a zero token-type table.  Gated (nomic) shapes: NomicBertModel's names, query / key projections ~N(0, 1 / hidden)."""
     h, f = shape.hidden, shape.ffn
+    if getattr(shape, "causal", False):     # Qwen3 under Qwen3Model's names: the token table, per-layer gains and matrices, no bias
+        hd = shape.head_dim or h // shape.heads
+        nq, nkv = shape.heads * hd, shape.kv_heads * hd
+        names = [("embed_tokens.weight", (shape.vocab_size, h))]
+        for i in range(shape.layers):
+            p = f"layers.{i}."
+            names += [(p + "input_layernorm.weight", (h,)), (p + "self_attn.q_proj.weight", (nq, h)), (p + "self_attn.k_proj.weight", (nkv, h)),
+                      (p + "self_attn.v_proj.weight", (nkv, h)), (p + "self_attn.o_proj.weight", (h, nq)),
+                      (p + "self_attn.q_norm.weight", (hd,)), (p + "self_attn.k_norm.weight", (hd,)),
+                      (p + "post_attention_layernorm.weight", (h,)), (p + "mlp.gate_proj.weight", (f, h)),
+                      (p + "mlp.up_proj.weight", (f, h)), (p + "mlp.down_proj.weight", (h, f))]
+        names.append(("norm.weight", (h,)))
+        out = {}
+        for idx, (name, shp) in enumerate(names):
+            rng = np.random.Generator(np.random.PCG64([seed, idx]))
+            if name.endswith("norm.weight"):
+                a = 1.0 + 0.05 * rng.standard_normal(shp, dtype=np.float32)
+            else:       # (the QK-norm fixes the logits' scale whatever the projections': no 1 / sqrt(h) rows here)
+                a = scale * rng.standard_normal(shp, dtype=np.float32)
+            out[name] = a.astype(np.float32)
+        return out
     if getattr(shape, "prenorm", False):    # ModernBERT under ModernBertModel's names: no position table, no token types, no biases
         names = [("embeddings.tok_embeddings.weight", (shape.vocab_size, h)), ("embeddings.norm.weight", (h,))]
         for i in range(shape.layers):
@@ -349,6 +379,44 @@ def _modernbert_shape_and_weights(cfg: dict, raw: Dict[str, np.ndarray], pooling
     return shape, weights
 
 
+QWEN3_MAX_HIDDEN = 1024      # the row kernels' width: Qwen3-Embedding-0.6B fits, the 4B (2560) and 8B (4096) checkpoints do not
+
+
+def _qwen3_shape_and_weights(cfg: dict, raw: Dict[str, np.ndarray], pooling: str, max_seq):
+    """(ModelShape, weights under Qwen3Model's names) of a model_type "qwen3" directory: a bare Qwen3Model or the sentence-transformers
+    layout; tensor names with or without a leading "model."; lm_head is ignored.  Every option this encoder does not run is refused
+    by name."""
+    from rag._encoder import CAUSAL_SHAPES, ModelShape
+    if cfg.get("use_sliding_window", False):
+        raise NotImplementedError("qwen3: use_sliding_window is not supported (full causal attention is)")
+    if any(t != "full_attention" for t in cfg.get("layer_types") or []):
+        raise NotImplementedError(f"qwen3: layer_types {cfg.get('layer_types')} are not supported (use_sliding_window: full_attention in every layer is)")
+    rp = dict(cfg.get("rope_parameters") or {})
+    if cfg.get("rope_scaling") not in (None, {}) or rp.get("rope_type", "default") != "default" or rp.get("factor") not in (None, 1, 1.0):
+        raise NotImplementedError(f"qwen3: rope scaling (rope_scaling {cfg.get('rope_scaling')}, rope_parameters {rp or None}) is not supported")
+    if cfg.get("attention_bias", False):
+        raise NotImplementedError("qwen3: attention_bias = true is not supported (projections without bias are)")
+    act = str(cfg.get("hidden_act", "silu")).lower()
+    if act != "silu":
+        raise NotImplementedError(f"qwen3: hidden_act '{act}' is not supported (silu is)")
+    hidden, heads, layers = int(cfg["hidden_size"]), int(cfg["num_attention_heads"]), int(cfg["num_hidden_layers"])
+    if hidden > QWEN3_MAX_HIDDEN:
+        raise NotImplementedError(f"qwen3: hidden_size {hidden} is not supported (up to {QWEN3_MAX_HIDDEN}: Qwen3-Embedding-0.6B; the 4B and 8B "
+                                  f"checkpoints are wider than the row kernels)")
+    kv_heads = int(cfg.get("num_key_value_heads") or heads)
+    hd = int(cfg.get("head_dim") or hidden // heads)
+    if kv_heads < 1 or heads % kv_heads or (hd, heads // kv_heads) not in CAUSAL_SHAPES:
+        raise NotImplementedError(f"qwen3: head_dim {hd} with num_attention_heads {heads} / num_key_value_heads {kv_heads} is not supported "
+                                  f"(head_dim 64 or 128 with 1 or 2 query heads per key-value head)")
+    max_pos = int(cfg.get("max_position_embeddings", 32768))
+    theta = float(rp.get("rope_theta", cfg.get("rope_theta", 1e6)))
+    weights = {(k[6:] if k.startswith("model.") else k): np.asarray(v, dtype=np.float32) for k, v in raw.items() if not k.startswith("lm_head.")}
+    shape = ModelShape(int(cfg["vocab_size"]), hidden, layers, heads, int(cfg["intermediate_size"]), max_pos, float(cfg.get("rms_norm_eps", 1e-6)),
+                       pooling, min(int(max_seq or max_pos), max_pos), rotary_theta=theta, gated=True, causal=True, kv_heads=kv_heads,
+                       head_dim=hd)
+    return shape, weights
+
+
 def _load_local_dir(path: str):
     """(ModelShape, weights dict, tokenizer, pre_lower, normalize_module) from a sentence-transformers directory.
 
@@ -394,9 +462,17 @@ def _load_local_dir(path: str):
                  if pcfg.get("pooling_mode_" + m)]
         if modes == ["cls_token"]:
             pooling = "cls"
+        elif modes == ["lasttoken"] and cfg.get("model_type") == "qwen3":
+            pooling = "last"
         elif modes not in ([], ["mean_tokens"]):
-            raise NotImplementedError(f"pooling mode(s) {modes} are not supported (mean and CLS are)")
+            raise NotImplementedError(f"pooling mode(s) {modes} are not supported (mean and CLS are, and lasttoken for qwen3)")
     model_type = cfg.get("model_type", "bert")
+    if model_type == "qwen3":
+        if not os.path.exists(pc):      # a bare Qwen3Model: a causal embedder's sentence vector is its last token, never the mean
+            pooling = "last"
+        raw = load_file(os.path.join(tr_dir, "model.safetensors"))
+        shape, weights = _qwen3_shape_and_weights(cfg, raw, pooling, sbc_max_seq)
+        return shape, weights, tokenizer_from_model_dir(tr_dir), pre_lower, has_normalize
     if model_type == "nomic_bert":
         raw = load_file(os.path.join(tr_dir, "model.safetensors"))
         shape, weights = _nomic_shape_and_weights(cfg, raw, pooling, sbc_max_seq)
@@ -406,7 +482,7 @@ def _load_local_dir(path: str):
         shape, weights = _modernbert_shape_and_weights(cfg, raw, pooling, sbc_max_seq)
         return shape, weights, tokenizer_from_model_dir(tr_dir), pre_lower, has_normalize
     if model_type not in ("bert", "mpnet", "xlm-roberta"):
-        raise NotImplementedError(f"model_type '{model_type}' is not supported by this encoder (bert, mpnet and xlm-roberta are, and nomic_bert, modernbert)")
+        raise NotImplementedError(f"model_type '{model_type}' is not supported by this encoder (bert, mpnet and xlm-roberta are, and nomic_bert, modernbert, qwen3)")
     rel_buckets = pos_offset = 0
     if model_type == "mpnet":
         rel_buckets = int(cfg.get("relative_attention_num_buckets", 32))
@@ -428,7 +504,7 @@ def _load_local_dir(path: str):
 
 
 class EmbeddingModel:
-    """Sentence encoder wrapper (BERT, MPNet, XLM-RoBERTa, nomic-embed-text and ModernBERT checkpoints) running on the GPU."""
+    """Sentence encoder wrapper (BERT, MPNet, XLM-RoBERTa, nomic-embed-text, ModernBERT and Qwen3-Embedding checkpoints) running on the GPU."""
 
     def __init__(self, config: dict):
         self.tokenize_mode = config.get('tokenize', 'host')     # additive key: 'device' = csrc/wordpiece.hip feeds the encoder
@@ -448,6 +524,9 @@ class EmbeddingModel:
         self._device_tokenizer = None
         if self.tokenize_mode == 'device' and shape.prenorm:
             raise NotImplementedError("rag.embedding.tokenize 'device' is not supported for ModernBERT models: their byte-level BPE "
+                                      "tokeniser has no device kernel (use 'host')")
+        if self.tokenize_mode == 'device' and shape.causal:
+            raise NotImplementedError("rag.embedding.tokenize 'device' is not supported for Qwen3 models: their byte-level BPE "
                                       "tokeniser has no device kernel (use 'host')")
         if self.tokenize_mode == 'device':
             from rag._unigram import tokenizer_spec

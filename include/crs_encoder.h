@@ -200,6 +200,63 @@ int crs_encoder_forward_queries_prenorm(const crs_encoder_desc* d, const crs_enc
  * full-attention line is followed by the sliding layers' attention_window_kernel line. */
 int crs_encoder_prenorm_plan_describe(const crs_encoder_desc* d, int batch, int seq, int window, char* buf, size_t cap);
 
+/* Causal decoder-style embedders (Qwen3-Embedding; additive to ABI 3).
+ * CRS_ENC_RMSNORM: every norm is RMSNorm(v; g) = v / sqrt(mean(v^2) + ln_eps) * g in fp32 (no mean, no bias), and the embedding step has
+ * no norm: r = word_emb[id].  CRS_ENC_CAUSAL: query q attends the keys <= q (and < len); the heads are grouped -- desc.heads query
+ * heads of crs_encoder_causal.head_dim columns each (heads * head_dim need not be hidden), kv_heads key / value heads, heads %
+ * kv_heads == 0 -- and every Q and K head gets an RMSNorm over head_dim (gains g_q / g_k, fp32 [head_dim], shared by a layer's heads)
+ * before the rotation.  The two flags come together, with CRS_ENC_PRENORM, CRS_ENC_ROTARY and CRS_ENC_GATED_SILU, through the _causal
+ * entry points only; every other entry point refuses them.  Per layer, with r the fp32 residual stream:
+ *     q, k, v = x Wqkv^T                     x = RMSNorm(r; ln1_g); w_qkv fp16 [(Hq + 2 Hkv) hd, H]: query, key, value rows stacked
+ *     q_h = rope(RMSNorm_hd(q_h; g_q)),  k_h likewise with g_k          one qk_norm_rope launch, in place, one fp16 rounding
+ *     r += attention(q, k, v) Wo^T           w_o fp16 [H, Hq hd]; head h reads key / value head h / (Hq / Hkv)
+ *     r += (silu(y Wgate^T) * (y Wup^T)) Wdown^T,   y = RMSNorm(r; ln2_g)     w_up in CRS_ENC_GATED_SILU's interleaved layout
+ * hidden states = RMSNorm(r; final_g).  The layer struct is reused: ln1_g (non-NULL on EVERY layer, layer 0 included) and ln2_g are
+ * the two gains; every bias and ln1_b / ln2_b must be NULL; weights->pos_emb, type_emb, emb_ln_g and emb_ln_b are not read.
+ * Supported (head_dim, Hq / Hkv): {64, 128} x {1, 2}; hidden a multiple of 64 in [128, 1024].  desc.pooling may be CRS_POOL_LAST: the row of the last real token. */
+#define CRS_ENC_RMSNORM 32
+#define CRS_ENC_CAUSAL 64
+#define CRS_POOL_LAST 2   /* Qwen3-Embedding: hidden state of token max(len, 1) - 1; the _causal forwards only (crs_pool_f32 keeps its two modes) */
+
+typedef struct crs_encoder_causal {
+  int32_t kv_heads;              /* key / value heads; desc.heads % kv_heads == 0                                   */
+  int32_t head_dim;              /* 64 or 128                                                                       */
+  const float* rope_dev;         /* fp32 [positions, head_dim], crs_encoder_rope's layout                           */
+  int32_t positions;             /* rows of the table, >= seq                                                       */
+  const float* const* g_q;       /* HOST array of desc.layers device pointers, fp32 [head_dim]: the Q heads' gain   */
+  const float* const* g_k;       /* the same for the K heads                                                        */
+  const float* final_g;          /* [H] gain of the final norm                                                      */
+} crs_encoder_causal;
+
+/* crs_encoder_forward / crs_encoder_forward_queries for such descriptors (workspace: crs_encoder_causal_workspace_bytes).  CRS_EINVAL,
+ * with a message and before any launch: a descriptor without all five flags; a NULL causal, table, gain array, gain or final gain;
+ * positions < seq; a misaligned (16 bytes) table; heads % kv_heads != 0; a (head_dim, group) outside the supported set; a NULL ln1_g
+ * or ln2_g; a non-NULL bias. */
+int crs_encoder_causal_workspace_bytes(const crs_encoder_desc* d, const crs_encoder_causal* c, int batch, int seq, size_t* bytes);
+int crs_encoder_forward_causal(const crs_encoder_desc* d, const crs_encoder_weights* w, const int32_t* ids_dev,
+                               const int32_t* lens_dev, int batch, int seq, void* workspace_dev, size_t workspace_bytes,
+                               float* out_dev, int normalize, float* hidden_out_dev, void* stream, const crs_encoder_causal* c);
+int crs_encoder_forward_queries_causal(const crs_encoder_desc* d, const crs_encoder_weights* w, const int32_t* ids_dev,
+                                       const int32_t* lens_dev, int batch, int seq, void* workspace_dev, size_t workspace_bytes,
+                                       float* out_dev, void* q16_out_dev, int slab_type, void* stream, const crs_encoder_causal* c);
+/* The launches of such a forward (crs_encoder_plan_describe's form); kv_heads and head_dim are the only fields of c it reads. */
+int crs_encoder_causal_plan_describe(const crs_encoder_desc* d, const crs_encoder_causal* c, int batch, int seq, char* buf, size_t cap);
+
+/* Test-facing (additive to ABI 3): the three new steps on their own.
+ * crs_attention_causal_f16: ctx_dev fp16 [batch * seq, heads * head_dim] <- causal grouped-query attention of qkv_dev fp16
+ * [batch * seq, (heads + 2 kv_heads) * head_dim] (Q | K | V blocks) under lens_dev (clamped to [1, seq]): row q attends the keys
+ * < min(q + 1, len); a padding row (q >= len) is the attention over the real keys: finite.  CRS_EINVAL: a NULL or misaligned pointer,
+ * batch outside [1, 65535], seq < 1, heads % kv_heads != 0, an unsupported (head_dim, group).
+ * crs_qk_norm_rope_f16: the QK-norm + rotation of that buffer's Q and K blocks, in place; table_dev / positions as crs_encoder_rope,
+ * g_q_dev / g_k_dev fp32 [head_dim].  CRS_EINVAL: a NULL or misaligned pointer, head_dim not 64 / 128, positions < seq, sizes < 1.
+ * crs_add_rmsnorm_f32: crs_add_layernorm_f32's RMS form (no bias, no b). */
+int crs_attention_causal_f16(const void* qkv_dev, const int32_t* lens_dev, void* ctx_dev, int batch, int seq, int heads, int kv_heads,
+                             int head_dim, void* stream);
+int crs_qk_norm_rope_f16(void* qkv_dev, const float* table_dev, int positions, const float* g_q_dev, const float* g_k_dev, float eps,
+                         int batch, int seq, int heads, int kv_heads, int head_dim, void* stream);
+int crs_add_rmsnorm_f32(const float* y_dev, int nsplit, const float* residual_dev, const float* g_dev, float eps, int tokens, int hidden,
+                        float* r32_dev, void* x16_dev, float* n32_dev, void* stream);
+
 /* Test-facing (additive to ABI 3): the sliding-window attention step on its own,
  *   ctx[b, q, h*hd : (h+1)*hd] = softmax over {j : |j - q| <= window, j < len_b} of (Q K^T / sqrt(hd)) V
  * Arguments as crs_attention_f16 (no bias, no route).  Rows q < len are the attention output; a row q >= len is finite: the

@@ -22,7 +22,7 @@
 #include "../compressed-rag-suite_amd/csrc/enc_plan.h"
 
 static const char* const kFamily[] = {"None", "Tiled", "Panel", "Stream", "StreamKS", "Big", "Gemm8", "Gemm8SplitK"};
-static const char* const kAttn[] = {"Fused", "Blocked", "Short", "Seq", "Seq32", "Window"};
+static const char* const kAttn[] = {"Fused", "Blocked", "Short", "Seq", "Seq32", "Window", "Causal"};
 
 static void gemm_fields(const char* step, const crs::GemmPlan& g) {
   printf("%s=%s/%d/%d/%d/%d/%d/%d/%d/%d/%d %s_lds=%d %s_wgs=%ld ", step, kFamily[(int)g.family], g.slabs, g.tm, g.kc, g.kin, (int)g.persist,
@@ -93,6 +93,16 @@ int main(int argc, char** argv) {
       const crs::AttnPlan a = crs::plan_attention_window(batch, seq, hds, hid / hds, window, kn);
       printf("attn=%s attn_lds=%d attn_wgs=%ld ", kAttn[(int)a.form], a.d.lds, (long)a.d.gx * a.d.gy * a.d.gz);
       crs::attn_plan_describe(a, text, sizeof text);
+      text_out(text);
+      continue;
+    }
+    if (!strcmp(kind, "fwdc")) {   // fwdc hidden q_heads kv_heads head_dim ffn flags batch seq: make_causal_plan (Qwen3)
+      int hid, hq, hkv, hd, f, fl, batch, seq;
+      if (scanf("%d %d %d %d %d %d %d %d", &hid, &hq, &hkv, &hd, &f, &fl, &batch, &seq) != 8 || hkv < 1 || hq % hkv) return 2;
+      if (!crs::forms::attn_causal_supported(hd, hq / hkv)) return 2;
+      const crs::CausalPlan p = crs::make_causal_plan(hid, hq, hkv, hd, f, fl, batch, seq, cus, kn);
+      printf("total=%zu max_split=%d attn_lds=%d ", p.total, p.max_split, p.attn.d.lds);
+      if (crs::causal_plan_describe(p, text, sizeof text) >= (int)sizeof text) return 3;
       text_out(text);
       continue;
     }
