@@ -1,0 +1,35 @@
+// maxsim_scan.h -- the exact late-interaction sweep: limits and the plan of one crs_maxsim_topk call.  Plain C++ (no
+// HIP), so the planner (maxsim_scan_plan.cpp) and the kernel (maxsim_scan.hip) share one definition.
+//
+// A call scores every row of [row_first, row_first + row_count) of a token-vector CSR against nq queries by MaxSim and keeps the k
+// best per query.  Queries are served in groups of 8 (one 256-thread workgroup, two queries per wave); the rows are cut into items
+// of CRS_MAXSIM_SCAN_ITEM_ROWS consecutive rows and the G workgroups of a query group walk items w, w + G, w + 2 G, ...  Every
+// (workgroup, query) leaves a sorted list of kp pairs in the workspace, [G][nq][kp], and merge.hip reduces the G lists to k.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+namespace crs {
+
+constexpr int kMsScanGroupQ = 8;           // queries of a workgroup: two per wave
+constexpr int kMsScanThreads = 256;
+constexpr int kMsScanCus = 256;            // the CUs G is sized for (MI355X); a fixed number keeps the plan a pure function
+constexpr int kMsScanFill = 2;             // workgroups per CU over all query groups (one is resident: two 64 KB buffers at dimp 128)
+constexpr int64_t kMsScanMaxRows = ((int64_t)1 << 32) - 1;   // a list entry names its row by 32 bits relative to row_first
+
+struct MaxsimScanPlan {
+  int nq, lq_max, dimp, ksteps, k, kp;
+  int qgroups;          // ceil(nq / 8): gridDim.y
+  int64_t items;        // ceil(row_count / 64)
+  int g;                // workgroups per query group: gridDim.x, the merge's nlists
+  int lds_bytes;        // two window buffers of 256 tokens
+  size_t part_s, part_r, bytes;   // workspace actually used: scores fp32 [g][nq][kp] | rows int64 [g][nq][kp]
+};
+// returns 0, or -1 with *why naming the argument
+int maxsim_scan_make_plan(int nq, int lq_max, int dimp, int k, int64_t row_count, MaxsimScanPlan* p, const char** why);
+int maxsim_scan_plan_describe(const MaxsimScanPlan& p, char* buf, size_t cap);
+// An upper bound of plan.bytes that depends on (nq, k, row_count) alone and grows with each of them (g falls as nq grows, so the
+// exact size does not): lists = g nq <= min(items nq, 8 * kMsScanFill * kMsScanCus + nq).
+size_t maxsim_scan_workspace_bound(int nq, int k, int64_t row_count);
+
+}  // namespace crs

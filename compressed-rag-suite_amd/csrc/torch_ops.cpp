@@ -26,6 +26,7 @@
 //   crs::pairs_above / crs::pairs_verify   near-duplicate detection: thresholded self-join of the slab, fp32 check (new vs the reference)
 //   crs::mlm_sparse_pool / crs::sparse_compact / crs::sparse_topk   learned sparse retrieval (SPLADE): MLM head with max-pool epilogue, compaction, impact scan (new vs the reference)
 //   crs::token_project / crs::maxsim   late interaction (ColBERT): per-token projection and MaxSim scoring of candidate lists (new vs the reference)
+//   crs::maxsim_topk       exact late-interaction retrieval: one MaxSim sweep of the whole token index, top-k in the sweep (new vs the reference)
 //   crs::ivf_topk          top-k of the rows of per-query inverted lists of an fp16 slab: grouping + gathered MFMA probe (new vs the reference)
 //   crs::rerank_lexical    replaces the scoring, threshold and _rerank loops of retrieve_batch  (reference rag/retrieval.py:75-77, 196-217)
 // Tensors are torch-owned; every op launches on the CURRENT HIP stream of the tensors' device, so the ops
@@ -687,6 +688,35 @@ void maxsim(const Tensor& q16, const Tensor& q_len, const Tensor& tok16, int64_t
                 out.data_ptr<float>(), cur_stream(q16)), "crs::maxsim");
 }
 
+// the sweep of the whole token index (csrc/maxsim_scan.hip): q16, q_len, tok16, offsets as maxsim takes them; workspace uint8;
+// out_scores fp32 / out_rows int64 [nq, k]
+void maxsim_topk(const Tensor& q16, const Tensor& q_len, const Tensor& tok16, int64_t n_tokens, const Tensor& offsets, int64_t n_rows,
+                 int64_t row_first, int64_t row_count, int64_t k, Tensor workspace, Tensor out_scores, Tensor out_rows) {
+  want(q16, at::kHalf, "q16");
+  want(q_len, at::kInt, "q_len");
+  want(tok16, at::kHalf, "tok16");
+  want(offsets, at::kLong, "offsets");
+  want(workspace, at::kByte, "workspace");
+  want(out_scores, at::kFloat, "out_scores");
+  want(out_rows, at::kLong, "out_rows");
+  same_device(q16, {&q_len, &tok16, &offsets, &workspace, &out_scores, &out_rows}, "crs::maxsim_topk");
+  TORCH_CHECK(q16.dim() == 3 && q16.size(1) >= 1 && q16.size(1) <= CRS_MAXSIM_MAX_QUERY, "q16 must be fp16 [nq, lq_max <= 64, dimp]");
+  const int64_t nq = q16.size(0), dimp = q16.size(2);
+  TORCH_CHECK(nq <= 65535, "too many queries");
+  TORCH_CHECK(dimp == 32 || dimp == 64 || dimp == 96 || dimp == 128, "dimp must be 32, 64, 96 or 128");
+  TORCH_CHECK(k >= 1 && k <= CRS_MAX_K, "k must be in 1..64");
+  TORCH_CHECK(q_len.dim() == 1 && q_len.size(0) == nq, "q_len must be int32 [nq]");
+  TORCH_CHECK(tok16.dim() == 2 && tok16.size(1) == dimp && n_tokens >= 0 && n_tokens <= tok16.size(0), "tok16 must be fp16 [>= n_tokens, dimp]");
+  TORCH_CHECK(n_rows >= 0 && offsets.dim() == 1 && offsets.numel() >= n_rows + 1, "offsets must be int64 [>= n_rows + 1]");
+  TORCH_CHECK(out_scores.numel() == nq * k && out_rows.numel() == nq * k, "outputs must hold [nq, k]");
+  if (nq == 0) return;
+  c10::hip::HIPGuardMasqueradingAsCUDA g(q16.device());
+  ok(crs_maxsim_topk(q16.data_ptr(), q_len.data_ptr<int32_t>(), (int)nq, (int)q16.size(1), n_tokens ? tok16.data_ptr() : nullptr,
+                     offsets.data_ptr<int64_t>(), n_rows, n_tokens, row_first, row_count, (int)dimp, (int)k, workspace.data_ptr(),
+                     (size_t)workspace.numel(), out_scores.data_ptr<float>(), out_rows.data_ptr<int64_t>(), cur_stream(q16)),
+     "crs::maxsim_topk");
+}
+
 // ---- near-duplicate join (csrc/join.hip) ---------------------------------------------------------------------------
 // slab fp16 [>= n_rows, pdim]; pairs int64 [cap, 2], scores fp32 [cap]; count int64 [1], zeroed by the caller, receives the number
 // of qualifying pairs (count > cap: overflow)
@@ -1332,6 +1362,7 @@ TORCH_LIBRARY(crs, m) {
         "Tensor q_norm, int k, float threshold, Tensor(a!) order, Tensor(b!) count, Tensor(c!) sim, Tensor(d!) rr, Tensor(e!) reranked) -> ()");
   m.def("token_project(Tensor hidden, Tensor w16, Tensor? bias, Tensor dst, Tensor(a!) out16) -> ()");
   m.def("maxsim(Tensor q16, Tensor q_len, Tensor tok16, int n_tokens, Tensor offsets, int n_rows, Tensor rows, Tensor(a!) out) -> ()");
+  m.def("maxsim_topk(Tensor q16, Tensor q_len, Tensor tok16, int n_tokens, Tensor offsets, int n_rows, int row_first, int row_count, int k, Tensor(a!) workspace, Tensor(b!) out_scores, Tensor(c!) out_rows) -> ()");
   m.def("pairs_above_out(Tensor slab, int n_rows, int dim, int a_first, int a_rows, int b_first, int b_rows, float thr, "
         "Tensor(a!) pairs, Tensor(b!) scores, Tensor(c!) count) -> ()");
   m.def("pairs_verify_out(Tensor pairs, Tensor shadow, int n_rows, float thr, Tensor(a!) rows_a, Tensor(b!) rows_b, Tensor(c!) sims, "
@@ -1401,6 +1432,7 @@ TORCH_LIBRARY_IMPL(crs, CUDA, m) {   // the HIP backend of torch-ROCm dispatches
   m.impl("rerank_lexical", &rerank_lexical);
   m.impl("token_project", &token_project);
   m.impl("maxsim", &maxsim);
+  m.impl("maxsim_topk", &maxsim_topk);
   m.impl("pairs_above_out", &pairs_above_out);
   m.impl("pairs_verify_out", &pairs_verify_out);
   m.impl("bm25_topk", &bm25_topk);

@@ -84,6 +84,10 @@ _SIGNATURES = {
     "crs_token_project": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "crs_maxsim": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_int, c_void_p,
                            c_void_p]),
+    "crs_maxsim_topk_workspace_bytes": (c_int, [c_int, c_int, c_int64, POINTER(c_size_t)]),
+    "crs_maxsim_topk_plan_describe": (c_int, [c_int, c_int, c_int, c_int, c_int64, ctypes.c_char_p, c_size_t]),
+    "crs_maxsim_topk": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int,
+                                c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     "crs_pairs_above_f16": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, c_int64, c_float, c_void_p, c_void_p, c_int64,
                                     c_void_p, c_void_p]),
     "crs_pairs_verify_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -518,6 +522,40 @@ def maxsim(q16, q_len, tok16, n_tokens: int, offsets, n_rows: int, rows, out=Non
     with _translate():
         ops().maxsim(q16, q_len, tok16, int(n_tokens), offsets, int(n_rows), rows, out)
     return out
+
+
+MAXSIM_SCAN_WINDOW = 256      # CRS_MAXSIM_SCAN_WINDOW: tokens of one staged window of crs_maxsim_topk (csrc/maxsim_scan.hip)
+MAXSIM_SCAN_ITEM_ROWS = 64    # CRS_MAXSIM_SCAN_ITEM_ROWS: consecutive rows of one of its work items
+
+
+def maxsim_topk_workspace_bytes(nq: int, k: int, row_count: int) -> int:
+    b = c_size_t(0)
+    check(load().crs_maxsim_topk_workspace_bytes(int(nq), int(k), int(row_count), ctypes.byref(b)))
+    return int(b.value)
+
+
+def maxsim_topk_plan_describe(nq: int, lq_max: int, dimp: int, k: int, row_count: int) -> str:
+    """The plan line of a late-interaction sweep (no device needed)."""
+    buf = ctypes.create_string_buffer(256)
+    check(load().crs_maxsim_topk_plan_describe(int(nq), int(lq_max), int(dimp), int(k), int(row_count), buf, 256))
+    return buf.value.decode()
+
+
+def maxsim_topk(q16, q_len, tok16, n_tokens: int, offsets, n_rows: int, k: int, row_first: int = 0, row_count=None, workspace=None):
+    """The k best rows of [row_first, row_first + row_count) (default: every row) per query by MaxSim, in one sweep of the token
+    index (crs_maxsim_topk, csrc/maxsim_scan.hip): arguments as maxsim takes them, 1 <= k <= 64.  Returns (scores fp32 [nq, k], rows
+    int64 [nq, k]) sorted score desc / row asc, (-inf, -1) in missing slots; a returned score is bit for bit maxsim's for that pair.
+    Rows without tokens are never returned.  No host sync."""
+    import torch
+    nq = q16.shape[0]
+    row_count = int(n_rows) - int(row_first) if row_count is None else int(row_count)
+    out_s = torch.empty((nq, k), dtype=torch.float32, device=q16.device)
+    out_r = torch.empty((nq, k), dtype=torch.int64, device=q16.device)
+    if workspace is None:
+        workspace = torch.empty(maxsim_topk_workspace_bytes(nq, k, max(row_count, 0)), dtype=torch.uint8, device=q16.device)
+    with _translate():
+        ops().maxsim_topk(q16, q_len, tok16, int(n_tokens), offsets, int(n_rows), int(row_first), row_count, int(k), workspace, out_s, out_r)
+    return out_s, out_r
 
 
 def pairs_epsilon(row_err: float, pdim: int) -> float:

@@ -713,6 +713,15 @@ class SlabCollection:
             index.extend(self.documents, max_bytes)
         return index
 
+    def _late_topk(self, index: _TokenIndex, encoder, queries, k: int):
+        """(scores fp32 [nq, k], rows int64 [nq, k], q_len int32 [nq]) as numpy: one crs_maxsim_topk sweep of `index` (this
+        collection's _token_index) for the queries as `encoder` encodes them; one readback."""
+        import torch
+        with torch.cuda.device(index.device):
+            q16, q_len = encoder.encode_queries_device(queries)
+            s, r = nat.maxsim_topk(q16, q_len, index.tok16, index.n_tokens, index.offsets_dev, index.n_rows, k)
+            return s.cpu().numpy(), r.cpu().numpy(), q_len.cpu().numpy()
+
     def _sparse_index(self, encoder, max_terms: int, max_bytes: int) -> _SparseIndex:
         """The learned-sparse vectors of every row (see _SparseIndex), for `encoder`: built on first use, extended by the rows that
         arrived since, like _token_index; dropped by _drop_derived, and when another encoder or term cap asks."""
@@ -1873,6 +1882,31 @@ class VectorStore:
     def search_sparse_batch(self, queries: Sequence[str], top_k: int = 5) -> Dict[str, Any]:
         """search_lexical_batch for the learned-sparse list (sparse_rows): the same dict, 'scores' the sparse dot products."""
         return self._rows_dict(*self.sparse_rows(queries, top_k))
+
+    def late_rows(self, queries: Sequence[str], top_k: int):
+        """Exact late-interaction top-k of every query over the WHOLE collection, on the device (crs_maxsim_topk,
+        csrc/maxsim_scan.hip): queries [nq] strings -> (MaxSim scores fp32 [nq, top_k], sidecar rows int64 [nq, top_k], query
+        token counts int32 [nq]) as numpy, best first, ties by lower row, (-inf, -1) past the rows that hold a token.  The token
+        index is built or extended exactly as token_index() does (the same call, so what it refuses is refused here), the queries
+        are encoded by the attached LateInteractionReranker, and ONE launch sweeps every row; a score is bit for bit what
+        score_rows gives for that pair.  top_k above MAX_K is not implemented."""
+        if not isinstance(top_k, (int, np.integer)) or isinstance(top_k, bool) or top_k < 1:
+            raise ValueError(f"top_k must be a positive integer for a late-interaction search, got {top_k!r}")
+        if top_k > nat.MAX_K:
+            raise NotImplementedError(f"top_k > {nat.MAX_K} is not implemented for the late-interaction sweep, got top_k = {top_k}")
+        index = self.token_index()
+        queries = list(queries)
+        if not queries:
+            return np.zeros((0, top_k), np.float32), np.zeros((0, top_k), np.int64), np.zeros(0, np.int32)
+        return self.collection._late_topk(index, self._token_encoder, queries, int(top_k))
+
+    def search_late_batch(self, queries: Sequence[str], top_k: int = 5) -> Dict[str, Any]:
+        """search_lexical_batch for the late-interaction list (late_rows): the same dict, 'scores' the MaxSim sums, plus 'rows'
+        (the hits' sidecar rows)."""
+        sc, rh, _ = self.late_rows(queries, top_k)
+        out = self._rows_dict(sc, rh)
+        out['rows'] = [[r for r in rh[a].tolist() if r >= 0] for a in range(len(rh))]
+        return out
 
     def mmr_order(self, rows, rel, counts, lam: float):
         """Greedy MMR order of many result lists at once, on the device (crs_mmr_order, csrc/mmr.hip): rows int64 / rel fp64

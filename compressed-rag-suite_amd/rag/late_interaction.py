@@ -309,3 +309,12 @@ class LateInteractionReranker:
         with torch.cuda.device(dev):
             q16, q_len = self.encode_queries_device(queries)
             return nat.maxsim(q16, q_len, index.tok16, index.n_tokens, index.offsets_dev, index.n_rows, torch.from_numpy(rows).to(dev))
+
+    def search_rows(self, queries: Sequence[str], store, k: int):
+        """(scores fp32 [nq, k], sidecar rows int64 [nq, k], query token counts int32 [nq]) as numpy: the k best rows of the WHOLE
+        store per query by MaxSim, in ONE crs_maxsim_topk sweep of its token index (VectorStore.late_rows) -- the queries encoded
+        as score_rows encodes them, each score bit for bit what score_rows gives for that pair; (-inf, -1) past the rows that hold
+        a token."""
+        if store._token_encoder is not self:
+            store.attach_token_encoder(self)
+        return store.late_rows(queries, k)

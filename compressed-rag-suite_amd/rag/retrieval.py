@@ -101,6 +101,15 @@ class ContextRetriever:
             from rag.late_interaction import LateInteractionReranker
             self.late_interaction = LateInteractionReranker(config['late_interaction'])
             vector_store.attach_token_encoder(self.late_interaction)
+        # additive: where a late-interaction query takes its 2 * top_k candidates from.  'dense' (default): the dense search, then
+        # re-scored.  'scan': VectorStore.late_rows -- one exact MaxSim sweep of the whole token index (csrc/maxsim_scan.hip), so a
+        # chunk the dense stage would miss is found; the sweep's scores are crs_maxsim's, nothing is re-scored; rerank_score is the
+        # MaxSim sum and score = rerank_score / query tokens, the mean maximum in [-1, 1] (similarity_threshold applies to it,
+        # distance = 1 - score).  Only with rerank on, no filters, no hybrid and 2 * top_k <= 64: any other call takes 'dense'
+        li_cfg = config.get('late_interaction')
+        self.late_first_stage = li_cfg.get('first_stage', 'dense') if isinstance(li_cfg, dict) else 'dense'
+        if self.late_first_stage not in ('dense', 'scan'):
+            raise ValueError(f"late_interaction: first_stage must be 'dense' or 'scan', got {self.late_first_stage!r}")
         # additive: hybrid retrieval.  False (default) | True | {'rrf_k': 60, 'weights': [1, 1], 'k1': 1.5, 'b': 0.75}: retrieve_batch
         # fuses each thresholded dense list with the BM25 list of the same query over the whole collection (same `fetch`) by
         # weighted reciprocal rank fusion: fused = w_dense / (rrf_k + i + 1) + w_lex / (rrf_k + j + 1) over the 0-based ranks; 'score'
@@ -361,7 +370,10 @@ class ContextRetriever:
         on_device = (self.lexical_rerank == 'device' and bool(self.rerank) and self.distance_metric == 'cosine' and fetch <= 64
                      and ids_l is not None and hasattr(store, 'rerank_lexical') and cross is None and late is None and hybrid is None)
         host_pieces = 0
-        for piece in self._search_many(queries, fetch):      # one device batch at a time: its dicts are built while the next ones run
+        scan = late is not None and self.late_first_stage == 'scan' and hybrid is None and fetch <= 64 and hasattr(store, 'late_rows')
+        if scan:
+            per_query = self._late_scan_lists(queries, fetch, k, row_of)
+        for piece in (() if scan else self._search_many(queries, fetch)):      # one device batch at a time: its dicts are built while the next ones run
             piece_start = len(per_query)
             if hybrid is not None:
                 if isinstance(piece, dict):
@@ -652,6 +664,28 @@ class ContextRetriever:
             for c, v in zip(chunks, scores[i, :len(chunks)].tolist()):
                 c['rerank_score'] = v
             out.append(sorted(chunks, key=lambda c: c['rerank_score'], reverse=True)[:top_k])
+        return out
+
+    def _late_scan_lists(self, queries: List[str], fetch: int, top_k: int, row_of: Dict[int, int]) -> List[List[Dict]]:
+        """first_stage 'scan': the chunk lists of several queries straight from ONE sweep of the token index
+        (LateInteractionReranker.search_rows): the `fetch` best rows by MaxSim, best first; rerank_score = the MaxSim sum,
+        score = rerank_score / query tokens, distance = 1 - score; thresholded on score and cut to top_k."""
+        col = self.vector_store.collection
+        sc, rows, q_len = self.late_interaction.search_rows(queries, self.vector_store, fetch)
+        out = []
+        for a in range(len(queries)):
+            n_tok = max(int(q_len[a]), 1)
+            chunks = []
+            for r, v in zip(rows[a].tolist(), sc[a].astype(np.float64).tolist()):
+                if r < 0 or v / n_tok < self.similarity_threshold:
+                    continue
+                c = {'text': col.documents[r], 'score': v / n_tok, 'distance': 1.0 - v / n_tok,
+                     'metadata': col.metadatas[r] if col.metadatas else {}, 'chunk_id': col.ids[r], 'rerank_score': v}
+                row_of[id(c)] = r
+                chunks.append(c)
+            if not chunks:
+                logger.warning(f"No chunks passed similarity threshold of {self.similarity_threshold}")
+            out.append(chunks[:top_k])
         return out
 
     def _apply_diversity(self, chunks: List[Dict], vectors=None) -> List[Dict]:

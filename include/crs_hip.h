@@ -493,6 +493,29 @@ int crs_token_project(const float* hidden_dev, const void* w16_dev, const float*
 int crs_maxsim(const void* q16_dev, const int32_t* q_len_dev, int nq, int lq_max, const void* tok16_dev, const int64_t* offsets_dev,
                int64_t n_rows, int64_t n_tokens, const int64_t* rows_dev, int m_max, int dimp, float* out_dev, void* stream);
 
+/* ---- exact late-interaction retrieval: a MaxSim top-k sweep of the whole token index (additive to ABI 3; csrc/maxsim_scan.hip,
+ * DESIGN 3.22) ----
+ * crs_maxsim_topk scores EVERY row of [row_first, row_first + row_count) that holds at least one token against each of nq queries
+ * (q16_dev, q_len_dev, tok16_dev, offsets_dev as crs_maxsim takes them) and returns per query the k best:
+ *   out_scores_dev fp32 [nq, k], out_rows_dev int64 [nq, k]   score descending, ties by lower row; missing slots (-inf, -1)
+ * The score of a returned (query, row) is bit for bit crs_maxsim's for that pair.  Rows with no tokens are never returned; a query
+ * with q_len 0 gets (-inf, -1) in every slot; offsets are clamped into [0, n_tokens] and must not descend (a row whose end lies
+ * before its predecessor's is treated as empty).  row_count == 0 fills the outputs with (-inf, -1).
+ * Workspace: crs_maxsim_topk_workspace_bytes(nq, k, row_count), grows with each argument.  crs_maxsim_topk_plan_describe writes the
+ * plan's line and needs no device.
+ * Limits (CRS_EINVAL otherwise, with a message, before any HIP call): non-null pointers, q16_dev / tok16_dev / workspace_dev 16-byte
+ * aligned (tok16_dev may be null when n_tokens is 0); 1 <= lq_max <= CRS_MAXSIM_MAX_QUERY; dimp in {32, 64, 96, 128};
+ * 1 <= k <= CRS_MAX_K; 0 <= nq <= 65535 (0: no launch); row_first >= 0, row_count >= 0, row_first + row_count <= n_rows,
+ * row_count < 2^32; workspace_bytes at least the plan's.  No atomics, no host synchronisation. */
+#define CRS_MAXSIM_SCAN_WINDOW 256       /* tokens of one staged window (two LDS buffers of this many token rows) */
+#define CRS_MAXSIM_SCAN_ITEM_ROWS 64     /* consecutive rows of a work item (tests aim at the boundaries) */
+int crs_maxsim_topk_workspace_bytes(int nq, int k, int64_t row_count, size_t* bytes);
+int crs_maxsim_topk_plan_describe(int nq, int lq_max, int dimp, int k, int64_t row_count, char* buf, size_t cap);   /* no device */
+int crs_maxsim_topk(const void* q16_dev, const int32_t* q_len_dev, int nq, int lq_max, const void* tok16_dev,
+                    const int64_t* offsets_dev, int64_t n_rows, int64_t n_tokens, int64_t row_first, int64_t row_count,
+                    int dimp, int k, void* workspace_dev, size_t workspace_bytes,
+                    float* out_scores_dev, int64_t* out_rows_dev, void* stream);
+
 /* ---- learned sparse retrieval (SPLADE): compaction of a dense weight row, impact top-k over a weighted token CSR -- no reference
  * call site (additive to ABI 3; csrc/sparse_compact.hip, csrc/sparse_scan.hip; the head that produces the dense rows
  * is crs_mlm_sparse_pool, crs_encoder.h) ----

@@ -1,0 +1,144 @@
+#!/usr/bin/env python3
+"""Throughput of exact late-interaction retrieval (crs_maxsim_topk, csrc/maxsim_scan.hip).
+
+  python tools/bench_late_scan.py --out profiles/late_scan_bench.json
+
+  kernel      crs_maxsim_topk alone over a synthetic token index of --rows rows of 64..180 random unit tokens at dimp 128, k 10, for
+              nq in 8, 64, 256 and every query 16, 32 and 64 tokens long: milliseconds, the token bytes ONE query group streams per
+              second (index bytes / time: every group of 8 queries reads the whole index once), the bytes all groups read per
+              second, and the MFMA FLOP/s (2 x query tokens padded to 16 x index tokens x dimp), beside the copy bandwidth measured
+              on the same buffer (bytes read per second by tensor.copy_ of its first 4 GiB) and the 2.5 PFLOP/s fp16 peak DESIGN uses
+  retriever   ContextRetriever.retrieve_batch end to end over a store of --store-rows chunks under ``synthetic:colbert-minilm``,
+              first_stage 'dense' against 'scan': queries/s
+
+hipEvent spans after a warm-up, median of --reps spans, clocks as found.  A report, not a pass condition."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "compressed-rag-suite_amd")):
+    sys.path.insert(0, p)
+
+PEAK_FLOPS = 2.5e15
+WORDS = ("retrieval augmented generation answers questions from compressed documents with a vector index and an encoder on the device "
+         "while late interaction keeps one small vector per token of every chunk and scores a query token by token").split()
+
+
+def span_ms(fn, reps):
+    import torch
+    out = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        out.append(e0.elapsed_time(e1))
+    return {"median": round(statistics.median(out), 4), "min": round(min(out), 4), "max": round(max(out), 4)}
+
+
+def kernel(args, result):
+    import numpy as np
+    import torch
+    from rag import _native as nat
+    dev = torch.device("cuda", torch.cuda.current_device())
+    rng = np.random.default_rng(0)
+    dimp, k = 128, 10
+    lens = rng.integers(64, 181, args.rows)
+    offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)).to(dev)
+    n_tokens = int(lens.sum())
+    tok = torch.empty((n_tokens, dimp), dtype=torch.float16, device=dev)
+    for lo in range(0, n_tokens, 1 << 22):                                   # random unit rows, a slice at a time
+        x = torch.randn((min(1 << 22, n_tokens - lo), dimp), device=dev)
+        tok[lo:lo + x.shape[0]] = torch.nn.functional.normalize(x, dim=1).half()
+    index_bytes = n_tokens * dimp * 2
+    part = tok[: min(n_tokens, (4 << 30) // (dimp * 2))]
+    scratch = torch.empty_like(part)
+    scratch.copy_(part)
+    t = span_ms(lambda: scratch.copy_(part), args.reps)
+    del scratch
+    copy_gbps = part.numel() * 2 / (t["median"] * 1e-3) / 1e9
+    result["index"] = {"rows": args.rows, "tokens": n_tokens, "bytes": index_bytes, "dimp": dimp, "copy_read_gb_per_s": round(copy_gbps, 1)}
+    print(json.dumps({"index": result["index"]}), flush=True)
+    result["kernel"] = []
+    for nq in (8, 64, 256):
+        for lq in (16, 32, 64):
+            q16 = torch.nn.functional.normalize(torch.randn((nq, lq, dimp), device=dev), dim=2).half().contiguous()
+            q_len = torch.full((nq,), lq, dtype=torch.int32, device=dev)
+            ws = torch.empty(nat.maxsim_topk_workspace_bytes(nq, k, args.rows), dtype=torch.uint8, device=dev)
+            fn = lambda: nat.maxsim_topk(q16, q_len, tok, n_tokens, offsets, args.rows, k, workspace=ws)
+            fn()
+            t = span_ms(fn, args.reps)
+            sec, groups = t["median"] * 1e-3, (nq + 7) // 8
+            flops = 2.0 * nq * lq * n_tokens * dimp
+            result["kernel"].append({"nq": nq, "q_len": lq, "ms": t, "plan": nat.maxsim_topk_plan_describe(nq, lq, dimp, k, args.rows),
+                                     "gb_per_s_per_query_group": round(index_bytes / sec / 1e9, 1),
+                                     "gb_per_s_all_groups": round(groups * index_bytes / sec / 1e9, 1),
+                                     "copy_read_gb_per_s": round(copy_gbps, 1), "tflop_per_s": round(flops / sec / 1e12, 1),
+                                     "share_of_peak": round(flops / sec / PEAK_FLOPS, 4), "queries_per_s": round(nq / sec, 1)})
+            print(json.dumps(result["kernel"][-1]), flush=True)
+
+
+def retriever(args, result):
+    import numpy as np
+    import torch
+    from rag import RAGPipeline
+    from rag.chunking import Chunk
+
+    class Stub:
+        def generate(self, prompt, **kw):
+            return "n/a"
+    rng = np.random.default_rng(1)
+    texts = [" ".join(str(w) for w in rng.choice(WORDS, int(rng.integers(60, 181)))) + f" chunk{r}" for r in range(args.store_rows)]
+    queries = [" ".join(str(w) for w in rng.choice(WORDS, int(rng.integers(4, 13)))) for _ in range(args.queries)]
+    result["retriever"] = {"rows": args.store_rows, "queries": args.queries, "top_k": 10}
+    for stage in ("dense", "scan"):
+        p = RAGPipeline({"embedding": {"model_name": "synthetic:tiny", "device": "cuda", "batch_size": 256, "normalize": True},
+                         "vector_store": {"collection_name": "late-scan-bench-" + stage},
+                         "retrieval": {"top_k": 10, "rerank": True, "similarity_threshold": -1.0, "diversity_penalty": 0.0,
+                                       "late_interaction": {"model_name": "synthetic:colbert-minilm", "first_stage": stage}}})
+        p.setup(Stub())
+        chunks = [Chunk(text=t, chunk_id=f"c_{r}", start_char=0, end_char=1) for r, t in enumerate(texts)]
+        p.vector_store.create_index(chunks, p.embedding_model.embed_chunks_device(chunks))
+        p.vector_store.token_index()
+        p.retriever.retrieve_batch(queries)
+        spans = []
+        for _ in range(args.reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            p.retriever.retrieve_batch(queries)
+            torch.cuda.synchronize()
+            spans.append(time.perf_counter() - t0)
+        sec = statistics.median(spans)
+        result["retriever"][stage] = {"ms": round(sec * 1e3, 3), "queries_per_s": round(args.queries / sec, 1)}
+        print(json.dumps({stage: result["retriever"][stage]}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=1_000_000)
+    ap.add_argument("--store-rows", type=int, default=16384)
+    ap.add_argument("--queries", type=int, default=64)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--skip-retriever", action="store_true")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    from rag import _native as nat
+    nat.require_gpu()
+    result = {"device": torch.cuda.get_device_name(torch.cuda.current_device())}
+    kernel(args, result)
+    if not args.skip_retriever:
+        retriever(args, result)
+    if args.out:
+        with open(args.out, "w") as fh:
+            json.dump(result, fh, indent=1)
+            fh.write("\n")
+
+
+if __name__ == "__main__":
+    main()
