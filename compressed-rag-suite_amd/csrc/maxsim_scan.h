@@ -32,4 +32,14 @@ int maxsim_scan_plan_describe(const MaxsimScanPlan& p, char* buf, size_t cap);
 // exact size does not): lists = g nq <= min(items nq, 8 * kMsScanFill * kMsScanCus + nq).
 size_t maxsim_scan_workspace_bound(int nq, int k, int64_t row_count);
 
+// ---- the same sweep over an fp8 (e4m3) token index (crs_maxsim_topk_f8, maxsim_scan_f8.hip).  The rows are decoded
+// to fp16 in registers (maxsim_f8.h), so a query's A fragments take what they take in fp16 and a wave keeps two queries, as the
+// fp16 sweep does: 237 VGPRs at dimp 128, no scratch.  A window buffer is 256 rows of dimp BYTES, two of them 64 KB at dimp 128,
+// so TWO workgroups share a CU where the fp16 sweep has one.  The plan has the same fields.
+constexpr int kMsF8WaveQ = 2;                              // queries resident per wave
+constexpr int kMsF8GroupQ = 4 * kMsF8WaveQ;                // queries of a workgroup
+int maxsim_scan_f8_make_plan(int nq, int lq_max, int dimp, int k, int64_t row_count, MaxsimScanPlan* p, const char** why);
+int maxsim_scan_f8_plan_describe(const MaxsimScanPlan& p, char* buf, size_t cap);
+size_t maxsim_scan_f8_workspace_bound(int nq, int k, int64_t row_count);
+
 }  // namespace crs

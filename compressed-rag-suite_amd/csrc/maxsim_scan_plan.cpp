@@ -10,7 +10,9 @@ namespace crs {
 static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 static int kp_of(int k) { return k <= 32 ? 32 : 64; }
 
-int maxsim_scan_make_plan(int nq, int lq_max, int dimp, int k, int64_t row_count, MaxsimScanPlan* p, const char** why) {
+// group_q queries per workgroup, elem_bytes per coordinate of a staged token row
+static int make_plan(int group_q, int elem_bytes, int nq, int lq_max, int dimp, int k, int64_t row_count, MaxsimScanPlan* p,
+                     const char** why) {
   if (lq_max < 1 || lq_max > CRS_MAXSIM_MAX_QUERY) { *why = "lq_max must be in 1..CRS_MAXSIM_MAX_QUERY"; return -1; }
   if (dimp != 32 && dimp != 64 && dimp != 96 && dimp != 128) { *why = "dimp must be 32, 64, 96 or 128"; return -1; }
   if (k < 1 || k > CRS_MAX_K) { *why = "k must be in 1..CRS_MAX_K"; return -1; }
@@ -22,16 +24,30 @@ int maxsim_scan_make_plan(int nq, int lq_max, int dimp, int k, int64_t row_count
   p->ksteps = dimp / 32;
   p->k = k;
   p->kp = kp_of(k);
-  p->qgroups = (nq + kMsScanGroupQ - 1) / kMsScanGroupQ;
+  p->qgroups = (nq + group_q - 1) / group_q;
   p->items = (row_count + CRS_MAXSIM_SCAN_ITEM_ROWS - 1) / CRS_MAXSIM_SCAN_ITEM_ROWS;
   const int want = p->qgroups ? (kMsScanFill * kMsScanCus + p->qgroups - 1) / p->qgroups : 1;
   p->g = (int)(p->items < want ? p->items : want);
-  p->lds_bytes = 2 * CRS_MAXSIM_SCAN_WINDOW * dimp * 2;
+  p->lds_bytes = 2 * CRS_MAXSIM_SCAN_WINDOW * dimp * elem_bytes;
   const size_t lists = (size_t)p->g * nq;
   p->part_s = 0;
   p->part_r = up256(lists * p->kp * 4);
   p->bytes = p->part_r + up256(lists * p->kp * 8);
   return 0;
+}
+
+static size_t workspace_bound(int group_q, int nq, int k, int64_t row_count) {
+  const size_t items = (size_t)((row_count + CRS_MAXSIM_SCAN_ITEM_ROWS - 1) / CRS_MAXSIM_SCAN_ITEM_ROWS);
+  const size_t a = items * (size_t)nq, b = (size_t)group_q * kMsScanFill * kMsScanCus + (size_t)nq;
+  const size_t lists = a < b ? a : b;
+  return up256(lists * kp_of(k) * 4) + up256(lists * kp_of(k) * 8) + 256;
+}
+
+int maxsim_scan_make_plan(int nq, int lq_max, int dimp, int k, int64_t row_count, MaxsimScanPlan* p, const char** why) {
+  return make_plan(kMsScanGroupQ, 2, nq, lq_max, dimp, k, row_count, p, why);
+}
+int maxsim_scan_f8_make_plan(int nq, int lq_max, int dimp, int k, int64_t row_count, MaxsimScanPlan* p, const char** why) {
+  return make_plan(kMsF8GroupQ, 1, nq, lq_max, dimp, k, row_count, p, why);
 }
 
 int maxsim_scan_plan_describe(const MaxsimScanPlan& p, char* buf, size_t cap) {
@@ -40,11 +56,13 @@ int maxsim_scan_plan_describe(const MaxsimScanPlan& p, char* buf, size_t cap) {
                   p.lds_bytes, p.g);
 }
 
-size_t maxsim_scan_workspace_bound(int nq, int k, int64_t row_count) {
-  const size_t items = (size_t)((row_count + CRS_MAXSIM_SCAN_ITEM_ROWS - 1) / CRS_MAXSIM_SCAN_ITEM_ROWS);
-  const size_t a = items * (size_t)nq, b = (size_t)kMsScanGroupQ * kMsScanFill * kMsScanCus + (size_t)nq;
-  const size_t lists = a < b ? a : b;
-  return up256(lists * kp_of(k) * 4) + up256(lists * kp_of(k) * 8) + 256;
+int maxsim_scan_f8_plan_describe(const MaxsimScanPlan& p, char* buf, size_t cap) {
+  return snprintf(buf, cap, "maxsim_scan_f8<dimp=%d> grid=%dx%d threads=%d queries/wave=%d window=%d item_rows=%d items=%lld kp=%d lds=%d + merge x1 (nlists=%d)",
+                  p.dimp, p.g, p.qgroups, kMsScanThreads, kMsF8WaveQ, CRS_MAXSIM_SCAN_WINDOW, CRS_MAXSIM_SCAN_ITEM_ROWS,
+                  (long long)p.items, p.kp, p.lds_bytes, p.g);
 }
+
+size_t maxsim_scan_workspace_bound(int nq, int k, int64_t row_count) { return workspace_bound(kMsScanGroupQ, nq, k, row_count); }
+size_t maxsim_scan_f8_workspace_bound(int nq, int k, int64_t row_count) { return workspace_bound(kMsF8GroupQ, nq, k, row_count); }
 
 }  // namespace crs

@@ -133,9 +133,15 @@ int token_match_launch(const float* a, const int* len_a, int seq_a, const float*
 // maxsim.hip: late-interaction scores of [nq, m_max] candidate rows over a token-vector CSR, one wave per pair; -1 = bad dimp
 int maxsim_launch(const void* q16, const int* q_len, int nq, int lq_max, const void* tok16, const int64_t* offsets, int64_t n_rows,
                   int64_t n_tokens, const int64_t* rows, int m_max, int dimp, float* out, hipStream_t stream);
+// maxsim_f8.hip: the same over uint8 e4m3 rows of dimp bytes (q8, tok8), decoded to fp16 in registers; -1 = bad dimp
+int maxsim_f8_launch(const void* q8, const int* q_len, int nq, int lq_max, const void* tok8, const int64_t* offsets, int64_t n_rows,
+                     int64_t n_tokens, const int64_t* rows, int m_max, int dimp, float* out, hipStream_t stream);
 // token_project.hip: hidden states -> packed unit-length fp16 token vectors, one wave per 16 tokens; -1 = bad dim
 int token_project_launch(const float* hidden, const void* w16, const float* bias, const int64_t* dst, void* out16, int64_t n_tok,
                          int H, int dim, hipStream_t stream);
+// token_project_f8.hip: the same kernel (token_project.h) writing e4m3 codes of the unit vector times 2^S, dimp bytes a token
+int token_project_f8_launch(const float* hidden, const void* w16, const float* bias, const int64_t* dst, void* out8, int64_t n_tok,
+                            int H, int dim, hipStream_t stream);
 
 // join.hip: thresholded self-join of an fp16 slab (pairs i < j with slab score >= thr, 256 x 256 tiles) and the fp32 check of its
 // candidates against the shadow, a quarter wave per pair

@@ -21,6 +21,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "e4m3.h"
 #include "mxfp4.h"
 #include "scan.h"
 #include "scan_common.h"
@@ -34,18 +35,7 @@ typedef int v8i __attribute__((ext_vector_type(8)));
 
 // ---------------------------------------------------------------- query prologue: fp32 -> MX e4m3 in B-operand lane order
 // One wave per query slot of the 16-query groups; slots past nq are zeroed (their columns of D are never read).
-// e4m3 code of y >= 0: round to nearest even on the float's bits, subnormals (below 2^-6) in steps of 2^-9, saturating at 448.
-__device__ __forceinline__ unsigned e4m3_code(float y) {
-  unsigned code;
-  if (y < 0.015625f) {
-    code = (unsigned)rintf(y * 512.0f);
-  } else {
-    const unsigned b = __float_as_uint(y);
-    code = ((b + 0x7ffffu + ((b >> 20) & 1u)) >> 20) - (120u << 3);
-  }
-  return code > 0x7eu ? 0x7eu : code;
-}
-
+// (e4m3_code: e4m3.h)
 __global__ __launch_bounds__(256) void mx_queries_kernel(const float* __restrict__ q, int nq, int dim, int pdim, uint8_t* __restrict__ qop,
                                                          uint8_t* __restrict__ qsc) {
   const int lane = threadIdx.x & 63;

@@ -1,4 +1,5 @@
-// token_project.hip -- hidden states to packed unit-length fp16 token vectors (gfx950): crs_token_project.
+// token_project.hip -- hidden states to packed unit-length fp16 token vectors (gfx950): crs_token_project.  The
+// kernel itself is in token_project.h, which token_project_f8.hip instantiates for the fp8 token index.
 //
 // The index-time half of late interaction: for every token with dst >= 0, v = W h (+ b), y = v / |v| (0 when |v| is 0), written as
 // fp16 to row dst of the token array, zeros in [dim, dimp).  A row-complete MFMA tile, as enc_rowln.hip's: one wave owns 16 tokens
@@ -17,6 +18,8 @@
 //   Epilogue: accumulator register e of lane (c = lane & 15, g = lane >> 4), tile j is column 16 j + c of token 4 g + e.  Bias in
 //     fp32, squares summed over the lane's tiles in j order, then an xor butterfly over the 16 lanes of the row; 1 / sqrt in fp32;
 //     the scaled value is rounded to fp16 once.  The 16 lanes of a row store 32 contiguous bytes per tile.
+//   F8: the same kernel up to the last rounding -- y 2^S (an exact scaling) is encoded as e4m3 instead of fp16, one byte per
+//     (token, column): the 16 lanes of a row store 16 contiguous bytes per tile, zeros (code 0) in [dim, dimp).
 // A token's arithmetic involves its own row of A alone: its output does not depend on what else is in the launch.  No scratch, no
 // LDS, no atomics.
 #include "../../include/crs_hip.h"
@@ -24,86 +27,17 @@
 #include <hip/hip_runtime.h>
 
 #include "scan.h"
+#include "token_project.h"
 
 namespace crs {
-namespace {
-
-typedef _Float16 tp_f16x8 __attribute__((ext_vector_type(8)));
-typedef float tp_f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kTpThreads = 256;
-
-template <int NJ>   // column tiles of 16: dimp = 16 NJ
-__global__ __launch_bounds__(kTpThreads) void token_project_kernel(const float* __restrict__ hidden, const _Float16* __restrict__ w16,
-                                                                   const float* __restrict__ bias, const long long* __restrict__ dst,
-                                                                   _Float16* __restrict__ out16, long long n_tok, int H, int dim) {
-  constexpr int kDimp = 16 * NJ;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int r = lane & 15, h = lane >> 4;
-  const long long tok0 = (long long)blockIdx.x * 64 + wave * 16;
-  if (tok0 >= n_tok) return;                                // (wave-uniform)
-
-  const long long tok = tok0 + r;
-  const bool live = tok < n_tok && dst[tok] >= 0;
-  const float* hrow = hidden + (size_t)(live ? tok : 0) * H + 8 * h;
-  const _Float16* wrow = w16 + 8 * h;
-
-  tp_f32x4 acc[NJ];
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) acc[j] = tp_f32x4{0.f, 0.f, 0.f, 0.f};
-
-  for (int k0 = 0; k0 < H; k0 += 32) {
-    tp_f16x8 af = tp_f16x8{0, 0, 0, 0, 0, 0, 0, 0};
-    if (live) {
-      const tp_f32x4 lo = *reinterpret_cast<const tp_f32x4*>(hrow + k0), hi = *reinterpret_cast<const tp_f32x4*>(hrow + k0 + 4);
-      af = tp_f16x8{(_Float16)lo[0], (_Float16)lo[1], (_Float16)lo[2], (_Float16)lo[3],
-                    (_Float16)hi[0], (_Float16)hi[1], (_Float16)hi[2], (_Float16)hi[3]};
-    }
-    tp_f16x8 bf[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      bf[j] = tp_f16x8{0, 0, 0, 0, 0, 0, 0, 0};
-      if (16 * j + r < dim) bf[j] = *reinterpret_cast<const tp_f16x8*>(wrow + (size_t)(16 * j + r) * H + k0);
-    }
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf[j], acc[j], 0, 0, 0);
-  }
-
-  // ---- epilogue: bias, row norm, scale, store
-  float bj[NJ];
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) bj[j] = (bias && 16 * j + r < dim) ? bias[16 * j + r] : 0.f;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    float ss = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      acc[j][e] += bj[j];
-      ss = fmaf(acc[j][e], acc[j][e], ss);
-    }
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
-    const float inv = ss > 0.f ? 1.f / sqrtf(ss) : 0.f;
-    const long long t = tok0 + 4 * h + e;
-    const long long d = t < n_tok ? dst[t] : -1;
-    if (d >= 0) {
-      _Float16* o16 = out16 + (size_t)d * kDimp + r;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) o16[16 * j] = (_Float16)(acc[j][e] * inv);
-    }
-  }
-}
-
-}  // namespace
 
 int token_project_launch(const float* hidden, const void* w16, const float* bias, const int64_t* dst, void* out16, int64_t n_tok,
                          int H, int dim, hipStream_t stream) {
   const int dimp = (dim + 31) / 32 * 32;
   const dim3 grid((unsigned)((n_tok + 63) / 64)), block(kTpThreads);
 #define CRS_TP_LAUNCH(NJ)                                                                                                          \
-  hipLaunchKernelGGL(token_project_kernel<NJ>, grid, block, 0, stream, hidden, static_cast<const _Float16*>(w16), bias,            \
-                     reinterpret_cast<const long long*>(dst), static_cast<_Float16*>(out16), (long long)n_tok, H, dim)
+  hipLaunchKernelGGL((token_project_kernel<NJ, false>), grid, block, 0, stream, hidden, static_cast<const _Float16*>(w16), bias,   \
+                     reinterpret_cast<const long long*>(dst), out16, (long long)n_tok, H, dim)
   switch (dimp) {
     case 32: CRS_TP_LAUNCH(2); break;
     case 64: CRS_TP_LAUNCH(4); break;

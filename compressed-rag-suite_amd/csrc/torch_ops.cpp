@@ -26,6 +26,7 @@
 //   crs::pairs_above / crs::pairs_verify   near-duplicate detection: thresholded self-join of the slab, fp32 check (new vs the reference)
 //   crs::mlm_sparse_pool / crs::sparse_compact / crs::sparse_topk   learned sparse retrieval (SPLADE): MLM head with max-pool epilogue, compaction, impact scan (new vs the reference)
 //   crs::token_project / crs::maxsim   late interaction (ColBERT): per-token projection and MaxSim scoring of candidate lists (new vs the reference)
+//   crs::token_project_f8 / crs::maxsim_f8 / crs::maxsim_topk_f8   the same three over an fp8 (e4m3) token index (new vs the reference)
 //   crs::maxsim_topk       exact late-interaction retrieval: one MaxSim sweep of the whole token index, top-k in the sweep (new vs the reference)
 //   crs::ivf_topk          top-k of the rows of per-query inverted lists of an fp16 slab: grouping + gathered MFMA probe (new vs the reference)
 //   crs::rerank_lexical    replaces the scoring, threshold and _rerank loops of retrieve_batch  (reference rag/retrieval.py:75-77, 196-217)
@@ -642,79 +643,109 @@ void rerank_lexical(const Tensor& scores, const Tensor& rows, const Tensor& doc_
 // ---- late interaction (csrc/token_project.hip, csrc/maxsim.hip) ------------------------------------------------------
 // hidden fp32 [n_tok, H]; w16 fp16 [dim, H]; bias fp32 [dim] (optional); dst int64 [n_tok], < 0 = drop, else a row of out16 (the
 // caller builds it on the host and keeps it below out16's rows); out16 fp16 [rows, dim rounded up to 32]
-void token_project(const Tensor& hidden, const Tensor& w16, c10::optional<Tensor> bias, const Tensor& dst, Tensor out16) {
+// (f8: out16 is the uint8 [rows, dimp] array of e4m3 codes instead, crs_token_project_f8)
+static void token_project_any(const Tensor& hidden, const Tensor& w16, c10::optional<Tensor> bias, const Tensor& dst, Tensor out16, bool f8) {
   want(hidden, at::kFloat, "hidden");
   want(w16, at::kHalf, "w16");
   want(dst, at::kLong, "dst");
-  want(out16, at::kHalf, "out16");
+  want(out16, f8 ? at::kByte : at::kHalf, f8 ? "out8" : "out16");
   if (has(bias)) want(*bias, at::kFloat, "bias");
   same_device(hidden, {&w16, opt_t(bias), &dst, &out16}, "crs::token_project");
   TORCH_CHECK(hidden.dim() == 2 && w16.dim() == 2 && w16.size(1) == hidden.size(1), "hidden must be fp32 [n_tok, H] and w16 fp16 [dim, H]");
   const int64_t n_tok = hidden.size(0), H = hidden.size(1), dim = w16.size(0);
   TORCH_CHECK(dim >= 1 && dim <= 128 && H <= 1024, "dim must be in 1..128 and H at most 1024");
   TORCH_CHECK(dst.dim() == 1 && dst.size(0) == n_tok, "dst must be int64 [n_tok]");
-  TORCH_CHECK(out16.dim() == 2 && out16.size(1) == (dim + 31) / 32 * 32, "out16 must be fp16 [rows, dim rounded up to 32]");
+  TORCH_CHECK(out16.dim() == 2 && out16.size(1) == (dim + 31) / 32 * 32, "the output must be [rows, dim rounded up to 32]");
   if (has(bias)) TORCH_CHECK(bias->numel() == dim, "bias must be fp32 [dim]");
   if (n_tok == 0) return;
   c10::hip::HIPGuardMasqueradingAsCUDA g(hidden.device());
-  ok(crs_token_project(hidden.data_ptr<float>(), w16.data_ptr(), (const float*)opt_ptr(bias), dst.data_ptr<int64_t>(), out16.data_ptr(),
-                       n_tok, (int)H, (int)dim, cur_stream(hidden)), "crs::token_project");
+  ok((f8 ? crs_token_project_f8 : crs_token_project)(hidden.data_ptr<float>(), w16.data_ptr(), (const float*)opt_ptr(bias),
+                                                      dst.data_ptr<int64_t>(), out16.data_ptr(), n_tok, (int)H, (int)dim,
+                                                      cur_stream(hidden)), f8 ? "crs::token_project_f8" : "crs::token_project");
+}
+void token_project(const Tensor& hidden, const Tensor& w16, c10::optional<Tensor> bias, const Tensor& dst, Tensor out16) {
+  token_project_any(hidden, w16, bias, dst, out16, false);
+}
+void token_project_f8(const Tensor& hidden, const Tensor& w16, c10::optional<Tensor> bias, const Tensor& dst, Tensor out8) {
+  token_project_any(hidden, w16, bias, dst, out8, true);
 }
 
 // q16 fp16 [nq, lq_max, dimp]; q_len int32 [nq]; tok16 fp16 [>= n_tokens, dimp]; offsets int64 [>= n_rows + 1]; rows int64 /
 // out fp32 [nq, m_max]
-void maxsim(const Tensor& q16, const Tensor& q_len, const Tensor& tok16, int64_t n_tokens, const Tensor& offsets, int64_t n_rows,
-            const Tensor& rows, Tensor out) {
-  want(q16, at::kHalf, "q16");
+// (f8: q16 / tok16 are the uint8 e4m3 arrays of the same shapes instead, crs_maxsim_f8)
+static void maxsim_any(const Tensor& q16, const Tensor& q_len, const Tensor& tok16, int64_t n_tokens, const Tensor& offsets, int64_t n_rows,
+                       const Tensor& rows, Tensor out, bool f8) {
+  want(q16, f8 ? at::kByte : at::kHalf, f8 ? "q8" : "q16");
   want(q_len, at::kInt, "q_len");
-  want(tok16, at::kHalf, "tok16");
+  want(tok16, f8 ? at::kByte : at::kHalf, f8 ? "tok8" : "tok16");
   want(offsets, at::kLong, "offsets");
   want(rows, at::kLong, "rows");
   want(out, at::kFloat, "out");
   same_device(q16, {&q_len, &tok16, &offsets, &rows, &out}, "crs::maxsim");
-  TORCH_CHECK(q16.dim() == 3 && q16.size(1) >= 1 && q16.size(1) <= CRS_MAXSIM_MAX_QUERY, "q16 must be fp16 [nq, lq_max <= 64, dimp]");
+  TORCH_CHECK(q16.dim() == 3 && q16.size(1) >= 1 && q16.size(1) <= CRS_MAXSIM_MAX_QUERY, "the queries must be [nq, lq_max <= 64, dimp]");
   const int64_t nq = q16.size(0), dimp = q16.size(2);
   TORCH_CHECK(nq <= 65535, "too many queries");
   TORCH_CHECK(dimp == 32 || dimp == 64 || dimp == 96 || dimp == 128, "dimp must be 32, 64, 96 or 128");
   TORCH_CHECK(q_len.dim() == 1 && q_len.size(0) == nq, "q_len must be int32 [nq]");
-  TORCH_CHECK(tok16.dim() == 2 && tok16.size(1) == dimp && n_tokens >= 0 && n_tokens <= tok16.size(0), "tok16 must be fp16 [>= n_tokens, dimp]");
+  TORCH_CHECK(tok16.dim() == 2 && tok16.size(1) == dimp && n_tokens >= 0 && n_tokens <= tok16.size(0), "the tokens must be [>= n_tokens, dimp]");
   TORCH_CHECK(n_rows >= 0 && offsets.dim() == 1 && offsets.numel() >= n_rows + 1, "offsets must be int64 [>= n_rows + 1]");
   TORCH_CHECK(rows.dim() == 2 && rows.size(0) == nq && rows.size(1) >= 1 && rows.size(1) <= 0x7fffffff && out.sizes() == rows.sizes(),
               "rows / out must be [nq, m_max >= 1]");
   if (nq == 0) return;
   c10::hip::HIPGuardMasqueradingAsCUDA g(q16.device());
-  ok(crs_maxsim(q16.data_ptr(), q_len.data_ptr<int32_t>(), (int)nq, (int)q16.size(1), n_tokens ? tok16.data_ptr() : nullptr,
-                offsets.data_ptr<int64_t>(), n_rows, n_tokens, rows.data_ptr<int64_t>(), (int)rows.size(1), (int)dimp,
-                out.data_ptr<float>(), cur_stream(q16)), "crs::maxsim");
+  ok((f8 ? crs_maxsim_f8 : crs_maxsim)(q16.data_ptr(), q_len.data_ptr<int32_t>(), (int)nq, (int)q16.size(1),
+                                        n_tokens ? tok16.data_ptr() : nullptr, offsets.data_ptr<int64_t>(), n_rows, n_tokens,
+                                        rows.data_ptr<int64_t>(), (int)rows.size(1), (int)dimp, out.data_ptr<float>(), cur_stream(q16)),
+     f8 ? "crs::maxsim_f8" : "crs::maxsim");
+}
+void maxsim(const Tensor& q16, const Tensor& q_len, const Tensor& tok16, int64_t n_tokens, const Tensor& offsets, int64_t n_rows,
+            const Tensor& rows, Tensor out) {
+  maxsim_any(q16, q_len, tok16, n_tokens, offsets, n_rows, rows, out, false);
+}
+void maxsim_f8(const Tensor& q8, const Tensor& q_len, const Tensor& tok8, int64_t n_tokens, const Tensor& offsets, int64_t n_rows,
+               const Tensor& rows, Tensor out) {
+  maxsim_any(q8, q_len, tok8, n_tokens, offsets, n_rows, rows, out, true);
 }
 
 // the sweep of the whole token index (csrc/maxsim_scan.hip): q16, q_len, tok16, offsets as maxsim takes them; workspace uint8;
 // out_scores fp32 / out_rows int64 [nq, k]
-void maxsim_topk(const Tensor& q16, const Tensor& q_len, const Tensor& tok16, int64_t n_tokens, const Tensor& offsets, int64_t n_rows,
-                 int64_t row_first, int64_t row_count, int64_t k, Tensor workspace, Tensor out_scores, Tensor out_rows) {
-  want(q16, at::kHalf, "q16");
+// (f8: q16 / tok16 are the uint8 e4m3 arrays instead, crs_maxsim_topk_f8, csrc/maxsim_scan_f8.hip)
+static void maxsim_topk_any(const Tensor& q16, const Tensor& q_len, const Tensor& tok16, int64_t n_tokens, const Tensor& offsets,
+                            int64_t n_rows, int64_t row_first, int64_t row_count, int64_t k, Tensor workspace, Tensor out_scores,
+                            Tensor out_rows, bool f8) {
+  want(q16, f8 ? at::kByte : at::kHalf, f8 ? "q8" : "q16");
   want(q_len, at::kInt, "q_len");
-  want(tok16, at::kHalf, "tok16");
+  want(tok16, f8 ? at::kByte : at::kHalf, f8 ? "tok8" : "tok16");
   want(offsets, at::kLong, "offsets");
   want(workspace, at::kByte, "workspace");
   want(out_scores, at::kFloat, "out_scores");
   want(out_rows, at::kLong, "out_rows");
   same_device(q16, {&q_len, &tok16, &offsets, &workspace, &out_scores, &out_rows}, "crs::maxsim_topk");
-  TORCH_CHECK(q16.dim() == 3 && q16.size(1) >= 1 && q16.size(1) <= CRS_MAXSIM_MAX_QUERY, "q16 must be fp16 [nq, lq_max <= 64, dimp]");
+  TORCH_CHECK(q16.dim() == 3 && q16.size(1) >= 1 && q16.size(1) <= CRS_MAXSIM_MAX_QUERY, "the queries must be [nq, lq_max <= 64, dimp]");
   const int64_t nq = q16.size(0), dimp = q16.size(2);
   TORCH_CHECK(nq <= 65535, "too many queries");
   TORCH_CHECK(dimp == 32 || dimp == 64 || dimp == 96 || dimp == 128, "dimp must be 32, 64, 96 or 128");
   TORCH_CHECK(k >= 1 && k <= CRS_MAX_K, "k must be in 1..64");
   TORCH_CHECK(q_len.dim() == 1 && q_len.size(0) == nq, "q_len must be int32 [nq]");
-  TORCH_CHECK(tok16.dim() == 2 && tok16.size(1) == dimp && n_tokens >= 0 && n_tokens <= tok16.size(0), "tok16 must be fp16 [>= n_tokens, dimp]");
+  TORCH_CHECK(tok16.dim() == 2 && tok16.size(1) == dimp && n_tokens >= 0 && n_tokens <= tok16.size(0), "the tokens must be [>= n_tokens, dimp]");
   TORCH_CHECK(n_rows >= 0 && offsets.dim() == 1 && offsets.numel() >= n_rows + 1, "offsets must be int64 [>= n_rows + 1]");
   TORCH_CHECK(out_scores.numel() == nq * k && out_rows.numel() == nq * k, "outputs must hold [nq, k]");
   if (nq == 0) return;
   c10::hip::HIPGuardMasqueradingAsCUDA g(q16.device());
-  ok(crs_maxsim_topk(q16.data_ptr(), q_len.data_ptr<int32_t>(), (int)nq, (int)q16.size(1), n_tokens ? tok16.data_ptr() : nullptr,
-                     offsets.data_ptr<int64_t>(), n_rows, n_tokens, row_first, row_count, (int)dimp, (int)k, workspace.data_ptr(),
-                     (size_t)workspace.numel(), out_scores.data_ptr<float>(), out_rows.data_ptr<int64_t>(), cur_stream(q16)),
-     "crs::maxsim_topk");
+  ok((f8 ? crs_maxsim_topk_f8 : crs_maxsim_topk)(q16.data_ptr(), q_len.data_ptr<int32_t>(), (int)nq, (int)q16.size(1),
+                                                  n_tokens ? tok16.data_ptr() : nullptr, offsets.data_ptr<int64_t>(), n_rows, n_tokens,
+                                                  row_first, row_count, (int)dimp, (int)k, workspace.data_ptr(),
+                                                  (size_t)workspace.numel(), out_scores.data_ptr<float>(),
+                                                  out_rows.data_ptr<int64_t>(), cur_stream(q16)),
+     f8 ? "crs::maxsim_topk_f8" : "crs::maxsim_topk");
+}
+void maxsim_topk(const Tensor& q16, const Tensor& q_len, const Tensor& tok16, int64_t n_tokens, const Tensor& offsets, int64_t n_rows,
+                 int64_t row_first, int64_t row_count, int64_t k, Tensor workspace, Tensor out_scores, Tensor out_rows) {
+  maxsim_topk_any(q16, q_len, tok16, n_tokens, offsets, n_rows, row_first, row_count, k, workspace, out_scores, out_rows, false);
+}
+void maxsim_topk_f8(const Tensor& q8, const Tensor& q_len, const Tensor& tok8, int64_t n_tokens, const Tensor& offsets, int64_t n_rows,
+                    int64_t row_first, int64_t row_count, int64_t k, Tensor workspace, Tensor out_scores, Tensor out_rows) {
+  maxsim_topk_any(q8, q_len, tok8, n_tokens, offsets, n_rows, row_first, row_count, k, workspace, out_scores, out_rows, true);
 }
 
 // ---- near-duplicate join (csrc/join.hip) ---------------------------------------------------------------------------
@@ -1363,6 +1394,9 @@ TORCH_LIBRARY(crs, m) {
   m.def("token_project(Tensor hidden, Tensor w16, Tensor? bias, Tensor dst, Tensor(a!) out16) -> ()");
   m.def("maxsim(Tensor q16, Tensor q_len, Tensor tok16, int n_tokens, Tensor offsets, int n_rows, Tensor rows, Tensor(a!) out) -> ()");
   m.def("maxsim_topk(Tensor q16, Tensor q_len, Tensor tok16, int n_tokens, Tensor offsets, int n_rows, int row_first, int row_count, int k, Tensor(a!) workspace, Tensor(b!) out_scores, Tensor(c!) out_rows) -> ()");
+  m.def("token_project_f8(Tensor hidden, Tensor w16, Tensor? bias, Tensor dst, Tensor(a!) out8) -> ()");
+  m.def("maxsim_f8(Tensor q8, Tensor q_len, Tensor tok8, int n_tokens, Tensor offsets, int n_rows, Tensor rows, Tensor(a!) out) -> ()");
+  m.def("maxsim_topk_f8(Tensor q8, Tensor q_len, Tensor tok8, int n_tokens, Tensor offsets, int n_rows, int row_first, int row_count, int k, Tensor(a!) workspace, Tensor(b!) out_scores, Tensor(c!) out_rows) -> ()");
   m.def("pairs_above_out(Tensor slab, int n_rows, int dim, int a_first, int a_rows, int b_first, int b_rows, float thr, "
         "Tensor(a!) pairs, Tensor(b!) scores, Tensor(c!) count) -> ()");
   m.def("pairs_verify_out(Tensor pairs, Tensor shadow, int n_rows, float thr, Tensor(a!) rows_a, Tensor(b!) rows_b, Tensor(c!) sims, "
@@ -1433,6 +1467,9 @@ TORCH_LIBRARY_IMPL(crs, CUDA, m) {   // the HIP backend of torch-ROCm dispatches
   m.impl("token_project", &token_project);
   m.impl("maxsim", &maxsim);
   m.impl("maxsim_topk", &maxsim_topk);
+  m.impl("token_project_f8", &token_project_f8);
+  m.impl("maxsim_f8", &maxsim_f8);
+  m.impl("maxsim_topk_f8", &maxsim_topk_f8);
   m.impl("pairs_above_out", &pairs_above_out);
   m.impl("pairs_verify_out", &pairs_verify_out);
   m.impl("bm25_topk", &bm25_topk);

@@ -88,6 +88,13 @@ _SIGNATURES = {
     "crs_maxsim_topk_plan_describe": (c_int, [c_int, c_int, c_int, c_int, c_int64, ctypes.c_char_p, c_size_t]),
     "crs_maxsim_topk": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int,
                                 c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "crs_token_project_f8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "crs_maxsim_f8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_int, c_void_p,
+                              c_void_p]),
+    "crs_maxsim_topk_f8_workspace_bytes": (c_int, [c_int, c_int, c_int64, POINTER(c_size_t)]),
+    "crs_maxsim_topk_f8_plan_describe": (c_int, [c_int, c_int, c_int, c_int, c_int64, ctypes.c_char_p, c_size_t]),
+    "crs_maxsim_topk_f8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int,
+                                   c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     "crs_pairs_above_f16": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, c_int64, c_float, c_void_p, c_void_p, c_int64,
                                     c_void_p, c_void_p]),
     "crs_pairs_verify_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -511,16 +518,29 @@ def token_project(hidden, w16, bias, dst, out16):
     return out16
 
 
+F8_TOKEN_SHIFT = 8      # CRS_F8_TOKEN_SHIFT (csrc/e4m3.h): an fp8 token vector is the unit vector times 2^8, rounded to e4m3
+
+
+def token_project_f8(hidden, w16, bias, dst, out8):
+    """token_project into an fp8 token array (crs_token_project_f8): out8 uint8 [rows, token_dim_padded(dim)] receives the e4m3
+    codes of the unit vector times 2^F8_TOKEN_SHIFT, code 0 past dim.  Queries and documents alike.  No host sync."""
+    with _translate():
+        ops().token_project_f8(hidden, w16, bias, dst, out8)
+    return out8
+
+
 def maxsim(q16, q_len, tok16, n_tokens: int, offsets, n_rows: int, rows, out=None):
     """Late-interaction scores of nq candidate lists in one launch (crs_maxsim, csrc/maxsim.hip): q16 cuda fp16 [nq, lq_max <= 64,
     dimp], q_len int32 [nq], tok16 fp16 [>= n_tokens, dimp] with the CSR offsets int64 [>= n_rows + 1], rows int64 [nq, m_max] ->
     fp32 [nq, m_max]: sum over the query's tokens of the best dot product with a token of the row's document; -inf for a row outside
-    [0, n_rows), 0 for an empty document or query.  No host sync."""
+    [0, n_rows), 0 for an empty document or query.  uint8 tokens (and queries) are an fp8 index: crs_maxsim_f8, csrc/maxsim_f8.hip,
+    the same sum over the stored e4m3 values times 2^(-2 F8_TOKEN_SHIFT).  No host sync."""
     import torch
     if out is None:
         out = torch.empty(rows.shape, dtype=torch.float32, device=rows.device)
     with _translate():
-        ops().maxsim(q16, q_len, tok16, int(n_tokens), offsets, int(n_rows), rows, out)
+        op = ops().maxsim_f8 if tok16.dtype == torch.uint8 else ops().maxsim
+        op(q16, q_len, tok16, int(n_tokens), offsets, int(n_rows), rows, out)
     return out
 
 
@@ -528,16 +548,18 @@ MAXSIM_SCAN_WINDOW = 256      # CRS_MAXSIM_SCAN_WINDOW: tokens of one staged win
 MAXSIM_SCAN_ITEM_ROWS = 64    # CRS_MAXSIM_SCAN_ITEM_ROWS: consecutive rows of one of its work items
 
 
-def maxsim_topk_workspace_bytes(nq: int, k: int, row_count: int) -> int:
+def maxsim_topk_workspace_bytes(nq: int, k: int, row_count: int, f8: bool = False) -> int:
     b = c_size_t(0)
-    check(load().crs_maxsim_topk_workspace_bytes(int(nq), int(k), int(row_count), ctypes.byref(b)))
+    fn = load().crs_maxsim_topk_f8_workspace_bytes if f8 else load().crs_maxsim_topk_workspace_bytes
+    check(fn(int(nq), int(k), int(row_count), ctypes.byref(b)))
     return int(b.value)
 
 
-def maxsim_topk_plan_describe(nq: int, lq_max: int, dimp: int, k: int, row_count: int) -> str:
-    """The plan line of a late-interaction sweep (no device needed)."""
+def maxsim_topk_plan_describe(nq: int, lq_max: int, dimp: int, k: int, row_count: int, f8: bool = False) -> str:
+    """The plan line of a late-interaction sweep (no device needed); f8: of the sweep of an fp8 token index."""
     buf = ctypes.create_string_buffer(256)
-    check(load().crs_maxsim_topk_plan_describe(int(nq), int(lq_max), int(dimp), int(k), int(row_count), buf, 256))
+    fn = load().crs_maxsim_topk_f8_plan_describe if f8 else load().crs_maxsim_topk_plan_describe
+    check(fn(int(nq), int(lq_max), int(dimp), int(k), int(row_count), buf, 256))
     return buf.value.decode()
 
 
@@ -545,16 +567,19 @@ def maxsim_topk(q16, q_len, tok16, n_tokens: int, offsets, n_rows: int, k: int, 
     """The k best rows of [row_first, row_first + row_count) (default: every row) per query by MaxSim, in one sweep of the token
     index (crs_maxsim_topk, csrc/maxsim_scan.hip): arguments as maxsim takes them, 1 <= k <= 64.  Returns (scores fp32 [nq, k], rows
     int64 [nq, k]) sorted score desc / row asc, (-inf, -1) in missing slots; a returned score is bit for bit maxsim's for that pair.
-    Rows without tokens are never returned.  No host sync."""
+    Rows without tokens are never returned.  uint8 tokens (and queries) are an fp8 index: crs_maxsim_topk_f8,
+    csrc/maxsim_scan_f8.hip, whose scores are bit for bit maxsim's on the same uint8 arrays.  No host sync."""
     import torch
     nq = q16.shape[0]
+    f8 = tok16.dtype == torch.uint8
     row_count = int(n_rows) - int(row_first) if row_count is None else int(row_count)
     out_s = torch.empty((nq, k), dtype=torch.float32, device=q16.device)
     out_r = torch.empty((nq, k), dtype=torch.int64, device=q16.device)
     if workspace is None:
-        workspace = torch.empty(maxsim_topk_workspace_bytes(nq, k, max(row_count, 0)), dtype=torch.uint8, device=q16.device)
+        workspace = torch.empty(maxsim_topk_workspace_bytes(nq, k, max(row_count, 0), f8), dtype=torch.uint8, device=q16.device)
     with _translate():
-        ops().maxsim_topk(q16, q_len, tok16, int(n_tokens), offsets, int(n_rows), int(row_first), row_count, int(k), workspace, out_s, out_r)
+        op = ops().maxsim_topk_f8 if f8 else ops().maxsim_topk
+        op(q16, q_len, tok16, int(n_tokens), offsets, int(n_rows), int(row_first), row_count, int(k), workspace, out_s, out_r)
     return out_s, out_r
 
 

@@ -488,10 +488,14 @@ class _TokenIndex:
     """The late-interaction token vectors of every row, for crs_maxsim (csrc/maxsim.hip): ``tok16`` cuda fp16 [capacity, dimp],
     the first ``n_tokens`` rows in use (row r's tokens are [offsets[r], offsets[r + 1])), grown by doubling; ``offsets`` int64
     [n_rows + 1] on the host, ``offsets_dev`` its device copy.  Extended in place as rows arrive: an append encodes the new rows
-    alone."""
+    alone.  With an fp8 encoder (``token_dtype: 'fp8'``) ``tok16`` holds uint8 e4m3 rows instead -- dimp bytes a token, half the
+    index -- and crs_maxsim_f8 / crs_maxsim_topk_f8 read it (csrc/maxsim_f8.hip, csrc/maxsim_scan_f8.hip)."""
 
     def __init__(self, encoder, device):
+        import torch
         self.encoder, self.device, self.dimp = encoder, device, encoder.dimp
+        self.dtype = getattr(encoder, "token_torch_dtype", torch.float16)
+        self.elem_bytes = 1 if self.dtype == torch.uint8 else 2
         self.tok16 = None
         self.n_tokens = 0
         self.offsets = np.zeros(1, dtype=np.int64)
@@ -517,15 +521,15 @@ class _TokenIndex:
         ids = self.encoder.tokenize_docs(new)
         counts = self.encoder.doc_token_counts(new, ids=ids)
         total = self.n_tokens + int(counts.sum())
-        need = total * self.dimp * 2
+        need = total * self.dimp * self.elem_bytes
         if need > max_bytes:
-            raise ValueError(f"the late-interaction token index would take {need} bytes ({total} tokens x {self.dimp} x 2) for "
+            raise ValueError(f"the late-interaction token index would take {need} bytes ({total} tokens x {self.dimp} x {self.elem_bytes}) for "
                              f"{len(documents)} rows, more than max_index_bytes = {int(max_bytes)}")
         with torch.cuda.device(self.device):
             held = self.tok16.shape[0] if self.tok16 is not None else 0
             if new and total > held:
-                cap = max(total, min(2 * held, int(max_bytes) // (self.dimp * 2)), 1)
-                grown = torch.zeros((cap, self.dimp), dtype=torch.float16, device=self.device)
+                cap = max(total, min(2 * held, int(max_bytes) // (self.dimp * self.elem_bytes)), 1)
+                grown = torch.zeros((cap, self.dimp), dtype=self.dtype, device=self.device)
                 if self.n_tokens:
                     grown[:self.n_tokens] = self.tok16[:self.n_tokens]
                 self.tok16 = grown
@@ -534,7 +538,7 @@ class _TokenIndex:
                 self.offsets = np.concatenate([self.offsets, self.n_tokens + np.cumsum(counts)]).astype(np.int64)
                 self.n_tokens = total
             if self.tok16 is None:
-                self.tok16 = torch.zeros((1, self.dimp), dtype=torch.float16, device=self.device)
+                self.tok16 = torch.zeros((1, self.dimp), dtype=self.dtype, device=self.device)
             self.offsets_dev = torch.from_numpy(self.offsets).to(self.device)
 
 

@@ -11,7 +11,9 @@ path.
 Config keys: ``model_name`` / ``model_path``, ``dim`` (checked against the checkpoint; sizes a synthetic one), ``query_maxlen``
 (default 32, at most 64: crs_maxsim holds the query in registers), ``doc_maxlen`` (default 180), ``query_augment`` (default false),
 ``mask_punctuation`` (default true), ``query_marker`` / ``doc_marker`` (a token string of the vocabulary, a token id, or ''/None for
-no marker), ``batch_size`` (texts per encoder forward, default 64), ``device``, ``synthetic_seed``.
+no marker), ``batch_size`` (texts per encoder forward, default 64), ``device``, ``synthetic_seed``, ``token_dtype`` (``'fp16'``,
+the default, or ``'fp8'``: queries and documents are stored as OCP e4m3 codes of the unit vector times 2^8, one byte a coordinate
+-- half the token index -- and scored by ``crs_maxsim_f8`` / ``crs_maxsim_topk_f8`` over those stored values).
 
 Model resolution, offline by construction, as ``CrossEncoderReranker``: a LOCAL BERT directory whose model.safetensors holds
 ``bert.*`` plus ``linear.weight [dim, H]`` and no bias; else ``$CRS_MODEL_DIR/<basename of model_name>``; else
@@ -116,6 +118,9 @@ class LateInteractionReranker:
         self.query_maxlen = int(config.get("query_maxlen", 32))
         if not 3 <= self.query_maxlen <= MAX_QUERY:
             raise ValueError(f"query_maxlen must be in 3..{MAX_QUERY} (crs_maxsim holds the query in registers), got {self.query_maxlen}")
+        self.token_dtype = config.get("token_dtype", "fp16")
+        if self.token_dtype not in ("fp16", "fp8"):
+            raise ValueError(f"token_dtype must be 'fp16' or 'fp8', got {self.token_dtype!r}")
         shape, weights, self.tokenizer, _cfg = self._resolve(config)
         self.dim = int(weights[LINEAR].shape[0])
         if config.get("dim") is not None and int(config["dim"]) != self.dim:
@@ -194,6 +199,12 @@ class LateInteractionReranker:
     def device(self):
         return self.model.device
 
+    @property
+    def token_torch_dtype(self):
+        """The element type of this encoder's token arrays: torch.float16, or torch.uint8 (e4m3 codes) with token_dtype 'fp8'."""
+        import torch
+        return torch.uint8 if self.token_dtype == "fp8" else torch.float16
+
     # ---- tokenisation ----------------------------------------------------------------------------------------------------------
     def _frame(self, body: Sequence[int], marker: Optional[int], maxlen: int) -> List[int]:
         tok = self.tokenizer
@@ -244,17 +255,18 @@ class LateInteractionReranker:
         _, hidden = model.forward(ids, lens, normalize=False, return_hidden=True)
         if dst.size and int(dst.max()) >= out16.shape[0]:
             raise ValueError("slot table leaves the output array")
-        nat.token_project(hidden.view(-1, self.shape.hidden), self._w16, None, torch.from_numpy(dst.reshape(-1)).to(model.device), out16)
+        project = nat.token_project_f8 if self.token_dtype == "fp8" else nat.token_project
+        project(hidden.view(-1, self.shape.hidden), self._w16, None, torch.from_numpy(dst.reshape(-1)).to(model.device), out16)
 
     def encode_queries_device(self, texts: Sequence[str]):
         """(q16 cuda fp16 [n, lq_max, dimp], q_len cuda int32 [n]): lq_max the longest query of the call; rows at and past q_len
-        are zeros.  One encoder forward per batch_size queries."""
+        are zeros.  One encoder forward per batch_size queries.  token_dtype 'fp8': q16 is uint8, e4m3 codes."""
         import torch
         model = self.model
         ids = self.tokenize_queries(texts)
         n = len(ids)
         lq_max = max((len(t) for t in ids), default=1)
-        q16 = torch.zeros((n, lq_max, self.dimp), dtype=torch.float16, device=model.device)
+        q16 = torch.zeros((n, lq_max, self.dimp), dtype=self.token_torch_dtype, device=model.device)
         lens_all = np.asarray([len(t) for t in ids], dtype=np.int32)
         pad = getattr(self.tokenizer, "pad_id", 0)
         flat = q16.view(n * lq_max, self.dimp)
@@ -270,7 +282,8 @@ class LateInteractionReranker:
         Processed longest first (equal lengths by their ids) in batches of batch_size, each batch padded to its longest, and
         scattered back through the host-built slot table.  `ids`: the documents' token ids when the caller already has them.
         `out` (cuda fp16 [>= first_slot + T, dimp]): write the T rows there from row first_slot on instead of into a new array
-        (the store's token index: no temporary copy of the new rows); the returned tok16 is then that slice of `out`."""
+        (the store's token index: no temporary copy of the new rows); the returned tok16 is then that slice of `out`.
+        token_dtype 'fp8': tok16 and `out` are uint8, e4m3 codes."""
         import torch
         model = self.model
         ids = self.tokenize_docs(texts) if ids is None else ids
@@ -282,9 +295,9 @@ class LateInteractionReranker:
         first += int(first_slot)
         total = int(first[-1])
         if out is None:
-            out = torch.zeros((total, self.dimp), dtype=torch.float16, device=model.device)
-        elif out.dtype != torch.float16 or out.dim() != 2 or out.shape[1] != self.dimp or out.shape[0] < total or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous fp16 [>= {total}, {self.dimp}] array")
+            out = torch.zeros((total, self.dimp), dtype=self.token_torch_dtype, device=model.device)
+        elif out.dtype != self.token_torch_dtype or out.dim() != 2 or out.shape[1] != self.dimp or out.shape[0] < total or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous {self.token_dtype} [>= {total}, {self.dimp}] array")
         order = sorted(range(n), key=lambda i: (-len(ids[i]), ids[i]))
         pad = getattr(self.tokenizer, "pad_id", 0)
         for lo in range(0, n, self.batch_size):

@@ -516,6 +516,29 @@ int crs_maxsim_topk(const void* q16_dev, const int32_t* q_len_dev, int nq, int l
                     int dimp, int k, void* workspace_dev, size_t workspace_bytes,
                     float* out_scores_dev, int64_t* out_rows_dev, void* stream);
 
+/* ---- an fp8 token index for late interaction: e4m3 rows of dimp BYTES, half the fp16 index (additive to ABI 3; csrc/e4m3.h,
+ * csrc/token_project.hip, csrc/maxsim_f8.hip, csrc/maxsim_scan_f8.hip) ----
+ * Format: a token vector is normalised to unit length in fp32 exactly as crs_token_project does, multiplied by 2^S, S = 8 (one
+ * constant, CRS_F8_TOKEN_SHIFT in csrc/e4m3.h, for documents and queries alike), and rounded once to OCP e4m3 (e4m3fn: round to
+ * nearest even, subnormals kept, saturating at 448, never NaN); elements [dim, dimp) are code 0.  A score is
+ *   2^(-2 S) sum_i max_j <Q_i, D_j>   over the stored values: exact products, fp32 accumulation from a zero accumulator
+ *   (the codes are decoded exactly to fp16 values stored * 2^-S in registers and multiplied by v_mfma_f32_16x16x32_f16; the fp8
+ *   matrix instructions do not accumulate in fp32).
+ * crs_token_project_f8 takes crs_token_project's arguments with out8_dev uint8 [*, dimp]; rows with a negative dst are never read
+ * or written.  crs_maxsim_f8 is crs_maxsim with q8_dev uint8 [nq, lq_max, dimp] and tok8_dev uint8 [n_tokens, dimp], and
+ * crs_maxsim_topk_f8 / _workspace_bytes / _plan_describe are crs_maxsim_topk's; every contract, limit and error of the fp16 entry
+ * points holds word for word, and a score returned by crs_maxsim_topk_f8 is bit for bit crs_maxsim_f8's for that pair. */
+int crs_token_project_f8(const float* hidden_dev, const void* w16_dev, const float* bias_dev, const int64_t* dst_dev, void* out8_dev,
+                         int64_t n_tok, int hidden, int dim, void* stream);
+int crs_maxsim_f8(const void* q8_dev, const int32_t* q_len_dev, int nq, int lq_max, const void* tok8_dev, const int64_t* offsets_dev,
+                  int64_t n_rows, int64_t n_tokens, const int64_t* rows_dev, int m_max, int dimp, float* out_dev, void* stream);
+int crs_maxsim_topk_f8_workspace_bytes(int nq, int k, int64_t row_count, size_t* bytes);
+int crs_maxsim_topk_f8_plan_describe(int nq, int lq_max, int dimp, int k, int64_t row_count, char* buf, size_t cap);   /* no device */
+int crs_maxsim_topk_f8(const void* q8_dev, const int32_t* q_len_dev, int nq, int lq_max, const void* tok8_dev,
+                       const int64_t* offsets_dev, int64_t n_rows, int64_t n_tokens, int64_t row_first, int64_t row_count,
+                       int dimp, int k, void* workspace_dev, size_t workspace_bytes,
+                       float* out_scores_dev, int64_t* out_rows_dev, void* stream);
+
 /* ---- learned sparse retrieval (SPLADE): compaction of a dense weight row, impact top-k over a weighted token CSR -- no reference
  * call site (additive to ABI 3; csrc/sparse_compact.hip, csrc/sparse_scan.hip; the head that produces the dense rows
  * is crs_mlm_sparse_pool, crs_encoder.h) ----

@@ -11,6 +11,10 @@
   retriever   ContextRetriever.retrieve_batch end to end over a store of --store-rows chunks under ``synthetic:colbert-minilm``,
               first_stage 'dense' against 'scan': queries/s
 
+--token-dtype fp16 | fp8 | both: the index and the queries as fp16 rows, as e4m3 rows (crs_maxsim_topk_f8, csrc/maxsim_scan_f8.hip,
+DESIGN 3.23: the same unit vectors times 2^8, rounded by torch's float8_e4m3fn cast), or both ALTERNATELY at every shape in one
+job, each fp8 entry then carrying its time as a ratio to the fp16 sweep's.
+
 hipEvent spans after a warm-up, median of --reps spans, clocks as found.  A report, not a pass condition."""
 import argparse
 import json
@@ -55,6 +59,9 @@ def kernel(args, result):
     for lo in range(0, n_tokens, 1 << 22):                                   # random unit rows, a slice at a time
         x = torch.randn((min(1 << 22, n_tokens - lo), dimp), device=dev)
         tok[lo:lo + x.shape[0]] = torch.nn.functional.normalize(x, dim=1).half()
+    dtypes = ("fp16", "fp8") if args.token_dtype == "both" else (args.token_dtype,)
+    f8 = lambda x: (x.float() * 256.0).to(torch.float8_e4m3fn).view(torch.uint8)
+    toks = {"fp16": tok, "fp8": f8(tok) if "fp8" in dtypes else None}
     index_bytes = n_tokens * dimp * 2
     part = tok[: min(n_tokens, (4 << 30) // (dimp * 2))]
     scratch = torch.empty_like(part)
@@ -69,18 +76,27 @@ def kernel(args, result):
         for lq in (16, 32, 64):
             q16 = torch.nn.functional.normalize(torch.randn((nq, lq, dimp), device=dev), dim=2).half().contiguous()
             q_len = torch.full((nq,), lq, dtype=torch.int32, device=dev)
-            ws = torch.empty(nat.maxsim_topk_workspace_bytes(nq, k, args.rows), dtype=torch.uint8, device=dev)
-            fn = lambda: nat.maxsim_topk(q16, q_len, tok, n_tokens, offsets, args.rows, k, workspace=ws)
-            fn()
-            t = span_ms(fn, args.reps)
-            sec, groups = t["median"] * 1e-3, (nq + 7) // 8
-            flops = 2.0 * nq * lq * n_tokens * dimp
-            result["kernel"].append({"nq": nq, "q_len": lq, "ms": t, "plan": nat.maxsim_topk_plan_describe(nq, lq, dimp, k, args.rows),
-                                     "gb_per_s_per_query_group": round(index_bytes / sec / 1e9, 1),
-                                     "gb_per_s_all_groups": round(groups * index_bytes / sec / 1e9, 1),
-                                     "copy_read_gb_per_s": round(copy_gbps, 1), "tflop_per_s": round(flops / sec / 1e12, 1),
-                                     "share_of_peak": round(flops / sec / PEAK_FLOPS, 4), "queries_per_s": round(nq / sec, 1)})
-            print(json.dumps(result["kernel"][-1]), flush=True)
+            base = None
+            for dt in dtypes:
+                is8 = dt == "fp8"
+                qx, tx, nbytes = (f8(q16), toks["fp8"], index_bytes // 2) if is8 else (q16, tok, index_bytes)
+                ws = torch.empty(nat.maxsim_topk_workspace_bytes(nq, k, args.rows, f8=is8), dtype=torch.uint8, device=dev)
+                fn = lambda: nat.maxsim_topk(qx, q_len, tx, n_tokens, offsets, args.rows, k, workspace=ws)
+                fn()
+                t = span_ms(fn, args.reps)
+                sec, groups = t["median"] * 1e-3, (nq + 7) // 8
+                flops = 2.0 * nq * lq * n_tokens * dimp
+                entry = {"token_dtype": dt, "nq": nq, "q_len": lq, "ms": t, "plan": nat.maxsim_topk_plan_describe(nq, lq, dimp, k, args.rows, f8=is8),
+                         "ms_per_query": round(t["median"] / nq, 4),
+                         "gb_per_s_per_query_group": round(nbytes / sec / 1e9, 1),
+                         "gb_per_s_all_groups": round(groups * nbytes / sec / 1e9, 1),
+                         "copy_read_gb_per_s": round(copy_gbps, 1), "tflop_per_s": round(flops / sec / 1e12, 1),
+                         "share_of_peak": round(flops / sec / PEAK_FLOPS, 4), "queries_per_s": round(nq / sec, 1)}
+                if is8 and base:
+                    entry["time_ratio_to_fp16"] = round(t["median"] / base, 3)
+                base = t["median"] if not is8 else base
+                result["kernel"].append(entry)
+                print(json.dumps(entry), flush=True)
 
 
 def retriever(args, result):
@@ -100,7 +116,8 @@ def retriever(args, result):
         p = RAGPipeline({"embedding": {"model_name": "synthetic:tiny", "device": "cuda", "batch_size": 256, "normalize": True},
                          "vector_store": {"collection_name": "late-scan-bench-" + stage},
                          "retrieval": {"top_k": 10, "rerank": True, "similarity_threshold": -1.0, "diversity_penalty": 0.0,
-                                       "late_interaction": {"model_name": "synthetic:colbert-minilm", "first_stage": stage}}})
+                                       "late_interaction": {"model_name": "synthetic:colbert-minilm", "first_stage": stage,
+                                                            "token_dtype": "fp16" if args.token_dtype == "both" else args.token_dtype}}})
         p.setup(Stub())
         chunks = [Chunk(text=t, chunk_id=f"c_{r}", start_char=0, end_char=1) for r, t in enumerate(texts)]
         p.vector_store.create_index(chunks, p.embedding_model.embed_chunks_device(chunks))
@@ -125,6 +142,7 @@ def main():
     ap.add_argument("--queries", type=int, default=64)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--skip-retriever", action="store_true")
+    ap.add_argument("--token-dtype", choices=("fp16", "fp8", "both"), default="fp16")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
