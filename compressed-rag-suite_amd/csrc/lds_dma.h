@@ -42,6 +42,13 @@ __device__ __forceinline__ void lds_dma16(unsigned lds_dst, const void* vaddr) {
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
                : "=&s"(keep) : "s"(lds_dst), "v"(vaddr) : "memory");
 }
+// 4 bytes per lane (lane i lands at base + 4 i): for rows whose length is no multiple of 16 bytes, whose windows start at
+// addresses that are only 4-byte aligned (the code rows of maxsim_scan_rc.hip at dimp 32 and 96)
+__device__ __forceinline__ void lds_dma4(unsigned lds_dst, const void* vaddr) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %2, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "s"(lds_dst), "v"(vaddr) : "memory");
+}
 
 // The LDS side of a transfer is linear (lane i lands at base + 16 i), so a tile's XOR swizzle is applied on the SOURCE side:
 // position P = j * kT + tid of the tile buffer (kT threads, kLoads transfers per lane) receives the tile's 16-byte chunk swz(P)

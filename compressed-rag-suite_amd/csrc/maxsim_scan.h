@@ -42,4 +42,16 @@ int maxsim_scan_f8_make_plan(int nq, int lq_max, int dimp, int k, int64_t row_co
 int maxsim_scan_f8_plan_describe(const MaxsimScanPlan& p, char* buf, size_t cap);
 size_t maxsim_scan_f8_workspace_bound(int nq, int k, int64_t row_count);
 
+// ---- the same sweep over a 2-bit residual token index (crs_maxsim_topk_rc, maxsim_scan_rc.hip).  Queries are fp16
+// and a wave keeps two, as above.  A window buffer holds 256 code rows of dimp / 4 bytes, 256 cids and 256 scales -- dimp / 4 + 6
+// bytes a token, 9.5 KB at dimp 128, two of them 19 KB; the centroid rows are gathered from global memory into registers and
+// never staged.  LDS would let eight workgroups share a CU; the registers (two queries a wave) allow three, two, two and one at
+// dimp 32, 64, 96 and 128, so kMsScanFill stays what it is.  The plan has the same fields.
+constexpr int kMsRcWaveQ = 2;                              // queries resident per wave
+constexpr int kMsRcGroupQ = 4 * kMsRcWaveQ;                // queries of a workgroup
+constexpr int kMsRcTokenLdsBytes(int dimp) { return dimp / 4 + 6; }
+int maxsim_scan_rc_make_plan(int nq, int lq_max, int dimp, int k, int64_t row_count, MaxsimScanPlan* p, const char** why);
+int maxsim_scan_rc_plan_describe(const MaxsimScanPlan& p, char* buf, size_t cap);
+size_t maxsim_scan_rc_workspace_bound(int nq, int k, int64_t row_count);
+
 }  // namespace crs

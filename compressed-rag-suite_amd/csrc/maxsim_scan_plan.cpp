@@ -10,8 +10,8 @@ namespace crs {
 static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 static int kp_of(int k) { return k <= 32 ? 32 : 64; }
 
-// group_q queries per workgroup, elem_bytes per coordinate of a staged token row
-static int make_plan(int group_q, int elem_bytes, int nq, int lq_max, int dimp, int k, int64_t row_count, MaxsimScanPlan* p,
+// group_q queries per workgroup, token_lds bytes of a window buffer per token
+static int make_plan(int group_q, int token_lds, int nq, int lq_max, int dimp, int k, int64_t row_count, MaxsimScanPlan* p,
                      const char** why) {
   if (lq_max < 1 || lq_max > CRS_MAXSIM_MAX_QUERY) { *why = "lq_max must be in 1..CRS_MAXSIM_MAX_QUERY"; return -1; }
   if (dimp != 32 && dimp != 64 && dimp != 96 && dimp != 128) { *why = "dimp must be 32, 64, 96 or 128"; return -1; }
@@ -28,7 +28,7 @@ static int make_plan(int group_q, int elem_bytes, int nq, int lq_max, int dimp, 
   p->items = (row_count + CRS_MAXSIM_SCAN_ITEM_ROWS - 1) / CRS_MAXSIM_SCAN_ITEM_ROWS;
   const int want = p->qgroups ? (kMsScanFill * kMsScanCus + p->qgroups - 1) / p->qgroups : 1;
   p->g = (int)(p->items < want ? p->items : want);
-  p->lds_bytes = 2 * CRS_MAXSIM_SCAN_WINDOW * dimp * elem_bytes;
+  p->lds_bytes = 2 * CRS_MAXSIM_SCAN_WINDOW * token_lds;
   const size_t lists = (size_t)p->g * nq;
   p->part_s = 0;
   p->part_r = up256(lists * p->kp * 4);
@@ -44,10 +44,13 @@ static size_t workspace_bound(int group_q, int nq, int k, int64_t row_count) {
 }
 
 int maxsim_scan_make_plan(int nq, int lq_max, int dimp, int k, int64_t row_count, MaxsimScanPlan* p, const char** why) {
-  return make_plan(kMsScanGroupQ, 2, nq, lq_max, dimp, k, row_count, p, why);
+  return make_plan(kMsScanGroupQ, 2 * dimp, nq, lq_max, dimp, k, row_count, p, why);
 }
 int maxsim_scan_f8_make_plan(int nq, int lq_max, int dimp, int k, int64_t row_count, MaxsimScanPlan* p, const char** why) {
-  return make_plan(kMsF8GroupQ, 1, nq, lq_max, dimp, k, row_count, p, why);
+  return make_plan(kMsF8GroupQ, dimp, nq, lq_max, dimp, k, row_count, p, why);
+}
+int maxsim_scan_rc_make_plan(int nq, int lq_max, int dimp, int k, int64_t row_count, MaxsimScanPlan* p, const char** why) {
+  return make_plan(kMsRcGroupQ, kMsRcTokenLdsBytes(dimp), nq, lq_max, dimp, k, row_count, p, why);
 }
 
 int maxsim_scan_plan_describe(const MaxsimScanPlan& p, char* buf, size_t cap) {
@@ -62,7 +65,14 @@ int maxsim_scan_f8_plan_describe(const MaxsimScanPlan& p, char* buf, size_t cap)
                   (long long)p.items, p.kp, p.lds_bytes, p.g);
 }
 
+int maxsim_scan_rc_plan_describe(const MaxsimScanPlan& p, char* buf, size_t cap) {
+  return snprintf(buf, cap, "maxsim_scan_rc<dimp=%d> grid=%dx%d threads=%d queries/wave=%d window=%d item_rows=%d items=%lld kp=%d lds=%d + merge x1 (nlists=%d)",
+                  p.dimp, p.g, p.qgroups, kMsScanThreads, kMsRcWaveQ, CRS_MAXSIM_SCAN_WINDOW, CRS_MAXSIM_SCAN_ITEM_ROWS,
+                  (long long)p.items, p.kp, p.lds_bytes, p.g);
+}
+
 size_t maxsim_scan_workspace_bound(int nq, int k, int64_t row_count) { return workspace_bound(kMsScanGroupQ, nq, k, row_count); }
 size_t maxsim_scan_f8_workspace_bound(int nq, int k, int64_t row_count) { return workspace_bound(kMsF8GroupQ, nq, k, row_count); }
+size_t maxsim_scan_rc_workspace_bound(int nq, int k, int64_t row_count) { return workspace_bound(kMsRcGroupQ, nq, k, row_count); }
 
 }  // namespace crs

@@ -27,6 +27,7 @@
 //   crs::mlm_sparse_pool / crs::sparse_compact / crs::sparse_topk   learned sparse retrieval (SPLADE): MLM head with max-pool epilogue, compaction, impact scan (new vs the reference)
 //   crs::token_project / crs::maxsim   late interaction (ColBERT): per-token projection and MaxSim scoring of candidate lists (new vs the reference)
 //   crs::token_project_f8 / crs::maxsim_f8 / crs::maxsim_topk_f8   the same three over an fp8 (e4m3) token index (new vs the reference)
+//   crs::token_compress / crs::maxsim_rc / crs::maxsim_topk_rc   a 2-bit residual token index: compression, candidate scoring, sweep (new vs the reference)
 //   crs::maxsim_topk       exact late-interaction retrieval: one MaxSim sweep of the whole token index, top-k in the sweep (new vs the reference)
 //   crs::ivf_topk          top-k of the rows of per-query inverted lists of an fp16 slab: grouping + gathered MFMA probe (new vs the reference)
 //   crs::rerank_lexical    replaces the scoring, threshold and _rerank loops of retrieve_batch  (reference rag/retrieval.py:75-77, 196-217)
@@ -748,6 +749,98 @@ void maxsim_topk_f8(const Tensor& q8, const Tensor& q_len, const Tensor& tok8, i
   maxsim_topk_any(q8, q_len, tok8, n_tokens, offsets, n_rows, row_first, row_count, k, workspace, out_scores, out_rows, true);
 }
 
+// ---- the 2-bit residual token index (csrc/token_compress.hip, csrc/maxsim_rc.hip, csrc/maxsim_scan_rc.hip) ----------
+// tok16 fp16 [n_tok, dimp] unit rows; centroids fp16 [K, dimp]; cutoffs fp32 [3] / weights fp32 [4]; cid int32 [>= first + n_tok],
+// codes uint8 [>= first + n_tok, dimp / 4], scale fp16 [>= first + n_tok]: token i is written to slot first + i.  codes and scale
+// absent: the nearest-centroid stage alone
+void token_compress(const Tensor& tok16, int64_t dim, const Tensor& centroids, c10::optional<Tensor> cutoffs, c10::optional<Tensor> weights,
+                    int64_t first, Tensor cid, c10::optional<Tensor> codes, c10::optional<Tensor> scale) {
+  want(tok16, at::kHalf, "tok16");
+  want(centroids, at::kHalf, "centroids");
+  want(cid, at::kInt, "cid");
+  same_device(tok16, {&centroids, opt_t(cutoffs), opt_t(weights), &cid, opt_t(codes), opt_t(scale)}, "crs::token_compress");
+  TORCH_CHECK(tok16.dim() == 2 && centroids.dim() == 2 && centroids.size(1) == tok16.size(1), "tok16 must be fp16 [n_tok, dimp] and centroids fp16 [K, dimp]");
+  const int64_t n_tok = tok16.size(0), dimp = tok16.size(1);
+  TORCH_CHECK(dimp == 32 || dimp == 64 || dimp == 96 || dimp == 128, "dimp must be 32, 64, 96 or 128");
+  TORCH_CHECK(first >= 0 && cid.dim() == 1 && cid.size(0) >= first + n_tok, "cid must be int32 [>= first + n_tok]");
+  TORCH_CHECK(has(codes) == has(scale), "codes and scale go together");
+  if (has(codes)) {
+    want(*codes, at::kByte, "codes");
+    want(*scale, at::kHalf, "scale");
+    TORCH_CHECK(has(cutoffs) && has(weights), "cutoffs and weights are needed to write codes");
+    want(*cutoffs, at::kFloat, "cutoffs");
+    want(*weights, at::kFloat, "weights");
+    TORCH_CHECK(cutoffs->numel() == 3 && weights->numel() == 4, "cutoffs must be fp32 [3] and weights fp32 [4]");
+    TORCH_CHECK(codes->dim() == 2 && codes->size(1) == dimp / 4 && codes->size(0) >= first + n_tok && scale->dim() == 1 &&
+                scale->size(0) >= first + n_tok, "codes must be uint8 [>= first + n_tok, dimp / 4] and scale fp16 [>= first + n_tok]");
+  }
+  c10::hip::HIPGuardMasqueradingAsCUDA g(tok16.device());
+  ok(crs_token_compress(tok16.data_ptr(), n_tok, (int)dimp, (int)dim, centroids.data_ptr(), (int)std::min<int64_t>(centroids.size(0), INT32_MAX),
+                        has(codes) ? cutoffs->data_ptr<float>() : nullptr, has(codes) ? weights->data_ptr<float>() : nullptr,
+                        cid.data_ptr<int32_t>() + first, has(codes) ? codes->data_ptr<uint8_t>() + first * (dimp / 4) : nullptr,
+                        has(codes) ? static_cast<char*>(scale->data_ptr()) + first * 2 : nullptr, cur_stream(tok16)), "crs::token_compress");
+}
+
+// what both scoring ops check of an index and a codec; returns dimp
+static int64_t rc_checks(const Tensor& q16, const Tensor& q_len, const Tensor& cid, const Tensor& codes, const Tensor& scale,
+                         const Tensor& centroids, const Tensor& weights, int64_t n_tokens, const Tensor& offsets, int64_t n_rows) {
+  want(q16, at::kHalf, "q16");
+  want(q_len, at::kInt, "q_len");
+  want(cid, at::kInt, "cid");
+  want(codes, at::kByte, "codes");
+  want(scale, at::kHalf, "scale");
+  want(centroids, at::kHalf, "centroids");
+  want(weights, at::kFloat, "weights");
+  want(offsets, at::kLong, "offsets");
+  TORCH_CHECK(q16.dim() == 3 && q16.size(1) >= 1 && q16.size(1) <= CRS_MAXSIM_MAX_QUERY, "the queries must be [nq, lq_max <= 64, dimp]");
+  const int64_t nq = q16.size(0), dimp = q16.size(2);
+  TORCH_CHECK(nq <= 65535, "too many queries");
+  TORCH_CHECK(dimp == 32 || dimp == 64 || dimp == 96 || dimp == 128, "dimp must be 32, 64, 96 or 128");
+  TORCH_CHECK(q_len.dim() == 1 && q_len.size(0) == nq, "q_len must be int32 [nq]");
+  TORCH_CHECK(n_tokens >= 0 && cid.dim() == 1 && cid.size(0) >= n_tokens && codes.dim() == 2 && codes.size(1) == dimp / 4 &&
+              codes.size(0) >= n_tokens && scale.dim() == 1 && scale.size(0) >= n_tokens,
+              "the index must be cid int32 [>= n_tokens], codes uint8 [>= n_tokens, dimp / 4], scale fp16 [>= n_tokens]");
+  TORCH_CHECK(centroids.dim() == 2 && centroids.size(1) == dimp && centroids.size(0) <= CRS_RC_MAX_CENTROIDS && weights.numel() == 4,
+              "the codec must be centroids fp16 [K, dimp] and weights fp32 [4]");
+  TORCH_CHECK(n_rows >= 0 && offsets.dim() == 1 && offsets.numel() >= n_rows + 1, "offsets must be int64 [>= n_rows + 1]");
+  return dimp;
+}
+
+void maxsim_rc(const Tensor& q16, const Tensor& q_len, const Tensor& cid, const Tensor& codes, const Tensor& scale, const Tensor& centroids,
+               const Tensor& weights, int64_t n_tokens, const Tensor& offsets, int64_t n_rows, const Tensor& rows, Tensor out) {
+  const int64_t dimp = rc_checks(q16, q_len, cid, codes, scale, centroids, weights, n_tokens, offsets, n_rows), nq = q16.size(0);
+  want(rows, at::kLong, "rows");
+  want(out, at::kFloat, "out");
+  same_device(q16, {&q_len, &cid, &codes, &scale, &centroids, &weights, &offsets, &rows, &out}, "crs::maxsim_rc");
+  TORCH_CHECK(rows.dim() == 2 && rows.size(0) == nq && rows.size(1) >= 1 && rows.size(1) <= 0x7fffffff && out.sizes() == rows.sizes(),
+              "rows / out must be [nq, m_max >= 1]");
+  if (nq == 0) return;
+  c10::hip::HIPGuardMasqueradingAsCUDA g(q16.device());
+  ok(crs_maxsim_rc(q16.data_ptr(), q_len.data_ptr<int32_t>(), (int)nq, (int)q16.size(1), cid.data_ptr<int32_t>(), codes.data_ptr(),
+                   scale.data_ptr(), centroids.data_ptr(), (int)centroids.size(0), weights.data_ptr<float>(), offsets.data_ptr<int64_t>(),
+                   n_rows, n_tokens, rows.data_ptr<int64_t>(), (int)rows.size(1), (int)dimp, out.data_ptr<float>(), cur_stream(q16)),
+     "crs::maxsim_rc");
+}
+
+void maxsim_topk_rc(const Tensor& q16, const Tensor& q_len, const Tensor& cid, const Tensor& codes, const Tensor& scale,
+                    const Tensor& centroids, const Tensor& weights, int64_t n_tokens, const Tensor& offsets, int64_t n_rows,
+                    int64_t row_first, int64_t row_count, int64_t k, Tensor workspace, Tensor out_scores, Tensor out_rows) {
+  const int64_t dimp = rc_checks(q16, q_len, cid, codes, scale, centroids, weights, n_tokens, offsets, n_rows), nq = q16.size(0);
+  want(workspace, at::kByte, "workspace");
+  want(out_scores, at::kFloat, "out_scores");
+  want(out_rows, at::kLong, "out_rows");
+  same_device(q16, {&q_len, &cid, &codes, &scale, &centroids, &weights, &offsets, &workspace, &out_scores, &out_rows}, "crs::maxsim_topk_rc");
+  TORCH_CHECK(k >= 1 && k <= CRS_MAX_K, "k must be in 1..64");
+  TORCH_CHECK(out_scores.numel() == nq * k && out_rows.numel() == nq * k, "outputs must hold [nq, k]");
+  if (nq == 0) return;
+  c10::hip::HIPGuardMasqueradingAsCUDA g(q16.device());
+  ok(crs_maxsim_topk_rc(q16.data_ptr(), q_len.data_ptr<int32_t>(), (int)nq, (int)q16.size(1), cid.data_ptr<int32_t>(), codes.data_ptr(),
+                        scale.data_ptr(), centroids.data_ptr(), (int)centroids.size(0), weights.data_ptr<float>(),
+                        offsets.data_ptr<int64_t>(), n_rows, n_tokens, row_first, row_count, (int)dimp, (int)k, workspace.data_ptr(),
+                        (size_t)workspace.numel(), out_scores.data_ptr<float>(), out_rows.data_ptr<int64_t>(), cur_stream(q16)),
+     "crs::maxsim_topk_rc");
+}
+
 // ---- near-duplicate join (csrc/join.hip) ---------------------------------------------------------------------------
 // slab fp16 [>= n_rows, pdim]; pairs int64 [cap, 2], scores fp32 [cap]; count int64 [1], zeroed by the caller, receives the number
 // of qualifying pairs (count > cap: overflow)
@@ -1397,6 +1490,9 @@ TORCH_LIBRARY(crs, m) {
   m.def("token_project_f8(Tensor hidden, Tensor w16, Tensor? bias, Tensor dst, Tensor(a!) out8) -> ()");
   m.def("maxsim_f8(Tensor q8, Tensor q_len, Tensor tok8, int n_tokens, Tensor offsets, int n_rows, Tensor rows, Tensor(a!) out) -> ()");
   m.def("maxsim_topk_f8(Tensor q8, Tensor q_len, Tensor tok8, int n_tokens, Tensor offsets, int n_rows, int row_first, int row_count, int k, Tensor(a!) workspace, Tensor(b!) out_scores, Tensor(c!) out_rows) -> ()");
+  m.def("token_compress(Tensor tok16, int dim, Tensor centroids, Tensor? cutoffs, Tensor? weights, int first, Tensor(a!) cid, Tensor(b!)? codes, Tensor(c!)? scale) -> ()");
+  m.def("maxsim_rc(Tensor q16, Tensor q_len, Tensor cid, Tensor codes, Tensor scale, Tensor centroids, Tensor weights, int n_tokens, Tensor offsets, int n_rows, Tensor rows, Tensor(a!) out) -> ()");
+  m.def("maxsim_topk_rc(Tensor q16, Tensor q_len, Tensor cid, Tensor codes, Tensor scale, Tensor centroids, Tensor weights, int n_tokens, Tensor offsets, int n_rows, int row_first, int row_count, int k, Tensor(a!) workspace, Tensor(b!) out_scores, Tensor(c!) out_rows) -> ()");
   m.def("pairs_above_out(Tensor slab, int n_rows, int dim, int a_first, int a_rows, int b_first, int b_rows, float thr, "
         "Tensor(a!) pairs, Tensor(b!) scores, Tensor(c!) count) -> ()");
   m.def("pairs_verify_out(Tensor pairs, Tensor shadow, int n_rows, float thr, Tensor(a!) rows_a, Tensor(b!) rows_b, Tensor(c!) sims, "
@@ -1470,6 +1566,9 @@ TORCH_LIBRARY_IMPL(crs, CUDA, m) {   // the HIP backend of torch-ROCm dispatches
   m.impl("token_project_f8", &token_project_f8);
   m.impl("maxsim_f8", &maxsim_f8);
   m.impl("maxsim_topk_f8", &maxsim_topk_f8);
+  m.impl("token_compress", &token_compress);
+  m.impl("maxsim_rc", &maxsim_rc);
+  m.impl("maxsim_topk_rc", &maxsim_topk_rc);
   m.impl("pairs_above_out", &pairs_above_out);
   m.impl("pairs_verify_out", &pairs_verify_out);
   m.impl("bm25_topk", &bm25_topk);

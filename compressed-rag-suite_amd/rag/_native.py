@@ -95,6 +95,13 @@ _SIGNATURES = {
     "crs_maxsim_topk_f8_plan_describe": (c_int, [c_int, c_int, c_int, c_int, c_int64, ctypes.c_char_p, c_size_t]),
     "crs_maxsim_topk_f8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int,
                                    c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "crs_token_compress": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "crs_maxsim_rc": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64,
+                              c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "crs_maxsim_topk_rc_workspace_bytes": (c_int, [c_int, c_int, c_int64, POINTER(c_size_t)]),
+    "crs_maxsim_topk_rc_plan_describe": (c_int, [c_int, c_int, c_int, c_int, c_int64, ctypes.c_char_p, c_size_t]),
+    "crs_maxsim_topk_rc": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64,
+                                   c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     "crs_pairs_above_f16": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, c_int64, c_float, c_void_p, c_void_p, c_int64,
                                     c_void_p, c_void_p]),
     "crs_pairs_verify_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -580,6 +587,65 @@ def maxsim_topk(q16, q_len, tok16, n_tokens: int, offsets, n_rows: int, k: int, 
     with _translate():
         op = ops().maxsim_topk_f8 if f8 else ops().maxsim_topk
         op(q16, q_len, tok16, int(n_tokens), offsets, int(n_rows), int(row_first), row_count, int(k), workspace, out_s, out_r)
+    return out_s, out_r
+
+
+RC_MIN_CENTROIDS, RC_MAX_CENTROIDS = 16, 1 << 20      # CRS_RC_MIN_CENTROIDS / CRS_RC_MAX_CENTROIDS
+
+
+def token_compress(tok16, dim: int, centroids, cutoffs=None, weights=None, first: int = 0, cid=None, codes=None, scale=None):
+    """fp16 unit token rows [n, dimp] -> the 2-bit residual format (crs_token_compress, csrc/token_compress.hip): token i's nearest
+    centroid id goes to cid[first + i] (int32; a new array when None) and, when `codes` (uint8 [>=, dimp / 4]) and `scale` (fp16)
+    are given, its residual codes and its scale to row first + i of those.  Without them only the assignment runs (the codec's
+    k-means).  Returns cid.  No host sync."""
+    import torch
+    if cid is None:
+        cid = torch.empty(int(first) + tok16.shape[0], dtype=torch.int32, device=tok16.device)
+    with _translate():
+        ops().token_compress(tok16, int(dim), centroids, cutoffs, weights, int(first), cid, codes, scale)
+    return cid
+
+
+def maxsim_rc(q16, q_len, index, rows, out=None):
+    """maxsim over a 2-bit residual index (crs_maxsim_rc, csrc/maxsim_rc.hip): `index` has cid / codes / scale / n_tokens / offsets_dev
+    / n_rows and a codec with centroids / weights; queries are fp16.  The score is the fp16 MaxSim over the decoded tokens."""
+    import torch
+    if out is None:
+        out = torch.empty(rows.shape, dtype=torch.float32, device=rows.device)
+    c = index.codec
+    with _translate():
+        ops().maxsim_rc(q16, q_len, index.cid, index.codes, index.scale, c.centroids, c.weights, int(index.n_tokens), index.offsets_dev,
+                        int(index.n_rows), rows, out)
+    return out
+
+
+def maxsim_topk_rc_workspace_bytes(nq: int, k: int, row_count: int) -> int:
+    b = c_size_t(0)
+    check(load().crs_maxsim_topk_rc_workspace_bytes(int(nq), int(k), int(row_count), ctypes.byref(b)))
+    return int(b.value)
+
+
+def maxsim_topk_rc_plan_describe(nq: int, lq_max: int, dimp: int, k: int, row_count: int) -> str:
+    """The plan line of a sweep of a 2-bit residual index (no device needed)."""
+    buf = ctypes.create_string_buffer(256)
+    check(load().crs_maxsim_topk_rc_plan_describe(int(nq), int(lq_max), int(dimp), int(k), int(row_count), buf, 256))
+    return buf.value.decode()
+
+
+def maxsim_topk_rc(q16, q_len, index, k: int, row_first: int = 0, row_count=None, workspace=None):
+    """maxsim_topk over a 2-bit residual index (crs_maxsim_topk_rc, csrc/maxsim_scan_rc.hip), `index` as maxsim_rc takes it: a
+    returned score is bit for bit maxsim_rc's for that pair.  No host sync."""
+    import torch
+    nq = q16.shape[0]
+    row_count = int(index.n_rows) - int(row_first) if row_count is None else int(row_count)
+    out_s = torch.empty((nq, k), dtype=torch.float32, device=q16.device)
+    out_r = torch.empty((nq, k), dtype=torch.int64, device=q16.device)
+    if workspace is None:
+        workspace = torch.empty(maxsim_topk_rc_workspace_bytes(nq, k, max(row_count, 0)), dtype=torch.uint8, device=q16.device)
+    c = index.codec
+    with _translate():
+        ops().maxsim_topk_rc(q16, q_len, index.cid, index.codes, index.scale, c.centroids, c.weights, int(index.n_tokens), index.offsets_dev,
+                             int(index.n_rows), int(row_first), row_count, int(k), workspace, out_s, out_r)
     return out_s, out_r
 
 

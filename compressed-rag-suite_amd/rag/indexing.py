@@ -127,6 +127,7 @@ import functools
 import json
 import logging
 import os
+import weakref
 from typing import Any, Dict, List, Optional, Sequence
 
 import numpy as np
@@ -489,13 +490,18 @@ class _TokenIndex:
     the first ``n_tokens`` rows in use (row r's tokens are [offsets[r], offsets[r + 1])), grown by doubling; ``offsets`` int64
     [n_rows + 1] on the host, ``offsets_dev`` its device copy.  Extended in place as rows arrive: an append encodes the new rows
     alone.  With an fp8 encoder (``token_dtype: 'fp8'``) ``tok16`` holds uint8 e4m3 rows instead -- dimp bytes a token, half the
-    index -- and crs_maxsim_f8 / crs_maxsim_topk_f8 read it (csrc/maxsim_f8.hip, csrc/maxsim_scan_f8.hip)."""
+    index -- and crs_maxsim_f8 / crs_maxsim_topk_f8 read it (csrc/maxsim_f8.hip, csrc/maxsim_scan_f8.hip).  With ``token_dtype:
+    'res2'`` there is no ``tok16``: ``cid`` / ``codes`` / ``scale`` and ``codec`` hold the 2-bit residual format, dimp / 4 + 6 bytes
+    a token, read by crs_maxsim_rc / crs_maxsim_topk_rc (_extend_res2)."""
 
-    def __init__(self, encoder, device):
+    def __init__(self, encoder, device, codec=None):
         import torch
         self.encoder, self.device, self.dimp = encoder, device, encoder.dimp
         self.dtype = getattr(encoder, "token_torch_dtype", torch.float16)
         self.elem_bytes = 1 if self.dtype == torch.uint8 else 2
+        self.res2 = getattr(encoder, "token_dtype", "fp16") == "res2"
+        self.codec = codec                # res2: the TokenCodec (rag/_token_codec.py); trained by the first extend when None
+        self.cid = self.codes = self.scale = None
         self.tok16 = None
         self.n_tokens = 0
         self.offsets = np.zeros(1, dtype=np.int64)
@@ -521,6 +527,8 @@ class _TokenIndex:
         ids = self.encoder.tokenize_docs(new)
         counts = self.encoder.doc_token_counts(new, ids=ids)
         total = self.n_tokens + int(counts.sum())
+        if self.res2:
+            return self._extend_res2(documents, new, ids, counts, total, max_bytes)
         need = total * self.dimp * self.elem_bytes
         if need > max_bytes:
             raise ValueError(f"the late-interaction token index would take {need} bytes ({total} tokens x {self.dimp} x {self.elem_bytes}) for "
@@ -539,6 +547,43 @@ class _TokenIndex:
                 self.n_tokens = total
             if self.tok16 is None:
                 self.tok16 = torch.zeros((1, self.dimp), dtype=self.dtype, device=self.device)
+            self.offsets_dev = torch.from_numpy(self.offsets).to(self.device)
+
+    def _extend_res2(self, documents, new, ids, counts, total: int, max_bytes: int) -> None:
+        """extend for a 2-bit residual index: three planes -- cid int32, codes uint8 [*, dimp / 4], scale fp16 --
+        grown by doubling together, and the codec, trained by the first build on a seeded sample of the new documents and kept
+        from then on.  max_bytes is compared with tokens x (dimp / 4 + 6) + centroids x dimp x 2 before any encoding."""
+        import torch
+        from . import _token_codec as tc
+        cfg = self.encoder.codec_config
+        if self.codec is None:
+            pick = tc.sample_rows(cfg, len(new))
+            k = tc.resolve_centroids(cfg, total, int(counts[pick].sum()))
+        else:
+            k = self.codec.n_centroids
+        need = tc.index_bytes(total, self.dimp, k)
+        if need > max_bytes:
+            raise ValueError(f"the late-interaction token index would take {need} bytes ({total} tokens x {self.dimp // 4 + 6} + {k} "
+                             f"centroids x {self.dimp} x 2) for {len(documents)} rows, more than max_index_bytes = {int(max_bytes)}")
+        per = self.dimp // 4 + 6
+        with torch.cuda.device(self.device):
+            if self.codec is None and new:
+                sample16, _ = self.encoder.encode_docs_device([new[i] for i in pick], ids=[ids[i] for i in pick])
+                self.codec = tc.train(sample16.contiguous(), self.encoder.dim, k, cfg)
+            held = self.cid.shape[0] if self.cid is not None else 0
+            if (new and total > held) or self.cid is None:
+                cap = max(total, min(2 * held, max(int(max_bytes) - k * self.dimp * 2, 0) // per), 1)
+                grown = (torch.zeros(cap, dtype=torch.int32, device=self.device),
+                         torch.zeros((cap, self.dimp // 4), dtype=torch.uint8, device=self.device),
+                         torch.zeros(cap, dtype=torch.float16, device=self.device))
+                for old, fresh in zip((self.cid, self.codes, self.scale), grown):
+                    if self.n_tokens:
+                        fresh[:self.n_tokens] = old[:self.n_tokens]
+                self.cid, self.codes, self.scale = grown
+            if new:
+                self.encoder.encode_docs_device(new, ids=ids, out=self, first_slot=self.n_tokens)
+                self.offsets = np.concatenate([self.offsets, self.n_tokens + np.cumsum(counts)]).astype(np.int64)
+                self.n_tokens = total
             self.offsets_dev = torch.from_numpy(self.offsets).to(self.device)
 
 
@@ -712,9 +757,15 @@ class SlabCollection:
         rows that arrived since, like _token_csr; dropped by _drop_derived, and when another encoder asks."""
         index = self.__dict__.get("_li")
         if index is None or index.encoder is not encoder:
-            index = self.__dict__["_li"] = _TokenIndex(encoder, self.device)
+            kept = self.__dict__.get("_li_codec")      # a res2 codec outlives a rebuild: it goes only with its encoder, which
+            if kept is not None and kept[0]() is not encoder:      # it names by a weak reference and so does not keep alive
+                del self.__dict__["_li_codec"]
+                kept = None
+            index = self.__dict__["_li"] = _TokenIndex(encoder, self.device, kept[1] if kept else None)
         if index.n_rows < len(self.documents) or index.offsets_dev is None:
             index.extend(self.documents, max_bytes)
+            if index.codec is not None:
+                self.__dict__["_li_codec"] = (weakref.ref(encoder), index.codec)
         return index
 
     def _late_topk(self, index: _TokenIndex, encoder, queries, k: int):
@@ -723,7 +774,13 @@ class SlabCollection:
         import torch
         with torch.cuda.device(index.device):
             q16, q_len = encoder.encode_queries_device(queries)
-            s, r = nat.maxsim_topk(q16, q_len, index.tok16, index.n_tokens, index.offsets_dev, index.n_rows, k)
+            if index.res2 and index.codec is None:      # no document yet, so no codec: nothing to return
+                s = torch.full((len(queries), k), float("-inf"), dtype=torch.float32, device=index.device)
+                r = torch.full((len(queries), k), -1, dtype=torch.int64, device=index.device)
+            elif index.res2:
+                s, r = nat.maxsim_topk_rc(q16, q_len, index, k)
+            else:
+                s, r = nat.maxsim_topk(q16, q_len, index.tok16, index.n_tokens, index.offsets_dev, index.n_rows, k)
             return s.cpu().numpy(), r.cpu().numpy(), q_len.cpu().numpy()
 
     def _sparse_index(self, encoder, max_terms: int, max_bytes: int) -> _SparseIndex:

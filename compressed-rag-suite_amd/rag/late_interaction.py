@@ -13,7 +13,11 @@ Config keys: ``model_name`` / ``model_path``, ``dim`` (checked against the check
 ``mask_punctuation`` (default true), ``query_marker`` / ``doc_marker`` (a token string of the vocabulary, a token id, or ''/None for
 no marker), ``batch_size`` (texts per encoder forward, default 64), ``device``, ``synthetic_seed``, ``token_dtype`` (``'fp16'``,
 the default, or ``'fp8'``: queries and documents are stored as OCP e4m3 codes of the unit vector times 2^8, one byte a coordinate
--- half the token index -- and scored by ``crs_maxsim_f8`` / ``crs_maxsim_topk_f8`` over those stored values).
+-- half the token index -- and scored by ``crs_maxsim_f8`` / ``crs_maxsim_topk_f8`` over those stored values; or
+``'res2'``: the store keeps each document token as the id of its nearest centroid, a 2-bit code per coordinate and an fp16 scale,
+dimp / 4 + 6 bytes a token, queries stay fp16, and ``crs_maxsim_rc`` / ``crs_maxsim_topk_rc`` score the decoded tokens; its codec is
+trained by the store on first use from ``centroids`` (a power of two; default from the token count), ``train_docs``,
+``kmeans_iters`` and ``codec_seed``).
 
 Model resolution, offline by construction, as ``CrossEncoderReranker``: a LOCAL BERT directory whose model.safetensors holds
 ``bert.*`` plus ``linear.weight [dim, H]`` and no bias; else ``$CRS_MODEL_DIR/<basename of model_name>``; else
@@ -119,8 +123,10 @@ class LateInteractionReranker:
         if not 3 <= self.query_maxlen <= MAX_QUERY:
             raise ValueError(f"query_maxlen must be in 3..{MAX_QUERY} (crs_maxsim holds the query in registers), got {self.query_maxlen}")
         self.token_dtype = config.get("token_dtype", "fp16")
-        if self.token_dtype not in ("fp16", "fp8"):
-            raise ValueError(f"token_dtype must be 'fp16' or 'fp8', got {self.token_dtype!r}")
+        if self.token_dtype not in ("fp16", "fp8", "res2"):
+            raise ValueError(f"token_dtype must be 'fp16', 'fp8' or 'res2', got {self.token_dtype!r}")
+        from . import _token_codec
+        self.codec_config = _token_codec.parse_config(config) if self.token_dtype == "res2" else None
         shape, weights, self.tokenizer, _cfg = self._resolve(config)
         self.dim = int(weights[LINEAR].shape[0])
         if config.get("dim") is not None and int(config["dim"]) != self.dim:
@@ -201,7 +207,8 @@ class LateInteractionReranker:
 
     @property
     def token_torch_dtype(self):
-        """The element type of this encoder's token arrays: torch.float16, or torch.uint8 (e4m3 codes) with token_dtype 'fp8'."""
+        """The element type of this encoder's token arrays: torch.float16, or torch.uint8 (e4m3 codes) with token_dtype 'fp8'.
+        ('res2' compresses the store's document tokens only: what the encoder itself returns is fp16.)"""
         import torch
         return torch.uint8 if self.token_dtype == "fp8" else torch.float16
 
@@ -283,7 +290,12 @@ class LateInteractionReranker:
         scattered back through the host-built slot table.  `ids`: the documents' token ids when the caller already has them.
         `out` (cuda fp16 [>= first_slot + T, dimp]): write the T rows there from row first_slot on instead of into a new array
         (the store's token index: no temporary copy of the new rows); the returned tok16 is then that slice of `out`.
-        token_dtype 'fp8': tok16 and `out` are uint8, e4m3 codes."""
+        token_dtype 'fp8': tok16 and `out` are uint8, e4m3 codes.  token_dtype 'res2': without `out` the rows are the uncompressed
+        fp16 vectors (what the codec is trained on); `out` is the store's index itself (its three planes and its codec), every
+        batch is projected into an fp16 scratch of that batch, each document's rows are compressed straight into its slots of
+        the planes by crs_token_compress, and the returned array is the slice of the code plane.  (The store's first build
+        therefore forwards its training sample twice, once uncompressed for the codec and once for the index, and doc_forwards /
+        docs_encoded count both: a store of at most train_docs documents encodes its whole corpus twice.)"""
         import torch
         model = self.model
         ids = self.tokenize_docs(texts) if ids is None else ids
@@ -294,7 +306,11 @@ class LateInteractionReranker:
         np.cumsum(counts, out=first[1:])
         first += int(first_slot)
         total = int(first[-1])
-        if out is None:
+        planes = out if self.token_dtype == "res2" and out is not None else None
+        if planes is not None:
+            if planes.codec is None or planes.codes.shape[0] < total:
+                raise ValueError(f"out must be a res2 token index with a codec and room for {total} tokens")
+        elif out is None:
             out = torch.zeros((total, self.dimp), dtype=self.token_torch_dtype, device=model.device)
         elif out.dtype != self.token_torch_dtype or out.dim() != 2 or out.shape[1] != self.dimp or out.shape[0] < total or not out.is_contiguous():
             raise ValueError(f"out must be a contiguous {self.token_dtype} [>= {total}, {self.dimp}] array")
@@ -303,11 +319,21 @@ class LateInteractionReranker:
         for lo in range(0, n, self.batch_size):
             sel = order[lo: lo + self.batch_size]
             b_ids, lens = pad_batch([ids[i] for i in sel], pad)
-            dst = self.dst_table([keeps[i] for i in sel], b_ids.shape[1], [first[i] for i in sel])
-            self._project(b_ids, lens, dst, out)
+            if planes is None:
+                dst = self.dst_table([keeps[i] for i in sel], b_ids.shape[1], [first[i] for i in sel])
+                self._project(b_ids, lens, dst, out)
+            else:
+                local = np.concatenate([[0], np.cumsum(counts[sel])])
+                scratch = torch.zeros((int(local[-1]), self.dimp), dtype=torch.float16, device=model.device)
+                self._project(b_ids, lens, self.dst_table([keeps[i] for i in sel], b_ids.shape[1], local[:-1]), scratch)
+                c = planes.codec
+                for j, i in enumerate(sel):      # a document's tokens are consecutive in the scratch and in the planes
+                    nat.token_compress(scratch[int(local[j]):int(local[j + 1])], c.dim, c.centroids, c.cutoffs, c.weights,
+                                       first=int(first[i]), cid=planes.cid, codes=planes.codes, scale=planes.scale)
             self.doc_forwards += 1
             self.docs_encoded += len(sel)
-        return out[int(first_slot):total], torch.from_numpy(counts.astype(np.int32)).to(model.device)
+        rows = planes.codes if planes is not None else out
+        return rows[int(first_slot):total], torch.from_numpy(counts.astype(np.int32)).to(model.device)
 
     # ---- scoring ---------------------------------------------------------------------------------------------------------------
     def score_rows(self, queries: Sequence[str], rows, store):
@@ -321,6 +347,10 @@ class LateInteractionReranker:
         dev = index.device
         with torch.cuda.device(dev):
             q16, q_len = self.encode_queries_device(queries)
+            if getattr(index, "res2", False):
+                if index.codec is None:          # no document yet, so no codec: every row is outside [0, 0)
+                    return torch.full(rows.shape, float("-inf"), dtype=torch.float32, device=dev)
+                return nat.maxsim_rc(q16, q_len, index, torch.from_numpy(rows).to(dev))
             return nat.maxsim(q16, q_len, index.tok16, index.n_tokens, index.offsets_dev, index.n_rows, torch.from_numpy(rows).to(dev))
 
     def search_rows(self, queries: Sequence[str], store, k: int):

@@ -539,6 +539,39 @@ int crs_maxsim_topk_f8(const void* q8_dev, const int32_t* q_len_dev, int nq, int
                        int dimp, int k, void* workspace_dev, size_t workspace_bytes,
                        float* out_scores_dev, int64_t* out_rows_dev, void* stream);
 
+/* ---- a 2-bit residual token index for late interaction ('res2', the format ColBERTv2 ships): dimp / 4 + 6 bytes a token
+ * (additive to ABI 3; csrc/maxsim_rc.h, csrc/token_compress.hip, csrc/maxsim_rc.hip, csrc/maxsim_scan_rc.hip) ----
+ * A codec is centroids fp16 [n_centroids, dimp] (unit rows, zeros past dim), cutoffs fp32 [3] and weights fp32 [4], all on the
+ * device.  The index is three planes in token order: cid int32 [n_tokens], codes uint8 [n_tokens, dimp / 4] (coordinate d in bits
+ * 2 (d % 4) of byte d / 4) and scale fp16 [n_tokens].  The decoded coordinate, the only thing a score sees, is the fp16 number
+ *   fp16_mul(fp16_add(centroids[cid][d], fp16(weights[code])), scale)      three individually rounded IEEE operations;
+ * a token whose cid is outside [0, n_centroids) decodes to zeros (the cid is never used as an index).  A score is the fp16
+ * MaxSim of crs_maxsim over those values with fp16 queries: exact products, fp32 accumulation, running fmaxf, crs_maxsim's sums.
+ * crs_token_compress(x fp16 [n_tok, dimp] unit rows): cid = the centroid of the largest dot product (fp32 accumulation), ties to
+ * the lowest id; code = how many cutoffs x[d] - centroid[d] (fp32) is >=; scale = fp16(1 / |centroid + weights[code]|) over the
+ * first dim coordinates in fp32.  With codes_dev and scale_dev both null only cid is written (k-means assignment) and cutoffs_dev /
+ * weights_dev are not read.  tok16_dev and centroids_dev 16-byte aligned; dimp in {32, 64, 96, 128}; 1 <= dim <= dimp;
+ * CRS_RC_MIN_CENTROIDS <= n_centroids <= CRS_RC_MAX_CENTROIDS; 0 <= n_tok <= 2^36.
+ * crs_maxsim_rc / crs_maxsim_topk_rc / _workspace_bytes / _plan_describe are crs_maxsim / crs_maxsim_topk with the token array
+ * replaced by the three planes and the codec (q16_dev, codes_dev, centroids_dev 16-byte aligned); every contract, limit and error
+ * of the fp16 entry points holds word for word, and a score returned by crs_maxsim_topk_rc is bit for bit crs_maxsim_rc's. */
+#define CRS_RC_MIN_CENTROIDS 16
+#define CRS_RC_MAX_CENTROIDS (1 << 20)
+int crs_token_compress(const void* tok16_dev, int64_t n_tok, int dimp, int dim, const void* centroids_dev, int n_centroids,
+                       const float* cutoffs_dev, const float* weights_dev, int32_t* cid_dev, void* codes_dev, void* scale_dev,
+                       void* stream);
+int crs_maxsim_rc(const void* q16_dev, const int32_t* q_len_dev, int nq, int lq_max, const int32_t* cid_dev, const void* codes_dev,
+                  const void* scale_dev, const void* centroids_dev, int n_centroids, const float* weights_dev,
+                  const int64_t* offsets_dev, int64_t n_rows, int64_t n_tokens, const int64_t* rows_dev, int m_max, int dimp,
+                  float* out_dev, void* stream);
+int crs_maxsim_topk_rc_workspace_bytes(int nq, int k, int64_t row_count, size_t* bytes);
+int crs_maxsim_topk_rc_plan_describe(int nq, int lq_max, int dimp, int k, int64_t row_count, char* buf, size_t cap);   /* no device */
+int crs_maxsim_topk_rc(const void* q16_dev, const int32_t* q_len_dev, int nq, int lq_max, const int32_t* cid_dev, const void* codes_dev,
+                       const void* scale_dev, const void* centroids_dev, int n_centroids, const float* weights_dev,
+                       const int64_t* offsets_dev, int64_t n_rows, int64_t n_tokens, int64_t row_first, int64_t row_count,
+                       int dimp, int k, void* workspace_dev, size_t workspace_bytes,
+                       float* out_scores_dev, int64_t* out_rows_dev, void* stream);
+
 /* ---- learned sparse retrieval (SPLADE): compaction of a dense weight row, impact top-k over a weighted token CSR -- no reference
  * call site (additive to ABI 3; csrc/sparse_compact.hip, csrc/sparse_scan.hip; the head that produces the dense rows
  * is crs_mlm_sparse_pool, crs_encoder.h) ----

@@ -15,6 +15,13 @@
 DESIGN 3.23: the same unit vectors times 2^8, rounded by torch's float8_e4m3fn cast), or both ALTERNATELY at every shape in one
 job, each fp8 entry then carrying its time as a ratio to the fp16 sweep's.
 
+--token-dtype res2: the fp16, fp8 and 2-bit residual sweeps (crs_maxsim_topk_rc, csrc/maxsim_scan_rc.hip) ALTERNATELY at
+every shape in one job.  The res2 index is the same unit rows compressed by crs_token_compress against a codec of --centroids
+centroids that rag/_token_codec.py trains on the first 32 x centroids tokens (two k-means iterations: random unit rows have no
+clusters to find, the table's size and the spread of the cids over it are what the sweep's gathers see); queries stay fp16.  Its
+index bytes are those of the planes and the table as built.  A third section, `overlap`, builds one store per format over
+--overlap-rows chunks under ``synthetic:colbert-minilm`` and reports how many of the fp16 top 10 each other format's top 10 holds.
+
 hipEvent spans after a warm-up, median of --reps spans, clocks as found.  A report, not a pass condition."""
 import argparse
 import json
@@ -59,10 +66,35 @@ def kernel(args, result):
     for lo in range(0, n_tokens, 1 << 22):                                   # random unit rows, a slice at a time
         x = torch.randn((min(1 << 22, n_tokens - lo), dimp), device=dev)
         tok[lo:lo + x.shape[0]] = torch.nn.functional.normalize(x, dim=1).half()
-    dtypes = ("fp16", "fp8") if args.token_dtype == "both" else (args.token_dtype,)
+    dtypes = {"both": ("fp16", "fp8"), "res2": ("fp16", "fp8", "res2")}.get(args.token_dtype, (args.token_dtype,))
     f8 = lambda x: (x.float() * 256.0).to(torch.float8_e4m3fn).view(torch.uint8)
     toks = {"fp16": tok, "fp8": f8(tok) if "fp8" in dtypes else None}
     index_bytes = n_tokens * dimp * 2
+    rc_index = rc_bytes = None
+    if "res2" in dtypes:
+        from types import SimpleNamespace
+        from rag import _token_codec as tc
+        kc = args.centroids
+        t0 = time.perf_counter()
+        codec = tc.train(tok[: min(n_tokens, 32 * kc)], dimp, kc, {"codec_seed": 0, "kmeans_iters": 2})
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        rc_index = SimpleNamespace(cid=torch.empty(n_tokens, dtype=torch.int32, device=dev),
+                                   codes=torch.empty((n_tokens, dimp // 4), dtype=torch.uint8, device=dev),
+                                   scale=torch.empty(n_tokens, dtype=torch.float16, device=dev), n_tokens=n_tokens, offsets_dev=offsets,
+                                   n_rows=args.rows, codec=codec)
+        for lo in range(0, n_tokens, 1 << 22):
+            nat.token_compress(tok[lo:lo + (1 << 22)], dimp, codec.centroids, codec.cutoffs, codec.weights, first=lo, cid=rc_index.cid,
+                               codes=rc_index.codes, scale=rc_index.scale)
+        torch.cuda.synchronize()
+        rc_bytes = sum(x.numel() * x.element_size() for x in (rc_index.cid, rc_index.codes, rc_index.scale, codec.centroids))
+        assert rc_bytes == tc.index_bytes(n_tokens, dimp, kc)
+        used = int(torch.unique(rc_index.cid).numel())
+        result["res2_index"] = {"centroids": kc, "bytes": rc_bytes, "bytes_per_token": round(rc_bytes / n_tokens, 2),
+                                "ratio_to_fp16_bytes": round(rc_bytes / index_bytes, 4), "centroids_in_use": used,
+                                "train_s": round(t1 - t0, 2), "compress_s": round(time.perf_counter() - t1, 2),
+                                "cutoffs": [round(float(x), 5) for x in codec.cutoffs], "weights": [round(float(x), 5) for x in codec.weights]}
+        print(json.dumps({"res2_index": result["res2_index"]}), flush=True)
     part = tok[: min(n_tokens, (4 << 30) // (dimp * 2))]
     scratch = torch.empty_like(part)
     scratch.copy_(part)
@@ -79,24 +111,64 @@ def kernel(args, result):
             base = None
             for dt in dtypes:
                 is8 = dt == "fp8"
-                qx, tx, nbytes = (f8(q16), toks["fp8"], index_bytes // 2) if is8 else (q16, tok, index_bytes)
-                ws = torch.empty(nat.maxsim_topk_workspace_bytes(nq, k, args.rows, f8=is8), dtype=torch.uint8, device=dev)
-                fn = lambda: nat.maxsim_topk(qx, q_len, tx, n_tokens, offsets, args.rows, k, workspace=ws)
+                if dt == "res2":
+                    nbytes = rc_bytes
+                    ws = torch.empty(nat.maxsim_topk_rc_workspace_bytes(nq, k, args.rows), dtype=torch.uint8, device=dev)
+                    fn = lambda: nat.maxsim_topk_rc(q16, q_len, rc_index, k, workspace=ws)
+                    plan = nat.maxsim_topk_rc_plan_describe(nq, lq, dimp, k, args.rows)
+                else:
+                    qx, tx, nbytes = (f8(q16), toks["fp8"], index_bytes // 2) if is8 else (q16, tok, index_bytes)
+                    ws = torch.empty(nat.maxsim_topk_workspace_bytes(nq, k, args.rows, f8=is8), dtype=torch.uint8, device=dev)
+                    fn = lambda: nat.maxsim_topk(qx, q_len, tx, n_tokens, offsets, args.rows, k, workspace=ws)
+                    plan = nat.maxsim_topk_plan_describe(nq, lq, dimp, k, args.rows, f8=is8)
                 fn()
                 t = span_ms(fn, args.reps)
                 sec, groups = t["median"] * 1e-3, (nq + 7) // 8
                 flops = 2.0 * nq * lq * n_tokens * dimp
-                entry = {"token_dtype": dt, "nq": nq, "q_len": lq, "ms": t, "plan": nat.maxsim_topk_plan_describe(nq, lq, dimp, k, args.rows, f8=is8),
+                entry = {"token_dtype": dt, "nq": nq, "q_len": lq, "ms": t, "plan": plan,
                          "ms_per_query": round(t["median"] / nq, 4),
                          "gb_per_s_per_query_group": round(nbytes / sec / 1e9, 1),
                          "gb_per_s_all_groups": round(groups * nbytes / sec / 1e9, 1),
                          "copy_read_gb_per_s": round(copy_gbps, 1), "tflop_per_s": round(flops / sec / 1e12, 1),
                          "share_of_peak": round(flops / sec / PEAK_FLOPS, 4), "queries_per_s": round(nq / sec, 1)}
-                if is8 and base:
+                if dt != "fp16" and base:
                     entry["time_ratio_to_fp16"] = round(t["median"] / base, 3)
-                base = t["median"] if not is8 else base
+                base = t["median"] if dt == "fp16" else base
                 result["kernel"].append(entry)
                 print(json.dumps(entry), flush=True)
+
+
+def overlap(args, result):
+    """Top-10 agreement of search_late_batch between token formats on seeded random weights: a report, no retrieval-quality claim."""
+    import numpy as np
+    from rag import RAGPipeline
+    from rag.chunking import Chunk
+
+    class Stub:
+        def generate(self, prompt, **kw):
+            return "n/a"
+    rng = np.random.default_rng(1)
+    texts = [" ".join(str(w) for w in rng.choice(WORDS, int(rng.integers(60, 181)))) + f" chunk{r}" for r in range(args.overlap_rows)]
+    queries = [" ".join(str(w) for w in rng.choice(WORDS, int(rng.integers(4, 13)))) for _ in range(args.queries)]
+    lists = {}
+    for dt in ("fp16", "fp8", "res2"):
+        p = RAGPipeline({"embedding": {"model_name": "synthetic:tiny", "device": "cuda", "batch_size": 256, "normalize": True},
+                         "vector_store": {"collection_name": "late-overlap-" + dt},
+                         "retrieval": {"top_k": 10, "rerank": True,
+                                       "late_interaction": {"model_name": "synthetic:colbert-minilm", "first_stage": "scan", "token_dtype": dt}}})
+        p.setup(Stub())
+        chunks = [Chunk(text=t, chunk_id=f"c_{r}", start_char=0, end_char=1) for r, t in enumerate(texts)]
+        p.vector_store.create_index(chunks, p.embedding_model.embed_chunks_device(chunks))
+        lists[dt] = p.vector_store.search_late_batch(queries, top_k=10)["rows"]
+        if dt == "res2":
+            index = p.vector_store.token_index()
+            result["overlap_res2_index"] = {"tokens": index.n_tokens, "centroids": index.codec.n_centroids}
+    result["overlap"] = {"rows": args.overlap_rows, "queries": args.queries, "top_k": 10}
+    for dt in ("fp8", "res2"):
+        shared = [len(set(a) & set(b)) / 10.0 for a, b in zip(lists["fp16"], lists[dt])]
+        result["overlap"][dt] = {"mean_overlap_at_10": round(float(np.mean(shared)), 3), "least": round(min(shared), 2),
+                                 "same_first_hit": round(float(np.mean([a[0] == b[0] for a, b in zip(lists["fp16"], lists[dt])])), 3)}
+    print(json.dumps({"overlap": result["overlap"]}), flush=True)
 
 
 def retriever(args, result):
@@ -117,7 +189,7 @@ def retriever(args, result):
                          "vector_store": {"collection_name": "late-scan-bench-" + stage},
                          "retrieval": {"top_k": 10, "rerank": True, "similarity_threshold": -1.0, "diversity_penalty": 0.0,
                                        "late_interaction": {"model_name": "synthetic:colbert-minilm", "first_stage": stage,
-                                                            "token_dtype": "fp16" if args.token_dtype == "both" else args.token_dtype}}})
+                                                            "token_dtype": "fp16" if args.token_dtype == "both" else args.token_dtype}}})      # 'res2': the res2 store
         p.setup(Stub())
         chunks = [Chunk(text=t, chunk_id=f"c_{r}", start_char=0, end_char=1) for r, t in enumerate(texts)]
         p.vector_store.create_index(chunks, p.embedding_model.embed_chunks_device(chunks))
@@ -142,7 +214,9 @@ def main():
     ap.add_argument("--queries", type=int, default=64)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--skip-retriever", action="store_true")
-    ap.add_argument("--token-dtype", choices=("fp16", "fp8", "both"), default="fp16")
+    ap.add_argument("--token-dtype", choices=("fp16", "fp8", "both", "res2"), default="fp16")
+    ap.add_argument("--centroids", type=int, default=1 << 17, help="res2: the codec's table (2^17 is the store's default at 1 M chunks)")
+    ap.add_argument("--overlap-rows", type=int, default=4096)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -150,6 +224,8 @@ def main():
     nat.require_gpu()
     result = {"device": torch.cuda.get_device_name(torch.cuda.current_device())}
     kernel(args, result)
+    if args.token_dtype == "res2":
+        overlap(args, result)
     if not args.skip_retriever:
         retriever(args, result)
     if args.out:
