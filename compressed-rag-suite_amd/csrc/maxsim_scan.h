@@ -54,4 +54,30 @@ int maxsim_scan_rc_make_plan(int nq, int lq_max, int dimp, int k, int64_t row_co
 int maxsim_scan_rc_plan_describe(const MaxsimScanPlan& p, char* buf, size_t cap);
 size_t maxsim_scan_rc_workspace_bound(int nq, int k, int64_t row_count);
 
+// ---- the pruned centroid-interaction sweep of a 2-bit residual index (crs_centroid_maxsim_topk, centroid_scan.hip).
+// Nothing is multiplied: the sweep streams the cid plane, tests each token's centroid against a per-query keep bitmap held in LDS
+// and gathers a row of precomputed centroid scores for the kept tokens only.  A workgroup of kCsThreads threads serves qg queries,
+// qg = min(8, kCsBitmapLds / bitmap bytes of a query), and loads their bitmaps once; each of its WAVES walks items of 64 rows
+// (wave v of the grid takes items v, v + waves, ...) for all qg queries, and the workgroup's waves merge their lists in LDS
+// (where the bitmaps were), so the workspace is [g][nq][kp] as for the other sweeps.
+constexpr int kCsThreads = 1024;
+constexpr int kCsWaves = kCsThreads / 64;
+constexpr int kCsBitmapLds = 128 * 1024;   // of the 160 KB of a CU; one workgroup is resident where the bitmaps fill it
+constexpr int kCsCus = 256;
+
+struct CentroidScanPlan {
+  int nq, lq_max, lqp, ch;      // lqp = lq_max rounded up to 8; ch = 16-byte chunks of a score row rounded up to a power of two
+  int n_centroids, words;       // words = ceil(n_centroids / 32): uint32 words of one query's bitmap
+  int k, kp;
+  int qg, qgroups;              // queries of a workgroup; ceil(nq / qg): gridDim.y
+  int64_t items;                // ceil(row_count / 64)
+  int g;                        // workgroups per query group: gridDim.x, the merge's nlists
+  int lds_bytes;                // max(qg bitmaps, qg * kCsWaves lists of 64 keys)
+  size_t part_s, part_r, bytes;
+};
+int centroid_scan_make_plan(int nq, int lq_max, int n_centroids, int k, int64_t row_count, CentroidScanPlan* p, const char** why);
+int centroid_scan_plan_describe(const CentroidScanPlan& p, char* buf, size_t cap);
+// an upper bound of plan.bytes that depends on (nq, k, row_count) alone and grows with each: g nq <= min(items nq, 8 kCsCus + nq)
+size_t centroid_scan_workspace_bound(int nq, int k, int64_t row_count);
+
 }  // namespace crs

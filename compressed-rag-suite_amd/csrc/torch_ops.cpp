@@ -28,6 +28,7 @@
 //   crs::token_project / crs::maxsim   late interaction (ColBERT): per-token projection and MaxSim scoring of candidate lists (new vs the reference)
 //   crs::token_project_f8 / crs::maxsim_f8 / crs::maxsim_topk_f8   the same three over an fp8 (e4m3) token index (new vs the reference)
 //   crs::token_compress / crs::maxsim_rc / crs::maxsim_topk_rc   a 2-bit residual token index: compression, candidate scoring, sweep (new vs the reference)
+//   crs::centroid_scores / crs::centroid_maxsim_topk   pruned centroid interaction over that index: PLAID's candidate stage (new vs the reference)
 //   crs::maxsim_topk       exact late-interaction retrieval: one MaxSim sweep of the whole token index, top-k in the sweep (new vs the reference)
 //   crs::ivf_topk          top-k of the rows of per-query inverted lists of an fp16 slab: grouping + gathered MFMA probe (new vs the reference)
 //   crs::rerank_lexical    replaces the scoring, threshold and _rerank loops of retrieve_batch  (reference rag/retrieval.py:75-77, 196-217)
@@ -841,6 +842,57 @@ void maxsim_topk_rc(const Tensor& q16, const Tensor& q_len, const Tensor& cid, c
      "crs::maxsim_topk_rc");
 }
 
+// ---- pruned centroid interaction over a res2 index (csrc/centroid_scores.hip, csrc/centroid_scan.hip) --------------
+// q16 fp16 [nq, lq_max, dimp], centroids fp16 [K, dimp] -> s16 fp16 [nq, K, lqp] (lqp = lq_max rounded up to 8), keep int32 [nq, ceil(K / 32)]
+void centroid_scores(const Tensor& q16, const Tensor& q_len, const Tensor& centroids, double threshold, Tensor s16, Tensor keep) {
+  want(q16, at::kHalf, "q16");
+  want(q_len, at::kInt, "q_len");
+  want(centroids, at::kHalf, "centroids");
+  want(s16, at::kHalf, "s16");
+  want(keep, at::kInt, "keep");
+  same_device(q16, {&q_len, &centroids, &s16, &keep}, "crs::centroid_scores");
+  TORCH_CHECK(q16.dim() == 3 && centroids.dim() == 2 && centroids.size(1) == q16.size(2), "q16 must be [nq, lq_max, dimp] and centroids [K, dimp]");
+  const int64_t nq = q16.size(0), lq_max = q16.size(1), K = centroids.size(0), lqp = (lq_max + 7) / 8 * 8;
+  TORCH_CHECK(K <= CRS_RC_MAX_CENTROIDS, "too many centroids");
+  TORCH_CHECK(q_len.dim() == 1 && q_len.size(0) == nq, "q_len must be int32 [nq]");
+  TORCH_CHECK(s16.numel() == nq * K * lqp && keep.numel() == nq * ((K + 31) / 32), "s16 must hold [nq, K, lqp] and keep [nq, ceil(K / 32)]");
+  if (nq == 0) return;
+  c10::hip::HIPGuardMasqueradingAsCUDA g(q16.device());
+  ok(crs_centroid_scores(q16.data_ptr(), q_len.data_ptr<int32_t>(), (int)std::min<int64_t>(nq, INT32_MAX), (int)std::min<int64_t>(lq_max, INT32_MAX),
+                         centroids.data_ptr(), (int)K, (int)std::min<int64_t>(q16.size(2), INT32_MAX), (float)threshold, s16.data_ptr(),
+                         reinterpret_cast<uint32_t*>(keep.data_ptr<int32_t>()), cur_stream(q16)), "crs::centroid_scores");
+}
+
+// s16 [nq, K, lqp] / keep [nq, ceil(K / 32)] as centroid_scores wrote them; cid int32 [>= n_tokens]; offsets int64 [>= n_rows + 1]
+void centroid_maxsim_topk(const Tensor& s16, const Tensor& keep, const Tensor& q_len, int64_t lq_max, const Tensor& cid, int64_t n_tokens,
+                          const Tensor& offsets, int64_t n_rows, int64_t row_first, int64_t row_count, int64_t k, Tensor workspace,
+                          Tensor out_scores, Tensor out_rows) {
+  want(s16, at::kHalf, "s16");
+  want(keep, at::kInt, "keep");
+  want(q_len, at::kInt, "q_len");
+  want(cid, at::kInt, "cid");
+  want(offsets, at::kLong, "offsets");
+  want(workspace, at::kByte, "workspace");
+  want(out_scores, at::kFloat, "out_scores");
+  want(out_rows, at::kLong, "out_rows");
+  same_device(s16, {&keep, &q_len, &cid, &offsets, &workspace, &out_scores, &out_rows}, "crs::centroid_maxsim_topk");
+  TORCH_CHECK(lq_max >= 1 && lq_max <= CRS_MAXSIM_MAX_QUERY, "lq_max must be in 1..64");
+  TORCH_CHECK(s16.dim() == 3 && s16.size(2) == (lq_max + 7) / 8 * 8 && s16.size(1) <= CRS_RC_MAX_CENTROIDS, "s16 must be [nq, K, lqp]");
+  const int64_t nq = s16.size(0), K = s16.size(1);
+  TORCH_CHECK(nq <= 65535, "too many queries");
+  TORCH_CHECK(keep.numel() == nq * ((K + 31) / 32) && q_len.dim() == 1 && q_len.size(0) == nq, "keep must hold [nq, ceil(K / 32)] and q_len [nq]");
+  TORCH_CHECK(n_tokens >= 0 && cid.dim() == 1 && cid.size(0) >= n_tokens, "cid must be int32 [>= n_tokens]");
+  TORCH_CHECK(n_rows >= 0 && offsets.dim() == 1 && offsets.numel() >= n_rows + 1, "offsets must be int64 [>= n_rows + 1]");
+  TORCH_CHECK(k >= 1 && k <= CRS_MAX_K, "k must be in 1..64");
+  TORCH_CHECK(out_scores.numel() == nq * k && out_rows.numel() == nq * k, "outputs must hold [nq, k]");
+  if (nq == 0) return;
+  c10::hip::HIPGuardMasqueradingAsCUDA g(s16.device());
+  ok(crs_centroid_maxsim_topk(s16.data_ptr(), reinterpret_cast<const uint32_t*>(keep.data_ptr<int32_t>()), q_len.data_ptr<int32_t>(), (int)nq,
+                              (int)lq_max, (int)K, cid.data_ptr<int32_t>(), offsets.data_ptr<int64_t>(), n_rows, n_tokens, row_first, row_count,
+                              (int)k, workspace.data_ptr(), (size_t)workspace.numel(), out_scores.data_ptr<float>(),
+                              out_rows.data_ptr<int64_t>(), cur_stream(s16)), "crs::centroid_maxsim_topk");
+}
+
 // ---- near-duplicate join (csrc/join.hip) ---------------------------------------------------------------------------
 // slab fp16 [>= n_rows, pdim]; pairs int64 [cap, 2], scores fp32 [cap]; count int64 [1], zeroed by the caller, receives the number
 // of qualifying pairs (count > cap: overflow)
@@ -1493,6 +1545,8 @@ TORCH_LIBRARY(crs, m) {
   m.def("token_compress(Tensor tok16, int dim, Tensor centroids, Tensor? cutoffs, Tensor? weights, int first, Tensor(a!) cid, Tensor(b!)? codes, Tensor(c!)? scale) -> ()");
   m.def("maxsim_rc(Tensor q16, Tensor q_len, Tensor cid, Tensor codes, Tensor scale, Tensor centroids, Tensor weights, int n_tokens, Tensor offsets, int n_rows, Tensor rows, Tensor(a!) out) -> ()");
   m.def("maxsim_topk_rc(Tensor q16, Tensor q_len, Tensor cid, Tensor codes, Tensor scale, Tensor centroids, Tensor weights, int n_tokens, Tensor offsets, int n_rows, int row_first, int row_count, int k, Tensor(a!) workspace, Tensor(b!) out_scores, Tensor(c!) out_rows) -> ()");
+  m.def("centroid_scores(Tensor q16, Tensor q_len, Tensor centroids, float threshold, Tensor(a!) s16, Tensor(b!) keep) -> ()");
+  m.def("centroid_maxsim_topk(Tensor s16, Tensor keep, Tensor q_len, int lq_max, Tensor cid, int n_tokens, Tensor offsets, int n_rows, int row_first, int row_count, int k, Tensor(a!) workspace, Tensor(b!) out_scores, Tensor(c!) out_rows) -> ()");
   m.def("pairs_above_out(Tensor slab, int n_rows, int dim, int a_first, int a_rows, int b_first, int b_rows, float thr, "
         "Tensor(a!) pairs, Tensor(b!) scores, Tensor(c!) count) -> ()");
   m.def("pairs_verify_out(Tensor pairs, Tensor shadow, int n_rows, float thr, Tensor(a!) rows_a, Tensor(b!) rows_b, Tensor(c!) sims, "
@@ -1569,6 +1623,8 @@ TORCH_LIBRARY_IMPL(crs, CUDA, m) {   // the HIP backend of torch-ROCm dispatches
   m.impl("token_compress", &token_compress);
   m.impl("maxsim_rc", &maxsim_rc);
   m.impl("maxsim_topk_rc", &maxsim_topk_rc);
+  m.impl("centroid_scores", &centroid_scores);
+  m.impl("centroid_maxsim_topk", &centroid_maxsim_topk);
   m.impl("pairs_above_out", &pairs_above_out);
   m.impl("pairs_verify_out", &pairs_verify_out);
   m.impl("bm25_topk", &bm25_topk);

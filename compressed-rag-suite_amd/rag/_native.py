@@ -102,6 +102,11 @@ _SIGNATURES = {
     "crs_maxsim_topk_rc_plan_describe": (c_int, [c_int, c_int, c_int, c_int, c_int64, ctypes.c_char_p, c_size_t]),
     "crs_maxsim_topk_rc": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64,
                                    c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "crs_centroid_scores": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    "crs_centroid_maxsim_topk_workspace_bytes": (c_int, [c_int, c_int, c_int64, POINTER(c_size_t)]),
+    "crs_centroid_maxsim_topk_plan_describe": (c_int, [c_int, c_int, c_int, c_int, c_int64, ctypes.c_char_p, c_size_t]),
+    "crs_centroid_maxsim_topk": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int64, c_int64,
+                                         c_int64, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     "crs_pairs_above_f16": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, c_int64, c_float, c_void_p, c_void_p, c_int64,
                                     c_void_p, c_void_p]),
     "crs_pairs_verify_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -646,6 +651,53 @@ def maxsim_topk_rc(q16, q_len, index, k: int, row_first: int = 0, row_count=None
     with _translate():
         ops().maxsim_topk_rc(q16, q_len, index.cid, index.codes, index.scale, c.centroids, c.weights, int(index.n_tokens), index.offsets_dev,
                              int(index.n_rows), int(row_first), row_count, int(k), workspace, out_s, out_r)
+    return out_s, out_r
+
+
+def centroid_scores(q16, q_len, centroids, threshold: float, s16=None, keep=None):
+    """Every query token against every centroid of a res2 codec (crs_centroid_scores, csrc/centroid_scores.hip):
+    q16 cuda fp16 [nq, lq_max <= 64, dimp], centroids fp16 [K, dimp] -> (s16 fp16 [nq, K, lqp], lqp = lq_max rounded up to 8, +0 in
+    the columns past a query's length; keep int32 [nq, ceil(K / 32)], bit c set iff the largest stored score of centroid c is
+    >= threshold).  No host sync."""
+    import torch
+    nq, lq_max, k_c = q16.shape[0], q16.shape[1], centroids.shape[0]
+    if s16 is None:
+        s16 = torch.empty((nq, k_c, (lq_max + 7) // 8 * 8), dtype=torch.float16, device=q16.device)
+    if keep is None:
+        keep = torch.empty((nq, (k_c + 31) // 32), dtype=torch.int32, device=q16.device)
+    with _translate():
+        ops().centroid_scores(q16, q_len, centroids, float(threshold), s16, keep)
+    return s16, keep
+
+
+def centroid_maxsim_topk_workspace_bytes(nq: int, k: int, row_count: int) -> int:
+    b = c_size_t(0)
+    check(load().crs_centroid_maxsim_topk_workspace_bytes(int(nq), int(k), int(row_count), ctypes.byref(b)))
+    return int(b.value)
+
+
+def centroid_maxsim_topk_plan_describe(nq: int, lq_max: int, n_centroids: int, k: int, row_count: int) -> str:
+    """The plan line of a pruned centroid sweep (no device needed); Qg is the number of queries whose bitmaps share LDS."""
+    buf = ctypes.create_string_buffer(256)
+    check(load().crs_centroid_maxsim_topk_plan_describe(int(nq), int(lq_max), int(n_centroids), int(k), int(row_count), buf, 256))
+    return buf.value.decode()
+
+
+def centroid_maxsim_topk(s16, keep, q_len, lq_max: int, index, k: int, row_first: int = 0, row_count=None, workspace=None):
+    """The pruned centroid-interaction sweep of a res2 index's cid plane (crs_centroid_maxsim_topk, csrc/centroid_scan.hip): s16 /
+    keep as centroid_scores returns them, `index` as maxsim_rc takes it (cid / n_tokens / offsets_dev / n_rows are read).  Returns
+    the k <= 64 best (approximate score fp32 [nq, k], row int64 [nq, k]) per query, (-inf, -1) in missing slots: candidates to be
+    scored exactly by maxsim_rc.  No host sync."""
+    import torch
+    nq = s16.shape[0]
+    row_count = int(index.n_rows) - int(row_first) if row_count is None else int(row_count)
+    out_s = torch.empty((nq, k), dtype=torch.float32, device=s16.device)
+    out_r = torch.empty((nq, k), dtype=torch.int64, device=s16.device)
+    if workspace is None:
+        workspace = torch.empty(centroid_maxsim_topk_workspace_bytes(nq, k, max(row_count, 0)), dtype=torch.uint8, device=s16.device)
+    with _translate():
+        ops().centroid_maxsim_topk(s16, keep, q_len, int(lq_max), index.cid, int(index.n_tokens), index.offsets_dev, int(index.n_rows),
+                                   int(row_first), row_count, int(k), workspace, out_s, out_r)
     return out_s, out_r
 
 

@@ -783,6 +783,41 @@ class SlabCollection:
                 s, r = nat.maxsim_topk(q16, q_len, index.tok16, index.n_tokens, index.offsets_dev, index.n_rows, k)
             return s.cpu().numpy(), r.cpu().numpy(), q_len.cpu().numpy()
 
+    # The centroid scores of a query batch (fp16 [nq, K, lqp]) are transient workspace of _late_centroid_topk: the batch is cut so
+    # that they stay under this many bytes.  256 MiB holds 32 queries of 32 tokens at the 2^17 centroids of a 1 M-chunk index -- four
+    # full query groups of the sweep -- and is under 0.1 % of the card's memory, so it never competes with the index it serves.
+    _CENTROID_SCORE_BYTES = 256 << 20
+
+    def _late_centroid_topk(self, index: _TokenIndex, encoder, queries, k: int, candidates: int, threshold: float):
+        """_late_topk through the pruned centroid-interaction first stage: crs_centroid_scores, the
+        crs_centroid_maxsim_topk sweep of the cid plane for `candidates` rows per query, crs_maxsim_rc on those rows, and the order
+        (score descending, row ascending) cut to k.  Which rows are candidates is approximate; every returned score is exact."""
+        import torch
+        if not index.res2:
+            raise ValueError("the centroid first stage needs a 2-bit residual token index: token_dtype must be 'res2', got "
+                             f"{getattr(encoder, 'token_dtype', 'fp16')!r}")
+        nq = len(queries)
+        with torch.cuda.device(index.device):
+            q16, q_len = encoder.encode_queries_device(queries)
+            if index.codec is None:      # no document yet, so no codec: nothing to return
+                return (np.full((nq, k), -np.inf, np.float32), np.full((nq, k), -1, np.int64), q_len.cpu().numpy())
+            cent = index.codec.centroids
+            lq_max = q16.shape[1]
+            per_query = cent.shape[0] * ((lq_max + 7) // 8 * 8) * 2
+            step = max(1, self._CENTROID_SCORE_BYTES // per_query)
+            s = torch.empty((nq, candidates), dtype=torch.float32, device=index.device)
+            r = torch.empty((nq, candidates), dtype=torch.int64, device=index.device)
+            for lo in range(0, nq, step):
+                hi = min(nq, lo + step)
+                s16, keep = nat.centroid_scores(q16[lo:hi], q_len[lo:hi], cent, threshold)
+                _, r[lo:hi] = nat.centroid_maxsim_topk(s16, keep, q_len[lo:hi], lq_max, index, candidates)
+                del s16, keep
+            nat.maxsim_rc(q16, q_len, index, r, out=s)      # a missing slot (row -1) scores -inf
+            s, r, q_len = s.cpu().numpy(), r.cpu().numpy(), q_len.cpu().numpy()
+        r_key = np.where(r < 0, np.iinfo(np.int64).max, r)
+        order = np.lexsort((r_key, -s.astype(np.float64)), axis=1)[:, :k]
+        return np.take_along_axis(s, order, 1), np.take_along_axis(r, order, 1), q_len
+
     def _sparse_index(self, encoder, max_terms: int, max_bytes: int) -> _SparseIndex:
         """The learned-sparse vectors of every row (see _SparseIndex), for `encoder`: built on first use, extended by the rows that
         arrived since, like _token_index; dropped by _drop_derived, and when another encoder or term cap asks."""
@@ -1944,27 +1979,45 @@ class VectorStore:
         """search_lexical_batch for the learned-sparse list (sparse_rows): the same dict, 'scores' the sparse dot products."""
         return self._rows_dict(*self.sparse_rows(queries, top_k))
 
-    def late_rows(self, queries: Sequence[str], top_k: int):
+    def late_rows(self, queries: Sequence[str], top_k: int, candidates: Optional[int] = None, threshold: Optional[float] = None):
         """Exact late-interaction top-k of every query over the WHOLE collection, on the device (crs_maxsim_topk,
         csrc/maxsim_scan.hip): queries [nq] strings -> (MaxSim scores fp32 [nq, top_k], sidecar rows int64 [nq, top_k], query
         token counts int32 [nq]) as numpy, best first, ties by lower row, (-inf, -1) past the rows that hold a token.  The token
         index is built or extended exactly as token_index() does (the same call, so what it refuses is refused here), the queries
         are encoded by the attached LateInteractionReranker, and ONE launch sweeps every row; a score is bit for bit what
-        score_rows gives for that pair.  top_k above MAX_K is not implemented."""
+        score_rows gives for that pair.  top_k above MAX_K is not implemented.
+        `candidates` = n', top_k <= n' <= MAX_K (a res2 index only): the pruned centroid-interaction first stage instead of the
+        exact sweep -- the n' best rows by centroid scores, with centroids scoring below `threshold` (default 0.5)
+        for every query token dropped, are scored exactly and cut to top_k.  The scores are still score_rows' bit for bit; which
+        rows are found is approximate."""
         if not isinstance(top_k, (int, np.integer)) or isinstance(top_k, bool) or top_k < 1:
             raise ValueError(f"top_k must be a positive integer for a late-interaction search, got {top_k!r}")
         if top_k > nat.MAX_K:
             raise NotImplementedError(f"top_k > {nat.MAX_K} is not implemented for the late-interaction sweep, got top_k = {top_k}")
+        if candidates is None and threshold is not None:
+            raise ValueError("threshold belongs to the centroid first stage: set candidates too")
+        if candidates is not None:
+            if not isinstance(candidates, (int, np.integer)) or isinstance(candidates, bool) or not top_k <= candidates <= nat.MAX_K:
+                raise ValueError(f"candidates must be an integer in top_k..{nat.MAX_K}, got {candidates!r}")
+            threshold = 0.5 if threshold is None else float(threshold)
+            if threshold != threshold:
+                raise ValueError("threshold must not be NaN")
         index = self.token_index()
+        if candidates is not None and not index.res2:
+            raise ValueError("the centroid first stage needs a 2-bit residual token index: token_dtype must be 'res2', got "
+                             f"{getattr(self._token_encoder, 'token_dtype', 'fp16')!r}")
         queries = list(queries)
         if not queries:
             return np.zeros((0, top_k), np.float32), np.zeros((0, top_k), np.int64), np.zeros(0, np.int32)
+        if candidates is not None:
+            return self.collection._late_centroid_topk(index, self._token_encoder, queries, int(top_k), int(candidates), threshold)
         return self.collection._late_topk(index, self._token_encoder, queries, int(top_k))
 
-    def search_late_batch(self, queries: Sequence[str], top_k: int = 5) -> Dict[str, Any]:
+    def search_late_batch(self, queries: Sequence[str], top_k: int = 5, candidates: Optional[int] = None,
+                          threshold: Optional[float] = None) -> Dict[str, Any]:
         """search_lexical_batch for the late-interaction list (late_rows): the same dict, 'scores' the MaxSim sums, plus 'rows'
-        (the hits' sidecar rows)."""
-        sc, rh, _ = self.late_rows(queries, top_k)
+        (the hits' sidecar rows).  `candidates` / `threshold` as late_rows takes them."""
+        sc, rh, _ = self.late_rows(queries, top_k, candidates, threshold)
         out = self._rows_dict(sc, rh)
         out['rows'] = [[r for r in rh[a].tolist() if r >= 0] for a in range(len(rh))]
         return out

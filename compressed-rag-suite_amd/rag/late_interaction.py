@@ -353,11 +353,14 @@ class LateInteractionReranker:
                 return nat.maxsim_rc(q16, q_len, index, torch.from_numpy(rows).to(dev))
             return nat.maxsim(q16, q_len, index.tok16, index.n_tokens, index.offsets_dev, index.n_rows, torch.from_numpy(rows).to(dev))
 
-    def search_rows(self, queries: Sequence[str], store, k: int):
+    def search_rows(self, queries: Sequence[str], store, k: int, candidates=None, threshold=None):
         """(scores fp32 [nq, k], sidecar rows int64 [nq, k], query token counts int32 [nq]) as numpy: the k best rows of the WHOLE
         store per query by MaxSim, in ONE crs_maxsim_topk sweep of its token index (VectorStore.late_rows) -- the queries encoded
         as score_rows encodes them, each score bit for bit what score_rows gives for that pair; (-inf, -1) past the rows that hold
-        a token."""
+        a token.  With `candidates` (and `threshold`) the rows come from the pruned centroid-interaction first stage instead
+        (VectorStore.late_rows): the scores are still exact, the choice of rows is approximate."""
         if store._token_encoder is not self:
             store.attach_token_encoder(self)
-        return store.late_rows(queries, k)
+        if candidates is None:
+            return store.late_rows(queries, k)
+        return store.late_rows(queries, k, candidates=candidates, threshold=threshold)

@@ -108,8 +108,24 @@ class ContextRetriever:
         # distance = 1 - score).  Only with rerank on, no filters, no hybrid and 2 * top_k <= 64: any other call takes 'dense'
         li_cfg = config.get('late_interaction')
         self.late_first_stage = li_cfg.get('first_stage', 'dense') if isinstance(li_cfg, dict) else 'dense'
-        if self.late_first_stage not in ('dense', 'scan'):
-            raise ValueError(f"late_interaction: first_stage must be 'dense' or 'scan', got {self.late_first_stage!r}")
+        if self.late_first_stage not in ('dense', 'scan', 'centroid'):
+            raise ValueError(f"late_interaction: first_stage must be 'dense', 'scan' or 'centroid', got {self.late_first_stage!r}")
+        # additive: 'centroid' (a 'res2' token index only): PLAID's pruned centroid interaction in place of the exact
+        # sweep -- VectorStore.late_rows(candidates=, threshold=).  centroid_candidates rows per query (2 * top_k .. 64, default 64)
+        # are found by centroid scores alone, centroids below centroid_threshold (default 0.5, PLAID's setting for k = 10) for
+        # every query token dropped, then scored exactly: rerank_score / score are what 'scan' gives for the same chunk, the choice
+        # of chunks is approximate.  Same conditions and same chunk dicts as 'scan'
+        self.centroid_threshold, self.centroid_candidates = 0.5, 64
+        if self.late_first_stage == 'centroid':
+            if li_cfg.get('token_dtype', 'fp16') != 'res2':
+                raise ValueError("late_interaction: first_stage 'centroid' needs token_dtype 'res2', got "
+                                 f"{li_cfg.get('token_dtype', 'fp16')!r}")
+            t, c = li_cfg.get('centroid_threshold', 0.5), li_cfg.get('centroid_candidates', 64)
+            if isinstance(t, bool) or not isinstance(t, (int, float)) or t != t:
+                raise ValueError(f"late_interaction: centroid_threshold must be a number, got {t!r}")
+            if isinstance(c, bool) or not isinstance(c, int) or not 1 <= c <= 64:
+                raise ValueError(f"late_interaction: centroid_candidates must be an integer in 2 * top_k..64, got {c!r}")
+            self.centroid_threshold, self.centroid_candidates = float(t), c
         # additive: hybrid retrieval.  False (default) | True | {'rrf_k': 60, 'weights': [1, 1], 'k1': 1.5, 'b': 0.75}: retrieve_batch
         # fuses each thresholded dense list with the BM25 list of the same query over the whole collection (same `fetch`) by
         # weighted reciprocal rank fusion: fused = w_dense / (rrf_k + i + 1) + w_lex / (rrf_k + j + 1) over the 0-based ranks; 'score'
@@ -370,7 +386,7 @@ class ContextRetriever:
         on_device = (self.lexical_rerank == 'device' and bool(self.rerank) and self.distance_metric == 'cosine' and fetch <= 64
                      and ids_l is not None and hasattr(store, 'rerank_lexical') and cross is None and late is None and hybrid is None)
         host_pieces = 0
-        scan = late is not None and self.late_first_stage == 'scan' and hybrid is None and fetch <= 64 and hasattr(store, 'late_rows')
+        scan = late is not None and self.late_first_stage in ('scan', 'centroid') and hybrid is None and fetch <= 64 and hasattr(store, 'late_rows')
         if scan:
             per_query = self._late_scan_lists(queries, fetch, k, row_of)
         for piece in (() if scan else self._search_many(queries, fetch)):      # one device batch at a time: its dicts are built while the next ones run
@@ -669,9 +685,17 @@ class ContextRetriever:
     def _late_scan_lists(self, queries: List[str], fetch: int, top_k: int, row_of: Dict[int, int]) -> List[List[Dict]]:
         """first_stage 'scan': the chunk lists of several queries straight from ONE sweep of the token index
         (LateInteractionReranker.search_rows): the `fetch` best rows by MaxSim, best first; rerank_score = the MaxSim sum,
-        score = rerank_score / query tokens, distance = 1 - score; thresholded on score and cut to top_k."""
+        score = rerank_score / query tokens, distance = 1 - score; thresholded on score and cut to top_k.  first_stage 'centroid':
+        the same lists from the pruned centroid-interaction first stage (exact scores of approximately chosen rows)."""
         col = self.vector_store.collection
-        sc, rows, q_len = self.late_interaction.search_rows(queries, self.vector_store, fetch)
+        if self.late_first_stage == 'centroid':
+            if self.centroid_candidates < fetch:
+                raise ValueError(f"late_interaction: centroid_candidates must be an integer in 2 * top_k..64, got "
+                                 f"{self.centroid_candidates} with 2 * top_k = {fetch}")
+            sc, rows, q_len = self.late_interaction.search_rows(queries, self.vector_store, fetch, candidates=self.centroid_candidates,
+                                                                threshold=self.centroid_threshold)
+        else:
+            sc, rows, q_len = self.late_interaction.search_rows(queries, self.vector_store, fetch)
         out = []
         for a in range(len(queries)):
             n_tok = max(int(q_len[a]), 1)

@@ -572,6 +572,38 @@ int crs_maxsim_topk_rc(const void* q16_dev, const int32_t* q_len_dev, int nq, in
                        int dimp, int k, void* workspace_dev, size_t workspace_bytes,
                        float* out_scores_dev, int64_t* out_rows_dev, void* stream);
 
+/* ---- pruned centroid interaction over a 2-bit residual index: PLAID's candidate stage (additive to ABI 3;
+ * csrc/centroid_scores.hip, csrc/centroid_scan.hip) ----
+ * crs_centroid_scores scores every query token against every centroid of a codec, once per query:
+ *   s16_dev  fp16 [nq][n_centroids][lqp], lqp = lq_max rounded up to a multiple of 8 (a centroid's scores for one query are one
+ *            16-byte-aligned row): S[q][c][i] = <Q_qi, C_c> on v_mfma_f32_16x16x32_f16 -- exact products, fp32 accumulation from a
+ *            zero accumulator, k-steps ascending -- rounded to fp16 once, to nearest even; columns i >= q_len[q] are +0.
+ *   keep_dev uint32 [nq][ceil(n_centroids / 32)]: bit c % 32 of word c / 32 is set iff q_len[q] > 0 and
+ *            max_{i < q_len[q]} float(S[q][c][i]) >= threshold, taken from the STORED fp16 values; bits past n_centroids are 0.
+ * q16_dev [nq, lq_max, dimp] / q_len_dev as crs_maxsim takes them; centroids_dev fp16 [n_centroids, dimp].  Limits (CRS_EINVAL
+ * otherwise, before any launch): 1 <= lq_max <= CRS_MAXSIM_MAX_QUERY; dimp in {32, 64, 96, 128}; 0 <= nq <= 65535 (0: no launch);
+ * CRS_RC_MIN_CENTROIDS <= n_centroids <= CRS_RC_MAX_CENTROIDS; threshold not NaN (-inf keeps every centroid of a non-empty query);
+ * q16_dev, centroids_dev, s16_dev 16-byte aligned.
+ * crs_centroid_maxsim_topk sweeps the cid plane of rows [row_first, row_first + row_count) and, for every row that holds a token,
+ *   A[q][r] = sum_{i < q_len[q]} float(max(+0, max_{j in row r, 0 <= cid_j < n_centroids, keep[q] bit cid_j} S[q][cid_j][i]))
+ * The maximum is an fp16 maximum (exact in any order).  The sum is fp32 in ONE order: within each chunk of 8 query tokens
+ * [8 c, 8 c + 8) ascending i from +0, then the chunk sums ascending c from +0.  A query token that no kept document token answers
+ * adds 0; a cid outside the table is skipped and never used as an index.  Per query the k best (A, row) are returned, A descending,
+ * ties to the lower row, missing slots (-inf, -1); rows without tokens are never returned; a query with q_len 0 gets all-missing
+ * slots.  A is a bit-reproducible function of (s16, keep, q_len, cid, offsets).  It is a candidate score only: the caller scores
+ * the returned rows exactly with crs_maxsim_rc.  Offsets are clamped as crs_maxsim_topk clamps them and every limit and error of
+ * that function holds (s16_dev and workspace_dev 16-byte aligned).  Workspace: crs_centroid_maxsim_topk_workspace_bytes(nq, k,
+ * row_count), grows with each argument.  crs_centroid_maxsim_topk_plan_describe writes the plan line (no device): a workgroup
+ * keeps the keep bitmaps of Qg = min(8, 128 KB / bitmap bytes of a query) queries in LDS. */
+int crs_centroid_scores(const void* q16_dev, const int32_t* q_len_dev, int nq, int lq_max, const void* centroids_dev, int n_centroids,
+                        int dimp, float threshold, void* s16_dev, uint32_t* keep_dev, void* stream);
+int crs_centroid_maxsim_topk_workspace_bytes(int nq, int k, int64_t row_count, size_t* bytes);
+int crs_centroid_maxsim_topk_plan_describe(int nq, int lq_max, int n_centroids, int k, int64_t row_count, char* buf, size_t cap);   /* no device */
+int crs_centroid_maxsim_topk(const void* s16_dev, const uint32_t* keep_dev, const int32_t* q_len_dev, int nq, int lq_max,
+                             int n_centroids, const int32_t* cid_dev, const int64_t* offsets_dev, int64_t n_rows, int64_t n_tokens,
+                             int64_t row_first, int64_t row_count, int k, void* workspace_dev, size_t workspace_bytes,
+                             float* out_scores_dev, int64_t* out_rows_dev, void* stream);
+
 /* ---- learned sparse retrieval (SPLADE): compaction of a dense weight row, impact top-k over a weighted token CSR -- no reference
  * call site (additive to ABI 3; csrc/sparse_compact.hip, csrc/sparse_scan.hip; the head that produces the dense rows
  * is crs_mlm_sparse_pool, crs_encoder.h) ----

@@ -22,6 +22,13 @@ clusters to find, the table's size and the spread of the cids over it are what t
 index bytes are those of the planes and the table as built.  A third section, `overlap`, builds one store per format over
 --overlap-rows chunks under ``synthetic:colbert-minilm`` and reports how many of the fp16 top 10 each other format's top 10 holds.
 
+--first-stage centroid (with --token-dtype res2): a fourth section, `centroid`, on the SAME res2 index and in the same job as the res2
+sweep: crs_centroid_scores, the crs_centroid_maxsim_topk sweep for 64 candidates and the exact crs_maxsim_rc re-score of those, each
+in ms per query beside the exact res2 sweep's, at centroid thresholds 0.5, 0.25 and 0.15; the share of index tokens whose centroid a
+query keeps; the cid-plane bytes the sweep reads per second per query group against tensor.copy_ of that plane; and how many of the
+exact sweep's top 10 the final top 10 holds.  The queries are document tokens of the index (random unit queries keep nothing at any
+of these thresholds).  The `overlap` section then also compares first_stage 'centroid' with 'scan' on the synthetic model.
+
 hipEvent spans after a warm-up, median of --reps spans, clocks as found.  A report, not a pass condition."""
 import argparse
 import json
@@ -136,6 +143,63 @@ def kernel(args, result):
                 base = t["median"] if dt == "fp16" else base
                 result["kernel"].append(entry)
                 print(json.dumps(entry), flush=True)
+    return tok, rc_index
+
+
+def centroid(args, result, tok, index):
+    """The pruned centroid-interaction first stage against the exact res2 sweep, on one index in one job."""
+    import torch
+    from rag import _native as nat
+    dev, dimp, k, cand, lq = tok.device, tok.shape[1], 10, 64, 32
+    cent = index.codec.centroids
+    scratch = torch.empty_like(index.cid)
+    scratch.copy_(index.cid)
+    t = span_ms(lambda: scratch.copy_(index.cid), args.reps)
+    del scratch
+    cid_bytes = index.cid.numel() * 4
+    copy_gbps = cid_bytes / (t["median"] * 1e-3) / 1e9
+    result["centroid"] = {"cid_plane_bytes": cid_bytes, "cid_copy_read_gb_per_s": round(copy_gbps, 1), "candidates": cand, "runs": []}
+    gen = torch.Generator(device=dev).manual_seed(5)
+    for nq in (8, 64):
+        pick = torch.randint(0, index.n_tokens, (nq * lq,), device=dev, generator=gen)
+        q16 = tok[pick].reshape(nq, lq, dimp).contiguous()
+        q_len = torch.full((nq,), lq, dtype=torch.int32, device=dev)
+        ws = torch.empty(nat.maxsim_topk_rc_workspace_bytes(nq, k, args.rows), dtype=torch.uint8, device=dev)
+        exact = lambda: nat.maxsim_topk_rc(q16, q_len, index, k, workspace=ws)
+        exact_rows = exact()[1]
+        t_exact = span_ms(exact, args.reps)
+        s16 = torch.empty((nq, cent.shape[0], lq), dtype=torch.float16, device=dev)
+        keep = torch.empty((nq, (cent.shape[0] + 31) // 32), dtype=torch.int32, device=dev)
+        ws2 = torch.empty(nat.centroid_maxsim_topk_workspace_bytes(nq, cand, args.rows), dtype=torch.uint8, device=dev)
+        for thr in (0.5, 0.25, 0.15):
+            f1 = lambda: nat.centroid_scores(q16, q_len, cent, thr, s16=s16, keep=keep)
+            f2 = lambda: nat.centroid_maxsim_topk(s16, keep, q_len, lq, index, cand, workspace=ws2)
+            f1()
+            rows = f2()[1]
+            out = torch.empty((nq, cand), dtype=torch.float32, device=dev)
+            f3 = lambda: nat.maxsim_rc(q16, q_len, index, rows, out=out)
+            f3()
+            t1, t2, t3 = span_ms(f1, args.reps), span_ms(f2, args.reps), span_ms(f3, args.reps)
+            order = torch.argsort(out, dim=1, descending=True, stable=True)[:, :k]
+            final = torch.gather(rows, 1, order).cpu().tolist()
+            shared = [len(set(a) & set(b)) / float(k) for a, b in zip(final, exact_rows.cpu().tolist())]
+            bits = (keep[:8, :, None] >> torch.arange(32, device=dev, dtype=torch.int32)) & 1       # the first 8 queries: [8, words, 32]
+            kept = [float(bits[a].reshape(-1)[index.cid.long()].float().mean()) for a in range(min(nq, 8))]
+            groups, sec2 = (nq + 7) // 8, t2["median"] * 1e-3
+            total = t1["median"] + t2["median"] + t3["median"]
+            entry = {"nq": nq, "q_len": lq, "threshold": thr, "plan": nat.centroid_maxsim_topk_plan_describe(nq, lq, cent.shape[0], cand, args.rows),
+                     "ms": {"centroid_scores": t1, "sweep": t2, "rescore": t3, "exact_res2_sweep": t_exact},
+                     "ms_per_query": {"centroid_scores": round(t1["median"] / nq, 4), "sweep": round(t2["median"] / nq, 4),
+                                      "rescore": round(t3["median"] / nq, 4), "total": round(total / nq, 4),
+                                      "exact_res2_sweep": round(t_exact["median"] / nq, 4)},
+                     "time_ratio_to_exact_res2_sweep": round(total / t_exact["median"], 3),
+                     "share_of_tokens_kept": round(sum(kept) / len(kept), 5),
+                     "share_of_centroids_kept": round(float(bits.float().mean()), 5),
+                     "cid_gb_per_s_per_query_group": round(cid_bytes / sec2 / 1e9, 1),
+                     "cid_gb_per_s_all_groups": round(groups * cid_bytes / sec2 / 1e9, 1),
+                     "mean_overlap_at_10_with_exact": round(sum(shared) / len(shared), 3), "least_overlap": min(shared)}
+            result["centroid"]["runs"].append(entry)
+            print(json.dumps(entry), flush=True)
 
 
 def overlap(args, result):
@@ -163,11 +227,17 @@ def overlap(args, result):
         if dt == "res2":
             index = p.vector_store.token_index()
             result["overlap_res2_index"] = {"tokens": index.n_tokens, "centroids": index.codec.n_centroids}
+            if args.first_stage == "centroid":      # the same store through the pruned first stage, at the retriever's defaults
+                lists["centroid"] = p.vector_store.search_late_batch(queries, top_k=10, candidates=64, threshold=0.5)["rows"]
     result["overlap"] = {"rows": args.overlap_rows, "queries": args.queries, "top_k": 10}
     for dt in ("fp8", "res2"):
         shared = [len(set(a) & set(b)) / 10.0 for a, b in zip(lists["fp16"], lists[dt])]
         result["overlap"][dt] = {"mean_overlap_at_10": round(float(np.mean(shared)), 3), "least": round(min(shared), 2),
                                  "same_first_hit": round(float(np.mean([a[0] == b[0] for a, b in zip(lists["fp16"], lists[dt])])), 3)}
+    if "centroid" in lists:
+        shared = [len(set(a) & set(b)) / 10.0 for a, b in zip(lists["res2"], lists["centroid"])]
+        result["overlap"]["centroid_vs_res2_scan"] = {"mean_overlap_at_10": round(float(np.mean(shared)), 3), "least": round(min(shared), 2),
+                                                      "candidates": 64, "threshold": 0.5}
     print(json.dumps({"overlap": result["overlap"]}), flush=True)
 
 
@@ -216,6 +286,7 @@ def main():
     ap.add_argument("--skip-retriever", action="store_true")
     ap.add_argument("--token-dtype", choices=("fp16", "fp8", "both", "res2"), default="fp16")
     ap.add_argument("--centroids", type=int, default=1 << 17, help="res2: the codec's table (2^17 is the store's default at 1 M chunks)")
+    ap.add_argument("--first-stage", choices=("scan", "centroid"), default="scan", help="centroid (with --token-dtype res2): also measure the pruned first stage")
     ap.add_argument("--overlap-rows", type=int, default=4096)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -223,7 +294,12 @@ def main():
     from rag import _native as nat
     nat.require_gpu()
     result = {"device": torch.cuda.get_device_name(torch.cuda.current_device())}
-    kernel(args, result)
+    if args.first_stage == "centroid" and args.token_dtype != "res2":
+        ap.error("--first-stage centroid needs --token-dtype res2")
+    tok, rc_index = kernel(args, result)
+    if args.first_stage == "centroid":
+        centroid(args, result, tok, rc_index)
+    del tok, rc_index
     if args.token_dtype == "res2":
         overlap(args, result)
     if not args.skip_retriever:
